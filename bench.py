@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- race-simulations/sec of the HIP hot path on 1..N MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -54,6 +54,27 @@ VALU_PEAK_TINST = 1024 * 2.4e9 / 2 / 1e12   # 256 CUs x 4 SIMD-32, one wave64 VA
 VALU_PEAK_TINST_4CYCLE = 1024 * 2.4e9 / 4 / 1e12
 COUNTERS_FILE = 'r5_counters.json'
 MIX_FILE = 'r5_valu_mix.json'
+DUMP_ORDER_ROWS = 1 << 16               # --dump-outputs: finishing orders of this many simulations (fixed, seeded sample)
+DUMP_SAMPLE_SEED = 20240302
+
+
+def dump_outputs(out_dir, hist, orders=None, first_sim=0):
+    """--dump-outputs: what the timed path handed back in its last step, as DIR/<name>.npy (float64 / float32).
+      hist.npy        [n, n] float64  driver x finishing-position counts of the step (all ranks: the reduced histogram)
+      orders.npy      [k, n] float32  driver index per position, k = min(DUMP_ORDER_ROWS, simulations) rows of
+                                      rank 0's orders, chosen by a fixed seed (only when the step wrote orders)
+      orders_sim.npy  [k]    float64  global simulation id of each of those rows
+    Returns the names written; k x n x 4 + k x 8 bytes stays far below 64 MB for every field size (n <= 32)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'hist.npy'), np.asarray(hist, np.float64))
+    names = ['hist']
+    if orders is not None:
+        rows = orders.shape[0]
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, min(rows, DUMP_ORDER_ROWS), replace=False))
+        np.save(os.path.join(out_dir, 'orders.npy'), np.asarray(orders[pick], np.float32))
+        np.save(os.path.join(out_dir, 'orders_sim.npy'), (first_sim + pick).astype(np.float64))
+        names += ['orders', 'orders_sim']
+    return names
 
 
 def load_workload(name):
@@ -240,7 +261,11 @@ def main():
     ap.add_argument('--orders', action='store_true', help='the timed steps also write the per-simulation finishing orders')
     ap.add_argument('--deviates', type=int, default=32, choices=(32, 53),
                     help='53: the timed steps run at the reference\'s deviate width (race_kernel_reg_wide; tools/profile.sh)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     # started as `python bench.py --gpus N` with no launcher around it: become the launcher's parent (before anything here
     # imports torch or touches the GPU)
@@ -288,8 +313,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def run_workload(name, steps, warmup, with_orders=False, deviates=32):
-        """`warmup` untimed steps, then exactly `steps` timed steps between barrier + synchronize pairs."""
+    def run_workload(name, steps, warmup, with_orders=False, deviates=32, dump_dir=None):
+        """`warmup` untimed steps, then exactly `steps` timed steps between barrier + synchronize pairs; with `dump_dir`,
+        rank 0 then writes what the last timed step computed (dump_outputs)."""
         case, set_pop = load_workload(name)
         cfg = RaceConfig(**case['config'])
         drivers = list(case['grid_probs'].keys())
@@ -347,6 +373,11 @@ def main():
         if with_orders and rank == 0:
             o = d_orders[:n * 4096].cpu().numpy().reshape(4096, n)
             assert (np.sort(o, axis=1) == np.arange(n)).all(), 'orders rows are not permutations'
+        if dump_dir and rank == 0:
+            # d_step / d_orders still hold the last timed step (index warmup + steps - 1); its first simulation id on rank 0:
+            dump_outputs(dump_dir, d_step.cpu().numpy().reshape(n, n),
+                         d_orders.view(per_gpu, n).cpu().numpy() if with_orders else None,
+                         first_sim=(warmup + steps - 1) * world * per_gpu)
         g, b, lds = C.c_uint32(), C.c_uint32(), C.c_uint32()
         lib.mcgp_last_launch_info(local_rank, C.byref(g), C.byref(b), C.byref(lds))
         return dict(name=name, n=n, L=L, seed=seed, drivers=drivers, elapsed=elapsed, total=total, hist=hist,
@@ -354,7 +385,8 @@ def main():
                     launch={'grid': g.value, 'block': b.value, 'lds_bytes': lds.value})
 
     t_gpu0 = time.perf_counter()
-    r = run_workload(args.workload, args.steps, args.warmup, with_orders=args.orders, deviates=args.deviates)
+    r = run_workload(args.workload, args.steps, args.warmup, with_orders=args.orders, deviates=args.deviates,
+                     dump_dir=args.dump_outputs)
     if rank == 0:
         n, L, kavg_ms, hist = r['n'], r['L'], r['kernel_ms'], r['hist']
         achieved = per_gpu * ALGORITHMIC_BYTES_PER_SIM / (kavg_ms * 1e-3) / 1e9

@@ -4,6 +4,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -97,3 +98,38 @@ def test_gpu_initialised_reads_torch_only_if_it_is_imported(monkeypatch):
     import torch
     monkeypatch.setattr(torch.cuda, 'is_initialized', lambda: True)
     assert bench.gpu_initialised() is True
+
+
+def test_dump_outputs_writes_the_last_step_as_float_arrays(tmp_path):
+    """--dump-outputs: the step's histogram whole, and a fixed, seeded sample of its finishing orders with the global
+    simulation id of every row; float64 / float32 only, far below 64 MB at the largest field size, the same files for
+    the same arrays."""
+    rng = np.random.default_rng(3)
+    n, rows, first = 32, 200_000, 7 * 200_000
+    hist = rng.integers(0, 10_000_000, (n, n))
+    orders = np.argsort(rng.random((rows, n)), axis=1).astype(np.uint8)
+    assert bench.dump_outputs(str(tmp_path / 'a'), hist, orders, first_sim=first) == ['hist', 'orders', 'orders_sim']
+    bench.dump_outputs(str(tmp_path / 'b'), hist, orders, first_sim=first)
+    got = {k: np.load(tmp_path / 'a' / f'{k}.npy') for k in ('hist', 'orders', 'orders_sim')}
+    assert got['hist'].dtype == np.float64 and np.array_equal(got['hist'], hist)
+    assert got['orders'].dtype == np.float32 and got['orders'].shape == (bench.DUMP_ORDER_ROWS, n)
+    assert got['orders_sim'].dtype == np.float64
+    ids = got['orders_sim'].astype(np.int64)
+    assert (np.diff(ids) > 0).all() and ids[0] >= first and ids[-1] < first + rows
+    assert np.array_equal(got['orders'], orders[ids - first])
+    assert sum(os.path.getsize(p) for p in (tmp_path / 'a').iterdir()) < 64 << 20
+    for k in got:
+        assert (tmp_path / 'a' / f'{k}.npy').read_bytes() == (tmp_path / 'b' / f'{k}.npy').read_bytes(), k
+    # a step without orders writes the histogram only; fewer rows than the sample size are written whole
+    assert bench.dump_outputs(str(tmp_path / 'c'), hist) == ['hist'] and sorted(os.listdir(tmp_path / 'c')) == ['hist.npy']
+    bench.dump_outputs(str(tmp_path / 'd'), hist, orders[:100], first_sim=5)
+    assert np.array_equal(np.load(tmp_path / 'd' / 'orders_sim.npy'), np.arange(5, 105))
+
+
+@pytest.mark.parametrize('argv', [['--steps', '0'], ['--steps', '-2'], ['--warmup', '-1']])
+def test_bench_refuses_step_counts_it_cannot_time(monkeypatch, argv):
+    """ms_per_step is the time of one timed step: at least one step is timed."""
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1'] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2

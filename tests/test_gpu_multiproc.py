@@ -203,3 +203,24 @@ def test_bench_through_rccl_world1(tmp_path):
     assert roof['bound'] == 'valu-issue' and roof['kernel'] == 'mcgp::race_kernel_reg<20>' and roof['kernel_ms_avg'] > 0
     assert roof['hbm_nominal']['bound'] == 'hbm' and 0 < roof['hbm_nominal']['frac'] < 1e-3
     assert (roof['frac'] is None) == (roof['counters_note'] is not None)      # counters quoted, or the reason why not
+
+
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """`bench.py --dump-outputs DIR`: the histogram and finishing orders of the LAST timed step (global simulations
+    [(warmup + steps - 1) x per_gpu, ...)) are the oracle's for those simulation ids, and `steps` timed steps ran."""
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MCGP_BENCH_SHARE_GPU')}
+    per, steps, warmup = 4096, 3, 2
+    cmd = [sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '1', '--steps', str(steps),
+           '--warmup', str(warmup), '--sims-per-step', str(per), '--no-cpu-baseline', '--no-extras', '--orders',
+           '--dump-outputs', str(tmp_path / 'out')]
+    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
+    assert d['steps'] == steps and d['ms_per_step'] > 0
+    first = (warmup + steps - 1) * per
+    ref = O.Problem(O.load_case('S60')).run(per, rng=O.RNG_PHILOX, seed=42, sim_offset=first, want_orders=True)
+    hist = np.load(tmp_path / 'out' / 'hist.npy')
+    assert hist.dtype == np.float64 and np.array_equal(hist, ref['hist'].astype(np.float64))
+    ids = np.load(tmp_path / 'out' / 'orders_sim.npy')
+    assert np.array_equal(ids, np.arange(first, first + per, dtype=np.float64))      # fewer rows than the sample: all
+    assert np.array_equal(np.load(tmp_path / 'out' / 'orders.npy'), ref['orders'].astype(np.float32))
