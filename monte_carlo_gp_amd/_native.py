@@ -220,7 +220,8 @@ def lib():
     """Load the library (building it if the sources are newer); raises if impossible."""
     global _lib
     if _lib is None:
-        path = os.environ.get('MCGP_LIB')          # diagnostic builds (tools/ablate.sh)
+        # another build of the library (diagnostic builds: the ablation records were made by tools/ablate.sh as of commit 355385d)
+        path = os.environ.get('MCGP_LIB')
         if not path:
             build()
             path = LIB_PATH

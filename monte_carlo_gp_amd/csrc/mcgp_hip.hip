@@ -47,14 +47,8 @@ int fail(int code, const std::string &msg)
 // Field sizes with a register-resident instantiation: every n the ABI admits (1..32).  The generic LDS kernel
 // (race_kernel.hip.h) is kept as an independently written second implementation, selected with
 // MCGP_FORCE_GENERIC=1: tests run both and require identical results.
-#ifdef MCGP_ONLY_N20      // diagnostic builds (tools/ablate.sh)
-#define MCGP_REG_SIZES(X) X(20)
-#elif defined(MCGP_ONLY_N)
-#define MCGP_REG_SIZES(X) X(MCGP_ONLY_N)
-#else
 #define MCGP_REG_SIZES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) \
     X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-#endif
 
 // The reference-width build (mcgp_config.deviates = MCGP_DEVIATES_53) is compiled for the same field sizes (reg_inst.hip).
 #define MCGP_WIDE_SIZES(X) MCGP_REG_SIZES(X)
@@ -409,10 +403,6 @@ void launch_geometry(const DeviceCtx &c, uint32_t n, bool is_reg, KernelFn kerne
         waves = (int)((c.lds_per_block - mcgp::kSharedTableBytes) / per_wave);
         if (waves > 8) waves = 8;
         if (waves < 1) waves = 1;
-        if (const char *e = std::getenv("MCGP_WAVES_PER_BLOCK")) {          // tuning / diagnostics (generic kernel only)
-            const int w = std::atoi(e);
-            if (w >= 1 && w <= waves) waves = w;
-        }
         uint32_t threads = (uint32_t)waves * 64u;
         if (n_sims < threads) threads = (uint32_t)(((n_sims + 63) / 64) * 64);
         if (threads == 0) threads = 64;
@@ -422,10 +412,6 @@ void launch_geometry(const DeviceCtx &c, uint32_t n, bool is_reg, KernelFn kerne
     blocks_per_cu = (int)(c.lds_per_block / bytes);
     if (blocks_per_cu * waves > reg_cap) blocks_per_cu = reg_cap / waves;
     if (blocks_per_cu < 1) blocks_per_cu = 1;
-    if (const char *e = std::getenv("MCGP_MAX_BLOCKS_PER_CU")) {
-        const int m = std::atoi(e);
-        if (m >= 1 && m < blocks_per_cu) blocks_per_cu = m;
-    }
     const uint32_t threads = (uint32_t)waves * 64u;
     const uint64_t n_batches = (n_sims + threads - 1) / threads;
     uint64_t g = (uint64_t)c.cu_count * (uint64_t)blocks_per_cu;

@@ -31,19 +31,11 @@
 #include "race_isa.hip.h"
 #include "sort_networks.h"
 
-// Diagnostic builds only (tools/ablate.sh): bit k set = run section k twice (each section is
-// idempotent, results unchanged) so its cost shows up as a time difference.  0 in the product build.
-#ifndef MCGP_DUP
-#define MCGP_DUP 0
-#endif
-// Diagnostic: bit k set = leave section k out (results become wrong; timing only).
-#ifndef MCGP_SKIP
-#define MCGP_SKIP 0
-#endif
-
 #include <utility>
 
-// Statistics hook of the host debugging build (tools/emu): nothing in the product build.
+// ---- Build switches.  They exist for the host build of this source (tools/emu, tests/kernel_host_build.py) and its tests
+// only: none of them changes a result, and the product build compiles every one at its default. ----
+// Statistics hooks of the host debugging build (tools/emu): nothing in the product build.
 #ifndef MCGP_STAT
 #define MCGP_STAT(what, value)
 #endif
@@ -51,13 +43,13 @@
 #define MCGP_TRACE_PASS(sim, lap, pass, n_cand)
 #endif
 // Race-interrupting events handled by the wave with lane = car (1) or by every lane for itself (0: the same
-// results; kept for A/B runs and for the host debugging build, whose threads run one at a time).
+// results; for the host debugging build, whose threads run one at a time).
+#ifndef MCGP_COOPERATIVE_EVENTS
+#define MCGP_COOPERATIVE_EVENTS 1
+#endif
 // Diagnostic (host build, tests): 1 = _sample_grid takes its exact, dividing path for every draw.
 #ifndef MCGP_GRID_EXACT
 #define MCGP_GRID_EXACT 0
-#endif
-#ifndef MCGP_COOPERATIVE_EVENTS
-#define MCGP_COOPERATIVE_EVENTS 1
 #endif
 // Diagnostic (host build, tests): 1 = the reference-width build takes its exact 53-bit path for every event draw and every
 // overtake pass (the path a wave otherwise takes for one draw in 2^32: a word equal to the leading word of its threshold),
@@ -119,29 +111,23 @@ __host__ __device__ constexpr size_t shared_lds_bytes_reg(int n)
            align16((size_t)n * n * 8);      // (16-byte multiple: the per-lane planes that follow are accessed 16 bytes at a time)
 }
 // Waves per SIMD the kernel is compiled for (__launch_bounds__: register budget 512 / this), chosen by measurement
-// for every field size (tools/sweep_waves.sh, one box, 4x10^6 simulations, profiles/r3_sweep_waves.txt): e.g. N = 10
+// for every field size (one box, 4x10^6 simulations, profiles/r3_sweep_waves.txt): e.g. N = 10
 // 13.2 ms at 4 waves, 13.6 at 3, 18.1 at 5; N = 20 32.3 at 3, 51.6 at 4 (spills); N = 22 37.0 at 3, 39.9 at 2; N = 23
 // 42.3 at 2, 51.1 at 3 (the LDS rows of 23 cars leave room for 10 waves per CU only).  N = 4 is the one irregular
 // entry: above 4 waves the compiler moves its arrays to scratch (288 B per lane) and it runs 2-4x slower.
-#ifdef MCGP_MIN_WAVES
-__host__ __device__ constexpr int reg_min_waves(int) { return MCGP_MIN_WAVES; }
-#else
 __host__ __device__ constexpr int reg_min_waves(int n) { return n <= 6 ? (n == 4 ? 4 : 6) : n <= 11 ? 4 : n <= 22 ? 3 : 2; }
-#endif
 // Waves per block: the (waves per block, blocks per CU) pair that keeps the most waves resident within the LDS
 // budget and the kernel's waves per SIMD; among equals a multiple of 4 waves per block (a block's waves go round the
 // 4 SIMDs: two blocks of 6 load them 4, 4, 2, 2), then the block nearest to 8 waves (1024-thread blocks make the
 // register allocator spill more -- N = 10: 164 B per lane against 48 --, many small ones copy the tables more often).
-#ifndef MCGP_MAX_BLOCK_WAVES
-#define MCGP_MAX_BLOCK_WAVES 16
-#endif
+constexpr int kMaxBlockWaves = 16;              // 1024 threads
 constexpr size_t kLdsReserve = 256;             // kept free: the block must fit beside what the runtime itself may take
 __host__ __device__ constexpr int block_shape_rank(int w) { return (w % 4 == 0 ? 0 : 100) + (w <= 8 ? 2 * (8 - w) : w - 8); }
 __host__ __device__ constexpr int reg_block_waves(int n)
 {
     const int cap = 4 * reg_min_waves(n);
     int best = 0, waves = 1;
-    for (int w = 1; w <= MCGP_MAX_BLOCK_WAVES; ++w) {
+    for (int w = 1; w <= kMaxBlockWaves; ++w) {
         int b = (int)((kLdsPerCu - kLdsReserve) / (shared_lds_bytes_reg(n) + (size_t)w * 64 * per_thread_lds_bytes_reg(n)));
         if (b * w > cap) b = cap / w;
         if (b < 1) continue;
@@ -154,24 +140,14 @@ __host__ __device__ constexpr int reg_block_waves(int n)
 __host__ __device__ constexpr size_t reg_retire_ws_bytes(int n, size_t lanes) { return (size_t)(n + 1) * lanes * 4; }
 
 // (WAVES: the default is the block shape measured best for the field size; the reference-width build runs at 2 waves per
-//  SIMD -- 256 registers instead of 168, which its binary64 deviates want -- in blocks of 8 waves)
+//  SIMD -- 256 registers instead of 168, which its binary64 deviates want -- in blocks of 8 waves from 23 cars on)
 // The reference-width build at 3 waves per SIMD (168 registers, as the default build at up to 22 cars): its lap step is
 // ordered so that a batch's four deviates are FINISHED before the batch's slots issue their LDS gathers -- the sixteen
 // registers of a table row and the sixty of the gathered values are then never alive together --, table rows are fetched
 // one at a time, a batch whose rows the block does not hold reads them from device memory one deviate at a time, and the
-// exact 53-bit overtake pass is out of line (wide_pass_exact_fn), so that its registers are not the race loop's to pay for.  Same-box A/B against blocks of 8 waves at 2 per SIMD with the default ordering (profiles/r5_ab.txt): 10 cars -18 %,
-// 16 -12 %, 18 -9.5 %, 19 -7 %, 20 -6.5 % (S78 -4 %), 21 +0.4 %, 22 -2.8 %.  MCGP_WIDE_LEAN=0 (diagnostic builds) keeps every
-// field size at 2 waves per SIMD, gathers first, two rows at a time.
-#ifndef MCGP_WIDE_LEAN
-#define MCGP_WIDE_LEAN 1
-#endif
-// MCGP_WIDE_BLOCK_WAVES / MCGP_WIDE_MIN_WAVES (diagnostic builds): a fixed block shape / register budget for every field size
-// instead of the choice of wide_block_waves() / wide_min_waves() below.
-#ifdef MCGP_WIDE_BLOCK_WAVES
-constexpr int kWideBlockWaves = MCGP_WIDE_BLOCK_WAVES;
-#else
-constexpr int kWideBlockWaves = 0;             // chosen per field size
-#endif
+// exact 53-bit overtake pass is out of line (wide_pass_exact_fn), so that its registers are not the race loop's to pay for.
+// Same-box A/B against blocks of 8 waves at 2 per SIMD, gathers first, two rows at a time (profiles/r5_ab.txt): 10 cars
+// -18 %, 16 -12 %, 18 -9.5 %, 19 -7 %, 20 -6.5 % (S78 -4 %), 21 +0.4 %, 22 -2.8 %.
 // The reference-width build keeps the binary64 inverse-normal table (normal53_table.h: 784 rows of 8 coefficients, 64 B
 // each) in LDS, behind the per-lane planes, instead of the 7 KB binary32 table it has no use for: as many of the table's
 // LAST rows -- the cells of the largest tail indices -- as fit beside the block's other data, in whole octaves of 16 rows,
@@ -251,32 +227,24 @@ struct RegGeo {
     static_assert(kBytes + kLdsReserve <= kLdsPerCu, "block does not fit LDS");
     static_assert(oLast < 65536, "row bases must fit the DS immediate offset");
 };
-// Waves per block of the reference-width build (one block per CU).  The lean ordering of its lap step (MCGP_WIDE_LEAN) fits
-// the 168 registers of 3 waves per SIMD, so the block is as large as the LDS allows while still holding kWideMinLdsRows
+// Waves per block of the reference-width build (one block per CU).  The lean ordering of its lap step fits the 168
+// registers of 3 waves per SIMD, so the block is as large as the LDS allows while still holding kWideMinLdsRows
 // rows of the table -- below that a batch of deviates leaves the LDS rows too often: 12 or 11 waves up to 20 cars, 10 at 21
-// and 22 --; without room for more than 8 waves (23 cars and more), or without the lean ordering, 8 waves at 2 per SIMD
-// (256 registers), fewer for the largest fields (31 cars and more).
+// and 22 --; without room for more than 8 waves (23 cars and more), 8 waves at 2 per SIMD (256 registers), fewer for the
+// largest fields (31 cars and more).
 constexpr int kWideMinLdsRows = 14 * 16;
 __host__ __device__ constexpr int wide_block_waves(int n)
 {
-    if (kWideBlockWaves == 0 && MCGP_WIDE_LEAN && n <= 22) {        // (23 cars and more: the default build itself runs at 2 waves per SIMD)
+    if (n <= 22) {        // (23 cars and more: the default build itself runs at 2 waves per SIMD)
         for (int w = 12; w > 8; --w)
             if (wide_fixed_lds_bytes(n, w) + kLdsReserve <= kLdsPerCu && wide_lds_rows(n, w) >= kWideMinLdsRows) return w;
     }
-    int w = kWideBlockWaves ? kWideBlockWaves : 8;
+    int w = 8;
     while (w > 1 && wide_fixed_lds_bytes(n, w) + kLdsReserve > kLdsPerCu) --w;
     return w;
 }
 // waves per SIMD it is compiled for (register budget 512 / this)
-__host__ __device__ constexpr int wide_min_waves(int n)
-{
-#ifdef MCGP_WIDE_MIN_WAVES
-    (void)n;
-    return MCGP_WIDE_MIN_WAVES;
-#else
-    return wide_block_waves(n) > 8 ? 3 : 2;
-#endif
-}
+__host__ __device__ constexpr int wide_min_waves(int n) { return wide_block_waves(n) > 8 ? 3 : 2; }
 template <int N>
 using WideGeo = RegGeo<N, wide_block_waves(N), true>;
 
@@ -564,30 +532,6 @@ __device__ __forceinline__ uint32_t pit_rule_word(int track, int regime, uint32_
     return (newc << k3CompShift) | ((used | (1u << newc)) & k3UsedMask);
 }
 
-// The instruction scheduler may not move anything across this point (no instruction is emitted).
-#ifndef MCGP_SCHED_FENCE
-#define MCGP_SCHED_FENCE() sched_fence()
-#endif
-#ifndef MCGP_STEP_BATCH
-#define MCGP_STEP_BATCH 4          // slots whose LDS gathers (and Philox blocks) are in flight together in the lap step
-#endif
-#ifndef MCGP_DISTINCT_PATH
-#define MCGP_DISTINCT_PATH 1       // update_positions_reg<N, true> for the wave-laps whose fields have no equal times
-#endif
-// Diagnostic (timing only, wrong results in the rare cases): 1 = the two rare paths of the reference-width build are never taken
-#ifndef MCGP_NOCALLS
-#define MCGP_NOCALLS 0
-#endif
-#ifndef MCGP_WIDE_STEP_BATCH
-#define MCGP_WIDE_STEP_BATCH 4
-#endif
-#ifndef MCGP_WIDE_PACE_BATCH
-#define MCGP_WIDE_PACE_BATCH 5
-#endif
-#ifndef MCGP_PACE_BATCH
-#define MCGP_PACE_BATCH 5          // slots whose pace gathers are in flight together in an overtake pass (10: same speed, 52 B of spills against 20)
-#endif
-
 // A lower bound of every lap time of the problem, lap 1 included (reference :317-332, :301-306), from the inputs alone:
 // slowest possible fuel effect, DRS gain, the largest negative noise a deviate can give (|z| < 6.5, 8.5 at reference width), the most
 // negative compound delta and degradation x age, the dirty-air penalty if it is negative, the largest start gain.
@@ -733,9 +677,6 @@ __device__ __forceinline__ uint32_t uniform_u32(uint32_t x)
     return x;                                   // (the host debugging build: one thread at a time)
 #endif
 }
-__device__ __forceinline__ uint64_t uniform_u64(uint64_t x) { return (uint64_t)uniform_u32((uint32_t)x) | ((uint64_t)uniform_u32((uint32_t)(x >> 32)) << 32); }
-template <typename T>
-__device__ __forceinline__ T *uniform_ptr(T *p) { return reinterpret_cast<T *>(uniform_u64(reinterpret_cast<uint64_t>(p))); }
 // The exact 53-bit decision of one overtake pass of the reference-width build (reg_simulate, overtakes): the path of a draw
 // word that EQUALS the leading word of its threshold, or of a lane with more than eight attempts.  Plain code, four attempts
 // at a time: their words in rows 0..3 of the W plane, the companion words in rows 4..7.  Returns bit i = the attempt at pair i
@@ -803,11 +744,11 @@ __device__ __forceinline__ uint32_t wide_pass_exact_body(const uint32_t (&pk)[N]
 }
 // The same OUT OF LINE, for the builds at 3 waves per SIMD (up to 22 cars): inlined, its forty registers of 64-bit thresholds
 // are the race loop's to pay for -- 880 B of scratch per lane at 168 registers; as a call it costs the loop about 20 scratch
-// accesses per lap (what lives across a call is saved where it is defined: profiles/r5_ab.txt, MCGP_NOCALLS).  The field's
-// pk words go in by value.  The builds at 2 waves per SIMD (23 cars and more, 256 registers) inline the body: a 32-car
-// build with the call gave wrong results in most simulations in three of six otherwise equivalent variants of the
-// surrounding code (a call inside divergent control flow of a kernel that spills 214 scalar registers to vector lanes;
-// tools/dbg_wide_n.py, profiles/r5_ab.txt) -- the call stays where every build of it has been checked at scale
+// accesses per lap (what lives across a call is saved where it is defined: profiles/r5_ab.txt, a timing build without the
+// call).  The field's pk words go in by value.  The builds at 2 waves per SIMD (23 cars and more, 256 registers) inline the
+// body: a 32-car build with the call gave wrong results in most simulations in three of six otherwise equivalent variants of
+// the surrounding code (a call inside divergent control flow of a kernel that spills 214 scalar registers to vector lanes;
+// profiles/r5_ab.txt) -- the call stays where every build of it has been checked at scale
 // (profiles/r5_deep_parity_wide.txt, also with every pass sent through it: MCGP_WIDE_EXACT=1).
 template <int N>
 struct PkWords {
@@ -842,11 +783,12 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                                              uint32_t ws_first_lane, const double *__restrict__ norm53 = nullptr)
 {
     constexpr int B = G::B;
-    // slots in flight together in the lap step / in an overtake pass (the reference-width build has 256 registers to spend)
-    constexpr int kStepBatch = WIDE ? MCGP_WIDE_STEP_BATCH : MCGP_STEP_BATCH;
-    // (WIDE, compiled for 3 waves per SIMD: deviates first, gathers last, one table row at a time -- see MCGP_WIDE_LEAN)
+    // slots whose LDS gathers (and Philox blocks) are in flight together in the lap step (both widths)
+    constexpr int kStepBatch = 4;
+    // (WIDE, compiled for 3 waves per SIMD: deviates first, gathers last, one table row at a time -- see wide_block_waves)
     constexpr bool kLean = WIDE && wide_min_waves(N) >= 3;
-    constexpr int kPaceBatch = WIDE ? MCGP_WIDE_PACE_BATCH : MCGP_PACE_BATCH;
+    // slots whose pace gathers are in flight together in an overtake pass, both widths (10: same speed, 52 B of spills against 20)
+    constexpr int kPaceBatch = 5;
     static_assert(kStepBatch % 4 == 0, "a Philox block serves four consecutive places");
     const uint32_t tid4 = tid * 4u, tid8 = tid * 8u;
     const int L = P->total_laps;
@@ -942,9 +884,6 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 uint32_t sel;
                 if (fixed_grid) {
                     sel = fixed_grid[pos];
-                } else if (MCGP_SKIP & 4) {
-                    sel = (uint32_t)((pos * 7 + (int)(c0 & 3u)) % N);
-                    while (!((remaining >> sel) & 1u)) sel = (sel + 1u) % (uint32_t)N;
                 } else {
                     if ((pos & 3) == 0) {
                         philox4x32_10(c0, c1, 0u, kPurposeGrid | (uint32_t)(pos >> 2), seed_lo, seed_hi, g0, g1, g2, g3);
@@ -1225,7 +1164,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                     survived[j] = 0u;
                 }
 #pragma unroll 1
-                for (int k = (MCGP_SKIP & 256) ? L + 1 : 2; k <= L; ++k) {
+                for (int k = 2; k <= L; ++k) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         survived[j] += rw[j] < S[j] ? 1u : 0u;                       // survives lap k
@@ -1239,7 +1178,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                     if (d >= N) continue;
                     if (P->t_dnf[d] == 0ull) continue;                               // (wave-uniform)
                     const uint32_t out_lap = 2u + survived[j];
-                    if (out_lap <= (uint32_t)L && !(MCGP_SKIP & 256)) {
+                    if (out_lap <= (uint32_t)L) {
                         const uint32_t key = (out_lap << 5) | (uint32_t)d;
                         // the list in device memory is only ever read by a lane with MORE than two retirements: the
                         // first two are written when a third turns up (about one race in thirteen), not before
@@ -1262,7 +1201,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
         // ================= laps 2..L, reference :166-228 =================
         int drs_disabled_until = 0;
 #pragma unroll 1
-        for (int lap = 2; lap <= ((MCGP_SKIP & 8) ? 1 : L); ++lap) {
+        for (int lap = 2; lap <= L; ++lap) {
             const int remaining_laps = L - lap;
             // The simulation id as this lap sees it: opaque to the optimiser, so that it does not lift the lap-
             // invariant part of every Philox block of the loop body (round 1 depends on the id and the block's
@@ -1295,11 +1234,6 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
             {
                 uint32_t e0, e1, e2, e3;
                 philox4x32_10(c0l, c1l, (uint32_t)lap, kPurposeEvent, k0l, k1l, e0, e1, e2, e3);
-                if (MCGP_DUP & 16) {
-                    uint32_t f0, f1, f2, f3;
-                    philox4x32_10(c0l ^ e0, c1l, (uint32_t)lap, kPurposeEvent, k0l, k1l, f0, f1, f2, f3);
-                    if ((f0 | f1 | f2 | f3) == 0u) e0 = f0;     // never true in practice; keeps the block alive
-                }
                 // the lap's four Bernoulli draws (:168, :171, :174, :392)
                 bool d_red, d_sc, d_vsc, d_tire;
                 if constexpr (WIDE) {
@@ -1344,7 +1278,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 // (two, in fact: one per half of the wave) at a time with LANE = CAR -- the leader is a ballot + readlane,
                 // a car's place among the running cars a popcount of the ballot below it, the neighbour's new time a
                 // bpermute -- and the lane takes its field back.
-                const bool evt = !(MCGP_SKIP & 2) && (red || sc || vsc);
+                const bool evt = red || sc || vsc;
                 const unsigned long long emask = __ballot(evt);
                 if (emask != 0ull) {
                     constexpr int kRowsPerField = (align16(8 * N) + 4 * N <= 256) ? 1 : 2;   // cum (8 N bytes) and pk (4 N) of one field
@@ -1456,7 +1390,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                     }
                 }
 #else
-                if (!(MCGP_SKIP & 2) && (red || sc || vsc)) {
+                if (red || sc || vsc) {
                     // Only a few lanes of a wave are in here, but the wave pays for every instruction: the handlers
                     // (:334-431) are one pass over the ranks without branches.  Running cars are re-spaced behind the
                     // leader (red flag 0.1 s apart, safety car 0.5 s apart, VSC gaps x 0.8), their time_behind_leader
@@ -1507,7 +1441,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
             // lap times are positive (reg_time_floor), a row is rewritten by every lap its driver runs and never read once
             // he is out.  Rare per lane (a retirement per race), so the wave branches; the next key comes from the lane's
             // list in device memory.
-            while (!(MCGP_SKIP & 512) && MCGP_ANY(((next_out >> 5) & 0x3FFu) == (uint32_t)lap)) {
+            while (MCGP_ANY(((next_out >> 5) & 0x3FFu) == (uint32_t)lap)) {
                 if (((next_out >> 5) & 0x3FFu) == (uint32_t)lap) {
                     const uint32_t key = next_out & kNoKey;
                     lds_or_u32(G::oLast + (key & 31u) * (uint32_t)(B * 8) + tid8 + 4u, 0x80000000u);   // (no value comes back: nothing to wait for)
@@ -1538,8 +1472,8 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 if constexpr (reg_min_waves(N) <= 3) pin(retire_word);      // (at 4+ waves per SIMD the register it takes is spilled)
                 double carry = 0.0;
 #pragma unroll
-                for (int i0 = 0; i0 < ((MCGP_SKIP & 64) ? 0 : N); i0 += kStepBatch) {
-                    MCGP_SCHED_FENCE();          // one batch at a time: gathers hoisted from later batches cost registers
+                for (int i0 = 0; i0 < N; i0 += kStepBatch) {
+                    sched_fence();         // one batch at a time: gathers hoisted from later batches cost registers
                     SlotIn in[kStepBatch];
                     if constexpr (!kLean) {
 #pragma unroll
@@ -1574,7 +1508,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                             rare |= (i0 + j < N) && zhi[j] < kRareHi;
                         }
                         MCGP_STAT(15, rare);
-                        if (MCGP_NOCALLS || __builtin_expect(!MCGP_ANY(rare), 1)) {
+                        if (__builtin_expect(!MCGP_ANY(rare), 1)) {
                             constexpr int R = kLean ? 1 : 2;                  // table rows fetched together (16 registers each)
 #pragma unroll
                             for (int j0 = 0; j0 < kStepBatch; j0 += R) {
@@ -1593,14 +1527,14 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                             for (int j = 0; j < kStepBatch; ++j) {
                                 z[j] = (i0 + j < N) ? normal53(w[j >> 2][j & 3], x[j >> 2][j & 3], norm53) : 0.0;
                                 pin(z[j]);
-                                MCGP_SCHED_FENCE();
+                                sched_fence();
                             }
                         }
                         if constexpr (kLean) {
                             // the deviates are done: only now the slots' gathers
 #pragma unroll
                             for (int j = 0; j < kStepBatch; ++j) pin(z[j]);
-                            MCGP_SCHED_FENCE();
+                            sched_fence();
 #pragma unroll
                             for (int j = 0; j < kStepBatch; ++j)
                                 if (i0 + j < N) in[j] = load_slot(pk[i0 + j], lut_base);
@@ -1679,14 +1613,12 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
             }
 
             // ---- _simulate_overtakes, :496-536 ----
-            bool distinct_times = true;
-            if (!(MCGP_SKIP & 16)) distinct_times = network_sort<N>(cum, pk);
-            if (MCGP_DUP & 1) network_sort<N>(cum, pk);
+            bool distinct_times = network_sort<N>(cum, pk);
             // The three passes are three copies of the code: a rolled loop makes the compiler shuffle the whole field
             // (60 registers, renamed by every compare-exchange) back into place at its back edge; unrolled it is 3-4 %
             // faster at every field size although the lap body no longer fits a 64 KB instruction cache.
 #pragma unroll
-            for (int pass = 0; pass < ((MCGP_SKIP & 1) ? 0 : 3); ++pass) {
+            for (int pass = 0; pass < 3; ++pass) {
                 // ---- overtakes: pace deltas and candidates ----
                 // pace of every slot (:514-515), the pace delta of every adjacent pair, and what an attempt needs to
                 // succeed.  Everything is scaled by 2^31 (tables, reg_load_tables): u < min(0.5, delta / 2) for the
@@ -1739,7 +1671,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                             double pace_prev = 0.0;
 #pragma unroll
                         for (int h = 0; h < N; h += H) {
-                            MCGP_SCHED_FENCE();
+                            sched_fence();
                             double pb[H], pd[H], pa[H];
 #pragma unroll
                             for (int j = 0; j < H; ++j) {
@@ -1785,7 +1717,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
 #pragma unroll
                         for (int i = 1; i < N; ++i) tie |= ((ow[i] ^ thr[i]) >> MCGP_WIDE_TIE_SHIFT) == 0u;
                         MCGP_STAT(11, tie);
-                        if (!MCGP_NOCALLS && __builtin_expect(MCGP_ANY(tie || MCGP_WIDE_EXACT || words_end > (uint32_t)(kWordRows * B * 4)), 0)) {
+                        if (__builtin_expect(MCGP_ANY(tie || MCGP_WIDE_EXACT || words_end > (uint32_t)(kWordRows * B * 4)), 0)) {
                             const uint32_t hits = wide_pass_exact();
 #pragma unroll
                             for (int i = 1; i < N; ++i) {
@@ -1853,16 +1785,12 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 if (!any_succ) break;
                 // ---- overtakes: re-sort ----
                 distinct_times = resort_after_overtakes<N>(cum, pk);     // sorted again for the next pass / _update_positions
-                if (MCGP_DUP & 8) resort_after_overtakes<N>(cum, pk);
             }
-            // ---- _update_positions, :227-228 ----
-            if (!(MCGP_SKIP & 32)) {
-                if (MCGP_DISTINCT_PATH && !MCGP_ANY(!distinct_times))
-                    update_positions_reg<N, true>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
-                else
-                    update_positions_reg<N>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
-            }
-            if (MCGP_DUP & 4) update_positions_reg<N>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
+            // ---- _update_positions, :227-228 ----  (update_positions_reg<N, true> for the wave-laps whose fields have no equal times)
+            if (!MCGP_ANY(!distinct_times))
+                update_positions_reg<N, true>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
+            else
+                update_positions_reg<N>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
         }
 
         // ================= classification, reference :230-242 =================
@@ -1968,39 +1896,13 @@ race_kernel_reg_wide(const KParams *__restrict__ P, uint64_t n_sims, uint64_t si
 struct BatchItem {
     uint64_t sim_offset, seed;
 };
-// One problem of the batch on this block: tables, the block's share of the problem's chunks, histogram flush.  A function
-// of its own (MCGP_BATCH_CALL=1) so that the register allocator sees the race loop as it sees it in the single-problem kernel.
-#ifndef MCGP_BATCH_CALL
-#define MCGP_BATCH_CALL 0
-#endif
+// One problem of the batch on this block: tables, the block's share of the problem's chunks, histogram flush.
 template <int N>
-#if MCGP_BATCH_CALL
-__device__ __attribute__((noinline))
-#else
-__device__ __forceinline__
-#endif
-void batch_problem(const KParams *__restrict__ P_, unsigned char *smem_, uint32_t *__restrict__ ticket_, uint64_t n_sims_,
-                   uint64_t sim_offset_, uint64_t seed_, uint32_t n_chunks_, uint32_t *__restrict__ retire_ws_,
-                   unsigned long long *__restrict__ hist_)
+__device__ __forceinline__ void batch_problem(const KParams *__restrict__ P, unsigned char *smem, uint32_t *__restrict__ ticket,
+                                              uint64_t n_sims, uint64_t sim_offset, uint64_t seed, uint32_t n_chunks,
+                                              uint32_t *__restrict__ retire_ws, unsigned long long *__restrict__ hist)
 {
     using G = RegGeo<N>;
-#if MCGP_BATCH_CALL
-    const KParams *__restrict__ P = uniform_ptr(P_);
-    unsigned char *smem = uniform_ptr(smem_);
-    uint32_t *__restrict__ ticket = uniform_ptr(ticket_);
-    uint32_t *__restrict__ retire_ws = uniform_ptr(retire_ws_);
-    unsigned long long *__restrict__ hist = uniform_ptr(hist_);
-    const uint64_t n_sims = uniform_u64(n_sims_), sim_offset = uniform_u64(sim_offset_), seed = uniform_u64(seed_);
-    const uint32_t n_chunks = uniform_u32(n_chunks_);
-#else
-    const KParams *__restrict__ P = P_;
-    unsigned char *smem = smem_;
-    uint32_t *__restrict__ ticket = ticket_;
-    uint32_t *__restrict__ retire_ws = retire_ws_;
-    unsigned long long *__restrict__ hist = hist_;
-    const uint64_t n_sims = n_sims_, sim_offset = sim_offset_, seed = seed_;
-    const uint32_t n_chunks = n_chunks_;
-#endif
     reg_load_tables<N>(P, smem, threadIdx.x);                    // (zeroes the LDS histogram)
     __syncthreads();
     reg_simulate<N>(P, smem, threadIdx.x, ticket, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32),

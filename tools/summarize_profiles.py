@@ -143,8 +143,9 @@ def main():
               '"VALU issue frac of peak" = SQ_INSTS_VALU / kernel time / (1024 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction); '
               'HBM bytes = (2 x FETCH_SIZE + WRITE_SIZE) KiB, separate passes (gfx950 correction for FETCH_SIZE).  '
               f'`VGPR` is rocprofv3\'s VGPR_Count = allocated registers / 2 (168 -> 84 for N = 20).', '',
-              f'Companion files: `{tag}_ablate.txt` (tools/ablate.sh: DUP = section run twice, SKIP = section left out; kernel ms at 4e6 '
-              f'simulations), `{tag}_ab.txt` (same-box A/B runs of the optimisation log, tools/ab.sh), `{tag}_deep_parity.txt` '
+              f'Companion files: `{tag}_ablate.txt` (DUP = section run twice, SKIP = section left out; kernel ms at 4e6 simulations; '
+              f'the ablation records were made by tools/ablate.sh as of commit 355385d), `{tag}_ab.txt` (same-box A/B runs of the '
+              f'optimisation log, made by tools/ab.sh as of the same commit), `{tag}_deep_parity.txt` '
               f'(tools/deep_parity.py), `{tag}_deviate_bias.txt` (tools/deviate_bias_gpu.py), `{tag}_<workload>_kernel_stats.csv` '
               '(verbatim `--kernel-trace --stats`).']
     with open(os.path.join(OUT, f'{tag}_summary.md'), 'w') as f:
