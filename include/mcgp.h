@@ -29,7 +29,8 @@ extern "C" {
 
 /* 2: mcgp_build_hash, mcgp_run_batch; the retirement draw of laps >= 2 moved to one word per driver and race, which
  * changes the results for a given seed (the oracle's Philox back-end moved with it) */
-#define MCGP_ABI_VERSION 2
+/* 3: mcgp_run_championship */
+#define MCGP_ABI_VERSION 3
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
 
@@ -151,6 +152,38 @@ int32_t mcgp_run_device(const mcgp_config *cfg, const mcgp_drivers *drv, const d
 int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_drivers *drvs,
                        const double *const *grid_probs, uint32_t n, uint64_t n_sims, const uint64_t *sim_offsets,
                        const uint64_t *seeds, int32_t device, uint64_t *hist_out);
+
+/* Championship simulation: drivers' and constructors' title odds over a calendar of n_races races (at most 64) of the same
+ * n drivers in the same index order.  Simulation s of the season (ids sim_offset .. sim_offset + n_sims - 1) is the tuple
+ * of the finishing orders mcgp_run gives each race r alone for id s: cfgs[r], drvs[r], grid_probs[r] (n x n) under
+ * seeds[r], at that race's deviate width.
+ *   points       [n_races][n] int32: points of classified position p + 1 (0 past the table; >= 0).  Points go by the
+ *                classification the race model makes -- retired cars are classified behind the finishers, as in the
+ *                reference -- so a retired car scores when fewer cars finish than the table pays.  Half points: scale
+ *                the table by 2.
+ *   countback    [n_races] u8: 1 for a Grand Prix, 0 for a sprint (scores, does not count for tie-breaks)
+ *   init_points  [n] int32 or NULL (0): points before these races
+ *   init_counts  [n][n] int32 or NULL (0): earlier countback finishes of driver d in position p + 1
+ *   team         [n] int32: team index of each driver in [0, n_teams), 1 <= n_teams <= n; a team's points and counts
+ *                are the sums of its drivers' (its initial standing too)
+ * Ranking: more points, then more 1st places, then more 2nd places, ... down to n-th; a full tie goes to the lower
+ * driver (team) index.  The regulations decide such a tie by further criteria this model does not have.
+ * Outputs, ACCUMULATED into (caller zeroes):
+ *   champ_hist   [n][n]    counts of [driver][championship position - 1]
+ *   team_hist    [n_teams][n_teams] the same for the teams
+ *   gain_hist    [n][G + 1] counts of [driver][points gained in these races], G = sum over r of max_p points[r][p]
+ *   race_hist    [n_races][n][n] or NULL: each race's position histogram, equal to mcgp_run's for that race
+ * Limits (MCGP_E_BAD_ARG, message names the limit, checked before any device lookup): n in [1, 32], n_races in
+ * [1, 64], init_points[d] + G <= 65535, init_counts[d][p] + (number of countback races) <= 31.
+ * The device work goes chunk by chunk (2^22 simulations) and race by race through mcgp_run's launch path; device memory
+ * does not grow with n_sims.  Host buffers in and out, blocking; any split of [0, N) over calls, sim_offsets or devices
+ * sums to the same counts.  mcgp_last_kernel_ms afterwards = the device time of everything the call ran. */
+int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                              const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                              const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                              const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                              uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                              uint64_t *gain_hist, uint64_t *race_hist);
 
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver

@@ -3,6 +3,7 @@
     python -m monte_carlo_gp_amd.cli predict  --race Bahrain --season 2024 --simulations 10000 --seed 42 --offline
     python -m monte_carlo_gp_amd.cli backtest --seasons 2024 --seed 42 --simulations 10000000 [--fixtures DIR]
     python -m monte_carlo_gp_amd.cli export-fixtures --seasons 2024 --out DIR
+    python -m monte_carlo_gp_amd.cli championship --season 2024 --from-round 18 --simulations 10000000 --seed 7
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -286,6 +287,68 @@ def cmd_export_fixtures(args) -> int:
     return 0
 
 
+def championship_jobs(season, seed, from_round=1, fixtures_dir=None):
+    """The races of a championship run: rounds from_round..end of results_<season>.json, each with backtest_jobs' inputs
+    and per-race seed (the same seed gives the same race draws as `backtest`).  The results file does not mark sprint
+    weekends, so every round is a Grand Prix."""
+    jobs = backtest_jobs([season], seed, fixtures_dir)
+    if not 1 <= from_round <= len(jobs):
+        raise ValueError(f'--from-round must be in [1, {len(jobs)}], got {from_round}')
+    return jobs[from_round - 1:]
+
+
+def championship_races(jobs, device=0):
+    """run_championship's race dicts for championship_jobs' rows (inputs from F1Predictor.simulator_inputs)."""
+    races = []
+    for season, entry, race_seed, fixture in jobs:
+        inp = F1Predictor(device=device).simulator_inputs(fixture, entry['race'])
+        races.append(dict(config=inp['config'], grid_probs=inp['grid_probs'], base_pace=inp['base_pace'],
+                          tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
+                          driver_dnf_rates=inp['driver_dnf_rates'], track_condition=inp['track_condition'],
+                          seed=race_seed))
+    return races
+
+
+def cmd_championship(args) -> int:
+    from .simulation import run_championship
+    jobs = championship_jobs(args.season, args.seed, args.from_round, args.fixtures)
+    standings = None
+    if args.standings:
+        with open(args.standings) as f:
+            standings = json.load(f)
+    races = championship_races(jobs, args.device)
+    t0 = time.perf_counter()
+    res = run_championship(races, args.simulations, standings=standings, device=args.device,
+                           return_race_histograms=True)
+    dt = time.perf_counter() - t0
+    partial = args.from_round > 1 and not standings
+    what = f'points from round {args.from_round} on' if partial else 'season standings'
+    print(f"\n{'=' * 60}\nChampionship {args.season}: rounds {args.from_round}-{args.from_round + len(jobs) - 1} "
+          f"({len(jobs)} Grands Prix), {what}\nSimulations: {args.simulations}  seed: {args.seed}   "
+          f"({args.simulations * len(jobs) / dt:,.0f} race simulations/s)\n{'=' * 60}\n")
+    _bars(f"DRIVERS' TITLE PROBABILITIES ({what})", res.title_probabilities)
+    print()
+    _bars(f"CONSTRUCTORS' TITLE PROBABILITIES ({what})", res.constructor_title_probabilities)
+    print()
+    exp = res.expected_points
+    print(f'EXPECTED POINTS ({what})\n' + '-' * 40)
+    for i, (d, p) in enumerate(sorted(exp.items(), key=lambda kv: kv[1], reverse=True)[:10], 1):
+        print(f'{i:2}. {d:4} {p:7.1f}')
+    if args.json:
+        n = res.n_simulations
+        out = dict(season=args.season, from_round=args.from_round, points_from_round_only=partial,
+                   simulations=n, seed=args.seed, drivers=res.drivers, teams=res.teams,
+                   title_probabilities=res.title_probabilities, position_probabilities=res.position_probabilities,
+                   expected_points=exp, constructor_title_probabilities=res.constructor_title_probabilities,
+                   constructor_position_probabilities=res.constructor_position_probabilities,
+                   races=[dict(race=entry['race'], seed=race_seed,
+                               win_probabilities={d: int(h[i, 0]) / n for i, d in enumerate(res.drivers)})
+                          for (_, entry, race_seed, _), h in zip(jobs, res.race_histograms)])
+        with open(args.json, 'w') as f:
+            json.dump(out, f)
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog='monte_carlo_gp_amd', description='F1 race prediction on MI355X')
     sub = ap.add_subparsers(dest='cmd', required=True)
@@ -313,6 +376,17 @@ def main(argv=None) -> int:
     e.add_argument('--seasons', type=int, nargs='+', default=[2024])
     e.add_argument('--out', type=str, required=True)
     e.set_defaults(fn=cmd_export_fixtures)
+    c = sub.add_parser('championship', help="drivers' and constructors' title odds over the rest of a season")
+    c.add_argument('--season', type=int, default=2024)
+    c.add_argument('--from-round', type=int, default=1, help='first round simulated (1-based)')
+    c.add_argument('--standings', type=str, default=None,
+                   help='JSON {driver: points} or {driver: {"points": p, "finishes": [P1s, P2s, ...]}} before that round')
+    c.add_argument('--fixtures', type=str, default=None, help='directory of per-race fixture files (as for backtest)')
+    c.add_argument('--simulations', type=int, default=10000)
+    c.add_argument('--seed', type=int, default=42)
+    c.add_argument('--device', type=int, default=0)
+    c.add_argument('--json', type=str, default=None)
+    c.set_defaults(fn=cmd_championship)
     args = ap.parse_args(argv)
     return args.fn(args)
 

@@ -9,6 +9,7 @@
 #include "params_build.h"
 #include "race_kernel.hip.h"
 #include "race_kernel_reg.hip.h"
+#include "championship.hip.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
 #include "frontend_exp.h"
@@ -20,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -169,6 +171,11 @@ struct DeviceCtx {
     uint32_t *d_batch_retire = nullptr;     // ... and the lanes' retirement lists
     size_t batch_retire_bytes = 0;
     hipEvent_t batch_start = nullptr, batch_stop = nullptr;     // ... and the timing events of the last batch call
+                                                                // (and of the last championship call)
+    uint64_t *d_champ_keys = nullptr;       // mcgp_run_championship: standing keys of a chunk (grow-only)
+    size_t champ_keys_bytes = 0;
+    unsigned char *d_champ = nullptr;       // ... and its tables and histograms (grow-only)
+    size_t champ_bytes = 0;
     uint32_t last_grid = 0, last_block = 0, last_lds = 0;
     char last_kernel[48] = "";
 };
@@ -225,6 +232,11 @@ void release_ctx(DeviceCtx &c)
     c.batch_start = c.batch_stop = nullptr;
     c.d_batch = nullptr;
     c.d_batch_retire = nullptr;
+    if (c.d_champ_keys) (void)hipFree(c.d_champ_keys);
+    if (c.d_champ) (void)hipFree(c.d_champ);
+    c.d_champ_keys = nullptr;
+    c.d_champ = nullptr;
+    c.champ_keys_bytes = c.champ_bytes = 0;
     c.batch_bytes = c.batch_retire_bytes = 0;
     for (auto &t : c.timer) {
         if (t.start) (void)hipEventDestroy(t.start);
@@ -478,6 +490,23 @@ int claim_timer(DeviceCtx &c, hipStream_t stream, int *out)
         c.timer[ti].used = true;
     }
     *out = ti;
+    return MCGP_OK;
+}
+
+// The pair of timing events of a call that runs several kernels (mcgp_run_batch, mcgp_run_championship): recorded on
+// the null stream around everything the call runs, so that mcgp_last_kernel_ms afterwards gives the whole call.
+int ensure_call_events(DeviceCtx &c)
+{
+    if (c.batch_start) return MCGP_OK;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t err = hipEventCreate(&e0);
+    if (err == hipSuccess) err = hipEventCreate(&e1);
+    if (err != hipSuccess) {
+        if (e0) (void)hipEventDestroy(e0);
+        return fail(MCGP_E_HIP, std::string("batch timing events: ") + hipGetErrorString(err));
+    }
+    c.batch_start = e0;
+    c.batch_stop = e1;
     return MCGP_OK;
 }
 
@@ -1005,17 +1034,8 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
         if (r != MCGP_OK) return r;
         HIP_TRY(hipSetDevice(device));
         // the call's own pair of timing events (mcgp_last_kernel_ms after a batch call = everything it ran on the device)
-        if (!c->batch_start) {
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            hipError_t err = hipEventCreate(&e0);
-            if (err == hipSuccess) err = hipEventCreate(&e1);
-            if (err != hipSuccess) {
-                if (e0) (void)hipEventDestroy(e0);
-                return fail(MCGP_E_HIP, std::string("batch timing events: ") + hipGetErrorString(err));
-            }
-            c->batch_start = e0;
-            c->batch_stop = e1;
-        }
+        r = ensure_call_events(*c);
+        if (r != MCGP_OK) return r;
         HIP_TRY(hipEventRecord(c->batch_start, nullptr));
         const size_t cell_bytes = sizeof(unsigned long long) * n * n;
         if (n_shared) {
@@ -1090,6 +1110,216 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
         }
         HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
         c->last_timer = kBatchTimer;
+        return MCGP_OK;
+    };
+    return body();
+}
+
+// Bits needed to hold x (at least 1).
+static uint32_t champ_bits(uint64_t x)
+{
+    uint32_t b = 1;
+    while (b < 64 && (x >> b) != 0) ++b;
+    return b;
+}
+
+int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                              const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                              const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                              const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                              uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                              uint64_t *gain_hist, uint64_t *race_hist)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!cfgs || !drvs || !grid_probs || !seeds || !points || !countback || !team || !champ_hist || !team_hist ||
+        !gain_hist)
+        return fail(MCGP_E_BAD_ARG, "a championship array is NULL");
+    if (n_races < 1 || n_races > (uint32_t)mcgp::kChampMaxRaces) return fail(MCGP_E_BAD_ARG, "n_races must be in [1, 64]");
+    if (n < 1 || n > MCGP_MAX_CARS) return fail(MCGP_E_BAD_ARG, "n must be in [1, 32]");
+    if (n_teams < 1 || n_teams > n) return fail(MCGP_E_BAD_ARG, "n_teams must be in [1, n]");
+    for (uint32_t d = 0; d < n; ++d)
+        if (team[d] < 0 || (uint32_t)team[d] >= n_teams) return fail(MCGP_E_BAD_ARG, "a team index is outside [0, n_teams)");
+    constexpr uint64_t kMaxPoints = (1u << mcgp::kChampPointsBits) - 1, kMaxCount = (1u << mcgp::kChampCountBits) - 1;
+    uint64_t G = 0, awarded = 0;         // most points one driver can gain in these races; points the races award in all
+    uint32_t n_cb = 0;                   // countback races
+    for (uint32_t r = 0; r < n_races; ++r) {
+        if (countback[r] > 1) return fail(MCGP_E_BAD_ARG, "countback[r] must be 0 or 1");
+        n_cb += countback[r];
+        int64_t best = 0;
+        for (uint32_t p = 0; p < n; ++p) {
+            const int32_t v = points[(size_t)r * n + p];
+            if (v < 0) return fail(MCGP_E_BAD_ARG, "a points-table entry is negative");
+            if ((uint64_t)v > kMaxPoints) return fail(MCGP_E_BAD_ARG, "a points-table entry is above 65535, the limit of a driver's total points");
+            if (v > best) best = v;
+            awarded += (uint64_t)v;
+        }
+        G += (uint64_t)best;
+    }
+    for (uint32_t d = 0; d < n; ++d) {
+        const int64_t ip = init_points ? init_points[d] : 0;
+        if (ip < 0) return fail(MCGP_E_BAD_ARG, "an initial points total is negative");
+        if ((uint64_t)ip + G > kMaxPoints)
+            return fail(MCGP_E_BAD_ARG, "a driver's total points (initial points plus the most these races award, " +
+                                            std::to_string((uint64_t)ip + G) + ") may exceed the limit of 65535");
+        for (uint32_t p = 0; p < n; ++p) {
+            const int64_t ic = init_counts ? init_counts[(size_t)d * n + p] : 0;
+            if (ic < 0) return fail(MCGP_E_BAD_ARG, "an initial countback count is negative");
+            if ((uint64_t)ic + n_cb > kMaxCount)
+                return fail(MCGP_E_BAD_ARG, "a driver's count of finishes in one position (initial count plus countback "
+                                            "races, " + std::to_string((uint64_t)ic + n_cb) + ") may exceed the limit of 31");
+        }
+    }
+    std::vector<mcgp::KParams> kps(n_races);
+    for (uint32_t r = 0; r < n_races; ++r) {
+        if (!grid_probs[r]) return fail(MCGP_E_BAD_ARG, "a grid_probs pointer of the championship is NULL");
+        const int rc = build_params(&cfgs[r], &drvs[r], grid_probs[r], n, &kps[r]);
+        if (rc != MCGP_OK) return rc;
+        if (kps[r].wide && !mcgp::reg_kernel_serves(kps[r]))
+            return fail(MCGP_E_BAD_ARG, "deviates = MCGP_DEVIATES_53 serves the problems the register kernel takes "
+                                        "(reg_kernel_serves: lap times clear of zero, overtake_delta >= 0)");
+    }
+    // ---- key layouts.  Drivers: 5-bit counts and 16-bit points (the limits checked above).  Teams: a team's count in a
+    // position grows by at most one per countback race, its points by at most what its drivers can take; the fields
+    // are as wide as those bounds need (at the limits: 10-bit counts, 21-bit points, 6 words).
+    const uint32_t words = (mcgp::kChampPointsBits + mcgp::kChampCountBits * n + 63) / 64;
+    std::vector<uint64_t> team_pts(n_teams, 0), team_cnt((size_t)n_teams * n, 0);
+    std::vector<uint32_t> team_size(n_teams, 0);
+    std::vector<uint8_t> members((size_t)n_teams * n, 0), n_members(n_teams, 0);
+    for (uint32_t d = 0; d < n; ++d) {
+        const uint32_t t = (uint32_t)team[d];
+        members[(size_t)t * n + team_size[t]++] = (uint8_t)d;
+        team_pts[t] += init_points ? (uint64_t)init_points[d] : 0;
+        for (uint32_t p = 0; p < n; ++p) team_cnt[(size_t)t * n + p] += init_counts ? (uint64_t)init_counts[(size_t)d * n + p] : 0;
+    }
+    uint64_t max_tpts = 0, max_tcnt = 0;
+    for (uint32_t t = 0; t < n_teams; ++t) {
+        n_members[t] = (uint8_t)team_size[t];
+        const uint64_t gain = std::min<uint64_t>((uint64_t)team_size[t] * G, awarded);
+        max_tpts = std::max<uint64_t>(max_tpts, team_pts[t] + gain);
+        for (uint32_t p = 0; p < n; ++p) max_tcnt = std::max<uint64_t>(max_tcnt, team_cnt[(size_t)t * n + p] + n_cb);
+    }
+    const uint32_t team_cbits = champ_bits(max_tcnt);
+    const uint32_t team_words = (champ_bits(max_tpts) + team_cbits * n + 63) / 64;
+    if (team_words > (uint32_t)mcgp::kChampMaxTeamWords) return fail(MCGP_E_BAD_ARG, "team standings too wide for a key");
+    if (n_sims == 0) return MCGP_OK;
+    // initial keys [words][n] and the key increment of each race and position [R][n][words]
+    std::vector<uint64_t> init_key((size_t)words * n, 0), add((size_t)n_races * n * words, 0);
+    std::vector<int32_t> init_pts(n, 0);
+    for (uint32_t d = 0; d < n; ++d) {
+        init_pts[d] = init_points ? init_points[d] : 0;
+        for (uint32_t w = 0; w < words; ++w) {
+            uint64_t k = mcgp::champ_piece((uint64_t)init_pts[d], mcgp::kChampCountBits * (int)n, (int)w);
+            for (uint32_t p = 0; p < n && init_counts; ++p)
+                k |= mcgp::champ_piece((uint64_t)init_counts[(size_t)d * n + p], mcgp::kChampCountBits * (int)(n - 1 - p), (int)w);
+            init_key[(size_t)w * n + d] = k;
+        }
+    }
+    for (uint32_t r = 0; r < n_races; ++r)
+        for (uint32_t p = 0; p < n; ++p)
+            for (uint32_t w = 0; w < words; ++w)
+                add[((size_t)r * n + p) * words + w] =
+                    mcgp::champ_piece((uint64_t)points[(size_t)r * n + p], mcgp::kChampCountBits * (int)n, (int)w) |
+                    (countback[r] ? mcgp::champ_piece(1, mcgp::kChampCountBits * (int)(n - 1 - p), (int)w) : 0ull);
+    const uint32_t gain_cols = (uint32_t)G + 1;
+    DeviceCtx *c = nullptr;
+    int rc = find_ctx(device, &c);
+    if (rc != MCGP_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    auto body = [&]() -> int {
+        int r = ensure_ctx_locked(device, *c);
+        if (r != MCGP_OK) return r;
+        HIP_TRY(hipSetDevice(device));
+        r = ensure_call_events(*c);
+        if (r != MCGP_OK) return r;
+        // rank kernel's LDS: the gain histogram joins the block when the block still leaves room for a second one
+        const mcgp::ChampRankLds lds_base = mcgp::champ_rank_lds(n, words, n_teams, team_words, gain_cols, false);
+        const mcgp::ChampRankLds lds_gain = mcgp::champ_rank_lds(n, words, n_teams, team_words, gain_cols, true);
+        const bool gain_in_lds = lds_gain.bytes <= c->lds_per_block / 2;
+        const uint32_t rank_lds = gain_in_lds ? lds_gain.bytes : lds_base.bytes;
+        if (rank_lds > c->lds_per_block)
+            return fail(MCGP_E_HIP, "the standings kernel needs " + std::to_string(rank_lds) + " bytes of LDS, the device offers " +
+                                        std::to_string(c->lds_per_block) + " per block");
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::champ_rank),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_lds));
+        // buffers: orders staging (shared with mcgp_run), keys of one chunk, tables and histograms; all grow-only
+        const uint64_t chunk = (uint64_t)1 << 22;
+        const uint64_t cap = n_sims < chunk ? n_sims : chunk;
+        if (cap * n > c->d_orders_bytes) {
+            if (c->d_orders) (void)hipFree(c->d_orders);
+            c->d_orders = nullptr;
+            c->d_orders_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_orders, cap * n));
+            c->d_orders_bytes = cap * n;
+        }
+        const size_t key_bytes = (size_t)words * n * cap * 8;
+        if (key_bytes > c->champ_keys_bytes) {
+            if (c->d_champ_keys) (void)hipFree(c->d_champ_keys);
+            c->d_champ_keys = nullptr;
+            c->champ_keys_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_champ_keys, key_bytes));
+            c->champ_keys_bytes = key_bytes;
+        }
+        auto up8 = [](size_t x) { return (x + 7) / 8 * 8; };
+        const size_t o_add = 0, o_init = o_add + add.size() * 8, o_mem = o_init + init_key.size() * 8;
+        const size_t o_nmem = o_mem + up8(members.size()), o_ipts = o_nmem + up8(n_teams), o_hist = o_ipts + up8(4 * n);
+        const size_t champ_cells = (size_t)n * n, team_cells = (size_t)n_teams * n_teams, gain_cells = (size_t)n * gain_cols;
+        const size_t race_cells = race_hist ? (size_t)n_races * n * n : 0;
+        const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells;
+        const size_t bytes = o_hist + hist_cells * 8;
+        if (bytes > c->champ_bytes) {
+            if (c->d_champ) (void)hipFree(c->d_champ);
+            c->d_champ = nullptr;
+            c->champ_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_champ, bytes));
+            c->champ_bytes = bytes;
+        }
+        unsigned char *d = c->d_champ;
+        unsigned long long *h = reinterpret_cast<unsigned long long *>(d + o_hist);
+        unsigned long long *h_champ = h, *h_team = h + champ_cells, *h_gain = h_team + team_cells, *h_race = h_gain + gain_cells;
+        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
+        HIP_TRY(hipMemcpyAsync(d + o_add, add.data(), add.size() * 8, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(d + o_init, init_key.data(), init_key.size() * 8, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(d + o_mem, members.data(), members.size(), hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(d + o_nmem, n_members.data(), n_teams, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(d + o_ipts, init_pts.data(), 4 * n, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemsetAsync(h, 0, hist_cells * 8, nullptr));
+        // without race_hist the race kernels count into the context's scratch histogram (not read back)
+        HIP_TRY(hipMemsetAsync(c->d_hist, 0, sizeof(unsigned long long) * n * n, nullptr));
+        const uint64_t acc_cap = (uint64_t)c->cu_count * 8;
+        uint64_t rank_per_cu = c->lds_per_block / rank_lds;
+        if (rank_per_cu > 8) rank_per_cu = 8;
+        if (rank_per_cu < 1) rank_per_cu = 1;
+        const uint64_t rank_cap = (uint64_t)c->cu_count * rank_per_cu;
+        for (uint64_t done = 0; done < n_sims; done += cap) {
+            const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
+            // chunk-outer, race-inner: every race of the chunk through mcgp_run's own launch path, its orders into the
+            // staging buffer, then folded into the keys before the next race overwrites them
+            for (uint32_t rr = 0; rr < n_races; ++rr) {
+                r = launch(*c, kps[rr], m, sim_offset + done, seeds[rr], nullptr,
+                           race_hist ? h_race + (size_t)rr * n * n : c->d_hist, c->d_orders, nullptr);
+                if (r != MCGP_OK) return r;
+                const uint64_t tiles = (m + mcgp::kChampAccBlock - 1) / mcgp::kChampAccBlock;
+                hipLaunchKernelGGL(mcgp::champ_accumulate, dim3((uint32_t)std::min(tiles, acc_cap)), dim3(mcgp::kChampAccBlock), 0,
+                                   nullptr, c->d_orders, m, n, words, cap, c->d_champ_keys,
+                                   reinterpret_cast<const uint64_t *>(d + o_add) + (size_t)rr * n * words,
+                                   reinterpret_cast<const uint64_t *>(d + o_init), rr == 0 ? 1u : 0u);
+                HIP_TRY(hipGetLastError());
+            }
+            const uint64_t tiles = (m + mcgp::kChampTile - 1) / mcgp::kChampTile;
+            hipLaunchKernelGGL(mcgp::champ_rank, dim3((uint32_t)std::min(tiles, rank_cap)), dim3(mcgp::kChampRankBlock), rank_lds,
+                               nullptr, c->d_champ_keys, m, cap, n, words, n_teams, team_words, team_cbits, d + o_mem,
+                               d + o_nmem, reinterpret_cast<const int32_t *>(d + o_ipts), gain_cols, gain_in_lds ? 1u : 0u,
+                               h_champ, h_team, h_gain);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
+        c->last_timer = kBatchTimer;
+        std::vector<unsigned long long> back(hist_cells);
+        HIP_TRY(hipMemcpy(back.data(), h, hist_cells * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < champ_cells; ++i) champ_hist[i] += back[i];
+        for (size_t i = 0; i < team_cells; ++i) team_hist[i] += back[champ_cells + i];
+        for (size_t i = 0; i < gain_cells; ++i) gain_hist[i] += back[champ_cells + team_cells + i];
+        for (size_t i = 0; i < race_cells; ++i) race_hist[i] += back[champ_cells + team_cells + gain_cells + i];
         return MCGP_OK;
     };
     return body();

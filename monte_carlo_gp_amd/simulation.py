@@ -384,6 +384,187 @@ def run_monte_carlo_batch(problems, n_simulations, device=0, set_pop=None):
     return out
 
 
+DEFAULT_POINTS = (25, 18, 15, 12, 10, 8, 6, 4, 2, 1)      # a Grand Prix, positions 1-10
+MAX_RACES = 64                                             # include/mcgp.h: mcgp_run_championship limits
+MAX_TOTAL_POINTS = 65535
+MAX_POSITION_COUNT = 31
+
+
+@dataclass
+class ChampionshipResult:
+    """What run_championship returns.  Integer histograms (counts over n_simulations):
+    champ_hist [n][n] = [driver][championship position - 1], team_hist [T][T] the same for the constructors,
+    gain_hist [n][G + 1] = [driver][points gained in these races]; race_histograms (when asked for) = one [n][n]
+    position histogram per race, what run_monte_carlo gives that race alone.  Probabilities derive from them."""
+    drivers: list
+    teams: list
+    n_simulations: int
+    champ_hist: np.ndarray
+    team_hist: np.ndarray
+    gain_hist: np.ndarray
+    initial_points: dict
+    race_histograms: list | None = None
+
+    @property
+    def title_probabilities(self) -> dict:
+        return {d: int(self.champ_hist[i, 0]) / self.n_simulations for i, d in enumerate(self.drivers)}
+
+    @property
+    def position_probabilities(self) -> dict:
+        return histogram_to_probs(self.champ_hist, self.drivers, self.n_simulations)
+
+    @property
+    def expected_points(self) -> dict:
+        """Standings carried in plus the mean points gained."""
+        g = np.arange(self.gain_hist.shape[1], dtype=np.float64)
+        return {d: self.initial_points.get(d, 0) + float(self.gain_hist[i] @ g) / self.n_simulations
+                for i, d in enumerate(self.drivers)}
+
+    @property
+    def constructor_title_probabilities(self) -> dict:
+        return {t: int(self.team_hist[i, 0]) / self.n_simulations for i, t in enumerate(self.teams)}
+
+    @property
+    def constructor_position_probabilities(self) -> dict:
+        return histogram_to_probs(self.team_hist, self.teams, self.n_simulations)
+
+
+def _standings_arrays(standings, drivers):
+    """{driver: points} or {driver: {'points': p, 'finishes': [count of P1, P2, ...]}} -> (points [n], counts [n][n])."""
+    n = len(drivers)
+    pts = np.zeros(n, np.int64)
+    counts = np.zeros((n, n), np.int64)
+    index = {d: i for i, d in enumerate(drivers)}
+    for d, v in (standings or {}).items():
+        if str(d) not in index:
+            raise ValueError(f'standings name {d!r}, who is not in the field')
+        i = index[str(d)]
+        if isinstance(v, dict):
+            pts[i] = int(v.get('points', 0))
+            fin = [int(x) for x in v.get('finishes', [])]
+            if len(fin) > n:
+                fin, extra = fin[:n], fin[n:]
+                if any(extra):
+                    raise ValueError(f'{d}: finishes list has counts past position {n}')
+            counts[i, :len(fin)] = fin
+        else:
+            pts[i] = int(v)
+    if (pts < 0).any() or (counts < 0).any():
+        raise ValueError('standings must not be negative')
+    return pts, counts
+
+
+def run_championship(races, n_simulations, *, standings=None, seed=None, sim_offset=0, device=0, set_pop=None,
+                     return_race_histograms=False) -> ChampionshipResult:
+    """Drivers' and constructors' championship over a calendar of races (include/mcgp.h: mcgp_run_championship).
+
+    `races`: a list of dicts with the keys run_monte_carlo_batch takes (`config`, `grid_probs`, `base_pace`,
+    `tire_deg`, `driver_variance`, optional `driver_dnf_rates`, `seed`, `track_condition`, `deviates`), plus `points`
+    (the table of positions 1, 2, ...; default 25-18-15-12-10-8-6-4-2-1) and `countback` (default True; False for a
+    sprint, whose results score but do not break ties).  Simulation s of the season is the tuple of what
+    run_monte_carlo gives each race alone for simulation id s under that race's seed.
+
+    The driver order is the first race's grid_probs key order; every race must have the same driver set.  Teams come
+    from the first race's config.driver_teams ('Unknown' for a driver it does not list), in order of first appearance.
+    `standings`: points before these races, {driver: points} or {driver: {'points': p, 'finishes': [P1s, P2s, ...]}}.
+    A race without `seed` gets random.Random(seed).getrandbits(63), in race order.  `device`: an index, a list of
+    indices or 'all' (simulation ids sharded over the devices, one host thread each).
+
+    Points follow the race model's classification: retired cars are classified behind the finishers (as in the
+    reference), so a retired car scores when fewer cars finish than the table pays.  Ties: more points, then more
+    wins, more seconds, ... (countback races only); a full tie goes to the lower driver (team) index -- the
+    regulations then use criteria this model does not have."""
+    races = list(races)
+    if not races:
+        raise ValueError('a championship needs at least one race')
+    if len(races) > MAX_RACES:
+        raise ValueError(f'at most {MAX_RACES} races per call, got {len(races)}')
+    set_pop = dict(set_pop or DEFAULT_SET_POP)
+    drivers = [str(d) for d in races[0]['grid_probs'].keys()]
+    n = len(drivers)
+    if not (1 <= n <= N.MAX_CARS):
+        raise ValueError(f'number of drivers must be in [1, {N.MAX_CARS}], got {n}')
+    rng = random.Random(seed)
+    probs, grids, seeds, deviates = [], [], [], []
+    points = np.zeros((len(races), n), np.int32)
+    countback = np.zeros(len(races), np.uint8)
+    for r, race in enumerate(races):
+        gp = {str(k): v for k, v in race['grid_probs'].items()}
+        if set(gp) != set(drivers) or len(gp) != n:
+            raise ValueError(f'race {r}: its drivers differ from the first race\'s')
+        probs.append(_Problem(race['config'], drivers, race['base_pace'], race['tire_deg'], race['driver_variance'],
+                              race.get('driver_dnf_rates'), race.get('track_condition', 'dry'), set_pop,
+                              race.get('deviates', 32)))
+        grids.append(RaceSimulator._grid_matrix(gp, drivers))
+        race_seed = race.get('seed')
+        seeds.append(RaceSimulator._resolve_seed(rng.getrandbits(63) if race_seed is None else race_seed))
+        table = [int(x) for x in race.get('points', DEFAULT_POINTS)]
+        if any(x < 0 for x in table):
+            raise ValueError(f'race {r}: points must not be negative')
+        points[r, :min(n, len(table))] = table[:n]           # positions past the table score 0
+        countback[r] = 1 if race.get('countback', True) else 0
+    teams_of = races[0]['config'].driver_teams
+    team_names = []
+    for d in drivers:
+        t = str(teams_of.get(d, 'Unknown'))
+        if t not in team_names:
+            team_names.append(t)
+    team = np.array([team_names.index(str(teams_of.get(d, 'Unknown'))) for d in drivers], np.int32)
+    init_pts, init_counts = _standings_arrays(standings, drivers)
+    # the limits of the device's standing keys (the library rejects the same calls with MCGP_E_BAD_ARG)
+    G = int(points.max(axis=1).sum())
+    if int(init_pts.max()) + G > MAX_TOTAL_POINTS:
+        raise ValueError(f'a driver could reach {int(init_pts.max()) + G} points: the limit is {MAX_TOTAL_POINTS}')
+    worst = int(init_counts.max()) + int(countback.sum())
+    if worst > MAX_POSITION_COUNT:
+        raise ValueError(f'a driver could have {worst} finishes in one position (standings plus countback races): '
+                         f'the limit is {MAX_POSITION_COUNT}')
+    init_pts32 = np.ascontiguousarray(init_pts, np.int32)
+    init_counts32 = np.ascontiguousarray(init_counts, np.int32)
+    T = len(team_names)
+    R = len(races)
+    n_simulations = int(n_simulations)
+    if n_simulations < 0:
+        raise ValueError('n_simulations must be >= 0')
+    devices = RaceSimulator(races[0]['config'], device=device).devices
+    lib = N.lib()
+    cfgs = (N.McgpConfig * R)(*[p.cfg for p in probs])
+    drvs = (N.McgpDrivers * R)(*[p.drv for p in probs])
+    gptrs = (C.POINTER(C.c_double) * R)(*[_dptr(g) for g in grids])
+    seeds_c = (C.c_uint64 * R)(*seeds)
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+    def run_shard(dev, offset, count):
+        ch = np.zeros((n, n), np.uint64)
+        th = np.zeros((T, T), np.uint64)
+        gh = np.zeros((n, G + 1), np.uint64)
+        rh = np.zeros((R, n, n), np.uint64) if return_race_histograms else None
+        rc = lib.mcgp_run_championship(R, cfgs, drvs, gptrs, n, int(count), int(sim_offset) + int(offset), seeds_c,
+                                       i32(points), countback.ctypes.data_as(C.POINTER(C.c_uint8)), i32(init_pts32),
+                                       i32(init_counts32), i32(team), T, int(dev), u64(ch), u64(th), u64(gh),
+                                       u64(rh) if rh is not None else None)
+        return (ch, th, gh, rh), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+    if len(devices) == 1:
+        parts = [run_shard(devices[0], 0, n_simulations)]
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        from .distributed import shard_range
+        world = len(devices)
+        shards = [shard_range(n_simulations, k, world) for k in range(world)]
+        with ThreadPoolExecutor(world) as ex:
+            parts = list(ex.map(lambda a: run_shard(a[0], *a[1]), zip(devices, shards)))
+    for _, rc, msg in parts:
+        if rc != 0:
+            raise N.McgpError(rc, msg)
+    total = lambda k: np.sum([p[0][k] for p in parts], axis=0, dtype=np.uint64).astype(np.int64)
+    return ChampionshipResult(
+        drivers=drivers, teams=team_names, n_simulations=n_simulations, champ_hist=total(0), team_hist=total(1),
+        gain_hist=total(2), initial_points={d: int(init_pts[i]) for i, d in enumerate(drivers)},
+        race_histograms=list(total(3)) if return_race_histograms else None)
+
+
 def histogram_to_probs(hist, drivers, n_simulations):
     """counts[driver][position-1] -> {driver: {position: count / n}} with zero cells omitted (:97-100)."""
     out = {}
