@@ -30,7 +30,8 @@ extern "C" {
 /* 2: mcgp_build_hash, mcgp_run_batch; the retirement draw of laps >= 2 moved to one word per driver and race, which
  * changes the results for a given seed (the oracle's Philox back-end moved with it) */
 /* 3: mcgp_run_championship */
-#define MCGP_ABI_VERSION 3
+/* 4: mcgp_run_matchups */
+#define MCGP_ABI_VERSION 4
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
 
@@ -184,6 +185,23 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
                               const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
                               uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
                               uint64_t *gain_hist, uint64_t *race_hist);
+
+/* Head-to-head and podium-combination counts of one race: mcgp_run's inputs and simulations (ids sim_offset ..
+ * sim_offset + n_sims - 1), counted on the device so that no finishing order leaves it.  "Classified" is the race model's
+ * order, which puts retired cars behind the finishers, as the reference does.
+ *   hist_out    [n][n]    [driver][position - 1] counts, equal to mcgp_run's
+ *   ahead_out   [n][n]    [i][j] = simulations in which driver i is classified ahead of driver j: the diagonal is 0 and
+ *                         ahead[i][j] + ahead[j][i] = n_sims for i != j
+ *   podium_out  [n][n][n] [a][b][c] = simulations whose first three classified cars are a, b, c in that order; NULL to
+ *                         skip (n >= 3 required otherwise); the sum over b and c is hist[a][0]
+ * All three are ACCUMULATED into (caller zeroes), and only after every launch has succeeded: on an error they are left
+ * as they were.  Arguments are checked as mcgp_run checks them, before any device lookup (MCGP_E_BAD_ARG).  The device
+ * work goes chunk by chunk (2^22 simulations) through mcgp_run's launch path into a staging buffer that a counting kernel
+ * reads; device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or devices sums to the
+ * same counts.  mcgp_last_kernel_ms afterwards = the device time of everything the call ran. */
+int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
+                          uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                          uint64_t *ahead_out, uint64_t *podium_out);
 
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver

@@ -1,13 +1,14 @@
 """MI355X-native Monte Carlo race-simulation engine (hot path of dan-lee-gh/monte-carlo-gp).
 
 Public surface mirrors reference src/simulation.py: CarState, RaceConfig, RaceSimulator; run_monte_carlo_batch runs several
-races in one launch; run_championship simulates the drivers' and constructors' standings over a calendar of races.
+races in one launch; RaceSimulator.run_matchups counts head-to-heads and podiums of one race (MatchupResult);
+run_championship simulates the drivers' and constructors' standings over a calendar of races.
 The compute path is the HIP library libmcgp_hip.so (C ABI: include/mcgp.h); there is no
 CPU fallback.
 """
-from .simulation import (CarState, ChampionshipResult, RaceConfig, RaceSimulator, histogram_to_probs,  # noqa: F401
-                         run_championship, run_monte_carlo_batch)
+from .simulation import (CarState, ChampionshipResult, MatchupResult, RaceConfig, RaceSimulator,  # noqa: F401
+                         histogram_to_probs, run_championship, run_monte_carlo_batch)
 from . import config  # noqa: F401
 
-__all__ = ['CarState', 'ChampionshipResult', 'RaceConfig', 'RaceSimulator', 'histogram_to_probs', 'run_championship',
-           'run_monte_carlo_batch', 'config']
+__all__ = ['CarState', 'ChampionshipResult', 'MatchupResult', 'RaceConfig', 'RaceSimulator', 'histogram_to_probs',
+           'run_championship', 'run_monte_carlo_batch', 'config']

@@ -9,7 +9,8 @@ Flags kept from the reference: --season, --race, --prediction-point, --simulatio
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
 simulator (the reference parses --simulations and drops it, main.py:14-15 vs predictor.py:284).
 --offline / --fixture replace the FastF1 sessions with a race fixture (see predictor.py); without
---fixture a synthetic weekend is used (SURVEY.md 8d canonical inputs) and labelled as such.
+--fixture a synthetic weekend is used (SURVEY.md 8d canonical inputs) and labelled as such.  predict --matchups also
+prints the teammate head-to-heads and the most likely podiums (counted on the device) and adds them to --json.
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
 on the data path; results are gathered once).
 """
@@ -62,7 +63,7 @@ def cmd_predict(args) -> int:
     t0 = time.perf_counter()
     res = F1Predictor(device=args.device).predict_weekend(
         args.season, args.race, fixture, prediction_point=args.prediction_point,
-        n_simulations=args.simulations, seed=args.seed)
+        n_simulations=args.simulations, seed=args.seed, matchups=args.matchups)
     dt = time.perf_counter() - t0
     print(f"Weather: {'Wet' if res['weather'].get('rainfall') else 'Dry'}")
     print(f"Confidence: {res['confidence']}   ({args.simulations / dt:,.0f} simulations/s incl. setup)\n")
@@ -71,6 +72,14 @@ def cmd_predict(args) -> int:
     _bars('RACE WINNER PROBABILITIES', res['win_probabilities'])
     print()
     _bars('PODIUM PROBABILITIES', res['podium_probabilities'])
+    if args.matchups:
+        print('\nTEAMMATE HEAD-TO-HEAD\n' + '-' * 40)
+        for b in res['teammate_battles']:
+            (a, c), (pa, pc) = b['drivers'], b['probabilities']
+            print(f"{b['team'][:16]:16} {a:4} {pa:6.1%} - {pc:6.1%} {c:4}")
+        print('\nMOST LIKELY PODIUMS\n' + '-' * 40)
+        for i, row in enumerate(res['likely_podiums'], 1):
+            print(f"{i:2}. {' - '.join(f'{d:4}' for d in row['podium'])} {row['probability']:6.2%}")
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({k: v for k, v in res.items() if k != 'full_distributions'}, f)
@@ -362,6 +371,8 @@ def main(argv=None) -> int:
     p.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
     p.add_argument('--device', type=int, default=0)
     p.add_argument('--json', type=str, default=None)
+    p.add_argument('--matchups', action='store_true',
+                   help='also count teammate head-to-heads and the most likely podiums (and add them to --json)')
     p.set_defaults(fn=cmd_predict)
     b = sub.add_parser('backtest', help='sweep a season and score it (backtest.py of the reference)')
     b.add_argument('--seasons', type=int, nargs='+', default=[2024])

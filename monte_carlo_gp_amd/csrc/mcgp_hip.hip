@@ -10,6 +10,7 @@
 #include "race_kernel.hip.h"
 #include "race_kernel_reg.hip.h"
 #include "championship.hip.h"
+#include "matchups.hip.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
 #include "frontend_exp.h"
@@ -171,11 +172,13 @@ struct DeviceCtx {
     uint32_t *d_batch_retire = nullptr;     // ... and the lanes' retirement lists
     size_t batch_retire_bytes = 0;
     hipEvent_t batch_start = nullptr, batch_stop = nullptr;     // ... and the timing events of the last batch call
-                                                                // (and of the last championship call)
+                                                                // (and of the last championship or matchups call)
     uint64_t *d_champ_keys = nullptr;       // mcgp_run_championship: standing keys of a chunk (grow-only)
     size_t champ_keys_bytes = 0;
     unsigned char *d_champ = nullptr;       // ... and its tables and histograms (grow-only)
     size_t champ_bytes = 0;
+    unsigned long long *d_match = nullptr;  // mcgp_run_matchups: its histograms (grow-only)
+    size_t match_bytes = 0;
     uint32_t last_grid = 0, last_block = 0, last_lds = 0;
     char last_kernel[48] = "";
 };
@@ -237,6 +240,9 @@ void release_ctx(DeviceCtx &c)
     c.d_champ_keys = nullptr;
     c.d_champ = nullptr;
     c.champ_keys_bytes = c.champ_bytes = 0;
+    if (c.d_match) (void)hipFree(c.d_match);
+    c.d_match = nullptr;
+    c.match_bytes = 0;
     c.batch_bytes = c.batch_retire_bytes = 0;
     for (auto &t : c.timer) {
         if (t.start) (void)hipEventDestroy(t.start);
@@ -493,8 +499,9 @@ int claim_timer(DeviceCtx &c, hipStream_t stream, int *out)
     return MCGP_OK;
 }
 
-// The pair of timing events of a call that runs several kernels (mcgp_run_batch, mcgp_run_championship): recorded on
-// the null stream around everything the call runs, so that mcgp_last_kernel_ms afterwards gives the whole call.
+// The pair of timing events of a call that runs several kernels (mcgp_run_batch, mcgp_run_championship,
+// mcgp_run_matchups): recorded on the null stream around everything the call runs, so that mcgp_last_kernel_ms
+// afterwards gives the whole call.
 int ensure_call_events(DeviceCtx &c)
 {
     if (c.batch_start) return MCGP_OK;
@@ -1320,6 +1327,106 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
         for (size_t i = 0; i < team_cells; ++i) team_hist[i] += back[champ_cells + i];
         for (size_t i = 0; i < gain_cells; ++i) gain_hist[i] += back[champ_cells + team_cells + i];
         for (size_t i = 0; i < race_cells; ++i) race_hist[i] += back[champ_cells + team_cells + gain_cells + i];
+        return MCGP_OK;
+    };
+    return body();
+}
+
+int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
+                          uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                          uint64_t *ahead_out, uint64_t *podium_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!grid_probs || !hist_out || !ahead_out) return fail(MCGP_E_BAD_ARG, "grid_probs / hist_out / ahead_out is NULL");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc != MCGP_OK) return rc;
+    if (podium_out && n < 3) return fail(MCGP_E_BAD_ARG, "podium_out needs n >= 3 (pass NULL to skip the podium counts)");
+    if (kp.wide && !mcgp::reg_kernel_serves(kp))
+        return fail(MCGP_E_BAD_ARG, "deviates = MCGP_DEVIATES_53 serves the problems the register kernel takes "
+                                    "(reg_kernel_serves: lap times clear of zero, overtake_delta >= 0)");
+    if (n_sims == 0) return MCGP_OK;
+    DeviceCtx *c = nullptr;
+    rc = find_ctx(device, &c);
+    if (rc != MCGP_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    auto body = [&]() -> int {
+        int r = ensure_ctx_locked(device, *c);
+        if (r != MCGP_OK) return r;
+        HIP_TRY(hipSetDevice(device));
+        r = ensure_call_events(*c);
+        if (r != MCGP_OK) return r;
+        // block shape: the widest block whose LDS fits the device's budget, with the podium table in LDS if any block
+        // can hold it, else with the podium counted by global atomics.  MCGP_LDS_PER_BLOCK (a device that offers less)
+        // is read per call here, so that a test reaches the global-atomic path in a process whose context exists.
+        size_t budget = c->lds_per_block;
+        if (const char *e = std::getenv("MCGP_LDS_PER_BLOCK")) {
+            const unsigned long long v = std::strtoull(e, nullptr, 10);
+            if (v >= 16384 && v < budget) budget = (size_t)v;
+        }
+        uint32_t mode = podium_out ? mcgp::kPodiumLds : mcgp::kPodiumNone, block = 0;
+        auto widest = [&](bool podium_in_lds) -> uint32_t {
+            for (uint32_t b = mcgp::kMatchMaxBlock; b >= 64; b /= 2)
+                if (mcgp::match_lds(n, b, podium_in_lds).bytes <= budget) return b;
+            return 0;
+        };
+        block = widest(mode == mcgp::kPodiumLds);
+        if (!block && mode == mcgp::kPodiumLds) {
+            mode = mcgp::kPodiumGlobal;
+            block = widest(false);
+        }
+        if (!block)
+            return fail(MCGP_E_HIP, "the matchups kernel needs " + std::to_string(mcgp::match_lds(n, 64, false).bytes) +
+                                        " bytes of LDS, the device offers " + std::to_string(budget) + " per block");
+        const uint32_t lds = mcgp::match_lds(n, block, mode == mcgp::kPodiumLds).bytes;
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_matchups),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        // buffers: the orders staging of mcgp_run (one chunk), and hist | ahead | podium; both grow-only
+        const uint64_t chunk = mcgp::kMatchMaxSims;
+        const uint64_t cap = n_sims < chunk ? n_sims : chunk;
+        if (cap * n > c->d_orders_bytes) {
+            if (c->d_orders) (void)hipFree(c->d_orders);
+            c->d_orders = nullptr;
+            c->d_orders_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_orders, cap * n));
+            c->d_orders_bytes = cap * n;
+        }
+        const size_t pair_cells = (size_t)n * n, podium_cells = podium_out ? (size_t)n * n * n : 0;
+        const size_t cells = 2 * pair_cells + podium_cells;
+        if (cells * 8 > c->match_bytes) {
+            if (c->d_match) (void)hipFree(c->d_match);
+            c->d_match = nullptr;
+            c->match_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_match, cells * 8));
+            c->match_bytes = cells * 8;
+        }
+        unsigned long long *h_hist = c->d_match, *h_ahead = h_hist + pair_cells, *h_podium = h_ahead + pair_cells;
+        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
+        HIP_TRY(hipMemsetAsync(c->d_match, 0, cells * 8, nullptr));
+        uint64_t per_cu = budget / lds;
+        if (per_cu > 8) per_cu = 8;
+        if (per_cu < 1) per_cu = 1;
+        const uint64_t grid_cap = (uint64_t)c->cu_count * per_cu;
+        for (uint64_t done = 0; done < n_sims; done += cap) {
+            const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
+            // the chunk's race through mcgp_run's own launch path (the position histogram is counted there), its
+            // orders into the staging buffer, then counted before the next chunk overwrites them
+            r = launch(*c, kp, m, sim_offset + done, seed, nullptr, h_hist, c->d_orders, nullptr);
+            if (r != MCGP_OK) return r;
+            const uint64_t tiles = (m + block - 1) / block;
+            hipLaunchKernelGGL(mcgp::race_matchups, dim3((uint32_t)std::min(tiles, grid_cap)), dim3(block), lds, nullptr,
+                               c->d_orders, m, n, mode, h_ahead, podium_out ? h_podium : nullptr);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
+        c->last_timer = kBatchTimer;
+        // the caller's buffers are added into only once everything has run
+        std::vector<unsigned long long> back(cells);
+        HIP_TRY(hipMemcpy(back.data(), c->d_match, cells * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < pair_cells; ++i) hist_out[i] += back[i];
+        for (size_t i = 0; i < pair_cells; ++i) ahead_out[i] += back[pair_cells + i];
+        for (size_t i = 0; i < podium_cells; ++i) podium_out[i] += back[2 * pair_cells + i];
         return MCGP_OK;
     };
     return body();

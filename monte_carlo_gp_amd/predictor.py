@@ -171,8 +171,13 @@ class F1Predictor:
 
     def predict_weekend(self, season: int, race: str, fixture: dict | str, grid_penalties=None, circuit_info=None,
                         prediction_point: str = 'fp2', actual_grid=None, n_simulations: int = 10000,
-                        seed: int | None = None) -> dict:
-        """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU."""
+                        seed: int | None = None, matchups: bool = False) -> dict:
+        """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU.
+
+        matchups=True (not in the reference): the race runs through RaceSimulator.run_matchups -- the same simulations,
+        so every key keeps its value -- and the result gains 'head_to_head' ({a: {b: P(a ahead of b)}}),
+        'teammate_battles' (MatchupResult.teammate_battles over the race config's teams) and 'likely_podiums' (the
+        MATCHUP_PODIUMS most likely ordered podiums, [{'podium': [P1, P2, P3], 'probability': p}])."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -183,16 +188,45 @@ class F1Predictor:
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
             # same inputs, the matrix built on the device from the ratings (no host matrix crosses PCIe)
             ratings = {d: self.elo_system.ratings.get(d, {}).get('quali', self.elo_system.initial) for d in inp['drivers']}
+            if matchups:
+                # the same matrix, read back from the device front end and handed to the matchups run
+                grid = sim.grid_probs_on_device(inp['drivers'], ratings, fixture.get('quali_features', {}),
+                                                grid_penalties or {})
+                return self._with_matchups(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid)
             race_probs, grid = sim.run_from_ratings(
                 n_simulations, inp['drivers'], ratings, fixture.get('quali_features', {}), grid_penalties or {},
                 inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'], seed=seed,
                 track_condition=inp['track_condition'])
             return pack_result(inp['drivers'], grid, race_probs, inp['weather'], prediction_point, actual_grid)
+        if matchups:
+            return self._with_matchups(sim, inp, inp['grid_probs'], n_simulations, seed, prediction_point, actual_grid)
         race_probs = sim.run_monte_carlo(
             n_simulations=n_simulations, grid_probs=inp['grid_probs'], base_pace=inp['base_pace'],
             tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
             driver_dnf_rates=inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'])
         return pack_result(inp['drivers'], inp['grid_probs'], race_probs, inp['weather'], prediction_point, actual_grid)
+
+    @staticmethod
+    def _with_matchups(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid) -> dict:
+        """predict_weekend's result from a run_matchups call on `grid`, with the matchup keys added."""
+        m = sim.run_matchups(n_simulations, grid, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
+                             inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'])
+        res = pack_result(inp['drivers'], grid, m.position_probabilities, inp['weather'], prediction_point, actual_grid)
+        res.update(matchup_keys(m, inp['config'].driver_teams))
+        return res
+
+
+MATCHUP_PODIUMS = 10         # ordered podiums listed by predict_weekend(matchups=True)
+
+
+def matchup_keys(m, driver_teams) -> dict:
+    """The keys predict_weekend(matchups=True) adds, JSON-safe, from a MatchupResult."""
+    podiums = m.most_likely_podiums(MATCHUP_PODIUMS) if m.podium is not None else []
+    return {
+        'head_to_head': m.ahead_probabilities,
+        'teammate_battles': m.teammate_battles(driver_teams),
+        'likely_podiums': [{'podium': list(p), 'probability': q} for p, q in podiums],
+    }
 
 
 def pack_result(drivers, quali_probs, race_probs, weather, prediction_point, actual_grid) -> dict:

@@ -6,6 +6,7 @@ Mirrors the reference's interface for the hot path (reference src/simulation.py)
     RaceSimulator(config)                        :55-57
     RaceSimulator.run_monte_carlo(...)           :59-100  same arguments, same result shape
     RaceSimulator.simulate_race(grid, ...)       :147-242 one race, list of (driver, position)
+    RaceSimulator.run_matchups(...)              (not in the reference) head-to-head and podium counts of one race
 
 The per-lap loop itself runs in hand-written HIP (csrc/race_kernel_reg.hip.h) behind
 the C ABI of include/mcgp.h; this module only resolves the reference's dict
@@ -190,6 +191,23 @@ class RaceSimulator:
             seed = -seed                     # random.seed() uses abs(seed)
         return seed & 0xFFFFFFFFFFFFFFFF
 
+    def _run_sharded(self, run_shard, n_simulations):
+        """run_shard(device, offset, count) -> (result, rc, message) over self.devices: contiguous shards of the
+        simulation ids, one host thread per device.  Raises on the first failed shard; returns the shards' results."""
+        if len(self.devices) == 1:
+            parts = [run_shard(self.devices[0], 0, int(n_simulations))]
+        else:
+            from concurrent.futures import ThreadPoolExecutor
+            from .distributed import shard_range
+            world = len(self.devices)
+            shards = [shard_range(int(n_simulations), k, world) for k in range(world)]
+            with ThreadPoolExecutor(world) as ex:          # ctypes releases the GIL for the duration of the call
+                parts = list(ex.map(lambda a: run_shard(a[0], *a[1]), zip(self.devices, shards)))
+        for _, rc, msg in parts:
+            if rc != 0:
+                raise N.McgpError(rc, msg)
+        return parts
+
     def _problem(self, drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition):
         n = len(drivers)
         if n < 1 or n > N.MAX_CARS:
@@ -238,23 +256,60 @@ class RaceSimulator:
             # (mcgp_last_error is thread-local: read it on the thread that made the call)
             return h, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
 
-        if len(self.devices) == 1:
-            parts = [run_shard(self.devices[0], 0, int(n_simulations))]
-        else:
-            from concurrent.futures import ThreadPoolExecutor
-            from .distributed import shard_range
-            world = len(self.devices)
-            shards = [shard_range(int(n_simulations), k, world) for k in range(world)]
-            with ThreadPoolExecutor(world) as ex:          # ctypes releases the GIL for the duration of the call
-                parts = list(ex.map(lambda a: run_shard(a[0], *a[1]), zip(self.devices, shards)))
-        for _, rc, msg in parts:
-            if rc != 0:
-                raise N.McgpError(rc, msg)
+        parts = self._run_sharded(run_shard, n_simulations)
         hist = np.sum([h for h, _, _ in parts], axis=0, dtype=np.uint64)
         self.last_histogram = hist.astype(np.int64)
         self.last_drivers = drivers
         result = histogram_to_probs(self.last_histogram, drivers, n_simulations)
         return (result, orders) if return_orders else result
+
+    def run_matchups(
+        self,
+        n_simulations: int,
+        grid_probs: dict,
+        base_pace: dict,
+        tire_deg: dict,
+        driver_variance: dict,
+        driver_dnf_rates: dict | None = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        podiums: bool = True,
+    ) -> 'MatchupResult':
+        """run_monte_carlo's race, counted for pairs and podiums on the device (include/mcgp.h: mcgp_run_matchups).
+
+        Same arguments, simulations and sharding over self.devices as run_monte_carlo; returns a MatchupResult whose
+        position histogram equals run_monte_carlo's, plus head-to-head counts and (podiums=True, at least 3 drivers) the
+        counts of every ordered podium.  No finishing order leaves the device.  Sets last_histogram / last_drivers."""
+        drivers = [str(d) for d in grid_probs.keys()]
+        n = len(drivers)
+        n_simulations = int(n_simulations)
+        want_podium = bool(podiums) and n >= 3
+        if not drivers or n_simulations <= 0:
+            z = np.zeros((n, n), np.int64)
+            self.last_histogram, self.last_drivers = z, drivers
+            return MatchupResult(drivers=drivers, n_simulations=max(n_simulations, 0), hist=z, ahead=z.copy(),
+                                 podium=np.zeros((n, n, n), np.int64) if want_podium else None)
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers)
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            h, a = np.zeros((n, n), np.uint64), np.zeros((n, n), np.uint64)
+            p = np.zeros((n, n, n), np.uint64) if want_podium else None
+            rc = lib.mcgp_run_matchups(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g), n, int(count),
+                                       int(sim_offset) + int(offset), seed64, device, u64(h), u64(a),
+                                       u64(p) if want_podium else None)
+            return (h, a, p), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([r[k] for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        self.last_histogram = total(0)
+        self.last_drivers = drivers
+        return MatchupResult(drivers=drivers, n_simulations=n_simulations, hist=self.last_histogram, ahead=total(1),
+                             podium=total(2) if want_podium else None)
 
     def simulate_race(
         self,
@@ -382,6 +437,71 @@ def run_monte_carlo_batch(problems, n_simulations, device=0, set_pop=None):
             h = hist[j].astype(np.int64)
             out[i] = (histogram_to_probs(h, prepared[i][0].drivers, n_simulations), h)
     return out
+
+
+@dataclass
+class MatchupResult:
+    """What RaceSimulator.run_matchups returns.  Integer counts over n_simulations: hist [n][n] = [driver][position - 1]
+    (run_monte_carlo's histogram), ahead [n][n] = [i][j] simulations in which driver i is classified ahead of driver j,
+    podium [n][n][n] = [a][b][c] simulations whose first three classified cars are a, b, c in that order (None when not
+    asked for or with fewer than 3 drivers).  Classified: the race model's order, which puts retired cars behind the
+    finishers, as the reference does; a pair whose cars both retire counts in that order too."""
+    drivers: list
+    n_simulations: int
+    hist: np.ndarray
+    ahead: np.ndarray
+    podium: np.ndarray | None = None
+
+    @property
+    def position_probabilities(self) -> dict:
+        """{driver: {position: probability}}, what run_monte_carlo returns for the same arguments."""
+        return histogram_to_probs(self.hist, self.drivers, self.n_simulations)
+
+    def head_to_head(self, a, b) -> float:
+        """P(driver a classified ahead of driver b)."""
+        i, j = self.drivers.index(str(a)), self.drivers.index(str(b))
+        return int(self.ahead[i, j]) / self.n_simulations if self.n_simulations else 0.0
+
+    @property
+    def ahead_probabilities(self) -> dict:
+        """{a: {b: P(a ahead of b)}} for every ordered pair of distinct drivers."""
+        n = max(self.n_simulations, 1)
+        return {a: {b: int(self.ahead[i, j]) / n for j, b in enumerate(self.drivers) if j != i}
+                for i, a in enumerate(self.drivers)}
+
+    def teammate_battles(self, driver_teams: dict) -> list:
+        """Every pair of drivers of one team (driver_teams: {driver: team}; drivers it does not list have no team), in
+        field order: [{'team', 'drivers': [a, b], 'probabilities': [P(a ahead), P(b ahead)]}]."""
+        out = []
+        for i, a in enumerate(self.drivers):
+            for b in self.drivers[i + 1:]:
+                team = driver_teams.get(a)
+                if team is not None and driver_teams.get(b) == team:
+                    p = self.head_to_head(a, b)
+                    out.append({'team': team, 'drivers': [a, b], 'probabilities': [p, self.head_to_head(b, a)]})
+        return out
+
+    def podium_set_probabilities(self) -> dict:
+        """{frozenset of three drivers: P(those three make the podium, in any order)}, non-zero sets only."""
+        self._need_podium()
+        out = {}
+        for a, b, c in zip(*np.nonzero(self.podium)):
+            key = frozenset((self.drivers[a], self.drivers[b], self.drivers[c]))
+            out[key] = out.get(key, 0) + int(self.podium[a, b, c])
+        return {k: v / self.n_simulations for k, v in out.items()}
+
+    def most_likely_podiums(self, k: int = 10) -> list:
+        """The k most likely ordered podiums: [((P1, P2, P3), probability)], most likely first (ties in cell order)."""
+        self._need_podium()
+        flat = self.podium.ravel()
+        nz = np.nonzero(flat)[0]
+        top = nz[np.argsort(-flat[nz], kind='stable')][:max(int(k), 0)]
+        n, d = len(self.drivers), self.drivers
+        return [((d[c // (n * n)], d[c // n % n], d[c % n]), int(flat[c]) / self.n_simulations) for c in top]
+
+    def _need_podium(self):
+        if self.podium is None:
+            raise ValueError('no podium counts: run_matchups(podiums=True) with at least 3 drivers')
 
 
 DEFAULT_POINTS = (25, 18, 15, 12, 10, 8, 6, 4, 2, 1)      # a Grand Prix, positions 1-10
