@@ -31,7 +31,8 @@ extern "C" {
  * changes the results for a given seed (the oracle's Philox back-end moved with it) */
 /* 3: mcgp_run_championship */
 /* 4: mcgp_run_matchups */
-#define MCGP_ABI_VERSION 4
+/* 5: mcgp_race_state, mcgp_run_from_state */
+#define MCGP_ABI_VERSION 5
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
 
@@ -202,6 +203,47 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
 int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
                           uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                           uint64_t *ahead_out, uint64_t *podium_out);
+
+/* A race after lap `lap` (laps completed), as the race model leaves it at the end of that lap; per-car arrays in
+ * driver-index order (the mcgp_drivers order). */
+typedef struct mcgp_race_state {
+    int32_t lap;                      /* laps completed, 1 .. total_laps */
+    int32_t drs_disabled_until;       /* 0 .. total_laps + 2: lap + 2 after a red flag or safety car, lap + 1 after a
+                                       * VSC (reference simulate_race's variable; 0 if no event has happened) */
+    const double *cumulative_time;    /* [n], finite */
+    const double *last_lap_time;      /* [n], finite */
+    const uint8_t *grid_slot;         /* [n], permutation of 0..n-1 */
+    const uint8_t *compound;          /* [n], MCGP_SOFT .. MCGP_WET */
+    const uint8_t *used_compounds;    /* [n], bit c = compound c used; must contain `compound` */
+    const int16_t *tire_age;          /* [n], 0 .. 1023 - (total_laps - lap) (the age field's width) */
+    const int16_t *retired_lap;       /* [n], 0 = running, else 1 .. lap */
+} mcgp_race_state;
+
+/* In-race odds: the rest of a race from n_states mid-race states of the same n drivers.  Simulation i of state s (ids
+ * sim_offsets[s] .. sim_offsets[s] + n_sims - 1; sim_offsets NULL: 0 for every state) runs laps lap + 1 .. total_laps
+ * with the draws mcgp_run's simulation i makes on those laps:
+ *   - the field order is rebuilt from the state: all cars, retired ones included, by (cumulative time, grid slot); DRS
+ *     and dirty air as the end of lap `lap` sets them (DRS only if lap > 2 and lap > drs_disabled_until); fuel from
+ *     the lap number;
+ *   - a running car retires on the lap its once-per-race draw gives, if that lap is after `lap` (or never); a draw of
+ *     an earlier lap contradicts the state and is redrawn from a second word with the per-lap chain shifted to start at
+ *     lap + 1, so that P(retire on lap + j | running) is the per-lap probability chain again;
+ *   - classification as mcgp_run's.
+ * So a state the race model itself produced for simulation i continues bit for bit into mcgp_run's finishing order of
+ * simulation i; giving every state the same ids gives common random numbers (a "pit now / stay out" comparison sees
+ * the same futures).
+ *   hist_out    [n_states][n][n] [state][driver][position - 1] counts, ACCUMULATED into only after every launch has
+ *               succeeded
+ *   orders_out  [n_states][n_sims][n] driver index classified p-th, or NULL
+ * Every argument is checked before any device lookup: a field outside the limits above, n_states outside [1, 4096],
+ * deviates other than MCGP_DEVIATES_32 (the resumed runs have no 53-bit path), a NULL pointer or a non-finite time is
+ * MCGP_E_BAD_ARG with a message that names the field and the state.  n_sims == 0 succeeds without a device.  Runs on
+ * the generic LDS kernel (mcgp::race_resume_kernel); orders are staged in chunks (at most 2^22 n bytes on the device),
+ * a state's runs are split at 2^32 simulations per launch.  Host buffers in and out, blocking.  mcgp_last_kernel_ms
+ * afterwards = the device time of everything the call ran. */
+int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uint32_t n, uint32_t n_states,
+                            const mcgp_race_state *states, uint64_t n_sims, const uint64_t *sim_offsets, uint64_t seed,
+                            int32_t device, uint64_t *hist_out, uint8_t *orders_out);
 
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver

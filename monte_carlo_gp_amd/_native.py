@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_PKG, 'libmcgp_hip.so')
 
 MAX_CARS = 32
 MAX_LAPS = 1000
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 COMPOUNDS = ('SOFT', 'MEDIUM', 'HARD', 'INTERMEDIATE', 'WET')
 COMPOUND_ID = {c: i for i, c in enumerate(COMPOUNDS)}
@@ -43,6 +43,17 @@ class McgpConfig(C.Structure):
 class McgpDrivers(C.Structure):
     _fields_ = [(k, C.POINTER(C.c_double)) for k in
                 ('base_pace', 'tire_deg', 'tire_deg_pit', 'variance', 'team_dnf', 'lap_dnf')]
+
+
+class McgpRaceState(C.Structure):
+    """mcgp_race_state: a race after `lap` laps; per-car arrays in driver-index order."""
+    _fields_ = [
+        ('lap', C.c_int32), ('drs_disabled_until', C.c_int32),
+        ('cumulative_time', C.POINTER(C.c_double)), ('last_lap_time', C.POINTER(C.c_double)),
+        ('grid_slot', C.POINTER(C.c_uint8)), ('compound', C.POINTER(C.c_uint8)),
+        ('used_compounds', C.POINTER(C.c_uint8)),
+        ('tire_age', C.POINTER(C.c_int16)), ('retired_lap', C.POINTER(C.c_int16)),
+    ]
 
 
 _hash_module = None
@@ -213,7 +224,8 @@ _lib = None
 EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device_count', 'mcgp_last_error', 'mcgp_run', 'mcgp_run_device',
            'mcgp_simulate_race', 'mcgp_grid_probs', 'mcgp_run_from_ratings', 'mcgp_last_kernel_ms',
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
-           'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups')
+           'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
+           'mcgp_run_from_state')
 
 
 def lib():
@@ -280,6 +292,11 @@ def lib():
             L.mcgp_run_matchups.restype = C.c_int32
             L.mcgp_run_matchups.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.c_uint32, C.c_uint64,
                                             C.c_uint64, C.c_uint64, C.c_int32, u64p, u64p, u64p]
+        if 'mcgp_run_from_state' not in missing:
+            L.mcgp_run_from_state.restype = C.c_int32
+            L.mcgp_run_from_state.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.c_uint32, C.c_uint32,
+                                              C.POINTER(McgpRaceState), C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64,
+                                              C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]
         L.mcgp_last_kernel_ms.restype = C.c_int32
         L.mcgp_last_kernel_ms.argtypes = [C.c_int32, C.POINTER(C.c_float)]
         if 'mcgp_stream_kernel_ms' not in missing:

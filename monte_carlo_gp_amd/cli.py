@@ -4,6 +4,7 @@
     python -m monte_carlo_gp_amd.cli backtest --seasons 2024 --seed 42 --simulations 10000000 [--fixtures DIR]
     python -m monte_carlo_gp_amd.cli export-fixtures --seasons 2024 --out DIR
     python -m monte_carlo_gp_amd.cli championship --season 2024 --from-round 18 --simulations 10000000 --seed 7
+    python -m monte_carlo_gp_amd.cli in-race --race Bahrain --season 2024 --offline --state lap30.json --simulations 1000000
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -11,6 +12,8 @@ simulator (the reference parses --simulations and drops it, main.py:14-15 vs pre
 --offline / --fixture replace the FastF1 sessions with a race fixture (see predictor.py); without
 --fixture a synthetic weekend is used (SURVEY.md 8d canonical inputs) and labelled as such.  predict --matchups also
 prints the teammate head-to-heads and the most likely podiums (counted on the device) and adds them to --json.
+in-race runs the rest of the race from one or more mid-race state files (RaceState JSON, simulation.py); with several
+--state files every state sees the same random futures and the columns compare the scenarios.
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
 on the data path; results are gathered once).
 """
@@ -83,6 +86,42 @@ def cmd_predict(args) -> int:
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({k: v for k, v in res.items() if k != 'full_distributions'}, f)
+    return 0
+
+
+def cmd_in_race(args) -> int:
+    from .simulation import RaceState
+    fixture = synthetic_fixture()
+    if args.fixture:
+        with open(args.fixture) as f:
+            fixture = json.load(f)
+    elif not args.offline:
+        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+        return 2
+    states = []
+    for path in args.state:
+        with open(path) as f:
+            states.append(RaceState.from_json(json.load(f)))
+    print(f"\n{'=' * 60}\nF1 In-Race Prediction: {args.season} {args.race}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}")
+    for i, (path, st) in enumerate(zip(args.state, states)):
+        print(f"State {i + 1}: {path} (after lap {st.lap})")
+    print('=' * 60 + '\n')
+    res = F1Predictor(device=args.device).predict_from_state(args.season, args.race, fixture, states,
+                                                             n_simulations=args.simulations, seed=args.seed)
+    drivers = list(res[0]['win_probabilities'])
+    for title, key in (('RACE WINNER PROBABILITIES', 'win_probabilities'), ('PODIUM PROBABILITIES', 'podium_probabilities')):
+        print(title)
+        print('-' * (6 + 9 * len(res)))
+        print('      ' + ''.join(f"{'S' + str(i + 1):>9}" for i in range(len(res))))
+        for d in sorted(drivers, key=lambda d: res[0][key][d], reverse=True)[:10]:
+            print(f"{d:4}  " + ''.join(f"{r[key][d]:9.1%}" for r in res))
+        print()
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump([dict({k: v for k, v in r.items() if k != 'full_distributions'}, state=path)
+                       for r, path in zip(res, args.state)], f)
     return 0
 
 
@@ -398,6 +437,18 @@ def main(argv=None) -> int:
     c.add_argument('--device', type=int, default=0)
     c.add_argument('--json', type=str, default=None)
     c.set_defaults(fn=cmd_championship)
+    r = sub.add_parser('in-race', help='win and podium odds from a mid-race state (one column per --state)')
+    r.add_argument('--season', type=int, default=2025)
+    r.add_argument('--race', type=str, required=True)
+    r.add_argument('--state', type=str, action='append', required=True,
+                   help='race state JSON (RaceState.to_json); repeat for scenarios run with common random numbers')
+    r.add_argument('--simulations', type=int, default=100000)
+    r.add_argument('--seed', type=int, default=None)
+    r.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
+    r.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
+    r.add_argument('--device', type=int, default=0)
+    r.add_argument('--json', type=str, default=None)
+    r.set_defaults(fn=cmd_in_race)
     args = ap.parse_args(argv)
     return args.fn(args)
 

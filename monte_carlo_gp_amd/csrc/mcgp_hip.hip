@@ -11,6 +11,7 @@
 #include "race_kernel_reg.hip.h"
 #include "championship.hip.h"
 #include "matchups.hip.h"
+#include "resume.hip.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
 #include "frontend_exp.h"
@@ -179,6 +180,8 @@ struct DeviceCtx {
     size_t champ_bytes = 0;
     unsigned long long *d_match = nullptr;  // mcgp_run_matchups: its histograms (grow-only)
     size_t match_bytes = 0;
+    unsigned char *d_resume = nullptr;      // mcgp_run_from_state: parameter block, states, histograms (grow-only)
+    size_t resume_bytes = 0;
     uint32_t last_grid = 0, last_block = 0, last_lds = 0;
     char last_kernel[48] = "";
 };
@@ -243,6 +246,9 @@ void release_ctx(DeviceCtx &c)
     if (c.d_match) (void)hipFree(c.d_match);
     c.d_match = nullptr;
     c.match_bytes = 0;
+    if (c.d_resume) (void)hipFree(c.d_resume);
+    c.d_resume = nullptr;
+    c.resume_bytes = 0;
     c.batch_bytes = c.batch_retire_bytes = 0;
     for (auto &t : c.timer) {
         if (t.start) (void)hipEventDestroy(t.start);
@@ -282,6 +288,8 @@ int init_ctx_body(int device, DeviceCtx &c)
     HIP_TRY(hipMalloc(&c.d_norm53, sizeof(mcgp_normal53_table_bits)));
     HIP_TRY(hipMemcpy(c.d_norm53, mcgp_normal53_table_bits, sizeof(mcgp_normal53_table_bits), hipMemcpyHostToDevice));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_resume_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
     // (the register kernels raise their dynamic-LDS limit when they are selected: launch())
     return MCGP_OK;
@@ -690,6 +698,51 @@ int launch(DeviceCtx &c, const mcgp::KParams &kp, uint64_t n_sims, uint64_t sim_
     else if (is_reg) std::snprintf(c.last_kernel, sizeof(c.last_kernel), "mcgp::race_kernel_reg<%d>", kp.n);
     else std::snprintf(c.last_kernel, sizeof(c.last_kernel), "mcgp::race_kernel");
     return MCGP_OK;
+}
+
+// One mcgp_race_state in the resume kernel's encoding, checked against the limits of include/mcgp.h; "" if it passes,
+// else the message (naming the field and state `si`).
+std::string pack_race_state(const mcgp_race_state &rs, uint32_t si, uint32_t n, int total_laps,
+                                   mcgp::ResumeState *out)
+{
+    const std::string at = "state " + std::to_string(si) + ": ";
+    if (rs.lap < 1 || rs.lap > total_laps) return at + "lap must be in [1, total_laps]";
+    if (rs.drs_disabled_until < 0 || rs.drs_disabled_until > total_laps + 2)
+        return at + "drs_disabled_until must be in [0, total_laps + 2]";
+    if (!rs.cumulative_time) return at + "cumulative_time is NULL";
+    if (!rs.last_lap_time) return at + "last_lap_time is NULL";
+    if (!rs.grid_slot) return at + "grid_slot is NULL";
+    if (!rs.compound) return at + "compound is NULL";
+    if (!rs.used_compounds) return at + "used_compounds is NULL";
+    if (!rs.tire_age) return at + "tire_age is NULL";
+    if (!rs.retired_lap) return at + "retired_lap is NULL";
+    const int max_age = (int)mcgp::kAgeMask - (total_laps - rs.lap);
+    uint32_t seen = 0;
+    std::memset(out, 0, sizeof(*out));
+    for (uint32_t d = 0; d < n; ++d) {
+        const std::string car = at + "car " + std::to_string(d) + ": ";
+        if (!std::isfinite(rs.cumulative_time[d])) return car + "cumulative_time is not finite";
+        if (!std::isfinite(rs.last_lap_time[d])) return car + "last_lap_time is not finite";
+        const uint32_t g = rs.grid_slot[d];
+        if (g >= n || ((seen >> g) & 1u)) return car + "grid_slot is not a permutation of 0..n-1";
+        seen |= 1u << g;
+        const uint32_t comp = rs.compound[d];
+        if (comp > MCGP_WET) return car + "compound must be in [MCGP_SOFT, MCGP_WET]";
+        const uint32_t used = rs.used_compounds[d];
+        if (used > 31u || !((used >> comp) & 1u)) return car + "used_compounds must be a subset of the 5 compounds that contains compound";
+        const int age = rs.tire_age[d];
+        if (age < 0 || age > max_age) return car + "tire_age must be in [0, 1023 - (total_laps - lap)]";
+        const int ret = rs.retired_lap[d];
+        if (ret < 0 || ret > rs.lap) return car + "retired_lap must be in [0, lap]";
+        uint32_t pk = (comp << mcgp::kCompShift) | (used << mcgp::kUsedShift) | (g << mcgp::kGposShift);
+        pk |= ret ? (mcgp::kDnf | (uint32_t)ret) : (uint32_t)age;       // a retired car's age field holds its lap
+        out->cum[d] = rs.cumulative_time[d];
+        out->last[d] = rs.last_lap_time[d];
+        out->pk[d] = pk;
+    }
+    out->lap = rs.lap;
+    out->drs_disabled_until = rs.drs_disabled_until;
+    return "";
 }
 
 }  // namespace
@@ -1427,6 +1480,104 @@ int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const
         for (size_t i = 0; i < pair_cells; ++i) hist_out[i] += back[i];
         for (size_t i = 0; i < pair_cells; ++i) ahead_out[i] += back[pair_cells + i];
         for (size_t i = 0; i < podium_cells; ++i) podium_out[i] += back[2 * pair_cells + i];
+        return MCGP_OK;
+    };
+    return body();
+}
+
+int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uint32_t n, uint32_t n_states,
+                            const mcgp_race_state *states, uint64_t n_sims, const uint64_t *sim_offsets, uint64_t seed,
+                            int32_t device, uint64_t *hist_out, uint8_t *orders_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+    if (!states) return fail(MCGP_E_BAD_ARG, "states is NULL");
+    if (n_states < 1 || n_states > mcgp::kMaxResumeStates) return fail(MCGP_E_BAD_ARG, "n_states must be in [1, 4096]");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, nullptr, n, &kp);
+    if (rc != MCGP_OK) return rc;
+    if (cfg->deviates != MCGP_DEVIATES_32)
+        return fail(MCGP_E_BAD_ARG, "deviates: a resumed race runs at MCGP_DEVIATES_32 only (the generic kernel has no "
+                                    "53-bit path)");
+    std::vector<mcgp::ResumeState> st(n_states);
+    for (uint32_t si = 0; si < n_states; ++si) {
+        const std::string err = pack_race_state(states[si], si, n, cfg->total_laps, &st[si]);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+        st[si].sim_offset = sim_offsets ? sim_offsets[si] : 0;
+    }
+    if (n_sims == 0) return MCGP_OK;
+    DeviceCtx *c = nullptr;
+    rc = find_ctx(device, &c);
+    if (rc != MCGP_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    auto body = [&]() -> int {
+        int r = ensure_ctx_locked(device, *c);
+        if (r != MCGP_OK) return r;
+        HIP_TRY(hipSetDevice(device));
+        r = ensure_call_events(*c);
+        if (r != MCGP_OK) return r;
+        // simulations per launch: at most max_sims_per_launch() per state (u32 block counts), and with orders at most
+        // 2^22 over all states (the staging buffer of mcgp_run: 2^22 n bytes)
+        uint64_t chunk = max_sims_per_launch();
+        if (orders_out) chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, (1u << 22) / n_states));
+        const uint64_t cap = n_sims < chunk ? n_sims : chunk;
+        if (orders_out && (size_t)n_states * cap * n > c->d_orders_bytes) {
+            if (c->d_orders) (void)hipFree(c->d_orders);
+            c->d_orders = nullptr;
+            c->d_orders_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_orders, (size_t)n_states * cap * n));
+            c->d_orders_bytes = (size_t)n_states * cap * n;
+        }
+        // device buffer: parameter block | states | histograms
+        const size_t o_st = (sizeof(mcgp::KParams) + 255) / 256 * 256;
+        const size_t o_hist = o_st + (sizeof(mcgp::ResumeState) * n_states + 255) / 256 * 256;
+        const size_t cells = (size_t)n_states * n * n;
+        const size_t bytes = o_hist + cells * 8;
+        if (bytes > c->resume_bytes) {
+            if (c->d_resume) (void)hipFree(c->d_resume);
+            c->d_resume = nullptr;
+            c->resume_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_resume, bytes));
+            c->resume_bytes = bytes;
+        }
+        const mcgp::KParams *d_kp = reinterpret_cast<const mcgp::KParams *>(c->d_resume);
+        const mcgp::ResumeState *d_st = reinterpret_cast<const mcgp::ResumeState *>(c->d_resume + o_st);
+        unsigned long long *d_h = reinterpret_cast<unsigned long long *>(c->d_resume + o_hist);
+        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
+        HIP_TRY(hipMemcpy(c->d_resume, &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_resume + o_st, st.data(), sizeof(mcgp::ResumeState) * n_states, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_h, 0, cells * 8, nullptr));
+        const KernelFn geo_fn = reinterpret_cast<KernelFn>(&mcgp::race_resume_kernel);   // (for its register count)
+        uint32_t grid = 0, block = 0, lds = 0;
+        for (uint64_t done = 0; done < n_sims; done += cap) {
+            const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
+            // the generic kernel's block shape; the blocks the device holds at once are shared out over the states
+            launch_geometry(*c, n, false, geo_fn, m, &grid, &block, &lds);
+            if (lds > c->lds_per_block)
+                return fail(MCGP_E_HIP, "the resume kernel's block needs " + std::to_string(lds) + " bytes of LDS, the device "
+                                        "offers " + std::to_string(c->lds_per_block) + " per block");
+            const uint64_t n_batches = (m + block - 1) / block;
+            const uint32_t gx = (grid + n_states - 1) / n_states;
+            hipLaunchKernelGGL(mcgp::race_resume_kernel, dim3(gx, n_states), dim3(block), lds, nullptr, d_kp, d_st, m, done,
+                               (uint32_t)seed, (uint32_t)(seed >> 32), d_h, orders_out ? c->d_orders : nullptr,
+                               (uint32_t)n_batches);
+            HIP_TRY(hipGetLastError());
+            if (orders_out)
+                HIP_TRY(hipMemcpy2D(orders_out + (size_t)done * n, (size_t)n_sims * n, c->d_orders, (size_t)m * n,
+                                    (size_t)m * n, n_states, hipMemcpyDeviceToHost));
+            grid = gx * n_states;
+        }
+        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
+        c->last_timer = kBatchTimer;
+        c->last_grid = grid;
+        c->last_block = block;
+        c->last_lds = lds;
+        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "mcgp::race_resume_kernel");
+        // the caller's histogram is added into only once everything has run
+        std::vector<unsigned long long> back(cells);
+        HIP_TRY(hipMemcpy(back.data(), d_h, cells * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < cells; ++i) hist_out[i] += back[i];
         return MCGP_OK;
     };
     return body();

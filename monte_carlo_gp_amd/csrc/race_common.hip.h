@@ -43,6 +43,15 @@ __host__ __device__ inline uint32_t draw_retirement_lap(uint32_t w, uint64_t t, 
     }
     return 0u;
 }
+// A race resumed after lap k (resume.hip.h) keeps a running car's draw above when it says lap k + 1 .. L or "not in this
+// race".  A draw of lap 2 .. k contradicts a car observed running after lap k; its lap then comes from a second word w'
+// (counter {sim, 0, RETIRE | (8 + (d >> 2))}, word d & 3) through the same chain shifted to start at lap k + 1:
+// P(retire on lap k + j | running after k) is the per-lap chain again.  Returns k + 1 .. L, or 0 (also for k >= L).
+__host__ __device__ inline uint32_t draw_retirement_lap_after(uint32_t w, uint64_t t, int k, int L)
+{
+    const uint32_t r = draw_retirement_lap(w, t, L - k + 1);
+    return r == 0u ? 0u : (uint32_t)(k - 1) + r;
+}
 
 // Read-only problem description, resident in device memory, uniform across lanes.
 struct KParams {

@@ -21,6 +21,9 @@
 // (cumulative_time, grid slot) -- reference :179,231,353,384,410,506,549 sort lists
 // that are in grid order (Q1), so equal times keep grid order.
 //
+// The block's LDS set-up (load_block), the laps after lap 1 (run_laps) and the classification (classify_and_count)
+// are functions shared with race_resume_kernel (resume.hip.h), which runs a race on from a mid-race state.
+//
 // Floating point: IEEE binary64 in the reference's evaluation order; this file
 // is compiled with -ffp-contract=off.  The only fused operations are the three
 // explicit binary32 fmaf of the inverse-normal cubic.
@@ -110,21 +113,26 @@ __device__ __forceinline__ void update_positions(const Rows &s, int n, bool drs_
     }
 }
 
-__global__ void __launch_bounds__(512)
-race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
-            uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist,
-            uint8_t *__restrict__ orders, const uint8_t *__restrict__ fixed_grid, uint32_t n_batches,
-            uint32_t * /*ticket: the register kernel's work counter; batches are dealt out by block index here*/,
-            uint32_t * /*retire_ws: the register kernel's retirement lists; an LDS row per driver here*/)
+// What the lap code reads besides the lane's rows: the block's LDS copies of the parameter block's tables, and its scalars.
+struct LapEnv {
+    const KParams *P;
+    int n, L, track;
+    const float4 *norm;
+    const double *base, *factor, *deg, *var;
+    const unsigned long long *dnf, *dnf1;
+    const double *cdeg, *cdelta;
+    const uint16_t *opt;
+    double pit_loss, overtake_delta, drs_delta, dirty_thr, dirty_pen;
+};
+
+// The block's dynamic LDS: tables, histogram (kMaxCars^2 u32), then the per-lane rows (offsets are multiples of 16).
+// Copies the tables in and zeroes the histogram -- the caller syncs before reading either --, sets the histogram and
+// the lane's rows, and returns the lap code's view.
+__device__ __forceinline__ LapEnv load_block(unsigned char *smem, const KParams *__restrict__ P, uint32_t *&s_hist, Rows &s)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
     const int B = blockDim.x;
     const int n = P->n;
-    const int L = P->total_laps;
-    const int track = P->track;
-
-    // ---- LDS carve-up (offsets are multiples of 16) ----
     float4 *t_norm = reinterpret_cast<float4 *>(smem);
     double *t_base = reinterpret_cast<double *>(smem + kNormalRows * 16);
     double *t_factor = t_base + kMaxCars;
@@ -135,8 +143,7 @@ race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
     double *t_cdeg = reinterpret_cast<double *>(t_dnf1 + kMaxCars);
     double *t_cdelta = t_cdeg + kCompStride;
     uint16_t *t_opt = reinterpret_cast<uint16_t *>(t_cdelta + kCompStride);
-    uint32_t *s_hist = reinterpret_cast<uint32_t *>(t_opt + kMaxCars * kCompStride);
-    Rows s;
+    s_hist = reinterpret_cast<uint32_t *>(t_opt + kMaxCars * kCompStride);
     s.cum = reinterpret_cast<double *>(s_hist + kMaxCars * kMaxCars);
     s.last = s.cum + (size_t)n * B;
     s.pk = reinterpret_cast<uint32_t *>(s.last + (size_t)n * B);
@@ -161,13 +168,262 @@ race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
     }
     for (int i = tid; i < kMaxCars * kCompStride; i += B) t_opt[i] = P->opt_laps[i];
     for (int i = tid; i < n * n; i += B) s_hist[i] = 0u;
-    __syncthreads();
 
-    const double pit_loss = P->pit_loss;
-    const double overtake_delta = P->overtake_delta;
-    const double drs_delta = P->drs_delta;
-    const double dirty_thr = P->dirty_thr;
-    const double dirty_pen = P->dirty_pen;
+    LapEnv e;
+    e.P = P;
+    e.n = n;
+    e.L = P->total_laps;
+    e.track = P->track;
+    e.norm = t_norm;
+    e.base = t_base;
+    e.factor = t_factor;
+    e.deg = t_deg;
+    e.var = t_var;
+    e.dnf = t_dnf;
+    e.dnf1 = t_dnf1;
+    e.cdeg = t_cdeg;
+    e.cdelta = t_cdelta;
+    e.opt = t_opt;
+    e.pit_loss = P->pit_loss;
+    e.overtake_delta = P->overtake_delta;
+    e.drs_delta = P->drs_delta;
+    e.dirty_thr = P->dirty_thr;
+    e.dirty_pen = P->dirty_pen;
+    return e;
+}
+
+// Laps first_lap .. L of one lane's race, reference :166-228, from the state the rows hold after lap first_lap - 1: `ord`
+// sorted by (cumulative time, grid slot), the DRS / dirty-air flags of update_positions, the retirement laps in `out`,
+// and the reference's drs_disabled_until.  race_kernel runs it from lap 2, race_resume_kernel (resume.hip.h) from k + 1.
+__device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1, uint32_t seed_lo,
+                                         uint32_t seed_hi, int first_lap, int drs_disabled_until)
+{
+    const KParams *__restrict__ P = e.P;
+    const int n = e.n, L = e.L, track = e.track;
+    const float4 *t_norm = e.norm;
+    const double *t_base = e.base, *t_factor = e.factor, *t_deg = e.deg, *t_var = e.var;
+    const double *t_cdeg = e.cdeg, *t_cdelta = e.cdelta;
+    const uint16_t *t_opt = e.opt;
+    const double pit_loss = e.pit_loss, overtake_delta = e.overtake_delta, drs_delta = e.drs_delta;
+    const double dirty_thr = e.dirty_thr, dirty_pen = e.dirty_pen;
+    for (int lap = first_lap; lap <= L; ++lap) {
+        const int remaining_laps = L - lap;
+        // ---- race-interrupting events, :168-176 (short-circuit chain, Q8) ----
+        {
+            uint32_t e0, e1, e2, e3;
+            philox4x32_10(c0, c1, (uint32_t)lap, kPurposeEvent, seed_lo, seed_hi, e0, e1, e2, e3);
+            const bool red = (uint64_t)e0 < P->t_red;
+            const bool sc = !red && (uint64_t)e1 < P->t_sc;
+            const bool vsc = !red && !sc && (uint64_t)e2 < P->t_vsc;
+            if (red || sc || vsc) {
+                // _handle_red_flag :397-431 / _handle_safety_car :334-376 / _handle_vsc :378-395
+                const bool dec_age = sc || (vsc && (uint64_t)e3 < P->t_vsc_tire);
+                const uint32_t newc = stint_compound(track, remaining_laps);
+                int k = 0;
+                double leader = 0.0, prev_nt = -1.0;
+                bool tie = false;
+                for (int i = 0; i < n; ++i) {
+                    const uint32_t d = s.Ord(i);
+                    uint32_t pk = s.Pk(d);
+                    if (pk & kDnf) continue;
+                    const double t = s.Cum(d);
+                    if (k == 0) leader = t;
+                    double nt;
+                    if (red) nt = leader + (double)k * 0.1;
+                    else if (sc) nt = leader + (double)k * 0.5;
+                    else { const double gap = t - leader; nt = leader + gap * 0.8; }
+                    tie |= nt == prev_nt;
+                    prev_nt = nt;
+                    const double tbl = nt - leader;
+                    pk &= ~kDirty;
+                    if (tbl > 0 && tbl < dirty_thr) pk |= kDirty;
+                    uint32_t age = pk & kAgeMask;
+                    if (red) {
+                        age = 0u;
+                        pk = (pk & ~(7u << kCompShift)) | (newc << kCompShift) | ((1u << newc) << kUsedShift);
+                    } else if (dec_age) {
+                        age = age > 0u ? age - 1u : 0u;
+                    }
+                    pk = (pk & ~kAgeMask) | age;
+                    s.Cum(d) = nt;
+                    s.Pk(d) = pk;
+                    ++k;
+                }
+                drs_disabled_until = lap + (vsc ? 1 : 2);
+                // x0.8 is monotone but may round two gaps together: equal times fall back to grid order.  Otherwise
+                // the field order (`ord`, which also addresses this lap's draws) stays what the last lap left.
+                if (tie) sort_by_time(s, n);
+            }
+        }
+
+        // ---- every running car's lap, :179-223, with the pit stop of :433-494 folded in ----
+        {
+            double fuel = 110.0 - 1.5 * (double)(lap - 1);     // fuel_load before this lap (Q7)
+            if (!(fuel > 0)) fuel = 0.0;
+            const double fuel_effect = (110.0 - fuel) * 0.03;
+            double carry = 0.0;                                 // car_ahead_times.get(driver, 0)
+            for (int i = 0; i < n; ++i) {
+                const uint32_t d = s.Ord(i);
+                uint32_t pk = s.Pk(d);
+                if (pk & kDnf) continue;
+                const double ahead_last = carry;
+                carry = s.Last(d);
+                if ((int)s.Out(d) == lap) {                     // :194-197, drawn before the race
+                    s.Pk(d) = (pk & ~kAgeMask) | kDnf | (uint32_t)lap;
+                    continue;
+                }
+                uint32_t w0, w1, w2, w3;
+                // the lap noise is addressed by the car's place i in the field order: one block serves places 4j .. 4j+3
+                philox4x32_10(c0, c1, (uint32_t)lap, kPurposeCar | ((uint32_t)i >> 2), seed_lo, seed_hi, w0, w1, w2, w3);
+                const uint32_t w1x = (i & 3) == 0 ? w0 : (i & 3) == 1 ? w1 : (i & 3) == 2 ? w2 : w3;
+                w1 = w1x;
+                uint32_t comp = (pk >> kCompShift) & 7u;
+                uint32_t age = pk & kAgeMask;
+                // _calculate_lap_time :313-332
+                const double eff = t_cdeg[comp] * t_factor[d];
+                const double tire = (double)age * eff;
+                const double drs_gain = (pk & kDrs) ? drs_delta : 0.0;
+                const double noise = 0.0 + t_var[d] * (double)normal_from_u32(w1, t_norm);
+                const double clean = t_base[d] + tire - fuel_effect + t_cdelta[comp] - drs_gain + noise;
+                double lap_time = clean;
+                if ((pk & kDirty) && ahead_last > 0) {          // :209-216
+                    const double dirty_time = clean + dirty_pen;
+                    lap_time = ahead_last > dirty_time ? ahead_last : dirty_time;
+                }
+                double t = s.Cum(d) + lap_time;
+                age += 1u;
+                // _handle_pit_stops :454-492 (no randomness, no cross-car dependence)
+                if ((int)age > (int)t_opt[d * kCompStride + comp] && remaining_laps > 5) {
+                    t = t + pit_loss;
+                    uint32_t newc = stint_compound(track, remaining_laps);
+                    const uint32_t used_dry = (pk >> kUsedShift) & 7u;
+                    if (track == 0 && __popc(used_dry) == 1 && ((used_dry >> newc) & 1u)) {
+                        const uint32_t avail = 7u & ~used_dry;
+                        const uint32_t popped = avail == 5u ? (uint32_t)P->pop_sh : avail == 6u ? (uint32_t)P->pop_mh : 0u;
+                        if (remaining_laps > 20) newc = (avail & 2u) ? 1u : popped;
+                        else newc = (avail & 1u) ? 0u : popped;
+                    }
+                    comp = newc;
+                    pk = (pk & ~(7u << kCompShift)) | (comp << kCompShift) | ((1u << comp) << kUsedShift);
+                    age = 0u;
+                }
+                s.Cum(d) = t;
+                s.Last(d) = lap_time;
+                s.Pk(d) = (pk & ~kAgeMask) | age;
+            }
+        }
+
+        // ---- _simulate_overtakes, :496-536 ----
+        bool need_sort = true;
+        for (int pass = 0; pass < 3; ++pass) {
+            sort_by_time(s, n);
+            need_sort = false;
+            // adjacent pairs that attempt a pass: neither retired, pace delta over the threshold.
+            uint32_t cand = 0u;
+            {
+                uint32_t dp = s.Ord(0);
+                uint32_t pkp = s.Pk(dp);
+                double pace_p = t_base[dp] + (double)(pkp & kAgeMask) * t_deg[dp];
+                for (int i = 1; i < n; ++i) {
+                    const uint32_t d = s.Ord(i);
+                    const uint32_t pk = s.Pk(d);
+                    const double pace = t_base[d] + (double)(pk & kAgeMask) * t_deg[d];
+                    double delta = pace_p - pace;
+                    if (pk & kDrs) delta += drs_delta;
+                    if (!((pk | pkp) & kDnf) && delta > overtake_delta) cand |= 1u << i;
+                    pkp = pk;
+                    pace_p = pace;
+                }
+            }
+            if (cand == 0u) break;
+            bool success = false;
+            uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
+            for (uint32_t k = 0; cand != 0u; ++k) {
+                if ((k & 3u) == 0u)
+                    philox4x32_10(c0, c1, (uint32_t)lap, kPurposeOvt | ((uint32_t)(8 * pass) + (k >> 2)),
+                                  seed_lo, seed_hi, o0, o1, o2, o3);
+                const uint32_t ow = (k & 3u) == 0u ? o0 : (k & 3u) == 1u ? o1 : (k & 3u) == 2u ? o2 : o3;
+                const int i = __ffs((int)cand) - 1;
+                cand &= cand - 1u;
+                const uint32_t db = s.Ord(i), da = s.Ord(i - 1);
+                const uint32_t pkb = s.Pk(db), pka = s.Pk(da);
+                const double pace_b = t_base[db] + (double)(pkb & kAgeMask) * t_deg[db];
+                const double pace_a = t_base[da] + (double)(pka & kAgeMask) * t_deg[da];
+                double delta = pace_a - pace_b;
+                if (pkb & kDrs) delta += drs_delta;
+                double prob = delta / 2.0;
+                if (!(prob < 0.5)) prob = 0.5;
+                if (u32_to_unit(ow) < prob) {
+                    double nb = s.Cum(da) - 0.1;
+                    if (!(nb > 0.1)) nb = 0.1;
+                    s.Cum(db) = nb;
+                    s.Cum(da) = nb + 0.3;
+                    success = true;
+                }
+            }
+            if (!success) break;
+            need_sort = true;
+        }
+        if (need_sort) sort_by_time(s, n);
+        update_positions(s, n, lap > 2 && lap > drs_disabled_until, dirty_thr);   // :227-228
+    }
+}
+
+// Classification, reference :230-242, of one lane's race, and its count: running cars by time, then retired cars by
+// (lap, time) descending, stable -- `ord` insertion-sorted in place with that comparator --; then one count per
+// (driver, position) into the block's LDS histogram and, unless `order` is NULL, the order into order[0 .. n).
+__device__ __forceinline__ void classify_and_count(const Rows &s, int n, uint32_t *s_hist, uint8_t *__restrict__ order)
+{
+    for (int i = 1; i < n; ++i) {
+        const uint32_t x = s.Ord(i);
+        const uint32_t pkx = s.Pk(x);
+        const double kx = s.Cum(x);
+        int j = i;
+        while (j > 0) {
+            const uint32_t y = s.Ord(j - 1);
+            const uint32_t pky = s.Pk(y);
+            bool y_after_x;   // does y classify behind x?
+            if (!(pky & kDnf)) {
+                // y running: it is ahead of every retired car; among runners `ord` is already sorted
+                y_after_x = false;
+            } else if (!(pkx & kDnf)) {
+                y_after_x = true;          // retired behind running
+            } else {
+                const uint32_t ly = pky & kAgeMask, lx = pkx & kAgeMask;
+                const double ky = s.Cum(y);
+                // descending (lap, time); ties keep grid order
+                y_after_x = ly < lx || (ly == lx && (ky < kx || (ky == kx && gpos_of(pky) > gpos_of(pkx))));
+            }
+            if (!y_after_x) break;
+            s.Ord(j) = (uint8_t)y;
+            --j;
+        }
+        s.Ord(j) = (uint8_t)x;
+    }
+    for (int p = 0; p < n; ++p) {
+        const uint32_t d = s.Ord(p);
+        atomicAdd(&s_hist[d * n + p], 1u);                       // reference :93-94
+        if (order) order[p] = (uint8_t)d;
+    }
+}
+
+__global__ void __launch_bounds__(512)
+race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
+            uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist,
+            uint8_t *__restrict__ orders, const uint8_t *__restrict__ fixed_grid, uint32_t n_batches,
+            uint32_t * /*ticket: the register kernel's work counter; batches are dealt out by block index here*/,
+            uint32_t * /*retire_ws: the register kernel's retirement lists; an LDS row per driver here*/)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x;
+    const int B = blockDim.x;
+    uint32_t *s_hist;
+    Rows s;
+    const LapEnv e = load_block(smem, P, s_hist, s);
+    __syncthreads();
+    const int n = e.n;
+    const int L = e.L;
+    const int track = e.track;
 
     for (uint32_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
         const uint64_t local = (uint64_t)batch * (uint64_t)B + (uint64_t)tid;
@@ -238,27 +494,27 @@ race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
             uint32_t pk = s.Pk(d);
             uint32_t w0, w1, w2, w3;
             philox4x32_10(c0, c1, 1u, kPurposeCar | d, seed_lo, seed_hi, w0, w1, w2, w3);
-            if ((uint64_t)w0 < t_dnf1[d]) {
+            if ((uint64_t)w0 < e.dnf1[d]) {
                 s.Pk(d) = (pk & ~kAgeMask) | kDnf | 1u;
                 continue;
             }
             const uint32_t comp = (pk >> kCompShift) & 7u;
             const uint32_t age = pk & kAgeMask;
-            const double eff = t_cdeg[comp] * t_factor[d];
+            const double eff = e.cdeg[comp] * e.factor[d];
             const double tire = (double)age * eff;
             const double fuel_effect = (110.0 - 110.0) * 0.03;
-            const double noise = 0.0 + t_var[d] * (double)normal_from_u32(w1, t_norm);
-            const double base_lap = t_base[d] + tire - fuel_effect + t_cdelta[comp] - 0.0 + noise;
+            const double noise = 0.0 + e.var[d] * (double)normal_from_u32(w1, e.norm);
+            const double base_lap = e.base[d] + tire - fuel_effect + e.cdelta[comp] - 0.0 + noise;
             double pf = 0.5 + (double)(pos + 1) * 0.1;
             if (!(pf < 1.5)) pf = 1.5;
-            double sd = 0.0 + pf * (double)normal_from_u32(w2, t_norm);
+            double sd = 0.0 + pf * (double)normal_from_u32(w2, e.norm);
             if (pos + 1 <= 3 && 1.0 < sd) sd = 1.0;
             const double lap_time = base_lap - sd * 0.5;
             s.Cum(d) = 0.0 + lap_time;
             s.Pk(d) = (pk & ~kAgeMask) | (age + 1u);
         }
         sort_by_time(s, n);
-        update_positions(s, n, false, dirty_thr);
+        update_positions(s, n, false, e.dirty_thr);
 
         // ================= retirements of laps 2..L (:190-197), drawn once per race: race_common.hip.h =================
         {
@@ -267,215 +523,15 @@ race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
                 if ((d & 3) == 0)
                     philox4x32_10(c0, c1, 0u, kPurposeRetire | (uint32_t)(d >> 2), seed_lo, seed_hi, r0, r1, r2, r3);
                 const uint32_t rw = (d & 3) == 0 ? r0 : (d & 3) == 1 ? r1 : (d & 3) == 2 ? r2 : r3;
-                s.Out(d) = (uint16_t)draw_retirement_lap(rw, t_dnf[d], L);
+                s.Out(d) = (uint16_t)draw_retirement_lap(rw, e.dnf[d], L);
             }
         }
 
         // ================= laps 2..L, reference :166-228 =================
-        int drs_disabled_until = 0;
-        for (int lap = 2; lap <= L; ++lap) {
-            const int remaining_laps = L - lap;
-            // ---- race-interrupting events, :168-176 (short-circuit chain, Q8) ----
-            {
-                uint32_t e0, e1, e2, e3;
-                philox4x32_10(c0, c1, (uint32_t)lap, kPurposeEvent, seed_lo, seed_hi, e0, e1, e2, e3);
-                const bool red = (uint64_t)e0 < P->t_red;
-                const bool sc = !red && (uint64_t)e1 < P->t_sc;
-                const bool vsc = !red && !sc && (uint64_t)e2 < P->t_vsc;
-                if (red || sc || vsc) {
-                    // _handle_red_flag :397-431 / _handle_safety_car :334-376 / _handle_vsc :378-395
-                    const bool dec_age = sc || (vsc && (uint64_t)e3 < P->t_vsc_tire);
-                    const uint32_t newc = stint_compound(track, remaining_laps);
-                    int k = 0;
-                    double leader = 0.0, prev_nt = -1.0;
-                    bool tie = false;
-                    for (int i = 0; i < n; ++i) {
-                        const uint32_t d = s.Ord(i);
-                        uint32_t pk = s.Pk(d);
-                        if (pk & kDnf) continue;
-                        const double t = s.Cum(d);
-                        if (k == 0) leader = t;
-                        double nt;
-                        if (red) nt = leader + (double)k * 0.1;
-                        else if (sc) nt = leader + (double)k * 0.5;
-                        else { const double gap = t - leader; nt = leader + gap * 0.8; }
-                        tie |= nt == prev_nt;
-                        prev_nt = nt;
-                        const double tbl = nt - leader;
-                        pk &= ~kDirty;
-                        if (tbl > 0 && tbl < dirty_thr) pk |= kDirty;
-                        uint32_t age = pk & kAgeMask;
-                        if (red) {
-                            age = 0u;
-                            pk = (pk & ~(7u << kCompShift)) | (newc << kCompShift) | ((1u << newc) << kUsedShift);
-                        } else if (dec_age) {
-                            age = age > 0u ? age - 1u : 0u;
-                        }
-                        pk = (pk & ~kAgeMask) | age;
-                        s.Cum(d) = nt;
-                        s.Pk(d) = pk;
-                        ++k;
-                    }
-                    drs_disabled_until = lap + (vsc ? 1 : 2);
-                    // x0.8 is monotone but may round two gaps together: equal times fall back to grid order.  Otherwise
-                    // the field order (`ord`, which also addresses this lap's draws) stays what the last lap left.
-                    if (tie) sort_by_time(s, n);
-                }
-            }
-
-            // ---- every running car's lap, :179-223, with the pit stop of :433-494 folded in ----
-            {
-                double fuel = 110.0 - 1.5 * (double)(lap - 1);     // fuel_load before this lap (Q7)
-                if (!(fuel > 0)) fuel = 0.0;
-                const double fuel_effect = (110.0 - fuel) * 0.03;
-                double carry = 0.0;                                 // car_ahead_times.get(driver, 0)
-                for (int i = 0; i < n; ++i) {
-                    const uint32_t d = s.Ord(i);
-                    uint32_t pk = s.Pk(d);
-                    if (pk & kDnf) continue;
-                    const double ahead_last = carry;
-                    carry = s.Last(d);
-                    if ((int)s.Out(d) == lap) {                     // :194-197, drawn before the race
-                        s.Pk(d) = (pk & ~kAgeMask) | kDnf | (uint32_t)lap;
-                        continue;
-                    }
-                    uint32_t w0, w1, w2, w3;
-                    // the lap noise is addressed by the car's place i in the field order: one block serves places 4j .. 4j+3
-                    philox4x32_10(c0, c1, (uint32_t)lap, kPurposeCar | ((uint32_t)i >> 2), seed_lo, seed_hi, w0, w1, w2, w3);
-                    const uint32_t w1x = (i & 3) == 0 ? w0 : (i & 3) == 1 ? w1 : (i & 3) == 2 ? w2 : w3;
-                    w1 = w1x;
-                    uint32_t comp = (pk >> kCompShift) & 7u;
-                    uint32_t age = pk & kAgeMask;
-                    // _calculate_lap_time :313-332
-                    const double eff = t_cdeg[comp] * t_factor[d];
-                    const double tire = (double)age * eff;
-                    const double drs_gain = (pk & kDrs) ? drs_delta : 0.0;
-                    const double noise = 0.0 + t_var[d] * (double)normal_from_u32(w1, t_norm);
-                    const double clean = t_base[d] + tire - fuel_effect + t_cdelta[comp] - drs_gain + noise;
-                    double lap_time = clean;
-                    if ((pk & kDirty) && ahead_last > 0) {          // :209-216
-                        const double dirty_time = clean + dirty_pen;
-                        lap_time = ahead_last > dirty_time ? ahead_last : dirty_time;
-                    }
-                    double t = s.Cum(d) + lap_time;
-                    age += 1u;
-                    // _handle_pit_stops :454-492 (no randomness, no cross-car dependence)
-                    if ((int)age > (int)t_opt[d * kCompStride + comp] && remaining_laps > 5) {
-                        t = t + pit_loss;
-                        uint32_t newc = stint_compound(track, remaining_laps);
-                        const uint32_t used_dry = (pk >> kUsedShift) & 7u;
-                        if (track == 0 && __popc(used_dry) == 1 && ((used_dry >> newc) & 1u)) {
-                            const uint32_t avail = 7u & ~used_dry;
-                            const uint32_t popped = avail == 5u ? (uint32_t)P->pop_sh : avail == 6u ? (uint32_t)P->pop_mh : 0u;
-                            if (remaining_laps > 20) newc = (avail & 2u) ? 1u : popped;
-                            else newc = (avail & 1u) ? 0u : popped;
-                        }
-                        comp = newc;
-                        pk = (pk & ~(7u << kCompShift)) | (comp << kCompShift) | ((1u << comp) << kUsedShift);
-                        age = 0u;
-                    }
-                    s.Cum(d) = t;
-                    s.Last(d) = lap_time;
-                    s.Pk(d) = (pk & ~kAgeMask) | age;
-                }
-            }
-
-            // ---- _simulate_overtakes, :496-536 ----
-            bool need_sort = true;
-            for (int pass = 0; pass < 3; ++pass) {
-                sort_by_time(s, n);
-                need_sort = false;
-                // adjacent pairs that attempt a pass: neither retired, pace delta over the threshold.
-                uint32_t cand = 0u;
-                {
-                    uint32_t dp = s.Ord(0);
-                    uint32_t pkp = s.Pk(dp);
-                    double pace_p = t_base[dp] + (double)(pkp & kAgeMask) * t_deg[dp];
-                    for (int i = 1; i < n; ++i) {
-                        const uint32_t d = s.Ord(i);
-                        const uint32_t pk = s.Pk(d);
-                        const double pace = t_base[d] + (double)(pk & kAgeMask) * t_deg[d];
-                        double delta = pace_p - pace;
-                        if (pk & kDrs) delta += drs_delta;
-                        if (!((pk | pkp) & kDnf) && delta > overtake_delta) cand |= 1u << i;
-                        pkp = pk;
-                        pace_p = pace;
-                    }
-                }
-                if (cand == 0u) break;
-                bool success = false;
-                uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
-                for (uint32_t k = 0; cand != 0u; ++k) {
-                    if ((k & 3u) == 0u)
-                        philox4x32_10(c0, c1, (uint32_t)lap, kPurposeOvt | ((uint32_t)(8 * pass) + (k >> 2)),
-                                      seed_lo, seed_hi, o0, o1, o2, o3);
-                    const uint32_t ow = (k & 3u) == 0u ? o0 : (k & 3u) == 1u ? o1 : (k & 3u) == 2u ? o2 : o3;
-                    const int i = __ffs((int)cand) - 1;
-                    cand &= cand - 1u;
-                    const uint32_t db = s.Ord(i), da = s.Ord(i - 1);
-                    const uint32_t pkb = s.Pk(db), pka = s.Pk(da);
-                    const double pace_b = t_base[db] + (double)(pkb & kAgeMask) * t_deg[db];
-                    const double pace_a = t_base[da] + (double)(pka & kAgeMask) * t_deg[da];
-                    double delta = pace_a - pace_b;
-                    if (pkb & kDrs) delta += drs_delta;
-                    double prob = delta / 2.0;
-                    if (!(prob < 0.5)) prob = 0.5;
-                    if (u32_to_unit(ow) < prob) {
-                        double nb = s.Cum(da) - 0.1;
-                        if (!(nb > 0.1)) nb = 0.1;
-                        s.Cum(db) = nb;
-                        s.Cum(da) = nb + 0.3;
-                        success = true;
-                    }
-                }
-                if (!success) break;
-                need_sort = true;
-            }
-            if (need_sort) sort_by_time(s, n);
-            update_positions(s, n, lap > 2 && lap > drs_disabled_until, dirty_thr);   // :227-228
-        }
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, 2, 0);
 
         // ================= classification, reference :230-242 =================
-        // running cars by time, then retired cars by (lap, time) descending, stable.
-        {
-            int n_dnf = 0;
-            int w = 0;
-            // compact running cars to the front (order kept), retired ones to scratch in `pk`-free bytes:
-            // simple two-pass walk using the `last` rows (dead now) as byte scratch is avoided; instead
-            // insertion-sort `ord` in place with the classification comparator.
-            for (int i = 1; i < n; ++i) {
-                const uint32_t x = s.Ord(i);
-                const uint32_t pkx = s.Pk(x);
-                const double kx = s.Cum(x);
-                int j = i;
-                while (j > 0) {
-                    const uint32_t y = s.Ord(j - 1);
-                    const uint32_t pky = s.Pk(y);
-                    bool y_after_x;   // does y classify behind x?
-                    if (!(pky & kDnf)) {
-                        // y running: it is ahead of every retired car; among runners `ord` is already sorted
-                        y_after_x = false;
-                    } else if (!(pkx & kDnf)) {
-                        y_after_x = true;          // retired behind running
-                    } else {
-                        const uint32_t ly = pky & kAgeMask, lx = pkx & kAgeMask;
-                        const double ky = s.Cum(y);
-                        // descending (lap, time); ties keep grid order
-                        y_after_x = ly < lx || (ly == lx && (ky < kx || (ky == kx && gpos_of(pky) > gpos_of(pkx))));
-                    }
-                    if (!y_after_x) break;
-                    s.Ord(j) = (uint8_t)y;
-                    --j;
-                }
-                s.Ord(j) = (uint8_t)x;
-            }
-            (void)n_dnf; (void)w;
-            for (int p = 0; p < n; ++p) {
-                const uint32_t d = s.Ord(p);
-                atomicAdd(&s_hist[d * n + p], 1u);                       // reference :93-94
-                if (orders) orders[local * (uint64_t)n + (uint64_t)p] = (uint8_t)d;
-            }
-        }
+        classify_and_count(s, n, s_hist, orders ? orders + local * (uint64_t)n : nullptr);
     }
 
     __syncthreads();

@@ -206,6 +206,33 @@ class F1Predictor:
             driver_dnf_rates=inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'])
         return pack_result(inp['drivers'], inp['grid_probs'], race_probs, inp['weather'], prediction_point, actual_grid)
 
+    def predict_from_state(self, season: int, race: str, fixture: dict | str, state, n_simulations: int = 100000,
+                           seed: int | None = None):
+        """In-race odds (not in the reference): the weekend's race inputs (simulator_inputs, as predict_weekend builds
+        them) run from a mid-race RaceState of the fixture's drivers -- or from each of a list of them, with common
+        random numbers -- through RaceSimulator.run_from_state.  Returns, per state, {'lap', 'win_probabilities', 'podium_probabilities',
+        'points_probabilities' (top 10), 'full_distributions'}: one dict, or a list for a list of states."""
+        if isinstance(fixture, str):
+            with open(fixture) as f:
+                fixture = json.load(f)
+        if not fixture.get('drivers'):
+            raise ValueError(f"No practice data available for {season} {race}")
+        single = not isinstance(state, (list, tuple))
+        states = [state] if single else list(state)
+        inp = self.simulator_inputs(fixture, race)
+        sim = RaceSimulator(inp['config'], device=self.device)
+        # the driver order of predict_weekend's run: a state that run's simulation i reached continues as simulation i
+        probs = sim.run_from_state(n_simulations, states, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
+                                   inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'],
+                                   drivers=list(inp['grid_probs']))
+        drivers = sim.last_drivers
+        out = []
+        for st, rp in zip(states, probs):
+            top = lambda k: {d: sum(rp.get(d, {}).get(p, 0) for p in range(1, k + 1)) for d in drivers}
+            out.append({'lap': int(st.lap), 'win_probabilities': top(1), 'podium_probabilities': top(3),
+                        'points_probabilities': top(10), 'full_distributions': rp})
+        return out[0] if single else out
+
     @staticmethod
     def _with_matchups(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid) -> dict:
         """predict_weekend's result from a run_matchups call on `grid`, with the matchup keys added."""

@@ -7,6 +7,7 @@ Mirrors the reference's interface for the hot path (reference src/simulation.py)
     RaceSimulator.run_monte_carlo(...)           :59-100  same arguments, same result shape
     RaceSimulator.simulate_race(grid, ...)       :147-242 one race, list of (driver, position)
     RaceSimulator.run_matchups(...)              (not in the reference) head-to-head and podium counts of one race
+    RaceSimulator.run_from_state(...)            (not in the reference) the rest of a race from a mid-race RaceState
 
 The per-lap loop itself runs in hand-written HIP (csrc/race_kernel_reg.hip.h) behind
 the C ABI of include/mcgp.h; this module only resolves the reference's dict
@@ -24,6 +25,7 @@ reference src/validation.py:172-174 relies on.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import random
 from dataclasses import dataclass, field
 
@@ -57,6 +59,98 @@ class CarState:
 
     def __post_init__(self):
         self.used_compounds.add(self.tire_compound)          # the starting compound counts as used (:31-34)
+
+
+@dataclass
+class RaceState:
+    """A race after `lap` laps (1 .. total_laps), as the race model leaves it at the end of that lap: the input of
+    RaceSimulator.run_from_state.  `cars` are CarState records in GRID order, as the reference's own list is (it never
+    reorders it): the list index is the car's start-grid slot.  Per car it reads `driver`, `cumulative_time`,
+    `last_lap_time`, `tire_compound` and `used_compounds` (the reference's compound names), `tire_age`, and `dnf` with
+    `lap` as the lap of retirement.  `drs_disabled_until` is the reference simulate_race's variable: lap + 2 after a red
+    flag or safety car, lap + 1 after a VSC, 0 if no event has happened."""
+    lap: int
+    drs_disabled_until: int = 0
+    cars: list = field(default_factory=list)
+
+    @staticmethod
+    def from_json(obj: dict) -> 'RaceState':
+        """{"lap", "drs_disabled_until" (optional), "cars": [{"driver", "cumulative_time", "last_lap_time",
+        "tire_compound", "tire_age", "used_compounds", "retired_lap" (0 = running)}, ...] in grid order}."""
+        lap = int(obj['lap'])
+        cars = []
+        for slot, c in enumerate(obj['cars']):
+            retired = int(c.get('retired_lap', 0))
+            cars.append(CarState(driver=str(c['driver']), team='', position=slot + 1, lap=retired if retired else lap,
+                                 tire_compound=str(c['tire_compound']), tire_age=int(c['tire_age']),
+                                 fuel_load=max(0.0, 110.0 - 1.5 * lap), time_behind_leader=0.0, pit_stops=0,
+                                 cumulative_time=float(c['cumulative_time']), dnf=bool(retired),
+                                 used_compounds={str(u) for u in c.get('used_compounds', [])},
+                                 laps_completed=retired if retired else lap, last_lap_time=float(c['last_lap_time'])))
+        return RaceState(lap=lap, drs_disabled_until=int(obj.get('drs_disabled_until', 0)), cars=cars)
+
+    def to_json(self) -> dict:
+        order = {c: i for i, c in enumerate(N.COMPOUNDS)}
+        return {'lap': int(self.lap), 'drs_disabled_until': int(self.drs_disabled_until),
+                'cars': [{'driver': c.driver, 'cumulative_time': float(c.cumulative_time),
+                          'last_lap_time': float(c.last_lap_time), 'tire_compound': c.tire_compound,
+                          'tire_age': int(c.tire_age),
+                          'used_compounds': sorted(c.used_compounds, key=lambda u: order.get(u, len(order))),
+                          'retired_lap': int(c.lap) if c.dnf else 0} for c in self.cars]}
+
+    def arrays(self, drivers, total_laps=None) -> dict:
+        """The mcgp_race_state arrays in the order of `drivers` (every car's driver exactly once): cumulative_time,
+        last_lap_time (float64), grid_slot (= list index), compound (id), used_compounds (bit per compound id; the
+        current compound included), tire_age, retired_lap (int16).  ValueError naming the driver on a bad field."""
+        drivers = [str(d) for d in drivers]
+        lap = int(self.lap)
+        if lap < 1 or (total_laps is not None and lap > int(total_laps)):
+            raise ValueError(f'lap must be in [1, total_laps], got {lap}')
+        dd = int(self.drs_disabled_until)
+        if dd < 0 or (total_laps is not None and dd > int(total_laps) + 2):
+            raise ValueError(f'drs_disabled_until must be in [0, total_laps + 2], got {dd}')
+        index = {d: i for i, d in enumerate(drivers)}
+        names = [str(c.driver) for c in self.cars]
+        if sorted(names) != sorted(drivers) or len(set(names)) != len(names):
+            raise ValueError(f'the state\'s cars {names} are not the drivers {drivers}, each once')
+        n = len(drivers)
+        a = dict(cumulative_time=np.zeros(n, np.float64), last_lap_time=np.zeros(n, np.float64),
+                 grid_slot=np.zeros(n, np.uint8), compound=np.zeros(n, np.uint8),
+                 used_compounds=np.zeros(n, np.uint8), tire_age=np.zeros(n, np.int16),
+                 retired_lap=np.zeros(n, np.int16))
+        max_age = 1023 - (int(total_laps) - lap) if total_laps is not None else 1023
+        for slot, c in enumerate(self.cars):
+            d, i = str(c.driver), index[str(c.driver)]
+            if c.tire_compound not in N.COMPOUND_ID:
+                raise ValueError(f'{d}: tire_compound must be one of {list(N.COMPOUNDS)}, got {c.tire_compound!r}')
+            bad = [u for u in c.used_compounds if u not in N.COMPOUND_ID]
+            if bad:
+                raise ValueError(f'{d}: used_compounds has unknown compounds {bad}')
+            for key in ('cumulative_time', 'last_lap_time'):
+                if not math.isfinite(float(getattr(c, key))):
+                    raise ValueError(f'{d}: {key} is not finite')
+            if not 0 <= int(c.tire_age) <= max_age:
+                raise ValueError(f'{d}: tire_age must be in [0, {max_age}], got {c.tire_age}')
+            retired = int(c.lap) if c.dnf else 0
+            if c.dnf and not 1 <= retired <= lap:
+                raise ValueError(f'{d}: a retired car\'s lap must be in [1, {lap}], got {c.lap}')
+            a['cumulative_time'][i] = float(c.cumulative_time)
+            a['last_lap_time'][i] = float(c.last_lap_time)
+            a['grid_slot'][i] = slot
+            a['compound'][i] = N.COMPOUND_ID[c.tire_compound]
+            a['used_compounds'][i] = sum(1 << N.COMPOUND_ID[u] for u in set(c.used_compounds) | {c.tire_compound})
+            a['tire_age'][i] = int(c.tire_age)
+            a['retired_lap'][i] = retired
+        return a
+
+    def c_struct(self, arrays):
+        """mcgp_race_state over `arrays` (from arrays(); the caller keeps them alive)."""
+        p = lambda k, t: arrays[k].ctypes.data_as(C.POINTER(t))
+        return N.McgpRaceState(lap=int(self.lap), drs_disabled_until=int(self.drs_disabled_until),
+                               cumulative_time=p('cumulative_time', C.c_double), last_lap_time=p('last_lap_time', C.c_double),
+                               grid_slot=p('grid_slot', C.c_uint8), compound=p('compound', C.c_uint8),
+                               used_compounds=p('used_compounds', C.c_uint8), tire_age=p('tire_age', C.c_int16),
+                               retired_lap=p('retired_lap', C.c_int16))
 
 
 @dataclass
@@ -310,6 +404,76 @@ class RaceSimulator:
         self.last_drivers = drivers
         return MatchupResult(drivers=drivers, n_simulations=n_simulations, hist=self.last_histogram, ahead=total(1),
                              podium=total(2) if want_podium else None)
+
+    def run_from_state(
+        self,
+        n_simulations: int,
+        state,
+        base_pace: dict,
+        tire_deg: dict,
+        driver_variance: dict,
+        driver_dnf_rates: dict | None = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset=0,
+        drivers=None,
+        return_orders: bool = False,
+    ):
+        """In-race odds: the rest of the race from a RaceState, or from each of a list of them (scenarios of the same
+        drivers), on the device (include/mcgp.h: mcgp_run_from_state).  Returns run_monte_carlo's {driver: {position:
+        probability}} for one state, a list of them for a list.
+
+        Simulation i of every state has id sim_offset + i (sim_offset: an int, or one per state) and makes on the laps
+        after the state exactly the draws run_monte_carlo's simulation i makes there: scenarios given the same ids see
+        the same random futures (common random numbers).  `drivers` fixes the driver-index order (default: the first
+        state's grid order); with a run_monte_carlo call's grid_probs key order, a state that run's simulation i reached
+        continues, as simulation i, into that run's finishing order.  A running car whose once-per-race retirement
+        draw names a lap the state has already passed gets a fresh draw over the remaining laps.  32-bit deviates only.
+        return_orders: also the finishing orders ([N, n], or [S, N, n] for a list).  last_histogram: [n, n], or
+        [S, n, n] for a list.  Same seed rules and device sharding as run_monte_carlo."""
+        single = isinstance(state, RaceState)
+        states = [state] if single else list(state)
+        if not states:
+            raise ValueError('no race state given')
+        drivers = [str(d) for d in (drivers if drivers is not None else [c.driver for c in states[0].cars])]
+        S, n_simulations = len(states), int(n_simulations)
+        offsets = [int(sim_offset)] * S if isinstance(sim_offset, (int, np.integer)) else [int(x) for x in sim_offset]
+        if len(offsets) != S:
+            raise ValueError(f'sim_offset: one per state ({S}), got {len(offsets)}')
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        n = prob.n
+        arrays = [st.arrays(drivers, self.config.total_laps) for st in states]
+        c_states = (N.McgpRaceState * S)(*[st.c_struct(a) for st, a in zip(states, arrays)])
+        shape = (n, n) if single else (S, n, n)
+        if n_simulations <= 0:
+            self.last_histogram, self.last_drivers = np.zeros(shape, np.int64), drivers
+            empty = [{} for _ in states]
+            res = empty[0] if single else empty
+            if return_orders:
+                return res, np.zeros((0, n) if single else (S, 0, n), np.uint8)
+            return res
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+
+        def run_shard(device, offset, count):
+            h = np.zeros((S, n, n), np.uint64)
+            o = np.zeros((S, count, n), np.uint8) if return_orders else None
+            so = (C.c_uint64 * S)(*[x + int(offset) for x in offsets])
+            rc = lib.mcgp_run_from_state(C.byref(prob.cfg), C.byref(prob.drv), n, S, c_states, int(count), so, seed64,
+                                         device, h.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
+            return (h, o), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        parts = self._run_sharded(run_shard, n_simulations)
+        hist = np.sum([h for (h, _), _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        self.last_histogram = hist[0] if single else hist
+        self.last_drivers = drivers
+        probs = [histogram_to_probs(hist[s], drivers, n_simulations) for s in range(S)]
+        res = probs[0] if single else probs
+        if return_orders:
+            orders = np.concatenate([o for (_, o), _, _ in parts], axis=1)
+            return res, (orders[0] if single else orders)
+        return res
 
     def simulate_race(
         self,
