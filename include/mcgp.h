@@ -32,7 +32,8 @@ extern "C" {
 /* 3: mcgp_run_championship */
 /* 4: mcgp_run_matchups */
 /* 5: mcgp_race_state, mcgp_run_from_state */
-#define MCGP_ABI_VERSION 5
+/* 6: mcgp_run_trace */
+#define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
 
@@ -244,6 +245,39 @@ typedef struct mcgp_race_state {
 int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uint32_t n, uint32_t n_states,
                             const mcgp_race_state *states, uint64_t n_sims, const uint64_t *sim_offsets, uint64_t seed,
                             int32_t device, uint64_t *hist_out, uint8_t *orders_out);
+
+/* Race trace: what happened lap by lap in mcgp_run's simulations (ids sim_offset .. sim_offset + n_sims - 1, the same
+ * draws, so hist_out equals mcgp_run's), counted on the device; no per-lap data leaves it.  Everything is read from the
+ * race model's state after the end of lap k (its update_positions), lap 1 included:
+ *   - running position after lap k: a car's rank among the cars not retired, by (cumulative time, grid slot); a retired
+ *     car has none and counts in column n.  After lap L the running positions are the classified positions of the
+ *     running cars;
+ *   - laps led: the laps k in 1..L after which the driver is in running position 0;
+ *   - pit stops: the laps k in 2..L on which the car pitted, i.e. after which it is running on tyres of age 0;
+ *   - fastest lap: the driver with the smallest lap time of a car running after lap k, over laps 2..L (lap 1 records no
+ *     lap time); a tie goes to the earlier lap, then to the better running position on that lap; a simulation in which
+ *     no car completes a lap >= 2 counts nowhere;
+ *   - race events: per simulation, the number of laps 2..L whose event draw gave a red flag, a safety car or a VSC
+ *     (the short-circuit chain, counted whether or not any car still runs).
+ *   hist_out      [n][n]        [driver][position - 1], equal to mcgp_run's
+ *   lap_pos_out   [L][n][n + 1] [lap - 1][driver][running position, or n = retired]; every row sums to n_sims
+ *   laps_led_out  [n][L + 1]    [driver][laps led], or NULL
+ *   stops_out     [n][L + 1]    [driver][pit stops], or NULL
+ *   fastest_out   [n]           simulations in which the driver sets the fastest lap, or NULL
+ *   events_out    [3][L + 1]    [red flag, safety car, VSC][number in the race], or NULL
+ * L = cfg->total_laps.  All are ACCUMULATED into (caller zeroes), and only after every launch has succeeded: on an error
+ * they are left as they were.  Arguments are checked as mcgp_run checks them, before any device lookup (MCGP_E_BAD_ARG);
+ * deviates must be MCGP_DEVIATES_32 (the generic kernel runs the trace and has no 53-bit path).  n_sims == 0 succeeds
+ * without a device.  The device work goes chunk by chunk through a staging buffer of 512 MiB / (L n) simulations (one
+ * byte per lap, driver and simulation; rounded down to a multiple of 256, then to whole rounds of the device's resident
+ * blocks, grid_blocks x block_threads of mcgp_last_launch_info, which after this call describes its first chunk's race
+ * launch) that counting kernels read; device memory does not grow with n_sims.  Any split
+ * of [0, N) over calls, sim_offsets or devices sums to the same counts.  mcgp_last_kernel_ms afterwards = the device time
+ * of everything the call ran. */
+int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
+                       uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                       uint64_t *lap_pos_out, uint64_t *laps_led_out, uint64_t *stops_out, uint64_t *fastest_out,
+                       uint64_t *events_out);
 
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver

@@ -3,13 +3,14 @@
 Public surface mirrors reference src/simulation.py: CarState, RaceConfig, RaceSimulator; run_monte_carlo_batch runs several
 races in one launch; RaceSimulator.run_matchups counts head-to-heads and podiums of one race (MatchupResult);
 run_championship simulates the drivers' and constructors' standings over a calendar of races;
-RaceSimulator.run_from_state simulates the rest of a race from a mid-race RaceState.
+RaceSimulator.run_from_state simulates the rest of a race from a mid-race RaceState; RaceSimulator.run_trace counts what
+happened lap by lap (TraceResult: lap chart, laps led, pit stops, fastest lap, race events).
 The compute path is the HIP library libmcgp_hip.so (C ABI: include/mcgp.h); there is no
 CPU fallback.
 """
 from .simulation import (CarState, ChampionshipResult, MatchupResult, RaceConfig, RaceSimulator, RaceState,  # noqa: F401
-                         histogram_to_probs, run_championship, run_monte_carlo_batch)
+                         TraceResult, histogram_to_probs, run_championship, run_monte_carlo_batch)
 from . import config  # noqa: F401
 
-__all__ = ['CarState', 'ChampionshipResult', 'MatchupResult', 'RaceConfig', 'RaceSimulator', 'RaceState', 'histogram_to_probs',
-           'run_championship', 'run_monte_carlo_batch', 'config']
+__all__ = ['CarState', 'ChampionshipResult', 'MatchupResult', 'RaceConfig', 'RaceSimulator', 'RaceState', 'TraceResult',
+           'histogram_to_probs', 'run_championship', 'run_monte_carlo_batch', 'config']

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_PKG, 'libmcgp_hip.so')
 
 MAX_CARS = 32
 MAX_LAPS = 1000
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 COMPOUNDS = ('SOFT', 'MEDIUM', 'HARD', 'INTERMEDIATE', 'WET')
 COMPOUND_ID = {c: i for i, c in enumerate(COMPOUNDS)}
@@ -225,7 +225,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_simulate_race', 'mcgp_grid_probs', 'mcgp_run_from_ratings', 'mcgp_last_kernel_ms',
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
-           'mcgp_run_from_state')
+           'mcgp_run_from_state', 'mcgp_run_trace')
 
 
 def lib():
@@ -297,6 +297,11 @@ def lib():
             L.mcgp_run_from_state.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.c_uint32, C.c_uint32,
                                               C.POINTER(McgpRaceState), C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64,
                                               C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]
+        if 'mcgp_run_trace' not in missing:
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_trace.restype = C.c_int32
+            L.mcgp_run_trace.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.c_uint32, C.c_uint64,
+                                         C.c_uint64, C.c_uint64, C.c_int32, u64p, u64p, u64p, u64p, u64p, u64p]
         L.mcgp_last_kernel_ms.restype = C.c_int32
         L.mcgp_last_kernel_ms.argtypes = [C.c_int32, C.POINTER(C.c_float)]
         if 'mcgp_stream_kernel_ms' not in missing:

@@ -11,7 +11,9 @@ Flags kept from the reference: --season, --race, --prediction-point, --simulatio
 simulator (the reference parses --simulations and drops it, main.py:14-15 vs predictor.py:284).
 --offline / --fixture replace the FastF1 sessions with a race fixture (see predictor.py); without
 --fixture a synthetic weekend is used (SURVEY.md 8d canonical inputs) and labelled as such.  predict --matchups also
-prints the teammate head-to-heads and the most likely podiums (counted on the device) and adds them to --json.
+prints the teammate head-to-heads and the most likely podiums (counted on the device) and adds them to --json;
+predict --trace prints who leads after lap 1 and at the flag, laps led, fastest lap, pit stops and safety-car odds
+(counted lap by lap on the device) and adds them to --json.
 in-race runs the rest of the race from one or more mid-race state files (RaceState JSON, simulation.py); with several
 --state files every state sees the same random futures and the columns compare the scenarios.
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
@@ -64,9 +66,10 @@ def cmd_predict(args) -> int:
     print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
           f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}\n{'=' * 60}\n")
     t0 = time.perf_counter()
+    extra = {'trace': True} if args.trace else {}
     res = F1Predictor(device=args.device).predict_weekend(
         args.season, args.race, fixture, prediction_point=args.prediction_point,
-        n_simulations=args.simulations, seed=args.seed, matchups=args.matchups)
+        n_simulations=args.simulations, seed=args.seed, matchups=args.matchups, **extra)
     dt = time.perf_counter() - t0
     print(f"Weather: {'Wet' if res['weather'].get('rainfall') else 'Dry'}")
     print(f"Confidence: {res['confidence']}   ({args.simulations / dt:,.0f} simulations/s incl. setup)\n")
@@ -83,10 +86,35 @@ def cmd_predict(args) -> int:
         print('\nMOST LIKELY PODIUMS\n' + '-' * 40)
         for i, row in enumerate(res['likely_podiums'], 1):
             print(f"{i:2}. {' - '.join(f'{d:4}' for d in row['podium'])} {row['probability']:6.2%}")
+    if args.trace:
+        _print_trace(res)
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({k: v for k, v in res.items() if k != 'full_distributions'}, f)
     return 0
+
+
+def _print_trace(res) -> None:
+    """predict --trace: the lap-by-lap block of a predict_weekend(trace=True) result."""
+    leader = res['leader_by_lap']
+    laps = len(next(iter(leader.values()), []))
+    print('\nLAP LEADER\n' + '-' * 40)
+    for k in sorted({1, laps}):
+        top = sorted(leader.items(), key=lambda kv: kv[1][k - 1], reverse=True)[:3]
+        print(f"after lap {k:<4} " + '  '.join(f"{d:4} {p[k - 1]:6.1%}" for d, p in top))
+    print('\nLAPS LED (expected)\n' + '-' * 40)
+    for i, (d, x) in enumerate(sorted(res['expected_laps_led'].items(), key=lambda kv: kv[1], reverse=True)[:5], 1):
+        print(f"{i:2}. {d:4} {x:6.1f}")
+    print()
+    _bars('FASTEST LAP', res['fastest_lap_probabilities'], top=5)
+    print('\nPIT STOPS\n' + '-' * 40)
+    dist = res['pit_stop_distribution']
+    for d in list(dist)[:5]:
+        print(f"{d:4} " + '  '.join(f"{j} stop{'s' if j != 1 else ''} {p:5.1%}" for j, p in enumerate(dist[d]) if p > 0))
+    print('\nSAFETY CAR\n' + '-' * 40)
+    for name, label in (('safety_car', 'safety car'), ('vsc', 'VSC'), ('red_flag', 'red flag')):
+        ev = res['race_event_probabilities'][name]
+        print(f"{label:10} P(at least one) {ev['probability']:6.1%}   expected {ev['expected']:.2f}")
 
 
 def cmd_in_race(args) -> int:
@@ -412,6 +440,9 @@ def main(argv=None) -> int:
     p.add_argument('--json', type=str, default=None)
     p.add_argument('--matchups', action='store_true',
                    help='also count teammate head-to-heads and the most likely podiums (and add them to --json)')
+    p.add_argument('--trace', action='store_true',
+                   help='also count the race lap by lap: leader, laps led, fastest lap, pit stops, safety cars '
+                        '(and add them to --json)')
     p.set_defaults(fn=cmd_predict)
     b = sub.add_parser('backtest', help='sweep a season and score it (backtest.py of the reference)')
     b.add_argument('--seasons', type=int, nargs='+', default=[2024])

@@ -12,6 +12,7 @@
 #include "championship.hip.h"
 #include "matchups.hip.h"
 #include "resume.hip.h"
+#include "trace.hip.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
 #include "frontend_exp.h"
@@ -182,6 +183,10 @@ struct DeviceCtx {
     size_t match_bytes = 0;
     unsigned char *d_resume = nullptr;      // mcgp_run_from_state: parameter block, states, histograms (grow-only)
     size_t resume_bytes = 0;
+    unsigned char *d_trace = nullptr;       // mcgp_run_trace: staging of a chunk and its records (grow-only, bounded)
+    size_t trace_bytes = 0;
+    unsigned char *d_trace_out = nullptr;   // ... and the call's parameter block and counts (grow-only)
+    size_t trace_out_bytes = 0;
     uint32_t last_grid = 0, last_block = 0, last_lds = 0;
     char last_kernel[48] = "";
 };
@@ -249,6 +254,10 @@ void release_ctx(DeviceCtx &c)
     if (c.d_resume) (void)hipFree(c.d_resume);
     c.d_resume = nullptr;
     c.resume_bytes = 0;
+    if (c.d_trace) (void)hipFree(c.d_trace);
+    if (c.d_trace_out) (void)hipFree(c.d_trace_out);
+    c.d_trace = c.d_trace_out = nullptr;
+    c.trace_bytes = c.trace_out_bytes = 0;
     c.batch_bytes = c.batch_retire_bytes = 0;
     for (auto &t : c.timer) {
         if (t.start) (void)hipEventDestroy(t.start);
@@ -290,6 +299,8 @@ int init_ctx_body(int device, DeviceCtx &c)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_resume_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_trace_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
     // (the register kernels raise their dynamic-LDS limit when they are selected: launch())
     return MCGP_OK;
@@ -460,6 +471,17 @@ uint64_t max_sims_per_launch()
         if (v >= 1 && v < cap) cap = v;
     }
     return cap;
+}
+
+// mcgp_run_trace's staging budget: a chunk of the trace holds budget / (L n) simulations (one byte per lap, driver and
+// simulation), at most max_sims_per_launch(), in multiples of 256 when it can (mcgp_run_trace then rounds it down to
+// whole rounds of the device); device memory does not grow with n_sims.
+constexpr uint64_t kTraceStageBytes = 512ull << 20;
+uint64_t trace_chunk_sims(uint32_t n, int total_laps)
+{
+    uint64_t chunk = std::min<uint64_t>(max_sims_per_launch(), std::max<uint64_t>(1, kTraceStageBytes / ((uint64_t)total_laps * n)));
+    if (chunk >= 256) chunk = chunk / 256 * 256;
+    return chunk;
 }
 
 // Front-end inputs of one call, already on the device (c.d_fe_in / c.d_fe_pen), or null.
@@ -1578,6 +1600,141 @@ int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uin
         std::vector<unsigned long long> back(cells);
         HIP_TRY(hipMemcpy(back.data(), d_h, cells * 8, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < cells; ++i) hist_out[i] += back[i];
+        return MCGP_OK;
+    };
+    return body();
+}
+
+int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
+                       uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                       uint64_t *lap_pos_out, uint64_t *laps_led_out, uint64_t *stops_out, uint64_t *fastest_out,
+                       uint64_t *events_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!grid_probs || !hist_out || !lap_pos_out) return fail(MCGP_E_BAD_ARG, "grid_probs / hist_out / lap_pos_out is NULL");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc != MCGP_OK) return rc;
+    if (kp.wide)
+        return fail(MCGP_E_BAD_ARG, "deviates: a trace runs at MCGP_DEVIATES_32 only (the generic kernel has no 53-bit path)");
+    if (n_sims == 0) return MCGP_OK;
+    DeviceCtx *c = nullptr;
+    rc = find_ctx(device, &c);
+    if (rc != MCGP_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    auto body = [&]() -> int {
+        int r = ensure_ctx_locked(device, *c);
+        if (r != MCGP_OK) return r;
+        HIP_TRY(hipSetDevice(device));
+        r = ensure_call_events(*c);
+        if (r != MCGP_OK) return r;
+        const uint32_t L = (uint32_t)kp.total_laps;
+        const uint32_t rows = L * n;
+        // staging of one chunk: rows of `stride` bytes (a multiple of 256: whole, aligned words for the counting
+        // kernels), then the chunk's records
+        const KernelFn geo_fn = reinterpret_cast<KernelFn>(&mcgp::race_trace_kernel);   // (for its register count)
+        uint64_t chunk = trace_chunk_sims(n, (int)L);
+        {
+            // whole rounds of the device (every resident block one batch): a chunk of 5.5 rounds costs 6
+            uint32_t g = 0, b = 0, l = 0;
+            launch_geometry(*c, n, false, geo_fn, chunk, &g, &b, &l);
+            const uint64_t round = (uint64_t)g * b;
+            if (chunk >= round) chunk = chunk / round * round;
+        }
+        chunk = std::min<uint64_t>(chunk, n_sims);
+        const uint64_t stride = (chunk + 255) / 256 * 256;
+        const size_t o_rec = (size_t)rows * stride;
+        const size_t stage_bytes = o_rec + (size_t)stride * 8;
+        if (stage_bytes > c->trace_bytes) {
+            if (c->d_trace) (void)hipFree(c->d_trace);
+            c->d_trace = nullptr;
+            c->trace_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_trace, stage_bytes));
+            c->trace_bytes = stage_bytes;
+        }
+        // parameter block | hist [n][n] | lap_pos [L][n][n + 1] | laps_led [n][L + 1] | stops [n][L + 1] | fastest [n] |
+        // events [3][L + 1]
+        const size_t o_cnt = (sizeof(mcgp::KParams) + 255) / 256 * 256;
+        const size_t c_hist = (size_t)n * n, c_pos = (size_t)rows * (n + 1), c_laps = (size_t)n * (L + 1),
+                     c_fast = n, c_ev = 3 * (size_t)(L + 1);
+        const size_t cells = c_hist + c_pos + 2 * c_laps + c_fast + c_ev;
+        const size_t out_bytes = o_cnt + cells * 8;
+        if (out_bytes > c->trace_out_bytes) {
+            if (c->d_trace_out) (void)hipFree(c->d_trace_out);
+            c->d_trace_out = nullptr;
+            c->trace_out_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_trace_out, out_bytes));
+            c->trace_out_bytes = out_bytes;
+        }
+        const mcgp::KParams *d_kp = reinterpret_cast<const mcgp::KParams *>(c->d_trace_out);
+        unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(c->d_trace_out + o_cnt);
+        unsigned long long *d_pos = d_hist + c_hist, *d_led = d_pos + c_pos, *d_stops = d_led + c_laps;
+        unsigned long long *d_fast = d_stops + c_laps, *d_ev = d_fast + c_fast;
+        uint8_t *d_stage = c->d_trace;
+        uint64_t *d_rec = reinterpret_cast<uint64_t *>(c->d_trace + o_rec);
+        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
+        HIP_TRY(hipMemcpy(c->d_trace_out, &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        const uint64_t grid_cap = (uint64_t)c->cu_count * 8;
+        const size_t laps_lds = 2 * (size_t)(L + 1) * 4, rec_lds = ((size_t)mcgp::kMaxCars + 3 * (size_t)(L + 1)) * 4;
+        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
+        for (uint64_t done = 0; done < n_sims; done += chunk) {
+            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+            // the race: the generic kernel's block shape and LDS
+            launch_geometry(*c, n, false, geo_fn, m, &grid, &block, &lds);
+            if (done == 0) { grid0 = grid; block0 = block; }
+            if (lds > c->lds_per_block)
+                return fail(MCGP_E_HIP, "the trace kernel's block needs " + std::to_string(lds) + " bytes of LDS, the device "
+                                        "offers " + std::to_string(c->lds_per_block) + " per block");
+            const uint64_t n_batches = (m + block - 1) / block;
+            hipLaunchKernelGGL(mcgp::race_trace_kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, m, sim_offset + done,
+                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, d_rec, (uint32_t)n_batches);
+            HIP_TRY(hipGetLastError());
+            // its counts, before the next chunk overwrites the staging
+            const uint64_t words = (m + 3) / 4;
+            const uint64_t tiles = (words + mcgp::kTraceCountBlock - 1) / mcgp::kTraceCountBlock;
+            hipLaunchKernelGGL(mcgp::trace_count_positions, dim3((uint32_t)std::min<uint64_t>(rows, grid_cap)),
+                               dim3(mcgp::kTraceCountBlock), 0, nullptr, d_stage, stride, m, rows, n, d_pos);
+            HIP_TRY(hipGetLastError());
+            if (laps_led_out || stops_out) {
+                const uint64_t gx = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / n));
+                hipLaunchKernelGGL(mcgp::trace_count_laps, dim3((uint32_t)gx, n), dim3(mcgp::kTraceCountBlock), laps_lds,
+                                   nullptr, d_stage, stride, m, n, L, d_led, d_stops);
+                HIP_TRY(hipGetLastError());
+            }
+            if (fastest_out || events_out) {
+                const uint64_t rtiles = (m + mcgp::kTraceCountBlock - 1) / mcgp::kTraceCountBlock;
+                hipLaunchKernelGGL(mcgp::trace_count_records, dim3((uint32_t)std::min<uint64_t>(rtiles, grid_cap)),
+                                   dim3(mcgp::kTraceCountBlock), rec_lds, nullptr, d_rec, m, n, L, d_fast, d_ev);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
+        c->last_timer = kBatchTimer;
+        c->last_grid = grid0;               // the launch shape of the first (fullest) chunk
+        c->last_block = block0;
+        c->last_lds = lds;
+        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "mcgp::race_trace_kernel");
+        // the caller's buffers are added into only once everything has run
+        std::vector<unsigned long long> back(cells);
+        HIP_TRY(hipMemcpy(back.data(), d_hist, cells * 8, hipMemcpyDeviceToHost));
+        const unsigned long long *b = back.data();
+        for (size_t i = 0; i < c_hist; ++i) hist_out[i] += b[i];
+        b += c_hist;
+        for (size_t i = 0; i < c_pos; ++i) lap_pos_out[i] += b[i];
+        b += c_pos;
+        if (laps_led_out)
+            for (size_t i = 0; i < c_laps; ++i) laps_led_out[i] += b[i];
+        b += c_laps;
+        if (stops_out)
+            for (size_t i = 0; i < c_laps; ++i) stops_out[i] += b[i];
+        b += c_laps;
+        if (fastest_out)
+            for (size_t i = 0; i < c_fast; ++i) fastest_out[i] += b[i];
+        b += c_fast;
+        if (events_out)
+            for (size_t i = 0; i < c_ev; ++i) events_out[i] += b[i];
         return MCGP_OK;
     };
     return body();

@@ -22,7 +22,8 @@
 // that are in grid order (Q1), so equal times keep grid order.
 //
 // The block's LDS set-up (load_block), the laps after lap 1 (run_laps) and the classification (classify_and_count)
-// are functions shared with race_resume_kernel (resume.hip.h), which runs a race on from a mid-race state.
+// are functions shared with race_resume_kernel (resume.hip.h), which runs a race on from a mid-race state, and with
+// race_trace_kernel (trace.hip.h), which also shares the start of a race (race_start.inc.h) and observes every lap.
 //
 // Floating point: IEEE binary64 in the reference's evaluation order; this file
 // is compiled with -ffp-contract=off.  The only fused operations are the three
@@ -192,11 +193,22 @@ __device__ __forceinline__ LapEnv load_block(unsigned char *smem, const KParams 
     return e;
 }
 
+// Race events of a lap, as run_laps hands them to its observer: the outcome of the short-circuit chain of :168-176.
+constexpr int kEventNone = 0, kEventRed = 1, kEventSc = 2, kEventVsc = 3;
+
+// The per-lap observer of race_kernel and race_resume_kernel: nothing (the call vanishes at compile time).
+struct NoLapObserver {
+    __device__ __forceinline__ void operator()(const Rows &, int /*lap*/, int /*event*/) {}
+};
+
 // Laps first_lap .. L of one lane's race, reference :166-228, from the state the rows hold after lap first_lap - 1: `ord`
 // sorted by (cumulative time, grid slot), the DRS / dirty-air flags of update_positions, the retirement laps in `out`,
 // and the reference's drs_disabled_until.  race_kernel runs it from lap 2, race_resume_kernel (resume.hip.h) from k + 1.
+// After update_positions of every lap, obs(s, lap, event) sees the rows and the lap's kEvent* (race_trace_kernel,
+// trace.hip.h, records them; the other kernels pass a NoLapObserver).
+template <class LapObserver>
 __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1, uint32_t seed_lo,
-                                         uint32_t seed_hi, int first_lap, int drs_disabled_until)
+                                         uint32_t seed_hi, int first_lap, int drs_disabled_until, LapObserver &obs)
 {
     const KParams *__restrict__ P = e.P;
     const int n = e.n, L = e.L, track = e.track;
@@ -208,6 +220,7 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
     const double dirty_thr = e.dirty_thr, dirty_pen = e.dirty_pen;
     for (int lap = first_lap; lap <= L; ++lap) {
         const int remaining_laps = L - lap;
+        int event = kEventNone;
         // ---- race-interrupting events, :168-176 (short-circuit chain, Q8) ----
         {
             uint32_t e0, e1, e2, e3;
@@ -215,6 +228,7 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
             const bool red = (uint64_t)e0 < P->t_red;
             const bool sc = !red && (uint64_t)e1 < P->t_sc;
             const bool vsc = !red && !sc && (uint64_t)e2 < P->t_vsc;
+            event = red ? kEventRed : sc ? kEventSc : vsc ? kEventVsc : kEventNone;
             if (red || sc || vsc) {
                 // _handle_red_flag :397-431 / _handle_safety_car :334-376 / _handle_vsc :378-395
                 const bool dec_age = sc || (vsc && (uint64_t)e3 < P->t_vsc_tire);
@@ -366,6 +380,7 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
         }
         if (need_sort) sort_by_time(s, n);
         update_positions(s, n, lap > 2 && lap > drs_disabled_until, dirty_thr);   // :227-228
+        obs(s, lap, event);
     }
 }
 
@@ -431,104 +446,11 @@ race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
         const uint64_t sim = sim_offset + local;
         const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
 
-        // ================= _sample_grid, reference :102-145 =================
-        // probs / cdf scratch lives in the `last` rows (not needed until lap 2).
-        {
-            uint32_t remaining = (n >= 32) ? 0xffffffffu : ((1u << n) - 1u);
-            int n_remaining = n;
-            uint32_t g0 = 0, g1 = 0, g2 = 0, g3 = 0;
-            for (int pos = 0; pos < n; ++pos) {
-                uint32_t sel;
-                if (fixed_grid) {
-                    sel = fixed_grid[pos];
-                } else {
-                    if ((pos & 3) == 0)
-                        philox4x32_10(c0, c1, 0u, kPurposeGrid | (uint32_t)(pos >> 2), seed_lo, seed_hi, g0, g1, g2, g3);
-                    const uint32_t gw = (pos & 3) == 0 ? g0 : (pos & 3) == 1 ? g1 : (pos & 3) == 2 ? g2 : g3;
-                    const double u = u32_to_unit(gw);
-                    double total = 0.0;                                   // :119-123
-                    for (int d = 0; d < n; ++d) {
-                        const double p = ((remaining >> d) & 1u) ? P->grid_probs[d * n + pos] : 0.0;
-                        total = total + p;
-                    }
-                    double prob_sum = 0.0;                                // :125-133
-                    for (int d = 0; d < n; ++d) {
-                        const bool rem = (remaining >> d) & 1u;
-                        double p;
-                        if (total > 0) p = (rem ? P->grid_probs[d * n + pos] : 0.0) / total;
-                        else p = rem ? 1.0 / (double)n_remaining : 0.0;
-                        s.Last(d) = p;
-                        prob_sum = prob_sum + p;
-                    }
-                    const bool renorm = prob_sum > 0 && fabs(prob_sum - 1.0) > 1e-9;   // :134-135
-                    // np.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; searchsorted(u, 'right')
-                    double acc = 0.0;
-                    for (int d = 0; d < n; ++d) {
-                        double p = s.Last(d);
-                        if (renorm) p = p / prob_sum;
-                        acc = (d == 0) ? p : acc + p;
-                        s.Last(d) = acc;
-                    }
-                    const double cdf_last = acc;
-                    sel = 0;
-                    for (int d = 0; d < n; ++d)
-                        if (s.Last(d) / cdf_last <= u) sel = (uint32_t)d + 1u;
-                    if (sel >= (uint32_t)n) sel = (uint32_t)n - 1u;       // unreachable: cdf[-1] == 1 > u
-                }
-                if ((remaining >> sel) & 1u) { remaining &= ~(1u << sel); --n_remaining; }
-                // _initialize_cars, reference :244-273
-                uint32_t comp, age;
-                if (track == 2) { comp = 4u; age = 0u; }
-                else if (track == 1) { comp = 3u; age = 0u; }
-                else { comp = pos < 10 ? 0u : 1u; age = pos < 10 ? 4u : 0u; }
-                s.Pk(sel) = age | (comp << kCompShift) | ((1u << comp) << kUsedShift) | ((uint32_t)pos << kGposShift);
-                s.Cum(sel) = 0.0;
-                s.Ord(pos) = (uint8_t)sel;
-            }
-            for (int d = 0; d < n; ++d) s.Last(d) = 0.0;
-        }
-
-        // ================= _simulate_lap_1, reference :275-311 =================
-        for (int pos = 0; pos < n; ++pos) {
-            const uint32_t d = s.Ord(pos);
-            uint32_t pk = s.Pk(d);
-            uint32_t w0, w1, w2, w3;
-            philox4x32_10(c0, c1, 1u, kPurposeCar | d, seed_lo, seed_hi, w0, w1, w2, w3);
-            if ((uint64_t)w0 < e.dnf1[d]) {
-                s.Pk(d) = (pk & ~kAgeMask) | kDnf | 1u;
-                continue;
-            }
-            const uint32_t comp = (pk >> kCompShift) & 7u;
-            const uint32_t age = pk & kAgeMask;
-            const double eff = e.cdeg[comp] * e.factor[d];
-            const double tire = (double)age * eff;
-            const double fuel_effect = (110.0 - 110.0) * 0.03;
-            const double noise = 0.0 + e.var[d] * (double)normal_from_u32(w1, e.norm);
-            const double base_lap = e.base[d] + tire - fuel_effect + e.cdelta[comp] - 0.0 + noise;
-            double pf = 0.5 + (double)(pos + 1) * 0.1;
-            if (!(pf < 1.5)) pf = 1.5;
-            double sd = 0.0 + pf * (double)normal_from_u32(w2, e.norm);
-            if (pos + 1 <= 3 && 1.0 < sd) sd = 1.0;
-            const double lap_time = base_lap - sd * 0.5;
-            s.Cum(d) = 0.0 + lap_time;
-            s.Pk(d) = (pk & ~kAgeMask) | (age + 1u);
-        }
-        sort_by_time(s, n);
-        update_positions(s, n, false, e.dirty_thr);
-
-        // ================= retirements of laps 2..L (:190-197), drawn once per race: race_common.hip.h =================
-        {
-            uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
-            for (int d = 0; d < n; ++d) {
-                if ((d & 3) == 0)
-                    philox4x32_10(c0, c1, 0u, kPurposeRetire | (uint32_t)(d >> 2), seed_lo, seed_hi, r0, r1, r2, r3);
-                const uint32_t rw = (d & 3) == 0 ? r0 : (d & 3) == 1 ? r1 : (d & 3) == 2 ? r2 : r3;
-                s.Out(d) = (uint16_t)draw_retirement_lap(rw, e.dnf[d], L);
-            }
-        }
+#include "race_start.inc.h"
 
         // ================= laps 2..L, reference :166-228 =================
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, 2, 0);
+        NoLapObserver none;
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, 2, 0, none);
 
         // ================= classification, reference :230-242 =================
         classify_and_count(s, n, s_hist, orders ? orders + local * (uint64_t)n : nullptr);

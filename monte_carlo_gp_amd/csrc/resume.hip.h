@@ -90,7 +90,8 @@ race_resume_kernel(const KParams *__restrict__ P, const ResumeState *__restrict_
         }
 
         // ================= laps k+1..L, reference :166-228 =================
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, k + 1, drs_disabled_until);
+        NoLapObserver none;
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, k + 1, drs_disabled_until, none);
 
         // ================= classification, reference :230-242 =================
         classify_and_count(s, n, s_hist,

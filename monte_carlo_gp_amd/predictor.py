@@ -171,13 +171,17 @@ class F1Predictor:
 
     def predict_weekend(self, season: int, race: str, fixture: dict | str, grid_penalties=None, circuit_info=None,
                         prediction_point: str = 'fp2', actual_grid=None, n_simulations: int = 10000,
-                        seed: int | None = None, matchups: bool = False) -> dict:
+                        seed: int | None = None, matchups: bool = False, trace: bool = False) -> dict:
         """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU.
 
         matchups=True (not in the reference): the race runs through RaceSimulator.run_matchups -- the same simulations,
         so every key keeps its value -- and the result gains 'head_to_head' ({a: {b: P(a ahead of b)}}),
         'teammate_battles' (MatchupResult.teammate_battles over the race config's teams) and 'likely_podiums' (the
-        MATCHUP_PODIUMS most likely ordered podiums, [{'podium': [P1, P2, P3], 'probability': p}])."""
+        MATCHUP_PODIUMS most likely ordered podiums, [{'podium': [P1, P2, P3], 'probability': p}]).
+
+        trace=True (not in the reference): the race also runs through RaceSimulator.run_trace -- again the same
+        simulations -- and the result gains the keys of trace_keys: 'leader_by_lap', 'expected_laps_led',
+        'pit_stop_distribution', 'fastest_lap_probabilities' and 'race_event_probabilities'."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -188,18 +192,20 @@ class F1Predictor:
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
             # same inputs, the matrix built on the device from the ratings (no host matrix crosses PCIe)
             ratings = {d: self.elo_system.ratings.get(d, {}).get('quali', self.elo_system.initial) for d in inp['drivers']}
-            if matchups:
-                # the same matrix, read back from the device front end and handed to the matchups run
+            if matchups or trace:
+                # the same matrix, read back from the device front end and handed to the matchups / trace run
                 grid = sim.grid_probs_on_device(inp['drivers'], ratings, fixture.get('quali_features', {}),
                                                 grid_penalties or {})
-                return self._with_matchups(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid)
+                return self._with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups,
+                                         trace)
             race_probs, grid = sim.run_from_ratings(
                 n_simulations, inp['drivers'], ratings, fixture.get('quali_features', {}), grid_penalties or {},
                 inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'], seed=seed,
                 track_condition=inp['track_condition'])
             return pack_result(inp['drivers'], grid, race_probs, inp['weather'], prediction_point, actual_grid)
-        if matchups:
-            return self._with_matchups(sim, inp, inp['grid_probs'], n_simulations, seed, prediction_point, actual_grid)
+        if matchups or trace:
+            return self._with_counts(sim, inp, inp['grid_probs'], n_simulations, seed, prediction_point, actual_grid,
+                                     matchups, trace)
         race_probs = sim.run_monte_carlo(
             n_simulations=n_simulations, grid_probs=inp['grid_probs'], base_pace=inp['base_pace'],
             tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
@@ -234,12 +240,22 @@ class F1Predictor:
         return out[0] if single else out
 
     @staticmethod
-    def _with_matchups(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid) -> dict:
-        """predict_weekend's result from a run_matchups call on `grid`, with the matchup keys added."""
-        m = sim.run_matchups(n_simulations, grid, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
-                             inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'])
-        res = pack_result(inp['drivers'], grid, m.position_probabilities, inp['weather'], prediction_point, actual_grid)
-        res.update(matchup_keys(m, inp['config'].driver_teams))
+    def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace) -> dict:
+        """predict_weekend's result from run_matchups and / or run_trace calls on `grid` (the same simulations: one seed
+        for both), with their keys added."""
+        args = (n_simulations, grid, inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'])
+        seed = sim._resolve_seed(seed)
+        res = None
+        if matchups:
+            m = sim.run_matchups(*args, seed=seed, track_condition=inp['track_condition'])
+            res = pack_result(inp['drivers'], grid, m.position_probabilities, inp['weather'], prediction_point, actual_grid)
+            res.update(matchup_keys(m, inp['config'].driver_teams))
+        if trace:
+            t = sim.run_trace(*args, seed=seed, track_condition=inp['track_condition'])
+            if res is None:
+                res = pack_result(inp['drivers'], grid, t.position_probabilities, inp['weather'], prediction_point,
+                                  actual_grid)
+            res.update(trace_keys(t))
         return res
 
 
@@ -253,6 +269,21 @@ def matchup_keys(m, driver_teams) -> dict:
         'head_to_head': m.ahead_probabilities,
         'teammate_battles': m.teammate_battles(driver_teams),
         'likely_podiums': [{'podium': list(p), 'probability': q} for p, q in podiums],
+    }
+
+
+def trace_keys(t) -> dict:
+    """The keys predict_weekend(trace=True) adds, JSON-safe, from a TraceResult: per driver, P(leading after each lap),
+    expected laps led, the pit-stop distribution up to the largest count any simulation reached, P(fastest lap); and
+    per race event P(at least one) and the expected number."""
+    used = int(np.max(np.nonzero(t.stops.sum(axis=0))[0])) + 1 if t.stops.any() else 1
+    return {
+        'leader_by_lap': {d: [float(x) for x in p] for d, p in t.leader_probabilities.items()},
+        'expected_laps_led': t.expected_laps_led,
+        'pit_stop_distribution': {d: [float(x) for x in p[:used]] for d, p in t.pit_stop_distribution.items()},
+        'expected_pit_stops': t.expected_pit_stops,
+        'fastest_lap_probabilities': t.fastest_lap_probabilities,
+        'race_event_probabilities': t.event_probabilities,
     }
 
 

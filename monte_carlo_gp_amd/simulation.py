@@ -405,6 +405,50 @@ class RaceSimulator:
         return MatchupResult(drivers=drivers, n_simulations=n_simulations, hist=self.last_histogram, ahead=total(1),
                              podium=total(2) if want_podium else None)
 
+    def run_trace(
+        self,
+        n_simulations: int,
+        grid_probs: dict,
+        base_pace: dict,
+        tire_deg: dict,
+        driver_variance: dict,
+        driver_dnf_rates: dict | None = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+    ) -> 'TraceResult':
+        """run_monte_carlo's race, counted lap by lap on the device (include/mcgp.h: mcgp_run_trace): running positions
+        after every lap, laps led, pit stops, fastest lap and race events.  Same arguments, simulations and sharding over
+        self.devices as run_monte_carlo; the TraceResult's position histogram equals run_monte_carlo's.  32-bit deviates
+        only.  Sets last_histogram / last_drivers."""
+        drivers = [str(d) for d in grid_probs.keys()]
+        n, L = len(drivers), int(self.config.total_laps)
+        n_simulations = int(n_simulations)
+        if not drivers or n_simulations <= 0:
+            self.last_histogram, self.last_drivers = np.zeros((n, n), np.int64), drivers
+            return TraceResult.empty(drivers, L, max(n_simulations, 0))
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers)
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            out = TraceResult.empty(drivers, L, count, dtype=np.uint64)
+            rc = lib.mcgp_run_trace(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g), n, int(count),
+                                    int(sim_offset) + int(offset), seed64, device, u64(out.hist), u64(out.lap_pos),
+                                    u64(out.laps_led), u64(out.stops), u64(out.fastest), u64(out.events))
+            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([getattr(r, k) for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        res = TraceResult(drivers=drivers, n_simulations=n_simulations, total_laps=L, hist=total('hist'),
+                          lap_pos=total('lap_pos'), laps_led=total('laps_led'), stops=total('stops'),
+                          fastest=total('fastest'), events=total('events'))
+        self.last_histogram = res.hist
+        self.last_drivers = drivers
+        return res
+
     def run_from_state(
         self,
         n_simulations: int,
@@ -666,6 +710,101 @@ class MatchupResult:
     def _need_podium(self):
         if self.podium is None:
             raise ValueError('no podium counts: run_matchups(podiums=True) with at least 3 drivers')
+
+
+RACE_EVENTS = ('red_flag', 'safety_car', 'vsc')          # the rows of TraceResult.events
+
+
+@dataclass
+class TraceResult:
+    """What RaceSimulator.run_trace returns: integer counts over n_simulations of what happened lap by lap, read after the
+    end of each lap (include/mcgp.h: mcgp_run_trace has the definitions).  L = total_laps, n = len(drivers):
+      hist      [n][n]        [driver][position - 1], run_monte_carlo's histogram
+      lap_pos   [L][n][n + 1] [lap - 1][driver][running position - 1, or n = retired]
+      laps_led  [n][L + 1]    [driver][laps led]
+      stops     [n][L + 1]    [driver][pit stops]
+      fastest   [n]           simulations in which the driver sets the fastest lap (laps 2..L)
+      events    [3][L + 1]    [red flag, safety car, VSC][number in the race]"""
+    drivers: list
+    n_simulations: int
+    total_laps: int
+    hist: np.ndarray
+    lap_pos: np.ndarray
+    laps_led: np.ndarray
+    stops: np.ndarray
+    fastest: np.ndarray
+    events: np.ndarray
+
+    @classmethod
+    def empty(cls, drivers, total_laps, n_simulations=0, dtype=np.int64) -> 'TraceResult':
+        n, L = len(drivers), int(total_laps)
+        z = lambda *shape: np.zeros(shape, dtype)
+        return cls(drivers=list(drivers), n_simulations=int(n_simulations), total_laps=L, hist=z(n, n),
+                   lap_pos=z(L, n, n + 1), laps_led=z(n, L + 1), stops=z(n, L + 1), fastest=z(n), events=z(3, L + 1))
+
+    def _p(self, counts):
+        return np.asarray(counts, np.float64) / max(self.n_simulations, 1)
+
+    @property
+    def position_probabilities(self) -> dict:
+        """{driver: {position: probability}}, what run_monte_carlo returns for the same arguments."""
+        return histogram_to_probs(self.hist, self.drivers, self.n_simulations)
+
+    @property
+    def position_probabilities_by_lap(self) -> dict:
+        """{driver: [L][n + 1] array}: P(running position p + 1 after lap k + 1), last column P(retired by then)."""
+        p = self._p(self.lap_pos)
+        return {d: p[:, i, :] for i, d in enumerate(self.drivers)}
+
+    @property
+    def leader_probabilities(self) -> dict:
+        """{driver: [L] array}: P(leading the race after lap k + 1) -- the lap chart."""
+        p = self._p(self.lap_pos[:, :, 0])
+        return {d: p[:, i] for i, d in enumerate(self.drivers)}
+
+    @property
+    def retired_by_lap(self) -> dict:
+        """{driver: [L] array}: P(retired by the end of lap k + 1)."""
+        p = self._p(self.lap_pos[:, :, -1])
+        return {d: p[:, i] for i, d in enumerate(self.drivers)}
+
+    @property
+    def laps_led_distribution(self) -> dict:
+        """{driver: [L + 1] array}: P(leading exactly j laps)."""
+        p = self._p(self.laps_led)
+        return {d: p[i] for i, d in enumerate(self.drivers)}
+
+    @property
+    def expected_laps_led(self) -> dict:
+        j = np.arange(self.total_laps + 1)
+        return {d: float(self._p(self.laps_led[i]) @ j) for i, d in enumerate(self.drivers)}
+
+    @property
+    def pit_stop_distribution(self) -> dict:
+        """{driver: [L + 1] array}: P(exactly j pit stops)."""
+        p = self._p(self.stops)
+        return {d: p[i] for i, d in enumerate(self.drivers)}
+
+    @property
+    def expected_pit_stops(self) -> dict:
+        j = np.arange(self.total_laps + 1)
+        return {d: float(self._p(self.stops[i]) @ j) for i, d in enumerate(self.drivers)}
+
+    @property
+    def fastest_lap_probabilities(self) -> dict:
+        """{driver: P(sets the fastest lap)}; they sum to less than 1 when some races have no lap 2 completed."""
+        p = self._p(self.fastest)
+        return {d: float(p[i]) for i, d in enumerate(self.drivers)}
+
+    @property
+    def event_probabilities(self) -> dict:
+        """{'red_flag' | 'safety_car' | 'vsc': {'probability': P(at least one), 'expected': expected number}}."""
+        j = np.arange(self.total_laps + 1)
+        out = {}
+        for k, name in enumerate(RACE_EVENTS):
+            p = self._p(self.events[k])
+            out[name] = {'probability': float(1.0 - p[0]) if self.n_simulations else 0.0, 'expected': float(p @ j)}
+        return out
 
 
 DEFAULT_POINTS = (25, 18, 15, 12, 10, 8, 6, 4, 2, 1)      # a Grand Prix, positions 1-10
