@@ -32,7 +32,8 @@ extern "C" {
 /* 3: mcgp_run_championship */
 /* 4: mcgp_run_matchups */
 /* 5: mcgp_race_state, mcgp_run_from_state */
-/* 6: mcgp_run_trace */
+/* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
+ * function changed, so the version stays; a caller tests for the symbol) */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -278,6 +279,58 @@ int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                        uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                        uint64_t *lap_pos_out, uint64_t *laps_led_out, uint64_t *stops_out, uint64_t *fastest_out,
                        uint64_t *events_out);
+
+/* A pit plan: one driver's strategy in a scenario of mcgp_run_strategies. */
+#define MCGP_MAX_PLAN_STOPS 8
+#define MCGP_MAX_SCENARIOS 64
+typedef struct mcgp_pit_plan {
+    int32_t driver;                   /* driver index, 0 .. n - 1, at most one plan per driver and scenario */
+    int32_t start_compound;           /* -1: the model's start; else MCGP_SOFT .. MCGP_WET (grid runs only) */
+    int32_t start_age;                /* 0 .. 1023 - total_laps with start_compound >= 0; 0 otherwise */
+    uint32_t n_stops;                 /* 0 .. MCGP_MAX_PLAN_STOPS */
+    int16_t stop_lap[MCGP_MAX_PLAN_STOPS];        /* strictly increasing; [2, L] from the grid, [lap + 1, L] from a state */
+    uint8_t stop_compound[MCGP_MAX_PLAN_STOPS];   /* MCGP_SOFT .. MCGP_WET */
+} mcgp_pit_plan;
+
+/* Pit-strategy comparison: one race under n_scenarios sets of planned pit stops, with common random numbers.
+ * Scenario s holds plan_count[s] plans (concatenated in `plans`), at most one per driver; drivers without a plan keep
+ * the race model's rule.  For a planned driver:
+ *   - the rule is off: the rule-based stop never fires for this car;
+ *   - on each stop lap p it stops where the rule's stop would happen: after its own lap time of lap p is added and
+ *     before the overtakes, only if it is still running after that lap.  The stop adds pit_loss, sets the compound,
+ *     sets the tyre age to 0 and adds the compound to the used set.  The rule's "more than 5 laps remain" guard does
+ *     not apply;
+ *   - race events are unchanged: a red flag's free tyre change and the safety car / VSC age decrement apply to it as
+ *     to every car, and its later planned stops still happen;
+ *   - from the grid (state NULL, grid_probs given), start_compound -1 is the model's start (SOFT at age 4 on slots
+ *     1-10, MEDIUM at age 0 behind, INTERMEDIATE / WET on a damp / wet track); otherwise the car starts on that
+ *     compound at start_age and its used set is that compound.  Lap 1 has no pit step, so stops lie in [2, L];
+ *   - from a state (grid_probs NULL), the state fixes the tyres: start_compound must be -1 and start_age 0; stops lie
+ *     in [state->lap + 1, L].
+ * The two-compound rule of a dry race is NOT enforced here: a plan may run one dry compound (the Python layer checks).
+ * Random numbers: simulation i of every scenario has id sim_offset + i and draws what mcgp_run's (from the grid) or
+ * mcgp_run_from_state's (from a state, sim_offsets[0] = sim_offset) simulation i draws.  An empty scenario is therefore
+ * bit-identical to those calls, and the grid, the retirement laps and the event draws are shared by every scenario.
+ * The lap noise is drawn per place in the running order, so a changed strategy reassigns it: the pairing between
+ * scenarios is partial.
+ *   hist_out    [S][n][n]      [scenario][driver][position - 1]
+ *   delta_out   [S][n][2n - 1] [scenario][driver][(pos_s - pos_0) + n - 1]: the paired change of each driver's position
+ *                              against scenario 0 in the same simulation (scenario 0 is all in the centre bin); or NULL
+ *   orders_out  [S][n_sims][n] driver index classified p-th, or NULL
+ * hist_out and delta_out are ACCUMULATED into, orders_out is written, and all only after every launch has succeeded:
+ * on an error they are left as they were.  Every argument is checked before any device lookup: n_scenarios outside
+ * [1, 64], a plan outside the limits above (driver, a duplicate driver, start fields, n_stops, a stop lap or
+ * compound), an invalid state (as mcgp_run_from_state checks it), grid_probs NULL from the grid or given with a state,
+ * deviates other than MCGP_DEVIATES_32 (the generic kernel runs the scenarios and has no 53-bit path), or a NULL
+ * pointer is MCGP_E_BAD_ARG with a message that names the scenario, the plan and the field.  n_sims == 0 succeeds
+ * without a device.  The device work goes chunk by chunk through a staging buffer of 256 MiB / (S n) simulations (one
+ * byte per scenario, simulation and driver) that a counting kernel reads; device memory does not grow with n_sims.  Any
+ * split of [0, N) over calls, sim_offsets or devices sums to the same counts.  mcgp_last_kernel_ms afterwards = the
+ * device time of everything the call ran; mcgp_last_launch_info describes its first chunk's race launch. */
+int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                            const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                            const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                            int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint8_t *orders_out);
 
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver

@@ -4,13 +4,16 @@ Public surface mirrors reference src/simulation.py: CarState, RaceConfig, RaceSi
 races in one launch; RaceSimulator.run_matchups counts head-to-heads and podiums of one race (MatchupResult);
 run_championship simulates the drivers' and constructors' standings over a calendar of races;
 RaceSimulator.run_from_state simulates the rest of a race from a mid-race RaceState; RaceSimulator.run_trace counts what
-happened lap by lap (TraceResult: lap chart, laps led, pit stops, fastest lap, race events).
+happened lap by lap (TraceResult: lap chart, laps led, pit stops, fastest lap, race events);
+RaceSimulator.run_strategies compares pit strategies (PitPlan, pit_window, StrategyResult).
 The compute path is the HIP library libmcgp_hip.so (C ABI: include/mcgp.h); there is no
 CPU fallback.
 """
-from .simulation import (CarState, ChampionshipResult, MatchupResult, RaceConfig, RaceSimulator, RaceState,  # noqa: F401
-                         TraceResult, histogram_to_probs, run_championship, run_monte_carlo_batch)
+from .simulation import (CarState, ChampionshipResult, MatchupResult, PitPlan, RaceConfig, RaceSimulator,  # noqa: F401
+                         RaceState, StrategyResult, TraceResult, histogram_to_probs, pit_window, run_championship,
+                         run_monte_carlo_batch)
 from . import config  # noqa: F401
 
-__all__ = ['CarState', 'ChampionshipResult', 'MatchupResult', 'RaceConfig', 'RaceSimulator', 'RaceState', 'TraceResult',
-           'histogram_to_probs', 'run_championship', 'run_monte_carlo_batch', 'config']
+__all__ = ['CarState', 'ChampionshipResult', 'MatchupResult', 'PitPlan', 'RaceConfig', 'RaceSimulator', 'RaceState',
+           'StrategyResult', 'TraceResult', 'histogram_to_probs', 'pit_window', 'run_championship', 'run_monte_carlo_batch',
+           'config']

@@ -56,6 +56,18 @@ class McgpRaceState(C.Structure):
     ]
 
 
+MAX_PLAN_STOPS = 8
+MAX_SCENARIOS = 64
+
+
+class McgpPitPlan(C.Structure):
+    """mcgp_pit_plan: one driver's planned stops in a scenario of mcgp_run_strategies."""
+    _fields_ = [
+        ('driver', C.c_int32), ('start_compound', C.c_int32), ('start_age', C.c_int32), ('n_stops', C.c_uint32),
+        ('stop_lap', C.c_int16 * MAX_PLAN_STOPS), ('stop_compound', C.c_uint8 * MAX_PLAN_STOPS),
+    ]
+
+
 _hash_module = None
 _hash_cache = {}            # key -> value; keys carry (path, mtime_ns, size) of every file the value was read from
 
@@ -225,7 +237,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_simulate_race', 'mcgp_grid_probs', 'mcgp_run_from_ratings', 'mcgp_last_kernel_ms',
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
-           'mcgp_run_from_state', 'mcgp_run_trace')
+           'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies')
 
 
 def lib():
@@ -302,6 +314,13 @@ def lib():
             L.mcgp_run_trace.restype = C.c_int32
             L.mcgp_run_trace.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.c_uint32, C.c_uint64,
                                          C.c_uint64, C.c_uint64, C.c_int32, u64p, u64p, u64p, u64p, u64p, u64p]
+        if 'mcgp_run_strategies' not in missing:
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_strategies.restype = C.c_int32
+            L.mcgp_run_strategies.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.POINTER(McgpRaceState),
+                                              C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
+                                              C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, u64p, u64p,
+                                              C.POINTER(C.c_uint8)]
         L.mcgp_last_kernel_ms.restype = C.c_int32
         L.mcgp_last_kernel_ms.argtypes = [C.c_int32, C.POINTER(C.c_float)]
         if 'mcgp_stream_kernel_ms' not in missing:

@@ -5,6 +5,8 @@
     python -m monte_carlo_gp_amd.cli export-fixtures --seasons 2024 --out DIR
     python -m monte_carlo_gp_amd.cli championship --season 2024 --from-round 18 --simulations 10000000 --seed 7
     python -m monte_carlo_gp_amd.cli in-race --race Bahrain --season 2024 --offline --state lap30.json --simulations 1000000
+    python -m monte_carlo_gp_amd.cli strategy --race Bahrain --season 2024 --offline --driver VER --plan one=:25/HARD \
+        --plan two=SOFT:15/MEDIUM,38/SOFT --window 15-30/HARD --simulations 1000000 --seed 7
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -16,6 +18,9 @@ predict --trace prints who leads after lap 1 and at the flag, laps led, fastest 
 (counted lap by lap on the device) and adds them to --json.
 in-race runs the rest of the race from one or more mid-race state files (RaceState JSON, simulation.py); with several
 --state files every state sees the same random futures and the columns compare the scenarios.
+strategy compares pit strategies for one driver: `model` (the race model's own stops) first, then each --plan
+NAME=START:LAP/COMP,LAP/COMP (START empty: the model's start) and each lap of a --window A-B/COMP sweep, all with common
+random numbers, from the grid or from a --state file.
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
 on the data path; results are gathered once).
 """
@@ -150,6 +155,109 @@ def cmd_in_race(args) -> int:
         with open(args.json, 'w') as f:
             json.dump([dict({k: v for k, v in r.items() if k != 'full_distributions'}, state=path)
                        for r, path in zip(res, args.state)], f)
+    return 0
+
+
+def _compound(text: str) -> str:
+    """A compound name, case-insensitive, or its first letter (S, M, H, I, W)."""
+    from . import _native as N
+    t = text.strip().upper()
+    for c in N.COMPOUNDS:
+        if t == c or (len(t) == 1 and c[0] == t):
+            return c
+    raise ValueError(f'unknown compound {text!r}: one of {", ".join(N.COMPOUNDS)} or its first letter')
+
+
+def parse_plan(text: str, driver: str):
+    """--plan NAME=START:LAP/COMP,LAP/COMP -> (NAME, PitPlan); START empty: the model's start; no stops after the
+    colon: the car never stops."""
+    from .simulation import PitPlan
+    name, sep, rest = text.partition('=')
+    if not sep or not name.strip():
+        raise ValueError(f'--plan {text!r}: expected NAME=START:LAP/COMP,...')
+    start, sep, stops_text = rest.partition(':')
+    if not sep:
+        raise ValueError(f'--plan {text!r}: expected NAME=START:LAP/COMP,... (START may be empty)')
+    stops = []
+    for item in filter(None, (x.strip() for x in stops_text.split(','))):
+        lap, sep, comp = item.partition('/')
+        if not sep or not lap.strip().isdigit():
+            raise ValueError(f'--plan {text!r}: a stop is LAP/COMP, got {item!r}')
+        stops.append((int(lap), _compound(comp)))
+    return name.strip(), PitPlan(driver, stops, start=_compound(start) if start.strip() else None)
+
+
+def parse_window(text: str):
+    """--window A-B/COMP -> (range(A, B + 1), COMP)."""
+    laps, sep, comp = text.partition('/')
+    a, dash, b = laps.partition('-')
+    if not sep or not dash or not a.strip().isdigit() or not b.strip().isdigit() or int(b) < int(a):
+        raise ValueError(f'--window {text!r}: expected A-B/COMP with A <= B')
+    return range(int(a), int(b) + 1), _compound(comp)
+
+
+def strategy_scenarios(driver: str, plans=(), window=None) -> dict:
+    """The strategy command's scenarios: 'model' (no plan) first, then each --plan, then the --window sweep."""
+    from .simulation import pit_window
+    out = {'model': []}
+    for text in plans or ():
+        name, plan = parse_plan(text, driver)
+        if name in out:
+            raise ValueError(f'--plan: scenario {name!r} given twice')
+        out[name] = [plan]
+    if window:
+        laps, comp = parse_window(window)
+        for name, plans_ in pit_window(driver, laps, comp).items():
+            out.setdefault(name, plans_)
+    return out
+
+
+def cmd_strategy(args) -> int:
+    from .simulation import RaceState
+    fixture = synthetic_fixture()
+    if args.fixture:
+        with open(args.fixture) as f:
+            fixture = json.load(f)
+    elif not args.offline:
+        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+        return 2
+    state = None
+    if args.state:
+        with open(args.state) as f:
+            state = RaceState.from_json(json.load(f))
+    try:
+        scenarios = strategy_scenarios(args.driver, args.plan, args.window)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    if len(scenarios) < 2:
+        print('error: give at least one --plan or --window to compare with the model', file=sys.stderr)
+        return 2
+    print(f"\n{'=' * 60}\nF1 Pit Strategy: {args.season} {args.race}, {args.driver}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
+          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
+    print('=' * 60 + '\n')
+    res = F1Predictor(device=args.device).predict_strategies(args.season, args.race, fixture, scenarios, state=state,
+                                                             n_simulations=args.simulations, seed=args.seed,
+                                                             allow_single_compound=args.allow_single_compound)
+    d = args.driver
+    rows = []
+    print(f"{'scenario':16} {'win':>7} {'podium':>7} {'E[pts]':>7} {'E[pos]':>7} {'P(better)':>10}  gain +- SE")
+    print('-' * 78)
+    for name in res.names:
+        c = res.compare(name, d)
+        row = dict(scenario=name, win=res.win_probability(name, d), podium=res.podium_probability(name, d),
+                   expected_points=res.expected_points(name)[d], expected_position=res.expected_position(name)[d],
+                   p_better=c['p_better'], p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'],
+                   se=c['se'], win_probabilities={x: res.win_probability(name, x) for x in res.drivers})
+        rows.append(row)
+        print(f"{name[:16]:16} {row['win']:7.1%} {row['podium']:7.1%} {row['expected_points']:7.2f} "
+              f"{row['expected_position']:7.2f} {row['p_better']:10.1%}  {row['mean_gain']:+.3f} +- {row['se']:.3f}")
+    print(f"\nbest by expected points: {res.best(d)}")
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump({'driver': d, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
     return 0
 
 
@@ -480,6 +588,23 @@ def main(argv=None) -> int:
     r.add_argument('--device', type=int, default=0)
     r.add_argument('--json', type=str, default=None)
     r.set_defaults(fn=cmd_in_race)
+    t = sub.add_parser('strategy', help="compare pit strategies for one driver against the model's own stops")
+    t.add_argument('--season', type=int, default=2025)
+    t.add_argument('--race', type=str, required=True)
+    t.add_argument('--driver', type=str, required=True)
+    t.add_argument('--plan', type=str, action='append', default=[],
+                   help='NAME=START:LAP/COMP,LAP/COMP (START empty: the model\'s start); repeat for more scenarios')
+    t.add_argument('--window', type=str, default=None, help='A-B/COMP: one single-stop scenario per lap A..B')
+    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
+    t.add_argument('--allow-single-compound', action='store_true',
+                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
+    t.add_argument('--simulations', type=int, default=100000)
+    t.add_argument('--seed', type=int, default=None)
+    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
+    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
+    t.add_argument('--device', type=int, default=0)
+    t.add_argument('--json', type=str, default=None)
+    t.set_defaults(fn=cmd_strategy)
     args = ap.parse_args(argv)
     return args.fn(args)
 

@@ -13,6 +13,7 @@
 #include "matchups.hip.h"
 #include "resume.hip.h"
 #include "trace.hip.h"
+#include "strategy.hip.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
 #include "frontend_exp.h"
@@ -187,6 +188,10 @@ struct DeviceCtx {
     size_t trace_bytes = 0;
     unsigned char *d_trace_out = nullptr;   // ... and the call's parameter block and counts (grow-only)
     size_t trace_out_bytes = 0;
+    uint8_t *d_strat_stage = nullptr;       // mcgp_run_strategies: staged positions of a chunk (grow-only, bounded)
+    size_t strat_stage_bytes = 0;
+    unsigned char *d_strat = nullptr;       // ... and the call's parameter block, state, plans and counts (grow-only)
+    size_t strat_bytes = 0;
     uint32_t last_grid = 0, last_block = 0, last_lds = 0;
     char last_kernel[48] = "";
 };
@@ -258,6 +263,11 @@ void release_ctx(DeviceCtx &c)
     if (c.d_trace_out) (void)hipFree(c.d_trace_out);
     c.d_trace = c.d_trace_out = nullptr;
     c.trace_bytes = c.trace_out_bytes = 0;
+    if (c.d_strat_stage) (void)hipFree(c.d_strat_stage);
+    if (c.d_strat) (void)hipFree(c.d_strat);
+    c.d_strat_stage = nullptr;
+    c.d_strat = nullptr;
+    c.strat_stage_bytes = c.strat_bytes = 0;
     c.batch_bytes = c.batch_retire_bytes = 0;
     for (auto &t : c.timer) {
         if (t.start) (void)hipEventDestroy(t.start);
@@ -480,6 +490,17 @@ constexpr uint64_t kTraceStageBytes = 512ull << 20;
 uint64_t trace_chunk_sims(uint32_t n, int total_laps)
 {
     uint64_t chunk = std::min<uint64_t>(max_sims_per_launch(), std::max<uint64_t>(1, kTraceStageBytes / ((uint64_t)total_laps * n)));
+    if (chunk >= 256) chunk = chunk / 256 * 256;
+    return chunk;
+}
+
+// mcgp_run_strategies' staging budget: a chunk holds budget / (S n) simulations of every scenario (one byte per
+// scenario, simulation and driver), at most max_sims_per_launch(), in multiples of 256 when it can.
+constexpr uint64_t kStrategyStageBytes = 256ull << 20;
+uint64_t strategy_chunk_sims(uint32_t n, uint32_t n_scenarios)
+{
+    uint64_t chunk = std::min<uint64_t>(max_sims_per_launch(),
+                                        std::max<uint64_t>(1, kStrategyStageBytes / ((uint64_t)n_scenarios * n)));
     if (chunk >= 256) chunk = chunk / 256 * 256;
     return chunk;
 }
@@ -764,6 +785,60 @@ std::string pack_race_state(const mcgp_race_state &rs, uint32_t si, uint32_t n, 
     }
     out->lap = rs.lap;
     out->drs_disabled_until = rs.drs_disabled_until;
+    return "";
+}
+
+// The scenarios of mcgp_run_strategies in the kernel's encoding, checked against the limits of include/mcgp.h; "" if
+// they pass, else the message (naming the scenario, the plan and the field).  first_lap: 2 from the grid, state lap + 1.
+std::string pack_scenarios(uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans, uint32_t n,
+                           int total_laps, int first_lap, bool from_state, std::vector<mcgp::StrategyScenario> *scen,
+                           std::vector<mcgp::StopLap> *laps)
+{
+    scen->assign(n_scenarios, mcgp::StrategyScenario());
+    laps->assign((size_t)n_scenarios * (total_laps + 1), mcgp::StopLap());
+    size_t next = 0;
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        mcgp::StrategyScenario &sc = (*scen)[si];
+        sc.planned = 0u;
+        sc.pad = 0u;
+        for (int d = 0; d < mcgp::kMaxCars; ++d) sc.start[d] = mcgp::kModelStart;
+        mcgp::StopLap *sl = laps->data() + (size_t)si * (total_laps + 1);
+        for (uint32_t pi = 0; pi < plan_count[si]; ++pi, ++next) {
+            const mcgp_pit_plan &pl = plans[next];
+            const std::string at = "scenario " + std::to_string(si) + ", plan " + std::to_string(pi) + ": ";
+            if (pl.driver < 0 || pl.driver >= (int)n) return at + "driver must be in [0, n)";
+            const uint32_t d = (uint32_t)pl.driver;
+            if ((sc.planned >> d) & 1u) return at + "driver " + std::to_string(d) + " has two plans in this scenario";
+            sc.planned |= 1u << d;
+            if (from_state) {
+                if (pl.start_compound != -1 || pl.start_age != 0)
+                    return at + "start_compound / start_age: a state fixes the tyres (start_compound must be -1, start_age 0)";
+            } else if (pl.start_compound == -1) {
+                if (pl.start_age != 0) return at + "start_age must be 0 with start_compound -1";
+            } else {
+                if (pl.start_compound < MCGP_SOFT || pl.start_compound > MCGP_WET)
+                    return at + "start_compound must be -1 or in [MCGP_SOFT, MCGP_WET]";
+                if (pl.start_age < 0 || pl.start_age > (int)mcgp::kAgeMask - total_laps)
+                    return at + "start_age must be in [0, 1023 - total_laps]";
+                sc.start[d] = (uint16_t)((uint32_t)pl.start_compound | ((uint32_t)pl.start_age << 3));
+            }
+            if (pl.n_stops > (uint32_t)mcgp::kMaxPlanStops) return at + "n_stops must be in [0, 8]";
+            int prev = 0;
+            for (uint32_t k = 0; k < pl.n_stops; ++k) {
+                const std::string stop = at + "stop " + std::to_string(k) + ": ";
+                const int lap = pl.stop_lap[k];
+                if (lap < first_lap || lap > total_laps)
+                    return stop + "stop_lap must be in [" + std::to_string(first_lap) + ", total_laps]" +
+                           (from_state ? " (after the state's lap)" : " (lap 1 has no pit step)");
+                if (lap <= prev) return stop + "stop_lap must be strictly increasing";
+                prev = lap;
+                const uint32_t comp = pl.stop_compound[k];
+                if (comp > MCGP_WET) return stop + "stop_compound must be in [MCGP_SOFT, MCGP_WET]";
+                sl[lap].mask |= 1u << d;
+                sl[lap].comp[d >> 3] |= comp << (4u * (d & 7u));
+            }
+        }
+    }
     return "";
 }
 
@@ -1735,6 +1810,170 @@ int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const do
         b += c_fast;
         if (events_out)
             for (size_t i = 0; i < c_ev; ++i) events_out[i] += b[i];
+        return MCGP_OK;
+    };
+    return body();
+}
+
+int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                            const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                            const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                            int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint8_t *orders_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+    if (!plan_count) return fail(MCGP_E_BAD_ARG, "plan_count is NULL");
+    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
+        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]");
+    uint64_t n_plans = 0;
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        if (plan_count[si] > mcgp::kMaxCars)
+            return fail(MCGP_E_BAD_ARG, "scenario " + std::to_string(si) + ": plan_count must be in [0, 32]");
+        n_plans += plan_count[si];
+    }
+    if (n_plans && !plans) return fail(MCGP_E_BAD_ARG, "plans is NULL");
+    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
+    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc != MCGP_OK) return rc;
+    if (cfg->deviates != MCGP_DEVIATES_32)
+        return fail(MCGP_E_BAD_ARG, "deviates: strategies run at MCGP_DEVIATES_32 only (the generic kernel has no 53-bit "
+                                    "path)");
+    const int L = cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string err = pack_race_state(*state, 0, n, L, &st);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+        st.sim_offset = sim_offset;
+    }
+    std::vector<mcgp::StrategyScenario> scen;
+    std::vector<mcgp::StopLap> stop_laps;
+    {
+        const std::string err = pack_scenarios(n_scenarios, plan_count, plans, n, L, state ? st.lap + 1 : 2, state != nullptr,
+                                               &scen, &stop_laps);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+    }
+    if (n_sims == 0) return MCGP_OK;
+    DeviceCtx *c = nullptr;
+    rc = find_ctx(device, &c);
+    if (rc != MCGP_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    auto body = [&]() -> int {
+        int r = ensure_ctx_locked(device, *c);
+        if (r != MCGP_OK) return r;
+        HIP_TRY(hipSetDevice(device));
+        r = ensure_call_events(*c);
+        if (r != MCGP_OK) return r;
+        const uint32_t S = n_scenarios;
+        const uint64_t chunk = std::min<uint64_t>(strategy_chunk_sims(n, S), n_sims);
+        const size_t stage_bytes = (size_t)S * chunk * n;
+        if (stage_bytes > c->strat_stage_bytes) {
+            if (c->d_strat_stage) (void)hipFree(c->d_strat_stage);
+            c->d_strat_stage = nullptr;
+            c->strat_stage_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_strat_stage, stage_bytes));
+            c->strat_stage_bytes = stage_bytes;
+        }
+        // parameter block | state | scenarios | stop laps | hist [S][n][n] | delta [S][n][2n - 1]
+        const size_t w = 2 * (size_t)n - 1;
+        const size_t o_st = (sizeof(mcgp::KParams) + 255) / 256 * 256;
+        const size_t o_sc = o_st + (sizeof(mcgp::ResumeState) + 255) / 256 * 256;
+        const size_t o_sl = o_sc + (sizeof(mcgp::StrategyScenario) * S + 255) / 256 * 256;
+        const size_t o_cnt = o_sl + (sizeof(mcgp::StopLap) * stop_laps.size() + 255) / 256 * 256;
+        const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w;
+        const size_t cells = c_hist + c_delta;
+        const size_t bytes = o_cnt + cells * 8;
+        if (bytes > c->strat_bytes) {
+            if (c->d_strat) (void)hipFree(c->d_strat);
+            c->d_strat = nullptr;
+            c->strat_bytes = 0;
+            HIP_TRY(hipMalloc(&c->d_strat, bytes));
+            c->strat_bytes = bytes;
+        }
+        const mcgp::KParams *d_kp = reinterpret_cast<const mcgp::KParams *>(c->d_strat);
+        const mcgp::ResumeState *d_st = reinterpret_cast<const mcgp::ResumeState *>(c->d_strat + o_st);
+        const mcgp::StrategyScenario *d_sc = reinterpret_cast<const mcgp::StrategyScenario *>(c->d_strat + o_sc);
+        const mcgp::StopLap *d_sl = reinterpret_cast<const mcgp::StopLap *>(c->d_strat + o_sl);
+        unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(c->d_strat + o_cnt);
+        unsigned long long *d_delta = d_hist + c_hist;
+        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
+        HIP_TRY(hipMemcpy(c->d_strat, &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_strat + o_st, &st, sizeof(st), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_strat + o_sc, scen.data(), sizeof(mcgp::StrategyScenario) * S, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_strat + o_sl, stop_laps.data(), sizeof(mcgp::StopLap) * stop_laps.size(),
+                          hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        // orders are collected on the host and handed over only once everything has run
+        std::vector<uint8_t> pos_back, orders;
+        if (orders_out) {
+            pos_back.resize(stage_bytes);
+            orders.resize((size_t)S * n_sims * n);
+        }
+        const KernelFn geo_fn = state ? reinterpret_cast<KernelFn>(&mcgp::race_strategy_kernel<true>)
+                                      : reinterpret_cast<KernelFn>(&mcgp::race_strategy_kernel<false>);   // (register count)
+        const uint64_t grid_cap = (uint64_t)c->cu_count * 8;
+        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
+        for (uint64_t done = 0; done < n_sims; done += chunk) {
+            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+            // the generic kernel's block shape; the blocks the device holds at once are shared out over the scenarios
+            launch_geometry(*c, n, false, geo_fn, m * S, &grid, &block, &lds);
+            if (lds > c->lds_per_block)
+                return fail(MCGP_E_HIP, "the strategy kernel's block needs " + std::to_string(lds) + " bytes of LDS, the "
+                                        "device offers " + std::to_string(c->lds_per_block) + " per block");
+            const uint64_t n_batches = (m + block - 1) / block;
+            const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + S - 1) / S);
+            if (done == 0) { grid0 = gx * S; block0 = block; }
+            if (state)
+                hipLaunchKernelGGL(mcgp::race_strategy_kernel<true>, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st,
+                                   d_sc, d_sl, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist,
+                                   c->d_strat_stage, (uint32_t)n_batches);
+            else
+                hipLaunchKernelGGL(mcgp::race_strategy_kernel<false>, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st,
+                                   d_sc, d_sl, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist,
+                                   c->d_strat_stage, (uint32_t)n_batches);
+            HIP_TRY(hipGetLastError());
+            // its counts, before the next chunk overwrites the staging
+            if (delta_out && S > 1) {
+                const uint64_t tiles = (m + mcgp::kStrategyCountBlock - 1) / mcgp::kStrategyCountBlock;
+                const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / (S - 1)));
+                hipLaunchKernelGGL(mcgp::strategy_count_deltas, dim3((uint32_t)gxc, S - 1), dim3(mcgp::kStrategyCountBlock),
+                                   0, nullptr, c->d_strat_stage, m, n, d_delta);
+                HIP_TRY(hipGetLastError());
+            }
+            if (orders_out) {
+                HIP_TRY(hipMemcpy(pos_back.data(), c->d_strat_stage, (size_t)S * m * n, hipMemcpyDeviceToHost));
+                for (uint32_t si = 0; si < S; ++si)
+                    for (uint64_t i = 0; i < m; ++i) {
+                        const uint8_t *pos = pos_back.data() + ((size_t)si * m + i) * n;
+                        uint8_t *ord = orders.data() + ((size_t)si * n_sims + done + i) * n;
+                        for (uint32_t d = 0; d < n; ++d) ord[pos[d]] = (uint8_t)d;
+                    }
+            }
+        }
+        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
+        c->last_timer = kBatchTimer;
+        c->last_grid = grid0;               // the launch shape of the first (fullest) chunk
+        c->last_block = block0;
+        c->last_lds = lds;
+        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "mcgp::race_strategy_kernel");
+        // the caller's buffers are added into only once everything has run
+        std::vector<unsigned long long> back(cells);
+        HIP_TRY(hipMemcpy(back.data(), d_hist, cells * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < c_hist; ++i) hist_out[i] += back[i];
+        if (delta_out) {
+            // the centre bin (no change) of every (scenario, driver) is what the other bins leave of n_sims
+            unsigned long long *b = back.data() + c_hist;
+            for (size_t row = 0; row < (size_t)S * n; ++row) {
+                unsigned long long rest = 0;
+                for (size_t j = 0; j < w; ++j) rest += j == n - 1 ? 0ull : b[row * w + j];
+                b[row * w + n - 1] = n_sims - rest;
+            }
+            for (size_t i = 0; i < c_delta; ++i) delta_out[i] += b[i];
+        }
+        if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
         return MCGP_OK;
     };
     return body();

@@ -193,6 +193,10 @@ __device__ __forceinline__ LapEnv load_block(unsigned char *smem, const KParams 
     return e;
 }
 
+// The hook of race_start.inc.h for a car's starting tyres: nothing here (race_strategy_kernel redefines it around its
+// own inclusion of the text).
+#define MCGP_START_OVERRIDE(driver, comp, age)
+
 // Race events of a lap, as run_laps hands them to its observer: the outcome of the short-circuit chain of :168-176.
 constexpr int kEventNone = 0, kEventRed = 1, kEventSc = 2, kEventVsc = 3;
 
@@ -201,14 +205,25 @@ struct NoLapObserver {
     __device__ __forceinline__ void operator()(const Rows &, int /*lap*/, int /*event*/) {}
 };
 
+// The pit policy of race_kernel, race_resume_kernel and race_trace_kernel: the race model's own rule for every car.
+// run_laps asks a policy once per lap, begin_lap(lap) (wave-uniform), and once per running car and lap, after the
+// car's lap time, decide(d, newc): -1 = the rule decides (_handle_pit_stops, reference :454-492); 0 = no stop and the
+// rule is off; 1 = a stop onto compound `newc`, rule off.  RulePit's constant -1 folds the branch away.
+struct RulePit {
+    __device__ __forceinline__ void begin_lap(int /*lap*/) {}
+    __device__ __forceinline__ int decide(uint32_t /*d*/, uint32_t & /*newc*/) const { return -1; }
+};
+
 // Laps first_lap .. L of one lane's race, reference :166-228, from the state the rows hold after lap first_lap - 1: `ord`
 // sorted by (cumulative time, grid slot), the DRS / dirty-air flags of update_positions, the retirement laps in `out`,
 // and the reference's drs_disabled_until.  race_kernel runs it from lap 2, race_resume_kernel (resume.hip.h) from k + 1.
 // After update_positions of every lap, obs(s, lap, event) sees the rows and the lap's kEvent* (race_trace_kernel,
-// trace.hip.h, records them; the other kernels pass a NoLapObserver).
-template <class LapObserver>
+// trace.hip.h, records them; the other kernels pass a NoLapObserver).  `pit` decides the stops (RulePit: the model's
+// rule; race_strategy_kernel, strategy.hip.h, passes planned stops).
+template <class LapObserver, class PitPolicy = RulePit>
 __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1, uint32_t seed_lo,
-                                         uint32_t seed_hi, int first_lap, int drs_disabled_until, LapObserver &obs)
+                                         uint32_t seed_hi, int first_lap, int drs_disabled_until, LapObserver &obs,
+                                         PitPolicy pit = PitPolicy())
 {
     const KParams *__restrict__ P = e.P;
     const int n = e.n, L = e.L, track = e.track;
@@ -272,6 +287,7 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
 
         // ---- every running car's lap, :179-223, with the pit stop of :433-494 folded in ----
         {
+            pit.begin_lap(lap);
             double fuel = 110.0 - 1.5 * (double)(lap - 1);     // fuel_load before this lap (Q7)
             if (!(fuel > 0)) fuel = 0.0;
             const double fuel_effect = (110.0 - fuel) * 0.03;
@@ -306,16 +322,23 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
                 }
                 double t = s.Cum(d) + lap_time;
                 age += 1u;
-                // _handle_pit_stops :454-492 (no randomness, no cross-car dependence)
-                if ((int)age > (int)t_opt[d * kCompStride + comp] && remaining_laps > 5) {
+                // _handle_pit_stops :454-492 (no randomness, no cross-car dependence), or the policy's planned stop
+                uint32_t plan_c = 0u;
+                const int plan = pit.decide(d, plan_c);
+                if (plan < 0 ? ((int)age > (int)t_opt[d * kCompStride + comp] && remaining_laps > 5) : plan > 0) {
                     t = t + pit_loss;
-                    uint32_t newc = stint_compound(track, remaining_laps);
-                    const uint32_t used_dry = (pk >> kUsedShift) & 7u;
-                    if (track == 0 && __popc(used_dry) == 1 && ((used_dry >> newc) & 1u)) {
-                        const uint32_t avail = 7u & ~used_dry;
-                        const uint32_t popped = avail == 5u ? (uint32_t)P->pop_sh : avail == 6u ? (uint32_t)P->pop_mh : 0u;
-                        if (remaining_laps > 20) newc = (avail & 2u) ? 1u : popped;
-                        else newc = (avail & 1u) ? 0u : popped;
+                    uint32_t newc;
+                    if (plan > 0) {
+                        newc = plan_c;
+                    } else {
+                        newc = stint_compound(track, remaining_laps);
+                        const uint32_t used_dry = (pk >> kUsedShift) & 7u;
+                        if (track == 0 && __popc(used_dry) == 1 && ((used_dry >> newc) & 1u)) {
+                            const uint32_t avail = 7u & ~used_dry;
+                            const uint32_t popped = avail == 5u ? (uint32_t)P->pop_sh : avail == 6u ? (uint32_t)P->pop_mh : 0u;
+                            if (remaining_laps > 20) newc = (avail & 2u) ? 1u : popped;
+                            else newc = (avail & 1u) ? 0u : popped;
+                        }
                     }
                     comp = newc;
                     pk = (pk & ~(7u << kCompShift)) | (comp << kCompShift) | ((1u << comp) << kUsedShift);

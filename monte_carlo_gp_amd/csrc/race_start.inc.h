@@ -6,7 +6,8 @@
 // simplifies the callee on its own before it inlines it).
 // In scope where it is included: `s` (Rows), `e` (LapEnv), `P`, `n`, `L`, `track`, `c0`, `c1`, `seed_lo`, `seed_hi`,
 // `fixed_grid` (NULL: the grid is sampled from grid_probs).  Leaves the rows after update_positions of lap 1 and every
-// driver's retirement lap (laps >= 2) in `out`.
+// driver's retirement lap (laps >= 2) in `out`.  MCGP_START_OVERRIDE(driver, comp, age) may replace a car's starting
+// tyres (race_strategy_kernel, strategy.hip.h); race_kernel.hip.h defines it to expand to nothing.
 
         // ================= _sample_grid, reference :102-145 =================
         // probs / cdf scratch lives in the `last` rows (not needed until lap 2).
@@ -58,6 +59,7 @@
                 if (track == 2) { comp = 4u; age = 0u; }
                 else if (track == 1) { comp = 3u; age = 0u; }
                 else { comp = pos < 10 ? 0u : 1u; age = pos < 10 ? 4u : 0u; }
+                MCGP_START_OVERRIDE(sel, comp, age);
                 s.Pk(sel) = age | (comp << kCompShift) | ((1u << comp) << kUsedShift) | ((uint32_t)pos << kGposShift);
                 s.Cum(sel) = 0.0;
                 s.Ord(pos) = (uint8_t)sel;

@@ -239,6 +239,26 @@ class F1Predictor:
                         'points_probabilities': top(10), 'full_distributions': rp})
         return out[0] if single else out
 
+    def predict_strategies(self, season: int, race: str, fixture: dict | str, strategies: dict, state=None,
+                           n_simulations: int = 100000, seed: int | None = None, prediction_point: str = 'fp2',
+                           allow_single_compound: bool = False):
+        """Pit-strategy comparison (not in the reference): the weekend's race inputs (simulator_inputs, as
+        predict_weekend builds them) run under each scenario of `strategies` ({name: [PitPlan, ...]}) through
+        RaceSimulator.run_strategies -- from the grid, or from a mid-race RaceState -- with common random numbers.  The
+        driver order is predict_weekend's, so an empty scenario reproduces predict_weekend's (or predict_from_state's)
+        race for the same seed.  Returns the StrategyResult."""
+        if isinstance(fixture, str):
+            with open(fixture) as f:
+                fixture = json.load(f)
+        if not fixture.get('drivers'):
+            raise ValueError(f"No practice data available for {season} {race}")
+        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
+        sim = RaceSimulator(inp['config'], device=self.device)
+        return sim.run_strategies(n_simulations, strategies, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
+                                  inp['driver_dnf_rates'], grid_probs=inp['grid_probs'] if state is None else None,
+                                  state=state, seed=seed, track_condition=inp['track_condition'],
+                                  drivers=list(inp['grid_probs']), allow_single_compound=allow_single_compound)
+
     @staticmethod
     def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace) -> dict:
         """predict_weekend's result from run_matchups and / or run_trace calls on `grid` (the same simulations: one seed

@@ -8,6 +8,7 @@ Mirrors the reference's interface for the hot path (reference src/simulation.py)
     RaceSimulator.simulate_race(grid, ...)       :147-242 one race, list of (driver, position)
     RaceSimulator.run_matchups(...)              (not in the reference) head-to-head and podium counts of one race
     RaceSimulator.run_from_state(...)            (not in the reference) the rest of a race from a mid-race RaceState
+    RaceSimulator.run_strategies(...)            (not in the reference) one race under planned pit stops (PitPlan)
 
 The per-lap loop itself runs in hand-written HIP (csrc/race_kernel_reg.hip.h) behind
 the C ABI of include/mcgp.h; this module only resolves the reference's dict
@@ -519,6 +520,93 @@ class RaceSimulator:
             return res, (orders[0] if single else orders)
         return res
 
+    def run_strategies(
+        self,
+        n_simulations: int,
+        strategies: dict,
+        base_pace: dict,
+        tire_deg: dict,
+        driver_variance: dict,
+        driver_dnf_rates: dict | None = None,
+        grid_probs: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        return_orders: bool = False,
+        allow_single_compound: bool = False,
+    ) -> 'StrategyResult':
+        """Pit-strategy comparison (include/mcgp.h: mcgp_run_strategies): the race under each scenario of `strategies`,
+        {name: [PitPlan, ...]} with at most one plan per driver (at most 64 scenarios; the first is the one `compare`
+        measures against).  Drivers without a plan keep the model's pit rule; a planned driver stops only on its plan's
+        laps.  From the grid (grid_probs) or from a mid-race RaceState (state; plans then have no start fields and stop
+        after the state's lap).  Simulation i of every scenario has id sim_offset + i and makes run_monte_carlo's (or
+        run_from_state's) draws: an empty scenario gives exactly that call's histogram, and the scenarios share the
+        grid, the retirements and the race events.  On a dry track a plan that cannot use two dry compounds raises
+        ValueError unless allow_single_compound.  32-bit deviates only; same seed rules and device sharding as
+        run_monte_carlo.  last_histogram: [S, n, n]."""
+        if (grid_probs is None) == (state is None):
+            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
+        names = [str(k) for k in strategies.keys()]
+        if not 1 <= len(names) <= N.MAX_SCENARIOS:
+            raise ValueError(f'strategies: 1 to {N.MAX_SCENARIOS} scenarios, got {len(names)}')
+        if drivers is None:
+            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
+        drivers = [str(d) for d in drivers]
+        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
+            raise ValueError('drivers must be the keys of grid_probs')
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        n, L = prob.n, int(self.config.total_laps)
+        arrays = state.arrays(drivers, L) if state is not None else None
+        index = {d: i for i, d in enumerate(drivers)}
+        counts, c_plans = [], []
+        for name in names:
+            plans = list(strategies[name])
+            for plan in plans:
+                if str(plan.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {plan.driver!r} is not one of the drivers')
+                if not allow_single_compound and track_condition == 'dry':
+                    used = None
+                    if arrays is not None:
+                        used = {c for j, c in enumerate(N.COMPOUNDS)
+                                if (int(arrays['used_compounds'][index[str(plan.driver)]]) >> j) & 1}
+                    check_two_compounds(plan, used, name)
+                c_plans.append(plan.c_struct(index, from_state=state is not None))
+            counts.append(len(plans))
+        S = len(names)
+        plan_arr = (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans)
+        count_arr = (C.c_uint32 * S)(*counts)
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
+        c_state = state.c_struct(arrays) if state is not None else None
+        n_simulations = int(n_simulations)
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            h = np.zeros((S, n, n), np.uint64)
+            dl = np.zeros((S, n, 2 * n - 1), np.uint64)
+            o = np.zeros((S, count, n), np.uint8) if return_orders else None
+            rc = lib.mcgp_run_strategies(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
+                                         C.byref(c_state) if c_state is not None else None, n, S, count_arr, plan_arr,
+                                         int(count), int(sim_offset) + int(offset), seed64, device, u64(h), u64(dl),
+                                         o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
+            return (h, dl, o), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        if n_simulations <= 0:
+            parts = [((np.zeros((S, n, n), np.uint64), np.zeros((S, n, 2 * n - 1), np.uint64),
+                       np.zeros((S, 0, n), np.uint8) if return_orders else None), 0, '')]
+            n_simulations = 0
+        else:
+            parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([p[k] for p, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        res = StrategyResult(names=names, drivers=drivers, n_simulations=n_simulations, hist=total(0), delta=total(1),
+                             orders=np.concatenate([p[2] for p, _, _ in parts], axis=1) if return_orders else None)
+        self.last_histogram = res.hist
+        self.last_drivers = drivers
+        return res
+
     def simulate_race(
         self,
         grid: list,
@@ -996,3 +1084,169 @@ def histogram_to_probs(hist, drivers, n_simulations):
         nz = np.nonzero(row)[0]
         out[d] = {int(p) + 1: int(row[p]) / n_simulations for p in nz}
     return out
+
+
+# ---------------------------------------------------------------------------------------------- pit-strategy comparison
+DRY_COMPOUNDS = ('SOFT', 'MEDIUM', 'HARD')
+
+
+@dataclass
+class PitPlan:
+    """One driver's strategy in a scenario of RaceSimulator.run_strategies: `stops` = [(lap, compound name), ...] with
+    strictly increasing laps (2 .. total_laps from the grid, after the state's lap from a RaceState), at most 8; `start`
+    = the starting compound name, or None for the model's start (SOFT at age 4 on the first ten grid slots, MEDIUM new
+    behind them, INTERMEDIATE / WET on a damp / wet track), with `start_age` laps on it.  A planned driver never takes
+    the model's own pit rule: it stops on its plan's laps and nowhere else."""
+    driver: str
+    stops: list = field(default_factory=list)
+    start: str | None = None
+    start_age: int = 0
+
+    def c_struct(self, index, from_state=False) -> N.McgpPitPlan:
+        """mcgp_pit_plan with the driver index from `index`; ValueError on an unknown compound or too many stops (the
+        library checks the laps and the rest)."""
+        stops = [(int(lap), str(comp)) for lap, comp in self.stops]
+        if len(stops) > N.MAX_PLAN_STOPS:
+            raise ValueError(f'{self.driver}: at most {N.MAX_PLAN_STOPS} stops, got {len(stops)}')
+        for _, comp in stops:
+            if comp not in N.COMPOUND_ID:
+                raise ValueError(f'{self.driver}: compound must be one of {list(N.COMPOUNDS)}, got {comp!r}')
+        if self.start is not None and self.start not in N.COMPOUND_ID:
+            raise ValueError(f'{self.driver}: start must be None or one of {list(N.COMPOUNDS)}, got {self.start!r}')
+        if from_state and (self.start is not None or int(self.start_age) != 0):
+            raise ValueError(f'{self.driver}: a plan from a race state has no start compound or age (the state fixes '
+                             'the tyres)')
+        p = N.McgpPitPlan()
+        p.driver = int(index[str(self.driver)])
+        p.start_compound = -1 if self.start is None else N.COMPOUND_ID[self.start]
+        p.start_age = int(self.start_age)
+        p.n_stops = len(stops)
+        for k, (lap, comp) in enumerate(stops):
+            p.stop_lap[k] = lap
+            p.stop_compound[k] = N.COMPOUND_ID[comp]
+        return p
+
+
+def check_two_compounds(plan: PitPlan, used=None, scenario=''):
+    """The two-compound rule of a dry race, for a plan: ValueError unless the car is sure to run two dry compounds.
+    `used`: the compounds a race state says the car has used (None: a run from the grid, where a plan without `start`
+    must work for both of the model's starts, SOFT and MEDIUM)."""
+    stops = {str(c) for _, c in plan.stops} & set(DRY_COMPOUNDS)
+    if used is not None:
+        starts = [set(used)]
+    elif plan.start is not None:
+        starts = [{plan.start}]
+    else:
+        starts = [{'SOFT'}, {'MEDIUM'}]
+    for st in starts:
+        if len((st & set(DRY_COMPOUNDS)) | stops) < 2:
+            where = f'scenario {scenario!r}: ' if scenario else ''
+            raise ValueError(f'{where}{plan.driver}: the plan runs one dry compound ({sorted(st | stops)}) on a dry '
+                             'track; pass allow_single_compound=True to run it anyway')
+
+
+def pit_window(driver: str, laps, compound: str, then=(), start=None, start_age=0) -> dict:
+    """The optimal-pit-window sweep: one single-stop scenario per lap of `laps`, {"<driver> L<lap>": [PitPlan]}, the
+    stop onto `compound`, followed by the stops of `then` ([(lap, compound)], laps after the window)."""
+    return {f'{driver} L{int(lap)}': [PitPlan(driver, [(int(lap), compound)] + [(int(a), str(c)) for a, c in then],
+                                              start=start, start_age=start_age)]
+            for lap in laps}
+
+
+@dataclass
+class StrategyResult:
+    """What RaceSimulator.run_strategies returns: integer counts per scenario (in `names` order) over n_simulations:
+      hist    [S][n][n]       [scenario][driver][position - 1]
+      delta   [S][n][2n - 1]  [scenario][driver][(pos_s - pos_0) + n - 1]: the paired change of the driver's position
+                              against the first scenario in the same simulation
+      orders  [S][N][n]       finishing orders (return_orders=True), else None"""
+    names: list
+    drivers: list
+    n_simulations: int
+    hist: np.ndarray
+    delta: np.ndarray
+    orders: np.ndarray | None = None
+
+    def _s(self, name):
+        if name is None:
+            return 0
+        if name not in self.names:
+            raise KeyError(f'no scenario {name!r}; scenarios: {self.names}')
+        return self.names.index(name)
+
+    def _d(self, driver):
+        if driver not in self.drivers:
+            raise KeyError(f'no driver {driver!r}')
+        return self.drivers.index(driver)
+
+    def position_probabilities(self, name=None) -> dict:
+        """{driver: {position: probability}} of scenario `name` (None: {name: that dict} for every scenario)."""
+        if name is None:
+            return {s: self.position_probabilities(s) for s in self.names}
+        return histogram_to_probs(self.hist[self._s(name)], self.drivers, max(self.n_simulations, 1))
+
+    def _p(self, name):
+        return np.asarray(self.hist[self._s(name)], np.float64) / max(self.n_simulations, 1)
+
+    def expected_position(self, name) -> dict:
+        p = self._p(name)
+        pos = np.arange(1, len(self.drivers) + 1, dtype=np.float64)
+        return {d: float(p[i] @ pos) for i, d in enumerate(self.drivers)}
+
+    def expected_points(self, name, points=DEFAULT_POINTS) -> dict:
+        p = self._p(name)
+        n = len(self.drivers)
+        table = np.zeros(n, np.float64)
+        m = min(n, len(points))
+        table[:m] = np.asarray(points[:m], np.float64)
+        return {d: float(p[i] @ table) for i, d in enumerate(self.drivers)}
+
+    def win_probability(self, name, driver) -> float:
+        return float(self._p(name)[self._d(driver), 0])
+
+    def podium_probability(self, name, driver) -> float:
+        return float(self._p(name)[self._d(driver), :3].sum())
+
+    def compare(self, name, driver, against=None) -> dict:
+        """Scenario `name` against `against` (default: the first scenario) for `driver`, paired by simulation:
+        p_better / p_same / p_worse (finishing ahead of, level with, behind its own result under `against`), mean_gain
+        (positions gained, mean) and its paired standard error `se`; `se_unpaired` is the standard error the two
+        marginal histograms alone would give (independent runs).  Against the first scenario this reads `delta`; against
+        another one it needs the finishing orders (return_orders=True)."""
+        s, a, i = self._s(name), self._s(against if against is not None else self.names[0]), self._d(driver)
+        n, N_ = len(self.drivers), self.n_simulations
+        if a == 0:
+            counts = np.asarray(self.delta[s, i], np.float64)
+            change = np.arange(-(n - 1), n, dtype=np.float64)            # pos_s - pos_against
+        else:
+            if self.orders is None:
+                raise ValueError('compare against a scenario other than the first needs return_orders=True')
+            pos = lambda k: np.argmax(self.orders[k] == i, axis=1)
+            diff = pos(s) - pos(a)
+            counts = np.bincount(diff + n - 1, minlength=2 * n - 1).astype(np.float64)
+            change = np.arange(-(n - 1), n, dtype=np.float64)
+        tot = max(counts.sum(), 1.0)
+        gain = -change
+        mean = float(counts @ gain) / tot
+        var = float(counts @ (gain - mean) ** 2) / max(tot - 1.0, 1.0)
+        pos = np.arange(1, n + 1, dtype=np.float64)
+        var_pos = lambda k: float(self.hist[k, i] @ (pos - float(self.hist[k, i] @ pos) / tot) ** 2) / max(tot - 1.0, 1.0)
+        return dict(p_better=float(counts[:n - 1].sum()) / tot, p_same=float(counts[n - 1]) / tot,
+                    p_worse=float(counts[n:].sum()) / tot, mean_gain=mean, se=math.sqrt(var / tot),
+                    se_unpaired=math.sqrt((var_pos(s) + var_pos(a)) / tot), n_simulations=int(N_))
+
+    def best(self, driver, by='expected_points'):
+        """The scenario name that is best for `driver` by 'expected_points', 'expected_position' (lowest), 'win' or
+        'podium'."""
+        if by == 'expected_points':
+            key = lambda s: self.expected_points(s)[driver]
+        elif by == 'expected_position':
+            key = lambda s: -self.expected_position(s)[driver]
+        elif by == 'win':
+            key = lambda s: self.win_probability(s, driver)
+        elif by == 'podium':
+            key = lambda s: self.podium_probability(s, driver)
+        else:
+            raise ValueError(f"by must be 'expected_points', 'expected_position', 'win' or 'podium', got {by!r}")
+        self._d(driver)
+        return max(self.names, key=key)
