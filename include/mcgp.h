@@ -148,11 +148,12 @@ int32_t mcgp_run_device(const mcgp_config *cfg, const mcgp_drivers *drv, const d
  * that size a launch lasts as long as one race of one lane and most of the device idles.  n_problems races of the same
  * field size n, n_sims simulations each: cfgs[p], drvs[p], grid_probs[p] (n x n) as for mcgp_run, simulation ids
  * sim_offsets[p] .. sim_offsets[p] + n_sims - 1 (NULL: 0) under seeds[p]; hist_out = [n_problems][n][n], ACCUMULATED
- * into.  Every problem gets exactly what mcgp_run would give it, error or histogram (a sweep of the reference is a loop
- * over independent predictions): the problems the shared launch takes go into it; a problem at deviates =
- * MCGP_DEVIATES_53, or one only the second kernel serves (lap times near zero, a negative overtake_delta), or every
- * problem under MCGP_FORCE_GENERIC=1, runs by itself inside the same call.  Host buffers in and out, blocking.
- * mcgp_last_kernel_ms afterwards = the device time of everything the call ran. */
+ * into only after every launch has succeeded: on an error it is left untouched.  Every problem gets exactly what
+ * mcgp_run would give it, error or histogram (a sweep of the reference is a loop over independent predictions): the
+ * problems the shared launch takes go into it; a problem at deviates = MCGP_DEVIATES_53, or one only the second kernel
+ * serves (lap times near zero, a negative overtake_delta), or every problem under MCGP_FORCE_GENERIC=1, runs by itself
+ * inside the same call.  Host buffers in and out, blocking.  mcgp_last_kernel_ms afterwards = the device time of
+ * everything the call ran. */
 int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_drivers *drvs,
                        const double *const *grid_probs, uint32_t n, uint64_t n_sims, const uint64_t *sim_offsets,
                        const uint64_t *seeds, int32_t device, uint64_t *hist_out);

@@ -2,9 +2,9 @@
 //
 // Host side of the drop-in boundary: validates arguments, folds the reference's
 // per-race constants into the kernel's parameter block, owns one cached context
-// per HIP device (parameter buffer, scratch histogram, events) and launches
-// race_kernel.  No CPU compute path exists here: without a HIP device every
-// compute entry point returns MCGP_E_NO_DEVICE.
+// per HIP device (parameter buffer, scratch histogram, events, the workspace of
+// the blocking calls) and launches race_kernel.  No CPU compute path exists here:
+// without a HIP device every compute entry point returns MCGP_E_NO_DEVICE.
 #include "../../include/mcgp.h"
 #include "params_build.h"
 #include "race_kernel.hip.h"
@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -55,9 +56,6 @@ int fail(int code, const std::string &msg)
 // MCGP_FORCE_GENERIC=1: tests run both and require identical results.
 #define MCGP_REG_SIZES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) \
     X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-
-// The reference-width build (mcgp_config.deviates = MCGP_DEVIATES_53) is compiled for the same field sizes (reg_inst.hip).
-#define MCGP_WIDE_SIZES(X) MCGP_REG_SIZES(X)
 
 // Grid-probability front end (reference src/elo.py:124-141, src/predictor.py:321-407): one thread per driver row.
 // in = [rating | teammate_delta | form_score | circuit_affinity], n doubles each.  Thread 0 computes the n pole
@@ -119,7 +117,32 @@ elo_season_kernel(int n, int n_events, const int32_t *__restrict__ kind, const d
 constexpr int kParamSlots = 4;
 constexpr int kSlotReaders = 8;        // streams with a launch in flight on one parameter block
 constexpr int kStreamTimers = 8;       // streams whose most recent call keeps its own timing events
-constexpr int kBatchTimer = -2;        // DeviceCtx::last_timer after mcgp_run_batch: the call's own pair of events
+constexpr int kCallTimer = -2;         // DeviceCtx::last_timer after a call of several kernels: the call's own pair of events
+
+// Device memory that grows on demand and never shrinks: reserve() reallocates, without keeping the contents, only when it
+// is asked for more than it holds.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t want)
+    {
+        if (want <= bytes) return MCGP_OK;
+        release();
+        HIP_TRY(hipMalloc(&p, want));
+        bytes = want;
+        return MCGP_OK;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <class T = unsigned char> T *at(size_t offset = 0) const
+    {
+        return reinterpret_cast<T *>(static_cast<unsigned char *>(p) + offset);
+    }
+};
 
 struct DeviceCtx {
     std::mutex mu;
@@ -153,45 +176,24 @@ struct DeviceCtx {
     int32_t *d_fe_pen = nullptr;
     double *d_fe_out = nullptr;
     double *d_norm53 = nullptr;               // binary64 inverse-normal table of the reference-width build (50 KB)
-    uint8_t *d_orders = nullptr;              // staging for mcgp_run(orders_out), grown on demand, kept
-    size_t d_orders_bytes = 0;
     // timing events per stream (most recent call on that stream), so that calls on different streams of one
     // device do not re-record each other's events
     struct Timer {
         hipStream_t stream = nullptr;
         hipEvent_t start = nullptr, stop = nullptr;
         uint32_t *d_ticket = nullptr;       // the work counter of this stream's launches (race_kernel_reg.hip.h, phase 2)
-        uint32_t *d_retire = nullptr;       // the lanes' retirement lists of this stream's launches (grow-only)
-        size_t retire_bytes = 0;
+        DevBuf retire;                      // the lanes' retirement lists of this stream's launches
         bool used = false;
         uint64_t seq = 0;
     } timer[kStreamTimers];
     uint64_t timer_seq = 0;
     int last_timer = -1;
-    unsigned char *d_elo = nullptr;         // scratch of mcgp_elo_season (grow-only)
-    size_t elo_bytes = 0;
-    unsigned char *d_batch = nullptr;       // mcgp_run_batch: parameter blocks, items, histograms, ticket (grow-only)
-    size_t batch_bytes = 0;
-    uint32_t *d_batch_retire = nullptr;     // ... and the lanes' retirement lists
-    size_t batch_retire_bytes = 0;
-    hipEvent_t batch_start = nullptr, batch_stop = nullptr;     // ... and the timing events of the last batch call
-                                                                // (and of the last championship or matchups call)
-    uint64_t *d_champ_keys = nullptr;       // mcgp_run_championship: standing keys of a chunk (grow-only)
-    size_t champ_keys_bytes = 0;
-    unsigned char *d_champ = nullptr;       // ... and its tables and histograms (grow-only)
-    size_t champ_bytes = 0;
-    unsigned long long *d_match = nullptr;  // mcgp_run_matchups: its histograms (grow-only)
-    size_t match_bytes = 0;
-    unsigned char *d_resume = nullptr;      // mcgp_run_from_state: parameter block, states, histograms (grow-only)
-    size_t resume_bytes = 0;
-    unsigned char *d_trace = nullptr;       // mcgp_run_trace: staging of a chunk and its records (grow-only, bounded)
-    size_t trace_bytes = 0;
-    unsigned char *d_trace_out = nullptr;   // ... and the call's parameter block and counts (grow-only)
-    size_t trace_out_bytes = 0;
-    uint8_t *d_strat_stage = nullptr;       // mcgp_run_strategies: staged positions of a chunk (grow-only, bounded)
-    size_t strat_stage_bytes = 0;
-    unsigned char *d_strat = nullptr;       // ... and the call's parameter block, state, plans and counts (grow-only)
-    size_t strat_bytes = 0;
+    hipEvent_t call_start = nullptr, call_stop = nullptr;     // the timing events of the last call of several kernels
+    // The workspace of every entry point but mcgp_run_device: parameter block, inputs, staging and counts of one call,
+    // in regions the call lays out (Layout).  Those calls run on the null stream and hold `mu` throughout, so that a
+    // call's work on it is ordered behind all of the previous call's; a grown buffer is replaced through hipFree, which
+    // waits for the device.
+    DevBuf work;
     uint32_t last_grid = 0, last_block = 0, last_lds = 0;
     char last_kernel[48] = "";
 };
@@ -233,53 +235,34 @@ void release_ctx(DeviceCtx &c)
     if (c.d_fe_in) (void)hipFree(c.d_fe_in);
     if (c.d_fe_pen) (void)hipFree(c.d_fe_pen);
     if (c.d_fe_out) (void)hipFree(c.d_fe_out);
-    c.d_fe_in = c.d_fe_out = nullptr;
-    c.d_fe_pen = nullptr;
-    if (c.d_orders) (void)hipFree(c.d_orders);
     if (c.d_norm53) (void)hipFree(c.d_norm53);
-    c.d_norm53 = nullptr;
-    if (c.d_elo) (void)hipFree(c.d_elo);
-    c.d_elo = nullptr;
-    c.elo_bytes = 0;
-    if (c.d_batch) (void)hipFree(c.d_batch);
-    if (c.d_batch_retire) (void)hipFree(c.d_batch_retire);
-    if (c.batch_start) (void)hipEventDestroy(c.batch_start);
-    if (c.batch_stop) (void)hipEventDestroy(c.batch_stop);
-    c.batch_start = c.batch_stop = nullptr;
-    c.d_batch = nullptr;
-    c.d_batch_retire = nullptr;
-    if (c.d_champ_keys) (void)hipFree(c.d_champ_keys);
-    if (c.d_champ) (void)hipFree(c.d_champ);
-    c.d_champ_keys = nullptr;
-    c.d_champ = nullptr;
-    c.champ_keys_bytes = c.champ_bytes = 0;
-    if (c.d_match) (void)hipFree(c.d_match);
-    c.d_match = nullptr;
-    c.match_bytes = 0;
-    if (c.d_resume) (void)hipFree(c.d_resume);
-    c.d_resume = nullptr;
-    c.resume_bytes = 0;
-    if (c.d_trace) (void)hipFree(c.d_trace);
-    if (c.d_trace_out) (void)hipFree(c.d_trace_out);
-    c.d_trace = c.d_trace_out = nullptr;
-    c.trace_bytes = c.trace_out_bytes = 0;
-    if (c.d_strat_stage) (void)hipFree(c.d_strat_stage);
-    if (c.d_strat) (void)hipFree(c.d_strat);
-    c.d_strat_stage = nullptr;
-    c.d_strat = nullptr;
-    c.strat_stage_bytes = c.strat_bytes = 0;
-    c.batch_bytes = c.batch_retire_bytes = 0;
+    c.d_hist = nullptr;
+    c.d_grid = c.d_order1 = nullptr;
+    c.d_fe_in = c.d_fe_out = c.d_norm53 = nullptr;
+    c.d_fe_pen = nullptr;
+    c.work.release();
+    if (c.call_start) (void)hipEventDestroy(c.call_start);
+    if (c.call_stop) (void)hipEventDestroy(c.call_stop);
+    c.call_start = c.call_stop = nullptr;
     for (auto &t : c.timer) {
         if (t.start) (void)hipEventDestroy(t.start);
         if (t.stop) (void)hipEventDestroy(t.stop);
         if (t.d_ticket) (void)hipFree(t.d_ticket);
-        if (t.d_retire) (void)hipFree(t.d_retire);
+        t.retire.release();
         t = DeviceCtx::Timer{};
     }
     c.last_timer = -1;
-    c.d_hist = nullptr;
-    c.d_grid = c.d_order1 = c.d_orders = nullptr;
-    c.d_orders_bytes = 0;
+}
+
+// LDS per block a launch may use: what the device offers, or less under MCGP_LDS_PER_BLOCK (tests: a device / runtime
+// that offers less LDS per block).
+size_t lds_limit(size_t device_bytes)
+{
+    if (const char *e = std::getenv("MCGP_LDS_PER_BLOCK")) {
+        const unsigned long long v = std::strtoull(e, nullptr, 10);
+        if (v >= 16384 && v < device_bytes) return (size_t)v;
+    }
+    return device_bytes;
 }
 
 int init_ctx_body(int device, DeviceCtx &c)
@@ -288,11 +271,7 @@ int init_ctx_body(int device, DeviceCtx &c)
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     c.cu_count = prop.multiProcessorCount;
-    c.lds_per_block = prop.sharedMemPerBlock;       // 160 KiB on gfx950
-    if (const char *e = std::getenv("MCGP_LDS_PER_BLOCK")) {      // tests: a device / runtime that offers less LDS per block
-        const unsigned long long v = std::strtoull(e, nullptr, 10);
-        if (v >= 16384 && v < c.lds_per_block) c.lds_per_block = (size_t)v;
-    }
+    c.lds_per_block = lds_limit(prop.sharedMemPerBlock);       // 160 KiB on gfx950
     for (auto &sl : c.slot) {
         HIP_TRY(hipMalloc(&sl.dev, sizeof(mcgp::KParams)));
         HIP_TRY(hipHostMalloc(&sl.host, sizeof(mcgp::KParams)));
@@ -347,23 +326,18 @@ using KernelFn = void (*)(const mcgp::KParams *, uint64_t, uint64_t, uint32_t, u
 // The register-resident instantiations are compiled one per translation unit (reg_inst.hip,
 // -DMCGP_INST_N=<n>) so that the build runs in parallel; here they are only declared.
 namespace mcgp {
-#define X(N_) extern template __global__ void race_kernel_reg<N_>(const KParams *, uint64_t, uint64_t, uint32_t, uint32_t, \
-                                                                  unsigned long long *, uint8_t *, const uint8_t *, uint32_t, \
-                                                                  uint32_t *, uint32_t *);
-MCGP_REG_SIZES(X)
-#undef X
-#define X(N_) extern template __global__ void race_kernel_reg<N_, kSmallBlockWaves>(const KParams *, uint64_t, uint64_t, uint32_t, \
-                                                                                    uint32_t, unsigned long long *, uint8_t *,   \
-                                                                                    const uint8_t *, uint32_t, uint32_t *, uint32_t *);
-MCGP_REG_SIZES(X)
-#undef X
-#define X(N_) extern template __global__ void race_kernel_reg_wide<N_>(const KParams *, uint64_t, uint64_t, uint32_t, uint32_t, \
-                                                                       unsigned long long *, uint8_t *, const uint8_t *, uint32_t, \
-                                                                       uint32_t *, uint32_t *, const double *);
-MCGP_WIDE_SIZES(X)
-#undef X
-#define X(N_) extern template __global__ void race_kernel_reg_batch<N_>(const KParams *, const BatchItem *, uint32_t, uint64_t, \
-                                                                        unsigned long long *, uint32_t, uint32_t *, uint32_t *);
+#define X(N_)                                                                                                                   \
+    extern template __global__ void race_kernel_reg<N_>(const KParams *, uint64_t, uint64_t, uint32_t, uint32_t,               \
+                                                        unsigned long long *, uint8_t *, const uint8_t *, uint32_t, uint32_t *, \
+                                                        uint32_t *);                                                           \
+    extern template __global__ void race_kernel_reg<N_, kSmallBlockWaves>(const KParams *, uint64_t, uint64_t, uint32_t,       \
+                                                                          uint32_t, unsigned long long *, uint8_t *,           \
+                                                                          const uint8_t *, uint32_t, uint32_t *, uint32_t *);  \
+    extern template __global__ void race_kernel_reg_wide<N_>(const KParams *, uint64_t, uint64_t, uint32_t, uint32_t,          \
+                                                             unsigned long long *, uint8_t *, const uint8_t *, uint32_t,       \
+                                                             uint32_t *, uint32_t *, const double *);                          \
+    extern template __global__ void race_kernel_reg_batch<N_>(const KParams *, const BatchItem *, uint32_t, uint64_t,          \
+                                                              unsigned long long *, uint32_t, uint32_t *, uint32_t *);
 MCGP_REG_SIZES(X)
 #undef X
 }  // namespace mcgp
@@ -374,50 +348,56 @@ using BatchKernelFn = void (*)(const mcgp::KParams *, const mcgp::BatchItem *, u
                                uint32_t, uint32_t *, uint32_t *);
 using WideKernelFn = void (*)(const mcgp::KParams *, uint64_t, uint64_t, uint32_t, uint32_t, unsigned long long *,
                               uint8_t *, const uint8_t *, uint32_t, uint32_t *, uint32_t *, const double *);
-WideKernelFn select_wide_kernel(uint32_t n)
-{
-    switch (n) {
-#define X(N_) case N_: return &mcgp::race_kernel_reg_wide<N_>;
-        MCGP_WIDE_SIZES(X)
-#undef X
-        default: return nullptr;
-    }
-}
 
-BatchKernelFn select_batch_kernel(uint32_t n)
-{
-    switch (n) {
-#define X(N_) case N_: return &mcgp::race_kernel_reg_batch<N_>;
-        MCGP_REG_SIZES(X)
+// The register-resident instantiations of field size n, at entry n - 1: the default block shape, the small one
+// (kSmallBlockWaves), the reference-width build (mcgp_config.deviates = MCGP_DEVIATES_53) and the batch kernel.
+struct RegKernels {
+    KernelFn reg, small;
+    WideKernelFn wide;
+    BatchKernelFn batch;
+};
+const RegKernels kRegKernels[] = {
+#define X(N_) {&mcgp::race_kernel_reg<N_>, &mcgp::race_kernel_reg<N_, mcgp::kSmallBlockWaves>, \
+               &mcgp::race_kernel_reg_wide<N_>, &mcgp::race_kernel_reg_batch<N_>},
+    MCGP_REG_SIZES(X)
 #undef X
-        default: return nullptr;
-    }
-}
+};
+static_assert(sizeof(kRegKernels) / sizeof(kRegKernels[0]) == MCGP_MAX_CARS, "one entry per field size 1..32");
 
-// the register kernel of a field size in its small block shape (kSmallBlockWaves)
-KernelFn select_small_kernel(uint32_t n)
+// The instantiations of field size n, or null when it has none.
+const RegKernels *reg_kernels(uint32_t n) { return n >= 1 && n <= MCGP_MAX_CARS ? &kRegKernels[n - 1] : nullptr; }
+
+// MCGP_FORCE_GENERIC=1: every problem goes to the generic LDS kernel.
+bool force_generic()
 {
-    switch (n) {
-#define X(N_) case N_: return &mcgp::race_kernel_reg<N_, mcgp::kSmallBlockWaves>;
-        MCGP_REG_SIZES(X)
-#undef X
-        default: return nullptr;
-    }
+    const char *e = std::getenv("MCGP_FORCE_GENERIC");
+    return e && e[0] == '1';
 }
 
 KernelFn select_kernel(const mcgp::KParams &kp, bool *is_reg)
 {
-    *is_reg = false;
-    const uint32_t n = (uint32_t)kp.n;
-    const char *force = std::getenv("MCGP_FORCE_GENERIC");
-    if (force && force[0] == '1') return &mcgp::race_kernel;
-    if (!mcgp::reg_kernel_serves(kp)) return &mcgp::race_kernel;      // lap times near zero, values near the ends of binary64
-    switch (n) {
-#define X(N_) case N_: *is_reg = true; return &mcgp::race_kernel_reg<N_>;
-        MCGP_REG_SIZES(X)
-#undef X
-        default: return &mcgp::race_kernel;
-    }
+    // (the generic kernel also takes lap times near zero and values near the ends of binary64: reg_kernel_serves)
+    const RegKernels *rk = reg_kernels((uint32_t)kp.n);
+    *is_reg = rk && !force_generic() && mcgp::reg_kernel_serves(kp);
+    return *is_reg ? rk->reg : &mcgp::race_kernel;
+}
+
+// deviates = MCGP_DEVIATES_53 has the register kernel's code only: a problem that kernel does not take is refused.
+int check_wide(const mcgp::KParams &kp)
+{
+    if (kp.wide && (!reg_kernels((uint32_t)kp.n) || !mcgp::reg_kernel_serves(kp)))
+        return fail(MCGP_E_BAD_ARG, "deviates = MCGP_DEVIATES_53 serves the problems the register kernel takes "
+                                    "(reg_kernel_serves: lap times clear of zero, overtake_delta >= 0)");
+    return MCGP_OK;
+}
+
+// The generic-shaped kernels (resume, trace, strategy) have no 53-bit path; `what` is the subject of the message.
+int check_deviates_32(const mcgp::KParams &kp, const char *what)
+{
+    if (kp.wide)
+        return fail(MCGP_E_BAD_ARG, std::string("deviates: ") + what +
+                                        " at MCGP_DEVIATES_32 only (the generic kernel has no 53-bit path)");
+    return MCGP_OK;
 }
 
 // Launch geometry: persistent blocks striding over batches of `block` simulations.  The register kernel's
@@ -469,6 +449,19 @@ void launch_geometry(const DeviceCtx &c, uint32_t n, bool is_reg, KernelFn kerne
     *lds = (uint32_t)bytes;
 }
 
+// The launch shape of a generic-shaped kernel (resume, trace, strategy: the generic race kernel's block and LDS) for
+// `n_sims` simulations; MCGP_E_HIP when its block needs more LDS than the device offers.  `name` is the kernel's, for
+// the message.
+int generic_geometry(const DeviceCtx &c, KernelFn kernel, const char *name, uint32_t n, uint64_t n_sims, uint32_t *grid,
+                     uint32_t *block, uint32_t *lds)
+{
+    launch_geometry(c, n, false, kernel, n_sims, grid, block, lds);
+    if (*lds > c.lds_per_block)
+        return fail(MCGP_E_HIP, std::string("the ") + name + " kernel's block needs " + std::to_string(*lds) +
+                                    " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
+    return MCGP_OK;
+}
+
 // Most simulations one kernel launch may take.  The per-block LDS histogram counts in uint32 and a cell
 // can receive at most one count per simulation the block runs, so keeping the whole launch below 2^32
 // simulations rules out a silent wrap; longer runs are split into several launches on the same stream
@@ -483,24 +476,20 @@ uint64_t max_sims_per_launch()
     return cap;
 }
 
-// mcgp_run_trace's staging budget: a chunk of the trace holds budget / (L n) simulations (one byte per lap, driver and
-// simulation), at most max_sims_per_launch(), in multiples of 256 when it can (mcgp_run_trace then rounds it down to
-// whole rounds of the device); device memory does not grow with n_sims.
-constexpr uint64_t kTraceStageBytes = 512ull << 20;
-uint64_t trace_chunk_sims(uint32_t n, int total_laps)
-{
-    uint64_t chunk = std::min<uint64_t>(max_sims_per_launch(), std::max<uint64_t>(1, kTraceStageBytes / ((uint64_t)total_laps * n)));
-    if (chunk >= 256) chunk = chunk / 256 * 256;
-    return chunk;
-}
+// Simulations per chunk of staged finishing orders (mcgp_run with orders_out, mcgp_run_championship, mcgp_run_from_state
+// with orders_out): the staging holds kOrdersChunk x n bytes.
+constexpr uint64_t kOrdersChunk = 1ull << 22;
 
-// mcgp_run_strategies' staging budget: a chunk holds budget / (S n) simulations of every scenario (one byte per
-// scenario, simulation and driver), at most max_sims_per_launch(), in multiples of 256 when it can.
+// Staging budgets of mcgp_run_trace (one byte per lap, driver and simulation) and mcgp_run_strategies (one byte per
+// scenario, simulation and driver): device memory does not grow with n_sims.
+constexpr uint64_t kTraceStageBytes = 512ull << 20;
 constexpr uint64_t kStrategyStageBytes = 256ull << 20;
-uint64_t strategy_chunk_sims(uint32_t n, uint32_t n_scenarios)
+
+// Simulations in one chunk of such a staging: budget / bytes_per_sim, at most max_sims_per_launch(), in multiples of 256
+// when it can (mcgp_run_trace then rounds it down to whole rounds of the device).
+uint64_t stage_chunk_sims(uint64_t budget, uint64_t bytes_per_sim)
 {
-    uint64_t chunk = std::min<uint64_t>(max_sims_per_launch(),
-                                        std::max<uint64_t>(1, kStrategyStageBytes / ((uint64_t)n_scenarios * n)));
+    uint64_t chunk = std::min<uint64_t>(max_sims_per_launch(), std::max<uint64_t>(1, budget / bytes_per_sim));
     if (chunk >= 256) chunk = chunk / 256 * 256;
     return chunk;
 }
@@ -550,12 +539,11 @@ int claim_timer(DeviceCtx &c, hipStream_t stream, int *out)
     return MCGP_OK;
 }
 
-// The pair of timing events of a call that runs several kernels (mcgp_run_batch, mcgp_run_championship,
-// mcgp_run_matchups): recorded on the null stream around everything the call runs, so that mcgp_last_kernel_ms
-// afterwards gives the whole call.
+// The pair of timing events of a call that runs several kernels (on_device): recorded on the null stream around
+// everything the call runs, so that mcgp_last_kernel_ms afterwards gives the whole call.
 int ensure_call_events(DeviceCtx &c)
 {
-    if (c.batch_start) return MCGP_OK;
+    if (c.call_start) return MCGP_OK;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t err = hipEventCreate(&e0);
     if (err == hipSuccess) err = hipEventCreate(&e1);
@@ -563,9 +551,23 @@ int ensure_call_events(DeviceCtx &c)
         if (e0) (void)hipEventDestroy(e0);
         return fail(MCGP_E_HIP, std::string("batch timing events: ") + hipGetErrorString(err));
     }
-    c.batch_start = e0;
-    c.batch_stop = e1;
+    c.call_start = e0;
+    c.call_stop = e1;
     return MCGP_OK;
+}
+
+// The launch that mcgp_last_launch_info and mcgp_last_kernel_name report: its shape and its kernel's name (a printf
+// format and its arguments).
+__attribute__((format(printf, 5, 6))) void note_launch(DeviceCtx &c, uint32_t grid, uint32_t block, uint32_t lds,
+                                                       const char *name, ...)
+{
+    c.last_grid = grid;
+    c.last_block = block;
+    c.last_lds = lds;
+    va_list args;
+    va_start(args, name);
+    std::vsnprintf(c.last_kernel, sizeof(c.last_kernel), name, args);
+    va_end(args);
 }
 
 int launch(DeviceCtx &c, const mcgp::KParams &kp, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
@@ -578,10 +580,9 @@ int launch(DeviceCtx &c, const mcgp::KParams &kp, uint64_t n_sims, uint64_t sim_
     // the reference-width build (mcgp_config.deviates = MCGP_DEVIATES_53): the register kernel's geometry, its own code
     WideKernelFn wide = nullptr;
     if (kp.wide) {
-        wide = select_wide_kernel((uint32_t)kp.n);
-        if (!wide || !mcgp::reg_kernel_serves(kp))
-            return fail(MCGP_E_BAD_ARG, "deviates = MCGP_DEVIATES_53 serves the problems the register kernel takes "
-                                        "(reg_kernel_serves: lap times clear of zero, overtake_delta >= 0)");
+        const int rc = check_wide(kp);
+        if (rc != MCGP_OK) return rc;
+        wide = reg_kernels((uint32_t)kp.n)->wide;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wide), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)c.lds_per_block));
         is_reg = true;
@@ -641,11 +642,8 @@ int launch(DeviceCtx &c, const mcgp::KParams &kp, uint64_t n_sims, uint64_t sim_
     for (uint64_t done = 0; done < n_sims; done += cap) {
         const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
         for (;;) {
-            KernelFn k = kernel;
-            if (small_shape) {
-                k = select_small_kernel((uint32_t)kp.n);
-                if (!k) return fail(MCGP_E_HIP, "no small-block instantiation for this field size");
-            }
+            // (small_shape is only ever set for the register kernel, whose field size has an entry)
+            const KernelFn k = small_shape ? reg_kernels((uint32_t)kp.n)->small : kernel;
             launch_geometry(c, (uint32_t)kp.n, is_reg, wide ? reinterpret_cast<KernelFn>(wide) : k, m, &grid, &block, &lds,
                             wide ? mcgp::wide_block_waves(kp.n) : small_shape ? mcgp::kSmallBlockWaves : 0, wide != nullptr,
                             kp.total_laps);
@@ -670,33 +668,27 @@ int launch(DeviceCtx &c, const mcgp::KParams &kp, uint64_t n_sims, uint64_t sim_
             // of the generic kernel takes batches of `block` by its index (both < 2^32 because m < 2^32)
             const uint64_t unit = is_reg ? 64u : block;
             const uint64_t n_batches = (m + unit - 1) / unit;
+            DevBuf &retire = c.timer[ti].retire;
             if (is_reg) {
                 HIP_TRY(hipMemsetAsync(c.timer[ti].d_ticket, 0, sizeof(uint32_t), stream));
                 // the lanes' retirement lists: scratch of the launch, (n + 1) words per lane, kept per stream and grown on
                 // demand (a launch of this stream that still uses the old buffer has been enqueued before the free, which
                 // the runtime orders behind it)
                 const size_t want = mcgp::reg_retire_ws_bytes(kp.n, (size_t)grid * block);
-                if (want > c.timer[ti].retire_bytes) {
-                    if (c.timer[ti].d_retire) {
-                        HIP_TRY(hipStreamSynchronize(stream));
-                        (void)hipFree(c.timer[ti].d_retire);
-                    }
-                    c.timer[ti].d_retire = nullptr;
-                    c.timer[ti].retire_bytes = 0;
-                    HIP_TRY(hipMalloc(&c.timer[ti].d_retire, want));
-                    c.timer[ti].retire_bytes = want;
-                }
+                if (want > retire.bytes && retire.p) HIP_TRY(hipStreamSynchronize(stream));
+                const int rc = retire.reserve(want);
+                if (rc != MCGP_OK) return rc;
             }
             if (wide)
                 hipLaunchKernelGGL(wide, dim3(grid), dim3(block), lds, stream, sl->dev, m, sim_offset + done,
                                    (uint32_t)seed, (uint32_t)(seed >> 32), d_hist,
                                    d_orders ? d_orders + (size_t)done * (size_t)kp.n : nullptr, d_fixed_grid,
-                                   (uint32_t)n_batches, c.timer[ti].d_ticket, c.timer[ti].d_retire, c.d_norm53);
+                                   (uint32_t)n_batches, c.timer[ti].d_ticket, retire.at<uint32_t>(), c.d_norm53);
             else
                 hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, stream, sl->dev, m, sim_offset + done,
                                    (uint32_t)seed, (uint32_t)(seed >> 32), d_hist,
                                    d_orders ? d_orders + (size_t)done * (size_t)kp.n : nullptr, d_fixed_grid,
-                                   (uint32_t)n_batches, c.timer[ti].d_ticket, c.timer[ti].d_retire);
+                                   (uint32_t)n_batches, c.timer[ti].d_ticket, retire.at<uint32_t>());
             const hipError_t e = hipGetLastError();
             if (e == hipSuccess) break;
             if (may_shrink && resource_error(e)) {                  // refused for its resources: once more, small blocks
@@ -733,14 +725,73 @@ int launch(DeviceCtx &c, const mcgp::KParams &kp, uint64_t n_sims, uint64_t sim_
         rd->seq = c.timer_seq;
         HIP_TRY(hipEventRecord(rd->done, stream));
     }
-    c.last_grid = grid;
-    c.last_block = block;
-    c.last_lds = lds;
-    if (wide) std::snprintf(c.last_kernel, sizeof(c.last_kernel), "mcgp::race_kernel_reg_wide<%d>", kp.n);
-    else if (is_reg && small_shape) std::snprintf(c.last_kernel, sizeof(c.last_kernel), "mcgp::race_kernel_reg<%d, %d>", kp.n, mcgp::kSmallBlockWaves);
-    else if (is_reg) std::snprintf(c.last_kernel, sizeof(c.last_kernel), "mcgp::race_kernel_reg<%d>", kp.n);
-    else std::snprintf(c.last_kernel, sizeof(c.last_kernel), "mcgp::race_kernel");
+    if (wide) note_launch(c, grid, block, lds, "mcgp::race_kernel_reg_wide<%d>", kp.n);
+    else if (is_reg && small_shape) note_launch(c, grid, block, lds, "mcgp::race_kernel_reg<%d, %d>", kp.n, mcgp::kSmallBlockWaves);
+    else if (is_reg) note_launch(c, grid, block, lds, "mcgp::race_kernel_reg<%d>", kp.n);
+    else note_launch(c, grid, block, lds, "mcgp::race_kernel");
     return MCGP_OK;
+}
+
+// Offsets of one call's regions in the workspace, each region rounded up to 256 bytes.
+struct Layout {
+    size_t bytes = 0;
+    size_t add(size_t region)
+    {
+        const size_t at = bytes;
+        bytes += (region + 255) / 256 * 256;
+        return at;
+    }
+};
+
+// The counts of one call: downloaded in one piece while the call holds its context, then added into the caller's
+// buffers once the whole call has returned MCGP_OK.  No entry point adds into a caller's buffer any other way, so a call
+// that fails leaves them untouched (and a retry counts nothing twice).
+struct Counts {
+    struct Seg {
+        uint64_t *dst;                      // a caller's buffer, or NULL: not wanted
+        size_t cells;
+    };
+    std::vector<unsigned long long> v;
+    int download(const void *d_src, size_t cells)
+    {
+        v.resize(cells);
+        HIP_TRY(hipMemcpy(v.data(), d_src, cells * 8, hipMemcpyDeviceToHost));
+        return MCGP_OK;
+    }
+    void add_to(const std::vector<Seg> &segs) const     // segs: in the order of the counts on the device
+    {
+        const unsigned long long *src = v.data();
+        for (const Seg &s : segs) {
+            if (s.dst)
+                for (size_t i = 0; i < s.cells; ++i) s.dst[i] += src[i];
+            src += s.cells;
+        }
+    }
+};
+
+// One call on `device`: looks its context up, holds the context's lock for the whole call, initialises it on first use,
+// makes the device current and runs body(context).  timed: a call of several kernels, bracketed on the null stream by
+// the call's own pair of events, so that mcgp_last_kernel_ms afterwards gives everything it ran; once the start is
+// recorded the stop is recorded too, whatever the body returns, so that no start is left paired with an older stop.
+template <class Body>
+int on_device(int32_t device, bool timed, Body &&body)
+{
+    DeviceCtx *c = nullptr;
+    int rc = find_ctx(device, &c);
+    if (rc != MCGP_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    rc = ensure_ctx_locked(device, *c);
+    if (rc != MCGP_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if (!timed) return body(*c);
+    rc = ensure_call_events(*c);
+    if (rc != MCGP_OK) return rc;
+    HIP_TRY(hipEventRecord(c->call_start, nullptr));
+    rc = body(*c);
+    const hipError_t e = hipEventRecord(c->call_stop, nullptr);
+    c->last_timer = e == hipSuccess ? kCallTimer : -1;        // (a pair without its stop is not reported)
+    if (rc == MCGP_OK && e != hipSuccess) return fail(MCGP_E_HIP, std::string("call timing event: ") + hipGetErrorString(e));
+    return rc;
 }
 
 // One mcgp_race_state in the resume kernel's encoding, checked against the limits of include/mcgp.h; "" if it passes,
@@ -869,18 +920,11 @@ int32_t mcgp_run_device(const mcgp_config *cfg, const mcgp_drivers *drv, const d
     mcgp::KParams *kp = new (std::nothrow) mcgp::KParams;
     if (!kp) return fail(MCGP_E_NOMEM, "host allocation failed");
     int rc = build_params(cfg, drv, grid_probs, n, kp);
-    DeviceCtx *c = nullptr;
-    if (rc == MCGP_OK) rc = find_ctx(device, &c);
-    if (rc == MCGP_OK) {
-        std::lock_guard<std::mutex> lock(c->mu);
-        rc = ensure_ctx_locked(device, *c);
-        if (rc == MCGP_OK) {
-            hipError_t e = hipSetDevice(device);
-            if (e != hipSuccess) rc = fail(MCGP_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-            else rc = launch(*c, *kp, n_sims, sim_offset, seed, (hipStream_t)stream,
-                             reinterpret_cast<unsigned long long *>(d_hist), d_orders, nullptr);
-        }
-    }
+    if (rc == MCGP_OK)
+        rc = on_device(device, false, [&](DeviceCtx &c) {
+            return launch(c, *kp, n_sims, sim_offset, seed, (hipStream_t)stream,
+                          reinterpret_cast<unsigned long long *>(d_hist), d_orders, nullptr);
+        });
     delete kp;
     return rc;
 }
@@ -893,46 +937,30 @@ int32_t mcgp_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *
     mcgp::KParams *kp = new (std::nothrow) mcgp::KParams;
     if (!kp) return fail(MCGP_E_NOMEM, "host allocation failed");
     int rc = build_params(cfg, drv, grid_probs, n, kp);
-    DeviceCtx *c = nullptr;
-    if (rc == MCGP_OK) rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) { delete kp; return rc; }
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        const size_t hist_bytes = sizeof(unsigned long long) * n * n;
-        HIP_TRY(hipMemsetAsync(c->d_hist, 0, hist_bytes, nullptr));
-        // per-simulation orders are staged in chunks so the device buffer stays bounded; the staging
-        // buffer is kept in the context (grown on demand), not allocated per call
-        const uint64_t chunk = orders_out ? (uint64_t)(1u << 22) : n_sims;
-        if (orders_out && n_sims) {
-            const size_t want = (size_t)(chunk < n_sims ? chunk : n_sims) * n;
-            if (want > c->d_orders_bytes) {
-                if (c->d_orders) (void)hipFree(c->d_orders);
-                c->d_orders = nullptr;
-                c->d_orders_bytes = 0;
-                HIP_TRY(hipMalloc(&c->d_orders, want));
-                c->d_orders_bytes = want;
+    Counts counts;
+    if (rc == MCGP_OK)
+        rc = on_device(device, false, [&](DeviceCtx &c) -> int {
+            HIP_TRY(hipMemsetAsync(c.d_hist, 0, sizeof(unsigned long long) * n * n, nullptr));
+            // per-simulation orders are staged in chunks so the device buffer stays bounded
+            const uint64_t chunk = orders_out ? kOrdersChunk : n_sims;
+            if (orders_out) {
+                const int r = c.work.reserve((size_t)std::min(chunk, n_sims) * n);
+                if (r != MCGP_OK) return r;
             }
-        }
-        uint8_t *d_orders = orders_out ? c->d_orders : nullptr;
-        for (uint64_t done = 0; done < n_sims && r == MCGP_OK; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            r = launch(*c, *kp, m, sim_offset + done, seed, nullptr, c->d_hist, d_orders, nullptr);
-            if (r == MCGP_OK && d_orders) {
-                hipError_t e = hipMemcpy(orders_out + (size_t)done * n, d_orders, (size_t)m * n, hipMemcpyDeviceToHost);
-                if (e != hipSuccess) r = fail(MCGP_E_HIP, std::string("hipMemcpy(orders): ") + hipGetErrorString(e));
+            uint8_t *d_orders = orders_out ? c.work.at<uint8_t>() : nullptr;
+            for (uint64_t done = 0; done < n_sims; done += chunk) {
+                const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+                const int r = launch(c, *kp, m, sim_offset + done, seed, nullptr, c.d_hist, d_orders, nullptr);
+                if (r != MCGP_OK) return r;
+                if (d_orders) {
+                    const hipError_t e = hipMemcpy(orders_out + (size_t)done * n, d_orders, (size_t)m * n, hipMemcpyDeviceToHost);
+                    if (e != hipSuccess) return fail(MCGP_E_HIP, std::string("hipMemcpy(orders): ") + hipGetErrorString(e));
+                }
             }
-        }
-        if (r != MCGP_OK) return r;
-        unsigned long long h[MCGP_MAX_CARS * MCGP_MAX_CARS];
-        HIP_TRY(hipMemcpy(h, c->d_hist, hist_bytes, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n * n; ++i) hist_out[i] += h[i];
-        return MCGP_OK;
-    };
-    rc = body();
+            return counts.download(c.d_hist, (size_t)n * n);
+        });
     delete kp;
+    if (rc == MCGP_OK) counts.add_to({{hist_out, (size_t)n * n}});
     return rc;
 }
 
@@ -950,24 +978,15 @@ int32_t mcgp_simulate_race(const mcgp_config *cfg, const mcgp_drivers *drv, cons
     mcgp::KParams *kp = new (std::nothrow) mcgp::KParams;
     if (!kp) return fail(MCGP_E_NOMEM, "host allocation failed");
     int rc = build_params(cfg, drv, nullptr, n, kp);
-    DeviceCtx *c = nullptr;
-    if (rc == MCGP_OK) rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) { delete kp; return rc; }
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMemcpy(c->d_grid, grid, n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(c->d_hist, 0, sizeof(unsigned long long) * n * n, nullptr));
-        r = launch(*c, *kp, 1, sim_id, seed, nullptr, c->d_hist, c->d_order1, c->d_grid);
-        if (r == MCGP_OK) {
-            hipError_t e = hipMemcpy(order_out, c->d_order1, n, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) r = fail(MCGP_E_HIP, std::string("hipMemcpy(order): ") + hipGetErrorString(e));
-        }
-        return r;
-    };
-    rc = body();
+    if (rc == MCGP_OK)
+        rc = on_device(device, false, [&](DeviceCtx &c) -> int {
+            HIP_TRY(hipMemcpy(c.d_grid, grid, n, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemsetAsync(c.d_hist, 0, sizeof(unsigned long long) * n * n, nullptr));
+            const int r = launch(c, *kp, 1, sim_id, seed, nullptr, c.d_hist, c.d_order1, c.d_grid);
+            if (r != MCGP_OK) return r;
+            const hipError_t e = hipMemcpy(order_out, c.d_order1, n, hipMemcpyDeviceToHost);
+            return e == hipSuccess ? MCGP_OK : fail(MCGP_E_HIP, std::string("hipMemcpy(order): ") + hipGetErrorString(e));
+        });
     delete kp;
     return rc;
 }
@@ -1002,23 +1021,15 @@ int32_t mcgp_grid_probs(const double *quali_rating, const double *teammate_delta
                         double *grid_probs_out)
 {
     if (!grid_probs_out) return fail(MCGP_E_BAD_ARG, "grid_probs_out is NULL");
-    DeviceCtx *c = nullptr;
-    int rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
+    return on_device(device, false, [&](DeviceCtx &c) -> int {
+        const int r = upload_front_end(c, quali_rating, teammate_delta, form_score, circuit_affinity, penalty, n);
         if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        r = upload_front_end(*c, quali_rating, teammate_delta, form_score, circuit_affinity, penalty, n);
-        if (r != MCGP_OK) return r;
-        hipLaunchKernelGGL(grid_probs_kernel, dim3(1), dim3(mcgp::kMaxCars), 0, nullptr, c->d_fe_in, c->d_fe_pen, (int)n,
-                           c->d_fe_out);
+        hipLaunchKernelGGL(grid_probs_kernel, dim3(1), dim3(mcgp::kMaxCars), 0, nullptr, c.d_fe_in, c.d_fe_pen, (int)n,
+                           c.d_fe_out);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(grid_probs_out, c->d_fe_out, sizeof(double) * n * n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(grid_probs_out, c.d_fe_out, sizeof(double) * n * n, hipMemcpyDeviceToHost));
         return MCGP_OK;
-    };
-    return body();
+    });
 }
 
 int32_t mcgp_elo_season(uint32_t n_drivers, uint32_t n_events, const int32_t *kind, const double *k,
@@ -1044,10 +1055,6 @@ int32_t mcgp_elo_season(uint32_t n_drivers, uint32_t n_events, const int32_t *ki
             if (!std::isfinite(value[(size_t)e * n + j])) return fail(MCGP_E_BAD_ARG, "non-finite lap time / position");
         }
     }
-    DeviceCtx *c = nullptr;
-    int rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
     // one buffer for everything the kernel reads and writes, packed on the host: one upload, one launch, one
     // download (the call is latency-bound: a season is a few hundred events for one wavefront)
     const size_t ne = n_events, row = n;
@@ -1064,18 +1071,10 @@ int32_t mcgp_elo_season(uint32_t n_drivers, uint32_t n_events, const int32_t *ki
         std::memcpy(host.data() + in0 + (o_cnt - o_k), count, ne * 4);
         std::memcpy(host.data() + in0 + (o_who - o_k), who, ne * row);
     }
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
+    return on_device(device, false, [&](DeviceCtx &c) -> int {
+        const int r = c.work.reserve(bytes);
         if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        if (c->elo_bytes < bytes) {                                    // grow-only scratch of the context
-            if (c->d_elo) (void)hipFree(c->d_elo);
-            c->d_elo = nullptr;
-            c->elo_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_elo, bytes));
-            c->elo_bytes = bytes;
-        }
-        unsigned char *d = c->d_elo;
+        unsigned char *d = c.work.at();
         HIP_TRY(hipMemcpy(d + o_rat, host.data(), 2 * row * 8, hipMemcpyHostToDevice));
         if (ne) HIP_TRY(hipMemcpy(d + o_k, host.data() + in0, bytes - o_k, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(elo_season_kernel, dim3(1), dim3(mcgp::kMaxCars * mcgp::kMaxCars), 0, nullptr, (int)n, (int)n_events,
@@ -1094,8 +1093,7 @@ int32_t mcgp_elo_season(uint32_t n_drivers, uint32_t n_events, const int32_t *ki
             HIP_TRY(hipMemcpy(ratings, d + o_rat, 2 * row * 8, hipMemcpyDeviceToHost));
         }
         return MCGP_OK;
-    };
-    return body();
+    });
 }
 
 int32_t mcgp_run_from_ratings(const mcgp_config *cfg, const mcgp_drivers *drv, const double *quali_rating,
@@ -1108,37 +1106,27 @@ int32_t mcgp_run_from_ratings(const mcgp_config *cfg, const mcgp_drivers *drv, c
     mcgp::KParams *kp = new (std::nothrow) mcgp::KParams;
     if (!kp) return fail(MCGP_E_NOMEM, "host allocation failed");
     int rc = build_params(cfg, drv, nullptr, n, kp);               // grid_probs slot left zero: the device fills it
-    DeviceCtx *c = nullptr;
-    if (rc == MCGP_OK) rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) { delete kp; return rc; }
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        r = upload_front_end(*c, quali_rating, teammate_delta, form_score, circuit_affinity, penalty, n);
-        if (r != MCGP_OK) return r;
-        const size_t hist_bytes = sizeof(unsigned long long) * n * n;
-        HIP_TRY(hipMemsetAsync(c->d_hist, 0, hist_bytes, nullptr));
-        FrontEnd fe;
-        fe.on = true;
-        r = launch(*c, *kp, n_sims, sim_offset, seed, nullptr, c->d_hist, nullptr, nullptr, fe);
-        if (r != MCGP_OK) return r;
-        unsigned long long h[MCGP_MAX_CARS * MCGP_MAX_CARS];
-        HIP_TRY(hipMemcpy(h, c->d_hist, hist_bytes, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n * n; ++i) hist_out[i] += h[i];
-        if (grid_probs_out) {
+    Counts counts;
+    if (rc == MCGP_OK)
+        rc = on_device(device, false, [&](DeviceCtx &c) -> int {
+            int r = upload_front_end(c, quali_rating, teammate_delta, form_score, circuit_affinity, penalty, n);
+            if (r != MCGP_OK) return r;
+            HIP_TRY(hipMemsetAsync(c.d_hist, 0, sizeof(unsigned long long) * n * n, nullptr));
+            FrontEnd fe;
+            fe.on = true;
+            r = launch(c, *kp, n_sims, sim_offset, seed, nullptr, c.d_hist, nullptr, nullptr, fe);
+            if (r == MCGP_OK) r = counts.download(c.d_hist, (size_t)n * n);
+            if (r != MCGP_OK || !grid_probs_out) return r;
             // the matrix the race kernel sampled from, recomputed by the same kernel from the same inputs into the
             // context's scratch matrix (the parameter block itself is not read back)
-            hipLaunchKernelGGL(grid_probs_kernel, dim3(1), dim3(mcgp::kMaxCars), 0, nullptr, c->d_fe_in, c->d_fe_pen, (int)n,
-                               c->d_fe_out);
+            hipLaunchKernelGGL(grid_probs_kernel, dim3(1), dim3(mcgp::kMaxCars), 0, nullptr, c.d_fe_in, c.d_fe_pen, (int)n,
+                               c.d_fe_out);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpy(grid_probs_out, c->d_fe_out, sizeof(double) * n * n, hipMemcpyDeviceToHost));
-        }
-        return MCGP_OK;
-    };
-    rc = body();
+            HIP_TRY(hipMemcpy(grid_probs_out, c.d_fe_out, sizeof(double) * n * n, hipMemcpyDeviceToHost));
+            return MCGP_OK;
+        });
     delete kp;
+    if (rc == MCGP_OK) counts.add_to({{hist_out, (size_t)n * n}});
     return rc;
 }
 
@@ -1159,19 +1147,16 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
     std::vector<mcgp::BatchItem> items;
     std::vector<uint32_t> shared_index, solo_index;  // original indices
     std::vector<mcgp::KParams> solo_kps;
-    const char *force = std::getenv("MCGP_FORCE_GENERIC");
-    const bool force_generic = force && force[0] == '1';
-    const BatchKernelFn kernel = select_batch_kernel(n);
+    const bool generic = force_generic();
+    const RegKernels *rk = reg_kernels(n);
     {
         mcgp::KParams kp;
         for (uint32_t p = 0; p < n_problems; ++p) {
             if (!grid_probs[p]) return fail(MCGP_E_BAD_ARG, "a grid_probs pointer of the batch is NULL");
-            const int rc = build_params(&cfgs[p], &drvs[p], grid_probs[p], n, &kp);
+            int rc = build_params(&cfgs[p], &drvs[p], grid_probs[p], n, &kp);
+            if (rc == MCGP_OK) rc = check_wide(kp);
             if (rc != MCGP_OK) return rc;
-            if (kp.wide && !mcgp::reg_kernel_serves(kp))
-                return fail(MCGP_E_BAD_ARG, "deviates = MCGP_DEVIATES_53 serves the problems the register kernel takes "
-                                            "(reg_kernel_serves: lap times clear of zero, overtake_delta >= 0)");
-            if (!kernel || force_generic || kp.wide || !mcgp::reg_kernel_serves(kp)) {
+            if (!rk || generic || kp.wide || !mcgp::reg_kernel_serves(kp)) {
                 solo_index.push_back(p);
                 solo_kps.push_back(kp);
             } else {
@@ -1182,94 +1167,62 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
         }
     }
     const uint32_t n_shared = (uint32_t)kps.size();
-    DeviceCtx *c = nullptr;
-    int rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
+    const size_t cells = (size_t)n * n;
+    Counts counts;
+    const int rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        // geometry of the shared launch: the register kernel's block, one more LDS word that names the block's next problem
+        const int waves = mcgp::reg_block_waves((int)n);
+        const uint32_t block = (uint32_t)waves * 64u;
+        const size_t lds = mcgp::shared_lds_bytes_reg((int)n) + (size_t)block * mcgp::per_thread_lds_bytes_reg((int)n) +
+                           mcgp::kBatchLdsExtra;
+        int reg_cap = 4 * mcgp::reg_min_waves((int)n);
+        int blocks_per_cu = (int)(c.lds_per_block / lds);
+        if (blocks_per_cu * waves > reg_cap) blocks_per_cu = reg_cap / waves;
+        if (blocks_per_cu < 1) blocks_per_cu = 1;
+        const uint32_t n_chunks = (uint32_t)((n_sims + 63) / 64);
+        // no more blocks than the batch has wave-chunks to fill them with
+        const uint64_t n_tasks = ((uint64_t)n_shared * n_chunks + (uint64_t)waves - 1) / (uint64_t)waves;
+        uint64_t grid = (uint64_t)c.cu_count * (uint64_t)blocks_per_cu;
+        if (grid > n_tasks) grid = n_tasks;
+        // workspace: parameter blocks | items | histograms (the shared launch's problems, then the solo ones) | one ticket
+        // counter per problem of the shared launch | its lanes' retirement lists
+        Layout ws;
+        const size_t o_kps = ws.add(sizeof(mcgp::KParams) * n_shared), o_items = ws.add(sizeof(mcgp::BatchItem) * n_shared);
+        const size_t o_hist = ws.add(sizeof(unsigned long long) * cells * n_problems);
+        const size_t o_ticket = ws.add(sizeof(uint32_t) * n_shared);
+        const size_t o_retire = ws.add(mcgp::reg_retire_ws_bytes((int)n, (size_t)grid * block));
+        int r = c.work.reserve(ws.bytes);
         if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        // the call's own pair of timing events (mcgp_last_kernel_ms after a batch call = everything it ran on the device)
-        r = ensure_call_events(*c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
-        const size_t cell_bytes = sizeof(unsigned long long) * n * n;
+        unsigned long long *d_hist = c.work.at<unsigned long long>(o_hist);
+        HIP_TRY(hipMemsetAsync(d_hist, 0, o_retire - o_hist, nullptr));         // the histograms and ticket counters
         if (n_shared) {
+            const BatchKernelFn kernel = rk->batch;
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)c->lds_per_block));
-            // geometry: the register kernel's block, one more LDS word that names the block's next problem
-            const int waves = mcgp::reg_block_waves((int)n);
-            const uint32_t block = (uint32_t)waves * 64u;
-            const size_t lds = mcgp::shared_lds_bytes_reg((int)n) + (size_t)block * mcgp::per_thread_lds_bytes_reg((int)n) +
-                               mcgp::kBatchLdsExtra;
-            int reg_cap = 4 * mcgp::reg_min_waves((int)n);
-            int blocks_per_cu = (int)(c->lds_per_block / lds);
-            if (blocks_per_cu * waves > reg_cap) blocks_per_cu = reg_cap / waves;
-            if (blocks_per_cu < 1) blocks_per_cu = 1;
-            const uint32_t n_chunks = (uint32_t)((n_sims + 63) / 64);
-            // no more blocks than the batch has wave-chunks to fill them with
-            const uint64_t n_tasks = ((uint64_t)n_shared * n_chunks + (uint64_t)waves - 1) / (uint64_t)waves;
-            uint64_t grid = (uint64_t)c->cu_count * (uint64_t)blocks_per_cu;
-            if (grid > n_tasks) grid = n_tasks;
-            // one device buffer: [parameter blocks | items | histograms | one ticket counter per problem]
-            const size_t o_items = sizeof(mcgp::KParams) * n_shared;
-            const size_t o_hist = o_items + sizeof(mcgp::BatchItem) * n_shared;
-            const size_t hist_bytes = cell_bytes * n_shared;
-            const size_t o_ticket = o_hist + hist_bytes;
-            const size_t ticket_bytes = (sizeof(uint32_t) * n_shared + 15) / 16 * 16;
-            const size_t bytes = o_ticket + ticket_bytes;
-            if (bytes > c->batch_bytes) {
-                if (c->d_batch) (void)hipFree(c->d_batch);
-                c->d_batch = nullptr;
-                c->batch_bytes = 0;
-                HIP_TRY(hipMalloc(&c->d_batch, bytes));
-                c->batch_bytes = bytes;
-            }
-            const size_t ws = mcgp::reg_retire_ws_bytes((int)n, (size_t)grid * block);
-            if (ws > c->batch_retire_bytes) {
-                if (c->d_batch_retire) (void)hipFree(c->d_batch_retire);
-                c->d_batch_retire = nullptr;
-                c->batch_retire_bytes = 0;
-                HIP_TRY(hipMalloc(&c->d_batch_retire, ws));
-                c->batch_retire_bytes = ws;
-            }
-            unsigned char *d = c->d_batch;
-            HIP_TRY(hipMemcpyAsync(d, kps.data(), o_items, hipMemcpyHostToDevice, nullptr));
-            HIP_TRY(hipMemcpyAsync(d + o_items, items.data(), sizeof(mcgp::BatchItem) * n_shared, hipMemcpyHostToDevice, nullptr));
-            HIP_TRY(hipMemsetAsync(d + o_hist, 0, hist_bytes + ticket_bytes, nullptr));
-            hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(block), lds, nullptr,
-                               reinterpret_cast<const mcgp::KParams *>(d), reinterpret_cast<const mcgp::BatchItem *>(d + o_items),
-                               n_shared, n_sims, reinterpret_cast<unsigned long long *>(d + o_hist), n_chunks,
-                               reinterpret_cast<uint32_t *>(d + o_ticket), c->d_batch_retire);
+                                        (int)c.lds_per_block));
+            HIP_TRY(hipMemcpyAsync(c.work.at(o_kps), kps.data(), sizeof(mcgp::KParams) * n_shared, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(c.work.at(o_items), items.data(), sizeof(mcgp::BatchItem) * n_shared, hipMemcpyHostToDevice,
+                                   nullptr));
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(block), lds, nullptr, c.work.at<const mcgp::KParams>(o_kps),
+                               c.work.at<const mcgp::BatchItem>(o_items), n_shared, n_sims, d_hist, n_chunks,
+                               c.work.at<uint32_t>(o_ticket), c.work.at<uint32_t>(o_retire));
             HIP_TRY(hipGetLastError());
-            std::vector<unsigned long long> h((size_t)n * n * n_shared);
-            HIP_TRY(hipMemcpy(h.data(), d + o_hist, hist_bytes, hipMemcpyDeviceToHost));
-            for (uint32_t j = 0; j < n_shared; ++j) {
-                uint64_t *out = hist_out + (size_t)shared_index[j] * n * n;
-                for (uint32_t i = 0; i < n * n; ++i) out[i] += h[(size_t)j * n * n + i];
-            }
-            c->last_grid = (uint32_t)grid;
-            c->last_block = block;
-            c->last_lds = (uint32_t)lds;
-            std::snprintf(c->last_kernel, sizeof(c->last_kernel), "mcgp::race_kernel_reg_batch<%u>", n);
+            note_launch(c, (uint32_t)grid, block, (uint32_t)lds, "mcgp::race_kernel_reg_batch<%u>", n);
         }
         // the problems that run by themselves: exactly mcgp_run's path, one after the other (null stream)
         for (size_t j = 0; j < solo_index.size(); ++j) {
             const uint32_t p = solo_index[j];
-            HIP_TRY(hipMemsetAsync(c->d_hist, 0, cell_bytes, nullptr));
-            r = launch(*c, solo_kps[j], n_sims, sim_offsets ? sim_offsets[p] : 0ull, seeds[p], nullptr, c->d_hist, nullptr, nullptr);
+            r = launch(c, solo_kps[j], n_sims, sim_offsets ? sim_offsets[p] : 0ull, seeds[p], nullptr,
+                       d_hist + (n_shared + j) * cells, nullptr, nullptr);
             if (r != MCGP_OK) return r;
-            unsigned long long h[MCGP_MAX_CARS * MCGP_MAX_CARS];
-            HIP_TRY(hipMemcpy(h, c->d_hist, cell_bytes, hipMemcpyDeviceToHost));
-            uint64_t *out = hist_out + (size_t)p * n * n;
-            for (uint32_t i = 0; i < n * n; ++i) out[i] += h[i];
         }
-        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
-        c->last_timer = kBatchTimer;
-        return MCGP_OK;
-    };
-    return body();
+        return counts.download(d_hist, cells * n_problems);
+    });
+    if (rc != MCGP_OK) return rc;
+    std::vector<Counts::Seg> segs;                  // in the order of the histograms on the device
+    for (uint32_t p : shared_index) segs.push_back({hist_out + (size_t)p * cells, cells});
+    for (uint32_t p : solo_index) segs.push_back({hist_out + (size_t)p * cells, cells});
+    counts.add_to(segs);
+    return MCGP_OK;
 }
 
 // Bits needed to hold x (at least 1).
@@ -1329,11 +1282,9 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
     std::vector<mcgp::KParams> kps(n_races);
     for (uint32_t r = 0; r < n_races; ++r) {
         if (!grid_probs[r]) return fail(MCGP_E_BAD_ARG, "a grid_probs pointer of the championship is NULL");
-        const int rc = build_params(&cfgs[r], &drvs[r], grid_probs[r], n, &kps[r]);
+        int rc = build_params(&cfgs[r], &drvs[r], grid_probs[r], n, &kps[r]);
+        if (rc == MCGP_OK) rc = check_wide(kps[r]);
         if (rc != MCGP_OK) return rc;
-        if (kps[r].wide && !mcgp::reg_kernel_serves(kps[r]))
-            return fail(MCGP_E_BAD_ARG, "deviates = MCGP_DEVIATES_53 serves the problems the register kernel takes "
-                                        "(reg_kernel_serves: lap times clear of zero, overtake_delta >= 0)");
     }
     // ---- key layouts.  Drivers: 5-bit counts and 16-bit points (the limits checked above).  Teams: a team's count in a
     // position grows by at most one per countback race, its points by at most what its drivers can take; the fields
@@ -1378,108 +1329,73 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
                     mcgp::champ_piece((uint64_t)points[(size_t)r * n + p], mcgp::kChampCountBits * (int)n, (int)w) |
                     (countback[r] ? mcgp::champ_piece(1, mcgp::kChampCountBits * (int)(n - 1 - p), (int)w) : 0ull);
     const uint32_t gain_cols = (uint32_t)G + 1;
-    DeviceCtx *c = nullptr;
-    int rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        r = ensure_call_events(*c);
-        if (r != MCGP_OK) return r;
+    const size_t champ_cells = (size_t)n * n, team_cells = (size_t)n_teams * n_teams, gain_cells = (size_t)n * gain_cols;
+    const size_t race_cells = race_hist ? (size_t)n_races * n * n : 0;
+    const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells;
+    Counts counts;
+    const int rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         // rank kernel's LDS: the gain histogram joins the block when the block still leaves room for a second one
         const mcgp::ChampRankLds lds_base = mcgp::champ_rank_lds(n, words, n_teams, team_words, gain_cols, false);
         const mcgp::ChampRankLds lds_gain = mcgp::champ_rank_lds(n, words, n_teams, team_words, gain_cols, true);
-        const bool gain_in_lds = lds_gain.bytes <= c->lds_per_block / 2;
+        const bool gain_in_lds = lds_gain.bytes <= c.lds_per_block / 2;
         const uint32_t rank_lds = gain_in_lds ? lds_gain.bytes : lds_base.bytes;
-        if (rank_lds > c->lds_per_block)
+        if (rank_lds > c.lds_per_block)
             return fail(MCGP_E_HIP, "the standings kernel needs " + std::to_string(rank_lds) + " bytes of LDS, the device offers " +
-                                        std::to_string(c->lds_per_block) + " per block");
+                                        std::to_string(c.lds_per_block) + " per block");
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::champ_rank),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_lds));
-        // buffers: orders staging (shared with mcgp_run), keys of one chunk, tables and histograms; all grow-only
-        const uint64_t chunk = (uint64_t)1 << 22;
-        const uint64_t cap = n_sims < chunk ? n_sims : chunk;
-        if (cap * n > c->d_orders_bytes) {
-            if (c->d_orders) (void)hipFree(c->d_orders);
-            c->d_orders = nullptr;
-            c->d_orders_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_orders, cap * n));
-            c->d_orders_bytes = cap * n;
-        }
-        const size_t key_bytes = (size_t)words * n * cap * 8;
-        if (key_bytes > c->champ_keys_bytes) {
-            if (c->d_champ_keys) (void)hipFree(c->d_champ_keys);
-            c->d_champ_keys = nullptr;
-            c->champ_keys_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_champ_keys, key_bytes));
-            c->champ_keys_bytes = key_bytes;
-        }
-        auto up8 = [](size_t x) { return (x + 7) / 8 * 8; };
-        const size_t o_add = 0, o_init = o_add + add.size() * 8, o_mem = o_init + init_key.size() * 8;
-        const size_t o_nmem = o_mem + up8(members.size()), o_ipts = o_nmem + up8(n_teams), o_hist = o_ipts + up8(4 * n);
-        const size_t champ_cells = (size_t)n * n, team_cells = (size_t)n_teams * n_teams, gain_cells = (size_t)n * gain_cols;
-        const size_t race_cells = race_hist ? (size_t)n_races * n * n : 0;
-        const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells;
-        const size_t bytes = o_hist + hist_cells * 8;
-        if (bytes > c->champ_bytes) {
-            if (c->d_champ) (void)hipFree(c->d_champ);
-            c->d_champ = nullptr;
-            c->champ_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_champ, bytes));
-            c->champ_bytes = bytes;
-        }
-        unsigned char *d = c->d_champ;
-        unsigned long long *h = reinterpret_cast<unsigned long long *>(d + o_hist);
-        unsigned long long *h_champ = h, *h_team = h + champ_cells, *h_gain = h_team + team_cells, *h_race = h_gain + gain_cells;
-        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
-        HIP_TRY(hipMemcpyAsync(d + o_add, add.data(), add.size() * 8, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(d + o_init, init_key.data(), init_key.size() * 8, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(d + o_mem, members.data(), members.size(), hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(d + o_nmem, n_members.data(), n_teams, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(d + o_ipts, init_pts.data(), 4 * n, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemsetAsync(h, 0, hist_cells * 8, nullptr));
+        // workspace: orders staging of one chunk | the chunk's standing keys | tables | histograms
+        const uint64_t cap = std::min(n_sims, kOrdersChunk);
+        Layout ws;
+        const size_t o_orders = ws.add(cap * n), o_keys = ws.add((size_t)words * n * cap * 8), o_add = ws.add(add.size() * 8);
+        const size_t o_init = ws.add(init_key.size() * 8), o_mem = ws.add(members.size()), o_nmem = ws.add(n_teams);
+        const size_t o_ipts = ws.add(4 * n), o_hist = ws.add(hist_cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint8_t *d_orders = c.work.at<uint8_t>(o_orders);
+        uint64_t *d_keys = c.work.at<uint64_t>(o_keys);
+        unsigned long long *h_champ = c.work.at<unsigned long long>(o_hist), *h_team = h_champ + champ_cells;
+        unsigned long long *h_gain = h_team + team_cells, *h_race = h_gain + gain_cells;
+        HIP_TRY(hipMemcpyAsync(c.work.at(o_add), add.data(), add.size() * 8, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(c.work.at(o_init), init_key.data(), init_key.size() * 8, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(c.work.at(o_mem), members.data(), members.size(), hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(c.work.at(o_nmem), n_members.data(), n_teams, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(c.work.at(o_ipts), init_pts.data(), 4 * n, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemsetAsync(h_champ, 0, hist_cells * 8, nullptr));
         // without race_hist the race kernels count into the context's scratch histogram (not read back)
-        HIP_TRY(hipMemsetAsync(c->d_hist, 0, sizeof(unsigned long long) * n * n, nullptr));
-        const uint64_t acc_cap = (uint64_t)c->cu_count * 8;
-        uint64_t rank_per_cu = c->lds_per_block / rank_lds;
+        HIP_TRY(hipMemsetAsync(c.d_hist, 0, sizeof(unsigned long long) * n * n, nullptr));
+        const uint64_t acc_cap = (uint64_t)c.cu_count * 8;
+        uint64_t rank_per_cu = c.lds_per_block / rank_lds;
         if (rank_per_cu > 8) rank_per_cu = 8;
         if (rank_per_cu < 1) rank_per_cu = 1;
-        const uint64_t rank_cap = (uint64_t)c->cu_count * rank_per_cu;
+        const uint64_t rank_cap = (uint64_t)c.cu_count * rank_per_cu;
         for (uint64_t done = 0; done < n_sims; done += cap) {
             const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
             // chunk-outer, race-inner: every race of the chunk through mcgp_run's own launch path, its orders into the
             // staging buffer, then folded into the keys before the next race overwrites them
             for (uint32_t rr = 0; rr < n_races; ++rr) {
-                r = launch(*c, kps[rr], m, sim_offset + done, seeds[rr], nullptr,
-                           race_hist ? h_race + (size_t)rr * n * n : c->d_hist, c->d_orders, nullptr);
+                r = launch(c, kps[rr], m, sim_offset + done, seeds[rr], nullptr,
+                           race_hist ? h_race + (size_t)rr * n * n : c.d_hist, d_orders, nullptr);
                 if (r != MCGP_OK) return r;
                 const uint64_t tiles = (m + mcgp::kChampAccBlock - 1) / mcgp::kChampAccBlock;
                 hipLaunchKernelGGL(mcgp::champ_accumulate, dim3((uint32_t)std::min(tiles, acc_cap)), dim3(mcgp::kChampAccBlock), 0,
-                                   nullptr, c->d_orders, m, n, words, cap, c->d_champ_keys,
-                                   reinterpret_cast<const uint64_t *>(d + o_add) + (size_t)rr * n * words,
-                                   reinterpret_cast<const uint64_t *>(d + o_init), rr == 0 ? 1u : 0u);
+                                   nullptr, d_orders, m, n, words, cap, d_keys,
+                                   c.work.at<const uint64_t>(o_add) + (size_t)rr * n * words, c.work.at<const uint64_t>(o_init),
+                                   rr == 0 ? 1u : 0u);
                 HIP_TRY(hipGetLastError());
             }
             const uint64_t tiles = (m + mcgp::kChampTile - 1) / mcgp::kChampTile;
             hipLaunchKernelGGL(mcgp::champ_rank, dim3((uint32_t)std::min(tiles, rank_cap)), dim3(mcgp::kChampRankBlock), rank_lds,
-                               nullptr, c->d_champ_keys, m, cap, n, words, n_teams, team_words, team_cbits, d + o_mem,
-                               d + o_nmem, reinterpret_cast<const int32_t *>(d + o_ipts), gain_cols, gain_in_lds ? 1u : 0u,
+                               nullptr, d_keys, m, cap, n, words, n_teams, team_words, team_cbits, c.work.at<const uint8_t>(o_mem),
+                               c.work.at<const uint8_t>(o_nmem), c.work.at<const int32_t>(o_ipts), gain_cols, gain_in_lds ? 1u : 0u,
                                h_champ, h_team, h_gain);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
-        c->last_timer = kBatchTimer;
-        std::vector<unsigned long long> back(hist_cells);
-        HIP_TRY(hipMemcpy(back.data(), h, hist_cells * 8, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < champ_cells; ++i) champ_hist[i] += back[i];
-        for (size_t i = 0; i < team_cells; ++i) team_hist[i] += back[champ_cells + i];
-        for (size_t i = 0; i < gain_cells; ++i) gain_hist[i] += back[champ_cells + team_cells + i];
-        for (size_t i = 0; i < race_cells; ++i) race_hist[i] += back[champ_cells + team_cells + gain_cells + i];
-        return MCGP_OK;
-    };
-    return body();
+        return counts.download(h_champ, hist_cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to({{champ_hist, champ_cells}, {team_hist, team_cells}, {gain_hist, gain_cells}, {race_hist, race_cells}});
+    return MCGP_OK;
 }
 
 int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
@@ -1493,28 +1409,17 @@ int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const
     int rc = build_params(cfg, drv, grid_probs, n, &kp);
     if (rc != MCGP_OK) return rc;
     if (podium_out && n < 3) return fail(MCGP_E_BAD_ARG, "podium_out needs n >= 3 (pass NULL to skip the podium counts)");
-    if (kp.wide && !mcgp::reg_kernel_serves(kp))
-        return fail(MCGP_E_BAD_ARG, "deviates = MCGP_DEVIATES_53 serves the problems the register kernel takes "
-                                    "(reg_kernel_serves: lap times clear of zero, overtake_delta >= 0)");
-    if (n_sims == 0) return MCGP_OK;
-    DeviceCtx *c = nullptr;
-    rc = find_ctx(device, &c);
+    rc = check_wide(kp);
     if (rc != MCGP_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        r = ensure_call_events(*c);
-        if (r != MCGP_OK) return r;
+    if (n_sims == 0) return MCGP_OK;
+    const size_t pair_cells = (size_t)n * n, podium_cells = podium_out ? (size_t)n * n * n : 0;
+    const size_t cells = 2 * pair_cells + podium_cells;
+    Counts counts;
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         // block shape: the widest block whose LDS fits the device's budget, with the podium table in LDS if any block
         // can hold it, else with the podium counted by global atomics.  MCGP_LDS_PER_BLOCK (a device that offers less)
         // is read per call here, so that a test reaches the global-atomic path in a process whose context exists.
-        size_t budget = c->lds_per_block;
-        if (const char *e = std::getenv("MCGP_LDS_PER_BLOCK")) {
-            const unsigned long long v = std::strtoull(e, nullptr, 10);
-            if (v >= 16384 && v < budget) budget = (size_t)v;
-        }
+        const size_t budget = lds_limit(c.lds_per_block);
         uint32_t mode = podium_out ? mcgp::kPodiumLds : mcgp::kPodiumNone, block = 0;
         auto widest = [&](bool podium_in_lds) -> uint32_t {
             for (uint32_t b = mcgp::kMatchMaxBlock; b >= 64; b /= 2)
@@ -1532,54 +1437,36 @@ int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const
         const uint32_t lds = mcgp::match_lds(n, block, mode == mcgp::kPodiumLds).bytes;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_matchups),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        // buffers: the orders staging of mcgp_run (one chunk), and hist | ahead | podium; both grow-only
-        const uint64_t chunk = mcgp::kMatchMaxSims;
-        const uint64_t cap = n_sims < chunk ? n_sims : chunk;
-        if (cap * n > c->d_orders_bytes) {
-            if (c->d_orders) (void)hipFree(c->d_orders);
-            c->d_orders = nullptr;
-            c->d_orders_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_orders, cap * n));
-            c->d_orders_bytes = cap * n;
-        }
-        const size_t pair_cells = (size_t)n * n, podium_cells = podium_out ? (size_t)n * n * n : 0;
-        const size_t cells = 2 * pair_cells + podium_cells;
-        if (cells * 8 > c->match_bytes) {
-            if (c->d_match) (void)hipFree(c->d_match);
-            c->d_match = nullptr;
-            c->match_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_match, cells * 8));
-            c->match_bytes = cells * 8;
-        }
-        unsigned long long *h_hist = c->d_match, *h_ahead = h_hist + pair_cells, *h_podium = h_ahead + pair_cells;
-        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
-        HIP_TRY(hipMemsetAsync(c->d_match, 0, cells * 8, nullptr));
+        // workspace: orders staging of one chunk | hist | ahead | podium
+        const uint64_t cap = std::min<uint64_t>(n_sims, mcgp::kMatchMaxSims);
+        Layout ws;
+        const size_t o_orders = ws.add(cap * n), o_cnt = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint8_t *d_orders = c.work.at<uint8_t>(o_orders);
+        unsigned long long *h_hist = c.work.at<unsigned long long>(o_cnt), *h_ahead = h_hist + pair_cells;
+        unsigned long long *h_podium = h_ahead + pair_cells;
+        HIP_TRY(hipMemsetAsync(h_hist, 0, cells * 8, nullptr));
         uint64_t per_cu = budget / lds;
         if (per_cu > 8) per_cu = 8;
         if (per_cu < 1) per_cu = 1;
-        const uint64_t grid_cap = (uint64_t)c->cu_count * per_cu;
+        const uint64_t grid_cap = (uint64_t)c.cu_count * per_cu;
         for (uint64_t done = 0; done < n_sims; done += cap) {
             const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
             // the chunk's race through mcgp_run's own launch path (the position histogram is counted there), its
             // orders into the staging buffer, then counted before the next chunk overwrites them
-            r = launch(*c, kp, m, sim_offset + done, seed, nullptr, h_hist, c->d_orders, nullptr);
+            r = launch(c, kp, m, sim_offset + done, seed, nullptr, h_hist, d_orders, nullptr);
             if (r != MCGP_OK) return r;
             const uint64_t tiles = (m + block - 1) / block;
             hipLaunchKernelGGL(mcgp::race_matchups, dim3((uint32_t)std::min(tiles, grid_cap)), dim3(block), lds, nullptr,
-                               c->d_orders, m, n, mode, h_ahead, podium_out ? h_podium : nullptr);
+                               d_orders, m, n, mode, h_ahead, podium_out ? h_podium : nullptr);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
-        c->last_timer = kBatchTimer;
-        // the caller's buffers are added into only once everything has run
-        std::vector<unsigned long long> back(cells);
-        HIP_TRY(hipMemcpy(back.data(), c->d_match, cells * 8, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < pair_cells; ++i) hist_out[i] += back[i];
-        for (size_t i = 0; i < pair_cells; ++i) ahead_out[i] += back[pair_cells + i];
-        for (size_t i = 0; i < podium_cells; ++i) podium_out[i] += back[2 * pair_cells + i];
-        return MCGP_OK;
-    };
-    return body();
+        return counts.download(h_hist, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to({{hist_out, pair_cells}, {ahead_out, pair_cells}, {podium_out, podium_cells}});
+    return MCGP_OK;
 }
 
 int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uint32_t n, uint32_t n_states,
@@ -1593,10 +1480,8 @@ int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uin
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
     int rc = build_params(cfg, drv, nullptr, n, &kp);
+    if (rc == MCGP_OK) rc = check_deviates_32(kp, "a resumed race runs");
     if (rc != MCGP_OK) return rc;
-    if (cfg->deviates != MCGP_DEVIATES_32)
-        return fail(MCGP_E_BAD_ARG, "deviates: a resumed race runs at MCGP_DEVIATES_32 only (the generic kernel has no "
-                                    "53-bit path)");
     std::vector<mcgp::ResumeState> st(n_states);
     for (uint32_t si = 0; si < n_states; ++si) {
         const std::string err = pack_race_state(states[si], si, n, cfg->total_laps, &st[si]);
@@ -1604,80 +1489,50 @@ int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uin
         st[si].sim_offset = sim_offsets ? sim_offsets[si] : 0;
     }
     if (n_sims == 0) return MCGP_OK;
-    DeviceCtx *c = nullptr;
-    rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        r = ensure_call_events(*c);
-        if (r != MCGP_OK) return r;
+    const size_t cells = (size_t)n_states * n * n;
+    Counts counts;
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         // simulations per launch: at most max_sims_per_launch() per state (u32 block counts), and with orders at most
-        // 2^22 over all states (the staging buffer of mcgp_run: 2^22 n bytes)
+        // kOrdersChunk over all states
         uint64_t chunk = max_sims_per_launch();
-        if (orders_out) chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, (1u << 22) / n_states));
+        if (orders_out) chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, kOrdersChunk / n_states));
         const uint64_t cap = n_sims < chunk ? n_sims : chunk;
-        if (orders_out && (size_t)n_states * cap * n > c->d_orders_bytes) {
-            if (c->d_orders) (void)hipFree(c->d_orders);
-            c->d_orders = nullptr;
-            c->d_orders_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_orders, (size_t)n_states * cap * n));
-            c->d_orders_bytes = (size_t)n_states * cap * n;
-        }
-        // device buffer: parameter block | states | histograms
-        const size_t o_st = (sizeof(mcgp::KParams) + 255) / 256 * 256;
-        const size_t o_hist = o_st + (sizeof(mcgp::ResumeState) * n_states + 255) / 256 * 256;
-        const size_t cells = (size_t)n_states * n * n;
-        const size_t bytes = o_hist + cells * 8;
-        if (bytes > c->resume_bytes) {
-            if (c->d_resume) (void)hipFree(c->d_resume);
-            c->d_resume = nullptr;
-            c->resume_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_resume, bytes));
-            c->resume_bytes = bytes;
-        }
-        const mcgp::KParams *d_kp = reinterpret_cast<const mcgp::KParams *>(c->d_resume);
-        const mcgp::ResumeState *d_st = reinterpret_cast<const mcgp::ResumeState *>(c->d_resume + o_st);
-        unsigned long long *d_h = reinterpret_cast<unsigned long long *>(c->d_resume + o_hist);
-        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
-        HIP_TRY(hipMemcpy(c->d_resume, &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_resume + o_st, st.data(), sizeof(mcgp::ResumeState) * n_states, hipMemcpyHostToDevice));
+        // workspace: orders staging | parameter block | states | histograms
+        Layout ws;
+        const size_t o_orders = ws.add(orders_out ? (size_t)n_states * cap * n : 0), o_kp = ws.add(sizeof(kp));
+        const size_t o_st = ws.add(sizeof(mcgp::ResumeState) * n_states), o_hist = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint8_t *d_orders = orders_out ? c.work.at<uint8_t>(o_orders) : nullptr;
+        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
+        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
+        unsigned long long *d_h = c.work.at<unsigned long long>(o_hist);
+        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_st), st.data(), sizeof(mcgp::ResumeState) * n_states, hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(d_h, 0, cells * 8, nullptr));
         const KernelFn geo_fn = reinterpret_cast<KernelFn>(&mcgp::race_resume_kernel);   // (for its register count)
         uint32_t grid = 0, block = 0, lds = 0;
         for (uint64_t done = 0; done < n_sims; done += cap) {
             const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
             // the generic kernel's block shape; the blocks the device holds at once are shared out over the states
-            launch_geometry(*c, n, false, geo_fn, m, &grid, &block, &lds);
-            if (lds > c->lds_per_block)
-                return fail(MCGP_E_HIP, "the resume kernel's block needs " + std::to_string(lds) + " bytes of LDS, the device "
-                                        "offers " + std::to_string(c->lds_per_block) + " per block");
+            r = generic_geometry(c, geo_fn, "resume", n, m, &grid, &block, &lds);
+            if (r != MCGP_OK) return r;
             const uint64_t n_batches = (m + block - 1) / block;
             const uint32_t gx = (grid + n_states - 1) / n_states;
             hipLaunchKernelGGL(mcgp::race_resume_kernel, dim3(gx, n_states), dim3(block), lds, nullptr, d_kp, d_st, m, done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), d_h, orders_out ? c->d_orders : nullptr,
-                               (uint32_t)n_batches);
+                               (uint32_t)seed, (uint32_t)(seed >> 32), d_h, d_orders, (uint32_t)n_batches);
             HIP_TRY(hipGetLastError());
             if (orders_out)
-                HIP_TRY(hipMemcpy2D(orders_out + (size_t)done * n, (size_t)n_sims * n, c->d_orders, (size_t)m * n,
+                HIP_TRY(hipMemcpy2D(orders_out + (size_t)done * n, (size_t)n_sims * n, d_orders, (size_t)m * n,
                                     (size_t)m * n, n_states, hipMemcpyDeviceToHost));
             grid = gx * n_states;
         }
-        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
-        c->last_timer = kBatchTimer;
-        c->last_grid = grid;
-        c->last_block = block;
-        c->last_lds = lds;
-        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "mcgp::race_resume_kernel");
-        // the caller's histogram is added into only once everything has run
-        std::vector<unsigned long long> back(cells);
-        HIP_TRY(hipMemcpy(back.data(), d_h, cells * 8, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < cells; ++i) hist_out[i] += back[i];
-        return MCGP_OK;
-    };
-    return body();
+        note_launch(c, grid, block, lds, "mcgp::race_resume_kernel");
+        return counts.download(d_h, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to({{hist_out, cells}});
+    return MCGP_OK;
 }
 
 int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
@@ -1690,78 +1545,52 @@ int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const do
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
     int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc == MCGP_OK) rc = check_deviates_32(kp, "a trace runs");
     if (rc != MCGP_OK) return rc;
-    if (kp.wide)
-        return fail(MCGP_E_BAD_ARG, "deviates: a trace runs at MCGP_DEVIATES_32 only (the generic kernel has no 53-bit path)");
     if (n_sims == 0) return MCGP_OK;
-    DeviceCtx *c = nullptr;
-    rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        r = ensure_call_events(*c);
-        if (r != MCGP_OK) return r;
-        const uint32_t L = (uint32_t)kp.total_laps;
-        const uint32_t rows = L * n;
-        // staging of one chunk: rows of `stride` bytes (a multiple of 256: whole, aligned words for the counting
-        // kernels), then the chunk's records
+    const uint32_t L = (uint32_t)kp.total_laps;
+    const uint32_t rows = L * n;
+    const size_t c_hist = (size_t)n * n, c_pos = (size_t)rows * (n + 1), c_laps = (size_t)n * (L + 1), c_fast = n,
+                 c_ev = 3 * (size_t)(L + 1);
+    const size_t cells = c_hist + c_pos + 2 * c_laps + c_fast + c_ev;
+    Counts counts;
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         const KernelFn geo_fn = reinterpret_cast<KernelFn>(&mcgp::race_trace_kernel);   // (for its register count)
-        uint64_t chunk = trace_chunk_sims(n, (int)L);
+        uint64_t chunk = stage_chunk_sims(kTraceStageBytes, (uint64_t)L * n);
         {
             // whole rounds of the device (every resident block one batch): a chunk of 5.5 rounds costs 6
             uint32_t g = 0, b = 0, l = 0;
-            launch_geometry(*c, n, false, geo_fn, chunk, &g, &b, &l);
+            launch_geometry(c, n, false, geo_fn, chunk, &g, &b, &l);
             const uint64_t round = (uint64_t)g * b;
             if (chunk >= round) chunk = chunk / round * round;
         }
         chunk = std::min<uint64_t>(chunk, n_sims);
+        // workspace: staging of one chunk in rows of `stride` bytes (a multiple of 256: whole, aligned words for the
+        // counting kernels) | the chunk's records | parameter block | hist [n][n] | lap_pos [L][n][n + 1] |
+        // laps_led [n][L + 1] | stops [n][L + 1] | fastest [n] | events [3][L + 1]
         const uint64_t stride = (chunk + 255) / 256 * 256;
-        const size_t o_rec = (size_t)rows * stride;
-        const size_t stage_bytes = o_rec + (size_t)stride * 8;
-        if (stage_bytes > c->trace_bytes) {
-            if (c->d_trace) (void)hipFree(c->d_trace);
-            c->d_trace = nullptr;
-            c->trace_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_trace, stage_bytes));
-            c->trace_bytes = stage_bytes;
-        }
-        // parameter block | hist [n][n] | lap_pos [L][n][n + 1] | laps_led [n][L + 1] | stops [n][L + 1] | fastest [n] |
-        // events [3][L + 1]
-        const size_t o_cnt = (sizeof(mcgp::KParams) + 255) / 256 * 256;
-        const size_t c_hist = (size_t)n * n, c_pos = (size_t)rows * (n + 1), c_laps = (size_t)n * (L + 1),
-                     c_fast = n, c_ev = 3 * (size_t)(L + 1);
-        const size_t cells = c_hist + c_pos + 2 * c_laps + c_fast + c_ev;
-        const size_t out_bytes = o_cnt + cells * 8;
-        if (out_bytes > c->trace_out_bytes) {
-            if (c->d_trace_out) (void)hipFree(c->d_trace_out);
-            c->d_trace_out = nullptr;
-            c->trace_out_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_trace_out, out_bytes));
-            c->trace_out_bytes = out_bytes;
-        }
-        const mcgp::KParams *d_kp = reinterpret_cast<const mcgp::KParams *>(c->d_trace_out);
-        unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(c->d_trace_out + o_cnt);
+        Layout ws;
+        const size_t o_stage = ws.add((size_t)rows * stride), o_rec = ws.add((size_t)stride * 8), o_kp = ws.add(sizeof(kp));
+        const size_t o_cnt = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
+        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
         unsigned long long *d_pos = d_hist + c_hist, *d_led = d_pos + c_pos, *d_stops = d_led + c_laps;
         unsigned long long *d_fast = d_stops + c_laps, *d_ev = d_fast + c_fast;
-        uint8_t *d_stage = c->d_trace;
-        uint64_t *d_rec = reinterpret_cast<uint64_t *>(c->d_trace + o_rec);
-        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
-        HIP_TRY(hipMemcpy(c->d_trace_out, &kp, sizeof(kp), hipMemcpyHostToDevice));
+        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
+        uint64_t *d_rec = c.work.at<uint64_t>(o_rec);
+        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
-        const uint64_t grid_cap = (uint64_t)c->cu_count * 8;
+        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
         const size_t laps_lds = 2 * (size_t)(L + 1) * 4, rec_lds = ((size_t)mcgp::kMaxCars + 3 * (size_t)(L + 1)) * 4;
         uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
         for (uint64_t done = 0; done < n_sims; done += chunk) {
             const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
             // the race: the generic kernel's block shape and LDS
-            launch_geometry(*c, n, false, geo_fn, m, &grid, &block, &lds);
+            r = generic_geometry(c, geo_fn, "trace", n, m, &grid, &block, &lds);
+            if (r != MCGP_OK) return r;
             if (done == 0) { grid0 = grid; block0 = block; }
-            if (lds > c->lds_per_block)
-                return fail(MCGP_E_HIP, "the trace kernel's block needs " + std::to_string(lds) + " bytes of LDS, the device "
-                                        "offers " + std::to_string(c->lds_per_block) + " per block");
             const uint64_t n_batches = (m + block - 1) / block;
             hipLaunchKernelGGL(mcgp::race_trace_kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, m, sim_offset + done,
                                (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, d_rec, (uint32_t)n_batches);
@@ -1785,34 +1614,13 @@ int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                 HIP_TRY(hipGetLastError());
             }
         }
-        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
-        c->last_timer = kBatchTimer;
-        c->last_grid = grid0;               // the launch shape of the first (fullest) chunk
-        c->last_block = block0;
-        c->last_lds = lds;
-        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "mcgp::race_trace_kernel");
-        // the caller's buffers are added into only once everything has run
-        std::vector<unsigned long long> back(cells);
-        HIP_TRY(hipMemcpy(back.data(), d_hist, cells * 8, hipMemcpyDeviceToHost));
-        const unsigned long long *b = back.data();
-        for (size_t i = 0; i < c_hist; ++i) hist_out[i] += b[i];
-        b += c_hist;
-        for (size_t i = 0; i < c_pos; ++i) lap_pos_out[i] += b[i];
-        b += c_pos;
-        if (laps_led_out)
-            for (size_t i = 0; i < c_laps; ++i) laps_led_out[i] += b[i];
-        b += c_laps;
-        if (stops_out)
-            for (size_t i = 0; i < c_laps; ++i) stops_out[i] += b[i];
-        b += c_laps;
-        if (fastest_out)
-            for (size_t i = 0; i < c_fast; ++i) fastest_out[i] += b[i];
-        b += c_fast;
-        if (events_out)
-            for (size_t i = 0; i < c_ev; ++i) events_out[i] += b[i];
-        return MCGP_OK;
-    };
-    return body();
+        note_launch(c, grid0, block0, lds, "mcgp::race_trace_kernel");      // the launch shape of the first (fullest) chunk
+        return counts.download(d_hist, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to({{hist_out, c_hist}, {lap_pos_out, c_pos}, {laps_led_out, c_laps}, {stops_out, c_laps},
+                   {fastest_out, c_fast}, {events_out, c_ev}});
+    return MCGP_OK;
 }
 
 int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
@@ -1837,10 +1645,8 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
     int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc == MCGP_OK) rc = check_deviates_32(kp, "strategies run");
     if (rc != MCGP_OK) return rc;
-    if (cfg->deviates != MCGP_DEVIATES_32)
-        return fail(MCGP_E_BAD_ARG, "deviates: strategies run at MCGP_DEVIATES_32 only (the generic kernel has no 53-bit "
-                                    "path)");
     const int L = cfg->total_laps;
     mcgp::ResumeState st;
     std::memset(&st, 0, sizeof(st));
@@ -1857,94 +1663,72 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
         if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
     }
     if (n_sims == 0) return MCGP_OK;
-    DeviceCtx *c = nullptr;
-    rc = find_ctx(device, &c);
-    if (rc != MCGP_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    auto body = [&]() -> int {
-        int r = ensure_ctx_locked(device, *c);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipSetDevice(device));
-        r = ensure_call_events(*c);
-        if (r != MCGP_OK) return r;
-        const uint32_t S = n_scenarios;
-        const uint64_t chunk = std::min<uint64_t>(strategy_chunk_sims(n, S), n_sims);
+    const uint32_t S = n_scenarios;
+    const size_t w = 2 * (size_t)n - 1;
+    const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w;
+    const size_t cells = c_hist + c_delta;
+    Counts counts;
+    std::vector<uint8_t> orders;            // collected on the host, handed over only once everything has run
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        const uint64_t chunk = std::min<uint64_t>(stage_chunk_sims(kStrategyStageBytes, (uint64_t)S * n), n_sims);
         const size_t stage_bytes = (size_t)S * chunk * n;
-        if (stage_bytes > c->strat_stage_bytes) {
-            if (c->d_strat_stage) (void)hipFree(c->d_strat_stage);
-            c->d_strat_stage = nullptr;
-            c->strat_stage_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_strat_stage, stage_bytes));
-            c->strat_stage_bytes = stage_bytes;
-        }
-        // parameter block | state | scenarios | stop laps | hist [S][n][n] | delta [S][n][2n - 1]
-        const size_t w = 2 * (size_t)n - 1;
-        const size_t o_st = (sizeof(mcgp::KParams) + 255) / 256 * 256;
-        const size_t o_sc = o_st + (sizeof(mcgp::ResumeState) + 255) / 256 * 256;
-        const size_t o_sl = o_sc + (sizeof(mcgp::StrategyScenario) * S + 255) / 256 * 256;
-        const size_t o_cnt = o_sl + (sizeof(mcgp::StopLap) * stop_laps.size() + 255) / 256 * 256;
-        const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w;
-        const size_t cells = c_hist + c_delta;
-        const size_t bytes = o_cnt + cells * 8;
-        if (bytes > c->strat_bytes) {
-            if (c->d_strat) (void)hipFree(c->d_strat);
-            c->d_strat = nullptr;
-            c->strat_bytes = 0;
-            HIP_TRY(hipMalloc(&c->d_strat, bytes));
-            c->strat_bytes = bytes;
-        }
-        const mcgp::KParams *d_kp = reinterpret_cast<const mcgp::KParams *>(c->d_strat);
-        const mcgp::ResumeState *d_st = reinterpret_cast<const mcgp::ResumeState *>(c->d_strat + o_st);
-        const mcgp::StrategyScenario *d_sc = reinterpret_cast<const mcgp::StrategyScenario *>(c->d_strat + o_sc);
-        const mcgp::StopLap *d_sl = reinterpret_cast<const mcgp::StopLap *>(c->d_strat + o_sl);
-        unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(c->d_strat + o_cnt);
+        // workspace: staged positions of a chunk | parameter block | state | scenarios | stop laps | hist [S][n][n] |
+        // delta [S][n][2n - 1]
+        Layout ws;
+        const size_t o_stage = ws.add(stage_bytes), o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st));
+        const size_t o_sc = ws.add(sizeof(mcgp::StrategyScenario) * S), o_sl = ws.add(sizeof(mcgp::StopLap) * stop_laps.size());
+        const size_t o_cnt = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
+        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
+        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
+        const mcgp::StrategyScenario *d_sc = c.work.at<const mcgp::StrategyScenario>(o_sc);
+        const mcgp::StopLap *d_sl = c.work.at<const mcgp::StopLap>(o_sl);
+        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
         unsigned long long *d_delta = d_hist + c_hist;
-        HIP_TRY(hipEventRecord(c->batch_start, nullptr));
-        HIP_TRY(hipMemcpy(c->d_strat, &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_strat + o_st, &st, sizeof(st), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_strat + o_sc, scen.data(), sizeof(mcgp::StrategyScenario) * S, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_strat + o_sl, stop_laps.data(), sizeof(mcgp::StopLap) * stop_laps.size(),
+        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_sc), scen.data(), sizeof(mcgp::StrategyScenario) * S, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_sl), stop_laps.data(), sizeof(mcgp::StopLap) * stop_laps.size(),
                           hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
-        // orders are collected on the host and handed over only once everything has run
-        std::vector<uint8_t> pos_back, orders;
+        std::vector<uint8_t> pos_back;
         if (orders_out) {
             pos_back.resize(stage_bytes);
             orders.resize((size_t)S * n_sims * n);
         }
         const KernelFn geo_fn = state ? reinterpret_cast<KernelFn>(&mcgp::race_strategy_kernel<true>)
                                       : reinterpret_cast<KernelFn>(&mcgp::race_strategy_kernel<false>);   // (register count)
-        const uint64_t grid_cap = (uint64_t)c->cu_count * 8;
+        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
         uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
         for (uint64_t done = 0; done < n_sims; done += chunk) {
             const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
             // the generic kernel's block shape; the blocks the device holds at once are shared out over the scenarios
-            launch_geometry(*c, n, false, geo_fn, m * S, &grid, &block, &lds);
-            if (lds > c->lds_per_block)
-                return fail(MCGP_E_HIP, "the strategy kernel's block needs " + std::to_string(lds) + " bytes of LDS, the "
-                                        "device offers " + std::to_string(c->lds_per_block) + " per block");
+            r = generic_geometry(c, geo_fn, "strategy", n, m * S, &grid, &block, &lds);
+            if (r != MCGP_OK) return r;
             const uint64_t n_batches = (m + block - 1) / block;
             const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + S - 1) / S);
             if (done == 0) { grid0 = gx * S; block0 = block; }
             if (state)
                 hipLaunchKernelGGL(mcgp::race_strategy_kernel<true>, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st,
                                    d_sc, d_sl, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist,
-                                   c->d_strat_stage, (uint32_t)n_batches);
+                                   d_stage, (uint32_t)n_batches);
             else
                 hipLaunchKernelGGL(mcgp::race_strategy_kernel<false>, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st,
                                    d_sc, d_sl, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist,
-                                   c->d_strat_stage, (uint32_t)n_batches);
+                                   d_stage, (uint32_t)n_batches);
             HIP_TRY(hipGetLastError());
             // its counts, before the next chunk overwrites the staging
             if (delta_out && S > 1) {
                 const uint64_t tiles = (m + mcgp::kStrategyCountBlock - 1) / mcgp::kStrategyCountBlock;
                 const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / (S - 1)));
                 hipLaunchKernelGGL(mcgp::strategy_count_deltas, dim3((uint32_t)gxc, S - 1), dim3(mcgp::kStrategyCountBlock),
-                                   0, nullptr, c->d_strat_stage, m, n, d_delta);
+                                   0, nullptr, d_stage, m, n, d_delta);
                 HIP_TRY(hipGetLastError());
             }
             if (orders_out) {
-                HIP_TRY(hipMemcpy(pos_back.data(), c->d_strat_stage, (size_t)S * m * n, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(pos_back.data(), d_stage, (size_t)S * m * n, hipMemcpyDeviceToHost));
                 for (uint32_t si = 0; si < S; ++si)
                     for (uint64_t i = 0; i < m; ++i) {
                         const uint8_t *pos = pos_back.data() + ((size_t)si * m + i) * n;
@@ -1953,30 +1737,22 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
                     }
             }
         }
-        HIP_TRY(hipEventRecord(c->batch_stop, nullptr));
-        c->last_timer = kBatchTimer;
-        c->last_grid = grid0;               // the launch shape of the first (fullest) chunk
-        c->last_block = block0;
-        c->last_lds = lds;
-        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "mcgp::race_strategy_kernel");
-        // the caller's buffers are added into only once everything has run
-        std::vector<unsigned long long> back(cells);
-        HIP_TRY(hipMemcpy(back.data(), d_hist, cells * 8, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < c_hist; ++i) hist_out[i] += back[i];
-        if (delta_out) {
-            // the centre bin (no change) of every (scenario, driver) is what the other bins leave of n_sims
-            unsigned long long *b = back.data() + c_hist;
-            for (size_t row = 0; row < (size_t)S * n; ++row) {
-                unsigned long long rest = 0;
-                for (size_t j = 0; j < w; ++j) rest += j == n - 1 ? 0ull : b[row * w + j];
-                b[row * w + n - 1] = n_sims - rest;
-            }
-            for (size_t i = 0; i < c_delta; ++i) delta_out[i] += b[i];
+        note_launch(c, grid0, block0, lds, "mcgp::race_strategy_kernel");   // the launch shape of the first (fullest) chunk
+        return counts.download(d_hist, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    if (delta_out) {
+        // the centre bin (no change) of every (scenario, driver) is what the other bins leave of n_sims
+        unsigned long long *b = counts.v.data() + c_hist;
+        for (size_t row = 0; row < (size_t)S * n; ++row) {
+            unsigned long long rest = 0;
+            for (size_t j = 0; j < w; ++j) rest += j == n - 1 ? 0ull : b[row * w + j];
+            b[row * w + n - 1] = n_sims - rest;
         }
-        if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
-        return MCGP_OK;
-    };
-    return body();
+    }
+    counts.add_to({{hist_out, c_hist}, {delta_out, c_delta}});
+    if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
+    return MCGP_OK;
 }
 
 int32_t mcgp_last_kernel_ms(int32_t device, float *ms_out)
@@ -1985,12 +1761,12 @@ int32_t mcgp_last_kernel_ms(int32_t device, float *ms_out)
     if (device < 0 || device >= kMaxDevices) return fail(MCGP_E_BAD_ARG, "device index out of range");
     DeviceCtx &c = g_ctx[device];
     std::lock_guard<std::mutex> lock(c.mu);
-    if (!c.ready || (c.last_timer < 0 && c.last_timer != kBatchTimer))
+    if (!c.ready || (c.last_timer < 0 && c.last_timer != kCallTimer))
         return fail(MCGP_E_BAD_ARG, "no kernel launched on this device yet");
     HIP_TRY(hipSetDevice(device));
-    if (c.last_timer == kBatchTimer) {                  // mcgp_run_batch: everything the call ran on the device
-        HIP_TRY(hipEventSynchronize(c.batch_stop));
-        HIP_TRY(hipEventElapsedTime(ms_out, c.batch_start, c.batch_stop));
+    if (c.last_timer == kCallTimer) {                   // a call of several kernels: everything it ran on the device
+        HIP_TRY(hipEventSynchronize(c.call_stop));
+        HIP_TRY(hipEventElapsedTime(ms_out, c.call_start, c.call_stop));
         return MCGP_OK;
     }
     HIP_TRY(hipEventSynchronize(c.timer[c.last_timer].stop));
@@ -2024,7 +1800,7 @@ const char *mcgp_last_kernel_name(int32_t device)
 int32_t mcgp_last_launch_info(int32_t device, uint32_t *grid_blocks, uint32_t *block_threads, uint32_t *lds_bytes)
 {
     if (device < 0 || device >= kMaxDevices || !g_ctx[device].ready ||
-        (g_ctx[device].last_timer < 0 && g_ctx[device].last_timer != kBatchTimer))
+        (g_ctx[device].last_timer < 0 && g_ctx[device].last_timer != kCallTimer))
         return fail(MCGP_E_BAD_ARG, "no kernel launched on this device yet");
     if (grid_blocks) *grid_blocks = g_ctx[device].last_grid;
     if (block_threads) *block_threads = g_ctx[device].last_block;
