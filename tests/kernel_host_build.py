@@ -80,3 +80,136 @@ def run(case, n_sims, seed, sim_offset=0, set_pop=None, fixed_grid=None, variant
 
 class NotServed(Exception):
     """The register kernel hands this problem to the generic kernel (csrc: reg_kernel_serves)."""
+
+
+# ---------------------------------------------------------------- the generic kernel family (tools/emu/emu_generic.cpp)
+GENERIC_LIB = os.path.join(EMU_DIR, 'libmcgp_emu_generic.so')
+GENERIC_HEADERS = ('race_kernel.hip.h', 'race_common.hip.h', 'race_start.inc.h', 'resume.hip.h', 'resume_start.inc.h',
+                   'trace.hip.h', 'strategy.hip.h', 'plan_pack.h', 'params_build.h', 'normal_table.h')
+TRACE_PIT, TRACE_POS_MASK = 0x80, 0x3F          # csrc/trace.hip.h: kTracePit, kTracePosMask
+
+
+def build_generic():
+    """tools/emu/libmcgp_emu_generic.so: race_kernel, race_resume_kernel, race_trace_kernel and race_strategy_kernel
+    compiled for the host (build()'s flags; rebuilt when a source it includes is newer)."""
+    srcs = [os.path.join(EMU_DIR, f) for f in ('emu_generic.cpp', 'hip/hip_runtime.h')]
+    srcs += [os.path.join(CSRC, f) for f in GENERIC_HEADERS] + [os.path.join(ROOT, 'include', 'mcgp.h')]
+    if not os.path.exists(GENERIC_LIB) or os.path.getmtime(GENERIC_LIB) < max(os.path.getmtime(s) for s in srcs):
+        tmp = f'{GENERIC_LIB[:-3]}.tmp{os.getpid()}.so'          # (renamed into place: a parallel run never maps half a file)
+        subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-fno-fast-math', '-fPIC', '-shared',
+                               '-I' + EMU_DIR, '-o', tmp, os.path.join(EMU_DIR, 'emu_generic.cpp')])
+        os.replace(tmp, GENERIC_LIB)
+    return GENERIC_LIB
+
+
+def generic_lib():
+    if 'generic' not in _libs:
+        L = C.CDLL(build_generic())
+        for f in ('emu_generic_run', 'emu_generic_resume', 'emu_generic_trace', 'emu_generic_strategy'):
+            getattr(L, f).restype = C.c_int
+        _libs['generic'] = L
+    return _libs['generic']
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _ok(rc, err):
+    assert rc == 0, (rc, err.value)
+
+
+def generic_problem(case):
+    """(the library's problem struct, the dense grid matrix) of a case dict."""
+    import oracle_py as O
+    import resume_ref as RR
+    return RR.problem(case), np.ascontiguousarray(O.Problem(case).grid_probs, np.float64)
+
+
+def generic_run(case, n_sims, seed, sim_offset=0, fixed_grid=None, prob=None):
+    """(hist, orders) of race_kernel on the host; it takes every problem (no reg_kernel_serves here)."""
+    p, g = prob or generic_problem(case)
+    n = p.n
+    hist, orders, err = np.zeros((n, n), np.uint64), np.zeros((n_sims, n), np.uint8), C.c_char_p()
+    fg = np.ascontiguousarray(fixed_grid, np.uint8) if fixed_grid is not None else None
+    _ok(generic_lib().emu_generic_run(C.byref(p.cfg), C.byref(p.drv), _vp(g), C.c_uint32(n), C.c_uint64(n_sims),
+                                      C.c_uint64(sim_offset), C.c_uint64(seed), _vp(hist), _vp(orders), _vp(fg),
+                                      C.byref(err)), err)
+    return hist.astype(np.int64), orders
+
+
+def generic_resume(case, states, n_sims, sim_offsets, seed, prob=None):
+    """race_resume_kernel on the host: states = [(mcgp_race_state arrays, lap, drs_disabled_until)] ->
+    (hist [S][n][n], orders [S][n_sims][n])."""
+    import resume_ref as RR
+    from monte_carlo_gp_amd import _native as N
+    p, _ = prob or generic_problem(case)
+    S, n = len(states), p.n
+    cs = (N.McgpRaceState * S)(*[RR.c_state(a, k, dd) for a, k, dd in states])
+    offs = (C.c_uint64 * S)(*[int(x) for x in sim_offsets])
+    hist, orders, err = np.zeros((S, n, n), np.uint64), np.zeros((S, n_sims, n), np.uint8), C.c_char_p()
+    _ok(generic_lib().emu_generic_resume(C.byref(p.cfg), C.byref(p.drv), C.c_uint32(n), C.c_uint32(S), cs,
+                                         C.c_uint64(n_sims), offs, C.c_uint64(seed), _vp(hist), _vp(orders),
+                                         C.byref(err)), err)
+    return hist.astype(np.int64), orders
+
+
+def trace_counts_from_staging(stage, rec, m, n, L):
+    """mcgp_run_trace's five count arrays from race_trace_kernel's raw output, by the layout documented at the top of
+    csrc/trace.hip.h: stage[(lap - 1) n + driver][simulation] = running position or n, | kTracePit; rec[simulation] =
+    fastest-lap driver (0xFFFF: none) | red flags << 16 | safety cars << 32 | VSCs << 48."""
+    b = stage[:, :m].reshape(L, n, m)
+    assert ((b & ~np.uint8(TRACE_PIT | TRACE_POS_MASK)) == 0).all()
+    pos = (b & TRACE_POS_MASK).astype(np.int64)
+    assert pos.max() <= n
+    out = dict(lap_pos=np.zeros((L, n, n + 1), np.int64), laps_led=np.zeros((n, L + 1), np.int64),
+               stops=np.zeros((n, L + 1), np.int64), fastest=np.zeros(n, np.int64), events=np.zeros((3, L + 1), np.int64))
+    for k in range(L):
+        for d in range(n):
+            out['lap_pos'][k, d] = np.bincount(pos[k, d], minlength=n + 1)
+    led, stops = (pos == 0).sum(axis=0), ((b & TRACE_PIT) != 0).sum(axis=0)          # [n][m]
+    for d in range(n):
+        out['laps_led'][d] = np.bincount(led[d], minlength=L + 1)
+        out['stops'][d] = np.bincount(stops[d], minlength=L + 1)
+    rec = rec[:m]
+    f = (rec & np.uint64(0xFFFF)).astype(np.int64)
+    assert ((f < n) | (f == 0xFFFF)).all()
+    out['fastest'] = np.bincount(f[f < n], minlength=n)
+    for kind in range(3):
+        c = ((rec >> np.uint64(16 * (kind + 1))) & np.uint64(0xFFFF)).astype(np.int64)
+        out['events'][kind] = np.bincount(c, minlength=L + 1)
+    return out
+
+
+def generic_trace(case, n_sims, seed, sim_offset=0, prob=None):
+    """race_trace_kernel on the host -> the dict trace_ref.trace_counts returns (hist and the five count arrays)."""
+    p, g = prob or generic_problem(case)
+    n, L = p.n, int(p.cfg.total_laps)
+    stride = (n_sims + 255) // 256 * 256
+    hist, err = np.zeros((n, n), np.uint64), C.c_char_p()
+    stage, rec = np.full((L * n, stride), 0x7F, np.uint8), np.zeros(stride, np.uint64)
+    _ok(generic_lib().emu_generic_trace(C.byref(p.cfg), C.byref(p.drv), _vp(g), C.c_uint32(n), C.c_uint64(n_sims),
+                                        C.c_uint64(sim_offset), C.c_uint64(seed), _vp(hist), _vp(stage),
+                                        C.c_uint64(stride), _vp(rec), C.byref(err)), err)
+    assert (stage[:, n_sims:] == 0x7F).all() and (rec[n_sims:] == 0).all()       # nothing written past the chunk
+    out = trace_counts_from_staging(stage, rec, n_sims, n, L)
+    out['hist'] = hist.astype(np.int64)
+    return out
+
+
+def generic_strategy(case, scenarios, n_sims, seed, sim_offset=0, state=None, prob=None):
+    """race_strategy_kernel<false> (state None) or <true> on the host: scenarios as strategy_ref.c_plans takes them ->
+    (hist [S][n][n], orders [S][n_sims][n])."""
+    import resume_ref as RR
+    import strategy_ref as SR
+    p, g = prob or generic_problem(case)
+    n, S = p.n, len(scenarios)
+    counts, plans = SR.c_plans(scenarios)
+    cs = RR.c_state(*state) if state is not None else None
+    hist, pos, err = np.zeros((S, n, n), np.uint64), np.full((S, n_sims, n), 0xFF, np.uint8), C.c_char_p()
+    _ok(generic_lib().emu_generic_strategy(C.byref(p.cfg), C.byref(p.drv), _vp(g) if state is None else None,
+                                           C.byref(cs) if cs is not None else None, C.c_uint32(n), C.c_uint32(S), counts,
+                                           plans, C.c_uint64(n_sims), C.c_uint64(sim_offset), C.c_uint64(seed),
+                                           _vp(hist), _vp(pos), C.byref(err)), err)
+    assert (np.sort(pos, axis=2) == np.arange(n, dtype=np.uint8)).all()            # every row a permutation
+    return hist.astype(np.int64), np.argsort(pos, axis=2).astype(np.uint8)

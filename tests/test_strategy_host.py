@@ -32,6 +32,28 @@ def test_restatement_without_plans_equals_the_oracle(name):
             assert np.array_equal(o[0], ref['orders'][i]), (name, k, i)
 
 
+def test_restatement_without_plans_equals_the_oracle_on_every_fuzz_configuration():
+    """The 84 configurations of tests/golden/fuzz_cases.json (the 12 corner cases among them), each with its own seed:
+    the restatement's orders are the oracle's, and from the oracle's traced state of simulation i after laps 1, L // 2
+    and L it ends in the oracle's order of i.  This licenses the restatement as the reference for plans there."""
+    with open(O.GOLDEN_DIR + '/fuzz_cases.json') as f:
+        cases = json.load(f)
+    m, done, resumed = 32, 0, 0
+    for name, case in cases.items():
+        seed, L = case['seed'], case['config']['total_laps']
+        ref = RR.traced_run(case, m, seed)
+        assert np.array_equal(SR.orders(case, m, seed, grids=ref['grids']), ref['orders']), name
+        done += 1
+        if L < 2:
+            continue
+        for k in sorted({1, L // 2, L}):
+            for i in range(0, m, 8):
+                st = (RR.state_arrays(ref, i, k), k, RR.drs_disabled_until(case, seed, i, k))
+                assert np.array_equal(SR.orders(case, 1, seed, i, state=st)[0], ref['orders'][i]), (name, k, i)
+                resumed += 1
+    assert done == 84 and resumed >= 83 * 2 * 4
+
+
 def test_restatement_plans_change_the_race():
     """A plan is not a no-op in the restatement: a driver who never stops in a dry race finishes differently."""
     case = O.load_case('S60')

@@ -146,6 +146,32 @@ def test_restatement_agrees_with_the_oracle_orders(name):
     assert t['stops'][:, 1:].sum() > 0                  # somebody pits in 60 / 34 laps
 
 
+def test_restatement_on_every_fuzz_configuration():
+    """The 84 configurations of tests/golden/fuzz_cases.json: the sum identities of the counts, the number of fastest laps
+    counted directly from the oracle's retirement trace, and hand values of the corner cases."""
+    import resume_ref as RR
+    with open(O.GOLDEN_DIR + '/fuzz_cases.json') as f:
+        cases = json.load(f)
+    m, counts = 32, {}
+    for name, case in cases.items():
+        L, seed = case['config']['total_laps'], case['seed']
+        t = counts[name] = TR.trace_counts(case, m, seed)
+        assert (t['lap_pos'].sum(axis=2) == m).all(), name
+        assert (t['laps_led'].sum(axis=1) == m).all() and (t['stops'].sum(axis=1) == m).all(), name
+        assert (t['events'].sum(axis=1) == m).all(), name
+        assert (t['laps_led'] @ np.arange(L + 1) == t['lap_pos'][:, :, 0].sum(axis=0)).all(), name
+        # a fastest lap exists where some car is running after some lap >= 2
+        dnf = RR.traced_run(case, m, seed)['trace']['dnf']
+        assert t['fastest'].sum() == (dnf[:, 1:, :] == 0).any(axis=(1, 2)).sum(), name
+    assert len(counts) == 84
+    one = counts['X_onelap']                            # no lap >= 2: no fastest lap, no event draw, no stop
+    assert (one['fastest'] == 0).all() and (one['events'][:, 0] == m).all() and (one['stops'][:, 0] == m).all()
+    for kind, name in ((TR.RED, 'X_always_red'), (TR.SC, 'X_always_sc'), (TR.VSC, 'X_always_vsc')):
+        L = cases[name]['config']['total_laps']
+        assert counts[name]['events'][kind, L - 1] == m, name       # laps 2 .. L
+    assert (counts['X_all_out_lap1']['fastest'] == 0).all()
+
+
 # ---------------------------------------------------------------- the CLI flag
 class _FakePredictor:
     """predict_weekend's result shape from hand-made counts (no device)."""

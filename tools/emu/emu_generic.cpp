@@ -1,0 +1,161 @@
+// emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
+// fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h
+// and strategy.hip.h with g++ through the stand-in <hip/hip_runtime.h> of this directory and calls the real
+// __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_strategy_kernel<false / true>.
+//
+// Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
+// __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
+// a kernel is an ordinary host function that walks the simulations one after another (the no-op __syncthreads() of the
+// stand-in header is correct for a block of one thread); blockIdx.y (states, scenarios) is looped over here.  The
+// state and plan arguments go through csrc/plan_pack.h, the text the C ABI itself uses.
+//
+// Not run here: trace_count_positions (__shfl_down), the matchups kernel (__ballot), and trace_count_laps,
+// trace_count_records and strategy_count_deltas, whose loops are written for their fixed block of 256 threads (a
+// one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and records
+// in numpy instead; the counting kernels are compared on the device.  tests/test_generic_host_build.py.
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../monte_carlo_gp_amd/csrc/params_build.h"
+#include "../../monte_carlo_gp_amd/csrc/trace.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/strategy.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/plan_pack.h"
+
+emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
+namespace mcgp {
+alignas(16) unsigned char smem[1 << 20];
+}
+
+namespace {
+
+std::string g_err;
+
+int fail(int rc, const std::string &msg, const char **err)
+{
+    g_err = msg;
+    *err = g_err.c_str();
+    return rc;
+}
+
+// The parameter block of a call, as the C ABI builds it.  The generic kernels are the 32-bit-deviate build.
+int params(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n, mcgp::KParams *kp,
+           const char **err)
+{
+    static const char *none = "";
+    *err = none;
+    const char *e = "";
+    const int rc = mcgp::build_params(cfg, drv, grid_probs, n, kp, &e);
+    if (rc != MCGP_OK) return fail(rc, e, err);
+    if (kp->wide) return fail(MCGP_E_BAD_ARG, "the generic kernels run MCGP_DEVIATES_32", err);
+    return MCGP_OK;
+}
+
+void one_thread_block(uint32_t grid_y)
+{
+    threadIdx = {0, 0, 0};
+    blockIdx = {0, 0, 0};
+    blockDim = {1, 1, 1};
+    gridDim = {1, grid_y, 1};
+}
+
+}  // namespace
+
+extern "C" {
+
+// race_kernel: hist [n][n] is accumulated into; orders [n_sims][n] or NULL; fixed_grid [n] or NULL.
+int emu_generic_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n, uint64_t n_sims,
+                    uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *orders,
+                    const uint8_t *fixed_grid, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    one_thread_block(1);
+    mcgp::race_kernel(&kp, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, orders, fixed_grid,
+                      (uint32_t)n_sims, nullptr, nullptr);
+    return MCGP_OK;
+}
+
+// race_resume_kernel: n_sims simulations of every state, ids sim_offsets[s] + [0, n_sims).  hist [states][n][n] is
+// accumulated into; orders [states][n_sims][n] or NULL.
+int emu_generic_resume(const mcgp_config *cfg, const mcgp_drivers *drv, uint32_t n, uint32_t n_states,
+                       const mcgp_race_state *states, uint64_t n_sims, const uint64_t *sim_offsets, uint64_t seed,
+                       unsigned long long *hist, uint8_t *orders, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, nullptr, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    std::vector<mcgp::ResumeState> st(n_states);
+    for (uint32_t si = 0; si < n_states; ++si) {
+        const std::string e = mcgp::pack_race_state(states[si], si, n, cfg->total_laps, &st[si]);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+        st[si].sim_offset = sim_offsets ? sim_offsets[si] : 0;
+    }
+    one_thread_block(n_states);
+    for (uint32_t si = 0; si < n_states; ++si) {
+        blockIdx.y = si;
+        mcgp::race_resume_kernel(&kp, st.data(), n_sims, 0, (uint32_t)seed, (uint32_t)(seed >> 32), hist, orders,
+                                 (uint32_t)n_sims);
+    }
+    blockIdx.y = 0;
+    return MCGP_OK;
+}
+
+// race_trace_kernel: hist [n][n] is accumulated into; stage [L n][stride] (stride >= n_sims) and rec [n_sims] are
+// written, in the layout documented at the top of csrc/trace.hip.h.
+int emu_generic_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n, uint64_t n_sims,
+                      uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *stage, uint64_t stride,
+                      uint64_t *rec, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if (stride < n_sims) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims", err);
+    one_thread_block(1);
+    mcgp::race_trace_kernel(&kp, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage, stride, rec,
+                            (uint32_t)n_sims);
+    return MCGP_OK;
+}
+
+// race_strategy_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every
+// scenario.  hist [S][n][n] is accumulated into; positions [S][n_sims][n] (each driver's classified position) is written.
+int emu_generic_strategy(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                         const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                         const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                         unsigned long long *hist, uint8_t *positions, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
+        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    const int L = cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+        st.sim_offset = sim_offset;
+    }
+    std::vector<mcgp::StrategyScenario> scen;
+    std::vector<mcgp::StopLap> stop_laps;
+    const std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, state ? st.lap + 1 : 2,
+                                               state != nullptr, &scen, &stop_laps);
+    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    one_thread_block(n_scenarios);
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        blockIdx.y = si;
+        if (state)
+            mcgp::race_strategy_kernel<true>(&kp, &st, scen.data(), stop_laps.data(), n_sims, sim_offset, (uint32_t)seed,
+                                             (uint32_t)(seed >> 32), hist, positions, (uint32_t)n_sims);
+        else
+            mcgp::race_strategy_kernel<false>(&kp, &st, scen.data(), stop_laps.data(), n_sims, sim_offset, (uint32_t)seed,
+                                              (uint32_t)(seed >> 32), hist, positions, (uint32_t)n_sims);
+    }
+    blockIdx.y = 0;
+    return MCGP_OK;
+}
+
+}  // extern "C"
