@@ -1,0 +1,92 @@
+// champ_pack.h -- host side of mcgp_run_championship: the key layouts of a call (championship.hip.h) and the tables the
+// two standings kernels read -- the teams' members, the initial keys, the key increment of every race and position.
+// Plain C++, no device code: mcgp_hip.hip includes it for the C ABI, and the host debugging build of the standings
+// kernels (tools/emu/emu_champ.cpp) includes the same text, so that what a test packs on the CPU is what the library
+// packs.  The argument checks (and G, awarded, n_cb, which they compute) stay with the C ABI.
+#pragma once
+#include "championship.hip.h"
+
+#include <algorithm>
+#include <cstddef>
+#include <string>
+#include <vector>
+
+namespace mcgp {
+
+// Bits needed to hold x (at least 1).
+inline uint32_t champ_bits(uint64_t x)
+{
+    uint32_t b = 1;
+    while (b < 64 && (x >> b) != 0) ++b;
+    return b;
+}
+
+struct ChampPack {
+    uint32_t words, team_cbits, team_words, gain_cols;
+    std::vector<uint8_t> members, n_members;        // [T][n] drivers of each team, [T]
+    std::vector<uint64_t> init_key, add;            // [words][n]; [R][n][words]
+    std::vector<int32_t> init_pts;                  // [n]
+};
+
+// The layouts and tables of a call whose arguments passed mcgp_run_championship's checks.  G: the most points one driver
+// can gain in these races; awarded: the points the races award in all; n_cb: the countback races.  "" if the team keys
+// fit, else the message.
+inline std::string pack_championship(uint32_t n_races, uint32_t n, const int32_t *points, const uint8_t *countback,
+                                     const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                                     uint32_t n_teams, uint64_t G, uint64_t awarded, uint32_t n_cb, ChampPack *out)
+{
+    // ---- key layouts.  Drivers: 5-bit counts and 16-bit points (the limits checked above).  Teams: a team's count in a
+    // position grows by at most one per countback race, its points by at most what its drivers can take; the fields
+    // are as wide as those bounds need (at the limits: 10-bit counts, 21-bit points, 6 words).
+    const uint32_t words = (mcgp::kChampPointsBits + mcgp::kChampCountBits * n + 63) / 64;
+    std::vector<uint64_t> team_pts(n_teams, 0), team_cnt((size_t)n_teams * n, 0);
+    std::vector<uint32_t> team_size(n_teams, 0);
+    std::vector<uint8_t> members((size_t)n_teams * n, 0), n_members(n_teams, 0);
+    for (uint32_t d = 0; d < n; ++d) {
+        const uint32_t t = (uint32_t)team[d];
+        members[(size_t)t * n + team_size[t]++] = (uint8_t)d;
+        team_pts[t] += init_points ? (uint64_t)init_points[d] : 0;
+        for (uint32_t p = 0; p < n; ++p) team_cnt[(size_t)t * n + p] += init_counts ? (uint64_t)init_counts[(size_t)d * n + p] : 0;
+    }
+    uint64_t max_tpts = 0, max_tcnt = 0;
+    for (uint32_t t = 0; t < n_teams; ++t) {
+        n_members[t] = (uint8_t)team_size[t];
+        const uint64_t gain = std::min<uint64_t>((uint64_t)team_size[t] * G, awarded);
+        max_tpts = std::max<uint64_t>(max_tpts, team_pts[t] + gain);
+        for (uint32_t p = 0; p < n; ++p) max_tcnt = std::max<uint64_t>(max_tcnt, team_cnt[(size_t)t * n + p] + n_cb);
+    }
+    const uint32_t team_cbits = champ_bits(max_tcnt);
+    const uint32_t team_words = (champ_bits(max_tpts) + team_cbits * n + 63) / 64;
+    if (team_words > (uint32_t)mcgp::kChampMaxTeamWords) return "team standings too wide for a key";
+    // initial keys [words][n] and the key increment of each race and position [R][n][words]
+    std::vector<uint64_t> init_key((size_t)words * n, 0), add((size_t)n_races * n * words, 0);
+    std::vector<int32_t> init_pts(n, 0);
+    for (uint32_t d = 0; d < n; ++d) {
+        init_pts[d] = init_points ? init_points[d] : 0;
+        for (uint32_t w = 0; w < words; ++w) {
+            uint64_t k = mcgp::champ_piece((uint64_t)init_pts[d], mcgp::kChampCountBits * (int)n, (int)w);
+            for (uint32_t p = 0; p < n && init_counts; ++p)
+                k |= mcgp::champ_piece((uint64_t)init_counts[(size_t)d * n + p], mcgp::kChampCountBits * (int)(n - 1 - p), (int)w);
+            init_key[(size_t)w * n + d] = k;
+        }
+    }
+    for (uint32_t r = 0; r < n_races; ++r)
+        for (uint32_t p = 0; p < n; ++p)
+            for (uint32_t w = 0; w < words; ++w)
+                add[((size_t)r * n + p) * words + w] =
+                    mcgp::champ_piece((uint64_t)points[(size_t)r * n + p], mcgp::kChampCountBits * (int)n, (int)w) |
+                    (countback[r] ? mcgp::champ_piece(1, mcgp::kChampCountBits * (int)(n - 1 - p), (int)w) : 0ull);
+    const uint32_t gain_cols = (uint32_t)G + 1;
+    out->words = words;
+    out->team_cbits = team_cbits;
+    out->team_words = team_words;
+    out->gain_cols = gain_cols;
+    out->members = std::move(members);
+    out->n_members = std::move(n_members);
+    out->init_key = std::move(init_key);
+    out->add = std::move(add);
+    out->init_pts = std::move(init_pts);
+    return "";
+}
+
+}  // namespace mcgp

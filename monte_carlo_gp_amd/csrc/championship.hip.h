@@ -137,7 +137,7 @@ champ_rank(const uint64_t *__restrict__ keys, uint64_t m, uint64_t stride, uint3
            uint32_t gain_in_lds, unsigned long long *__restrict__ champ_hist, unsigned long long *__restrict__ team_hist,
            unsigned long long *__restrict__ gain_hist)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
+    HIP_DYNAMIC_SHARED(__align__(16) unsigned char, smem)
     const ChampRankLds L = champ_rank_lds(n, words, n_teams, team_words, gain_cols, gain_in_lds != 0);
     uint64_t *dk = reinterpret_cast<uint64_t *>(smem);
     uint64_t *tk = reinterpret_cast<uint64_t *>(smem + L.o_tk);

@@ -15,6 +15,7 @@
 #include "trace.hip.h"
 #include "strategy.hip.h"
 #include "plan_pack.h"
+#include "champ_pack.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
 #include "frontend_exp.h"
@@ -1127,14 +1128,6 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
     return MCGP_OK;
 }
 
-// Bits needed to hold x (at least 1).
-static uint32_t champ_bits(uint64_t x)
-{
-    uint32_t b = 1;
-    while (b < 64 && (x >> b) != 0) ++b;
-    return b;
-}
-
 int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
                               const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
                               const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
@@ -1188,49 +1181,16 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
         if (rc == MCGP_OK) rc = check_wide(kps[r]);
         if (rc != MCGP_OK) return rc;
     }
-    // ---- key layouts.  Drivers: 5-bit counts and 16-bit points (the limits checked above).  Teams: a team's count in a
-    // position grows by at most one per countback race, its points by at most what its drivers can take; the fields
-    // are as wide as those bounds need (at the limits: 10-bit counts, 21-bit points, 6 words).
-    const uint32_t words = (mcgp::kChampPointsBits + mcgp::kChampCountBits * n + 63) / 64;
-    std::vector<uint64_t> team_pts(n_teams, 0), team_cnt((size_t)n_teams * n, 0);
-    std::vector<uint32_t> team_size(n_teams, 0);
-    std::vector<uint8_t> members((size_t)n_teams * n, 0), n_members(n_teams, 0);
-    for (uint32_t d = 0; d < n; ++d) {
-        const uint32_t t = (uint32_t)team[d];
-        members[(size_t)t * n + team_size[t]++] = (uint8_t)d;
-        team_pts[t] += init_points ? (uint64_t)init_points[d] : 0;
-        for (uint32_t p = 0; p < n; ++p) team_cnt[(size_t)t * n + p] += init_counts ? (uint64_t)init_counts[(size_t)d * n + p] : 0;
-    }
-    uint64_t max_tpts = 0, max_tcnt = 0;
-    for (uint32_t t = 0; t < n_teams; ++t) {
-        n_members[t] = (uint8_t)team_size[t];
-        const uint64_t gain = std::min<uint64_t>((uint64_t)team_size[t] * G, awarded);
-        max_tpts = std::max<uint64_t>(max_tpts, team_pts[t] + gain);
-        for (uint32_t p = 0; p < n; ++p) max_tcnt = std::max<uint64_t>(max_tcnt, team_cnt[(size_t)t * n + p] + n_cb);
-    }
-    const uint32_t team_cbits = champ_bits(max_tcnt);
-    const uint32_t team_words = (champ_bits(max_tpts) + team_cbits * n + 63) / 64;
-    if (team_words > (uint32_t)mcgp::kChampMaxTeamWords) return fail(MCGP_E_BAD_ARG, "team standings too wide for a key");
+    // ---- key layouts and the kernels' tables (champ_pack.h)
+    mcgp::ChampPack pk;
+    const std::string pack_err = mcgp::pack_championship(n_races, n, points, countback, init_points, init_counts, team,
+                                                         n_teams, G, awarded, n_cb, &pk);
+    if (!pack_err.empty()) return fail(MCGP_E_BAD_ARG, pack_err);
     if (n_sims == 0) return MCGP_OK;
-    // initial keys [words][n] and the key increment of each race and position [R][n][words]
-    std::vector<uint64_t> init_key((size_t)words * n, 0), add((size_t)n_races * n * words, 0);
-    std::vector<int32_t> init_pts(n, 0);
-    for (uint32_t d = 0; d < n; ++d) {
-        init_pts[d] = init_points ? init_points[d] : 0;
-        for (uint32_t w = 0; w < words; ++w) {
-            uint64_t k = mcgp::champ_piece((uint64_t)init_pts[d], mcgp::kChampCountBits * (int)n, (int)w);
-            for (uint32_t p = 0; p < n && init_counts; ++p)
-                k |= mcgp::champ_piece((uint64_t)init_counts[(size_t)d * n + p], mcgp::kChampCountBits * (int)(n - 1 - p), (int)w);
-            init_key[(size_t)w * n + d] = k;
-        }
-    }
-    for (uint32_t r = 0; r < n_races; ++r)
-        for (uint32_t p = 0; p < n; ++p)
-            for (uint32_t w = 0; w < words; ++w)
-                add[((size_t)r * n + p) * words + w] =
-                    mcgp::champ_piece((uint64_t)points[(size_t)r * n + p], mcgp::kChampCountBits * (int)n, (int)w) |
-                    (countback[r] ? mcgp::champ_piece(1, mcgp::kChampCountBits * (int)(n - 1 - p), (int)w) : 0ull);
-    const uint32_t gain_cols = (uint32_t)G + 1;
+    const uint32_t words = pk.words, team_cbits = pk.team_cbits, team_words = pk.team_words, gain_cols = pk.gain_cols;
+    const std::vector<uint8_t> &members = pk.members, &n_members = pk.n_members;
+    const std::vector<uint64_t> &init_key = pk.init_key, &add = pk.add;
+    const std::vector<int32_t> &init_pts = pk.init_pts;
     const size_t champ_cells = (size_t)n * n, team_cells = (size_t)n_teams * n_teams, gain_cells = (size_t)n * gain_cols;
     const size_t race_cells = race_hist ? (size_t)n_races * n * n : 0;
     const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells;

@@ -79,6 +79,19 @@ def rank_grouped(pts, cnt, block=1 << 15):
     return out
 
 
+def rank_lexsort(pts, cnt):
+    """Same positions as rank(), for many simulations at wide fields: one numpy lexsort of the unpacked fields (the
+    simulation, then fewer points, fewer P1s, ..., then the index)."""
+    sims, m = pts.shape
+    keys = [np.tile(np.arange(m), sims)]
+    keys += [-cnt[:, :, p].reshape(-1) for p in range(cnt.shape[2] - 1, -1, -1)]
+    keys += [-pts.reshape(-1), np.repeat(np.arange(sims), m)]
+    order = np.lexsort(keys)                                            # the last key is the primary one
+    pos = np.empty(sims * m, np.int64)
+    pos[order] = np.tile(np.arange(m), sims)
+    return pos.reshape(sims, m)
+
+
 def histogram(pos, m):
     """counts[entrant][position] of positions [sims][m]."""
     h = np.zeros((m, m), np.int64)
@@ -100,7 +113,7 @@ def championship(orders_list, points_list, countback, team, n_teams, init_points
     n = orders_list[0].shape[1]
     pts, cnt = standings(orders_list, points_list, countback, init_points, init_counts)
     tp, tc = team_standings(pts, cnt, team, n_teams)
-    rk = rank_grouped if grouped else rank
+    rk = {False: rank, True: rank_grouped, 'lexsort': rank_lexsort}[grouped]
     champ = histogram(rk(pts, cnt), n)
     teams = histogram(rk(tp, tc), n_teams)
     G = sum(max([int(x) for x in t[:n]] + [0]) for t in points_list)
@@ -110,3 +123,18 @@ def championship(orders_list, points_list, countback, team, n_teams, init_points
         gain_hist[d] = np.bincount(gain[:, d], minlength=G + 1)[:G + 1]
     races = np.array([race_histogram(o) for o in orders_list])
     return champ, teams, gain_hist, races
+
+
+def decision_depth(pts, cnt, pos=None):
+    """How deep the ranking had to look: depth[k] = the number of pairs of entrants adjacent in the final ranking (over
+    all simulations) that are first told apart at field k, where field 0 is the points, field 1 + p the count of
+    position p + 1, and field 1 + (number of count fields) the index (every field equal).  Length 2 + cnt.shape[2]."""
+    sims, m = pts.shape
+    if pos is None:
+        pos = rank(pts, cnt)
+    fields = np.concatenate([pts[:, :, None], cnt], axis=2)              # [s][entrant][field]
+    order = np.argsort(pos, axis=1)                                     # [s][rank] = entrant
+    ranked = np.take_along_axis(fields, order[:, :, None], axis=1)
+    diff = ranked[:, :-1, :] != ranked[:, 1:, :]                        # [s][pair][field]
+    first = np.where(diff.any(axis=2), diff.argmax(axis=2), fields.shape[2])
+    return np.bincount(first.reshape(-1), minlength=fields.shape[2] + 1)

@@ -213,3 +213,67 @@ def generic_strategy(case, scenarios, n_sims, seed, sim_offset=0, state=None, pr
                                            _vp(hist), _vp(pos), C.byref(err)), err)
     assert (np.sort(pos, axis=2) == np.arange(n, dtype=np.uint8)).all()            # every row a permutation
     return hist.astype(np.int64), np.argsort(pos, axis=2).astype(np.uint8)
+
+
+# ---------------------------------------------------------------- the standings kernels (tools/emu/emu_champ.cpp)
+CHAMP_HEADERS = ('championship.hip.h', 'champ_pack.h', 'race_common.hip.h')
+CHAMP_VARIANTS = {
+    None: [],
+    # the host's undefined-behaviour sanitizer over the kernels' shifts and indices (reports go to stderr)
+    'ubsan': ['-fsanitize=undefined'],
+}
+
+
+def build_champ(variant=None):
+    """tools/emu/libmcgp_emu_champ.so: champ_accumulate and champ_rank compiled for the host with blocks of 256 real
+    threads (rebuilt when a source it includes is newer)."""
+    out = os.path.join(EMU_DIR, 'libmcgp_emu_champ.so' if variant is None else f'libmcgp_emu_champ_{variant}.so')
+    srcs = [os.path.join(EMU_DIR, f) for f in ('emu_champ.cpp', 'hip/hip_runtime.h')]
+    srcs += [os.path.join(CSRC, f) for f in CHAMP_HEADERS] + [os.path.join(ROOT, 'include', 'mcgp.h')]
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in srcs):
+        tmp = f'{out[:-3]}.tmp{os.getpid()}.so'
+        subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fPIC', '-shared', '-pthread', '-I' + EMU_DIR]
+                              + CHAMP_VARIANTS[variant] + ['-o', tmp, os.path.join(EMU_DIR, 'emu_champ.cpp')])
+        os.replace(tmp, out)
+    return out
+
+
+def champ_lib(variant=None):
+    if ('champ', variant) not in _libs:
+        L = C.CDLL(build_champ(variant))
+        L.emu_champ_run.restype = C.c_int
+        _libs['champ', variant] = L
+    return _libs['champ', variant]
+
+
+def champ_run(orders_list, points_list, countback, team, n_teams, init_points=None, init_counts=None, cap=None,
+              gain_in_lds=-1, lds_per_block=160 * 1024, acc_grid=1 << 20, rank_grid=1 << 20, want_keys=False,
+              variant=None):
+    """champ_accumulate (once per race) and champ_rank on the host over the orders [sims][n] of each race ->
+    dict(champ, team, gain: the histograms; info: words, team_cbits, team_words, gain_cols, gain_in_lds, lds_bytes;
+    keys: [words][n][cap] u64 of the last chunk when want_keys).  Points tables are padded with zeros to n."""
+    R = len(orders_list)
+    sims, n = orders_list[0].shape
+    orders = np.ascontiguousarray(np.stack([np.asarray(o, np.uint8) for o in orders_list]))
+    pts = np.zeros((R, n), np.int32)
+    for r, t in enumerate(points_list):
+        t = [int(x) for x in t][:n]
+        pts[r, :len(t)] = t
+    G = int(pts.max(axis=1).sum())
+    cb = np.ascontiguousarray(countback, np.uint8)
+    tm = np.ascontiguousarray(team, np.int32)
+    ip = None if init_points is None else np.ascontiguousarray(init_points, np.int32)
+    ic = None if init_counts is None else np.ascontiguousarray(init_counts, np.int32)
+    cap = sims if cap is None else int(cap)
+    champ, teams = np.zeros((n, n), np.uint64), np.zeros((n_teams, n_teams), np.uint64)
+    gain, info, err = np.zeros((n, G + 1), np.uint64), np.zeros(6, np.uint32), C.c_char_p()
+    words = (16 + 5 * n + 63) // 64
+    keys = np.zeros((words, n, max(min(cap, sims), 1)), np.uint64) if want_keys else None
+    rc = champ_lib(variant).emu_champ_run(
+        C.c_uint32(R), C.c_uint32(n), C.c_uint64(sims), C.c_uint64(cap), _vp(orders), _vp(pts), _vp(cb), _vp(ip), _vp(ic),
+        _vp(tm), C.c_uint32(n_teams), C.c_int32(gain_in_lds), C.c_uint32(lds_per_block), C.c_uint32(acc_grid),
+        C.c_uint32(rank_grid), _vp(champ), _vp(teams), _vp(gain), _vp(keys), _vp(info), C.byref(err))
+    _ok(rc, err)
+    names = ('words', 'team_cbits', 'team_words', 'gain_cols', 'gain_in_lds', 'lds_bytes')
+    return dict(champ=champ.astype(np.int64), team=teams.astype(np.int64), gain=gain.astype(np.int64),
+                info={k: int(v) for k, v in zip(names, info)}, keys=keys)

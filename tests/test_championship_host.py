@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import championship_cases as CC
 import championship_ref as CR
 import oracle_py as O
 from monte_carlo_gp_amd import RaceConfig, cli, run_championship
@@ -234,3 +235,74 @@ def test_cli_races_are_the_backtest_races_with_their_seeds():
 def test_cli_championship_parses_and_checks_the_round(capsys):
     with pytest.raises(ValueError, match='from-round'):
         cli.main(['championship', '--season', '2024', '--from-round', '0', '--simulations', '10'])
+
+
+# ---------------------------------------------------------------- the seasons of championship_cases reach their edges
+# (the half of tests/test_gpu_championship_limits.py that needs no device: the CPU oracle and championship_ref alone)
+def test_decision_depth_names_the_first_field_that_differs():
+    # three entrants: 0 and 1 differ in points; 1 and 2 tie on points and P1s and differ in P2s
+    pts = np.array([[9, 5, 5]])
+    cnt = np.array([[[0, 0, 1], [1, 1, 0], [1, 0, 0]]])
+    assert CR.decision_depth(pts, cnt).tolist() == [1, 0, 1, 0, 0]
+    # a full tie is decided by the index: the last cell
+    assert CR.decision_depth(np.array([[4, 4]]), np.zeros((1, 2, 2), np.int64)).tolist() == [0, 0, 0, 1]
+
+
+def test_lexsort_ranking_equals_the_per_simulation_sort():
+    rng = np.random.default_rng(4)
+    for n, races in ((1, 3), (5, 4), (12, 2), (23, 3)):
+        orders = [np.array([rng.permutation(n) for _ in range(400)], np.uint8) for _ in range(races)]
+        pts, cnt = CR.standings(orders, [CC.SHORT] * races, [1] * races, rng.integers(0, 3, n), rng.integers(0, 2, (n, n)))
+        assert np.array_equal(CR.rank(pts, cnt), CR.rank_lexsort(pts, cnt))
+
+
+@pytest.mark.parametrize('n', list(range(1, 33)))
+def test_tie_rich_seasons_reach_the_word_boundaries(n):
+    season = CC.tie_rich(n)
+    pts, cnt, _, _ = CC.reference_standings(season, CC.oracle_orders(season))
+    CC.assert_tie_rich_edges(n, pts, cnt, CC.standings_arrays(season)[0])
+
+
+def test_the_layout_restated():
+    assert [n for n in range(1, 33) if CC.points_low_bits(n)] == list(CC.POINTS_STRADDLE)
+    assert [CC.points_low_bits(n) for n in CC.POINTS_STRADDLE] == [14, 9, 4, 13, 8, 3]
+    for n in CC.POINTS_STRADDLE:            # 3 short of a full lower piece
+        p, low = CC.tie_rich_points(n), CC.points_low_bits(n)
+        assert (p + 2) >> low == p >> low and (p + 3) >> low == (p >> low) + 1
+
+
+@pytest.mark.parametrize('n', [20, 32])
+def test_procession_seasons_reach_31_wins_and_65535_points(n):
+    season = CC.procession(n)
+    pts, cnt, _, _ = CC.reference_standings(season, CC.oracle_orders(season))
+    CC.assert_procession_edges(pts, cnt)
+
+
+def test_long_calendar_season():
+    season = CC.long_calendar()
+    assert len(season['plan']) == 64 and sum(p[4] for p in season['plan']) == 31
+    pts, cnt, _, _ = CC.reference_standings(season, CC.oracle_orders(season))
+    assert cnt.sum(axis=2).max() == 31 and len(np.unique(pts)) > 100
+
+
+@pytest.mark.parametrize('name', list(CC.team_seasons()))
+def test_team_seasons_reach_their_layouts(name):
+    season, words = CC.team_seasons()[name]
+    _, _, tp, tc = CC.reference_standings(season, CC.oracle_orders(season))
+    CC.assert_team_edges(name, season, tp, tc)
+    assert sorted(set(CC.team_seasons_words().values())) == [1, 3, 4, 5, 6]
+
+
+@pytest.mark.parametrize('name', list(CC.gain_seasons()))
+def test_gain_seasons_take_their_path_and_reach_both_ends(name):
+    season, path = CC.gain_seasons()[name]
+    assert CC.gain_path(season, 64 * 1024) == path and CC.gain_path(season, 160 * 1024) == path
+    pts, _, _, _ = CC.reference_standings(season, CC.oracle_orders(season))
+    gain = pts - CC.standings_arrays(season)[0][None, :]
+    G = sum(max(p[3]) for p in season['plan'])
+    assert (gain == 0).sum() >= 50 and (gain == G).sum() >= 50
+
+
+def test_tail_seasons_leave_one_two_and_three_bytes():
+    for n in (9, 23, 31):
+        assert sorted(CC.tail_bytes(n, k) for k in (501, 502, 503)) == [1, 2, 3]

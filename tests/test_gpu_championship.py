@@ -43,11 +43,12 @@ def _standings_arrays(standings, drivers):
     return p, c
 
 
-def _check(res, cases, plan, n_sims, sim_offset, standings, grouped=False):
-    """plan: [(case name or case dict, seed, deviates, points table, countback)]."""
+def _check(res, cases, plan, n_sims, sim_offset, standings, grouped=False, orders=None):
+    """plan: [(case name or case dict, seed, deviates, points table, countback)].  orders: the oracle's orders of the
+    plan's races, when the caller has them already."""
     drivers = res.drivers
-    orders = []
-    for case, seed, dev, _, _ in plan:
+    orders = [] if orders is None else orders
+    for case, seed, dev, _, _ in plan[len(orders):]:
         case = cases[case] if isinstance(case, str) else case
         assert list(case['grid_probs']) == drivers
         rng = O.RNG_PHILOX53 if dev == 53 else O.RNG_PHILOX

@@ -109,6 +109,18 @@ def test_field_sizes_equal_the_oracle(require_gpu, n):
     _identities(res)
 
 
+@pytest.mark.parametrize('n_sims', [501, 502, 503])
+def test_byte_tail_of_the_staged_orders(require_gpu, n_sims):
+    """23 cars and a last tile of 245, 246 and 247 simulations: its orders end 3, 2 and 1 bytes past a whole word, the
+    bytes race_matchups copies one by one (the same for its blocks of 256, 128 and 64)."""
+    n = 23
+    assert all((n_sims % b) * n % 4 == 504 - n_sims for b in (256, 128, 64))
+    case = _field(n)
+    res = _run(case, n_sims, 90 + n_sims, sim_offset=5)
+    _equals_oracle(res, case, n_sims, 90 + n_sims, 5)
+    _identities(res)
+
+
 def test_generic_kernel_problem(require_gpu):
     """A negative overtake_delta is served by the generic race kernel only; the counting is the same."""
     case = copy.deepcopy(O.load_case('S60'))

@@ -3,6 +3,12 @@
 // seconds before it is sent to a GPU.  Execution model: the threads of ONE block run one after another, phase by
 // phase (tools/emu/emu_kernel.cpp); __syncthreads() is a no-op and LDS is a plain array.  Nothing under monte_carlo_gp_amd/
 // includes or links this: the product has no CPU path.
+//
+// EMU_BLOCK_THREADS (tools/emu/emu_champ.cpp only): a block is blockDim.x HOST THREADS that run at the same time.
+// threadIdx and blockIdx are thread-local, __syncthreads() is a real barrier over the block (emu_block_barrier, defined
+// by the driver), atomicAdd is atomic, a __shared__ array is one static object that all threads of the block see, and the
+// dynamic LDS is the buffer emu_dynamic_lds points to.
+// Without the macro everything below is as it always was.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -13,7 +19,14 @@
 #define __host__
 #define __forceinline__ inline __attribute__((always_inline))
 #define __launch_bounds__(...)
+#ifdef EMU_BLOCK_THREADS
+#define __shared__ static
+#define HIP_DYNAMIC_SHARED(type, var) type *var = reinterpret_cast<type *>(emu_dynamic_lds);
+extern void *emu_dynamic_lds;            // the running launch's dynamic LDS: a buffer of exactly the launch's bytes
+#else
 #define __shared__
+#define HIP_DYNAMIC_SHARED(type, var) extern __shared__ type var[];
+#endif
 #define __align__(x)
 #ifndef __restrict__
 #define __restrict__ __restrict
@@ -22,13 +35,23 @@
 struct emu_dim3 {
     unsigned x, y, z;
 };
+#ifdef EMU_BLOCK_THREADS
+extern thread_local emu_dim3 threadIdx, blockIdx;
+extern emu_dim3 blockDim, gridDim;
+void emu_block_barrier();
+#else
 extern emu_dim3 threadIdx, blockIdx, blockDim, gridDim;
+#endif
 
 struct float4 {
     float x, y, z, w;
 };
 
+#ifdef EMU_BLOCK_THREADS
+inline void __syncthreads() { emu_block_barrier(); }
+#else
 inline void __syncthreads() {}
+#endif
 inline int __popc(unsigned v) { return __builtin_popcount(v); }
 inline int __ffs(int v) { return __builtin_ffs(v); }
 inline int __clz(int v) { return v == 0 ? 32 : __builtin_clz((unsigned)v); }
@@ -71,9 +94,13 @@ inline float __uint_as_float(uint32_t u)
 template <typename T>
 inline T atomicAdd(T *p, T v)
 {
+#ifdef EMU_BLOCK_THREADS
+    return __atomic_fetch_add(p, v, __ATOMIC_RELAXED);
+#else
     const T old = *p;
     *p = old + v;
     return old;
+#endif
 }
 // Cross-lane operations have no meaning in a block of one thread.  They are declared so that headers whose GPU-only
 // kernels use them (trace_count_positions: __shfl_down; the matchups kernel: __ballot) compile here; the host builds
