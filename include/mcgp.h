@@ -33,7 +33,7 @@ extern "C" {
 /* 4: mcgp_run_matchups */
 /* 5: mcgp_race_state, mcgp_run_from_state */
 /* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
- * function changed, so the version stays; a caller tests for the symbol) */
+ * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -332,6 +332,48 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
                             const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
                             const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
                             int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint8_t *orders_out);
+
+/* Race time gaps: the model's binary64 cumulative times, counted on the device as histograms over caller-given edges
+ * (seconds): every car's gap to the leader by lap, the lead (winning margin on the last lap) and the gap between named
+ * pairs of drivers, from the grid or from a mid-race state.  Everything is read from the race model's state after the
+ * end of lap k (its update_positions; where mcgp_run_trace reads), L = cfg->total_laps, B = n_edges + 1 bins.
+ *   - simulations: from the grid (state NULL, grid_probs given) ids sim_offset .. sim_offset + n_sims - 1 with the draws
+ *     of mcgp_run's simulation i; laps 1 .. L are recorded.  From a state (grid_probs NULL, one mcgp_race_state) the
+ *     draws and rules of mcgp_run_from_state with sim_offsets[0] = sim_offset; laps state->lap + 1 .. L are recorded
+ *     and the rows of earlier laps are left as the caller passed them.  hist_out equals mcgp_run's /
+ *     mcgp_run_from_state's for the same ids;
+ *   - bins: edges finite, edges[0] > 0, strictly increasing; bin(x) = the number of edges <= x (edges[b - 1] <= x <
+ *     edges[b]: a value equal to an edge goes up).  Every binned value is one binary64 subtraction of the cumulative
+ *     times of two running cars, the later minus the earlier in the running order, so it is >= 0; no other arithmetic
+ *     is applied, so the counts are a pure function of the model's times;
+ *   - running order: the cars not retired by (cumulative time, grid slot), as mcgp_run_trace defines it.
+ *   hist_out     [n][n]                [driver][position - 1]
+ *   lap_gap_out  [L][n][B + 1]         [lap - 1][driver][bin(cum_driver - cum_leader)], column B = retired (no gap).
+ *                                      The leader counts in bin 0; each recorded row sums to n_sims; row L - 1 is the
+ *                                      finishing-gap distribution of the classified runners
+ *   lead_out     [L][B + 1]            [lap - 1][bin(cum_second - cum_leader)], column B = fewer than two cars running;
+ *                                      row L - 1 is the winning margin; or NULL
+ *   pair_out     [L][n_pairs][2B + 1]  for pair p = (a, b) = pairs[2p], pairs[2p + 1]: column bin(cum_b - cum_a) if both
+ *                                      run and a is ahead of b in the running order, B + bin(cum_a - cum_b) if b is
+ *                                      ahead, 2B if either has retired; NULL exactly when n_pairs == 0
+ * All are ACCUMULATED into (caller zeroes), and only after every launch has succeeded: on an error they are left as they
+ * were.  Every argument is checked before any device lookup (MCGP_E_BAD_ARG, the message names the field): what mcgp_run
+ * / mcgp_run_from_state check, grid_probs and state both or neither given, n_edges outside [1, 63], an edge that is
+ * non-finite, <= 0 or not above its predecessor, n_pairs > 64, a pair index >= n, a pair of one driver, pairs / pair_out
+ * NULL with n_pairs > 0 or pair_out given with n_pairs == 0, deviates other than MCGP_DEVIATES_32 (the generic kernel
+ * runs the call and has no 53-bit path).  n_sims == 0 succeeds without a device.  The device work goes chunk by chunk
+ * through a staging buffer of 512 MiB / (recorded laps x (n + 1 + n_pairs)) simulations (one byte per recorded lap, row
+ * and simulation; rounded down to a multiple of 256, then to whole rounds of the device's resident blocks, grid_blocks x
+ * block_threads of mcgp_last_launch_info, which after this call describes its first chunk's race launch) that a
+ * counting kernel reads; device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or
+ * devices sums to the same counts.  mcgp_last_kernel_ms afterwards = the device time of everything the call ran;
+ * mcgp_last_kernel_name = "mcgp::race_gaps_kernel". */
+#define MCGP_MAX_GAP_EDGES 63
+#define MCGP_MAX_GAP_PAIRS 64
+int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                      const mcgp_race_state *state, uint32_t n, uint32_t n_edges, const double *edges, uint32_t n_pairs,
+                      const uint8_t *pairs, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device,
+                      uint64_t *hist_out, uint64_t *lap_gap_out, uint64_t *lead_out, uint64_t *pair_out);
 
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver

@@ -58,6 +58,8 @@ class McgpRaceState(C.Structure):
 
 MAX_PLAN_STOPS = 8
 MAX_SCENARIOS = 64
+MAX_GAP_EDGES = 63          # include/mcgp.h: MCGP_MAX_GAP_EDGES, MCGP_MAX_GAP_PAIRS
+MAX_GAP_PAIRS = 64
 
 
 class McgpPitPlan(C.Structure):
@@ -237,7 +239,14 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_simulate_race', 'mcgp_grid_probs', 'mcgp_run_from_ratings', 'mcgp_last_kernel_ms',
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
-           'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies')
+           'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps')
+
+
+# mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
+# lap_gap_out, lead_out, pair_out)
+GAPS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
+                 C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint64,
+                 C.c_uint64, C.c_int32] + [C.POINTER(C.c_uint64)] * 4
 
 
 def lib():
@@ -321,6 +330,9 @@ def lib():
                                               C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
                                               C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, u64p, u64p,
                                               C.POINTER(C.c_uint8)]
+        if 'mcgp_run_gaps' not in missing:
+            L.mcgp_run_gaps.restype = C.c_int32
+            L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES
         L.mcgp_last_kernel_ms.restype = C.c_int32
         L.mcgp_last_kernel_ms.argtypes = [C.c_int32, C.POINTER(C.c_float)]
         if 'mcgp_stream_kernel_ms' not in missing:

@@ -15,7 +15,9 @@ simulator (the reference parses --simulations and drops it, main.py:14-15 vs pre
 --fixture a synthetic weekend is used (SURVEY.md 8d canonical inputs) and labelled as such.  predict --matchups also
 prints the teammate head-to-heads and the most likely podiums (counted on the device) and adds them to --json;
 predict --trace prints who leads after lap 1 and at the flag, laps led, fastest lap, pit stops and safety-car odds
-(counted lap by lap on the device) and adds them to --json.
+(counted lap by lap on the device) and adds them to --json.  predict --gaps [--gap-edges 1,2,5] [--gap-pair VER:NOR]...
+(also on in-race) prints the winning margin, each driver's odds of finishing within about 1 s / 5 s / 20 s of the winner
+(the nearest edges present) and the named pairs' gaps (time gaps counted on the device) and adds a 'gaps' block to --json.
 in-race runs the rest of the race from one or more mid-race state files (RaceState JSON, simulation.py); with several
 --state files every state sees the same random futures and the columns compare the scenarios.
 strategy compares pit strategies for one driver: `model` (the race model's own stops) first, then each --plan
@@ -72,6 +74,8 @@ def cmd_predict(args) -> int:
           f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}\n{'=' * 60}\n")
     t0 = time.perf_counter()
     extra = {'trace': True} if args.trace else {}
+    if args.gaps:
+        extra['gaps'] = gaps_argument(args)
     res = F1Predictor(device=args.device).predict_weekend(
         args.season, args.race, fixture, prediction_point=args.prediction_point,
         n_simulations=args.simulations, seed=args.seed, matchups=args.matchups, **extra)
@@ -93,6 +97,8 @@ def cmd_predict(args) -> int:
             print(f"{i:2}. {' - '.join(f'{d:4}' for d in row['podium'])} {row['probability']:6.2%}")
     if args.trace:
         _print_trace(res)
+    if args.gaps:
+        _print_gaps(res['gaps'])
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({k: v for k, v in res.items() if k != 'full_distributions'}, f)
@@ -122,6 +128,64 @@ def _print_trace(res) -> None:
         print(f"{label:10} P(at least one) {ev['probability']:6.1%}   expected {ev['expected']:.2f}")
 
 
+def gaps_argument(args):
+    """predict_weekend's / predict_from_state's gaps argument from --gaps, --gap-edges and --gap-pair: True without the
+    two options, else {'edges': [...], 'pairs': [(a, b), ...]}."""
+    opt = {}
+    if args.gap_edges:
+        try:
+            opt['edges'] = [float(x) for x in args.gap_edges.split(',')]
+        except ValueError:
+            raise SystemExit(f'error: --gap-edges {args.gap_edges!r}: comma-separated seconds, e.g. 1,2,5') from None
+    pairs = []
+    for text in args.gap_pair or []:
+        a, sep, b = text.partition(':')
+        if not sep or not a.strip() or not b.strip():
+            raise SystemExit(f'error: --gap-pair {text!r}: two drivers as A:B, e.g. VER:NOR')
+        pairs.append((a.strip(), b.strip()))
+    if pairs:
+        opt['pairs'] = pairs
+    return opt or True
+
+
+GAP_MARKS = (1.0, 5.0, 20.0)         # seconds behind the winner that --gaps reports: the nearest edges present
+
+
+def _nearest_edges(edges):
+    out = []
+    for mark in GAP_MARKS:
+        e = min(edges, key=lambda x: (abs(x - mark), x))
+        if e not in out:
+            out.append(e)
+    return out
+
+
+def _print_gaps(g, label='') -> None:
+    """--gaps: the block of a result's 'gaps' key (predictor.gap_keys)."""
+    edges = g['edges']
+    bounds = [0.0] + edges
+    print(f"\nWINNING MARGIN{label}\n" + '-' * 40)
+    margin = g['winning_margin']
+    for b, p in enumerate(margin[:-1]):
+        if p > 0:
+            hi = f"{edges[b]:g} s" if b < len(edges) else 'more'
+            print(f"{bounds[b]:6g} s to {hi:8} {p:6.1%}")
+    if margin[-1] > 0:
+        print(f"{'fewer than two finish':20} {margin[-1]:6.1%}")
+    marks = _nearest_edges(edges)
+    print(f"\nWITHIN OF THE WINNER AT THE FLAG{label}\n" + '-' * 40)
+    print('      ' + ''.join(f"{f'< {e:g} s':>10}" for e in marks))
+    rows = g['within_at_flag']
+    for d in sorted(rows, key=lambda d: rows[d][str(marks[-1])], reverse=True)[:10]:
+        print(f"{d:4}  " + ''.join(f"{rows[d][str(e)]:10.1%}" for e in marks))
+    if g['pairs']:
+        print(f"\nPAIR GAPS AT THE FLAG{label}\n" + '-' * 40)
+    for pr in g['pairs']:
+        close = '  '.join(f"|gap| < {e:g} s {pr['within_by_lap'][str(e)][-1]:6.1%}" for e in marks)
+        print(f"{pr['a']:4} ahead {pr['a_ahead']:6.1%}   {pr['b']:4} ahead {pr['b_ahead']:6.1%}   "
+              f"either out {pr['either_out']:6.1%}   {close}")
+
+
 def cmd_in_race(args) -> int:
     from .simulation import RaceState
     fixture = synthetic_fixture()
@@ -141,8 +205,9 @@ def cmd_in_race(args) -> int:
     for i, (path, st) in enumerate(zip(args.state, states)):
         print(f"State {i + 1}: {path} (after lap {st.lap})")
     print('=' * 60 + '\n')
+    extra = {'gaps': gaps_argument(args)} if args.gaps else {}
     res = F1Predictor(device=args.device).predict_from_state(args.season, args.race, fixture, states,
-                                                             n_simulations=args.simulations, seed=args.seed)
+                                                             n_simulations=args.simulations, seed=args.seed, **extra)
     drivers = list(res[0]['win_probabilities'])
     for title, key in (('RACE WINNER PROBABILITIES', 'win_probabilities'), ('PODIUM PROBABILITIES', 'podium_probabilities')):
         print(title)
@@ -150,6 +215,10 @@ def cmd_in_race(args) -> int:
         print('      ' + ''.join(f"{'S' + str(i + 1):>9}" for i in range(len(res))))
         for d in sorted(drivers, key=lambda d: res[0][key][d], reverse=True)[:10]:
             print(f"{d:4}  " + ''.join(f"{r[key][d]:9.1%}" for r in res))
+        print()
+    if args.gaps:
+        for i, r in enumerate(res):
+            _print_gaps(r['gaps'], label=f' (S{i + 1})' if len(res) > 1 else '')
         print()
     if args.json:
         with open(args.json, 'w') as f:
@@ -551,6 +620,13 @@ def main(argv=None) -> int:
     p.add_argument('--trace', action='store_true',
                    help='also count the race lap by lap: leader, laps led, fastest lap, pit stops, safety cars '
                         '(and add them to --json)')
+    p.add_argument('--gaps', action='store_true',
+                   help='also count time gaps: winning margin, gap to the winner at the flag, named pairs (and add them '
+                        'to --json)')
+    p.add_argument('--gap-edges', type=str, default=None,
+                   help='with --gaps: the bin edges in seconds, comma-separated and increasing (default: 0.5 ... 120)')
+    p.add_argument('--gap-pair', type=str, action='append', default=None,
+                   help='with --gaps: a pair of drivers A:B whose gap is counted; repeat for more (at most 64)')
     p.set_defaults(fn=cmd_predict)
     b = sub.add_parser('backtest', help='sweep a season and score it (backtest.py of the reference)')
     b.add_argument('--seasons', type=int, nargs='+', default=[2024])
@@ -587,6 +663,13 @@ def main(argv=None) -> int:
     r.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
     r.add_argument('--device', type=int, default=0)
     r.add_argument('--json', type=str, default=None)
+    r.add_argument('--gaps', action='store_true',
+                   help='also count time gaps: winning margin, gap to the winner at the flag, named pairs (and add them '
+                        'to --json)')
+    r.add_argument('--gap-edges', type=str, default=None,
+                   help='with --gaps: the bin edges in seconds, comma-separated and increasing (default: 0.5 ... 120)')
+    r.add_argument('--gap-pair', type=str, action='append', default=None,
+                   help='with --gaps: a pair of drivers A:B whose gap is counted; repeat for more (at most 64)')
     r.set_defaults(fn=cmd_in_race)
     t = sub.add_parser('strategy', help="compare pit strategies for one driver against the model's own stops")
     t.add_argument('--season', type=int, default=2025)

@@ -14,6 +14,7 @@
 #include "resume.hip.h"
 #include "trace.hip.h"
 #include "strategy.hip.h"
+#include "gaps.hip.h"
 #include "plan_pack.h"
 #include "champ_pack.h"
 
@@ -486,6 +487,8 @@ constexpr uint64_t kOrdersChunk = 1ull << 22;
 // scenario, simulation and driver): device memory does not grow with n_sims.
 constexpr uint64_t kTraceStageBytes = 512ull << 20;
 constexpr uint64_t kStrategyStageBytes = 256ull << 20;
+// ... and of mcgp_run_gaps: one byte per recorded lap, row (n drivers + 1 lead + n_pairs pairs) and simulation.
+constexpr uint64_t kGapsStageBytes = 512ull << 20;
 
 // Simulations in one chunk of such a staging: budget / bytes_per_sim, at most max_sims_per_launch(), in multiples of 256
 // when it can (mcgp_run_trace then rounds it down to whole rounds of the device).
@@ -1614,6 +1617,135 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
     }
     counts.add_to({{hist_out, c_hist}, {delta_out, c_delta}});
     if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
+    return MCGP_OK;
+}
+
+int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                      const mcgp_race_state *state, uint32_t n, uint32_t n_edges, const double *edges, uint32_t n_pairs,
+                      const uint8_t *pairs, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device,
+                      uint64_t *hist_out, uint64_t *lap_gap_out, uint64_t *lead_out, uint64_t *pair_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+    if (!lap_gap_out) return fail(MCGP_E_BAD_ARG, "lap_gap_out is NULL");
+    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
+    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    if (n_edges < 1 || n_edges > mcgp::kMaxGapEdges) return fail(MCGP_E_BAD_ARG, "n_edges must be in [1, 63]");
+    if (!edges) return fail(MCGP_E_BAD_ARG, "edges is NULL");
+    for (uint32_t i = 0; i < n_edges; ++i) {
+        if (!std::isfinite(edges[i])) return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] is not finite");
+        if (i == 0 && !(edges[0] > 0.0)) return fail(MCGP_E_BAD_ARG, "edges[0] must be > 0");
+        if (i > 0 && !(edges[i] > edges[i - 1]))
+            return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] must be above edges[" + std::to_string(i - 1) + "]");
+    }
+    if (n_pairs > mcgp::kMaxGapPairs) return fail(MCGP_E_BAD_ARG, "n_pairs must be in [0, 64]");
+    if (n_pairs && !pairs) return fail(MCGP_E_BAD_ARG, "pairs is NULL");
+    if (n_pairs && !pair_out) return fail(MCGP_E_BAD_ARG, "pair_out is NULL");
+    if (!n_pairs && pair_out) return fail(MCGP_E_BAD_ARG, "pair_out must be NULL when n_pairs is 0");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc == MCGP_OK) rc = check_deviates_32(kp, "gaps run");
+    if (rc != MCGP_OK) return rc;
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        const uint32_t a = pairs[2 * p], b = pairs[2 * p + 1];
+        if (a >= n || b >= n)
+            return fail(MCGP_E_BAD_ARG, "pairs[" + std::to_string(p) + "]: driver index must be below n");
+        if (a == b) return fail(MCGP_E_BAD_ARG, "pairs[" + std::to_string(p) + "]: a pair needs two different drivers");
+    }
+    const uint32_t L = (uint32_t)cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string err = mcgp::pack_race_state(*state, 0, n, (int)L, &st);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+        st.sim_offset = 0;          // (race_gaps_kernel takes the ids from its sim_offset argument)
+    }
+    if (n_sims == 0) return MCGP_OK;
+    const uint32_t lap0 = state ? (uint32_t)st.lap : 0u;       // laps lap0 + 1 .. L are recorded
+    const uint32_t B = n_edges + 1, R = n + 1 + n_pairs;
+    const uint32_t rows = (L - lap0) * R;
+    const size_t c_hist = (size_t)n * n, c_gap = (size_t)L * n * (B + 1), c_lead = (size_t)L * (B + 1),
+                 c_pair = (size_t)L * n_pairs * (2 * B + 1);
+    const size_t cells = c_hist + c_gap + c_lead + c_pair;
+    Counts counts;
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        const KernelFn geo_fn = state ? reinterpret_cast<KernelFn>(&mcgp::race_gaps_kernel<true>)
+                                      : reinterpret_cast<KernelFn>(&mcgp::race_gaps_kernel<false>);   // (register count)
+        // a race resumed after its last lap records nothing: one row's worth of staging keeps the sizes non-zero
+        uint64_t chunk = stage_chunk_sims(kGapsStageBytes, std::max<uint64_t>(rows, 1));
+        {
+            // whole rounds of the device (every resident block one batch), as mcgp_run_trace does
+            uint32_t g = 0, b = 0, l = 0;
+            launch_geometry(c, n, false, geo_fn, chunk, &g, &b, &l);
+            const uint64_t round = (uint64_t)g * b;
+            if (chunk >= round) chunk = chunk / round * round;
+        }
+        chunk = std::min<uint64_t>(chunk, n_sims);
+        // workspace: staging of one chunk in rows of `stride` bytes (a multiple of 256: whole, aligned words for the
+        // counting kernel) | parameter block | state | edges | pairs | hist [n][n] | lap_gap [L][n][B + 1] |
+        // lead [L][B + 1] | pair [L][n_pairs][2B + 1]
+        const uint64_t stride = (chunk + 255) / 256 * 256;
+        Layout ws;
+        const size_t o_stage = ws.add((size_t)std::max<uint32_t>(rows, 1) * stride), o_kp = ws.add(sizeof(kp));
+        const size_t o_st = ws.add(sizeof(st)), o_edges = ws.add(sizeof(double) * mcgp::kGapEdgeSlots);
+        const size_t o_pairs = ws.add(2 * (size_t)std::max<uint32_t>(n_pairs, 1)), o_cnt = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
+        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
+        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
+        const double *d_edges = c.work.at<const double>(o_edges);
+        const uint8_t *d_pairs = c.work.at<const uint8_t>(o_pairs);
+        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
+        unsigned long long *d_gap = d_hist + c_hist, *d_lead = d_gap + c_gap, *d_pair = d_lead + c_lead;
+        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
+        double edge_table[mcgp::kGapEdgeSlots];                 // the call's edges, then +inf (gaps.hip.h: gap_bin)
+        for (uint32_t i = 0; i < mcgp::kGapEdgeSlots; ++i) edge_table[i] = i < n_edges ? edges[i] : HUGE_VAL;
+        HIP_TRY(hipMemcpy(c.work.at(o_edges), edge_table, sizeof(edge_table), hipMemcpyHostToDevice));
+        if (n_pairs) HIP_TRY(hipMemcpy(c.work.at(o_pairs), pairs, 2 * (size_t)n_pairs, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        // the counting kernel's columns: 4 x 256 bytes per value, up to 129 values (129 KiB of a CU's 160)
+        const size_t count_lds = (size_t)(n_pairs ? 2 * B + 1 : B + 1) * mcgp::kGapsCountBlock * 4;
+        if (count_lds > c.lds_per_block)
+            return fail(MCGP_E_HIP, "the gaps counting kernel's block needs " + std::to_string(count_lds) +
+                                        " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::gaps_count_rows),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)c.lds_per_block));
+        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
+        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
+        for (uint64_t done = 0; done < n_sims; done += chunk) {
+            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+            // the race: the generic kernel's block shape and LDS
+            r = generic_geometry(c, geo_fn, "gaps", n, m, &grid, &block, &lds);
+            if (r != MCGP_OK) return r;
+            if (done == 0) { grid0 = grid; block0 = block; }
+            const uint64_t n_batches = (m + block - 1) / block;
+            if (state)
+                hipLaunchKernelGGL(mcgp::race_gaps_kernel<true>, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_edges,
+                                   n_edges, d_pairs, n_pairs, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32),
+                                   d_hist, d_stage, stride, (uint32_t)n_batches);
+            else
+                hipLaunchKernelGGL(mcgp::race_gaps_kernel<false>, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_edges,
+                                   n_edges, d_pairs, n_pairs, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32),
+                                   d_hist, d_stage, stride, (uint32_t)n_batches);
+            HIP_TRY(hipGetLastError());
+            // its counts, before the next chunk overwrites the staging
+            if (rows) {
+                hipLaunchKernelGGL(mcgp::gaps_count_rows, dim3((uint32_t)std::min<uint64_t>(rows, grid_cap)),
+                                   dim3(mcgp::kGapsCountBlock), count_lds, nullptr, d_stage, stride, m, rows, n, n_pairs, B,
+                                   lap0, d_gap, d_lead, d_pair);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        note_launch(c, grid0, block0, lds, "mcgp::race_gaps_kernel");       // the launch shape of the first (fullest) chunk
+        return counts.download(d_hist, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to({{hist_out, c_hist}, {lap_gap_out, c_gap}, {lead_out, c_lead}, {pair_out, c_pair}});
     return MCGP_OK;
 }
 

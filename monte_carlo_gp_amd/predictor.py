@@ -171,7 +171,7 @@ class F1Predictor:
 
     def predict_weekend(self, season: int, race: str, fixture: dict | str, grid_penalties=None, circuit_info=None,
                         prediction_point: str = 'fp2', actual_grid=None, n_simulations: int = 10000,
-                        seed: int | None = None, matchups: bool = False, trace: bool = False) -> dict:
+                        seed: int | None = None, matchups: bool = False, trace: bool = False, gaps=None) -> dict:
         """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU.
 
         matchups=True (not in the reference): the race runs through RaceSimulator.run_matchups -- the same simulations,
@@ -181,7 +181,11 @@ class F1Predictor:
 
         trace=True (not in the reference): the race also runs through RaceSimulator.run_trace -- again the same
         simulations -- and the result gains the keys of trace_keys: 'leader_by_lap', 'expected_laps_led',
-        'pit_stop_distribution', 'fastest_lap_probabilities' and 'race_event_probabilities'."""
+        'pit_stop_distribution', 'fastest_lap_probabilities' and 'race_event_probabilities'.
+
+        gaps=True, or {'edges': [...], 'pairs': [(a, b), ...]} (not in the reference): the race also runs through
+        RaceSimulator.run_gaps -- the same simulations once more -- and the result gains 'gaps', the block gap_keys
+        builds: the winning-margin distribution, each driver's finishing-gap distribution and the requested pairs."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -192,20 +196,20 @@ class F1Predictor:
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
             # same inputs, the matrix built on the device from the ratings (no host matrix crosses PCIe)
             ratings = {d: self.elo_system.ratings.get(d, {}).get('quali', self.elo_system.initial) for d in inp['drivers']}
-            if matchups or trace:
-                # the same matrix, read back from the device front end and handed to the matchups / trace run
+            if matchups or trace or gaps:
+                # the same matrix, read back from the device front end and handed to the matchups / trace / gaps run
                 grid = sim.grid_probs_on_device(inp['drivers'], ratings, fixture.get('quali_features', {}),
                                                 grid_penalties or {})
                 return self._with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups,
-                                         trace)
+                                         trace, gaps)
             race_probs, grid = sim.run_from_ratings(
                 n_simulations, inp['drivers'], ratings, fixture.get('quali_features', {}), grid_penalties or {},
                 inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'], seed=seed,
                 track_condition=inp['track_condition'])
             return pack_result(inp['drivers'], grid, race_probs, inp['weather'], prediction_point, actual_grid)
-        if matchups or trace:
+        if matchups or trace or gaps:
             return self._with_counts(sim, inp, inp['grid_probs'], n_simulations, seed, prediction_point, actual_grid,
-                                     matchups, trace)
+                                     matchups, trace, gaps)
         race_probs = sim.run_monte_carlo(
             n_simulations=n_simulations, grid_probs=inp['grid_probs'], base_pace=inp['base_pace'],
             tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
@@ -213,11 +217,12 @@ class F1Predictor:
         return pack_result(inp['drivers'], inp['grid_probs'], race_probs, inp['weather'], prediction_point, actual_grid)
 
     def predict_from_state(self, season: int, race: str, fixture: dict | str, state, n_simulations: int = 100000,
-                           seed: int | None = None):
+                           seed: int | None = None, gaps=None):
         """In-race odds (not in the reference): the weekend's race inputs (simulator_inputs, as predict_weekend builds
         them) run from a mid-race RaceState of the fixture's drivers -- or from each of a list of them, with common
         random numbers -- through RaceSimulator.run_from_state.  Returns, per state, {'lap', 'win_probabilities', 'podium_probabilities',
-        'points_probabilities' (top 10), 'full_distributions'}: one dict, or a list for a list of states."""
+        'points_probabilities' (top 10), 'full_distributions'}: one dict, or a list for a list of states.  gaps (as in
+        predict_weekend): every state's dict gains 'gaps' from RaceSimulator.run_gaps on that state, same simulations."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -227,6 +232,7 @@ class F1Predictor:
         states = [state] if single else list(state)
         inp = self.simulator_inputs(fixture, race)
         sim = RaceSimulator(inp['config'], device=self.device)
+        seed = sim._resolve_seed(seed) if gaps else seed
         # the driver order of predict_weekend's run: a state that run's simulation i reached continues as simulation i
         probs = sim.run_from_state(n_simulations, states, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
                                    inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'],
@@ -237,6 +243,12 @@ class F1Predictor:
             top = lambda k: {d: sum(rp.get(d, {}).get(p, 0) for p in range(1, k + 1)) for d in drivers}
             out.append({'lap': int(st.lap), 'win_probabilities': top(1), 'podium_probabilities': top(3),
                         'points_probabilities': top(10), 'full_distributions': rp})
+        if gaps:
+            for st, res in zip(states, out):
+                g = sim.run_gaps(n_simulations, None, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
+                                 inp['driver_dnf_rates'], state=st, seed=seed, track_condition=inp['track_condition'],
+                                 drivers=list(inp['grid_probs']), **gap_options(gaps))
+                res['gaps'] = gap_keys(g)
         return out[0] if single else out
 
     def predict_strategies(self, season: int, race: str, fixture: dict | str, strategies: dict, state=None,
@@ -260,9 +272,10 @@ class F1Predictor:
                                   drivers=list(inp['grid_probs']), allow_single_compound=allow_single_compound)
 
     @staticmethod
-    def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace) -> dict:
-        """predict_weekend's result from run_matchups and / or run_trace calls on `grid` (the same simulations: one seed
-        for both), with their keys added."""
+    def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace,
+                     gaps=None) -> dict:
+        """predict_weekend's result from run_matchups, run_trace and / or run_gaps calls on `grid` (the same simulations:
+        one seed for all), with their keys added."""
         args = (n_simulations, grid, inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'])
         seed = sim._resolve_seed(seed)
         res = None
@@ -276,6 +289,12 @@ class F1Predictor:
                 res = pack_result(inp['drivers'], grid, t.position_probabilities, inp['weather'], prediction_point,
                                   actual_grid)
             res.update(trace_keys(t))
+        if gaps:
+            g = sim.run_gaps(*args, seed=seed, track_condition=inp['track_condition'], **gap_options(gaps))
+            if res is None:
+                res = pack_result(inp['drivers'], grid, g.position_probabilities, inp['weather'], prediction_point,
+                                  actual_grid)
+            res['gaps'] = gap_keys(g)
         return res
 
 
@@ -304,6 +323,39 @@ def trace_keys(t) -> dict:
         'expected_pit_stops': t.expected_pit_stops,
         'fastest_lap_probabilities': t.fastest_lap_probabilities,
         'race_event_probabilities': t.event_probabilities,
+    }
+
+
+def gap_options(gaps) -> dict:
+    """run_gaps's edges / pairs from predict_weekend's gaps argument: True, or {'edges': [...], 'pairs': [(a, b), ...]}."""
+    if gaps is True:
+        return {}
+    unknown = set(gaps) - {'edges', 'pairs'}
+    if unknown:
+        raise ValueError(f'gaps: unknown keys {sorted(unknown)} (edges, pairs)')
+    out = {}
+    if gaps.get('edges') is not None:
+        out['edges'] = [float(x) for x in gaps['edges']]
+    if gaps.get('pairs'):
+        out['pairs'] = [(str(a), str(b)) for a, b in gaps['pairs']]
+    return out
+
+
+def gap_keys(g) -> dict:
+    """The 'gaps' block predict_weekend(gaps=...) / predict_from_state(gaps=...) add, JSON-safe, from a GapResult: the
+    edges; the winning-margin distribution ([B + 1]: the bins, then P(fewer than two finish)); per driver the
+    finishing-gap distribution ([B + 1]: the bins, then P(retired)) and P(within each edge of the leader at the flag);
+    per pair P(a ahead), P(b ahead), P(either out) at the flag and P(|gap| < edge) by lap for every edge."""
+    fl = lambda a: [float(x) for x in a]
+    return {
+        'edges': list(g.edges),
+        'first_lap': g.first_lap,
+        'winning_margin': fl(g.winning_margin_distribution),
+        'finishing_gap': {d: fl(g.gap_distribution(d)) for d in g.drivers},
+        'within_at_flag': {d: {str(e): g.within(d, e) for e in g.edges} for d in g.drivers},
+        'pairs': [dict(a=a, b=b, **g.pair_summary(a, b),
+                       within_by_lap={str(e): fl(g.pair_within_by_lap(a, b, e)) for e in g.edges})
+                  for a, b in g.pairs],
     }
 
 

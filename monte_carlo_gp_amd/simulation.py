@@ -607,6 +607,84 @@ class RaceSimulator:
         self.last_drivers = drivers
         return res
 
+    def run_gaps(
+        self,
+        n_simulations: int,
+        grid_probs: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        state: 'RaceState | None' = None,
+        edges=None,
+        pairs=(),
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+    ) -> 'GapResult':
+        """Race time gaps (include/mcgp.h: mcgp_run_gaps): histograms over `edges` (seconds, default DEFAULT_GAP_EDGES) of
+        every car's gap to the leader after each lap, of the lead (the winning margin on the last lap) and of the gap
+        between each of `pairs` = [(driver a, driver b), ...] (at most 64), counted on the device.  From the grid
+        (grid_probs: run_monte_carlo's simulations, laps 1..L) or from a mid-race RaceState (state: run_from_state's
+        simulations, the laps after the state's).  The GapResult's position histogram equals that call's.  32-bit
+        deviates only; same seed rules and device sharding as run_monte_carlo.  Sets last_histogram / last_drivers."""
+        if (grid_probs is None) == (state is None):
+            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
+        if drivers is None:
+            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
+        drivers = [str(d) for d in drivers]
+        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
+            raise ValueError('drivers must be the keys of grid_probs')
+        edge_arr = np.ascontiguousarray(DEFAULT_GAP_EDGES if edges is None else list(edges), np.float64)
+        if edge_arr.ndim != 1 or not 1 <= len(edge_arr) <= N.MAX_GAP_EDGES:
+            raise ValueError(f'edges: 1 to {N.MAX_GAP_EDGES} values, got {edge_arr.shape}')
+        if not (np.isfinite(edge_arr).all() and edge_arr[0] > 0 and (np.diff(edge_arr) > 0).all()):
+            raise ValueError('edges must be finite, positive and strictly increasing')
+        index = {d: i for i, d in enumerate(drivers)}
+        names = [(str(a), str(b)) for a, b in pairs]
+        for a, b in names:
+            if a not in index or b not in index:
+                raise ValueError(f'pair ({a!r}, {b!r}): not among the drivers')
+            if a == b:
+                raise ValueError(f'pair ({a!r}, {b!r}): a pair needs two different drivers')
+        if len(names) > N.MAX_GAP_PAIRS:
+            raise ValueError(f'pairs: at most {N.MAX_GAP_PAIRS}, got {len(names)}')
+        n, L, E, P = len(drivers), int(self.config.total_laps), len(edge_arr), len(names)
+        n_simulations = int(n_simulations)
+        first_lap = 1 if state is None else int(state.lap) + 1
+        mk = lambda count, dtype: GapResult.empty(drivers, L, edge_arr, names, count, first_lap, dtype)
+        if not drivers or n_simulations <= 0:
+            res = mk(0, np.int64)
+            self.last_histogram, self.last_drivers = res.hist, drivers
+            return res
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        arrays = state.arrays(drivers, L) if state is not None else None
+        c_state = state.c_struct(arrays) if state is not None else None
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
+        pair_arr = np.ascontiguousarray([[index[a], index[b]] for a, b in names], np.uint8).reshape(P, 2)
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            out = mk(count, np.uint64)
+            rc = lib.mcgp_run_gaps(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
+                                   C.byref(c_state) if c_state is not None else None, n, E, _dptr(edge_arr), P,
+                                   pair_arr.ctypes.data_as(C.POINTER(C.c_uint8)) if P else None, int(count),
+                                   int(sim_offset) + int(offset), seed64, device, u64(out.hist), u64(out.lap_gap),
+                                   u64(out.lead), u64(out.pair) if P else None)
+            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([getattr(r, k) for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        res = GapResult(drivers=drivers, n_simulations=n_simulations, total_laps=L, edges=tuple(float(x) for x in edge_arr),
+                        pairs=names, first_lap=first_lap, hist=total('hist'), lap_gap=total('lap_gap'), lead=total('lead'),
+                        pair=total('pair'))
+        self.last_histogram = res.hist
+        self.last_drivers = drivers
+        return res
+
     def simulate_race(
         self,
         grid: list,
@@ -893,6 +971,151 @@ class TraceResult:
             p = self._p(self.events[k])
             out[name] = {'probability': float(1.0 - p[0]) if self.n_simulations else 0.0, 'expected': float(p @ j)}
         return out
+
+
+DEFAULT_GAP_EDGES = (0.5, 1, 2, 3, 5, 7.5, 10, 15, 20, 30, 45, 60, 90, 120)      # seconds
+
+
+@dataclass
+class GapResult:
+    """What RaceSimulator.run_gaps returns: integer counts over n_simulations of the race's time gaps, read after the end
+    of each lap (include/mcgp.h: mcgp_run_gaps has the definitions).  L = total_laps, n = len(drivers), B = len(edges)
+    + 1 bins: bin b holds gaps in [edges[b - 1], edges[b]), bin 0 from 0, bin B - 1 without an upper bound.
+      hist     [n][n]            [driver][position - 1], run_monte_carlo's / run_from_state's histogram
+      lap_gap  [L][n][B + 1]     [lap - 1][driver][bin of the gap to the leader], column B = retired
+      lead     [L][B + 1]        [lap - 1][bin of second minus leader], column B = fewer than two cars running
+      pair     [L][P][2B + 1]    [lap - 1][pair (a, b)][bin of b - a with a ahead | B + bin of a - b with b ahead | 2B =
+                                 either retired]
+    Laps before first_lap (a run from a state) are not recorded: their rows are zero.  The counts carry no value between
+    two edges, so every reader answers in terms of edges and bins, never an interpolated number."""
+    drivers: list
+    n_simulations: int
+    total_laps: int
+    edges: tuple
+    pairs: list
+    first_lap: int
+    hist: np.ndarray
+    lap_gap: np.ndarray
+    lead: np.ndarray
+    pair: np.ndarray
+
+    @classmethod
+    def empty(cls, drivers, total_laps, edges, pairs=(), n_simulations=0, first_lap=1, dtype=np.int64) -> 'GapResult':
+        n, L, B, P = len(drivers), int(total_laps), len(edges) + 1, len(pairs)
+        z = lambda *shape: np.zeros(shape, dtype)
+        return cls(drivers=list(drivers), n_simulations=int(n_simulations), total_laps=L,
+                   edges=tuple(float(x) for x in edges), pairs=[(str(a), str(b)) for a, b in pairs],
+                   first_lap=int(first_lap), hist=z(n, n), lap_gap=z(L, n, B + 1), lead=z(L, B + 1), pair=z(L, P, 2 * B + 1))
+
+    @property
+    def n_bins(self) -> int:
+        return len(self.edges) + 1
+
+    def _p(self, counts):
+        return np.asarray(counts, np.float64) / max(self.n_simulations, 1)
+
+    def _d(self, driver):
+        try:
+            return self.drivers.index(str(driver))
+        except ValueError:
+            raise ValueError(f'{driver!r} is not one of the drivers') from None
+
+    def _lap(self, lap):
+        lap = self.total_laps if lap is None else int(lap)
+        if not self.first_lap <= lap <= self.total_laps:
+            raise ValueError(f'lap must be in [{self.first_lap}, {self.total_laps}], got {lap}')
+        return lap - 1
+
+    def _edge(self, seconds):
+        """The number of bins below `seconds`, which must be an edge: the counts cannot answer anything else."""
+        for j, e in enumerate(self.edges):
+            if e == float(seconds):
+                return j + 1
+        raise ValueError(f'{seconds!r} is not one of the edges {self.edges}: the counts cannot answer it')
+
+    def _pair(self, a, b):
+        """(index, mirrored): the pair as given, or as its mirror image."""
+        a, b = str(a), str(b)
+        if (a, b) in self.pairs:
+            return self.pairs.index((a, b)), False
+        if (b, a) in self.pairs:
+            return self.pairs.index((b, a)), True
+        raise ValueError(f'({a!r}, {b!r}) is not one of the pairs {self.pairs}')
+
+    def bin_bounds(self, b) -> tuple:
+        """(low, high) of bin b in seconds; the last bin's high is inf."""
+        b = int(b)
+        if not 0 <= b < self.n_bins:
+            raise ValueError(f'bin must be in [0, {self.n_bins - 1}], got {b}')
+        return (0.0 if b == 0 else self.edges[b - 1], self.edges[b] if b < len(self.edges) else math.inf)
+
+    @property
+    def position_probabilities(self) -> dict:
+        """{driver: {position: probability}}, what run_monte_carlo / run_from_state returns for the same arguments."""
+        return histogram_to_probs(self.hist, self.drivers, self.n_simulations)
+
+    def gap_distribution(self, driver, lap=None) -> np.ndarray:
+        """[B + 1]: P(gap to the leader in bin b after `lap`), last entry P(retired by then).  lap None: the flag (the
+        finishing-gap distribution)."""
+        return self._p(self.lap_gap[self._lap(lap), self._d(driver)])
+
+    @property
+    def finishing_gap_distributions(self) -> dict:
+        """{driver: [B + 1] array} at the flag."""
+        return {d: self.gap_distribution(d) for d in self.drivers}
+
+    def within(self, driver, seconds, lap=None) -> float:
+        """P(running and less than `seconds` behind the leader after `lap`; None: at the flag).  `seconds` must be one
+        of the edges (ValueError otherwise).  The leader is within every edge."""
+        j = self._edge(seconds)
+        return float(self._p(self.lap_gap[self._lap(lap), self._d(driver), :j].sum()))
+
+    @property
+    def winning_margin_distribution(self) -> np.ndarray:
+        """[B + 1]: P(second finishes in bin b behind the winner), last entry P(fewer than two cars finish)."""
+        return self._p(self.lead[self.total_laps - 1])
+
+    def winning_margin_under(self, seconds) -> float:
+        """P(two cars finish and the margin is less than `seconds`), an edge."""
+        return float(self._p(self.lead[self.total_laps - 1, :self._edge(seconds)].sum()))
+
+    @property
+    def lead_by_lap(self) -> np.ndarray:
+        """[L][B + 1]: the distribution of the leader's advantage over second after every lap."""
+        return self._p(self.lead)
+
+    def median_gap_bin_by_lap(self, driver) -> list:
+        """[L] of (low, high): the bounds of the bin that holds the median gap to the leader among the simulations in
+        which the driver is running after that lap; None for a lap that is not recorded or on which it never runs."""
+        i, B, out = self._d(driver), self.n_bins, []
+        for k in range(self.total_laps):
+            c = self.lap_gap[k, i, :B]
+            tot = int(c.sum())
+            if tot == 0:
+                out.append(None)
+                continue
+            # the lower median: the smallest bin b with 2 x (count up to and including b) >= the number running
+            b = int(np.searchsorted(2 * np.cumsum(c), tot, side='left'))
+            out.append(self.bin_bounds(b))
+        return out
+
+    def pair_summary(self, a, b, lap=None) -> dict:
+        """{'a_ahead', 'b_ahead', 'either_out'}: probabilities after `lap` (None: at the flag) for a requested pair, in
+        either orientation."""
+        p, mirrored = self._pair(a, b)
+        B = self.n_bins
+        c = self.pair[self._lap(lap), p]
+        first, second = float(self._p(c[:B].sum())), float(self._p(c[B:2 * B].sum()))      # (counts summed, then divided)
+        if mirrored:
+            first, second = second, first
+        return {'a_ahead': first, 'b_ahead': second, 'either_out': float(self._p(c[2 * B]))}
+
+    def pair_within_by_lap(self, a, b, seconds) -> np.ndarray:
+        """[L]: P(both running and |gap| < seconds after each lap), `seconds` an edge -- e.g. 1.0 for DRS range, or the
+        pit-stop loss for "is a stop free"."""
+        p, _ = self._pair(a, b)
+        j, B = self._edge(seconds), self.n_bins
+        return self._p(self.pair[:, p, :j].sum(axis=1) + self.pair[:, p, B:B + j].sum(axis=1))
 
 
 DEFAULT_POINTS = (25, 18, 15, 12, 10, 8, 6, 4, 2, 1)      # a Grand Prix, positions 1-10
