@@ -1,7 +1,7 @@
 // gaps.hip.h -- the time gaps of a race, counted on the device (mcgp_run_gaps, include/mcgp.h).
 //
 // race_gaps_kernel runs mcgp_run's simulations (from the grid, kFromState false) or mcgp_run_from_state's (from one
-// state) with the generic kernel's code -- race_start.inc.h or resume_start.inc.h, run_laps, classify_and_count -- and
+// state) with the generic kernel's code -- start_from_grid or start_from_state, run_laps, classify_and_count -- and
 // a per-lap observer (GapObserver) that sees the rows after update_positions of every recorded lap: laps 1..L from the
 // grid, laps k + 1 .. L from a state after lap k.  Simulation i draws exactly what those calls' simulation i draws, so
 // the position histogram is theirs.  Read at that point of a lap (the state the CPU oracle's per-lap trace records):
@@ -113,61 +113,27 @@ race_gaps_kernel(const KParams *__restrict__ P, const ResumeState *__restrict__ 
                  uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist, uint8_t *__restrict__ stage,
                  uint64_t stride, uint32_t n_batches)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int B = blockDim.x;
-    uint32_t *s_hist;
-    Rows s;
-    const LapEnv e = load_block(smem, P, s_hist, s);
-    __syncthreads();
-    const int n = e.n;
-    const int L = e.L;
-
-    for (uint32_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
-        const uint64_t local = (uint64_t)batch * (uint64_t)B + (uint64_t)tid;
-        if (local >= m) continue;           // tail lanes idle; no barrier inside the loop
+    run_block(P, m, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
         const uint64_t sim = sim_offset + local;
         const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
+        const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
+                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr);
 
         GapObserver obs;
         obs.lane = stage + local;
-        obs.lap_bytes = (uint64_t)(n + 1 + (int)n_pairs) * stride;
+        obs.lap_bytes = (uint64_t)(e.n + 1 + (int)n_pairs) * stride;
         obs.stride = stride;
         obs.edges = edges;
         obs.pairs = pairs;
         obs.n_edges = n_edges;
         obs.n_pairs = n_pairs;
-        obs.n = n;
-        int first_lap = 2, dd = 0;
+        obs.n = e.n;
+        obs.first_lap = kFromState ? at.first_lap : 1;
+        if (!kFromState) obs(s, 1, kEventNone);
 
-        if constexpr (kFromState) {
-            const ResumeState &st = *state;
-            const int k = st.lap;
-            const int drs_disabled_until = st.drs_disabled_until;
-#include "resume_start.inc.h"
-            first_lap = k + 1;
-            dd = drs_disabled_until;
-            obs.first_lap = first_lap;
-        } else {
-            const int track = e.track;
-            const uint8_t *fixed_grid = nullptr;
-#include "race_start.inc.h"
-            obs.first_lap = 1;
-            obs(s, 1, kEventNone);
-        }
-
-        // ================= laps first_lap..L, reference :166-228 =================
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, first_lap, dd, obs);
-
-        // ================= classification, reference :230-242 =================
-        classify_and_count(s, n, s_hist, nullptr);
-    }
-
-    __syncthreads();
-    for (int i = tid; i < n * n; i += B) {
-        const uint32_t c = s_hist[i];
-        if (c) atomicAdd(&hist[i], (unsigned long long)c);
-    }
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, obs);         // reference :166-228
+        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
+    });
 }
 
 // The staged rows' counts of m simulations, added into their places: staged row q = lap_index R + j (lap_index = lap -

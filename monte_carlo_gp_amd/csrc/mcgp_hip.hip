@@ -491,12 +491,25 @@ constexpr uint64_t kStrategyStageBytes = 256ull << 20;
 constexpr uint64_t kGapsStageBytes = 512ull << 20;
 
 // Simulations in one chunk of such a staging: budget / bytes_per_sim, at most max_sims_per_launch(), in multiples of 256
-// when it can (mcgp_run_trace then rounds it down to whole rounds of the device).
+// when it can.
 uint64_t stage_chunk_sims(uint64_t budget, uint64_t bytes_per_sim)
 {
     uint64_t chunk = std::min<uint64_t>(max_sims_per_launch(), std::max<uint64_t>(1, budget / bytes_per_sim));
     if (chunk >= 256) chunk = chunk / 256 * 256;
     return chunk;
+}
+
+// ... rounded down to whole rounds of the device under the generic-shaped `kernel` (every resident block one batch: a
+// chunk of 5.5 rounds costs 6), and at most n_sims (mcgp_run_trace, mcgp_run_gaps).
+uint64_t stage_chunk_rounds(const DeviceCtx &c, uint32_t n, KernelFn kernel, uint64_t budget, uint64_t bytes_per_sim,
+                            uint64_t n_sims)
+{
+    uint64_t chunk = stage_chunk_sims(budget, bytes_per_sim);
+    uint32_t g = 0, b = 0, l = 0;
+    launch_geometry(c, n, false, kernel, chunk, &g, &b, &l);
+    const uint64_t round = (uint64_t)g * b;
+    if (chunk >= round) chunk = chunk / round * round;
+    return std::min<uint64_t>(chunk, n_sims);
 }
 
 // Front-end inputs of one call, already on the device (c.d_fe_in / c.d_fe_pen), or null.
@@ -1421,15 +1434,7 @@ int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const do
     Counts counts;
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         const KernelFn geo_fn = reinterpret_cast<KernelFn>(&mcgp::race_trace_kernel);   // (for its register count)
-        uint64_t chunk = stage_chunk_sims(kTraceStageBytes, (uint64_t)L * n);
-        {
-            // whole rounds of the device (every resident block one batch): a chunk of 5.5 rounds costs 6
-            uint32_t g = 0, b = 0, l = 0;
-            launch_geometry(c, n, false, geo_fn, chunk, &g, &b, &l);
-            const uint64_t round = (uint64_t)g * b;
-            if (chunk >= round) chunk = chunk / round * round;
-        }
-        chunk = std::min<uint64_t>(chunk, n_sims);
+        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kTraceStageBytes, (uint64_t)L * n, n_sims);
         // workspace: staging of one chunk in rows of `stride` bytes (a multiple of 256: whole, aligned words for the
         // counting kernels) | the chunk's records | parameter block | hist [n][n] | lap_pos [L][n][n + 1] |
         // laps_led [n][L + 1] | stops [n][L + 1] | fastest [n] | events [3][L + 1]
@@ -1563,8 +1568,8 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
             pos_back.resize(stage_bytes);
             orders.resize((size_t)S * n_sims * n);
         }
-        const KernelFn geo_fn = state ? reinterpret_cast<KernelFn>(&mcgp::race_strategy_kernel<true>)
-                                      : reinterpret_cast<KernelFn>(&mcgp::race_strategy_kernel<false>);   // (register count)
+        const auto kernel = state ? &mcgp::race_strategy_kernel<true> : &mcgp::race_strategy_kernel<false>;
+        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
         const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
         uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
         for (uint64_t done = 0; done < n_sims; done += chunk) {
@@ -1575,14 +1580,8 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
             const uint64_t n_batches = (m + block - 1) / block;
             const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + S - 1) / S);
             if (done == 0) { grid0 = gx * S; block0 = block; }
-            if (state)
-                hipLaunchKernelGGL(mcgp::race_strategy_kernel<true>, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st,
-                                   d_sc, d_sl, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist,
-                                   d_stage, (uint32_t)n_batches);
-            else
-                hipLaunchKernelGGL(mcgp::race_strategy_kernel<false>, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st,
-                                   d_sc, d_sl, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist,
-                                   d_stage, (uint32_t)n_batches);
+            hipLaunchKernelGGL(kernel, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st, d_sc, d_sl, m, sim_offset + done,
+                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, (uint32_t)n_batches);
             HIP_TRY(hipGetLastError());
             // its counts, before the next chunk overwrites the staging
             if (delta_out && S > 1) {
@@ -1670,18 +1669,10 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     const size_t cells = c_hist + c_gap + c_lead + c_pair;
     Counts counts;
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        const KernelFn geo_fn = state ? reinterpret_cast<KernelFn>(&mcgp::race_gaps_kernel<true>)
-                                      : reinterpret_cast<KernelFn>(&mcgp::race_gaps_kernel<false>);   // (register count)
+        const auto kernel = state ? &mcgp::race_gaps_kernel<true> : &mcgp::race_gaps_kernel<false>;
+        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
         // a race resumed after its last lap records nothing: one row's worth of staging keeps the sizes non-zero
-        uint64_t chunk = stage_chunk_sims(kGapsStageBytes, std::max<uint64_t>(rows, 1));
-        {
-            // whole rounds of the device (every resident block one batch), as mcgp_run_trace does
-            uint32_t g = 0, b = 0, l = 0;
-            launch_geometry(c, n, false, geo_fn, chunk, &g, &b, &l);
-            const uint64_t round = (uint64_t)g * b;
-            if (chunk >= round) chunk = chunk / round * round;
-        }
-        chunk = std::min<uint64_t>(chunk, n_sims);
+        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kGapsStageBytes, std::max<uint64_t>(rows, 1), n_sims);
         // workspace: staging of one chunk in rows of `stride` bytes (a multiple of 256: whole, aligned words for the
         // counting kernel) | parameter block | state | edges | pairs | hist [n][n] | lap_gap [L][n][B + 1] |
         // lead [L][B + 1] | pair [L][n_pairs][2B + 1]
@@ -1724,14 +1715,9 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
             if (r != MCGP_OK) return r;
             if (done == 0) { grid0 = grid; block0 = block; }
             const uint64_t n_batches = (m + block - 1) / block;
-            if (state)
-                hipLaunchKernelGGL(mcgp::race_gaps_kernel<true>, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_edges,
-                                   n_edges, d_pairs, n_pairs, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32),
-                                   d_hist, d_stage, stride, (uint32_t)n_batches);
-            else
-                hipLaunchKernelGGL(mcgp::race_gaps_kernel<false>, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_edges,
-                                   n_edges, d_pairs, n_pairs, m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32),
-                                   d_hist, d_stage, stride, (uint32_t)n_batches);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_edges, n_edges, d_pairs, n_pairs,
+                               m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride,
+                               (uint32_t)n_batches);
             HIP_TRY(hipGetLastError());
             // its counts, before the next chunk overwrites the staging
             if (rows) {

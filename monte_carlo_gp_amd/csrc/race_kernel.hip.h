@@ -21,9 +21,11 @@
 // (cumulative_time, grid slot) -- reference :179,231,353,384,410,506,549 sort lists
 // that are in grid order (Q1), so equal times keep grid order.
 //
-// The block's LDS set-up (load_block), the laps after lap 1 (run_laps) and the classification (classify_and_count)
-// are functions shared with race_resume_kernel (resume.hip.h), which runs a race on from a mid-race state, and with
-// race_trace_kernel (trace.hip.h), which also shares the start of a race (race_start.inc.h) and observes every lap.
+// The block protocol (run_block, over load_block), the start of a race (start_from_grid), the laps after lap 1
+// (run_laps) and the classification (classify_and_count) are functions shared with the other race kernels of this
+// family: race_resume_kernel (resume.hip.h) runs a race on from a mid-race state, race_trace_kernel (trace.hip.h) and
+// race_gaps_kernel (gaps.hip.h) observe every lap, race_strategy_kernel (strategy.hip.h) plans the pit stops.  A kernel
+// is its arguments and the lane body it hands run_block: sim id, start, run_laps, classify_and_count, its own output.
 //
 // Floating point: IEEE binary64 in the reference's evaluation order; this file
 // is compiled with -ffp-contract=off.  The only fused operations are the three
@@ -193,9 +195,126 @@ __device__ __forceinline__ LapEnv load_block(unsigned char *smem, const KParams 
     return e;
 }
 
-// The hook of race_start.inc.h for a car's starting tyres: nothing here (race_strategy_kernel redefines it around its
-// own inclusion of the text).
-#define MCGP_START_OVERRIDE(driver, comp, age)
+// What a start hands run_laps: the first lap to run and the reference's drs_disabled_until before it.
+struct RaceStart {
+    int first_lap, drs_disabled_until;
+};
+
+// start_from_grid's hook for a car's starting tyres: the model's own (the call vanishes at compile time).
+struct ModelTyres {
+    __device__ __forceinline__ void operator()(uint32_t /*driver*/, uint32_t & /*comp*/, uint32_t & /*age*/) const {}
+};
+
+// The start of one lane's race: grid (`fixed_grid`, or NULL: sampled from grid_probs), cars, lap 1 and the once-per-race
+// retirement draws.  Leaves the rows after update_positions of lap 1 and every driver's retirement lap (laps >= 2) in
+// `out`.  hook(driver, comp, age) may replace a car's starting tyres after the model has picked them
+// (race_strategy_kernel, strategy.hip.h).
+template <class StartHook = ModelTyres>
+__device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1,
+                                                     uint32_t seed_lo, uint32_t seed_hi,
+                                                     const uint8_t *__restrict__ fixed_grid, StartHook hook = StartHook())
+{
+    const KParams *__restrict__ P = e.P;
+    const int n = e.n, L = e.L, track = e.track;
+
+    // ================= _sample_grid, reference :102-145 =================
+    // probs / cdf scratch lives in the `last` rows (not needed until lap 2).
+    {
+        uint32_t remaining = (n >= 32) ? 0xffffffffu : ((1u << n) - 1u);
+        int n_remaining = n;
+        uint32_t g0 = 0, g1 = 0, g2 = 0, g3 = 0;
+        for (int pos = 0; pos < n; ++pos) {
+            uint32_t sel;
+            if (fixed_grid) {
+                sel = fixed_grid[pos];
+            } else {
+                if ((pos & 3) == 0)
+                    philox4x32_10(c0, c1, 0u, kPurposeGrid | (uint32_t)(pos >> 2), seed_lo, seed_hi, g0, g1, g2, g3);
+                const uint32_t gw = (pos & 3) == 0 ? g0 : (pos & 3) == 1 ? g1 : (pos & 3) == 2 ? g2 : g3;
+                const double u = u32_to_unit(gw);
+                double total = 0.0;                                   // :119-123
+                for (int d = 0; d < n; ++d) {
+                    const double p = ((remaining >> d) & 1u) ? P->grid_probs[d * n + pos] : 0.0;
+                    total = total + p;
+                }
+                double prob_sum = 0.0;                                // :125-133
+                for (int d = 0; d < n; ++d) {
+                    const bool rem = (remaining >> d) & 1u;
+                    double p;
+                    if (total > 0) p = (rem ? P->grid_probs[d * n + pos] : 0.0) / total;
+                    else p = rem ? 1.0 / (double)n_remaining : 0.0;
+                    s.Last(d) = p;
+                    prob_sum = prob_sum + p;
+                }
+                const bool renorm = prob_sum > 0 && fabs(prob_sum - 1.0) > 1e-9;   // :134-135
+                // np.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; searchsorted(u, 'right')
+                double acc = 0.0;
+                for (int d = 0; d < n; ++d) {
+                    double p = s.Last(d);
+                    if (renorm) p = p / prob_sum;
+                    acc = (d == 0) ? p : acc + p;
+                    s.Last(d) = acc;
+                }
+                const double cdf_last = acc;
+                sel = 0;
+                for (int d = 0; d < n; ++d)
+                    if (s.Last(d) / cdf_last <= u) sel = (uint32_t)d + 1u;
+                if (sel >= (uint32_t)n) sel = (uint32_t)n - 1u;       // unreachable: cdf[-1] == 1 > u
+            }
+            if ((remaining >> sel) & 1u) { remaining &= ~(1u << sel); --n_remaining; }
+            // _initialize_cars, reference :244-273
+            uint32_t comp, age;
+            if (track == 2) { comp = 4u; age = 0u; }
+            else if (track == 1) { comp = 3u; age = 0u; }
+            else { comp = pos < 10 ? 0u : 1u; age = pos < 10 ? 4u : 0u; }
+            hook(sel, comp, age);
+            s.Pk(sel) = age | (comp << kCompShift) | ((1u << comp) << kUsedShift) | ((uint32_t)pos << kGposShift);
+            s.Cum(sel) = 0.0;
+            s.Ord(pos) = (uint8_t)sel;
+        }
+        for (int d = 0; d < n; ++d) s.Last(d) = 0.0;
+    }
+
+    // ================= _simulate_lap_1, reference :275-311 =================
+    for (int pos = 0; pos < n; ++pos) {
+        const uint32_t d = s.Ord(pos);
+        uint32_t pk = s.Pk(d);
+        uint32_t w0, w1, w2, w3;
+        philox4x32_10(c0, c1, 1u, kPurposeCar | d, seed_lo, seed_hi, w0, w1, w2, w3);
+        if ((uint64_t)w0 < e.dnf1[d]) {
+            s.Pk(d) = (pk & ~kAgeMask) | kDnf | 1u;
+            continue;
+        }
+        const uint32_t comp = (pk >> kCompShift) & 7u;
+        const uint32_t age = pk & kAgeMask;
+        const double eff = e.cdeg[comp] * e.factor[d];
+        const double tire = (double)age * eff;
+        const double fuel_effect = (110.0 - 110.0) * 0.03;
+        const double noise = 0.0 + e.var[d] * (double)normal_from_u32(w1, e.norm);
+        const double base_lap = e.base[d] + tire - fuel_effect + e.cdelta[comp] - 0.0 + noise;
+        double pf = 0.5 + (double)(pos + 1) * 0.1;
+        if (!(pf < 1.5)) pf = 1.5;
+        double sd = 0.0 + pf * (double)normal_from_u32(w2, e.norm);
+        if (pos + 1 <= 3 && 1.0 < sd) sd = 1.0;
+        const double lap_time = base_lap - sd * 0.5;
+        s.Cum(d) = 0.0 + lap_time;
+        s.Pk(d) = (pk & ~kAgeMask) | (age + 1u);
+    }
+    sort_by_time(s, n);
+    update_positions(s, n, false, e.dirty_thr);
+
+    // ================= retirements of laps 2..L (:190-197), drawn once per race: race_common.hip.h =================
+    {
+        uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
+        for (int d = 0; d < n; ++d) {
+            if ((d & 3) == 0)
+                philox4x32_10(c0, c1, 0u, kPurposeRetire | (uint32_t)(d >> 2), seed_lo, seed_hi, r0, r1, r2, r3);
+            const uint32_t rw = (d & 3) == 0 ? r0 : (d & 3) == 1 ? r1 : (d & 3) == 2 ? r2 : r3;
+            s.Out(d) = (uint16_t)draw_retirement_lap(rw, e.dnf[d], L);
+        }
+    }
+    return {2, 0};
+}
 
 // Race events of a lap, as run_laps hands them to its observer: the outcome of the short-circuit chain of :168-176.
 constexpr int kEventNone = 0, kEventRed = 1, kEventSc = 2, kEventVsc = 3;
@@ -445,12 +564,12 @@ __device__ __forceinline__ void classify_and_count(const Rows &s, int n, uint32_
     }
 }
 
-__global__ void __launch_bounds__(512)
-race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
-            uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist,
-            uint8_t *__restrict__ orders, const uint8_t *__restrict__ fixed_grid, uint32_t n_batches,
-            uint32_t * /*ticket: the register kernel's work counter; batches are dealt out by block index here*/,
-            uint32_t * /*retire_ws: the register kernel's retirement lists; an LDS row per driver here*/)
+// The block protocol of every race kernel of this family: the dynamic LDS is loaded (load_block), the block's batches
+// of blockDim.x simulations are dealt out by block index, grid-stride, lane(s, e, s_hist, local) runs simulation `local`
+// of the launch's n_sims in this lane's rows, and the block's u32 LDS histogram goes to hist [n][n] with u64 atomics.
+template <class Lane>
+__device__ __forceinline__ void run_block(const KParams *__restrict__ P, uint64_t n_sims, uint32_t n_batches,
+                                          unsigned long long *__restrict__ hist, Lane lane)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -459,31 +578,35 @@ race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
     Rows s;
     const LapEnv e = load_block(smem, P, s_hist, s);
     __syncthreads();
-    const int n = e.n;
-    const int L = e.L;
-    const int track = e.track;
 
     for (uint32_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
         const uint64_t local = (uint64_t)batch * (uint64_t)B + (uint64_t)tid;
         if (local >= n_sims) continue;      // tail lanes idle; no barrier inside the loop
-        const uint64_t sim = sim_offset + local;
-        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-
-#include "race_start.inc.h"
-
-        // ================= laps 2..L, reference :166-228 =================
-        NoLapObserver none;
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, 2, 0, none);
-
-        // ================= classification, reference :230-242 =================
-        classify_and_count(s, n, s_hist, orders ? orders + local * (uint64_t)n : nullptr);
+        lane(s, e, s_hist, local);
     }
 
     __syncthreads();
-    for (int i = tid; i < n * n; i += B) {
+    for (int i = tid; i < e.n * e.n; i += B) {
         const uint32_t c = s_hist[i];
         if (c) atomicAdd(&hist[i], (unsigned long long)c);
     }
+}
+
+__global__ void __launch_bounds__(512)
+race_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_offset,
+            uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist,
+            uint8_t *__restrict__ orders, const uint8_t *__restrict__ fixed_grid, uint32_t n_batches,
+            uint32_t * /*ticket: the register kernel's work counter; batches are dealt out by block index here*/,
+            uint32_t * /*retire_ws: the register kernel's retirement lists; an LDS row per driver here*/)
+{
+    run_block(P, n_sims, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
+        const uint64_t sim = sim_offset + local;
+        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
+        const RaceStart at = start_from_grid(s, e, c0, c1, seed_lo, seed_hi, fixed_grid);
+        NoLapObserver none;
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, none);        // reference :166-228
+        classify_and_count(s, e.n, s_hist, orders ? orders + local * (uint64_t)e.n : nullptr);      // reference :230-242
+    });
 }
 
 }  // namespace mcgp

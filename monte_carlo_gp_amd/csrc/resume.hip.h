@@ -35,6 +35,45 @@ struct ResumeState {
     int32_t drs_disabled_until;
 };
 
+// The start of one lane's race from a mid-race state: the rows, the field order, the DRS and dirty-air flags after lap
+// st.lap, and the retirement laps after it.
+__device__ __forceinline__ RaceStart start_from_state(const Rows &s, const LapEnv &e, const ResumeState &st, uint32_t c0,
+                                                      uint32_t c1, uint32_t seed_lo, uint32_t seed_hi)
+{
+    const int n = e.n, L = e.L;
+    const int k = st.lap;
+    const int drs_disabled_until = st.drs_disabled_until;
+
+    // ================= the state after lap k, as race_kernel leaves it =================
+    for (int d = 0; d < n; ++d) {
+        s.Cum(d) = st.cum[d];
+        s.Last(d) = st.last[d];
+        s.Pk(d) = st.pk[d];
+        s.Ord(d) = (uint8_t)d;
+    }
+    sort_by_time(s, n);
+    update_positions(s, n, k > 2 && k > drs_disabled_until, e.dirty_thr);
+
+    // ================= retirements after lap k: race_kernel's draw, redrawn where the state contradicts it =================
+    {
+        uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
+        for (int d = 0; d < n; ++d) {
+            if ((d & 3) == 0)
+                philox4x32_10(c0, c1, 0u, kPurposeRetire | (uint32_t)(d >> 2), seed_lo, seed_hi, r0, r1, r2, r3);
+            const uint32_t rw = (d & 3) == 0 ? r0 : (d & 3) == 1 ? r1 : (d & 3) == 2 ? r2 : r3;
+            uint32_t out = draw_retirement_lap(rw, e.dnf[d], L);
+            if (out != 0u && (int)out <= k && !(s.Pk(d) & kDnf)) {
+                uint32_t v0, v1, v2, v3;
+                philox4x32_10(c0, c1, 0u, kPurposeRetire | (8u + (uint32_t)(d >> 2)), seed_lo, seed_hi, v0, v1, v2, v3);
+                const uint32_t vw = (d & 3) == 0 ? v0 : (d & 3) == 1 ? v1 : (d & 3) == 2 ? v2 : v3;
+                out = draw_retirement_lap_after(vw, e.dnf[d], k, L);
+            }
+            s.Out(d) = (uint16_t)out;
+        }
+    }
+    return {k + 1, drs_disabled_until};
+}
+
 // n_sims simulations per state, ids states[s].sim_offset + sim_base + [0, n_sims); gridDim.y = number of states.
 // hist [states][n][n] is ACCUMULATED into; orders (NULL: none) = [states][n_sims][n].
 __global__ void __launch_bounds__(512)
@@ -42,42 +81,18 @@ race_resume_kernel(const KParams *__restrict__ P, const ResumeState *__restrict_
                    uint64_t sim_base, uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist,
                    uint8_t *__restrict__ orders, uint32_t n_batches)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int B = blockDim.x;
-    uint32_t *s_hist;
-    Rows s;
-    const LapEnv e = load_block(smem, P, s_hist, s);
-    __syncthreads();
-    const int n = e.n;
-    const int L = e.L;
-    const ResumeState &st = states[blockIdx.y];
-    const int k = st.lap;
-    const int drs_disabled_until = st.drs_disabled_until;
-
-    for (uint32_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
-        const uint64_t local = (uint64_t)batch * (uint64_t)B + (uint64_t)tid;
-        if (local >= n_sims) continue;      // tail lanes idle; no barrier inside the loop
-        const uint64_t sim = st.sim_offset + sim_base + local;
+    const uint32_t si = blockIdx.y;
+    const ResumeState *__restrict__ st = states + si;
+    run_block(P, n_sims, n_batches, hist + (size_t)si * (size_t)(P->n * P->n),
+              [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
+        const uint64_t sim = st->sim_offset + sim_base + local;
         const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-
-#include "resume_start.inc.h"
-
-        // ================= laps k+1..L, reference :166-228 =================
+        const RaceStart at = start_from_state(s, e, *st, c0, c1, seed_lo, seed_hi);
         NoLapObserver none;
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, k + 1, drs_disabled_until, none);
-
-        // ================= classification, reference :230-242 =================
-        classify_and_count(s, n, s_hist,
-                           orders ? orders + ((uint64_t)blockIdx.y * n_sims + local) * (uint64_t)n : nullptr);
-    }
-
-    __syncthreads();
-    unsigned long long *h = hist + (size_t)blockIdx.y * (size_t)(n * n);
-    for (int i = tid; i < n * n; i += B) {
-        const uint32_t c = s_hist[i];
-        if (c) atomicAdd(&h[i], (unsigned long long)c);
-    }
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, none);        // reference :166-228
+        classify_and_count(s, e.n, s_hist,                                                          // reference :230-242
+                           orders ? orders + ((uint64_t)si * n_sims + local) * (uint64_t)e.n : nullptr);
+    });
 }
 
 }  // namespace mcgp

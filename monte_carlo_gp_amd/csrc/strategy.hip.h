@@ -2,9 +2,9 @@
 //
 // race_strategy_kernel runs S scenarios of one race with common random numbers: simulation i of every scenario draws
 // what mcgp_run's (from the grid) or mcgp_run_from_state's (from a state) simulation i draws.  It is the generic kernel's
-// code -- race_start.inc.h or resume_start.inc.h, run_laps, classify_and_count -- with two hooks:
+// code -- start_from_grid or start_from_state, run_laps, classify_and_count -- with two hooks:
 //
-//   start   MCGP_START_OVERRIDE in race_start.inc.h: a planned driver's starting compound and age (grid runs only);
+//   start   a PlannedTyres hook for start_from_grid: a planned driver's starting compound and age (grid runs only);
 //   stops   a PlanPit policy for run_laps: a planned driver never takes the model's rule; on a lap of its plan it
 //           stops where the rule's stop would happen (after its lap time, before overtakes, only if still running).
 //
@@ -66,6 +66,17 @@ struct PlanPit {
     }
 };
 
+// start_from_grid's hook for one scenario: a planned driver's starting compound and age.
+struct PlannedTyres {
+    const StrategyScenario *__restrict__ sc;
+
+    __device__ __forceinline__ void operator()(uint32_t driver, uint32_t &comp, uint32_t &age) const
+    {
+        const uint32_t o = sc->start[driver];
+        if (o != kModelStart) { comp = o & 7u; age = o >> 3; }
+    }
+};
+
 // Simulations sim_offset + [0, m) of every scenario (gridDim.y = S), from the grid (kFromState false) or from `state`.
 // hist [S][n][n] is ACCUMULATED into; stage [S][m][n] is written (classified position of each driver).
 template <bool kFromState>
@@ -75,67 +86,22 @@ race_strategy_kernel(const KParams *__restrict__ P, const ResumeState *__restric
                      uint64_t sim_offset, uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist,
                      uint8_t *__restrict__ stage, uint32_t n_batches)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int B = blockDim.x;
-    uint32_t *s_hist;
-    Rows s;
-    const LapEnv e = load_block(smem, P, s_hist, s);
-    __syncthreads();
-    const int n = e.n;
-    const int L = e.L;
     const uint32_t sid = blockIdx.y;
     const StrategyScenario *__restrict__ sc = scen + sid;
-    PlanPit pit;
-    pit.laps = stop_laps + (size_t)sid * (size_t)(L + 1);
-    pit.planned = sc->planned;
-    pit.mask = 0u;
-    pit.lap = 0;
-
-    for (uint32_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
-        const uint64_t local = (uint64_t)batch * (uint64_t)B + (uint64_t)tid;
-        if (local >= m) continue;           // tail lanes idle; no barrier inside the loop
+    const PlanPit pit = {stop_laps + (size_t)sid * (size_t)(P->total_laps + 1), sc->planned, 0u, 0};
+    run_block(P, m, n_batches, hist + (size_t)sid * (size_t)(P->n * P->n),
+              [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
         const uint64_t sim = sim_offset + local;
         const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-        int first_lap = 2, dd = 0;
-
-        if constexpr (kFromState) {
-            const ResumeState &st = *state;
-            const int k = st.lap;
-            const int drs_disabled_until = st.drs_disabled_until;
-#include "resume_start.inc.h"
-            first_lap = k + 1;
-            dd = drs_disabled_until;
-        } else {
-            const int track = e.track;
-            const uint8_t *fixed_grid = nullptr;
-#undef MCGP_START_OVERRIDE
-#define MCGP_START_OVERRIDE(driver, comp, age)                                          \
-            {                                                                           \
-                const uint32_t o = sc->start[driver];                                   \
-                if (o != kModelStart) { comp = o & 7u; age = o >> 3; }                  \
-            }
-#include "race_start.inc.h"
-#undef MCGP_START_OVERRIDE
-#define MCGP_START_OVERRIDE(driver, comp, age)
-        }
-
-        // ================= laps first_lap..L with the scenario's stops, reference :166-228 =================
+        const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
+                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr, PlannedTyres{sc});
         NoLapObserver none;
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, first_lap, dd, none, pit);
-
-        // ================= classification, reference :230-242, and each driver's position =================
-        classify_and_count(s, n, s_hist, nullptr);
-        uint8_t *row = stage + ((uint64_t)sid * m + local) * (uint64_t)n;
-        for (int p = 0; p < n; ++p) row[s.Ord(p)] = (uint8_t)p;
-    }
-
-    __syncthreads();
-    unsigned long long *h = hist + (size_t)sid * (size_t)(n * n);
-    for (int i = tid; i < n * n; i += B) {
-        const uint32_t c = s_hist[i];
-        if (c) atomicAdd(&h[i], (unsigned long long)c);
-    }
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, none, pit);   // reference :166-228
+        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
+        // each driver's classified position
+        uint8_t *row = stage + ((uint64_t)sid * m + local) * (uint64_t)e.n;
+        for (int p = 0; p < e.n; ++p) row[s.Ord(p)] = (uint8_t)p;
+    });
 }
 
 // delta [S][n][2n - 1] += the staged positions' paired changes against scenario 0: for scenario s = blockIdx.y + 1 and

@@ -1,6 +1,6 @@
 // trace.hip.h -- what happened lap by lap in a race, counted on the device (mcgp_run_trace, include/mcgp.h).
 //
-// race_trace_kernel runs mcgp_run's simulations with the generic kernel's code -- race_start.inc.h for the grid and
+// race_trace_kernel runs mcgp_run's simulations with the generic kernel's code -- start_from_grid for the grid and
 // lap 1, run_laps for laps 2..L, classify_and_count -- and a per-lap observer (TraceObserver) that sees the rows after
 // update_positions of every lap, lap 1 included.  Simulation i draws exactly what race_kernel's simulation i draws, so
 // its position histogram is mcgp_run's.  Read at that point of lap k (the state the CPU oracle's per-lap trace records):
@@ -83,49 +83,25 @@ race_trace_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_o
                   uint32_t seed_hi, unsigned long long *__restrict__ hist, uint8_t *__restrict__ stage, uint64_t stride,
                   uint64_t *__restrict__ rec, uint32_t n_batches)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int B = blockDim.x;
-    uint32_t *s_hist;
-    Rows s;
-    const LapEnv e = load_block(smem, P, s_hist, s);
-    __syncthreads();
-    const int n = e.n;
-    const int L = e.L;
-    const int track = e.track;
-    const uint8_t *fixed_grid = nullptr;
-
-    for (uint32_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
-        const uint64_t local = (uint64_t)batch * (uint64_t)B + (uint64_t)tid;
-        if (local >= n_sims) continue;      // tail lanes idle; no barrier inside the loop
+    run_block(P, n_sims, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
         const uint64_t sim = sim_offset + local;
         const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-
-#include "race_start.inc.h"
+        const RaceStart at = start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr);
 
         TraceObserver obs;
         obs.lane = stage + local;
-        obs.lap_bytes = (uint64_t)n * stride;
+        obs.lap_bytes = (uint64_t)e.n * stride;
         obs.stride = stride;
-        obs.n = n;
+        obs.n = e.n;
         obs.best = __builtin_inf();
         obs.best_d = kNoFastest;
         obs.red = obs.sc = obs.vsc = 0u;
         obs(s, 1, kEventNone);
 
-        // ================= laps 2..L, reference :166-228 =================
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, 2, 0, obs);
-
-        // ================= classification, reference :230-242 =================
-        classify_and_count(s, n, s_hist, nullptr);
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, obs);         // reference :166-228
+        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
         rec[local] = (uint64_t)obs.best_d | ((uint64_t)obs.red << 16) | ((uint64_t)obs.sc << 32) | ((uint64_t)obs.vsc << 48);
-    }
-
-    __syncthreads();
-    for (int i = tid; i < n * n; i += B) {
-        const uint32_t c = s_hist[i];
-        if (c) atomicAdd(&hist[i], (unsigned long long)c);
-    }
+    });
 }
 
 // lap_pos [L n][n + 1] += the staged rows' counts: row r (= (lap - 1) n + driver) of m simulations, value v at

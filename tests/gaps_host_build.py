@@ -1,9 +1,7 @@
-"""Host DEBUGGING build of csrc/gaps.hip.h (tools/emu/emu_gaps.cpp): compile, load, run race_gaps_kernel<false / true>
-on the CPU and decode its raw staging by the layout documented at the top of gaps.hip.h.  Test infrastructure only -- the
-product (monte_carlo_gp_amd/) never imports this and has no CPU path."""
+"""Host DEBUGGING build of csrc/gaps.hip.h (tools/emu/emu_generic.cpp, kernel_host_build.generic_lib): run
+race_gaps_kernel<false / true> on the CPU and decode its raw staging by the layout documented at the top of gaps.hip.h.
+Test infrastructure only -- the product (monte_carlo_gp_amd/) never imports this and has no CPU path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
@@ -11,33 +9,7 @@ import gaps_ref as GR
 import kernel_host_build as KH
 import resume_ref as RR
 
-GAPS_LIB = os.path.join(KH.EMU_DIR, 'libmcgp_emu_gaps.so')
-GAPS_HEADERS = ('gaps.hip.h', 'race_kernel.hip.h', 'race_common.hip.h', 'race_start.inc.h', 'resume.hip.h',
-                'resume_start.inc.h', 'plan_pack.h', 'params_build.h', 'normal_table.h')
 FILL = 0xEE             # what the staging holds before the kernel runs (no staged value: 2B <= 128)
-
-_lib = None
-
-
-def build_gaps():
-    """tools/emu/libmcgp_emu_gaps.so (the flags of kernel_host_build.build_generic; rebuilt when a source it includes is
-    newer)."""
-    srcs = [os.path.join(KH.EMU_DIR, f) for f in ('emu_gaps.cpp', 'hip/hip_runtime.h')]
-    srcs += [os.path.join(KH.CSRC, f) for f in GAPS_HEADERS] + [os.path.join(KH.ROOT, 'include', 'mcgp.h')]
-    if not os.path.exists(GAPS_LIB) or os.path.getmtime(GAPS_LIB) < max(os.path.getmtime(s) for s in srcs):
-        tmp = f'{GAPS_LIB[:-3]}.tmp{os.getpid()}.so'             # (renamed into place: a parallel run never maps half a file)
-        subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-fno-fast-math', '-fPIC', '-shared',
-                               '-I' + KH.EMU_DIR, '-o', tmp, os.path.join(KH.EMU_DIR, 'emu_gaps.cpp')])
-        os.replace(tmp, GAPS_LIB)
-    return GAPS_LIB
-
-
-def gaps_lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build_gaps())
-        _lib.emu_gaps_run.restype = C.c_int
-    return _lib
 
 
 def values_from_staging(stage, m, n, L, n_edges, n_pairs, lap0=0):
@@ -61,7 +33,7 @@ def gaps_values(case, n_sims, seed, sim_offset=0, edges=GR.DEFAULT_EDGES, pairs=
     hist, err = np.zeros((n, n), np.uint64), C.c_char_p()
     stage = np.full((max((L - lap0) * R, 1), stride), FILL, np.uint8)
     cs = RR.c_state(*state) if state is not None else None
-    rc = gaps_lib().emu_gaps_run(C.byref(p.cfg), C.byref(p.drv), KH._vp(g) if state is None else None,
+    rc = KH.generic_lib().emu_gaps_run(C.byref(p.cfg), C.byref(p.drv), KH._vp(g) if state is None else None,
                                  C.byref(cs) if cs is not None else None, C.c_uint32(n), C.c_uint32(len(e)), KH._vp(e),
                                  C.c_uint32(len(pr)), KH._vp(pr) if len(pr) else None, C.c_uint64(n_sims),
                                  C.c_uint64(sim_offset), C.c_uint64(seed), KH._vp(hist), KH._vp(stage), C.c_uint64(stride),

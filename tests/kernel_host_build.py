@@ -1,6 +1,7 @@
 """Host DEBUGGING build of the kernel sources (tools/emu): compile, load, run.  Test infrastructure only --
 the product (monte_carlo_gp_amd/) never imports this and has no CPU path."""
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -84,16 +85,15 @@ class NotServed(Exception):
 
 # ---------------------------------------------------------------- the generic kernel family (tools/emu/emu_generic.cpp)
 GENERIC_LIB = os.path.join(EMU_DIR, 'libmcgp_emu_generic.so')
-GENERIC_HEADERS = ('race_kernel.hip.h', 'race_common.hip.h', 'race_start.inc.h', 'resume.hip.h', 'resume_start.inc.h',
-                   'trace.hip.h', 'strategy.hip.h', 'plan_pack.h', 'params_build.h', 'normal_table.h')
 TRACE_PIT, TRACE_POS_MASK = 0x80, 0x3F          # csrc/trace.hip.h: kTracePit, kTracePosMask
 
 
 def build_generic():
-    """tools/emu/libmcgp_emu_generic.so: race_kernel, race_resume_kernel, race_trace_kernel and race_strategy_kernel
-    compiled for the host (build()'s flags; rebuilt when a source it includes is newer)."""
+    """tools/emu/libmcgp_emu_generic.so: race_kernel, race_resume_kernel, race_trace_kernel, race_strategy_kernel and
+    race_gaps_kernel compiled for the host (build()'s flags; rebuilt when one of the product's headers, every csrc/*.h
+    and include/mcgp.h, is newer)."""
     srcs = [os.path.join(EMU_DIR, f) for f in ('emu_generic.cpp', 'hip/hip_runtime.h')]
-    srcs += [os.path.join(CSRC, f) for f in GENERIC_HEADERS] + [os.path.join(ROOT, 'include', 'mcgp.h')]
+    srcs += glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(ROOT, 'include', 'mcgp.h')]
     if not os.path.exists(GENERIC_LIB) or os.path.getmtime(GENERIC_LIB) < max(os.path.getmtime(s) for s in srcs):
         tmp = f'{GENERIC_LIB[:-3]}.tmp{os.getpid()}.so'          # (renamed into place: a parallel run never maps half a file)
         subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-fno-fast-math', '-fPIC', '-shared',
@@ -105,7 +105,7 @@ def build_generic():
 def generic_lib():
     if 'generic' not in _libs:
         L = C.CDLL(build_generic())
-        for f in ('emu_generic_run', 'emu_generic_resume', 'emu_generic_trace', 'emu_generic_strategy'):
+        for f in ('emu_generic_run', 'emu_generic_resume', 'emu_generic_trace', 'emu_generic_strategy', 'emu_gaps_run'):
             getattr(L, f).restype = C.c_int
         _libs['generic'] = L
     return _libs['generic']

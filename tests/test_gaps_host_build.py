@@ -1,4 +1,4 @@
-"""race_gaps_kernel<false> and <true> (csrc/gaps.hip.h) compiled for the host (tools/emu/emu_gaps.cpp) and compared,
+"""race_gaps_kernel<false> and <true> (csrc/gaps.hip.h) compiled for the host (tools/emu/emu_generic.cpp) and compared,
 integers only, with references that do not share its code: the raw staging, decoded by the layout documented at the top
 of gaps.hip.h, against gaps_ref's numpy restatement over the CPU oracle's per-lap trace; the histogram against the
 oracle's.  Inputs (generic_cases.py): the 8 golden cases, the 84 fuzz configurations, two fields with tiny lap times,

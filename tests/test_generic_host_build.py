@@ -1,5 +1,5 @@
 """The generic kernel family's SOURCE -- race_kernel, race_resume_kernel, race_trace_kernel, race_strategy_kernel<false>
-and <true>, i.e. load_block, race_start.inc.h, resume_start.inc.h, run_laps and classify_and_count -- compiled for the
+and <true>, i.e. run_block, start_from_grid, start_from_state, run_laps and classify_and_count -- compiled for the
 host (tools/emu/emu_generic.cpp) and compared bit for bit, integers only, with references that do not share its code:
 the CPU oracle's finishing orders and per-lap trace, trace_ref.trace_counts, and the Python restatement
 strategy_ref.orders (pinned to the oracle on the same configurations by test_strategy_host.py).

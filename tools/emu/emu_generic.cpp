@@ -1,7 +1,8 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
-// fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h
-// and strategy.hip.h with g++ through the stand-in <hip/hip_runtime.h> of this directory and calls the real
-// __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_strategy_kernel<false / true>.
+// fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
+// strategy.hip.h and gaps.hip.h with g++ through the stand-in <hip/hip_runtime.h> of this directory and calls the real
+// __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_strategy_kernel<false / true>,
+// race_gaps_kernel<false / true>.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -9,10 +10,12 @@
 // stand-in header is correct for a block of one thread); blockIdx.y (states, scenarios) is looped over here.  The
 // state and plan arguments go through csrc/plan_pack.h, the text the C ABI itself uses.
 //
-// Not run here: trace_count_positions (__shfl_down), the matchups kernel (__ballot), and trace_count_laps,
-// trace_count_records and strategy_count_deltas, whose loops are written for their fixed block of 256 threads (a
-// one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and records
-// in numpy instead; the counting kernels are compared on the device.  tests/test_generic_host_build.py.
+// Not run here: trace_count_positions and gaps_count_rows (__shfl_down), the matchups kernel (__ballot), and
+// trace_count_laps, trace_count_records and strategy_count_deltas, whose loops are written for their fixed block of 256
+// threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
+// records in numpy instead; the counting kernels are compared on the device.  tests/test_generic_host_build.py,
+// tests/test_gaps_host_build.py.
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -20,6 +23,7 @@
 #include "../../monte_carlo_gp_amd/csrc/params_build.h"
 #include "../../monte_carlo_gp_amd/csrc/trace.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/strategy.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/gaps.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/plan_pack.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -145,16 +149,42 @@ int emu_generic_strategy(const mcgp_config *cfg, const mcgp_drivers *drv, const 
                                                state != nullptr, &scen, &stop_laps);
     if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
     one_thread_block(n_scenarios);
+    const auto kernel = state ? &mcgp::race_strategy_kernel<true> : &mcgp::race_strategy_kernel<false>;
     for (uint32_t si = 0; si < n_scenarios; ++si) {
         blockIdx.y = si;
-        if (state)
-            mcgp::race_strategy_kernel<true>(&kp, &st, scen.data(), stop_laps.data(), n_sims, sim_offset, (uint32_t)seed,
-                                             (uint32_t)(seed >> 32), hist, positions, (uint32_t)n_sims);
-        else
-            mcgp::race_strategy_kernel<false>(&kp, &st, scen.data(), stop_laps.data(), n_sims, sim_offset, (uint32_t)seed,
-                                              (uint32_t)(seed >> 32), hist, positions, (uint32_t)n_sims);
+        kernel(&kp, &st, scen.data(), stop_laps.data(), n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist,
+               positions, (uint32_t)n_sims);
     }
     blockIdx.y = 0;
+    return MCGP_OK;
+}
+
+// race_gaps_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims).  hist [n][n] is
+// accumulated into; stage [(L - first_lap + 1) (n + 1 + n_pairs)][stride] (stride >= n_sims) is written.
+int emu_gaps_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                 uint32_t n, uint32_t n_edges, const double *edges, uint32_t n_pairs, const uint8_t *pairs, uint64_t n_sims,
+                 uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *stage, uint64_t stride,
+                 const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    if (n_edges < 1 || n_edges > mcgp::kMaxGapEdges || n_pairs > mcgp::kMaxGapPairs)
+        return fail(MCGP_E_BAD_ARG, "n_edges in [1, 63], n_pairs in [0, 64]", err);
+    if (stride < n_sims) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims", err);
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, cfg->total_laps, &st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    }
+    double table[mcgp::kGapEdgeSlots];                      // the call's edges, then +inf, as the C ABI uploads them
+    for (uint32_t i = 0; i < mcgp::kGapEdgeSlots; ++i) table[i] = i < n_edges ? edges[i] : HUGE_VAL;
+    one_thread_block(1);
+    const auto kernel = state ? &mcgp::race_gaps_kernel<true> : &mcgp::race_gaps_kernel<false>;
+    kernel(&kp, &st, table, n_edges, pairs, n_pairs, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
+           stride, (uint32_t)n_sims);
     return MCGP_OK;
 }
 
