@@ -375,6 +375,56 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
                       const uint8_t *pairs, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device,
                       uint64_t *hist_out, uint64_t *lap_gap_out, uint64_t *lead_out, uint64_t *pair_out);
 
+/* Combination and conditional odds: up to 64 conditions evaluated inside every simulation on its own finished race, from
+ * the grid or from a mid-race state; per condition the number of simulations that met it and the position histogram
+ * among those.  An atom holds in a simulation iff (lo <= value <= hi) != (negate != 0); a condition holds iff all of its
+ * atoms hold; a condition with zero atoms always holds.  Values are integers, read once per simulation after
+ * classification:
+ *   MCGP_FACT_POSITION(a)     classified position of driver a, 1 .. n (the race model's classification: retired cars
+ *                             behind the finishers, as everywhere else in this ABI)
+ *   MCGP_FACT_GRID(a)         grid slot of a, 1 .. n: the sampled slot from the grid, grid_slot[a] + 1 from a state
+ *   MCGP_FACT_RETIRED_LAP(a)  0 if a is running at the flag, else the lap on which it retired (lap 1 included; from a
+ *                             state also the state's own retired_lap of a car that is already out)
+ *   MCGP_FACT_AHEAD_BY(a, b)  POSITION(b) - POSITION(a), a != b: > 0 means a is classified ahead of b
+ *   MCGP_FACT_GAINED(a)       GRID(a) - POSITION(a)
+ *   MCGP_FACT_FINISHERS       the number of cars with RETIRED_LAP = 0
+ *   MCGP_FACT_RED_FLAGS / MCGP_FACT_SAFETY_CARS / MCGP_FACT_VSCS
+ *                             the number of laps whose event draw gave that event (the short-circuit chain, counted as
+ *                             mcgp_run_trace counts it): laps 2 .. L from the grid, laps state->lap + 1 .. L from a state
+ *                             (earlier events are not part of a state)
+ * a (and b) are ignored for the race-wide facts.  Bounds beyond a fact's range are legal: such an atom is always true or
+ * always false.
+ *   - simulations: from the grid (state NULL, grid_probs given) ids sim_offset .. sim_offset + n_sims - 1 with the draws
+ *     of mcgp_run's simulation i; from a state (grid_probs NULL, one mcgp_race_state) the draws and rules of
+ *     mcgp_run_from_state with sim_offsets[0] = sim_offset.
+ *   hist_out       [n][n]      [driver][position - 1]: equal to mcgp_run's / mcgp_run_from_state's for the same ids
+ *   count_out      [C]         the number of simulations in which condition c holds
+ *   cond_hist_out  [C][n][n]   [c][driver][position - 1] over those simulations, or NULL; every row of condition c sums
+ *                              to count_out[c]
+ * All are ACCUMULATED into (caller zeroes), and only after every launch has succeeded: on an error they are left as they
+ * were.  Every argument is checked before any device lookup (MCGP_E_BAD_ARG, the message names the condition, the atom
+ * and the field): what mcgp_run / mcgp_run_from_state check, grid_probs and state both or neither given, n_conditions
+ * outside [1, 64], conditions / hist_out / count_out NULL, n_atoms > 8, an unknown fact, a (or b, for AHEAD_BY) outside
+ * [0, n), a == b for AHEAD_BY, lo > hi, deviates other than MCGP_DEVIATES_32 (the generic kernel runs the call and has no
+ * 53-bit path).  n_sims == 0 succeeds without a device.  The device work goes chunk by chunk through a staging buffer of
+ * 256 MiB / (n + 8) simulations (per simulation the finishing order, n bytes, and one 64-bit mask of the conditions met;
+ * rounded down to a multiple of 256, then to whole rounds of the device's resident blocks, grid_blocks x block_threads of
+ * mcgp_last_launch_info, which after this call describes its first chunk's race launch) that a counting kernel reads;
+ * device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or devices sums to the same
+ * counts.  mcgp_last_kernel_ms afterwards = the device time of everything the call ran; mcgp_last_kernel_name =
+ * "mcgp::race_conditions_kernel". */
+#define MCGP_MAX_CONDITIONS 64
+#define MCGP_MAX_CONDITION_ATOMS 8
+enum { MCGP_FACT_POSITION = 0, MCGP_FACT_GRID = 1, MCGP_FACT_RETIRED_LAP = 2, MCGP_FACT_AHEAD_BY = 3,
+       MCGP_FACT_GAINED = 4, MCGP_FACT_FINISHERS = 5, MCGP_FACT_RED_FLAGS = 6, MCGP_FACT_SAFETY_CARS = 7,
+       MCGP_FACT_VSCS = 8 };
+typedef struct mcgp_condition_atom { int32_t fact, a, b, lo, hi, negate; } mcgp_condition_atom;
+typedef struct mcgp_condition { uint32_t n_atoms; mcgp_condition_atom atom[MCGP_MAX_CONDITION_ATOMS]; } mcgp_condition;
+int32_t mcgp_run_conditions(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                            const mcgp_race_state *state, uint32_t n, uint32_t n_conditions,
+                            const mcgp_condition *conditions, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                            int32_t device, uint64_t *hist_out, uint64_t *count_out, uint64_t *cond_hist_out);
+
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver
  * index classified p-th.  Bit-identical to what mcgp_run computes for a simulation

@@ -60,6 +60,11 @@ MAX_PLAN_STOPS = 8
 MAX_SCENARIOS = 64
 MAX_GAP_EDGES = 63          # include/mcgp.h: MCGP_MAX_GAP_EDGES, MCGP_MAX_GAP_PAIRS
 MAX_GAP_PAIRS = 64
+MAX_CONDITIONS = 64         # include/mcgp.h: MCGP_MAX_CONDITIONS, MCGP_MAX_CONDITION_ATOMS
+MAX_CONDITION_ATOMS = 8
+# include/mcgp.h: MCGP_FACT_*
+(FACT_POSITION, FACT_GRID, FACT_RETIRED_LAP, FACT_AHEAD_BY, FACT_GAINED, FACT_FINISHERS, FACT_RED_FLAGS, FACT_SAFETY_CARS,
+ FACT_VSCS) = range(9)
 
 
 class McgpPitPlan(C.Structure):
@@ -68,6 +73,17 @@ class McgpPitPlan(C.Structure):
         ('driver', C.c_int32), ('start_compound', C.c_int32), ('start_age', C.c_int32), ('n_stops', C.c_uint32),
         ('stop_lap', C.c_int16 * MAX_PLAN_STOPS), ('stop_compound', C.c_uint8 * MAX_PLAN_STOPS),
     ]
+
+
+class McgpConditionAtom(C.Structure):
+    """mcgp_condition_atom: holds iff (lo <= value <= hi) != (negate != 0)."""
+    _fields_ = [('fact', C.c_int32), ('a', C.c_int32), ('b', C.c_int32), ('lo', C.c_int32), ('hi', C.c_int32),
+                ('negate', C.c_int32)]
+
+
+class McgpCondition(C.Structure):
+    """mcgp_condition: the conjunction of its atoms (none: always true)."""
+    _fields_ = [('n_atoms', C.c_uint32), ('atom', McgpConditionAtom * MAX_CONDITION_ATOMS)]
 
 
 _hash_module = None
@@ -239,7 +255,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_simulate_race', 'mcgp_grid_probs', 'mcgp_run_from_ratings', 'mcgp_last_kernel_ms',
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
-           'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps')
+           'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -247,6 +263,12 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
 GAPS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
                  C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint64,
                  C.c_uint64, C.c_int32] + [C.POINTER(C.c_uint64)] * 4
+
+# mcgp_run_conditions(cfg, drv, grid_probs, state, n, n_conditions, conditions, n_sims, sim_offset, seed, device, hist_out,
+# count_out, cond_hist_out)
+CONDITIONS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
+                       C.c_uint32, C.c_uint32, C.POINTER(McgpCondition), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32] \
+    + [C.POINTER(C.c_uint64)] * 3
 
 
 def lib():
@@ -333,6 +355,9 @@ def lib():
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES
+        if 'mcgp_run_conditions' not in missing:
+            L.mcgp_run_conditions.restype = C.c_int32
+            L.mcgp_run_conditions.argtypes = CONDITIONS_ARGTYPES
         L.mcgp_last_kernel_ms.restype = C.c_int32
         L.mcgp_last_kernel_ms.argtypes = [C.c_int32, C.POINTER(C.c_float)]
         if 'mcgp_stream_kernel_ms' not in missing:

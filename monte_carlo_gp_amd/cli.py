@@ -18,6 +18,9 @@ predict --trace prints who leads after lap 1 and at the flag, laps led, fastest 
 (counted lap by lap on the device) and adds them to --json.  predict --gaps [--gap-edges 1,2,5] [--gap-pair VER:NOR]...
 (also on in-race) prints the winning margin, each driver's odds of finishing within about 1 s / 5 s / 20 s of the winner
 (the nearest edges present) and the named pairs' gaps (time gaps counted on the device) and adds a 'gaps' block to --json.
+predict --if TEXT (repeatable, also on in-race) evaluates the condition inside every simulation on the device
+(conditions.py: e.g. --if 'VER.wins & NOR.podium' --if 'sc>=1' --if 'LEC.pole'), prints its probability with the leading
+win odds given it beside the unconditional ones, and adds a 'conditions' block to --json.
 in-race runs the rest of the race from one or more mid-race state files (RaceState JSON, simulation.py); with several
 --state files every state sees the same random futures and the columns compare the scenarios.
 strategy compares pit strategies for one driver: `model` (the race model's own stops) first, then each --plan
@@ -76,6 +79,8 @@ def cmd_predict(args) -> int:
     extra = {'trace': True} if args.trace else {}
     if args.gaps:
         extra['gaps'] = gaps_argument(args)
+    if args.conditions:
+        extra['conditions'] = conditions_argument(args)
     res = F1Predictor(device=args.device).predict_weekend(
         args.season, args.race, fixture, prediction_point=args.prediction_point,
         n_simulations=args.simulations, seed=args.seed, matchups=args.matchups, **extra)
@@ -99,6 +104,8 @@ def cmd_predict(args) -> int:
         _print_trace(res)
     if args.gaps:
         _print_gaps(res['gaps'])
+    if args.conditions:
+        _print_conditions(res['conditions'])
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({k: v for k, v in res.items() if k != 'full_distributions'}, f)
@@ -146,6 +153,31 @@ def gaps_argument(args):
     if pairs:
         opt['pairs'] = pairs
     return opt or True
+
+
+def conditions_argument(args) -> dict:
+    """predict_weekend's / predict_from_state's conditions argument from the --if options: {text: text}."""
+    out = {}
+    for text in args.conditions or []:
+        name = text.strip()
+        if name in out:
+            raise SystemExit(f'error: --if {text!r} given twice')
+        out[name] = text
+    return out
+
+
+def _print_conditions(block, label='', top=3) -> None:
+    """--if: the block of a result's 'conditions' key (predictor.condition_keys)."""
+    print(f"\nCONDITIONS{label}\n" + '-' * 40)
+    for name, c in block.items():
+        print(f"{name}: {c['probability']:6.1%} +- {c['standard_error']:.1%}  ({c['count']} simulations)")
+        if not c['count']:
+            print('    never met: no conditional odds')
+            continue
+        win = c['win']
+        for d in sorted(win, key=lambda d: win[d]['given'], reverse=True)[:top]:
+            print(f"    {d:4} wins {win[d]['given']:6.1%} if so (overall {win[d]['unconditional']:6.1%})   "
+                  f"podium {c['podium'][d]['given']:6.1%} (overall {c['podium'][d]['unconditional']:6.1%})")
 
 
 GAP_MARKS = (1.0, 5.0, 20.0)         # seconds behind the winner that --gaps reports: the nearest edges present
@@ -206,6 +238,8 @@ def cmd_in_race(args) -> int:
         print(f"State {i + 1}: {path} (after lap {st.lap})")
     print('=' * 60 + '\n')
     extra = {'gaps': gaps_argument(args)} if args.gaps else {}
+    if args.conditions:
+        extra['conditions'] = conditions_argument(args)
     res = F1Predictor(device=args.device).predict_from_state(args.season, args.race, fixture, states,
                                                              n_simulations=args.simulations, seed=args.seed, **extra)
     drivers = list(res[0]['win_probabilities'])
@@ -219,6 +253,10 @@ def cmd_in_race(args) -> int:
     if args.gaps:
         for i, r in enumerate(res):
             _print_gaps(r['gaps'], label=f' (S{i + 1})' if len(res) > 1 else '')
+        print()
+    if args.conditions:
+        for i, r in enumerate(res):
+            _print_conditions(r['conditions'], label=f' (S{i + 1})' if len(res) > 1 else '')
         print()
     if args.json:
         with open(args.json, 'w') as f:
@@ -627,6 +665,9 @@ def main(argv=None) -> int:
                    help='with --gaps: the bin edges in seconds, comma-separated and increasing (default: 0.5 ... 120)')
     p.add_argument('--gap-pair', type=str, action='append', default=None,
                    help='with --gaps: a pair of drivers A:B whose gap is counted; repeat for more (at most 64)')
+    p.add_argument('--if', dest='conditions', metavar='TEXT', type=str, action='append', default=None,
+                   help="a condition evaluated inside every simulation, e.g. 'VER.wins & NOR.podium', 'sc>=1', 'LEC.pole': "
+                        'its probability and the odds given it (and in --json); repeat for more (at most 64)')
     p.set_defaults(fn=cmd_predict)
     b = sub.add_parser('backtest', help='sweep a season and score it (backtest.py of the reference)')
     b.add_argument('--seasons', type=int, nargs='+', default=[2024])
@@ -670,6 +711,9 @@ def main(argv=None) -> int:
                    help='with --gaps: the bin edges in seconds, comma-separated and increasing (default: 0.5 ... 120)')
     r.add_argument('--gap-pair', type=str, action='append', default=None,
                    help='with --gaps: a pair of drivers A:B whose gap is counted; repeat for more (at most 64)')
+    r.add_argument('--if', dest='conditions', metavar='TEXT', type=str, action='append', default=None,
+                   help="a condition evaluated inside every simulation, e.g. 'VER.wins & NOR.podium', 'sc>=1', 'LEC.pole': "
+                        'its probability and the odds given it (and in --json); repeat for more (at most 64)')
     r.set_defaults(fn=cmd_in_race)
     t = sub.add_parser('strategy', help="compare pit strategies for one driver against the model's own stops")
     t.add_argument('--season', type=int, default=2025)

@@ -15,6 +15,7 @@
 #include "trace.hip.h"
 #include "strategy.hip.h"
 #include "gaps.hip.h"
+#include "conditions.hip.h"
 #include "plan_pack.h"
 #include "champ_pack.h"
 
@@ -27,6 +28,7 @@
 
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -489,6 +491,8 @@ constexpr uint64_t kTraceStageBytes = 512ull << 20;
 constexpr uint64_t kStrategyStageBytes = 256ull << 20;
 // ... and of mcgp_run_gaps: one byte per recorded lap, row (n drivers + 1 lead + n_pairs pairs) and simulation.
 constexpr uint64_t kGapsStageBytes = 512ull << 20;
+// ... and of mcgp_run_conditions: per simulation the finishing order (n bytes) and one u64 mask of the conditions met.
+constexpr uint64_t kConditionsStageBytes = 256ull << 20;
 
 // Simulations in one chunk of such a staging: budget / bytes_per_sim, at most max_sims_per_launch(), in multiples of 256
 // when it can.
@@ -1732,6 +1736,112 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     });
     if (rc != MCGP_OK) return rc;
     counts.add_to({{hist_out, c_hist}, {lap_gap_out, c_gap}, {lead_out, c_lead}, {pair_out, c_pair}});
+    return MCGP_OK;
+}
+
+static_assert(sizeof(mcgp::CondAtom) == sizeof(mcgp_condition_atom) && sizeof(mcgp::Cond) == sizeof(mcgp_condition) &&
+                  offsetof(mcgp::Cond, atom) == offsetof(mcgp_condition, atom),
+              "the device's condition table is the C ABI's array as it is");
+static_assert(mcgp::kMaxConditions == MCGP_MAX_CONDITIONS && mcgp::kMaxConditionAtoms == MCGP_MAX_CONDITION_ATOMS &&
+                  mcgp::kFactCount == MCGP_FACT_VSCS + 1, "conditions.hip.h and mcgp.h state the same limits");
+
+int32_t mcgp_run_conditions(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                            const mcgp_race_state *state, uint32_t n, uint32_t n_conditions,
+                            const mcgp_condition *conditions, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                            int32_t device, uint64_t *hist_out, uint64_t *count_out, uint64_t *cond_hist_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+    if (!count_out) return fail(MCGP_E_BAD_ARG, "count_out is NULL");
+    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
+    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    if (n_conditions < 1 || n_conditions > mcgp::kMaxConditions) return fail(MCGP_E_BAD_ARG, "n_conditions must be in [1, 64]");
+    if (!conditions) return fail(MCGP_E_BAD_ARG, "conditions is NULL");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc == MCGP_OK) rc = check_deviates_32(kp, "conditions run");
+    if (rc != MCGP_OK) return rc;
+    for (uint32_t ci = 0; ci < n_conditions; ++ci) {
+        const mcgp_condition &cond = conditions[ci];
+        const std::string where = "conditions[" + std::to_string(ci) + "]";
+        if (cond.n_atoms > mcgp::kMaxConditionAtoms) return fail(MCGP_E_BAD_ARG, where + ".n_atoms must be in [0, 8]");
+        for (uint32_t k = 0; k < cond.n_atoms; ++k) {
+            const mcgp_condition_atom &at = cond.atom[k];
+            const std::string atom = where + ".atom[" + std::to_string(k) + "]";
+            if (at.fact < 0 || at.fact >= mcgp::kFactCount)
+                return fail(MCGP_E_BAD_ARG, atom + ".fact: unknown fact " + std::to_string(at.fact));
+            const bool per_driver = at.fact <= MCGP_FACT_GAINED;
+            if (per_driver && (at.a < 0 || at.a >= (int32_t)n))
+                return fail(MCGP_E_BAD_ARG, atom + ".a: driver index must be in [0, n)");
+            if (at.fact == MCGP_FACT_AHEAD_BY) {
+                if (at.b < 0 || at.b >= (int32_t)n) return fail(MCGP_E_BAD_ARG, atom + ".b: driver index must be in [0, n)");
+                if (at.a == at.b) return fail(MCGP_E_BAD_ARG, atom + ".b: AHEAD_BY needs two different drivers");
+            }
+            if (at.lo > at.hi) return fail(MCGP_E_BAD_ARG, atom + ".lo must not be above .hi");
+        }
+    }
+    const uint32_t L = (uint32_t)cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string err = mcgp::pack_race_state(*state, 0, n, (int)L, &st);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+        st.sim_offset = 0;          // (race_conditions_kernel takes the ids from its sim_offset argument)
+    }
+    if (n_sims == 0) return MCGP_OK;
+    const uint32_t C = n_conditions;
+    const size_t c_hist = (size_t)n * n, c_count = C, c_cond = cond_hist_out ? (size_t)C * n * n : 0;
+    const size_t cells = c_hist + c_count + c_cond;
+    Counts counts;
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        const auto kernel = state ? &mcgp::race_conditions_kernel<true> : &mcgp::race_conditions_kernel<false>;
+        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
+        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kConditionsStageBytes, (uint64_t)n + 8, n_sims);
+        // workspace: staging of one chunk, n rows of `stride` bytes (a multiple of 256) then `stride` u64 masks |
+        // parameter block | state | condition table | hist [n][n] | count [C] | cond_hist [C][n][n]
+        const uint64_t stride = (chunk + 255) / 256 * 256;
+        Layout ws;
+        const size_t o_stage = ws.add((size_t)(n + 8) * stride), o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st));
+        const size_t o_cond = ws.add(sizeof(mcgp::Cond) * C), o_cnt = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
+        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
+        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
+        const mcgp::Cond *d_cond = c.work.at<const mcgp::Cond>(o_cond);
+        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
+        unsigned long long *d_count = d_hist + c_hist, *d_chist = cond_hist_out ? d_count + c_count : nullptr;
+        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_cond), conditions, sizeof(mcgp::Cond) * C, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)c.lds_per_block));
+        const uint32_t groups = (C + mcgp::kCondGroup - 1) / mcgp::kCondGroup;
+        const uint64_t grid_cap = std::max<uint64_t>(1, (uint64_t)c.cu_count * 8 / groups);
+        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
+        for (uint64_t done = 0; done < n_sims; done += chunk) {
+            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+            // the race: the generic kernel's block shape and LDS
+            r = generic_geometry(c, geo_fn, "conditions", n, m, &grid, &block, &lds);
+            if (r != MCGP_OK) return r;
+            if (done == 0) { grid0 = grid; block0 = block; }
+            const uint64_t n_batches = (m + block - 1) / block;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_cond, C, m, sim_offset + done,
+                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, (uint32_t)n_batches);
+            HIP_TRY(hipGetLastError());
+            // its counts, before the next chunk overwrites the staging
+            const uint64_t tiles = (m + mcgp::kCondCountBlock - 1) / mcgp::kCondCountBlock;
+            hipLaunchKernelGGL(mcgp::conditions_count, dim3((uint32_t)std::min<uint64_t>(tiles, grid_cap), groups),
+                               dim3(mcgp::kCondCountBlock), 0, nullptr, d_stage, stride, m, n, C, d_count, d_chist);
+            HIP_TRY(hipGetLastError());
+        }
+        note_launch(c, grid0, block0, lds, "mcgp::race_conditions_kernel");     // the launch shape of the first (fullest) chunk
+        return counts.download(d_hist, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to({{hist_out, c_hist}, {count_out, c_count}, {cond_hist_out, c_cond}});
     return MCGP_OK;
 }
 

@@ -171,7 +171,8 @@ class F1Predictor:
 
     def predict_weekend(self, season: int, race: str, fixture: dict | str, grid_penalties=None, circuit_info=None,
                         prediction_point: str = 'fp2', actual_grid=None, n_simulations: int = 10000,
-                        seed: int | None = None, matchups: bool = False, trace: bool = False, gaps=None) -> dict:
+                        seed: int | None = None, matchups: bool = False, trace: bool = False, gaps=None,
+                        conditions=None) -> dict:
         """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU.
 
         matchups=True (not in the reference): the race runs through RaceSimulator.run_matchups -- the same simulations,
@@ -185,7 +186,12 @@ class F1Predictor:
 
         gaps=True, or {'edges': [...], 'pairs': [(a, b), ...]} (not in the reference): the race also runs through
         RaceSimulator.run_gaps -- the same simulations once more -- and the result gains 'gaps', the block gap_keys
-        builds: the winning-margin distribution, each driver's finishing-gap distribution and the requested pairs."""
+        builds: the winning-margin distribution, each driver's finishing-gap distribution and the requested pairs.
+
+        conditions={name: text} (not in the reference; the grammar is in conditions.py): the race also runs through
+        RaceSimulator.run_conditions -- the same simulations -- and the result gains 'conditions', the block
+        condition_keys builds: per name the probability, its standard error and the win / podium odds given the
+        condition beside the unconditional ones."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -196,20 +202,20 @@ class F1Predictor:
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
             # same inputs, the matrix built on the device from the ratings (no host matrix crosses PCIe)
             ratings = {d: self.elo_system.ratings.get(d, {}).get('quali', self.elo_system.initial) for d in inp['drivers']}
-            if matchups or trace or gaps:
+            if matchups or trace or gaps or conditions:
                 # the same matrix, read back from the device front end and handed to the matchups / trace / gaps run
                 grid = sim.grid_probs_on_device(inp['drivers'], ratings, fixture.get('quali_features', {}),
                                                 grid_penalties or {})
                 return self._with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups,
-                                         trace, gaps)
+                                         trace, gaps, conditions)
             race_probs, grid = sim.run_from_ratings(
                 n_simulations, inp['drivers'], ratings, fixture.get('quali_features', {}), grid_penalties or {},
                 inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'], seed=seed,
                 track_condition=inp['track_condition'])
             return pack_result(inp['drivers'], grid, race_probs, inp['weather'], prediction_point, actual_grid)
-        if matchups or trace or gaps:
+        if matchups or trace or gaps or conditions:
             return self._with_counts(sim, inp, inp['grid_probs'], n_simulations, seed, prediction_point, actual_grid,
-                                     matchups, trace, gaps)
+                                     matchups, trace, gaps, conditions)
         race_probs = sim.run_monte_carlo(
             n_simulations=n_simulations, grid_probs=inp['grid_probs'], base_pace=inp['base_pace'],
             tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
@@ -217,12 +223,14 @@ class F1Predictor:
         return pack_result(inp['drivers'], inp['grid_probs'], race_probs, inp['weather'], prediction_point, actual_grid)
 
     def predict_from_state(self, season: int, race: str, fixture: dict | str, state, n_simulations: int = 100000,
-                           seed: int | None = None, gaps=None):
+                           seed: int | None = None, gaps=None, conditions=None):
         """In-race odds (not in the reference): the weekend's race inputs (simulator_inputs, as predict_weekend builds
         them) run from a mid-race RaceState of the fixture's drivers -- or from each of a list of them, with common
         random numbers -- through RaceSimulator.run_from_state.  Returns, per state, {'lap', 'win_probabilities', 'podium_probabilities',
         'points_probabilities' (top 10), 'full_distributions'}: one dict, or a list for a list of states.  gaps (as in
-        predict_weekend): every state's dict gains 'gaps' from RaceSimulator.run_gaps on that state, same simulations."""
+        predict_weekend): every state's dict gains 'gaps' from RaceSimulator.run_gaps on that state, same simulations.
+        conditions (as in predict_weekend): every state's dict gains 'conditions' from RaceSimulator.run_conditions on
+        that state, same simulations; race events count from the state's lap on."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -232,7 +240,7 @@ class F1Predictor:
         states = [state] if single else list(state)
         inp = self.simulator_inputs(fixture, race)
         sim = RaceSimulator(inp['config'], device=self.device)
-        seed = sim._resolve_seed(seed) if gaps else seed
+        seed = sim._resolve_seed(seed) if gaps or conditions else seed
         # the driver order of predict_weekend's run: a state that run's simulation i reached continues as simulation i
         probs = sim.run_from_state(n_simulations, states, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
                                    inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'],
@@ -249,6 +257,12 @@ class F1Predictor:
                                  inp['driver_dnf_rates'], state=st, seed=seed, track_condition=inp['track_condition'],
                                  drivers=list(inp['grid_probs']), **gap_options(gaps))
                 res['gaps'] = gap_keys(g)
+        if conditions:
+            for st, res in zip(states, out):
+                c = sim.run_conditions(n_simulations, conditions, None, inp['base_pace'], inp['tire_deg'],
+                                       inp['driver_variance'], inp['driver_dnf_rates'], state=st, seed=seed,
+                                       track_condition=inp['track_condition'], drivers=list(inp['grid_probs']))
+                res['conditions'] = condition_keys(c)
         return out[0] if single else out
 
     def predict_strategies(self, season: int, race: str, fixture: dict | str, strategies: dict, state=None,
@@ -273,9 +287,9 @@ class F1Predictor:
 
     @staticmethod
     def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace,
-                     gaps=None) -> dict:
-        """predict_weekend's result from run_matchups, run_trace and / or run_gaps calls on `grid` (the same simulations:
-        one seed for all), with their keys added."""
+                     gaps=None, conditions=None) -> dict:
+        """predict_weekend's result from run_matchups, run_trace, run_gaps and / or run_conditions calls on `grid` (the
+        same simulations: one seed for all), with their keys added."""
         args = (n_simulations, grid, inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'])
         seed = sim._resolve_seed(seed)
         res = None
@@ -295,6 +309,14 @@ class F1Predictor:
                 res = pack_result(inp['drivers'], grid, g.position_probabilities, inp['weather'], prediction_point,
                                   actual_grid)
             res['gaps'] = gap_keys(g)
+        if conditions:
+            c = sim.run_conditions(n_simulations, conditions, grid, inp['base_pace'], inp['tire_deg'],
+                                   inp['driver_variance'], inp['driver_dnf_rates'], seed=seed,
+                                   track_condition=inp['track_condition'])
+            if res is None:
+                res = pack_result(inp['drivers'], grid, c.position_probabilities(), inp['weather'], prediction_point,
+                                  actual_grid)
+            res['conditions'] = condition_keys(c)
         return res
 
 
@@ -324,6 +346,13 @@ def trace_keys(t) -> dict:
         'fastest_lap_probabilities': t.fastest_lap_probabilities,
         'race_event_probabilities': t.event_probabilities,
     }
+
+
+def condition_keys(c) -> dict:
+    """The 'conditions' block predict_weekend(conditions=...) / predict_from_state(conditions=...) add, JSON-safe, from a
+    ConditionResult: {name: {'probability', 'standard_error', 'count', 'win': {driver: {'given', 'unconditional'}},
+    'podium': the same}}; 'given' is None where no simulation met the condition."""
+    return c.summary()
 
 
 def gap_options(gaps) -> dict:

@@ -685,6 +685,76 @@ class RaceSimulator:
         self.last_drivers = drivers
         return res
 
+    def run_conditions(
+        self,
+        n_simulations: int,
+        conditions: dict,
+        grid_probs: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        histograms: bool = True,
+    ) -> 'ConditionResult':
+        """Combination and conditional odds (include/mcgp.h: mcgp_run_conditions): `conditions` = {name: text or
+        Condition} (1 to 64; the grammar is in conditions.py), each evaluated on the device inside every simulation.
+        Counted per condition: the simulations that met it and, unless histograms is False (the result's cond_hist is
+        then None and it has no conditional odds to give), the position histogram among those.  From the grid (grid_probs: run_monte_carlo's simulations) or from a mid-race RaceState (state:
+        run_from_state's simulations; race events count from the state's lap on).  The ConditionResult's position
+        histogram equals that call's.  32-bit deviates only; same seed rules and device sharding as run_monte_carlo.
+        Sets last_histogram / last_drivers."""
+        from . import conditions as CD
+        if (grid_probs is None) == (state is None):
+            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
+        if drivers is None:
+            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
+        drivers = [str(d) for d in drivers]
+        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
+            raise ValueError('drivers must be the keys of grid_probs')
+        parsed = CD.parse_all(conditions, drivers)
+        names = list(parsed)
+        n, L, K = len(drivers), int(self.config.total_laps), len(names)
+        n_simulations = int(n_simulations)
+
+        def result(hist, count, cond_hist):
+            return CD.ConditionResult(drivers=drivers, names=names, n_simulations=max(n_simulations, 0), hist=hist,
+                                      counts={k: int(c) for k, c in zip(names, count)}, cond_hist=cond_hist)
+
+        if not drivers or n_simulations <= 0:
+            res = result(np.zeros((n, n), np.int64), np.zeros(K, np.int64),
+                         np.zeros((K, n, n), np.int64) if histograms else None)
+            self.last_histogram, self.last_drivers = res.hist, drivers
+            return res
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        arrays = state.arrays(drivers, L) if state is not None else None
+        c_state = state.c_struct(arrays) if state is not None else None
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
+        table = CD.c_array(parsed)
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            out = (np.zeros((n, n), np.uint64), np.zeros(K, np.uint64),
+                   np.zeros((K, n, n), np.uint64) if histograms else None)
+            rc = lib.mcgp_run_conditions(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
+                                         C.byref(c_state) if c_state is not None else None, n, K, table, int(count),
+                                         int(sim_offset) + int(offset), seed64, device, u64(out[0]), u64(out[1]),
+                                         u64(out[2]) if histograms else None)
+            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([r[k] for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        res = result(total(0), total(1), total(2) if histograms else None)
+        self.last_histogram = res.hist
+        self.last_drivers = drivers
+        return res
+
     def simulate_race(
         self,
         grid: list,

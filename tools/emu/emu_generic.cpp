@@ -1,8 +1,8 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
 // fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
-// strategy.hip.h and gaps.hip.h with g++ through the stand-in <hip/hip_runtime.h> of this directory and calls the real
-// __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_strategy_kernel<false / true>,
-// race_gaps_kernel<false / true>.
+// strategy.hip.h, gaps.hip.h and conditions.hip.h with g++ through the stand-in <hip/hip_runtime.h> of this directory and
+// calls the real __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_strategy_kernel<false /
+// true>, race_gaps_kernel<false / true>, race_conditions_kernel<false / true>, conditions_count.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -13,8 +13,9 @@
 // Not run here: trace_count_positions and gaps_count_rows (__shfl_down), the matchups kernel (__ballot), and
 // trace_count_laps, trace_count_records and strategy_count_deltas, whose loops are written for their fixed block of 256
 // threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
-// records in numpy instead; the counting kernels are compared on the device.  tests/test_generic_host_build.py,
-// tests/test_gaps_host_build.py.
+// records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
+// operation and strides by its block's size, so it does run here, as blocks of one thread.
+// tests/test_generic_host_build.py, tests/test_gaps_host_build.py, tests/test_conditions_host_build.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -24,6 +25,7 @@
 #include "../../monte_carlo_gp_amd/csrc/trace.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/strategy.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/gaps.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/conditions.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/plan_pack.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -185,6 +187,46 @@ int emu_gaps_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *
     const auto kernel = state ? &mcgp::race_gaps_kernel<true> : &mcgp::race_gaps_kernel<false>;
     kernel(&kp, &st, table, n_edges, pairs, n_pairs, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
            stride, (uint32_t)n_sims);
+    return MCGP_OK;
+}
+
+// race_conditions_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims).  hist [n][n]
+// is accumulated into; stage ([n][stride] bytes, then [stride] u64 masks; stride >= n_sims, a multiple of 8) is written.
+// count [C] and cond_hist [C][n][n] (or NULL) are accumulated into by conditions_count, run as grid_x x ceil(C / 8) blocks
+// of one thread (count NULL: not run).
+int emu_conditions_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                       const mcgp_race_state *state, uint32_t n, uint32_t n_conditions, const mcgp_condition *conditions,
+                       uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *stage,
+                       uint64_t stride, unsigned long long *count, unsigned long long *cond_hist, uint32_t grid_x,
+                       const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    if (n_conditions < 1 || n_conditions > mcgp::kMaxConditions) return fail(MCGP_E_BAD_ARG, "n_conditions in [1, 64]", err);
+    if (stride < n_sims || stride % 8) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims and a multiple of 8", err);
+    static_assert(sizeof(mcgp::Cond) == sizeof(mcgp_condition), "the table is the C ABI's array");
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, cfg->total_laps, &st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    }
+    one_thread_block(1);
+    const auto kernel = state ? &mcgp::race_conditions_kernel<true> : &mcgp::race_conditions_kernel<false>;
+    kernel(&kp, &st, reinterpret_cast<const mcgp::Cond *>(conditions), n_conditions, n_sims, sim_offset, (uint32_t)seed,
+           (uint32_t)(seed >> 32), hist, stage, stride, (uint32_t)n_sims);
+    if (count) {
+        const uint32_t groups = (n_conditions + mcgp::kCondGroup - 1) / mcgp::kCondGroup;
+        gridDim = {grid_x, groups, 1};
+        for (uint32_t y = 0; y < groups; ++y)
+            for (uint32_t x = 0; x < grid_x; ++x) {
+                blockIdx = {x, y, 0};
+                mcgp::conditions_count(stage, stride, n_sims, n, n_conditions, count, cond_hist);
+            }
+        one_thread_block(1);
+    }
     return MCGP_OK;
 }
 
