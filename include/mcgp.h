@@ -33,7 +33,8 @@ extern "C" {
 /* 4: mcgp_run_matchups */
 /* 5: mcgp_race_state, mcgp_run_from_state */
 /* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
- * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way */
+ * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
+ * mcgp_run_championship_rounds likewise */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -189,6 +190,51 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
                               const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
                               uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
                               uint64_t *gain_hist, uint64_t *race_hist);
+
+/* Championship by round: mcgp_run_championship, and the standings after EVERY race of the call.  Every argument through
+ * race_hist is mcgp_run_championship's, same order and meaning, and champ_hist, team_hist, gain_hist and race_hist equal
+ * what that call gives for the same arguments.
+ *
+ * Definitions.  R races, n drivers, T teams, points[r][p] as above.  "After race r" (r = 0..R-1) means the initial
+ * standings plus races 0..r of the call.  Ranking is the existing one, for drivers and for teams: points, then
+ * countback, then the lower index.
+ *   - Standings position after race r: the rank of the entrant by that rule among the keys after race r.
+ *   - Leader: the entrant in position 0.  It has the most points; `lead` is its points.
+ *   - Remaining points.  For a driver: M_r = sum over q > r of max_p points[q][p].  For team e with m_e drivers:
+ *     B_r(e) = sum over q > r of (the sum of the m_e largest entries of points[q][0..n)).  Both are 0 for r = R-1.  The
+ *     host computes them.
+ *   - In contention after race r.  The leader is always in contention.  For r < R-1, any other driver d with
+ *     lead - pts_d <= M_r is in contention.  For teams the test is lead - pts_e <= B_r(e).  The bound is inclusive.  A
+ *     driver who can draw level on points is still in, because the countback of races not yet run could go their way.
+ *     After the last race only the leader is in contention.
+ *   - Secure after race r: the entrant is the only one in contention.  The bound is the conventional sufficient one.
+ *     It ignores that two entrants cannot both take a race's maximum.  Whoever is secure at r is the final champion,
+ *     because points are >= 0.  Once secure, an entrant stays secure.  That follows from the two properties:
+ *     secure[r][d] is non-decreasing in r, and secure[R-1][d] = champ_hist[d][0].  The clinch-round distribution is
+ *     therefore the difference of consecutive rows.  No per-simulation state has to survive between races.  A title
+ *     that is already secure before race 0 shows in row 0.
+ *
+ * Outputs, ACCUMULATED into (caller zeroes), and only after every launch has succeeded: a call that fails leaves all of
+ * them untouched.
+ *   round_hist        [R][n][n]  [race][driver][standings position]; required
+ *   contend_out       [R][n]     simulations with the driver in contention after race r; required
+ *   secure_out        [R][n]     simulations with the driver's title secure after race r; required
+ *   team_round_hist   [R][T][T]  \
+ *   team_contend_out  [R][T]      > the same for the teams: all three given or all three NULL
+ *   team_secure_out   [R][T]     /
+ * The limits and argument checks are mcgp_run_championship's, made before any device lookup; a NULL round_hist,
+ * contend_out or secure_out, or a partly given team trio, is MCGP_E_BAD_ARG and the message names the argument.  A
+ * per-round standings kernel runs after every race of a chunk on the keys as they then stand (csrc/champ_rounds.hip.h);
+ * device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or devices sums to the same
+ * counts.  mcgp_last_kernel_ms afterwards = the device time of the whole call. */
+int32_t mcgp_run_championship_rounds(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                                     const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                                     const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                                     const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                                     uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                                     uint64_t *gain_hist, uint64_t *race_hist, uint64_t *round_hist, uint64_t *contend_out,
+                                     uint64_t *secure_out, uint64_t *team_round_hist, uint64_t *team_contend_out,
+                                     uint64_t *team_secure_out);
 
 /* Head-to-head and podium-combination counts of one race: mcgp_run's inputs and simulations (ids sim_offset ..
  * sim_offset + n_sims - 1), counted on the device so that no finishing order leaves it.  "Classified" is the race model's

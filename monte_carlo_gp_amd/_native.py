@@ -255,7 +255,8 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_simulate_race', 'mcgp_grid_probs', 'mcgp_run_from_ratings', 'mcgp_last_kernel_ms',
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
-           'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions')
+           'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
+           'mcgp_run_championship_rounds')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -330,6 +331,10 @@ def lib():
             L.mcgp_run_championship.argtypes = [C.c_uint32, C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(dp),
                                                 C.c_uint32, C.c_uint64, C.c_uint64, u64p, ip, C.POINTER(C.c_uint8), ip, ip,
                                                 ip, C.c_uint32, C.c_int32, u64p, u64p, u64p, u64p]
+        if 'mcgp_run_championship_rounds' not in missing:
+            # mcgp_run_championship's arguments, then round_hist, contend_out, secure_out and the teams' three
+            L.mcgp_run_championship_rounds.restype = C.c_int32
+            L.mcgp_run_championship_rounds.argtypes = L.mcgp_run_championship.argtypes + [C.POINTER(C.c_uint64)] * 6
         if 'mcgp_run_matchups' not in missing:
             u64p = C.POINTER(C.c_uint64)
             L.mcgp_run_matchups.restype = C.c_int32

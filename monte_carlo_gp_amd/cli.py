@@ -610,7 +610,7 @@ def cmd_championship(args) -> int:
     races = championship_races(jobs, args.device)
     t0 = time.perf_counter()
     res = run_championship(races, args.simulations, standings=standings, device=args.device,
-                           return_race_histograms=True)
+                           return_race_histograms=True, by_round=args.by_round)
     dt = time.perf_counter() - t0
     partial = args.from_round > 1 and not standings
     what = f'points from round {args.from_round} on' if partial else 'season standings'
@@ -625,6 +625,15 @@ def cmd_championship(args) -> int:
     print(f'EXPECTED POINTS ({what})\n' + '-' * 40)
     for i, (d, p) in enumerate(sorted(exp.items(), key=lambda kv: kv[1], reverse=True)[:10], 1):
         print(f'{i:2}. {d:4} {p:7.1f}')
+    if args.by_round:
+        print(f'\nBY ROUND ({what})\n' + '-' * 40)
+        print(f"{'round':>5}  {'race':<22} {'decided':>8}  {'in contention':>13}  leaders")
+        rows = zip(jobs, res.decided_by_round, res.leader_probabilities_by_round, res.contention_probabilities_by_round)
+        for k, ((_, entry, _, _), decided, lead, cont) in enumerate(rows):
+            top = sorted(lead.items(), key=lambda kv: kv[1], reverse=True)[:3]
+            print(f"{args.from_round + k:>5}  {str(entry['race'])[:22]:<22} {decided * 100:7.1f}%  "
+                  f"{sum(1 for v in cont.values() if v > 0.01):>13}  "
+                  + '  '.join(f'{d} {v * 100:.1f}%' for d, v in top if v > 0))
     if args.json:
         n = res.n_simulations
         out = dict(season=args.season, from_round=args.from_round, points_from_round_only=partial,
@@ -635,6 +644,13 @@ def cmd_championship(args) -> int:
                    races=[dict(race=entry['race'], seed=race_seed,
                                win_probabilities={d: int(h[i, 0]) / n for i, d in enumerate(res.drivers)})
                           for (_, entry, race_seed, _), h in zip(jobs, res.race_histograms)])
+        if args.by_round:
+            # one entry per simulated round, in race order (index 0 = round --from-round)
+            for key in ('decided_by_round', 'leader_probabilities_by_round', 'contention_probabilities_by_round',
+                        'clinch_round_probabilities', 'constructor_decided_by_round',
+                        'constructor_leader_probabilities_by_round', 'constructor_contention_probabilities_by_round',
+                        'constructor_clinch_round_probabilities'):
+                out[key] = getattr(res, key)
         with open(args.json, 'w') as f:
             json.dump(out, f)
     return 0
@@ -692,6 +708,9 @@ def main(argv=None) -> int:
     c.add_argument('--seed', type=int, default=42)
     c.add_argument('--device', type=int, default=0)
     c.add_argument('--json', type=str, default=None)
+    c.add_argument('--by-round', action='store_true',
+                   help='also count the standings after every round: P(title decided by then), the likeliest leaders, '
+                        'the drivers still in contention (and add the tables to --json)')
     c.set_defaults(fn=cmd_championship)
     r = sub.add_parser('in-race', help='win and podium odds from a mid-race state (one column per --state)')
     r.add_argument('--season', type=int, default=2025)

@@ -2,7 +2,8 @@
 // two standings kernels read -- the teams' members, the initial keys, the key increment of every race and position.
 // Plain C++, no device code: mcgp_hip.hip includes it for the C ABI, and the host debugging build of the standings
 // kernels (tools/emu/emu_champ.cpp) includes the same text, so that what a test packs on the CPU is what the library
-// packs.  The argument checks (and G, awarded, n_cb, which they compute) stay with the C ABI.
+// packs.  The argument checks (and G, awarded, n_cb, which they compute) stay with the C ABI.  champ_remaining builds
+// the remaining-points tables of mcgp_run_championship_rounds (champ_rounds.hip.h).
 #pragma once
 #include "championship.hip.h"
 
@@ -87,6 +88,30 @@ inline std::string pack_championship(uint32_t n_races, uint32_t n, const int32_t
     out->add = std::move(add);
     out->init_pts = std::move(init_pts);
     return "";
+}
+
+// The points still to be had after race r (include/mcgp.h, "Remaining points"): for a driver M_r = the sum over the
+// later races q of the largest entry of points[q]; for a team of m drivers B_r = the sum over q of the m largest
+// entries of points[q].  driver_rem: [R]; team_rem: [R][T], n_members [T] as pack_championship gives it.  Both are 0
+// in the last row.
+inline void champ_remaining(uint32_t n_races, uint32_t n, const int32_t *points, const uint8_t *n_members, uint32_t n_teams,
+                            std::vector<uint32_t> *driver_rem, std::vector<uint32_t> *team_rem)
+{
+    driver_rem->assign(n_races, 0);
+    team_rem->assign((size_t)n_races * n_teams, 0);
+    std::vector<uint32_t> best(n + 1, 0);           // best[k]: the k largest entries of the races after r, summed
+    std::vector<int32_t> row(n);
+    for (uint32_t r = n_races; r-- > 0;) {
+        (*driver_rem)[r] = best[1];
+        for (uint32_t t = 0; t < n_teams; ++t) (*team_rem)[(size_t)r * n_teams + t] = best[n_members[t]];
+        std::copy(points + (size_t)r * n, points + (size_t)(r + 1) * n, row.begin());
+        std::sort(row.begin(), row.end(), [](int32_t a, int32_t b) { return a > b; });
+        uint32_t sum = 0;
+        for (uint32_t k = 1; k <= n; ++k) {
+            sum += (uint32_t)row[k - 1];
+            best[k] += sum;
+        }
+    }
 }
 
 }  // namespace mcgp

@@ -10,6 +10,7 @@
 #include "race_kernel.hip.h"
 #include "race_kernel_reg.hip.h"
 #include "championship.hip.h"
+#include "champ_rounds.hip.h"
 #include "matchups.hip.h"
 #include "resume.hip.h"
 #include "trace.hip.h"
@@ -1148,14 +1149,29 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
     return MCGP_OK;
 }
 
-int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
-                              const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
-                              const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
-                              const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
-                              uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
-                              uint64_t *gain_hist, uint64_t *race_hist)
+// The per-round outputs of mcgp_run_championship_rounds (NULL for mcgp_run_championship: no per-round kernel runs).
+struct ChampRoundsOut {
+    uint64_t *round_hist, *contend, *secure, *team_round_hist, *team_contend, *team_secure;
+};
+
+// mcgp_run_championship (rounds == NULL) and mcgp_run_championship_rounds: one body, so that the four season outputs of
+// the two calls come from the same launches.
+static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                                const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                                const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                                const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                                uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                                uint64_t *gain_hist, uint64_t *race_hist, const ChampRoundsOut *rounds)
 {
     // ---- every argument is checked before any device is looked up
+    if (rounds) {
+        if (!rounds->round_hist) return fail(MCGP_E_BAD_ARG, "round_hist is NULL");
+        if (!rounds->contend) return fail(MCGP_E_BAD_ARG, "contend_out is NULL");
+        if (!rounds->secure) return fail(MCGP_E_BAD_ARG, "secure_out is NULL");
+        const int given = (rounds->team_round_hist != nullptr) + (rounds->team_contend != nullptr) + (rounds->team_secure != nullptr);
+        if (given != 0 && given != 3)
+            return fail(MCGP_E_BAD_ARG, "team_round_hist, team_contend_out and team_secure_out must be all given or all NULL");
+    }
     if (!cfgs || !drvs || !grid_probs || !seeds || !points || !countback || !team || !champ_hist || !team_hist ||
         !gain_hist)
         return fail(MCGP_E_BAD_ARG, "a championship array is NULL");
@@ -1213,7 +1229,15 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
     const std::vector<int32_t> &init_pts = pk.init_pts;
     const size_t champ_cells = (size_t)n * n, team_cells = (size_t)n_teams * n_teams, gain_cells = (size_t)n * gain_cols;
     const size_t race_cells = race_hist ? (size_t)n_races * n * n : 0;
-    const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells;
+    // per round: [R][n][n] | [R][n] | [R][n], then the same three for the teams (behind the season's histograms)
+    const bool round_teams = rounds && rounds->team_round_hist;
+    const uint32_t round_T = round_teams ? n_teams : 0;
+    const size_t rh_cells = rounds ? (size_t)n_races * n * n : 0, rc_cells = rounds ? (size_t)n_races * n : 0;
+    const size_t trh_cells = (size_t)n_races * round_T * round_T, trc_cells = (size_t)n_races * round_T;
+    const size_t round_cells = rh_cells + 2 * rc_cells + trh_cells + 2 * trc_cells;
+    const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells + round_cells;
+    std::vector<uint32_t> driver_rem, team_rem;
+    if (rounds) mcgp::champ_remaining(n_races, n, points, n_members.data(), n_teams, &driver_rem, &team_rem);
     Counts counts;
     const int rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         // rank kernel's LDS: the gain histogram joins the block when the block still leaves room for a second one
@@ -1226,18 +1250,29 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
                                         std::to_string(c.lds_per_block) + " per block");
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::champ_rank),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_lds));
+        const uint32_t round_lds = rounds ? mcgp::champ_round_lds(n, words, round_T, team_words).bytes : 0;
+        if (round_lds > c.lds_per_block)
+            return fail(MCGP_E_HIP, "the per-round standings kernel needs " + std::to_string(round_lds) +
+                                        " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
+        if (rounds)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::champ_round),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)round_lds));
         // workspace: orders staging of one chunk | the chunk's standing keys | tables | histograms
         const uint64_t cap = std::min(n_sims, kOrdersChunk);
         Layout ws;
         const size_t o_orders = ws.add(cap * n), o_keys = ws.add((size_t)words * n * cap * 8), o_add = ws.add(add.size() * 8);
         const size_t o_init = ws.add(init_key.size() * 8), o_mem = ws.add(members.size()), o_nmem = ws.add(n_teams);
-        const size_t o_ipts = ws.add(4 * n), o_hist = ws.add(hist_cells * 8);
+        const size_t o_ipts = ws.add(4 * n), o_trem = ws.add(4 * team_rem.size()), o_hist = ws.add(hist_cells * 8);
         int r = c.work.reserve(ws.bytes);
         if (r != MCGP_OK) return r;
         uint8_t *d_orders = c.work.at<uint8_t>(o_orders);
         uint64_t *d_keys = c.work.at<uint64_t>(o_keys);
         unsigned long long *h_champ = c.work.at<unsigned long long>(o_hist), *h_team = h_champ + champ_cells;
         unsigned long long *h_gain = h_team + team_cells, *h_race = h_gain + gain_cells;
+        unsigned long long *h_round = h_race + race_cells, *h_contend = h_round + rh_cells, *h_secure = h_contend + rc_cells;
+        unsigned long long *h_tround = h_secure + rc_cells, *h_tcontend = h_tround + trh_cells, *h_tsecure = h_tcontend + trc_cells;
+        if (!team_rem.empty())
+            HIP_TRY(hipMemcpyAsync(c.work.at(o_trem), team_rem.data(), 4 * team_rem.size(), hipMemcpyHostToDevice, nullptr));
         HIP_TRY(hipMemcpyAsync(c.work.at(o_add), add.data(), add.size() * 8, hipMemcpyHostToDevice, nullptr));
         HIP_TRY(hipMemcpyAsync(c.work.at(o_init), init_key.data(), init_key.size() * 8, hipMemcpyHostToDevice, nullptr));
         HIP_TRY(hipMemcpyAsync(c.work.at(o_mem), members.data(), members.size(), hipMemcpyHostToDevice, nullptr));
@@ -1251,6 +1286,9 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
         if (rank_per_cu > 8) rank_per_cu = 8;
         if (rank_per_cu < 1) rank_per_cu = 1;
         const uint64_t rank_cap = (uint64_t)c.cu_count * rank_per_cu;
+        uint64_t round_per_cu = rounds ? c.lds_per_block / round_lds : 1;
+        if (round_per_cu > 8) round_per_cu = 8;
+        const uint64_t round_cap = (uint64_t)c.cu_count * round_per_cu;
         for (uint64_t done = 0; done < n_sims; done += cap) {
             const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
             // chunk-outer, race-inner: every race of the chunk through mcgp_run's own launch path, its orders into the
@@ -1265,6 +1303,18 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
                                    c.work.at<const uint64_t>(o_add) + (size_t)rr * n * words, c.work.at<const uint64_t>(o_init),
                                    rr == 0 ? 1u : 0u);
                 HIP_TRY(hipGetLastError());
+                if (rounds) {
+                    // the standings as they now are, before the next race adds to them
+                    const uint64_t rtiles = (m + mcgp::kChampTile - 1) / mcgp::kChampTile;
+                    hipLaunchKernelGGL(mcgp::champ_round, dim3((uint32_t)std::min(rtiles, round_cap)),
+                                       dim3(mcgp::kChampRoundBlock), round_lds, nullptr, d_keys, m, cap, n, words, round_T,
+                                       team_words, team_cbits, c.work.at<const uint8_t>(o_mem), c.work.at<const uint8_t>(o_nmem),
+                                       driver_rem[rr], c.work.at<const uint32_t>(o_trem) + (size_t)rr * n_teams,
+                                       rr + 1 == n_races ? 1u : 0u, h_round + (size_t)rr * n * n, h_contend + (size_t)rr * n,
+                                       h_secure + (size_t)rr * n, h_tround + (size_t)rr * round_T * round_T,
+                                       h_tcontend + (size_t)rr * round_T, h_tsecure + (size_t)rr * round_T);
+                    HIP_TRY(hipGetLastError());
+                }
             }
             const uint64_t tiles = (m + mcgp::kChampTile - 1) / mcgp::kChampTile;
             hipLaunchKernelGGL(mcgp::champ_rank, dim3((uint32_t)std::min(tiles, rank_cap)), dim3(mcgp::kChampRankBlock), rank_lds,
@@ -1276,8 +1326,43 @@ int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const m
         return counts.download(h_champ, hist_cells);
     });
     if (rc != MCGP_OK) return rc;
-    counts.add_to({{champ_hist, champ_cells}, {team_hist, team_cells}, {gain_hist, gain_cells}, {race_hist, race_cells}});
+    std::vector<Counts::Seg> segs = {{champ_hist, champ_cells}, {team_hist, team_cells}, {gain_hist, gain_cells},
+                                     {race_hist, race_cells}};
+    if (rounds) {
+        segs.push_back({rounds->round_hist, rh_cells});
+        segs.push_back({rounds->contend, rc_cells});
+        segs.push_back({rounds->secure, rc_cells});
+        segs.push_back({rounds->team_round_hist, trh_cells});
+        segs.push_back({rounds->team_contend, trc_cells});
+        segs.push_back({rounds->team_secure, trc_cells});
+    }
+    counts.add_to(segs);
     return MCGP_OK;
+}
+
+int32_t mcgp_run_championship(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                              const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                              const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                              const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                              uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                              uint64_t *gain_hist, uint64_t *race_hist)
+{
+    return run_championship(n_races, cfgs, drvs, grid_probs, n, n_sims, sim_offset, seeds, points, countback, init_points,
+                            init_counts, team, n_teams, device, champ_hist, team_hist, gain_hist, race_hist, nullptr);
+}
+
+int32_t mcgp_run_championship_rounds(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                                     const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                                     const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                                     const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                                     uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                                     uint64_t *gain_hist, uint64_t *race_hist, uint64_t *round_hist, uint64_t *contend_out,
+                                     uint64_t *secure_out, uint64_t *team_round_hist, uint64_t *team_contend_out,
+                                     uint64_t *team_secure_out)
+{
+    const ChampRoundsOut rounds = {round_hist, contend_out, secure_out, team_round_hist, team_contend_out, team_secure_out};
+    return run_championship(n_races, cfgs, drvs, grid_probs, n, n_sims, sim_offset, seeds, points, countback, init_points,
+                            init_counts, team, n_teams, device, champ_hist, team_hist, gain_hist, race_hist, &rounds);
 }
 
 int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,

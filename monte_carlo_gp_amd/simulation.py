@@ -1199,7 +1199,12 @@ class ChampionshipResult:
     """What run_championship returns.  Integer histograms (counts over n_simulations):
     champ_hist [n][n] = [driver][championship position - 1], team_hist [T][T] the same for the constructors,
     gain_hist [n][G + 1] = [driver][points gained in these races]; race_histograms (when asked for) = one [n][n]
-    position histogram per race, what run_monte_carlo gives that race alone.  Probabilities derive from them."""
+    position histogram per race, what run_monte_carlo gives that race alone.  Probabilities derive from them.
+
+    With by_round=True (None otherwise), the standings after every race r of the call (include/mcgp.h:
+    mcgp_run_championship_rounds): round_hist [R][n][n] = [race][driver][standings position], contend [R][n] and
+    secure [R][n] = simulations in which the driver is in contention / has the title secure after race r, and
+    team_round_hist [R][T][T], team_contend [R][T], team_secure [R][T] for the constructors."""
     drivers: list
     teams: list
     n_simulations: int
@@ -1208,6 +1213,12 @@ class ChampionshipResult:
     gain_hist: np.ndarray
     initial_points: dict
     race_histograms: list | None = None
+    round_hist: np.ndarray | None = None
+    contend: np.ndarray | None = None
+    secure: np.ndarray | None = None
+    team_round_hist: np.ndarray | None = None
+    team_contend: np.ndarray | None = None
+    team_secure: np.ndarray | None = None
 
     @property
     def title_probabilities(self) -> dict:
@@ -1231,6 +1242,65 @@ class ChampionshipResult:
     @property
     def constructor_position_probabilities(self) -> dict:
         return histogram_to_probs(self.team_hist, self.teams, self.n_simulations)
+
+    # ---- by round (run_championship(..., by_round=True)): one entry per race of the call, in race order
+    def _by_round(self, counts, names, what):
+        if counts is None:
+            raise ValueError(f'{what} needs run_championship(..., by_round=True)')
+        return [{e: int(row[i]) / self.n_simulations for i, e in enumerate(names)} for row in counts]
+
+    def _decided(self, secure, what):
+        if secure is None:
+            raise ValueError(f'{what} needs run_championship(..., by_round=True)')
+        return [int(row.sum()) / self.n_simulations for row in secure]
+
+    def _clinch(self, secure, names, what):
+        if secure is None:
+            raise ValueError(f'{what} needs run_championship(..., by_round=True)')
+        # once secure, always secure: the simulations that clinch AT race r are the growth of the row
+        first = np.diff(np.asarray(secure, np.int64), axis=0, prepend=0)
+        return {e: {int(r): int(first[r, i]) / self.n_simulations for r in np.nonzero(first[:, i])[0]}
+                for i, e in enumerate(names)}
+
+    @property
+    def leader_probabilities_by_round(self) -> list:
+        """[race] {driver: P(leads the standings after that race)}."""
+        return self._by_round(None if self.round_hist is None else self.round_hist[:, :, 0], self.drivers,
+                              'leader_probabilities_by_round')
+
+    @property
+    def contention_probabilities_by_round(self) -> list:
+        """[race] {driver: P(still in contention after that race)}: leading, or within the points a driver can still
+        take."""
+        return self._by_round(self.contend, self.drivers, 'contention_probabilities_by_round')
+
+    @property
+    def decided_by_round(self) -> list:
+        """[race] P(some driver's title is secure after that race); non-decreasing, 1 after the last race."""
+        return self._decided(self.secure, 'decided_by_round')
+
+    @property
+    def clinch_round_probabilities(self) -> dict:
+        """{driver: {race index: P(the driver's title becomes secure at that race)}}, zero entries omitted; a driver's
+        entries sum to its title probability.  Index 0 includes titles already secure before the first race."""
+        return self._clinch(self.secure, self.drivers, 'clinch_round_probabilities')
+
+    @property
+    def constructor_leader_probabilities_by_round(self) -> list:
+        return self._by_round(None if self.team_round_hist is None else self.team_round_hist[:, :, 0], self.teams,
+                              'constructor_leader_probabilities_by_round')
+
+    @property
+    def constructor_contention_probabilities_by_round(self) -> list:
+        return self._by_round(self.team_contend, self.teams, 'constructor_contention_probabilities_by_round')
+
+    @property
+    def constructor_decided_by_round(self) -> list:
+        return self._decided(self.team_secure, 'constructor_decided_by_round')
+
+    @property
+    def constructor_clinch_round_probabilities(self) -> dict:
+        return self._clinch(self.team_secure, self.teams, 'constructor_clinch_round_probabilities')
 
 
 def _standings_arrays(standings, drivers):
@@ -1259,7 +1329,7 @@ def _standings_arrays(standings, drivers):
 
 
 def run_championship(races, n_simulations, *, standings=None, seed=None, sim_offset=0, device=0, set_pop=None,
-                     return_race_histograms=False) -> ChampionshipResult:
+                     return_race_histograms=False, by_round=False) -> ChampionshipResult:
     """Drivers' and constructors' championship over a calendar of races (include/mcgp.h: mcgp_run_championship).
 
     `races`: a list of dicts with the keys run_monte_carlo_batch takes (`config`, `grid_probs`, `base_pace`,
@@ -1277,7 +1347,12 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
     Points follow the race model's classification: retired cars are classified behind the finishers (as in the
     reference), so a retired car scores when fewer cars finish than the table pays.  Ties: more points, then more
     wins, more seconds, ... (countback races only); a full tie goes to the lower driver (team) index -- the
-    regulations then use criteria this model does not have."""
+    regulations then use criteria this model does not have.
+
+    `by_round=True` also counts, on the device, the standings after every race of the call (include/mcgp.h:
+    mcgp_run_championship_rounds): who leads, who is still in contention and whose title is secure after each race,
+    for drivers and constructors (ChampionshipResult.round_hist and the fields and properties next to it).  The other
+    results are the same either way."""
     races = list(races)
     if not races:
         raise ValueError('a championship needs at least one race')
@@ -1332,6 +1407,9 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
         raise ValueError('n_simulations must be >= 0')
     devices = RaceSimulator(races[0]['config'], device=device).devices
     lib = N.lib()
+    if by_round and not hasattr(lib, 'mcgp_run_championship_rounds'):
+        raise N.McgpError(-1, 'the loaded library does not export mcgp_run_championship_rounds: by_round=True needs a '
+                              'library built from sources that have it')
     cfgs = (N.McgpConfig * R)(*[p.cfg for p in probs])
     drvs = (N.McgpDrivers * R)(*[p.drv for p in probs])
     gptrs = (C.POINTER(C.c_double) * R)(*[_dptr(g) for g in grids])
@@ -1344,11 +1422,16 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
         th = np.zeros((T, T), np.uint64)
         gh = np.zeros((n, G + 1), np.uint64)
         rh = np.zeros((R, n, n), np.uint64) if return_race_histograms else None
-        rc = lib.mcgp_run_championship(R, cfgs, drvs, gptrs, n, int(count), int(sim_offset) + int(offset), seeds_c,
-                                       i32(points), countback.ctypes.data_as(C.POINTER(C.c_uint8)), i32(init_pts32),
-                                       i32(init_counts32), i32(team), T, int(dev), u64(ch), u64(th), u64(gh),
-                                       u64(rh) if rh is not None else None)
-        return (ch, th, gh, rh), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+        args = (R, cfgs, drvs, gptrs, n, int(count), int(sim_offset) + int(offset), seeds_c, i32(points),
+                countback.ctypes.data_as(C.POINTER(C.c_uint8)), i32(init_pts32), i32(init_counts32), i32(team), T, int(dev),
+                u64(ch), u64(th), u64(gh), u64(rh) if rh is not None else None)
+        rounds = ()
+        if by_round:
+            rounds = tuple(np.zeros(shape, np.uint64) for shape in ((R, n, n), (R, n), (R, n), (R, T, T), (R, T), (R, T)))
+            rc = lib.mcgp_run_championship_rounds(*args, *[u64(a) for a in rounds])
+        else:
+            rc = lib.mcgp_run_championship(*args)
+        return (ch, th, gh, rh) + rounds, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
 
     if len(devices) == 1:
         parts = [run_shard(devices[0], 0, n_simulations)]
@@ -1366,7 +1449,9 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
     return ChampionshipResult(
         drivers=drivers, teams=team_names, n_simulations=n_simulations, champ_hist=total(0), team_hist=total(1),
         gain_hist=total(2), initial_points={d: int(init_pts[i]) for i, d in enumerate(drivers)},
-        race_histograms=list(total(3)) if return_race_histograms else None)
+        race_histograms=list(total(3)) if return_race_histograms else None,
+        **({k: total(4 + i) for i, k in enumerate(('round_hist', 'contend', 'secure', 'team_round_hist', 'team_contend',
+                                                   'team_secure'))} if by_round else {}))
 
 
 def histogram_to_probs(hist, drivers, n_simulations):

@@ -2,7 +2,8 @@
 // nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/championship.hip.h with g++ through the stand-in
 // <hip/hip_runtime.h> of this directory in its EMU_BLOCK_THREADS mode and calls the two real __global__ functions,
 // champ_accumulate and champ_rank, on finishing orders the caller hands in.  The key layout and the kernels' tables
-// come from csrc/champ_pack.h, the text the C ABI itself uses.
+// come from csrc/champ_pack.h, the text the C ABI itself uses.  emu_champ_rounds_run does the same for champ_round
+// (csrc/champ_rounds.hip.h), the per-round standings kernel of mcgp_run_championship_rounds.
 //
 // Execution model: REAL BLOCK SEMANTICS.  A block is 256 host threads (both kernels have a fixed block of 256) that
 // run at the same time and meet at __syncthreads(), a pthread barrier; atomicAdd is __atomic_fetch_add; a __shared__
@@ -20,6 +21,7 @@
 
 #include "../../include/mcgp.h"
 #include "../../monte_carlo_gp_amd/csrc/champ_pack.h"
+#include "../../monte_carlo_gp_amd/csrc/champ_rounds.hip.h"
 
 thread_local emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0};
 emu_dim3 blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -29,6 +31,7 @@ namespace {
 
 constexpr unsigned kBlock = 256;
 static_assert(kBlock == (unsigned)mcgp::kChampAccBlock && kBlock == (unsigned)mcgp::kChampRankBlock, "one block size");
+static_assert(kBlock == (unsigned)mcgp::kChampRoundBlock, "one block size");
 
 pthread_barrier_t g_block_barrier;       // __syncthreads(): the 256 threads of the block
 pthread_barrier_t g_pool_barrier;        // start and end of a launch: the 256 threads and the caller
@@ -106,31 +109,13 @@ int fail(int rc, const std::string &msg, const char **err)
     return rc;
 }
 
-}  // namespace
-
-void emu_block_barrier() { pthread_barrier_wait(&g_block_barrier); }
-
-extern "C" {
-
-// The standings of n_sims seasons from their finishing orders.  orders: [n_races][n_sims][n] u8 (driver classified
-// p-th); points [n_races][n], countback [n_races], init_points [n] or NULL, init_counts [n][n] or NULL, team [n]: as
-// mcgp_run_championship takes them, and checked against the same limits.  The simulations go through in chunks of
-// `cap` (the library's staging capacity; the key buffer's simulation stride): every chunk starts from the initial keys
-// again, in a key buffer that still holds the chunk before it (0xA5 bytes before the first).  gain_in_lds: 0 or 1, or
-// -1 for the library's rule under a block budget of lds_per_block bytes.  acc_grid / rank_grid: most blocks of a
-// launch (the library's cu_count * 8 and cu_count * blocks per CU).  champ_hist [n][n], team_hist [T][T] and
-// gain_hist [n][G + 1] are ACCUMULATED into.  keys_out: NULL or [words][n][cap], the key buffer after the last chunk.
-// info_out: NULL or {words, team_cbits, team_words, gain_cols, gain_in_lds, the rank kernel's LDS bytes}.
-int emu_champ_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t cap, const uint8_t *orders, const int32_t *points,
-                  const uint8_t *countback, const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
-                  uint32_t n_teams, int32_t gain_in_lds_arg, uint32_t lds_per_block, uint32_t acc_grid, uint32_t rank_grid,
-                  unsigned long long *champ_hist, unsigned long long *team_hist, unsigned long long *gain_hist,
-                  uint64_t *keys_out, uint32_t *info_out, const char **err)
+// The limits of mcgp_run_championship on a season handed in as finishing orders; G, awarded, n_cb: the three sums the
+// checks hand to the layout (pack_championship).
+int check_season(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t cap, const uint8_t *orders, const int32_t *points,
+                 const uint8_t *countback, const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                 uint32_t n_teams, uint32_t acc_grid, uint32_t rank_grid, uint64_t *G_out, uint64_t *awarded_out,
+                 uint32_t *n_cb_out, const char **err)
 {
-    static const char *none = "";
-    *err = none;
-    if (!orders || !points || !countback || !team || !champ_hist || !team_hist || !gain_hist)
-        return fail(MCGP_E_BAD_ARG, "a championship array is NULL", err);
     if (n_races < 1 || n_races > (uint32_t)mcgp::kChampMaxRaces) return fail(MCGP_E_BAD_ARG, "n_races must be in [1, 64]", err);
     if (n < 1 || n > MCGP_MAX_CARS) return fail(MCGP_E_BAD_ARG, "n must be in [1, 32]", err);
     if (n_teams < 1 || n_teams > n) return fail(MCGP_E_BAD_ARG, "n_teams must be in [1, n]", err);
@@ -163,6 +148,42 @@ int emu_champ_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t cap, c
     }
     for (uint64_t i = 0; i < (uint64_t)n_races * n_sims * n; ++i)
         if (orders[i] >= n) return fail(MCGP_E_BAD_ARG, "an order names a driver outside [0, n)", err);
+    *G_out = G;
+    *awarded_out = awarded;
+    *n_cb_out = n_cb;
+    return MCGP_OK;
+}
+
+}  // namespace
+
+void emu_block_barrier() { pthread_barrier_wait(&g_block_barrier); }
+
+extern "C" {
+
+// The standings of n_sims seasons from their finishing orders.  orders: [n_races][n_sims][n] u8 (driver classified
+// p-th); points [n_races][n], countback [n_races], init_points [n] or NULL, init_counts [n][n] or NULL, team [n]: as
+// mcgp_run_championship takes them, and checked against the same limits.  The simulations go through in chunks of
+// `cap` (the library's staging capacity; the key buffer's simulation stride): every chunk starts from the initial keys
+// again, in a key buffer that still holds the chunk before it (0xA5 bytes before the first).  gain_in_lds: 0 or 1, or
+// -1 for the library's rule under a block budget of lds_per_block bytes.  acc_grid / rank_grid: most blocks of a
+// launch (the library's cu_count * 8 and cu_count * blocks per CU).  champ_hist [n][n], team_hist [T][T] and
+// gain_hist [n][G + 1] are ACCUMULATED into.  keys_out: NULL or [words][n][cap], the key buffer after the last chunk.
+// info_out: NULL or {words, team_cbits, team_words, gain_cols, gain_in_lds, the rank kernel's LDS bytes}.
+int emu_champ_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t cap, const uint8_t *orders, const int32_t *points,
+                  const uint8_t *countback, const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                  uint32_t n_teams, int32_t gain_in_lds_arg, uint32_t lds_per_block, uint32_t acc_grid, uint32_t rank_grid,
+                  unsigned long long *champ_hist, unsigned long long *team_hist, unsigned long long *gain_hist,
+                  uint64_t *keys_out, uint32_t *info_out, const char **err)
+{
+    static const char *none = "";
+    *err = none;
+    if (!orders || !points || !countback || !team || !champ_hist || !team_hist || !gain_hist)
+        return fail(MCGP_E_BAD_ARG, "a championship array is NULL", err);
+    uint64_t G = 0, awarded = 0;
+    uint32_t n_cb = 0;
+    const int chk = check_season(n_races, n, n_sims, cap, orders, points, countback, init_points, init_counts, team, n_teams,
+                                 acc_grid, rank_grid, &G, &awarded, &n_cb, err);
+    if (chk != MCGP_OK) return chk;
     mcgp::ChampPack pk;
     const std::string e = mcgp::pack_championship(n_races, n, points, countback, init_points, init_counts, team, n_teams, G,
                                                   awarded, n_cb, &pk);
@@ -209,6 +230,80 @@ int emu_champ_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t cap, c
         emu_dynamic_lds = nullptr;
     }
     if (keys_out) std::memcpy(keys_out, keys.data(), keys.size() * 8);
+    return MCGP_OK;
+}
+
+// The standings after every race of n_sims seasons: emu_champ_run's inputs (orders, tables, standings, teams, cap,
+// acc_grid), champ_accumulate after every race of a chunk and champ_round right behind it on a grid of at most
+// round_grid blocks, as mcgp_run_championship_rounds launches them.  round_hist [R][n][n], contend [R][n], secure [R][n]
+// and, when teams != 0, team_round_hist [R][T][T], team_contend [R][T], team_secure [R][T] are ACCUMULATED into
+// (teams == 0: the three may be NULL and the kernel runs without teams).  rem_out: NULL or [R + R * T], the
+// remaining-points tables (drivers, then teams).  info_out: NULL or {words, team_cbits, team_words, the kernel's LDS
+// bytes}.
+int emu_champ_rounds_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t cap, const uint8_t *orders,
+                         const int32_t *points, const uint8_t *countback, const int32_t *init_points,
+                         const int32_t *init_counts, const int32_t *team, uint32_t n_teams, uint32_t teams, uint32_t acc_grid,
+                         uint32_t round_grid, unsigned long long *round_hist, unsigned long long *contend,
+                         unsigned long long *secure, unsigned long long *team_round_hist, unsigned long long *team_contend,
+                         unsigned long long *team_secure, uint32_t *rem_out, uint32_t *info_out, const char **err)
+{
+    static const char *none = "";
+    *err = none;
+    if (!orders || !points || !countback || !team || !round_hist || !contend || !secure)
+        return fail(MCGP_E_BAD_ARG, "a championship array is NULL", err);
+    if (teams && (!team_round_hist || !team_contend || !team_secure)) return fail(MCGP_E_BAD_ARG, "a team array is NULL", err);
+    uint64_t G = 0, awarded = 0;
+    uint32_t n_cb = 0;
+    const int chk = check_season(n_races, n, n_sims, cap, orders, points, countback, init_points, init_counts, team, n_teams,
+                                 acc_grid, round_grid, &G, &awarded, &n_cb, err);
+    if (chk != MCGP_OK) return chk;
+    mcgp::ChampPack pk;
+    const std::string e = mcgp::pack_championship(n_races, n, points, countback, init_points, init_counts, team, n_teams, G,
+                                                  awarded, n_cb, &pk);
+    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    std::vector<uint32_t> driver_rem, team_rem;
+    mcgp::champ_remaining(n_races, n, points, pk.n_members.data(), n_teams, &driver_rem, &team_rem);
+    if (rem_out) {
+        std::memcpy(rem_out, driver_rem.data(), 4 * driver_rem.size());
+        std::memcpy(rem_out + n_races, team_rem.data(), 4 * team_rem.size());
+    }
+    const uint32_t words = pk.words, T = teams ? n_teams : 0;
+    const uint32_t round_lds = mcgp::champ_round_lds(n, words, T, pk.team_words).bytes;
+    if (info_out) {
+        const uint32_t info[4] = {words, pk.team_cbits, pk.team_words, round_lds};
+        std::memcpy(info_out, info, sizeof(info));
+    }
+    if (n_sims == 0) return MCGP_OK;
+    if (cap > n_sims) cap = n_sims;
+    std::vector<uint64_t> keys((size_t)words * n * cap);
+    std::memset(keys.data(), 0xA5, keys.size() * 8);
+    std::vector<unsigned char> lds(round_lds);
+    unsigned char *lds_at = lds.data();
+    g_pool.start();
+    for (uint64_t done = 0; done < n_sims; done += cap) {
+        const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
+        for (uint32_t rr = 0; rr < n_races; ++rr) {
+            std::vector<uint32_t> stage((m * n + 3) / 4 + 1);
+            uint8_t *d_orders = reinterpret_cast<uint8_t *>(stage.data());
+            std::memcpy(d_orders, orders + ((size_t)rr * n_sims + done) * n, m * n);
+            const uint64_t tiles = (m + mcgp::kChampAccBlock - 1) / mcgp::kChampAccBlock;
+            const uint64_t *add = pk.add.data() + (size_t)rr * n * words;
+            const uint32_t first = rr == 0 ? 1u : 0u;
+            launch((unsigned)(tiles < acc_grid ? tiles : acc_grid), [&] {
+                mcgp::champ_accumulate(d_orders, m, n, words, cap, keys.data(), add, pk.init_key.data(), first);
+            });
+            const uint64_t rtiles = (m + mcgp::kChampTile - 1) / mcgp::kChampTile;
+            emu_dynamic_lds = lds_at;
+            launch((unsigned)(rtiles < round_grid ? rtiles : round_grid), [&] {
+                mcgp::champ_round(keys.data(), m, cap, n, words, T, pk.team_words, pk.team_cbits, pk.members.data(),
+                                  pk.n_members.data(), driver_rem[rr], team_rem.data() + (size_t)rr * n_teams,
+                                  rr + 1 == n_races ? 1u : 0u, round_hist + (size_t)rr * n * n, contend + (size_t)rr * n,
+                                  secure + (size_t)rr * n, T ? team_round_hist + (size_t)rr * T * T : nullptr,
+                                  T ? team_contend + (size_t)rr * T : nullptr, T ? team_secure + (size_t)rr * T : nullptr);
+            });
+            emu_dynamic_lds = nullptr;
+        }
+    }
     return MCGP_OK;
 }
 
