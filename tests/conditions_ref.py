@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 import gaps_ref as GR
+import generic_cases as G
 import oracle_py as O
 import resume_ref as RR
 import strategy_ref as SR
@@ -130,6 +131,17 @@ def counts(facts, conds):
     return out
 
 
+def counts_each(facts, conds):
+    """masks() and counts() of every simulation on its own, for runs of one simulation each: dict(masks [m], hist
+    [m][n][n], count [m][C], cond_hist [m][C][n][n])."""
+    orders = facts['orders']
+    m, n = orders.shape
+    hist = np.zeros((m, n, n), np.int64)
+    hist[np.arange(m)[:, None], orders, np.arange(n)[None, :]] = 1
+    count = met(facts, conds).astype(np.int64)
+    return dict(masks=masks(facts, conds), hist=hist, count=count, cond_hist=count[:, :, None, None] * hist[:, None, :, :])
+
+
 def informative(facts, conds):
     """bool [C]: met by at least one and by fewer than all simulations."""
     k = met(facts, conds).sum(axis=0)
@@ -170,8 +182,8 @@ def simple_candidates(n, L):
 
 
 def wide_candidates(n, L, rng, count, n_atoms=8):
-    """`count` conditions of n_atoms atoms each with wide ranges, so that a conjunction of eight is still met sometimes."""
-    out = []
+    """`count` conditions of n_atoms atoms each with wide ranges, so that a conjunction of eight is still met sometimes;
+    generated one by one as they are asked for, so that pick() pays only for the candidates it looks at."""
     for _ in range(count):
         cond = []
         for _ in range(n_atoms):
@@ -197,8 +209,7 @@ def wide_candidates(n, L, rng, count, n_atoms=8):
                 lo, hi = ((0, 0), (0, 1), (1, HI), (0, 3))[int(rng.integers(0, 4))]
             negate = int(rng.random() < 0.15)
             cond.append((f, a, b if f == AHEAD_BY else 0, int(lo), int(hi), negate))
-        out.append(cond)
-    return out
+        yield cond
 
 
 def pick(facts, candidates, most=64):
@@ -212,6 +223,29 @@ def pick(facts, candidates, most=64):
             if len(keep) == most:
                 break
     return keep
+
+
+def choose(facts, n, L, seed, most=61, wide=600):
+    """(conditions, indices of the constant ones): informative simple and eight-atom conditions chosen on the reference's
+    facts (`wide` eight-atom candidates from default_rng(seed)), then the empty condition, an always-true and an
+    always-false bound."""
+    rng = np.random.default_rng(seed)
+    simple = pick(facts, simple_candidates(n, L), most // 2)
+    conds = simple + pick(facts, wide_candidates(n, L, rng, wide), most - len(simple))
+    k = len(conds)
+    return conds + [EMPTY, ALWAYS, NEVER], (k, k + 1, k + 2)
+
+
+def state_runs(case, seed, ref, sims, base):
+    """[(i, k, state)]: the traced simulations `sims` of ref (simulation ids base + i) after every lap of
+    generic_cases.resume_laps, as (mcgp_race_state arrays, lap, drs_disabled_until)."""
+    return [(i, k, (RR.state_arrays(ref, i, k), k, RR.drs_disabled_until(case, seed, base + i, k)))
+            for i in sims for k in G.resume_laps(case, seed, base + i)]
+
+
+def concat(parts):
+    """The facts of several runs as one."""
+    return {key: np.concatenate([p[key] for p in parts], axis=0) for key in parts[0]}
 
 
 def facts_used(conds):
@@ -232,19 +266,21 @@ def empty(n, C_):
     return dict(hist=np.zeros((n, n), np.int64), count=np.zeros(C_, np.int64), cond_hist=np.zeros((C_, n, n), np.int64))
 
 
-def run_c(case, conds, n_sims, seed, sim_offset=0, state=None, device=0, prob=None, cond_hist=True, into=None):
+def run_c(case, conds, n_sims, seed, sim_offset=0, state=None, device=0, prob=None, cond_hist=True, into=None,
+          table=None):
     """mcgp_run_conditions on a case -> (rc, counts dict as counts() returns; cond_hist stays as passed when cond_hist is
     False).  state = (mcgp_race_state arrays, lap, drs_disabled_until) or None (from the grid).  into: a dict of uint64
-    arrays to accumulate into."""
+    arrays to accumulate into.  table: c_conditions(conds), where a caller makes many calls with the same conditions."""
     prob = prob or RR.problem(case)
     n = prob.n
     g = np.ascontiguousarray(O.Problem(case).grid_probs, np.float64) if state is None else None
     cs = RR.c_state(*state) if state is not None else None
+    table = table if table is not None else c_conditions(conds)
     out = into if into is not None else {k: v.astype(np.uint64) for k, v in empty(n, len(conds)).items()}
     u64 = lambda k: out[k].ctypes.data_as(C.POINTER(C.c_uint64))
     rc = N.lib().mcgp_run_conditions(C.byref(prob.cfg), C.byref(prob.drv),
                                      g.ctypes.data_as(C.POINTER(C.c_double)) if g is not None else None,
-                                     C.byref(cs) if cs is not None else None, n, len(conds), c_conditions(conds),
+                                     C.byref(cs) if cs is not None else None, n, len(conds), table,
                                      int(n_sims), int(sim_offset), int(seed), device, u64('hist'), u64('count'),
                                      u64('cond_hist') if cond_hist else None)
     return rc, {k: v.astype(np.int64) for k, v in out.items()}

@@ -34,6 +34,7 @@ def values_from_times(cum, dnf, slot, edges=DEFAULT_EDGES, pairs=()):
     B = len(edges) + 1
     vals = np.zeros((m, L, n + 1 + len(pairs)), np.int64)
     rows = np.arange(m)[:, None]
+    pa, pb = (np.array(pairs, np.int64).reshape(-1, 2).T if len(pairs) else (None, None))
     for k in range(L):                                        # after lap k + 1
         t = cum[:, k, :]
         running = dnf[:, k, :] == 0
@@ -46,11 +47,11 @@ def values_from_times(cum, dnf, slot, edges=DEFAULT_EDGES, pairs=()):
         second = np.where(pos == 1, t, 0.0).sum(axis=1)
         vals[:, k, :n] = np.where(running, bin_of(t - leader[:, None], edges), B)
         vals[:, k, n] = np.where(running.sum(axis=1) >= 2, bin_of(second - leader, edges), B)
-        for p, (a, b) in enumerate(pairs):
-            both = running[:, a] & running[:, b]
-            a_ahead = pos[:, a] < pos[:, b]
-            v = np.where(a_ahead, bin_of(t[:, b] - t[:, a], edges), B + bin_of(t[:, a] - t[:, b], edges))
-            vals[:, k, n + 1 + p] = np.where(both, v, 2 * B)
+        if len(pairs):                                        # all pairs at once: [m][P]
+            both = running[:, pa] & running[:, pb]
+            a_ahead = pos[:, pa] < pos[:, pb]
+            v = np.where(a_ahead, bin_of(t[:, pb] - t[:, pa], edges), B + bin_of(t[:, pa] - t[:, pb], edges))
+            vals[:, k, n + 1:] = np.where(both, v, 2 * B)
     return vals
 
 
@@ -58,12 +59,14 @@ def counts_from_values(vals, n, n_edges, n_pairs, lap0=0):
     """lap_gap, lead and pair from values [m][L][n + 1 + P]; the rows of laps 1 .. lap0 stay zero."""
     L, B = vals.shape[1], n_edges + 1
     out = empty(n, L, n_edges, n_pairs)
-    for k in range(lap0, L):
-        for d in range(n):
-            out['lap_gap'][k, d] = np.bincount(vals[:, k, d], minlength=B + 1)
-        out['lead'][k] = np.bincount(vals[:, k, n], minlength=B + 1)
-        for p in range(n_pairs):
-            out['pair'][k, p] = np.bincount(vals[:, k, n + 1 + p], minlength=2 * B + 1)
+    v = np.asarray(vals, np.int64)[:, lap0:, :]
+    for key, cols, width in (('lap_gap', slice(0, n), B + 1), ('lead', slice(n, n + 1), B + 1),
+                             ('pair', slice(n + 1, n + 1 + n_pairs), 2 * B + 1)):
+        x = v[:, :, cols]
+        assert x.size == 0 or (0 <= x.min() and x.max() < width)
+        cell = np.arange(x.shape[1] * x.shape[2]).reshape(1, x.shape[1], x.shape[2])      # (lap, row) of every value
+        count = np.bincount((cell * width + x).ravel(), minlength=x.shape[1] * x.shape[2] * width)
+        out[key][lap0:] = count.reshape((L - lap0,) + out[key].shape[1:])
     return out
 
 
@@ -79,23 +82,71 @@ def slots_of(grids):
     return slot
 
 
-def gap_counts(case, m, seed, sim_offset=0, edges=DEFAULT_EDGES, pairs=(), ref=None):
-    """The counts (and the histogram) of simulations sim_offset .. sim_offset + m - 1 from the grid, from the oracle."""
+def gap_counts(case, m, seed, sim_offset=0, edges=DEFAULT_EDGES, pairs=(), ref=None, vals=None):
+    """The counts (and the histogram) of simulations sim_offset .. sim_offset + m - 1 from the grid, from the oracle.
+    vals: values_from_times of ref with these edges and pairs, where the caller has them already."""
     ref = ref or RR.traced_run(case, m, seed, sim_offset)
     tr = ref['trace']
-    out = counts_from_times(tr['cum'], tr['dnf'], slots_of(ref['grids']), edges, pairs)
+    if vals is None:
+        vals = values_from_times(tr['cum'], tr['dnf'], slots_of(ref['grids']), edges, pairs)
+    out = counts_from_values(vals, tr['cum'].shape[2], len(edges), len(pairs))
     out['hist'] = ref['hist'].astype(np.int64)
     return out
 
 
-def continued_counts(ref, sims, k, edges=DEFAULT_EDGES, pairs=()):
+def continued_counts(ref, sims, k, edges=DEFAULT_EDGES, pairs=(), vals=None):
     """The counts of the traced simulations `sims`, each resumed after lap k as itself: the oracle trace's laps k + 1 ..
-    L of those simulations.  hist = their finishing orders' counts."""
+    L of those simulations.  hist = their finishing orders' counts.  vals: values_from_times of the whole traced run with
+    these edges and pairs, where a caller continues many states of one run."""
     tr = ref['trace']
     sims = np.asarray(sims)
-    out = counts_from_times(tr['cum'][sims], tr['dnf'][sims], slots_of(ref['grids'][sims]), edges, pairs, lap0=k)
+    if vals is None:
+        out = counts_from_times(tr['cum'][sims], tr['dnf'][sims], slots_of(ref['grids'][sims]), edges, pairs, lap0=k)
+    else:
+        out = counts_from_values(vals[sims], tr['cum'].shape[2], len(edges), len(pairs), lap0=k)
     out['hist'] = RR.counts(ref['orders'][sims], ref['grids'].shape[1])
     return out
+
+
+def own_edges(cum, dnf, most=63):
+    """Edges that are values the oracle itself shows: of the distinct positive gaps to the leader, cum[d] - cum[leader]
+    over the running cars of every simulation and lap (the subtraction of values_from_times: the leader's time is the
+    smallest of the running cars'), min(most, their number) at evenly spaced ranks; None when no gap is positive.  Each
+    edge e then decides a cell of the reference by e <= e, and the next double above it by the opposite."""
+    running = dnf == 0
+    leader = np.where(running, cum, np.inf).min(axis=2, keepdims=True)
+    gaps = (cum - np.where(np.isfinite(leader), leader, 0.0))[running]
+    v = np.unique(gaps[gaps > 0])
+    if v.size == 0:
+        return None
+    ranks = np.round(np.linspace(0, v.size - 1, min(most, v.size))).astype(np.int64)
+    assert (np.diff(ranks) > 0).all()
+    return tuple(float(x) for x in v[ranks])
+
+
+def tied_pairs(cum, dnf, most=64):
+    """(pairs, cells): the driver pairs (a, b) that some (simulation, lap) shows both running with EQUAL cumulative
+    times -- where the pair's column is decided by the grid slots alone --, the most often tied first, each in both
+    orientations, at most `most`; and the number of such (simulation, lap, pair a < b) cells."""
+    n = cum.shape[2]
+    times = np.zeros((n, n), np.int64)
+    for t, x in zip(cum, dnf):                                # one simulation: [L][n]
+        run = x == 0
+        times += ((t[:, :, None] == t[:, None, :]) & run[:, :, None] & run[:, None, :]).sum(axis=0)
+    times = np.triu(times, 1)
+    a, b = np.nonzero(times)
+    first = np.argsort(-times[a, b], kind='stable')
+    pairs = [p for i in first for p in ((int(a[i]), int(b[i])), (int(b[i]), int(a[i])))]
+    return pairs[:most], int(times.sum())
+
+
+def pairs_then(first, more, most=64):
+    """`first`, then those of `more` not yet listed, at most `most`."""
+    out = list(first)
+    for p in more:
+        if p not in out:
+            out.append(p)
+    return out[:most]
 
 
 def restated_times(case, m, seed, sim_offset=0, state=None, grids=None):
@@ -133,6 +184,27 @@ def restated_counts(case, m, seed, sim_offset=0, state=None, edges=DEFAULT_EDGES
     out = counts_from_times(cum, dnf, slot, edges, pairs, lap0=0 if state is None else state[1])
     out['hist'] = RR.counts(orders, cum.shape[2])
     return out
+
+
+def few_pairs(n):
+    """A few pairs in both orientations; none for a field of one."""
+    if n < 2:
+        return []
+    return [(0, 1), (1, 0), (n - 1, 0), (n // 2, n - 1)] if n > 2 else [(0, 1), (1, 0)]
+
+
+def own_call(ref, most_pairs=64, more_pairs=None):
+    """The edges and pairs of a call that the traced run `ref` itself decides: dict(edges = own_edges or, without a
+    positive gap, the default ones; up = the next doubles above them; own = whether the edges are the run's; pairs =
+    tied_pairs, then more_pairs (few_pairs unless given); cells = the run's tie cells)."""
+    tr = ref['trace']
+    n = tr['cum'].shape[2]
+    edges = own_edges(tr['cum'], tr['dnf'])
+    pairs, cells = tied_pairs(tr['cum'], tr['dnf'], most_pairs)
+    use = edges if edges is not None else tuple(float(e) for e in DEFAULT_EDGES)
+    return dict(edges=use, up=tuple(float(x) for x in np.nextafter(np.asarray(use, np.float64), np.inf)),
+                own=edges is not None, cells=cells,
+                pairs=pairs_then(pairs, few_pairs(n) if more_pairs is None else more_pairs, most_pairs))
 
 
 def c_pairs(pairs):

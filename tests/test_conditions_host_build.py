@@ -5,6 +5,9 @@ conditions_ref's numpy restatement of the nine facts over the CPU oracle's run; 
 counting kernel's counts against the restated ones.  Every compared condition is shown informative by the reference (met
 by some, not by all simulations) except the deliberate always / never / empty ones.  The host build is test
 infrastructure: nothing under monte_carlo_gp_amd/ can reach it and the product has no CPU path."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import pytest
 
@@ -19,15 +22,7 @@ CASES = ('S60', 'EVT', 'WET', 'HET', 'N10')
 FIELD_SIZES = (1, 2, 3, 22, 32)
 
 
-def _conditions(facts, n, L, seed, most=61):
-    """(conditions, indices of the constant ones): informative simple and eight-atom conditions chosen on the reference's
-    facts, then the empty condition, an always-true and an always-false bound."""
-    rng = np.random.default_rng(seed)
-    simple = CR.pick(facts, CR.simple_candidates(n, L), most // 2)
-    wide = CR.pick(facts, CR.wide_candidates(n, L, rng, 600), most - len(simple))
-    conds = simple + wide
-    k = len(conds)
-    return conds + [CR.EMPTY, CR.ALWAYS, CR.NEVER], (k, k + 1, k + 2)
+_conditions = CR.choose          # informative simple and eight-atom conditions, then the three constant ones
 
 
 def _compare(name, got, facts, conds, hist):
@@ -86,6 +81,78 @@ def test_conditions_kernel_from_the_grid_equals_the_restated_masks():
     assert eight >= 100 and total >= 300
 
 
+def _grid_facts(args, ref):
+    name, case, seed = args
+    facts = CR.oracle_facts(case, RUN_SIMS, seed, 3, ref=ref)
+    return ref, facts, _conditions(facts, len(case['grid_probs']), case['config']['total_laps'], seed)
+
+
+def _pool():
+    return ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1))
+
+
+def test_conditions_kernel_from_the_grid_on_every_input():
+    """All of generic_cases.run_inputs(): the 84 fuzz configurations with their corner cases (wet and damp tracks, two-
+    and three-car fields, every car out on lap 1, no noise, every overtake attempted), lap times near zero and the field
+    sizes, each with the conditions its own reference run shows informative."""
+    inputs = G.run_inputs()
+    O.lib()
+    with _pool() as pool:                                       # the oracle's runs; the rest is Python and gains nothing
+        refs = list(pool.map(lambda a: RR.traced_run(a[1], RUN_SIMS, a[2], 3), inputs))
+    prepared = [_grid_facts(a, ref) for a, ref in zip(inputs, refs)]
+    used, eight, total, done = set(), 0, 0, 0
+    for (name, case, seed), (ref, facts, (conds, constant)) in zip(inputs, prepared):
+        n = len(case['grid_probs'])
+        CR.assert_informative(facts, conds, constant)
+        k = constant[0]
+        if n >= 3:
+            assert k >= 20, (name, k)
+        _compare(name, CH.staged(case, conds, RUN_SIMS, seed, sim_offset=3), facts, conds, ref['hist'])
+        used |= CR.facts_used(conds[:k])
+        eight += sum(len(c) == 8 for c in conds[:k])
+        total += k
+        done += name in G.fuzz_cases()
+    assert done == G.N_FUZZ and len(inputs) == 100
+    assert used == set(CR.FACT_NAMES)
+    assert total >= 5000 and eight >= 2500, (total, eight)
+
+
+def _state_facts(args, ref, m=4, base=40):
+    name, case, seed = args
+    runs = CR.state_runs(case, seed, ref, range(m), base)
+    parts = [CR.oracle_facts(case, 0, seed, base, ref=ref, sims=[i], lap0=k) for i, k, _ in runs]
+    conds, constant = _conditions(CR.concat(parts), len(case['grid_probs']), case['config']['total_laps'], seed + 1)
+    return runs, parts, conds, constant
+
+
+def test_conditions_kernel_from_a_state_on_every_input():
+    """All of generic_cases.resume_inputs(): four simulations' states after every lap of resume_laps, each resumed as
+    itself, with the conditions informative over those states' facts."""
+    inputs = G.resume_inputs()
+    O.lib()
+    with _pool() as pool:
+        refs = list(pool.map(lambda a: RR.traced_run(a[1], 4, a[2], 40), inputs))
+    prepared = [_state_facts(a, ref) for a, ref in zip(inputs, refs)]
+    done = states = compared = 0
+    for (name, case, seed), (runs, parts, conds, constant) in zip(inputs, prepared):
+        facts = CR.concat(parts)
+        CR.assert_informative(facts, conds, constant)
+        want = CR.counts_each(facts, conds)
+        prob, table = CH.KH.generic_problem(case), CR.c_conditions(conds)
+        for s_, (i, k, st) in enumerate(runs):
+            got = CH.staged(case, conds, 1, seed, sim_offset=40 + i, state=st, prob=prob, table=table)
+            assert np.array_equal(got['orders'][0], facts['orders'][s_]), (name, i, k)
+            assert int(got['masks'][0]) == int(want['masks'][s_]), (name, i, k, hex(int(got['masks'][0]) ^ int(want['masks'][s_])))
+            for key in ('hist', 'count', 'cond_hist'):
+                assert np.array_equal(got[key], want[key][s_]), (name, i, k, key)
+        assert len(runs) >= 4, name
+        states += len(runs)
+        compared += constant[0]
+        done += name in G.fuzz_cases()
+    assert done == G.N_FUZZ
+    assert states >= 94 * 4 * 3 and compared >= 94 * 10, (states, compared)
+
+
 def test_sixty_four_conditions_of_eight_atoms():
     case, seed, m = O.load_case('EVT'), 42, 96
     n, L = len(case['grid_probs']), case['config']['total_laps']
@@ -112,8 +179,7 @@ def _resume_runs(case, seed, sims, base):
     return ref, runs
 
 
-def _concat(parts):
-    return {key: np.concatenate([p[key] for p in parts], axis=0) for key in parts[0]}
+_concat = CR.concat
 
 
 @pytest.mark.parametrize('name', CASES + ('corner', 'n1', 'n2', 'n3', 'n22', 'n32'))

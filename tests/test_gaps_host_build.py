@@ -2,9 +2,10 @@
 integers only, with references that do not share its code: the raw staging, decoded by the layout documented at the top
 of gaps.hip.h, against gaps_ref's numpy restatement over the CPU oracle's per-lap trace; the histogram against the
 oracle's.  Inputs (generic_cases.py): the 8 golden cases, the 84 fuzz configurations, two fields with tiny lap times,
-synthetic fields of 1, 2, 3, 19, 31 and 32 cars, a 1000-lap race.  The counting kernel and the host-side chunking are
-compared on the device (test_gpu_gaps.py).  The host build is test infrastructure: nothing under monte_carlo_gp_amd/ can
-reach it and the product has no CPU path."""
+synthetic fields of 1, 2, 3, 19, 31 and 32 cars, a 1000-lap race; all of them a second time at edges and pairs taken
+from the oracle's own trace: gaps it shows as edges, the next doubles above them, and pairs it shows tied.  The counting
+kernel and the host-side chunking are compared on the device (test_gpu_gaps.py, test_gpu_gaps_conditions_fuzz.py).  The
+host build is test infrastructure: nothing under monte_carlo_gp_amd/ can reach it and the product has no CPU path."""
 import copy
 
 import numpy as np
@@ -15,15 +16,11 @@ import generic_cases as G
 import oracle_py as O
 import resume_ref as RR
 
-RUN_SIMS, RESUME_SIMS = 32, 8
+RUN_SIMS, RESUME_SIMS, OWN_SIMS = 32, 8, 48
 KEYS = ('hist', 'lap_gap', 'lead', 'pair')
 
 
-def _pairs(n):
-    """A few pairs in both orientations; none for a field of one."""
-    if n < 2:
-        return []
-    return [(0, 1), (1, 0), (n - 1, 0), (n // 2, n - 1)] if n > 2 else [(0, 1), (1, 0)]
+_pairs = GR.few_pairs
 
 
 def _same(name, got, ref):
@@ -49,6 +46,51 @@ def test_gaps_kernel_from_the_grid_equals_the_restated_counts():
         done += name in G.fuzz_cases()
     assert done == G.N_FUZZ and len(G.run_inputs()) == 100
     assert filled > 100 * 8            # (the comparison is not one of constant rows)
+
+
+def _own(args):
+    """One input's traced run, the call it decides (gaps_ref.own_call) and the reference's staged values at the own edges
+    and at the next doubles above them."""
+    name, case, seed = args
+    ref = RR.traced_run(case, OWN_SIMS, seed, 3)
+    call = GR.own_call(ref)
+    tr, slot = ref['trace'], GR.slots_of(ref['grids'])
+    want = [GR.values_from_times(tr['cum'], tr['dnf'], slot, edges=e, pairs=call['pairs']) for e in (call['edges'], call['up'])]
+    return ref, call, want
+
+
+def test_gaps_kernel_at_the_oracles_own_gaps_and_ties():
+    """Every input at edges that are gaps the oracle's trace shows (63 of them, at evenly spaced ranks of the distinct
+    positive ones) and at the next double above each, with the pairs the trace shows at equal cumulative times: a time
+    off by an ulp, `<` for `<=` in the bin, or a tie decided otherwise than by grid slot moves a staged value here on
+    nearly every input.  (At the default edges and four fixed pairs above, `<` for `<=` shows on 31 inputs -- the model
+    does produce gaps equal to a default edge --, a reversed slot comparison on 5; here on 98 and on 31.)  What makes
+    that so is asserted from the reference alone."""
+    inputs = G.run_inputs()
+    full, tied, done = 0, set(), 0
+    for name, case, seed in inputs:
+        ref, call, (want, want_up) = _own((name, case, seed))
+        n = len(case['grid_probs'])
+        if call['own']:
+            moved = int((want != want_up).sum())
+            assert moved >= len(call['edges']), (name, moved)         # every edge decides a cell of the reference
+        else:
+            assert name in ('X_all_out_lap1', 'n1'), name              # no positive gap: nobody runs, or one car
+        full += call['own'] and len(call['edges']) == 63
+        if call['cells']:
+            tied.add(name)
+            a, b = call['pairs'][0]
+            assert call['pairs'][1] == (b, a)
+        for edges, ref_vals in ((call['edges'], want), (call['up'], want_up)):
+            hist, got = GH.gaps_values(case, OWN_SIMS, seed, sim_offset=3, edges=edges, pairs=call['pairs'])
+            bad = np.argwhere(got != ref_vals)
+            assert bad.size == 0, f'{name}: {len(bad)} staged values differ, first (simulation, lap - 1, row) ' \
+                                  f'{bad[:3].tolist()} of {n} drivers, 1 lead, pairs {call["pairs"][:4]}'
+            assert np.array_equal(hist, ref['hist']), name
+        done += name in G.fuzz_cases()
+    assert done == G.N_FUZZ and len(inputs) == 100
+    assert full >= 98, full
+    assert len(tied) >= 25 and {'X_no_noise', 'X_all_attempt'} <= tied, sorted(tied)
 
 
 def _resume_case(name, case, seed, m=RESUME_SIMS, base=40):
