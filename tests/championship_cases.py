@@ -2,7 +2,9 @@
 from championship_ref alone, that a season got there.
 
 TEST INFRASTRUCTURE, shared by the device tests (test_gpu_championship_limits.py), the host build of the kernels
-(test_champ_host_build.py) and the builders' own tests (test_championship_host.py).  A season is a dict:
+(test_champ_host_build.py), the by-round call's device and host-build tests (test_gpu_championship_rounds_limits.py,
+test_champ_rounds_host_build.py; their proofs read championship_rounds_ref's per-simulation view, "by round" below) and
+the builders' own tests (test_championship_host.py).  A season is a dict:
 case (an n-car race, S60's parameters), plan [(case, seed, 32, points table, countback)] as test_gpu_championship._check
 takes it, standings {driver: {'points', 'finishes'}}, n_sims, sim_offset.  Teams are case['config']['driver_teams'], in
 order of first appearance.
@@ -17,6 +19,7 @@ import json
 import numpy as np
 
 import championship_ref as CR
+import championship_rounds_ref as RR
 import oracle_py as O
 
 F1 = [25, 18, 15, 12, 10, 8, 6, 4, 2, 1]
@@ -137,6 +140,37 @@ def long_calendar(n=5, n_sims=300, seed=640):
                 sim_offset=3)
 
 
+def uneven_teams(n_sims=600, seed=4000):
+    """Seven cars in teams of 3, 2, 1 and 1, so that the points a team can still take (B_r(e), championship_rounds_ref)
+    differ from team to team: [43 35 22 22] after race 0, falling to [3 3 2 2] after race 4.  Five short Grands Prix
+    and a two-place sprint; the single-driver teams, the slowest cars, carry in 5 points each and the pair 2 + 2, so
+    that team totals stay within a few points of each other's bounds."""
+    team = [0, 0, 0, 1, 1, 2, 3]
+    case = field(7, pace_step=0.05, team=team)
+    drivers = list(case['grid_probs'])
+    tables = [[5, 3, 2, 1]] * 5 + [[2, 1]]
+    plan = [(case, seed + r, 32, tables[r], r < 5) for r in range(6)]
+    carried = [0, 0, 0, 2, 2, 5, 5]
+    return dict(case=case, plan=plan, standings={d: {'points': carried[i], 'finishes': []} for i, d in enumerate(drivers)},
+                n_sims=n_sims, sim_offset=3)
+
+
+DUEL_GAP, DUEL_ROW = 103, 20
+
+
+def procession_duel(n, n_sims=200, seed=500):
+    """procession(n) with a rival: driver 1 carries in 103 points fewer than driver 0.  In a procession driver 0 gains
+    25 a race and driver 1 gains 18, so after race index 20 the gap is 103 + 7 x 21 = 250 = 25 x 10 = M_20, exactly the
+    bound, and one race later driver 1 is out.  There both totals are above 65 000: bit 15 of both points fields is
+    set, and lead - points is a difference of two such fields."""
+    season = procession(n, n_sims=n_sims, seed=seed)
+    drivers = list(season['case']['grid_probs'])
+    lead = season['standings'][drivers[0]]['points']
+    assert lead == MAX_POINTS - 775 and DUEL_GAP + 7 * (DUEL_ROW + 1) == 25 * (30 - DUEL_ROW)
+    season['standings'][drivers[1]] = {'points': lead - DUEL_GAP, 'finishes': []}
+    return season
+
+
 # ------------------------------------------------------------------------------------------------ team layouts
 def bits(x):
     b = 1
@@ -162,10 +196,29 @@ def team_layout(season):
     return bits(max_c), (bits(max_p) + bits(max_c) * n + 63) // 64
 
 
+def team_points_bits(season):
+    """Bits of the points field of the season's team keys by team_layout's rule: what the largest total a team can
+    reach needs.  The field starts at bit n x count bits."""
+    team, T = team_of(season)
+    n = len(team)
+    ip, _ = standings_arrays(season)
+    tables = [list(p[3][:n]) + [0] * (n - len(p[3][:n])) for p in season['plan']]
+    G, awarded = sum(max(t) for t in tables), sum(sum(t) for t in tables)
+    return bits(max(int(ip[[d for d in range(n) if team[d] == t]].sum()) + min(team.count(t) * G, awarded) for t in range(T)))
+
+
 def rank_lds_bytes(n, T, team_words, gain_cols, gain_in_lds):
     """champ_rank_lds (csrc/championship.hip.h) restated: the rank kernel's LDS."""
     words = (16 + 5 * n + 63) // 64
     b = words * n * 64 * 8 + team_words * T * 64 * 8 + n * n * 4 + T * T * 4 + (n * gain_cols * 4 if gain_in_lds else 0)
+    return (b + 15) // 16 * 16
+
+
+def round_lds_bytes(n, T, team_words):
+    """champ_round_lds (csrc/champ_rounds.hip.h) restated: the by-round kernel's LDS.  Driver keys, team keys, six rows
+    of 64 u32 per simulation, and the u32 histograms n x n + 2 n + T x T + 2 T.  T = 0: drivers only."""
+    words = (16 + 5 * n + 63) // 64
+    b = words * n * 64 * 8 + team_words * T * 64 * 8 + 6 * 64 * 4 + (n * n + 2 * n + T * T + 2 * T) * 4
     return (b + 15) // 16 * 16
 
 
@@ -212,6 +265,16 @@ def team_seasons():
         'singletons_9': (tie_rich(9, team=list(range(9))), 1),         # no carried-in counts: 3-bit counts, 16 + 27 bits
         'quads_27': (tie_rich(27, team=[i // 4 for i in range(27)]), 4),   # 4 x 15 + 4: 7-bit counts, 18-bit points: 207 bits
     }
+
+
+def team_points_borrow(n=20):
+    """Pairs whose totals start 4 short of 2^16 (32 766 a driver), tie-rich: within two races the leading team is past
+    65 536 with rivals still below it and within the bound, so lead - points borrows across bit 16 of a 17-bit points
+    field -- and across the word boundary, since the field starts at bit 120 (6-bit counts x 20) and has its 8 low
+    bits in the lower word.  The seasons of team_seasons() carry in 40 000 a driver: their teams' totals, level to
+    within a few points, never lie on two sides of such a boundary, and there a points field read short gives the
+    same difference as the whole one."""
+    return tie_rich(n, team=pairs(n), points=(1 << 15) - 2)
 
 
 # ------------------------------------------------------------------------------------------------ the reference
@@ -289,6 +352,129 @@ def assert_team_edges(name, season, tp, tc):
     else:
         # adjacent teams are told apart by the points and by each of the first eight count fields
         assert (depth[:min(9, n - 1)] > 0).all(), depth
+
+
+# ------------------------------------------------------------------------------------------------ by round
+def season_args(season):
+    """(tables, countback, team, T, initial points, initial counts) as championship_rounds_ref takes them."""
+    team, T = team_of(season)
+    ip, ic = standings_arrays(season)
+    return [p[3] for p in season['plan']], [int(p[4]) for p in season['plan']], team, T, ip, ic
+
+
+_rounds = {}
+
+
+def reference_rounds(season):
+    """championship_rounds_ref.per_simulation of the season on the oracle's orders (kept, like the orders; read only)."""
+    key = json.dumps([season['case'], [p[1:] for p in season['plan']], season['standings'], season['n_sims'],
+                      season['sim_offset']], sort_keys=True)
+    if key not in _rounds:
+        _rounds[key] = RR.per_simulation(oracle_orders(season), *season_args(season))
+    return _rounds[key]
+
+
+def assert_uneven_team_edges(per):
+    """uneven_teams() tells a team's own bound B_r(e) from any other team's.  Over the rows before the last, among the
+    non-leading teams: those exactly on their own bound, and the in-or-out decisions that come out differently when the
+    bound is the leader's, the round's largest, the round's smallest.  Measured on the CPU oracle: 151, 899, 916 and
+    262, with some but not all team titles secure in rows 2, 3 and 4."""
+    sizes = {tuple(int(b) for b in s['B']) for s in per[:-1]}
+    assert all(len(set(b)) > 1 for b in sizes), sizes                      # the bounds differ within every such row
+    on = by_leader = by_largest = by_smallest = 0
+    for s in per[:-1]:
+        lead = s['tp'].max(axis=1)
+        gap = lead[:, None] - s['tp']
+        non = s['tpos'] != 0
+        leader = np.argmax(s['tpos'] == 0, axis=1)
+        own = gap <= s['B'][None, :]
+        assert np.array_equal(own | ~non, s['tcontend'])
+        on += int(((gap == s['B'][None, :]) & non).sum())
+        by_leader += int(((own != (gap <= s['B'][leader][:, None])) & non).sum())
+        by_largest += int(((own != (gap <= s['B'].max())) & non).sum())
+        by_smallest += int(((own != (gap <= s['B'].min())) & non).sum())
+    e = dict(on_own_bound=on, differ_under_leaders_bound=by_leader, differ_under_largest_bound=by_largest,
+             differ_under_smallest_bound=by_smallest)
+    assert min(e.values()) >= 50, e
+    n_sims = len(per[0]['tp'])
+    assert sum(0 < int(s['tsecure'].sum()) < n_sims for s in per) >= 3, 'three partly decided rounds'
+    return e
+
+
+def assert_duel_edges(per):
+    """procession_duel(n): in at least 100 seasons driver 1 is in contention through row 20 and out from row 21, sits
+    exactly on the bound M_20 = 250 behind the leading driver 0 in row 20, and driver 0 ends on 65 535 points; in those
+    seasons both points fields of row 20 have bit 15 set.  Measured on the CPU oracle: all 200 seasons, at 20 and at
+    32 cars."""
+    assert len(per) == 31
+    inside = np.array([s['contend'][:, 1] for s in per])
+    through = inside[:DUEL_ROW + 1].all(axis=0) & ~inside[DUEL_ROW + 1:].any(axis=0)
+    s = per[DUEL_ROW]
+    assert s['M'] == 25 * (30 - DUEL_ROW)
+    on = (s['pos'][:, 0] == 0) & (s['pts'][:, 0] - s['pts'][:, 1] == s['M'])
+    all_three = through & on & (per[-1]['pts'][:, 0] == MAX_POINTS)
+    assert all_three.sum() >= 100, (through.sum(), on.sum(), all_three.sum())
+    assert ((s['pts'][all_three][:, :2] >> 15) == 1).all()
+    return int(all_three.sum())
+
+
+def assert_team_round_edges(name, season, per):
+    """What the by-round kernel alone reads of a team key, the points field above n count fields, matters in the team
+    seasons: in some row before the last the leading team's total needs the top bit of the layout's points field, and
+    it exceeds 65 535 wherever that field is wider than 16 bits, so a read cut to 16 bits or to one word changes
+    lead - points.  uneven_pairs_20 and quads_27: some non-leading team is in contention in some simulations of a row
+    and out in others."""
+    cbits, words = team_layout(season)
+    assert words == team_seasons_words()[name]
+    pbits = team_points_bits(season)
+    assert (pbits + cbits * len(team_of(season)[0]) + 63) // 64 == words
+    leads = [s['tp'].max(axis=1) for s in per]
+    for s, lead in zip(per, leads):
+        assert np.array_equal(lead, (s['tp'] * (s['tpos'] == 0)).sum(axis=1))
+    assert any(((lead >> (pbits - 1)) == 1).any() for lead in leads[:-1]), pbits
+    if pbits > 16:
+        assert all((lead > MAX_POINTS).all() for lead in leads), pbits
+    if name in ('uneven_pairs_20', 'quads_27'):
+        mixed = 0
+        for s in per[:-1]:
+            non = s['tpos'] != 0
+            inside, outside = (s['tcontend'] & non).sum(axis=0), (~s['tcontend'] & non).sum(axis=0)
+            mixed += int(((inside > 0) & (outside > 0)).sum())
+        assert mixed >= 1, name
+    return pbits
+
+
+def assert_team_borrow_edges(season, per):
+    """team_points_borrow(): the team points field is wider than 16 bits and straddles a word, and over the rows before
+    the last at least 50 non-leading teams are in contention with a total below 2^16 under a leader at or above it:
+    the difference of the two fields' low 16 bits, or of their pieces in the lower word, is not lead - points.
+    Measured on the CPU oracle: 882, 3603, 3905 and 637 such cells in rows 0 to 3."""
+    cbits, words = team_layout(season)
+    pbits, off = team_points_bits(season), cbits * len(team_of(season)[0])
+    low = 64 - off % 64
+    assert pbits > 16 and 0 < low < pbits and low <= 16, (pbits, off)
+    across = 0
+    for s in per[:-1]:
+        lead = s['tp'].max(axis=1)[:, None]
+        hit = s['tcontend'] & (s['tpos'] != 0) & (lead >= 1 << 16) & (s['tp'] < 1 << 16)
+        assert ((lead - s['tp'])[hit] <= s['B'][None, :].repeat(len(lead), 0)[hit]).all()
+        assert (((lead & 0xFFFF) < (s['tp'] & 0xFFFF)) | ~hit).all() and (((lead >> low) != (s['tp'] >> low)) | ~hit).all()
+        across += int(hit.sum())
+    assert across >= 50, across
+    return across
+
+
+def assert_long_calendar_rounds(per, n_sims):
+    """64 rows, M falling to 0, and the drivers' title secure in some but not all seasons in at least three rows."""
+    assert len(per) == 64 and per[0]['M'] > per[32]['M'] > per[62]['M'] > per[63]['M'] == 0
+    assert sum(0 < int(s['secure'].sum()) < n_sims for s in per) >= 3
+
+
+def assert_some_in_some_out(s):
+    """One row of per_simulation: among the non-leaders, drivers and teams, some are in contention and some are out."""
+    for pos, con in ((s['pos'], s['contend']), (s['tpos'], s['tcontend'])):
+        non = pos != 0
+        assert (con & non).sum() >= 100 and (~con & non).sum() >= 100, ((con & non).sum(), (~con & non).sum())
 
 
 def tail_bytes(n, n_sims):

@@ -16,11 +16,12 @@ def _perms(rng, sims, n):
     return rng.permuted(np.tile(np.arange(n, dtype=np.uint8), (sims, 1)), axis=1)
 
 
-def _compare(orders, tables, cb, team, T, ip=None, ic=None, **kw):
-    """The host build against the restatement; returns (the host build's output, the reference's per-simulation view)."""
+def _compare(orders, tables, cb, team, T, ip=None, ic=None, per=None, **kw):
+    """The host build against the restatement; returns (the host build's output, the reference's per-simulation view).
+    per: the reference's view of these very arguments, when the caller has it."""
     sims, n = orders[0].shape
     out = H.rounds_run(orders, tables, cb, team, T, ip, ic, **kw)
-    per = RR.per_simulation(orders, tables, [int(c) for c in cb], team, T, ip, ic)
+    per = per or RR.per_simulation(orders, tables, [int(c) for c in cb], team, T, ip, ic)
     ref = RR.rounds(orders, tables, cb, team, T, sims=per)
     M, B = RR.remaining(tables, n, team, T)
     assert np.array_equal(out['rem'][0], M) and np.array_equal(out['rem'][1], B)
@@ -172,3 +173,65 @@ def test_decisive_season():
     assert (e['driver_on_bound'], e['team_on_bound'], e['final_points_ties']) == (525, 129, 5)
     assert [int(s['secure'].sum()) for s in per] == [0, 0, 0, 57, 233, 326, 400]
     _compare(orders, tables, cb, team, T, ip, None, round_grid=2)
+
+
+# ---------------------------------------------------------------- the limit seasons of championship_cases.py, by round
+# (what tests/test_gpu_championship_rounds_limits.py runs on the device: the same seasons, after the same proofs)
+def _limit_season(season, per):
+    """The season on the oracle's orders on one block and on three; the restated LDS size is the kernel's."""
+    args = CC.season_args(season)
+    outs = [_compare(CC.oracle_orders(season), *args, per=per, round_grid=g)[0] for g in (1, 3)]
+    n, T = len(args[2]), args[3]
+    assert outs[0]['info']['lds_bytes'] == CC.round_lds_bytes(n, T, outs[0]['info']['team_words'])
+    assert outs[0]['info']['team_words'] == CC.team_layout(season)[1]
+    return outs[0]
+
+
+def test_uneven_team_bounds():
+    """Teams of 3, 2, 1 and 1: every team is tested against its own B_r(e), where the leader's, the largest and the
+    smallest bound of the round each decide hundreds of cells differently."""
+    season = CC.uneven_teams()
+    per = CC.reference_rounds(season)
+    CC.assert_uneven_team_edges(per)
+    out = _limit_season(season, per)
+    assert [list(b) for b in out['rem'][1][[0, 4]]] == [[43, 35, 22, 22], [3, 3, 2, 2]]
+
+
+@pytest.mark.parametrize('n', [20, 32])
+def test_procession_duel_at_the_points_limit(n):
+    """A leader that ends on 65 535 points and a rival exactly on the bound in row 20, out in row 21: lead - points
+    between two points fields with bit 15 set."""
+    season = CC.procession_duel(n)
+    per = CC.reference_rounds(season)
+    CC.assert_duel_edges(per)
+    out = _limit_season(season, per)
+    assert (out['contend'][:21, 1] >= 100).all() and (out['contend'][21:, 1] <= 100).all()
+
+
+def test_calendar_of_64_races_by_round():
+    """64 launches and 64 rows of every output, 31 races that count back."""
+    season = CC.long_calendar()
+    per = CC.reference_rounds(season)
+    CC.assert_long_calendar_rounds(per, season['n_sims'])
+    out = _limit_season(season, per)
+    assert out['round_hist'].shape[0] == 64 and (np.diff(out['secure'], axis=0) >= 0).all()
+
+
+@pytest.mark.parametrize('name', ['pairs_32', 'uneven_pairs_20', 'quads_27'])
+def test_team_points_field_by_round(name):
+    """The team seasons that test_wide_team_keys leaves out, each after the by-round proof: the leading team's total
+    needs the top bit of a 17- or 18-bit points field that starts above 120 to 192 bits of counts."""
+    season, _ = CC.team_seasons()[name]
+    per = CC.reference_rounds(season)
+    CC.assert_team_round_edges(name, season, per)
+    _limit_season(season, per)
+
+
+def test_team_points_borrow_across_bit_16_and_a_word():
+    """Rival teams just below 2^16 under a leader just above it, within the bound: lead - points borrows across bit 16
+    of the team points field and across the word boundary inside it.  A field read with 16 bits, or from its lower
+    word alone, gives another difference here and in no other season."""
+    season = CC.team_points_borrow()
+    per = CC.reference_rounds(season)
+    CC.assert_team_borrow_edges(season, per)
+    _limit_season(season, per)

@@ -303,6 +303,40 @@ def test_gain_seasons_take_their_path_and_reach_both_ends(name):
     assert (gain == 0).sum() >= 50 and (gain == G).sum() >= 50
 
 
+def test_uneven_teams_season_tells_the_bounds_apart():
+    e = CC.assert_uneven_team_edges(CC.reference_rounds(CC.uneven_teams()))
+    assert list(e.values()) == [151, 899, 916, 262], e
+
+
+@pytest.mark.parametrize('n', [20, 32])
+def test_procession_duel_sits_on_the_bound_in_row_20(n):
+    assert CC.assert_duel_edges(CC.reference_rounds(CC.procession_duel(n))) == 200
+
+
+def test_long_calendar_by_round():
+    season = CC.long_calendar()
+    CC.assert_long_calendar_rounds(CC.reference_rounds(season), season['n_sims'])
+
+
+@pytest.mark.parametrize('name', list(CC.team_seasons()))
+def test_team_seasons_need_the_whole_points_field_by_round(name):
+    season, _ = CC.team_seasons()[name]
+    pbits = CC.assert_team_round_edges(name, season, CC.reference_rounds(season))
+    assert pbits == {'six_words': 21, 'one_team_32': 21, 'one_team_20': 20, 'quads_27': 18}.get(name, 16 if 'singletons' in name else 17)
+
+
+def test_team_points_borrow_season_straddles_bit_16():
+    season = CC.team_points_borrow()
+    assert CC.team_layout(season) == (6, 3) and CC.team_points_bits(season) == 17
+    assert CC.assert_team_borrow_edges(season, CC.reference_rounds(season)) == 882 + 3603 + 3905 + 637
+
+
+def test_round_lds_restated():
+    """DESIGN 3.7.1's two figures: 32 drivers in 32 teams with six-word team keys; 20 drivers in 10 teams of two."""
+    assert CC.round_lds_bytes(32, 32, 6) == 157696 and CC.round_lds_bytes(20, 10, 2) == 34496
+    assert CC.round_lds_bytes(3, 0, 1) == (3 * 64 * 8 + 6 * 64 * 4 + (9 + 6) * 4 + 15) // 16 * 16
+
+
 def test_tail_seasons_leave_one_two_and_three_bytes():
     for n in (9, 23, 31):
         assert sorted(CC.tail_bytes(n, k) for k in (501, 502, 503)) == [1, 2, 3]

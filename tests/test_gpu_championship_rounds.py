@@ -1,6 +1,9 @@
 """mcgp_run_championship_rounds on the device: the standings, contention and secure titles after every race equal
 championship_rounds_ref fed with the CPU oracle's finishing orders, count for count, and the four season outputs equal
-mcgp_run_championship's.  No tolerance anywhere."""
+mcgp_run_championship's.  No tolerance anywhere.
+
+Wall time on one MI355X, behind test_gpu_championship_rounds_limits.py in one pytest command: 2.3 s for the 12 tests
+here, 1.5 s of it the six-race season of 3000 simulations with its oracle runs."""
 import ctypes as C
 import json
 
