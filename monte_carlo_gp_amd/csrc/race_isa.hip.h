@@ -300,6 +300,82 @@ __device__ __forceinline__ void ovt_threshold(double dl, double od, uint32_t row
     }
 }
 
+// ---- overtake commits under EXEC ----
+// The write-back chain of an overtake pass (reference :523-531): per adjacent pair (ahead, behind) with draw word w and
+// threshold t, a success (w < t) sets  behind = ahead - 0.1,  ahead = behind + 0.3,  each rounded once, and the next pair
+// sees the result.  A value that is computed and then kept or dropped needs no selects: v_cmpx narrows EXEC to the lanes
+// whose attempt succeeded, the two additions write in place under it, and the scalar unit -- not the bottleneck -- ORs the
+// pair's hits (VCC: v_cmpx writes both) into `acc` and restores EXEC.  3 VALU instructions per pair instead of 7.
+// EXEC is saved once per statement and is back at its entry value when the statement ends: the compiler never sees a
+// changed mask.  A lane that is off at entry (it has left the pass loop) stays off throughout -- v_cmpx only clears
+// bits -- and contributes 0 to `acc`.  Wait states: an ordinary VALU instruction takes its lane mask from EXEC
+// interlocked, whoever wrote it (the manual's EXEC hazards are DPP, v_readlane / v_writelane and EXECZ / VCCZ as data,
+// none of which is here); the scalar reads of VCC and the scalar writes of EXEC are interlocked too.  -0.1 and 0.3
+// come in SGPR pairs (VOP3 has no literals on gfx9).  Several pairs per statement for the reason given above.
+#define MCGP_OVT_PAIR(a, b, w, t)                                                                                       \
+    "v_cmpx_lt_u32 vcc, %[" #w "], %[" #t "]\n\t"                                                                       \
+    "v_add_f64 %[" #b "], %[" #a "], %[dn]\n\t"                                                                         \
+    "v_add_f64 %[" #a "], %[" #b "], %[up]\n\t"                                                                         \
+    "s_or_b64 %[acc], %[acc], vcc\n\t"                                                                                  \
+    "s_mov_b64 exec, %[ex]\n\t"
+#define MCGP_OVT_CONSTS [dn] "s"(-0.1), [up] "s"(0.3)
+
+__device__ __forceinline__ void ovt_commit1(double &c0, double &c1, uint32_t w1, uint32_t t1, uint64_t &acc)
+{
+    uint64_t ex;
+    asm volatile("s_mov_b64 %[ex], exec\n\t"
+                 MCGP_OVT_PAIR(c0, c1, w1, t1)
+                 : [c0] "+v"(c0), [c1] "+v"(c1), [acc] "+s"(acc), [ex] "=&s"(ex)
+                 : [w1] "v"(w1), [t1] "v"(t1), MCGP_OVT_CONSTS
+                 : "vcc");
+}
+__device__ __forceinline__ void ovt_commit2(double &c0, double &c1, double &c2, uint32_t w1, uint32_t t1, uint32_t w2, uint32_t t2,
+                                            uint64_t &acc)
+{
+    uint64_t ex;
+    asm volatile("s_mov_b64 %[ex], exec\n\t"
+                 MCGP_OVT_PAIR(c0, c1, w1, t1)
+                 MCGP_OVT_PAIR(c1, c2, w2, t2)
+                 : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [acc] "+s"(acc), [ex] "=&s"(ex)
+                 : [w1] "v"(w1), [t1] "v"(t1), [w2] "v"(w2), [t2] "v"(t2), MCGP_OVT_CONSTS
+                 : "vcc");
+}
+__device__ __forceinline__ void ovt_commit3(double &c0, double &c1, double &c2, double &c3, uint32_t w1, uint32_t t1, uint32_t w2,
+                                            uint32_t t2, uint32_t w3, uint32_t t3, uint64_t &acc)
+{
+    uint64_t ex;
+    asm volatile("s_mov_b64 %[ex], exec\n\t"
+                 MCGP_OVT_PAIR(c0, c1, w1, t1)
+                 MCGP_OVT_PAIR(c1, c2, w2, t2)
+                 MCGP_OVT_PAIR(c2, c3, w3, t3)
+                 : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3), [acc] "+s"(acc), [ex] "=&s"(ex)
+                 : [w1] "v"(w1), [t1] "v"(t1), [w2] "v"(w2), [t2] "v"(t2), [w3] "v"(w3), [t3] "v"(t3), MCGP_OVT_CONSTS
+                 : "vcc");
+}
+__device__ __forceinline__ void ovt_commit4(double &c0, double &c1, double &c2, double &c3, double &c4, uint32_t w1, uint32_t t1,
+                                            uint32_t w2, uint32_t t2, uint32_t w3, uint32_t t3, uint32_t w4, uint32_t t4, uint64_t &acc)
+{
+    uint64_t ex;
+    asm volatile("s_mov_b64 %[ex], exec\n\t"
+                 MCGP_OVT_PAIR(c0, c1, w1, t1)
+                 MCGP_OVT_PAIR(c1, c2, w2, t2)
+                 MCGP_OVT_PAIR(c2, c3, w3, t3)
+                 MCGP_OVT_PAIR(c3, c4, w4, t4)
+                 : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3), [c4] "+v"(c4), [acc] "+s"(acc), [ex] "=&s"(ex)
+                 : [w1] "v"(w1), [t1] "v"(t1), [w2] "v"(w2), [t2] "v"(t2), [w3] "v"(w3), [t3] "v"(t3), [w4] "v"(w4), [t4] "v"(t4),
+                   MCGP_OVT_CONSTS
+                 : "vcc");
+}
+#undef MCGP_OVT_CONSTS
+#undef MCGP_OVT_PAIR
+// this lane's bit of the hits accumulated by the commits of a pass: one VOP3 select on the SGPR pair
+__device__ __forceinline__ bool ovt_lane_hit(uint64_t acc)
+{
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(r) : "s"(acc));
+    return r != 0u;
+}
+
 // LDS access by ABSOLUTE byte address.  The register kernel declares no static __shared__ data, so its
 // dynamic LDS block starts at address 0 (checked once at kernel entry); addressing it by number instead of
 // through the `extern __shared__` symbol lets the compiler fold every table / row base into the 16-bit

@@ -116,6 +116,12 @@ __host__ __device__ constexpr size_t shared_lds_bytes_reg(int n)
 // 42.3 at 2, 51.1 at 3 (the LDS rows of 23 cars leave room for 10 waves per CU only).  N = 4 is the one irregular
 // entry: above 4 waves the compiler moves its arrays to scratch (288 B per lane) and it runs 2-4x slower.
 __host__ __device__ constexpr int reg_min_waves(int n) { return n <= 6 ? (n == 4 ? 4 : 6) : n <= 11 ? 4 : n <= 22 ? 3 : 2; }
+// Field sizes whose overtake chain commits by selects instead of under EXEC (reg_simulate, "success test and write-back
+// chain"): the ones where the EXEC form makes an instantiation spill more (scratch bytes per lane, select form -> EXEC
+// form: N = 6 156 -> 172, N = 8 batch 92 -> 96, N = 9 0 -> 180, N = 10 0 -> 196, N = 24 / 25 reference width 40 -> 44 /
+// 56 -> 60; everywhere else scratch stays or falls).  The small ones run at 4 and more waves per SIMD on 128 VGPRs or
+// fewer, where the chain's fixed registers -- the times are updated in place -- leave the allocator no slack.
+__host__ __device__ constexpr bool reg_commit_by_selects(int n) { return n == 6 || (n >= 8 && n <= 10) || n == 24 || n == 25; }
 // Waves per block: the (waves per block, blocks per CU) pair that keeps the most waves resident within the LDS
 // budget and the kernel's waves per SIMD; among equals a multiple of 4 waves per block (a block's waves go round the
 // 4 SIMDs: two blocks of 6 load them 4, 4, 2, 2), then the block nearest to 8 waves (1024-thread blocks make the
@@ -381,6 +387,25 @@ __device__ __forceinline__ void bubble_backward(double (&c)[N], uint32_t (&p)[N]
         bubble_bwd2(c[0], p[0], c[1], p[1], c[2], p[2]);
     } else if constexpr (T == 1) {
         cmpx_time(c[0], p[0], c[1], p[1]);
+    }
+}
+
+// The write-back chain of an overtake pass from pair I on: pairs (I-1, I), (I, I+1), .. (N-2, N-1) in sequence, each
+// committed under EXEC (ovt_commit*), four to an instruction block; `acc` gathers the lanes with a success.
+template <int N, int I>
+__device__ __forceinline__ void overtake_commits(double (&c)[N], const uint32_t (&w)[N], const uint32_t (&t)[N], uint64_t &acc)
+{
+    constexpr int left = N - I;
+    if constexpr (left >= 4) {
+        ovt_commit4(c[I - 1], c[I], c[I + 1], c[I + 2], c[I + 3], w[I], t[I], w[I + 1], t[I + 1], w[I + 2], t[I + 2], w[I + 3], t[I + 3],
+                    acc);
+        overtake_commits<N, I + 4>(c, w, t, acc);
+    } else if constexpr (left == 3) {
+        ovt_commit3(c[I - 1], c[I], c[I + 1], c[I + 2], w[I], t[I], w[I + 1], t[I + 1], w[I + 2], t[I + 2], acc);
+    } else if constexpr (left == 2) {
+        ovt_commit2(c[I - 1], c[I], c[I + 1], w[I], t[I], w[I + 1], t[I + 1], acc);
+    } else if constexpr (left == 1) {
+        ovt_commit1(c[I - 1], c[I], w[I], t[I], acc);
     }
 }
 
@@ -1766,17 +1791,26 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                     }
                 }
                 // ---- overtakes: success test and write-back chain ----
-                // :523-531 in sorted order, each pair seeing the previous pair's mutation (Q15).  Branch-free: the
-                // new times of a pair are computed for every slot and committed by selects under the success mask.
+                // :523-531 in sorted order, each pair seeing the previous pair's mutation (Q15).  Branch-free: per pair
+                // hit = ow < thr,  behind = max(0.1, ahead - 0.1) = ahead - 0.1 (:528, reg_time_floor()),  ahead = behind + 0.3
+                // (:530), the two additions issued under EXEC narrowed to the lanes with a hit and written in place
+                // (ovt_commit*, race_isa.hip.h).  The field sizes of reg_commit_by_selects() compute the new times of a
+                // pair for every lane and commit them by four selects under the success mask.
                 bool any_succ = false;
+                if constexpr (reg_commit_by_selects(N)) {
 #pragma unroll
-                for (int i = 1; i < N; ++i) {
-                    const bool hit = ow[i] < thr[i];
-                    const double nb = cum[i - 1] - 0.1;                        // max(0.1, ahead - 0.1), :528: reg_time_floor()
-                    const double na = nb + 0.3;                                // :530
-                    cum[i] = hit ? nb : cum[i];
-                    cum[i - 1] = hit ? na : cum[i - 1];
-                    any_succ |= hit;
+                    for (int i = 1; i < N; ++i) {
+                        const bool hit = ow[i] < thr[i];
+                        const double nb = cum[i - 1] - 0.1;
+                        const double na = nb + 0.3;
+                        cum[i] = hit ? nb : cum[i];
+                        cum[i - 1] = hit ? na : cum[i - 1];
+                        any_succ |= hit;
+                    }
+                } else {
+                    uint64_t hit_lanes = 0u;     // wave mask of the lanes with a success in this pass (an SGPR pair)
+                    overtake_commits<N, 1>(cum, ow, thr, hit_lanes);
+                    any_succ = ovt_lane_hit(hit_lanes);
                 }
                 MCGP_STAT(4 + pass, any_succ);
                 MCGP_STAT(8, n_attempts);

@@ -2,6 +2,9 @@
 //   A  the kernel's form (race_isa.hip.h cmpx_time): v_cmp_gt_f64 vcc; v_min_f64; v_max_f64; 2 x v_cndmask_b32 (payload)
 //   B  v_cmpx_gt_f64 (EXEC := the lanes that swap); 3 x v_swap_b32 (time low, time high, payload); s_mov_b64 exec, saved
 //   C  v_cmp_gt_f64 vcc; s_and_b64 exec, saved, vcc; 3 x v_swap_b32; s_mov_b64 exec, saved
+//   S  the write-back chain of an overtake pass by selects: v_cmp_lt_u32 vcc; 2 x v_add_f64; 4 x v_cndmask_b32; s_or_b64 (hit lanes)
+//   E  the same under EXEC (race_isa.hip.h ovt_commit*): v_cmpx_lt_u32; 2 x v_add_f64 in place; s_or_b64; s_mov_b64 exec, saved
+//      (S and E as chains of 15 dependent pairs only; "comparator" in the output is then one pair)
 // each as layers of 8 independent comparators (the sorting network) and as a chain of 15 dependent ones (a bubble pass).
 // The loop bodies are written on fixed registers (v[10:41] = 16 times, v50..v65 = 16 payloads): inline assembly cannot
 // name the halves of a 64-bit operand, which form B needs.
@@ -25,7 +28,9 @@ int main()
                           {"B layers (cmpx, 3 swaps, restore)", k_B_layer, 16}, {"C layers (cmp, s_and exec, 3 swaps, restore)", k_C_layer, 16},
                           {"D layers (cmpx, payload swap, restore, min, max + 2 moves)", k_D_layer, 16},
                           {"A chain", k_A_chain, 15}, {"A0 chain", k_A0_chain, 15}, {"B chain", k_B_chain, 15}, {"C chain", k_C_chain, 15},
-                          {"D chain", k_D_chain, 15}};
+                          {"D chain", k_D_chain, 15},
+                          {"S chain (overtake commit: cmp, 2 add, 4 cndmask)", k_S_chain, 15},
+                          {"E chain (overtake commit: cmpx, 2 add in place, restore)", k_E_chain, 15}};
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;

@@ -105,6 +105,34 @@ inline void ovt_threshold(double dl, double od, uint32_t row, uint32_t &thr, uin
     thr = c ? min_u32(cvt_u32_f64_sat(CEIL ? std::ceil(dl) : dl), 0x80000000u) : 0u;
     next = row + (c ? stride : 0u);
 }
+// overtake commits (reference :523-531): the portable loop body; `acc` is the one emulated lane's hit bit
+inline void ovt_commit1(double &c0, double &c1, uint32_t w1, uint32_t t1, uint64_t &acc)
+{
+    const bool hit = w1 < t1;
+    const double nb = c0 - 0.1;
+    const double na = nb + 0.3;
+    c1 = hit ? nb : c1;
+    c0 = hit ? na : c0;
+    acc |= hit ? 1u : 0u;
+}
+inline void ovt_commit2(double &c0, double &c1, double &c2, uint32_t w1, uint32_t t1, uint32_t w2, uint32_t t2, uint64_t &acc)
+{
+    ovt_commit1(c0, c1, w1, t1, acc);
+    ovt_commit1(c1, c2, w2, t2, acc);
+}
+inline void ovt_commit3(double &c0, double &c1, double &c2, double &c3, uint32_t w1, uint32_t t1, uint32_t w2, uint32_t t2, uint32_t w3,
+                        uint32_t t3, uint64_t &acc)
+{
+    ovt_commit2(c0, c1, c2, w1, t1, w2, t2, acc);
+    ovt_commit1(c2, c3, w3, t3, acc);
+}
+inline void ovt_commit4(double &c0, double &c1, double &c2, double &c3, double &c4, uint32_t w1, uint32_t t1, uint32_t w2, uint32_t t2,
+                        uint32_t w3, uint32_t t3, uint32_t w4, uint32_t t4, uint64_t &acc)
+{
+    ovt_commit3(c0, c1, c2, c3, w1, t1, w2, t2, w3, t3, acc);
+    ovt_commit1(c3, c4, w4, t4, acc);
+}
+inline bool ovt_lane_hit(uint64_t acc) { return acc != 0u; }
 // threads of the emulated block run one after another: "any lane" is this thread alone (both paths behind an
 // MCGP_ANY test compute the same results, so which one a thread takes does not matter); EMU_FORCE_ANY=1 sends every
 // thread down the "some lane needs it" path, which a single-thread view would otherwise reach only rarely
