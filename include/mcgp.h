@@ -34,7 +34,7 @@ extern "C" {
 /* 5: mcgp_race_state, mcgp_run_from_state */
 /* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
- * mcgp_run_championship_rounds likewise */
+ * mcgp_run_championship_rounds likewise; mcgp_run_conditions and mcgp_run_stints too */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -470,6 +470,47 @@ int32_t mcgp_run_conditions(const mcgp_config *cfg, const mcgp_drivers *drv, con
                             const mcgp_race_state *state, uint32_t n, uint32_t n_conditions,
                             const mcgp_condition *conditions, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
                             int32_t device, uint64_t *hist_out, uint64_t *count_out, uint64_t *cond_hist_out);
+
+/* Tyre stints: when the race model pits each driver, which compound sequence it runs and how a driver's finishing
+ * positions split by stop count, counted on the device, from the grid or from a mid-race state.  Everything is read from
+ * the race model's state after the end of lap k (its update_positions; where mcgp_run_trace reads), L = cfg->total_laps.
+ *   - recorded laps: from the grid laps 2 .. L (lap 1 has no pit step and no race event); from a state laps state->lap +
+ *     1 .. L (stops before the state's lap are unknown and not counted);
+ *   - pit stop on lap k: the car is running after lap k with tyre age 0 (mcgp_run_trace's definition); red-flag change
+ *     on lap k: lap k's event is a red flag and the car is running after lap k;
+ *   - stints: a car begins a new stint on a recorded lap with a pit stop or a red-flag change (both on one lap: one
+ *     stint), on the compound it has after that lap.  Stint 0 is on the compound the race starts on (from a state:
+ *     state->compound[d], for retired cars too), so every car has at least one; a car's stops and stints count up to
+ *     its retirement;
+ *   - simulations: from the grid (state NULL, grid_probs given) ids sim_offset .. sim_offset + n_sims - 1 with the draws
+ *     of mcgp_run's simulation i; from a state (grid_probs NULL, one mcgp_race_state) the draws and rules of
+ *     mcgp_run_from_state with sim_offsets[0] = sim_offset.
+ *   hist_out       [n][n]          [driver][position - 1]: equal to mcgp_run's / mcgp_run_from_state's for the same ids
+ *   stop_lap_out   [n][4][L + 1]   [driver][k][lap of the driver's (k + 1)-th stop among the recorded laps], column 0 =
+ *                                  no such stop; every [driver][k] row sums to n_sims, column 1 stays 0, a fifth or
+ *                                  later stop is recorded nowhere here
+ *   stops_pos_out  [n][5][n]       [driver][min(stops, 4)][position - 1], or NULL; summed over the stops axis it equals
+ *                                  hist_out
+ *   seq_out        [n][1296]       [driver][code], or NULL: code = sum over j < m of (c_j + 1) 6^j for a car with m <= 4
+ *                                  stints on compounds c_0 .. c_{m-1} (MCGP_SOFT .. MCGP_WET), column 0 = more than 4
+ *                                  stints; every row sums to n_sims
+ * All are ACCUMULATED into (caller zeroes), and only after every launch has succeeded: on an error they are left as they
+ * were.  Every argument is checked before any device lookup (MCGP_E_BAD_ARG, the message names the field): what mcgp_run
+ * / mcgp_run_from_state check, grid_probs and state both or neither given, hist_out / stop_lap_out NULL, deviates other
+ * than MCGP_DEVIATES_32 (the generic kernel runs the call and has no 53-bit path).  n_sims == 0 succeeds without a
+ * device.  The device work goes chunk by chunk through a staging buffer of 256 MiB / (9 n) simulations (per driver and
+ * simulation one 64-bit record and one position byte; rounded down to a multiple of 256, then to whole rounds of the
+ * device's resident blocks, grid_blocks x block_threads of mcgp_last_launch_info, which after this call describes its
+ * first chunk's race launch) that a counting kernel reads; device memory does not grow with n_sims.  Any split of [0, N)
+ * over calls, sim_offsets or devices sums to the same counts.  mcgp_last_kernel_ms afterwards = the device time of
+ * everything the call ran; mcgp_last_kernel_name = "mcgp::race_stints_kernel". */
+#define MCGP_STINT_STOPS 4        /* stops whose lap is recorded; stop counts are capped here */
+#define MCGP_STINT_SEQ 4          /* stints a sequence code holds */
+#define MCGP_STINT_SEQ_CODES 1296 /* 6^4 */
+int32_t mcgp_run_stints(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                        const mcgp_race_state *state, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                        uint64_t seed, int32_t device, uint64_t *hist_out, uint64_t *stop_lap_out,
+                        uint64_t *stops_pos_out, uint64_t *seq_out);
 
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver

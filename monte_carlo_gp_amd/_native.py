@@ -60,6 +60,9 @@ MAX_PLAN_STOPS = 8
 MAX_SCENARIOS = 64
 MAX_GAP_EDGES = 63          # include/mcgp.h: MCGP_MAX_GAP_EDGES, MCGP_MAX_GAP_PAIRS
 MAX_GAP_PAIRS = 64
+STINT_STOPS = 4             # include/mcgp.h: MCGP_STINT_STOPS, MCGP_STINT_SEQ, MCGP_STINT_SEQ_CODES
+STINT_SEQ = 4
+STINT_SEQ_CODES = 1296
 MAX_CONDITIONS = 64         # include/mcgp.h: MCGP_MAX_CONDITIONS, MCGP_MAX_CONDITION_ATOMS
 MAX_CONDITION_ATOMS = 8
 # include/mcgp.h: MCGP_FACT_*
@@ -256,7 +259,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
-           'mcgp_run_championship_rounds')
+           'mcgp_run_championship_rounds', 'mcgp_run_stints')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -270,6 +273,11 @@ GAPS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_do
 CONDITIONS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
                        C.c_uint32, C.c_uint32, C.POINTER(McgpCondition), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32] \
     + [C.POINTER(C.c_uint64)] * 3
+
+# mcgp_run_stints(cfg, drv, grid_probs, state, n, n_sims, sim_offset, seed, device, hist_out, stop_lap_out, stops_pos_out,
+# seq_out)
+STINTS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
+                   C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32] + [C.POINTER(C.c_uint64)] * 4
 
 
 def lib():
@@ -363,6 +371,9 @@ def lib():
         if 'mcgp_run_conditions' not in missing:
             L.mcgp_run_conditions.restype = C.c_int32
             L.mcgp_run_conditions.argtypes = CONDITIONS_ARGTYPES
+        if 'mcgp_run_stints' not in missing:
+            L.mcgp_run_stints.restype = C.c_int32
+            L.mcgp_run_stints.argtypes = STINTS_ARGTYPES
         L.mcgp_last_kernel_ms.restype = C.c_int32
         L.mcgp_last_kernel_ms.argtypes = [C.c_int32, C.POINTER(C.c_float)]
         if 'mcgp_stream_kernel_ms' not in missing:

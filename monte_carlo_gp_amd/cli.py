@@ -20,7 +20,9 @@ predict --trace prints who leads after lap 1 and at the flag, laps led, fastest 
 (the nearest edges present) and the named pairs' gaps (time gaps counted on the device) and adds a 'gaps' block to --json.
 predict --if TEXT (repeatable, also on in-race) evaluates the condition inside every simulation on the device
 (conditions.py: e.g. --if 'VER.wins & NOR.podium' --if 'sc>=1' --if 'LEC.pole'), prints its probability with the leading
-win odds given it beside the unconditional ones, and adds a 'conditions' block to --json.
+win odds given it beside the unconditional ones, and adds a 'conditions' block to --json.  predict --tyres (also on
+in-race) prints per driver the odds of 0 / 1 / 2 / 3 / 4+ pit stops, the first-stop window, the most likely compound
+sequence and the win odds by stop count (stints counted on the device) and adds a 'tyres' block to --json.
 in-race runs the rest of the race from one or more mid-race state files (RaceState JSON, simulation.py); with several
 --state files every state sees the same random futures and the columns compare the scenarios.
 strategy compares pit strategies for one driver: `model` (the race model's own stops) first, then each --plan
@@ -81,6 +83,8 @@ def cmd_predict(args) -> int:
         extra['gaps'] = gaps_argument(args)
     if args.conditions:
         extra['conditions'] = conditions_argument(args)
+    if args.tyres:
+        extra['tyres'] = True
     res = F1Predictor(device=args.device).predict_weekend(
         args.season, args.race, fixture, prediction_point=args.prediction_point,
         n_simulations=args.simulations, seed=args.seed, matchups=args.matchups, **extra)
@@ -106,6 +110,8 @@ def cmd_predict(args) -> int:
         _print_gaps(res['gaps'])
     if args.conditions:
         _print_conditions(res['conditions'])
+    if args.tyres:
+        _print_tyres(res['tyres'])
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({k: v for k, v in res.items() if k != 'full_distributions'}, f)
@@ -218,6 +224,23 @@ def _print_gaps(g, label='') -> None:
               f"either out {pr['either_out']:6.1%}   {close}")
 
 
+def _print_tyres(t, label='', top=10) -> None:
+    """--tyres: the block of a result's 'tyres' key (predictor.tyre_keys)."""
+    print(f"\nTYRE STRATEGY{label} (laps {t['first_lap']} on)\n" + '-' * 40)
+    print('      ' + ''.join(f"{h:>8}" for h in ('0 stops', '1 stop', '2 stops', '3 stops', '4+')) +
+          '   first stop   most likely')
+    for d, row in list(t['drivers'].items())[:top]:
+        w = row['first_stop_window']
+        window = f"laps {w[0]:>3}-{w[1]:<3}" if w else 'none       '
+        st = row['strategy']
+        print(f"{d:4}  " + ''.join(f"{p:8.1%}" for p in row['stops']) + f"   {window}  {st['sequence']} {st['probability']:6.1%}")
+    print(f"\nWIN ODDS BY STOP COUNT{label}\n" + '-' * 40)
+    for d, row in list(t['drivers'].items())[:top]:
+        cells = [f"{s if s < 4 else '4+'} stop{'' if s == 1 else 's'} {p:6.1%}" for s, p in enumerate(row['win_by_stops'])
+                 if p is not None]
+        print(f"{d:4}  " + '   '.join(cells))
+
+
 def cmd_in_race(args) -> int:
     from .simulation import RaceState
     fixture = synthetic_fixture()
@@ -240,6 +263,8 @@ def cmd_in_race(args) -> int:
     extra = {'gaps': gaps_argument(args)} if args.gaps else {}
     if args.conditions:
         extra['conditions'] = conditions_argument(args)
+    if args.tyres:
+        extra['tyres'] = True
     res = F1Predictor(device=args.device).predict_from_state(args.season, args.race, fixture, states,
                                                              n_simulations=args.simulations, seed=args.seed, **extra)
     drivers = list(res[0]['win_probabilities'])
@@ -257,6 +282,10 @@ def cmd_in_race(args) -> int:
     if args.conditions:
         for i, r in enumerate(res):
             _print_conditions(r['conditions'], label=f' (S{i + 1})' if len(res) > 1 else '')
+        print()
+    if args.tyres:
+        for i, r in enumerate(res):
+            _print_tyres(r['tyres'], label=f' (S{i + 1})' if len(res) > 1 else '')
         print()
     if args.json:
         with open(args.json, 'w') as f:
@@ -684,6 +713,9 @@ def main(argv=None) -> int:
     p.add_argument('--if', dest='conditions', metavar='TEXT', type=str, action='append', default=None,
                    help="a condition evaluated inside every simulation, e.g. 'VER.wins & NOR.podium', 'sc>=1', 'LEC.pole': "
                         'its probability and the odds given it (and in --json); repeat for more (at most 64)')
+    p.add_argument('--tyres', action='store_true',
+                   help="also count the model's tyre stints: stop-count odds, first-stop window, most likely compound "
+                        'sequence and win odds by stop count (and add them to --json)')
     p.set_defaults(fn=cmd_predict)
     b = sub.add_parser('backtest', help='sweep a season and score it (backtest.py of the reference)')
     b.add_argument('--seasons', type=int, nargs='+', default=[2024])
@@ -733,6 +765,9 @@ def main(argv=None) -> int:
     r.add_argument('--if', dest='conditions', metavar='TEXT', type=str, action='append', default=None,
                    help="a condition evaluated inside every simulation, e.g. 'VER.wins & NOR.podium', 'sc>=1', 'LEC.pole': "
                         'its probability and the odds given it (and in --json); repeat for more (at most 64)')
+    r.add_argument('--tyres', action='store_true',
+                   help="also count the model's tyre stints: stop-count odds, first-stop window, most likely compound "
+                        'sequence and win odds by stop count (and add them to --json)')
     r.set_defaults(fn=cmd_in_race)
     t = sub.add_parser('strategy', help="compare pit strategies for one driver against the model's own stops")
     t.add_argument('--season', type=int, default=2025)

@@ -17,6 +17,7 @@
 #include "strategy.hip.h"
 #include "gaps.hip.h"
 #include "conditions.hip.h"
+#include "stints.hip.h"
 #include "plan_pack.h"
 #include "champ_pack.h"
 
@@ -494,6 +495,8 @@ constexpr uint64_t kStrategyStageBytes = 256ull << 20;
 constexpr uint64_t kGapsStageBytes = 512ull << 20;
 // ... and of mcgp_run_conditions: per simulation the finishing order (n bytes) and one u64 mask of the conditions met.
 constexpr uint64_t kConditionsStageBytes = 256ull << 20;
+// ... and of mcgp_run_stints: per driver and simulation one u64 record and one position byte.
+constexpr uint64_t kStintsStageBytes = 256ull << 20;
 
 // Simulations in one chunk of such a staging: budget / bytes_per_sim, at most max_sims_per_launch(), in multiples of 256
 // when it can.
@@ -1927,6 +1930,97 @@ int32_t mcgp_run_conditions(const mcgp_config *cfg, const mcgp_drivers *drv, con
     });
     if (rc != MCGP_OK) return rc;
     counts.add_to({{hist_out, c_hist}, {count_out, c_count}, {cond_hist_out, c_cond}});
+    return MCGP_OK;
+}
+
+static_assert(mcgp::kStintStops == MCGP_STINT_STOPS && mcgp::kStintSeq == MCGP_STINT_SEQ &&
+                  mcgp::kStintSeqCodes == MCGP_STINT_SEQ_CODES, "stints.hip.h and mcgp.h state the same limits");
+
+int32_t mcgp_run_stints(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                        const mcgp_race_state *state, uint32_t n, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                        int32_t device, uint64_t *hist_out, uint64_t *stop_lap_out, uint64_t *stops_pos_out,
+                        uint64_t *seq_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+    if (!stop_lap_out) return fail(MCGP_E_BAD_ARG, "stop_lap_out is NULL");
+    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
+    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc == MCGP_OK) rc = check_deviates_32(kp, "stints run");
+    if (rc != MCGP_OK) return rc;
+    const uint32_t L = (uint32_t)cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string err = mcgp::pack_race_state(*state, 0, n, (int)L, &st);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+        st.sim_offset = 0;          // (race_stints_kernel takes the ids from its sim_offset argument)
+    }
+    if (n_sims == 0) return MCGP_OK;
+    const size_t c_hist = (size_t)n * n, c_lap = (size_t)n * mcgp::kStintStops * (L + 1);
+    const size_t c_sp = stops_pos_out ? (size_t)n * (mcgp::kStintStops + 1) * n : 0;
+    const size_t c_seq = seq_out ? (size_t)n * mcgp::kStintSeqCodes : 0;
+    const size_t cells = c_hist + c_lap + c_sp + c_seq;
+    Counts counts;
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        const auto kernel = state ? &mcgp::race_stints_kernel<true> : &mcgp::race_stints_kernel<false>;
+        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
+        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kStintsStageBytes, 9ull * n, n_sims);
+        // workspace: staging of one chunk, n rows of `stride` u64 records then n rows of `stride` position bytes (stride
+        // a multiple of 256) | parameter block | state | hist [n][n] | stop_lap [n][4][L + 1] | stops_pos [n][5][n] |
+        // seq [n][1296]
+        const uint64_t stride = (chunk + 255) / 256 * 256;
+        Layout ws;
+        const size_t o_rec = ws.add((size_t)n * stride * 8), o_pos = ws.add((size_t)n * stride);
+        const size_t o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st)), o_cnt = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint64_t *d_rec = c.work.at<uint64_t>(o_rec);
+        uint8_t *d_pos = c.work.at<uint8_t>(o_pos);
+        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
+        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
+        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
+        unsigned long long *d_lap = d_hist + c_hist;
+        unsigned long long *d_sp = stops_pos_out ? d_lap + c_lap : nullptr;
+        unsigned long long *d_seq = seq_out ? d_lap + c_lap + c_sp : nullptr;
+        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        // the counting kernel's histograms: 6.4 KiB at 60 laps and 20 cars, 21 KiB at 1000 laps
+        const size_t count_lds = ((size_t)mcgp::kStintStops * (L + 1) + (size_t)(mcgp::kStintStops + 1) * n +
+                                  mcgp::kStintSeqCodes) * 4;
+        if (count_lds > c.lds_per_block)
+            return fail(MCGP_E_HIP, "the stints counting kernel's block needs " + std::to_string(count_lds) +
+                                        " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)c.lds_per_block));
+        const uint64_t grid_cap = std::max<uint64_t>(1, (uint64_t)c.cu_count * 8 / n);
+        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0, lds0 = 0;
+        for (uint64_t done = 0; done < n_sims; done += chunk) {
+            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+            // the race: the generic kernel's block shape and LDS
+            r = generic_geometry(c, geo_fn, "stints", n, m, &grid, &block, &lds);
+            if (r != MCGP_OK) return r;
+            if (done == 0) { grid0 = grid; block0 = block; lds0 = lds; }
+            const uint64_t n_batches = (m + block - 1) / block;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, m, sim_offset + done,
+                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_rec, d_pos, stride, (uint32_t)n_batches);
+            HIP_TRY(hipGetLastError());
+            // its counts, before the next chunk overwrites the staging
+            const uint64_t tiles = (m + mcgp::kStintsCountBlock - 1) / mcgp::kStintsCountBlock;
+            hipLaunchKernelGGL(mcgp::stints_count, dim3((uint32_t)std::min<uint64_t>(tiles, grid_cap), n),
+                               dim3(mcgp::kStintsCountBlock), count_lds, nullptr, d_rec, d_pos, stride, m, n, L, d_lap, d_sp,
+                               d_seq);
+            HIP_TRY(hipGetLastError());
+        }
+        note_launch(c, grid0, block0, lds0, "mcgp::race_stints_kernel");     // the launch shape of the first (fullest) chunk
+        return counts.download(d_hist, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to({{hist_out, c_hist}, {stop_lap_out, c_lap}, {stops_pos_out, c_sp}, {seq_out, c_seq}});
     return MCGP_OK;
 }
 

@@ -172,7 +172,7 @@ class F1Predictor:
     def predict_weekend(self, season: int, race: str, fixture: dict | str, grid_penalties=None, circuit_info=None,
                         prediction_point: str = 'fp2', actual_grid=None, n_simulations: int = 10000,
                         seed: int | None = None, matchups: bool = False, trace: bool = False, gaps=None,
-                        conditions=None) -> dict:
+                        conditions=None, tyres: bool = False) -> dict:
         """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU.
 
         matchups=True (not in the reference): the race runs through RaceSimulator.run_matchups -- the same simulations,
@@ -191,7 +191,11 @@ class F1Predictor:
         conditions={name: text} (not in the reference; the grammar is in conditions.py): the race also runs through
         RaceSimulator.run_conditions -- the same simulations -- and the result gains 'conditions', the block
         condition_keys builds: per name the probability, its standard error and the win / podium odds given the
-        condition beside the unconditional ones."""
+        condition beside the unconditional ones.
+
+        tyres=True (not in the reference): the race also runs through RaceSimulator.run_stints -- the same simulations --
+        and the result gains 'tyres', the block tyre_keys builds: per driver the stop-count odds, the first-stop window,
+        the most likely compound sequence and the win odds by stop count."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -202,20 +206,20 @@ class F1Predictor:
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
             # same inputs, the matrix built on the device from the ratings (no host matrix crosses PCIe)
             ratings = {d: self.elo_system.ratings.get(d, {}).get('quali', self.elo_system.initial) for d in inp['drivers']}
-            if matchups or trace or gaps or conditions:
+            if matchups or trace or gaps or conditions or tyres:
                 # the same matrix, read back from the device front end and handed to the matchups / trace / gaps run
                 grid = sim.grid_probs_on_device(inp['drivers'], ratings, fixture.get('quali_features', {}),
                                                 grid_penalties or {})
                 return self._with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups,
-                                         trace, gaps, conditions)
+                                         trace, gaps, conditions, tyres)
             race_probs, grid = sim.run_from_ratings(
                 n_simulations, inp['drivers'], ratings, fixture.get('quali_features', {}), grid_penalties or {},
                 inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'], seed=seed,
                 track_condition=inp['track_condition'])
             return pack_result(inp['drivers'], grid, race_probs, inp['weather'], prediction_point, actual_grid)
-        if matchups or trace or gaps or conditions:
+        if matchups or trace or gaps or conditions or tyres:
             return self._with_counts(sim, inp, inp['grid_probs'], n_simulations, seed, prediction_point, actual_grid,
-                                     matchups, trace, gaps, conditions)
+                                     matchups, trace, gaps, conditions, tyres)
         race_probs = sim.run_monte_carlo(
             n_simulations=n_simulations, grid_probs=inp['grid_probs'], base_pace=inp['base_pace'],
             tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
@@ -223,14 +227,16 @@ class F1Predictor:
         return pack_result(inp['drivers'], inp['grid_probs'], race_probs, inp['weather'], prediction_point, actual_grid)
 
     def predict_from_state(self, season: int, race: str, fixture: dict | str, state, n_simulations: int = 100000,
-                           seed: int | None = None, gaps=None, conditions=None):
+                           seed: int | None = None, gaps=None, conditions=None, tyres: bool = False):
         """In-race odds (not in the reference): the weekend's race inputs (simulator_inputs, as predict_weekend builds
         them) run from a mid-race RaceState of the fixture's drivers -- or from each of a list of them, with common
         random numbers -- through RaceSimulator.run_from_state.  Returns, per state, {'lap', 'win_probabilities', 'podium_probabilities',
         'points_probabilities' (top 10), 'full_distributions'}: one dict, or a list for a list of states.  gaps (as in
         predict_weekend): every state's dict gains 'gaps' from RaceSimulator.run_gaps on that state, same simulations.
         conditions (as in predict_weekend): every state's dict gains 'conditions' from RaceSimulator.run_conditions on
-        that state, same simulations; race events count from the state's lap on."""
+        that state, same simulations; race events count from the state's lap on.  tyres (as in predict_weekend): every
+        state's dict gains 'tyres' from RaceSimulator.run_stints on that state, same simulations; stops count from the
+        state's lap on."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -240,7 +246,7 @@ class F1Predictor:
         states = [state] if single else list(state)
         inp = self.simulator_inputs(fixture, race)
         sim = RaceSimulator(inp['config'], device=self.device)
-        seed = sim._resolve_seed(seed) if gaps or conditions else seed
+        seed = sim._resolve_seed(seed) if gaps or conditions or tyres else seed
         # the driver order of predict_weekend's run: a state that run's simulation i reached continues as simulation i
         probs = sim.run_from_state(n_simulations, states, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
                                    inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'],
@@ -263,6 +269,12 @@ class F1Predictor:
                                        inp['driver_variance'], inp['driver_dnf_rates'], state=st, seed=seed,
                                        track_condition=inp['track_condition'], drivers=list(inp['grid_probs']))
                 res['conditions'] = condition_keys(c)
+        if tyres:
+            for st, res in zip(states, out):
+                t = sim.run_stints(n_simulations, None, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
+                                   inp['driver_dnf_rates'], state=st, seed=seed, track_condition=inp['track_condition'],
+                                   drivers=list(inp['grid_probs']))
+                res['tyres'] = tyre_keys(t)
         return out[0] if single else out
 
     def predict_strategies(self, season: int, race: str, fixture: dict | str, strategies: dict, state=None,
@@ -287,9 +299,9 @@ class F1Predictor:
 
     @staticmethod
     def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace,
-                     gaps=None, conditions=None) -> dict:
-        """predict_weekend's result from run_matchups, run_trace, run_gaps and / or run_conditions calls on `grid` (the
-        same simulations: one seed for all), with their keys added."""
+                     gaps=None, conditions=None, tyres=False) -> dict:
+        """predict_weekend's result from run_matchups, run_trace, run_gaps, run_conditions and / or run_stints calls on
+        `grid` (the same simulations: one seed for all), with their keys added."""
         args = (n_simulations, grid, inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'])
         seed = sim._resolve_seed(seed)
         res = None
@@ -317,6 +329,12 @@ class F1Predictor:
                 res = pack_result(inp['drivers'], grid, c.position_probabilities(), inp['weather'], prediction_point,
                                   actual_grid)
             res['conditions'] = condition_keys(c)
+        if tyres:
+            t = sim.run_stints(*args, seed=seed, track_condition=inp['track_condition'])
+            if res is None:
+                res = pack_result(inp['drivers'], grid, t.position_probabilities(), inp['weather'], prediction_point,
+                                  actual_grid)
+            res['tyres'] = tyre_keys(t)
         return res
 
 
@@ -353,6 +371,26 @@ def condition_keys(c) -> dict:
     ConditionResult: {name: {'probability', 'standard_error', 'count', 'win': {driver: {'given', 'unconditional'}},
     'podium': the same}}; 'given' is None where no simulation met the condition."""
     return c.summary()
+
+
+def tyre_keys(t) -> dict:
+    """The 'tyres' block predict_weekend(tyres=True) / predict_from_state(tyres=True) add, JSON-safe, from a StintResult:
+    {'first_lap', 'drivers': {driver: {'stops': [P(0), P(1), P(2), P(3), P(4 or more)], 'first_stop_window': [lap at the
+    10 % quantile, lap at the 90 % quantile] among the simulations that stop or None, 'strategy': {'sequence',
+    'probability'} the most likely compound sequence, 'win_by_stops': [P(win | s stops)] with None where no simulation
+    makes s stops}}}."""
+    stops = t.stop_count_probabilities()
+    out = {}
+    for d in t.drivers:
+        window = t.stop_window(d)
+        best = t.strategy_probabilities(d)[:1]
+        out[d] = {
+            'stops': stops[d],
+            'first_stop_window': list(window) if window else None,
+            'strategy': {'sequence': best[0][0], 'probability': best[0][1]} if best else None,
+            'win_by_stops': [t.win_probability_given_stops(d, s) for s in range(t.stops_pos.shape[1])],
+        }
+    return {'first_lap': t.first_lap, 'drivers': out}
 
 
 def gap_options(gaps) -> dict:

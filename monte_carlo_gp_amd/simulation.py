@@ -685,6 +685,65 @@ class RaceSimulator:
         self.last_drivers = drivers
         return res
 
+    def run_stints(
+        self,
+        n_simulations: int,
+        grid_probs: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+    ) -> 'StintResult':
+        """Tyre stints (include/mcgp.h: mcgp_run_stints): on which lap the race model makes each driver's first four pit
+        stops, which compound sequence the driver runs (red-flag tyre changes start a stint too) and how the finishing
+        positions split by stop count, counted on the device.  From the grid (grid_probs: run_monte_carlo's simulations,
+        laps 2..L) or from a mid-race RaceState (state: run_from_state's simulations, the laps after the state's; earlier
+        stops are not part of a state).  The StintResult's position histogram equals that call's.  32-bit deviates only;
+        same seed rules and device sharding as run_monte_carlo.  Sets last_histogram / last_drivers."""
+        if (grid_probs is None) == (state is None):
+            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
+        if drivers is None:
+            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
+        drivers = [str(d) for d in drivers]
+        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
+            raise ValueError('drivers must be the keys of grid_probs')
+        n, L = len(drivers), int(self.config.total_laps)
+        n_simulations = int(n_simulations)
+        first_lap = 2 if state is None else int(state.lap) + 1
+        mk = lambda count, dtype: StintResult.empty(drivers, L, count, first_lap, dtype)
+        if not drivers or n_simulations <= 0:
+            res = mk(0, np.int64)
+            self.last_histogram, self.last_drivers = res.hist, drivers
+            return res
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        arrays = state.arrays(drivers, L) if state is not None else None
+        c_state = state.c_struct(arrays) if state is not None else None
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            out = mk(count, np.uint64)
+            rc = lib.mcgp_run_stints(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
+                                     C.byref(c_state) if c_state is not None else None, n, int(count),
+                                     int(sim_offset) + int(offset), seed64, device, u64(out.hist), u64(out.stop_lap),
+                                     u64(out.stops_pos), u64(out.seq))
+            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([getattr(r, k) for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        res = StintResult(drivers=drivers, n_simulations=n_simulations, total_laps=L, first_lap=first_lap,
+                          hist=total('hist'), stop_lap=total('stop_lap'), stops_pos=total('stops_pos'), seq=total('seq'))
+        self.last_histogram = res.hist
+        self.last_drivers = drivers
+        return res
+
     def run_conditions(
         self,
         n_simulations: int,
@@ -1186,6 +1245,150 @@ class GapResult:
         p, _ = self._pair(a, b)
         j, B = self._edge(seconds), self.n_bins
         return self._p(self.pair[:, p, :j].sum(axis=1) + self.pair[:, p, B:B + j].sum(axis=1))
+
+
+STINT_LETTERS = 'SMHIW'                 # one letter per compound of _native.COMPOUNDS, as strategy strings spell them
+MANY_STINTS = '5+ stints'              # column 0 of StintResult.seq: more stints than a sequence code holds
+
+
+def encode_stints(compounds) -> int:
+    """The sequence code (include/mcgp.h: mcgp_run_stints' seq_out) of a car's stints: compounds as names ('MEDIUM'),
+    letters ('M'), ids (1) or one string such as 'M-H'; sum of (id + 1) 6^j over 1 .. 4 stints, 0 for more than 4."""
+    if isinstance(compounds, str):
+        compounds = compounds.split('-')
+    ids = []
+    for c in compounds:
+        if isinstance(c, str):
+            name = c.strip().upper()
+            if name in N.COMPOUND_ID:
+                c = N.COMPOUND_ID[name]
+            elif len(name) == 1 and name in STINT_LETTERS:
+                c = STINT_LETTERS.index(name)
+            else:
+                raise ValueError(f'{c!r} is not a tyre compound')
+        c = int(c)
+        if not 0 <= c < len(N.COMPOUNDS):
+            raise ValueError(f'compound id must be in [0, {len(N.COMPOUNDS) - 1}], got {c}')
+        ids.append(c)
+    if not ids:
+        raise ValueError('a car has at least one stint')
+    if len(ids) > N.STINT_SEQ:
+        return 0
+    return sum((c + 1) * 6 ** j for j, c in enumerate(ids))
+
+
+def decode_stints(code: int):
+    """The compound ids of a sequence code, in stint order; () for code 0 (more than 4 stints); None for a code no car
+    can have (a digit 0 between stints)."""
+    code = int(code)
+    if not 0 <= code < N.STINT_SEQ_CODES:
+        raise ValueError(f'code must be in [0, {N.STINT_SEQ_CODES - 1}], got {code}')
+    digits = []
+    while code:
+        digits.append(code % 6)
+        code //= 6
+    if 0 in digits:
+        return None
+    return tuple(x - 1 for x in digits)
+
+
+def stint_string(code: int) -> str:
+    """'M-H', 'S-H-S', ...; MANY_STINTS for code 0."""
+    ids = decode_stints(code)
+    if ids is None:
+        raise ValueError(f'{code} is not the code of a stint sequence')
+    return '-'.join(STINT_LETTERS[c] for c in ids) if ids else MANY_STINTS
+
+
+@dataclass
+class StintResult:
+    """What RaceSimulator.run_stints returns: integer counts over n_simulations (include/mcgp.h: mcgp_run_stints has the
+    definitions).  L = total_laps, n = len(drivers); laps first_lap .. L are recorded (2 from the grid, the state's lap +
+    1 from a state).
+      hist       [n][n]          [driver][position - 1], run_monte_carlo's / run_from_state's histogram
+      stop_lap   [n][4][L + 1]   [driver][k][lap of the (k + 1)-th stop], column 0 = no such stop
+      stops_pos  [n][5][n]       [driver][min(stops, 4)][position - 1]
+      seq        [n][1296]       [driver][sequence code (encode_stints)], column 0 = more than 4 stints"""
+    drivers: list
+    n_simulations: int
+    total_laps: int
+    first_lap: int
+    hist: np.ndarray
+    stop_lap: np.ndarray
+    stops_pos: np.ndarray
+    seq: np.ndarray
+
+    @classmethod
+    def empty(cls, drivers, total_laps, n_simulations=0, first_lap=2, dtype=np.int64) -> 'StintResult':
+        n, L = len(drivers), int(total_laps)
+        z = lambda *shape: np.zeros(shape, dtype)
+        return cls(drivers=list(drivers), n_simulations=int(n_simulations), total_laps=L, first_lap=int(first_lap),
+                   hist=z(n, n), stop_lap=z(n, N.STINT_STOPS, L + 1), stops_pos=z(n, N.STINT_STOPS + 1, n),
+                   seq=z(n, N.STINT_SEQ_CODES))
+
+    def _p(self, counts):
+        return np.asarray(counts, np.float64) / max(self.n_simulations, 1)
+
+    def _d(self, driver):
+        try:
+            return self.drivers.index(str(driver))
+        except ValueError:
+            raise ValueError(f'{driver!r} is not one of the drivers') from None
+
+    def _k(self, k):
+        k = int(k)
+        if not 0 <= k < N.STINT_STOPS:
+            raise ValueError(f'k must be in [0, {N.STINT_STOPS - 1}] (the first {N.STINT_STOPS} stops are recorded), got {k}')
+        return k
+
+    def position_probabilities(self) -> dict:
+        """{driver: {position: probability}}, what run_monte_carlo / run_from_state returns for the same arguments."""
+        return histogram_to_probs(self.hist, self.drivers, self.n_simulations)
+
+    def stop_count_probabilities(self) -> dict:
+        """{driver: [P(0 stops), P(1), P(2), P(3), P(4 or more)]} over the recorded laps."""
+        return {d: [float(x) for x in self._p(self.stops_pos[i].sum(axis=1))] for i, d in enumerate(self.drivers)}
+
+    def stop_lap_distribution(self, driver, k=0) -> np.ndarray:
+        """[L + 1]: P(the driver's (k + 1)-th stop is on that lap), entry 0 = P(no such stop)."""
+        return self._p(self.stop_lap[self._d(driver), self._k(k)])
+
+    def stop_window(self, driver, k=0, lo=0.1, hi=0.9):
+        """(lap_lo, lap_hi): the laps at the quantiles lo and hi of the (k + 1)-th stop's lap among the simulations that
+        make that stop -- the smallest lap by which at least that share of them has stopped; None if none makes it."""
+        if not 0.0 <= lo <= hi <= 1.0:
+            raise ValueError(f'quantiles must satisfy 0 <= lo <= hi <= 1, got {lo}, {hi}')
+        c = self.stop_lap[self._d(driver), self._k(k)].astype(np.int64).copy()
+        c[0] = 0
+        tot = int(c.sum())
+        if tot == 0:
+            return None
+        cum = np.cumsum(c)
+        at = lambda q: int(np.searchsorted(cum, max(q * tot, 1), side='left'))
+        return at(lo), at(hi)
+
+    def strategy_probabilities(self, driver) -> list:
+        """[(strategy, probability)] sorted by probability (then by text): 'M-H', 'S-H-S', ..., '5+ stints'; only the
+        sequences that occur."""
+        row = self.seq[self._d(driver)]
+        out = [(stint_string(code), float(self._p(row[code]))) for code in np.nonzero(row)[0]]
+        return sorted(out, key=lambda kv: (-kv[1], kv[0]))
+
+    def position_probabilities_by_stops(self, driver) -> np.ndarray:
+        """[5][n]: P(position p + 1 | s stops) for s = 0 .. 3 and 4 or more; a row of zeros where no simulation makes s
+        stops."""
+        c = self.stops_pos[self._d(driver)].astype(np.float64)
+        tot = c.sum(axis=1, keepdims=True)
+        return np.divide(c, tot, out=np.zeros_like(c), where=tot > 0)
+
+    def win_probability_given_stops(self, driver, s):
+        """P(win | s stops), s in 0 .. 4 (4 = 4 or more); None where no simulation makes s stops."""
+        s = int(s)
+        if not 0 <= s <= N.STINT_STOPS:
+            raise ValueError(f's must be in [0, {N.STINT_STOPS}], got {s}')
+        row = self.stops_pos[self._d(driver), s]
+        tot = int(row.sum())
+        return float(row[0] / tot) if tot else None
 
 
 DEFAULT_POINTS = (25, 18, 15, 12, 10, 8, 6, 4, 2, 1)      # a Grand Prix, positions 1-10

@@ -103,12 +103,18 @@ inline T atomicAdd(T *p, T v)
 #endif
 }
 // Cross-lane operations have no meaning in a block of one thread.  They are declared so that headers whose GPU-only
-// kernels use them (trace_count_positions: __shfl_down; the matchups kernel: __ballot) compile here; the host builds
-// never call those kernels, and a call ends the process rather than return a made-up value.
+// kernels use them (trace_count_positions: __shfl_down; the matchups kernel: __ballot; stints_count: __ballot, __shfl)
+// compile here; the host builds never call those kernels, and a call ends the process rather than return a made-up value.
 template <typename T>
 inline T __shfl_down(T, int, int = 64)
 {
     __builtin_trap();
 }
+template <typename T>
+inline T __shfl(T, int, int = 64)
+{
+    __builtin_trap();
+}
 inline unsigned long long __ballot(int) { __builtin_trap(); }
 inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
+inline int __ffsll(unsigned long long v) { return __builtin_ffsll((long long)v); }
