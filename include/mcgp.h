@@ -34,7 +34,7 @@ extern "C" {
 /* 5: mcgp_race_state, mcgp_run_from_state */
 /* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
- * mcgp_run_championship_rounds likewise; mcgp_run_conditions and mcgp_run_stints too */
+ * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -511,6 +511,56 @@ int32_t mcgp_run_stints(const mcgp_config *cfg, const mcgp_drivers *drv, const d
                         const mcgp_race_state *state, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
                         uint64_t seed, int32_t device, uint64_t *hist_out, uint64_t *stop_lap_out,
                         uint64_t *stops_pos_out, uint64_t *seq_out);
+
+/* Race movement: how a car got where it finished -- the joint grid x finish table, the places won or lost at the start
+ * and the passes by driver, lap and pair -- counted on the device, from the grid or from a mid-race state.  Everything is
+ * read where mcgp_run_trace reads: after update_positions of lap k, L = cfg->total_laps.  Let run_k(d) mean "d is not
+ * retired after lap k".  Let pos_k(d) be its running position among the running cars, in `ord` order (cumulative time,
+ * then grid slot).  Let pit_k(d) mean "running after lap k with tyre age 0", for k >= 2.  This is the trace's definition.
+ *   - Baseline.  From the grid, pos_0(d) is d's sampled grid slot and every car runs.  From a state after lap k0, the
+ *     baseline is pos_k0.  This is the order start_from_state leaves after its own update_positions.
+ *   - Start gain (from the grid only).  This is slot(d) - pos_1(d).  A car that retires on lap 1 has none.
+ *   - Pass on lap k.  From the grid, k runs over 2..L.  From a state, k runs over k0 + 1..L.  Take an ordered pair (a, b)
+ *     with run_{k-1} and run_k true for both.  If pos_{k-1}(a) > pos_{k-1}(b) and pos_k(a) < pos_k(b), then a took a
+ *     place from b on lap k.  The pass is through the pits if pit_k(a) or pit_k(b).  Otherwise it is on track.  A place
+ *     gained because a car retired is not a pass.  This is the model's order change, not a claim about a wheel-to-wheel
+ *     move: two lap ends are compared, and a place swapped twice within a lap is not seen.
+ *   - Classified position.  This is classify_and_count's position.  Retired cars rank behind the runners, as in hist.
+ *   - simulations: from the grid (state NULL, grid_probs given) ids sim_offset .. sim_offset + n_sims - 1 with the draws
+ *     of mcgp_run's simulation i; from a state (grid_probs NULL, one mcgp_race_state) the draws and rules of
+ *     mcgp_run_from_state with sim_offsets[0] = sim_offset.
+ *   hist_out         [n][n]        [driver][position - 1]: equal to mcgp_run's / mcgp_run_from_state's for the same ids
+ *   grid_fin_out     [n][n][n]     [driver][grid slot][classified position - 1]; from a state the slot is
+ *                                  state->grid_slot.  Summed over slots it equals hist_out
+ *   start_gain_out   [n][2n]       [driver][slot - pos_1 + n - 1]; column 2n - 1 = retired on lap 1; every row sums to
+ *                                  n_sims.  May be NULL; with a state it MUST be NULL
+ *   passes_out       [n][4][128]   [driver][kind][min(count, MCGP_MOVE_DRIVER_CAP)]; kinds: 0 made on track, 1 lost on
+ *                                  track, 2 gained through the pits, 3 lost through the pits; every [driver][kind] row
+ *                                  sums to n_sims.  May be NULL
+ *   race_passes_out  [1024]        [min(on-track passes of the race, MCGP_MOVE_RACE_CAP)]; sums to n_sims.  May be NULL
+ *   lap_passes_out   [L + 1][2]    [lap][on track, through the pits]: the passes on that lap summed over the simulations;
+ *                                  rows 0 and 1 stay 0.  May be NULL
+ *   pair_passes_out  [n][n]        [a][b]: times a took a place from b on track, summed over laps and simulations.  May
+ *                                  be NULL
+ * All are ACCUMULATED into (caller zeroes), and only after every launch has succeeded: on an error they are left as they
+ * were.  An output that is NULL is not counted.  Every argument is checked before any device lookup (MCGP_E_BAD_ARG, the
+ * message names the field): what mcgp_run / mcgp_run_from_state check, grid_probs and state both or neither given,
+ * hist_out / grid_fin_out NULL, start_gain_out with a state, deviates other than MCGP_DEVIATES_32 (the generic kernel
+ * runs the call and has no 53-bit path).  n_sims == 0 succeeds without a device.  The device work goes chunk by chunk
+ * through a staging buffer of 512 MiB / ((L + 2) n) simulations (one byte per lap and driver as mcgp_run_trace stages
+ * them, then every driver's grid slot and classified position; at most the launch cap, rounded down to a multiple of 256,
+ * then to whole rounds of the device's resident blocks, grid_blocks x block_threads of mcgp_last_launch_info, which after
+ * this call describes its first chunk's race launch) that two counting kernels read; with passes_out the first hands the
+ * second 4 n more bytes per simulation of the chunk.  Device memory does not grow with n_sims.  Any split of [0, N) over
+ * calls, sim_offsets or devices sums to the same counts.  mcgp_last_kernel_ms afterwards = the device time of everything
+ * the call ran; mcgp_last_kernel_name = "mcgp::race_moves_kernel". */
+#define MCGP_MOVE_DRIVER_CAP 127   /* a driver's passes of one kind in one race, saturating */
+#define MCGP_MOVE_RACE_CAP  1023   /* on-track passes in one race, saturating */
+int32_t mcgp_run_moves(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                       const mcgp_race_state *state, uint32_t n, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                       int32_t device, uint64_t *hist_out, uint64_t *grid_fin_out, uint64_t *start_gain_out,
+                       uint64_t *passes_out, uint64_t *race_passes_out, uint64_t *lap_passes_out,
+                       uint64_t *pair_passes_out);
 
 /* simulate_race (reference :147-242): one race from a FIXED starting grid
  * (grid[p] = driver index on slot p), simulation id sim_id.  order_out[p] = driver

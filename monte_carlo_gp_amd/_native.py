@@ -63,6 +63,9 @@ MAX_GAP_PAIRS = 64
 STINT_STOPS = 4             # include/mcgp.h: MCGP_STINT_STOPS, MCGP_STINT_SEQ, MCGP_STINT_SEQ_CODES
 STINT_SEQ = 4
 STINT_SEQ_CODES = 1296
+MOVE_DRIVER_CAP = 127       # include/mcgp.h: MCGP_MOVE_DRIVER_CAP, MCGP_MOVE_RACE_CAP
+MOVE_RACE_CAP = 1023
+MOVE_KINDS = ('made_on_track', 'lost_on_track', 'gained_in_pits', 'lost_in_pits')   # passes_out's kind axis
 MAX_CONDITIONS = 64         # include/mcgp.h: MCGP_MAX_CONDITIONS, MCGP_MAX_CONDITION_ATOMS
 MAX_CONDITION_ATOMS = 8
 # include/mcgp.h: MCGP_FACT_*
@@ -259,7 +262,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
-           'mcgp_run_championship_rounds', 'mcgp_run_stints')
+           'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -278,6 +281,11 @@ CONDITIONS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(
 # seq_out)
 STINTS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
                    C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32] + [C.POINTER(C.c_uint64)] * 4
+
+# mcgp_run_moves(cfg, drv, grid_probs, state, n, n_sims, sim_offset, seed, device, hist_out, grid_fin_out, start_gain_out,
+# passes_out, race_passes_out, lap_passes_out, pair_passes_out)
+MOVES_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
+                  C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32] + [C.POINTER(C.c_uint64)] * 7
 
 
 def lib():
@@ -374,6 +382,9 @@ def lib():
         if 'mcgp_run_stints' not in missing:
             L.mcgp_run_stints.restype = C.c_int32
             L.mcgp_run_stints.argtypes = STINTS_ARGTYPES
+        if 'mcgp_run_moves' not in missing:
+            L.mcgp_run_moves.restype = C.c_int32
+            L.mcgp_run_moves.argtypes = MOVES_ARGTYPES
         L.mcgp_last_kernel_ms.restype = C.c_int32
         L.mcgp_last_kernel_ms.argtypes = [C.c_int32, C.POINTER(C.c_float)]
         if 'mcgp_stream_kernel_ms' not in missing:

@@ -22,7 +22,10 @@ predict --if TEXT (repeatable, also on in-race) evaluates the condition inside e
 (conditions.py: e.g. --if 'VER.wins & NOR.podium' --if 'sc>=1' --if 'LEC.pole'), prints its probability with the leading
 win odds given it beside the unconditional ones, and adds a 'conditions' block to --json.  predict --tyres (also on
 in-race) prints per driver the odds of 0 / 1 / 2 / 3 / 4+ pit stops, the first-stop window, the most likely compound
-sequence and the win odds by stop count (stints counted on the device) and adds a 'tyres' block to --json.
+sequence and the win odds by stop count (stints counted on the device) and adds a 'tyres' block to --json.  predict
+--moves (also on in-race) prints per driver the expected places gained, the expected start gain and the passes made and
+lost, the expected on-track passes per race with their 10-90 % range and the five commonest (a, b) pairs (order changes
+between lap ends, counted on the device) and adds a 'moves' block to --json.
 in-race runs the rest of the race from one or more mid-race state files (RaceState JSON, simulation.py); with several
 --state files every state sees the same random futures and the columns compare the scenarios.
 strategy compares pit strategies for one driver: `model` (the race model's own stops) first, then each --plan
@@ -85,6 +88,8 @@ def cmd_predict(args) -> int:
         extra['conditions'] = conditions_argument(args)
     if args.tyres:
         extra['tyres'] = True
+    if args.moves:
+        extra['moves'] = True
     res = F1Predictor(device=args.device).predict_weekend(
         args.season, args.race, fixture, prediction_point=args.prediction_point,
         n_simulations=args.simulations, seed=args.seed, matchups=args.matchups, **extra)
@@ -112,6 +117,8 @@ def cmd_predict(args) -> int:
         _print_conditions(res['conditions'])
     if args.tyres:
         _print_tyres(res['tyres'])
+    if args.moves:
+        _print_moves(res['moves'])
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({k: v for k, v in res.items() if k != 'full_distributions'}, f)
@@ -241,6 +248,21 @@ def _print_tyres(t, label='', top=10) -> None:
         print(f"{d:4}  " + '   '.join(cells))
 
 
+def _print_moves(mv, label='', top=10) -> None:
+    """--moves: the block of a result's 'moves' key (predictor.move_keys)."""
+    print(f"\nRACE MOVEMENT{label} (passes on laps {mv['first_lap']} on; order changes between lap ends)\n" + '-' * 40)
+    print('      places gained  start gain   made   lost  via pits +/-')
+    for d, row in list(mv['drivers'].items())[:top]:
+        p = row['passes']
+        start = f"{row['start_gain']:+10.2f}" if row['start_gain'] is not None else '         -'
+        print(f"{d:4}  {row['places_gained']:+13.2f}  {start}  {p['made_on_track']:5.1f}  {p['lost_on_track']:5.1f}  "
+              f"{p['gained_in_pits']:5.1f} / {p['lost_in_pits']:.1f}")
+    r = mv['race_passes']
+    print(f"on-track passes per race: {r['expected']:.1f} (10-90 %: {r['p10']}-{r['p90']})")
+    for pr in mv['pairs']:
+        print(f"  {pr['a']:4} on {pr['b']:4} {pr['per_race']:5.2f} per race")
+
+
 def cmd_in_race(args) -> int:
     from .simulation import RaceState
     fixture = synthetic_fixture()
@@ -265,6 +287,8 @@ def cmd_in_race(args) -> int:
         extra['conditions'] = conditions_argument(args)
     if args.tyres:
         extra['tyres'] = True
+    if args.moves:
+        extra['moves'] = True
     res = F1Predictor(device=args.device).predict_from_state(args.season, args.race, fixture, states,
                                                              n_simulations=args.simulations, seed=args.seed, **extra)
     drivers = list(res[0]['win_probabilities'])
@@ -286,6 +310,10 @@ def cmd_in_race(args) -> int:
     if args.tyres:
         for i, r in enumerate(res):
             _print_tyres(r['tyres'], label=f' (S{i + 1})' if len(res) > 1 else '')
+        print()
+    if args.moves:
+        for i, r in enumerate(res):
+            _print_moves(r['moves'], label=f' (S{i + 1})' if len(res) > 1 else '')
         print()
     if args.json:
         with open(args.json, 'w') as f:
@@ -716,6 +744,9 @@ def main(argv=None) -> int:
     p.add_argument('--tyres', action='store_true',
                    help="also count the model's tyre stints: stop-count odds, first-stop window, most likely compound "
                         'sequence and win odds by stop count (and add them to --json)')
+    p.add_argument('--moves', action='store_true',
+                   help='also count how the field moves: expected places gained, start gain, passes made and lost per '
+                        'driver, on-track passes per race and the commonest pairs (and add them to --json)')
     p.set_defaults(fn=cmd_predict)
     b = sub.add_parser('backtest', help='sweep a season and score it (backtest.py of the reference)')
     b.add_argument('--seasons', type=int, nargs='+', default=[2024])
@@ -768,6 +799,9 @@ def main(argv=None) -> int:
     r.add_argument('--tyres', action='store_true',
                    help="also count the model's tyre stints: stop-count odds, first-stop window, most likely compound "
                         'sequence and win odds by stop count (and add them to --json)')
+    r.add_argument('--moves', action='store_true',
+                   help='also count how the field moves: expected places gained, start gain, passes made and lost per '
+                        'driver, on-track passes per race and the commonest pairs (and add them to --json)')
     r.set_defaults(fn=cmd_in_race)
     t = sub.add_parser('strategy', help="compare pit strategies for one driver against the model's own stops")
     t.add_argument('--season', type=int, default=2025)

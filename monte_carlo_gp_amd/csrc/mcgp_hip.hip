@@ -18,6 +18,7 @@
 #include "gaps.hip.h"
 #include "conditions.hip.h"
 #include "stints.hip.h"
+#include "moves.hip.h"
 #include "plan_pack.h"
 #include "champ_pack.h"
 
@@ -497,6 +498,8 @@ constexpr uint64_t kGapsStageBytes = 512ull << 20;
 constexpr uint64_t kConditionsStageBytes = 256ull << 20;
 // ... and of mcgp_run_stints: per driver and simulation one u64 record and one position byte.
 constexpr uint64_t kStintsStageBytes = 256ull << 20;
+// ... and of mcgp_run_moves: per lap and driver one byte, then per driver the grid slot and the classified position.
+constexpr uint64_t kMovesStageBytes = 512ull << 20;
 
 // Simulations in one chunk of such a staging: budget / bytes_per_sim, at most max_sims_per_launch(), in multiples of 256
 // when it can.
@@ -2021,6 +2024,120 @@ int32_t mcgp_run_stints(const mcgp_config *cfg, const mcgp_drivers *drv, const d
     });
     if (rc != MCGP_OK) return rc;
     counts.add_to({{hist_out, c_hist}, {stop_lap_out, c_lap}, {stops_pos_out, c_sp}, {seq_out, c_seq}});
+    return MCGP_OK;
+}
+
+static_assert(mcgp::kMoveDriverCap == MCGP_MOVE_DRIVER_CAP && mcgp::kMoveRaceCap == MCGP_MOVE_RACE_CAP,
+              "moves.hip.h and mcgp.h state the same caps");
+
+int32_t mcgp_run_moves(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                       const mcgp_race_state *state, uint32_t n, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                       int32_t device, uint64_t *hist_out, uint64_t *grid_fin_out, uint64_t *start_gain_out,
+                       uint64_t *passes_out, uint64_t *race_passes_out, uint64_t *lap_passes_out,
+                       uint64_t *pair_passes_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+    if (!grid_fin_out) return fail(MCGP_E_BAD_ARG, "grid_fin_out is NULL");
+    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
+    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    if (state && start_gain_out)
+        return fail(MCGP_E_BAD_ARG, "start_gain_out must be NULL when a state is given (a start gain is from the grid)");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc == MCGP_OK) rc = check_deviates_32(kp, "moves run");
+    if (rc != MCGP_OK) return rc;
+    const uint32_t L = (uint32_t)cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string err = mcgp::pack_race_state(*state, 0, n, (int)L, &st);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+        st.sim_offset = 0;          // (race_moves_kernel takes the ids from its sim_offset argument)
+    }
+    if (n_sims == 0) return MCGP_OK;
+    const uint32_t lap0 = state ? (uint32_t)st.lap : 1u;                    // the baseline row
+    const size_t c_hist = (size_t)n * n, c_gf = (size_t)n * n * n;
+    const size_t c_gain = start_gain_out ? (size_t)n * 2 * n : 0;
+    const size_t c_pass = passes_out ? (size_t)n * 4 * (mcgp::kMoveDriverCap + 1) : 0;
+    const size_t c_race = race_passes_out ? (size_t)mcgp::kMoveRaceCap + 1 : 0;
+    const size_t c_lap = lap_passes_out ? 2 * (size_t)(L + 1) : 0;
+    const size_t c_pair = pair_passes_out ? (size_t)n * n : 0;
+    const size_t cells = c_hist + c_gf + c_gain + c_pass + c_race + c_lap + c_pair;
+    const bool walk = passes_out || race_passes_out || lap_passes_out || pair_passes_out;
+    Counts counts;
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        const auto kernel = state ? &mcgp::race_moves_kernel<true> : &mcgp::race_moves_kernel<false>;
+        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
+        const uint64_t rows = ((uint64_t)L + 2) * n;
+        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kMovesStageBytes, rows, n_sims);
+        // workspace: staging of one chunk, (L + 2) n rows of `stride` bytes (a multiple of 256) | every car's packed
+        // pass counts, n rows of `stride` u32 (only if passes_out) | parameter block | state | hist [n][n] | grid_fin
+        // [n][n][n] | start_gain [n][2n] | passes [n][4][128] | race_passes [1024] | lap_passes [L + 1][2] |
+        // pair_passes [n][n]
+        const uint64_t stride = (chunk + 255) / 256 * 256;
+        Layout ws;
+        const size_t o_stage = ws.add((size_t)rows * stride), o_tot = ws.add(passes_out ? (size_t)n * stride * 4 : 0);
+        const size_t o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st)), o_cnt = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
+        uint32_t *d_tot = passes_out ? c.work.at<uint32_t>(o_tot) : nullptr;
+        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
+        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
+        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
+        unsigned long long *d_gf = d_hist + c_hist;
+        unsigned long long *d_gain = start_gain_out ? d_gf + c_gf : nullptr;
+        unsigned long long *d_pass = passes_out ? d_gf + c_gf + c_gain : nullptr;
+        unsigned long long *d_race = race_passes_out ? d_gf + c_gf + c_gain + c_pass : nullptr;
+        unsigned long long *d_lap = lap_passes_out ? d_gf + c_gf + c_gain + c_pass + c_race : nullptr;
+        unsigned long long *d_pair = pair_passes_out ? d_gf + c_gf + c_gain + c_pass + c_race + c_lap : nullptr;
+        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        // moves_count_laps' tables and sums: 29 KiB at 60 laps and 20 cars, 52 KiB at 1000 laps and 32 cars
+        const size_t laps_lds = 9 * (size_t)n * mcgp::kMovesLapsBlock +
+                                ((size_t)n * n + 2 * (size_t)(L + 1) + mcgp::kMoveRaceCap + 1) * 4;
+        if (laps_lds > c.lds_per_block)
+            return fail(MCGP_E_HIP, "the moves counting kernel's block needs " + std::to_string(laps_lds) +
+                                        " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)c.lds_per_block));
+        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
+        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0, lds0 = 0;
+        for (uint64_t done = 0; done < n_sims; done += chunk) {
+            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+            // the race: the generic kernel's block shape and LDS
+            r = generic_geometry(c, geo_fn, "moves", n, m, &grid, &block, &lds);
+            if (r != MCGP_OK) return r;
+            if (done == 0) { grid0 = grid; block0 = block; lds0 = lds; }
+            const uint64_t n_batches = (m + block - 1) / block;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, m, sim_offset + done,
+                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, (uint32_t)n_batches);
+            HIP_TRY(hipGetLastError());
+            // its counts, before the next chunk overwrites the staging
+            if (walk) {
+                // a block takes at most kMovesBlockShare simulations, so that its u32 sums cannot wrap (moves.hip.h)
+                const uint64_t tiles = (m + mcgp::kMovesLapsBlock - 1) / mcgp::kMovesLapsBlock;
+                const uint64_t per_block = mcgp::kMovesBlockShare / mcgp::kMovesLapsBlock;
+                const uint64_t gx = std::min<uint64_t>(tiles, std::max<uint64_t>(grid_cap, (tiles + per_block - 1) / per_block));
+                hipLaunchKernelGGL(mcgp::moves_count_laps, dim3((uint32_t)gx), dim3(mcgp::kMovesLapsBlock), laps_lds, nullptr,
+                                   d_stage, stride, m, n, L, lap0, d_tot, d_race, d_lap, d_pair);
+                HIP_TRY(hipGetLastError());
+            }
+            const uint64_t dtiles = (m + mcgp::kMovesDriversBlock - 1) / mcgp::kMovesDriversBlock;
+            const uint64_t gx = std::max<uint64_t>(1, std::min<uint64_t>(dtiles, grid_cap / n));
+            hipLaunchKernelGGL(mcgp::moves_count_drivers, dim3((uint32_t)gx, n), dim3(mcgp::kMovesDriversBlock), 0, nullptr,
+                               d_stage, d_tot, stride, m, n, L, d_gf, d_gain, d_pass);
+            HIP_TRY(hipGetLastError());
+        }
+        note_launch(c, grid0, block0, lds0, "mcgp::race_moves_kernel");      // the launch shape of the first (fullest) chunk
+        return counts.download(d_hist, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to({{hist_out, c_hist}, {grid_fin_out, c_gf}, {start_gain_out, c_gain}, {passes_out, c_pass},
+                   {race_passes_out, c_race}, {lap_passes_out, c_lap}, {pair_passes_out, c_pair}});
     return MCGP_OK;
 }
 

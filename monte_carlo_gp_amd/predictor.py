@@ -172,7 +172,7 @@ class F1Predictor:
     def predict_weekend(self, season: int, race: str, fixture: dict | str, grid_penalties=None, circuit_info=None,
                         prediction_point: str = 'fp2', actual_grid=None, n_simulations: int = 10000,
                         seed: int | None = None, matchups: bool = False, trace: bool = False, gaps=None,
-                        conditions=None, tyres: bool = False) -> dict:
+                        conditions=None, tyres: bool = False, moves: bool = False) -> dict:
         """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU.
 
         matchups=True (not in the reference): the race runs through RaceSimulator.run_matchups -- the same simulations,
@@ -195,7 +195,12 @@ class F1Predictor:
 
         tyres=True (not in the reference): the race also runs through RaceSimulator.run_stints -- the same simulations --
         and the result gains 'tyres', the block tyre_keys builds: per driver the stop-count odds, the first-stop window,
-        the most likely compound sequence and the win odds by stop count."""
+        the most likely compound sequence and the win odds by stop count.
+
+        moves=True (not in the reference): the race also runs through RaceSimulator.run_moves -- the same simulations --
+        and the result gains 'moves', the block move_keys builds: per driver the expected places gained, the expected
+        start gain and the passes made and lost, and for the race the expected on-track passes with their 10-90 % range
+        and the commonest (a, b) pairs."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -206,20 +211,20 @@ class F1Predictor:
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
             # same inputs, the matrix built on the device from the ratings (no host matrix crosses PCIe)
             ratings = {d: self.elo_system.ratings.get(d, {}).get('quali', self.elo_system.initial) for d in inp['drivers']}
-            if matchups or trace or gaps or conditions or tyres:
+            if matchups or trace or gaps or conditions or tyres or moves:
                 # the same matrix, read back from the device front end and handed to the matchups / trace / gaps run
                 grid = sim.grid_probs_on_device(inp['drivers'], ratings, fixture.get('quali_features', {}),
                                                 grid_penalties or {})
                 return self._with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups,
-                                         trace, gaps, conditions, tyres)
+                                         trace, gaps, conditions, tyres, moves)
             race_probs, grid = sim.run_from_ratings(
                 n_simulations, inp['drivers'], ratings, fixture.get('quali_features', {}), grid_penalties or {},
                 inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'], seed=seed,
                 track_condition=inp['track_condition'])
             return pack_result(inp['drivers'], grid, race_probs, inp['weather'], prediction_point, actual_grid)
-        if matchups or trace or gaps or conditions or tyres:
+        if matchups or trace or gaps or conditions or tyres or moves:
             return self._with_counts(sim, inp, inp['grid_probs'], n_simulations, seed, prediction_point, actual_grid,
-                                     matchups, trace, gaps, conditions, tyres)
+                                     matchups, trace, gaps, conditions, tyres, moves)
         race_probs = sim.run_monte_carlo(
             n_simulations=n_simulations, grid_probs=inp['grid_probs'], base_pace=inp['base_pace'],
             tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
@@ -227,7 +232,8 @@ class F1Predictor:
         return pack_result(inp['drivers'], inp['grid_probs'], race_probs, inp['weather'], prediction_point, actual_grid)
 
     def predict_from_state(self, season: int, race: str, fixture: dict | str, state, n_simulations: int = 100000,
-                           seed: int | None = None, gaps=None, conditions=None, tyres: bool = False):
+                           seed: int | None = None, gaps=None, conditions=None, tyres: bool = False,
+                           moves: bool = False):
         """In-race odds (not in the reference): the weekend's race inputs (simulator_inputs, as predict_weekend builds
         them) run from a mid-race RaceState of the fixture's drivers -- or from each of a list of them, with common
         random numbers -- through RaceSimulator.run_from_state.  Returns, per state, {'lap', 'win_probabilities', 'podium_probabilities',
@@ -236,7 +242,8 @@ class F1Predictor:
         conditions (as in predict_weekend): every state's dict gains 'conditions' from RaceSimulator.run_conditions on
         that state, same simulations; race events count from the state's lap on.  tyres (as in predict_weekend): every
         state's dict gains 'tyres' from RaceSimulator.run_stints on that state, same simulations; stops count from the
-        state's lap on."""
+        state's lap on.  moves (as in predict_weekend): every state's dict gains 'moves' from RaceSimulator.run_moves on
+        that state, same simulations; passes count from the state's lap on and there is no start gain."""
         if isinstance(fixture, str):
             with open(fixture) as f:
                 fixture = json.load(f)
@@ -246,7 +253,7 @@ class F1Predictor:
         states = [state] if single else list(state)
         inp = self.simulator_inputs(fixture, race)
         sim = RaceSimulator(inp['config'], device=self.device)
-        seed = sim._resolve_seed(seed) if gaps or conditions or tyres else seed
+        seed = sim._resolve_seed(seed) if gaps or conditions or tyres or moves else seed
         # the driver order of predict_weekend's run: a state that run's simulation i reached continues as simulation i
         probs = sim.run_from_state(n_simulations, states, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
                                    inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'],
@@ -275,6 +282,12 @@ class F1Predictor:
                                    inp['driver_dnf_rates'], state=st, seed=seed, track_condition=inp['track_condition'],
                                    drivers=list(inp['grid_probs']))
                 res['tyres'] = tyre_keys(t)
+        if moves:
+            for st, res in zip(states, out):
+                mv = sim.run_moves(n_simulations, None, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
+                                   inp['driver_dnf_rates'], state=st, seed=seed, track_condition=inp['track_condition'],
+                                   drivers=list(inp['grid_probs']))
+                res['moves'] = move_keys(mv)
         return out[0] if single else out
 
     def predict_strategies(self, season: int, race: str, fixture: dict | str, strategies: dict, state=None,
@@ -299,8 +312,8 @@ class F1Predictor:
 
     @staticmethod
     def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace,
-                     gaps=None, conditions=None, tyres=False) -> dict:
-        """predict_weekend's result from run_matchups, run_trace, run_gaps, run_conditions and / or run_stints calls on
+                     gaps=None, conditions=None, tyres=False, moves=False) -> dict:
+        """predict_weekend's result from run_matchups, run_trace, run_gaps, run_conditions, run_stints and / or run_moves calls on
         `grid` (the same simulations: one seed for all), with their keys added."""
         args = (n_simulations, grid, inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'])
         seed = sim._resolve_seed(seed)
@@ -335,6 +348,12 @@ class F1Predictor:
                 res = pack_result(inp['drivers'], grid, t.position_probabilities(), inp['weather'], prediction_point,
                                   actual_grid)
             res['tyres'] = tyre_keys(t)
+        if moves:
+            mv = sim.run_moves(*args, seed=seed, track_condition=inp['track_condition'])
+            if res is None:
+                res = pack_result(inp['drivers'], grid, mv.position_probabilities(), inp['weather'], prediction_point,
+                                  actual_grid)
+            res['moves'] = move_keys(mv)
         return res
 
 
@@ -391,6 +410,21 @@ def tyre_keys(t) -> dict:
             'win_by_stops': [t.win_probability_given_stops(d, s) for s in range(t.stops_pos.shape[1])],
         }
     return {'first_lap': t.first_lap, 'drivers': out}
+
+
+def move_keys(mv, pairs=5) -> dict:
+    """The 'moves' block predict_weekend(moves=True) / predict_from_state(moves=True) add, JSON-safe, from a MoveResult:
+    {'first_lap', 'drivers': {driver: {'places_gained' E[grid slot - classified position], 'start_gain' E[slot -
+    position after lap 1 | running] or None (None from a state), 'passes': {kind name: expected per race}}},
+    'race_passes': {'expected', 'p10', 'p90'} on track, 'pairs': [{'a', 'b', 'per_race'}] the commonest (a, b) with a
+    taking a place from b on track}.  A pass is the model's order change between two lap ends."""
+    gained, passes = mv.expected_positions_gained(), mv.expected_passes()
+    start = mv.expected_start_gain() if mv.from_grid else {}
+    return {'first_lap': mv.first_lap,
+            'drivers': {d: {'places_gained': gained[d], 'start_gain': start.get(d), 'passes': passes[d]} for d in mv.drivers},
+            'race_passes': {'expected': mv.expected_race_passes(), 'p10': mv.race_passes_quantile(0.1),
+                            'p90': mv.race_passes_quantile(0.9)},
+            'pairs': [{'a': a, 'b': b, 'per_race': x} for a, b, x in mv.most_frequent_passes(pairs)]}
 
 
 def gap_options(gaps) -> dict:

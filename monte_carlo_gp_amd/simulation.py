@@ -744,6 +744,68 @@ class RaceSimulator:
         self.last_drivers = drivers
         return res
 
+    def run_moves(
+        self,
+        n_simulations: int,
+        grid_probs: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+    ) -> 'MoveResult':
+        """Race movement (include/mcgp.h: mcgp_run_moves): the joint grid x finish table, the places won or lost at the
+        start, and the model's order changes between lap ends -- passes made and lost per driver, on track and through
+        the pits, per race, per lap and per pair -- counted on the device.  From the grid (grid_probs: run_monte_carlo's
+        simulations, passes on laps 2..L) or from a mid-race RaceState (state: run_from_state's simulations, the laps
+        after the state's; no start gain).  The MoveResult's position histogram equals that call's.  32-bit deviates
+        only; same seed rules and device sharding as run_monte_carlo.  Sets last_histogram / last_drivers."""
+        if (grid_probs is None) == (state is None):
+            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
+        if drivers is None:
+            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
+        drivers = [str(d) for d in drivers]
+        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
+            raise ValueError('drivers must be the keys of grid_probs')
+        n, L = len(drivers), int(self.config.total_laps)
+        n_simulations = int(n_simulations)
+        first_lap = 2 if state is None else int(state.lap) + 1
+        mk = lambda count, dtype: MoveResult.empty(drivers, L, count, first_lap, state is None, dtype)
+        if not drivers or n_simulations <= 0:
+            res = mk(0, np.int64)
+            self.last_histogram, self.last_drivers = res.hist, drivers
+            return res
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        arrays = state.arrays(drivers, L) if state is not None else None
+        c_state = state.c_struct(arrays) if state is not None else None
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            out = mk(count, np.uint64)
+            rc = lib.mcgp_run_moves(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
+                                    C.byref(c_state) if c_state is not None else None, n, int(count),
+                                    int(sim_offset) + int(offset), seed64, device, u64(out.hist), u64(out.grid_fin),
+                                    u64(out.start_gain) if state is None else None, u64(out.passes),
+                                    u64(out.race_passes), u64(out.lap_passes), u64(out.pair_passes))
+            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([getattr(r, k) for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        res = MoveResult(drivers=drivers, n_simulations=n_simulations, total_laps=L, first_lap=first_lap,
+                         from_grid=state is None, hist=total('hist'), grid_fin=total('grid_fin'),
+                         start_gain=total('start_gain'), passes=total('passes'), race_passes=total('race_passes'),
+                         lap_passes=total('lap_passes'), pair_passes=total('pair_passes'))
+        self.last_histogram = res.hist
+        self.last_drivers = drivers
+        return res
+
     def run_conditions(
         self,
         n_simulations: int,
@@ -1389,6 +1451,159 @@ class StintResult:
         row = self.stops_pos[self._d(driver), s]
         tot = int(row.sum())
         return float(row[0] / tot) if tot else None
+
+
+@dataclass
+class MoveResult:
+    """What RaceSimulator.run_moves returns: integer counts over n_simulations (include/mcgp.h: mcgp_run_moves has the
+    definitions).  L = total_laps, n = len(drivers); passes are counted on laps first_lap .. L (2 from the grid, the
+    state's lap + 1 from a state).  A pass is the model's order change between two lap ends, not a claim about a
+    wheel-to-wheel move.
+      hist         [n][n]        [driver][position - 1], run_monte_carlo's / run_from_state's histogram
+      grid_fin     [n][n][n]     [driver][grid slot][position - 1]
+      start_gain   [n][2n]       [driver][slot - position after lap 1 + n - 1], column 2n - 1 = retired on lap 1; zeros
+                                 from a state
+      passes       [n][4][128]   [driver][kind (_native.MOVE_KINDS)][min(count, 127)]
+      race_passes  [1024]        [min(on-track passes of the race, 1023)]
+      lap_passes   [L + 1][2]    [lap][on track, through the pits], summed over the simulations
+      pair_passes  [n][n]        [a][b]: times a took a place from b on track"""
+    drivers: list
+    n_simulations: int
+    total_laps: int
+    first_lap: int
+    from_grid: bool
+    hist: np.ndarray
+    grid_fin: np.ndarray
+    start_gain: np.ndarray
+    passes: np.ndarray
+    race_passes: np.ndarray
+    lap_passes: np.ndarray
+    pair_passes: np.ndarray
+
+    @classmethod
+    def empty(cls, drivers, total_laps, n_simulations=0, first_lap=2, from_grid=True, dtype=np.int64) -> 'MoveResult':
+        n, L = len(drivers), int(total_laps)
+        z = lambda *shape: np.zeros(shape, dtype)
+        return cls(drivers=list(drivers), n_simulations=int(n_simulations), total_laps=L, first_lap=int(first_lap),
+                   from_grid=bool(from_grid), hist=z(n, n), grid_fin=z(n, n, n), start_gain=z(n, 2 * n),
+                   passes=z(n, len(N.MOVE_KINDS), N.MOVE_DRIVER_CAP + 1), race_passes=z(N.MOVE_RACE_CAP + 1),
+                   lap_passes=z(L + 1, 2), pair_passes=z(n, n))
+
+    def _p(self, counts):
+        return np.asarray(counts, np.float64) / max(self.n_simulations, 1)
+
+    def _d(self, driver):
+        try:
+            return self.drivers.index(str(driver))
+        except ValueError:
+            raise ValueError(f'{driver!r} is not one of the drivers') from None
+
+    def _slot(self, slot):
+        slot = int(slot)
+        if not 1 <= slot <= len(self.drivers):
+            raise ValueError(f'slot must be in [1, {len(self.drivers)}] (1 = pole), got {slot}')
+        return slot - 1
+
+    def _kind(self, kind):
+        if isinstance(kind, str):
+            if kind not in N.MOVE_KINDS:
+                raise ValueError(f'kind must be one of {N.MOVE_KINDS}, got {kind!r}')
+            return N.MOVE_KINDS.index(kind)
+        kind = int(kind)
+        if not 0 <= kind < len(N.MOVE_KINDS):
+            raise ValueError(f'kind must be in [0, {len(N.MOVE_KINDS) - 1}], got {kind}')
+        return kind
+
+    def _needs_grid(self):
+        if not self.from_grid:
+            raise ValueError('a run from a race state has no start: start gains are counted from the grid only')
+
+    def position_probabilities(self) -> dict:
+        """{driver: {position: probability}}, what run_monte_carlo / run_from_state returns for the same arguments."""
+        return histogram_to_probs(self.hist, self.drivers, self.n_simulations)
+
+    def finish_given_grid(self, driver, slot):
+        """[n]: P(position p + 1 | the driver starts from `slot`, 1 = pole); None where no simulation starts it there."""
+        row = self.grid_fin[self._d(driver), self._slot(slot)].astype(np.float64)
+        tot = row.sum()
+        return row / tot if tot else None
+
+    def win_probability_from(self, driver, slot):
+        """P(win | the driver starts from `slot`, 1 = pole); None where no simulation starts it there."""
+        p = self.finish_given_grid(driver, slot)
+        return float(p[0]) if p is not None else None
+
+    def positions_gained_distribution(self, driver) -> np.ndarray:
+        """[2n - 1]: P(grid slot - classified position = g) at index g + n - 1, g in -(n - 1) .. n - 1 (from grid_fin;
+        retirements count with their classified position)."""
+        n = len(self.drivers)
+        gf = self.grid_fin[self._d(driver)]
+        out = np.zeros(2 * n - 1, np.float64)
+        for g in range(-(n - 1), n):
+            out[g + n - 1] = np.trace(gf, offset=-g)               # cells [slot][slot - g]
+        return self._p(out)
+
+    def expected_positions_gained(self) -> dict:
+        """{driver: E[grid slot - classified position]}."""
+        n = len(self.drivers)
+        g = np.arange(-(n - 1), n)
+        return {d: float((self.positions_gained_distribution(d) * g).sum()) for d in self.drivers}
+
+    def start_gain_distribution(self, driver) -> np.ndarray:
+        """[2n]: P(grid slot - position after lap 1 = g) at index g + n - 1; the last entry = P(retired on lap 1)."""
+        self._needs_grid()
+        return self._p(self.start_gain[self._d(driver)])
+
+    def expected_start_gain(self) -> dict:
+        """{driver: E[grid slot - position after lap 1 | running after lap 1]}; None for a driver that never is."""
+        self._needs_grid()
+        n = len(self.drivers)
+        g = np.arange(-(n - 1), n)
+        out = {}
+        for i, d in enumerate(self.drivers):
+            row = self.start_gain[i, :2 * n - 1].astype(np.float64)
+            out[d] = float((row * g).sum() / row.sum()) if row.sum() else None
+        return out
+
+    def passes_distribution(self, driver, kind=0) -> np.ndarray:
+        """[128]: P(the driver's passes of that kind in a race = c) at index c; the last entry = 127 or more.  kind: 0 ..
+        3 or a name of _native.MOVE_KINDS."""
+        return self._p(self.passes[self._d(driver), self._kind(kind)])
+
+    def expected_passes(self) -> dict:
+        """{driver: {kind name: expected passes per race}} (a count of 127 or more counts as 127)."""
+        c = np.arange(self.passes.shape[2])
+        return {d: {k: float((self._p(self.passes[i, j]) * c).sum()) for j, k in enumerate(N.MOVE_KINDS)}
+                for i, d in enumerate(self.drivers)}
+
+    def race_passes_distribution(self) -> np.ndarray:
+        """[1024]: P(on-track passes of the race = c) at index c; the last entry = 1023 or more."""
+        return self._p(self.race_passes)
+
+    def race_passes_quantile(self, q) -> int:
+        """The smallest count c with P(on-track passes of the race <= c) >= q."""
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f'q must be in [0, 1], got {q}')
+        tot = int(self.race_passes.sum())
+        if tot == 0:
+            return 0
+        return int(np.searchsorted(np.cumsum(self.race_passes), max(q * tot, 1), side='left'))
+
+    def expected_race_passes(self) -> float:
+        """Expected on-track passes per race, from the uncapped per-lap sums."""
+        return float(self.lap_passes[:, 0].sum() / max(self.n_simulations, 1))
+
+    def passes_by_lap(self) -> np.ndarray:
+        """[L + 1][2]: expected passes on that lap, on track and through the pits (rows 0 and 1 are 0)."""
+        return self._p(self.lap_passes)
+
+    def most_frequent_passes(self, k=10) -> list:
+        """[(a, b, expected times per race a takes a place from b on track)], the k commonest pairs, by count then name."""
+        n = len(self.drivers)
+        cells = [(int(self.pair_passes[a, b]), self.drivers[a], self.drivers[b]) for a in range(n) for b in range(n)
+                 if self.pair_passes[a, b]]
+        cells.sort(key=lambda c: (-c[0], c[1], c[2]))
+        return [(a, b, float(self._p(c))) for c, a, b in cells[:int(k)]]
 
 
 DEFAULT_POINTS = (25, 18, 15, 12, 10, 8, 6, 4, 2, 1)      # a Grand Prix, positions 1-10

@@ -1,9 +1,9 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
 // fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
-// strategy.hip.h, gaps.hip.h, conditions.hip.h and stints.hip.h with g++ through the stand-in <hip/hip_runtime.h> of this
-// directory and calls the real __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel,
-// race_strategy_kernel<false / true>, race_gaps_kernel<false / true>, race_conditions_kernel<false / true>,
-// conditions_count, race_stints_kernel<false / true>.
+// strategy.hip.h, gaps.hip.h, conditions.hip.h, stints.hip.h and moves.hip.h with g++ through the stand-in
+// <hip/hip_runtime.h> of this directory and calls the real __global__ functions: race_kernel, race_resume_kernel,
+// race_trace_kernel, race_strategy_kernel<false / true>, race_gaps_kernel<false / true>, race_conditions_kernel<false /
+// true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false / true>.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -11,13 +11,14 @@
 // stand-in header is correct for a block of one thread); blockIdx.y (states, scenarios) is looped over here.  The
 // state and plan arguments go through csrc/plan_pack.h, the text the C ABI itself uses.
 //
-// Not run here: trace_count_positions and gaps_count_rows (__shfl_down), the matchups kernel and stints_count (__ballot), and
+// Not run here: trace_count_positions, gaps_count_rows and moves_count_laps (__shfl_down), the matchups kernel and
+// stints_count (__ballot), moves_count_drivers (a fixed block of 256 threads), and
 // trace_count_laps, trace_count_records and strategy_count_deltas, whose loops are written for their fixed block of 256
 // threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
 // records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
 // operation and strides by its block's size, so it does run here, as blocks of one thread.
 // tests/test_generic_host_build.py, tests/test_gaps_host_build.py, tests/test_conditions_host_build.py,
-// tests/test_stints_host_build.py.
+// tests/test_stints_host_build.py, tests/test_moves_host_build.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -29,6 +30,7 @@
 #include "../../monte_carlo_gp_amd/csrc/gaps.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/conditions.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/stints.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/moves.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/plan_pack.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -254,6 +256,30 @@ int emu_stints_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double
     one_thread_block(1);
     const auto kernel = state ? &mcgp::race_stints_kernel<true> : &mcgp::race_stints_kernel<false>;
     kernel(&kp, &st, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, rec, pos, stride, (uint32_t)n_sims);
+    return MCGP_OK;
+}
+
+// race_moves_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims).  hist [n][n] is
+// accumulated into; stage [(L + 2) n][stride] bytes (stride >= n_sims) is written, in the layout documented at the top
+// of csrc/moves.hip.h.
+int emu_moves_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                  uint32_t n, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *stage,
+                  uint64_t stride, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    if (stride < n_sims) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims", err);
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, cfg->total_laps, &st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    }
+    one_thread_block(1);
+    const auto kernel = state ? &mcgp::race_moves_kernel<true> : &mcgp::race_moves_kernel<false>;
+    kernel(&kp, &st, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage, stride, (uint32_t)n_sims);
     return MCGP_OK;
 }
 
