@@ -2,17 +2,24 @@
 compared, integers only, with references that do not share its code: the raw staging -- records and position bytes,
 decoded by the layout documented at the top of stints.hip.h -- against stints_ref's numpy restatement over the CPU
 oracle's per-lap trace (tyre age, compound, retirement) and the restated event draws; the histogram against the
-oracle's.  The counting kernel and the host-side chunking are compared on the device (test_gpu_stints.py).  The host
-build is test infrastructure: nothing under monte_carlo_gp_amd/ can reach it and the product has no CPU path."""
+oracle's.  Inputs: seven golden cases, a cap case, fields of 1, 2 and 32 cars, and a second pass over everything
+generic_cases.py holds -- the 8 golden cases, the 84 fuzz configurations with their corner cases, lap times near zero
+and at the overtake's floor, fields of 1, 2, 3, 19, 31 and 32 cars -- from the grid and from the states of
+conditions_ref.state_runs.  The counting kernel and the host-side chunking are compared on the device
+(test_gpu_stints.py, test_gpu_stints_moves_fuzz.py).  The host build is test infrastructure: nothing under
+monte_carlo_gp_amd/ can reach it and the product has no CPU path."""
 import numpy as np
 import pytest
 
+import conditions_ref as CR
+import generic_cases as G
 import oracle_py as O
 import resume_ref as RR
 import stints_host_build as SH
 import stints_ref as SR
 
 SIMS = 96
+RUN_SIMS, STATE_SIMS, OFFSET, BASE = 32, 4, 3, 40
 GOLDEN = ('S60', 'EVT', 'WET', 'N10', 'HET', 'S78', 'DMP')
 
 
@@ -86,3 +93,38 @@ def test_oracle_states_continue_into_the_oracle_trace():
                     comp = ref['trace']['comp'][i, L - 1].astype(np.uint64)
                     assert np.array_equal(rec[:, 0], np.uint64(1) | (comp << np.uint64(4))), (name, i)
                     assert not got['stop_lap'][:, :, 1:].any()
+
+
+# ---------------------------------------------------------------- the second pass: every input of generic_cases.py
+def test_stints_kernel_from_the_grid_on_every_input():
+    """All of generic_cases.run_inputs() at each input's own seed: every key equals stints_ref over the oracle's trace."""
+    inputs = G.run_inputs()
+    done = 0
+    for name, case, seed in inputs:
+        ref = RR.traced_run(case, RUN_SIMS, seed, OFFSET)
+        got = SH.stints(case, RUN_SIMS, seed, sim_offset=OFFSET)
+        _same(name, got, SR.stint_counts(case, RUN_SIMS, seed, OFFSET, ref=ref))
+        assert (got['stop_lap'].sum(axis=2) == RUN_SIMS).all() and (got['seq'].sum(axis=1) == RUN_SIMS).all(), name
+        done += name in G.fuzz_cases()
+    assert done == G.N_FUZZ and len(inputs) == 100
+
+
+def test_stints_kernel_from_a_state_on_every_input():
+    """All of generic_cases.resume_inputs(): four simulations' states after every lap of resume_laps, each continued as
+    itself; the records are the oracle trace's of the later laps, stint 0 on the state's compound."""
+    done = states = 0
+    for name, case, seed in G.resume_inputs():
+        L = case['config']['total_laps']
+        ref = RR.traced_run(case, STATE_SIMS, seed, BASE)
+        runs = CR.state_runs(case, seed, ref, range(STATE_SIMS), BASE)
+        prob = SH.KH.generic_problem(case)
+        for i, k, st in runs:
+            hist, rec, pos = SH.stints_raw(case, 1, seed, sim_offset=BASE + i, state=st, prob=prob)
+            got = SH.counts_from_staging(rec, pos, L)
+            got['hist'] = hist
+            _same((name, i, k), got, SR.continued_counts(ref, [i], k, case, seed, BASE))
+            assert not got['stop_lap'][:, :, 1:k + 1].any(), (name, i, k)
+        assert len(runs) >= STATE_SIMS, name
+        states += len(runs)
+        done += name in G.fuzz_cases()
+    assert done == G.N_FUZZ and states >= 94 * STATE_SIMS * 3, (done, states)
