@@ -34,7 +34,8 @@ extern "C" {
 /* 5: mcgp_race_state, mcgp_run_from_state */
 /* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
- * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too */
+ * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too; and
+ * mcgp_run_championship_bonus */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -235,6 +236,48 @@ int32_t mcgp_run_championship_rounds(uint32_t n_races, const mcgp_config *cfgs, 
                                      uint64_t *gain_hist, uint64_t *race_hist, uint64_t *round_hist, uint64_t *contend_out,
                                      uint64_t *secure_out, uint64_t *team_round_hist, uint64_t *team_contend_out,
                                      uint64_t *team_secure_out);
+
+/* Championship with a fastest-lap bonus: mcgp_run_championship_rounds, and per race a bonus for the driver who sets the
+ * fastest lap (the 2019-2024 rule: 1 point, if classified in the top ten).  Every argument through team_secure_out is
+ * mcgp_run_championship_rounds', same order and meaning, except that round_hist, contend_out and secure_out may be all
+ * three NULL (no per-round work; the team trio must then be NULL too).  With every bonus_points[r] == 0 the call
+ * returns what mcgp_run_championship_rounds (mcgp_run_championship, without the round trio) returns, cell for cell.
+ *
+ * Definitions.
+ *   - Fastest lap of a race simulation: mcgp_run_trace's.  The smallest last lap time of a car running after lap k,
+ *     over laps 2..L; a tie goes to the earlier lap, then to the better running position (strict <, laps in order, cars
+ *     in running order).  A race in which no car completes a lap >= 2 has none; every race of one lap is such a race.
+ *   - Bonus of race r: bonus_points[r] >= 0 points to the fastest-lap driver, if that driver's classified position
+ *     (1-based, the race model's classification) is <= bonus_within[r].  A car that set the fastest lap and retired later
+ *     still takes the bonus if it is classified inside the limit, as a retired car scores when fewer cars finish than
+ *     the table pays.  The bonus adds to the points only, never to a countback count; team points are the sums of the
+ *     drivers' points, bonus included.
+ *   - Limits and bounds.  G = sum over r of (max_p points[r][p] + bonus_points[r]): gain_hist has G + 1 columns and the
+ *     65535 limit applies to init_points[d] + this G.  By round, the remaining points include the bonuses still to
+ *     come: M_r and B_r(e) each add the sum over q > r of bonus_points[q] (at most one car of a team takes a bonus).
+ *     Secure stays monotone and secure[R-1] = champ_hist[.][0], because points are >= 0.
+ *   bonus_points  [R] int32 in [0, 65535]
+ *   bonus_within  [R] int32 in [1, n] where bonus_points[r] > 0, ignored otherwise
+ *   bonus_hist    [R][n] or NULL: simulations in which the driver took race r's bonus; ACCUMULATED into
+ *   fastest_hist  [R][n] or NULL: simulations in which the driver set race r's fastest lap (equal to mcgp_run_trace's
+ *                 fastest_out for that race); ACCUMULATED into; rows of races without a bonus stay untouched
+ * Every argument is checked before any device lookup and the message names the field and the race; a race with a bonus
+ * at MCGP_DEVIATES_53 is MCGP_E_BAD_ARG (the generic kernel has no 53-bit path).  Outputs are added into only after every
+ * launch has succeeded; n_sims == 0 succeeds without a device.
+ * Price: a race without a bonus goes through mcgp_run's launch path as before; a race with one runs on the generic
+ * kernel's code (race_fastest_kernel, csrc/fastest.hip.h), which tracks lap times: about 52 ms per 10^6 simulations of a
+ * 20-car, 60-lap race on an MI355X against 6.7 ms on the register kernel.  champ_bonus (csrc/champ_bonus.hip.h) then adds
+ * the bonus to the standing keys behind the race's champ_accumulate.  Added entry point only: MCGP_ABI_VERSION stays 6
+ * and a caller tests for the symbol. */
+int32_t mcgp_run_championship_bonus(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                                    const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                                    const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                                    const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                                    uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                                    uint64_t *gain_hist, uint64_t *race_hist, uint64_t *round_hist, uint64_t *contend_out,
+                                    uint64_t *secure_out, uint64_t *team_round_hist, uint64_t *team_contend_out,
+                                    uint64_t *team_secure_out, const int32_t *bonus_points, const int32_t *bonus_within,
+                                    uint64_t *bonus_hist, uint64_t *fastest_hist);
 
 /* Head-to-head and podium-combination counts of one race: mcgp_run's inputs and simulations (ids sim_offset ..
  * sim_offset + n_sims - 1), counted on the device so that no finishing order leaves it.  "Classified" is the race model's

@@ -635,10 +635,14 @@ def cmd_export_fixtures(args) -> int:
     return 0
 
 
+FASTEST_LAP_POINT, FASTEST_LAP_WITHIN = 1, 10              # cli championship --fastest-lap-point
+
+
 def championship_jobs(season, seed, from_round=1, fixtures_dir=None):
     """The races of a championship run: rounds from_round..end of results_<season>.json, each with backtest_jobs' inputs
     and per-race seed (the same seed gives the same race draws as `backtest`).  The results file does not mark sprint
-    weekends, so every round is a Grand Prix."""
+    weekends, so every round is a Grand Prix (still so with --fastest-lap-point: sprints, which pay no fastest-lap point,
+    are not in the file)."""
     jobs = backtest_jobs([season], seed, fixtures_dir)
     if not 1 <= from_round <= len(jobs):
         raise ValueError(f'--from-round must be in [1, {len(jobs)}], got {from_round}')
@@ -665,6 +669,10 @@ def cmd_championship(args) -> int:
         with open(args.standings) as f:
             standings = json.load(f)
     races = championship_races(jobs, args.device)
+    if args.fastest_lap_point:
+        # the 2019-2024 rule: a point for the race's fastest lap, if classified in the top ten
+        for race in races:
+            race.update(fastest_lap_points=FASTEST_LAP_POINT, fastest_lap_within=FASTEST_LAP_WITHIN)
     t0 = time.perf_counter()
     res = run_championship(races, args.simulations, standings=standings, device=args.device,
                            return_race_histograms=True, by_round=args.by_round)
@@ -682,6 +690,14 @@ def cmd_championship(args) -> int:
     print(f'EXPECTED POINTS ({what})\n' + '-' * 40)
     for i, (d, p) in enumerate(sorted(exp.items(), key=lambda kv: kv[1], reverse=True)[:10], 1):
         print(f'{i:2}. {d:4} {p:7.1f}')
+    if args.fastest_lap_point:
+        print(f'\nFASTEST-LAP POINT ({FASTEST_LAP_POINT} point within the top {FASTEST_LAP_WITHIN}, every round)\n' + '-' * 40)
+        print(f"{'':2}  {'':4} {'expected':>8}  {'fastest laps':>12}")
+        bonus, laps = res.expected_bonus_points, res.fastest_lap_counts.sum(axis=0)
+        order = sorted(range(len(res.drivers)), key=lambda i: (-bonus[res.drivers[i]], res.drivers[i]))
+        for k, i in enumerate(order[:10], 1):
+            d = res.drivers[i]
+            print(f'{k:2}. {d:4} {bonus[d]:8.2f}  {int(laps[i]) / max(res.n_simulations, 1):12.2f}')
     if args.by_round:
         print(f'\nBY ROUND ({what})\n' + '-' * 40)
         print(f"{'round':>5}  {'race':<22} {'decided':>8}  {'in contention':>13}  leaders")
@@ -708,6 +724,14 @@ def cmd_championship(args) -> int:
                         'constructor_leader_probabilities_by_round', 'constructor_contention_probabilities_by_round',
                         'constructor_clinch_round_probabilities'):
                 out[key] = getattr(res, key)
+        if args.fastest_lap_point:
+            out['fastest_lap_point'] = dict(
+                points=FASTEST_LAP_POINT, within=FASTEST_LAP_WITHIN, expected_bonus_points=res.expected_bonus_points,
+                expected_constructor_bonus_points=res.expected_constructor_bonus_points,
+                bonus_probabilities_by_round=res.bonus_probabilities_by_round,
+                fastest_lap_probabilities_by_round=[
+                    {d: int(row[i]) / max(res.n_simulations, 1) for i, d in enumerate(res.drivers)}
+                    for row in res.fastest_lap_counts])
         with open(args.json, 'w') as f:
             json.dump(out, f)
     return 0
@@ -774,6 +798,9 @@ def main(argv=None) -> int:
     c.add_argument('--by-round', action='store_true',
                    help='also count the standings after every round: P(title decided by then), the likeliest leaders, '
                         'the drivers still in contention (and add the tables to --json)')
+    c.add_argument('--fastest-lap-point', action='store_true',
+                   help='score the 2019-2024 fastest-lap point: 1 point to the driver who sets the fastest lap of a round, '
+                        'if classified in the top ten (every round then runs on the slower lap-time-tracking kernel)')
     c.set_defaults(fn=cmd_championship)
     r = sub.add_parser('in-race', help='win and podium odds from a mid-race state (one column per --state)')
     r.add_argument('--season', type=int, default=2025)

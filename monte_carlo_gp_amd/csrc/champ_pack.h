@@ -3,8 +3,11 @@
 // Plain C++, no device code: mcgp_hip.hip includes it for the C ABI, and the host debugging build of the standings
 // kernels (tools/emu/emu_champ.cpp) includes the same text, so that what a test packs on the CPU is what the library
 // packs.  The argument checks (and G, awarded, n_cb, which they compute) stay with the C ABI.  champ_remaining builds
-// the remaining-points tables of mcgp_run_championship_rounds (champ_rounds.hip.h).
+// the remaining-points tables of mcgp_run_championship_rounds (champ_rounds.hip.h).  A call with fastest-lap bonuses
+// (mcgp_run_championship_bonus, champ_bonus.hip.h) hands both its bonus_points: the caller's G and awarded then include
+// the bonuses, pack_championship adds every race's bonus increment and champ_remaining the bonuses still to come.
 #pragma once
+#include "champ_bonus.hip.h"
 #include "championship.hip.h"
 
 #include <algorithm>
@@ -27,14 +30,17 @@ struct ChampPack {
     std::vector<uint8_t> members, n_members;        // [T][n] drivers of each team, [T]
     std::vector<uint64_t> init_key, add;            // [words][n]; [R][n][words]
     std::vector<int32_t> init_pts;                  // [n]
+    std::vector<ChampBonusAdd> bonus_add;           // [R]: the key increment of each race's bonus (zero without one)
 };
 
 // The layouts and tables of a call whose arguments passed mcgp_run_championship's checks.  G: the most points one driver
-// can gain in these races; awarded: the points the races award in all; n_cb: the countback races.  "" if the team keys
-// fit, else the message.
+// can gain in these races; awarded: the points the races award in all; n_cb: the countback races (G and awarded with the
+// bonuses, when the call has them).  bonus_points: [R] or NULL (no race has a bonus).  "" if the team keys fit, else the
+// message.
 inline std::string pack_championship(uint32_t n_races, uint32_t n, const int32_t *points, const uint8_t *countback,
                                      const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
-                                     uint32_t n_teams, uint64_t G, uint64_t awarded, uint32_t n_cb, ChampPack *out)
+                                     uint32_t n_teams, uint64_t G, uint64_t awarded, uint32_t n_cb, ChampPack *out,
+                                     const int32_t *bonus_points = nullptr)
 {
     // ---- key layouts.  Drivers: 5-bit counts and 16-bit points (the limits checked above).  Teams: a team's count in a
     // position grows by at most one per countback race, its points by at most what its drivers can take; the fields
@@ -77,6 +83,11 @@ inline std::string pack_championship(uint32_t n_races, uint32_t n, const int32_t
                 add[((size_t)r * n + p) * words + w] =
                     mcgp::champ_piece((uint64_t)points[(size_t)r * n + p], mcgp::kChampCountBits * (int)n, (int)w) |
                     (countback[r] ? mcgp::champ_piece(1, mcgp::kChampCountBits * (int)(n - 1 - p), (int)w) : 0ull);
+    // the bonus goes to the points field only
+    std::vector<ChampBonusAdd> bonus_add(n_races, ChampBonusAdd{{0, 0, 0}});
+    for (uint32_t r = 0; r < n_races && bonus_points; ++r)
+        for (uint32_t w = 0; w < words; ++w)
+            bonus_add[r].w[w] = mcgp::champ_piece((uint64_t)bonus_points[r], mcgp::kChampCountBits * (int)n, (int)w);
     const uint32_t gain_cols = (uint32_t)G + 1;
     out->words = words;
     out->team_cbits = team_cbits;
@@ -87,15 +98,18 @@ inline std::string pack_championship(uint32_t n_races, uint32_t n, const int32_t
     out->init_key = std::move(init_key);
     out->add = std::move(add);
     out->init_pts = std::move(init_pts);
+    out->bonus_add = std::move(bonus_add);
     return "";
 }
 
 // The points still to be had after race r (include/mcgp.h, "Remaining points"): for a driver M_r = the sum over the
 // later races q of the largest entry of points[q]; for a team of m drivers B_r = the sum over q of the m largest
 // entries of points[q].  driver_rem: [R]; team_rem: [R][T], n_members [T] as pack_championship gives it.  Both are 0
-// in the last row.
+// in the last row.  bonus_points: [R] or NULL; a later race's bonus adds to M_r and, once (one car takes it), to the B_r of
+// every team that has a driver.
 inline void champ_remaining(uint32_t n_races, uint32_t n, const int32_t *points, const uint8_t *n_members, uint32_t n_teams,
-                            std::vector<uint32_t> *driver_rem, std::vector<uint32_t> *team_rem)
+                            std::vector<uint32_t> *driver_rem, std::vector<uint32_t> *team_rem,
+                            const int32_t *bonus_points = nullptr)
 {
     driver_rem->assign(n_races, 0);
     team_rem->assign((size_t)n_races * n_teams, 0);
@@ -109,7 +123,7 @@ inline void champ_remaining(uint32_t n_races, uint32_t n, const int32_t *points,
         uint32_t sum = 0;
         for (uint32_t k = 1; k <= n; ++k) {
             sum += (uint32_t)row[k - 1];
-            best[k] += sum;
+            best[k] += sum + (bonus_points ? (uint32_t)bonus_points[r] : 0u);
         }
     }
 }

@@ -19,6 +19,8 @@
 #include "conditions.hip.h"
 #include "stints.hip.h"
 #include "moves.hip.h"
+#include "fastest.hip.h"
+#include "champ_bonus.hip.h"
 #include "plan_pack.h"
 #include "champ_pack.h"
 
@@ -1160,14 +1162,22 @@ struct ChampRoundsOut {
     uint64_t *round_hist, *contend, *secure, *team_round_hist, *team_contend, *team_secure;
 };
 
-// mcgp_run_championship (rounds == NULL) and mcgp_run_championship_rounds: one body, so that the four season outputs of
-// the two calls come from the same launches.
+// The fastest-lap bonuses of mcgp_run_championship_bonus (NULL for the other two calls: no race has one).
+struct ChampBonus {
+    const int32_t *points, *within;         // [R] each
+    uint64_t *bonus_hist, *fastest_hist;    // [R][n] each, or NULL
+};
+
+// mcgp_run_championship (rounds == NULL), mcgp_run_championship_rounds and mcgp_run_championship_bonus: one body, so that
+// the four season outputs of the calls come from the same launches.  A race without a bonus goes through launch(); a
+// race with one runs race_fastest_kernel (fastest.hip.h) on the same chunk, and champ_bonus behind its champ_accumulate.
 static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
                                 const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
                                 const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
                                 const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
                                 uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
-                                uint64_t *gain_hist, uint64_t *race_hist, const ChampRoundsOut *rounds)
+                                uint64_t *gain_hist, uint64_t *race_hist, const ChampRoundsOut *rounds,
+                                const ChampBonus *bonus = nullptr)
 {
     // ---- every argument is checked before any device is looked up
     if (rounds) {
@@ -1202,6 +1212,19 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         }
         G += (uint64_t)best;
     }
+    if (bonus && (!bonus->points || !bonus->within)) return fail(MCGP_E_BAD_ARG, "bonus_points / bonus_within is NULL");
+    bool any_bonus = false;
+    for (uint32_t r = 0; r < n_races && bonus; ++r) {
+        const int32_t b = bonus->points[r], w = bonus->within[r];
+        if (b < 0 || (uint64_t)b > kMaxPoints)
+            return fail(MCGP_E_BAD_ARG, "bonus_points[" + std::to_string(r) + "] = " + std::to_string(b) + " is outside [0, 65535]");
+        if (b == 0) continue;                               // (bonus_within is ignored where there is no bonus)
+        if (w < 1 || (uint32_t)w > n)
+            return fail(MCGP_E_BAD_ARG, "bonus_within[" + std::to_string(r) + "] = " + std::to_string(w) + " is outside [1, n]");
+        any_bonus = true;
+        G += (uint64_t)b;
+        awarded += (uint64_t)b;
+    }
     for (uint32_t d = 0; d < n; ++d) {
         const int64_t ip = init_points ? init_points[d] : 0;
         if (ip < 0) return fail(MCGP_E_BAD_ARG, "an initial points total is negative");
@@ -1222,11 +1245,15 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         int rc = build_params(&cfgs[r], &drvs[r], grid_probs[r], n, &kps[r]);
         if (rc == MCGP_OK) rc = check_wide(kps[r]);
         if (rc != MCGP_OK) return rc;
+        if (any_bonus && bonus->points[r] > 0 && kps[r].wide)
+            return fail(MCGP_E_BAD_ARG, "bonus_points[" + std::to_string(r) + "]: a race with a bonus runs at MCGP_DEVIATES_32 "
+                                        "only (the generic kernel has no 53-bit path)");
     }
+    const int32_t *bonus_pts = any_bonus ? bonus->points : nullptr;     // NULL: every race through launch(), as without bonuses
     // ---- key layouts and the kernels' tables (champ_pack.h)
     mcgp::ChampPack pk;
     const std::string pack_err = mcgp::pack_championship(n_races, n, points, countback, init_points, init_counts, team,
-                                                         n_teams, G, awarded, n_cb, &pk);
+                                                         n_teams, G, awarded, n_cb, &pk, bonus_pts);
     if (!pack_err.empty()) return fail(MCGP_E_BAD_ARG, pack_err);
     if (n_sims == 0) return MCGP_OK;
     const uint32_t words = pk.words, team_cbits = pk.team_cbits, team_words = pk.team_words, gain_cols = pk.gain_cols;
@@ -1241,9 +1268,19 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
     const size_t rh_cells = rounds ? (size_t)n_races * n * n : 0, rc_cells = rounds ? (size_t)n_races * n : 0;
     const size_t trh_cells = (size_t)n_races * round_T * round_T, trc_cells = (size_t)n_races * round_T;
     const size_t round_cells = rh_cells + 2 * rc_cells + trh_cells + 2 * trc_cells;
-    const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells + round_cells;
+    // bonus [R][n] | fastest [R][n], behind the per-round counts
+    const size_t bonus_cells = bonus_pts ? (size_t)n_races * n : 0;
+    const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells + round_cells + 2 * bonus_cells;
     std::vector<uint32_t> driver_rem, team_rem;
-    if (rounds) mcgp::champ_remaining(n_races, n, points, n_members.data(), n_teams, &driver_rem, &team_rem);
+    if (rounds) mcgp::champ_remaining(n_races, n, points, n_members.data(), n_teams, &driver_rem, &team_rem, bonus_pts);
+    // the parameter blocks of the bonus races, in race order (kp_index[r]: the race's block, -1 without a bonus)
+    std::vector<mcgp::KParams> bonus_kps;
+    std::vector<int> kp_index(n_races, -1);
+    for (uint32_t r = 0; r < n_races && bonus_pts; ++r)
+        if (bonus_pts[r] > 0) {
+            kp_index[r] = (int)bonus_kps.size();
+            bonus_kps.push_back(kps[r]);
+        }
     Counts counts;
     const int rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         // rank kernel's LDS: the gain histogram joins the block when the block still leaves room for a second one
@@ -1263,20 +1300,31 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         if (rounds)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::champ_round),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)round_lds));
-        // workspace: orders staging of one chunk | the chunk's standing keys | tables | histograms
+        const KernelFn fast_fn = reinterpret_cast<KernelFn>(&mcgp::race_fastest_kernel);   // (for its register count)
+        if (bonus_pts)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_fastest_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
+        // workspace: orders staging of one chunk | the chunk's standing keys | tables | histograms | the bonus races'
+        // parameter blocks | the chunk's fastest-lap bytes (two rows of the chunk's capacity)
         const uint64_t cap = std::min(n_sims, kOrdersChunk);
         Layout ws;
         const size_t o_orders = ws.add(cap * n), o_keys = ws.add((size_t)words * n * cap * 8), o_add = ws.add(add.size() * 8);
         const size_t o_init = ws.add(init_key.size() * 8), o_mem = ws.add(members.size()), o_nmem = ws.add(n_teams);
         const size_t o_ipts = ws.add(4 * n), o_trem = ws.add(4 * team_rem.size()), o_hist = ws.add(hist_cells * 8);
+        const size_t o_bkp = ws.add(sizeof(mcgp::KParams) * bonus_kps.size()), o_fl = ws.add(bonus_pts ? 2 * cap : 0);
         int r = c.work.reserve(ws.bytes);
         if (r != MCGP_OK) return r;
         uint8_t *d_orders = c.work.at<uint8_t>(o_orders);
         uint64_t *d_keys = c.work.at<uint64_t>(o_keys);
+        uint8_t *d_fl = c.work.at<uint8_t>(o_fl);
         unsigned long long *h_champ = c.work.at<unsigned long long>(o_hist), *h_team = h_champ + champ_cells;
         unsigned long long *h_gain = h_team + team_cells, *h_race = h_gain + gain_cells;
         unsigned long long *h_round = h_race + race_cells, *h_contend = h_round + rh_cells, *h_secure = h_contend + rc_cells;
         unsigned long long *h_tround = h_secure + rc_cells, *h_tcontend = h_tround + trh_cells, *h_tsecure = h_tcontend + trc_cells;
+        unsigned long long *h_bonus = h_tsecure + trc_cells, *h_fastest = h_bonus + bonus_cells;
+        if (!bonus_kps.empty())
+            HIP_TRY(hipMemcpyAsync(c.work.at(o_bkp), bonus_kps.data(), sizeof(mcgp::KParams) * bonus_kps.size(),
+                                   hipMemcpyHostToDevice, nullptr));
         if (!team_rem.empty())
             HIP_TRY(hipMemcpyAsync(c.work.at(o_trem), team_rem.data(), 4 * team_rem.size(), hipMemcpyHostToDevice, nullptr));
         HIP_TRY(hipMemcpyAsync(c.work.at(o_add), add.data(), add.size() * 8, hipMemcpyHostToDevice, nullptr));
@@ -1300,15 +1348,35 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
             // chunk-outer, race-inner: every race of the chunk through mcgp_run's own launch path, its orders into the
             // staging buffer, then folded into the keys before the next race overwrites them
             for (uint32_t rr = 0; rr < n_races; ++rr) {
-                r = launch(c, kps[rr], m, sim_offset + done, seeds[rr], nullptr,
-                           race_hist ? h_race + (size_t)rr * n * n : c.d_hist, d_orders, nullptr);
-                if (r != MCGP_OK) return r;
+                unsigned long long *h_this = race_hist ? h_race + (size_t)rr * n * n : c.d_hist;
+                if (kp_index[rr] < 0) {
+                    r = launch(c, kps[rr], m, sim_offset + done, seeds[rr], nullptr, h_this, d_orders, nullptr);
+                    if (r != MCGP_OK) return r;
+                } else {
+                    // the generic kernel's block shape and LDS (m <= 2^22: one launch)
+                    uint32_t grid = 0, block = 0, lds = 0;
+                    r = generic_geometry(c, fast_fn, "fastest-lap", n, m, &grid, &block, &lds);
+                    if (r != MCGP_OK) return r;
+                    const uint64_t n_batches = (m + block - 1) / block;
+                    hipLaunchKernelGGL(mcgp::race_fastest_kernel, dim3(grid), dim3(block), lds, nullptr,
+                                       c.work.at<const mcgp::KParams>(o_bkp) + kp_index[rr], m, sim_offset + done,
+                                       (uint32_t)seeds[rr], (uint32_t)(seeds[rr] >> 32), h_this, d_orders, d_fl, d_fl + cap,
+                                       (uint32_t)n_batches);
+                    HIP_TRY(hipGetLastError());
+                    note_launch(c, grid, block, lds, "mcgp::race_fastest_kernel");
+                }
                 const uint64_t tiles = (m + mcgp::kChampAccBlock - 1) / mcgp::kChampAccBlock;
                 hipLaunchKernelGGL(mcgp::champ_accumulate, dim3((uint32_t)std::min(tiles, acc_cap)), dim3(mcgp::kChampAccBlock), 0,
                                    nullptr, d_orders, m, n, words, cap, d_keys,
                                    c.work.at<const uint64_t>(o_add) + (size_t)rr * n * words, c.work.at<const uint64_t>(o_init),
                                    rr == 0 ? 1u : 0u);
                 HIP_TRY(hipGetLastError());
+                if (kp_index[rr] >= 0) {
+                    hipLaunchKernelGGL(mcgp::champ_bonus, dim3((uint32_t)std::min(tiles, acc_cap)), dim3(mcgp::kChampAccBlock), 0,
+                                       nullptr, d_fl, d_fl + cap, m, n, words, cap, d_keys, pk.bonus_add[rr],
+                                       (uint32_t)bonus->within[rr], h_fastest + (size_t)rr * n, h_bonus + (size_t)rr * n);
+                    HIP_TRY(hipGetLastError());
+                }
                 if (rounds) {
                     // the standings as they now are, before the next race adds to them
                     const uint64_t rtiles = (m + mcgp::kChampTile - 1) / mcgp::kChampTile;
@@ -1342,6 +1410,10 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         segs.push_back({rounds->team_contend, trc_cells});
         segs.push_back({rounds->team_secure, trc_cells});
     }
+    if (bonus) {
+        segs.push_back({bonus->bonus_hist, bonus_cells});
+        segs.push_back({bonus->fastest_hist, bonus_cells});
+    }
     counts.add_to(segs);
     return MCGP_OK;
 }
@@ -1369,6 +1441,27 @@ int32_t mcgp_run_championship_rounds(uint32_t n_races, const mcgp_config *cfgs, 
     const ChampRoundsOut rounds = {round_hist, contend_out, secure_out, team_round_hist, team_contend_out, team_secure_out};
     return run_championship(n_races, cfgs, drvs, grid_probs, n, n_sims, sim_offset, seeds, points, countback, init_points,
                             init_counts, team, n_teams, device, champ_hist, team_hist, gain_hist, race_hist, &rounds);
+}
+
+int32_t mcgp_run_championship_bonus(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                                    const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                                    const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                                    const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                                    uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                                    uint64_t *gain_hist, uint64_t *race_hist, uint64_t *round_hist, uint64_t *contend_out,
+                                    uint64_t *secure_out, uint64_t *team_round_hist, uint64_t *team_contend_out,
+                                    uint64_t *team_secure_out, const int32_t *bonus_points, const int32_t *bonus_within,
+                                    uint64_t *bonus_hist, uint64_t *fastest_hist)
+{
+    const ChampRoundsOut rounds = {round_hist, contend_out, secure_out, team_round_hist, team_contend_out, team_secure_out};
+    const ChampBonus bonus = {bonus_points, bonus_within, bonus_hist, fastest_hist};
+    const bool by_round = round_hist || contend_out || secure_out;      // all three NULL: no per-round work
+    if (!by_round && (team_round_hist || team_contend_out || team_secure_out))
+        return fail(MCGP_E_BAD_ARG, "team_round_hist, team_contend_out and team_secure_out need round_hist, contend_out and "
+                                    "secure_out");
+    return run_championship(n_races, cfgs, drvs, grid_probs, n, n_sims, sim_offset, seeds, points, countback, init_points,
+                            init_counts, team, n_teams, device, champ_hist, team_hist, gain_hist, race_hist,
+                            by_round ? &rounds : nullptr, &bonus);
 }
 
 int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,

@@ -1610,6 +1610,7 @@ DEFAULT_POINTS = (25, 18, 15, 12, 10, 8, 6, 4, 2, 1)      # a Grand Prix, positi
 MAX_RACES = 64                                             # include/mcgp.h: mcgp_run_championship limits
 MAX_TOTAL_POINTS = 65535
 MAX_POSITION_COUNT = 31
+DEFAULT_FASTEST_LAP_WITHIN = 10                            # the 2019-2024 rule: classified in the top ten
 
 
 @dataclass
@@ -1622,7 +1623,12 @@ class ChampionshipResult:
     With by_round=True (None otherwise), the standings after every race r of the call (include/mcgp.h:
     mcgp_run_championship_rounds): round_hist [R][n][n] = [race][driver][standings position], contend [R][n] and
     secure [R][n] = simulations in which the driver is in contention / has the title secure after race r, and
-    team_round_hist [R][T][T], team_contend [R][T], team_secure [R][T] for the constructors."""
+    team_round_hist [R][T][T], team_contend [R][T], team_secure [R][T] for the constructors.
+
+    When some race has a fastest-lap bonus (the races' `fastest_lap_points`; None otherwise, include/mcgp.h:
+    mcgp_run_championship_bonus): fastest_lap_counts [R][n] = simulations in which the driver set race r's fastest lap,
+    bonus_counts [R][n] = those in which the driver also took the bonus (rows of races without a bonus are zero), and
+    bonus_points [R] the bonus of each race."""
     drivers: list
     teams: list
     n_simulations: int
@@ -1637,6 +1643,10 @@ class ChampionshipResult:
     team_round_hist: np.ndarray | None = None
     team_contend: np.ndarray | None = None
     team_secure: np.ndarray | None = None
+    fastest_lap_counts: np.ndarray | None = None
+    bonus_counts: np.ndarray | None = None
+    bonus_points: list | None = None
+    team_index: list | None = None           # [n] index into `teams` of each driver
 
     @property
     def title_probabilities(self) -> dict:
@@ -1720,6 +1730,34 @@ class ChampionshipResult:
     def constructor_clinch_round_probabilities(self) -> dict:
         return self._clinch(self.team_secure, self.teams, 'constructor_clinch_round_probabilities')
 
+    # ---- fastest-lap bonus (races with `fastest_lap_points`)
+    def _bonus(self, what):
+        if self.bonus_counts is None:
+            raise ValueError(f'{what} needs a race with fastest_lap_points')
+        return np.asarray(self.bonus_counts, np.int64)
+
+    @property
+    def bonus_probabilities_by_round(self) -> list:
+        """[race] {driver: P(takes that race's fastest-lap bonus)}; all zero for a race without a bonus."""
+        counts = self._bonus('bonus_probabilities_by_round')
+        return [{d: int(row[i]) / self.n_simulations for i, d in enumerate(self.drivers)} for row in counts]
+
+    @property
+    def expected_bonus_points(self) -> dict:
+        """{driver: mean bonus points over these races} (part of expected_points)."""
+        counts = self._bonus('expected_bonus_points')
+        e = np.asarray(self.bonus_points, np.int64) @ counts
+        return {d: int(e[i]) / self.n_simulations for i, d in enumerate(self.drivers)}
+
+    @property
+    def expected_constructor_bonus_points(self) -> dict:
+        """{team: mean bonus points of its drivers over these races}."""
+        per_driver = self.expected_bonus_points
+        out = {t: 0.0 for t in self.teams}
+        for i, d in enumerate(self.drivers):
+            out[self.teams[self.team_index[i]]] += per_driver[d]
+        return out
+
 
 def _standings_arrays(standings, drivers):
     """{driver: points} or {driver: {'points': p, 'finishes': [count of P1, P2, ...]}} -> (points [n], counts [n][n])."""
@@ -1752,8 +1790,11 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
 
     `races`: a list of dicts with the keys run_monte_carlo_batch takes (`config`, `grid_probs`, `base_pace`,
     `tire_deg`, `driver_variance`, optional `driver_dnf_rates`, `seed`, `track_condition`, `deviates`), plus `points`
-    (the table of positions 1, 2, ...; default 25-18-15-12-10-8-6-4-2-1) and `countback` (default True; False for a
-    sprint, whose results score but do not break ties).  Simulation s of the season is the tuple of what
+    (the table of positions 1, 2, ...; default 25-18-15-12-10-8-6-4-2-1), `countback` (default True; False for a
+    sprint, whose results score but do not break ties), `fastest_lap_points` (default 0: the bonus for the driver who
+    sets the race's fastest lap) and `fastest_lap_within` (default 10, at most the field size: the classified positions
+    that take it).  A race with a bonus runs on the lap-time-tracking kernel, several times the cost of one without
+    (include/mcgp.h: mcgp_run_championship_bonus); with no bonus anywhere the call is what it was.  Simulation s of the season is the tuple of what
     run_monte_carlo gives each race alone for simulation id s under that race's seed.
 
     The driver order is the first race's grid_probs key order; every race must have the same driver set.  Teams come
@@ -1785,6 +1826,8 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
     probs, grids, seeds, deviates = [], [], [], []
     points = np.zeros((len(races), n), np.int32)
     countback = np.zeros(len(races), np.uint8)
+    bonus_pts = np.zeros(len(races), np.int32)
+    bonus_within = np.ones(len(races), np.int32)
     for r, race in enumerate(races):
         gp = {str(k): v for k, v in race['grid_probs'].items()}
         if set(gp) != set(drivers) or len(gp) != n:
@@ -1800,6 +1843,14 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
             raise ValueError(f'race {r}: points must not be negative')
         points[r, :min(n, len(table))] = table[:n]           # positions past the table score 0
         countback[r] = 1 if race.get('countback', True) else 0
+        fl = int(race.get('fastest_lap_points', 0))
+        within = int(race.get('fastest_lap_within', DEFAULT_FASTEST_LAP_WITHIN))
+        if fl < 0 or fl > MAX_TOTAL_POINTS:
+            raise ValueError(f'race {r}: fastest_lap_points must be in [0, {MAX_TOTAL_POINTS}], got {fl}')
+        if fl > 0 and within < 1:
+            raise ValueError(f'race {r}: fastest_lap_within must be at least 1, got {within}')
+        bonus_pts[r] = fl
+        bonus_within[r] = max(1, min(within, n))
     teams_of = races[0]['config'].driver_teams
     team_names = []
     for d in drivers:
@@ -1809,7 +1860,8 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
     team = np.array([team_names.index(str(teams_of.get(d, 'Unknown'))) for d in drivers], np.int32)
     init_pts, init_counts = _standings_arrays(standings, drivers)
     # the limits of the device's standing keys (the library rejects the same calls with MCGP_E_BAD_ARG)
-    G = int(points.max(axis=1).sum())
+    with_bonus = bool((bonus_pts > 0).any())
+    G = int(points.max(axis=1).sum()) + int(bonus_pts.sum())
     if int(init_pts.max()) + G > MAX_TOTAL_POINTS:
         raise ValueError(f'a driver could reach {int(init_pts.max()) + G} points: the limit is {MAX_TOTAL_POINTS}')
     worst = int(init_counts.max()) + int(countback.sum())
@@ -1828,6 +1880,9 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
     if by_round and not hasattr(lib, 'mcgp_run_championship_rounds'):
         raise N.McgpError(-1, 'the loaded library does not export mcgp_run_championship_rounds: by_round=True needs a '
                               'library built from sources that have it')
+    if with_bonus and not hasattr(lib, 'mcgp_run_championship_bonus'):
+        raise N.McgpError(-1, 'the loaded library does not export mcgp_run_championship_bonus: fastest_lap_points needs '
+                              'a library built from sources that have it')
     cfgs = (N.McgpConfig * R)(*[p.cfg for p in probs])
     drvs = (N.McgpDrivers * R)(*[p.drv for p in probs])
     gptrs = (C.POINTER(C.c_double) * R)(*[_dptr(g) for g in grids])
@@ -1843,13 +1898,18 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
         args = (R, cfgs, drvs, gptrs, n, int(count), int(sim_offset) + int(offset), seeds_c, i32(points),
                 countback.ctypes.data_as(C.POINTER(C.c_uint8)), i32(init_pts32), i32(init_counts32), i32(team), T, int(dev),
                 u64(ch), u64(th), u64(gh), u64(rh) if rh is not None else None)
-        rounds = ()
+        rounds = bonus = ()
         if by_round:
             rounds = tuple(np.zeros(shape, np.uint64) for shape in ((R, n, n), (R, n), (R, n), (R, T, T), (R, T), (R, T)))
+        if with_bonus:
+            bonus = (np.zeros((R, n), np.uint64), np.zeros((R, n), np.uint64))          # bonus_hist, fastest_hist
+            rc = lib.mcgp_run_championship_bonus(*args, *([u64(a) for a in rounds] if by_round else [None] * 6),
+                                                 i32(bonus_pts), i32(bonus_within), *[u64(a) for a in bonus])
+        elif by_round:
             rc = lib.mcgp_run_championship_rounds(*args, *[u64(a) for a in rounds])
         else:
             rc = lib.mcgp_run_championship(*args)
-        return (ch, th, gh, rh) + rounds, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+        return (ch, th, gh, rh) + rounds + bonus, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
 
     if len(devices) == 1:
         parts = [run_shard(devices[0], 0, n_simulations)]
@@ -1869,7 +1929,10 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
         gain_hist=total(2), initial_points={d: int(init_pts[i]) for i, d in enumerate(drivers)},
         race_histograms=list(total(3)) if return_race_histograms else None,
         **({k: total(4 + i) for i, k in enumerate(('round_hist', 'contend', 'secure', 'team_round_hist', 'team_contend',
-                                                   'team_secure'))} if by_round else {}))
+                                                   'team_secure'))} if by_round else {}),
+        team_index=[int(t) for t in team],
+        **(dict(bonus_counts=total(-2), fastest_lap_counts=total(-1), bonus_points=[int(b) for b in bonus_pts])
+           if with_bonus else {}))
 
 
 def histogram_to_probs(hist, drivers, n_simulations):

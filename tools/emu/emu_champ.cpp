@@ -3,7 +3,8 @@
 // <hip/hip_runtime.h> of this directory in its EMU_BLOCK_THREADS mode and calls the two real __global__ functions,
 // champ_accumulate and champ_rank, on finishing orders the caller hands in.  The key layout and the kernels' tables
 // come from csrc/champ_pack.h, the text the C ABI itself uses.  emu_champ_rounds_run does the same for champ_round
-// (csrc/champ_rounds.hip.h), the per-round standings kernel of mcgp_run_championship_rounds.
+// (csrc/champ_rounds.hip.h), the per-round standings kernel of mcgp_run_championship_rounds, and emu_champ_bonus_run for
+// champ_bonus (csrc/champ_bonus.hip.h), the fastest-lap bonus of mcgp_run_championship_bonus.
 //
 // Execution model: REAL BLOCK SEMANTICS.  A block is 256 host threads (both kernels have a fixed block of 256) that
 // run at the same time and meet at __syncthreads(), a pthread barrier; atomicAdd is __atomic_fetch_add; a __shared__
@@ -304,6 +305,84 @@ int emu_champ_rounds_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t
             emu_dynamic_lds = nullptr;
         }
     }
+    return MCGP_OK;
+}
+
+// The standing keys of n_sims seasons with fastest-lap bonuses: emu_champ_run's inputs, and per race bonus_points [R],
+// bonus_within [R] and the two byte rows race_fastest_kernel leaves, fl_driver and fl_pos [R][n_sims] (rows of races
+// without a bonus are not read).  The argument checks are the library's: the bonuses join G and awarded before the
+// limits.  Per chunk and race: champ_accumulate, then champ_bonus where the race has a bonus, on a grid of at most
+// acc_grid blocks.  keys_out [words][n][cap]: the key buffer after the last chunk, for the caller to decode; bonus_hist
+// and fastest_hist [R][n] are ACCUMULATED into.  info_out: NULL or {words, team_cbits, team_words, gain_cols}.
+int emu_champ_bonus_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t cap, const uint8_t *orders,
+                        const int32_t *points, const uint8_t *countback, const int32_t *init_points,
+                        const int32_t *init_counts, const int32_t *team, uint32_t n_teams, const int32_t *bonus_points,
+                        const int32_t *bonus_within, const uint8_t *fl_driver, const uint8_t *fl_pos, uint32_t acc_grid,
+                        uint64_t *keys_out, unsigned long long *bonus_hist, unsigned long long *fastest_hist,
+                        uint32_t *info_out, const char **err)
+{
+    static const char *none = "";
+    *err = none;
+    if (!orders || !points || !countback || !team || !bonus_points || !bonus_within || !fl_driver || !fl_pos || !keys_out ||
+        !bonus_hist || !fastest_hist)
+        return fail(MCGP_E_BAD_ARG, "a championship array is NULL", err);
+    // check_season's limits hold without the bonuses; G and awarded then take them, and the points limit is tested again
+    uint64_t G = 0, awarded = 0;
+    uint32_t n_cb = 0;
+    if (n_races < 1 || n_races > (uint32_t)mcgp::kChampMaxRaces) return fail(MCGP_E_BAD_ARG, "n_races must be in [1, 64]", err);
+    if (n < 1 || n > MCGP_MAX_CARS) return fail(MCGP_E_BAD_ARG, "n must be in [1, 32]", err);
+    uint64_t bonus_sum = 0;
+    for (uint32_t r = 0; r < n_races; ++r) {
+        if (bonus_points[r] < 0 || bonus_points[r] > 65535) return fail(MCGP_E_BAD_ARG, "bonus_points is outside [0, 65535]", err);
+        if (bonus_points[r] > 0 && (bonus_within[r] < 1 || (uint32_t)bonus_within[r] > n))
+            return fail(MCGP_E_BAD_ARG, "bonus_within is outside [1, n]", err);
+        bonus_sum += (uint64_t)bonus_points[r];
+    }
+    const int chk = check_season(n_races, n, n_sims, cap, orders, points, countback, init_points, init_counts, team, n_teams,
+                                 acc_grid, 1, &G, &awarded, &n_cb, err);
+    if (chk != MCGP_OK) return chk;
+    G += bonus_sum;
+    awarded += bonus_sum;
+    for (uint32_t d = 0; d < n; ++d)
+        if ((uint64_t)(init_points ? init_points[d] : 0) + G > 65535)
+            return fail(MCGP_E_BAD_ARG, "a driver's total points may leave [0, 65535]", err);
+    mcgp::ChampPack pk;
+    const std::string e = mcgp::pack_championship(n_races, n, points, countback, init_points, init_counts, team, n_teams, G,
+                                                  awarded, n_cb, &pk, bonus_points);
+    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    const uint32_t words = pk.words;
+    if (info_out) {
+        const uint32_t info[4] = {words, pk.team_cbits, pk.team_words, pk.gain_cols};
+        std::memcpy(info_out, info, sizeof(info));
+    }
+    if (n_sims == 0) return MCGP_OK;
+    if (cap > n_sims) cap = n_sims;
+    std::vector<uint64_t> keys((size_t)words * n * cap);
+    std::memset(keys.data(), 0xA5, keys.size() * 8);
+    g_pool.start();
+    for (uint64_t done = 0; done < n_sims; done += cap) {
+        const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
+        for (uint32_t rr = 0; rr < n_races; ++rr) {
+            std::vector<uint32_t> stage((m * n + 3) / 4 + 1);
+            uint8_t *d_orders = reinterpret_cast<uint8_t *>(stage.data());
+            std::memcpy(d_orders, orders + ((size_t)rr * n_sims + done) * n, m * n);
+            const uint64_t tiles = (m + mcgp::kChampAccBlock - 1) / mcgp::kChampAccBlock;
+            const uint64_t *add = pk.add.data() + (size_t)rr * n * words;
+            const uint32_t first = rr == 0 ? 1u : 0u;
+            launch((unsigned)(tiles < acc_grid ? tiles : acc_grid), [&] {
+                mcgp::champ_accumulate(d_orders, m, n, words, cap, keys.data(), add, pk.init_key.data(), first);
+            });
+            if (bonus_points[rr] == 0) continue;
+            // the chunk's two byte rows in buffers of their own size (an index past the chunk is past the allocation)
+            std::vector<uint8_t> d_drv(fl_driver + (size_t)rr * n_sims + done, fl_driver + (size_t)rr * n_sims + done + m);
+            std::vector<uint8_t> d_pos(fl_pos + (size_t)rr * n_sims + done, fl_pos + (size_t)rr * n_sims + done + m);
+            launch((unsigned)(tiles < acc_grid ? tiles : acc_grid), [&] {
+                mcgp::champ_bonus(d_drv.data(), d_pos.data(), m, n, words, cap, keys.data(), pk.bonus_add[rr],
+                                  (uint32_t)bonus_within[rr], fastest_hist + (size_t)rr * n, bonus_hist + (size_t)rr * n);
+            });
+        }
+    }
+    std::memcpy(keys_out, keys.data(), keys.size() * 8);
     return MCGP_OK;
 }
 

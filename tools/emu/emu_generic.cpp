@@ -1,9 +1,9 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
 // fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
-// strategy.hip.h, gaps.hip.h, conditions.hip.h, stints.hip.h and moves.hip.h with g++ through the stand-in
+// strategy.hip.h, gaps.hip.h, conditions.hip.h, stints.hip.h, moves.hip.h and fastest.hip.h with g++ through the stand-in
 // <hip/hip_runtime.h> of this directory and calls the real __global__ functions: race_kernel, race_resume_kernel,
 // race_trace_kernel, race_strategy_kernel<false / true>, race_gaps_kernel<false / true>, race_conditions_kernel<false /
-// true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false / true>.
+// true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false / true>, race_fastest_kernel.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -18,7 +18,7 @@
 // records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
 // operation and strides by its block's size, so it does run here, as blocks of one thread.
 // tests/test_generic_host_build.py, tests/test_gaps_host_build.py, tests/test_conditions_host_build.py,
-// tests/test_stints_host_build.py, tests/test_moves_host_build.py.
+// tests/test_stints_host_build.py, tests/test_moves_host_build.py, tests/test_fastest_host_build.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -31,6 +31,7 @@
 #include "../../monte_carlo_gp_amd/csrc/conditions.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/stints.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/moves.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/fastest.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/plan_pack.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -280,6 +281,22 @@ int emu_moves_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double 
     one_thread_block(1);
     const auto kernel = state ? &mcgp::race_moves_kernel<true> : &mcgp::race_moves_kernel<false>;
     kernel(&kp, &st, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage, stride, (uint32_t)n_sims);
+    return MCGP_OK;
+}
+
+// race_fastest_kernel: simulations sim_offset + [0, n_sims).  hist [n][n] is accumulated into; orders [n_sims][n],
+// fl_driver [n_sims] and fl_pos [n_sims] are written, in the layout documented at the top of csrc/fastest.hip.h.
+int emu_fastest_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n, uint64_t n_sims,
+                    uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *orders, uint8_t *fl_driver,
+                    uint8_t *fl_pos, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if (!grid_probs || !orders || !fl_driver || !fl_pos) return fail(MCGP_E_BAD_ARG, "grid_probs / an output is NULL", err);
+    one_thread_block(1);
+    mcgp::race_fastest_kernel(&kp, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, orders, fl_driver, fl_pos,
+                              (uint32_t)n_sims);
     return MCGP_OK;
 }
 
