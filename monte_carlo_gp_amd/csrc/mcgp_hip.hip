@@ -162,6 +162,9 @@ struct DeviceCtx {
     // Parameter blocks: a small ring so that a launch never rewrites a block an
     // earlier, still running launch reads; an unchanged problem re-uses its block
     // with no upload at all (bench.py's steady state).
+    // Behind each block, in the same allocation, sits the retirement table of its problem (kRetireTabOffset,
+    // race_common.hip.h): a function of the block's bytes, built when the block is and uploaded in the same copy, so a
+    // block that is re-used brings the table of exactly its rates and laps.
     struct Slot {
         mcgp::KParams *dev = nullptr;
         mcgp::KParams *host = nullptr;        // pinned copy of what `dev` holds
@@ -283,8 +286,8 @@ int init_ctx_body(int device, DeviceCtx &c)
     c.cu_count = prop.multiProcessorCount;
     c.lds_per_block = lds_limit(prop.sharedMemPerBlock);       // 160 KiB on gfx950
     for (auto &sl : c.slot) {
-        HIP_TRY(hipMalloc(&sl.dev, sizeof(mcgp::KParams)));
-        HIP_TRY(hipHostMalloc(&sl.host, sizeof(mcgp::KParams)));
+        HIP_TRY(hipMalloc(&sl.dev, mcgp::kRetireTabOffset + mcgp::kRetireTabMaxBytes));
+        HIP_TRY(hipHostMalloc(&sl.host, mcgp::kRetireTabOffset + mcgp::kRetireTabMaxBytes));
         HIP_TRY(hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming));
     }
     HIP_TRY(hipMalloc(&c.d_hist, sizeof(unsigned long long) * MCGP_MAX_CARS * MCGP_MAX_CARS));
@@ -347,7 +350,8 @@ namespace mcgp {
                                                              unsigned long long *, uint8_t *, const uint8_t *, uint32_t,       \
                                                              uint32_t *, uint32_t *, const double *);                          \
     extern template __global__ void race_kernel_reg_batch<N_>(const KParams *, const BatchItem *, uint32_t, uint64_t,          \
-                                                              unsigned long long *, uint32_t, uint32_t *, uint32_t *);
+                                                              unsigned long long *, uint32_t, uint32_t *, uint32_t *,      \
+                                                              uint32_t);
 MCGP_REG_SIZES(X)
 #undef X
 }  // namespace mcgp
@@ -355,7 +359,7 @@ MCGP_REG_SIZES(X)
 namespace {
 
 using BatchKernelFn = void (*)(const mcgp::KParams *, const mcgp::BatchItem *, uint32_t, uint64_t, unsigned long long *,
-                               uint32_t, uint32_t *, uint32_t *);
+                               uint32_t, uint32_t *, uint32_t *, uint32_t);
 using WideKernelFn = void (*)(const mcgp::KParams *, uint64_t, uint64_t, uint32_t, uint32_t, unsigned long long *,
                               uint8_t *, const uint8_t *, uint32_t, uint32_t *, uint32_t *, const double *);
 
@@ -635,7 +639,11 @@ int launch(DeviceCtx &c, const mcgp::KParams &kp, uint64_t n_sims, uint64_t sim_
         std::memcpy(sl->host, &kp, sizeof(kp));
         sl->used = true;
         sl->shareable = !fe.on;
-        HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, sizeof(kp), hipMemcpyHostToDevice, stream));
+        // the register kernels' retirement table, behind the block (built for every block: which kernel serves a
+        // re-used block is decided per launch)
+        mcgp::build_retire_table(kp, kp.wide != 0, reinterpret_cast<unsigned char *>(sl->host) + mcgp::kRetireTabOffset);
+        const size_t upload = mcgp::kRetireTabOffset + mcgp::retire_table_bytes(kp.n, kp.total_laps, kp.wide != 0);
+        HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, upload, hipMemcpyHostToDevice, stream));
         if (fe.on) {
             // the n x n matrix goes from the front-end kernel straight into the block's grid_probs slot, on
             // the launch stream, between the upload and the race kernel (the slot is marked not shareable:
@@ -1100,6 +1108,16 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
     }
     const uint32_t n_shared = (uint32_t)kps.size();
     const size_t cells = (size_t)n * n;
+    // the parameter blocks of the shared launch as the kernel reads them: `param_stride` bytes apart, each with its
+    // problem's retirement table behind it (build_retire_table; room for the largest: the problems may differ in laps)
+    size_t param_stride = 0;
+    for (const mcgp::KParams &k : kps) param_stride = std::max(param_stride, mcgp::retire_table_bytes(k.n, k.total_laps, false));
+    param_stride = mcgp::kRetireTabOffset + (param_stride + 255) / 256 * 256;
+    std::vector<unsigned char> blocks(param_stride * n_shared);
+    for (uint32_t j = 0; j < n_shared; ++j) {
+        std::memcpy(blocks.data() + param_stride * j, &kps[j], sizeof(mcgp::KParams));
+        mcgp::build_retire_table(kps[j], false, blocks.data() + param_stride * j + mcgp::kRetireTabOffset);
+    }
     Counts counts;
     const int rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         // geometry of the shared launch: the register kernel's block, one more LDS word that names the block's next problem
@@ -1116,10 +1134,10 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
         const uint64_t n_tasks = ((uint64_t)n_shared * n_chunks + (uint64_t)waves - 1) / (uint64_t)waves;
         uint64_t grid = (uint64_t)c.cu_count * (uint64_t)blocks_per_cu;
         if (grid > n_tasks) grid = n_tasks;
-        // workspace: parameter blocks | items | histograms (the shared launch's problems, then the solo ones) | one ticket
-        // counter per problem of the shared launch | its lanes' retirement lists
+        // workspace: parameter blocks with their retirement tables | items | histograms (the shared launch's problems, then
+        // the solo ones) | one ticket counter per problem of the shared launch | its lanes' retirement lists
         Layout ws;
-        const size_t o_kps = ws.add(sizeof(mcgp::KParams) * n_shared), o_items = ws.add(sizeof(mcgp::BatchItem) * n_shared);
+        const size_t o_kps = ws.add(blocks.size()), o_items = ws.add(sizeof(mcgp::BatchItem) * n_shared);
         const size_t o_hist = ws.add(sizeof(unsigned long long) * cells * n_problems);
         const size_t o_ticket = ws.add(sizeof(uint32_t) * n_shared);
         const size_t o_retire = ws.add(mcgp::reg_retire_ws_bytes((int)n, (size_t)grid * block));
@@ -1131,12 +1149,12 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
             const BatchKernelFn kernel = rk->batch;
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)c.lds_per_block));
-            HIP_TRY(hipMemcpyAsync(c.work.at(o_kps), kps.data(), sizeof(mcgp::KParams) * n_shared, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(c.work.at(o_kps), blocks.data(), blocks.size(), hipMemcpyHostToDevice, nullptr));
             HIP_TRY(hipMemcpyAsync(c.work.at(o_items), items.data(), sizeof(mcgp::BatchItem) * n_shared, hipMemcpyHostToDevice,
                                    nullptr));
             hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(block), lds, nullptr, c.work.at<const mcgp::KParams>(o_kps),
                                c.work.at<const mcgp::BatchItem>(o_items), n_shared, n_sims, d_hist, n_chunks,
-                               c.work.at<uint32_t>(o_ticket), c.work.at<uint32_t>(o_retire));
+                               c.work.at<uint32_t>(o_ticket), c.work.at<uint32_t>(o_retire), (uint32_t)param_stride);
             HIP_TRY(hipGetLastError());
             note_launch(c, (uint32_t)grid, block, (uint32_t)lds, "mcgp::race_kernel_reg_batch<%u>", n);
         }

@@ -112,4 +112,37 @@ inline int build_params(const mcgp_config *cfg, const mcgp_drivers *drv, const d
     return MCGP_OK;
 }
 
+static_assert(MCGP_MAX_LAPS == kMaxLaps && MCGP_MAX_CARS == kMaxCars, "limits of the retirement table");
+
+// The retirement thresholds of a problem (race_common.hip.h: retirement_lap_from_table), the chain of draw_retirement_lap
+// step for step: row d = S_2 .. S_L of driver d, S_2 = q, then zeros to the end of the row; a driver who never retires
+// (t_dnf = 0) and the padding rows are all zeros.  `out`: retire_table_bytes(n, total_laps, wide) bytes, u32 entries,
+// or u64 for the 64-bit chain of the reference-width kernel (wide).  A function of (t_dnf, q64_dnf, total_laps) alone.
+inline void build_retire_table(const KParams &kp, bool wide, void *out)
+{
+    const int L = kp.total_laps;
+    const size_t row = retire_row_entries(L);
+    std::memset(out, 0, retire_table_bytes(kp.n, L, wide));
+    for (int d = 0; d < kp.n; ++d) {
+        if (kp.t_dnf[d] == 0ull) continue;
+        if (wide) {
+            uint64_t *S = static_cast<uint64_t *>(out) + (size_t)d * row;
+            const uint64_t q = kp.q64_dnf[d];
+            uint64_t s = q;
+            for (int k = 2; k <= L; ++k) {
+                S[k - 2] = s;
+                s = (uint64_t)(((unsigned __int128)s * q) >> 64);
+            }
+        } else {
+            uint32_t *S = static_cast<uint32_t *>(out) + (size_t)d * row;
+            const uint32_t q = (uint32_t)(4294967296ull - kp.t_dnf[d]);
+            uint32_t s = q;
+            for (int k = 2; k <= L; ++k) {
+                S[k - 2] = s;
+                s = retire_next_threshold(s, q);
+            }
+        }
+    }
+}
+
 }  // namespace mcgp

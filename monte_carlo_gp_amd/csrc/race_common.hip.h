@@ -43,6 +43,34 @@ __host__ __device__ inline uint32_t draw_retirement_lap(uint32_t w, uint64_t t, 
     }
     return 0u;
 }
+// The thresholds depend on (t, L) alone, the same for every simulation of a launch: the register kernels read them from a
+// table the host builds per launch (build_retire_table, params_build.h) and find a word's lap by search, not by chain.
+// A driver's row holds S_2 .. S_L and then zeros up to retire_row_entries(L) = 2^rounds entries, the smallest power of
+// two above L - 1: "w < S" is true for a prefix of the row (S is non-increasing, a zero is below no word), and a binary
+// search of `rounds` steps, none of which leaves the row, counts that prefix -- the laps survived.  T = uint32_t for the
+// chain above, uint64_t for the 64-bit chain of the reference-width kernel (S_{k+1} = floor(S_k q / 2^64), KParams::q64_dnf).
+__host__ __device__ inline int retire_search_rounds(int L) { return L > 1 ? 32 - __builtin_clz((unsigned)(L - 1)) : 0; }
+__host__ __device__ inline uint32_t retire_row_entries(int L) { return 1u << retire_search_rounds(L); }
+// rows of the table: the field padded to the four drivers of a Philox block
+__host__ __device__ constexpr uint32_t retire_table_rows(int n) { return ((uint32_t)n + 3u) & ~3u; }
+// one step of the search: `at` = the bytes of the row the word is known to survive, `span` = the bytes of this step
+template <typename T>
+__host__ __device__ inline uint32_t retire_search_step(T w, const T *row, uint32_t at, uint32_t span)
+{
+    const T S = *reinterpret_cast<const T *>(reinterpret_cast<const unsigned char *>(row) + at + (span - (uint32_t)sizeof(T)));
+    return at + (w < S ? span : 0u);
+}
+// what draw_retirement_lap(w, t, L) returns for t != 0, from the driver's row S of the table (a driver with t = 0 has no
+// row to search: the caller skips him, as it skips the chain)
+template <typename T>
+__host__ __device__ inline uint32_t retirement_lap_from_table(T w, const T *S, int L)
+{
+    uint32_t at = 0u;
+    for (uint32_t span = retire_row_entries(L) * (uint32_t)sizeof(T) >> 1; span >= (uint32_t)sizeof(T); span >>= 1)
+        at = retire_search_step(w, S, at, span);
+    const uint32_t lap = 2u + at / (uint32_t)sizeof(T);
+    return lap <= (uint32_t)L ? lap : 0u;
+}
 // A race resumed after lap k (resume.hip.h) keeps a running car's draw above when it says lap k + 1 .. L or "not in this
 // race".  A draw of lap 2 .. k contradicts a car observed running after lap k; its lap then comes from a second word w'
 // (counter {sim, 0, RETIRE | (8 + (d >> 2))}, word d & 3) through the same chain shifted to start at lap k + 1:
@@ -78,6 +106,19 @@ struct KParams {
     // retirement chain of laps >= 2 in 64 bits: q = 2^64 - ceil(p 2^64) (0 for p >= 1; unused for p <= 0: t_dnf = 0)
     uint64_t q64_dnf[kMaxCars];
 };
+// The retirement table of a single-problem launch of the register kernels sits behind its parameter block, in the same
+// allocation and the same upload: [retire_table_rows(n)][retire_row_entries(total_laps)] thresholds, u32 or (wide) u64.
+constexpr size_t kRetireTabOffset = (sizeof(KParams) + 255) / 256 * 256;
+constexpr int kMaxLaps = 1000;                 // MCGP_MAX_LAPS (include/mcgp.h)
+constexpr size_t kRetireTabMaxBytes = (size_t)kMaxCars * 1024 * 8;
+__host__ __device__ inline size_t retire_table_bytes(int n, int L, bool wide)
+{
+    return (size_t)retire_table_rows(n) * retire_row_entries(L) * (wide ? 8u : 4u);
+}
+__host__ __device__ inline const void *retire_table_behind(const KParams *P)
+{
+    return reinterpret_cast<const unsigned char *>(P) + kRetireTabOffset;
+}
 
 // LDS bytes: block-shared tables, then per-thread rows.
 constexpr size_t kSharedTableBytes =

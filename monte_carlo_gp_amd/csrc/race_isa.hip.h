@@ -507,6 +507,15 @@ __device__ __forceinline__ void pin_scalar(uint32_t &x) { asm volatile("" : "+s"
 // a wave-uniform pointer the optimiser cannot see through: loads through it stay where they are written
 template <typename T>
 __device__ __forceinline__ void pin_ptr(const T *&p) { asm volatile("" : "+s"(p)); }
+// A load from device memory at `base` (wave-uniform) + `off` bytes (per lane), said to be global: a pointer that went
+// through pin_ptr has lost its address space, and a flat load through it pays 64-bit vector address arithmetic where
+// the global one takes the base in scalar registers and the offset as it is.
+#define MCGP_GLOBAL __attribute__((address_space(1)))
+template <typename T>
+__device__ __forceinline__ T global_ld(const void *base, uint32_t off)
+{
+    return *(const MCGP_GLOBAL T *)((const MCGP_GLOBAL unsigned char *)base + off);
+}
 
 // address of the dynamic LDS block as the hardware sees it
 __device__ __forceinline__ uint32_t lds_base_of(const void *p)

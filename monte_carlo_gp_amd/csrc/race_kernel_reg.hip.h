@@ -787,6 +787,29 @@ __device__ __attribute__((noinline)) uint32_t wide_pass_exact_fn(PkWords<N> fiel
     return wide_pass_exact_body<N, G>(field.v, od31, lap, pass, c0l, c1l, uniform_u32(k0l_), uniform_u32(k1l_), tid);
 }
 
+// The laps survived by the four retirement words of one Philox block (retirement_lap_from_table, race_common.hip.h, four
+// drivers abreast): `tab` + `first_row` = the row of the first of the four in the launch's table, rows of `row_bytes`.
+// A round loads the four thresholds (row base and step are wave-uniform: the lane's position is the only vector part of
+// the address) and then moves the four positions, so the four loads are in flight together; the trip count is wave-uniform.
+template <typename T>
+__device__ __forceinline__ void retire_search4(const T (&w)[4], const void *__restrict__ tab, uint32_t first_row,
+                                               uint32_t row_bytes, uint32_t (&survived)[4])
+{
+    const unsigned char *rows = static_cast<const unsigned char *>(tab) + first_row;
+    uint32_t at[4] = {0u, 0u, 0u, 0u};                          // bytes of the row the word survives
+#pragma unroll 1
+    for (uint32_t span = row_bytes >> 1; span >= (uint32_t)sizeof(T); span >>= 1) {
+        T S[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            S[j] = global_ld<T>(rows + ((uint32_t)j * row_bytes + span - (uint32_t)sizeof(T)), at[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) at[j] += w[j] < S[j] ? span : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) survived[j] = at[j] / (uint32_t)sizeof(T);
+}
+
 // Phase 2: the simulations, one full race per lane.  The unit of work is a WAVE-CHUNK of 64 consecutive simulations,
 // and every wave of the launch claims its next chunk from one ticket counter in device memory (zeroed by the host
 // before the launch) until the chunks run out: a wave that runs faster than its neighbours takes more of them instead
@@ -1107,9 +1130,11 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
         // probability p: the lap of the first success is geometric, independent of everything else in the race.  It is
         // drawn HERE, from one word per driver (draw_retirement_lap, race_common.hip.h), which halves the Philox blocks
         // of the lap step (a block then serves four cars' lap noise instead of two cars' noise + retirement draws).
-        // The survival thresholds S_k are wave-uniform (scalar unit: one s_mul_hi per lap); a lane counts the laps its
-        // word survives.  A lane's retirements go to its column of `retire_ws` (device memory: about one entry per
-        // race, read back only on the lap of a retirement) as keys lap << 5 | driver; the smallest is kept in `next_out`.
+        // The survival thresholds S_k are the same for every simulation of the launch: the host tabulates them
+        // behind the parameter block (build_retire_table, retire_table_behind) and a lane finds the laps its word survives by binary search in its
+        // driver's row (retirement_lap_from_table, race_common.hip.h).  A lane's retirements go to its column of
+        // `retire_ws` (device memory: about one entry per race, read back only on the lap of a retirement) as keys
+        // lap << 5 | driver; the smallest is kept in `next_out`.
         // `next_out` holds the lane's next two retirements, 15-bit keys (lap << 5 | driver, 0x7FFF = none) in bits 0..14
         // and 16..30, bit 31 = "the list in device memory has more": the race loop tests one register per lap and goes to
         // memory only for a lane's third, fifth .. retirement.
@@ -1138,8 +1163,15 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
             pin(tid_w);
             uint32_t *retire_ws = retire_ws_base + ws_first_lane + tid_w;
             uint32_t n_out = 0u, k1 = kNoKey, k2 = kNoKey;
-            // four drivers at a time (the four words of one Philox block): their survival thresholds advance together on
-            // the scalar unit, one loop iteration per lap for the four of them
+            // four drivers at a time (the four words of one Philox block): retire_search4.  The table's address and its
+            // row size are formed here, per chunk, from opaque copies of what the lap loop keeps anyway (P, L): two
+            // scalar instructions, instead of three more scalar registers carried across the whole race.
+            const KParams *Pt = P;
+            pin_ptr(Pt);
+            const void *retire_tab = retire_table_behind(Pt);
+            uint32_t laps_t = (uint32_t)L;
+            pin_scalar(laps_t);
+            const uint32_t row_bytes = retire_row_entries((int)laps_t) * (uint32_t)(WIDE ? 8u : 4u);
 #pragma unroll 1
             for (int d0 = 0; d0 < N; d0 += 4) {
                 uint32_t rw[4];
@@ -1147,15 +1179,14 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 uint32_t survived[4];
                 if constexpr (WIDE) {
                     // the word refined to 53 bits (left-aligned in 64) against 64-bit thresholds S_2 = q,
-                    // S_{k+1} = floor(S_k q / 2^64), q = 2^64 - ceil(p 2^64) (P->q64_dnf; the oracle's philox_retirement_lap)
+                    // S_{k+1} = floor(S_k q / 2^64), q = 2^64 - ceil(p 2^64) (P->q64_dnf; the oracle's philox_retirement_lap):
+                    // from the block's LDS where they fit (reg_load_tables), else from the launch's table
                     uint32_t rx[4];
                     philox4x32_10(c0, c1, 0u, kPurposeRetire | kCompanion | (uint32_t)(d0 >> 2), seed_lo, seed_hi, rx[0], rx[1], rx[2], rx[3]);
-                    uint64_t Q[4], q64[4], S64[4];
+                    uint64_t Q[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         Q[j] = ((uint64_t)rw[j] << 32) | ((uint64_t)(rx[j] >> 11) << 11);
-                        q64[j] = d0 + j < N ? P->q64_dnf[d0 + j] : 0ull;
-                        S64[j] = q64[j];
                         survived[j] = 0u;
                     }
                     if (G::chain_fits(L)) {
@@ -1168,34 +1199,12 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                             a += G::kChainStride;
                         }
                     } else {
-#pragma unroll 1
-                    for (int k = 2; k <= L; ++k) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            survived[j] += Q[j] < S64[j] ? 1u : 0u;
-                            S64[j] = __umul64hi(S64[j], q64[j]);
-                        }
-                    }
+                        retire_search4(Q, retire_tab, (uint32_t)d0 * row_bytes, row_bytes, survived);
                     }
                 } else {
-                uint32_t q[4], S[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint64_t t = d0 + j < N ? P->t_dnf[d0 + j] : 0ull;         // ceil(p 2^32), 0 .. 2^32
-                    // p = 0 (t = 0) never retires: a threshold no word reaches ... q = 2^32 does not fit, so such a
-                    // driver is skipped below; p >= 1 (t = 2^32) has q = 0 and retires on lap 2
-                    q[j] = (uint32_t)(4294967296ull - t);
-                    S[j] = q[j];
-                    survived[j] = 0u;
-                }
-#pragma unroll 1
-                for (int k = 2; k <= L; ++k) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        survived[j] += rw[j] < S[j] ? 1u : 0u;                       // survives lap k
-                        S[j] = retire_next_threshold(S[j], q[j]);
-                    }
-                }
+                    // p = 0 (t = 0) never retires: such a driver's row is all zeros and he is skipped below; p >= 1
+                    // (t = 2^32) has S_2 = 0 and retires on lap 2
+                    retire_search4(rw, retire_tab, (uint32_t)d0 * row_bytes, row_bytes, survived);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -1926,7 +1935,8 @@ race_kernel_reg_wide(const KParams *__restrict__ P, uint64_t n_sims, uint64_t si
 // from where it started) that still has chunks to hand out, reloads the tables and goes on; blocks start spread evenly
 // over the problems.  Nothing waits for a whole group of chunks: the second round of a problem whose chunks do not fill
 // its blocks' waves evenly runs on the few waves that come free first, with the SIMDs nearly to themselves.
-// Per-problem inputs that are not in the parameter block:
+// The problems' parameter blocks lie `param_stride` bytes apart, each with its retirement table behind it
+// (retire_table_behind).  Per-problem inputs that are not in the parameter block:
 struct BatchItem {
     uint64_t sim_offset, seed;
 };
@@ -1949,7 +1959,7 @@ template <int N>
 __global__ void __launch_bounds__(RegGeo<N>::B, reg_min_waves(N))
 race_kernel_reg_batch(const KParams *__restrict__ P, const BatchItem *__restrict__ items, uint32_t n_problems,
                       uint64_t n_sims, unsigned long long *__restrict__ hist, uint32_t n_chunks,
-                      uint32_t *__restrict__ tickets, uint32_t *__restrict__ retire_ws)
+                      uint32_t *__restrict__ tickets, uint32_t *__restrict__ retire_ws, uint32_t param_stride)
 {
     using G = RegGeo<N>;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1982,7 +1992,8 @@ race_kernel_reg_batch(const KParams *__restrict__ P, const BatchItem *__restrict
         if (p >= n_problems) p -= n_problems;
         visited = found + 1u;
         const BatchItem it = items[p];
-        batch_problem<N>(P + p, smem, tickets + p, n_sims, it.sim_offset, it.seed, n_chunks, retire_ws, hist + (size_t)p * N * N);
+        const KParams *Pp = reinterpret_cast<const KParams *>(reinterpret_cast<const unsigned char *>(P) + (size_t)p * param_stride);
+        batch_problem<N>(Pp, smem, tickets + p, n_sims, it.sim_offset, it.seed, n_chunks, retire_ws, hist + (size_t)p * N * N);
         p += 1u;
         if (p >= n_problems) p -= n_problems;
     }

@@ -130,11 +130,14 @@ extern "C" int emu_run(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                        uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist,
                        uint8_t *orders, const uint8_t *fixed_grid, const char **err)
 {
-    static mcgp::KParams kp;
+    // the parameter block with its retirement table behind it, as the library uploads them (retire_table_behind)
+    alignas(16) static unsigned char block[mcgp::kRetireTabOffset + mcgp::kRetireTabMaxBytes];
+    mcgp::KParams &kp = *reinterpret_cast<mcgp::KParams *>(block);
     static const char *none = "";
     *err = none;
     const int rc = mcgp::build_params(cfg, drv, grid_probs, n, &kp, err);
     if (rc != MCGP_OK) return rc;
+    mcgp::build_retire_table(kp, kp.wide != 0, block + mcgp::kRetireTabOffset);
     if (!mcgp::reg_kernel_serves(kp)) { *err = "served by the generic kernel (reg_kernel_serves)"; return -100; }
     threadIdx = {0, 0, 0};
     blockIdx = {0, 0, 0};

@@ -146,6 +146,11 @@ inline void pin(double &) {}
 inline void pin_scalar(uint32_t &) {}
 template <typename T>
 inline void pin_ptr(const T *&) {}
+template <typename T>
+inline T global_ld(const void *base, uint32_t off)
+{
+    return *reinterpret_cast<const T *>(static_cast<const unsigned char *>(base) + off);
+}
 inline float4 lds_ld_float4(uint32_t addr) { return lds_ld<float4>(addr); }
 inline uint32_t lds_base_of(const void *p) { return (uint32_t)((const unsigned char *)p - smem); }
 }  // namespace mcgp
