@@ -35,7 +35,7 @@ extern "C" {
 /* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
  * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too; and
- * mcgp_run_championship_bonus */
+ * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -421,6 +421,63 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
                             const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
                             const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
                             int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint8_t *orders_out);
+
+/* A time penalty: seconds added to one driver's race in a scenario of mcgp_run_penalties. */
+#define MCGP_MAX_SCENARIO_PENALTIES 256
+enum { MCGP_PEN_SERVE_AT_STOP = 0, MCGP_PEN_AT_FLAG = 1, MCGP_PEN_ON_LAP = 2 };
+typedef struct mcgp_time_penalty {
+    int32_t driver;                   /* driver index, 0 .. n - 1 */
+    int32_t kind;                     /* MCGP_PEN_* */
+    int32_t lap;                      /* SERVE_AT_STOP: pending from this lap; ON_LAP: the lap; AT_FLAG: 0 */
+    double seconds;                   /* finite, in (0, 1e6] */
+} mcgp_time_penalty;
+
+/* Time penalties: one race under n_scenarios sets of planned pit stops AND time penalties, with common random numbers.
+ * Scenario s holds plan_count[s] plans (concatenated in `plans`; exactly mcgp_run_strategies' plans, with its checks;
+ * `plans` may be NULL when every count is 0) and penalty_count[s] penalties (concatenated in `penalties`, which may be
+ * NULL when every count is 0).  L = cfg->total_laps; `first` = 2 from the grid and state->lap + 1 from a state, the first
+ * lap that has a pit step.
+ *   - MCGP_PEN_SERVE_AT_STOP (a 5 s or 10 s penalty): pending from lap `lap` in [first, L]; served at the car's first pit
+ *     stop on a lap >= `lap`, the model's rule stop or a planned one.  Served means, where the pit step is:
+ *     t = cum + lap_time; t = t + pit_loss; t = t + seconds, in this order.  A red flag's free tyre change is not a stop
+ *     and serves nothing.  A car still running at the flag with the penalty unserved adds it at the flag; a car that
+ *     retires first never serves it;
+ *   - MCGP_PEN_AT_FLAG (a post-race penalty): `lap` must be 0; added at the flag if the car is running;
+ *   - MCGP_PEN_ON_LAP (a drive-through, a stop-go, any time lost on a known lap; the caller gives the loss): `lap` in
+ *     [first, L]; on that lap t = t + seconds after the car's lap time and after any pit stop of that lap (a served
+ *     penalty included), before the overtakes, only if the car is still running after that lap (a car whose retirement
+ *     lap is that lap gets nothing).  No tyre change; last_lap_time is untouched, as pit_loss leaves it untouched;
+ *   - at the flag, after the last lap and before the classification: every running car adds its unserved SERVE_AT_STOP
+ *     seconds, then its AT_FLAG seconds (at most two binary64 additions to its cumulative time, in that order); then the
+ *     field is sorted by (time, grid slot) again.  Retired cars are untouched and classify as they always do.
+ * Per scenario and driver at most one SERVE_AT_STOP, one AT_FLAG and one ON_LAP per lap (the caller sums penalties of
+ * one kind), and at most MCGP_MAX_SCENARIO_PENALTIES penalties per scenario.
+ * Random numbers: simulation i of every scenario has id sim_offset + i and draws what mcgp_run's (from the grid) or
+ * mcgp_run_from_state's (from a state) simulation i draws; nothing new is drawn, and a pending penalty changes nobody's
+ * behaviour (the model has no driver reaction to it).  A scenario without penalties is bit-identical to the same
+ * scenario of mcgp_run_strategies.
+ *   hist_out    [S][n][n]      [scenario][driver][position - 1]
+ *   delta_out   [S][n][2n - 1] as mcgp_run_strategies': paired position changes against scenario 0; or NULL
+ *   fate_out    [S][n][4]      [scenario][driver][fate of the driver's SERVE_AT_STOP penalty]: 0 = the driver has none in
+ *                              the scenario, 1 = served at a stop, 2 = added at the flag, 3 = retired unserved; every row
+ *                              sums to n_sims; or NULL
+ *   orders_out  [S][n_sims][n] driver index classified p-th, or NULL
+ * hist_out, delta_out and fate_out are ACCUMULATED into, orders_out is written, and all only after every launch has
+ * succeeded: on an error they are left as they were.  Every argument is checked before any device lookup: what
+ * mcgp_run_strategies checks (n_scenarios, plans, the state, grid_probs, deviates other than MCGP_DEVIATES_32, NULLs),
+ * penalty_count NULL or above 256, `penalties` NULL with a non-zero count, and a penalty outside the limits above (kind,
+ * driver, lap for its kind and for a grid or state run, seconds, a duplicate) are MCGP_E_BAD_ARG with a message that
+ * names the scenario, the penalty and the field.  n_sims == 0 succeeds without a device.  The device work goes chunk by
+ * chunk through mcgp_run_strategies' staging budget (one byte per scenario, simulation and driver: position | fate << 5)
+ * that one counting kernel reads; device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets
+ * or devices sums to the same counts.  mcgp_last_kernel_name afterwards is "mcgp::race_penalties_kernel".
+ * Measured on one MI355X (S60, two scenarios x 10^6 simulations, device ms per 10^6): 98.76 without penalties against
+ * 97.76 for mcgp_run_strategies (1 % more, outside its 0.38 ms of noise), 98.6 to 99.0 with one penalised scenario. */
+int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                           const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                           const mcgp_pit_plan *plans, const uint32_t *penalty_count, const mcgp_time_penalty *penalties,
+                           uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                           uint64_t *delta_out, uint64_t *fate_out, uint8_t *orders_out);
 
 /* Race time gaps: the model's binary64 cumulative times, counted on the device as histograms over caller-given edges
  * (seconds): every car's gap to the leader by lap, the lead (winning margin on the last lap) and the gap between named

@@ -81,6 +81,17 @@ class McgpPitPlan(C.Structure):
     ]
 
 
+MAX_SCENARIO_PENALTIES = 256                       # include/mcgp.h: MCGP_MAX_SCENARIO_PENALTIES, MCGP_PEN_*
+PEN_SERVE_AT_STOP, PEN_AT_FLAG, PEN_ON_LAP = range(3)
+PENALTY_KIND = {'serve': PEN_SERVE_AT_STOP, 'flag': PEN_AT_FLAG, 'lap': PEN_ON_LAP}
+PENALTY_FATES = ('none', 'served', 'at_flag', 'retired')   # fate_out's last axis
+
+
+class McgpTimePenalty(C.Structure):
+    """mcgp_time_penalty: seconds added to one driver's race in a scenario of mcgp_run_penalties."""
+    _fields_ = [('driver', C.c_int32), ('kind', C.c_int32), ('lap', C.c_int32), ('seconds', C.c_double)]
+
+
 class McgpConditionAtom(C.Structure):
     """mcgp_condition_atom: holds iff (lo <= value <= hi) != (negate != 0)."""
     _fields_ = [('fact', C.c_int32), ('a', C.c_int32), ('b', C.c_int32), ('lo', C.c_int32), ('hi', C.c_int32),
@@ -262,7 +273,8 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_stream_kernel_ms', 'mcgp_elo_season',
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
-           'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus')
+           'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
+           'mcgp_run_penalties')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -378,6 +390,13 @@ def lib():
                                               C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
                                               C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, u64p, u64p,
                                               C.POINTER(C.c_uint8)]
+        if 'mcgp_run_penalties' not in missing:
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_penalties.restype = C.c_int32
+            L.mcgp_run_penalties.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.POINTER(McgpRaceState),
+                                             C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
+                                             C.POINTER(C.c_uint32), C.POINTER(McgpTimePenalty), C.c_uint64, C.c_uint64,
+                                             C.c_uint64, C.c_int32, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES

@@ -7,6 +7,8 @@
     python -m monte_carlo_gp_amd.cli in-race --race Bahrain --season 2024 --offline --state lap30.json --simulations 1000000
     python -m monte_carlo_gp_amd.cli strategy --race Bahrain --season 2024 --offline --driver VER --plan one=:25/HARD \
         --plan two=SOFT:15/MEDIUM,38/SOFT --window 15-30/HARD --simulations 1000000 --seed 7
+    python -m monte_carlo_gp_amd.cli penalty --race Bahrain --season 2024 --offline --give NOR:5 --give VER:5:flag \
+        --driver NOR --plan box=:30/HARD --simulations 1000000 --seed 7
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -31,6 +33,10 @@ in-race runs the rest of the race from one or more mid-race state files (RaceSta
 strategy compares pit strategies for one driver: `model` (the race model's own stops) first, then each --plan
 NAME=START:LAP/COMP,LAP/COMP (START empty: the model's start) and each lap of a --window A-B/COMP sweep, all with common
 random numbers, from the grid or from a --state file.
+penalty gives time penalties (--give DRIVER:SECONDS[:serve|flag|lap][@LAP]: served at the car's first pit stop from LAP
+on or else added at the flag; added at the flag; or lost on LAP) and compares `none`, `penalised` and, for each --plan of
+--driver, `penalised + NAME`: win and podium odds and expected position, and for each penalised driver the paired change
+against `none` and where its penalty ended up (served in the pits, added at the flag, retired first).
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
 on the data path; results are gathered once).
 """
@@ -422,6 +428,109 @@ def cmd_strategy(args) -> int:
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({'driver': d, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
+    return 0
+
+
+def parse_give(text: str):
+    """--give DRIVER:SECONDS[:serve|flag|lap][@LAP] -> TimePenalty (kind 'serve' unless given; 'lap' needs @LAP, 'flag'
+    takes none)."""
+    from .simulation import TimePenalty
+    body, at, lap = text.partition('@')
+    parts = [x.strip() for x in body.split(':')]
+    if len(parts) not in (2, 3) or not parts[0]:
+        raise ValueError(f'--give {text!r}: expected DRIVER:SECONDS[:serve|flag|lap][@LAP]')
+    try:
+        seconds = float(parts[1])
+    except ValueError:
+        raise ValueError(f'--give {text!r}: SECONDS must be a number, got {parts[1]!r}') from None
+    if not 0 < seconds <= 1e6:
+        raise ValueError(f'--give {text!r}: SECONDS must be in (0, 1e6]')
+    kind = parts[2].lower() if len(parts) == 3 else 'serve'
+    if kind not in ('serve', 'flag', 'lap'):
+        raise ValueError(f"--give {text!r}: the kind is 'serve', 'flag' or 'lap', got {parts[2]!r}")
+    if at and not lap.strip().isdigit():
+        raise ValueError(f'--give {text!r}: @LAP must be a lap number')
+    if kind == 'flag' and at:
+        raise ValueError(f"--give {text!r}: a 'flag' penalty takes no @LAP")
+    if kind == 'lap' and not at:
+        raise ValueError(f"--give {text!r}: a 'lap' penalty needs @LAP")
+    return TimePenalty(parts[0], seconds, kind, int(lap) if at else None)
+
+
+def penalty_scenarios(gives, driver=None, plans=()):
+    """The penalty command's scenarios -> (penalties, strategies): 'none', 'penalised' (every --give), and for each --plan
+    of --driver 'penalised + NAME' (the same penalties with that plan)."""
+    given = [parse_give(text) for text in gives or ()]
+    if not given:
+        raise ValueError('give at least one --give DRIVER:SECONDS[:serve|flag|lap][@LAP]')
+    if plans and not driver:
+        raise ValueError('--plan needs --driver')
+    penalties, strategies = {'none': [], 'penalised': given}, {}
+    for text in plans or ():
+        name, plan = parse_plan(text, driver)
+        name = f'penalised + {name}'
+        if name in penalties:
+            raise ValueError(f'--plan: scenario {name!r} given twice')
+        penalties[name] = list(given)
+        strategies[name] = [plan]
+    return penalties, strategies
+
+
+def cmd_penalty(args) -> int:
+    from .simulation import RaceState
+    fixture = synthetic_fixture()
+    if args.fixture:
+        with open(args.fixture) as f:
+            fixture = json.load(f)
+    elif not args.offline:
+        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+        return 2
+    state = None
+    if args.state:
+        with open(args.state) as f:
+            state = RaceState.from_json(json.load(f))
+    try:
+        penalties, strategies = penalty_scenarios(args.give, args.driver, args.plan)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    print(f"\n{'=' * 60}\nF1 Time Penalties: {args.season} {args.race}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
+          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
+    print('=' * 60 + '\n')
+    try:
+        res = F1Predictor(device=args.device).predict_penalties(args.season, args.race, fixture, penalties, strategies,
+                                                                state=state, n_simulations=args.simulations,
+                                                                seed=args.seed,
+                                                                allow_single_compound=args.allow_single_compound)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    penalised = list(dict.fromkeys(p.driver for p in penalties['penalised']))
+    rows = []
+    for name in res.names:
+        print(f"scenario: {name}")
+        print(f"  {'driver':8} {'win':>7} {'podium':>7} {'E[pos]':>7} {'P(better)':>10} {'P(worse)':>9}  gain +- SE"
+              f"       served  at flag  retired")
+        epos = res.expected_position(name)
+        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
+                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
+                   expected_position=epos, drivers={})
+        for d in penalised:
+            c, f = res.compare(name, d), res.fate_probabilities(name, d)
+            row['drivers'][d] = dict(win=row['win_probabilities'][d], podium=row['podium_probabilities'][d],
+                                     expected_position=epos[d], p_better=c['p_better'], p_same=c['p_same'],
+                                     p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'], fate=f)
+            print(f"  {d[:8]:8} {row['win_probabilities'][d]:7.1%} {row['podium_probabilities'][d]:7.1%} {epos[d]:7.2f} "
+                  f"{c['p_better']:10.1%} {c['p_worse']:9.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}  "
+                  f"{f['served']:7.1%} {f['at_flag']:8.1%} {f['retired']:8.1%}")
+        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
+        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
+        rows.append(row)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump({'penalised': penalised, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
     return 0
 
 
@@ -847,6 +956,25 @@ def main(argv=None) -> int:
     t.add_argument('--device', type=int, default=0)
     t.add_argument('--json', type=str, default=None)
     t.set_defaults(fn=cmd_strategy)
+    t = sub.add_parser('penalty', help='race odds under time penalties, served in the pits or added at the flag')
+    t.add_argument('--season', type=int, default=2025)
+    t.add_argument('--race', type=str, required=True)
+    t.add_argument('--give', type=str, action='append', default=[],
+                   help="DRIVER:SECONDS[:serve|flag|lap][@LAP]: 'serve' (default) is served at the car's first stop from "
+                        "LAP on, else added at the flag; 'flag' is added at the flag; 'lap' is lost on LAP; repeat for more")
+    t.add_argument('--driver', type=str, default=None, help='the driver whose --plan scenarios are compared')
+    t.add_argument('--plan', type=str, action='append', default=[],
+                   help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's: one scenario 'penalised + NAME' each")
+    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
+    t.add_argument('--allow-single-compound', action='store_true',
+                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
+    t.add_argument('--simulations', type=int, default=100000)
+    t.add_argument('--seed', type=int, default=None)
+    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
+    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
+    t.add_argument('--device', type=int, default=0)
+    t.add_argument('--json', type=str, default=None)
+    t.set_defaults(fn=cmd_penalty)
     args = ap.parse_args(argv)
     return args.fn(args)
 

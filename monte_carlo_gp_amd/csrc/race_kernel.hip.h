@@ -327,10 +327,13 @@ struct NoLapObserver {
 // The pit policy of race_kernel, race_resume_kernel and race_trace_kernel: the race model's own rule for every car.
 // run_laps asks a policy once per lap, begin_lap(lap) (wave-uniform), and once per running car and lap, after the
 // car's lap time, decide(d, newc): -1 = the rule decides (_handle_pit_stops, reference :454-492); 0 = no stop and the
-// rule is off; 1 = a stop onto compound `newc`, rule off.  RulePit's constant -1 folds the branch away.
+// rule is off; 1 = a stop onto compound `newc`, rule off.  RulePit's constant -1 folds the branch away.  After the pit
+// step of every running car, after_pit(d, stopped, t) sees the car's new cumulative time and returns what is stored:
+// `t` itself here and in PlanPit, so that the call vanishes; race_penalties_kernel (penalties.hip.h) adds time there.
 struct RulePit {
     __device__ __forceinline__ void begin_lap(int /*lap*/) {}
     __device__ __forceinline__ int decide(uint32_t /*d*/, uint32_t & /*newc*/) const { return -1; }
+    __device__ __forceinline__ double after_pit(uint32_t /*d*/, bool /*stopped*/, double t) const { return t; }
 };
 
 // Laps first_lap .. L of one lane's race, reference :166-228, from the state the rows hold after lap first_lap - 1: `ord`
@@ -338,7 +341,8 @@ struct RulePit {
 // and the reference's drs_disabled_until.  race_kernel runs it from lap 2, race_resume_kernel (resume.hip.h) from k + 1.
 // After update_positions of every lap, obs(s, lap, event) sees the rows and the lap's kEvent* (race_trace_kernel,
 // trace.hip.h, records them; the other kernels pass a NoLapObserver).  `pit` decides the stops (RulePit: the model's
-// rule; race_strategy_kernel, strategy.hip.h, passes planned stops).
+// rule; race_strategy_kernel, strategy.hip.h, passes planned stops; race_penalties_kernel, penalties.hip.h, planned stops
+// and time penalties).
 template <class LapObserver, class PitPolicy = RulePit>
 __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1, uint32_t seed_lo,
                                          uint32_t seed_hi, int first_lap, int drs_disabled_until, LapObserver &obs,
@@ -444,7 +448,9 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
                 // _handle_pit_stops :454-492 (no randomness, no cross-car dependence), or the policy's planned stop
                 uint32_t plan_c = 0u;
                 const int plan = pit.decide(d, plan_c);
+                bool stopped = false;
                 if (plan < 0 ? ((int)age > (int)t_opt[d * kCompStride + comp] && remaining_laps > 5) : plan > 0) {
+                    stopped = true;
                     t = t + pit_loss;
                     uint32_t newc;
                     if (plan > 0) {
@@ -463,6 +469,7 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
                     pk = (pk & ~(7u << kCompShift)) | (comp << kCompShift) | ((1u << comp) << kUsedShift);
                     age = 0u;
                 }
+                t = pit.after_pit(d, stopped, t);
                 s.Cum(d) = t;
                 s.Last(d) = lap_time;
                 s.Pk(d) = (pk & ~kAgeMask) | age;

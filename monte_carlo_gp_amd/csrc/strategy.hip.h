@@ -64,6 +64,7 @@ struct PlanPit {
         newc = (laps[lap].comp[d >> 3] >> (4u * (d & 7u))) & 7u;
         return 1;
     }
+    __device__ __forceinline__ double after_pit(uint32_t /*d*/, bool /*stopped*/, double t) const { return t; }
 };
 
 // start_from_grid's hook for one scenario: a planned driver's starting compound and age.

@@ -9,6 +9,7 @@ Mirrors the reference's interface for the hot path (reference src/simulation.py)
     RaceSimulator.run_matchups(...)              (not in the reference) head-to-head and podium counts of one race
     RaceSimulator.run_from_state(...)            (not in the reference) the rest of a race from a mid-race RaceState
     RaceSimulator.run_strategies(...)            (not in the reference) one race under planned pit stops (PitPlan)
+    RaceSimulator.run_penalties(...)             (not in the reference) ... and under time penalties (TimePenalty)
 
 The per-lap loop itself runs in hand-written HIP (csrc/race_kernel_reg.hip.h) behind
 the C ABI of include/mcgp.h; this module only resolves the reference's dict
@@ -603,6 +604,117 @@ class RaceSimulator:
         total = lambda k: np.sum([p[k] for p, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
         res = StrategyResult(names=names, drivers=drivers, n_simulations=n_simulations, hist=total(0), delta=total(1),
                              orders=np.concatenate([p[2] for p, _, _ in parts], axis=1) if return_orders else None)
+        self.last_histogram = res.hist
+        self.last_drivers = drivers
+        return res
+
+    def run_penalties(
+        self,
+        n_simulations: int,
+        penalties: dict,
+        strategies: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        grid_probs: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        return_orders: bool = False,
+        allow_single_compound: bool = False,
+    ) -> 'PenaltyResult':
+        """Time penalties (include/mcgp.h: mcgp_run_penalties): the race under each scenario of `penalties`, {name:
+        [TimePenalty, ...]}, and `strategies`, {name: [PitPlan, ...]} or None; a scenario holds the penalties and the
+        plans given under its name, and the scenario names are the union of the two dicts in the order given (penalties
+        first; at most 64; the first is the one `compare` measures against).  Per scenario and driver at most one
+        penalty of kind 'serve', one of kind 'flag' and one of kind 'lap' per lap: two of one kind raise ValueError (sum
+        them).  Everything else -- the remaining arguments, the plans' checks, the simulation ids and draws, the seed
+        rules and the device sharding -- is run_strategies': a scenario without penalties gives exactly its counts.
+        last_histogram: [S, n, n]."""
+        if (grid_probs is None) == (state is None):
+            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
+        strategies = strategies or {}
+        names = [str(k) for k in penalties.keys()] + [str(k) for k in strategies.keys() if str(k) not in
+                                                       {str(j) for j in penalties.keys()}]
+        pens_of = {str(k): list(v) for k, v in penalties.items()}
+        plans_of = {str(k): list(v) for k, v in strategies.items()}
+        if not 1 <= len(names) <= N.MAX_SCENARIOS:
+            raise ValueError(f'penalties / strategies: 1 to {N.MAX_SCENARIOS} scenarios, got {len(names)}')
+        if drivers is None:
+            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
+        drivers = [str(d) for d in drivers]
+        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
+            raise ValueError('drivers must be the keys of grid_probs')
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        n, L = prob.n, int(self.config.total_laps)
+        arrays = state.arrays(drivers, L) if state is not None else None
+        index = {d: i for i, d in enumerate(drivers)}
+        counts, c_plans, pen_counts, c_pens = [], [], [], []
+        for name in names:
+            plans = plans_of.get(name, [])
+            for plan in plans:
+                if str(plan.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {plan.driver!r} is not one of the drivers')
+                if not allow_single_compound and track_condition == 'dry':
+                    used = None
+                    if arrays is not None:
+                        used = {c for j, c in enumerate(N.COMPOUNDS)
+                                if (int(arrays['used_compounds'][index[str(plan.driver)]]) >> j) & 1}
+                    check_two_compounds(plan, used, name)
+                c_plans.append(plan.c_struct(index, from_state=state is not None))
+            counts.append(len(plans))
+            pens = pens_of.get(name, [])
+            seen = set()
+            for pen in pens:
+                if str(pen.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {pen.driver!r} is not one of the drivers')
+                c = pen.c_struct(index, 2 if state is None else int(state.lap) + 1)
+                key = (c.driver, c.kind, c.lap if c.kind == N.PEN_ON_LAP else 0)
+                if key in seen:
+                    raise ValueError(f'scenario {name!r}: {pen.driver} has two penalties of kind {pen.kind!r}'
+                                     + (f' on lap {c.lap}' if c.kind == N.PEN_ON_LAP else '') + '; sum them into one')
+                seen.add(key)
+                c_pens.append(c)
+            if len(pens) > N.MAX_SCENARIO_PENALTIES:
+                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_PENALTIES} penalties, got {len(pens)}')
+            pen_counts.append(len(pens))
+        S = len(names)
+        plan_arr = (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans)
+        count_arr = (C.c_uint32 * S)(*counts)
+        pen_arr = (N.McgpTimePenalty * max(len(c_pens), 1))(*c_pens)
+        pen_count_arr = (C.c_uint32 * S)(*pen_counts)
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
+        c_state = state.c_struct(arrays) if state is not None else None
+        n_simulations = int(n_simulations)
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            h = np.zeros((S, n, n), np.uint64)
+            dl = np.zeros((S, n, 2 * n - 1), np.uint64)
+            ft = np.zeros((S, n, 4), np.uint64)
+            o = np.zeros((S, count, n), np.uint8) if return_orders else None
+            rc = lib.mcgp_run_penalties(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
+                                        C.byref(c_state) if c_state is not None else None, n, S, count_arr, plan_arr,
+                                        pen_count_arr, pen_arr, int(count), int(sim_offset) + int(offset), seed64, device,
+                                        u64(h), u64(dl), u64(ft),
+                                        o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
+            return (h, dl, o, ft), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        if n_simulations <= 0:
+            parts = [((np.zeros((S, n, n), np.uint64), np.zeros((S, n, 2 * n - 1), np.uint64),
+                       np.zeros((S, 0, n), np.uint8) if return_orders else None, np.zeros((S, n, 4), np.uint64)), 0, '')]
+            n_simulations = 0
+        else:
+            parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([p[k] for p, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        res = PenaltyResult(names=names, drivers=drivers, n_simulations=n_simulations, hist=total(0), delta=total(1),
+                            orders=np.concatenate([p[2] for p, _, _ in parts], axis=1) if return_orders else None,
+                            fate=total(3))
         self.last_histogram = res.hist
         self.last_drivers = drivers
         return res
@@ -2109,3 +2221,46 @@ class StrategyResult:
             raise ValueError(f"by must be 'expected_points', 'expected_position', 'win' or 'podium', got {by!r}")
         self._d(driver)
         return max(self.names, key=key)
+
+
+# ---------------------------------------------------------------------------------------------- time penalties
+@dataclass
+class TimePenalty:
+    """One time penalty in a scenario of RaceSimulator.run_penalties: `seconds` (in (0, 1e6]) added to `driver`'s race.
+    kind 'serve': a 5 s / 10 s penalty pending from lap `lap` (None: the first lap that has a pit step), served at the
+    car's first pit stop from that lap on, else added at the flag; 'flag': a post-race penalty, added at the flag (`lap`
+    must be None); 'lap': time lost on lap `lap` (a drive-through, a stop-go: give the loss), after any pit stop of
+    that lap.  A car that retires first takes nothing."""
+    driver: str
+    seconds: float
+    kind: str = 'serve'
+    lap: int | None = None
+
+    def c_struct(self, index, first_lap=2) -> N.McgpTimePenalty:
+        """mcgp_time_penalty with the driver index from `index`; ValueError on an unknown kind or a lap that does not
+        go with it (the library checks the ranges)."""
+        if self.kind not in N.PENALTY_KIND:
+            raise ValueError(f"{self.driver}: kind must be 'serve', 'flag' or 'lap', got {self.kind!r}")
+        if self.kind == 'flag' and self.lap is not None:
+            raise ValueError(f"{self.driver}: a 'flag' penalty has no lap")
+        if self.kind == 'lap' and self.lap is None:
+            raise ValueError(f"{self.driver}: a 'lap' penalty needs its lap")
+        p = N.McgpTimePenalty()
+        p.driver = int(index[str(self.driver)])
+        p.kind = N.PENALTY_KIND[self.kind]
+        p.lap = 0 if self.kind == 'flag' else int(first_lap) if self.lap is None else int(self.lap)
+        p.seconds = float(self.seconds)
+        return p
+
+
+@dataclass
+class PenaltyResult(StrategyResult):
+    """What RaceSimulator.run_penalties returns: StrategyResult's counts and helpers, and
+      fate    [S][n][4]   [scenario][driver][fate of the driver's 'serve' penalty]: 0 = it has none in the scenario,
+                          1 = served at a stop, 2 = added at the flag, 3 = retired unserved; every row sums to N"""
+    fate: np.ndarray | None = None
+
+    def fate_probabilities(self, name, driver) -> dict:
+        """{'none' | 'served' | 'at_flag' | 'retired': probability} of `driver`'s 'serve' penalty in scenario `name`."""
+        row = np.asarray(self.fate[self._s(name), self._d(driver)], np.float64) / max(self.n_simulations, 1)
+        return {k: float(v) for k, v in zip(N.PENALTY_FATES, row)}

@@ -1,0 +1,252 @@
+"""Independent Python restatement of one race with planned pit stops and time penalties (include/mcgp.h:
+mcgp_run_penalties), for the tests of RaceSimulator.run_penalties.  It is built on strategy_ref's pieces -- the CPU
+oracle's Philox (oracle_py.philox) and inverse-normal (orc_normal_from_u32), resume_ref's grids, states and retirement
+chains, strategy_ref's Model and _Race (start, sort, update_positions, classify) -- and restates the lap loop with the
+three additions of the header in their stated order: at a stop t = cum + lap_time, t = t + pit_loss, t = t + seconds of
+a pending SERVE_AT_STOP penalty; then t = t + seconds of the lap's ON_LAP addition; and at the flag, for every running
+car, the unserved SERVE_AT_STOP seconds and then the AT_FLAG seconds, followed by a sort.  Without penalties it must give
+strategy_ref's finishing orders (tests/test_penalties_host.py checks that).
+
+plans: as strategy_ref takes them.  penalties: [(driver index, kind, lap, seconds)], kind SERVE / FLAG / LAP."""
+import ctypes as C
+
+import numpy as np
+
+import oracle_py as O
+import resume_ref as RR
+import strategy_ref as SR
+
+SERVE, FLAG, LAP = 0, 1, 2                                          # MCGP_PEN_*
+FATE_NONE, FATE_SERVED, FATE_FLAG, FATE_RETIRED = 0, 1, 2, 3        # fate_out's columns
+PURPOSE_EVENT, PURPOSE_CAR, PURPOSE_OVT = SR.PURPOSE_EVENT, SR.PURPOSE_CAR, SR.PURPOSE_OVT
+
+
+class _Race(SR._Race):
+    """strategy_ref's race with a `served` set and the lap loop restated with the additions."""
+
+    def laps(self, first_lap, dd, plans, penalties=()):
+        M = self.M
+        stops = {d: dict(p[2]) for d, p in plans.items()}
+        self.serve = {d: (lap, sec) for d, kind, lap, sec in penalties if kind == SERVE}
+        self.flag = {d: sec for d, kind, lap, sec in penalties if kind == FLAG}
+        on_lap = {(d, lap): sec for d, kind, lap, sec in penalties if kind == LAP}
+        self.served = set()
+        for lap in range(first_lap, M.L + 1):
+            remaining = M.L - lap
+            e = self.draw(lap, PURPOSE_EVENT)
+            red = e[0] < M.t_red
+            sc = not red and e[1] < M.t_sc
+            vsc = not red and not sc and e[2] < M.t_vsc
+            if red or sc or vsc:
+                dec_age = sc or (vsc and e[3] < M.t_vsc_tire)
+                newc = SR._stint(M.track, remaining)
+                k, leader, prev_nt, tie = 0, 0.0, -1.0, False
+                for d in self.ord:
+                    if self.dnf[d]:
+                        continue
+                    t = self.cum[d]
+                    if k == 0:
+                        leader = t
+                    nt = leader + k * 0.1 if red else leader + k * 0.5 if sc else leader + (t - leader) * 0.8
+                    tie |= nt == prev_nt
+                    prev_nt = nt
+                    self.dirty[d] = 0 < nt - leader < M.dirty_thr
+                    if red:                                 # the free tyre change: not a stop, serves nothing
+                        self.age[d], self.comp[d] = 0, newc
+                        self.used[d] |= 1 << newc
+                    elif dec_age:
+                        self.age[d] = max(self.age[d] - 1, 0)
+                    self.cum[d] = nt
+                    k += 1
+                dd = lap + (1 if vsc else 2)
+                if tie:
+                    self.sort()
+            fuel = 110.0 - 1.5 * (lap - 1)
+            if not fuel > 0:
+                fuel = 0.0
+            fuel_effect = (110.0 - fuel) * 0.03
+            carry = 0.0
+            for i, d in enumerate(list(self.ord)):
+                if self.dnf[d]:
+                    continue
+                ahead_last, carry = carry, self.last[d]
+                if self.out[d] == lap:                      # retires on this lap: no stop, no addition
+                    self.dnf[d] = lap
+                    continue
+                w = self.draw(lap, PURPOSE_CAR | (i >> 2))[i & 3]
+                comp, age = self.comp[d], self.age[d]
+                tire = age * (M.cdeg[comp] * M.factor[d])
+                drs_gain = M.drs_delta if self.drs[d] else 0.0
+                noise = 0.0 + M.var[d] * SR._normal(w)
+                clean = M.base[d] + tire - fuel_effect + M.cdelta[comp] - drs_gain + noise
+                lap_time = clean
+                if self.dirty[d] and ahead_last > 0:
+                    dirty_time = clean + M.dirty_pen
+                    lap_time = ahead_last if ahead_last > dirty_time else dirty_time
+                t = self.cum[d] + lap_time
+                age += 1
+                if d in plans:
+                    stop, newc = lap in stops[d], stops[d].get(lap)
+                else:
+                    stop, newc = age > M.opt[d][comp] and remaining > 5, None
+                    if stop:
+                        newc = SR._stint(M.track, remaining)
+                        used_dry = self.used[d] & 7
+                        if M.track == 0 and bin(used_dry).count('1') == 1 and (used_dry >> newc) & 1:
+                            avail = 7 & ~used_dry
+                            popped = M.pop_sh if avail == 5 else M.pop_mh if avail == 6 else 0
+                            if remaining > 20:
+                                newc = 1 if avail & 2 else popped
+                            else:
+                                newc = 0 if avail & 1 else popped
+                if stop:
+                    t = t + M.pit_loss
+                    comp = newc
+                    self.used[d] |= 1 << comp
+                    age = 0
+                    if d in self.serve and d not in self.served and lap >= self.serve[d][0]:
+                        t = t + self.serve[d][1]            # served in the pits
+                        self.served.add(d)
+                if (d, lap) in on_lap:
+                    t = t + on_lap[d, lap]
+                self.cum[d], self.last[d], self.comp[d], self.age[d] = t, lap_time, comp, age
+            for pas in range(3):
+                self.sort()
+                o = self.ord
+                pace = lambda d: M.base[d] + (self.dnf[d] if self.dnf[d] else self.age[d]) * M.deg[d]
+                cand = []
+                for i in range(1, M.n):
+                    a, b = o[i - 1], o[i]
+                    delta = pace(a) - pace(b)
+                    if self.drs[b]:
+                        delta += M.drs_delta
+                    if not self.dnf[a] and not self.dnf[b] and delta > M.overtake_delta:
+                        cand.append(i)
+                if not cand:
+                    break
+                success, words = False, None
+                for k, i in enumerate(cand):
+                    if k % 4 == 0:
+                        words = self.draw(lap, PURPOSE_OVT | (8 * pas + (k >> 2)))
+                    db, da = o[i], o[i - 1]
+                    delta = pace(da) - pace(db)
+                    if self.drs[db]:
+                        delta += M.drs_delta
+                    prob = delta / 2.0
+                    if not prob < 0.5:
+                        prob = 0.5
+                    if words[k & 3] * (1.0 / 4294967296.0) < prob:
+                        nb = self.cum[da] - 0.1
+                        if not nb > 0.1:
+                            nb = 0.1
+                        self.cum[db], self.cum[da] = nb, nb + 0.3
+                        success = True
+                if not success:
+                    break
+            self.sort()
+            self.update_positions(lap > 2 and lap > dd)
+
+    def at_the_flag(self):
+        """The additions at the flag, then the sort; returns the fate code of every driver."""
+        fate = [FATE_NONE] * self.M.n
+        for d in range(self.M.n):
+            if d in self.serve:
+                fate[d] = FATE_SERVED if d in self.served else FATE_RETIRED if self.dnf[d] else FATE_FLAG
+            if self.dnf[d]:
+                continue
+            t = self.cum[d]
+            if d in self.serve and d not in self.served:
+                t = t + self.serve[d][1]
+            if d in self.flag:
+                t = t + self.flag[d]
+            self.cum[d] = t
+        self.sort()
+        return fate
+
+
+def orders(case, m, seed, sim_offset=0, plans=None, penalties=(), state=None, grids=None):
+    """(finishing orders [m][n], fates [m][n]) of simulations sim_offset .. sim_offset + m - 1 under `plans` and
+    `penalties`, from the grid (the oracle's sampled grids, or `grids`) or from state = (mcgp_race_state arrays, lap,
+    drs_disabled_until)."""
+    M = SR.Model(case)
+    plans = plans or {}
+    if state is None and grids is None:
+        grids = RR.traced_run(case, m, seed, sim_offset)['grids']
+    out, fates = np.zeros((m, M.n), np.uint8), np.zeros((m, M.n), np.uint8)
+    for i in range(m):
+        r = _Race(M, seed, sim_offset + i)
+        first, dd = r.start_grid(grids[i], plans) if state is None else r.start_state(*state)
+        r.laps(first, dd, plans, penalties)
+        fates[i] = r.at_the_flag()
+        out[i] = r.classify()
+    return out, fates
+
+
+def fate_counts(fates, n):
+    """fate_out [S][n][4] of fates [S][N][n]."""
+    S = fates.shape[0]
+    out = np.zeros((S, n, 4), np.int64)
+    for s in range(S):
+        for d in range(n):
+            out[s, d] = np.bincount(fates[s][:, d], minlength=4)
+    return out
+
+
+def hist_counts(orders, n):
+    """hist_out [S][n][n] of orders [S][N][n]."""
+    return np.stack([RR.counts(orders[s], n) for s in range(orders.shape[0])])
+
+
+# ---------------------------------------------------------------- the C-ABI call for the tests
+def c_penalties(scenarios):
+    """[[(driver, kind, lap, seconds), ...], ...] -> (penalty_count array, mcgp_time_penalty array)."""
+    from monte_carlo_gp_amd import _native as N
+    flat = [N.McgpTimePenalty(driver=int(d), kind=int(k), lap=int(lap), seconds=float(sec))
+            for sc in scenarios for d, k, lap, sec in sc]
+    counts = [len(sc) for sc in scenarios]
+    return (C.c_uint32 * max(len(counts), 1))(*counts), (N.McgpTimePenalty * max(len(flat), 1))(*flat)
+
+
+def run_c(case, plans, penalties, n_sims, seed, sim_offset=0, state=None, orders=True, delta=True, fate=True, prob=None,
+          grid=None, device=0):
+    """mcgp_run_penalties on a case -> (rc, hist [S][n][n], delta [S][n][2n-1], fate [S][n][4], orders [S][N][n] or
+    None).  plans / penalties: one entry per scenario (plans None: none anywhere).  state as strategy_ref.run_c's."""
+    from monte_carlo_gp_amd import _native as N
+    prob = prob or RR.problem(case)
+    n, S = prob.n, len(penalties)
+    plans = plans if plans is not None else [{}] * S
+    assert len(plans) == S
+    counts, c_plans = SR.c_plans(plans)
+    pcounts, c_pens = c_penalties(penalties)
+    g = None
+    if state is None:
+        g = np.ascontiguousarray(grid if grid is not None else O.Problem(case).grid_probs, np.float64)
+    cs = RR.c_state(*state) if state is not None else None
+    h = np.zeros((S, n, n), np.uint64)
+    dl = np.zeros((S, n, 2 * n - 1), np.uint64)
+    ft = np.zeros((S, n, 4), np.uint64)
+    o = np.zeros((S, n_sims, n), np.uint8) if orders else None
+    u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+    rc = N.lib().mcgp_run_penalties(C.byref(prob.cfg), C.byref(prob.drv),
+                                    g.ctypes.data_as(C.POINTER(C.c_double)) if g is not None else None,
+                                    C.byref(cs) if cs is not None else None, n, S, counts, c_plans, pcounts, c_pens,
+                                    int(n_sims), int(sim_offset), int(seed), device, u64(h), u64(dl) if delta else None,
+                                    u64(ft) if fate else None, o.ctypes.data_as(C.POINTER(C.c_uint8)) if orders else None)
+    return rc, h.astype(np.int64), dl.astype(np.int64), ft.astype(np.int64), o
+
+
+def scenarios(first, L, n):
+    """The tests' scenarios for a run whose first lap with a pit step is `first` (2 from the grid, k + 1 from a state
+    after lap k): [(penalties, plans)].  Empty; a post-race penalty; a serve penalty pending from the first lap and
+    from the last; lap additions on the first and the last lap; a serve penalty with a planned stop on lap L, which is
+    served in the pits; and all three kinds on driver n - 1 (mask bit 31 of a 32-car field)."""
+    a, b, c = 0, 1 % n, 2 % n
+    return [
+        ([], {}),
+        ([(a, FLAG, 0, 5.0)], {}),
+        ([(b, SERVE, first, 5.0)], {}),
+        ([(b, SERVE, L, 5.0)], {}),
+        ([(a, LAP, first, 20.0), (c, LAP, L, 20.0)] + ([(b, LAP, first, 7.5)] if n > 2 else []), {}),
+        ([(a, SERVE, first, 10.0)], {a: (-1, 0, [(L, 0)])}),
+        ([(n - 1, SERVE, first, 5.0), (n - 1, FLAG, 0, 5.0), (n - 1, LAP, L, 3.0)], {}),
+    ]
