@@ -208,9 +208,10 @@ def c_penalties(scenarios):
 
 
 def run_c(case, plans, penalties, n_sims, seed, sim_offset=0, state=None, orders=True, delta=True, fate=True, prob=None,
-          grid=None, device=0):
+          grid=None, device=0, fill=0):
     """mcgp_run_penalties on a case -> (rc, hist [S][n][n], delta [S][n][2n-1], fate [S][n][4], orders [S][N][n] or
-    None).  plans / penalties: one entry per scenario (plans None: none anywhere).  state as strategy_ref.run_c's."""
+    None).  plans / penalties: one entry per scenario (plans None: none anywhere).  state as strategy_ref.run_c's.
+    fill: what hist, delta and fate hold before the call (they are accumulated into)."""
     from monte_carlo_gp_amd import _native as N
     prob = prob or RR.problem(case)
     n, S = prob.n, len(penalties)
@@ -222,9 +223,9 @@ def run_c(case, plans, penalties, n_sims, seed, sim_offset=0, state=None, orders
     if state is None:
         g = np.ascontiguousarray(grid if grid is not None else O.Problem(case).grid_probs, np.float64)
     cs = RR.c_state(*state) if state is not None else None
-    h = np.zeros((S, n, n), np.uint64)
-    dl = np.zeros((S, n, 2 * n - 1), np.uint64)
-    ft = np.zeros((S, n, 4), np.uint64)
+    h = np.full((S, n, n), fill, np.uint64)
+    dl = np.full((S, n, 2 * n - 1), fill, np.uint64)
+    ft = np.full((S, n, 4), fill, np.uint64)
     o = np.zeros((S, n_sims, n), np.uint8) if orders else None
     u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
     rc = N.lib().mcgp_run_penalties(C.byref(prob.cfg), C.byref(prob.drv),

@@ -1,11 +1,20 @@
 """race_penalties_kernel<false / true> and penalties_count executed on the host (tools/emu/emu_generic.cpp, through
 penalties_host_build) against the Python restatement (penalties_ref): order for order and fate for fate, from the grid and
 from states after laps 1, L // 2 and L - 1, under the scenarios of penalties_ref.scenarios; the staged bytes stay inside
-the chunk; the counting kernel's bins are the counts of the staged orders and fates whatever its grid."""
+the chunk; the counting kernel's bins are the counts of the staged orders and fates whatever its grid.
+
+Second pass, the comparisons of tests/test_gpu_penalties_fuzz.py that need no device, so that a failure there splits at
+once into "kernel text" and "device build or host side": the generator's scenarios (penalties_cases.scenarios) from the
+grid on the 100 inputs of generic_cases.run_inputs() at 8 simulations, and the ties at the flag by construction."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import pytest
 
+import generic_cases as G
 import oracle_py as O
+import penalties_cases as PC
 import penalties_host_build as PH
 import penalties_ref as PR
 import resume_ref as RR
@@ -95,3 +104,52 @@ def test_counting_kernel_does_not_depend_on_its_grid(grid_x):
     # without the counting kernel nothing is counted, and either output may be left out
     _, stage2, d2, f2 = PH.penalties_raw(case, plans, pens, m, SEED, 11, count=False)
     assert np.array_equal(stage2, stage) and not d2.any() and not f2.any()
+
+
+# ---------------------------------------------------------------- second pass: every input, ties at the flag
+FUZZ_SIMS, FUZZ_OFFSET, TIE_SIMS = 8, 3, 64
+
+
+def test_emulated_kernel_on_every_input_from_the_grid():
+    """Orders and fates are the restatement's (itself checked against both trace references on every input), hist, delta
+    and fate their counts.  At 8 simulations the restatement shows 8 inputs on which nothing bites (NO_BITE),
+    served on 89 inputs, at the flag on 94, retired on 96, a penalty served at a planned stop on its pending lap on 87
+    and missed by a stop one lap early on 83."""
+    inputs = G.run_inputs()
+    O.lib()
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        refs = list(pool.map(lambda a: RR.traced_run(a[1], FUZZ_SIMS, a[2], FUZZ_OFFSET), inputs))
+    done, quiet, seen, on_lap, early = 0, set(), {f: 0 for f in (1, 2, 3)}, 0, 0
+    for (name, case, seed), ref in zip(inputs, refs):
+        n = len(case['grid_probs'])
+        e = PC.grid_expectation(name, case, seed, ref, FUZZ_SIMS, FUZZ_OFFSET)
+        if not e['bites']:
+            quiet.add(name)
+        for f in e['fates_seen']:
+            seen[f] += 1
+        on_lap, early = on_lap + e['on_lap'], early + e['early']
+        got = PH.penalties(case, [pl for _, pl in e['scen']], [p for p, _ in e['scen']], FUZZ_SIMS, seed, FUZZ_OFFSET)
+        bad = np.argwhere((got['orders'] != e['orders']).any(axis=2))
+        assert bad.size == 0, f'{name}: {len(bad)} orders differ, first (scenario, simulation) {bad[0]}'
+        assert np.array_equal(got['fates'], e['fates']), name
+        assert np.array_equal(got['hist'], PR.hist_counts(e['orders'], n)), name
+        assert np.array_equal(got['delta'], SR.delta_counts(e['orders'], n)), name
+        assert np.array_equal(got['fate'], PR.fate_counts(e['fates'], n)), name
+        done += name in G.fuzz_cases()
+    assert done == G.N_FUZZ and len(inputs) == 100
+    assert len(PC.NO_BITE) <= 12 and quiet <= set(PC.NO_BITE), sorted(quiet)
+    assert min(seen.values()) >= 70 and on_lap >= 70 and early >= 70, (seen, on_lap, early)
+
+
+@pytest.mark.parametrize('name, flips, keeps', [('S60', 20, 20), ('X_no_noise', 20, 20)])
+def test_emulated_ties_at_the_flag(name, flips, keeps):
+    """An AT_FLAG penalty of exactly t_b - t_a on the winner a (penalties_cases.flag_tie): the kernel's second
+    sort_by_time orders the tied pair by grid slot, as the restatement and the re-sorted oracle order do."""
+    case = O.load_case(name) if name in G.GOLDEN else G.fuzz_cases()[name]
+    seed = 42 if name in G.GOLDEN else case['seed']
+    ties, n_flips, n_keeps = PC.flag_ties(case, seed, TIE_SIMS, FUZZ_OFFSET)
+    assert len(ties) >= 60 and n_flips >= flips and n_keeps >= keeps, (len(ties), n_flips, n_keeps)
+    prob = KH.generic_problem(case)
+    for i, pens, want in ties:
+        got = PH.penalties(case, [{}], [pens], 1, seed, FUZZ_OFFSET + i, prob=prob)
+        assert np.array_equal(got['orders'][0, 0], want), (name, i)
