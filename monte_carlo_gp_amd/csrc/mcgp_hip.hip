@@ -1126,6 +1126,11 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
         const uint32_t block = (uint32_t)waves * 64u;
         const size_t lds = mcgp::shared_lds_bytes_reg((int)n) + (size_t)block * mcgp::per_thread_lds_bytes_reg((int)n) +
                            mcgp::kBatchLdsExtra;
+        // The batch kernel is built in the default block shape only.  On a device that offers less LDS per block than that
+        // block needs there is no shared launch: its problems run one after the other through launch(), like the solo ones
+        // and into the same histograms, in blocks of kSmallBlockWaves waves -- or fail with launch()'s error when not even
+        // those fit (mcgp_last_kernel_name / mcgp_last_launch_info then describe the last of these launches).
+        const bool shared_launch = n_shared != 0 && lds <= c.lds_per_block;
         int reg_cap = 4 * mcgp::reg_min_waves((int)n);
         int blocks_per_cu = (int)(c.lds_per_block / lds);
         if (blocks_per_cu * waves > reg_cap) blocks_per_cu = reg_cap / waves;
@@ -1135,6 +1140,7 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
         const uint64_t n_tasks = ((uint64_t)n_shared * n_chunks + (uint64_t)waves - 1) / (uint64_t)waves;
         uint64_t grid = (uint64_t)c.cu_count * (uint64_t)blocks_per_cu;
         if (grid > n_tasks) grid = n_tasks;
+        if (!shared_launch) grid = 0;                                           // (no lanes, no retirement lists)
         // workspace: parameter blocks with their retirement tables | items | histograms (the shared launch's problems, then
         // the solo ones) | one ticket counter per problem of the shared launch | its lanes' retirement lists
         Layout ws;
@@ -1146,7 +1152,7 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
         if (r != MCGP_OK) return r;
         unsigned long long *d_hist = c.work.at<unsigned long long>(o_hist);
         HIP_TRY(hipMemsetAsync(d_hist, 0, o_retire - o_hist, nullptr));         // the histograms and ticket counters
-        if (n_shared) {
+        if (shared_launch) {
             const BatchKernelFn kernel = rk->batch;
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)c.lds_per_block));
@@ -1158,6 +1164,12 @@ int32_t mcgp_run_batch(uint32_t n_problems, const mcgp_config *cfgs, const mcgp_
                                c.work.at<uint32_t>(o_ticket), c.work.at<uint32_t>(o_retire), (uint32_t)param_stride);
             HIP_TRY(hipGetLastError());
             note_launch(c, (uint32_t)grid, block, (uint32_t)lds, "mcgp::race_kernel_reg_batch<%u>", n);
+        } else {
+            for (uint32_t j = 0; j < n_shared; ++j) {
+                r = launch(c, kps[j], n_sims, items[j].sim_offset, items[j].seed, nullptr, d_hist + (size_t)j * cells, nullptr,
+                           nullptr);
+                if (r != MCGP_OK) return r;
+            }
         }
         // the problems that run by themselves: exactly mcgp_run's path, one after the other (null stream)
         for (size_t j = 0; j < solo_index.size(); ++j) {

@@ -255,3 +255,50 @@ def test_generated_sort_networks_sort_every_zero_one_input():
         assert built == net and built_layers == layers
     # the checker itself: a network with one comparator missing is caught
     assert not G.sorts_all_zero_one_inputs(10, [(a, b) for a, b, _ in found[10]][:-1])
+
+
+def _batch(k=3, fill=0):
+    from batch_cases import RawBatch, field
+    cases = [field(4, 5, shift=i) for i in range(3)]
+    return RawBatch([(cases[i % 3], 10 + i, 64 * i, 32) for i in range(k)], fill=fill)
+
+
+def test_batch_call_rejects_bad_arguments_before_any_device_lookup():
+    """mcgp_run_batch: every argument check comes before the device is looked up (on a machine without a device each of
+    these would otherwise be MCGP_E_NO_DEVICE), names what is wrong and leaves hist_out as it was."""
+    L = N.lib()
+    SENTINEL = 0xDEADBEEF
+    b = _batch(fill=SENTINEL)
+
+    def rejected(word, n_sims=5, **replace):
+        assert b.call(n_sims, **replace) == -1, replace
+        assert word in L.mcgp_last_error(), (replace, L.mcgp_last_error())
+        assert (b.hist == SENTINEL).all(), replace
+
+    rejected(b'n_problems', n_problems=0)
+    rejected(b'n_problems', n_problems=4097)
+    big = _batch(4097, fill=SENTINEL)                   # (arrays that long, should the check ever move)
+    assert big.call(5) == -1 and b'n_problems' in L.mcgp_last_error() and (big.hist == SENTINEL).all()
+    rejected(b'n_sims', n_sims=0xFFFFFE00)
+    for name in ('cfgs', 'drvs', 'grids', 'seeds', 'hist_ptr'):
+        rejected(b'NULL', **{name: None})
+    grids = (C.POINTER(C.c_double) * 3)(b.grids[0], None, b.grids[2])
+    rejected(b'grid_probs', grids=grids)
+    # a middle problem that build_params refuses: its error is the call's, nothing is counted
+    cfgs = (N.McgpConfig * 3)(*b.cfgs)
+    cfgs[1].total_laps = 0
+    rejected(b'total_laps', cfgs=cfgs)
+    nan = b.grids_np[1].copy()
+    nan[2, 1] = np.nan
+    grids = (C.POINTER(C.c_double) * 3)(b.grids[0], nan.ctypes.data_as(C.POINTER(C.c_double)), b.grids[2])
+    rejected(b'grid_probs', grids=grids)
+    for n in (0, 33):
+        assert b.call(5, n=n) == -1 and (b.hist == SENTINEL).all()
+    # no simulations: nothing to do, no device needed, nothing written
+    assert b.call(0) == 0 and (b.hist == SENTINEL).all()
+    # sim_offsets may be NULL (zeros): not an argument error
+    if L.mcgp_device_count() == 0:
+        for offsets in (b.offsets, None):
+            rc = b.call(5, offsets=offsets)
+            assert rc == -2 and b'no HIP device' in L.mcgp_last_error(), (rc, L.mcgp_last_error())
+            assert (b.hist == SENTINEL).all()
