@@ -35,7 +35,7 @@ extern "C" {
 /* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
  * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too; and
- * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties */
+ * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties; mcgp_lap_event and mcgp_run_events */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -478,6 +478,59 @@ int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, cons
                            const mcgp_pit_plan *plans, const uint32_t *penalty_count, const mcgp_time_penalty *penalties,
                            uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                            uint64_t *delta_out, uint64_t *fate_out, uint8_t *orders_out);
+
+/* An event override: on laps first_lap..last_lap (inclusive) of a scenario of mcgp_run_events the race-interrupting event
+ * is `kind` instead of what the lap's draw gives. */
+#define MCGP_MAX_SCENARIO_EVENTS 64
+enum { MCGP_EVT_NONE = 0, MCGP_EVT_RED_FLAG = 1, MCGP_EVT_SAFETY_CAR = 2, MCGP_EVT_VSC = 3 };
+typedef struct mcgp_lap_event {
+    int32_t first_lap, last_lap;      /* both in [first, L], first_lap <= last_lap */
+    int32_t kind;                     /* MCGP_EVT_* */
+} mcgp_lap_event;
+
+/* Event scenarios: one race under n_scenarios sets of planned pit stops AND race events set on chosen laps (a safety
+ * car on lap 31; no event for the rest of the race; a red flag in the last ten laps), with common random numbers.
+ * Scenario s holds plan_count[s] plans (concatenated in `plans`; exactly mcgp_run_strategies' plans, with its checks;
+ * `plans` may be NULL when every count is 0) and event_count[s] overrides (concatenated in `events`, which may be NULL
+ * when every count is 0).  L = cfg->total_laps; `first` = 2 from the grid and state->lap + 1 from a state, the first lap
+ * that has an event step.
+ *   - an override covers laps first_lap..last_lap, both in [first, L]; two overrides of one scenario share no lap, and a
+ *     scenario has at most MCGP_MAX_SCENARIO_EVENTS of them;
+ *   - on a covered lap the outcome of the model's short-circuit chain (red flag, else safety car, else VSC, else
+ *     nothing) is REPLACED by `kind`, whatever the lap's event words say: MCGP_EVT_NONE = no event on that lap; any other
+ *     kind = that event's handler runs exactly as if it had been drawn.  Laps without an override are drawn as always;
+ *   - nothing new is drawn and no other draw moves: a forced VSC still decides its tyre-age decrement from word 3 of the
+ *     lap's event block (e3 < t_vsc_tire), a forced event sets drs_disabled_until as a drawn one does, and an event on a
+ *     lap with no running car does what a drawn one does.  So a scenario without overrides is cell for cell the same
+ *     scenario of mcgp_run_strategies, and a scenario whose overrides equal what a simulation drew changes nothing for
+ *     that simulation;
+ *   - an event in this model is ONE lap's instantaneous bunching of the field (the gaps close on that lap, DRS is off
+ *     for the next one or two laps); it has no duration.  A safety-car period of several laps is a range of laps;
+ *   - no driver reacts to a forced event beyond what the model does on a drawn one: pitting under the safety car is
+ *     what the caller's plans express (a planned stop on the forced lap).
+ * Random numbers: simulation i of every scenario has id sim_offset + i and draws what mcgp_run's (from the grid) or
+ * mcgp_run_from_state's (from a state) simulation i draws.
+ *   hist_out    [S][n][n]      [scenario][driver][position - 1]
+ *   delta_out   [S][n][2n - 1] as mcgp_run_strategies': paired position changes against scenario 0; or NULL
+ *   events_out  [S][3][L + 1]  [scenario][red flag, safety car, VSC][number of such laps], over the recorded laps (2..L
+ *                              from the grid, state->lap + 1..L from a state), counted as mcgp_run_trace counts (whether
+ *                              or not a car still runs), forced and drawn alike; every row sums to n_sims; or NULL
+ *   orders_out  [S][n_sims][n] driver index classified p-th, or NULL
+ * hist_out, delta_out and events_out are ACCUMULATED into, orders_out is written, and all only after every launch has
+ * succeeded: on an error they are left as they were.  Every argument is checked before any device lookup: what
+ * mcgp_run_strategies checks (n_scenarios, plans, the state, grid_probs, deviates other than MCGP_DEVIATES_32, NULLs),
+ * event_count NULL or above 64, `events` NULL with a non-zero count, a kind outside the enum, first_lap > last_lap, a lap
+ * outside [first, L] ("(lap 1 has no event)" from the grid, "(after the state's lap)" from a state) and two overrides of
+ * one scenario that share a lap are MCGP_E_BAD_ARG with a message that names the scenario, the override and the field.
+ * n_sims == 0 succeeds without a device.  The device work goes chunk by chunk through mcgp_run_strategies' staging budget
+ * (one byte per scenario, simulation and driver, and one u32 per scenario and simulation) that one counting kernel reads;
+ * device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or devices sums to the same
+ * counts.  mcgp_last_kernel_name afterwards is "mcgp::race_events_kernel". */
+int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                        const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                        const mcgp_pit_plan *plans, const uint32_t *event_count, const mcgp_lap_event *events,
+                        uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                        uint64_t *delta_out, uint64_t *events_out, uint8_t *orders_out);
 
 /* Race time gaps: the model's binary64 cumulative times, counted on the device as histograms over caller-given edges
  * (seconds): every car's gap to the leader by lap, the lead (winning margin on the last lap) and the gap between named

@@ -92,6 +92,17 @@ class McgpTimePenalty(C.Structure):
     _fields_ = [('driver', C.c_int32), ('kind', C.c_int32), ('lap', C.c_int32), ('seconds', C.c_double)]
 
 
+MAX_SCENARIO_EVENTS = 64                           # include/mcgp.h: MCGP_MAX_SCENARIO_EVENTS, MCGP_EVT_*
+EVT_NONE, EVT_RED_FLAG, EVT_SAFETY_CAR, EVT_VSC = range(4)
+EVENT_KIND = {'none': EVT_NONE, 'red': EVT_RED_FLAG, 'sc': EVT_SAFETY_CAR, 'vsc': EVT_VSC}
+EVENT_ROWS = ('red', 'sc', 'vsc')                  # events_out's middle axis
+
+
+class McgpLapEvent(C.Structure):
+    """mcgp_lap_event: the event of laps first_lap..last_lap in a scenario of mcgp_run_events."""
+    _fields_ = [('first_lap', C.c_int32), ('last_lap', C.c_int32), ('kind', C.c_int32)]
+
+
 class McgpConditionAtom(C.Structure):
     """mcgp_condition_atom: holds iff (lo <= value <= hi) != (negate != 0)."""
     _fields_ = [('fact', C.c_int32), ('a', C.c_int32), ('b', C.c_int32), ('lo', C.c_int32), ('hi', C.c_int32),
@@ -274,7 +285,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
            'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
-           'mcgp_run_penalties')
+           'mcgp_run_penalties', 'mcgp_run_events')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -397,6 +408,13 @@ def lib():
                                              C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
                                              C.POINTER(C.c_uint32), C.POINTER(McgpTimePenalty), C.c_uint64, C.c_uint64,
                                              C.c_uint64, C.c_int32, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
+        if 'mcgp_run_events' not in missing:
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_events.restype = C.c_int32
+            L.mcgp_run_events.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.POINTER(McgpRaceState),
+                                          C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
+                                          C.POINTER(C.c_uint32), C.POINTER(McgpLapEvent), C.c_uint64, C.c_uint64,
+                                          C.c_uint64, C.c_int32, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES

@@ -9,6 +9,8 @@
         --plan two=SOFT:15/MEDIUM,38/SOFT --window 15-30/HARD --simulations 1000000 --seed 7
     python -m monte_carlo_gp_amd.cli penalty --race Bahrain --season 2024 --offline --give NOR:5 --give VER:5:flag \
         --driver NOR --plan box=:30/HARD --simulations 1000000 --seed 7
+    python -m monte_carlo_gp_amd.cli events --race Bahrain --season 2024 --offline --state lap30.json --event sc=sc@31 \
+        --driver NOR --plan sc=:31/HARD --event green=none@31-57
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -37,6 +39,10 @@ penalty gives time penalties (--give DRIVER:SECONDS[:serve|flag|lap][@LAP]: serv
 on or else added at the flag; added at the flag; or lost on LAP) and compares `none`, `penalised` and, for each --plan of
 --driver, `penalised + NAME`: win and podium odds and expected position, and for each penalised driver the paired change
 against `none` and where its penalty ended up (served in the pits, added at the flag, retired first).
+events sets the race's events on chosen laps (--event NAME=KIND@LAP[-LAP], KIND sc | vsc | red | none; several per NAME
+make one scenario; a --plan of --driver whose NAME matches joins that scenario) and compares the scenarios with
+`as drawn` (no override, no plan), which comes first unless the first --event or --plan names its own baseline by using
+that name: win and podium odds and their change against the first scenario, and the expected number of event laps.
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
 on the data path; results are gathered once).
 """
@@ -534,6 +540,109 @@ def cmd_penalty(args) -> int:
     return 0
 
 
+EVENT_BASELINE = 'as drawn'
+
+
+def parse_event(text: str):
+    """--event NAME=KIND@LAP[-LAP] -> (NAME, RaceEvent)."""
+    from .simulation import RaceEvent
+    name, sep, rest = text.partition('=')
+    if not sep or not name.strip():
+        raise ValueError(f'--event {text!r}: expected NAME=KIND@LAP[-LAP]')
+    kind, at, laps = rest.partition('@')
+    kind = kind.strip().lower()
+    if kind not in ('sc', 'vsc', 'red', 'none'):
+        raise ValueError(f"--event {text!r}: KIND is 'sc', 'vsc', 'red' or 'none', got {kind!r}")
+    a, dash, b = laps.partition('-')
+    if not at or not a.strip().isdigit() or (dash and not b.strip().isdigit()):
+        raise ValueError(f'--event {text!r}: expected @LAP or @LAP-LAP after the kind')
+    lo, hi = int(a), int(b) if dash else int(a)
+    if hi < lo:
+        raise ValueError(f'--event {text!r}: the range runs backwards')
+    return name.strip(), RaceEvent(kind, lo, hi if dash else None)
+
+
+def event_scenarios(events, driver=None, plans=()):
+    """The events command's scenarios -> (events, strategies): 'as drawn' (no override, no plan) first, unless the user
+    names a scenario 'as drawn' themselves (then theirs, wherever it stands, is moved to the front); then one scenario
+    per NAME, holding every --event of that NAME and the --plan of that NAME."""
+    if not events:
+        raise ValueError('give at least one --event NAME=KIND@LAP[-LAP]')
+    if plans and not driver:
+        raise ValueError('--plan needs --driver')
+    out, strategies = {EVENT_BASELINE: []}, {}
+    for text in events:
+        name, ev = parse_event(text)
+        out.setdefault(name, []).append(ev)
+    for text in plans or ():
+        name, plan = parse_plan(text, driver)
+        if name in strategies:
+            raise ValueError(f'--plan: scenario {name!r} given twice')
+        out.setdefault(name, [])
+        strategies[name] = [plan]
+    return out, strategies
+
+
+def cmd_events(args) -> int:
+    from .simulation import RaceState
+    fixture = synthetic_fixture()
+    if args.fixture:
+        with open(args.fixture) as f:
+            fixture = json.load(f)
+    elif not args.offline:
+        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+        return 2
+    state = None
+    if args.state:
+        with open(args.state) as f:
+            state = RaceState.from_json(json.load(f))
+    try:
+        events, strategies = event_scenarios(args.event, args.driver, args.plan)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    print(f"\n{'=' * 60}\nF1 Event Scenarios: {args.season} {args.race}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
+          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
+    print('=' * 60 + '\n')
+    try:
+        res = F1Predictor(device=args.device).predict_events(args.season, args.race, fixture, events, strategies,
+                                                             state=state, n_simulations=args.simulations, seed=args.seed,
+                                                             allow_single_compound=args.allow_single_compound)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    base = res.names[0]
+    shown = [args.driver] if args.driver else sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
+    rows = []
+    for name in res.names:
+        ee = res.expected_events(name)
+        print(f"scenario: {name}   (laps with: safety car {ee['sc']:.2f}, VSC {ee['vsc']:.2f}, red flag {ee['red']:.2f})")
+        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'P(better)':>10}  gain +- SE")
+        epos = res.expected_position(name)
+        row = dict(scenario=name, expected_events=ee,
+                   win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
+                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
+                   expected_position=epos, drivers={})
+        for d in shown:
+            c = res.compare(name, d)
+            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
+            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
+            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
+                                     p_better=c['p_better'], p_same=c['p_same'], p_worse=c['p_worse'],
+                                     mean_gain=c['mean_gain'], se=c['se'])
+            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {c['p_better']:10.1%}  "
+                  f"{c['mean_gain']:+.3f} +- {c['se']:.3f}")
+        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
+        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
+        rows.append(row)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
+    return 0
+
+
 def load_results(season: int) -> list:
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', f'results_{season}.json')
     with open(path) as f:
@@ -975,6 +1084,25 @@ def main(argv=None) -> int:
     t.add_argument('--device', type=int, default=0)
     t.add_argument('--json', type=str, default=None)
     t.set_defaults(fn=cmd_penalty)
+    t = sub.add_parser('events', help='race odds with a safety car, VSC, red flag or no event on chosen laps')
+    t.add_argument('--season', type=int, default=2025)
+    t.add_argument('--race', type=str, required=True)
+    t.add_argument('--event', type=str, action='append', default=[],
+                   help="NAME=KIND@LAP[-LAP]: in scenario NAME the laps have KIND (sc, vsc, red, none) instead of their "
+                        "draw; repeat for more; several of one NAME make one scenario")
+    t.add_argument('--driver', type=str, default=None, help='the driver of the --plan scenarios, and the one shown')
+    t.add_argument('--plan', type=str, action='append', default=[],
+                   help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's; joins the --event scenario of that NAME")
+    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
+    t.add_argument('--allow-single-compound', action='store_true',
+                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
+    t.add_argument('--simulations', type=int, default=100000)
+    t.add_argument('--seed', type=int, default=None)
+    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
+    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
+    t.add_argument('--device', type=int, default=0)
+    t.add_argument('--json', type=str, default=None)
+    t.set_defaults(fn=cmd_events)
     args = ap.parse_args(argv)
     return args.fn(args)
 

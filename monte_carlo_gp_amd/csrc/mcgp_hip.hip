@@ -23,6 +23,7 @@
 #include "champ_bonus.hip.h"
 #include "plan_pack.h"
 #include "penalty_pack.h"
+#include "event_pack.h"
 #include "champ_pack.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
@@ -496,7 +497,8 @@ uint64_t max_sims_per_launch()
 constexpr uint64_t kOrdersChunk = 1ull << 22;
 
 // Staging budgets of mcgp_run_trace (one byte per lap, driver and simulation) and mcgp_run_strategies and
-// mcgp_run_penalties (one byte per scenario, simulation and driver): device memory does not grow with n_sims.
+// mcgp_run_penalties (one byte per scenario, simulation and driver; mcgp_run_events one u32 per scenario and simulation
+// more): device memory does not grow with n_sims.
 constexpr uint64_t kTraceStageBytes = 512ull << 20;
 constexpr uint64_t kStrategyStageBytes = 256ull << 20;
 // ... and of mcgp_run_gaps: one byte per recorded lap, row (n drivers + 1 lead + n_pairs pairs) and simulation.
@@ -1985,6 +1987,151 @@ int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, cons
         for (size_t row = 0; row < (size_t)S * n; ++row) f[row * 4] = n_sims - (f[row * 4 + 1] + f[row * 4 + 2] + f[row * 4 + 3]);
     }
     counts.add_to({{hist_out, c_hist}, {delta_out, c_delta}, {fate_out, c_fate}});
+    if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
+    return MCGP_OK;
+}
+
+int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                        const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                        const mcgp_pit_plan *plans, const uint32_t *event_count, const mcgp_lap_event *events,
+                        uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                        uint64_t *delta_out, uint64_t *events_out, uint8_t *orders_out)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+    if (!plan_count) return fail(MCGP_E_BAD_ARG, "plan_count is NULL");
+    if (!event_count) return fail(MCGP_E_BAD_ARG, "event_count is NULL");
+    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
+        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]");
+    uint64_t n_plans = 0, n_events = 0;
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        if (plan_count[si] > mcgp::kMaxCars)
+            return fail(MCGP_E_BAD_ARG, "scenario " + std::to_string(si) + ": plan_count must be in [0, 32]");
+        n_plans += plan_count[si];
+    }
+    {
+        const std::string err = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+    }
+    if (n_plans && !plans) return fail(MCGP_E_BAD_ARG, "plans is NULL");
+    if (n_events && !events) return fail(MCGP_E_BAD_ARG, "events is NULL");
+    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
+    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    int rc = build_params(cfg, drv, grid_probs, n, &kp);
+    if (rc == MCGP_OK) rc = check_deviates_32(kp, "events run");
+    if (rc != MCGP_OK) return rc;
+    const int L = cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string err = mcgp::pack_race_state(*state, 0, n, L, &st);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+        st.sim_offset = sim_offset;
+    }
+    const int first_lap = state ? st.lap + 1 : 2;
+    std::vector<mcgp::StrategyScenario> scen;
+    std::vector<mcgp::StopLap> stop_laps;
+    std::vector<uint8_t> event_laps;
+    {
+        std::string err = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen,
+                                               &stop_laps);
+        if (err.empty())
+            err = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, state != nullptr, &event_laps);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+    }
+    if (n_sims == 0) return MCGP_OK;
+    const uint32_t S = n_scenarios;
+    const size_t w = 2 * (size_t)n - 1;
+    const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w, c_ev = (size_t)S * 3 * (L + 1);
+    const size_t cells = c_hist + c_delta + c_ev;
+    Counts counts;
+    std::vector<uint8_t> orders;            // collected on the host, handed over only once everything has run
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        // positions and event counts of a chunk share the strategy call's budget: n + 4 bytes per scenario and simulation
+        const uint64_t chunk = std::min<uint64_t>(stage_chunk_sims(kStrategyStageBytes, (uint64_t)S * (n + 4)), n_sims);
+        const size_t stage_bytes = (size_t)S * chunk * n, ev_bytes = (size_t)S * chunk * sizeof(uint32_t);
+        // workspace: staged positions of a chunk | staged event counts | parameter block | state | scenarios | stop laps |
+        // event laps | hist [S][n][n] | delta [S][n][2n - 1] | events [S][3][L + 1]
+        Layout ws;
+        const size_t o_stage = ws.add(stage_bytes), o_evs = ws.add(ev_bytes), o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st));
+        const size_t o_sc = ws.add(sizeof(mcgp::StrategyScenario) * S), o_sl = ws.add(sizeof(mcgp::StopLap) * stop_laps.size());
+        const size_t o_el = ws.add(event_laps.size());
+        const size_t o_cnt = ws.add(cells * 8);
+        int r = c.work.reserve(ws.bytes);
+        if (r != MCGP_OK) return r;
+        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
+        uint32_t *d_evs = c.work.at<uint32_t>(o_evs);
+        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
+        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
+        const mcgp::StrategyScenario *d_sc = c.work.at<const mcgp::StrategyScenario>(o_sc);
+        const mcgp::StopLap *d_sl = c.work.at<const mcgp::StopLap>(o_sl);
+        const uint8_t *d_el = c.work.at<const uint8_t>(o_el);
+        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
+        unsigned long long *d_delta = d_hist + c_hist, *d_ev = d_delta + c_delta;
+        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_sc), scen.data(), sizeof(mcgp::StrategyScenario) * S, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_sl), stop_laps.data(), sizeof(mcgp::StopLap) * stop_laps.size(),
+                          hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.work.at(o_el), event_laps.data(), event_laps.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        std::vector<uint8_t> pos_back;
+        if (orders_out) {
+            pos_back.resize(stage_bytes);
+            orders.resize((size_t)S * n_sims * n);
+        }
+        const auto kernel = state ? &mcgp::race_events_kernel<true> : &mcgp::race_events_kernel<false>;
+        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
+        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
+        const bool count_delta = delta_out && S > 1;
+        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
+        for (uint64_t done = 0; done < n_sims; done += chunk) {
+            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+            // the generic kernel's block shape; the blocks the device holds at once are shared out over the scenarios
+            r = generic_geometry(c, geo_fn, "events", n, m * S, &grid, &block, &lds);
+            if (r != MCGP_OK) return r;
+            const uint64_t n_batches = (m + block - 1) / block;
+            const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + S - 1) / S);
+            if (done == 0) { grid0 = gx * S; block0 = block; }
+            hipLaunchKernelGGL(kernel, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st, d_sc, d_sl, d_el, m,
+                               sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, d_evs,
+                               (uint32_t)n_batches);
+            HIP_TRY(hipGetLastError());
+            // its counts, before the next chunk overwrites the staging
+            if (count_delta || events_out) {
+                const uint64_t tiles = (m + mcgp::kEventsCountBlock - 1) / mcgp::kEventsCountBlock;
+                const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / S));
+                hipLaunchKernelGGL(mcgp::events_count, dim3((uint32_t)gxc, S), dim3(mcgp::kEventsCountBlock), 0, nullptr,
+                                   d_stage, d_evs, m, n, (uint32_t)L, count_delta ? d_delta : nullptr,
+                                   events_out ? d_ev : nullptr);
+                HIP_TRY(hipGetLastError());
+            }
+            if (orders_out) {
+                HIP_TRY(hipMemcpy(pos_back.data(), d_stage, (size_t)S * m * n, hipMemcpyDeviceToHost));
+                for (uint32_t si = 0; si < S; ++si)
+                    for (uint64_t i = 0; i < m; ++i) {
+                        const uint8_t *pos = pos_back.data() + ((size_t)si * m + i) * n;
+                        uint8_t *ord = orders.data() + ((size_t)si * n_sims + done + i) * n;
+                        for (uint32_t d = 0; d < n; ++d) ord[pos[d]] = (uint8_t)d;
+                    }
+            }
+        }
+        note_launch(c, grid0, block0, lds, "mcgp::race_events_kernel");     // the launch shape of the first (fullest) chunk
+        return counts.download(d_hist, cells);
+    });
+    if (rc != MCGP_OK) return rc;
+    if (delta_out) {
+        // the centre bin (no change) of every (scenario, driver) is what the other bins leave of n_sims
+        unsigned long long *b = counts.v.data() + c_hist;
+        for (size_t row = 0; row < (size_t)S * n; ++row) {
+            unsigned long long rest = 0;
+            for (size_t j = 0; j < w; ++j) rest += j == n - 1 ? 0ull : b[row * w + j];
+            b[row * w + n - 1] = n_sims - rest;
+        }
+    }
+    counts.add_to({{hist_out, c_hist}, {delta_out, c_delta}, {events_out, c_ev}});
     if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
     return MCGP_OK;
 }

@@ -336,17 +336,26 @@ struct RulePit {
     __device__ __forceinline__ double after_pit(uint32_t /*d*/, bool /*stopped*/, double t) const { return t; }
 };
 
+// The event policy of every kernel but race_events_kernel: each lap's event is drawn.  run_laps asks a policy once per
+// lap, at a wave-uniform point before the event step, at(lap): -1 = the short-circuit chain decides, as drawn; a kEvent*
+// = that outcome replaces the chain's, whatever the lap's event words say (ForcedEvents, events.hip.h).  DrawnEvents'
+// constant -1 folds the test away.
+struct DrawnEvents {
+    __device__ __forceinline__ int at(int /*lap*/) const { return -1; }
+};
+
 // Laps first_lap .. L of one lane's race, reference :166-228, from the state the rows hold after lap first_lap - 1: `ord`
 // sorted by (cumulative time, grid slot), the DRS / dirty-air flags of update_positions, the retirement laps in `out`,
 // and the reference's drs_disabled_until.  race_kernel runs it from lap 2, race_resume_kernel (resume.hip.h) from k + 1.
 // After update_positions of every lap, obs(s, lap, event) sees the rows and the lap's kEvent* (race_trace_kernel,
 // trace.hip.h, records them; the other kernels pass a NoLapObserver).  `pit` decides the stops (RulePit: the model's
 // rule; race_strategy_kernel, strategy.hip.h, passes planned stops; race_penalties_kernel, penalties.hip.h, planned stops
-// and time penalties).
-template <class LapObserver, class PitPolicy = RulePit>
+// and time penalties).  `evp` may replace a lap's event (DrawnEvents: never; race_events_kernel, events.hip.h, passes the
+// caller's overrides).
+template <class LapObserver, class PitPolicy = RulePit, class EventPolicy = DrawnEvents>
 __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1, uint32_t seed_lo,
                                          uint32_t seed_hi, int first_lap, int drs_disabled_until, LapObserver &obs,
-                                         PitPolicy pit = PitPolicy())
+                                         PitPolicy pit = PitPolicy(), EventPolicy evp = EventPolicy())
 {
     const KParams *__restrict__ P = e.P;
     const int n = e.n, L = e.L, track = e.track;
@@ -363,9 +372,10 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
         {
             uint32_t e0, e1, e2, e3;
             philox4x32_10(c0, c1, (uint32_t)lap, kPurposeEvent, seed_lo, seed_hi, e0, e1, e2, e3);
-            const bool red = (uint64_t)e0 < P->t_red;
-            const bool sc = !red && (uint64_t)e1 < P->t_sc;
-            const bool vsc = !red && !sc && (uint64_t)e2 < P->t_vsc;
+            const int forced = evp.at(lap);
+            const bool red = forced < 0 ? (uint64_t)e0 < P->t_red : forced == kEventRed;
+            const bool sc = forced < 0 ? !red && (uint64_t)e1 < P->t_sc : forced == kEventSc;
+            const bool vsc = forced < 0 ? !red && !sc && (uint64_t)e2 < P->t_vsc : forced == kEventVsc;
             event = red ? kEventRed : sc ? kEventSc : vsc ? kEventVsc : kEventNone;
             if (red || sc || vsc) {
                 // _handle_red_flag :397-431 / _handle_safety_car :334-376 / _handle_vsc :378-395

@@ -719,6 +719,123 @@ class RaceSimulator:
         self.last_drivers = drivers
         return res
 
+    def run_events(
+        self,
+        n_simulations: int,
+        events: dict,
+        strategies: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        grid_probs: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        return_orders: bool = False,
+        allow_single_compound: bool = False,
+    ) -> 'EventResult':
+        """Event scenarios (include/mcgp.h: mcgp_run_events): the race under each scenario of `events`, {name:
+        [RaceEvent, ...]}, and `strategies`, {name: [PitPlan, ...]} or None; a scenario holds the overrides and the plans
+        given under its name, and the scenario names are the union of the two dicts in the order given (events first; at
+        most 64; the first is the one `compare` measures against).  On the laps a RaceEvent covers, the race has that
+        event ('sc', 'vsc', 'red') or none ('none') instead of what the lap draws; other laps are drawn as always.  An
+        event is one lap's bunching of the field: a safety-car period of several laps is a range, and pitting under it
+        is what the plans say.  Overlapping overrides in one scenario, an unknown kind and a lap outside the laps still
+        to run raise ValueError.  Everything else -- the remaining arguments, the plans' checks, the simulation ids and
+        draws, the seed rules and the device sharding -- is run_strategies': a scenario without overrides gives exactly
+        its counts.  last_histogram: [S, n, n]."""
+        if (grid_probs is None) == (state is None):
+            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
+        strategies = strategies or {}
+        names = [str(k) for k in events.keys()] + [str(k) for k in strategies.keys() if str(k) not in
+                                                    {str(j) for j in events.keys()}]
+        events_of = {str(k): list(v) for k, v in events.items()}
+        plans_of = {str(k): list(v) for k, v in strategies.items()}
+        if not 1 <= len(names) <= N.MAX_SCENARIOS:
+            raise ValueError(f'events / strategies: 1 to {N.MAX_SCENARIOS} scenarios, got {len(names)}')
+        if drivers is None:
+            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
+        drivers = [str(d) for d in drivers]
+        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
+            raise ValueError('drivers must be the keys of grid_probs')
+        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
+        n, L = prob.n, int(self.config.total_laps)
+        arrays = state.arrays(drivers, L) if state is not None else None
+        index = {d: i for i, d in enumerate(drivers)}
+        first = 2 if state is None else int(state.lap) + 1
+        counts, c_plans, ev_counts, c_events = [], [], [], []
+        for name in names:
+            plans = plans_of.get(name, [])
+            for plan in plans:
+                if str(plan.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {plan.driver!r} is not one of the drivers')
+                if not allow_single_compound and track_condition == 'dry':
+                    used = None
+                    if arrays is not None:
+                        used = {c for j, c in enumerate(N.COMPOUNDS)
+                                if (int(arrays['used_compounds'][index[str(plan.driver)]]) >> j) & 1}
+                    check_two_compounds(plan, used, name)
+                c_plans.append(plan.c_struct(index, from_state=state is not None))
+            counts.append(len(plans))
+            evs = events_of.get(name, [])
+            if len(evs) > N.MAX_SCENARIO_EVENTS:
+                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_EVENTS} overrides, got {len(evs)}')
+            covered = {}
+            for ev in evs:
+                try:
+                    c = ev.c_struct(first, L)
+                except ValueError as e:
+                    raise ValueError(f'scenario {name!r}: {e}') from None
+                for lap in range(c.first_lap, c.last_lap + 1):
+                    if lap in covered:
+                        raise ValueError(f'scenario {name!r}: lap {lap} has two overrides ({covered[lap]} and {ev})')
+                    covered[lap] = ev
+                c_events.append(c)
+            ev_counts.append(len(evs))
+        S = len(names)
+        plan_arr = (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans)
+        count_arr = (C.c_uint32 * S)(*counts)
+        ev_arr = (N.McgpLapEvent * max(len(c_events), 1))(*c_events)
+        ev_count_arr = (C.c_uint32 * S)(*ev_counts)
+        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
+        c_state = state.c_struct(arrays) if state is not None else None
+        n_simulations = int(n_simulations)
+        seed64 = self._resolve_seed(seed)
+        lib = N.lib()
+        if not hasattr(lib, 'mcgp_run_events'):
+            raise N.McgpError(-1, 'the loaded library does not export mcgp_run_events')
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def run_shard(device, offset, count):
+            h = np.zeros((S, n, n), np.uint64)
+            dl = np.zeros((S, n, 2 * n - 1), np.uint64)
+            ec = np.zeros((S, 3, L + 1), np.uint64)
+            o = np.zeros((S, count, n), np.uint8) if return_orders else None
+            rc = lib.mcgp_run_events(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
+                                     C.byref(c_state) if c_state is not None else None, n, S, count_arr, plan_arr,
+                                     ev_count_arr, ev_arr, int(count), int(sim_offset) + int(offset), seed64, device,
+                                     u64(h), u64(dl), u64(ec),
+                                     o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
+            return (h, dl, o, ec), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+        if n_simulations <= 0:
+            parts = [((np.zeros((S, n, n), np.uint64), np.zeros((S, n, 2 * n - 1), np.uint64),
+                       np.zeros((S, 0, n), np.uint8) if return_orders else None, np.zeros((S, 3, L + 1), np.uint64)), 0,
+                      '')]
+            n_simulations = 0
+        else:
+            parts = self._run_sharded(run_shard, n_simulations)
+        total = lambda k: np.sum([p[k] for p, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        res = EventResult(names=names, drivers=drivers, n_simulations=n_simulations, hist=total(0), delta=total(1),
+                          orders=np.concatenate([p[2] for p, _, _ in parts], axis=1) if return_orders else None,
+                          events=total(3))
+        self.last_histogram = res.hist
+        self.last_drivers = drivers
+        return res
+
     def run_gaps(
         self,
         n_simulations: int,
@@ -2264,3 +2381,58 @@ class PenaltyResult(StrategyResult):
         """{'none' | 'served' | 'at_flag' | 'retired': probability} of `driver`'s 'serve' penalty in scenario `name`."""
         row = np.asarray(self.fate[self._s(name), self._d(driver)], np.float64) / max(self.n_simulations, 1)
         return {k: float(v) for k, v in zip(N.PENALTY_FATES, row)}
+
+
+# ---------------------------------------------------------------------------------------------- event scenarios
+@dataclass
+class RaceEvent:
+    """One override in a scenario of RaceSimulator.run_events: on laps `lap`..`to_lap` (to_lap None: that one lap) the
+    race has a safety car ('sc'), a VSC ('vsc'), a red flag ('red') or no event ('none'), whatever the lap draws.  An
+    event is one lap's bunching of the field; a period of several laps is a range."""
+    kind: str
+    lap: int
+    to_lap: int | None = None
+
+    def c_struct(self, first_lap=2, total_laps=None) -> N.McgpLapEvent:
+        """mcgp_lap_event; ValueError on an unknown kind, lap > to_lap, or a lap outside [first_lap, total_laps]."""
+        if self.kind not in N.EVENT_KIND:
+            raise ValueError(f"event kind must be 'sc', 'vsc', 'red' or 'none', got {self.kind!r}")
+        a, b = int(self.lap), int(self.lap if self.to_lap is None else self.to_lap)
+        if a > b:
+            raise ValueError(f'{self.kind}@{a}-{b}: lap must not be above to_lap')
+        hi = b if total_laps is None else int(total_laps)
+        if a < int(first_lap) or b > hi:
+            raise ValueError(f'{self.kind}@{a}' + (f'-{b}' if b != a else '') +
+                             f': laps must be in [{int(first_lap)}, {hi}]' +
+                             (' (lap 1 has no event)' if int(first_lap) == 2 else " (after the state's lap)"))
+        e = N.McgpLapEvent()
+        e.first_lap, e.last_lap, e.kind = a, b, N.EVENT_KIND[self.kind]
+        return e
+
+
+@dataclass
+class EventResult(StrategyResult):
+    """What RaceSimulator.run_events returns: StrategyResult's counts and helpers, and
+      events  [S][3][L + 1]   [scenario][red flag, safety car, VSC][number of such laps over the laps run]: the
+                              simulations with that many, forced and drawn alike; every row sums to N"""
+    events: np.ndarray | None = None
+
+    def _k(self, kind):
+        if kind not in N.EVENT_ROWS:
+            raise KeyError(f"kind must be one of {N.EVENT_ROWS}, got {kind!r}")
+        return N.EVENT_ROWS.index(kind)
+
+    def event_count_distribution(self, name) -> dict:
+        """{'red' | 'sc' | 'vsc': probabilities by number of such laps} of scenario `name`."""
+        rows = np.asarray(self.events[self._s(name)], np.float64) / max(self.n_simulations, 1)
+        return {k: rows[i] for i, k in enumerate(N.EVENT_ROWS)}
+
+    def expected_events(self, name) -> dict:
+        """{'red' | 'sc' | 'vsc': mean number of such laps} of scenario `name`."""
+        count = np.arange(self.events.shape[2], dtype=np.float64)
+        return {k: float(p @ count) for k, p in self.event_count_distribution(name).items()}
+
+    def probability_of(self, name, kind, at_least=1) -> float:
+        """P(at least `at_least` laps of `kind`) in scenario `name`."""
+        p = self.event_count_distribution(name)[N.EVENT_ROWS[self._k(kind)]]
+        return float(p[max(int(at_least), 0):].sum())

@@ -4,7 +4,7 @@
 // the stand-in <hip/hip_runtime.h> of this directory and calls the real __global__ functions: race_kernel, race_resume_kernel,
 // race_trace_kernel, race_strategy_kernel<false / true>, race_gaps_kernel<false / true>, race_conditions_kernel<false /
 // true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false / true>, race_fastest_kernel,
-// race_penalties_kernel<false / true>, penalties_count.
+// race_penalties_kernel<false / true>, penalties_count; and events.hip.h: race_events_kernel<false / true>, events_count.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -17,8 +17,8 @@
 // trace_count_laps, trace_count_records and strategy_count_deltas, whose loops are written for their fixed block of 256
 // threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
 // records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
-// operation and strides by its block's size, so it does run here, as blocks of one thread; so does penalties_count.
-// tests/test_generic_host_build.py, tests/test_gaps_host_build.py, tests/test_conditions_host_build.py,
+// operation and strides by its block's size, so it does run here, as blocks of one thread; so do penalties_count and events_count.
+// tests/test_events_host_build.py, tests/test_generic_host_build.py, tests/test_gaps_host_build.py, tests/test_conditions_host_build.py,
 // tests/test_stints_host_build.py, tests/test_moves_host_build.py, tests/test_fastest_host_build.py,
 // tests/test_penalties_host_build.py.
 #include <cmath>
@@ -36,6 +36,7 @@
 #include "../../monte_carlo_gp_amd/csrc/fastest.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/plan_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/penalty_pack.h"
+#include "../../monte_carlo_gp_amd/csrc/event_pack.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
 namespace mcgp {
@@ -353,6 +354,60 @@ int emu_penalties_run(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
             for (uint32_t x = 0; x < grid_x; ++x) {
                 blockIdx = {x, y, 0};
                 mcgp::penalties_count(stage, n_sims, n, delta, fate);
+            }
+    }
+    one_thread_block(1);
+    return MCGP_OK;
+}
+
+// race_events_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every scenario,
+// plans and event overrides packed by plan_pack.h and event_pack.h.  hist [S][n][n] is accumulated into; stage
+// [S][n_sims][n] (classified position of each driver) and ev_stage [S][n_sims] (red | sc << 10 | vsc << 20) are written.
+// delta [S][n][2n - 1] and events_cnt [S][3][L + 1] (either may be NULL) are accumulated into by events_count, run as
+// grid_x x S blocks of one thread (both NULL: not run): the centre bin stays what it was, as on the device.
+int emu_events_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                   uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                   const uint32_t *event_count, const mcgp_lap_event *events, uint64_t n_sims, uint64_t sim_offset,
+                   uint64_t seed, unsigned long long *hist, uint8_t *stage, uint32_t *ev_stage, unsigned long long *delta,
+                   unsigned long long *events_cnt, uint32_t grid_x, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
+        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    const int L = cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+        st.sim_offset = sim_offset;
+    }
+    const int first_lap = state ? st.lap + 1 : 2;
+    std::vector<mcgp::StrategyScenario> scen;
+    std::vector<mcgp::StopLap> stop_laps;
+    std::vector<uint8_t> event_laps;
+    uint64_t n_events = 0;
+    std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen, &stop_laps);
+    if (e.empty()) e = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
+    if (e.empty() && n_events && !events) e = "events is NULL";
+    if (e.empty()) e = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, state != nullptr, &event_laps);
+    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    one_thread_block(n_scenarios);
+    const auto kernel = state ? &mcgp::race_events_kernel<true> : &mcgp::race_events_kernel<false>;
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        blockIdx.y = si;
+        kernel(&kp, &st, scen.data(), stop_laps.data(), event_laps.data(), n_sims, sim_offset, (uint32_t)seed,
+               (uint32_t)(seed >> 32), hist, stage, ev_stage, (uint32_t)n_sims);
+    }
+    if (delta || events_cnt) {
+        gridDim = {grid_x, n_scenarios, 1};
+        for (uint32_t y = 0; y < n_scenarios; ++y)
+            for (uint32_t x = 0; x < grid_x; ++x) {
+                blockIdx = {x, y, 0};
+                mcgp::events_count(stage, ev_stage, n_sims, n, (uint32_t)L, delta, events_cnt);
             }
     }
     one_thread_block(1);
