@@ -376,6 +376,156 @@ __device__ __forceinline__ bool ovt_lane_hit(uint64_t acc)
     return r != 0u;
 }
 
+// ---- lap-step commits under EXEC ----
+// What a car's lap changes (reference :179-223, :450-492), for 1..4 consecutive slots in time-rank order.  Per slot, with
+// the old pk word p, the driver's LAST value `last` (its sign: the car retires on this lap) and `lt` holding the clean
+// lap time at entry:
+//   dirty  (p & DIRTY):                  lt = max(|carry|, lt + pen)       the lap time: clean-air cars keep the clean time
+//   active (!(p & DNF)):                 carry = last                      (after this slot has read it)
+//   run    (active, last >= 0):          cum += lt;  pk += 1 << AGE        (not on a lane that stops)
+//   pit    (run, window, agef >= pitw):  cum += pit_loss;  pk = (p & ~(comp | used | age)) | fit
+//   retire (active, last < 0):           pk = (p & ~age) | retire_word
+// Nothing is computed for every lane and then selected: the compares go into SGPR pairs, the scalar unit -- not the
+// bottleneck -- combines them, and each write is issued in place under EXEC = saved & mask, as in ovt_commit*.  The two
+// additions to the time round in the order the select form had ((cum + lt) + pit_loss), a car that does not run keeps its
+// bits (the select form added +0.0, the identity: no cumulative time is -0.0), and both pit and retirement words are
+// built from the OLD p: a stopping lane is taken out of the age increment rather than masked afterwards.
+// The mask sets alternate between two groups of SGPR pairs (x: even slots, z: odd) so that the compares of slot k + 1
+// are issued before the writes of slot k wait for slot k's scalar results; a group of compares therefore opens by putting
+// EXEC back to the saved mask (the writes before it have left it narrowed: a compare writes 0 for a lane that is off).
+// EXEC is saved once and is back at its entry value at the end; every narrowing is saved & mask, so a lane that is off
+// at entry stays off (v_cmp also writes 0 for such a lane).  Wait states, by producer / consumer pair:
+//   v_cmp (VOP3) writes an SGPR pair -> s_and_b64 / s_xor_b64 reads it: a scalar read of a VALU-written SGPR is
+//     interlocked (the manual's cases are v_readlane / v_writelane lane selects, v_div_fmas and VMEM, none here); no VALU
+//     instruction of the statement reads an SGPR that a VALU instruction wrote: the masks reach the VALU only as EXEC.
+//   s_and_b64 writes EXEC -> VALU: interlocked (see ovt_commit*; no DPP, lane access or EXECZ / VCCZ operand here).
+//   No select remains, and VCC is not touched: there is no v_cmp -> VOP2 select pair to space.
+//   pen, pit_loss and the two field masks come in SGPRs written by the scalar unit long before (lap constants).
+#define MCGP_STEP_TEST(k, g)                                                                                            \
+    "s_mov_b64 exec, %[ex]\n\t"                                                                                         \
+    "v_and_b32 %[t], %[dnf], %[p" #k "]\n\t"                                                                            \
+    "v_cmp_eq_u32 %[a" #g "], 0, %[t]\n\t"                                                                              \
+    "v_cmp_gt_i32 %[d" #g "], 0, %[h" #k "]\n\t"                                                                        \
+    "v_and_b32 %[t], %[dty], %[p" #k "]\n\t"                                                                            \
+    "v_cmp_ge_u32 %[c" #g "], %[g" #k "], %[w" #k "]\n\t"                                                               \
+    "v_cmp_ne_u32 %[y" #g "], 0, %[t]\n\t"
+#define MCGP_STEP_WRITE(k, g)                                                                                           \
+    "s_and_b64 exec, %[ex], %[y" #g "]\n\t"                                                                             \
+    "v_add_f64 %[l" #k "], %[l" #k "], %[pen]\n\t"                                                                      \
+    "v_max_f64 %[l" #k "], |%[cy]|, %[l" #k "]\n\t"                                                                     \
+    "s_and_b64 exec, %[ex], %[a" #g "]\n\t"                                                                             \
+    "v_mov_b64 %[cy], %[s" #k "]\n\t"                                                                                   \
+    "s_and_b64 %[d" #g "], %[a" #g "], %[d" #g "]\n\t"                                                                  \
+    "s_xor_b64 %[a" #g "], %[a" #g "], %[d" #g "]\n\t"                                                                  \
+    "s_and_b64 %[c" #g "], %[c" #g "], %[a" #g "]\n\t"                                                                  \
+    "s_and_b64 %[c" #g "], %[c" #g "], %[win]\n\t"                                                                      \
+    "s_and_b64 exec, %[ex], %[a" #g "]\n\t"                                                                             \
+    "v_add_f64 %[u" #k "], %[u" #k "], %[l" #k "]\n\t"                                                                  \
+    "s_xor_b64 %[a" #g "], %[a" #g "], %[c" #g "]\n\t"                                                                  \
+    "s_and_b64 exec, %[ex], %[c" #g "]\n\t"                                                                             \
+    "v_add_f64 %[u" #k "], %[u" #k "], %[pl]\n\t"                                                                       \
+    "v_and_or_b32 %[p" #k "], %[p" #k "], %[mpit], %[f" #k "]\n\t"                                                      \
+    "s_and_b64 exec, %[ex], %[a" #g "]\n\t"                                                                             \
+    "v_add_u32 %[p" #k "], %[age1], %[p" #k "]\n\t"                                                                     \
+    "s_and_b64 exec, %[ex], %[d" #g "]\n\t"                                                                             \
+    "v_and_or_b32 %[p" #k "], %[p" #k "], %[mage], %[rw]\n\t"
+#define MCGP_STEP_OUT(k) [p##k] "+v"(pk[k]), [u##k] "+v"(cum[k]), [l##k] "+v"(lt[k])
+#define MCGP_STEP_IN(k)                                                                                                 \
+    [h##k] "v"((uint32_t)__double2hiint(s[k].last)), [s##k] "v"(s[k].last), [g##k] "v"(s[k].agef), [w##k] "v"(s[k].pitw),  \
+        [f##k] "v"(s[k].fit)
+#define MCGP_STEP_ENTER "s_mov_b64 %[ex], exec\n\ts_mov_b32 %[mpit], %[kpit]\n\ts_mov_b32 %[mage], %[kret]\n\t"
+#define MCGP_STEP_TEMPS_X [t] "=&v"(t), [ex] "=&s"(ex), [mpit] "=&s"(mpit), [mage] "=&s"(mage), [ax] "=&s"(ax), [dx] "=&s"(dx), [cx] "=&s"(cx), [yx] "=&s"(yx)
+#define MCGP_STEP_TEMPS_Z , [az] "=&s"(az), [dz] "=&s"(dz), [cz] "=&s"(cz), [yz] "=&s"(yz)
+#define MCGP_STEP_COMMON                                                                                                \
+    [rw] "v"(c.retire_word), [win] "s"(c.window), [pl] "s"(c.pit_loss), [pen] "s"(c.pen), [kpit] "n"(KEEP_PIT),           \
+        [kret] "n"(KEEP_RET), [dnf] "n"(DNF), [dty] "n"(DIRTY), [age1] "n"(AGE1)
+// one slot's inputs that are not updated in place
+struct StepSlot {
+    double last;         // the driver's LAST value: the last lap time, negative iff the car retires on this lap
+    uint32_t agef;       // the age field of p, in place
+    uint32_t pitw;       // pit threshold, positioned as the age field
+    uint32_t fit;        // compound and used-set a stop on this lap leaves, positioned as in pk
+};
+// the lap's wave-uniform inputs (SGPRs) and the retirement word (a VGPR: v_and_or_b32 takes one scalar operand)
+struct StepLap {
+    uint32_t retire_word;
+    uint64_t window;     // all ones while the pit window is open, 0 otherwise
+    double pit_loss, pen;
+};
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+__device__ __forceinline__ void step_commit1(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    uint32_t t, mpit, mage;
+    uint64_t ex, ax, dx, cx, yx;
+    asm volatile(MCGP_STEP_ENTER
+                 MCGP_STEP_TEST(0, x)
+                 MCGP_STEP_WRITE(0, x)
+                 "s_mov_b64 exec, %[ex]"
+                 : MCGP_STEP_OUT(0), [cy] "+v"(carry), MCGP_STEP_TEMPS_X
+                 : MCGP_STEP_IN(0), MCGP_STEP_COMMON
+                 : "scc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+__device__ __forceinline__ void step_commit2(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    uint32_t t, mpit, mage;
+    uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
+    asm volatile(MCGP_STEP_ENTER
+                 MCGP_STEP_TEST(0, x)
+                 MCGP_STEP_TEST(1, z)
+                 MCGP_STEP_WRITE(0, x)
+                 MCGP_STEP_WRITE(1, z)
+                 "s_mov_b64 exec, %[ex]"
+                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
+                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_COMMON
+                 : "scc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+__device__ __forceinline__ void step_commit3(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    uint32_t t, mpit, mage;
+    uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
+    asm volatile(MCGP_STEP_ENTER
+                 MCGP_STEP_TEST(0, x)
+                 MCGP_STEP_TEST(1, z)
+                 MCGP_STEP_WRITE(0, x)
+                 MCGP_STEP_TEST(2, x)
+                 MCGP_STEP_WRITE(1, z)
+                 MCGP_STEP_WRITE(2, x)
+                 "s_mov_b64 exec, %[ex]"
+                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), MCGP_STEP_OUT(2), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
+                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_IN(2), MCGP_STEP_COMMON
+                 : "scc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+__device__ __forceinline__ void step_commit4(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    uint32_t t, mpit, mage;
+    uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
+    asm volatile(MCGP_STEP_ENTER
+                 MCGP_STEP_TEST(0, x)
+                 MCGP_STEP_TEST(1, z)
+                 MCGP_STEP_WRITE(0, x)
+                 MCGP_STEP_TEST(2, x)
+                 MCGP_STEP_WRITE(1, z)
+                 MCGP_STEP_TEST(3, z)
+                 MCGP_STEP_WRITE(2, x)
+                 MCGP_STEP_WRITE(3, z)
+                 "s_mov_b64 exec, %[ex]"
+                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), MCGP_STEP_OUT(2), MCGP_STEP_OUT(3), [cy] "+v"(carry),
+                   MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
+                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_IN(2), MCGP_STEP_IN(3), MCGP_STEP_COMMON
+                 : "scc");
+}
+#undef MCGP_STEP_COMMON
+#undef MCGP_STEP_ENTER
+#undef MCGP_STEP_TEMPS_Z
+#undef MCGP_STEP_TEMPS_X
+#undef MCGP_STEP_IN
+#undef MCGP_STEP_OUT
+#undef MCGP_STEP_WRITE
+#undef MCGP_STEP_TEST
+
 // LDS access by ABSOLUTE byte address.  The register kernel declares no static __shared__ data, so its
 // dynamic LDS block starts at address 0 (checked once at kernel entry); addressing it by number instead of
 // through the `extern __shared__` symbol lets the compiler fold every table / row base into the 16-bit

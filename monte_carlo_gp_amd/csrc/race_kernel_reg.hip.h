@@ -122,6 +122,13 @@ __host__ __device__ constexpr int reg_min_waves(int n) { return n <= 6 ? (n == 4
 // 56 -> 60; everywhere else scratch stays or falls).  The small ones run at 4 and more waves per SIMD on 128 VGPRs or
 // fewer, where the chain's fixed registers -- the times are updated in place -- leave the allocator no slack.
 __host__ __device__ constexpr bool reg_commit_by_selects(int n) { return n == 6 || (n >= 8 && n <= 10) || n == 24 || n == 25; }
+// Field sizes whose lap step merges a car's lap by selects instead of committing it under EXEC (reg_simulate, "every
+// running car's lap"; step_commit*, race_isa.hip.h): the ones where the EXEC form costs some instantiation scratch or
+// registers (bytes of scratch per lane, select form -> EXEC form: N = 3 24 -> 36, 4-wave blocks 20 -> 44, batch 100 -> 104;
+// N = 25 batch 8 -> 24; N = 26 reference width 68 -> 76; N = 29 batch 8 -> 16; N = 11 / 12 reference width 167 -> 168
+// VGPRs).  Everywhere else every instantiation keeps or lowers both (N = 20: 28 -> 0 B, batch 108 -> 88, reference width
+// 192 -> 176); occupancy changes nowhere.
+__host__ __device__ constexpr bool reg_step_by_selects(int n) { return n == 3 || n == 11 || n == 12 || n == 25 || n == 26 || n == 29; }
 // Waves per block: the (waves per block, blocks per CU) pair that keeps the most waves resident within the LDS
 // budget and the kernel's waves per SIMD; among equals a multiple of 4 waves per block (a block's waves go round the
 // 4 SIMDs: two blocks of 6 load them 4, 4, 2, 2), then the block nearest to 8 waves (1024-thread blocks make the
@@ -702,6 +709,19 @@ __device__ __forceinline__ uint32_t uniform_u32(uint32_t x)
     return x;                                   // (the host debugging build: one thread at a time)
 #endif
 }
+// A wave-uniform value for an "s" operand of an assembly statement, whatever the compiler makes of the scalar code that
+// computes it: it moves short scalar chains to the vector unit (a parameter read behind a barrier arrives by a vector load,
+// a select between two scalars becomes a v_cndmask) and then hands the statement a vector register without a word.  Pinned
+// in a vector register and read back from the first lane, the value is in an SGPR by construction.
+__device__ __forceinline__ uint32_t scalar_u32(uint32_t x)
+{
+    pin(x);
+    return uniform_u32(x);
+}
+__device__ __forceinline__ double scalar_f64(double x)
+{
+    return __hiloint2double((int)scalar_u32((uint32_t)__double2hiint(x)), (int)scalar_u32((uint32_t)__double2loint(x)));
+}
 // The exact 53-bit decision of one overtake pass of the reference-width build (reg_simulate, overtakes): the path of a draw
 // word that EQUALS the leading word of its threshold, or of a lane with more than eight attempts.  Plain code, four attempts
 // at a time: their words in rows 0..3 of the W plane, the companion words in rows 4..7.  Returns bit i = the attempt at pair i
@@ -1169,7 +1189,9 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
             const KParams *Pt = P;
             pin_ptr(Pt);
             const void *retire_tab = retire_table_behind(Pt);
-            uint32_t laps_t = (uint32_t)L;
+            // (L is read behind the table build's barrier, by a vector load; said to be uniform here, so that the pin holds
+            //  whether or not the compiler keeps the scalar code that uses L on the scalar unit)
+            uint32_t laps_t = uniform_u32((uint32_t)L);
             pin_scalar(laps_t);
             const uint32_t row_bytes = retire_row_entries((int)laps_t) * (uint32_t)(WIDE ? 8u : 4u);
 #pragma unroll 1
@@ -1262,6 +1284,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
             pin_ptr(Pl);
             const double od31 = Pl->overtake_delta_31, dirty_thr = Pl->dirty_thr;
             const double dirty_pen_lap = lap == 2 ? 0.0 : Pl->dirty_pen;         // (no dirty-air constraint in lap 2: see the lap step)
+            [[maybe_unused]] const double pit_loss_lap = Pl->pit_loss;           // (the EXEC form of the lap step adds it as a scalar operand)
             const uint64_t t_red = WIDE ? Pl->t53_red : Pl->t_red, t_sc = WIDE ? Pl->t53_sc : Pl->t_sc,
                            t_vsc = WIDE ? Pl->t53_vsc : Pl->t_vsc, t_vsc_tire = WIDE ? Pl->t53_vsc_tire : Pl->t_vsc_tire;
             // ---- race-interrupting events, :168-176 ----
@@ -1489,10 +1512,12 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
             }
 
             // ---- every running car's lap (:179-223) with its pit stop (:433-494), in time-rank order ----
-            // Written without branches: every slot computes its lap and the results are merged by selects, so the
-            // LDS gathers of kStepBatch slots stay in flight together (nothing can be sunk into a branch) and
-            // the wave does not pay exec-mask bookkeeping per car.  What a retired car "computes" is discarded:
-            // +0.0 on its time, its pk kept, and a LAST value nobody reads (only running cars feed `carry`).
+            // Written without branches, so that the LDS gathers of kStepBatch slots stay in flight together (nothing can be
+            // sunk into a branch).  What a lap changes -- the carry, the car's time, its pk word -- is committed under EXEC
+            // narrowed to the lanes it changes for, one assembly statement per batch (step_commit*, race_isa.hip.h); the field
+            // sizes of reg_step_by_selects() compute every slot's lap for every lane and merge the results by selects
+            // instead.  Either way a retired car keeps its time and its pk, and its LAST value is one nobody reads (only
+            // running cars feed `carry`).
             // The lap-noise draws of places 4j .. 4j+3 are the four words of ONE Philox block, computed here between the
             // gathers and their use (it covers their latency) and consumed from registers.
             {
@@ -1504,6 +1529,14 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 // in a vector register, so that (p & ~age) | retire_word is one v_and_or_b32 (an instruction takes one scalar operand)
                 uint32_t retire_word = k3Dnf | ((uint32_t)lap << k3AgeShift);
                 if constexpr (reg_min_waves(N) <= 3) pin(retire_word);      // (at 4+ waves per SIMD the register it takes is spilled)
+                constexpr bool kStepBySelects = reg_step_by_selects(N);
+                [[maybe_unused]] StepLap step_lap{};
+                if constexpr (!kStepBySelects) {
+                    // (scalar_*: six v_readfirstlane a lap make its scalar operands scalar)
+                    const uint32_t window32 = scalar_u32(pit_window ? ~0u : 0u);
+                    step_lap = StepLap{retire_word, ((uint64_t)window32 << 32) | window32, scalar_f64(pit_loss_lap), scalar_f64(dirty_pen_lap)};
+                }
+                constexpr uint32_t kKeepPit = ~(k3CompMask | k3UsedMask | k3AgeMask), kKeepRet = ~k3AgeMask;    // what of p a stop / a retirement keeps
                 double carry = 0.0;
 #pragma unroll
                 for (int i0 = 0; i0 < N; i0 += kStepBatch) {
@@ -1590,6 +1623,34 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                                 z[j0 + j] = (i0 + j0 + j < N) ? normal_evaluate(w[(j0 + j) >> 2][(j0 + j) & 3], zc[j], zt[j]) : 0.0f;
                         }
                     }
+                    if constexpr (!kStepBySelects) {
+                        // The clean lap time of every slot of the batch, then one statement (step_commit*, race_isa.hip.h)
+                        // that turns it into the lap time where the car runs in dirty air (:207-215: a car flagged dirty has
+                        // a running car ahead whose last lap is a lap time, see the select form below; for a clean-air car
+                        // max(|0|, clean + 0.0) was the clean time itself) and commits the lap -- carry, time, pk word --
+                        // under EXEC narrowed to the lanes each write is for.
+                        static_assert(kStepBatch == 4, "step_commit1..4");
+                        const int K = N - i0 < kStepBatch ? N - i0 : kStepBatch;      // (a constant once the loop is unrolled)
+                        double lt[kStepBatch];
+                        StepSlot ss[kStepBatch];
+#pragma unroll
+                        for (int j = 0; j < kStepBatch; ++j) {
+                            if (j >= K) continue;
+                            const SlotIn &s = in[j];
+                            const uint32_t agef = pk[i0 + j] & k3AgeMask;
+                            const double tire = (double)agef * s.eff;                                   // :319-322 (eff x 2^-16)
+                            const double noise = s.var * (double)z[j];                                  // :330 (see below)
+                            lt[j] = s.base + tire - fuel_effect + s.cdelta - s.drs + noise;             // :332
+                            ss[j] = StepSlot{s.last, agef, s.pitw, s.fit};
+                        }
+                        if constexpr (N >= 4) if (K == 4) step_commit4<k3Dnf, k3Dirty, 1u << k3AgeShift, kKeepPit, kKeepRet>(&cum[i0], &pk[i0], lt, carry, ss, step_lap);
+                        if constexpr (N % 4 == 3) if (K == 3) step_commit3<k3Dnf, k3Dirty, 1u << k3AgeShift, kKeepPit, kKeepRet>(&cum[i0], &pk[i0], lt, carry, ss, step_lap);
+                        if constexpr (N % 4 == 2) if (K == 2) step_commit2<k3Dnf, k3Dirty, 1u << k3AgeShift, kKeepPit, kKeepRet>(&cum[i0], &pk[i0], lt, carry, ss, step_lap);
+                        if constexpr (N % 4 == 1) if (K == 1) step_commit1<k3Dnf, k3Dirty, 1u << k3AgeShift, kKeepPit, kKeepRet>(&cum[i0], &pk[i0], lt, carry, ss, step_lap);
+#pragma unroll
+                        for (int j = 0; j < kStepBatch; ++j)
+                            if (j < K) lds_st<double>(G::oLast + in[j].la, lt[j]);                      // :219
+                    } else {
 #pragma unroll
                     for (int j = 0; j < kStepBatch; ++j) {
                         const int i = i0 + j;
@@ -1642,6 +1703,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                         cum[i] = (cum[i] + lap_add) + pit_add;
                         pin(cum[i]);             // done HERE: not sunk, with its masks and lap time, to where it is used
                         lds_st<double>(G::oLast + s.la, lap_time);                                  // :219
+                    }
                     }
                 }
             }

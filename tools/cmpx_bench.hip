@@ -5,6 +5,10 @@
 //   S  the write-back chain of an overtake pass by selects: v_cmp_lt_u32 vcc; 2 x v_add_f64; 4 x v_cndmask_b32; s_or_b64 (hit lanes)
 //   E  the same under EXEC (race_isa.hip.h ovt_commit*): v_cmpx_lt_u32; 2 x v_add_f64 in place; s_or_b64; s_mov_b64 exec, saved
 //      (S and E as chains of 15 dependent pairs only; "comparator" in the output is then one pair)
+//   LS the lap step's commit of four consecutive slots by selects (the carry, the dirty-air lap time, the time and the pk word: 3
+//      compares, 2 shifts + 4 ands, 8 selects, a two-entry LDS read)
+//   LE the same under EXEC (race_isa.hip.h step_commit4): 4 compares into SGPR pairs, each write in place under saved & mask
+//      ("comparator" in the output is one slot; both include the same clean-time and age-field instructions and loop overhead)
 // each as layers of 8 independent comparators (the sorting network) and as a chain of 15 dependent ones (a bubble pass).
 // The loop bodies are written on fixed registers (v[10:41] = 16 times, v50..v65 = 16 payloads): inline assembly cannot
 // name the halves of a 64-bit operand, which form B needs.
@@ -30,7 +34,9 @@ int main()
                           {"A chain", k_A_chain, 15}, {"A0 chain", k_A0_chain, 15}, {"B chain", k_B_chain, 15}, {"C chain", k_C_chain, 15},
                           {"D chain", k_D_chain, 15},
                           {"S chain (overtake commit: cmp, 2 add, 4 cndmask)", k_S_chain, 15},
-                          {"E chain (overtake commit: cmpx, 2 add in place, restore)", k_E_chain, 15}};
+                          {"E chain (overtake commit: cmpx, 2 add in place, restore)", k_E_chain, 15},
+                          {"LS (lap-step commit of 4 slots by selects; per slot)", k_LS_chain, 4},
+                          {"LE (lap-step commit of 4 slots under EXEC; per slot)", k_LE_chain, 4}};
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;

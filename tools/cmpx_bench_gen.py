@@ -35,11 +35,76 @@ def comparator(form, a, b):
                 's_or_b64 s[28:29], s[28:29], vcc', 's_mov_b64 exec, s[20:21]']
     raise ValueError(form)
 
+# The lap step's commit of one slot (race_kernel_reg.hip.h, "every running car's lap"; race_isa.hip.h step_commit*): slot i has its
+# time in t(i) and its pk word in p(i); LAST in v[100 + 2 i], the clean lap time in v[116 + 2 i] (in: clean, out: lap time), the
+# age field in v(124 + i), the pit word in v(128 + i), the word a stop leaves in v(132 + i); the retirement word in v136, the
+# carry (last lap of the running car ahead) in v[138:139]; pit_loss s[24:25], the dirty-air penalty s[26:27], the pit window
+# s[30:31], the two field masks s32 / s33; {0.0, pit_loss} at LDS address 0 for the select form.
+def last(i): return f'v[{100 + 2 * i}:{101 + 2 * i}]'
+def lt(i): return f'v[{116 + 2 * i}:{117 + 2 * i}]'
+def step_select(i):    # today's form: every lane computes everything, the results are merged by selects
+    return [f'v_and_b32 v140, 0x200, {p(i)}', 'v_cmp_eq_u32 s[34:35], 0, v140', f'v_cmp_gt_i64 s[36:37], 0, {last(i)}',
+            's_andn2_b64 s[38:39], s[34:35], s[36:37]',
+            f'v_lshlrev_b32 v148, 18, {p(i)}', 'v_ashrrev_i32 v148, 31, v148', 'v_and_b32 v142, s26, v148', 'v_and_b32 v143, s27, v148',
+            'v_and_b32 v144, v138, v148', 'v_and_b32 v145, v139, v148',
+            f'v_cndmask_b32_e64 v138, v138, v{100 + 2 * i}, s[34:35]', f'v_cndmask_b32_e64 v139, v139, v{101 + 2 * i}, s[34:35]',
+            f'v_add_f64 {lt(i)}, {lt(i)}, v[142:143]', f'v_max_f64 {lt(i)}, |v[144:145]|, {lt(i)}',
+            f'v_cmp_ge_u32 s[40:41], v{124 + i}, v{128 + i}', 's_and_b64 s[40:41], s[40:41], s[38:39]', 's_and_b64 s[40:41], s[40:41], s[30:31]',
+            f'v_and_or_b32 v140, {p(i)}, s32, v{132 + i}', f'v_add_u32 v141, 0x10000, {p(i)}', 'v_cndmask_b32_e64 v140, v141, v140, s[40:41]',
+            f'v_and_or_b32 v141, {p(i)}, s33, v136', 'v_cndmask_b32_e64 v140, v140, v141, s[36:37]',
+            f'v_cndmask_b32_e64 {p(i)}, {p(i)}, v140, s[34:35]',
+            f'v_cndmask_b32_e64 v146, 0, v{116 + 2 * i}, s[38:39]', f'v_cndmask_b32_e64 v147, 0, v{117 + 2 * i}, s[38:39]',
+            'v_cndmask_b32_e64 v141, 0, 8, s[40:41]', f'ds_read_b64 v[{150 + 2 * i}:{151 + 2 * i}], v141',
+            f'v_add_f64 {t(i)}, {t(i)}, v[146:147]']
+def step_select_tail(i): return [f'v_add_f64 {t(i)}, {t(i)}, v[{150 + 2 * i}:{151 + 2 * i}]']
+def step_test(i, g):   # under EXEC, the compares of slot i into the SGPR pairs of group g (step_commit*: MCGP_STEP_TEST)
+    a, d, c, y = (f's[{g + 2 * k}:{g + 2 * k + 1}]' for k in range(4))
+    return ['s_mov_b64 exec, s[20:21]', f'v_and_b32 v140, 0x200, {p(i)}', f'v_cmp_eq_u32 {a}, 0, v140', f'v_cmp_gt_i32 {d}, 0, v{101 + 2 * i}',
+            f'v_and_b32 v140, 0x2000, {p(i)}', f'v_cmp_ge_u32 {c}, v{124 + i}, v{128 + i}', f'v_cmp_ne_u32 {y}, 0, v140']
+def step_write(i, g):  # ... and its writes, each under EXEC = saved & mask (MCGP_STEP_WRITE)
+    a, d, c, y = (f's[{g + 2 * k}:{g + 2 * k + 1}]' for k in range(4))
+    return [f's_and_b64 exec, s[20:21], {y}', f'v_add_f64 {lt(i)}, {lt(i)}, s[26:27]', f'v_max_f64 {lt(i)}, |v[138:139]|, {lt(i)}',
+            f's_and_b64 exec, s[20:21], {a}', f'v_mov_b64 v[138:139], {last(i)}',
+            f's_and_b64 {d}, {a}, {d}', f's_xor_b64 {a}, {a}, {d}', f's_and_b64 {c}, {c}, {a}', f's_and_b64 {c}, {c}, s[30:31]',
+            f's_and_b64 exec, s[20:21], {a}', f'v_add_f64 {t(i)}, {t(i)}, {lt(i)}', f's_xor_b64 {a}, {a}, {c}',
+            f's_and_b64 exec, s[20:21], {c}', f'v_add_f64 {t(i)}, {t(i)}, s[24:25]', f'v_and_or_b32 {p(i)}, {p(i)}, s32, v{132 + i}',
+            f's_and_b64 exec, s[20:21], {a}', f'v_add_u32 {p(i)}, 0x10000, {p(i)}',
+            f's_and_b64 exec, s[20:21], {d}', f'v_and_or_b32 {p(i)}, {p(i)}, s33, v136']
+def step_body(form):
+    # both forms: the carry starts at 0, the clean lap time and the age field of every slot are worked out afresh
+    ins = ['v_mov_b32 v138, 0', 'v_mov_b32 v139, 0']
+    for i in range(4):
+        ins += [f'v_add_f64 {lt(i)}, v[{108 + 2 * i}:{109 + 2 * i}], 0.5', f'v_and_b32 v{124 + i}, 0x7ff0000, {p(i)}']
+    if form == 'LS':
+        for i in range(4): ins += step_select(i)
+        ins += ['s_waitcnt lgkmcnt(0)']
+        for i in range(4): ins += step_select_tail(i)
+    else:              # the order of step_commit4: the compares of slot i + 1 ahead of the writes of slot i
+        ins += step_test(0, 34) + step_test(1, 42) + step_write(0, 34) + step_test(2, 34) + step_write(1, 42) + step_test(3, 42)
+        ins += step_write(2, 34) + step_write(3, 42) + ['s_mov_b64 exec, s[20:21]']
+    # (the carry and the last slot's lap time go into the check value)
+    return ins + [f'v_add_f64 {t(12)}, {t(12)}, v[138:139]', f'v_add_f64 {t(12)}, {t(12)}, {lt(3)}']
+def step_setup():
+    ins = ['v_mov_b32 v136, 0x70200', 's_mov_b32 s24, 0', 's_mov_b32 s25, 0x40340000', 's_mov_b32 s26, 0', 's_mov_b32 s27, 0x3fe00000',
+           's_mov_b64 s[30:31], -1', 's_mov_b32 s32, 0xf800e3f8', 's_mov_b32 s33, 0xf800ffff',
+           'v_mov_b32 v140, 0', 'v_mov_b32 v142, 0', 'v_mov_b32 v143, 0', 'ds_write_b64 v140, v[142:143]', 'v_mov_b32 v143, 0x40340000',
+           'ds_write_b64 v140, v[142:143] offset:8', 's_waitcnt lgkmcnt(0)']
+    for i in range(4):   # dirty flag by lane and slot, pit words 3 .. 9 laps, one slot whose car retires in a sixteenth of the lanes
+        ins += [f'v_lshrrev_b32 v140, {i}, v70', 'v_and_b32 v140, 1, v140', 'v_lshlrev_b32 v140, 13, v140', f'v_or_b32 {p(i)}, {i << 4}, v140',
+                'v_and_b32 v140, 3, v70', f'v_add_u32 v140, {3 + i}, v140', f'v_lshlrev_b32 v{128 + i}, 16, v140',
+                f'v_mov_b32 v{132 + i}, 0x{(1 + i % 3) << 10 | 1:x}', f'v_mov_b32 v140, {90 + i}', f'v_cvt_f64_u32 {last(i)}, v140',
+                f'v_mov_b32 v140, {88 + i}', f'v_cvt_f64_u32 v[{108 + 2 * i}:{109 + 2 * i}], v140']
+    ins += ['v_and_b32 v140, 15, v70', 'v_cmp_eq_u32 vcc, 5, v140', 'v_mov_b32 v141, 0x80000000', 's_nop 1', 'v_cndmask_b32 v141, 0, v141, vcc',
+            'v_or_b32 v105, v105, v141']
+    return ins
+
 clob = ','.join(f'"v{i}"' for i in list(range(10, 42)) + list(range(50, 66)) + list(range(70, 76))) + ',"vcc","s20","s21","s22","memory"'
+step_clob = ','.join(f'"v{i}"' for i in range(76, 160)) + ',' + ','.join(f'"s{i}"' for i in range(23, 50)) + ','
 commit_clob = ','.join(f'"v{i}"' for i in (76, 77) + tuple(range(80, 96))) + ',"s24","s25","s26","s27","s28","s29",'
-for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E'):
+for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE'):
     commit = form in 'SE'
-    for shape in ('chain',) if commit else ('layer', 'chain'):
+    step = form in ('LS', 'LE')
+    for shape in ('chain',) if commit or step else ('layer', 'chain'):
         ins = ['v_mbcnt_lo_u32_b32 v70, -1, 0', 'v_mbcnt_hi_u32_b32 v70, -1, v70', 'v_mov_b32 v72, 0', 'v_mov_b32 v73, 0', 'v_mov_b32 v74, 0']
         for i in range(16):
             ins += [f'v_mul_u32_u24 v71, 13, v70', f'v_add_u32 v71, {i * 7 % 64}, v71', 'v_and_b32 v71, 31, v71', f'v_cvt_f64_u32 {t(i)}, v71', f'v_mov_b32 {p(i)}, {i}']
@@ -49,9 +114,11 @@ for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E'):
                 ins += [f'v_add_u32 {p(i)}, 0x{i * 0x61c88647 & 0xffffffff:x}, v71', f'v_mov_b32 v{80 + i}, 0x40000000']
             ins += ['s_mov_b32 s24, 0x9999999a', 's_mov_b32 s25, 0xbfb99999', 's_mov_b32 s26, 0x33333333', 's_mov_b32 s27, 0x3fd33333',
                     's_mov_b64 s[28:29], 0']
+        if step: ins += step_setup()
         ins += ['s_mov_b64 s[20:21], exec', 's_mov_b32 s22, %0', '1:']
         pairs = [(i, i + 1) for i in range(15)] if shape == 'chain' else [(i, i + 8) for i in range(8)] + [(2 * i, 2 * i + 1) for i in range(8)]
-        for a, b in pairs:
+        if step: ins += step_body(form)
+        for a, b in [] if step else pairs:
             ins += comparator(form, a, b)
         if commit:       # (two of the words move on, so the lanes with a hit change from one iteration to the next)
             ins += [f'v_add_u32 {p(3)}, 0x9e3779b9, {p(3)}', f'v_add_u32 {p(11)}, 0x7f4a7c15, {p(11)}']
@@ -64,4 +131,4 @@ for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E'):
         print(f'__global__ void __launch_bounds__(256) k_{form}_{shape}(uint32_t iters, double *out)\n{{\n    asm volatile(')
         for x in ins:
             print(f'        "{x}\\n\\t"')
-        print(f'        : : "s"(iters), "s"(out) : {commit_clob if commit else ""}{clob});\n}}')
+        print(f'        : : "s"(iters), "s"(out) : {commit_clob if commit else step_clob if step else ""}{clob});\n}}')

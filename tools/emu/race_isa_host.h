@@ -133,6 +133,52 @@ inline void ovt_commit4(double &c0, double &c1, double &c2, double &c3, double &
     ovt_commit1(c3, c4, w4, t4, acc);
 }
 inline bool ovt_lane_hit(uint64_t acc) { return acc != 0u; }
+// lap-step commits (reference :179-223, :450-492): the portable body of one slot, slots in order
+struct StepSlot {
+    double last;
+    uint32_t agef, pitw, fit;
+};
+struct StepLap {
+    uint32_t retire_word;
+    uint64_t window;
+    double pit_loss, pen;
+};
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+inline void step_commit1(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    const uint32_t p = pk[0];
+    const bool active = !(p & DNF);
+    uint64_t bits;
+    std::memcpy(&bits, &s[0].last, 8);
+    const bool dnf_hit = (bits >> 63) != 0u;
+    const bool run = active && !dnf_hit;
+    const bool pit = run && c.window != 0u && s[0].agef >= s[0].pitw;
+    if (p & DIRTY) lt[0] = max_abs_f64(carry, lt[0] + c.pen);
+    if (active) carry = s[0].last;
+    if (run) cum[0] = cum[0] + lt[0];
+    if (pit) cum[0] = cum[0] + c.pit_loss;
+    if (pit) pk[0] = (p & KEEP_PIT) | s[0].fit;
+    else if (run) pk[0] = p + AGE1;
+    else if (active) pk[0] = (p & KEEP_RET) | c.retire_word;
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+inline void step_commit2(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum, pk, lt, carry, s, c);
+    step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum + 1, pk + 1, lt + 1, carry, s + 1, c);
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+inline void step_commit3(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    step_commit2<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum, pk, lt, carry, s, c);
+    step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum + 2, pk + 2, lt + 2, carry, s + 2, c);
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+inline void step_commit4(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    step_commit3<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum, pk, lt, carry, s, c);
+    step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum + 3, pk + 3, lt + 3, carry, s + 3, c);
+}
 // threads of the emulated block run one after another: "any lane" is this thread alone (both paths behind an
 // MCGP_ANY test compute the same results, so which one a thread takes does not matter); EMU_FORCE_ANY=1 sends every
 // thread down the "some lane needs it" path, which a single-thread view would otherwise reach only rarely
