@@ -40,6 +40,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -416,6 +417,35 @@ int check_deviates_32(const mcgp::KParams &kp, const char *what)
     return MCGP_OK;
 }
 
+// The prologue of the entry points that run from the grid or from a race state, in the order they call it: the source
+// (exactly one of the two), the parameter block (`what`: the call, for check_deviates_32's message), the state as the
+// kernels read it.  An entry point's own checks stand between these, where they always stood.
+int check_source(const double *grid_probs, const mcgp_race_state *state)
+{
+    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
+    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    return MCGP_OK;
+}
+
+int build_params_32(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n, const char *what,
+                    mcgp::KParams *kp)
+{
+    const int rc = build_params(cfg, drv, grid_probs, n, kp);
+    return rc == MCGP_OK ? check_deviates_32(*kp, what) : rc;
+}
+
+// *st: zero from the grid, else the packed state; sim_offset: the first simulation id for the kernels that take the ids
+// from the state (the scenario kernels), 0 for those that take them from their own argument.
+int pack_state(const mcgp_race_state *state, uint32_t n, int total_laps, uint64_t sim_offset, mcgp::ResumeState *st)
+{
+    std::memset(st, 0, sizeof(*st));
+    if (!state) return MCGP_OK;
+    const std::string err = mcgp::pack_race_state(*state, 0, n, total_laps, st);
+    if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+    st->sim_offset = sim_offset;
+    return MCGP_OK;
+}
+
 // Launch geometry: persistent blocks striding over batches of `block` simulations.  The register kernel's
 // block size and LDS footprint are compile-time functions of the field size (RegGeo<N>, shared with the
 // kernel); the number of blocks per CU follows from LDS and the kernel's register allocation.
@@ -774,7 +804,18 @@ int launch(DeviceCtx &c, const mcgp::KParams &kp, uint64_t n_sims, uint64_t sim_
     return MCGP_OK;
 }
 
-// Offsets of one call's regions in the workspace, each region rounded up to 256 bytes.
+// One segment of a call's counts: a caller's buffer (NULL: not wanted) and its cells.  A call lists its segments once,
+// in the order they have on the device, for Layout::counts and for Counts::add_to.
+struct CountSeg {
+    uint64_t *dst;
+    size_t cells;
+};
+
+// One call's regions in the workspace, each rounded up to 256 bytes.  add(size) only reserves and returns the offset.
+// add(&pointer, count, source) declares a region of `count` items together with the device pointer that is to address
+// it and, for an input, the host array it is filled from; counts(segments) declares the call's counts, one block of
+// u64 cells.  commit() then reserves the workspace, points every declared pointer at its region, uploads the sources
+// and zeroes the counts (on the null stream, like everything these calls do).
 struct Layout {
     size_t bytes = 0;
     size_t add(size_t region)
@@ -783,16 +824,50 @@ struct Layout {
         bytes += (region + 255) / 256 * 256;
         return at;
     }
+    template <class T, class U = T> void add(T **at, size_t count, const U *src = nullptr)
+    {
+        regions.push_back({add(sizeof(T) * count), (void **)at, src, src ? sizeof(T) * count : 0});
+    }
+    void counts(const std::vector<CountSeg> &segs)
+    {
+        for (const CountSeg &s : segs) {
+            seg_at.push_back(count_cells);
+            count_cells += s.cells;
+        }
+        o_counts = add(count_cells * 8);
+    }
+    int commit(DevBuf &buf)
+    {
+        const int rc = buf.reserve(bytes);
+        if (rc != MCGP_OK) return rc;
+        for (const Region &g : regions) {
+            *g.at = buf.at(g.offset);
+            if (g.bytes) HIP_TRY(hipMemcpy(*g.at, g.src, g.bytes, hipMemcpyHostToDevice));
+        }
+        d_counts = buf.at<unsigned long long>(o_counts);
+        if (count_cells) HIP_TRY(hipMemsetAsync(d_counts, 0, count_cells * 8, nullptr));
+        return MCGP_OK;
+    }
+    // segment i of the counts on the device (after commit)
+    unsigned long long *count(size_t i) const { return d_counts + seg_at[i]; }
+
+    struct Region {
+        size_t offset;
+        void **at;
+        const void *src;
+        size_t bytes;                       // to upload (0: no source)
+    };
+    std::vector<Region> regions;
+    std::vector<size_t> seg_at;
+    size_t count_cells = 0, o_counts = 0;
+    unsigned long long *d_counts = nullptr;
 };
 
 // The counts of one call: downloaded in one piece while the call holds its context, then added into the caller's
 // buffers once the whole call has returned MCGP_OK.  No entry point adds into a caller's buffer any other way, so a call
 // that fails leaves them untouched (and a retry counts nothing twice).
 struct Counts {
-    struct Seg {
-        uint64_t *dst;                      // a caller's buffer, or NULL: not wanted
-        size_t cells;
-    };
+    using Seg = CountSeg;
     std::vector<unsigned long long> v;
     int download(const void *d_src, size_t cells)
     {
@@ -800,6 +875,7 @@ struct Counts {
         HIP_TRY(hipMemcpy(v.data(), d_src, cells * 8, hipMemcpyDeviceToHost));
         return MCGP_OK;
     }
+    int download(const Layout &ws) { return download(ws.d_counts, ws.count_cells); }
     void add_to(const std::vector<Seg> &segs) const     // segs: in the order of the counts on the device
     {
         const unsigned long long *src = v.data();
@@ -834,6 +910,183 @@ int on_device(int32_t device, bool timed, Body &&body)
     c->last_timer = e == hipSuccess ? kCallTimer : -1;        // (a pair without its stop is not reported)
     if (rc == MCGP_OK && e != hipSuccess) return fail(MCGP_E_HIP, std::string("call timing event: ") + hipGetErrorString(e));
     return rc;
+}
+
+// The loop of the calls that stage per-simulation results on the device and count them there: n_sims simulations in
+// chunks of `chunk`, each chunk in the launch shape of the generic-shaped kernel `geo_fn` (`geo_name`: its name in the LDS
+// message) -- the blocks the device holds at once shared out over `rows` grid rows, 1 for a call without scenarios --
+// handed to body(done, m, gx, block, lds, n_batches): simulations done .. done + m - 1 of the call in a launch of (gx,
+// rows) blocks, each striding over the chunk's n_batches batches of `block` simulations.  The body launches the race
+// and its counting kernels, before the next chunk overwrites the staging.  Afterwards the first (fullest) chunk's shape
+// is what mcgp_last_launch_info reports, under `kernel_name`, and the counts laid out in `ws` are downloaded.
+template <class Body>
+int staged_run(DeviceCtx &c, KernelFn geo_fn, const char *geo_name, const char *kernel_name, uint32_t n, uint32_t rows,
+               uint64_t n_sims, uint64_t chunk, const Layout &ws, Counts &counts, Body &&body)
+{
+    uint32_t grid0 = 0, block0 = 0, lds0 = 0;
+    for (uint64_t done = 0; done < n_sims; done += chunk) {
+        const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
+        uint32_t grid = 0, block = 0, lds = 0;
+        int r = generic_geometry(c, geo_fn, geo_name, n, m * rows, &grid, &block, &lds);
+        if (r != MCGP_OK) return r;
+        const uint64_t n_batches = (m + block - 1) / block;
+        const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + rows - 1) / rows);
+        if (done == 0) { grid0 = gx * rows; block0 = block; lds0 = lds; }
+        r = body(done, m, gx, block, lds, (uint32_t)n_batches);
+        if (r != MCGP_OK) return r;
+    }
+    note_launch(c, grid0, block0, lds0, "%s", kernel_name);
+    return counts.download(ws);
+}
+
+// One chunk of a scenario call as its kernels are launched: (gx, S) blocks of `block` threads over simulations
+// first_sim .. first_sim + m - 1, the shared inputs and outputs on the device.
+struct ScenarioChunk {
+    uint32_t gx, S, block, lds, n_batches;
+    uint64_t m, first_sim, seed;
+    const mcgp::KParams *kp;
+    const mcgp::ResumeState *st;
+    const mcgp::StrategyScenario *sc;
+    const mcgp::StopLap *sl;
+    unsigned long long *hist;
+    uint8_t *stage;                         // [S][m][n] bytes: every driver's finishing position
+};
+
+// What mcgp_run_strategies, mcgp_run_penalties and mcgp_run_events each have of their own; run_scenarios has the rest.
+struct ScenarioKind {
+    const char *what;                       // the call in check_deviates_32's message
+    const char *geo_name, *kernel_name;     // generic_geometry's and note_launch's name of the race kernel
+    KernelFn geo_fn;                        // the race kernel (for its register count)
+    // the kind's own input table, one count per scenario: the arguments and their names (all NULL: no table)
+    const char *count_name = nullptr, *items_name = nullptr;
+    const uint32_t *item_count = nullptr;
+    const void *items = nullptr;
+    std::function<std::string(uint64_t *n_items)> check_counts;          // its counts, before anything is packed
+    std::function<std::string(int first_lap, bool resumed)> pack;        // its items, behind pack_scenarios
+    size_t sim_bytes;                                                    // staged per (scenario, simulation)
+    uint8_t pos_mask = 0xFF;                                             // the position in a staged byte
+    std::function<void(Layout &, uint64_t chunk)> regions;               // its regions of the workspace
+    std::function<void(const ScenarioChunk &)> race;                     // launches the race kernel
+    // launches the counting kernel (run when delta or the kind's output is wanted; NULL for the one that is not)
+    std::function<void(const ScenarioChunk &, uint64_t grid_cap, unsigned long long *delta, unsigned long long *extra)> count;
+    // the kind's own count segment behind hist and delta: the caller's buffer, its cells, a fix-up on the host
+    uint64_t *extra_out = nullptr;
+    size_t (*extra_cells)(size_t S, size_t n, size_t L) = nullptr;
+    void (*fix_up)(unsigned long long *extra, size_t rows, uint64_t n_sims) = nullptr;
+};
+
+int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                      uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                      uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                      uint64_t *delta_out, uint8_t *orders_out, const ScenarioKind &k)
+{
+    // ---- every argument is checked before any device is looked up
+    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+    if (!plan_count) return fail(MCGP_E_BAD_ARG, "plan_count is NULL");
+    if (k.count_name && !k.item_count) return fail(MCGP_E_BAD_ARG, std::string(k.count_name) + " is NULL");
+    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
+        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]");
+    uint64_t n_plans = 0, n_items = 0;
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        if (plan_count[si] > mcgp::kMaxCars)
+            return fail(MCGP_E_BAD_ARG, "scenario " + std::to_string(si) + ": plan_count must be in [0, 32]");
+        n_plans += plan_count[si];
+    }
+    if (k.check_counts) {
+        const std::string err = k.check_counts(&n_items);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+    }
+    if (n_plans && !plans) return fail(MCGP_E_BAD_ARG, "plans is NULL");
+    if (n_items && !k.items) return fail(MCGP_E_BAD_ARG, std::string(k.items_name) + " is NULL");
+    int rc = check_source(grid_probs, state);
+    if (rc != MCGP_OK) return rc;
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    rc = build_params_32(cfg, drv, grid_probs, n, k.what, &kp);
+    if (rc != MCGP_OK) return rc;
+    const int L = cfg->total_laps;
+    mcgp::ResumeState st;
+    rc = pack_state(state, n, L, sim_offset, &st);
+    if (rc != MCGP_OK) return rc;
+    const int first_lap = state ? st.lap + 1 : 2;
+    std::vector<mcgp::StrategyScenario> scen;
+    std::vector<mcgp::StopLap> stop_laps;
+    {
+        std::string err = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen,
+                                               &stop_laps);
+        if (err.empty() && k.pack) err = k.pack(first_lap, state != nullptr);
+        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
+    }
+    if (n_sims == 0) return MCGP_OK;
+    const uint32_t S = n_scenarios;
+    const size_t w = 2 * (size_t)n - 1;
+    const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w;
+    // hist [S][n][n] | delta [S][n][2n - 1] | the kind's own counts
+    std::vector<Counts::Seg> segs = {{hist_out, c_hist}, {delta_out, c_delta}};
+    if (k.extra_cells) segs.push_back({k.extra_out, k.extra_cells(S, n, (size_t)L)});
+    Counts counts;
+    std::vector<uint8_t> orders;            // collected on the host, handed over only once everything has run
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        const uint64_t chunk = std::min<uint64_t>(stage_chunk_sims(kStrategyStageBytes, (uint64_t)S * k.sim_bytes), n_sims);
+        const size_t stage_bytes = (size_t)S * chunk * n;
+        // workspace: staged positions of a chunk | parameter block | state | scenarios | stop laps | the kind's regions |
+        // the counts
+        ScenarioChunk l = {};
+        Layout ws;
+        ws.add(&l.stage, stage_bytes);
+        ws.add(&l.kp, 1, &kp);
+        ws.add(&l.st, 1, &st);
+        ws.add(&l.sc, S, scen.data());
+        ws.add(&l.sl, stop_laps.size(), stop_laps.data());
+        if (k.regions) k.regions(ws, chunk);
+        ws.counts(segs);
+        const int r = ws.commit(c.work);
+        if (r != MCGP_OK) return r;
+        l.hist = ws.count(0);
+        l.S = S;
+        l.seed = seed;
+        std::vector<uint8_t> pos_back;
+        if (orders_out) {
+            pos_back.resize(stage_bytes);
+            orders.resize((size_t)S * n_sims * n);
+        }
+        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
+        const bool count_delta = delta_out && S > 1;
+        return staged_run(c, k.geo_fn, k.geo_name, k.kernel_name, n, S, n_sims, chunk, ws, counts,
+                          [&](uint64_t done, uint64_t m, uint32_t gx, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
+            l.gx = gx, l.block = block, l.lds = lds, l.n_batches = n_batches, l.m = m, l.first_sim = sim_offset + done;
+            k.race(l);
+            HIP_TRY(hipGetLastError());
+            if (count_delta || k.extra_out) {
+                k.count(l, grid_cap, count_delta ? ws.count(1) : nullptr, k.extra_out ? ws.count(2) : nullptr);
+                HIP_TRY(hipGetLastError());
+            }
+            if (orders_out) {
+                HIP_TRY(hipMemcpy(pos_back.data(), l.stage, (size_t)S * m * n, hipMemcpyDeviceToHost));
+                for (uint32_t si = 0; si < S; ++si)
+                    for (uint64_t i = 0; i < m; ++i) {
+                        const uint8_t *pos = pos_back.data() + ((size_t)si * m + i) * n;
+                        uint8_t *ord = orders.data() + ((size_t)si * n_sims + done + i) * n;
+                        for (uint32_t d = 0; d < n; ++d) ord[pos[d] & k.pos_mask] = (uint8_t)d;
+                    }
+            }
+            return MCGP_OK;
+        });
+    });
+    if (rc != MCGP_OK) return rc;
+    unsigned long long *b = counts.v.data() + c_hist;
+    if (delta_out) {
+        // the centre bin (no change) of every (scenario, driver) is what the other bins leave of n_sims
+        for (size_t row = 0; row < (size_t)S * n; ++row) {
+            unsigned long long rest = 0;
+            for (size_t j = 0; j < w; ++j) rest += j == n - 1 ? 0ull : b[row * w + j];
+            b[row * w + n - 1] = n_sims - rest;
+        }
+    }
+    if (k.extra_out && k.fix_up) k.fix_up(b + c_delta, (size_t)S * n, n_sims);
+    counts.add_to(segs);
+    if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
+    return MCGP_OK;
 }
 
 }  // namespace
@@ -1578,8 +1831,7 @@ int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uin
     if (n_states < 1 || n_states > mcgp::kMaxResumeStates) return fail(MCGP_E_BAD_ARG, "n_states must be in [1, 4096]");
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, nullptr, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "a resumed race runs");
+    int rc = build_params_32(cfg, drv, nullptr, n, "a resumed race runs", &kp);
     if (rc != MCGP_OK) return rc;
     std::vector<mcgp::ResumeState> st(n_states);
     for (uint32_t si = 0; si < n_states; ++si) {
@@ -1597,18 +1849,18 @@ int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uin
         if (orders_out) chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, kOrdersChunk / n_states));
         const uint64_t cap = n_sims < chunk ? n_sims : chunk;
         // workspace: orders staging | parameter block | states | histograms
+        uint8_t *d_orders;
+        const mcgp::KParams *d_kp;
+        const mcgp::ResumeState *d_st;
         Layout ws;
-        const size_t o_orders = ws.add(orders_out ? (size_t)n_states * cap * n : 0), o_kp = ws.add(sizeof(kp));
-        const size_t o_st = ws.add(sizeof(mcgp::ResumeState) * n_states), o_hist = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
+        ws.add(&d_orders, orders_out ? (size_t)n_states * cap * n : 0);
+        ws.add(&d_kp, 1, &kp);
+        ws.add(&d_st, n_states, st.data());
+        ws.counts({{hist_out, cells}});
+        int r = ws.commit(c.work);
         if (r != MCGP_OK) return r;
-        uint8_t *d_orders = orders_out ? c.work.at<uint8_t>(o_orders) : nullptr;
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
-        unsigned long long *d_h = c.work.at<unsigned long long>(o_hist);
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_st), st.data(), sizeof(mcgp::ResumeState) * n_states, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_h, 0, cells * 8, nullptr));
+        if (!orders_out) d_orders = nullptr;
+        unsigned long long *d_h = ws.count(0);
         const KernelFn geo_fn = reinterpret_cast<KernelFn>(&mcgp::race_resume_kernel);   // (for its register count)
         uint32_t grid = 0, block = 0, lds = 0;
         for (uint64_t done = 0; done < n_sims; done += cap) {
@@ -1643,50 +1895,42 @@ int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const do
     if (!grid_probs || !hist_out || !lap_pos_out) return fail(MCGP_E_BAD_ARG, "grid_probs / hist_out / lap_pos_out is NULL");
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, grid_probs, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "a trace runs");
+    int rc = build_params_32(cfg, drv, grid_probs, n, "a trace runs", &kp);
     if (rc != MCGP_OK) return rc;
     if (n_sims == 0) return MCGP_OK;
     const uint32_t L = (uint32_t)kp.total_laps;
     const uint32_t rows = L * n;
-    const size_t c_hist = (size_t)n * n, c_pos = (size_t)rows * (n + 1), c_laps = (size_t)n * (L + 1), c_fast = n,
-                 c_ev = 3 * (size_t)(L + 1);
-    const size_t cells = c_hist + c_pos + 2 * c_laps + c_fast + c_ev;
+    const size_t c_laps = (size_t)n * (L + 1);
+    // hist [n][n] | lap_pos [L][n][n + 1] | laps_led [n][L + 1] | stops [n][L + 1] | fastest [n] | events [3][L + 1]
+    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n}, {lap_pos_out, (size_t)rows * (n + 1)},
+                                           {laps_led_out, c_laps},    {stops_out, c_laps},
+                                           {fastest_out, n},          {events_out, 3 * (size_t)(L + 1)}};
     Counts counts;
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         const KernelFn geo_fn = reinterpret_cast<KernelFn>(&mcgp::race_trace_kernel);   // (for its register count)
         const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kTraceStageBytes, (uint64_t)L * n, n_sims);
         // workspace: staging of one chunk in rows of `stride` bytes (a multiple of 256: whole, aligned words for the
-        // counting kernels) | the chunk's records | parameter block | hist [n][n] | lap_pos [L][n][n + 1] |
-        // laps_led [n][L + 1] | stops [n][L + 1] | fastest [n] | events [3][L + 1]
+        // counting kernels) | the chunk's records | parameter block | the counts
         const uint64_t stride = (chunk + 255) / 256 * 256;
+        uint8_t *d_stage;
+        uint64_t *d_rec;
+        const mcgp::KParams *d_kp;
         Layout ws;
-        const size_t o_stage = ws.add((size_t)rows * stride), o_rec = ws.add((size_t)stride * 8), o_kp = ws.add(sizeof(kp));
-        const size_t o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
+        ws.add(&d_stage, (size_t)rows * stride);
+        ws.add(&d_rec, (size_t)stride);
+        ws.add(&d_kp, 1, &kp);
+        ws.counts(segs);
+        const int r = ws.commit(c.work);
         if (r != MCGP_OK) return r;
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
-        unsigned long long *d_pos = d_hist + c_hist, *d_led = d_pos + c_pos, *d_stops = d_led + c_laps;
-        unsigned long long *d_fast = d_stops + c_laps, *d_ev = d_fast + c_fast;
-        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
-        uint64_t *d_rec = c.work.at<uint64_t>(o_rec);
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        unsigned long long *d_hist = ws.count(0), *d_pos = ws.count(1), *d_led = ws.count(2), *d_stops = ws.count(3);
+        unsigned long long *d_fast = ws.count(4), *d_ev = ws.count(5);
         const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
         const size_t laps_lds = 2 * (size_t)(L + 1) * 4, rec_lds = ((size_t)mcgp::kMaxCars + 3 * (size_t)(L + 1)) * 4;
-        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
-        for (uint64_t done = 0; done < n_sims; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            // the race: the generic kernel's block shape and LDS
-            r = generic_geometry(c, geo_fn, "trace", n, m, &grid, &block, &lds);
-            if (r != MCGP_OK) return r;
-            if (done == 0) { grid0 = grid; block0 = block; }
-            const uint64_t n_batches = (m + block - 1) / block;
+        return staged_run(c, geo_fn, "trace", "mcgp::race_trace_kernel", n, 1, n_sims, chunk, ws, counts,
+                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
             hipLaunchKernelGGL(mcgp::race_trace_kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, d_rec, (uint32_t)n_batches);
+                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, d_rec, n_batches);
             HIP_TRY(hipGetLastError());
-            // its counts, before the next chunk overwrites the staging
             const uint64_t words = (m + 3) / 4;
             const uint64_t tiles = (words + mcgp::kTraceCountBlock - 1) / mcgp::kTraceCountBlock;
             hipLaunchKernelGGL(mcgp::trace_count_positions, dim3((uint32_t)std::min<uint64_t>(rows, grid_cap)),
@@ -1704,13 +1948,11 @@ int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                                    dim3(mcgp::kTraceCountBlock), rec_lds, nullptr, d_rec, m, n, L, d_fast, d_ev);
                 HIP_TRY(hipGetLastError());
             }
-        }
-        note_launch(c, grid0, block0, lds, "mcgp::race_trace_kernel");      // the launch shape of the first (fullest) chunk
-        return counts.download(d_hist, cells);
+            return MCGP_OK;
+        });
     });
     if (rc != MCGP_OK) return rc;
-    counts.add_to({{hist_out, c_hist}, {lap_pos_out, c_pos}, {laps_led_out, c_laps}, {stops_out, c_laps},
-                   {fastest_out, c_fast}, {events_out, c_ev}});
+    counts.add_to(segs);
     return MCGP_OK;
 }
 
@@ -1719,125 +1961,22 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
                             const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
                             int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint8_t *orders_out)
 {
-    // ---- every argument is checked before any device is looked up
-    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
-    if (!plan_count) return fail(MCGP_E_BAD_ARG, "plan_count is NULL");
-    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
-        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]");
-    uint64_t n_plans = 0;
-    for (uint32_t si = 0; si < n_scenarios; ++si) {
-        if (plan_count[si] > mcgp::kMaxCars)
-            return fail(MCGP_E_BAD_ARG, "scenario " + std::to_string(si) + ": plan_count must be in [0, 32]");
-        n_plans += plan_count[si];
-    }
-    if (n_plans && !plans) return fail(MCGP_E_BAD_ARG, "plans is NULL");
-    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
-    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
-    std::vector<mcgp::KParams> kps(1);
-    mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, grid_probs, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "strategies run");
-    if (rc != MCGP_OK) return rc;
-    const int L = cfg->total_laps;
-    mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string err = mcgp::pack_race_state(*state, 0, n, L, &st);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-        st.sim_offset = sim_offset;
-    }
-    std::vector<mcgp::StrategyScenario> scen;
-    std::vector<mcgp::StopLap> stop_laps;
-    {
-        const std::string err = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, state ? st.lap + 1 : 2,
-                                                     state != nullptr, &scen, &stop_laps);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-    }
-    if (n_sims == 0) return MCGP_OK;
-    const uint32_t S = n_scenarios;
-    const size_t w = 2 * (size_t)n - 1;
-    const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w;
-    const size_t cells = c_hist + c_delta;
-    Counts counts;
-    std::vector<uint8_t> orders;            // collected on the host, handed over only once everything has run
-    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        const uint64_t chunk = std::min<uint64_t>(stage_chunk_sims(kStrategyStageBytes, (uint64_t)S * n), n_sims);
-        const size_t stage_bytes = (size_t)S * chunk * n;
-        // workspace: staged positions of a chunk | parameter block | state | scenarios | stop laps | hist [S][n][n] |
-        // delta [S][n][2n - 1]
-        Layout ws;
-        const size_t o_stage = ws.add(stage_bytes), o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st));
-        const size_t o_sc = ws.add(sizeof(mcgp::StrategyScenario) * S), o_sl = ws.add(sizeof(mcgp::StopLap) * stop_laps.size());
-        const size_t o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
-        if (r != MCGP_OK) return r;
-        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
-        const mcgp::StrategyScenario *d_sc = c.work.at<const mcgp::StrategyScenario>(o_sc);
-        const mcgp::StopLap *d_sl = c.work.at<const mcgp::StopLap>(o_sl);
-        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
-        unsigned long long *d_delta = d_hist + c_hist;
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_sc), scen.data(), sizeof(mcgp::StrategyScenario) * S, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_sl), stop_laps.data(), sizeof(mcgp::StopLap) * stop_laps.size(),
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
-        std::vector<uint8_t> pos_back;
-        if (orders_out) {
-            pos_back.resize(stage_bytes);
-            orders.resize((size_t)S * n_sims * n);
-        }
-        const auto kernel = state ? &mcgp::race_strategy_kernel<true> : &mcgp::race_strategy_kernel<false>;
-        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
-        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
-        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
-        for (uint64_t done = 0; done < n_sims; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            // the generic kernel's block shape; the blocks the device holds at once are shared out over the scenarios
-            r = generic_geometry(c, geo_fn, "strategy", n, m * S, &grid, &block, &lds);
-            if (r != MCGP_OK) return r;
-            const uint64_t n_batches = (m + block - 1) / block;
-            const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + S - 1) / S);
-            if (done == 0) { grid0 = gx * S; block0 = block; }
-            hipLaunchKernelGGL(kernel, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st, d_sc, d_sl, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, (uint32_t)n_batches);
-            HIP_TRY(hipGetLastError());
-            // its counts, before the next chunk overwrites the staging
-            if (delta_out && S > 1) {
-                const uint64_t tiles = (m + mcgp::kStrategyCountBlock - 1) / mcgp::kStrategyCountBlock;
-                const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / (S - 1)));
-                hipLaunchKernelGGL(mcgp::strategy_count_deltas, dim3((uint32_t)gxc, S - 1), dim3(mcgp::kStrategyCountBlock),
-                                   0, nullptr, d_stage, m, n, d_delta);
-                HIP_TRY(hipGetLastError());
-            }
-            if (orders_out) {
-                HIP_TRY(hipMemcpy(pos_back.data(), d_stage, (size_t)S * m * n, hipMemcpyDeviceToHost));
-                for (uint32_t si = 0; si < S; ++si)
-                    for (uint64_t i = 0; i < m; ++i) {
-                        const uint8_t *pos = pos_back.data() + ((size_t)si * m + i) * n;
-                        uint8_t *ord = orders.data() + ((size_t)si * n_sims + done + i) * n;
-                        for (uint32_t d = 0; d < n; ++d) ord[pos[d]] = (uint8_t)d;
-                    }
-            }
-        }
-        note_launch(c, grid0, block0, lds, "mcgp::race_strategy_kernel");   // the launch shape of the first (fullest) chunk
-        return counts.download(d_hist, cells);
-    });
-    if (rc != MCGP_OK) return rc;
-    if (delta_out) {
-        // the centre bin (no change) of every (scenario, driver) is what the other bins leave of n_sims
-        unsigned long long *b = counts.v.data() + c_hist;
-        for (size_t row = 0; row < (size_t)S * n; ++row) {
-            unsigned long long rest = 0;
-            for (size_t j = 0; j < w; ++j) rest += j == n - 1 ? 0ull : b[row * w + j];
-            b[row * w + n - 1] = n_sims - rest;
-        }
-    }
-    counts.add_to({{hist_out, c_hist}, {delta_out, c_delta}});
-    if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
-    return MCGP_OK;
+    const auto kernel = state ? &mcgp::race_strategy_kernel<true> : &mcgp::race_strategy_kernel<false>;
+    ScenarioKind k = {"strategies run", "strategy", "mcgp::race_strategy_kernel", reinterpret_cast<KernelFn>(kernel)};
+    k.sim_bytes = n;                        // a position byte per driver
+    k.race = [&](const ScenarioChunk &l) {
+        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, l.m, l.first_sim,
+                           (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, l.n_batches);
+    };
+    // every scenario but the first against the first: S - 1 grid rows (never run for one scenario)
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *) {
+        const uint64_t tiles = (l.m + mcgp::kStrategyCountBlock - 1) / mcgp::kStrategyCountBlock;
+        const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / (l.S - 1)));
+        hipLaunchKernelGGL(mcgp::strategy_count_deltas, dim3((uint32_t)gxc, l.S - 1), dim3(mcgp::kStrategyCountBlock), 0,
+                           nullptr, l.stage, l.m, n, d_delta);
+    };
+    return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
+                         hist_out, delta_out, orders_out, k);
 }
 
 int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
@@ -1846,149 +1985,42 @@ int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, cons
                            uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                            uint64_t *delta_out, uint64_t *fate_out, uint8_t *orders_out)
 {
-    // ---- every argument is checked before any device is looked up
-    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
-    if (!plan_count) return fail(MCGP_E_BAD_ARG, "plan_count is NULL");
-    if (!penalty_count) return fail(MCGP_E_BAD_ARG, "penalty_count is NULL");
-    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
-        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]");
-    uint64_t n_plans = 0, n_pens = 0;
-    for (uint32_t si = 0; si < n_scenarios; ++si) {
-        if (plan_count[si] > mcgp::kMaxCars)
-            return fail(MCGP_E_BAD_ARG, "scenario " + std::to_string(si) + ": plan_count must be in [0, 32]");
-        n_plans += plan_count[si];
-    }
-    {
-        const std::string err = mcgp::check_penalty_counts(n_scenarios, penalty_count, &n_pens);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-    }
-    if (n_plans && !plans) return fail(MCGP_E_BAD_ARG, "plans is NULL");
-    if (n_pens && !penalties) return fail(MCGP_E_BAD_ARG, "penalties is NULL");
-    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
-    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
-    std::vector<mcgp::KParams> kps(1);
-    mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, grid_probs, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "penalties run");
-    if (rc != MCGP_OK) return rc;
-    const int L = cfg->total_laps;
-    mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string err = mcgp::pack_race_state(*state, 0, n, L, &st);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-        st.sim_offset = sim_offset;
-    }
-    const int first_lap = state ? st.lap + 1 : 2;
-    std::vector<mcgp::StrategyScenario> scen;
-    std::vector<mcgp::StopLap> stop_laps;
+    const auto kernel = state ? &mcgp::race_penalties_kernel<true> : &mcgp::race_penalties_kernel<false>;
     std::vector<mcgp::PenaltyScenario> pens;
     std::vector<mcgp::PenaltyLap> pen_laps;
-    {
-        std::string err = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen,
-                                               &stop_laps);
-        if (err.empty())
-            err = mcgp::pack_penalties(n_scenarios, penalty_count, penalties, n, L, first_lap, state != nullptr, &pens,
-                                       &pen_laps);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-    }
-    if (n_sims == 0) return MCGP_OK;
-    const uint32_t S = n_scenarios;
-    const size_t w = 2 * (size_t)n - 1;
-    const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w, c_fate = (size_t)S * n * 4;
-    const size_t cells = c_hist + c_delta + c_fate;
-    Counts counts;
-    std::vector<uint8_t> orders;            // collected on the host, handed over only once everything has run
-    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        const uint64_t chunk = std::min<uint64_t>(stage_chunk_sims(kStrategyStageBytes, (uint64_t)S * n), n_sims);
-        const size_t stage_bytes = (size_t)S * chunk * n;
-        // workspace: staged bytes of a chunk | parameter block | state | scenarios | stop laps | penalties | penalty
-        // laps | hist [S][n][n] | delta [S][n][2n - 1] | fate [S][n][4]
-        Layout ws;
-        const size_t o_stage = ws.add(stage_bytes), o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st));
-        const size_t o_sc = ws.add(sizeof(mcgp::StrategyScenario) * S), o_sl = ws.add(sizeof(mcgp::StopLap) * stop_laps.size());
-        const size_t o_pn = ws.add(sizeof(mcgp::PenaltyScenario) * S), o_pl = ws.add(sizeof(mcgp::PenaltyLap) * pen_laps.size());
-        const size_t o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
-        if (r != MCGP_OK) return r;
-        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
-        const mcgp::StrategyScenario *d_sc = c.work.at<const mcgp::StrategyScenario>(o_sc);
-        const mcgp::StopLap *d_sl = c.work.at<const mcgp::StopLap>(o_sl);
-        const mcgp::PenaltyScenario *d_pn = c.work.at<const mcgp::PenaltyScenario>(o_pn);
-        const mcgp::PenaltyLap *d_pl = c.work.at<const mcgp::PenaltyLap>(o_pl);
-        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
-        unsigned long long *d_delta = d_hist + c_hist, *d_fate = d_delta + c_delta;
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_sc), scen.data(), sizeof(mcgp::StrategyScenario) * S, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_sl), stop_laps.data(), sizeof(mcgp::StopLap) * stop_laps.size(),
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_pn), pens.data(), sizeof(mcgp::PenaltyScenario) * S, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_pl), pen_laps.data(), sizeof(mcgp::PenaltyLap) * pen_laps.size(),
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
-        std::vector<uint8_t> pos_back;
-        if (orders_out) {
-            pos_back.resize(stage_bytes);
-            orders.resize((size_t)S * n_sims * n);
-        }
-        const auto kernel = state ? &mcgp::race_penalties_kernel<true> : &mcgp::race_penalties_kernel<false>;
-        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
-        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
-        const bool count_delta = delta_out && S > 1;
-        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
-        for (uint64_t done = 0; done < n_sims; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            // the generic kernel's block shape; the blocks the device holds at once are shared out over the scenarios
-            r = generic_geometry(c, geo_fn, "penalties", n, m * S, &grid, &block, &lds);
-            if (r != MCGP_OK) return r;
-            const uint64_t n_batches = (m + block - 1) / block;
-            const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + S - 1) / S);
-            if (done == 0) { grid0 = gx * S; block0 = block; }
-            hipLaunchKernelGGL(kernel, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st, d_sc, d_sl, d_pn, d_pl, m,
-                               sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, (uint32_t)n_batches);
-            HIP_TRY(hipGetLastError());
-            // its counts, before the next chunk overwrites the staging
-            if (count_delta || fate_out) {
-                const uint64_t tiles = (m + mcgp::kPenaltyCountBlock - 1) / mcgp::kPenaltyCountBlock;
-                const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / S));
-                hipLaunchKernelGGL(mcgp::penalties_count, dim3((uint32_t)gxc, S), dim3(mcgp::kPenaltyCountBlock), 0, nullptr,
-                                   d_stage, m, n, count_delta ? d_delta : nullptr, fate_out ? d_fate : nullptr);
-                HIP_TRY(hipGetLastError());
-            }
-            if (orders_out) {
-                HIP_TRY(hipMemcpy(pos_back.data(), d_stage, (size_t)S * m * n, hipMemcpyDeviceToHost));
-                for (uint32_t si = 0; si < S; ++si)
-                    for (uint64_t i = 0; i < m; ++i) {
-                        const uint8_t *pos = pos_back.data() + ((size_t)si * m + i) * n;
-                        uint8_t *ord = orders.data() + ((size_t)si * n_sims + done + i) * n;
-                        for (uint32_t d = 0; d < n; ++d) ord[pos[d] & mcgp::kStagePosMask] = (uint8_t)d;
-                    }
-            }
-        }
-        note_launch(c, grid0, block0, lds, "mcgp::race_penalties_kernel");  // the launch shape of the first (fullest) chunk
-        return counts.download(d_hist, cells);
-    });
-    if (rc != MCGP_OK) return rc;
-    unsigned long long *b = counts.v.data() + c_hist;
-    if (delta_out) {
-        // the centre bin (no change) of every (scenario, driver) is what the other bins leave of n_sims
-        for (size_t row = 0; row < (size_t)S * n; ++row) {
-            unsigned long long rest = 0;
-            for (size_t j = 0; j < w; ++j) rest += j == n - 1 ? 0ull : b[row * w + j];
-            b[row * w + n - 1] = n_sims - rest;
-        }
-    }
-    if (fate_out) {
-        // column 0 (no SERVE_AT_STOP penalty) likewise
-        unsigned long long *f = b + c_delta;
-        for (size_t row = 0; row < (size_t)S * n; ++row) f[row * 4] = n_sims - (f[row * 4 + 1] + f[row * 4 + 2] + f[row * 4 + 3]);
-    }
-    counts.add_to({{hist_out, c_hist}, {delta_out, c_delta}, {fate_out, c_fate}});
-    if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
-    return MCGP_OK;
+    const mcgp::PenaltyScenario *d_pn = nullptr;
+    const mcgp::PenaltyLap *d_pl = nullptr;
+    ScenarioKind k = {"penalties run", "penalties", "mcgp::race_penalties_kernel", reinterpret_cast<KernelFn>(kernel)};
+    k.count_name = "penalty_count", k.item_count = penalty_count, k.items_name = "penalties", k.items = penalties;
+    k.check_counts = [&](uint64_t *n_pens) { return mcgp::check_penalty_counts(n_scenarios, penalty_count, n_pens); };
+    k.pack = [&](int first_lap, bool resumed) {
+        return mcgp::pack_penalties(n_scenarios, penalty_count, penalties, n, cfg->total_laps, first_lap, resumed, &pens,
+                                    &pen_laps);
+    };
+    k.sim_bytes = n;                        // a byte per driver: its position, and the fate of its penalty above it
+    k.pos_mask = mcgp::kStagePosMask;
+    k.regions = [&](Layout &ws, uint64_t) {
+        ws.add(&d_pn, n_scenarios, pens.data());
+        ws.add(&d_pl, pen_laps.size(), pen_laps.data());
+    };
+    k.race = [&](const ScenarioChunk &l) {
+        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_pn, d_pl, l.m,
+                           l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, l.n_batches);
+    };
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *d_fate) {
+        const uint64_t tiles = (l.m + mcgp::kPenaltyCountBlock - 1) / mcgp::kPenaltyCountBlock;
+        const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
+        hipLaunchKernelGGL(mcgp::penalties_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kPenaltyCountBlock), 0, nullptr,
+                           l.stage, l.m, n, d_delta, d_fate);
+    };
+    // fate [S][n][4]; column 0 (no SERVE_AT_STOP penalty) is, like delta's centre bin, what the others leave of n_sims
+    k.extra_out = fate_out;
+    k.extra_cells = [](size_t S, size_t n_, size_t) { return S * n_ * 4; };
+    k.fix_up = [](unsigned long long *f, size_t rows, uint64_t n_sims_) {
+        for (size_t row = 0; row < rows; ++row) f[row * 4] = n_sims_ - (f[row * 4 + 1] + f[row * 4 + 2] + f[row * 4 + 3]);
+    };
+    return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
+                         hist_out, delta_out, orders_out, k);
 }
 
 int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
@@ -1997,143 +2029,36 @@ int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const d
                         uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                         uint64_t *delta_out, uint64_t *events_out, uint8_t *orders_out)
 {
-    // ---- every argument is checked before any device is looked up
-    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
-    if (!plan_count) return fail(MCGP_E_BAD_ARG, "plan_count is NULL");
-    if (!event_count) return fail(MCGP_E_BAD_ARG, "event_count is NULL");
-    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
-        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]");
-    uint64_t n_plans = 0, n_events = 0;
-    for (uint32_t si = 0; si < n_scenarios; ++si) {
-        if (plan_count[si] > mcgp::kMaxCars)
-            return fail(MCGP_E_BAD_ARG, "scenario " + std::to_string(si) + ": plan_count must be in [0, 32]");
-        n_plans += plan_count[si];
-    }
-    {
-        const std::string err = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-    }
-    if (n_plans && !plans) return fail(MCGP_E_BAD_ARG, "plans is NULL");
-    if (n_events && !events) return fail(MCGP_E_BAD_ARG, "events is NULL");
-    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
-    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
-    std::vector<mcgp::KParams> kps(1);
-    mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, grid_probs, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "events run");
-    if (rc != MCGP_OK) return rc;
-    const int L = cfg->total_laps;
-    mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string err = mcgp::pack_race_state(*state, 0, n, L, &st);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-        st.sim_offset = sim_offset;
-    }
-    const int first_lap = state ? st.lap + 1 : 2;
-    std::vector<mcgp::StrategyScenario> scen;
-    std::vector<mcgp::StopLap> stop_laps;
+    const auto kernel = state ? &mcgp::race_events_kernel<true> : &mcgp::race_events_kernel<false>;
     std::vector<uint8_t> event_laps;
-    {
-        std::string err = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen,
-                                               &stop_laps);
-        if (err.empty())
-            err = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, state != nullptr, &event_laps);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-    }
-    if (n_sims == 0) return MCGP_OK;
-    const uint32_t S = n_scenarios;
-    const size_t w = 2 * (size_t)n - 1;
-    const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w, c_ev = (size_t)S * 3 * (L + 1);
-    const size_t cells = c_hist + c_delta + c_ev;
-    Counts counts;
-    std::vector<uint8_t> orders;            // collected on the host, handed over only once everything has run
-    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        // positions and event counts of a chunk share the strategy call's budget: n + 4 bytes per scenario and simulation
-        const uint64_t chunk = std::min<uint64_t>(stage_chunk_sims(kStrategyStageBytes, (uint64_t)S * (n + 4)), n_sims);
-        const size_t stage_bytes = (size_t)S * chunk * n, ev_bytes = (size_t)S * chunk * sizeof(uint32_t);
-        // workspace: staged positions of a chunk | staged event counts | parameter block | state | scenarios | stop laps |
-        // event laps | hist [S][n][n] | delta [S][n][2n - 1] | events [S][3][L + 1]
-        Layout ws;
-        const size_t o_stage = ws.add(stage_bytes), o_evs = ws.add(ev_bytes), o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st));
-        const size_t o_sc = ws.add(sizeof(mcgp::StrategyScenario) * S), o_sl = ws.add(sizeof(mcgp::StopLap) * stop_laps.size());
-        const size_t o_el = ws.add(event_laps.size());
-        const size_t o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
-        if (r != MCGP_OK) return r;
-        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
-        uint32_t *d_evs = c.work.at<uint32_t>(o_evs);
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
-        const mcgp::StrategyScenario *d_sc = c.work.at<const mcgp::StrategyScenario>(o_sc);
-        const mcgp::StopLap *d_sl = c.work.at<const mcgp::StopLap>(o_sl);
-        const uint8_t *d_el = c.work.at<const uint8_t>(o_el);
-        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
-        unsigned long long *d_delta = d_hist + c_hist, *d_ev = d_delta + c_delta;
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_sc), scen.data(), sizeof(mcgp::StrategyScenario) * S, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_sl), stop_laps.data(), sizeof(mcgp::StopLap) * stop_laps.size(),
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_el), event_laps.data(), event_laps.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
-        std::vector<uint8_t> pos_back;
-        if (orders_out) {
-            pos_back.resize(stage_bytes);
-            orders.resize((size_t)S * n_sims * n);
-        }
-        const auto kernel = state ? &mcgp::race_events_kernel<true> : &mcgp::race_events_kernel<false>;
-        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
-        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
-        const bool count_delta = delta_out && S > 1;
-        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
-        for (uint64_t done = 0; done < n_sims; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            // the generic kernel's block shape; the blocks the device holds at once are shared out over the scenarios
-            r = generic_geometry(c, geo_fn, "events", n, m * S, &grid, &block, &lds);
-            if (r != MCGP_OK) return r;
-            const uint64_t n_batches = (m + block - 1) / block;
-            const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + S - 1) / S);
-            if (done == 0) { grid0 = gx * S; block0 = block; }
-            hipLaunchKernelGGL(kernel, dim3(gx, S), dim3(block), lds, nullptr, d_kp, d_st, d_sc, d_sl, d_el, m,
-                               sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, d_evs,
-                               (uint32_t)n_batches);
-            HIP_TRY(hipGetLastError());
-            // its counts, before the next chunk overwrites the staging
-            if (count_delta || events_out) {
-                const uint64_t tiles = (m + mcgp::kEventsCountBlock - 1) / mcgp::kEventsCountBlock;
-                const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / S));
-                hipLaunchKernelGGL(mcgp::events_count, dim3((uint32_t)gxc, S), dim3(mcgp::kEventsCountBlock), 0, nullptr,
-                                   d_stage, d_evs, m, n, (uint32_t)L, count_delta ? d_delta : nullptr,
-                                   events_out ? d_ev : nullptr);
-                HIP_TRY(hipGetLastError());
-            }
-            if (orders_out) {
-                HIP_TRY(hipMemcpy(pos_back.data(), d_stage, (size_t)S * m * n, hipMemcpyDeviceToHost));
-                for (uint32_t si = 0; si < S; ++si)
-                    for (uint64_t i = 0; i < m; ++i) {
-                        const uint8_t *pos = pos_back.data() + ((size_t)si * m + i) * n;
-                        uint8_t *ord = orders.data() + ((size_t)si * n_sims + done + i) * n;
-                        for (uint32_t d = 0; d < n; ++d) ord[pos[d]] = (uint8_t)d;
-                    }
-            }
-        }
-        note_launch(c, grid0, block0, lds, "mcgp::race_events_kernel");     // the launch shape of the first (fullest) chunk
-        return counts.download(d_hist, cells);
-    });
-    if (rc != MCGP_OK) return rc;
-    if (delta_out) {
-        // the centre bin (no change) of every (scenario, driver) is what the other bins leave of n_sims
-        unsigned long long *b = counts.v.data() + c_hist;
-        for (size_t row = 0; row < (size_t)S * n; ++row) {
-            unsigned long long rest = 0;
-            for (size_t j = 0; j < w; ++j) rest += j == n - 1 ? 0ull : b[row * w + j];
-            b[row * w + n - 1] = n_sims - rest;
-        }
-    }
-    counts.add_to({{hist_out, c_hist}, {delta_out, c_delta}, {events_out, c_ev}});
-    if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
-    return MCGP_OK;
+    const uint8_t *d_el = nullptr;
+    uint32_t *d_evs = nullptr;              // [S][m] packed event counts of a chunk's simulations
+    ScenarioKind k = {"events run", "events", "mcgp::race_events_kernel", reinterpret_cast<KernelFn>(kernel)};
+    k.count_name = "event_count", k.item_count = event_count, k.items_name = "events", k.items = events;
+    k.check_counts = [&](uint64_t *n_events) { return mcgp::check_event_counts(n_scenarios, event_count, n_events); };
+    k.pack = [&](int first_lap, bool resumed) {
+        return mcgp::pack_events(n_scenarios, event_count, events, cfg->total_laps, first_lap, resumed, &event_laps);
+    };
+    // positions and event counts of a chunk share the strategy call's budget: n + 4 bytes per scenario and simulation
+    k.sim_bytes = (size_t)n + 4;
+    k.regions = [&](Layout &ws, uint64_t chunk) {
+        ws.add(&d_evs, (size_t)n_scenarios * chunk);
+        ws.add(&d_el, event_laps.size(), event_laps.data());
+    };
+    k.race = [&](const ScenarioChunk &l) {
+        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_el, l.m,
+                           l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, d_evs, l.n_batches);
+    };
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *d_ev) {
+        const uint64_t tiles = (l.m + mcgp::kEventsCountBlock - 1) / mcgp::kEventsCountBlock;
+        const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
+        hipLaunchKernelGGL(mcgp::events_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kEventsCountBlock), 0, nullptr, l.stage,
+                           d_evs, l.m, n, (uint32_t)cfg->total_laps, d_delta, d_ev);
+    };
+    k.extra_out = events_out;               // events [S][3][L + 1]
+    k.extra_cells = [](size_t S, size_t, size_t L) { return S * 3 * (L + 1); };
+    return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
+                         hist_out, delta_out, orders_out, k);
 }
 
 int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
@@ -2144,8 +2069,8 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     // ---- every argument is checked before any device is looked up
     if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
     if (!lap_gap_out) return fail(MCGP_E_BAD_ARG, "lap_gap_out is NULL");
-    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
-    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    int rc = check_source(grid_probs, state);
+    if (rc != MCGP_OK) return rc;
     if (n_edges < 1 || n_edges > mcgp::kMaxGapEdges) return fail(MCGP_E_BAD_ARG, "n_edges must be in [1, 63]");
     if (!edges) return fail(MCGP_E_BAD_ARG, "edges is NULL");
     for (uint32_t i = 0; i < n_edges; ++i) {
@@ -2160,8 +2085,7 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     if (!n_pairs && pair_out) return fail(MCGP_E_BAD_ARG, "pair_out must be NULL when n_pairs is 0");
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, grid_probs, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "gaps run");
+    rc = build_params_32(cfg, drv, grid_probs, n, "gaps run", &kp);
     if (rc != MCGP_OK) return rc;
     for (uint32_t p = 0; p < n_pairs; ++p) {
         const uint32_t a = pairs[2 * p], b = pairs[2 * p + 1];
@@ -2171,19 +2095,17 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     }
     const uint32_t L = (uint32_t)cfg->total_laps;
     mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string err = mcgp::pack_race_state(*state, 0, n, (int)L, &st);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-        st.sim_offset = 0;          // (race_gaps_kernel takes the ids from its sim_offset argument)
-    }
+    rc = pack_state(state, n, (int)L, 0, &st);
+    if (rc != MCGP_OK) return rc;
     if (n_sims == 0) return MCGP_OK;
     const uint32_t lap0 = state ? (uint32_t)st.lap : 0u;       // laps lap0 + 1 .. L are recorded
     const uint32_t B = n_edges + 1, R = n + 1 + n_pairs;
     const uint32_t rows = (L - lap0) * R;
-    const size_t c_hist = (size_t)n * n, c_gap = (size_t)L * n * (B + 1), c_lead = (size_t)L * (B + 1),
-                 c_pair = (size_t)L * n_pairs * (2 * B + 1);
-    const size_t cells = c_hist + c_gap + c_lead + c_pair;
+    // hist [n][n] | lap_gap [L][n][B + 1] | lead [L][B + 1] | pair [L][n_pairs][2B + 1]
+    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n},
+                                           {lap_gap_out, (size_t)L * n * (B + 1)},
+                                           {lead_out, (size_t)L * (B + 1)},
+                                           {pair_out, (size_t)L * n_pairs * (2 * B + 1)}};
     Counts counts;
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         const auto kernel = state ? &mcgp::race_gaps_kernel<true> : &mcgp::race_gaps_kernel<false>;
@@ -2191,29 +2113,24 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
         // a race resumed after its last lap records nothing: one row's worth of staging keeps the sizes non-zero
         const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kGapsStageBytes, std::max<uint64_t>(rows, 1), n_sims);
         // workspace: staging of one chunk in rows of `stride` bytes (a multiple of 256: whole, aligned words for the
-        // counting kernel) | parameter block | state | edges | pairs | hist [n][n] | lap_gap [L][n][B + 1] |
-        // lead [L][B + 1] | pair [L][n_pairs][2B + 1]
+        // counting kernel) | parameter block | state | edges | pairs | the counts
         const uint64_t stride = (chunk + 255) / 256 * 256;
-        Layout ws;
-        const size_t o_stage = ws.add((size_t)std::max<uint32_t>(rows, 1) * stride), o_kp = ws.add(sizeof(kp));
-        const size_t o_st = ws.add(sizeof(st)), o_edges = ws.add(sizeof(double) * mcgp::kGapEdgeSlots);
-        const size_t o_pairs = ws.add(2 * (size_t)std::max<uint32_t>(n_pairs, 1)), o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
-        if (r != MCGP_OK) return r;
-        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
-        const double *d_edges = c.work.at<const double>(o_edges);
-        const uint8_t *d_pairs = c.work.at<const uint8_t>(o_pairs);
-        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
-        unsigned long long *d_gap = d_hist + c_hist, *d_lead = d_gap + c_gap, *d_pair = d_lead + c_lead;
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
         double edge_table[mcgp::kGapEdgeSlots];                 // the call's edges, then +inf (gaps.hip.h: gap_bin)
         for (uint32_t i = 0; i < mcgp::kGapEdgeSlots; ++i) edge_table[i] = i < n_edges ? edges[i] : HUGE_VAL;
-        HIP_TRY(hipMemcpy(c.work.at(o_edges), edge_table, sizeof(edge_table), hipMemcpyHostToDevice));
-        if (n_pairs) HIP_TRY(hipMemcpy(c.work.at(o_pairs), pairs, 2 * (size_t)n_pairs, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        uint8_t *d_stage;
+        const mcgp::KParams *d_kp;
+        const mcgp::ResumeState *d_st;
+        const double *d_edges;
+        const uint8_t *d_pairs;
+        Layout ws;
+        ws.add(&d_stage, (size_t)std::max<uint32_t>(rows, 1) * stride);
+        ws.add(&d_kp, 1, &kp);
+        ws.add(&d_st, 1, &st);
+        ws.add(&d_edges, mcgp::kGapEdgeSlots, edge_table);
+        ws.add(&d_pairs, 2 * (size_t)std::max<uint32_t>(n_pairs, 1), n_pairs ? pairs : nullptr);
+        ws.counts(segs);
+        const int r = ws.commit(c.work);
+        if (r != MCGP_OK) return r;
         // the counting kernel's columns: 4 x 256 bytes per value, up to 129 values (129 KiB of a CU's 160)
         const size_t count_lds = (size_t)(n_pairs ? 2 * B + 1 : B + 1) * mcgp::kGapsCountBlock * 4;
         if (count_lds > c.lds_per_block)
@@ -2224,31 +2141,23 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)c.lds_per_block));
         const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
-        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
-        for (uint64_t done = 0; done < n_sims; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            // the race: the generic kernel's block shape and LDS
-            r = generic_geometry(c, geo_fn, "gaps", n, m, &grid, &block, &lds);
-            if (r != MCGP_OK) return r;
-            if (done == 0) { grid0 = grid; block0 = block; }
-            const uint64_t n_batches = (m + block - 1) / block;
+        return staged_run(c, geo_fn, "gaps", "mcgp::race_gaps_kernel", n, 1, n_sims, chunk, ws, counts,
+                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_edges, n_edges, d_pairs, n_pairs,
-                               m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride,
-                               (uint32_t)n_batches);
+                               m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), ws.count(0), d_stage, stride,
+                               n_batches);
             HIP_TRY(hipGetLastError());
-            // its counts, before the next chunk overwrites the staging
             if (rows) {
                 hipLaunchKernelGGL(mcgp::gaps_count_rows, dim3((uint32_t)std::min<uint64_t>(rows, grid_cap)),
                                    dim3(mcgp::kGapsCountBlock), count_lds, nullptr, d_stage, stride, m, rows, n, n_pairs, B,
-                                   lap0, d_gap, d_lead, d_pair);
+                                   lap0, ws.count(1), ws.count(2), ws.count(3));
                 HIP_TRY(hipGetLastError());
             }
-        }
-        note_launch(c, grid0, block0, lds, "mcgp::race_gaps_kernel");       // the launch shape of the first (fullest) chunk
-        return counts.download(d_hist, cells);
+            return MCGP_OK;
+        });
     });
     if (rc != MCGP_OK) return rc;
-    counts.add_to({{hist_out, c_hist}, {lap_gap_out, c_gap}, {lead_out, c_lead}, {pair_out, c_pair}});
+    counts.add_to(segs);
     return MCGP_OK;
 }
 
@@ -2266,14 +2175,13 @@ int32_t mcgp_run_conditions(const mcgp_config *cfg, const mcgp_drivers *drv, con
     // ---- every argument is checked before any device is looked up
     if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
     if (!count_out) return fail(MCGP_E_BAD_ARG, "count_out is NULL");
-    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
-    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    int rc = check_source(grid_probs, state);
+    if (rc != MCGP_OK) return rc;
     if (n_conditions < 1 || n_conditions > mcgp::kMaxConditions) return fail(MCGP_E_BAD_ARG, "n_conditions must be in [1, 64]");
     if (!conditions) return fail(MCGP_E_BAD_ARG, "conditions is NULL");
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, grid_probs, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "conditions run");
+    rc = build_params_32(cfg, drv, grid_probs, n, "conditions run", &kp);
     if (rc != MCGP_OK) return rc;
     for (uint32_t ci = 0; ci < n_conditions; ++ci) {
         const mcgp_condition &cond = conditions[ci];
@@ -2294,67 +2202,53 @@ int32_t mcgp_run_conditions(const mcgp_config *cfg, const mcgp_drivers *drv, con
             if (at.lo > at.hi) return fail(MCGP_E_BAD_ARG, atom + ".lo must not be above .hi");
         }
     }
-    const uint32_t L = (uint32_t)cfg->total_laps;
     mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string err = mcgp::pack_race_state(*state, 0, n, (int)L, &st);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-        st.sim_offset = 0;          // (race_conditions_kernel takes the ids from its sim_offset argument)
-    }
+    rc = pack_state(state, n, cfg->total_laps, 0, &st);
+    if (rc != MCGP_OK) return rc;
     if (n_sims == 0) return MCGP_OK;
     const uint32_t C = n_conditions;
-    const size_t c_hist = (size_t)n * n, c_count = C, c_cond = cond_hist_out ? (size_t)C * n * n : 0;
-    const size_t cells = c_hist + c_count + c_cond;
+    // hist [n][n] | count [C] | cond_hist [C][n][n]
+    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n}, {count_out, C},
+                                           {cond_hist_out, cond_hist_out ? (size_t)C * n * n : 0}};
     Counts counts;
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         const auto kernel = state ? &mcgp::race_conditions_kernel<true> : &mcgp::race_conditions_kernel<false>;
         const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
         const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kConditionsStageBytes, (uint64_t)n + 8, n_sims);
         // workspace: staging of one chunk, n rows of `stride` bytes (a multiple of 256) then `stride` u64 masks |
-        // parameter block | state | condition table | hist [n][n] | count [C] | cond_hist [C][n][n]
+        // parameter block | state | condition table | the counts
         const uint64_t stride = (chunk + 255) / 256 * 256;
+        uint8_t *d_stage;
+        const mcgp::KParams *d_kp;
+        const mcgp::ResumeState *d_st;
+        const mcgp::Cond *d_cond;
         Layout ws;
-        const size_t o_stage = ws.add((size_t)(n + 8) * stride), o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st));
-        const size_t o_cond = ws.add(sizeof(mcgp::Cond) * C), o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
+        ws.add(&d_stage, (size_t)(n + 8) * stride);
+        ws.add(&d_kp, 1, &kp);
+        ws.add(&d_st, 1, &st);
+        ws.add(&d_cond, C, reinterpret_cast<const mcgp::Cond *>(conditions));
+        ws.counts(segs);
+        const int r = ws.commit(c.work);
         if (r != MCGP_OK) return r;
-        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
-        const mcgp::Cond *d_cond = c.work.at<const mcgp::Cond>(o_cond);
-        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
-        unsigned long long *d_count = d_hist + c_hist, *d_chist = cond_hist_out ? d_count + c_count : nullptr;
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_cond), conditions, sizeof(mcgp::Cond) * C, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)c.lds_per_block));
         const uint32_t groups = (C + mcgp::kCondGroup - 1) / mcgp::kCondGroup;
         const uint64_t grid_cap = std::max<uint64_t>(1, (uint64_t)c.cu_count * 8 / groups);
-        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0;
-        for (uint64_t done = 0; done < n_sims; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            // the race: the generic kernel's block shape and LDS
-            r = generic_geometry(c, geo_fn, "conditions", n, m, &grid, &block, &lds);
-            if (r != MCGP_OK) return r;
-            if (done == 0) { grid0 = grid; block0 = block; }
-            const uint64_t n_batches = (m + block - 1) / block;
+        return staged_run(c, geo_fn, "conditions", "mcgp::race_conditions_kernel", n, 1, n_sims, chunk, ws, counts,
+                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_cond, C, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, (uint32_t)n_batches);
+                               (uint32_t)seed, (uint32_t)(seed >> 32), ws.count(0), d_stage, stride, n_batches);
             HIP_TRY(hipGetLastError());
-            // its counts, before the next chunk overwrites the staging
             const uint64_t tiles = (m + mcgp::kCondCountBlock - 1) / mcgp::kCondCountBlock;
             hipLaunchKernelGGL(mcgp::conditions_count, dim3((uint32_t)std::min<uint64_t>(tiles, grid_cap), groups),
-                               dim3(mcgp::kCondCountBlock), 0, nullptr, d_stage, stride, m, n, C, d_count, d_chist);
+                               dim3(mcgp::kCondCountBlock), 0, nullptr, d_stage, stride, m, n, C, ws.count(1),
+                               cond_hist_out ? ws.count(2) : nullptr);
             HIP_TRY(hipGetLastError());
-        }
-        note_launch(c, grid0, block0, lds, "mcgp::race_conditions_kernel");     // the launch shape of the first (fullest) chunk
-        return counts.download(d_hist, cells);
+            return MCGP_OK;
+        });
     });
     if (rc != MCGP_OK) return rc;
-    counts.add_to({{hist_out, c_hist}, {count_out, c_count}, {cond_hist_out, c_cond}});
+    counts.add_to(segs);
     return MCGP_OK;
 }
 
@@ -2369,51 +2263,42 @@ int32_t mcgp_run_stints(const mcgp_config *cfg, const mcgp_drivers *drv, const d
     // ---- every argument is checked before any device is looked up
     if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
     if (!stop_lap_out) return fail(MCGP_E_BAD_ARG, "stop_lap_out is NULL");
-    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
-    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    int rc = check_source(grid_probs, state);
+    if (rc != MCGP_OK) return rc;
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, grid_probs, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "stints run");
+    rc = build_params_32(cfg, drv, grid_probs, n, "stints run", &kp);
     if (rc != MCGP_OK) return rc;
     const uint32_t L = (uint32_t)cfg->total_laps;
     mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string err = mcgp::pack_race_state(*state, 0, n, (int)L, &st);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-        st.sim_offset = 0;          // (race_stints_kernel takes the ids from its sim_offset argument)
-    }
+    rc = pack_state(state, n, (int)L, 0, &st);
+    if (rc != MCGP_OK) return rc;
     if (n_sims == 0) return MCGP_OK;
-    const size_t c_hist = (size_t)n * n, c_lap = (size_t)n * mcgp::kStintStops * (L + 1);
-    const size_t c_sp = stops_pos_out ? (size_t)n * (mcgp::kStintStops + 1) * n : 0;
-    const size_t c_seq = seq_out ? (size_t)n * mcgp::kStintSeqCodes : 0;
-    const size_t cells = c_hist + c_lap + c_sp + c_seq;
+    // hist [n][n] | stop_lap [n][4][L + 1] | stops_pos [n][5][n] | seq [n][1296]
+    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n},
+                                           {stop_lap_out, (size_t)n * mcgp::kStintStops * (L + 1)},
+                                           {stops_pos_out, stops_pos_out ? (size_t)n * (mcgp::kStintStops + 1) * n : 0},
+                                           {seq_out, seq_out ? (size_t)n * mcgp::kStintSeqCodes : 0}};
     Counts counts;
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         const auto kernel = state ? &mcgp::race_stints_kernel<true> : &mcgp::race_stints_kernel<false>;
         const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
         const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kStintsStageBytes, 9ull * n, n_sims);
         // workspace: staging of one chunk, n rows of `stride` u64 records then n rows of `stride` position bytes (stride
-        // a multiple of 256) | parameter block | state | hist [n][n] | stop_lap [n][4][L + 1] | stops_pos [n][5][n] |
-        // seq [n][1296]
+        // a multiple of 256) | parameter block | state | the counts
         const uint64_t stride = (chunk + 255) / 256 * 256;
+        uint64_t *d_rec;
+        uint8_t *d_pos;
+        const mcgp::KParams *d_kp;
+        const mcgp::ResumeState *d_st;
         Layout ws;
-        const size_t o_rec = ws.add((size_t)n * stride * 8), o_pos = ws.add((size_t)n * stride);
-        const size_t o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st)), o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
+        ws.add(&d_rec, (size_t)n * stride);
+        ws.add(&d_pos, (size_t)n * stride);
+        ws.add(&d_kp, 1, &kp);
+        ws.add(&d_st, 1, &st);
+        ws.counts(segs);
+        const int r = ws.commit(c.work);
         if (r != MCGP_OK) return r;
-        uint64_t *d_rec = c.work.at<uint64_t>(o_rec);
-        uint8_t *d_pos = c.work.at<uint8_t>(o_pos);
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
-        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
-        unsigned long long *d_lap = d_hist + c_hist;
-        unsigned long long *d_sp = stops_pos_out ? d_lap + c_lap : nullptr;
-        unsigned long long *d_seq = seq_out ? d_lap + c_lap + c_sp : nullptr;
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
         // the counting kernel's histograms: 6.4 KiB at 60 laps and 20 cars, 21 KiB at 1000 laps
         const size_t count_lds = ((size_t)mcgp::kStintStops * (L + 1) + (size_t)(mcgp::kStintStops + 1) * n +
                                   mcgp::kStintSeqCodes) * 4;
@@ -2423,29 +2308,21 @@ int32_t mcgp_run_stints(const mcgp_config *cfg, const mcgp_drivers *drv, const d
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)c.lds_per_block));
         const uint64_t grid_cap = std::max<uint64_t>(1, (uint64_t)c.cu_count * 8 / n);
-        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0, lds0 = 0;
-        for (uint64_t done = 0; done < n_sims; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            // the race: the generic kernel's block shape and LDS
-            r = generic_geometry(c, geo_fn, "stints", n, m, &grid, &block, &lds);
-            if (r != MCGP_OK) return r;
-            if (done == 0) { grid0 = grid; block0 = block; lds0 = lds; }
-            const uint64_t n_batches = (m + block - 1) / block;
+        return staged_run(c, geo_fn, "stints", "mcgp::race_stints_kernel", n, 1, n_sims, chunk, ws, counts,
+                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_rec, d_pos, stride, (uint32_t)n_batches);
+                               (uint32_t)seed, (uint32_t)(seed >> 32), ws.count(0), d_rec, d_pos, stride, n_batches);
             HIP_TRY(hipGetLastError());
-            // its counts, before the next chunk overwrites the staging
             const uint64_t tiles = (m + mcgp::kStintsCountBlock - 1) / mcgp::kStintsCountBlock;
             hipLaunchKernelGGL(mcgp::stints_count, dim3((uint32_t)std::min<uint64_t>(tiles, grid_cap), n),
-                               dim3(mcgp::kStintsCountBlock), count_lds, nullptr, d_rec, d_pos, stride, m, n, L, d_lap, d_sp,
-                               d_seq);
+                               dim3(mcgp::kStintsCountBlock), count_lds, nullptr, d_rec, d_pos, stride, m, n, L, ws.count(1),
+                               stops_pos_out ? ws.count(2) : nullptr, seq_out ? ws.count(3) : nullptr);
             HIP_TRY(hipGetLastError());
-        }
-        note_launch(c, grid0, block0, lds0, "mcgp::race_stints_kernel");     // the launch shape of the first (fullest) chunk
-        return counts.download(d_hist, cells);
+            return MCGP_OK;
+        });
     });
     if (rc != MCGP_OK) return rc;
-    counts.add_to({{hist_out, c_hist}, {stop_lap_out, c_lap}, {stops_pos_out, c_sp}, {seq_out, c_seq}});
+    counts.add_to(segs);
     return MCGP_OK;
 }
 
@@ -2461,32 +2338,29 @@ int32_t mcgp_run_moves(const mcgp_config *cfg, const mcgp_drivers *drv, const do
     // ---- every argument is checked before any device is looked up
     if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
     if (!grid_fin_out) return fail(MCGP_E_BAD_ARG, "grid_fin_out is NULL");
-    if (state && grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs must be NULL when a state is given");
-    if (!state && !grid_probs) return fail(MCGP_E_BAD_ARG, "grid_probs is NULL (a run from the grid needs it)");
+    int rc = check_source(grid_probs, state);
+    if (rc != MCGP_OK) return rc;
     if (state && start_gain_out)
         return fail(MCGP_E_BAD_ARG, "start_gain_out must be NULL when a state is given (a start gain is from the grid)");
     std::vector<mcgp::KParams> kps(1);
     mcgp::KParams &kp = kps[0];
-    int rc = build_params(cfg, drv, grid_probs, n, &kp);
-    if (rc == MCGP_OK) rc = check_deviates_32(kp, "moves run");
+    rc = build_params_32(cfg, drv, grid_probs, n, "moves run", &kp);
     if (rc != MCGP_OK) return rc;
     const uint32_t L = (uint32_t)cfg->total_laps;
     mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string err = mcgp::pack_race_state(*state, 0, n, (int)L, &st);
-        if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
-        st.sim_offset = 0;          // (race_moves_kernel takes the ids from its sim_offset argument)
-    }
+    rc = pack_state(state, n, (int)L, 0, &st);
+    if (rc != MCGP_OK) return rc;
     if (n_sims == 0) return MCGP_OK;
     const uint32_t lap0 = state ? (uint32_t)st.lap : 1u;                    // the baseline row
-    const size_t c_hist = (size_t)n * n, c_gf = (size_t)n * n * n;
-    const size_t c_gain = start_gain_out ? (size_t)n * 2 * n : 0;
-    const size_t c_pass = passes_out ? (size_t)n * 4 * (mcgp::kMoveDriverCap + 1) : 0;
-    const size_t c_race = race_passes_out ? (size_t)mcgp::kMoveRaceCap + 1 : 0;
-    const size_t c_lap = lap_passes_out ? 2 * (size_t)(L + 1) : 0;
-    const size_t c_pair = pair_passes_out ? (size_t)n * n : 0;
-    const size_t cells = c_hist + c_gf + c_gain + c_pass + c_race + c_lap + c_pair;
+    // hist [n][n] | grid_fin [n][n][n] | start_gain [n][2n] | passes [n][4][128] | race_passes [1024] |
+    // lap_passes [L + 1][2] | pair_passes [n][n]: the optional ones take no cells when they are not wanted
+    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n},
+                                           {grid_fin_out, (size_t)n * n * n},
+                                           {start_gain_out, start_gain_out ? (size_t)n * 2 * n : 0},
+                                           {passes_out, passes_out ? (size_t)n * 4 * (mcgp::kMoveDriverCap + 1) : 0},
+                                           {race_passes_out, race_passes_out ? (size_t)mcgp::kMoveRaceCap + 1 : 0},
+                                           {lap_passes_out, lap_passes_out ? 2 * (size_t)(L + 1) : 0},
+                                           {pair_passes_out, pair_passes_out ? (size_t)n * n : 0}};
     const bool walk = passes_out || race_passes_out || lap_passes_out || pair_passes_out;
     Counts counts;
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
@@ -2495,29 +2369,23 @@ int32_t mcgp_run_moves(const mcgp_config *cfg, const mcgp_drivers *drv, const do
         const uint64_t rows = ((uint64_t)L + 2) * n;
         const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kMovesStageBytes, rows, n_sims);
         // workspace: staging of one chunk, (L + 2) n rows of `stride` bytes (a multiple of 256) | every car's packed
-        // pass counts, n rows of `stride` u32 (only if passes_out) | parameter block | state | hist [n][n] | grid_fin
-        // [n][n][n] | start_gain [n][2n] | passes [n][4][128] | race_passes [1024] | lap_passes [L + 1][2] |
-        // pair_passes [n][n]
+        // pass counts, n rows of `stride` u32 (only if passes_out) | parameter block | state | the counts
         const uint64_t stride = (chunk + 255) / 256 * 256;
+        uint8_t *d_stage;
+        uint32_t *d_tot;
+        const mcgp::KParams *d_kp;
+        const mcgp::ResumeState *d_st;
         Layout ws;
-        const size_t o_stage = ws.add((size_t)rows * stride), o_tot = ws.add(passes_out ? (size_t)n * stride * 4 : 0);
-        const size_t o_kp = ws.add(sizeof(kp)), o_st = ws.add(sizeof(st)), o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
+        ws.add(&d_stage, (size_t)rows * stride);
+        ws.add(&d_tot, passes_out ? (size_t)n * stride : 0);
+        ws.add(&d_kp, 1, &kp);
+        ws.add(&d_st, 1, &st);
+        ws.counts(segs);
+        const int r = ws.commit(c.work);
         if (r != MCGP_OK) return r;
-        uint8_t *d_stage = c.work.at<uint8_t>(o_stage);
-        uint32_t *d_tot = passes_out ? c.work.at<uint32_t>(o_tot) : nullptr;
-        const mcgp::KParams *d_kp = c.work.at<const mcgp::KParams>(o_kp);
-        const mcgp::ResumeState *d_st = c.work.at<const mcgp::ResumeState>(o_st);
-        unsigned long long *d_hist = c.work.at<unsigned long long>(o_cnt);
-        unsigned long long *d_gf = d_hist + c_hist;
-        unsigned long long *d_gain = start_gain_out ? d_gf + c_gf : nullptr;
-        unsigned long long *d_pass = passes_out ? d_gf + c_gf + c_gain : nullptr;
-        unsigned long long *d_race = race_passes_out ? d_gf + c_gf + c_gain + c_pass : nullptr;
-        unsigned long long *d_lap = lap_passes_out ? d_gf + c_gf + c_gain + c_pass + c_race : nullptr;
-        unsigned long long *d_pair = pair_passes_out ? d_gf + c_gf + c_gain + c_pass + c_race + c_lap : nullptr;
-        HIP_TRY(hipMemcpy(c.work.at(o_kp), &kp, sizeof(kp), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.work.at(o_st), &st, sizeof(st), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 8, nullptr));
+        if (!passes_out) d_tot = nullptr;
+        // a segment that is not wanted is NULL for the counting kernels
+        auto wanted = [&](size_t i) { return segs[i].dst ? ws.count(i) : nullptr; };
         // moves_count_laps' tables and sums: 29 KiB at 60 laps and 20 cars, 52 KiB at 1000 laps and 32 cars
         const size_t laps_lds = 9 * (size_t)n * mcgp::kMovesLapsBlock +
                                 ((size_t)n * n + 2 * (size_t)(L + 1) + mcgp::kMoveRaceCap + 1) * 4;
@@ -2527,39 +2395,30 @@ int32_t mcgp_run_moves(const mcgp_config *cfg, const mcgp_drivers *drv, const do
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)c.lds_per_block));
         const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
-        uint32_t grid = 0, block = 0, lds = 0, grid0 = 0, block0 = 0, lds0 = 0;
-        for (uint64_t done = 0; done < n_sims; done += chunk) {
-            const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
-            // the race: the generic kernel's block shape and LDS
-            r = generic_geometry(c, geo_fn, "moves", n, m, &grid, &block, &lds);
-            if (r != MCGP_OK) return r;
-            if (done == 0) { grid0 = grid; block0 = block; lds0 = lds; }
-            const uint64_t n_batches = (m + block - 1) / block;
+        return staged_run(c, geo_fn, "moves", "mcgp::race_moves_kernel", n, 1, n_sims, chunk, ws, counts,
+                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, (uint32_t)n_batches);
+                               (uint32_t)seed, (uint32_t)(seed >> 32), ws.count(0), d_stage, stride, n_batches);
             HIP_TRY(hipGetLastError());
-            // its counts, before the next chunk overwrites the staging
             if (walk) {
                 // a block takes at most kMovesBlockShare simulations, so that its u32 sums cannot wrap (moves.hip.h)
                 const uint64_t tiles = (m + mcgp::kMovesLapsBlock - 1) / mcgp::kMovesLapsBlock;
                 const uint64_t per_block = mcgp::kMovesBlockShare / mcgp::kMovesLapsBlock;
                 const uint64_t gx = std::min<uint64_t>(tiles, std::max<uint64_t>(grid_cap, (tiles + per_block - 1) / per_block));
                 hipLaunchKernelGGL(mcgp::moves_count_laps, dim3((uint32_t)gx), dim3(mcgp::kMovesLapsBlock), laps_lds, nullptr,
-                                   d_stage, stride, m, n, L, lap0, d_tot, d_race, d_lap, d_pair);
+                                   d_stage, stride, m, n, L, lap0, d_tot, wanted(4), wanted(5), wanted(6));
                 HIP_TRY(hipGetLastError());
             }
             const uint64_t dtiles = (m + mcgp::kMovesDriversBlock - 1) / mcgp::kMovesDriversBlock;
             const uint64_t gx = std::max<uint64_t>(1, std::min<uint64_t>(dtiles, grid_cap / n));
             hipLaunchKernelGGL(mcgp::moves_count_drivers, dim3((uint32_t)gx, n), dim3(mcgp::kMovesDriversBlock), 0, nullptr,
-                               d_stage, d_tot, stride, m, n, L, d_gf, d_gain, d_pass);
+                               d_stage, d_tot, stride, m, n, L, ws.count(1), wanted(2), wanted(3));
             HIP_TRY(hipGetLastError());
-        }
-        note_launch(c, grid0, block0, lds0, "mcgp::race_moves_kernel");      // the launch shape of the first (fullest) chunk
-        return counts.download(d_hist, cells);
+            return MCGP_OK;
+        });
     });
     if (rc != MCGP_OK) return rc;
-    counts.add_to({{hist_out, c_hist}, {grid_fin_out, c_gf}, {start_gain_out, c_gain}, {passes_out, c_pass},
-                   {race_passes_out, c_race}, {lap_passes_out, c_lap}, {pair_passes_out, c_pair}});
+    counts.add_to(segs);
     return MCGP_OK;
 }
 

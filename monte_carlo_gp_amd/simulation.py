@@ -183,6 +183,48 @@ def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _optr(a):
+    """An output buffer as the C ABI takes it: uint64 counts or uint8 finishing orders; None (not wanted) is NULL."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8 if a.dtype == np.uint8 else C.c_uint64))
+
+
+def _count_arrays(result):
+    """The count arrays of a result object, by field name."""
+    return {k: v for k, v in vars(result).items() if isinstance(v, np.ndarray)}
+
+
+class _Source:
+    """Where a call's races start, as RaceSimulator._source resolved it: from the grid (grid_probs) or from a mid-race
+    RaceState (state), for `drivers` in index order.  The grid matrix and the state's arrays are built on first use, so
+    that a call with nothing to run builds (and checks) neither."""
+
+    def __init__(self, grid_probs, state, drivers, total_laps):
+        self.grid_probs, self.state, self.drivers, self.total_laps = grid_probs, state, drivers, int(total_laps)
+        self._arrays = self._keep = self._c_args = None
+
+    def first_lap(self, from_grid=2):
+        """The first lap the call runs: `from_grid` (2: the first lap with a pit step), or the one after the state's."""
+        return from_grid if self.state is None else int(self.state.lap) + 1
+
+    @property
+    def arrays(self):
+        """The state's arrays in driver order (RaceState.arrays; None from the grid)."""
+        if self.state is not None and self._arrays is None:
+            self._arrays = self.state.arrays(self.drivers, self.total_laps)
+        return self._arrays
+
+    def c_args(self):
+        """The entry points' (grid_probs, state) arguments: the matrix and NULL, or NULL and the mcgp_race_state."""
+        if self._c_args is None:
+            if self.state is None:
+                self._keep = RaceSimulator._grid_matrix({str(k): v for k, v in self.grid_probs.items()}, self.drivers)
+                self._c_args = (_dptr(self._keep), None)
+            else:
+                self._keep = self.state.c_struct(self.arrays)
+                self._c_args = (None, C.byref(self._keep))
+        return self._c_args
+
+
 class _Problem:
     """run_monte_carlo's arguments resolved to the dense tables of include/mcgp.h."""
 
@@ -311,6 +353,129 @@ class RaceSimulator:
         return _Problem(self.config, drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates,
                         track_condition, self.set_pop, self.deviates)
 
+    def _source(self, grid_probs, state, drivers):
+        """The start of a call's races and its drivers (default: grid_probs' keys, or the state's grid order)."""
+        if (grid_probs is None) == (state is None):
+            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
+        if drivers is None:
+            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
+        drivers = [str(d) for d in drivers]
+        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
+            raise ValueError('drivers must be the keys of grid_probs')
+        return _Source(grid_probs, state, drivers, self.config.total_laps)
+
+    def _run_counted(self, n_simulations, drivers, alloc, call, orders_axis=None):
+        """The sharded run behind every run_* method.  alloc(count) -> {name: buffer} makes one shard's outputs:
+        np.uint64 counts, under 'orders' the np.uint8 finishing orders of `count` simulations, None for an output that
+        is not wanted.  call(lib, device, offset, count, buffers) makes the C call for simulations offset .. offset +
+        count - 1 of the run and returns its code.  Returns, by name, the shards' counts added up (np.int64), their
+        orders one after the other along `orders_axis`, and None where alloc gave None -- for n_simulations <= 0 what
+        alloc(0) gives, without a call.  Sets last_histogram (the 'hist' counts) and last_drivers."""
+        if n_simulations <= 0:
+            parts = [alloc(0)]
+        else:
+            lib = N.lib()
+
+            def shard(device, offset, count):
+                bufs = alloc(int(count))
+                rc = call(lib, device, int(offset), int(count), bufs)
+                # (mcgp_last_error is thread-local: read it on the thread that made the call)
+                return bufs, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+
+            parts = [bufs for bufs, _, _ in self._run_sharded(shard, n_simulations)]
+        total = {}
+        for k, first in parts[0].items():
+            if first is None:
+                total[k] = None
+            elif k == 'orders':
+                total[k] = np.concatenate([p[k] for p in parts], axis=orders_axis)
+            else:
+                total[k] = np.sum([p[k] for p in parts], axis=0, dtype=np.uint64).astype(np.int64)
+        self.last_histogram, self.last_drivers = total['hist'], drivers
+        return total
+
+    @staticmethod
+    def _entry_call(entry, prob, head, sim_offset, seed64, outs):
+        """_run_counted's `call` for an entry point of the usual shape: lib.<entry>(cfg, drivers, *head, n_sims,
+        sim_offset, seed, device, *outputs), the outputs being the buffers named by `outs` (None: NULL)."""
+        def call(lib, device, offset, count, bufs):
+            return getattr(lib, entry)(C.byref(prob.cfg), C.byref(prob.drv), *head, count, int(sim_offset) + offset,
+                                       seed64, device, *[_optr(bufs.get(k)) for k in outs])
+        return call
+
+    def _run_entry(self, entry, n_simulations, drivers, race, seed, sim_offset, head, alloc, outs):
+        """One race counted by lib.<entry>: _run_counted over _entry_call.  race: _problem's arguments after the drivers;
+        head(n): the entry point's arguments between the driver tables and n_sims.  Without drivers or simulations
+        nothing is resolved, built or called: the counts are alloc(0)'s."""
+        if not drivers or n_simulations <= 0:
+            return self._run_counted(0, drivers, alloc, None)
+        prob = self._problem(drivers, *race)
+        call = self._entry_call(entry, prob, head(prob.n), sim_offset, self._resolve_seed(seed), outs)
+        return self._run_counted(n_simulations, drivers, alloc, call)
+
+    def _pack_plans(self, names, plans_of, src, check_compounds, items_of=None, pack_items=None):
+        """The scenarios' pit plans as mcgp_pit_plan structs with their count per scenario, and the items of the call's
+        own kind likewise, through pack_items(name, items, index) -> [struct]: scenario by scenario, plans first.
+        check_compounds: the two-compound rule holds for every plan."""
+        index = {d: i for i, d in enumerate(src.drivers)}
+        counts, c_plans, item_counts, c_items = [], [], [], []
+        for name in names:
+            plans = plans_of.get(name, [])
+            for plan in plans:
+                if str(plan.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {plan.driver!r} is not one of the drivers')
+                if check_compounds:
+                    used = None
+                    if src.arrays is not None:
+                        used = {c for j, c in enumerate(N.COMPOUNDS)
+                                if (int(src.arrays['used_compounds'][index[str(plan.driver)]]) >> j) & 1}
+                    check_two_compounds(plan, used, name)
+                c_plans.append(plan.c_struct(index, from_state=src.state is not None))
+            counts.append(len(plans))
+            if pack_items is not None:
+                packed = pack_items(name, items_of.get(name, []), index)
+                c_items += packed
+                item_counts.append(len(packed))
+        return counts, c_plans, item_counts, c_items
+
+    def _run_scenarios(self, entry, result, label, n_simulations, items, strategies, race, grid_probs, state, seed,
+                       sim_offset, drivers, return_orders, allow_single_compound, item_type=None, pack_items=None,
+                       extra=None):
+        """run_strategies, run_penalties and run_events: the race under named scenarios of pit plans (`strategies`) and,
+        for the latter two, of the call's own `items` ({name: [item]}; their names come first).  pack_items: see
+        _pack_plans, its structs are `item_type`s; extra = (name, shape(S, n, L)): the kind's own count array, behind
+        hist and delta among the outputs; result: the result class; label: the dicts' names for the message."""
+        src = self._source(grid_probs, state, drivers)
+        strategies = strategies or {}
+        first = strategies if items is None else items
+        names = [str(k) for k in first.keys()] + [str(k) for k in strategies.keys() if str(k) not in
+                                                  {str(j) for j in first.keys()}]
+        if not 1 <= len(names) <= N.MAX_SCENARIOS:
+            raise ValueError(f'{label}: 1 to {N.MAX_SCENARIOS} scenarios, got {len(names)}')
+        drivers = src.drivers
+        prob = self._problem(drivers, *race)
+        n, L, S = prob.n, int(self.config.total_laps), len(names)
+        src.arrays                                   # (a bad state is reported before a bad plan)
+        counts, c_plans, item_counts, c_items = self._pack_plans(
+            names, {str(k): list(v) for k, v in strategies.items()}, src, not allow_single_compound and race[-1] == 'dry',
+            {str(k): list(v) for k, v in (items or {}).items()}, pack_items)
+        head = src.c_args() + (n, S, (C.c_uint32 * S)(*counts), (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans))
+        if pack_items is not None:
+            head += ((C.c_uint32 * S)(*item_counts), (item_type * max(len(c_items), 1))(*c_items))
+        n_simulations = max(int(n_simulations), 0)
+        seed64 = self._resolve_seed(seed)
+        if not hasattr(N.lib(), entry):
+            raise N.McgpError(-1, f'the loaded library does not export {entry}')
+        shapes = dict(hist=(S, n, n), delta=(S, n, 2 * n - 1), **({extra[0]: extra[1](S, n, L)} if extra else {}))
+
+        def alloc(count):
+            return dict({k: np.zeros(shape, np.uint64) for k, shape in shapes.items()},
+                        orders=np.zeros((S, count, n), np.uint8) if return_orders else None)
+
+        total = self._run_counted(n_simulations, drivers, alloc,
+                                  self._entry_call(entry, prob, head, sim_offset, seed64, list(shapes) + ['orders']), 1)
+        return result(names=names, drivers=drivers, n_simulations=n_simulations, **total)
+
     # ------------------------------------------------------------------ reference surface
     def run_monte_carlo(
         self,
@@ -341,21 +506,13 @@ class RaceSimulator:
         g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers)
         orders = np.zeros((n_simulations, n), np.uint8) if return_orders else None
         seed64 = self._resolve_seed(seed)
-        lib = N.lib()
 
-        def run_shard(device, offset, count):
-            h = np.zeros((n, n), np.uint64)
+        def call(lib, device, offset, count, bufs):
             o = orders[offset:offset + count] if return_orders else None       # contiguous rows of the caller's buffer
-            rc = lib.mcgp_run(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g), n, int(count), int(sim_offset) + int(offset),
-                              seed64, device, h.ctypes.data_as(C.POINTER(C.c_uint64)),
-                              o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
-            # (mcgp_last_error is thread-local: read it on the thread that made the call)
-            return h, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+            return lib.mcgp_run(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g), n, count, int(sim_offset) + offset, seed64,
+                                device, _optr(bufs['hist']), _optr(o))
 
-        parts = self._run_sharded(run_shard, n_simulations)
-        hist = np.sum([h for h, _, _ in parts], axis=0, dtype=np.uint64)
-        self.last_histogram = hist.astype(np.int64)
-        self.last_drivers = drivers
+        self._run_counted(n_simulations, drivers, lambda count: dict(hist=np.zeros((n, n), np.uint64)), call)
         result = histogram_to_probs(self.last_histogram, drivers, n_simulations)
         return (result, orders) if return_orders else result
 
@@ -381,31 +538,15 @@ class RaceSimulator:
         n = len(drivers)
         n_simulations = int(n_simulations)
         want_podium = bool(podiums) and n >= 3
-        if not drivers or n_simulations <= 0:
-            z = np.zeros((n, n), np.int64)
-            self.last_histogram, self.last_drivers = z, drivers
-            return MatchupResult(drivers=drivers, n_simulations=max(n_simulations, 0), hist=z, ahead=z.copy(),
-                                 podium=np.zeros((n, n, n), np.int64) if want_podium else None)
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers)
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
-
-        def run_shard(device, offset, count):
-            h, a = np.zeros((n, n), np.uint64), np.zeros((n, n), np.uint64)
-            p = np.zeros((n, n, n), np.uint64) if want_podium else None
-            rc = lib.mcgp_run_matchups(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g), n, int(count),
-                                       int(sim_offset) + int(offset), seed64, device, u64(h), u64(a),
-                                       u64(p) if want_podium else None)
-            return (h, a, p), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([r[k] for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        self.last_histogram = total(0)
-        self.last_drivers = drivers
-        return MatchupResult(drivers=drivers, n_simulations=n_simulations, hist=self.last_histogram, ahead=total(1),
-                             podium=total(2) if want_podium else None)
+        src = _Source(grid_probs, None, drivers, self.config.total_laps)
+        total = self._run_entry(
+            'mcgp_run_matchups', n_simulations, drivers,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), seed, sim_offset,
+            lambda n: (src.c_args()[0], n),
+            lambda count: dict(hist=np.zeros((n, n), np.uint64), ahead=np.zeros((n, n), np.uint64),
+                               podium=np.zeros((n, n, n), np.uint64) if want_podium else None),
+            ['hist', 'ahead', 'podium'])
+        return MatchupResult(drivers=drivers, n_simulations=max(n_simulations, 0), **total)
 
     def run_trace(
         self,
@@ -426,30 +567,14 @@ class RaceSimulator:
         drivers = [str(d) for d in grid_probs.keys()]
         n, L = len(drivers), int(self.config.total_laps)
         n_simulations = int(n_simulations)
-        if not drivers or n_simulations <= 0:
-            self.last_histogram, self.last_drivers = np.zeros((n, n), np.int64), drivers
-            return TraceResult.empty(drivers, L, max(n_simulations, 0))
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers)
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
-
-        def run_shard(device, offset, count):
-            out = TraceResult.empty(drivers, L, count, dtype=np.uint64)
-            rc = lib.mcgp_run_trace(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g), n, int(count),
-                                    int(sim_offset) + int(offset), seed64, device, u64(out.hist), u64(out.lap_pos),
-                                    u64(out.laps_led), u64(out.stops), u64(out.fastest), u64(out.events))
-            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([getattr(r, k) for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        res = TraceResult(drivers=drivers, n_simulations=n_simulations, total_laps=L, hist=total('hist'),
-                          lap_pos=total('lap_pos'), laps_led=total('laps_led'), stops=total('stops'),
-                          fastest=total('fastest'), events=total('events'))
-        self.last_histogram = res.hist
-        self.last_drivers = drivers
-        return res
+        src = _Source(grid_probs, None, drivers, L)
+        total = self._run_entry(
+            'mcgp_run_trace', n_simulations, drivers,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), seed, sim_offset,
+            lambda n: (src.c_args()[0], n),
+            lambda count: _count_arrays(TraceResult.empty(drivers, L, count, dtype=np.uint64)),
+            ['hist', 'lap_pos', 'laps_led', 'stops', 'fastest', 'events'])
+        return TraceResult(drivers=drivers, n_simulations=max(n_simulations, 0), total_laps=L, **total)
 
     def run_from_state(
         self,
@@ -499,25 +624,23 @@ class RaceSimulator:
                 return res, np.zeros((0, n) if single else (S, 0, n), np.uint8)
             return res
         seed64 = self._resolve_seed(seed)
-        lib = N.lib()
 
-        def run_shard(device, offset, count):
-            h = np.zeros((S, n, n), np.uint64)
-            o = np.zeros((S, count, n), np.uint8) if return_orders else None
-            so = (C.c_uint64 * S)(*[x + int(offset) for x in offsets])
-            rc = lib.mcgp_run_from_state(C.byref(prob.cfg), C.byref(prob.drv), n, S, c_states, int(count), so, seed64,
-                                         device, h.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                         o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
-            return (h, o), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+        def alloc(count):
+            return dict(hist=np.zeros((S, n, n), np.uint64),
+                        orders=np.zeros((S, count, n), np.uint8) if return_orders else None)
 
-        parts = self._run_sharded(run_shard, n_simulations)
-        hist = np.sum([h for (h, _), _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        self.last_histogram = hist[0] if single else hist
-        self.last_drivers = drivers
+        def call(lib, device, offset, count, bufs):
+            so = (C.c_uint64 * S)(*[x + offset for x in offsets])
+            return lib.mcgp_run_from_state(C.byref(prob.cfg), C.byref(prob.drv), n, S, c_states, count, so, seed64, device,
+                                           _optr(bufs['hist']), _optr(bufs['orders']))
+
+        total = self._run_counted(n_simulations, drivers, alloc, call, 1)
+        hist, orders = total['hist'], total['orders']
+        if single:
+            self.last_histogram = hist[0]
         probs = [histogram_to_probs(hist[s], drivers, n_simulations) for s in range(S)]
         res = probs[0] if single else probs
         if return_orders:
-            orders = np.concatenate([o for (_, o), _, _ in parts], axis=1)
             return res, (orders[0] if single else orders)
         return res
 
@@ -547,66 +670,10 @@ class RaceSimulator:
         grid, the retirements and the race events.  On a dry track a plan that cannot use two dry compounds raises
         ValueError unless allow_single_compound.  32-bit deviates only; same seed rules and device sharding as
         run_monte_carlo.  last_histogram: [S, n, n]."""
-        if (grid_probs is None) == (state is None):
-            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
-        names = [str(k) for k in strategies.keys()]
-        if not 1 <= len(names) <= N.MAX_SCENARIOS:
-            raise ValueError(f'strategies: 1 to {N.MAX_SCENARIOS} scenarios, got {len(names)}')
-        if drivers is None:
-            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
-        drivers = [str(d) for d in drivers]
-        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
-            raise ValueError('drivers must be the keys of grid_probs')
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        n, L = prob.n, int(self.config.total_laps)
-        arrays = state.arrays(drivers, L) if state is not None else None
-        index = {d: i for i, d in enumerate(drivers)}
-        counts, c_plans = [], []
-        for name in names:
-            plans = list(strategies[name])
-            for plan in plans:
-                if str(plan.driver) not in index:
-                    raise ValueError(f'scenario {name!r}: {plan.driver!r} is not one of the drivers')
-                if not allow_single_compound and track_condition == 'dry':
-                    used = None
-                    if arrays is not None:
-                        used = {c for j, c in enumerate(N.COMPOUNDS)
-                                if (int(arrays['used_compounds'][index[str(plan.driver)]]) >> j) & 1}
-                    check_two_compounds(plan, used, name)
-                c_plans.append(plan.c_struct(index, from_state=state is not None))
-            counts.append(len(plans))
-        S = len(names)
-        plan_arr = (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans)
-        count_arr = (C.c_uint32 * S)(*counts)
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
-        c_state = state.c_struct(arrays) if state is not None else None
-        n_simulations = int(n_simulations)
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
-
-        def run_shard(device, offset, count):
-            h = np.zeros((S, n, n), np.uint64)
-            dl = np.zeros((S, n, 2 * n - 1), np.uint64)
-            o = np.zeros((S, count, n), np.uint8) if return_orders else None
-            rc = lib.mcgp_run_strategies(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
-                                         C.byref(c_state) if c_state is not None else None, n, S, count_arr, plan_arr,
-                                         int(count), int(sim_offset) + int(offset), seed64, device, u64(h), u64(dl),
-                                         o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
-            return (h, dl, o), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        if n_simulations <= 0:
-            parts = [((np.zeros((S, n, n), np.uint64), np.zeros((S, n, 2 * n - 1), np.uint64),
-                       np.zeros((S, 0, n), np.uint8) if return_orders else None), 0, '')]
-            n_simulations = 0
-        else:
-            parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([p[k] for p, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        res = StrategyResult(names=names, drivers=drivers, n_simulations=n_simulations, hist=total(0), delta=total(1),
-                             orders=np.concatenate([p[2] for p, _, _ in parts], axis=1) if return_orders else None)
-        self.last_histogram = res.hist
-        self.last_drivers = drivers
-        return res
+        return self._run_scenarios(
+            'mcgp_run_strategies', StrategyResult, 'strategies', n_simulations, None, strategies,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
+            drivers, return_orders, allow_single_compound)
 
     def run_penalties(
         self,
@@ -634,40 +701,8 @@ class RaceSimulator:
         them).  Everything else -- the remaining arguments, the plans' checks, the simulation ids and draws, the seed
         rules and the device sharding -- is run_strategies': a scenario without penalties gives exactly its counts.
         last_histogram: [S, n, n]."""
-        if (grid_probs is None) == (state is None):
-            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
-        strategies = strategies or {}
-        names = [str(k) for k in penalties.keys()] + [str(k) for k in strategies.keys() if str(k) not in
-                                                       {str(j) for j in penalties.keys()}]
-        pens_of = {str(k): list(v) for k, v in penalties.items()}
-        plans_of = {str(k): list(v) for k, v in strategies.items()}
-        if not 1 <= len(names) <= N.MAX_SCENARIOS:
-            raise ValueError(f'penalties / strategies: 1 to {N.MAX_SCENARIOS} scenarios, got {len(names)}')
-        if drivers is None:
-            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
-        drivers = [str(d) for d in drivers]
-        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
-            raise ValueError('drivers must be the keys of grid_probs')
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        n, L = prob.n, int(self.config.total_laps)
-        arrays = state.arrays(drivers, L) if state is not None else None
-        index = {d: i for i, d in enumerate(drivers)}
-        counts, c_plans, pen_counts, c_pens = [], [], [], []
-        for name in names:
-            plans = plans_of.get(name, [])
-            for plan in plans:
-                if str(plan.driver) not in index:
-                    raise ValueError(f'scenario {name!r}: {plan.driver!r} is not one of the drivers')
-                if not allow_single_compound and track_condition == 'dry':
-                    used = None
-                    if arrays is not None:
-                        used = {c for j, c in enumerate(N.COMPOUNDS)
-                                if (int(arrays['used_compounds'][index[str(plan.driver)]]) >> j) & 1}
-                    check_two_compounds(plan, used, name)
-                c_plans.append(plan.c_struct(index, from_state=state is not None))
-            counts.append(len(plans))
-            pens = pens_of.get(name, [])
-            seen = set()
+        def pack(name, pens, index):
+            packed, seen = [], set()
             for pen in pens:
                 if str(pen.driver) not in index:
                     raise ValueError(f'scenario {name!r}: {pen.driver!r} is not one of the drivers')
@@ -677,47 +712,15 @@ class RaceSimulator:
                     raise ValueError(f'scenario {name!r}: {pen.driver} has two penalties of kind {pen.kind!r}'
                                      + (f' on lap {c.lap}' if c.kind == N.PEN_ON_LAP else '') + '; sum them into one')
                 seen.add(key)
-                c_pens.append(c)
+                packed.append(c)
             if len(pens) > N.MAX_SCENARIO_PENALTIES:
                 raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_PENALTIES} penalties, got {len(pens)}')
-            pen_counts.append(len(pens))
-        S = len(names)
-        plan_arr = (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans)
-        count_arr = (C.c_uint32 * S)(*counts)
-        pen_arr = (N.McgpTimePenalty * max(len(c_pens), 1))(*c_pens)
-        pen_count_arr = (C.c_uint32 * S)(*pen_counts)
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
-        c_state = state.c_struct(arrays) if state is not None else None
-        n_simulations = int(n_simulations)
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+            return packed
 
-        def run_shard(device, offset, count):
-            h = np.zeros((S, n, n), np.uint64)
-            dl = np.zeros((S, n, 2 * n - 1), np.uint64)
-            ft = np.zeros((S, n, 4), np.uint64)
-            o = np.zeros((S, count, n), np.uint8) if return_orders else None
-            rc = lib.mcgp_run_penalties(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
-                                        C.byref(c_state) if c_state is not None else None, n, S, count_arr, plan_arr,
-                                        pen_count_arr, pen_arr, int(count), int(sim_offset) + int(offset), seed64, device,
-                                        u64(h), u64(dl), u64(ft),
-                                        o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
-            return (h, dl, o, ft), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        if n_simulations <= 0:
-            parts = [((np.zeros((S, n, n), np.uint64), np.zeros((S, n, 2 * n - 1), np.uint64),
-                       np.zeros((S, 0, n), np.uint8) if return_orders else None, np.zeros((S, n, 4), np.uint64)), 0, '')]
-            n_simulations = 0
-        else:
-            parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([p[k] for p, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        res = PenaltyResult(names=names, drivers=drivers, n_simulations=n_simulations, hist=total(0), delta=total(1),
-                            orders=np.concatenate([p[2] for p, _, _ in parts], axis=1) if return_orders else None,
-                            fate=total(3))
-        self.last_histogram = res.hist
-        self.last_drivers = drivers
-        return res
+        return self._run_scenarios(
+            'mcgp_run_penalties', PenaltyResult, 'penalties / strategies', n_simulations, penalties, strategies,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
+            drivers, return_orders, allow_single_compound, N.McgpTimePenalty, pack, ('fate', lambda S, n, L: (S, n, 4)))
 
     def run_events(
         self,
@@ -747,94 +750,26 @@ class RaceSimulator:
         to run raise ValueError.  Everything else -- the remaining arguments, the plans' checks, the simulation ids and
         draws, the seed rules and the device sharding -- is run_strategies': a scenario without overrides gives exactly
         its counts.  last_histogram: [S, n, n]."""
-        if (grid_probs is None) == (state is None):
-            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
-        strategies = strategies or {}
-        names = [str(k) for k in events.keys()] + [str(k) for k in strategies.keys() if str(k) not in
-                                                    {str(j) for j in events.keys()}]
-        events_of = {str(k): list(v) for k, v in events.items()}
-        plans_of = {str(k): list(v) for k, v in strategies.items()}
-        if not 1 <= len(names) <= N.MAX_SCENARIOS:
-            raise ValueError(f'events / strategies: 1 to {N.MAX_SCENARIOS} scenarios, got {len(names)}')
-        if drivers is None:
-            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
-        drivers = [str(d) for d in drivers]
-        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
-            raise ValueError('drivers must be the keys of grid_probs')
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        n, L = prob.n, int(self.config.total_laps)
-        arrays = state.arrays(drivers, L) if state is not None else None
-        index = {d: i for i, d in enumerate(drivers)}
-        first = 2 if state is None else int(state.lap) + 1
-        counts, c_plans, ev_counts, c_events = [], [], [], []
-        for name in names:
-            plans = plans_of.get(name, [])
-            for plan in plans:
-                if str(plan.driver) not in index:
-                    raise ValueError(f'scenario {name!r}: {plan.driver!r} is not one of the drivers')
-                if not allow_single_compound and track_condition == 'dry':
-                    used = None
-                    if arrays is not None:
-                        used = {c for j, c in enumerate(N.COMPOUNDS)
-                                if (int(arrays['used_compounds'][index[str(plan.driver)]]) >> j) & 1}
-                    check_two_compounds(plan, used, name)
-                c_plans.append(plan.c_struct(index, from_state=state is not None))
-            counts.append(len(plans))
-            evs = events_of.get(name, [])
+        def pack(name, evs, index):
             if len(evs) > N.MAX_SCENARIO_EVENTS:
                 raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_EVENTS} overrides, got {len(evs)}')
-            covered = {}
+            packed, covered = [], {}
             for ev in evs:
                 try:
-                    c = ev.c_struct(first, L)
+                    c = ev.c_struct(2 if state is None else int(state.lap) + 1, int(self.config.total_laps))
                 except ValueError as e:
                     raise ValueError(f'scenario {name!r}: {e}') from None
                 for lap in range(c.first_lap, c.last_lap + 1):
                     if lap in covered:
                         raise ValueError(f'scenario {name!r}: lap {lap} has two overrides ({covered[lap]} and {ev})')
                     covered[lap] = ev
-                c_events.append(c)
-            ev_counts.append(len(evs))
-        S = len(names)
-        plan_arr = (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans)
-        count_arr = (C.c_uint32 * S)(*counts)
-        ev_arr = (N.McgpLapEvent * max(len(c_events), 1))(*c_events)
-        ev_count_arr = (C.c_uint32 * S)(*ev_counts)
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
-        c_state = state.c_struct(arrays) if state is not None else None
-        n_simulations = int(n_simulations)
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        if not hasattr(lib, 'mcgp_run_events'):
-            raise N.McgpError(-1, 'the loaded library does not export mcgp_run_events')
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+                packed.append(c)
+            return packed
 
-        def run_shard(device, offset, count):
-            h = np.zeros((S, n, n), np.uint64)
-            dl = np.zeros((S, n, 2 * n - 1), np.uint64)
-            ec = np.zeros((S, 3, L + 1), np.uint64)
-            o = np.zeros((S, count, n), np.uint8) if return_orders else None
-            rc = lib.mcgp_run_events(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
-                                     C.byref(c_state) if c_state is not None else None, n, S, count_arr, plan_arr,
-                                     ev_count_arr, ev_arr, int(count), int(sim_offset) + int(offset), seed64, device,
-                                     u64(h), u64(dl), u64(ec),
-                                     o.ctypes.data_as(C.POINTER(C.c_uint8)) if return_orders else None)
-            return (h, dl, o, ec), rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        if n_simulations <= 0:
-            parts = [((np.zeros((S, n, n), np.uint64), np.zeros((S, n, 2 * n - 1), np.uint64),
-                       np.zeros((S, 0, n), np.uint8) if return_orders else None, np.zeros((S, 3, L + 1), np.uint64)), 0,
-                      '')]
-            n_simulations = 0
-        else:
-            parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([p[k] for p, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        res = EventResult(names=names, drivers=drivers, n_simulations=n_simulations, hist=total(0), delta=total(1),
-                          orders=np.concatenate([p[2] for p, _, _ in parts], axis=1) if return_orders else None,
-                          events=total(3))
-        self.last_histogram = res.hist
-        self.last_drivers = drivers
-        return res
+        return self._run_scenarios(
+            'mcgp_run_events', EventResult, 'events / strategies', n_simulations, events, strategies,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
+            drivers, return_orders, allow_single_compound, N.McgpLapEvent, pack, ('events', lambda S, n, L: (S, 3, L + 1)))
 
     def run_gaps(
         self,
@@ -858,13 +793,8 @@ class RaceSimulator:
         (grid_probs: run_monte_carlo's simulations, laps 1..L) or from a mid-race RaceState (state: run_from_state's
         simulations, the laps after the state's).  The GapResult's position histogram equals that call's.  32-bit
         deviates only; same seed rules and device sharding as run_monte_carlo.  Sets last_histogram / last_drivers."""
-        if (grid_probs is None) == (state is None):
-            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
-        if drivers is None:
-            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
-        drivers = [str(d) for d in drivers]
-        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
-            raise ValueError('drivers must be the keys of grid_probs')
+        src = self._source(grid_probs, state, drivers)
+        drivers = src.drivers
         edge_arr = np.ascontiguousarray(DEFAULT_GAP_EDGES if edges is None else list(edges), np.float64)
         if edge_arr.ndim != 1 or not 1 <= len(edge_arr) <= N.MAX_GAP_EDGES:
             raise ValueError(f'edges: 1 to {N.MAX_GAP_EDGES} values, got {edge_arr.shape}')
@@ -881,38 +811,16 @@ class RaceSimulator:
             raise ValueError(f'pairs: at most {N.MAX_GAP_PAIRS}, got {len(names)}')
         n, L, E, P = len(drivers), int(self.config.total_laps), len(edge_arr), len(names)
         n_simulations = int(n_simulations)
-        first_lap = 1 if state is None else int(state.lap) + 1
-        mk = lambda count, dtype: GapResult.empty(drivers, L, edge_arr, names, count, first_lap, dtype)
-        if not drivers or n_simulations <= 0:
-            res = mk(0, np.int64)
-            self.last_histogram, self.last_drivers = res.hist, drivers
-            return res
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        arrays = state.arrays(drivers, L) if state is not None else None
-        c_state = state.c_struct(arrays) if state is not None else None
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
+        first_lap = src.first_lap(1)
         pair_arr = np.ascontiguousarray([[index[a], index[b]] for a, b in names], np.uint8).reshape(P, 2)
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
-
-        def run_shard(device, offset, count):
-            out = mk(count, np.uint64)
-            rc = lib.mcgp_run_gaps(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
-                                   C.byref(c_state) if c_state is not None else None, n, E, _dptr(edge_arr), P,
-                                   pair_arr.ctypes.data_as(C.POINTER(C.c_uint8)) if P else None, int(count),
-                                   int(sim_offset) + int(offset), seed64, device, u64(out.hist), u64(out.lap_gap),
-                                   u64(out.lead), u64(out.pair) if P else None)
-            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([getattr(r, k) for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        res = GapResult(drivers=drivers, n_simulations=n_simulations, total_laps=L, edges=tuple(float(x) for x in edge_arr),
-                        pairs=names, first_lap=first_lap, hist=total('hist'), lap_gap=total('lap_gap'), lead=total('lead'),
-                        pair=total('pair'))
-        self.last_histogram = res.hist
-        self.last_drivers = drivers
-        return res
+        total = self._run_entry(
+            'mcgp_run_gaps', n_simulations, drivers,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), seed, sim_offset,
+            lambda n: src.c_args() + (n, E, _dptr(edge_arr), P, _optr(pair_arr) if P else None),
+            lambda count: _count_arrays(GapResult.empty(drivers, L, edge_arr, names, count, first_lap, np.uint64)),
+            ['hist', 'lap_gap', 'lead', 'pair' if P else None])
+        return GapResult(drivers=drivers, n_simulations=n_simulations if drivers and n_simulations > 0 else 0,
+                         total_laps=L, edges=tuple(float(x) for x in edge_arr), pairs=names, first_lap=first_lap, **total)
 
     def run_stints(
         self,
@@ -934,44 +842,16 @@ class RaceSimulator:
         laps 2..L) or from a mid-race RaceState (state: run_from_state's simulations, the laps after the state's; earlier
         stops are not part of a state).  The StintResult's position histogram equals that call's.  32-bit deviates only;
         same seed rules and device sharding as run_monte_carlo.  Sets last_histogram / last_drivers."""
-        if (grid_probs is None) == (state is None):
-            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
-        if drivers is None:
-            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
-        drivers = [str(d) for d in drivers]
-        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
-            raise ValueError('drivers must be the keys of grid_probs')
-        n, L = len(drivers), int(self.config.total_laps)
-        n_simulations = int(n_simulations)
-        first_lap = 2 if state is None else int(state.lap) + 1
-        mk = lambda count, dtype: StintResult.empty(drivers, L, count, first_lap, dtype)
-        if not drivers or n_simulations <= 0:
-            res = mk(0, np.int64)
-            self.last_histogram, self.last_drivers = res.hist, drivers
-            return res
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        arrays = state.arrays(drivers, L) if state is not None else None
-        c_state = state.c_struct(arrays) if state is not None else None
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
-
-        def run_shard(device, offset, count):
-            out = mk(count, np.uint64)
-            rc = lib.mcgp_run_stints(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
-                                     C.byref(c_state) if c_state is not None else None, n, int(count),
-                                     int(sim_offset) + int(offset), seed64, device, u64(out.hist), u64(out.stop_lap),
-                                     u64(out.stops_pos), u64(out.seq))
-            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([getattr(r, k) for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        res = StintResult(drivers=drivers, n_simulations=n_simulations, total_laps=L, first_lap=first_lap,
-                          hist=total('hist'), stop_lap=total('stop_lap'), stops_pos=total('stops_pos'), seq=total('seq'))
-        self.last_histogram = res.hist
-        self.last_drivers = drivers
-        return res
+        src = self._source(grid_probs, state, drivers)
+        drivers, L, n_simulations = src.drivers, int(self.config.total_laps), int(n_simulations)
+        total = self._run_entry(
+            'mcgp_run_stints', n_simulations, drivers,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), seed, sim_offset,
+            lambda n: src.c_args() + (n,),
+            lambda count: _count_arrays(StintResult.empty(drivers, L, count, src.first_lap(), np.uint64)),
+            ['hist', 'stop_lap', 'stops_pos', 'seq'])
+        return StintResult(drivers=drivers, n_simulations=n_simulations if drivers and n_simulations > 0 else 0,
+                           total_laps=L, first_lap=src.first_lap(), **total)
 
     def run_moves(
         self,
@@ -993,47 +873,17 @@ class RaceSimulator:
         simulations, passes on laps 2..L) or from a mid-race RaceState (state: run_from_state's simulations, the laps
         after the state's; no start gain).  The MoveResult's position histogram equals that call's.  32-bit deviates
         only; same seed rules and device sharding as run_monte_carlo.  Sets last_histogram / last_drivers."""
-        if (grid_probs is None) == (state is None):
-            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
-        if drivers is None:
-            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
-        drivers = [str(d) for d in drivers]
-        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
-            raise ValueError('drivers must be the keys of grid_probs')
-        n, L = len(drivers), int(self.config.total_laps)
-        n_simulations = int(n_simulations)
-        first_lap = 2 if state is None else int(state.lap) + 1
-        mk = lambda count, dtype: MoveResult.empty(drivers, L, count, first_lap, state is None, dtype)
-        if not drivers or n_simulations <= 0:
-            res = mk(0, np.int64)
-            self.last_histogram, self.last_drivers = res.hist, drivers
-            return res
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        arrays = state.arrays(drivers, L) if state is not None else None
-        c_state = state.c_struct(arrays) if state is not None else None
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
-
-        def run_shard(device, offset, count):
-            out = mk(count, np.uint64)
-            rc = lib.mcgp_run_moves(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
-                                    C.byref(c_state) if c_state is not None else None, n, int(count),
-                                    int(sim_offset) + int(offset), seed64, device, u64(out.hist), u64(out.grid_fin),
-                                    u64(out.start_gain) if state is None else None, u64(out.passes),
-                                    u64(out.race_passes), u64(out.lap_passes), u64(out.pair_passes))
-            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([getattr(r, k) for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        res = MoveResult(drivers=drivers, n_simulations=n_simulations, total_laps=L, first_lap=first_lap,
-                         from_grid=state is None, hist=total('hist'), grid_fin=total('grid_fin'),
-                         start_gain=total('start_gain'), passes=total('passes'), race_passes=total('race_passes'),
-                         lap_passes=total('lap_passes'), pair_passes=total('pair_passes'))
-        self.last_histogram = res.hist
-        self.last_drivers = drivers
-        return res
+        src = self._source(grid_probs, state, drivers)
+        drivers, L, n_simulations = src.drivers, int(self.config.total_laps), int(n_simulations)
+        total = self._run_entry(
+            'mcgp_run_moves', n_simulations, drivers,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), seed, sim_offset,
+            lambda n: src.c_args() + (n,),
+            lambda count: _count_arrays(MoveResult.empty(drivers, L, count, src.first_lap(), state is None, np.uint64)),
+            ['hist', 'grid_fin', 'start_gain' if state is None else None, 'passes', 'race_passes', 'lap_passes',
+             'pair_passes'])
+        return MoveResult(drivers=drivers, n_simulations=n_simulations if drivers and n_simulations > 0 else 0,
+                          total_laps=L, first_lap=src.first_lap(), from_grid=state is None, **total)
 
     def run_conditions(
         self,
@@ -1059,51 +909,21 @@ class RaceSimulator:
         histogram equals that call's.  32-bit deviates only; same seed rules and device sharding as run_monte_carlo.
         Sets last_histogram / last_drivers."""
         from . import conditions as CD
-        if (grid_probs is None) == (state is None):
-            raise ValueError('give exactly one of grid_probs (a run from the grid) and state (a run from a race state)')
-        if drivers is None:
-            drivers = list(grid_probs.keys()) if grid_probs is not None else [c.driver for c in state.cars]
-        drivers = [str(d) for d in drivers]
-        if grid_probs is not None and sorted(drivers) != sorted(str(k) for k in grid_probs.keys()):
-            raise ValueError('drivers must be the keys of grid_probs')
+        src = self._source(grid_probs, state, drivers)
+        drivers = src.drivers
         parsed = CD.parse_all(conditions, drivers)
         names = list(parsed)
-        n, L, K = len(drivers), int(self.config.total_laps), len(names)
+        n, K = len(drivers), len(names)
         n_simulations = int(n_simulations)
-
-        def result(hist, count, cond_hist):
-            return CD.ConditionResult(drivers=drivers, names=names, n_simulations=max(n_simulations, 0), hist=hist,
-                                      counts={k: int(c) for k, c in zip(names, count)}, cond_hist=cond_hist)
-
-        if not drivers or n_simulations <= 0:
-            res = result(np.zeros((n, n), np.int64), np.zeros(K, np.int64),
-                         np.zeros((K, n, n), np.int64) if histograms else None)
-            self.last_histogram, self.last_drivers = res.hist, drivers
-            return res
-        prob = self._problem(drivers, base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition)
-        arrays = state.arrays(drivers, L) if state is not None else None
-        c_state = state.c_struct(arrays) if state is not None else None
-        g = self._grid_matrix({str(k): v for k, v in grid_probs.items()}, drivers) if grid_probs is not None else None
-        table = CD.c_array(parsed)
-        seed64 = self._resolve_seed(seed)
-        lib = N.lib()
-        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
-
-        def run_shard(device, offset, count):
-            out = (np.zeros((n, n), np.uint64), np.zeros(K, np.uint64),
-                   np.zeros((K, n, n), np.uint64) if histograms else None)
-            rc = lib.mcgp_run_conditions(C.byref(prob.cfg), C.byref(prob.drv), _dptr(g) if g is not None else None,
-                                         C.byref(c_state) if c_state is not None else None, n, K, table, int(count),
-                                         int(sim_offset) + int(offset), seed64, device, u64(out[0]), u64(out[1]),
-                                         u64(out[2]) if histograms else None)
-            return out, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
-
-        parts = self._run_sharded(run_shard, n_simulations)
-        total = lambda k: np.sum([r[k] for r, _, _ in parts], axis=0, dtype=np.uint64).astype(np.int64)
-        res = result(total(0), total(1), total(2) if histograms else None)
-        self.last_histogram = res.hist
-        self.last_drivers = drivers
-        return res
+        total = self._run_entry(
+            'mcgp_run_conditions', n_simulations, drivers,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), seed, sim_offset,
+            lambda n: src.c_args() + (n, K, CD.c_array(parsed)),
+            lambda count: dict(hist=np.zeros((n, n), np.uint64), count=np.zeros(K, np.uint64),
+                               cond_hist=np.zeros((K, n, n), np.uint64) if histograms else None),
+            ['hist', 'count', 'cond_hist'])
+        return CD.ConditionResult(drivers=drivers, names=names, n_simulations=max(n_simulations, 0), hist=total['hist'],
+                                  counts={k: int(c) for k, c in zip(names, total['count'])}, cond_hist=total['cond_hist'])
 
     def simulate_race(
         self,
