@@ -526,6 +526,143 @@ __device__ __forceinline__ void step_commit4(double *cum, uint32_t *pk, double *
 #undef MCGP_STEP_WRITE
 #undef MCGP_STEP_TEST
 
+// ---- position update under EXEC ----
+// _update_positions (reference :538-560) for 1..4 consecutive slots in time-rank order, for a field WITHOUT equal times
+// (update_positions_reg<N, true>, race_kernel_reg.hip.h).  Threaded through the slots, and from one statement to the
+// next: `leader` and `prev` (the time of the first running car and of the last running car so far) and `first`, the
+// lanes that have not met a running car yet (an SGPR pair).  Per slot, with time t and pk word p:
+//   A = !(p & DNF)  (the car runs);   p &= ~(DRS | DIRTY)
+//   under first:                                 leader = t   (it stops moving at the first running car: A leaves `first` below)
+//   under ~first,      where t - leader < thr:   p |= DIRTY
+//   under ~first & drs, where t - prev < 1.0:    p |= DRS
+//   under A:  prev = t;   first &= ~A
+// Nothing is merged by selects: `leader` and `prev` are moved in place under the lanes they change for, and each flag is
+// OR-ed in under EXEC narrowed first to the lanes that may get it and then, by v_cmpx, to the lanes whose gap is below the
+// bound.  Both subtractions are the select form's, rounded once; `thr > tbl` is the C++ `tbl < thr` (a compare does not
+// round, no time is NaN).  For a field without equal times "not the first running car" stands in for :552's 0 < gap, as
+// in update_positions_reg<N, true>.  A retired car's two flags come out as the arithmetic leaves them, as in the select
+// form: nothing reads them.  FIRST: the statement opens the field -- every lane is still looking for its first running
+// car at slot 0, which therefore gets no flag and hands its time to `leader` and to `prev` (a lane whose slot 0 is
+// retired reads neither before the first running car has replaced both), and `first` is written, not read.
+// The running tests of all slots and the clearing of the flags open the statement under the saved mask, so that a slot
+// itself changes EXEC four times and no compare result has to be kept: six SGPR pairs besides the inputs.  EXEC is saved
+// once, only ever set to a subset of the saved mask (saved & mask, or narrowed further by v_cmpx, which only clears bits),
+// and back at its entry value at the end: a lane that is off at entry stays off and nothing of it is written.
+// Wait states, by producer / consumer pair:
+//   v_cmp (VOP3) writes an SGPR pair -> s_and_b64 / s_andn2_b64 reads it: interlocked, as in step_commit* above; no VALU
+//     instruction reads an SGPR a VALU instruction of the statement wrote (VCC is written by v_cmpx and never read).
+//   s_and_b64 / v_cmpx writes EXEC -> VALU: interlocked (see ovt_commit*; no DPP, lane access or EXECZ / VCCZ operand).
+//   thr comes in an SGPR pair written before the statement (scalar_f64: at least three VALU instructions earlier), the
+//     DRS lanes in one the scalar unit reads.
+#define MCGP_UPD_ENTER "s_mov_b64 %[ex], exec\n\ts_and_b64 %[xd], %[ex], %[drm]\n\t"
+#define MCGP_UPD_HEAD(k)                                                                                                \
+    "v_and_b32 %[t], %[dnf], %[p" #k "]\n\t"                                                                            \
+    "v_and_b32 %[p" #k "], %[clr], %[p" #k "]\n\t"                                                                      \
+    "v_cmp_eq_u32 %[a" #k "], 0, %[t]\n\t"
+#define MCGP_UPD_SLOT(k)                                                                                                \
+    "s_and_b64 exec, %[ex], %[f]\n\t"                                                                                   \
+    "v_mov_b64 %[ld], %[u" #k "]\n\t"                                                                                   \
+    "s_andn2_b64 exec, %[ex], %[f]\n\t"                                                                                 \
+    "v_add_f64 %[tb], %[u" #k "], -%[ld]\n\t"                                                                           \
+    "v_add_f64 %[gp], %[u" #k "], -%[pv]\n\t"                                                                           \
+    "v_cmpx_gt_f64 vcc, %[thr], %[tb]\n\t"                                                                              \
+    "v_or_b32 %[p" #k "], %[dty], %[p" #k "]\n\t"                                                                       \
+    "s_andn2_b64 exec, %[xd], %[f]\n\t"                                                                                 \
+    "v_cmpx_gt_f64 vcc, 1.0, %[gp]\n\t"                                                                                 \
+    "v_or_b32 %[p" #k "], %[drs], %[p" #k "]\n\t"                                                                       \
+    "s_and_b64 exec, %[ex], %[a" #k "]\n\t"                                                                             \
+    "v_mov_b64 %[pv], %[u" #k "]\n\t"                                                                                   \
+    "s_andn2_b64 %[f], %[f], %[a" #k "]\n\t"
+#define MCGP_UPD_SLOT_FIRST                                                                                             \
+    "v_mov_b64 %[ld], %[u0]\n\t"                                                                                        \
+    "v_mov_b64 %[pv], %[u0]\n\t"                                                                                        \
+    "s_andn2_b64 %[f], %[ex], %[a0]\n\t"
+#define MCGP_UPD_LEAVE "s_mov_b64 exec, %[ex]"
+#define MCGP_UPD_BODY1(S0) MCGP_UPD_ENTER MCGP_UPD_HEAD(0) S0 MCGP_UPD_LEAVE
+#define MCGP_UPD_BODY2(S0) MCGP_UPD_ENTER MCGP_UPD_HEAD(0) MCGP_UPD_HEAD(1) S0 MCGP_UPD_SLOT(1) MCGP_UPD_LEAVE
+#define MCGP_UPD_BODY3(S0) MCGP_UPD_ENTER MCGP_UPD_HEAD(0) MCGP_UPD_HEAD(1) MCGP_UPD_HEAD(2) S0 MCGP_UPD_SLOT(1) MCGP_UPD_SLOT(2) MCGP_UPD_LEAVE
+#define MCGP_UPD_BODY4(S0)                                                                                              \
+    MCGP_UPD_ENTER MCGP_UPD_HEAD(0) MCGP_UPD_HEAD(1) MCGP_UPD_HEAD(2) MCGP_UPD_HEAD(3) S0 MCGP_UPD_SLOT(1) MCGP_UPD_SLOT(2)   \
+        MCGP_UPD_SLOT(3) MCGP_UPD_LEAVE
+#define MCGP_UPD_SLOT_OPS(k) [p##k] "+v"(pk[k]), [a##k] "=&s"(a[k])
+#define MCGP_UPD_STATE [ld] "+v"(leader), [pv] "+v"(prev), [f] "+s"(first), [t] "=&v"(t), [tb] "=&v"(tb), [gp] "=&v"(gp), [ex] "=&s"(ex), [xd] "=&s"(xd)
+#define MCGP_UPD_COMMON [thr] "s"(c.thr), [drm] "s"(c.drs), [dnf] "n"(DNF), [dty] "n"(DIRTY), [drs] "n"(DRS), [clr] "n"(~(DIRTY | DRS))
+#define MCGP_UPD_TEMPS                                                                                                  \
+    uint32_t t;                                                                                                         \
+    double tb, gp;                                                                                                      \
+    uint64_t ex, xd, a[4]
+// the lap's wave-uniform inputs (SGPR pairs)
+struct UpdLap {
+    double thr;          // dirty-air threshold
+    uint64_t drs;        // the lanes whose race has DRS enabled on this lap
+};
+template <uint32_t DNF, uint32_t DIRTY, uint32_t DRS, bool FIRST>
+__device__ __forceinline__ void upd_commit1(const double *cum, uint32_t *pk, double &leader, double &prev, uint64_t &first, const UpdLap &c)
+{
+    MCGP_UPD_TEMPS;
+    if constexpr (FIRST)
+        asm volatile(MCGP_UPD_BODY1(MCGP_UPD_SLOT_FIRST)
+                     : MCGP_UPD_SLOT_OPS(0), MCGP_UPD_STATE : [u0] "v"(cum[0]), MCGP_UPD_COMMON : "scc", "vcc");
+    else
+        asm volatile(MCGP_UPD_BODY1(MCGP_UPD_SLOT(0))
+                     : MCGP_UPD_SLOT_OPS(0), MCGP_UPD_STATE : [u0] "v"(cum[0]), MCGP_UPD_COMMON : "scc", "vcc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t DRS, bool FIRST>
+__device__ __forceinline__ void upd_commit2(const double *cum, uint32_t *pk, double &leader, double &prev, uint64_t &first, const UpdLap &c)
+{
+    MCGP_UPD_TEMPS;
+    if constexpr (FIRST)
+        asm volatile(MCGP_UPD_BODY2(MCGP_UPD_SLOT_FIRST)
+                     : MCGP_UPD_SLOT_OPS(0), MCGP_UPD_SLOT_OPS(1), MCGP_UPD_STATE
+                     : [u0] "v"(cum[0]), [u1] "v"(cum[1]), MCGP_UPD_COMMON : "scc", "vcc");
+    else
+        asm volatile(MCGP_UPD_BODY2(MCGP_UPD_SLOT(0))
+                     : MCGP_UPD_SLOT_OPS(0), MCGP_UPD_SLOT_OPS(1), MCGP_UPD_STATE
+                     : [u0] "v"(cum[0]), [u1] "v"(cum[1]), MCGP_UPD_COMMON : "scc", "vcc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t DRS, bool FIRST>
+__device__ __forceinline__ void upd_commit3(const double *cum, uint32_t *pk, double &leader, double &prev, uint64_t &first, const UpdLap &c)
+{
+    MCGP_UPD_TEMPS;
+    if constexpr (FIRST)
+        asm volatile(MCGP_UPD_BODY3(MCGP_UPD_SLOT_FIRST)
+                     : MCGP_UPD_SLOT_OPS(0), MCGP_UPD_SLOT_OPS(1), MCGP_UPD_SLOT_OPS(2), MCGP_UPD_STATE
+                     : [u0] "v"(cum[0]), [u1] "v"(cum[1]), [u2] "v"(cum[2]), MCGP_UPD_COMMON : "scc", "vcc");
+    else
+        asm volatile(MCGP_UPD_BODY3(MCGP_UPD_SLOT(0))
+                     : MCGP_UPD_SLOT_OPS(0), MCGP_UPD_SLOT_OPS(1), MCGP_UPD_SLOT_OPS(2), MCGP_UPD_STATE
+                     : [u0] "v"(cum[0]), [u1] "v"(cum[1]), [u2] "v"(cum[2]), MCGP_UPD_COMMON : "scc", "vcc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t DRS, bool FIRST>
+__device__ __forceinline__ void upd_commit4(const double *cum, uint32_t *pk, double &leader, double &prev, uint64_t &first, const UpdLap &c)
+{
+    MCGP_UPD_TEMPS;
+    if constexpr (FIRST)
+        asm volatile(MCGP_UPD_BODY4(MCGP_UPD_SLOT_FIRST)
+                     : MCGP_UPD_SLOT_OPS(0), MCGP_UPD_SLOT_OPS(1), MCGP_UPD_SLOT_OPS(2), MCGP_UPD_SLOT_OPS(3), MCGP_UPD_STATE
+                     : [u0] "v"(cum[0]), [u1] "v"(cum[1]), [u2] "v"(cum[2]), [u3] "v"(cum[3]), MCGP_UPD_COMMON : "scc", "vcc");
+    else
+        asm volatile(MCGP_UPD_BODY4(MCGP_UPD_SLOT(0))
+                     : MCGP_UPD_SLOT_OPS(0), MCGP_UPD_SLOT_OPS(1), MCGP_UPD_SLOT_OPS(2), MCGP_UPD_SLOT_OPS(3), MCGP_UPD_STATE
+                     : [u0] "v"(cum[0]), [u1] "v"(cum[1]), [u2] "v"(cum[2]), [u3] "v"(cum[3]), MCGP_UPD_COMMON : "scc", "vcc");
+}
+#undef MCGP_UPD_TEMPS
+#undef MCGP_UPD_COMMON
+#undef MCGP_UPD_STATE
+#undef MCGP_UPD_SLOT_OPS
+#undef MCGP_UPD_BODY4
+#undef MCGP_UPD_BODY3
+#undef MCGP_UPD_BODY2
+#undef MCGP_UPD_BODY1
+#undef MCGP_UPD_LEAVE
+#undef MCGP_UPD_SLOT_FIRST
+#undef MCGP_UPD_SLOT
+#undef MCGP_UPD_HEAD
+#undef MCGP_UPD_ENTER
+// the lanes of the wavefront in which the predicate holds (an SGPR pair), and the mask with every lane in it
+__device__ __forceinline__ uint64_t lane_mask(bool pred) { return __ballot(pred); }
+constexpr uint64_t kAllLanes = ~0ull;
+
 // LDS access by ABSOLUTE byte address.  The register kernel declares no static __shared__ data, so its
 // dynamic LDS block starts at address 0 (checked once at kernel entry); addressing it by number instead of
 // through the `extern __shared__` symbol lets the compiler fold every table / row base into the 16-bit

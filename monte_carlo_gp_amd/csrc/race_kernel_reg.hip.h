@@ -24,6 +24,11 @@
 // per-(compound, driver) {degradation x factor, pit threshold}, per-compound pace delta, the pit rule, the
 // n x n histogram (u32) and the transposed grid matrix.
 //
+// What a pass over the field changes for SOME lanes only -- an overtake's two times, a car's lap, and at the end of a lap
+// the position update's leader, car ahead and dirty-air / DRS flags -- is written in place under EXEC narrowed to those
+// lanes, a few slots to an assembly statement (race_isa.hip.h), instead of computed for every lane and merged by selects;
+// the position update of a wave that holds two equal times, and lap 1's, keep the general select form.
+//
 // Random draws of a lap are addressed by the car's PLACE in the field order (its register index): the Philox block of
 // places 4j .. 4j+3 is computed right where the four cars' laps are, and never touches LDS.
 #pragma once
@@ -129,6 +134,17 @@ __host__ __device__ constexpr bool reg_commit_by_selects(int n) { return n == 6 
 // VGPRs).  Everywhere else every instantiation keeps or lowers both (N = 20: 28 -> 0 B, batch 108 -> 88, reference width
 // 192 -> 176); occupancy changes nowhere.
 __host__ __device__ constexpr bool reg_step_by_selects(int n) { return n == 3 || n == 11 || n == 12 || n == 25 || n == 26 || n == 29; }
+// Field sizes whose position update of a field without equal times stays merged by selects instead of written under EXEC
+// (update_positions_distinct; upd_commit*, race_isa.hip.h): the ones where the EXEC form costs some instantiation scratch
+// or registers (select form -> EXEC form: N = 1 56 -> 57 VGPRs, batch 74 -> 75; N = 6 batch 188 -> 208 B of scratch per lane;
+// N = 9 / 10 reference width 157 -> 158 / 163 -> 164 VGPRs; N = 11 80 -> 84 B, 4-wave blocks 76 -> 80; N = 22 batch 92 -> 100;
+// N = 28 / 29 reference width 144 -> 156 / 216 -> 224).  A cut by resources alone, as the two lists above: neither form was
+// timed at these sizes.  Everywhere else every instantiation keeps or lowers both (N = 20: 168 VGPRs and 0 B as before,
+// batch 88 -> 84; N = 5 batch 180 -> 116); occupancy changes nowhere.
+__host__ __device__ constexpr bool reg_update_by_selects(int n)
+{
+    return n == 1 || n == 6 || (n >= 9 && n <= 11) || n == 22 || n == 28 || n == 29;
+}
 // Waves per block: the (waves per block, blocks per CU) pair that keeps the most waves resident within the LDS
 // budget and the kernel's waves per SIMD; among equals a multiple of 4 waves per block (a block's waves go round the
 // 4 SIMDs: two blocks of 6 load them 4, 4, 2, 2), then the block nearest to 8 waves (1024-thread blocks make the
@@ -522,7 +538,9 @@ __device__ __forceinline__ void update_positions_reg(const double (&cum)[N], uin
 {
     bool first = true;
     double leader = 0.0, prev = 0.0;
-    // one straight pass, merged by selects (a few lanes hold retired cars; the wave would pay for the branches).
+    // one straight pass, merged by selects (a few lanes hold retired cars; the wave would pay for the branches).  The
+    // general, exact form: lap 1, a wave with two equal times, the field sizes of reg_update_by_selects();
+    // update_positions_distinct below is what the lap loop otherwise runs.
     // A RETIRED car's two flags are written like everybody's, with whatever the arithmetic gives: nothing reads them
     // again (the lap step and the event handler test the dnf bit first, a retired car's overtake pace is NaN whatever
     // its DRS bit adds, the classification does not look at flags), and not protecting them saves a select per slot.
@@ -721,6 +739,33 @@ __device__ __forceinline__ uint32_t scalar_u32(uint32_t x)
 __device__ __forceinline__ double scalar_f64(double x)
 {
     return __hiloint2double((int)scalar_u32((uint32_t)__double2hiint(x)), (int)scalar_u32((uint32_t)__double2loint(x)));
+}
+// update_positions_reg<N, true> as the lap loop calls it: `leader`, `prev` and the two flags written in place under EXEC
+// narrowed to the lanes they change for, four slots to an assembly statement (upd_commit*, race_isa.hip.h), instead of
+// merged by selects for every lane; the field sizes of reg_update_by_selects() keep the select form.  `drs_allowed` is
+// per lane (an event ends DRS in that race only): it goes in as a lane mask made once a lap.
+template <int N>
+__device__ __forceinline__ void update_positions_distinct(const double (&cum)[N], uint32_t (&pk)[N], bool drs_allowed, double dirty_thr)
+{
+    if constexpr (reg_update_by_selects(N)) {
+        update_positions_reg<N, true>(cum, pk, drs_allowed, dirty_thr);
+    } else {
+        const UpdLap c{scalar_f64(dirty_thr), lane_mask(drs_allowed)};
+        uint64_t first = kAllLanes;                     // (the statement that opens the field writes it)
+        double leader = 0.0, prev = 0.0;
+        if constexpr (N >= 4) upd_commit4<k3Dnf, k3Dirty, k3Drs, true>(&cum[0], &pk[0], leader, prev, first, c);
+        if constexpr (N == 3) upd_commit3<k3Dnf, k3Dirty, k3Drs, true>(&cum[0], &pk[0], leader, prev, first, c);
+        if constexpr (N == 2) upd_commit2<k3Dnf, k3Dirty, k3Drs, true>(&cum[0], &pk[0], leader, prev, first, c);
+        if constexpr (N == 1) upd_commit1<k3Dnf, k3Dirty, k3Drs, true>(&cum[0], &pk[0], leader, prev, first, c);
+#pragma unroll
+        for (int i0 = 4; i0 < N; i0 += 4) {
+            const int K = N - i0 < 4 ? N - i0 : 4;      // (a constant once the loop is unrolled)
+            if constexpr (N >= 8) if (K == 4) upd_commit4<k3Dnf, k3Dirty, k3Drs, false>(&cum[i0], &pk[i0], leader, prev, first, c);
+            if constexpr (N > 4 && N % 4 == 3) if (K == 3) upd_commit3<k3Dnf, k3Dirty, k3Drs, false>(&cum[i0], &pk[i0], leader, prev, first, c);
+            if constexpr (N > 4 && N % 4 == 2) if (K == 2) upd_commit2<k3Dnf, k3Dirty, k3Drs, false>(&cum[i0], &pk[i0], leader, prev, first, c);
+            if constexpr (N > 4 && N % 4 == 1) if (K == 1) upd_commit1<k3Dnf, k3Dirty, k3Drs, false>(&cum[i0], &pk[i0], leader, prev, first, c);
+        }
+    }
 }
 // The exact 53-bit decision of one overtake pass of the reference-width build (reg_simulate, overtakes): the path of a draw
 // word that EQUALS the leading word of its threshold, or of a lane with more than eight attempts.  Plain code, four attempts
@@ -1891,9 +1936,9 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 // ---- overtakes: re-sort ----
                 distinct_times = resort_after_overtakes<N>(cum, pk);     // sorted again for the next pass / _update_positions
             }
-            // ---- _update_positions, :227-228 ----  (update_positions_reg<N, true> for the wave-laps whose fields have no equal times)
+            // ---- _update_positions, :227-228 ----  (under EXEC, upd_commit*, for the wave-laps whose fields have no equal times)
             if (!MCGP_ANY(!distinct_times))
-                update_positions_reg<N, true>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
+                update_positions_distinct<N>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
             else
                 update_positions_reg<N>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
         }

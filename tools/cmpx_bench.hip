@@ -9,6 +9,11 @@
 //      compares, 2 shifts + 4 ands, 8 selects, a two-entry LDS read)
 //   LE the same under EXEC (race_isa.hip.h step_commit4): 4 compares into SGPR pairs, each write in place under saved & mask
 //      ("comparator" in the output is one slot; both include the same clean-time and age-field instructions and loop overhead)
+//   US the position update of four consecutive slots by selects (update_positions_reg<N, true> as compiled: leader, prev and the two
+//      flag bits merged by 6 selects, the running test twice, 3 ands, 2 subtractions, 2 binary64 compares, a v_or3)
+//   UE the same under EXEC (race_isa.hip.h upd_commit4<.., false>): leader and prev moved in place, each flag OR-ed in under EXEC
+//      narrowed by a mask and then by v_cmpx;  UF with slot 0 opening the field (upd_commit4<.., true>)
+//      (per slot; lanes with a retired car in front of the first running one, with one between two running ones, with DRS off)
 // each as layers of 8 independent comparators (the sorting network) and as a chain of 15 dependent ones (a bubble pass).
 // The loop bodies are written on fixed registers (v[10:41] = 16 times, v50..v65 = 16 payloads): inline assembly cannot
 // name the halves of a 64-bit operand, which form B needs.
@@ -36,7 +41,10 @@ int main()
                           {"S chain (overtake commit: cmp, 2 add, 4 cndmask)", k_S_chain, 15},
                           {"E chain (overtake commit: cmpx, 2 add in place, restore)", k_E_chain, 15},
                           {"LS (lap-step commit of 4 slots by selects; per slot)", k_LS_chain, 4},
-                          {"LE (lap-step commit of 4 slots under EXEC; per slot)", k_LE_chain, 4}};
+                          {"LE (lap-step commit of 4 slots under EXEC; per slot)", k_LE_chain, 4},
+                          {"US (position update of 4 slots by selects; per slot)", k_US_chain, 4},
+                          {"UE (position update of 4 slots under EXEC; per slot)", k_UE_chain, 4},
+                          {"UF (the same, slot 0 opening the field; per slot)", k_UF_chain, 4}};
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
@@ -59,10 +67,11 @@ int main()
             CHECK(hipEventSynchronize(e1));
             float ms;
             CHECK(hipEventElapsedTime(&ms, e0, e1));
-            double h[8];
+            double h[64], sum = 0.0;       // (every block writes the same 64 values: one per lane)
             CHECK(hipMemcpy(h, out, sizeof(h), hipMemcpyDeviceToHost));
+            for (double x : h) sum += x;
             const double cyc = 1024.0 * 2.4e9 * ms * 1e-3 / ((double)cus * 4 * W * iters * c.comparators);
-            printf("waves/SIMD %d  %-48s %.2f cycles per comparator per SIMD   (check %.3f %.3f)\n", W, c.name, cyc, h[0], h[5]);
+            printf("waves/SIMD %d  %-48s %.2f cycles per comparator per SIMD   (check %.3f %.3f, all lanes %.3f)\n", W, c.name, cyc, h[0], h[5], sum);
         }
     }
     return 0;

@@ -98,12 +98,61 @@ def step_setup():
             'v_or_b32 v105, v105, v141']
     return ins
 
+# The position update of one slot (race_kernel_reg.hip.h update_positions_reg<N, true>; race_isa.hip.h upd_commit*): slot i has
+# its time in t(i) and its pk word in p(i); leader in v[100:101], prev in v[102:103], the two gaps in v[104:107]; the lanes that
+# have not met a running car in s[24:25], the dirty-air threshold in s[26:27] (v[114:115] for the select form's VOPC compare), the
+# lanes with DRS enabled in s[28:29], the running tests of the four slots in s[34:41], saved & DRS lanes in s[42:43].
+def upd_select(i):     # today's form as compiled: leader, prev and the two flag bits merged by six selects, the running test twice
+    return [f'v_and_b32 v108, 0x200, {p(i)}', f'v_and_b32 v112, 0x200, {p(i)}', f'v_and_b32 v113, 0xffffdff7, {p(i)}',
+            'v_cmp_eq_u32 vcc, 0, v108', 's_and_b64 vcc, vcc, s[24:25]',
+            f'v_cndmask_b32 v101, v101, {hi(i)}, vcc', f'v_cndmask_b32 v100, v100, {lo(i)}, vcc',
+            f'v_add_f64 v[104:105], {t(i)}, -v[100:101]', 'v_cmp_nlt_f64 vcc, v[104:105], v[114:115]',
+            f'v_add_f64 v[106:107], {t(i)}, -v[102:103]', 's_andn2_b64 s[36:37], s[28:29], s[24:25]',
+            'v_cmp_gt_f64 s[38:39], 1.0, v[106:107]', 's_and_b64 s[38:39], s[36:37], s[38:39]',
+            'v_cndmask_b32_e64 v110, 0, 8, s[38:39]', 's_or_b64 s[40:41], s[24:25], vcc', 'v_cndmask_b32_e64 v109, v111, 0, s[40:41]',
+            f'v_or3_b32 {p(i)}, v110, v113, v109', 'v_cmp_ne_u32 vcc, 0, v112',
+            f'v_cndmask_b32 v103, {hi(i)}, v103, vcc', f'v_cndmask_b32 v102, {lo(i)}, v102, vcc', 's_and_b64 s[24:25], s[24:25], vcc']
+def A(i): return f's[{34 + 2 * i}:{35 + 2 * i}]'
+def upd_head(n):       # under the saved mask: the running test of every slot of the statement into an SGPR pair, the two flags cleared
+    ins = ['s_and_b64 s[42:43], s[20:21], s[28:29]']
+    for i in range(n): ins += [f'v_and_b32 v108, 0x200, {p(i)}', f'v_and_b32 {p(i)}, 0xffffdff7, {p(i)}', f'v_cmp_eq_u32 {A(i)}, 0, v108']
+    return ins
+def upd_slot(i, first=False):   # one slot under EXEC (MCGP_UPD_SLOT; first: MCGP_UPD_SLOT_FIRST, slot 0 of the field)
+    if first: return [f'v_mov_b64 v[100:101], {t(i)}', f'v_mov_b64 v[102:103], {t(i)}', f's_andn2_b64 s[24:25], s[20:21], {A(i)}']
+    return ['s_and_b64 exec, s[20:21], s[24:25]', f'v_mov_b64 v[100:101], {t(i)}', 's_andn2_b64 exec, s[20:21], s[24:25]',
+            f'v_add_f64 v[104:105], {t(i)}, -v[100:101]', f'v_add_f64 v[106:107], {t(i)}, -v[102:103]',
+            'v_cmpx_gt_f64 vcc, s[26:27], v[104:105]', f'v_or_b32 {p(i)}, 0x2000, {p(i)}', 's_andn2_b64 exec, s[42:43], s[24:25]',
+            'v_cmpx_gt_f64 vcc, 1.0, v[106:107]', f'v_or_b32 {p(i)}, 8, {p(i)}',
+            f's_and_b64 exec, s[20:21], {A(i)}', f'v_mov_b64 v[102:103], {t(i)}', f's_andn2_b64 s[24:25], s[24:25], {A(i)}']
+def upd_body(form):
+    # all forms: no running car met yet, leader and prev start at 0
+    ins = ['s_mov_b64 s[24:25], s[20:21]', 'v_mov_b32 v100, 0', 'v_mov_b32 v101, 0', 'v_mov_b32 v102, 0', 'v_mov_b32 v103, 0']
+    if form == 'US':
+        for i in range(4): ins += upd_select(i)
+    else:              # UE: upd_commit4<.., false>, a statement further down the field; UF: upd_commit4<.., true>, the one that opens it
+        ins += upd_head(4)
+        for i in range(4): ins += upd_slot(i, first=form == 'UF' and i == 0)
+        ins += ['s_mov_b64 exec, s[20:21]']
+    # (leader and prev go into the check value; the times move on, so the lanes of the masks change from one iteration to the next)
+    return ins + [f'v_add_f64 {t(12)}, {t(12)}, v[100:101]', f'v_add_f64 {t(12)}, {t(12)}, v[102:103]',
+                  f'v_add_f64 {t(1)}, {t(1)}, 0.5', f'v_add_f64 {t(2)}, {t(2)}, 1.0', f'v_add_f64 {t(3)}, {t(3)}, 2.0']
+def upd_setup():
+    # threshold 6.0; DRS off in a quarter of the lanes; slot 0 retired in a quarter of the lanes (a retired car in front of the first
+    # running one), slot 1 in an eighth (all of them behind a retired slot 0: two in front), slot 2 in half (a retired car between two running ones)
+    ins = ['s_mov_b32 s26, 0', 's_mov_b32 s27, 0x40180000', 's_mov_b32 s28, 0x77777777', 's_mov_b32 s29, 0x77777777', 'v_mov_b32 v111, 0x2000',
+           'v_mov_b32 v114, 0', 'v_mov_b32 v115, 0x40180000']
+    for i, (mask, want) in enumerate(((3, 1), (7, 5), (4, 4), (0, 1))):
+        ins += [f'v_and_b32 v108, {mask}, v70', f'v_cmp_eq_u32 vcc, {want}, v108', 'v_mov_b32 v109, 0x200', 's_nop 1',
+                'v_cndmask_b32 v109, 0, v109, vcc', f'v_or_b32 {p(i)}, {i << 4}, v109']
+    return ins
+
 clob = ','.join(f'"v{i}"' for i in list(range(10, 42)) + list(range(50, 66)) + list(range(70, 76))) + ',"vcc","s20","s21","s22","memory"'
 step_clob = ','.join(f'"v{i}"' for i in range(76, 160)) + ',' + ','.join(f'"s{i}"' for i in range(23, 50)) + ','
 commit_clob = ','.join(f'"v{i}"' for i in (76, 77) + tuple(range(80, 96))) + ',"s24","s25","s26","s27","s28","s29",'
-for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE'):
+for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE', 'US', 'UE', 'UF'):
     commit = form in 'SE'
-    step = form in ('LS', 'LE')
+    upd = form[0] == 'U'
+    step = form in ('LS', 'LE') or upd      # (a body of its own on the step forms' registers)
     for shape in ('chain',) if commit or step else ('layer', 'chain'):
         ins = ['v_mbcnt_lo_u32_b32 v70, -1, 0', 'v_mbcnt_hi_u32_b32 v70, -1, v70', 'v_mov_b32 v72, 0', 'v_mov_b32 v73, 0', 'v_mov_b32 v74, 0']
         for i in range(16):
@@ -114,10 +163,12 @@ for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE'):
                 ins += [f'v_add_u32 {p(i)}, 0x{i * 0x61c88647 & 0xffffffff:x}, v71', f'v_mov_b32 v{80 + i}, 0x40000000']
             ins += ['s_mov_b32 s24, 0x9999999a', 's_mov_b32 s25, 0xbfb99999', 's_mov_b32 s26, 0x33333333', 's_mov_b32 s27, 0x3fd33333',
                     's_mov_b64 s[28:29], 0']
-        if step: ins += step_setup()
+        if upd: ins += upd_setup()
+        elif step: ins += step_setup()
         ins += ['s_mov_b64 s[20:21], exec', 's_mov_b32 s22, %0', '1:']
         pairs = [(i, i + 1) for i in range(15)] if shape == 'chain' else [(i, i + 8) for i in range(8)] + [(2 * i, 2 * i + 1) for i in range(8)]
-        if step: ins += step_body(form)
+        if upd: ins += upd_body(form)
+        elif step: ins += step_body(form)
         for a, b in [] if step else pairs:
             ins += comparator(form, a, b)
         if commit:       # (two of the words move on, so the lanes with a hit change from one iteration to the next)

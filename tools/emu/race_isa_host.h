@@ -179,6 +179,46 @@ inline void step_commit4(double *cum, uint32_t *pk, double *lt, double &carry, c
     step_commit3<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum, pk, lt, carry, s, c);
     step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum + 3, pk + 3, lt + 3, carry, s + 3, c);
 }
+// position update of a field without equal times (reference :538-560): the portable body of one slot, slots in order;
+// `first` and the DRS mask are the one emulated lane's bits
+struct UpdLap {
+    double thr;
+    uint64_t drs;
+};
+template <uint32_t DNF, uint32_t DIRTY, uint32_t DRS, bool FIRST>
+inline void upd_commit1(const double *cum, uint32_t *pk, double &leader, double &prev, uint64_t &first, const UpdLap &c)
+{
+    const uint32_t p = pk[0];
+    const bool act = !(p & DNF), fst = FIRST || first != 0u;       // (FIRST: slot 0 of the field, `first` is written only)
+    const double t = cum[0];
+    if (fst) leader = t;
+    const double tbl = t - leader;
+    const bool dirty = !fst && tbl < c.thr;
+    const bool drs = !fst && c.drs != 0u && (t - prev) < 1.0;
+    pk[0] = (p & ~(DRS | DIRTY)) | (dirty ? DIRTY : 0u) | (drs ? DRS : 0u);
+    if (act || FIRST) prev = t;
+    first = fst && !act ? 1u : 0u;
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t DRS, bool FIRST>
+inline void upd_commit2(const double *cum, uint32_t *pk, double &leader, double &prev, uint64_t &first, const UpdLap &c)
+{
+    upd_commit1<DNF, DIRTY, DRS, FIRST>(cum, pk, leader, prev, first, c);
+    upd_commit1<DNF, DIRTY, DRS, false>(cum + 1, pk + 1, leader, prev, first, c);
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t DRS, bool FIRST>
+inline void upd_commit3(const double *cum, uint32_t *pk, double &leader, double &prev, uint64_t &first, const UpdLap &c)
+{
+    upd_commit2<DNF, DIRTY, DRS, FIRST>(cum, pk, leader, prev, first, c);
+    upd_commit1<DNF, DIRTY, DRS, false>(cum + 2, pk + 2, leader, prev, first, c);
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t DRS, bool FIRST>
+inline void upd_commit4(const double *cum, uint32_t *pk, double &leader, double &prev, uint64_t &first, const UpdLap &c)
+{
+    upd_commit3<DNF, DIRTY, DRS, FIRST>(cum, pk, leader, prev, first, c);
+    upd_commit1<DNF, DIRTY, DRS, false>(cum + 3, pk + 3, leader, prev, first, c);
+}
+inline uint64_t lane_mask(bool pred) { return pred ? 1u : 0u; }
+constexpr uint64_t kAllLanes = 1u;
 // threads of the emulated block run one after another: "any lane" is this thread alone (both paths behind an
 // MCGP_ANY test compute the same results, so which one a thread takes does not matter); EMU_FORCE_ANY=1 sends every
 // thread down the "some lane needs it" path, which a single-thread view would otherwise reach only rarely
