@@ -35,7 +35,8 @@ extern "C" {
 /* 6: mcgp_run_trace; later, mcgp_pit_plan and mcgp_run_strategies (added entry points only: no existing struct or
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
  * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too; and
- * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties; mcgp_lap_event and mcgp_run_events */
+ * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties; mcgp_lap_event and mcgp_run_events;
+ * mcgp_run_championship_live */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -336,6 +337,55 @@ typedef struct mcgp_race_state {
 int32_t mcgp_run_from_state(const mcgp_config *cfg, const mcgp_drivers *drv, uint32_t n, uint32_t n_states,
                             const mcgp_race_state *states, uint64_t n_sims, const uint64_t *sim_offsets, uint64_t seed,
                             int32_t device, uint64_t *hist_out, uint8_t *orders_out);
+
+/* Live title odds: a championship whose FIRST race resumes from a mid-race state, and the title odds by finishing position
+ * in one race of the call.  Every argument through fastest_hist is mcgp_run_championship_bonus', same order and meaning,
+ * except that bonus_points and bonus_within may BOTH be NULL (no bonus anywhere; bonus_hist and fastest_hist are then
+ * not read) and that the round trio may be NULL as there.
+ *   state0           NULL: race 0 from the grid, as before.  Else race 0 is mcgp_run_from_state's race of one state:
+ *                    cfgs[0], drvs[0], the state, seed seeds[0], sim_offsets[0] = sim_offset.  Simulation i of the season
+ *                    uses for race 0 the finishing order mcgp_run_from_state gives for id sim_offset + i; with race_hist,
+ *                    race_hist[0] equals that call's hist_out.  Races 1..R-1 are unchanged.  init_points / init_counts
+ *                    are the standings before race 0, as before: nothing is inferred from the state.
+ *   given_race       -1: no conditional table; else 0 .. n_races - 1
+ *   title_given_out  [n][n][n], NULL exactly when given_race == -1.  Cell [d][p][e] counts the simulations in which driver
+ *                    d is classified p + 1-th in race given_race AND driver e is champion.  Champion: position 0 by the
+ *                    ranking above (the largest key; a full tie goes to the lower driver index), judged on the final
+ *                    standings, bonuses included.  ACCUMULATED into.  Invariants: for every (d, p) the sum over e equals
+ *                    race_hist[given_race][d][p]; for every p and e the sum over d equals champ_hist[e][0].
+ * Without state0 and with given_race == -1 every output equals mcgp_run_championship_bonus', cell for cell (with the bonus
+ * arrays NULL: mcgp_run_championship_rounds' or mcgp_run_championship's), from the same launches.
+ * Checks, all before any device lookup, each MCGP_E_BAD_ARG with a message that names the argument: given_race outside
+ * [-1, n_races - 1]; title_given_out given with given_race == -1, or NULL otherwise; with state0: grid_probs[0] given,
+ * cfgs[0].deviates != MCGP_DEVIATES_32 (the resumed race has no 53-bit path), bonus_points[0] > 0 (the laps before the
+ * state are unknown, so the race's fastest lap is not defined), and any field mcgp_run_from_state rejects, with its
+ * message.  Without state0, grid_probs[0] is required as before; every championship check is unchanged.
+ * n_sims == 0 succeeds without a device.  Outputs are added into only after every launch has succeeded.  Any split of
+ * [0, N) over calls, sim_offsets or devices sums to the same counts; device memory does not grow with n_sims (the given
+ * race's orders of one chunk stay in a second staging buffer of 2^22 n bytes until the chunk's standings are ranked).
+ * Race 0 with a state runs mcgp::race_resume_kernel inside the chunk loop; the table is counted by champ_given
+ * (csrc/champ_given.hip.h) behind the chunk's champ_rank: its table is a per-block LDS table when that fits the device's
+ * LDS per block next to a tile of orders, else it is counted by global atomics (with a given race,
+ * mcgp_last_launch_info / mcgp_last_kernel_name describe the last champ_given launch; its LDS bytes tell the two apart:
+ * 256 n rounded up to 16, plus 4 n^3 with the table).  mcgp_last_kernel_ms afterwards = the device time of the whole
+ * call.
+ * Device times on one MI355X, three S60 races x 10^6 simulations, medians of 5 calls (max - min of the five in brackets;
+ * tools/championship_live_time.py): (a) mcgp_run_championship at the parent commit 21.512 ms (1.325; 0.091 without the
+ * first call); (b) the same call at this commit 21.515 ms (1.430); (c) this entry with state0 = NULL and given_race = -1
+ * 21.550 ms (1.121) -- b and c issue a's launches and lie within a's spread; (d) given_race = 0: 21.694 ms (1.358), champ_given
+ * about 0.18 ms; (e) a lap-30 state as race 0: 37.718 ms (0.843), the 30 remaining laps on the generic kernel's code
+ * against 60 laps on the register kernel.
+ * Added entry point only: MCGP_ABI_VERSION stays 6 and a caller tests for the symbol. */
+int32_t mcgp_run_championship_live(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                                   const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                                   const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                                   const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                                   uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                                   uint64_t *gain_hist, uint64_t *race_hist, uint64_t *round_hist, uint64_t *contend_out,
+                                   uint64_t *secure_out, uint64_t *team_round_hist, uint64_t *team_contend_out,
+                                   uint64_t *team_secure_out, const int32_t *bonus_points, const int32_t *bonus_within,
+                                   uint64_t *bonus_hist, uint64_t *fastest_hist, const mcgp_race_state *state0,
+                                   int32_t given_race, uint64_t *title_given_out);
 
 /* Race trace: what happened lap by lap in mcgp_run's simulations (ids sim_offset .. sim_offset + n_sims - 1, the same
  * draws, so hist_out equals mcgp_run's), counted on the device; no per-lap data leaves it.  Everything is read from the

@@ -285,7 +285,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
            'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
-           'mcgp_run_penalties', 'mcgp_run_events')
+           'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -379,6 +379,12 @@ def lib():
             L.mcgp_run_championship_bonus.restype = C.c_int32
             L.mcgp_run_championship_bonus.argtypes = L.mcgp_run_championship_rounds.argtypes + [ip, ip] \
                 + [C.POINTER(C.c_uint64)] * 2
+        if 'mcgp_run_championship_live' not in missing and 'mcgp_run_championship_bonus' not in missing \
+                and 'mcgp_run_championship_rounds' not in missing:
+            # mcgp_run_championship_bonus' arguments, then state0, given_race, title_given_out
+            L.mcgp_run_championship_live.restype = C.c_int32
+            L.mcgp_run_championship_live.argtypes = L.mcgp_run_championship_bonus.argtypes \
+                + [C.POINTER(McgpRaceState), C.c_int32, C.POINTER(C.c_uint64)]
         if 'mcgp_run_matchups' not in missing:
             u64p = C.POINTER(C.c_uint64)
             L.mcgp_run_matchups.restype = C.c_int32

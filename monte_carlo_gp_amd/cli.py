@@ -4,6 +4,8 @@
     python -m monte_carlo_gp_amd.cli backtest --seasons 2024 --seed 42 --simulations 10000000 [--fixtures DIR]
     python -m monte_carlo_gp_amd.cli export-fixtures --seasons 2024 --out DIR
     python -m monte_carlo_gp_amd.cli championship --season 2024 --from-round 18 --simulations 10000000 --seed 7
+    python -m monte_carlo_gp_amd.cli championship --season 2024 --from-round 24 --standings before24.json \
+        --state lap40.json --needs NOR --needs VER --simulations 1000000 --seed 7
     python -m monte_carlo_gp_amd.cli in-race --race Bahrain --season 2024 --offline --state lap30.json --simulations 1000000
     python -m monte_carlo_gp_amd.cli strategy --race Bahrain --season 2024 --offline --driver VER --plan one=:25/HARD \
         --plan two=SOFT:15/MEDIUM,38/SOFT --window 15-30/HARD --simulations 1000000 --seed 7
@@ -32,6 +34,9 @@ lost, the expected on-track passes per race with their 10-90 % range and the fiv
 between lap ends, counted on the device) and adds a 'moves' block to --json.
 in-race runs the rest of the race from one or more mid-race state files (RaceState JSON, simulation.py); with several
 --state files every state sees the same random futures and the columns compare the scenarios.
+championship --state FILE resumes round --from-round from a mid-race state (the other rounds from the grid); --needs DRIVER
+(repeatable, with --needs-round K, default --from-round) prints that driver's title odds by finishing position in the
+round, with the two strongest rivals' given that finish (counted on the device), and adds 'title_needs' to --json.
 strategy compares pit strategies for one driver: `model` (the race model's own stops) first, then each --plan
 NAME=START:LAP/COMP,LAP/COMP (START empty: the model's start) and each lap of a --window A-B/COMP sweep, all with common
 random numbers, from the grid or from a --state file.
@@ -54,6 +59,8 @@ import os
 import random
 import sys
 import time
+
+import numpy as np
 
 from . import config as K
 from .predictor import F1Predictor, circuit_info
@@ -891,15 +898,38 @@ def cmd_championship(args) -> int:
         # the 2019-2024 rule: a point for the race's fastest lap, if classified in the top ten
         for race in races:
             race.update(fastest_lap_points=FASTEST_LAP_POINT, fastest_lap_within=FASTEST_LAP_WITHIN)
+    live = {}
+    state = None
+    if args.state:
+        # round --from-round is under way: it resumes from the state, in the field's own driver order
+        from .simulation import RaceState
+        with open(args.state) as f:
+            state = RaceState.from_json(json.load(f))
+        live['drivers'] = [str(d) for d in races[0]['grid_probs']]
+        races[0] = {k: v for k, v in races[0].items() if k not in ('grid_probs', 'fastest_lap_points', 'fastest_lap_within')}
+        races[0]['state'] = state
+    needs_round = args.from_round if args.needs_round is None else args.needs_round
+    if args.needs:
+        if not args.from_round <= needs_round < args.from_round + len(jobs):
+            raise ValueError(f'--needs-round must be in [{args.from_round}, {args.from_round + len(jobs) - 1}], got '
+                             f'{needs_round}')
+        live['given_race'] = needs_round - args.from_round
+    elif args.needs_round is not None:
+        raise ValueError('--needs-round goes with --needs DRIVER')
     t0 = time.perf_counter()
     res = run_championship(races, args.simulations, standings=standings, device=args.device,
-                           return_race_histograms=True, by_round=args.by_round)
+                           return_race_histograms=True, by_round=args.by_round, **live)
     dt = time.perf_counter() - t0
+    for d in args.needs or []:
+        if d not in res.drivers:
+            raise ValueError(f'--needs {d}: not in the field {res.drivers}')
     partial = args.from_round > 1 and not standings
     what = f'points from round {args.from_round} on' if partial else 'season standings'
     print(f"\n{'=' * 60}\nChampionship {args.season}: rounds {args.from_round}-{args.from_round + len(jobs) - 1} "
           f"({len(jobs)} Grands Prix), {what}\nSimulations: {args.simulations}  seed: {args.seed}   "
           f"({args.simulations * len(jobs) / dt:,.0f} race simulations/s)\n{'=' * 60}\n")
+    if state is not None:
+        print(f"Round {args.from_round} ({jobs[0][1]['race']}) resumes from {args.state} (after lap {state.lap})\n")
     _bars(f"DRIVERS' TITLE PROBABILITIES ({what})", res.title_probabilities)
     print()
     _bars(f"CONSTRUCTORS' TITLE PROBABILITIES ({what})", res.constructor_title_probabilities)
@@ -925,6 +955,9 @@ def cmd_championship(args) -> int:
             print(f"{args.from_round + k:>5}  {str(entry['race'])[:22]:<22} {decided * 100:7.1f}%  "
                   f"{sum(1 for v in cont.values() if v > 0.01):>13}  "
                   + '  '.join(f'{d} {v * 100:.1f}%' for d, v in top if v > 0))
+    needs = {d: title_needs_table(res, d) for d in args.needs or []}
+    for d, rows in needs.items():
+        _print_title_needs(d, rows, needs_round, str(jobs[needs_round - args.from_round][1]['race']))
     if args.json:
         n = res.n_simulations
         out = dict(season=args.season, from_round=args.from_round, points_from_round_only=partial,
@@ -950,9 +983,39 @@ def cmd_championship(args) -> int:
                 fastest_lap_probabilities_by_round=[
                     {d: int(row[i]) / max(res.n_simulations, 1) for i, d in enumerate(res.drivers)}
                     for row in res.fastest_lap_counts])
+        if state is not None:
+            out['state_lap'] = int(state.lap)
+        if args.needs:
+            out['given_round'] = needs_round
+            out['title_needs'] = {d: {str(pos): dict(p_finish=row['p_finish'], title=row['title'])
+                                      for pos, row in rows.items()} for d, rows in needs.items()}
         with open(args.json, 'w') as f:
             json.dump(out, f)
     return 0
+
+
+def title_needs_table(res, driver) -> dict:
+    """{position: {'p_finish', 'count', 'title': {driver: P(that driver is champion | `driver` finishes there)}}} for the
+    positions `driver` took in the given race of a run_championship(..., given_race=...) result; 'title' lists the
+    drivers with a non-zero count, `driver` always."""
+    table = res.title_given[res.drivers.index(driver)]
+    rows = {}
+    for p in np.nonzero(table.sum(axis=1))[0]:
+        count = int(table[p].sum())
+        title = {e: int(table[p, i]) / count for i, e in enumerate(res.drivers) if table[p, i] or e == driver}
+        rows[int(p) + 1] = dict(p_finish=count / max(res.n_simulations, 1), count=count, title=title)
+    return rows
+
+
+def _print_title_needs(driver, rows, round_no, race):
+    """One row per finishing position of `driver`: P(position), P(title | position) and the title odds of the two
+    strongest rivals given that finish."""
+    print(f'\nWHAT {driver} NEEDS (round {round_no}, {race})\n' + '-' * 60)
+    print(f"{'finish':>6}  {'P(finish)':>9}  {'P(title | finish)':>17}  rivals' title odds given that finish")
+    for pos, row in sorted(rows.items()):
+        rivals = sorted(((e, v) for e, v in row['title'].items() if e != driver and v > 0), key=lambda kv: -kv[1])[:2]
+        print(f"{'P' + str(pos):>6}  {row['p_finish'] * 100:8.1f}%  {row['title'][driver] * 100:16.1f}%  "
+              + '  '.join(f'{e} {v * 100:.1f}%' for e, v in rivals))
 
 
 def main(argv=None) -> int:
@@ -1019,6 +1082,15 @@ def main(argv=None) -> int:
     c.add_argument('--fastest-lap-point', action='store_true',
                    help='score the 2019-2024 fastest-lap point: 1 point to the driver who sets the fastest lap of a round, '
                         'if classified in the top ten (every round then runs on the slower lap-time-tracking kernel)')
+    c.add_argument('--state', type=str, default=None,
+                   help='race state JSON (RaceState.to_json) of round --from-round, which then resumes from it (as in-race '
+                        'does) instead of starting from the grid; --standings are those before that round')
+    c.add_argument('--needs', metavar='DRIVER', type=str, action='append', default=None,
+                   help="title odds by that driver's finishing position in one round: P(finish), P(title | finish) and the "
+                        'two strongest rivals given that finish (and in --json); repeat for more drivers')
+    c.add_argument('--needs-round', type=int, default=None,
+                   help='with --needs: the round (absolute number) whose finishing positions are conditioned on; default '
+                        '--from-round')
     c.set_defaults(fn=cmd_championship)
     r = sub.add_parser('in-race', help='win and podium odds from a mid-race state (one column per --state)')
     r.add_argument('--season', type=int, default=2025)

@@ -21,6 +21,7 @@
 #include "moves.hip.h"
 #include "fastest.hip.h"
 #include "champ_bonus.hip.h"
+#include "champ_given.hip.h"
 #include "plan_pack.h"
 #include "penalty_pack.h"
 #include "event_pack.h"
@@ -1454,17 +1455,29 @@ struct ChampBonus {
     uint64_t *bonus_hist, *fastest_hist;    // [R][n] each, or NULL
 };
 
-// mcgp_run_championship (rounds == NULL), mcgp_run_championship_rounds and mcgp_run_championship_bonus: one body, so that
-// the four season outputs of the calls come from the same launches.  A race without a bonus goes through launch(); a
-// race with one runs race_fastest_kernel (fastest.hip.h) on the same chunk, and champ_bonus behind its champ_accumulate.
+// What mcgp_run_championship_live adds (NULL for the other three calls: race 0 from the grid, no conditional table).
+struct ChampLive {
+    const mcgp_race_state *state0;      // NULL: race 0 from the grid
+    int32_t given_race;                 // -1: no conditional table
+    uint64_t *title_given;              // [n][n][n], NULL exactly when given_race == -1
+};
+
+// mcgp_run_championship (rounds == NULL), mcgp_run_championship_rounds, mcgp_run_championship_bonus and
+// mcgp_run_championship_live: one body, so that the four season outputs of the calls come from the same launches.  A race
+// without a bonus goes through launch(); a race with one runs race_fastest_kernel (fastest.hip.h) on the same chunk, and
+// champ_bonus behind its champ_accumulate.  With live->state0, race 0 is race_resume_kernel's of that one state
+// (resume.hip.h); with live->given_race >= 0 that race's orders go to a staging buffer of their own, which champ_given
+// (champ_given.hip.h) reads behind the chunk's champ_rank.  Without `live` the launches are what they always were.
 static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
                                 const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
                                 const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
                                 const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
                                 uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
                                 uint64_t *gain_hist, uint64_t *race_hist, const ChampRoundsOut *rounds,
-                                const ChampBonus *bonus = nullptr)
+                                const ChampBonus *bonus = nullptr, const ChampLive *live = nullptr)
 {
+    const mcgp_race_state *state0 = live ? live->state0 : nullptr;
+    const int32_t given_race = live ? live->given_race : -1;
     // ---- every argument is checked before any device is looked up
     if (rounds) {
         if (!rounds->round_hist) return fail(MCGP_E_BAD_ARG, "round_hist is NULL");
@@ -1482,6 +1495,12 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
     if (n_teams < 1 || n_teams > n) return fail(MCGP_E_BAD_ARG, "n_teams must be in [1, n]");
     for (uint32_t d = 0; d < n; ++d)
         if (team[d] < 0 || (uint32_t)team[d] >= n_teams) return fail(MCGP_E_BAD_ARG, "a team index is outside [0, n_teams)");
+    if (given_race < -1 || given_race >= (int32_t)n_races)
+        return fail(MCGP_E_BAD_ARG, "given_race = " + std::to_string(given_race) + " is outside [-1, n_races - 1]");
+    if (live && given_race == -1 && live->title_given)
+        return fail(MCGP_E_BAD_ARG, "title_given_out must be NULL when given_race is -1");
+    if (live && given_race >= 0 && !live->title_given)
+        return fail(MCGP_E_BAD_ARG, "title_given_out is NULL (given_race names a race)");
     constexpr uint64_t kMaxPoints = (1u << mcgp::kChampPointsBits) - 1, kMaxCount = (1u << mcgp::kChampCountBits) - 1;
     uint64_t G = 0, awarded = 0;         // most points one driver can gain in these races; points the races award in all
     uint32_t n_cb = 0;                   // countback races
@@ -1526,7 +1545,21 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         }
     }
     std::vector<mcgp::KParams> kps(n_races);
+    mcgp::ResumeState st0;
+    std::memset(&st0, 0, sizeof(st0));
     for (uint32_t r = 0; r < n_races; ++r) {
+        if (r == 0 && state0) {
+            // race 0 from a state: mcgp_run_from_state's checks of one state, with its messages
+            if (grid_probs[0]) return fail(MCGP_E_BAD_ARG, "grid_probs[0] must be NULL when state0 is given");
+            int rc = build_params_32(&cfgs[0], &drvs[0], nullptr, n, "a resumed race runs", &kps[0]);
+            if (rc != MCGP_OK) return rc;
+            if (any_bonus && bonus->points[0] > 0)
+                return fail(MCGP_E_BAD_ARG, "bonus_points[0]: a race resumed from a state has no fastest-lap bonus (the laps "
+                                            "before the state are unknown)");
+            rc = pack_state(state0, n, cfgs[0].total_laps, sim_offset, &st0);
+            if (rc != MCGP_OK) return rc;
+            continue;
+        }
         if (!grid_probs[r]) return fail(MCGP_E_BAD_ARG, "a grid_probs pointer of the championship is NULL");
         int rc = build_params(&cfgs[r], &drvs[r], grid_probs[r], n, &kps[r]);
         if (rc == MCGP_OK) rc = check_wide(kps[r]);
@@ -1556,7 +1589,9 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
     const size_t round_cells = rh_cells + 2 * rc_cells + trh_cells + 2 * trc_cells;
     // bonus [R][n] | fastest [R][n], behind the per-round counts
     const size_t bonus_cells = bonus_pts ? (size_t)n_races * n : 0;
-    const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells + round_cells + 2 * bonus_cells;
+    // title_given [n][n][n], behind the bonus counts
+    const size_t given_cells = given_race >= 0 ? (size_t)n * n * n : 0;
+    const size_t hist_cells = champ_cells + team_cells + gain_cells + race_cells + round_cells + 2 * bonus_cells + given_cells;
     std::vector<uint32_t> driver_rem, team_rem;
     if (rounds) mcgp::champ_remaining(n_races, n, points, n_members.data(), n_teams, &driver_rem, &team_rem, bonus_pts);
     // the parameter blocks of the bonus races, in race order (kp_index[r]: the race's block, -1 without a bonus)
@@ -1590,14 +1625,30 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         if (bonus_pts)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_fastest_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
+        // champ_given's table: in the block's LDS when it fits the budget next to the tile, else by global atomics.
+        // MCGP_LDS_PER_BLOCK is read per call here, as mcgp_run_matchups reads it.
+        const size_t given_budget = lds_limit(c.lds_per_block);
+        const bool given_in_lds = mcgp::champ_given_lds(n, true).bytes <= given_budget;
+        const uint32_t given_lds = mcgp::champ_given_lds(n, given_in_lds).bytes;
+        if (given_cells) {
+            if (given_lds > given_budget)
+                return fail(MCGP_E_HIP, "the title-by-finish kernel needs " + std::to_string(given_lds) +
+                                            " bytes of LDS, the device offers " + std::to_string(given_budget) + " per block");
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::champ_given),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)given_lds));
+        }
+        const KernelFn resume_fn = reinterpret_cast<KernelFn>(&mcgp::race_resume_kernel);   // (for its register count)
         // workspace: orders staging of one chunk | the chunk's standing keys | tables | histograms | the bonus races'
-        // parameter blocks | the chunk's fastest-lap bytes (two rows of the chunk's capacity)
+        // parameter blocks | the chunk's fastest-lap bytes (two rows of the chunk's capacity) | the given race's orders
+        // of the chunk | the resumed race's parameter block and state
         const uint64_t cap = std::min(n_sims, kOrdersChunk);
         Layout ws;
         const size_t o_orders = ws.add(cap * n), o_keys = ws.add((size_t)words * n * cap * 8), o_add = ws.add(add.size() * 8);
         const size_t o_init = ws.add(init_key.size() * 8), o_mem = ws.add(members.size()), o_nmem = ws.add(n_teams);
         const size_t o_ipts = ws.add(4 * n), o_trem = ws.add(4 * team_rem.size()), o_hist = ws.add(hist_cells * 8);
         const size_t o_bkp = ws.add(sizeof(mcgp::KParams) * bonus_kps.size()), o_fl = ws.add(bonus_pts ? 2 * cap : 0);
+        const size_t o_keep = ws.add(given_cells ? cap * n : 0), o_lkp = ws.add(state0 ? sizeof(mcgp::KParams) : 0);
+        const size_t o_lst = ws.add(state0 ? sizeof(mcgp::ResumeState) : 0);
         int r = c.work.reserve(ws.bytes);
         if (r != MCGP_OK) return r;
         uint8_t *d_orders = c.work.at<uint8_t>(o_orders);
@@ -1608,6 +1659,12 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         unsigned long long *h_round = h_race + race_cells, *h_contend = h_round + rh_cells, *h_secure = h_contend + rc_cells;
         unsigned long long *h_tround = h_secure + rc_cells, *h_tcontend = h_tround + trh_cells, *h_tsecure = h_tcontend + trc_cells;
         unsigned long long *h_bonus = h_tsecure + trc_cells, *h_fastest = h_bonus + bonus_cells;
+        unsigned long long *h_given = h_fastest + bonus_cells;
+        uint8_t *d_keep = c.work.at<uint8_t>(o_keep);
+        if (state0) {
+            HIP_TRY(hipMemcpyAsync(c.work.at(o_lkp), &kps[0], sizeof(mcgp::KParams), hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(c.work.at(o_lst), &st0, sizeof(mcgp::ResumeState), hipMemcpyHostToDevice, nullptr));
+        }
         if (!bonus_kps.empty())
             HIP_TRY(hipMemcpyAsync(c.work.at(o_bkp), bonus_kps.data(), sizeof(mcgp::KParams) * bonus_kps.size(),
                                    hipMemcpyHostToDevice, nullptr));
@@ -1629,14 +1686,30 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         uint64_t round_per_cu = rounds ? c.lds_per_block / round_lds : 1;
         if (round_per_cu > 8) round_per_cu = 8;
         const uint64_t round_cap = (uint64_t)c.cu_count * round_per_cu;
+        uint64_t given_per_cu = given_budget / given_lds;
+        if (given_per_cu > 8) given_per_cu = 8;
+        const uint64_t given_cap = (uint64_t)c.cu_count * given_per_cu;
         for (uint64_t done = 0; done < n_sims; done += cap) {
             const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
             // chunk-outer, race-inner: every race of the chunk through mcgp_run's own launch path, its orders into the
             // staging buffer, then folded into the keys before the next race overwrites them
             for (uint32_t rr = 0; rr < n_races; ++rr) {
                 unsigned long long *h_this = race_hist ? h_race + (size_t)rr * n * n : c.d_hist;
-                if (kp_index[rr] < 0) {
-                    r = launch(c, kps[rr], m, sim_offset + done, seeds[rr], nullptr, h_this, d_orders, nullptr);
+                // the given race's orders outlive the race loop: they go to a buffer no other race writes
+                uint8_t *d_ord = (int32_t)rr == given_race ? d_keep : d_orders;
+                if (rr == 0 && state0) {
+                    // mcgp_run_from_state's launch of one state (m <= 2^22: one launch); ids st0.sim_offset + done + i
+                    uint32_t grid = 0, block = 0, lds = 0;
+                    r = generic_geometry(c, resume_fn, "resume", n, m, &grid, &block, &lds);
+                    if (r != MCGP_OK) return r;
+                    const uint64_t n_batches = (m + block - 1) / block;
+                    hipLaunchKernelGGL(mcgp::race_resume_kernel, dim3(grid, 1), dim3(block), lds, nullptr,
+                                       c.work.at<const mcgp::KParams>(o_lkp), c.work.at<const mcgp::ResumeState>(o_lst), m, done,
+                                       (uint32_t)seeds[0], (uint32_t)(seeds[0] >> 32), h_this, d_ord, (uint32_t)n_batches);
+                    HIP_TRY(hipGetLastError());
+                    note_launch(c, grid, block, lds, "mcgp::race_resume_kernel");
+                } else if (kp_index[rr] < 0) {
+                    r = launch(c, kps[rr], m, sim_offset + done, seeds[rr], nullptr, h_this, d_ord, nullptr);
                     if (r != MCGP_OK) return r;
                 } else {
                     // the generic kernel's block shape and LDS (m <= 2^22: one launch)
@@ -1646,14 +1719,14 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
                     const uint64_t n_batches = (m + block - 1) / block;
                     hipLaunchKernelGGL(mcgp::race_fastest_kernel, dim3(grid), dim3(block), lds, nullptr,
                                        c.work.at<const mcgp::KParams>(o_bkp) + kp_index[rr], m, sim_offset + done,
-                                       (uint32_t)seeds[rr], (uint32_t)(seeds[rr] >> 32), h_this, d_orders, d_fl, d_fl + cap,
+                                       (uint32_t)seeds[rr], (uint32_t)(seeds[rr] >> 32), h_this, d_ord, d_fl, d_fl + cap,
                                        (uint32_t)n_batches);
                     HIP_TRY(hipGetLastError());
                     note_launch(c, grid, block, lds, "mcgp::race_fastest_kernel");
                 }
                 const uint64_t tiles = (m + mcgp::kChampAccBlock - 1) / mcgp::kChampAccBlock;
                 hipLaunchKernelGGL(mcgp::champ_accumulate, dim3((uint32_t)std::min(tiles, acc_cap)), dim3(mcgp::kChampAccBlock), 0,
-                                   nullptr, d_orders, m, n, words, cap, d_keys,
+                                   nullptr, d_ord, m, n, words, cap, d_keys,
                                    c.work.at<const uint64_t>(o_add) + (size_t)rr * n * words, c.work.at<const uint64_t>(o_init),
                                    rr == 0 ? 1u : 0u);
                 HIP_TRY(hipGetLastError());
@@ -1682,6 +1755,15 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
                                c.work.at<const uint8_t>(o_nmem), c.work.at<const int32_t>(o_ipts), gain_cols, gain_in_lds ? 1u : 0u,
                                h_champ, h_team, h_gain);
             HIP_TRY(hipGetLastError());
+            if (given_cells) {
+                // the chunk's final keys and the kept orders, before the next chunk starts both afresh
+                const uint64_t gtiles = (m + mcgp::kChampGivenBlock - 1) / mcgp::kChampGivenBlock;
+                hipLaunchKernelGGL(mcgp::champ_given, dim3((uint32_t)std::min(gtiles, given_cap)), dim3(mcgp::kChampGivenBlock),
+                                   given_lds, nullptr, d_keys, d_keep, m, cap, n, words, given_in_lds ? 1u : 0u, h_given);
+                HIP_TRY(hipGetLastError());
+                // (its dynamic LDS tells the two modes apart: the tile alone, or the tile and the table)
+                note_launch(c, (uint32_t)std::min(gtiles, given_cap), mcgp::kChampGivenBlock, given_lds, "mcgp::champ_given");
+            }
         }
         return counts.download(h_champ, hist_cells);
     });
@@ -1700,6 +1782,7 @@ static int32_t run_championship(uint32_t n_races, const mcgp_config *cfgs, const
         segs.push_back({bonus->bonus_hist, bonus_cells});
         segs.push_back({bonus->fastest_hist, bonus_cells});
     }
+    if (given_cells) segs.push_back({live->title_given, given_cells});      // (without `bonus` there are no bonus cells)
     counts.add_to(segs);
     return MCGP_OK;
 }
@@ -1748,6 +1831,30 @@ int32_t mcgp_run_championship_bonus(uint32_t n_races, const mcgp_config *cfgs, c
     return run_championship(n_races, cfgs, drvs, grid_probs, n, n_sims, sim_offset, seeds, points, countback, init_points,
                             init_counts, team, n_teams, device, champ_hist, team_hist, gain_hist, race_hist,
                             by_round ? &rounds : nullptr, &bonus);
+}
+
+int32_t mcgp_run_championship_live(uint32_t n_races, const mcgp_config *cfgs, const mcgp_drivers *drvs,
+                                   const double *const *grid_probs, uint32_t n, uint64_t n_sims, uint64_t sim_offset,
+                                   const uint64_t *seeds, const int32_t *points, const uint8_t *countback,
+                                   const int32_t *init_points, const int32_t *init_counts, const int32_t *team,
+                                   uint32_t n_teams, int32_t device, uint64_t *champ_hist, uint64_t *team_hist,
+                                   uint64_t *gain_hist, uint64_t *race_hist, uint64_t *round_hist, uint64_t *contend_out,
+                                   uint64_t *secure_out, uint64_t *team_round_hist, uint64_t *team_contend_out,
+                                   uint64_t *team_secure_out, const int32_t *bonus_points, const int32_t *bonus_within,
+                                   uint64_t *bonus_hist, uint64_t *fastest_hist, const mcgp_race_state *state0,
+                                   int32_t given_race, uint64_t *title_given_out)
+{
+    const ChampRoundsOut rounds = {round_hist, contend_out, secure_out, team_round_hist, team_contend_out, team_secure_out};
+    const ChampBonus bonus = {bonus_points, bonus_within, bonus_hist, fastest_hist};
+    const ChampLive live = {state0, given_race, title_given_out};
+    const bool by_round = round_hist || contend_out || secure_out;      // all three NULL: no per-round work
+    if (!by_round && (team_round_hist || team_contend_out || team_secure_out))
+        return fail(MCGP_E_BAD_ARG, "team_round_hist, team_contend_out and team_secure_out need round_hist, contend_out and "
+                                    "secure_out");
+    const bool with_bonus = bonus_points || bonus_within;               // both NULL: no bonus anywhere
+    return run_championship(n_races, cfgs, drvs, grid_probs, n, n_sims, sim_offset, seeds, points, countback, init_points,
+                            init_counts, team, n_teams, device, champ_hist, team_hist, gain_hist, race_hist,
+                            by_round ? &rounds : nullptr, with_bonus ? &bonus : nullptr, &live);
 }
 
 int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,

@@ -1677,7 +1677,12 @@ class ChampionshipResult:
     When some race has a fastest-lap bonus (the races' `fastest_lap_points`; None otherwise, include/mcgp.h:
     mcgp_run_championship_bonus): fastest_lap_counts [R][n] = simulations in which the driver set race r's fastest lap,
     bonus_counts [R][n] = those in which the driver also took the bonus (rows of races without a bonus are zero), and
-    bonus_points [R] the bonus of each race."""
+    bonus_points [R] the bonus of each race.
+
+    With given_race (None otherwise, include/mcgp.h: mcgp_run_championship_live): title_given [n][n][n] = simulations in
+    which [driver] is classified [position - 1] in race given_race and [champion] takes the title; summed over the
+    champion it is that race's position histogram, summed over the driver it is champ_hist[champion][0] for every
+    position."""
     drivers: list
     teams: list
     n_simulations: int
@@ -1696,6 +1701,8 @@ class ChampionshipResult:
     bonus_counts: np.ndarray | None = None
     bonus_points: list | None = None
     team_index: list | None = None           # [n] index into `teams` of each driver
+    title_given: np.ndarray | None = None    # [n][n][n] = [driver][position - 1 in race given_race][champion], or None
+    given_race: int | None = None            # index into the call's races
 
     @property
     def title_probabilities(self) -> dict:
@@ -1808,6 +1815,36 @@ class ChampionshipResult:
         return out
 
 
+    # ---- title odds by finishing position (run_championship(..., given_race=k))
+    def _given(self, what):
+        if self.title_given is None:
+            raise ValueError(f'{what}: not counted (it needs run_championship(..., given_race=...))')
+        return np.asarray(self.title_given, np.int64)
+
+    def _driver_index(self, driver):
+        if str(driver) not in self.drivers:
+            raise KeyError(f'no driver {driver!r}')
+        return self.drivers.index(str(driver))
+
+    def title_probability_given(self, driver, position, champion=None):
+        """P(`champion` takes the title | `driver` is classified `position` (1-based) in the given race); `champion`
+        defaults to `driver`.  None when no simulation has that finish."""
+        table = self._given('title_probability_given')
+        d, e = self._driver_index(driver), self._driver_index(driver if champion is None else champion)
+        position = int(position)
+        if not 1 <= position <= len(self.drivers):
+            raise ValueError(f'position must be in [1, {len(self.drivers)}], got {position}')
+        finishes = int(table[d, position - 1].sum())
+        return int(table[d, position - 1, e]) / finishes if finishes else None
+
+    def title_needs(self, driver) -> dict:
+        """{position: P(`driver` takes the title | `driver` is classified there in the given race)} for the positions
+        that occurred."""
+        table = self._given('title_needs')
+        d = self._driver_index(driver)
+        return {int(p) + 1: int(table[d, p, d]) / int(table[d, p].sum()) for p in np.nonzero(table[d].sum(axis=1))[0]}
+
+
 def _standings_arrays(standings, drivers):
     """{driver: points} or {driver: {'points': p, 'finishes': [count of P1, P2, ...]}} -> (points [n], counts [n][n])."""
     n = len(drivers)
@@ -1834,7 +1871,7 @@ def _standings_arrays(standings, drivers):
 
 
 def run_championship(races, n_simulations, *, standings=None, seed=None, sim_offset=0, device=0, set_pop=None,
-                     return_race_histograms=False, by_round=False) -> ChampionshipResult:
+                     return_race_histograms=False, by_round=False, drivers=None, given_race=None) -> ChampionshipResult:
     """Drivers' and constructors' championship over a calendar of races (include/mcgp.h: mcgp_run_championship).
 
     `races`: a list of dicts with the keys run_monte_carlo_batch takes (`config`, `grid_probs`, `base_pace`,
@@ -1860,15 +1897,38 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
     `by_round=True` also counts, on the device, the standings after every race of the call (include/mcgp.h:
     mcgp_run_championship_rounds): who leads, who is still in contention and whose title is secure after each race,
     for drivers and constructors (ChampionshipResult.round_hist and the fields and properties next to it).  The other
-    results are the same either way."""
+    results are the same either way.
+
+    Live title odds (include/mcgp.h: mcgp_run_championship_live).  races[0] may carry `state`, a RaceState, instead of
+    `grid_probs`: that race is then RaceSimulator.run_from_state's from the state (32-bit deviates, no fastest-lap bonus),
+    simulation i of the season taking the finishing order that call gives id sim_offset + i.  The driver order is then
+    `drivers` if given, else the state's grid order (run_from_state's rule); the later races' grid_probs must have the
+    same driver set.  `standings` are those before race 0: nothing is inferred from the state.  `given_race=k` also counts
+    ChampionshipResult.title_given, the title odds by finishing position in races[k] (title_probability_given,
+    title_needs).  Without a state and given_race the call goes where it always went."""
     races = list(races)
     if not races:
         raise ValueError('a championship needs at least one race')
     if len(races) > MAX_RACES:
         raise ValueError(f'at most {MAX_RACES} races per call, got {len(races)}')
     set_pop = dict(set_pop or DEFAULT_SET_POP)
-    drivers = [str(d) for d in races[0]['grid_probs'].keys()]
+    state = races[0].get('state')
+    if state is not None and races[0].get('grid_probs') is not None:
+        raise ValueError('race 0: give either state or grid_probs, not both')
+    for r, race in enumerate(races[1:], 1):
+        if race.get('state') is not None:
+            raise ValueError(f'race {r}: only the first race of the call can start from a state')
+    if drivers is not None:
+        drivers = [str(d) for d in drivers]
+    elif state is not None:
+        drivers = [str(c.driver) for c in state.cars]
+    else:
+        drivers = [str(d) for d in races[0]['grid_probs'].keys()]
     n = len(drivers)
+    if given_race is not None:
+        given_race = int(given_race)
+        if not 0 <= given_race < len(races):
+            raise ValueError(f'given_race must be an index into races, in [0, {len(races) - 1}], got {given_race}')
     if not (1 <= n <= N.MAX_CARS):
         raise ValueError(f'number of drivers must be in [1, {N.MAX_CARS}], got {n}')
     rng = random.Random(seed)
@@ -1878,13 +1938,19 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
     bonus_pts = np.zeros(len(races), np.int32)
     bonus_within = np.ones(len(races), np.int32)
     for r, race in enumerate(races):
-        gp = {str(k): v for k, v in race['grid_probs'].items()}
-        if set(gp) != set(drivers) or len(gp) != n:
-            raise ValueError(f'race {r}: its drivers differ from the first race\'s')
+        live_race = r == 0 and state is not None
+        if not live_race:
+            gp = {str(k): v for k, v in race['grid_probs'].items()}
+            if set(gp) != set(drivers) or len(gp) != n:
+                raise ValueError(f'race {r}: its drivers differ from the first race\'s')
+        elif int(race.get('deviates', 32)) != 32:
+            raise ValueError('race 0: a race from a state runs with deviates=32 only')
+        elif int(race.get('fastest_lap_points', 0)) > 0:
+            raise ValueError('race 0: a race from a state has no fastest-lap bonus (the laps before the state are unknown)')
         probs.append(_Problem(race['config'], drivers, race['base_pace'], race['tire_deg'], race['driver_variance'],
                               race.get('driver_dnf_rates'), race.get('track_condition', 'dry'), set_pop,
                               race.get('deviates', 32)))
-        grids.append(RaceSimulator._grid_matrix(gp, drivers))
+        grids.append(None if live_race else RaceSimulator._grid_matrix(gp, drivers))
         race_seed = race.get('seed')
         seeds.append(RaceSimulator._resolve_seed(rng.getrandbits(63) if race_seed is None else race_seed))
         table = [int(x) for x in race.get('points', DEFAULT_POINTS)]
@@ -1932,9 +1998,15 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
     if with_bonus and not hasattr(lib, 'mcgp_run_championship_bonus'):
         raise N.McgpError(-1, 'the loaded library does not export mcgp_run_championship_bonus: fastest_lap_points needs '
                               'a library built from sources that have it')
+    live = state is not None or given_race is not None
+    if live and not hasattr(lib, 'mcgp_run_championship_live'):
+        raise N.McgpError(-1, 'the loaded library does not export mcgp_run_championship_live: a state or given_race needs '
+                              'a library built from sources that have it')
+    state_arrays = state.arrays(drivers, races[0]['config'].total_laps) if state is not None else None
+    c_state = state.c_struct(state_arrays) if state is not None else None
     cfgs = (N.McgpConfig * R)(*[p.cfg for p in probs])
     drvs = (N.McgpDrivers * R)(*[p.drv for p in probs])
-    gptrs = (C.POINTER(C.c_double) * R)(*[_dptr(g) for g in grids])
+    gptrs = (C.POINTER(C.c_double) * R)(*[C.POINTER(C.c_double)() if g is None else _dptr(g) for g in grids])
     seeds_c = (C.c_uint64 * R)(*seeds)
     i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
     u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
@@ -1947,18 +2019,27 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
         args = (R, cfgs, drvs, gptrs, n, int(count), int(sim_offset) + int(offset), seeds_c, i32(points),
                 countback.ctypes.data_as(C.POINTER(C.c_uint8)), i32(init_pts32), i32(init_counts32), i32(team), T, int(dev),
                 u64(ch), u64(th), u64(gh), u64(rh) if rh is not None else None)
-        rounds = bonus = ()
+        rounds = bonus = given = ()
         if by_round:
             rounds = tuple(np.zeros(shape, np.uint64) for shape in ((R, n, n), (R, n), (R, n), (R, T, T), (R, T), (R, T)))
         if with_bonus:
             bonus = (np.zeros((R, n), np.uint64), np.zeros((R, n), np.uint64))          # bonus_hist, fastest_hist
+        if given_race is not None:
+            given = (np.zeros((n, n, n), np.uint64),)
+        if live:
+            rc = lib.mcgp_run_championship_live(
+                *args, *([u64(a) for a in rounds] if by_round else [None] * 6),
+                *([i32(bonus_pts), i32(bonus_within)] + [u64(a) for a in bonus] if with_bonus else [None] * 4),
+                C.byref(c_state) if c_state is not None else None, -1 if given_race is None else given_race,
+                u64(given[0]) if given else None)
+        elif with_bonus:
             rc = lib.mcgp_run_championship_bonus(*args, *([u64(a) for a in rounds] if by_round else [None] * 6),
                                                  i32(bonus_pts), i32(bonus_within), *[u64(a) for a in bonus])
         elif by_round:
             rc = lib.mcgp_run_championship_rounds(*args, *[u64(a) for a in rounds])
         else:
             rc = lib.mcgp_run_championship(*args)
-        return (ch, th, gh, rh) + rounds + bonus, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
+        return (ch, th, gh, rh) + rounds + bonus + given, rc, (lib.mcgp_last_error().decode('utf-8', 'replace') if rc != 0 else '')
 
     if len(devices) == 1:
         parts = [run_shard(devices[0], 0, n_simulations)]
@@ -1973,6 +2054,7 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
         if rc != 0:
             raise N.McgpError(rc, msg)
     total = lambda k: np.sum([p[0][k] for p in parts], axis=0, dtype=np.uint64).astype(np.int64)
+    at_bonus = 4 + (6 if by_round else 0)            # the shard tuple: four season arrays, rounds, bonus, title_given
     return ChampionshipResult(
         drivers=drivers, teams=team_names, n_simulations=n_simulations, champ_hist=total(0), team_hist=total(1),
         gain_hist=total(2), initial_points={d: int(init_pts[i]) for i, d in enumerate(drivers)},
@@ -1980,8 +2062,10 @@ def run_championship(races, n_simulations, *, standings=None, seed=None, sim_off
         **({k: total(4 + i) for i, k in enumerate(('round_hist', 'contend', 'secure', 'team_round_hist', 'team_contend',
                                                    'team_secure'))} if by_round else {}),
         team_index=[int(t) for t in team],
-        **(dict(bonus_counts=total(-2), fastest_lap_counts=total(-1), bonus_points=[int(b) for b in bonus_pts])
-           if with_bonus else {}))
+        **(dict(bonus_counts=total(at_bonus), fastest_lap_counts=total(at_bonus + 1), bonus_points=[int(b) for b in bonus_pts])
+           if with_bonus else {}),
+        **(dict(title_given=total(at_bonus + (2 if with_bonus else 0)), given_race=given_race)
+           if given_race is not None else {}))
 
 
 def histogram_to_probs(hist, drivers, n_simulations):

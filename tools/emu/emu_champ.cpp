@@ -4,7 +4,8 @@
 // champ_accumulate and champ_rank, on finishing orders the caller hands in.  The key layout and the kernels' tables
 // come from csrc/champ_pack.h, the text the C ABI itself uses.  emu_champ_rounds_run does the same for champ_round
 // (csrc/champ_rounds.hip.h), the per-round standings kernel of mcgp_run_championship_rounds, and emu_champ_bonus_run for
-// champ_bonus (csrc/champ_bonus.hip.h), the fastest-lap bonus of mcgp_run_championship_bonus.
+// champ_bonus (csrc/champ_bonus.hip.h), the fastest-lap bonus of mcgp_run_championship_bonus, and emu_champ_given_run for
+// champ_given (csrc/champ_given.hip.h), the title odds by finishing position of mcgp_run_championship_live.
 //
 // Execution model: REAL BLOCK SEMANTICS.  A block is 256 host threads (both kernels have a fixed block of 256) that
 // run at the same time and meet at __syncthreads(), a pthread barrier; atomicAdd is __atomic_fetch_add; a __shared__
@@ -23,6 +24,7 @@
 #include "../../include/mcgp.h"
 #include "../../monte_carlo_gp_amd/csrc/champ_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/champ_rounds.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/champ_given.hip.h"
 
 thread_local emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0};
 emu_dim3 blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -33,6 +35,7 @@ namespace {
 constexpr unsigned kBlock = 256;
 static_assert(kBlock == (unsigned)mcgp::kChampAccBlock && kBlock == (unsigned)mcgp::kChampRankBlock, "one block size");
 static_assert(kBlock == (unsigned)mcgp::kChampRoundBlock, "one block size");
+static_assert(kBlock == (unsigned)mcgp::kChampGivenBlock, "one block size");
 
 pthread_barrier_t g_block_barrier;       // __syncthreads(): the 256 threads of the block
 pthread_barrier_t g_pool_barrier;        // start and end of a launch: the 256 threads and the caller
@@ -383,6 +386,71 @@ int emu_champ_bonus_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t 
         }
     }
     std::memcpy(keys_out, keys.data(), keys.size() * 8);
+    return MCGP_OK;
+}
+
+// The title odds by finishing position of n_sims seasons: emu_champ_run's inputs (orders, tables, standings, teams, cap,
+// acc_grid) and given_race in [0, n_races).  Per chunk: champ_accumulate after every race, the given race's from a kept
+// buffer of exactly the chunk's size that lives to the end of the chunk, then champ_given on the chunk's keys and the kept
+// orders on a grid of at most given_grid blocks, as mcgp_run_championship_live launches them.  table_in_lds: 1 for the
+// kernel's per-block LDS table, 0 for global atomics; the dynamic LDS is a buffer of exactly champ_given_lds' bytes.
+// given_out [n][n][n] ([driver][position][champion]) is ACCUMULATED into.  info_out: NULL or {words, the kernel's LDS
+// bytes}.
+int emu_champ_given_run(uint32_t n_races, uint32_t n, uint64_t n_sims, uint64_t cap, const uint8_t *orders,
+                        const int32_t *points, const uint8_t *countback, const int32_t *init_points,
+                        const int32_t *init_counts, const int32_t *team, uint32_t n_teams, uint32_t given_race,
+                        uint32_t table_in_lds, uint32_t acc_grid, uint32_t given_grid, unsigned long long *given_out,
+                        uint32_t *info_out, const char **err)
+{
+    static const char *none = "";
+    *err = none;
+    if (!orders || !points || !countback || !team || !given_out) return fail(MCGP_E_BAD_ARG, "a championship array is NULL", err);
+    uint64_t G = 0, awarded = 0;
+    uint32_t n_cb = 0;
+    const int chk = check_season(n_races, n, n_sims, cap, orders, points, countback, init_points, init_counts, team, n_teams,
+                                 acc_grid, given_grid, &G, &awarded, &n_cb, err);
+    if (chk != MCGP_OK) return chk;
+    if (given_race >= n_races) return fail(MCGP_E_BAD_ARG, "given_race is outside [0, n_races)", err);
+    mcgp::ChampPack pk;
+    const std::string e = mcgp::pack_championship(n_races, n, points, countback, init_points, init_counts, team, n_teams, G,
+                                                  awarded, n_cb, &pk);
+    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    const uint32_t words = pk.words;
+    const uint32_t given_lds = mcgp::champ_given_lds(n, table_in_lds != 0).bytes;
+    if (info_out) {
+        const uint32_t info[2] = {words, given_lds};
+        std::memcpy(info_out, info, sizeof(info));
+    }
+    if (n_sims == 0) return MCGP_OK;
+    // (cap is not cut down to n_sims here: a key stride above the simulation count is part of what is tested)
+    std::vector<uint64_t> keys((size_t)words * n * cap);
+    std::memset(keys.data(), 0xA5, keys.size() * 8);
+    std::vector<unsigned char> lds(given_lds);
+    unsigned char *lds_at = lds.data();
+    g_pool.start();
+    for (uint64_t done = 0; done < n_sims; done += cap) {
+        const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
+        // the given race's orders of the chunk, in a buffer of their own size, aligned as an allocation is
+        std::vector<uint32_t> keep((m * n + 3) / 4);
+        uint8_t *d_keep = reinterpret_cast<uint8_t *>(keep.data());
+        for (uint32_t rr = 0; rr < n_races; ++rr) {
+            std::vector<uint32_t> stage((m * n + 3) / 4);
+            uint8_t *d_orders = rr == given_race ? d_keep : reinterpret_cast<uint8_t *>(stage.data());
+            std::memcpy(d_orders, orders + ((size_t)rr * n_sims + done) * n, m * n);
+            const uint64_t tiles = (m + mcgp::kChampAccBlock - 1) / mcgp::kChampAccBlock;
+            const uint64_t *add = pk.add.data() + (size_t)rr * n * words;
+            const uint32_t first = rr == 0 ? 1u : 0u;
+            launch((unsigned)(tiles < acc_grid ? tiles : acc_grid), [&] {
+                mcgp::champ_accumulate(d_orders, m, n, words, cap, keys.data(), add, pk.init_key.data(), first);
+            });
+        }
+        const uint64_t gtiles = (m + mcgp::kChampGivenBlock - 1) / mcgp::kChampGivenBlock;
+        emu_dynamic_lds = lds_at;
+        launch((unsigned)(gtiles < given_grid ? gtiles : given_grid), [&] {
+            mcgp::champ_given(keys.data(), d_keep, m, cap, n, words, table_in_lds, given_out);
+        });
+        emu_dynamic_lds = nullptr;
+    }
     return MCGP_OK;
 }
 
