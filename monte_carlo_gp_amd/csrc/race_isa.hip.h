@@ -300,6 +300,76 @@ __device__ __forceinline__ void ovt_threshold(double dl, double od, uint32_t row
     }
 }
 
+// The same pair under EXEC, with the fetch of its draw word inside the statement.  ovt_threshold computes a threshold and
+// an advanced row for every lane and then drops both, by two selects, for the pairs that are no candidates -- all but 3
+// or 4 of a lane's 19.  Here, under the entry mask:  thr = 0;  ow = the word at W-plane address `row` (the LDS block's
+// W plane starts at OW, an immediate of the ds_read like STRIDE);  v_cmpx narrows EXEC to the candidates' lanes (a NaN
+// pace compares false, as above).  Under the narrowed mask:  thr = min(ceil(dl), 2^31),  row += STRIDE in place.  Then EXEC
+// goes back to the saved mask.  6 VALU instructions for 7 (reference width: 5 for 6): the zeroing replaces one select, the
+// other select and the copy of `row` the compiler makes when the read is left to it are gone.  A non-candidate fetches the
+// word of the next attempt, or one row past the plane, as above.
+// EXEC is saved once per statement, only ever narrowed from the saved mask (v_cmpx only clears bits) and back at its entry
+// value when the statement ends: the compiler never sees a changed mask, and a lane that is off at entry (it has left
+// the pass loop) stays off.  v_cmpx writes VCC as well on gfx9: clobbered, never read.  Wait states: VALU after a v_cmpx
+// write of EXEC is interlocked, as is the scalar write of EXEC (see ovt_commit* below; no DPP, lane access or EXECZ /
+// VCCZ operand here); od comes in an SGPR pair written by the scalar unit long before.
+// THE LOAD IS HIDDEN FROM THE COMPILER: it counts no LDS operation for the statement and emits no s_waitcnt for `ow`.
+//   * WAIT = true (the last pair of a pass's stage) ends the statement with s_waitcnt lgkmcnt(0).  LDS operations of a
+//     wave return in order, so that one wait covers every word fetched by the stage's statements before it; it sits ahead
+//     of everything that follows the stage: the branch out of the pass when no lane has a candidate (whose dead word
+//     registers the allocator may hand out again at once -- a late return would land on their new contents), the paths
+//     that overwrite the words with zeros, and the first commit that reads them.
+//   * Between a statement and that wait the compiler's own code must not read or copy a word register: it is free to, as
+//     far as it knows.  Checked in the assembly of the kernel's stage -- the stage's code between
+//     statements is pace arithmetic on other registers -- and to be checked again when the stage changes.
+//   * The compiler's own s_waitcnt lgkmcnt(n) for the pace gathers of the stage stay correct: the fetches it does not
+//     count are younger than the gathers it waits for, so its counts are only conservative.
+//   * volatile with a "memory" clobber: the stores of the two Philox blocks into the W plane stay ahead of the fetches,
+//     and the statements stay in order.
+template <uint32_t STRIDE, uint32_t OW, bool CEIL = true, bool WAIT = false>
+__device__ __forceinline__ void ovt_threshold_x(double dl, double od, uint32_t &row, uint32_t &thr, uint32_t &ow)
+{
+    static_assert(OW <= 0xFFFFu, "the W plane's base must fit the 16-bit offset of a ds_read");
+    uint64_t ex;
+#define MCGP_THR_HEAD                                                                                                   \
+    "s_mov_b64 %[ex], exec\n\t"                                                                                         \
+    "v_mov_b32 %[thr], 0\n\t"                                                                                           \
+    "ds_read_b32 %[ow], %[row] offset:%[base]\n\t"                                                                      \
+    "v_cmpx_lt_f64 vcc, %[od], %[dl]\n\t"
+#define MCGP_THR_TAIL                                                                                                   \
+    "v_min_u32 %[thr], 0x80000000, %[thr]\n\t"                                                                          \
+    "v_add_u32 %[row], %[stride], %[row]\n\t"                                                                           \
+    "s_mov_b64 exec, %[ex]"
+#define MCGP_THR_WAIT "\n\ts_waitcnt lgkmcnt(0)"
+    if constexpr (CEIL) {
+        double t;
+        if constexpr (WAIT)
+            asm volatile(MCGP_THR_HEAD "v_ceil_f64 %[t], %[dl]\n\tv_cvt_u32_f64 %[thr], %[t]\n\t" MCGP_THR_TAIL MCGP_THR_WAIT
+                         : [thr] "=&v"(thr), [ow] "=&v"(ow), [row] "+v"(row), [t] "=&v"(t), [ex] "=&s"(ex)
+                         : [dl] "v"(dl), [od] "s"(od), [stride] "n"(STRIDE), [base] "n"(OW)
+                         : "vcc", "memory");
+        else
+            asm volatile(MCGP_THR_HEAD "v_ceil_f64 %[t], %[dl]\n\tv_cvt_u32_f64 %[thr], %[t]\n\t" MCGP_THR_TAIL
+                         : [thr] "=&v"(thr), [ow] "=&v"(ow), [row] "+v"(row), [t] "=&v"(t), [ex] "=&s"(ex)
+                         : [dl] "v"(dl), [od] "s"(od), [stride] "n"(STRIDE), [base] "n"(OW)
+                         : "vcc", "memory");
+    } else {
+        if constexpr (WAIT)
+            asm volatile(MCGP_THR_HEAD "v_cvt_u32_f64 %[thr], %[dl]\n\t" MCGP_THR_TAIL MCGP_THR_WAIT
+                         : [thr] "=&v"(thr), [ow] "=&v"(ow), [row] "+v"(row), [ex] "=&s"(ex)
+                         : [dl] "v"(dl), [od] "s"(od), [stride] "n"(STRIDE), [base] "n"(OW)
+                         : "vcc", "memory");
+        else
+            asm volatile(MCGP_THR_HEAD "v_cvt_u32_f64 %[thr], %[dl]\n\t" MCGP_THR_TAIL
+                         : [thr] "=&v"(thr), [ow] "=&v"(ow), [row] "+v"(row), [ex] "=&s"(ex)
+                         : [dl] "v"(dl), [od] "s"(od), [stride] "n"(STRIDE), [base] "n"(OW)
+                         : "vcc", "memory");
+    }
+#undef MCGP_THR_WAIT
+#undef MCGP_THR_TAIL
+#undef MCGP_THR_HEAD
+}
+
 // ---- overtake commits under EXEC ----
 // The write-back chain of an overtake pass (reference :523-531): per adjacent pair (ahead, behind) with draw word w and
 // threshold t, a success (w < t) sets  behind = ahead - 0.1,  ahead = behind + 0.3,  each rounded once, and the next pair

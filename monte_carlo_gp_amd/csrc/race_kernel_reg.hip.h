@@ -145,6 +145,15 @@ __host__ __device__ constexpr bool reg_update_by_selects(int n)
 {
     return n == 1 || n == 6 || (n >= 9 && n <= 11) || n == 22 || n == 28 || n == 29;
 }
+// Field sizes whose overtake passes keep computing a pair's threshold and row for every lane and dropping them by selects
+// (ovt_threshold) instead of under EXEC with the word fetch inside the statement (ovt_threshold_x, race_isa.hip.h): the
+// ones where the EXEC form costs some instantiation scratch or registers (select form -> EXEC form: N = 6 batch 188 -> 192 B
+// of scratch per lane; N = 7 reference width 145 -> 146 VGPRs; N = 23 reference width 0 -> 20 B; N = 24 238 -> 240 VGPRs,
+// batch 0 -> 16 B, reference width 28 -> 48; N = 25 reference width 56 -> 68; N = 27 248 -> 250 VGPRs, batch 0 -> 12 B;
+// N = 28 batch 8 -> 12, reference width 144 -> 172; N = 29 .. 32 reference width 216 -> 248, 216 -> 260, 260 -> 272,
+// 324 -> 332).  A cut by resources alone, as the lists above.  Everywhere else every instantiation keeps both (N = 20: 168
+// VGPRs and 0 B, 4-wave blocks 8 B, batch 84, reference width 176, as before); occupancy changes nowhere.
+__host__ __device__ constexpr bool reg_threshold_by_selects(int n) { return n == 6 || n == 7 || (n >= 23 && n <= 25) || n >= 27; }
 // Waves per block: the (waves per block, blocks per CU) pair that keeps the most waves resident within the LDS
 // budget and the kernel's waves per SIMD; among equals a multiple of 4 waves per block (a block's waves go round the
 // 4 SIMDs: two blocks of 6 load them 4, 4, 2, 2), then the block nearest to 8 waves (1024-thread blocks make the
@@ -1804,8 +1813,8 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                         lds_st<uint32_t>(w_row(7), o3);
                     }
                     // W-plane address of the NEXT attempt's word: a running sum over the candidates so far (row k of the plane
-                    // holds the word of the lane's k-th attempt), advanced inside ovt_threshold by the compare that makes
-                    // the pair a candidate
+                    // holds the word of the lane's k-th attempt), advanced inside ovt_threshold / ovt_threshold_x by the compare
+                    // that makes the pair a candidate
                     uint32_t row = tid4;
                     {
                         constexpr int H = kPaceBatch;
@@ -1833,12 +1842,20 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                                     if (i > 0) {
                                         const double dl = (pace_prev - pace) + pa[j];                   // :516, :519-520 (x 2^31)
                                         // candidate iff dl > overtake_delta (:522); threshold min(ceil(dl), 2^31) (:523-524)
-                                        uint32_t next;
-                                        ovt_threshold<(uint32_t)(B * 4), !WIDE>(dl, od31, row, thr[i], next);
                                         // (a pair that is no candidate fetches the word of the next attempt, or one just past
                                         //  the plane: its threshold is 0)
-                                        ow[i] = lds_ld<uint32_t>(G::oW + row);
-                                        row = next;
+                                        if constexpr (reg_threshold_by_selects(N)) {
+                                            uint32_t next;
+                                            ovt_threshold<(uint32_t)(B * 4), !WIDE>(dl, od31, row, thr[i], next);
+                                            ow[i] = lds_ld<uint32_t>(G::oW + row);
+                                            row = next;
+                                        } else {
+                                            // under EXEC, the fetch inside the statement; the last pair's waits for all of them
+                                            if (i == N - 1)
+                                                ovt_threshold_x<(uint32_t)(B * 4), G::oW, !WIDE, true>(dl, od31, row, thr[i], ow[i]);
+                                            else
+                                                ovt_threshold_x<(uint32_t)(B * 4), G::oW, !WIDE, false>(dl, od31, row, thr[i], ow[i]);
+                                        }
                                     }
                                     pace_prev = pace;
                                 }

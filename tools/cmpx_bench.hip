@@ -14,6 +14,11 @@
 //   UE the same under EXEC (race_isa.hip.h upd_commit4<.., false>): leader and prev moved in place, each flag OR-ed in under EXEC
 //      narrowed by a mask and then by v_cmpx;  UF with slot 0 opening the field (upd_commit4<.., true>)
 //      (per slot; lanes with a retired car in front of the first running one, with one between two running ones, with DRS off)
+//   TS the threshold stage of an overtake pass by selects (race_isa.hip.h ovt_threshold): per adjacent pair a binary64 compare, ceil,
+//      convert, min, add, 2 x v_cndmask_b32 and the read of the pair's draw word from the W plane; a chain of 19 pairs
+//   TE the same under EXEC (race_isa.hip.h ovt_threshold_x): threshold zeroed, word read, v_cmpx, then ceil, convert, min and the row
+//      advance in place on the candidates' lanes; EXEC saved and restored per pair.  TE4: four pairs to a statement (EXEC saved once
+//      per four).  TE4Z: TE4 with two thresholds zeroed by one v_mov_b64.  (per pair; 5 pairs in 32 are candidates, lane by lane)
 // each as layers of 8 independent comparators (the sorting network) and as a chain of 15 dependent ones (a bubble pass).
 // The loop bodies are written on fixed registers (v[10:41] = 16 times, v50..v65 = 16 payloads): inline assembly cannot
 // name the halves of a 64-bit operand, which form B needs.
@@ -44,7 +49,11 @@ int main()
                           {"LE (lap-step commit of 4 slots under EXEC; per slot)", k_LE_chain, 4},
                           {"US (position update of 4 slots by selects; per slot)", k_US_chain, 4},
                           {"UE (position update of 4 slots under EXEC; per slot)", k_UE_chain, 4},
-                          {"UF (the same, slot 0 opening the field; per slot)", k_UF_chain, 4}};
+                          {"UF (the same, slot 0 opening the field; per slot)", k_UF_chain, 4},
+                          {"TS (overtake thresholds of 19 pairs by selects; per pair)", k_TS_chain, 19},
+                          {"TE (overtake thresholds under EXEC, a pair to a statement; per pair)", k_TE_chain, 19},
+                          {"TE4 (the same, four pairs to a statement; per pair)", k_TE4_chain, 19},
+                          {"TE4Z (TE4, thresholds zeroed two at a time; per pair)", k_TE4Z_chain, 19}};
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;

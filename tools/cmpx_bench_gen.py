@@ -146,6 +146,59 @@ def upd_setup():
                 'v_cndmask_b32 v109, 0, v109, vcc', f'v_or_b32 {p(i)}, {i << 4}, v109']
     return ins
 
+# The threshold stage of an overtake pass (race_kernel_reg.hip.h, "overtakes: draw words"; race_isa.hip.h ovt_threshold /
+# ovt_threshold_x): a chain of 19 adjacent pairs.  Pair i has its pace delta in v[10 + 2 i : 11 + 2 i], its threshold in v(50 + i),
+# its draw word in v(80 + i); the W-plane row address runs in v100 (v101: the advanced one of the select form), the ceiling in
+# v[102:103]; overtake_delta in s[24:25].  The plane (21 rows of 256 words at LDS address 0) holds a word per (lane, row).
+# The deltas are lane * 5 + pair * 11 mod 32, plus a half, against a bound of 26.5: 5 pairs in 32 are candidates, in
+# different pairs from lane to lane.
+T_PAIRS = 19
+def dl(i): return f'v[{10 + 2 * i}:{11 + 2 * i}]'
+def thr_select(i):     # today's form: threshold and advanced row for every lane, two selects; the word read from the row before
+    return [f'v_cmp_lt_f64 vcc, s[24:25], {dl(i)}', f'v_ceil_f64 v[102:103], {dl(i)}', f'v_cvt_u32_f64 v{50 + i}, v[102:103]',
+            f'v_min_u32 v{50 + i}, 0x80000000, v{50 + i}', 'v_add_u32 v101, 0x400, v100', f'v_cndmask_b32 v{50 + i}, 0, v{50 + i}, vcc',
+            f'ds_read_b32 v{80 + i}, v100', 'v_cndmask_b32 v100, v100, v101, vcc']
+def thr_exec(i, zero=True):   # under EXEC: zero, fetch, narrow, then threshold and row advance in place on the candidates' lanes
+    return ([f'v_mov_b32 v{50 + i}, 0'] if zero else []) + [
+            f'ds_read_b32 v{80 + i}, v100', f'v_cmpx_lt_f64 vcc, s[24:25], {dl(i)}', f'v_ceil_f64 v[102:103], {dl(i)}',
+            f'v_cvt_u32_f64 v{50 + i}, v[102:103]', f'v_min_u32 v{50 + i}, 0x80000000, v{50 + i}', 'v_add_u32 v100, 0x400, v100',
+            's_mov_b64 exec, s[26:27]']
+def thr_body(form):
+    ins = ['v_lshlrev_b32 v100, 2, v70']
+    if form == 'TS':
+        for i in range(T_PAIRS): ins += thr_select(i)
+    else:
+        per = 1 if form == 'TE' else 4        # pairs to a statement: EXEC is saved once per statement
+        for i in range(T_PAIRS):
+            if i % per == 0: ins += ['s_mov_b64 s[26:27], exec']
+            if form == 'TE4Z':                # thresholds zeroed two at a time (the thresholds of two pairs in an aligned register pair)
+                if i % 2 == 0 and i + 1 < T_PAIRS: ins += [f'v_mov_b64 v[{50 + i}:{51 + i}], 0']
+                ins += thr_exec(i, zero=i % 2 == 0 and i + 1 == T_PAIRS)
+            else:
+                ins += thr_exec(i)
+    return ins + ['s_waitcnt lgkmcnt(0)']
+def thr_kernel(form):
+    ins = ['v_mbcnt_lo_u32_b32 v70, -1, 0', 'v_mbcnt_hi_u32_b32 v70, -1, v70', 'v_lshlrev_b32 v72, 2, v70', 'v_mov_b32 v73, 0x9e3779b1',
+           'v_mul_lo_u32 v73, v73, v70']
+    for k in range(T_PAIRS + 2):
+        ins += [f'v_add_u32 v74, 0x{k * 0x61c88647 & 0xffffffff:x}, v73', f'ds_write_b32 v72, v74 offset:{k * 0x400}']
+    for i in range(T_PAIRS):
+        ins += ['v_mul_u32_u24 v71, 5, v70', f'v_add_u32 v71, {i * 11 % 32}, v71', 'v_and_b32 v71, 31, v71', f'v_cvt_f64_u32 {dl(i)}, v71',
+                f'v_add_f64 {dl(i)}, {dl(i)}, 0.5']
+    ins += ['s_mov_b32 s24, 0', 's_mov_b32 s25, 0x403a8000', 's_waitcnt lgkmcnt(0)', 's_mov_b64 s[20:21], exec', 's_mov_b32 s22, %0', '1:']
+    ins += thr_body(form)
+    ins += ['s_sub_u32 s22, s22, 1', 's_cmp_lg_u32 s22, 0', 's_cbranch_scc1 1b']
+    # (the check value: the last iteration's thresholds, words and final row)
+    ins += ['v_mov_b32 v75, v100']
+    for i in range(T_PAIRS): ins += [f'v_mad_u32_u24 v75, v75, 31, v{50 + i}', f'v_xor_b32 v75, v75, v{80 + i}']
+    ins += ['v_lshrrev_b32 v75, 8, v75', 'v_cvt_f64_u32 v[72:73], v75', 'v_lshlrev_b32 v70, 3, v70', 'global_store_dwordx2 v70, v[72:73], %1',
+            's_waitcnt vmcnt(0)']
+    print(f'__global__ void __launch_bounds__(256) k_{form}_chain(uint32_t iters, double *out)\n{{\n    asm volatile(')
+    for x in ins:
+        print(f'        "{x}\\n\\t"')
+    tclob = ','.join(f'"v{i}"' for i in list(range(10, 48)) + list(range(50, 69)) + list(range(70, 76)) + list(range(80, 104)))
+    print(f'        : : "s"(iters), "s"(out) : {tclob},"vcc","s20","s21","s22","s24","s25","s26","s27","memory");\n}}')
+
 clob = ','.join(f'"v{i}"' for i in list(range(10, 42)) + list(range(50, 66)) + list(range(70, 76))) + ',"vcc","s20","s21","s22","memory"'
 step_clob = ','.join(f'"v{i}"' for i in range(76, 160)) + ',' + ','.join(f'"s{i}"' for i in range(23, 50)) + ','
 commit_clob = ','.join(f'"v{i}"' for i in (76, 77) + tuple(range(80, 96))) + ',"s24","s25","s26","s27","s28","s29",'
@@ -183,3 +236,5 @@ for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE', 'US', 'UE', 'UF'):
         for x in ins:
             print(f'        "{x}\\n\\t"')
         print(f'        : : "s"(iters), "s"(out) : {commit_clob if commit else step_clob if step else ""}{clob});\n}}')
+for form in ('TS', 'TE', 'TE4', 'TE4Z'):
+    thr_kernel(form)

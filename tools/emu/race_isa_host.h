@@ -105,6 +105,16 @@ inline void ovt_threshold(double dl, double od, uint32_t row, uint32_t &thr, uin
     thr = c ? min_u32(cvt_u32_f64_sat(CEIL ? std::ceil(dl) : dl), 0x80000000u) : 0u;
     next = row + (c ? stride : 0u);
 }
+// the same pair with the word fetch inside (the device statement narrows EXEC; WAIT is its wait for the fetches)
+template <uint32_t STRIDE, uint32_t OW, bool CEIL = true, bool WAIT = false>
+inline void ovt_threshold_x(double dl, double od, uint32_t &row, uint32_t &thr, uint32_t &ow)
+{
+    const uint32_t stride = STRIDE;
+    const bool c = dl > od;
+    ow = lds_ld<uint32_t>(OW + row);
+    thr = c ? min_u32(cvt_u32_f64_sat(CEIL ? std::ceil(dl) : dl), 0x80000000u) : 0u;
+    row += c ? stride : 0u;
+}
 // overtake commits (reference :523-531): the portable loop body; `acc` is the one emulated lane's hit bit
 inline void ovt_commit1(double &c0, double &c1, uint32_t w1, uint32_t t1, uint64_t &acc)
 {
