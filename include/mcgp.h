@@ -36,7 +36,7 @@ extern "C" {
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
  * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too; and
  * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties; mcgp_lap_event and mcgp_run_events;
- * mcgp_run_championship_live */
+ * mcgp_run_championship_live; mcgp_pace_offset and mcgp_run_paces */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -581,6 +581,71 @@ int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const d
                         const mcgp_pit_plan *plans, const uint32_t *event_count, const mcgp_lap_event *events,
                         uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                         uint64_t *delta_out, uint64_t *events_out, uint8_t *orders_out);
+
+/* A lap-time offset: in a scenario of mcgp_run_paces, `seconds` are added to `driver`'s base pace on laps
+ * first_lap..last_lap (MCGP_PACE_LAPS) or from first_lap until the car's next pit stop (MCGP_PACE_UNTIL_STOP). */
+#define MCGP_MAX_SCENARIO_PACES 64
+enum { MCGP_PACE_LAPS = 0, MCGP_PACE_UNTIL_STOP = 1 };
+typedef struct mcgp_pace_offset {
+    int32_t driver;               /* 0 .. n - 1 */
+    int32_t kind;                 /* MCGP_PACE_* */
+    int32_t first_lap, last_lap;  /* LAPS: both in [first, L], first_lap <= last_lap; UNTIL_STOP: first_lap in [first, L], last_lap 0 */
+    double seconds;               /* finite, |seconds| <= 60; negative = faster; 0 is legal */
+} mcgp_pace_offset;
+
+/* Pace scenarios: one race under n_scenarios sets of planned pit stops AND lap-time offsets (front-wing damage that
+ * costs 0.6 s a lap until the nose is changed; an engine mode worth 0.15 s a lap for ten laps; an upgrade worth 0.2 s
+ * from lap 1), with common random numbers.  Scenario s holds plan_count[s] plans (concatenated in `plans`; exactly
+ * mcgp_run_strategies' plans, with its checks; `plans` may be NULL when every count is 0) and pace_count[s] offsets
+ * (concatenated in `paces`, which may be NULL when every count is 0).  L = cfg->total_laps; `first`, the first lap an
+ * offset may name, is 1 from the grid (lap 1 reads the base pace too) and state->lap + 1 from a state.
+ *   - effective base pace of car d on lap k, built in this order: b = base_pace[d]; if a LAPS offset of d covers lap k,
+ *     b = b + seconds; if d's UNTIL_STOP offset is active, b = b + seconds: at most two binary64 additions.  b replaces
+ *     base_pace[d] in exactly these places and nowhere else: lap 1's base_lap; the lap time of laps >= 2
+ *     ((b + tire) - fuel_effect + ...); the pace of the overtake model on lap k, in the candidate scan and in the
+ *     attempt probability, on all three passes.  So, unlike an MCGP_PEN_ON_LAP penalty, a slowed car is easier to pass
+ *     and the car behind inherits its lap time through dirty air.  The pit rule, the retirement draw, the event step,
+ *     DRS and dirty air, and every random word do not move; nothing new is drawn;
+ *   - an UNTIL_STOP offset is active from lap first_lap on.  The pit step of the car's first stop on a lap
+ *     q >= first_lap (the rule's or a planned one) clears it: the lap time of lap q carries the offset, because it is
+ *     computed before the pit step; the overtakes of lap q and everything later do not.  A red flag's free tyre change
+ *     is not a stop and clears nothing (as for mcgp_run_penalties' SERVE_AT_STOP); lap 1 has no pit step;
+ *   - per scenario and driver: the LAPS offsets of one driver share no lap; a driver has at most one UNTIL_STOP offset
+ *     (a LAPS and an UNTIL_STOP offset may cover the same laps); a scenario has at most MCGP_MAX_SCENARIO_PACES offsets.
+ * Identities: a scenario without offsets is cell for cell the same scenario of mcgp_run_strategies; so is a scenario
+ * whose offsets are all 0.0 (x + 0.0 == x); a LAPS offset [first, L] on every driver is the race under
+ * base_pace[d] + seconds[d], bit for bit.
+ * Random numbers: simulation i of every scenario has id sim_offset + i and draws what mcgp_run's (from the grid) or
+ * mcgp_run_from_state's (from a state) simulation i draws.
+ *   hist_out    [S][n][n]      [scenario][driver][position - 1]
+ *   delta_out   [S][n][2n - 1] as mcgp_run_strategies': paired position changes against scenario 0; or NULL
+ *   carried_out [S][n][L + 1]  [scenario][driver][c], c = the number of laps whose lap time carried the driver's
+ *                              UNTIL_STOP offset, p its first_lap: the car stops on lap q >= p: q - p + 1; it retires
+ *                              on lap r > p: r - p; it retires on lap r <= p, or was retired in the state: 0; it runs to
+ *                              the flag unstopped: L - p + 1; a driver without an UNTIL_STOP offset in the scenario:
+ *                              column 0.  Every row sums to n_sims; or NULL
+ *   orders_out  [S][n_sims][n] driver index classified p-th, or NULL
+ * hist_out, delta_out and carried_out are ACCUMULATED into, orders_out is written, and all only after every launch has
+ * succeeded: on an error they are left as they were.  Every argument is checked before any device lookup: what
+ * mcgp_run_strategies checks (n_scenarios, plans, the state, grid_probs, deviates other than MCGP_DEVIATES_32, NULLs),
+ * pace_count NULL or above 64, `paces` NULL with a non-zero count, a kind outside the enum, a driver outside [0, n), a lap
+ * outside [first, L] ("(after the state's lap)" from a state), first_lap > last_lap, last_lap != 0 with UNTIL_STOP,
+ * seconds not finite or |seconds| > 60, two LAPS offsets of one driver that share a lap and a second UNTIL_STOP offset
+ * of one driver are MCGP_E_BAD_ARG with a message that names the scenario, the offset and the field.  n_sims == 0
+ * succeeds without a device.  The device work goes chunk by chunk through mcgp_run_strategies' staging budget (one byte
+ * per scenario, simulation and driver, and a u16 more when carried_out is wanted) that one counting kernel reads; device
+ * memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or devices sums to the same counts.
+ * mcgp_last_kernel_name afterwards is "mcgp::race_paces_kernel".
+ * Price (one MI355X, S60, two scenarios x 10^6 simulations, device ms per 10^6, medians of five with max - min;
+ * profiles/paces_time.txt): mcgp_run_strategies built from the parent commit, two empty scenarios, 97.72 (0.34);
+ * mcgp_run_paces, two empty scenarios, 99.61 (0.48), 1.9 % more; an empty scenario and one LAPS range of ten laps on one
+ * driver 101.24 (0.50); an empty scenario and one UNTIL_STOP offset from lap 5, 105.76 (0.43), 8.2 % more: a lap on which
+ * the scenario has an offset pays a bit test wherever a base pace is read, every other lap one wave-uniform test. */
+int32_t mcgp_run_paces(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                       const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                       const mcgp_pit_plan *plans, const uint32_t *pace_count, const mcgp_pace_offset *paces,
+                       uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                       uint64_t *delta_out, uint64_t *carried_out, uint8_t *orders_out);
 
 /* Race time gaps: the model's binary64 cumulative times, counted on the device as histograms over caller-given edges
  * (seconds): every car's gap to the leader by lap, the lead (winning margin on the last lap) and the gap between named

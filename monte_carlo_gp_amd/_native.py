@@ -103,6 +103,18 @@ class McgpLapEvent(C.Structure):
     _fields_ = [('first_lap', C.c_int32), ('last_lap', C.c_int32), ('kind', C.c_int32)]
 
 
+MAX_SCENARIO_PACES = 64                            # include/mcgp.h: MCGP_MAX_SCENARIO_PACES, MCGP_PACE_*
+PACE_LAPS, PACE_UNTIL_STOP = range(2)
+MAX_PACE_SECONDS = 60.0
+
+
+class McgpPaceOffset(C.Structure):
+    """mcgp_pace_offset: seconds added to one driver's base pace, on laps or until its next stop, in a scenario of
+    mcgp_run_paces."""
+    _fields_ = [('driver', C.c_int32), ('kind', C.c_int32), ('first_lap', C.c_int32), ('last_lap', C.c_int32),
+                ('seconds', C.c_double)]
+
+
 class McgpConditionAtom(C.Structure):
     """mcgp_condition_atom: holds iff (lo <= value <= hi) != (negate != 0)."""
     _fields_ = [('fact', C.c_int32), ('a', C.c_int32), ('b', C.c_int32), ('lo', C.c_int32), ('hi', C.c_int32),
@@ -285,7 +297,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
            'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
-           'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live')
+           'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live', 'mcgp_run_paces')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -421,6 +433,13 @@ def lib():
                                           C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
                                           C.POINTER(C.c_uint32), C.POINTER(McgpLapEvent), C.c_uint64, C.c_uint64,
                                           C.c_uint64, C.c_int32, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
+        if 'mcgp_run_paces' not in missing:
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_paces.restype = C.c_int32
+            L.mcgp_run_paces.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.POINTER(McgpRaceState),
+                                         C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
+                                         C.POINTER(C.c_uint32), C.POINTER(McgpPaceOffset), C.c_uint64, C.c_uint64,
+                                         C.c_uint64, C.c_int32, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES

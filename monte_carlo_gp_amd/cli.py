@@ -13,6 +13,8 @@
         --driver NOR --plan box=:30/HARD --simulations 1000000 --seed 7
     python -m monte_carlo_gp_amd.cli events --race Bahrain --season 2024 --offline --state lap30.json --event sc=sc@31 \
         --driver NOR --plan sc=:31/HARD --event green=none@31-57
+    python -m monte_carlo_gp_amd.cli pace --race Bahrain --season 2024 --offline --driver NOR --offset damage=NOR:0.6@12+ \
+        --offset 'box now=NOR:0.6@12+' --plan 'box now=:13/HARD' --offset push=NOR:-0.15@40-49
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -48,6 +50,11 @@ events sets the race's events on chosen laps (--event NAME=KIND@LAP[-LAP], KIND 
 make one scenario; a --plan of --driver whose NAME matches joins that scenario) and compares the scenarios with
 `as drawn` (no override, no plan), which comes first unless the first --event or --plan names its own baseline by using
 that name: win and podium odds and their change against the first scenario, and the expected number of event laps.
+pace adds lap-time offsets (--offset NAME=DRIVER:SECONDS@LAP-LAP on a range of laps, NAME=DRIVER:SECONDS@LAP+ from LAP until
+the car's next pit stop; negative seconds are faster; several per NAME make one scenario; a --plan of --driver whose NAME
+matches joins that scenario) and compares the scenarios with `as is` (no offset, no plan): for --driver the win, podium
+and expected-position change against the first scenario and, for an until-stop offset, the distribution of the laps it
+was carried.
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
 on the data path; results are gathered once).
 """
@@ -650,6 +657,125 @@ def cmd_events(args) -> int:
     return 0
 
 
+PACE_BASELINE = 'as is'
+
+
+def parse_offset(text: str):
+    """--offset NAME=DRIVER:SECONDS@LAP-LAP or NAME=DRIVER:SECONDS@LAP+ ('+': until the car's next stop) -> (NAME,
+    PaceOffset)."""
+    from .simulation import PaceOffset
+    usage = f'--offset {text!r}: expected NAME=DRIVER:SECONDS@LAP-LAP or NAME=DRIVER:SECONDS@LAP+'
+    name, sep, rest = text.partition('=')
+    if not sep or not name.strip():
+        raise ValueError(usage)
+    what, at, laps = rest.rpartition('@')
+    driver, colon, seconds = what.partition(':')
+    if not at or not colon or not driver.strip():
+        raise ValueError(usage)
+    try:
+        sec = float(seconds)
+    except ValueError:
+        raise ValueError(f'--offset {text!r}: SECONDS is a number, got {seconds.strip()!r}') from None
+    laps = laps.strip()
+    if laps.endswith('+'):
+        if not laps[:-1].strip().isdigit():
+            raise ValueError(usage)
+        return name.strip(), PaceOffset(driver.strip(), sec, until_stop_from=int(laps[:-1]))
+    a, dash, b = laps.partition('-')
+    if not dash or not a.strip().isdigit() or not b.strip().isdigit():
+        raise ValueError(usage)
+    if int(b) < int(a):
+        raise ValueError(f'--offset {text!r}: the range runs backwards')
+    return name.strip(), PaceOffset(driver.strip(), sec, laps=(int(a), int(b)))
+
+
+def pace_scenarios(offsets, driver=None, plans=()):
+    """The pace command's scenarios -> (paces, strategies): 'as is' (no offset, no plan) first, unless the user names a
+    scenario 'as is' themselves; then one scenario per NAME, holding every --offset of that NAME and the --plan of that
+    NAME."""
+    if not offsets:
+        raise ValueError('give at least one --offset NAME=DRIVER:SECONDS@LAP-LAP or NAME=DRIVER:SECONDS@LAP+')
+    if plans and not driver:
+        raise ValueError('--plan needs --driver')
+    out, strategies = {PACE_BASELINE: []}, {}
+    for text in offsets:
+        name, off = parse_offset(text)
+        out.setdefault(name, []).append(off)
+    for text in plans or ():
+        name, plan = parse_plan(text, driver)
+        if name in strategies:
+            raise ValueError(f'--plan: scenario {name!r} given twice')
+        out.setdefault(name, [])
+        strategies[name] = [plan]
+    return out, strategies
+
+
+def cmd_pace(args) -> int:
+    from .simulation import RaceState
+    fixture = synthetic_fixture()
+    if args.fixture:
+        with open(args.fixture) as f:
+            fixture = json.load(f)
+    elif not args.offline:
+        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+        return 2
+    state = None
+    if args.state:
+        with open(args.state) as f:
+            state = RaceState.from_json(json.load(f))
+    try:
+        paces, strategies = pace_scenarios(args.offset, args.driver, args.plan)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    print(f"\n{'=' * 60}\nF1 Pace Scenarios: {args.season} {args.race}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
+          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
+    print('=' * 60 + '\n')
+    try:
+        res = F1Predictor(device=args.device).predict_paces(args.season, args.race, fixture, paces, strategies,
+                                                            state=state, n_simulations=args.simulations, seed=args.seed,
+                                                            allow_single_compound=args.allow_single_compound)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    base = res.names[0]
+    shown = [args.driver] if args.driver else sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
+    rows = []
+    for name in res.names:
+        print(f"scenario: {name}")
+        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'change':>7} {'P(better)':>10}"
+              f"  gain +- SE")
+        epos, epos0 = res.expected_position(name), res.expected_position(base)
+        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
+                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
+                   expected_position=epos, drivers={})
+        for d in shown:
+            c = res.compare(name, d)
+            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
+            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
+            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
+                                     expected_position_change=epos[d] - epos0[d], p_better=c['p_better'],
+                                     p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'])
+            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {epos[d] - epos0[d]:+7.2f} "
+                  f"{c['p_better']:10.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}")
+            if (name, d) in (res.until_from or {}):         # the laps its until-stop offset was carried
+                dist = res.carried_distribution(name, d)
+                row['drivers'][d]['laps_carried'] = [float(x) for x in dist]
+                row['drivers'][d]['expected_laps_carried'] = res.expected_laps_carried(name, d)
+                top = sorted(range(len(dist)), key=lambda k: -dist[k])[:5]
+                print(f"    offset carried {row['drivers'][d]['expected_laps_carried']:.2f} laps on average; most likely: "
+                      + ', '.join(f'{k} laps {dist[k]:.1%}' for k in sorted(top) if dist[k] > 0))
+        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
+        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
+        rows.append(row)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
+    return 0
+
+
 def load_results(season: int) -> list:
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', f'results_{season}.json')
     with open(path) as f:
@@ -1175,6 +1301,26 @@ def main(argv=None) -> int:
     t.add_argument('--device', type=int, default=0)
     t.add_argument('--json', type=str, default=None)
     t.set_defaults(fn=cmd_events)
+    t = sub.add_parser('pace', help="race odds under lap-time offsets on chosen laps or until a car's next stop")
+    t.add_argument('--season', type=int, default=2025)
+    t.add_argument('--race', type=str, required=True)
+    t.add_argument('--offset', type=str, action='append', default=[],
+                   help="NAME=DRIVER:SECONDS@LAP-LAP or NAME=DRIVER:SECONDS@LAP+: in scenario NAME, SECONDS (negative = "
+                        "faster) are added to DRIVER's base pace on the laps, or ('+') from LAP until the car's next stop; "
+                        "repeat for more; several of one NAME make one scenario")
+    t.add_argument('--driver', type=str, default=None, help='the driver of the --plan scenarios, and the one shown')
+    t.add_argument('--plan', type=str, action='append', default=[],
+                   help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's; joins the --offset scenario of that NAME")
+    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
+    t.add_argument('--allow-single-compound', action='store_true',
+                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
+    t.add_argument('--simulations', type=int, default=100000)
+    t.add_argument('--seed', type=int, default=None)
+    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
+    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
+    t.add_argument('--device', type=int, default=0)
+    t.add_argument('--json', type=str, default=None)
+    t.set_defaults(fn=cmd_pace)
     args = ap.parse_args(argv)
     return args.fn(args)
 

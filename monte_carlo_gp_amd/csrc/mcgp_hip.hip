@@ -24,6 +24,7 @@
 #include "champ_given.hip.h"
 #include "plan_pack.h"
 #include "penalty_pack.h"
+#include "pace_pack.h"
 #include "event_pack.h"
 #include "champ_pack.h"
 
@@ -953,7 +954,7 @@ struct ScenarioChunk {
     uint8_t *stage;                         // [S][m][n] bytes: every driver's finishing position
 };
 
-// What mcgp_run_strategies, mcgp_run_penalties and mcgp_run_events each have of their own; run_scenarios has the rest.
+// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events and mcgp_run_paces each have of their own; run_scenarios has the rest.
 struct ScenarioKind {
     const char *what;                       // the call in check_deviates_32's message
     const char *geo_name, *kernel_name;     // generic_geometry's and note_launch's name of the race kernel
@@ -973,7 +974,7 @@ struct ScenarioKind {
     // the kind's own count segment behind hist and delta: the caller's buffer, its cells, a fix-up on the host
     uint64_t *extra_out = nullptr;
     size_t (*extra_cells)(size_t S, size_t n, size_t L) = nullptr;
-    void (*fix_up)(unsigned long long *extra, size_t rows, uint64_t n_sims) = nullptr;
+    std::function<void(unsigned long long *extra, size_t rows, uint64_t n_sims)> fix_up;
 };
 
 int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
@@ -2164,6 +2165,64 @@ int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const d
     };
     k.extra_out = events_out;               // events [S][3][L + 1]
     k.extra_cells = [](size_t S, size_t, size_t L) { return S * 3 * (L + 1); };
+    return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
+                         hist_out, delta_out, orders_out, k);
+}
+
+int32_t mcgp_run_paces(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                       const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                       const mcgp_pit_plan *plans, const uint32_t *pace_count, const mcgp_pace_offset *paces,
+                       uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                       uint64_t *delta_out, uint64_t *carried_out, uint8_t *orders_out)
+{
+    const auto kernel = state ? &mcgp::race_paces_kernel<true> : &mcgp::race_paces_kernel<false>;
+    std::vector<mcgp::PaceScenario> pscen;
+    std::vector<mcgp::PaceLap> pace_laps;
+    std::vector<double> lap_sec;
+    const mcgp::PaceScenario *d_ps = nullptr;
+    const mcgp::PaceLap *d_pl = nullptr;
+    const double *d_sec = nullptr;
+    uint16_t *d_car = nullptr;              // [S][m][n] laps carried of a chunk's simulations (carried_out wanted)
+    ScenarioKind k = {"paces run", "paces", "mcgp::race_paces_kernel", reinterpret_cast<KernelFn>(kernel)};
+    k.count_name = "pace_count", k.item_count = pace_count, k.items_name = "paces", k.items = paces;
+    k.check_counts = [&](uint64_t *n_paces) { return mcgp::check_pace_counts(n_scenarios, pace_count, n_paces); };
+    // lap 1 reads the base pace too: from the grid an offset may name it
+    k.pack = [&](int first_lap, bool resumed) {
+        return mcgp::pack_paces(n_scenarios, pace_count, paces, n, cfg->total_laps, resumed ? first_lap : 1, resumed, &pscen,
+                                &pace_laps, &lap_sec);
+    };
+    // a position byte per driver, and its u16 of laps carried when they are counted
+    k.sim_bytes = carried_out ? (size_t)n * 3 : (size_t)n;
+    k.regions = [&](Layout &ws, uint64_t chunk) {
+        if (carried_out) ws.add(&d_car, (size_t)n_scenarios * chunk * n);
+        ws.add(&d_ps, n_scenarios, pscen.data());
+        ws.add(&d_pl, pace_laps.size(), pace_laps.data());
+        ws.add(&d_sec, lap_sec.size(), lap_sec.data());
+    };
+    k.race = [&](const ScenarioChunk &l) {
+        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_ps, d_pl, d_sec,
+                           l.m, l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, d_car, l.n_batches);
+    };
+    // grid rows: the scenarios; grid layers: the deltas, then (carried_out wanted) one per driver
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *d_carried) {
+        const uint32_t gz = d_carried ? 1u + n : 1u;
+        const uint64_t tiles = (l.m + mcgp::kPacesCountBlock - 1) / mcgp::kPacesCountBlock;
+        const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / ((uint64_t)l.S * gz)));
+        hipLaunchKernelGGL(mcgp::paces_count, dim3((uint32_t)gxc, l.S, gz), dim3(mcgp::kPacesCountBlock), 0, nullptr, l.stage,
+                           d_car, d_ps, l.m, n, (uint32_t)cfg->total_laps, d_delta, d_carried);
+    };
+    // carried [S][n][L + 1]; column 0 is, like delta's centre bin, what the others leave of n_sims: all of it for a
+    // driver without an UNTIL_STOP offset
+    k.extra_out = carried_out;
+    k.extra_cells = [](size_t S, size_t n_, size_t L) { return S * n_ * (L + 1); };
+    k.fix_up = [&](unsigned long long *c, size_t rows, uint64_t n_sims_) {
+        const size_t w = (size_t)cfg->total_laps + 1;
+        for (size_t row = 0; row < rows; ++row) {
+            unsigned long long rest = 0;
+            for (size_t j = 1; j < w; ++j) rest += c[row * w + j];
+            c[row * w] = n_sims_ - rest;
+        }
+    };
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
                          hist_out, delta_out, orders_out, k);
 }

@@ -205,14 +205,25 @@ struct ModelTyres {
     __device__ __forceinline__ void operator()(uint32_t /*driver*/, uint32_t & /*comp*/, uint32_t & /*age*/) const {}
 };
 
+// The pace policy of every kernel but race_paces_kernel: a car's base pace is the model's.  start_from_grid and run_laps
+// ask a policy once per lap, begin_lap(lap) (wave-uniform), and wherever the model reads base_pace[d] -- lap 1's base_lap,
+// the lap time of laps >= 2, the pace of the overtake passes (candidate scan and attempt probability) -- base(d, b) with
+// b = base_pace[d], and use what it returns.  ModelPace returns b itself, so that the call vanishes; OffsetPace
+// (paces.hip.h) adds the caller's lap-time offsets there.
+struct ModelPace {
+    __device__ __forceinline__ void begin_lap(int /*lap*/) {}
+    __device__ __forceinline__ double base(uint32_t /*d*/, double b) const { return b; }
+};
+
 // The start of one lane's race: grid (`fixed_grid`, or NULL: sampled from grid_probs), cars, lap 1 and the once-per-race
 // retirement draws.  Leaves the rows after update_positions of lap 1 and every driver's retirement lap (laps >= 2) in
 // `out`.  hook(driver, comp, age) may replace a car's starting tyres after the model has picked them
-// (race_strategy_kernel, strategy.hip.h).
-template <class StartHook = ModelTyres>
+// (race_strategy_kernel, strategy.hip.h).  `pace` gives lap 1's base pace (ModelPace: the model's).
+template <class StartHook = ModelTyres, class PacePolicy = ModelPace>
 __device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1,
                                                      uint32_t seed_lo, uint32_t seed_hi,
-                                                     const uint8_t *__restrict__ fixed_grid, StartHook hook = StartHook())
+                                                     const uint8_t *__restrict__ fixed_grid, StartHook hook = StartHook(),
+                                                     PacePolicy pace = PacePolicy())
 {
     const KParams *__restrict__ P = e.P;
     const int n = e.n, L = e.L, track = e.track;
@@ -276,6 +287,7 @@ __device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv
     }
 
     // ================= _simulate_lap_1, reference :275-311 =================
+    pace.begin_lap(1);
     for (int pos = 0; pos < n; ++pos) {
         const uint32_t d = s.Ord(pos);
         uint32_t pk = s.Pk(d);
@@ -291,7 +303,7 @@ __device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv
         const double tire = (double)age * eff;
         const double fuel_effect = (110.0 - 110.0) * 0.03;
         const double noise = 0.0 + e.var[d] * (double)normal_from_u32(w1, e.norm);
-        const double base_lap = e.base[d] + tire - fuel_effect + e.cdelta[comp] - 0.0 + noise;
+        const double base_lap = pace.base(d, e.base[d]) + tire - fuel_effect + e.cdelta[comp] - 0.0 + noise;
         double pf = 0.5 + (double)(pos + 1) * 0.1;
         if (!(pf < 1.5)) pf = 1.5;
         double sd = 0.0 + pf * (double)normal_from_u32(w2, e.norm);
@@ -351,11 +363,13 @@ struct DrawnEvents {
 // trace.hip.h, records them; the other kernels pass a NoLapObserver).  `pit` decides the stops (RulePit: the model's
 // rule; race_strategy_kernel, strategy.hip.h, passes planned stops; race_penalties_kernel, penalties.hip.h, planned stops
 // and time penalties).  `evp` may replace a lap's event (DrawnEvents: never; race_events_kernel, events.hip.h, passes the
-// caller's overrides).
-template <class LapObserver, class PitPolicy = RulePit, class EventPolicy = DrawnEvents>
+// caller's overrides).  `pace` gives a car's base pace on a lap (ModelPace: the model's; race_paces_kernel, paces.hip.h,
+// passes the caller's lap-time offsets).
+template <class LapObserver, class PitPolicy = RulePit, class EventPolicy = DrawnEvents, class PacePolicy = ModelPace>
 __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1, uint32_t seed_lo,
                                          uint32_t seed_hi, int first_lap, int drs_disabled_until, LapObserver &obs,
-                                         PitPolicy pit = PitPolicy(), EventPolicy evp = EventPolicy())
+                                         PitPolicy pit = PitPolicy(), EventPolicy evp = EventPolicy(),
+                                         PacePolicy pace = PacePolicy())
 {
     const KParams *__restrict__ P = e.P;
     const int n = e.n, L = e.L, track = e.track;
@@ -368,6 +382,7 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
     for (int lap = first_lap; lap <= L; ++lap) {
         const int remaining_laps = L - lap;
         int event = kEventNone;
+        pace.begin_lap(lap);
         // ---- race-interrupting events, :168-176 (short-circuit chain, Q8) ----
         {
             uint32_t e0, e1, e2, e3;
@@ -447,7 +462,7 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
                 const double tire = (double)age * eff;
                 const double drs_gain = (pk & kDrs) ? drs_delta : 0.0;
                 const double noise = 0.0 + t_var[d] * (double)normal_from_u32(w1, t_norm);
-                const double clean = t_base[d] + tire - fuel_effect + t_cdelta[comp] - drs_gain + noise;
+                const double clean = pace.base(d, t_base[d]) + tire - fuel_effect + t_cdelta[comp] - drs_gain + noise;
                 double lap_time = clean;
                 if ((pk & kDirty) && ahead_last > 0) {          // :209-216
                     const double dirty_time = clean + dirty_pen;
@@ -496,16 +511,16 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
             {
                 uint32_t dp = s.Ord(0);
                 uint32_t pkp = s.Pk(dp);
-                double pace_p = t_base[dp] + (double)(pkp & kAgeMask) * t_deg[dp];
+                double pace_p = pace.base(dp, t_base[dp]) + (double)(pkp & kAgeMask) * t_deg[dp];
                 for (int i = 1; i < n; ++i) {
                     const uint32_t d = s.Ord(i);
                     const uint32_t pk = s.Pk(d);
-                    const double pace = t_base[d] + (double)(pk & kAgeMask) * t_deg[d];
-                    double delta = pace_p - pace;
+                    const double pace_d = pace.base(d, t_base[d]) + (double)(pk & kAgeMask) * t_deg[d];
+                    double delta = pace_p - pace_d;
                     if (pk & kDrs) delta += drs_delta;
                     if (!((pk | pkp) & kDnf) && delta > overtake_delta) cand |= 1u << i;
                     pkp = pk;
-                    pace_p = pace;
+                    pace_p = pace_d;
                 }
             }
             if (cand == 0u) break;
@@ -520,8 +535,8 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
                 cand &= cand - 1u;
                 const uint32_t db = s.Ord(i), da = s.Ord(i - 1);
                 const uint32_t pkb = s.Pk(db), pka = s.Pk(da);
-                const double pace_b = t_base[db] + (double)(pkb & kAgeMask) * t_deg[db];
-                const double pace_a = t_base[da] + (double)(pka & kAgeMask) * t_deg[da];
+                const double pace_b = pace.base(db, t_base[db]) + (double)(pkb & kAgeMask) * t_deg[db];
+                const double pace_a = pace.base(da, t_base[da]) + (double)(pka & kAgeMask) * t_deg[da];
                 double delta = pace_a - pace_b;
                 if (pkb & kDrs) delta += drs_delta;
                 double prob = delta / 2.0;

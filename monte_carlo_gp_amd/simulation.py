@@ -441,8 +441,8 @@ class RaceSimulator:
     def _run_scenarios(self, entry, result, label, n_simulations, items, strategies, race, grid_probs, state, seed,
                        sim_offset, drivers, return_orders, allow_single_compound, item_type=None, pack_items=None,
                        extra=None):
-        """run_strategies, run_penalties and run_events: the race under named scenarios of pit plans (`strategies`) and,
-        for the latter two, of the call's own `items` ({name: [item]}; their names come first).  pack_items: see
+        """run_strategies, run_penalties, run_events and run_paces: the race under named scenarios of pit plans
+        (`strategies`) and, for all but the first, of the call's own `items` ({name: [item]}; their names come first).  pack_items: see
         _pack_plans, its structs are `item_type`s; extra = (name, shape(S, n, L)): the kind's own count array, behind
         hist and delta among the outputs; result: the result class; label: the dicts' names for the message."""
         src = self._source(grid_probs, state, drivers)
@@ -770,6 +770,70 @@ class RaceSimulator:
             'mcgp_run_events', EventResult, 'events / strategies', n_simulations, events, strategies,
             (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
             drivers, return_orders, allow_single_compound, N.McgpLapEvent, pack, ('events', lambda S, n, L: (S, 3, L + 1)))
+
+    def run_paces(
+        self,
+        n_simulations: int,
+        paces: dict,
+        strategies: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        grid_probs: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        return_orders: bool = False,
+        allow_single_compound: bool = False,
+    ) -> 'PaceResult':
+        """Pace scenarios (include/mcgp.h: mcgp_run_paces): the race under each scenario of `paces`, {name:
+        [PaceOffset, ...]}, and `strategies`, {name: [PitPlan, ...]} or None; a scenario holds the offsets and the plans
+        given under its name, and the scenario names are the union of the two dicts in the order given (paces first; at
+        most 64; the first is the one `compare` measures against).  A PaceOffset adds seconds to a driver's base pace on
+        a range of laps, or from a lap until the car's next pit stop, wherever the model reads the base pace: the lap
+        time, and the pace of the overtake model (a slowed car is easier to pass).  From the grid an offset may name lap
+        1; from a state, the laps after the state's.  Two lap ranges of one driver that share a lap, a second
+        until-stop offset of one driver, and a lap outside the laps still to run raise ValueError.  Everything else --
+        the remaining arguments, the plans' checks, the simulation ids and draws, the seed rules and the device
+        sharding -- is run_strategies': a scenario without offsets gives exactly its counts.  last_histogram:
+        [S, n, n]."""
+        first = _Source(grid_probs, state, None, self.config.total_laps).first_lap(from_grid=1)
+
+        def pack(name, offs, index):
+            if len(offs) > N.MAX_SCENARIO_PACES:
+                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_PACES} offsets, got {len(offs)}')
+            packed, covered, until = [], {}, {}
+            for off in offs:
+                if str(off.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {off.driver!r} is not one of the drivers')
+                try:
+                    c = off.c_struct(index, first, int(self.config.total_laps))
+                except ValueError as e:
+                    raise ValueError(f'scenario {name!r}: {e}') from None
+                if c.kind == N.PACE_UNTIL_STOP:
+                    if c.driver in until:
+                        raise ValueError(f'scenario {name!r}: {off.driver} has two until-stop offsets '
+                                         f'({until[c.driver]} and {off})')
+                    until[c.driver] = off
+                else:
+                    for lap in range(c.first_lap, c.last_lap + 1):
+                        if (c.driver, lap) in covered:
+                            raise ValueError(f'scenario {name!r}: {off.driver} has two offsets on lap {lap} '
+                                             f'({covered[c.driver, lap]} and {off})')
+                        covered[c.driver, lap] = off
+                packed.append(c)
+            return packed
+
+        res = self._run_scenarios(
+            'mcgp_run_paces', PaceResult, 'paces / strategies', n_simulations, paces, strategies,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
+            drivers, return_orders, allow_single_compound, N.McgpPaceOffset, pack, ('carried', lambda S, n, L: (S, n, L + 1)))
+        res.until_from = {(str(name), str(off.driver)): int(off.until_stop_from) for name, offs in paces.items()
+                          for off in offs if off.until_stop_from is not None}
+        return res
 
     def run_gaps(
         self,
@@ -2340,3 +2404,72 @@ class EventResult(StrategyResult):
         """P(at least `at_least` laps of `kind`) in scenario `name`."""
         p = self.event_count_distribution(name)[N.EVENT_ROWS[self._k(kind)]]
         return float(p[max(int(at_least), 0):].sum())
+
+
+# ---------------------------------------------------------------------------------------------- pace scenarios
+@dataclass
+class PaceOffset:
+    """One lap-time offset in a scenario of RaceSimulator.run_paces: `seconds` (finite, |seconds| <= 60; negative =
+    faster) added to `driver`'s base pace, either on laps a..b (laps=(a, b)) or from lap p until the pit step of the car's
+    next stop (until_stop_from=p): exactly one of the two is given.  The offset enters where the model reads the base
+    pace: the lap time, and the pace of the overtake model."""
+    driver: str
+    seconds: float
+    laps: tuple | None = None
+    until_stop_from: int | None = None
+
+    def c_struct(self, index, first_lap=1, total_laps=None) -> N.McgpPaceOffset:
+        """mcgp_pace_offset with the driver index from `index`; ValueError unless exactly one of laps / until_stop_from
+        is given, on a > b, on a lap outside [first_lap, total_laps] and on seconds out of range."""
+        who = f'{self.driver}:{self.seconds}'
+        if (self.laps is None) == (self.until_stop_from is None):
+            raise ValueError(f'{who}: give either laps=(a, b) or until_stop_from=lap')
+        sec = float(self.seconds)
+        if not math.isfinite(sec) or abs(sec) > N.MAX_PACE_SECONDS:
+            raise ValueError(f'{who}: seconds must be finite and in [-60, 60]')
+        if self.laps is not None:
+            a, b = (int(x) for x in self.laps)
+            if a > b:
+                raise ValueError(f'{who}@{a}-{b}: the first lap must not be above the last')
+        else:
+            a = b = int(self.until_stop_from)
+        hi = b if total_laps is None else int(total_laps)
+        if a < int(first_lap) or b > hi:
+            raise ValueError(f'{who}@{a}' + (f'-{b}' if self.laps is not None else '+') +
+                             f': laps must be in [{int(first_lap)}, {hi}]' +
+                             ('' if int(first_lap) == 1 else " (after the state's lap)"))
+        p = N.McgpPaceOffset()
+        p.driver = int(index[str(self.driver)])
+        p.kind = N.PACE_LAPS if self.laps is not None else N.PACE_UNTIL_STOP
+        p.first_lap, p.last_lap = a, b if self.laps is not None else 0
+        p.seconds = sec
+        return p
+
+
+@dataclass
+class PaceResult(StrategyResult):
+    """What RaceSimulator.run_paces returns: StrategyResult's counts and helpers, and
+      carried  [S][n][L + 1]  [scenario][driver][laps whose lap time carried the driver's until-stop offset]: from its
+                              first lap p, q - p + 1 for a stop on lap q, r - p for a retirement on lap r > p (else 0),
+                              L - p + 1 unstopped to the flag; column 0 for a driver without one; every row sums to N"""
+    carried: np.ndarray | None = None
+    until_from: dict | None = None          # {(scenario name, driver): the first lap of its until-stop offset}
+
+    def carried_distribution(self, name, driver) -> np.ndarray:
+        """Probabilities by number of laps carried of `driver`'s until-stop offset in scenario `name`."""
+        return np.asarray(self.carried[self._s(name), self._d(driver)], np.float64) / max(self.n_simulations, 1)
+
+    def expected_laps_carried(self, name, driver) -> float:
+        p = self.carried_distribution(name, driver)
+        return float(p @ np.arange(p.shape[0], dtype=np.float64))
+
+    def probability_cleared_by(self, name, driver, lap) -> float:
+        """P(`driver`'s until-stop offset of scenario `name`, which begins on lap p, is carried on at most lap - p + 1
+        laps): by the end of `lap` a stop has cleared it or the car is out (a retirement on lap + 1 carries as many laps
+        and counts too).  0.0 before p; at the last lap 1.0.  KeyError if the driver has no until-stop offset there."""
+        key = (name if name is not None else self.names[0], driver)
+        self._s(name), self._d(driver)
+        if key not in (self.until_from or {}):
+            raise KeyError(f'{driver!r} has no until-stop offset in scenario {key[0]!r}')
+        c = int(lap) - self.until_from[key] + 1
+        return float(self.carried_distribution(name, driver)[:max(c + 1, 0)].sum()) if c >= 1 else 0.0

@@ -4,7 +4,8 @@
 // the stand-in <hip/hip_runtime.h> of this directory and calls the real __global__ functions: race_kernel, race_resume_kernel,
 // race_trace_kernel, race_strategy_kernel<false / true>, race_gaps_kernel<false / true>, race_conditions_kernel<false /
 // true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false / true>, race_fastest_kernel,
-// race_penalties_kernel<false / true>, penalties_count; and events.hip.h: race_events_kernel<false / true>, events_count.
+// race_penalties_kernel<false / true>, penalties_count; and events.hip.h: race_events_kernel<false / true>, events_count;
+// and paces.hip.h: race_paces_kernel<false / true>, paces_count.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -17,10 +18,11 @@
 // trace_count_laps, trace_count_records and strategy_count_deltas, whose loops are written for their fixed block of 256
 // threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
 // records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
-// operation and strides by its block's size, so it does run here, as blocks of one thread; so do penalties_count and events_count.
+// operation and strides by its block's size, so it does run here, as blocks of one thread; so do penalties_count, events_count
+// and paces_count.
 // tests/test_events_host_build.py, tests/test_generic_host_build.py, tests/test_gaps_host_build.py, tests/test_conditions_host_build.py,
 // tests/test_stints_host_build.py, tests/test_moves_host_build.py, tests/test_fastest_host_build.py,
-// tests/test_penalties_host_build.py.
+// tests/test_penalties_host_build.py, tests/test_paces_host_build.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -37,6 +39,7 @@
 #include "../../monte_carlo_gp_amd/csrc/plan_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/penalty_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/event_pack.h"
+#include "../../monte_carlo_gp_amd/csrc/pace_pack.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
 namespace mcgp {
@@ -409,6 +412,68 @@ int emu_events_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double
                 blockIdx = {x, y, 0};
                 mcgp::events_count(stage, ev_stage, n_sims, n, (uint32_t)L, delta, events_cnt);
             }
+    }
+    one_thread_block(1);
+    return MCGP_OK;
+}
+
+// race_paces_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every scenario,
+// plans and offsets packed by plan_pack.h and pace_pack.h.  hist [S][n][n] is accumulated into; stage [S][n_sims][n]
+// (classified position of each driver) and car_stage [S][n_sims][n] u16 (the laps carried, at the drivers with an
+// UNTIL_STOP offset; NULL: not staged) are written.  delta [S][n][2n - 1] and carried [S][n][L + 1] (either may be NULL;
+// carried needs car_stage) are accumulated into by paces_count, run as grid_x x S x (1 + n) blocks of one thread (both
+// NULL: not run): the centre bin and column 0 stay what they were, as on the device.
+int emu_paces_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                  uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                  const uint32_t *pace_count, const mcgp_pace_offset *paces, uint64_t n_sims, uint64_t sim_offset,
+                  uint64_t seed, unsigned long long *hist, uint8_t *stage, uint16_t *car_stage, unsigned long long *delta,
+                  unsigned long long *carried, uint32_t grid_x, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
+        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    if (carried && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
+    const int L = cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+        st.sim_offset = sim_offset;
+    }
+    const int first_lap = state ? st.lap + 1 : 2;
+    std::vector<mcgp::StrategyScenario> scen;
+    std::vector<mcgp::StopLap> stop_laps;
+    std::vector<mcgp::PaceScenario> pscen;
+    std::vector<mcgp::PaceLap> pace_laps;
+    std::vector<double> lap_sec;
+    uint64_t n_paces = 0;
+    std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen, &stop_laps);
+    if (e.empty()) e = mcgp::check_pace_counts(n_scenarios, pace_count, &n_paces);
+    if (e.empty() && n_paces && !paces) e = "paces is NULL";
+    if (e.empty())      // lap 1 reads the base pace too: from the grid an offset may name it
+        e = mcgp::pack_paces(n_scenarios, pace_count, paces, n, L, state ? first_lap : 1, state != nullptr, &pscen, &pace_laps,
+                             &lap_sec);
+    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    one_thread_block(n_scenarios);
+    const auto kernel = state ? &mcgp::race_paces_kernel<true> : &mcgp::race_paces_kernel<false>;
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        blockIdx.y = si;
+        kernel(&kp, &st, scen.data(), stop_laps.data(), pscen.data(), pace_laps.data(), lap_sec.data(), n_sims, sim_offset,
+               (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage, car_stage, (uint32_t)n_sims);
+    }
+    if (delta || carried) {
+        const uint32_t gz = carried ? 1u + n : 1u;
+        gridDim = {grid_x, n_scenarios, gz};
+        for (uint32_t z = 0; z < gz; ++z)
+            for (uint32_t y = 0; y < n_scenarios; ++y)
+                for (uint32_t x = 0; x < grid_x; ++x) {
+                    blockIdx = {x, y, z};
+                    mcgp::paces_count(stage, car_stage, pscen.data(), n_sims, n, (uint32_t)L, delta, carried);
+                }
     }
     one_thread_block(1);
     return MCGP_OK;
