@@ -647,6 +647,70 @@ int32_t mcgp_run_paces(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                        uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                        uint64_t *delta_out, uint64_t *carried_out, uint8_t *orders_out);
 
+/* Combined what-if scenarios: one race under n_scenarios sets of planned pit stops, time penalties, event overrides AND
+ * lap-time offsets, with common random numbers ("a safety car on lap 31; NOR has 5 s to serve and stops under it; VER
+ * carries 0.4 s of damage until his next stop").  Scenario s holds plan_count[s] plans, penalty_count[s] penalties,
+ * event_count[s] overrides and pace_count[s] offsets, each concatenated in its array: the structs, limits and checks of
+ * mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events and mcgp_run_paces.  Unlike in those calls, penalty_count,
+ * event_count and pace_count may each be NULL: none in any scenario, and the item pointer is then not read.  A non-NULL
+ * count array with a non-zero total and a NULL item array is MCGP_E_BAD_ARG.  L = cfg->total_laps.  The first lap an item
+ * may name stays per kind: penalties and events 2 from the grid, state->lap + 1 from a state; offsets 1 from the grid,
+ * state->lap + 1 from a state.
+ * Each rule is the one its own call states above; nothing new is drawn and no draw moves.  On lap k they meet so:
+ *   1. event step.  A lap with an override takes the override's kind instead of the chain's outcome, with the drawn
+ *      event's handler (bunching, tyre step, drs_disabled_until, re-sort after a tie).  A forced red flag's free tyre
+ *      change is not a stop: it serves no SERVE_AT_STOP penalty and clears no UNTIL_STOP offset;
+ *   2. car step, for every running car in field order.  b = base_pace[d], + the covering LAPS offset, + the active
+ *      UNTIL_STOP offset, stands wherever mcgp_run_paces puts it.  t = cum + lap_time.  If the car stops (rule or plan),
+ *      t = t + pit_loss; then, if a SERVE_AT_STOP penalty is pending and k >= its lap, t = t + seconds and it is served;
+ *      then, if an UNTIL_STOP offset is active and k >= its first_lap, it is cleared, which does not touch t (the lap
+ *      time of lap k carried the offset, the overtakes of lap k do not).  Stopped or not, an ON_LAP addition on lap k:
+ *      t = t + seconds.  At most four binary64 additions to t, in that order.  A car that retires on lap k reaches none
+ *      of this;
+ *   3. overtake passes.  They read the offset pace, as in mcgp_run_paces; penalties make nobody easier to pass;
+ *   4. at the flag, after lap L and before classification: every running car adds its unserved SERVE_AT_STOP seconds,
+ *      then its AT_FLAG seconds, and the field is sorted by (time, grid slot) again.  A scenario with no SERVE_AT_STOP
+ *      and no AT_FLAG penalty skips the step;
+ *   5. fate and laps carried as in mcgp_run_penalties and mcgp_run_paces: one stop on a lap k that is >= both laps
+ *      gives fate 1 (served at a stop) and closes the carried count at k - first_lap + 1.
+ * Identities: a call with every count zero is mcgp_run_strategies on the same plans, cell for cell; a call whose only
+ * non-empty table is the penalties is mcgp_run_penalties on the same arguments (hist, delta, fate, every order), and
+ * its carried is all in column 0 and its events are mcgp_run_events' counts of a scenario without overrides; the same
+ * for events only against mcgp_run_events (fate and carried all in column 0) and for offsets only against
+ * mcgp_run_paces; a scenario whose overrides equal what a simulation drew changes nothing for that simulation.
+ *   hist_out    [S][n][n]      [scenario][driver][position - 1]
+ *   delta_out   [S][n][2n - 1] as mcgp_run_strategies'; or NULL
+ *   fate_out    [S][n][4]      as mcgp_run_penalties'; or NULL
+ *   events_out  [S][3][L + 1]  as mcgp_run_events'; or NULL
+ *   carried_out [S][n][L + 1]  as mcgp_run_paces'; or NULL
+ *   orders_out  [S][n_sims][n] driver index classified p-th, or NULL
+ * The count outputs are ACCUMULATED into, orders_out is written, and all only after every launch has succeeded: on an
+ * error they are left as they were.  delta's centre bin, fate column 0 and carried column 0 are derived on the host
+ * from n_sims.  Every argument is checked before any device lookup, the tables in the order penalties, events, offsets,
+ * with the single-kind calls' messages: they name the scenario, the item by its table ("penalty 2", "event 0",
+ * "offset 1") and the field, so a "lap" or "first_lap" is never ambiguous.  deviates other than MCGP_DEVIATES_32 is
+ * refused.  n_sims == 0 succeeds without a device.  The device work goes chunk by chunk through mcgp_run_strategies'
+ * staging budget: per scenario and simulation a byte per driver (position | fate << 5), a u32 when events_out is wanted
+ * and a u16 per driver when carried_out is wanted, each in its own call's layout and counted by that call's counting
+ * kernel; device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or devices sums to the
+ * same counts.  mcgp_last_kernel_name afterwards is "mcgp::race_combined_kernel"; mcgp_last_launch_info describes the
+ * first chunk's race launch.  Added entry point only: MCGP_ABI_VERSION stays 6 and a caller tests for the symbol.
+ * Price (one MI355X, S60, two scenarios x 10^6 simulations, device ms per 10^6, medians of five with max - min;
+ * profiles/combined_time.txt): at the parent commit mcgp_run_strategies 98.22 (0.39), mcgp_run_penalties with
+ * a penalty to serve 99.83 (0.34), mcgp_run_events with a safety car 98.97 (0.23), mcgp_run_paces with an UNTIL_STOP
+ * offset 106.69 (0.39), the dearest; mcgp_run_combined with two empty scenarios 102.84 (0.41), 3.6 % below that; with the
+ * penalty 103.08 (0.35), the safety car 102.50 (0.45), the offset 108.13 (0.49), +1.4 %; with all three and a planned
+ * stop 109.59 (0.42), +2.7 %: each kind costs what it costs alone, their meeting nothing. */
+int32_t mcgp_run_combined(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                          const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios,
+                          const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                          const uint32_t *penalty_count, const mcgp_time_penalty *penalties,
+                          const uint32_t *event_count, const mcgp_lap_event *events,
+                          const uint32_t *pace_count, const mcgp_pace_offset *paces,
+                          uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device,
+                          uint64_t *hist_out, uint64_t *delta_out, uint64_t *fate_out,
+                          uint64_t *events_out, uint64_t *carried_out, uint8_t *orders_out);
+
 /* Race time gaps: the model's binary64 cumulative times, counted on the device as histograms over caller-given edges
  * (seconds): every car's gap to the leader by lap, the lead (winning margin on the last lap) and the gap between named
  * pairs of drivers, from the grid or from a mid-race state.  Everything is read from the race model's state after the

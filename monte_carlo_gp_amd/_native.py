@@ -297,7 +297,8 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_last_launch_info', 'mcgp_last_kernel_name', 'mcgp_run_championship', 'mcgp_run_matchups',
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
            'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
-           'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live', 'mcgp_run_paces')
+           'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live', 'mcgp_run_paces',
+           'mcgp_run_combined')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -440,6 +441,17 @@ def lib():
                                          C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
                                          C.POINTER(C.c_uint32), C.POINTER(McgpPaceOffset), C.c_uint64, C.c_uint64,
                                          C.c_uint64, C.c_int32, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
+        if 'mcgp_run_combined' not in missing:
+            # the plans, then (count, items) of the penalties, the events and the offsets, any pair of which may be NULL;
+            # hist, delta, fate, events, carried, orders
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_combined.restype = C.c_int32
+            L.mcgp_run_combined.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.POINTER(McgpRaceState),
+                                            C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
+                                            C.POINTER(C.c_uint32), C.POINTER(McgpTimePenalty),
+                                            C.POINTER(C.c_uint32), C.POINTER(McgpLapEvent),
+                                            C.POINTER(C.c_uint32), C.POINTER(McgpPaceOffset), C.c_uint64, C.c_uint64,
+                                            C.c_uint64, C.c_int32, u64p, u64p, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES

@@ -15,6 +15,8 @@
         --driver NOR --plan sc=:31/HARD --event green=none@31-57
     python -m monte_carlo_gp_amd.cli pace --race Bahrain --season 2024 --offline --driver NOR --offset damage=NOR:0.6@12+ \
         --offset 'box now=NOR:0.6@12+' --plan 'box now=:13/HARD' --offset push=NOR:-0.15@40-49
+    python -m monte_carlo_gp_amd.cli what-if --race Bahrain --season 2024 --offline --state lap30.json --driver NOR \
+        --event 'sc=sc@31' --plan 'sc=:31/HARD' --give 'sc=NOR:5' --offset 'sc=VER:0.4@31+'
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -776,6 +778,134 @@ def cmd_pace(args) -> int:
     return 0
 
 
+WHAT_IF_BASELINE = 'as drawn'
+
+
+def what_if_scenarios(driver=None, plans=(), window=None, gives=(), events=(), offsets=()):
+    """The what-if command's scenarios -> {NAME: {'plans', 'penalties', 'events', 'paces'}} for run_combined: 'as drawn'
+    (nothing) first, unless the user names a scenario 'as drawn' themselves; then one scenario per NAME in the order the
+    names first appear (events, gives, offsets, plans), holding every item given under that NAME.  --give takes the
+    penalty command's grammar behind NAME=.  --window [NAME=]A-B/COMP adds one scenario per lap, 'NAME L<lap>' (or
+    '<driver> L<lap>'), with the items of NAME and --driver's single stop on that lap."""
+    if not (plans or window or gives or events or offsets):
+        raise ValueError('give at least one --event, --give, --offset, --plan or --window')
+    if (plans or window) and not driver:
+        raise ValueError('--plan and --window need --driver')
+    out = {WHAT_IF_BASELINE: dict(plans=[], penalties=[], events=[], paces=[])}
+    at = lambda name: out.setdefault(name, dict(plans=[], penalties=[], events=[], paces=[]))
+    for text in events or ():
+        name, ev = parse_event(text)
+        at(name)['events'].append(ev)
+    for text in gives or ():
+        name, sep, rest = text.partition('=')
+        if not sep or not name.strip():
+            raise ValueError(f'--give {text!r}: expected NAME=DRIVER:SECONDS[:serve|flag|lap][@LAP]')
+        at(name.strip())['penalties'].append(parse_give(rest))
+    for text in offsets or ():
+        name, off = parse_offset(text)
+        at(name)['paces'].append(off)
+    for text in plans or ():
+        name, plan = parse_plan(text, driver)
+        if at(name)['plans']:
+            raise ValueError(f'--plan: scenario {name!r} given twice')
+        out[name]['plans'] = [plan]
+    if window:
+        from .simulation import PitPlan
+        name, sep, rest = window.partition('=')
+        of = name.strip() if sep else None
+        if sep and of not in out:
+            raise ValueError(f'--window {window!r}: no scenario {of!r} to sweep')
+        if of is not None and out[of]['plans']:
+            raise ValueError(f'--window {window!r}: scenario {of!r} has a --plan already')
+        laps, comp = parse_window(rest if sep else window)
+        for lap in laps:
+            sc = at(f'{of if of is not None else driver} L{lap}')
+            if of is not None:
+                sc.update({k: list(out[of][k]) for k in ('penalties', 'events', 'paces')})
+            sc['plans'] = [PitPlan(driver, [(lap, comp)])]
+    return out
+
+
+def cmd_what_if(args) -> int:
+    from .simulation import RaceState
+    fixture = synthetic_fixture()
+    if args.fixture:
+        with open(args.fixture) as f:
+            fixture = json.load(f)
+    elif not args.offline:
+        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+        return 2
+    state = None
+    if args.state:
+        with open(args.state) as f:
+            state = RaceState.from_json(json.load(f))
+    try:
+        scenarios = what_if_scenarios(args.driver, args.plan, args.window, args.give, args.event, args.offset)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    print(f"\n{'=' * 60}\nF1 What-If Scenarios: {args.season} {args.race}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
+          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
+    print('=' * 60 + '\n')
+    try:
+        res = F1Predictor(device=args.device).predict_combined(args.season, args.race, fixture, scenarios, state=state,
+                                                               n_simulations=args.simulations, seed=args.seed,
+                                                               allow_single_compound=args.allow_single_compound)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    base = res.names[0]
+    # --driver, then every driver an item names, in the order given; without either the five likeliest winners
+    named = ([args.driver] if args.driver else []) + [x.driver for sc in scenarios.values()
+                                                      for k in ('penalties', 'paces') for x in sc[k]]
+    shown = list(dict.fromkeys(d for d in named if d in res.drivers)) \
+        or sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
+    rows = []
+    for name in res.names:
+        sc = scenarios.get(name, {})
+        head = f"scenario: {name}"
+        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
+                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers}, drivers={})
+        if sc.get('events'):
+            ee = row['expected_events'] = res.expected_events(name)
+            head += f"   (laps with: safety car {ee['sc']:.2f}, VSC {ee['vsc']:.2f}, red flag {ee['red']:.2f})"
+        print(head)
+        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'change':>7} {'P(better)':>10}"
+              f"  gain +- SE")
+        epos, epos0 = res.expected_position(name), res.expected_position(base)
+        row['expected_position'] = epos
+        serving = {p.driver for p in sc.get('penalties', ()) if p.kind == 'serve'}
+        for d in shown:
+            c = res.compare(name, d)
+            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
+            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
+            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
+                                     expected_position_change=epos[d] - epos0[d], p_better=c['p_better'],
+                                     p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'])
+            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {epos[d] - epos0[d]:+7.2f} "
+                  f"{c['p_better']:10.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}")
+            if d in serving:                                # the fate of its penalty to serve
+                f = row['drivers'][d]['fate'] = res.fate_probabilities(name, d)
+                print(f"    penalty served at a stop {f['served']:.1%}, added at the flag {f['at_flag']:.1%}, "
+                      f"retired unserved {f['retired']:.1%}")
+            if (name, d) in (res.until_from or {}):         # the laps its until-stop offset was carried
+                dist = res.carried_distribution(name, d)
+                row['drivers'][d]['laps_carried'] = [float(x) for x in dist]
+                row['drivers'][d]['expected_laps_carried'] = res.expected_laps_carried(name, d)
+                top = sorted(range(len(dist)), key=lambda k: -dist[k])[:5]
+                print(f"    offset carried {row['drivers'][d]['expected_laps_carried']:.2f} laps on average; most likely: "
+                      + ', '.join(f'{k} laps {dist[k]:.1%}' for k in sorted(top) if dist[k] > 0))
+        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
+        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
+        rows.append(row)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
+    return 0
+
+
 def load_results(season: int) -> list:
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', f'results_{season}.json')
     with open(path) as f:
@@ -1321,6 +1451,32 @@ def main(argv=None) -> int:
     t.add_argument('--device', type=int, default=0)
     t.add_argument('--json', type=str, default=None)
     t.set_defaults(fn=cmd_pace)
+    t = sub.add_parser('what-if', help='race odds under scenarios that mix pit plans, time penalties, race events and '
+                                       'lap-time offsets')
+    t.add_argument('--season', type=int, default=2025)
+    t.add_argument('--race', type=str, required=True)
+    t.add_argument('--event', type=str, action='append', default=[],
+                   help="NAME=KIND@LAP[-LAP], as the events command's; items of one NAME make one scenario")
+    t.add_argument('--give', type=str, action='append', default=[],
+                   help="NAME=DRIVER:SECONDS[:serve|flag|lap][@LAP]: the penalty command's grammar behind the scenario's NAME")
+    t.add_argument('--offset', type=str, action='append', default=[],
+                   help="NAME=DRIVER:SECONDS@LAP-LAP or NAME=DRIVER:SECONDS@LAP+, as the pace command's")
+    t.add_argument('--driver', type=str, default=None,
+                   help='the driver of the --plan and --window scenarios; shown with every driver an item names')
+    t.add_argument('--plan', type=str, action='append', default=[],
+                   help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's; joins the scenario of that NAME")
+    t.add_argument('--window', type=str, default=None,
+                   help='[NAME=]A-B/COMP: one scenario per lap A..B with the items of NAME and a single stop on that lap')
+    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
+    t.add_argument('--allow-single-compound', action='store_true',
+                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
+    t.add_argument('--simulations', type=int, default=100000)
+    t.add_argument('--seed', type=int, default=None)
+    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
+    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
+    t.add_argument('--device', type=int, default=0)
+    t.add_argument('--json', type=str, default=None)
+    t.set_defaults(fn=cmd_what_if)
     args = ap.parse_args(argv)
     return args.fn(args)
 

@@ -26,6 +26,7 @@
 #include "penalty_pack.h"
 #include "pace_pack.h"
 #include "event_pack.h"
+#include "combined.hip.h"
 #include "champ_pack.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
@@ -954,27 +955,40 @@ struct ScenarioChunk {
     uint8_t *stage;                         // [S][m][n] bytes: every driver's finishing position
 };
 
-// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events and mcgp_run_paces each have of their own; run_scenarios has the rest.
+// One item table of a scenario call beside the plans, one count per scenario: the arguments, their names and the check of
+// the counts before anything is packed.
+struct ScenarioTable {
+    const char *count_name, *items_name;
+    const uint32_t *item_count;
+    const void *items;
+    std::function<std::string(uint64_t *n_items)> check_counts;
+};
+
+// One count segment of a scenario call behind hist and delta: the caller's buffer (NULL: not wanted), its cells, a
+// fix-up on the host (empty: none).
+struct ScenarioOutput {
+    uint64_t *out;
+    size_t (*cells)(size_t S, size_t n, size_t L);
+    std::function<void(unsigned long long *extra, size_t rows, uint64_t n_sims)> fix_up;
+};
+
+// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces and mcgp_run_combined each have of their
+// own; run_scenarios has the rest.
 struct ScenarioKind {
     const char *what;                       // the call in check_deviates_32's message
     const char *geo_name, *kernel_name;     // generic_geometry's and note_launch's name of the race kernel
     KernelFn geo_fn;                        // the race kernel (for its register count)
-    // the kind's own input table, one count per scenario: the arguments and their names (all NULL: no table)
-    const char *count_name = nullptr, *items_name = nullptr;
-    const uint32_t *item_count = nullptr;
-    const void *items = nullptr;
-    std::function<std::string(uint64_t *n_items)> check_counts;          // its counts, before anything is packed
-    std::function<std::string(int first_lap, bool resumed)> pack;        // its items, behind pack_scenarios
-    size_t sim_bytes;                                                    // staged per (scenario, simulation)
+    std::vector<ScenarioTable> tables;                                   // the kind's own input tables, checked in this order
+    std::function<std::string(int first_lap, bool resumed)> pack;        // their items, behind pack_scenarios
+    size_t sim_bytes = 0;                                                // staged per (scenario, simulation)
     uint8_t pos_mask = 0xFF;                                             // the position in a staged byte
     std::function<void(Layout &, uint64_t chunk)> regions;               // its regions of the workspace
     std::function<void(const ScenarioChunk &)> race;                     // launches the race kernel
-    // launches the counting kernel (run when delta or the kind's output is wanted; NULL for the one that is not)
-    std::function<void(const ScenarioChunk &, uint64_t grid_cap, unsigned long long *delta, unsigned long long *extra)> count;
-    // the kind's own count segment behind hist and delta: the caller's buffer, its cells, a fix-up on the host
-    uint64_t *extra_out = nullptr;
-    size_t (*extra_cells)(size_t S, size_t n, size_t L) = nullptr;
-    std::function<void(unsigned long long *extra, size_t rows, uint64_t n_sims)> fix_up;
+    // launches the counting kernels (run when delta or one of the kind's outputs is wanted): delta and extra[i], the
+    // device segment of outputs[i], are NULL for what is not wanted
+    std::function<void(const ScenarioChunk &, uint64_t grid_cap, unsigned long long *delta, unsigned long long *const *extra)>
+        count;
+    std::vector<ScenarioOutput> outputs;                                 // the kind's own count segments
 };
 
 int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
@@ -985,21 +999,24 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     // ---- every argument is checked before any device is looked up
     if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
     if (!plan_count) return fail(MCGP_E_BAD_ARG, "plan_count is NULL");
-    if (k.count_name && !k.item_count) return fail(MCGP_E_BAD_ARG, std::string(k.count_name) + " is NULL");
+    for (const ScenarioTable &t : k.tables)
+        if (!t.item_count) return fail(MCGP_E_BAD_ARG, std::string(t.count_name) + " is NULL");
     if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
         return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]");
-    uint64_t n_plans = 0, n_items = 0;
+    uint64_t n_plans = 0;
+    std::vector<uint64_t> n_items(k.tables.size(), 0);
     for (uint32_t si = 0; si < n_scenarios; ++si) {
         if (plan_count[si] > mcgp::kMaxCars)
             return fail(MCGP_E_BAD_ARG, "scenario " + std::to_string(si) + ": plan_count must be in [0, 32]");
         n_plans += plan_count[si];
     }
-    if (k.check_counts) {
-        const std::string err = k.check_counts(&n_items);
+    for (size_t ti = 0; ti < k.tables.size(); ++ti) {
+        const std::string err = k.tables[ti].check_counts(&n_items[ti]);
         if (!err.empty()) return fail(MCGP_E_BAD_ARG, err);
     }
     if (n_plans && !plans) return fail(MCGP_E_BAD_ARG, "plans is NULL");
-    if (n_items && !k.items) return fail(MCGP_E_BAD_ARG, std::string(k.items_name) + " is NULL");
+    for (size_t ti = 0; ti < k.tables.size(); ++ti)
+        if (n_items[ti] && !k.tables[ti].items) return fail(MCGP_E_BAD_ARG, std::string(k.tables[ti].items_name) + " is NULL");
     int rc = check_source(grid_probs, state);
     if (rc != MCGP_OK) return rc;
     std::vector<mcgp::KParams> kps(1);
@@ -1025,7 +1042,11 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     const size_t c_hist = (size_t)S * n * n, c_delta = (size_t)S * n * w;
     // hist [S][n][n] | delta [S][n][2n - 1] | the kind's own counts
     std::vector<Counts::Seg> segs = {{hist_out, c_hist}, {delta_out, c_delta}};
-    if (k.extra_cells) segs.push_back({k.extra_out, k.extra_cells(S, n, (size_t)L)});
+    bool want_extra = false;
+    for (const ScenarioOutput &o : k.outputs) {
+        segs.push_back({o.out, o.cells(S, n, (size_t)L)});
+        want_extra |= o.out != nullptr;
+    }
     Counts counts;
     std::vector<uint8_t> orders;            // collected on the host, handed over only once everything has run
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
@@ -1059,8 +1080,10 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
             l.gx = gx, l.block = block, l.lds = lds, l.n_batches = n_batches, l.m = m, l.first_sim = sim_offset + done;
             k.race(l);
             HIP_TRY(hipGetLastError());
-            if (count_delta || k.extra_out) {
-                k.count(l, grid_cap, count_delta ? ws.count(1) : nullptr, k.extra_out ? ws.count(2) : nullptr);
+            if (count_delta || want_extra) {
+                std::vector<unsigned long long *> extra;
+                for (size_t oi = 0; oi < k.outputs.size(); ++oi) extra.push_back(k.outputs[oi].out ? ws.count(2 + oi) : nullptr);
+                k.count(l, grid_cap, count_delta ? ws.count(1) : nullptr, extra.data());
                 HIP_TRY(hipGetLastError());
             }
             if (orders_out) {
@@ -1085,10 +1108,46 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
             b[row * w + n - 1] = n_sims - rest;
         }
     }
-    if (k.extra_out && k.fix_up) k.fix_up(b + c_delta, (size_t)S * n, n_sims);
+    {
+        unsigned long long *x = b + c_delta;
+        for (const ScenarioOutput &o : k.outputs) {
+            if (o.out && o.fix_up) o.fix_up(x, (size_t)S * n, n_sims);
+            x += o.cells(S, n, (size_t)L);
+        }
+    }
     counts.add_to(segs);
     if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
     return MCGP_OK;
+}
+
+// fate [S][n][4]; column 0 (no SERVE_AT_STOP penalty) is, like delta's centre bin, what the others leave of n_sims
+ScenarioOutput fate_output(uint64_t *fate_out)
+{
+    return {fate_out, [](size_t S, size_t n, size_t) { return S * n * 4; },
+            [](unsigned long long *f, size_t rows, uint64_t n_sims) {
+                for (size_t row = 0; row < rows; ++row) f[row * 4] = n_sims - (f[row * 4 + 1] + f[row * 4 + 2] + f[row * 4 + 3]);
+            }};
+}
+
+// events [S][3][L + 1]
+ScenarioOutput events_output(uint64_t *events_out)
+{
+    return {events_out, [](size_t S, size_t, size_t L) { return S * 3 * (L + 1); }, nullptr};
+}
+
+// carried [S][n][L + 1]; column 0 is, like delta's centre bin, what the others leave of n_sims: all of it for a driver
+// without an UNTIL_STOP offset
+ScenarioOutput carried_output(uint64_t *carried_out, const mcgp_config *cfg)
+{
+    return {carried_out, [](size_t S, size_t n, size_t L) { return S * n * (L + 1); },
+            [cfg](unsigned long long *c, size_t rows, uint64_t n_sims) {      // (cfg has been checked by then)
+                const size_t w = (size_t)cfg->total_laps + 1;
+                for (size_t row = 0; row < rows; ++row) {
+                    unsigned long long rest = 0;
+                    for (size_t j = 1; j < w; ++j) rest += c[row * w + j];
+                    c[row * w] = n_sims - rest;
+                }
+            }};
 }
 
 }  // namespace
@@ -2077,7 +2136,7 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
                            (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, l.n_batches);
     };
     // every scenario but the first against the first: S - 1 grid rows (never run for one scenario)
-    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *) {
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *) {
         const uint64_t tiles = (l.m + mcgp::kStrategyCountBlock - 1) / mcgp::kStrategyCountBlock;
         const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / (l.S - 1)));
         hipLaunchKernelGGL(mcgp::strategy_count_deltas, dim3((uint32_t)gxc, l.S - 1), dim3(mcgp::kStrategyCountBlock), 0,
@@ -2099,8 +2158,9 @@ int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, cons
     const mcgp::PenaltyScenario *d_pn = nullptr;
     const mcgp::PenaltyLap *d_pl = nullptr;
     ScenarioKind k = {"penalties run", "penalties", "mcgp::race_penalties_kernel", reinterpret_cast<KernelFn>(kernel)};
-    k.count_name = "penalty_count", k.item_count = penalty_count, k.items_name = "penalties", k.items = penalties;
-    k.check_counts = [&](uint64_t *n_pens) { return mcgp::check_penalty_counts(n_scenarios, penalty_count, n_pens); };
+    k.tables = {{"penalty_count", "penalties", penalty_count, penalties, [&](uint64_t *n_pens) {
+        return mcgp::check_penalty_counts(n_scenarios, penalty_count, n_pens);
+    }}};
     k.pack = [&](int first_lap, bool resumed) {
         return mcgp::pack_penalties(n_scenarios, penalty_count, penalties, n, cfg->total_laps, first_lap, resumed, &pens,
                                     &pen_laps);
@@ -2115,18 +2175,15 @@ int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, cons
         hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_pn, d_pl, l.m,
                            l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, l.n_batches);
     };
-    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *d_fate) {
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
+        unsigned long long *d_fate = extra[0];
         const uint64_t tiles = (l.m + mcgp::kPenaltyCountBlock - 1) / mcgp::kPenaltyCountBlock;
         const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
         hipLaunchKernelGGL(mcgp::penalties_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kPenaltyCountBlock), 0, nullptr,
                            l.stage, l.m, n, d_delta, d_fate);
     };
     // fate [S][n][4]; column 0 (no SERVE_AT_STOP penalty) is, like delta's centre bin, what the others leave of n_sims
-    k.extra_out = fate_out;
-    k.extra_cells = [](size_t S, size_t n_, size_t) { return S * n_ * 4; };
-    k.fix_up = [](unsigned long long *f, size_t rows, uint64_t n_sims_) {
-        for (size_t row = 0; row < rows; ++row) f[row * 4] = n_sims_ - (f[row * 4 + 1] + f[row * 4 + 2] + f[row * 4 + 3]);
-    };
+    k.outputs = {fate_output(fate_out)};
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
                          hist_out, delta_out, orders_out, k);
 }
@@ -2142,8 +2199,9 @@ int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const d
     const uint8_t *d_el = nullptr;
     uint32_t *d_evs = nullptr;              // [S][m] packed event counts of a chunk's simulations
     ScenarioKind k = {"events run", "events", "mcgp::race_events_kernel", reinterpret_cast<KernelFn>(kernel)};
-    k.count_name = "event_count", k.item_count = event_count, k.items_name = "events", k.items = events;
-    k.check_counts = [&](uint64_t *n_events) { return mcgp::check_event_counts(n_scenarios, event_count, n_events); };
+    k.tables = {{"event_count", "events", event_count, events, [&](uint64_t *n_events) {
+        return mcgp::check_event_counts(n_scenarios, event_count, n_events);
+    }}};
     k.pack = [&](int first_lap, bool resumed) {
         return mcgp::pack_events(n_scenarios, event_count, events, cfg->total_laps, first_lap, resumed, &event_laps);
     };
@@ -2157,14 +2215,14 @@ int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const d
         hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_el, l.m,
                            l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, d_evs, l.n_batches);
     };
-    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *d_ev) {
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
+        unsigned long long *d_ev = extra[0];
         const uint64_t tiles = (l.m + mcgp::kEventsCountBlock - 1) / mcgp::kEventsCountBlock;
         const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
         hipLaunchKernelGGL(mcgp::events_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kEventsCountBlock), 0, nullptr, l.stage,
                            d_evs, l.m, n, (uint32_t)cfg->total_laps, d_delta, d_ev);
     };
-    k.extra_out = events_out;               // events [S][3][L + 1]
-    k.extra_cells = [](size_t S, size_t, size_t L) { return S * 3 * (L + 1); };
+    k.outputs = {events_output(events_out)};
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
                          hist_out, delta_out, orders_out, k);
 }
@@ -2184,8 +2242,9 @@ int32_t mcgp_run_paces(const mcgp_config *cfg, const mcgp_drivers *drv, const do
     const double *d_sec = nullptr;
     uint16_t *d_car = nullptr;              // [S][m][n] laps carried of a chunk's simulations (carried_out wanted)
     ScenarioKind k = {"paces run", "paces", "mcgp::race_paces_kernel", reinterpret_cast<KernelFn>(kernel)};
-    k.count_name = "pace_count", k.item_count = pace_count, k.items_name = "paces", k.items = paces;
-    k.check_counts = [&](uint64_t *n_paces) { return mcgp::check_pace_counts(n_scenarios, pace_count, n_paces); };
+    k.tables = {{"pace_count", "paces", pace_count, paces, [&](uint64_t *n_paces) {
+        return mcgp::check_pace_counts(n_scenarios, pace_count, n_paces);
+    }}};
     // lap 1 reads the base pace too: from the grid an offset may name it
     k.pack = [&](int first_lap, bool resumed) {
         return mcgp::pack_paces(n_scenarios, pace_count, paces, n, cfg->total_laps, resumed ? first_lap : 1, resumed, &pscen,
@@ -2204,25 +2263,109 @@ int32_t mcgp_run_paces(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                            l.m, l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, d_car, l.n_batches);
     };
     // grid rows: the scenarios; grid layers: the deltas, then (carried_out wanted) one per driver
-    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *d_carried) {
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
+        unsigned long long *d_carried = extra[0];
         const uint32_t gz = d_carried ? 1u + n : 1u;
         const uint64_t tiles = (l.m + mcgp::kPacesCountBlock - 1) / mcgp::kPacesCountBlock;
         const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / ((uint64_t)l.S * gz)));
         hipLaunchKernelGGL(mcgp::paces_count, dim3((uint32_t)gxc, l.S, gz), dim3(mcgp::kPacesCountBlock), 0, nullptr, l.stage,
                            d_car, d_ps, l.m, n, (uint32_t)cfg->total_laps, d_delta, d_carried);
     };
-    // carried [S][n][L + 1]; column 0 is, like delta's centre bin, what the others leave of n_sims: all of it for a
-    // driver without an UNTIL_STOP offset
-    k.extra_out = carried_out;
-    k.extra_cells = [](size_t S, size_t n_, size_t L) { return S * n_ * (L + 1); };
-    k.fix_up = [&](unsigned long long *c, size_t rows, uint64_t n_sims_) {
-        const size_t w = (size_t)cfg->total_laps + 1;
-        for (size_t row = 0; row < rows; ++row) {
-            unsigned long long rest = 0;
-            for (size_t j = 1; j < w; ++j) rest += c[row * w + j];
-            c[row * w] = n_sims_ - rest;
+    k.outputs = {carried_output(carried_out, cfg)};
+    return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
+                         hist_out, delta_out, orders_out, k);
+}
+
+int32_t mcgp_run_combined(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                          const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                          const mcgp_pit_plan *plans, const uint32_t *penalty_count, const mcgp_time_penalty *penalties,
+                          const uint32_t *event_count, const mcgp_lap_event *events, const uint32_t *pace_count,
+                          const mcgp_pace_offset *paces, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                          int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *fate_out, uint64_t *events_out,
+                          uint64_t *carried_out, uint8_t *orders_out)
+{
+    const auto kernel = state ? &mcgp::race_combined_kernel<true> : &mcgp::race_combined_kernel<false>;
+    // a NULL count array: none in any scenario (n_scenarios is checked, against the same limit, before a count is read)
+    static const uint32_t none[mcgp::kMaxStrategyScenarios] = {};
+    if (!penalty_count) penalty_count = none;
+    if (!event_count) event_count = none;
+    if (!pace_count) pace_count = none;
+    std::vector<mcgp::PenaltyScenario> pens;
+    std::vector<mcgp::PenaltyLap> pen_laps;
+    std::vector<uint8_t> event_laps;
+    std::vector<mcgp::PaceScenario> pscen;
+    std::vector<mcgp::PaceLap> pace_laps;
+    std::vector<double> lap_sec;
+    const mcgp::PenaltyScenario *d_pn = nullptr;
+    const mcgp::PenaltyLap *d_nl = nullptr;
+    const uint8_t *d_el = nullptr;
+    const mcgp::PaceScenario *d_ps = nullptr;
+    const mcgp::PaceLap *d_pl = nullptr;
+    const double *d_sec = nullptr;
+    uint32_t *d_evs = nullptr;              // [S][m] packed event counts of a chunk's simulations (events_out wanted)
+    uint16_t *d_car = nullptr;              // [S][m][n] laps carried of a chunk's simulations (carried_out wanted)
+    ScenarioKind k = {"combined run", "combined", "mcgp::race_combined_kernel", reinterpret_cast<KernelFn>(kernel)};
+    k.tables = {
+        {"penalty_count", "penalties", penalty_count, penalties,
+         [&](uint64_t *total) { return mcgp::check_penalty_counts(n_scenarios, penalty_count, total); }},
+        {"event_count", "events", event_count, events,
+         [&](uint64_t *total) { return mcgp::check_event_counts(n_scenarios, event_count, total); }},
+        {"pace_count", "paces", pace_count, paces,
+         [&](uint64_t *total) { return mcgp::check_pace_counts(n_scenarios, pace_count, total); }},
+    };
+    // each packer with its own call's first lap: lap 1 reads the base pace, so from the grid an offset may name it
+    k.pack = [&](int first_lap, bool resumed) {
+        const int L = cfg->total_laps;
+        std::string e = mcgp::pack_penalties(n_scenarios, penalty_count, penalties, n, L, first_lap, resumed, &pens, &pen_laps);
+        if (e.empty()) e = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, resumed, &event_laps);
+        if (e.empty())
+            e = mcgp::pack_paces(n_scenarios, pace_count, paces, n, L, resumed ? first_lap : 1, resumed, &pscen, &pace_laps,
+                                 &lap_sec);
+        return e;
+    };
+    // a byte per driver (position | fate << 5), the u32 of event counts and the drivers' u16 of laps carried when wanted
+    k.sim_bytes = (size_t)n + (events_out ? 4 : 0) + (carried_out ? (size_t)n * 2 : 0);
+    k.pos_mask = mcgp::kStagePosMask;
+    k.regions = [&](Layout &ws, uint64_t chunk) {
+        if (events_out) ws.add(&d_evs, (size_t)n_scenarios * chunk);
+        if (carried_out) ws.add(&d_car, (size_t)n_scenarios * chunk * n);
+        ws.add(&d_pn, n_scenarios, pens.data());
+        ws.add(&d_nl, pen_laps.size(), pen_laps.data());
+        ws.add(&d_el, event_laps.size(), event_laps.data());
+        ws.add(&d_ps, n_scenarios, pscen.data());
+        ws.add(&d_pl, pace_laps.size(), pace_laps.data());
+        ws.add(&d_sec, lap_sec.size(), lap_sec.data());
+    };
+    k.race = [&](const ScenarioChunk &l) {
+        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_pn, d_nl, d_el, d_ps,
+                           d_pl, d_sec, l.m, l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, d_evs,
+                           d_car, l.n_batches);
+    };
+    // the three siblings' counting kernels as they are, each on the staging in its own layout; the deltas come from
+    // penalties_count, the one that masks the fate off the position byte
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
+        const uint32_t L = (uint32_t)cfg->total_laps;
+        if (d_delta || extra[0]) {
+            const uint64_t tiles = (l.m + mcgp::kPenaltyCountBlock - 1) / mcgp::kPenaltyCountBlock;
+            const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
+            hipLaunchKernelGGL(mcgp::penalties_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kPenaltyCountBlock), 0, nullptr,
+                               l.stage, l.m, n, d_delta, extra[0]);
+        }
+        if (extra[1]) {
+            const uint64_t tiles = (l.m + mcgp::kEventsCountBlock - 1) / mcgp::kEventsCountBlock;
+            const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
+            hipLaunchKernelGGL(mcgp::events_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kEventsCountBlock), 0, nullptr, l.stage,
+                               d_evs, l.m, n, L, (unsigned long long *)nullptr, extra[1]);
+        }
+        if (extra[2]) {
+            const uint32_t gz = 1u + n;     // layer 0, the deltas, returns at once
+            const uint64_t tiles = (l.m + mcgp::kPacesCountBlock - 1) / mcgp::kPacesCountBlock;
+            const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / ((uint64_t)l.S * gz)));
+            hipLaunchKernelGGL(mcgp::paces_count, dim3((uint32_t)gxc, l.S, gz), dim3(mcgp::kPacesCountBlock), 0, nullptr,
+                               l.stage, d_car, d_ps, l.m, n, L, (unsigned long long *)nullptr, extra[2]);
         }
     };
+    k.outputs = {fate_output(fate_out), events_output(events_out), carried_output(carried_out, cfg)};
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
                          hist_out, delta_out, orders_out, k);
 }

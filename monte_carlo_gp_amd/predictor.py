@@ -370,6 +370,25 @@ class F1Predictor:
                              track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
                              allow_single_compound=allow_single_compound)
 
+    def predict_combined(self, season: int, race: str, fixture: dict | str, scenarios: dict, state=None,
+                         n_simulations: int = 100000, seed: int | None = None, prediction_point: str = 'fp2',
+                         allow_single_compound: bool = False):
+        """Combined what-if scenarios (not in the reference): predict_strategies' race run through
+        RaceSimulator.run_combined under each scenario of `scenarios` ({name: {'plans': [PitPlan, ...], 'penalties':
+        [TimePenalty, ...], 'events': [RaceEvent, ...], 'paces': [PaceOffset, ...]}}).  An empty scenario reproduces
+        predict_weekend's (or predict_from_state's) race for the same seed.  Returns the CombinedResult."""
+        if isinstance(fixture, str):
+            with open(fixture) as f:
+                fixture = json.load(f)
+        if not fixture.get('drivers'):
+            raise ValueError(f"No practice data available for {season} {race}")
+        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
+        sim = RaceSimulator(inp['config'], device=self.device)
+        return sim.run_combined(n_simulations, scenarios, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
+                                inp['driver_dnf_rates'], grid_probs=inp['grid_probs'] if state is None else None,
+                                state=state, seed=seed, track_condition=inp['track_condition'],
+                                drivers=list(inp['grid_probs']), allow_single_compound=allow_single_compound)
+
     @staticmethod
     def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace,
                      gaps=None, conditions=None, tyres=False, moves=False) -> dict:

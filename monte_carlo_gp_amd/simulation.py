@@ -413,12 +413,13 @@ class RaceSimulator:
         call = self._entry_call(entry, prob, head(prob.n), sim_offset, self._resolve_seed(seed), outs)
         return self._run_counted(n_simulations, drivers, alloc, call)
 
-    def _pack_plans(self, names, plans_of, src, check_compounds, items_of=None, pack_items=None):
-        """The scenarios' pit plans as mcgp_pit_plan structs with their count per scenario, and the items of the call's
-        own kind likewise, through pack_items(name, items, index) -> [struct]: scenario by scenario, plans first.
-        check_compounds: the two-compound rule holds for every plan."""
+    def _pack_plans(self, names, plans_of, src, check_compounds, kinds=()):
+        """The scenarios' pit plans as mcgp_pit_plan structs with their count per scenario, and likewise the items of
+        each of the call's own `kinds`, (items_of {name: [item]}, pack_items), through pack_items(name, items, index)
+        -> [struct]: scenario by scenario, plans first, then the kinds in their order.  check_compounds: the
+        two-compound rule holds for every plan.  -> counts, structs, [(counts, structs) of each kind]."""
         index = {d: i for i, d in enumerate(src.drivers)}
-        counts, c_plans, item_counts, c_items = [], [], [], []
+        counts, c_plans, packed_kinds = [], [], [([], []) for _ in kinds]
         for name in names:
             plans = plans_of.get(name, [])
             for plan in plans:
@@ -432,41 +433,43 @@ class RaceSimulator:
                     check_two_compounds(plan, used, name)
                 c_plans.append(plan.c_struct(index, from_state=src.state is not None))
             counts.append(len(plans))
-            if pack_items is not None:
+            for (items_of, pack_items), (item_counts, c_items) in zip(kinds, packed_kinds):
                 packed = pack_items(name, items_of.get(name, []), index)
                 c_items += packed
                 item_counts.append(len(packed))
-        return counts, c_plans, item_counts, c_items
+        return counts, c_plans, packed_kinds
 
-    def _run_scenarios(self, entry, result, label, n_simulations, items, strategies, race, grid_probs, state, seed,
-                       sim_offset, drivers, return_orders, allow_single_compound, item_type=None, pack_items=None,
-                       extra=None):
-        """run_strategies, run_penalties, run_events and run_paces: the race under named scenarios of pit plans
-        (`strategies`) and, for all but the first, of the call's own `items` ({name: [item]}; their names come first).  pack_items: see
-        _pack_plans, its structs are `item_type`s; extra = (name, shape(S, n, L)): the kind's own count array, behind
-        hist and delta among the outputs; result: the result class; label: the dicts' names for the message."""
+    def _run_scenarios(self, entry, result, label, n_simulations, kinds, strategies, race, grid_probs, state, seed,
+                       sim_offset, drivers, return_orders, allow_single_compound):
+        """run_strategies, run_penalties, run_events, run_paces and run_combined: the race under named scenarios of pit
+        plans (`strategies`) and of the call's own `kinds` of items, a list (empty for run_strategies) of (items {name:
+        [item]}, item_type: their struct, pack_items: see _pack_plans, extra = (name, shape(S, n, L)): the kind's own
+        count array).  The scenario names are the union of the dicts in the order given, the kinds' first; the kinds'
+        (count, items) pairs follow the plans among the arguments and their count arrays follow hist and delta among
+        the outputs, both in the kinds' order.  result: the result class; label: the dicts' names for the message."""
         src = self._source(grid_probs, state, drivers)
         strategies = strategies or {}
-        first = strategies if items is None else items
-        names = [str(k) for k in first.keys()] + [str(k) for k in strategies.keys() if str(k) not in
-                                                  {str(j) for j in first.keys()}]
+        names = []
+        for given in [items for items, _, _, _ in kinds] + [strategies]:
+            names += [str(k) for k in given.keys() if str(k) not in names]
         if not 1 <= len(names) <= N.MAX_SCENARIOS:
             raise ValueError(f'{label}: 1 to {N.MAX_SCENARIOS} scenarios, got {len(names)}')
         drivers = src.drivers
         prob = self._problem(drivers, *race)
         n, L, S = prob.n, int(self.config.total_laps), len(names)
         src.arrays                                   # (a bad state is reported before a bad plan)
-        counts, c_plans, item_counts, c_items = self._pack_plans(
-            names, {str(k): list(v) for k, v in strategies.items()}, src, not allow_single_compound and race[-1] == 'dry',
-            {str(k): list(v) for k, v in (items or {}).items()}, pack_items)
+        by_name = lambda given: {str(k): list(v) for k, v in given.items()}
+        counts, c_plans, packed_kinds = self._pack_plans(
+            names, by_name(strategies), src, not allow_single_compound and race[-1] == 'dry',
+            [(by_name(items), pack) for items, _, pack, _ in kinds])
         head = src.c_args() + (n, S, (C.c_uint32 * S)(*counts), (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans))
-        if pack_items is not None:
+        for (_, item_type, _, _), (item_counts, c_items) in zip(kinds, packed_kinds):
             head += ((C.c_uint32 * S)(*item_counts), (item_type * max(len(c_items), 1))(*c_items))
         n_simulations = max(int(n_simulations), 0)
         seed64 = self._resolve_seed(seed)
         if not hasattr(N.lib(), entry):
             raise N.McgpError(-1, f'the loaded library does not export {entry}')
-        shapes = dict(hist=(S, n, n), delta=(S, n, 2 * n - 1), **({extra[0]: extra[1](S, n, L)} if extra else {}))
+        shapes = dict(hist=(S, n, n), delta=(S, n, 2 * n - 1), **{extra[0]: extra[1](S, n, L) for _, _, _, extra in kinds})
 
         def alloc(count):
             return dict({k: np.zeros(shape, np.uint64) for k, shape in shapes.items()},
@@ -475,6 +478,80 @@ class RaceSimulator:
         total = self._run_counted(n_simulations, drivers, alloc,
                                   self._entry_call(entry, prob, head, sim_offset, seed64, list(shapes) + ['orders']), 1)
         return result(names=names, drivers=drivers, n_simulations=n_simulations, **total)
+
+    # ---- the scenario calls' own kinds of items: (items, struct, pack_items, (count array, its shape)) for _run_scenarios
+    def _penalty_kind(self, penalties, state):
+        def pack(name, pens, index):
+            packed, seen = [], set()
+            for pen in pens:
+                if str(pen.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {pen.driver!r} is not one of the drivers')
+                c = pen.c_struct(index, 2 if state is None else int(state.lap) + 1)
+                key = (c.driver, c.kind, c.lap if c.kind == N.PEN_ON_LAP else 0)
+                if key in seen:
+                    raise ValueError(f'scenario {name!r}: {pen.driver} has two penalties of kind {pen.kind!r}'
+                                     + (f' on lap {c.lap}' if c.kind == N.PEN_ON_LAP else '') + '; sum them into one')
+                seen.add(key)
+                packed.append(c)
+            if len(pens) > N.MAX_SCENARIO_PENALTIES:
+                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_PENALTIES} penalties, got {len(pens)}')
+            return packed
+
+        return penalties, N.McgpTimePenalty, pack, ('fate', lambda S, n, L: (S, n, 4))
+
+    def _event_kind(self, events, state):
+        def pack(name, evs, index):
+            if len(evs) > N.MAX_SCENARIO_EVENTS:
+                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_EVENTS} overrides, got {len(evs)}')
+            packed, covered = [], {}
+            for ev in evs:
+                try:
+                    c = ev.c_struct(2 if state is None else int(state.lap) + 1, int(self.config.total_laps))
+                except ValueError as e:
+                    raise ValueError(f'scenario {name!r}: {e}') from None
+                for lap in range(c.first_lap, c.last_lap + 1):
+                    if lap in covered:
+                        raise ValueError(f'scenario {name!r}: lap {lap} has two overrides ({covered[lap]} and {ev})')
+                    covered[lap] = ev
+                packed.append(c)
+            return packed
+
+        return events, N.McgpLapEvent, pack, ('events', lambda S, n, L: (S, 3, L + 1))
+
+    def _pace_kind(self, paces, grid_probs, state):
+        first = _Source(grid_probs, state, None, self.config.total_laps).first_lap(from_grid=1)
+
+        def pack(name, offs, index):
+            if len(offs) > N.MAX_SCENARIO_PACES:
+                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_PACES} offsets, got {len(offs)}')
+            packed, covered, until = [], {}, {}
+            for off in offs:
+                if str(off.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {off.driver!r} is not one of the drivers')
+                try:
+                    c = off.c_struct(index, first, int(self.config.total_laps))
+                except ValueError as e:
+                    raise ValueError(f'scenario {name!r}: {e}') from None
+                if c.kind == N.PACE_UNTIL_STOP:
+                    if c.driver in until:
+                        raise ValueError(f'scenario {name!r}: {off.driver} has two until-stop offsets '
+                                         f'({until[c.driver]} and {off})')
+                    until[c.driver] = off
+                else:
+                    for lap in range(c.first_lap, c.last_lap + 1):
+                        if (c.driver, lap) in covered:
+                            raise ValueError(f'scenario {name!r}: {off.driver} has two offsets on lap {lap} '
+                                             f'({covered[c.driver, lap]} and {off})')
+                        covered[c.driver, lap] = off
+                packed.append(c)
+            return packed
+
+        return paces, N.McgpPaceOffset, pack, ('carried', lambda S, n, L: (S, n, L + 1))
+
+    @staticmethod
+    def _until_from(paces):
+        return {(str(name), str(off.driver)): int(off.until_stop_from) for name, offs in paces.items()
+                for off in offs if off.until_stop_from is not None}
 
     # ------------------------------------------------------------------ reference surface
     def run_monte_carlo(
@@ -671,7 +748,7 @@ class RaceSimulator:
         ValueError unless allow_single_compound.  32-bit deviates only; same seed rules and device sharding as
         run_monte_carlo.  last_histogram: [S, n, n]."""
         return self._run_scenarios(
-            'mcgp_run_strategies', StrategyResult, 'strategies', n_simulations, None, strategies,
+            'mcgp_run_strategies', StrategyResult, 'strategies', n_simulations, [], strategies,
             (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
             drivers, return_orders, allow_single_compound)
 
@@ -701,26 +778,11 @@ class RaceSimulator:
         them).  Everything else -- the remaining arguments, the plans' checks, the simulation ids and draws, the seed
         rules and the device sharding -- is run_strategies': a scenario without penalties gives exactly its counts.
         last_histogram: [S, n, n]."""
-        def pack(name, pens, index):
-            packed, seen = [], set()
-            for pen in pens:
-                if str(pen.driver) not in index:
-                    raise ValueError(f'scenario {name!r}: {pen.driver!r} is not one of the drivers')
-                c = pen.c_struct(index, 2 if state is None else int(state.lap) + 1)
-                key = (c.driver, c.kind, c.lap if c.kind == N.PEN_ON_LAP else 0)
-                if key in seen:
-                    raise ValueError(f'scenario {name!r}: {pen.driver} has two penalties of kind {pen.kind!r}'
-                                     + (f' on lap {c.lap}' if c.kind == N.PEN_ON_LAP else '') + '; sum them into one')
-                seen.add(key)
-                packed.append(c)
-            if len(pens) > N.MAX_SCENARIO_PENALTIES:
-                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_PENALTIES} penalties, got {len(pens)}')
-            return packed
-
         return self._run_scenarios(
-            'mcgp_run_penalties', PenaltyResult, 'penalties / strategies', n_simulations, penalties, strategies,
+            'mcgp_run_penalties', PenaltyResult, 'penalties / strategies', n_simulations,
+            [self._penalty_kind(penalties, state)], strategies,
             (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
-            drivers, return_orders, allow_single_compound, N.McgpTimePenalty, pack, ('fate', lambda S, n, L: (S, n, 4)))
+            drivers, return_orders, allow_single_compound)
 
     def run_events(
         self,
@@ -750,26 +812,10 @@ class RaceSimulator:
         to run raise ValueError.  Everything else -- the remaining arguments, the plans' checks, the simulation ids and
         draws, the seed rules and the device sharding -- is run_strategies': a scenario without overrides gives exactly
         its counts.  last_histogram: [S, n, n]."""
-        def pack(name, evs, index):
-            if len(evs) > N.MAX_SCENARIO_EVENTS:
-                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_EVENTS} overrides, got {len(evs)}')
-            packed, covered = [], {}
-            for ev in evs:
-                try:
-                    c = ev.c_struct(2 if state is None else int(state.lap) + 1, int(self.config.total_laps))
-                except ValueError as e:
-                    raise ValueError(f'scenario {name!r}: {e}') from None
-                for lap in range(c.first_lap, c.last_lap + 1):
-                    if lap in covered:
-                        raise ValueError(f'scenario {name!r}: lap {lap} has two overrides ({covered[lap]} and {ev})')
-                    covered[lap] = ev
-                packed.append(c)
-            return packed
-
         return self._run_scenarios(
-            'mcgp_run_events', EventResult, 'events / strategies', n_simulations, events, strategies,
-            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
-            drivers, return_orders, allow_single_compound, N.McgpLapEvent, pack, ('events', lambda S, n, L: (S, 3, L + 1)))
+            'mcgp_run_events', EventResult, 'events / strategies', n_simulations, [self._event_kind(events, state)],
+            strategies, (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed,
+            sim_offset, drivers, return_orders, allow_single_compound)
 
     def run_paces(
         self,
@@ -800,39 +846,51 @@ class RaceSimulator:
         the remaining arguments, the plans' checks, the simulation ids and draws, the seed rules and the device
         sharding -- is run_strategies': a scenario without offsets gives exactly its counts.  last_histogram:
         [S, n, n]."""
-        first = _Source(grid_probs, state, None, self.config.total_laps).first_lap(from_grid=1)
-
-        def pack(name, offs, index):
-            if len(offs) > N.MAX_SCENARIO_PACES:
-                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_PACES} offsets, got {len(offs)}')
-            packed, covered, until = [], {}, {}
-            for off in offs:
-                if str(off.driver) not in index:
-                    raise ValueError(f'scenario {name!r}: {off.driver!r} is not one of the drivers')
-                try:
-                    c = off.c_struct(index, first, int(self.config.total_laps))
-                except ValueError as e:
-                    raise ValueError(f'scenario {name!r}: {e}') from None
-                if c.kind == N.PACE_UNTIL_STOP:
-                    if c.driver in until:
-                        raise ValueError(f'scenario {name!r}: {off.driver} has two until-stop offsets '
-                                         f'({until[c.driver]} and {off})')
-                    until[c.driver] = off
-                else:
-                    for lap in range(c.first_lap, c.last_lap + 1):
-                        if (c.driver, lap) in covered:
-                            raise ValueError(f'scenario {name!r}: {off.driver} has two offsets on lap {lap} '
-                                             f'({covered[c.driver, lap]} and {off})')
-                        covered[c.driver, lap] = off
-                packed.append(c)
-            return packed
-
         res = self._run_scenarios(
-            'mcgp_run_paces', PaceResult, 'paces / strategies', n_simulations, paces, strategies,
+            'mcgp_run_paces', PaceResult, 'paces / strategies', n_simulations, [self._pace_kind(paces, grid_probs, state)],
+            strategies, (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed,
+            sim_offset, drivers, return_orders, allow_single_compound)
+        res.until_from = self._until_from(paces)
+        return res
+
+    def run_combined(
+        self,
+        n_simulations: int,
+        scenarios: dict,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        grid_probs: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        return_orders: bool = False,
+        allow_single_compound: bool = False,
+    ) -> 'CombinedResult':
+        """Combined what-if scenarios (include/mcgp.h: mcgp_run_combined, which states how the rule sets meet on one
+        lap): the race under each scenario of `scenarios`, {name: {'plans': [PitPlan, ...], 'penalties': [TimePenalty,
+        ...], 'events': [RaceEvent, ...], 'paces': [PaceOffset, ...]}}, any of the four keys left out or empty (at most 64
+        scenarios, in the order given; the first is the one `compare` measures against).  Each kind keeps the checks
+        and limits of its own call (run_strategies, run_penalties, run_events, run_paces), and a scenario with one kind
+        of item gives exactly that call's counts.  Everything else -- the remaining arguments, the simulation ids and
+        draws, the seed rules and the device sharding -- is run_strategies'.  last_histogram: [S, n, n]."""
+        known = ('plans', 'penalties', 'events', 'paces')
+        for name, sc in scenarios.items():
+            if not isinstance(sc, dict) or set(sc) - set(known):
+                raise ValueError(f'scenario {str(name)!r}: a dict with any of the keys {list(known)}, got '
+                                 + (f'{sorted(set(sc) - set(known))}' if isinstance(sc, dict) else type(sc).__name__))
+        of = lambda key: {str(name): list(sc.get(key) or []) for name, sc in scenarios.items()}
+        paces = of('paces')
+        res = self._run_scenarios(
+            'mcgp_run_combined', CombinedResult, 'scenarios', n_simulations,
+            [self._penalty_kind(of('penalties'), state), self._event_kind(of('events'), state),
+             self._pace_kind(paces, grid_probs, state)], of('plans'),
             (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed, sim_offset,
-            drivers, return_orders, allow_single_compound, N.McgpPaceOffset, pack, ('carried', lambda S, n, L: (S, n, L + 1)))
-        res.until_from = {(str(name), str(off.driver)): int(off.until_stop_from) for name, offs in paces.items()
-                          for off in offs if off.until_stop_from is not None}
+            drivers, return_orders, allow_single_compound)
+        res.until_from = self._until_from(paces)
         return res
 
     def run_gaps(
@@ -2473,3 +2531,10 @@ class PaceResult(StrategyResult):
             raise KeyError(f'{driver!r} has no until-stop offset in scenario {key[0]!r}')
         c = int(lap) - self.until_from[key] + 1
         return float(self.carried_distribution(name, driver)[:max(c + 1, 0)].sum()) if c >= 1 else 0.0
+
+
+# ---------------------------------------------------------------------------------------------- combined scenarios
+@dataclass
+class CombinedResult(PenaltyResult, EventResult, PaceResult):
+    """What RaceSimulator.run_combined returns: StrategyResult's counts and helpers with PenaltyResult's `fate`,
+    EventResult's `events` and PaceResult's `carried` and `until_from`, and the helpers of all three."""

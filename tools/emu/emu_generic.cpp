@@ -5,7 +5,7 @@
 // race_trace_kernel, race_strategy_kernel<false / true>, race_gaps_kernel<false / true>, race_conditions_kernel<false /
 // true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false / true>, race_fastest_kernel,
 // race_penalties_kernel<false / true>, penalties_count; and events.hip.h: race_events_kernel<false / true>, events_count;
-// and paces.hip.h: race_paces_kernel<false / true>, paces_count.
+// and paces.hip.h: race_paces_kernel<false / true>, paces_count; and combined.hip.h: race_combined_kernel<false / true>.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -22,7 +22,7 @@
 // and paces_count.
 // tests/test_events_host_build.py, tests/test_generic_host_build.py, tests/test_gaps_host_build.py, tests/test_conditions_host_build.py,
 // tests/test_stints_host_build.py, tests/test_moves_host_build.py, tests/test_fastest_host_build.py,
-// tests/test_penalties_host_build.py, tests/test_paces_host_build.py.
+// tests/test_penalties_host_build.py, tests/test_paces_host_build.py, tests/test_combined_host_build.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -40,6 +40,7 @@
 #include "../../monte_carlo_gp_amd/csrc/penalty_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/event_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/pace_pack.h"
+#include "../../monte_carlo_gp_amd/csrc/combined.hip.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
 namespace mcgp {
@@ -475,6 +476,89 @@ int emu_paces_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double 
                     mcgp::paces_count(stage, car_stage, pscen.data(), n_sims, n, (uint32_t)L, delta, carried);
                 }
     }
+    one_thread_block(1);
+    return MCGP_OK;
+}
+
+// race_combined_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every
+// scenario, plans, penalties, overrides and offsets packed by plan_pack.h, penalty_pack.h, event_pack.h and pace_pack.h
+// (a NULL count array: none in any scenario).  hist [S][n][n] is accumulated into; stage [S][n_sims][n] (position |
+// fate << 5) is written, and ev_stage [S][n_sims] and car_stage [S][n_sims][n] u16 where given (NULL: not staged).  delta
+// [S][n][2n - 1], fate [S][n][4], events_cnt [S][3][L + 1] (needs ev_stage) and carried [S][n][L + 1] (needs car_stage),
+// each of which may be NULL, are accumulated into as the C ABI does it: delta and fate by penalties_count, events_cnt by
+// events_count and carried by paces_count, both with delta NULL, as grid_x (x S (x 1 + n)) blocks of one thread.
+int emu_combined_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                     uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                     const uint32_t *penalty_count, const mcgp_time_penalty *penalties, const uint32_t *event_count,
+                     const mcgp_lap_event *events, const uint32_t *pace_count, const mcgp_pace_offset *paces, uint64_t n_sims,
+                     uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *stage, uint32_t *ev_stage,
+                     uint16_t *car_stage, unsigned long long *delta, unsigned long long *fate, unsigned long long *events_cnt,
+                     unsigned long long *carried, uint32_t grid_x, const char **err)
+{
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
+        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    if (events_cnt && !ev_stage) return fail(MCGP_E_BAD_ARG, "events_cnt needs ev_stage", err);
+    if (carried && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
+    static const uint32_t none[mcgp::kMaxStrategyScenarios] = {};
+    if (!penalty_count) penalty_count = none;
+    if (!event_count) event_count = none;
+    if (!pace_count) pace_count = none;
+    const int L = cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+        st.sim_offset = sim_offset;
+    }
+    const int first_lap = state ? st.lap + 1 : 2;
+    const bool resumed = state != nullptr;
+    std::vector<mcgp::StrategyScenario> scen;
+    std::vector<mcgp::StopLap> stop_laps;
+    std::vector<mcgp::PenaltyScenario> pens;
+    std::vector<mcgp::PenaltyLap> pen_laps;
+    std::vector<uint8_t> event_laps;
+    std::vector<mcgp::PaceScenario> pscen;
+    std::vector<mcgp::PaceLap> pace_laps;
+    std::vector<double> lap_sec;
+    uint64_t n_pens = 0, n_events = 0, n_paces = 0;
+    std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, resumed, &scen, &stop_laps);
+    if (e.empty()) e = mcgp::check_penalty_counts(n_scenarios, penalty_count, &n_pens);
+    if (e.empty()) e = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
+    if (e.empty()) e = mcgp::check_pace_counts(n_scenarios, pace_count, &n_paces);
+    if (e.empty() && n_pens && !penalties) e = "penalties is NULL";
+    if (e.empty() && n_events && !events) e = "events is NULL";
+    if (e.empty() && n_paces && !paces) e = "paces is NULL";
+    if (e.empty()) e = mcgp::pack_penalties(n_scenarios, penalty_count, penalties, n, L, first_lap, resumed, &pens, &pen_laps);
+    if (e.empty()) e = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, resumed, &event_laps);
+    if (e.empty())      // lap 1 reads the base pace too: from the grid an offset may name it
+        e = mcgp::pack_paces(n_scenarios, pace_count, paces, n, L, state ? first_lap : 1, resumed, &pscen, &pace_laps, &lap_sec);
+    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    one_thread_block(n_scenarios);
+    const auto kernel = state ? &mcgp::race_combined_kernel<true> : &mcgp::race_combined_kernel<false>;
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        blockIdx.y = si;
+        kernel(&kp, &st, scen.data(), stop_laps.data(), pens.data(), pen_laps.data(), event_laps.data(), pscen.data(),
+               pace_laps.data(), lap_sec.data(), n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
+               ev_stage, car_stage, (uint32_t)n_sims);
+    }
+    const uint32_t gz = carried ? 1u + n : 1u;
+    for (uint32_t z = 0; z < gz; ++z)
+        for (uint32_t y = 0; y < n_scenarios; ++y)
+            for (uint32_t x = 0; x < grid_x; ++x) {
+                blockIdx = {x, y, z};
+                if (z == 0) {
+                    gridDim = {grid_x, n_scenarios, 1};
+                    if (delta || fate) mcgp::penalties_count(stage, n_sims, n, delta, fate);
+                    if (events_cnt) mcgp::events_count(stage, ev_stage, n_sims, n, (uint32_t)L, nullptr, events_cnt);
+                }
+                gridDim = {grid_x, n_scenarios, gz};
+                if (carried) mcgp::paces_count(stage, car_stage, pscen.data(), n_sims, n, (uint32_t)L, nullptr, carried);
+            }
     one_thread_block(1);
     return MCGP_OK;
 }
