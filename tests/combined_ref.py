@@ -47,6 +47,7 @@ class _Race(PR._Race):
         self.served = set()
         forced = ER.by_lap(overrides)
         self.seen = [0, 0, 0]                               # red flags, safety cars, VSCs
+        self.most_added = 0                                 # the most ON_LAP additions that reached a car on one lap
         for lap in range(first_lap, M.L + 1):
             remaining = M.L - lap
             e = self.draw(lap, PURPOSE_EVENT)
@@ -85,7 +86,7 @@ class _Race(PR._Race):
             if not fuel > 0:
                 fuel = 0.0
             fuel_effect = (110.0 - fuel) * 0.03
-            carry = 0.0
+            carry, added = 0.0, 0
             for i, d in enumerate(list(self.ord)):
                 if self.dnf[d]:
                     continue
@@ -129,10 +130,12 @@ class _Race(PR._Race):
                         self.served.add(d)
                     if d in self.active and lap >= self.until[d][0]:        # the stop clears the offset; t untouched
                         self.active.discard(d)
-                        self.carried[d] = lap - self.until[d][0] + 1
+                        self.carried[d], self.fate[d] = lap - self.until[d][0] + 1, PR.FATE_STOP
                 if (d, lap) in on_lap:
                     t = t + on_lap[d, lap]
+                    added += 1
                 self.cum[d], self.last[d], self.comp[d], self.age[d] = t, lap_time, comp, age
+            self.most_added = max(self.most_added, added)
             for pas in range(3):
                 self.sort()
                 o = self.ord
@@ -172,18 +175,22 @@ class _Race(PR._Race):
         for d in self.active:
             p = self.until[d][0]
             self.carried[d] = max(self.dnf[d] - p, 0) if self.dnf[d] else M.L - p + 1
+            self.fate[d] = PR.FATE_RETIRED if self.dnf[d] else PR.FATE_FLAG
 
 
-def orders(case, m, seed, sim_offset=0, plans=None, penalties=(), overrides=(), offsets=(), state=None, grids=None):
+def orders(case, m, seed, sim_offset=0, plans=None, penalties=(), overrides=(), offsets=(), state=None, grids=None,
+           want_ends=False):
     """(finishing orders [m][n], fates [m][n], event laps [m][3], laps carried [m][n]) of simulations sim_offset ..
     sim_offset + m - 1 under one scenario, from the grid (the oracle's sampled grids, or `grids`) or from state =
-    (mcgp_race_state arrays, lap, drs_disabled_until)."""
+    (mcgp_race_state arrays, lap, drs_disabled_until).  want_ends: also how each driver's UNTIL_STOP offset ended
+    (paces_ref.FATE_* [m][n]) and the most ON_LAP additions that reached a running car on one lap [m]."""
     M = SR.Model(case)
     plans = plans or {}
     if state is None and grids is None:
         grids = RR.traced_run(case, m, seed, sim_offset)['grids']
     out, fates = np.zeros((m, M.n), np.uint8), np.zeros((m, M.n), np.uint8)
     seen, carried = np.zeros((m, 3), np.int64), np.zeros((m, M.n), np.int64)
+    ends, most = np.zeros((m, M.n), np.int64), np.zeros(m, np.int64)
     for i in range(m):
         r = _Race(M, seed, sim_offset + i)
         r.set_offsets(offsets)
@@ -192,8 +199,9 @@ def orders(case, m, seed, sim_offset=0, plans=None, penalties=(), overrides=(), 
         fates[i] = r.at_the_flag()
         out[i], seen[i] = r.classify(), r.seen
         for d, c in r.carried.items():
-            carried[i, d] = c
-    return out, fates, seen, carried
+            carried[i, d], ends[i, d] = c, r.fate[d]
+        most[i] = r.most_added
+    return (out, fates, seen, carried, ends, most) if want_ends else (out, fates, seen, carried)
 
 
 def scenario(plans=None, penalties=(), events=(), paces=()):
@@ -201,13 +209,14 @@ def scenario(plans=None, penalties=(), events=(), paces=()):
     return {'plans': plans or {}, 'penalties': list(penalties), 'events': list(events), 'paces': list(paces)}
 
 
-def ref_run(case, scen, m, seed, sim_offset=0, state=None, grids=None):
-    """orders [S][m][n], fates [S][m][n], event laps [S][m][3], laps carried [S][m][n] of the scenarios `scen`."""
+def ref_run(case, scen, m, seed, sim_offset=0, state=None, grids=None, want_ends=False):
+    """orders [S][m][n], fates [S][m][n], event laps [S][m][3], laps carried [S][m][n] of the scenarios `scen`; with
+    want_ends also orders()' two more, [S][m][n] and [S][m]."""
     if state is None and grids is None:
         grids = RR.traced_run(case, m, seed, sim_offset)['grids']
-    rows = [orders(case, m, seed, sim_offset, sc['plans'], sc['penalties'], sc['events'], sc['paces'], state, grids)
-            for sc in scen]
-    return tuple(np.stack([r[k] for r in rows]) for k in range(4))
+    rows = [orders(case, m, seed, sim_offset, sc['plans'], sc['penalties'], sc['events'], sc['paces'], state, grids,
+                   want_ends) for sc in scen]
+    return tuple(np.stack([r[k] for r in rows]) for k in range(6 if want_ends else 4))
 
 
 # ---------------------------------------------------------------- the C-ABI call for the tests

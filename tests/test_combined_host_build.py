@@ -5,13 +5,18 @@
      from the grid and from a state, on S60, EVT and a 32-car field;
   2. the emulated single-kind kernels: with at most one table non-empty the combined kernel must stage what
      race_strategy_kernel, race_penalties_kernel, race_events_kernel and race_paces_kernel stage, simulation for
-     simulation, and count what they count.
+     simulation, and count what they count;
+  3. the restatement again, under the generated scenarios of combined_cases on every input of generic_cases.py, from the
+     grid and from a state (the sweeps of tests/test_gpu_combined_fuzz.py that need no device).
 
 The three stagings stay inside their chunks (guard fill on both sides, checked by combined_host_build on every call), and
 the counting kernels' bins are the counts of the staged data whatever their grid."""
+import functools
+
 import numpy as np
 import pytest
 
+import combined_cases as CC
 import combined_host_build as CH
 import combined_ref as CR
 import events_host_build as EH
@@ -55,6 +60,11 @@ def _start(name, start):
 def _leader(name):
     """The driver who wins most of the oracle's simulations of the case."""
     return int(np.bincount(_ref(name)['orders'][:, 0]).argmax())
+
+
+@functools.lru_cache(maxsize=None)
+def _fuzz_inputs():
+    return CC.fuzz_inputs()
 
 
 # ---------------------------------------------------------------- 1. the restatement
@@ -161,3 +171,18 @@ def test_counting_kernels_do_not_depend_on_their_grid(grid_x):
     r2 = CH.combined_raw(case, scen, m, SEED, 11, count=False)
     assert np.array_equal(r2['stage'], r['stage']) and np.array_equal(r2['evs'], r['evs']) and np.array_equal(r2['car'], r['car'])
     assert not (r2['delta'].any() or r2['fate'].any() or r2['events'].any() or r2['carried'].any())
+
+
+# ---------------------------------------------------------------- 3. every input under generated scenarios
+@pytest.mark.parametrize('start', ['grid', 'state'])
+def test_emulated_kernel_on_every_input(start):
+    """The comparisons of tests/test_gpu_combined_fuzz.py parts a and b that need no device: combined_cases' scenarios on
+    the 100 inputs of generic_cases.run_inputs() from the grid and on the 94 of resume_inputs() from the oracle's state of
+    simulation 3 after max(1, L // 2), 8 simulations each.  The generator's conditions are asserted in the sweep."""
+    def compare(case, seed, scen, want, m, offset, state):
+        got = CH.combined(case, scen, m, seed, offset, state=state)
+        CH.check_against(got, case, want, m)
+        assert np.array_equal(got['fates'], want[1]) and np.array_equal(got['seen'], want[2])
+        assert np.array_equal(got['laps'], want[3])
+
+    CC.fuzz_sweep(*_fuzz_inputs(), compare, from_state=start == 'state')

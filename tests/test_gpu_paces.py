@@ -1,8 +1,13 @@
 """Pace scenarios on the device (mcgp_run_paces, through the C ABI) against two independent references -- the pinned C
 oracle under another base_pace (whole-race LAPS offsets from the grid and from states, an UNTIL_STOP offset no stop
 clears) and the Python restatement (paces_ref) under mixed scenarios, at the limits and under the generated offset sets of
-paces_cases on every input -- and against itself: the outputs are accumulated into, a split by sim_offset sums to the one
-call, and hist, delta and carried are the counts of the returned orders."""
+paces_cases on every input, from the grid and from states -- and against itself: the outputs are accumulated into, a split
+by sim_offset sums to the one call, several staging chunks equal one, and hist, delta and carried are the counts of the
+returned orders at simulation counts that leave a wave and a counting block ragged.  Wall time on an MI355X machine, in
+one visit: this file 12.7 s (the two sweeps 4.0 s and 1.9 s) against 28.2 s for tests/test_gpu_stints_moves_fuzz.py, the
+family's yardstick."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -164,12 +169,77 @@ def test_a_race_of_one_lap(require_gpu):
 
 
 # ---------------------------------------------------------------- 4. every input under generated offset sets
+@functools.lru_cache(maxsize=None)
+def _fuzz_inputs():
+    return PC.fuzz_inputs()
+
+
 def test_device_on_every_input_from_the_grid(require_gpu):
     def compare(case, seed, scen, want_o, want_c):
         got = _run(case, scen, PC.FUZZ_SIMS, seed, PC.FUZZ_OFFSET)
         PC.check_against(got, case, want_o, want_c, PC.FUZZ_SIMS)
 
-    PC.fuzz_sweep(*PC.fuzz_inputs(), compare)
+    PC.fuzz_sweep(*_fuzz_inputs(), compare)
+
+
+def test_device_on_every_input_from_a_state(require_gpu):
+    """The gains of buffers of fives are the restatement's counts."""
+    def compare(case, seed, scen, want_o, want_c, state):
+        got = _run(case, scen, PC.FUZZ_SIMS, seed, 0, state=state, fill=5)
+        got = {k: v - 5 if k != 'orders' else v for k, v in got.items()}
+        PC.check_against(got, case, want_o, want_c, PC.FUZZ_SIMS)
+        assert (got['carried'].sum(axis=2) == PC.FUZZ_SIMS).all()
+
+    PC.state_sweep(*_fuzz_inputs(), compare)
+
+
+def test_chunks_from_a_state(require_gpu, monkeypatch):
+    """200 simulations under a cap of 64 per launch are four staging chunks with a short last one, with and without the
+    staging of the laps carried."""
+    case = _case('S60')
+    L, n = case['config']['total_laps'], len(case['grid_probs'])
+    k, m = L // 2, 200
+    state = (RR.state_arrays(_ref('S60'), 3, k), k, RR.drs_disabled_until(case, SEED, OFF + 3, k))
+    scen = PR.scenarios(k + 1, L, n)
+    whole = _run(case, scen, m, SEED, OFF, state=state)
+    monkeypatch.setenv('MCGP_MAX_SIMS_PER_LAUNCH', '64')
+    chunked = _run(case, scen, m, SEED, OFF, state=state)
+    bare = _run(case, scen, m, SEED, OFF, state=state, carried=False, orders=False)
+    monkeypatch.delenv('MCGP_MAX_SIMS_PER_LAUNCH')
+    for key in ('hist', 'delta', 'carried', 'orders'):
+        assert np.array_equal(chunked[key], whole[key]), key
+    assert np.array_equal(bare['hist'], whole['hist']) and np.array_equal(bare['delta'], whole['delta'])
+    assert not bare['carried'].any() and bare['orders'] is None
+    o = whole['orders']
+    assert np.array_equal(whole['hist'], PR.hist_counts(o, n)) and np.array_equal(whole['delta'], SR.delta_counts(o, n))
+    assert (whole['carried'].sum(axis=2) == m).all() and (whole['carried'][1:, :, 1:] > 0).any() and (o[1:] != o[0]).any()
+
+
+@pytest.mark.parametrize('n', [31, 3])
+def test_ragged_counts(require_gpu, n):
+    """Simulation counts one short of, one past and far from a wave, two waves and a counting block: the restatement up to
+    65 simulations, beyond that the counts of the returned orders and the sum of split calls."""
+    name, seed, off = f'n{n}', 5, PC.FUZZ_OFFSET
+    case = _case(name)
+    L = case['config']['total_laps']
+    scen = PC.scenarios(name, case) + PR.scenarios(1, L, n)[3:6]
+    grids = RR.traced_run(case, 65, seed, off)['grids']
+    want = [PR.orders(case, 65, seed, off, plans=pl, offsets=offs, grids=grids) for offs, pl in scen]       # once, cut to m
+    want_o, want_c = np.stack([w[0] for w in want]), np.stack([w[1] for w in want])
+    for m in (1, 63, 65, 129, 257):
+        got = _run(case, scen, m, seed, off)
+        assert np.array_equal(got['hist'], PR.hist_counts(got['orders'], n)), (n, m)
+        assert np.array_equal(got['delta'], SR.delta_counts(got['orders'], n)), (n, m)
+        assert (got['carried'].sum(axis=2) == m).all(), (n, m)
+        if m <= 65:
+            PC.check_against(got, case, want_o[:, :m], want_c[:, :m], m)
+        else:
+            a = m // 2 + 1
+            lo, hi = _run(case, scen, a, seed, off), _run(case, scen, m - a, seed, off + a)
+            for key in ('hist', 'delta', 'carried'):
+                assert np.array_equal(got[key], lo[key] + hi[key]), (n, m, key)
+            assert np.array_equal(got['orders'], np.concatenate([lo['orders'], hi['orders']], axis=1))
+            assert (got['carried'][1:, :, 1:] > 0).any()
 
 
 # ---------------------------------------------------------------- 5. accumulation, split, counts of the orders

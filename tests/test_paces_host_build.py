@@ -11,7 +11,9 @@ the chunk (guard bytes on both sides, checked by paces_host_build on every call)
 counts of the staged data whatever its grid.
 
 Last, the comparison of tests/test_gpu_paces.py that needs no device: the generated offset sets (paces_cases) from the
-grid on the 100 inputs of generic_cases.run_inputs() at 8 simulations."""
+grid on the 100 inputs of generic_cases.run_inputs() and from states on the 94 of resume_inputs(), at 8 simulations."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -265,10 +267,24 @@ def test_counting_kernel_does_not_depend_on_its_grid(grid_x):
 
 
 # ---------------------------------------------------------------- every input under generated offset sets
+@functools.lru_cache(maxsize=None)
+def _fuzz_inputs():
+    return PC.fuzz_inputs()
+
+
 def test_emulated_kernel_on_every_input_from_the_grid():
     def compare(case, seed, scen, want_o, want_c):
         got = PH.paces(case, [pl for _, pl in scen], [offs for offs, _ in scen], PC.FUZZ_SIMS, seed, PC.FUZZ_OFFSET)
         PC.check_against(got, case, want_o, want_c, PC.FUZZ_SIMS)
         assert np.array_equal(got['laps'], want_c)
 
-    PC.fuzz_sweep(*PC.fuzz_inputs(), compare)
+    PC.fuzz_sweep(*_fuzz_inputs(), compare)
+
+
+def test_emulated_kernel_on_every_input_from_a_state():
+    def compare(case, seed, scen, want_o, want_c, state):
+        got = PH.paces(case, [pl for _, pl in scen], [offs for offs, _ in scen], PC.FUZZ_SIMS, seed, 0, state=state)
+        PC.check_against(got, case, want_o, want_c, PC.FUZZ_SIMS)
+        assert np.array_equal(got['laps'], want_c)
+
+    PC.state_sweep(*_fuzz_inputs(), compare)
