@@ -800,6 +800,16 @@ __device__ __forceinline__ void lds_ld_f64_u32x2(uint32_t addr, double &d, uint3
     u1 = v.w;
 }
 
+// Two doubles 16 bytes apart at BASE + addr: one ds_read2_b64, offsets BASE / 8 and BASE / 8 + 2 (8-bit fields in units of
+// 8 bytes; the compiler pairs two loads off one address register whose offsets fit them)
+template <uint32_t BASE>
+__device__ __forceinline__ void lds_ld2_f64(uint32_t addr, double &a, double &b)
+{
+    static_assert(BASE % 8 == 0 && BASE / 8 + 2 <= 255, "ds_read2_b64 offsets");
+    a = lds_ld<double>(BASE + addr);
+    b = lds_ld<double>(BASE + 16u + addr);
+}
+
 // binary64 -> uint32 the way the hardware converts: toward zero, saturating at 0 and 2^32 - 1, NaN -> 0.
 // (A C++ cast is undefined outside the range; the draw-word thresholds of the overtake step rely on the clamp.)
 __device__ __forceinline__ uint32_t cvt_u32_f64_sat(double x)

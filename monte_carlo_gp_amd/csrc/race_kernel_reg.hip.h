@@ -71,26 +71,25 @@
 
 namespace mcgp {
 
-// pk word of the register kernel.  Field positions are chosen so that LDS addresses fall out of ONE mask wherever a
-// table is indexed three times a lap (the overtake passes) and of a shift + mask elsewhere:  pk & 0x1F0 = 16 driver;
-// pk & 0x3F0 = 16 (32 dnf + driver);  pk & 8 = 8 drs;  (pk & 0x1C00) >> 1 = 512 compound;  (pk >> 6) & 0x70 = 16 compound;
-// and (pk & k3AgeMask) + (1 << 16) = (tyre age + 1) << 16, which compares directly with the pit-stop word.
+// pk word of the register kernel.  Field positions are chosen so that an LDS address falls out of ONE mask of the word
+// wherever a table is gathered by it.  Fixed for every field size:
+//     [0..2] dry compounds used   [3] drs   [4..8] driver   [16..26] tyre age   [27..31] grid slot
+// and, per geometry (RegTables below; kPk*/kDnf/... of RegGeo), the re-laid form
+//     [9..11] compound, directly above the driver:  pk & 0xFF0 = 16 (32 compound + driver), the oIc entry;
+//                                                    pk & 0xE08 = 512 compound + 8 drs, the {delta, drs gain} pair rows
+//     [12] or [13] dnf:  pk & (0x1F0 | dnf) = 16 driver (+ 4096 or 8192 for a retired car: the NaN copy of the overtake pace)
+//     [13] or [12] dirty air
+// or, where the block-shared tables do not pack around that distance (reg_tables), the earlier form
+//     [9] dnf (NaN copy 32 entries on)   [10..12] compound ((pk & 0x1C00) >> 1 = 512 compound)   [13] dirty air.
+// (pk & k3AgeMask) + (1 << 16) = (tyre age + 1) << 16 compares directly with the pit-stop word.
 constexpr uint32_t k3UsedMask = 7u;            // [0..2] dry compounds used so far (SOFT, MEDIUM, HARD)
-constexpr uint32_t k3Drs = 1u << 3;            // (pk & 8) = 8 drs: byte offset into the {0.0, drs_delta} table
+constexpr uint32_t k3Drs = 1u << 3;            // (pk & 8) = 8 drs: byte offset into a {0.0, drs_delta} table
 constexpr int k3IdShift = 4;                   // [4..8] driver index: (pk & k3IdMask) = 16 driver
 constexpr uint32_t k3IdMask = 31u << k3IdShift;
-constexpr uint32_t k3Dnf = 1u << 9;            // directly above the driver index: pk & k3SlotMask = 16 (32 dnf + driver)
-constexpr uint32_t k3SlotMask = k3IdMask | k3Dnf;
-constexpr int k3CompShift = 10;                // [10..12] tyre compound
-constexpr uint32_t k3CompMask = 7u << k3CompShift;
-constexpr uint32_t k3Dirty = 1u << 13;         // 0 < time_behind_leader < dirty_air_threshold   ([14..15] unused)
-constexpr int k3AgeShift = 16;                 // [16..26] tyre age; lap of retirement once dnf is set
+constexpr int k3AgeShift = 16;                 // [16..26] tyre age; lap of retirement once dnf is set   ([14..15] unused)
 constexpr uint32_t k3AgeMask = 0x7FFu << k3AgeShift;
 constexpr int k3GposShift = 27;                // [27..31] grid slot (most significant: tie-break)
 __host__ __device__ constexpr uint32_t pk_driver16(uint32_t p) { return p & k3IdMask; }                  // 16 x driver
-__host__ __device__ constexpr uint32_t pk_slot16(uint32_t p) { return p & k3SlotMask; }                  // 16 x (32 dnf + driver)
-__host__ __device__ constexpr uint32_t pk_comp512(uint32_t p) { return (p & k3CompMask) >> (k3CompShift - 9); }   // 512 x compound
-__host__ __device__ constexpr uint32_t pk_comp16(uint32_t p) { return (p >> (k3CompShift - 4)) & 0x70u; }        // 16 x compound
 constexpr double kAgeFieldUnit = 1.0 / 65536.0;   // tables that multiply (pk & k3AgeMask) carry this factor
 
 // ---- launch geometry and LDS map, fixed per field size ----
@@ -102,10 +101,11 @@ __host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) / 16 * 
 constexpr int kWordRows = 8;
 __host__ __device__ constexpr size_t per_thread_lds_bytes_reg(int n) { return (size_t)kWordRows * 4 + (size_t)n * 8; }
 // block-shared tables: inverse-normal rows; per-driver {var, base}; {base, deg} x 2^31 with a second copy of
-// NaNs 32 entries further on, which the pk word of a RETIRED car indexes: its pace is NaN, so both pairs it
-// belongs to fail every overtake test without a flag test; per-(compound, driver) {eff f64, pit word u32, DNF
-// threshold u32} (compound stride 32 entries); per-compound {delta, pad}; {0.0, drs_delta} and the same x 2^31;
-// n x n histogram (u32); transposed grid matrix (f64).  The driver index varies fastest in every table (16-byte
+// NaNs further on (32 entries, or 4096 / 8192 bytes: RegTables below), which the pk word of a RETIRED car indexes:
+// its pace is NaN, so both pairs it belongs to fail every overtake test without a flag test; per-(compound, driver)
+// {eff f64, pit word u32, DNF threshold u32} (compound stride 32 entries); per-compound {delta, pad}; {0.0, drs_delta}
+// and the same x 2^31; n x n histogram (u32); transposed grid matrix (f64).  The byte count below is that of the
+// earlier map, tables end to end; the re-laid map (RegTables) fits the same bytes, and the launch asks for them as before.  The driver index varies fastest in every table (16-byte
 // entries): lanes holding different drivers hit different banks, the same driver broadcasts.  Tables end at the
 // last driver (not at 32): the LDS saved is what lets the N = 20 block hold three waves per SIMD.
 constexpr int kNumCompounds = 5;
@@ -114,6 +114,119 @@ __host__ __device__ constexpr size_t shared_lds_bytes_reg(int n)
     return (size_t)kNormalRows * 16 + (size_t)n * 16 + (size_t)(kMaxCars + n) * 16 +
            (size_t)((kNumCompounds - 1) * kMaxCars + n) * 16 + kCompStride * 16 + 64 + 128 + align16((size_t)n * n * 4) +
            align16((size_t)n * n * 8);      // (16-byte multiple: the per-lane planes that follow are accessed 16 bytes at a time)
+}
+// Where the block-shared tables lie inside those bytes, and the pk bits that follow from it (per field size and deviate
+// width; the block shape does not enter).  The re-laid map puts the NaN copy of the overtake pace 4096 or 8192 bytes after
+// the live table -- the dnf bit of pk is then bit 12 or 13, and the compound sits directly above the driver index -- with
+// WHOLE tables filling the span between the two:
+//     default width     [oIc] [pace] [ span: tables chosen to fill it ] [NaN copy] [the other tables] .. pad .. end
+//     or                [pace] [oIc] [ span ............................] [NaN copy] [the other tables] .. pad .. end
+// and, at up to 30 cars, keeps the per-compound pace delta and the DRS gain in the entries of oIc that no driver uses: for
+// compound c at oIc + 512 c + 16 n the four doubles {delta_c, delta_c, 0.0, drs_delta}, which ONE ds_read2_b64 at
+// pk & (compound | drs) with offsets 0 and 2 reads as (delta_c, 0.0 or drs_delta); the last compound's row ends 32 bytes
+// past the table.  The base of those rows must fit the instruction's 8-bit offsets (units of 8 bytes): oIc + 16 n <= 2024,
+// hence oIc first or right behind the pace table.  31 and 32 cars have no such padding and keep a separate delta table.
+// The packing is searched here, at compile time: every subset of the other tables for the span, both distances, both
+// heads; the one with the least waste is taken if the map still ends within shared_lds_bytes_reg(n) -- the launch's LDS size
+// and with it every block shape stay what they were.  Where none does (1 to 3 and 31 cars at default width: the span
+// cannot be filled within the bytes at hand), or for a size on reg_pk_earlier_layout's list, the earlier map and pk word stay.
+struct RegTables {
+    bool relaid;                // compound at [9..11], dnf at bit 12 / 13 (else: dnf [9], compound [10..12])
+    bool pair;                  // {delta, drs gain} rows in oIc's padding (else: the oComp table and the oDrs row)
+    int comp_shift;
+    uint32_t dnf, dirty;
+    uint32_t oDrvA, oDrvB, oIc, oComp, oDrs, oLut, oNorm, oHist, oGrid, end;
+};
+// Field sizes that keep the earlier layout although the re-laid one packs: the ones where it costs an instantiation
+// registers or scratch (tools/resources.sh; earlier -> re-laid), listed per kernel -- the batch kernel and the reference
+// width have maps of their own, the default and the 4-wave blocks share one.  Default / 4-wave blocks: N = 6 112 -> 116 B of
+// scratch per lane, N = 9 4-wave blocks 127 -> 128 VGPRs, N = 21 0 -> 12 B.  Batch: N = 5 116 -> 168 B, N = 6 188 -> 204,
+// N = 13 24 -> 28, N = 16 68 -> 72, N = 20 84 -> 88, N = 21 88 -> 92, N = 22 92 -> 100.  Reference width: N = 9 / 10 157 -> 158 /
+// 163 -> 164 VGPRs, N = 21 176 -> 192 B.  A cut by resources alone, as the lists above.  Everywhere else every instantiation
+// keeps or lowers both (N = 20: 168 VGPRs and 0 B, 4-wave blocks 8 B, reference width 176 B, as before; N = 5 92 -> 28 B,
+// N = 27 reference width 116 -> 92); occupancy changes nowhere.
+enum RegKind { kRegDefault = 0, kRegBatch = 1, kRegWide = 2 };     // the default and the 4-wave blocks; the batch kernel; reference width
+__host__ __device__ constexpr bool reg_pk_earlier_layout(int n, int kind)
+{
+    return kind == kRegBatch  ? n == 5 || n == 6 || n == 13 || n == 16 || (n >= 20 && n <= 22)
+           : kind == kRegWide ? n == 9 || n == 10 || n == 21
+                              : n == 6 || n == 9 || n == 21;
+}
+__host__ __device__ constexpr RegTables reg_tables(int n, int kind)
+{
+    const bool wide = kind == kRegWide;
+    const uint32_t un = (uint32_t)n;
+    const uint32_t total = (uint32_t)shared_lds_bytes_reg(n) - (wide ? (uint32_t)kNormalRows * 16u : 0u);
+    const uint32_t sz_norm = wide ? 0u : (uint32_t)kNormalRows * 16u, sz_hist = (uint32_t)align16((size_t)n * n * 4),
+                   sz_grid = (uint32_t)align16((size_t)n * n * 8);
+    RegTables t{};
+    t.relaid = false;
+    t.pair = false;
+    t.comp_shift = 10;
+    t.dnf = 1u << 9;
+    t.dirty = 1u << 13;
+    t.oDrvA = 0;
+    t.oDrvB = t.oDrvA + un * 16u;
+    t.oIc = t.oDrvB + ((uint32_t)kMaxCars + un) * 16u;
+    t.oComp = t.oIc + ((uint32_t)(kNumCompounds - 1) * kMaxCars + un) * 16u;
+    t.oDrs = t.oComp + (uint32_t)kCompStride * 16u;
+    t.oLut = t.oDrs + 64u;
+    t.oNorm = t.oLut + 128u;
+    t.oHist = t.oNorm + sz_norm;
+    t.oGrid = t.oHist + sz_hist;
+    t.end = t.oGrid + sz_grid;
+    if (reg_pk_earlier_layout(n, kind)) return t;
+
+    const bool pair = n <= 30;
+    const uint32_t sz_ic = ((uint32_t)(kNumCompounds - 1) * kMaxCars + un) * 16u + (pair ? 32u : 0u), sz_pace = un * 16u;
+    // the tables free to go into the span or behind the NaN copy: normal rows, {var, base}, the DRS / pit rows, the pit
+    // rule, the delta table (without pair rows), histogram, grid matrix
+    constexpr int kItems = 7;
+    const uint32_t sz[kItems] = {sz_norm, un * 16u, 64u, 128u, pair ? 0u : (uint32_t)kCompStride * 16u, sz_hist, sz_grid};
+    uint32_t sum_all = 0;
+    for (int k = 0; k < kItems; ++k) sum_all += sz[k];
+    uint32_t best_waste = ~0u, best_set = 0, best_dist = 0;
+    bool best_ic_first = true;
+    for (uint32_t dist = 8192u; dist >= 4096u; dist >>= 1)
+        for (int head = 0; head < 2; ++head) {
+            const bool ic_first = head == 0;
+            const uint32_t fixed = sz_pace + (ic_first ? 0u : sz_ic);           // of the span, already taken
+            if (fixed > dist) continue;
+            for (uint32_t set = 0; set < (1u << kItems); ++set) {
+                uint32_t in = 0;
+                for (int k = 0; k < kItems; ++k) in += (set >> k) & 1u ? sz[k] : 0u;
+                if (fixed + in > dist) continue;
+                const uint32_t waste = dist - fixed - in;
+                // [oIc] pace span NaN rest  /  pace [oIc ..span] NaN rest
+                const uint32_t end = (ic_first ? sz_ic : 0u) + dist + sz_pace + (sum_all - in);
+                if (end <= total && waste < best_waste) { best_waste = waste; best_set = set; best_dist = dist; best_ic_first = ic_first; }
+            }
+        }
+    if (best_dist == 0) return t;                                                // nothing packs: the earlier map
+
+    t.relaid = true;
+    t.pair = pair;
+    t.comp_shift = 9;
+    t.dnf = best_dist;                                                           // pk & dnf = the byte distance itself
+    t.dirty = best_dist == 8192u ? 4096u : 8192u;
+    t.oIc = best_ic_first ? 0u : sz_pace;
+    t.oDrvB = best_ic_first ? sz_ic : 0u;
+    uint32_t in_span = sz_ic + sz_pace, behind = t.oDrvB + best_dist + sz_pace;
+    uint32_t at[kItems] = {};
+    for (int k = 0; k < kItems; ++k) {
+        uint32_t &cursor = (best_set >> k) & 1u ? in_span : behind;
+        at[k] = cursor;
+        cursor += sz[k];
+    }
+    t.oNorm = at[0];
+    t.oDrvA = at[1];
+    t.oDrs = at[2];
+    t.oLut = at[3];
+    t.oComp = at[4];
+    t.oHist = at[5];
+    t.oGrid = at[6];
+    t.end = behind;
+    return t;
 }
 // Waves per SIMD the kernel is compiled for (__launch_bounds__: register budget 512 / this), chosen by measurement
 // for every field size (one box, 4x10^6 simulations, profiles/r3_sweep_waves.txt): e.g. N = 10
@@ -226,26 +339,42 @@ __host__ __device__ constexpr size_t wide_launch_lds_bytes(int n, int waves, int
     const size_t base = wide_lds_bytes(n, waves), chain = wide_chain_bytes(n, total_laps);
     return base + chain + kLdsReserve <= kLdsPerCu ? base + chain : base;
 }
-template <int N, int WAVES = reg_block_waves(N), bool WIDE = false>
+template <int N, int WAVES = reg_block_waves(N), bool WIDE = false, int KIND = WIDE ? kRegWide : kRegDefault>
 struct RegGeo {
     static constexpr int kWaves = WAVES;
     static constexpr bool kWide = WIDE;
     static constexpr int B = 64 * kWaves;                         // threads per block
     // block-shared tables first: their bases (and the row bases below) fit the 16-bit immediate offset of a DS
     // instruction, so an address is just the bit field taken from pk
-    static constexpr uint32_t oDrvA = 0;                          // {var, base} x N drivers, 16 B each   (lap step)
-    static constexpr uint32_t oDrvB = oDrvA + N * 16;             // {base, deg} 2^31 x N drivers; at +32 entries {NaN, NaN} x N  (overtake pace)
-    static constexpr uint32_t oIc = oDrvB + (kMaxCars + N) * 16;  // [compound][driver] {eff f64, pit word u32, DNF threshold u32}
-    static constexpr uint32_t oComp = oIc + ((kNumCompounds - 1) * kMaxCars + N) * 16;   // {delta f64, pad} x 8, 16 B each
-    static constexpr uint32_t oDrs = oComp + kCompStride * 16;    // {0.0, drs_delta}                          (lap time)
+    static_assert(WIDE == (KIND == kRegWide), "RegKind");
+    static constexpr RegTables T = reg_tables(N, KIND);
+    static constexpr uint32_t oDrvA = T.oDrvA;                    // {var, base} x N drivers, 16 B each   (lap step)
+    static constexpr uint32_t oDrvB = T.oDrvB;                    // {base, deg} 2^31 x N drivers; kDnf bytes further on {NaN, NaN} x N  (overtake pace)
+    static constexpr uint32_t oIc = T.oIc;                        // [compound][driver] {eff f64, pit word u32, DNF threshold u32}, compound stride 32 entries
+    static constexpr uint32_t oPair = oIc + N * 16;               // kPair: [compound] {delta, delta, 0.0, drs_delta} at the same stride, in oIc's padding
+    static constexpr uint32_t oComp = T.oComp;                    // !kPair: {delta f64, pad} x 8, 16 B each
+    static constexpr uint32_t oDrs = T.oDrs;                      // {0.0, drs_delta}                          (lap time, !kPair)
     static constexpr uint32_t oPit = oDrs + 16;                   // {0.0, pit_loss}                           (the stop's time, by flag)
     static constexpr uint32_t oDrsB = oDrs + 32;                  // {0.0, drs_delta 2^31}                     (overtake pace)
-    static constexpr uint32_t oLut = oDrsB + 32;                  // pit rule: u32 [4 regimes][8 used-sets]
-    static constexpr uint32_t oNorm = oLut + 128;                 // float4[kNormalRows]; addressed from kNormalRowBias rows before it (not WIDE)
-    static constexpr uint32_t oHist = oNorm + (WIDE ? 0 : kNormalRows * 16);   // u32[N x N]
+    static constexpr uint32_t oLut = T.oLut;                      // pit rule: u32 [4 regimes][8 used-sets]
+    static constexpr uint32_t oNorm = T.oNorm;                    // float4[kNormalRows]; addressed from kNormalRowBias rows before it (not WIDE)
+    static constexpr uint32_t oHist = T.oHist;                    // u32[N x N]
+    // the pk bits that go with the map (pk word, above)
+    static constexpr bool kRelaid = T.relaid, kPair = T.pair;
+    static constexpr uint32_t kDnf = T.dnf, kDirty = T.dirty;
+    static constexpr int kCompShift = T.comp_shift;
+    static constexpr uint32_t kCompMask = 7u << kCompShift;
+    static constexpr uint32_t kSlotMask = k3IdMask | kDnf;        // pk & kSlotMask = 16 driver + kDnf (retired): the overtake pace entry
+    static constexpr uint32_t kIcMask = k3IdMask | kCompMask;     // kRelaid: pk & kIcMask = 16 (32 compound + driver)
+    static constexpr uint32_t kPairMask = kCompMask | k3Drs;      // kPair: pk & kPairMask = 512 compound + 8 drs
+    static_assert(T.end <= shared_lds_bytes_reg(N) - (WIDE ? (size_t)kNormalRows * 16 : 0), "the table map ends within the bytes the launch has always had");
+    static_assert(!kRelaid || (kCompShift == 9 && (kDnf == 4096u || kDnf == 8192u) && (kDnf | kDirty) == 0x3000u), "pk word");
+    static_assert(!kPair || (kRelaid && N <= 30 && oPair % 8 == 0 && oPair / 8 + 2 <= 255), "pair rows: in oIc's padding, base within the ds_read2_b64 offsets");
+    static_assert((kSlotMask & ~k3IdMask) == kDnf && kDnf % 16 == 0, "the NaN copy of the overtake pace lies kDnf bytes after the live table");
     static_assert(WIDE || oNorm >= kNormalRowBias * 16, "the inverse-normal rows are addressed through a base 48 rows before the table");
-    static constexpr uint32_t oGrid = oHist + (uint32_t)align16((size_t)N * N * 4);   // f64 [slot][driver]
-    static constexpr uint32_t oW = oGrid + (uint32_t)align16((size_t)N * N * 8);   // [kWordRows][B] u32, 16-byte aligned (odd N: padded)
+    static constexpr uint32_t oGrid = T.oGrid;                    // f64 [slot][driver]
+    // (the per-lane planes start where they always have: what the re-laid map saves is padding before them)
+    static constexpr uint32_t oW = (uint32_t)shared_lds_bytes_reg(N) - (WIDE ? (uint32_t)kNormalRows * 16u : 0u);   // [kWordRows][B] u32, 16-byte aligned (odd N: padded)
     static constexpr uint32_t oLast = oW + (uint32_t)kWordRows * B * 4;      // [N][B] f64
     // WIDE: rows kNorm53First .. 783 of the binary64 inverse-normal table, 64 B each, behind the per-lane planes
     static constexpr uint32_t oNorm53 = oLast + (uint32_t)N * B * 8;
@@ -285,6 +414,8 @@ __host__ __device__ constexpr int wide_block_waves(int n)
 __host__ __device__ constexpr int wide_min_waves(int n) { return wide_block_waves(n) > 8 ? 3 : 2; }
 template <int N>
 using WideGeo = RegGeo<N, wide_block_waves(N), true>;
+template <int N>
+using BatchGeo = RegGeo<N, reg_block_waves(N), false, kRegBatch>;     // the batch kernel: the default block, its own table map
 
 // The sorting network of the full sort: Knuth, TAOCP 5.2.2 Algorithm M (merge exchange) for any N, or, for the sizes
 // listed in sort_networks.h, two size-optimal half sorters and Batcher's odd-even merge (20 cars: 93 comparators instead
@@ -541,10 +672,11 @@ __device__ __forceinline__ bool resort_after_overtakes(double (&cum)[N], uint32_
 // DISTINCT: the caller knows that no two times of the field are equal (the sorts report it; all but a few wave-laps
 // in a hundred).  Every car behind the leader then has a gap > 0 and the first half of :552's  0 < gap < threshold
 // is the "not the first running car" mask the DRS flag needs anyway: one binary64 compare less per slot.
-template <int N, bool DISTINCT = false>
+template <int N, class G, bool DISTINCT = false>
 __device__ __forceinline__ void update_positions_reg(const double (&cum)[N], uint32_t (&pk)[N],
                                                      bool drs_allowed, double dirty_thr)
 {
+    constexpr uint32_t k3Dnf = G::kDnf, k3Dirty = G::kDirty;
     bool first = true;
     double leader = 0.0, prev = 0.0;
     // one straight pass, merged by selects (a few lanes hold retired cars; the wave would pay for the branches).  The
@@ -576,7 +708,7 @@ __host__ __device__ constexpr int pit_regime(int remaining_laps)
 {
     return remaining_laps > 30 ? 0 : remaining_laps > 20 ? 1 : remaining_laps > 15 ? 2 : 3;
 }
-__device__ __forceinline__ uint32_t pit_rule_word(int track, int regime, uint32_t used, uint32_t pop_sh, uint32_t pop_mh)
+__device__ __forceinline__ uint32_t pit_rule_word(int track, int regime, uint32_t used, uint32_t pop_sh, uint32_t pop_mh, int comp_shift)
 {
     const int remaining_laps = regime == 0 ? 31 : regime == 1 ? 21 : regime == 2 ? 16 : 0;     // one value per regime
     uint32_t newc = stint_compound(track, remaining_laps);
@@ -588,7 +720,7 @@ __device__ __forceinline__ uint32_t pit_rule_word(int track, int regime, uint32_
         if (remaining_laps > 20) newc = (avail & 2u) ? 1u : popped;
         else newc = (avail & 1u) ? 0u : popped;
     }
-    return (newc << k3CompShift) | ((used | (1u << newc)) & k3UsedMask);
+    return (newc << comp_shift) | ((used | (1u << newc)) & k3UsedMask);
 }
 
 // A lower bound of every lap time of the problem, lap 1 included (reference :317-332, :301-306), from the inputs alone:
@@ -683,12 +815,12 @@ __device__ __forceinline__ void reg_load_tables(const KParams *__restrict__ P, u
         // the pace delta then comes out as delta x 2^31, whose ceiling IS the integer threshold of the draw word
         b[0] = P->base_pace[d] * 2147483648.0;
         b[1] = P->tire_deg[d] * 32768.0;                         // x 2^31 / 2^16: multiplies the age FIELD of pk (age << 16)
-        b[2 * kMaxCars] = qnan;                                  // the retired copy: pace = NaN
-        b[2 * kMaxCars + 1] = qnan;
+        b[G::kDnf / 8] = qnan;                                   // the retired copy, kDnf bytes on: pace = NaN
+        b[G::kDnf / 8 + 1] = qnan;
     }
     if (tid < 2) {
         // {0.0, drs_delta}: a car's row is at byte offset (pk & k3Drs)
-        *reinterpret_cast<double *>(smem + G::oDrs + tid * k3Drs) = tid ? P->drs_delta : 0.0;
+        if constexpr (!G::kPair) *reinterpret_cast<double *>(smem + G::oDrs + tid * k3Drs) = tid ? P->drs_delta : 0.0;
         *reinterpret_cast<double *>(smem + G::oDrsB + tid * k3Drs) = tid ? P->drs_delta * 2147483648.0 : 0.0;
         *reinterpret_cast<double *>(smem + G::oPit + tid * 8u) = tid ? P->pit_loss : 0.0;
     }
@@ -704,11 +836,22 @@ __device__ __forceinline__ void reg_load_tables(const KParams *__restrict__ P, u
     }
     for (uint32_t i = tid; i < 32u; i += B)
         *reinterpret_cast<uint32_t *>(smem + G::oLut + i * 4) =
-            pit_rule_word(P->track, (int)(i >> 3), i & 7u, (uint32_t)P->pop_sh, (uint32_t)P->pop_mh);
-    for (uint32_t c = tid; c < (uint32_t)kCompStride; c += B) {
-        double *r = reinterpret_cast<double *>(smem + G::oComp + c * 16);
-        r[0] = P->comp_delta[c];
-        r[1] = 0.0;
+            pit_rule_word(P->track, (int)(i >> 3), i & 7u, (uint32_t)P->pop_sh, (uint32_t)P->pop_mh, G::kCompShift);
+    if constexpr (G::kPair) {
+        // {delta_c, delta_c, 0.0, drs_delta} behind the drivers of compound c: a car's pair is at (pk & kPairMask) and 16 bytes on
+        for (uint32_t c = tid; c < (uint32_t)kNumCompounds; c += B) {
+            double *r = reinterpret_cast<double *>(smem + G::oPair + c * (kMaxCars * 16u));
+            r[0] = P->comp_delta[c];
+            r[1] = P->comp_delta[c];
+            r[2] = 0.0;
+            r[3] = P->drs_delta;
+        }
+    } else {
+        for (uint32_t c = tid; c < (uint32_t)kCompStride; c += B) {
+            double *r = reinterpret_cast<double *>(smem + G::oComp + c * 16);
+            r[0] = P->comp_delta[c];
+            r[1] = 0.0;
+        }
     }
     for (uint32_t i = tid; i < (uint32_t)(N * N); i += B) {
         s_hist[i] = 0u;
@@ -753,11 +896,12 @@ __device__ __forceinline__ double scalar_f64(double x)
 // narrowed to the lanes they change for, four slots to an assembly statement (upd_commit*, race_isa.hip.h), instead of
 // merged by selects for every lane; the field sizes of reg_update_by_selects() keep the select form.  `drs_allowed` is
 // per lane (an event ends DRS in that race only): it goes in as a lane mask made once a lap.
-template <int N>
+template <int N, class G>
 __device__ __forceinline__ void update_positions_distinct(const double (&cum)[N], uint32_t (&pk)[N], bool drs_allowed, double dirty_thr)
 {
+    constexpr uint32_t k3Dnf = G::kDnf, k3Dirty = G::kDirty;
     if constexpr (reg_update_by_selects(N)) {
-        update_positions_reg<N, true>(cum, pk, drs_allowed, dirty_thr);
+        update_positions_reg<N, G, true>(cum, pk, drs_allowed, dirty_thr);
     } else {
         const UpdLap c{scalar_f64(dirty_thr), lane_mask(drs_allowed)};
         uint64_t first = kAllLanes;                     // (the statement that opens the field writes it)
@@ -785,6 +929,7 @@ __device__ __forceinline__ uint32_t wide_pass_exact_body(const uint32_t (&pk)[N]
                                                          uint32_t c1l, uint32_t k0l, uint32_t k1l, uint32_t tid)
 {
     constexpr int B = G::B;
+    constexpr uint32_t k3SlotMask = G::kSlotMask;
     const uint32_t tid4 = tid * 4u;
     auto w_row_ = [&](int r) -> uint32_t { return G::oW + (uint32_t)r * (B * 4) + tid4; };
     uint32_t hits53 = 0u;
@@ -794,7 +939,7 @@ __device__ __forceinline__ uint32_t wide_pass_exact_body(const uint32_t (&pk)[N]
         double pace_prev = 0.0;
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            const f64x2 bd = lds_ld_f64x2(G::oDrvB + pk_slot16(pk[i]));
+            const f64x2 bd = lds_ld_f64x2(G::oDrvB + (pk[i] & k3SlotMask));
             const double pace = bd.x + (double)(pk[i] & k3AgeMask) * bd.y;
             thr64[i] = 0ull;
             if (i > 0) {
@@ -905,6 +1050,9 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                                              uint32_t ws_first_lane, const double *__restrict__ norm53 = nullptr)
 {
     constexpr int B = G::B;
+    // the pk bits that depend on the geometry's table map (pk word, RegTables)
+    constexpr uint32_t k3Dnf = G::kDnf, k3Dirty = G::kDirty, k3CompMask = G::kCompMask, k3SlotMask = G::kSlotMask;
+    constexpr int k3CompShift = G::kCompShift;
     // slots whose LDS gathers (and Philox blocks) are in flight together in the lap step (both widths)
     constexpr int kStepBatch = 4;
     // (WIDE, compiled for 3 waves per SIMD: deviates first, gathers last, one table row at a time -- see wide_block_waves)
@@ -961,20 +1109,34 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
         uint32_t la;            // byte offset of the driver's LAST row
         uint32_t fit;           // compound and used-set a pit stop on this lap would leave, positioned as in pk
     };
+    // a car's oIc entry: one mask where the compound sits directly above the driver index
+    auto ic_of = [&](uint32_t p) -> uint32_t {
+        if constexpr (G::kRelaid) return p & G::kIcMask;
+        else return pk_driver16(p) + ((p & k3CompMask) >> (k3CompShift - 9));
+    };
+    // ... and the address of its compound's pace delta (lap 1; the lap step reads it with the DRS gain where G::kPair)
+    auto cdelta_at = [&](uint32_t p) -> uint32_t {
+        if constexpr (G::kPair) return G::oPair + (p & k3CompMask);
+        else return G::oComp + ((p >> (k3CompShift - 4)) & 0x70u);
+    };
     auto load_slot = [&](uint32_t p, uint32_t lut_base) -> SlotIn {
         SlotIn r;
         r.fit = lds_ld<uint32_t>(((p & k3UsedMask) << 2) + lut_base);
         const uint32_t id16 = pk_driver16(p);                                     // 16 x driver
         r.la = id16 * (uint32_t)(B / 2) + tid8;                                   // = driver x (B x 8) + tid8
         r.last = lds_ld<double>(G::oLast + r.la);
-        const uint32_t ic = id16 + pk_comp512(p);                                 // 16 x (32 compound + driver)
+        const uint32_t ic = ic_of(p);                                             // 16 x (32 compound + driver)
         const f64x2 vb = lds_ld_f64x2(G::oDrvA + id16);
         r.var = vb.x;
         r.base = vb.y;
         uint32_t pad;
         lds_ld_f64_u32x2(G::oIc + ic, r.eff, r.pitw, pad);
-        r.cdelta = lds_ld<double>(G::oComp + pk_comp16(p));                        // 16 x compound
-        r.drs = lds_ld<double>(G::oDrs + (p & k3Drs));                            // 0.0 or drs_delta
+        if constexpr (G::kPair) {
+            lds_ld2_f64<G::oPair>(p & G::kPairMask, r.cdelta, r.drs);              // compound delta; 0.0 or drs_delta
+        } else {
+            r.cdelta = lds_ld<double>(cdelta_at(p));
+            r.drs = lds_ld<double>(G::oDrs + (p & k3Drs));                        // 0.0 or drs_delta
+        }
         return r;
     };
 
@@ -1117,8 +1279,8 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 const double z = lds_ld<double>(G::oLast + last_of(p));
                 const uint32_t id16 = pk_driver16(p);
                 const f64x2 vb = lds_ld_f64x2(G::oDrvA + id16);                        // {variance, base pace}
-                const double eff = lds_ld<double>(G::oIc + id16 + pk_comp512(p));
-                const double cdelta = lds_ld<double>(G::oComp + pk_comp16(p));
+                const double eff = lds_ld<double>(G::oIc + ic_of(p));
+                const double cdelta = lds_ld<double>(cdelta_at(p));
                 if (z != z) {
                     pk[i] = (p & ~k3AgeMask) | k3Dnf | (1u << k3AgeShift);
                     cum[i] = -(double)(i + 1) * 0x1p-1000;                              // (see the default path below)
@@ -1168,8 +1330,8 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 const double zs = (double)lds_ld<float>(G::oLast + la + 4u);
                 const uint32_t id16 = pk_driver16(p);
                 const f64x2 vb = lds_ld_f64x2(G::oDrvA + id16);                        // {variance, base pace}
-                const double eff = lds_ld<double>(G::oIc + id16 + pk_comp512(p));
-                const double cdelta = lds_ld<double>(G::oComp + pk_comp16(p));
+                const double eff = lds_ld<double>(G::oIc + ic_of(p));
+                const double cdelta = lds_ld<double>(cdelta_at(p));
                 if (z != z) {
                     pk[i] = (p & ~k3AgeMask) | k3Dnf | (1u << k3AgeShift);
                     // The reference leaves a lap-1 retirement at cumulative_time 0.0, so several of them tie; ties sort
@@ -1197,7 +1359,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
 #pragma unroll 1
         for (int d = 0; d < N; ++d) lds_st<double>(l_row(d), 0.0);          // last_lap_time is not set on lap 1 (Q3)
         network_sort<N>(cum, pk);
-        update_positions_reg<N>(cum, pk, false, dirty_thr);
+        update_positions_reg<N, G>(cum, pk, false, dirty_thr);
 
         // ================= retirements of laps 2..L, reference :190-197, drawn once per race =================
         // The reference draws one uniform per running car per lap and retires the car if it is below the driver's per-lap
@@ -1733,7 +1895,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                         // that lap runs with a penalty of +0.0 and, ahead = 0, a maximum that returns the clean time.
                         // Masked by the flag, both terms of :213-215 vanish for a clean-air car:  max(|0|, clean + 0.0) = clean
                         // (clean > 0).
-                        const uint32_t dirty_m = (uint32_t)((int32_t)(p << (31 - 13)) >> 31);                  // all ones iff k3Dirty
+                        const uint32_t dirty_m = (uint32_t)((int32_t)(p << (k3Dirty == 8192u ? 31 - 13 : 31 - 12)) >> 31);                  // all ones iff k3Dirty
                         const double pen_if_dirty = __hiloint2double((int)((uint32_t)__double2hiint(dirty_pen_lap) & dirty_m),
                                                                      (int)((uint32_t)__double2loint(dirty_pen_lap) & dirty_m));
                         const double ahead_if_dirty = __hiloint2double((int)((uint32_t)__double2hiint(ahead_last) & dirty_m),
@@ -1826,7 +1988,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
 #pragma unroll
                             for (int j = 0; j < H; ++j) {
                                 if (h + j < N) {
-                                    const uint32_t id16 = pk_slot16(pk[h + j]);           // 16 x (32 dnf + driver)
+                                    const uint32_t id16 = pk[h + j] & k3SlotMask;          // 16 x driver (+ kDnf: retired)
                                     const f64x2 bd = lds_ld_f64x2(G::oDrvB + id16);
                                     pb[j] = bd.x;
                                     pd[j] = bd.y;
@@ -1955,9 +2117,9 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
             }
             // ---- _update_positions, :227-228 ----  (under EXEC, upd_commit*, for the wave-laps whose fields have no equal times)
             if (!MCGP_ANY(!distinct_times))
-                update_positions_distinct<N>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
+                update_positions_distinct<N, G>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
             else
-                update_positions_reg<N>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
+                update_positions_reg<N, G>(cum, pk, lap > 2 && lap > drs_disabled_until, dirty_thr);
         }
 
         // ================= classification, reference :230-242 =================
@@ -2070,22 +2232,22 @@ __device__ __forceinline__ void batch_problem(const KParams *__restrict__ P, uns
                                               uint64_t n_sims, uint64_t sim_offset, uint64_t seed, uint32_t n_chunks,
                                               uint32_t *__restrict__ retire_ws, unsigned long long *__restrict__ hist)
 {
-    using G = RegGeo<N>;
-    reg_load_tables<N>(P, smem, threadIdx.x);                    // (zeroes the LDS histogram)
+    using G = BatchGeo<N>;
+    reg_load_tables<N, G>(P, smem, threadIdx.x);                 // (zeroes the LDS histogram)
     __syncthreads();
-    reg_simulate<N>(P, smem, threadIdx.x, ticket, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32),
-                    nullptr, nullptr, n_chunks, retire_ws, (uint32_t)(gridDim.x * G::B), (uint32_t)(blockIdx.x * G::B));
+    reg_simulate<N, false, G>(P, smem, threadIdx.x, ticket, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32),
+                              nullptr, nullptr, n_chunks, retire_ws, (uint32_t)(gridDim.x * G::B), (uint32_t)(blockIdx.x * G::B));
     __syncthreads();                                             // every wave's counts are in
-    reg_flush_hist<N>(smem, threadIdx.x, hist);
+    reg_flush_hist<N, G>(smem, threadIdx.x, hist);
     __syncthreads();                                             // (the flush reads what the next table load zeroes)
 }
 template <int N>
-__global__ void __launch_bounds__(RegGeo<N>::B, reg_min_waves(N))
+__global__ void __launch_bounds__(BatchGeo<N>::B, reg_min_waves(N))
 race_kernel_reg_batch(const KParams *__restrict__ P, const BatchItem *__restrict__ items, uint32_t n_problems,
                       uint64_t n_sims, unsigned long long *__restrict__ hist, uint32_t n_chunks,
                       uint32_t *__restrict__ tickets, uint32_t *__restrict__ retire_ws, uint32_t param_stride)
 {
-    using G = RegGeo<N>;
+    using G = BatchGeo<N>;
     extern __shared__ __align__(16) unsigned char smem[];
     if ((int)blockDim.x != G::B || lds_base_of(smem) != 0u) __builtin_trap();
     // first problem of this block; `visited` problems have been looked at (each at most once: the loop ends)

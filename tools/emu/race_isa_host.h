@@ -83,6 +83,12 @@ inline void lds_ld_f64_u32x2(uint32_t addr, double &d, uint32_t &u0, uint32_t &u
     u0 = lds_ld<uint32_t>(addr + 8);
     u1 = lds_ld<uint32_t>(addr + 12);
 }
+template <uint32_t BASE>
+inline void lds_ld2_f64(uint32_t addr, double &a, double &b)
+{
+    a = lds_ld<double>(BASE + addr);
+    b = lds_ld<double>(BASE + 16u + addr);
+}
 // v_cvt_u32_f64: toward zero, saturating, NaN -> 0
 inline uint32_t cvt_u32_f64_sat(double x)
 {
