@@ -1,10 +1,11 @@
 """Inputs shared by the tests of the generic kernel family (race_kernel, race_resume_kernel, race_trace_kernel,
 race_strategy_kernel, race_gaps_kernel, race_conditions_kernel, race_stints_kernel, race_moves_kernel,
-race_penalties_kernel) on the host build (test_generic_host_build.py, test_gaps_host_build.py,
-test_conditions_host_build.py, test_stints_host_build.py, test_moves_host_build.py, test_penalties_host_build.py) and on
-the device (test_gpu_generic_fuzz.py for trace, resume and strategies, test_gpu_gaps_conditions_fuzz.py for gaps and
-conditions, test_gpu_stints_moves_fuzz.py for stints and moves with their counting kernels, test_gpu_penalties_fuzz.py
-for penalties, whose scenarios are in penalties_cases.py): the configurations, the laps a race is resumed from, and the
+race_penalties_kernel, race_fastest_kernel) on the host build (test_generic_host_build.py, test_gaps_host_build.py,
+test_conditions_host_build.py, test_stints_host_build.py, test_moves_host_build.py, test_penalties_host_build.py,
+test_fastest_host_build.py) and on the device (test_gpu_generic_fuzz.py for trace, resume and strategies,
+test_gpu_gaps_conditions_fuzz.py for gaps and conditions, test_gpu_stints_moves_fuzz.py for stints and moves with their
+counting kernels, test_gpu_penalties_fuzz.py for penalties, whose scenarios are in penalties_cases.py,
+test_gpu_bonus_live_fuzz.py for the fastest lap): the configurations, the laps a race is resumed from, and the
 plan scenarios, all scaled to a case's field size and lap count.  Nothing here looks at what the code under test returns."""
 import copy
 import json
@@ -128,3 +129,25 @@ def smallest_lap_time_ties(ref):
     t = np.where(tr['dnf'][:, 1:, :] == 0, tr['last'][:, 1:, :], np.inf)
     best = t.min(axis=2, keepdims=True)
     return int((((t == best) & np.isfinite(t)).sum(axis=2) >= 2).sum())
+
+
+def fastest_lap_ties(ref):
+    """From the oracle's trace alone: (simulations whose smallest running lap time of the race, laps >= 2, is shared by
+    two different drivers, simulations in which it is set on two different laps)."""
+    tr = ref['trace']
+    t = np.where(tr['dnf'][:, 1:, :] == 0, tr['last'][:, 1:, :], np.inf)          # [m][L - 1][n]
+    if t.shape[1] == 0:
+        return 0, 0
+    hit = (t == t.min(axis=(1, 2), keepdims=True)) & np.isfinite(t)
+    return int((hit.any(axis=1).sum(axis=1) >= 2).sum()), int((hit.any(axis=2).sum(axis=1) >= 2).sum())
+
+
+def run_input_slices(k):
+    """run_inputs() dealt into k lists for tests that take a slice each: together every input once, the 84 fuzz
+    configurations among them."""
+    inputs = run_inputs()
+    parts = [inputs[i::k] for i in range(k)]
+    names = [name for part in parts for name, _, _ in part]
+    assert sorted(names) == sorted(name for name, _, _ in inputs) and len(set(names)) == len(inputs)
+    assert sum(name in fuzz_cases() for name in names) == N_FUZZ
+    return parts

@@ -39,6 +39,31 @@ def test_random_orders(n, sims):
                 assert info['lds_bytes'] == (256 * n + 15) // 16 * 16 + (4 * n ** 3 if in_lds else 0)
 
 
+@pytest.mark.parametrize('n,b', [(10, 14), (11, 9), (12, 4), (23, 13), (24, 8), (25, 3)])
+def test_points_across_the_word_boundary(n, b):
+    """The sizes at which the points field straddles a key word, b of its bits in the lower word: every driver carries in
+    2^b - (1 .. 6) points, so the tables (8 points at most) take some totals, not all, to 2^b and above, where the upper
+    word's part of the field is no longer zero and the compare has to order it above the lower word.  259 simulations: a
+    tail tile of 3."""
+    rng = np.random.default_rng(7000 + n)
+    sims = 259
+    orders = [_perms(rng, sims, n) for _ in TABLES]
+    ip = (1 << b) - rng.integers(1, 7, n)
+    ic = rng.integers(0, 2, (n, n))
+    pts, cnt = CR.standings(orders, TABLES, CB, ip, ic)
+    above = (pts >= 1 << b).sum(axis=1)
+    mixed = int(((above > 0) & (above < n)).sum())
+    champions = len(set(np.argmin(CR.rank(pts, cnt), axis=1).tolist()))
+    print(f'n = {n}: {mixed} of {sims} simulations with totals on both sides of 2^{b}, {champions} distinct champions')
+    assert mixed >= 200 and champions >= 10
+    for given in (0, 2):
+        ref = LR.title_given(orders, TABLES, CB, given, ip, ic)
+        for in_lds in (True, False):
+            out, info = H.given_run(orders, TABLES, CB, given, ip, ic, in_lds=in_lds)
+            assert np.array_equal(out, ref), (given, in_lds)
+            assert info['words'] == (16 + 5 * n + 63) // 64
+
+
 @pytest.mark.parametrize('in_lds', [True, False])
 @pytest.mark.parametrize('n', [3, 23])
 def test_chunks_and_grid_stride(n, in_lds):

@@ -11,6 +11,7 @@ import championship_bonus_ref as BR
 import championship_cases as CC
 import championship_ref as CR
 import fastest_host_build as FH
+import generic_cases as G
 import oracle_py as O
 import resume_ref as RS
 
@@ -63,6 +64,55 @@ def test_a_race_in_which_everybody_retires_on_lap_1():
     case['config']['dnf_rates'] = {k: 1.0 for k in case['config']['dnf_rates']}
     ref = _compare_race(case, 16, seed=1)
     assert (ref['fl_driver'] == BR.NONE).all()
+
+
+def test_every_fuzz_configuration():
+    """The generic family's inputs (8 golden, 84 fuzz, lap times near zero and at the overtake's floor, six field sizes):
+    32 simulations each under the case's own seed, sim_offset 3.  Under a second for the hundred, references included."""
+    done = 0
+    for name, case, seed in G.run_inputs():
+        _compare_race(case, 32, seed, sim_offset=3)
+        done += name in G.fuzz_cases()
+    assert done == G.N_FUZZ
+
+
+def _last_of_equal_times_wins(ref):
+    """The fastest-lap driver [m] under the WRONG tie rule, <= instead of <: of equal times the later lap, then the worse
+    running position (-1 for none)."""
+    tr, m, n = ref['trace'], *ref['orders'].shape
+    rows = np.arange(m)
+    slot = np.zeros((m, n), np.int64)
+    slot[rows[:, None], ref['grids']] = np.arange(n)[None, :]
+    best, driver = np.full(m, np.inf), np.full(m, BR.NONE, np.int64)
+    for k in range(1, tr['cum'].shape[1]):
+        order = np.lexsort((slot, tr['cum'][:, k, :]), axis=-1)
+        t = np.where(np.take_along_axis(tr['dnf'][:, k, :], order, axis=1) == 0,
+                     np.take_along_axis(tr['last'][:, k, :], order, axis=1), np.inf)
+        j = n - 1 - np.argmin(t[:, ::-1], axis=1)                       # the last of equal times
+        better = (t[rows, j] <= best) & np.isfinite(t[rows, j])
+        best, driver = np.where(better, t[rows, j], best), np.where(better, order[rows, j], driver)
+    return driver
+
+
+def assert_ties_of_the_fastest_lap(case, m, seed, sim_offset):
+    """From the oracle's trace alone: in at least 32 of X_no_noise's simulations two drivers share the race's fastest
+    time, in at least one it is set on two laps, and in at least 32 the tie rule decides who has the fastest lap."""
+    ref = RS.traced_run(case, m, seed, sim_offset)
+    two_drivers, two_laps = G.fastest_lap_ties(ref)
+    print(f'fastest-lap ties of {m} simulations: {two_drivers} between two drivers, {two_laps} across two laps')
+    assert two_drivers >= 32 and two_laps >= 1
+    first = BR.fastest_lap(ref)[0]
+    differ = int((_last_of_equal_times_wins(ref) != first).sum())
+    print(f'the fastest-lap driver under "last of equal times wins" differs in {differ} simulations')
+    assert differ >= 32 and (first != BR.NONE).all()
+
+
+def test_ties_of_the_fastest_lap():
+    """X_no_noise (no lap-time noise: equal cars set equal times), 64 simulations: 63 have the fastest time shared by two
+    drivers, 1 by two laps; an observer with <=, or one that walked the cars by index, gives another driver."""
+    case = G.fuzz_cases()['X_no_noise']
+    assert_ties_of_the_fastest_lap(case, 64, case['seed'], 3)
+    _compare_race(case, 64, case['seed'], sim_offset=3)
 
 
 # ---------------------------------------------------------------- champ_bonus behind champ_accumulate

@@ -9,8 +9,10 @@ import json
 import numpy as np
 import pytest
 
+import championship_bonus_ref as BR
 import championship_live_ref as LR
 import championship_ref as CR
+import championship_rounds_ref as RR
 import oracle_py as O
 import resume_ref as RS
 from monte_carlo_gp_amd import RaceConfig, RaceSimulator, cli, run_championship
@@ -63,20 +65,54 @@ def _given_lds(n):
     return vals[2].value, tile + 4 * n ** 3, tile
 
 
-def _check_live(plan, state, n_sims, sim_offset, standings, given, by_round=False, orders=None, **kw):
-    """plan: [(case, seed, deviates, table, countback)], race 0 from `state`.  Every given race of `given` in a call of its
-    own against the references; returns (the last result, the races' reference orders)."""
+def _check_live(plan, state, n_sims, sim_offset, standings, given, by_round=False, orders=None, bonus=None, **kw):
+    """plan: [(case, seed, deviates, table, countback)], race 0 from `state` (from the grid when state is None).  Every
+    given race of `given` in a call of its own against the references; returns (the last result, the races' reference
+    orders).  bonus: None, or [(fastest-lap points, within)] per race (0 points: none); the references are then
+    championship_bonus_ref's on the oracle's traced runs of the bonus races, title_given's with the bonus matrix."""
     case0 = plan[0][0]
     drivers = list(case0['grid_probs'])
-    races = [_live(case0, plan[0][1], state, points=plan[0][3], countback=plan[0][4])]
-    races += [_race(c, seed, deviates=dev, points=pts, countback=cb) for c, seed, dev, pts, cb in plan[1:]]
+    extra = [{}] * len(plan) if bonus is None else [dict(fastest_lap_points=b, fastest_lap_within=w) for b, w in bonus]
+    if state is None:
+        races = [_race(case0, plan[0][1], deviates=plan[0][2], points=plan[0][3], countback=plan[0][4], **extra[0])]
+    else:
+        races = [_live(case0, plan[0][1], state, points=plan[0][3], countback=plan[0][4], **extra[0])]
+    races += [_race(c, seed, deviates=dev, points=pts, countback=cb, **e) for (c, seed, dev, pts, cb), e in zip(plan[1:], extra[1:])]
+    traced = {}
     if orders is None:
-        orders = [_resumed_orders(case0, state, plan[0][1], n_sims, sim_offset)[0]]
-        orders += [_oracle_orders(c, seed, dev, n_sims, sim_offset) for c, seed, dev, _, _ in plan[1:]]
+        if state is None:
+            orders = [_oracle_orders(case0, plan[0][1], plan[0][2], n_sims, sim_offset)]
+        else:
+            orders = [_resumed_orders(case0, state, plan[0][1], n_sims, sim_offset)[0]]
+        for r, (c, seed, dev, _, _) in enumerate(plan[1:], 1):
+            if bonus is not None and bonus[r][0] > 0:
+                traced[r] = BR.race(c, n_sims, seed, sim_offset)          # (a bonus race runs at 32-bit deviates only)
+                orders.append(traced[r]['orders'])
+            else:
+                orders.append(_oracle_orders(c, seed, dev, n_sims, sim_offset))
+    else:
+        orders = list(orders)
+        for r, o in enumerate(orders):
+            if isinstance(o, dict):                                       # a championship_bonus_ref race the caller has
+                traced[r], orders[r] = o, o['orders']
     names, team = _teams(case0, drivers)
     ip, ic = _standings_arrays(standings, drivers)
     tables, cb = [p[3] for p in plan], [int(p[4]) for p in plan]
-    champ, teams, gain, race_hists = CR.championship(orders, tables, cb, team, len(names), init_points=ip, init_counts=ic)
+    matrix = ref = None
+    if bonus is None:
+        champ, teams, gain, race_hists = CR.championship(orders, tables, cb, team, len(names), init_points=ip, init_counts=ic)
+    else:
+        assert bonus[0][0] == 0 or state is None
+        none = np.full(n_sims, BR.NONE, np.int64)
+        if state is None and bonus[0][0] > 0:
+            traced[0] = BR.race(case0, n_sims, plan[0][1], sim_offset)
+            assert np.array_equal(traced[0]['orders'], orders[0])
+        ref_races = [traced.get(r, dict(orders=o, fl_driver=none, fl_pos=none)) for r, o in enumerate(orders)]
+        assert all(b == 0 or r in traced for r, (b, _) in enumerate(bonus))
+        bp, bw = [b for b, _ in bonus], [w for _, w in bonus]
+        matrix = BR.bonus_matrix(ref_races, bp, bw)
+        ref = BR.season(ref_races, tables, cb, team, len(names), bp, bw, ip, ic, by_round=by_round)
+        champ, teams, gain, race_hists = (ref[k] for k in BR.SEASON_KEYS)
     res = None
     for g in given:
         res = run_championship(races, n_sims, standings=standings, sim_offset=sim_offset, set_pop=SET_POP, drivers=drivers,
@@ -86,12 +122,19 @@ def _check_live(plan, state, n_sims, sim_offset, standings, given, by_round=Fals
         assert np.array_equal(res.gain_hist, gain)
         for r, h in enumerate(res.race_histograms):
             assert np.array_equal(h, race_hists[r]), r
+        if ref is not None and any(b > 0 for b, _ in bonus):
+            assert np.array_equal(res.bonus_counts, ref['bonus_hist']), g
+            assert np.array_equal(res.fastest_lap_counts, ref['fastest_hist']), g
         if g is None:
             assert res.title_given is None
             continue
-        assert np.array_equal(res.title_given, LR.title_given(orders, tables, cb, g, ip, ic)), g
+        assert np.array_equal(res.title_given, LR.title_given(orders, tables, cb, g, ip, ic, bonus=matrix)), g
         LR.check_invariants(res.title_given, res.race_histograms[g], res.champ_hist)
-        if by_round:
+        if by_round and ref is not None:
+            for k in RR.KEYS:
+                assert np.array_equal(getattr(res, k), ref[k]), (g, k)
+            RR.assert_identities({k: getattr(res, k) for k in RR.KEYS}, n_sims, res.champ_hist, res.team_hist)
+        elif by_round:
             _assert_rounds(res, orders, tables, cb, team, len(names), ip, ic, n_sims)
     return res, orders
 
