@@ -479,14 +479,40 @@ __device__ __forceinline__ bool ovt_lane_hit(uint64_t acc)
     "v_and_b32 %[t], %[dty], %[p" #k "]\n\t"                                                                            \
     "v_cmp_ge_u32 %[c" #g "], %[g" #k "], %[w" #k "]\n\t"                                                               \
     "v_cmp_ne_u32 %[y" #g "], 0, %[t]\n\t"
-#define MCGP_STEP_WRITE(k, g)                                                                                           \
+// The pit writes behind a branch.  A stop is decided by tyre age against a per-(compound, driver) threshold, so the 64
+// races of a wave stop on the same few laps: at 20 cars some lane of the wave stops in one slot visit in eight (DESIGN
+// 3.3j), yet the two pit writes and the fetch of the word a stop leaves were issued for every slot of every lap.  In the
+// form below (StepSlot) the wave jumps over them:  s_and_b64 c, c, win leaves SCC = (c != 0) and s_cbranch_scc0 skips the
+// pit region -- the address of the rule word from the OLD p and the lap's rule row (`lut`, an SGPR), its ds_read_b32, the
+// time's second addition, s_waitcnt lgkmcnt(0) and the pk write.  s_xor a, a, c (a stopping lane leaves the age increment)
+// is inside as well: with c = 0 it changes nothing.  (The retirement write stays on the common path: a branch over it
+// costs more than the write at 2 and at 4 waves per SIMD, profiles/step_rare_bench.txt.)
+// Every mask and every value is computed exactly as in the form without a branch (StepSlotFit, kept for the field sizes of
+// reg_step_plain(): the word fetched ahead of the statement for every slot, every write issued); the time's first addition
+// moves ahead of the pit mask's two ANDs so that nothing scalar sits between the AND that sets SCC and the branch.  The
+// mask is an AND with compares that wrote 0 for a lane that is off: a lane off at entry never makes the wave enter the region.
+// Wait states and the compiler's view, in addition to the list above:
+//   s_and_b64 writes SCC -> s_cbranch_scc0 reads it: scalar to scalar, interlocked; no scalar instruction in between.
+//   s_and_b64 writes EXEC -> v_and_b32 / ds_read_b32 (LDS takes its lanes from EXEC): interlocked, as for the VALU above.
+//   THE FETCH IS HIDDEN FROM THE COMPILER, which counts no LDS operation for the statement.  The word lives in a statement
+//     temporary ("=&v") that is dead when the region ends, and the region waits with s_waitcnt lgkmcnt(0) before it reads
+//     it: whatever the compiler has in flight at entry has then returned as well (LDS returns in order), so every count it
+//     emits after the statement is conservative-correct on both paths -- on the path that skips nothing was added, on the
+//     path that fetches nothing is left.  The address sits in `t`, which no compare of a later slot reads before writing.
+//     The rule rows are written once, before the block's first barrier, and never again: no "memory" clobber.
+//   EXEC: set only to saved & mask inside the region, and back at the saved mask on both paths at the statement's end (a
+//     region that is skipped leaves EXEC as the instruction ahead of its branch set it, which the next s_and_b64 replaces).
+//   The branch target is a local label, unique per expansion of the statement (%=) and per slot.
+#define MCGP_STEP_WRITE_HEAD(k, g)                                                                                      \
     "s_and_b64 exec, %[ex], %[y" #g "]\n\t"                                                                             \
     "v_add_f64 %[l" #k "], %[l" #k "], %[pen]\n\t"                                                                      \
     "v_max_f64 %[l" #k "], |%[cy]|, %[l" #k "]\n\t"                                                                     \
     "s_and_b64 exec, %[ex], %[a" #g "]\n\t"                                                                             \
     "v_mov_b64 %[cy], %[s" #k "]\n\t"                                                                                   \
     "s_and_b64 %[d" #g "], %[a" #g "], %[d" #g "]\n\t"                                                                  \
-    "s_xor_b64 %[a" #g "], %[a" #g "], %[d" #g "]\n\t"                                                                  \
+    "s_xor_b64 %[a" #g "], %[a" #g "], %[d" #g "]\n\t"
+#define MCGP_STEP_WRITE_FIT(k, g)                                                                                       \
+    MCGP_STEP_WRITE_HEAD(k, g)                                                                                          \
     "s_and_b64 %[c" #g "], %[c" #g "], %[a" #g "]\n\t"                                                                  \
     "s_and_b64 %[c" #g "], %[c" #g "], %[win]\n\t"                                                                      \
     "s_and_b64 exec, %[ex], %[a" #g "]\n\t"                                                                             \
@@ -499,21 +525,54 @@ __device__ __forceinline__ bool ovt_lane_hit(uint64_t acc)
     "v_add_u32 %[p" #k "], %[age1], %[p" #k "]\n\t"                                                                     \
     "s_and_b64 exec, %[ex], %[d" #g "]\n\t"                                                                             \
     "v_and_or_b32 %[p" #k "], %[p" #k "], %[mage], %[rw]\n\t"
+#define MCGP_STEP_WRITE_RARE(k, g)                                                                                      \
+    MCGP_STEP_WRITE_HEAD(k, g)                                                                                          \
+    "s_and_b64 exec, %[ex], %[a" #g "]\n\t"                                                                             \
+    "v_add_f64 %[u" #k "], %[u" #k "], %[l" #k "]\n\t"                                                                  \
+    "s_and_b64 %[c" #g "], %[c" #g "], %[a" #g "]\n\t"                                                                  \
+    "s_and_b64 %[c" #g "], %[c" #g "], %[win]\n\t"                                                                      \
+    "s_cbranch_scc0 .Lmcgp_step_run" #k "_%=\n\t"                                                                       \
+    "s_xor_b64 %[a" #g "], %[a" #g "], %[c" #g "]\n\t"                                                                  \
+    "s_and_b64 exec, %[ex], %[c" #g "]\n\t"                                                                             \
+    "v_and_b32 %[t], %[used], %[p" #k "]\n\t"                                                                           \
+    "v_lshl_add_u32 %[t], %[t], 2, %[lut]\n\t"                                                                          \
+    "ds_read_b32 %[f], %[t]\n\t"                                                                                        \
+    "v_add_f64 %[u" #k "], %[u" #k "], %[pl]\n\t"                                                                       \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                          \
+    "v_and_or_b32 %[p" #k "], %[p" #k "], %[mpit], %[f]\n"                                                              \
+    ".Lmcgp_step_run" #k "_%=:\n\t"                                                                                     \
+    "s_and_b64 exec, %[ex], %[a" #g "]\n\t"                                                                             \
+    "v_add_u32 %[p" #k "], %[age1], %[p" #k "]\n\t"                                                                     \
+    "s_and_b64 exec, %[ex], %[d" #g "]\n\t"                                                                             \
+    "v_and_or_b32 %[p" #k "], %[p" #k "], %[mage], %[rw]\n\t"
 #define MCGP_STEP_OUT(k) [p##k] "+v"(pk[k]), [u##k] "+v"(cum[k]), [l##k] "+v"(lt[k])
 #define MCGP_STEP_IN(k)                                                                                                 \
-    [h##k] "v"((uint32_t)__double2hiint(s[k].last)), [s##k] "v"(s[k].last), [g##k] "v"(s[k].agef), [w##k] "v"(s[k].pitw),  \
-        [f##k] "v"(s[k].fit)
+    [h##k] "v"((uint32_t)__double2hiint(s[k].last)), [s##k] "v"(s[k].last), [g##k] "v"(s[k].agef), [w##k] "v"(s[k].pitw)
+#define MCGP_STEP_IN_FIT(k) MCGP_STEP_IN(k), [f##k] "v"(s[k].fit)
 #define MCGP_STEP_ENTER "s_mov_b64 %[ex], exec\n\ts_mov_b32 %[mpit], %[kpit]\n\ts_mov_b32 %[mage], %[kret]\n\t"
+#define MCGP_STEP_LEAVE "s_mov_b64 exec, %[ex]"
+// the order of the slots: the compares of slot k + 1 ahead of the writes of slot k (W: the write form)
+#define MCGP_STEP_BODY1(W) MCGP_STEP_ENTER MCGP_STEP_TEST(0, x) W(0, x) MCGP_STEP_LEAVE
+#define MCGP_STEP_BODY2(W) MCGP_STEP_ENTER MCGP_STEP_TEST(0, x) MCGP_STEP_TEST(1, z) W(0, x) W(1, z) MCGP_STEP_LEAVE
+#define MCGP_STEP_BODY3(W) MCGP_STEP_ENTER MCGP_STEP_TEST(0, x) MCGP_STEP_TEST(1, z) W(0, x) MCGP_STEP_TEST(2, x) W(1, z) W(2, x) MCGP_STEP_LEAVE
+#define MCGP_STEP_BODY4(W)                                                                                              \
+    MCGP_STEP_ENTER MCGP_STEP_TEST(0, x) MCGP_STEP_TEST(1, z) W(0, x) MCGP_STEP_TEST(2, x) W(1, z) MCGP_STEP_TEST(3, z) W(2, x) W(3, z)   \
+        MCGP_STEP_LEAVE
 #define MCGP_STEP_TEMPS_X [t] "=&v"(t), [ex] "=&s"(ex), [mpit] "=&s"(mpit), [mage] "=&s"(mage), [ax] "=&s"(ax), [dx] "=&s"(dx), [cx] "=&s"(cx), [yx] "=&s"(yx)
 #define MCGP_STEP_TEMPS_Z , [az] "=&s"(az), [dz] "=&s"(dz), [cz] "=&s"(cz), [yz] "=&s"(yz)
+#define MCGP_STEP_TEMPS_RARE , [f] "=&v"(f)
 #define MCGP_STEP_COMMON                                                                                                \
     [rw] "v"(c.retire_word), [win] "s"(c.window), [pl] "s"(c.pit_loss), [pen] "s"(c.pen), [kpit] "n"(KEEP_PIT),           \
         [kret] "n"(KEEP_RET), [dnf] "n"(DNF), [dty] "n"(DIRTY), [age1] "n"(AGE1)
+#define MCGP_STEP_COMMON_RARE MCGP_STEP_COMMON, [lut] "s"(c.lut), [used] "n"(kStepUsed)
 // one slot's inputs that are not updated in place
 struct StepSlot {
     double last;         // the driver's LAST value: the last lap time, negative iff the car retires on this lap
     uint32_t agef;       // the age field of p, in place
     uint32_t pitw;       // pit threshold, positioned as the age field
+};
+// ... with the word a stop leaves fetched for every slot: selects the form without branches
+struct StepSlotFit : StepSlot {
     uint32_t fit;        // compound and used-set a stop on this lap leaves, positioned as in pk
 };
 // the lap's wave-uniform inputs (SGPRs) and the retirement word (a VGPR: v_and_or_b32 takes one scalar operand)
@@ -521,79 +580,108 @@ struct StepLap {
     uint32_t retire_word;
     uint64_t window;     // all ones while the pit window is open, 0 otherwise
     double pit_loss, pen;
+    uint32_t lut;        // byte address of the lap's row of the pit rule: the word a stop leaves, by used-set (StepSlot only)
 };
+constexpr uint32_t kStepUsed = 7u;           // the used-set bits of pk ([0..2]), the word index into that row
 template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
-__device__ __forceinline__ void step_commit1(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+__device__ __forceinline__ void step_commit1(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlotFit *s, const StepLap &c)
 {
     uint32_t t, mpit, mage;
     uint64_t ex, ax, dx, cx, yx;
-    asm volatile(MCGP_STEP_ENTER
-                 MCGP_STEP_TEST(0, x)
-                 MCGP_STEP_WRITE(0, x)
-                 "s_mov_b64 exec, %[ex]"
+    asm volatile(MCGP_STEP_BODY1(MCGP_STEP_WRITE_FIT)
                  : MCGP_STEP_OUT(0), [cy] "+v"(carry), MCGP_STEP_TEMPS_X
-                 : MCGP_STEP_IN(0), MCGP_STEP_COMMON
+                 : MCGP_STEP_IN_FIT(0), MCGP_STEP_COMMON
+                 : "scc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+__device__ __forceinline__ void step_commit1(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+{
+    uint32_t t, f, mpit, mage;
+    uint64_t ex, ax, dx, cx, yx;
+    asm volatile(MCGP_STEP_BODY1(MCGP_STEP_WRITE_RARE)
+                 : MCGP_STEP_OUT(0), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_RARE
+                 : MCGP_STEP_IN(0), MCGP_STEP_COMMON_RARE
+                 : "scc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+__device__ __forceinline__ void step_commit2(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlotFit *s, const StepLap &c)
+{
+    uint32_t t, mpit, mage;
+    uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
+    asm volatile(MCGP_STEP_BODY2(MCGP_STEP_WRITE_FIT)
+                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
+                 : MCGP_STEP_IN_FIT(0), MCGP_STEP_IN_FIT(1), MCGP_STEP_COMMON
                  : "scc");
 }
 template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
 __device__ __forceinline__ void step_commit2(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
 {
+    uint32_t t, f, mpit, mage;
+    uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
+    asm volatile(MCGP_STEP_BODY2(MCGP_STEP_WRITE_RARE)
+                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z MCGP_STEP_TEMPS_RARE
+                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_COMMON_RARE
+                 : "scc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+__device__ __forceinline__ void step_commit3(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlotFit *s, const StepLap &c)
+{
     uint32_t t, mpit, mage;
     uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
-    asm volatile(MCGP_STEP_ENTER
-                 MCGP_STEP_TEST(0, x)
-                 MCGP_STEP_TEST(1, z)
-                 MCGP_STEP_WRITE(0, x)
-                 MCGP_STEP_WRITE(1, z)
-                 "s_mov_b64 exec, %[ex]"
-                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
-                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_COMMON
+    asm volatile(MCGP_STEP_BODY3(MCGP_STEP_WRITE_FIT)
+                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), MCGP_STEP_OUT(2), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
+                 : MCGP_STEP_IN_FIT(0), MCGP_STEP_IN_FIT(1), MCGP_STEP_IN_FIT(2), MCGP_STEP_COMMON
                  : "scc");
 }
 template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
 __device__ __forceinline__ void step_commit3(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
 {
+    uint32_t t, f, mpit, mage;
+    uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
+    asm volatile(MCGP_STEP_BODY3(MCGP_STEP_WRITE_RARE)
+                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), MCGP_STEP_OUT(2), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z MCGP_STEP_TEMPS_RARE
+                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_IN(2), MCGP_STEP_COMMON_RARE
+                 : "scc");
+}
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
+__device__ __forceinline__ void step_commit4(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlotFit *s, const StepLap &c)
+{
     uint32_t t, mpit, mage;
     uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
-    asm volatile(MCGP_STEP_ENTER
-                 MCGP_STEP_TEST(0, x)
-                 MCGP_STEP_TEST(1, z)
-                 MCGP_STEP_WRITE(0, x)
-                 MCGP_STEP_TEST(2, x)
-                 MCGP_STEP_WRITE(1, z)
-                 MCGP_STEP_WRITE(2, x)
-                 "s_mov_b64 exec, %[ex]"
-                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), MCGP_STEP_OUT(2), [cy] "+v"(carry), MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
-                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_IN(2), MCGP_STEP_COMMON
+    asm volatile(MCGP_STEP_BODY4(MCGP_STEP_WRITE_FIT)
+                 : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), MCGP_STEP_OUT(2), MCGP_STEP_OUT(3), [cy] "+v"(carry),
+                   MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
+                 : MCGP_STEP_IN_FIT(0), MCGP_STEP_IN_FIT(1), MCGP_STEP_IN_FIT(2), MCGP_STEP_IN_FIT(3), MCGP_STEP_COMMON
                  : "scc");
 }
 template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
 __device__ __forceinline__ void step_commit4(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
 {
-    uint32_t t, mpit, mage;
+    uint32_t t, f, mpit, mage;
     uint64_t ex, ax, dx, cx, yx, az, dz, cz, yz;
-    asm volatile(MCGP_STEP_ENTER
-                 MCGP_STEP_TEST(0, x)
-                 MCGP_STEP_TEST(1, z)
-                 MCGP_STEP_WRITE(0, x)
-                 MCGP_STEP_TEST(2, x)
-                 MCGP_STEP_WRITE(1, z)
-                 MCGP_STEP_TEST(3, z)
-                 MCGP_STEP_WRITE(2, x)
-                 MCGP_STEP_WRITE(3, z)
-                 "s_mov_b64 exec, %[ex]"
+    asm volatile(MCGP_STEP_BODY4(MCGP_STEP_WRITE_RARE)
                  : MCGP_STEP_OUT(0), MCGP_STEP_OUT(1), MCGP_STEP_OUT(2), MCGP_STEP_OUT(3), [cy] "+v"(carry),
-                   MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z
-                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_IN(2), MCGP_STEP_IN(3), MCGP_STEP_COMMON
+                   MCGP_STEP_TEMPS_X MCGP_STEP_TEMPS_Z MCGP_STEP_TEMPS_RARE
+                 : MCGP_STEP_IN(0), MCGP_STEP_IN(1), MCGP_STEP_IN(2), MCGP_STEP_IN(3), MCGP_STEP_COMMON_RARE
                  : "scc");
 }
+#undef MCGP_STEP_COMMON_RARE
 #undef MCGP_STEP_COMMON
-#undef MCGP_STEP_ENTER
+#undef MCGP_STEP_TEMPS_RARE
 #undef MCGP_STEP_TEMPS_Z
 #undef MCGP_STEP_TEMPS_X
+#undef MCGP_STEP_BODY4
+#undef MCGP_STEP_BODY3
+#undef MCGP_STEP_BODY2
+#undef MCGP_STEP_BODY1
+#undef MCGP_STEP_LEAVE
+#undef MCGP_STEP_ENTER
+#undef MCGP_STEP_IN_FIT
 #undef MCGP_STEP_IN
 #undef MCGP_STEP_OUT
-#undef MCGP_STEP_WRITE
+#undef MCGP_STEP_WRITE_RARE
+#undef MCGP_STEP_WRITE_FIT
+#undef MCGP_STEP_WRITE_HEAD
 #undef MCGP_STEP_TEST
 
 // ---- position update under EXEC ----

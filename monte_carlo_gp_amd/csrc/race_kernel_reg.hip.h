@@ -47,6 +47,10 @@
 #ifndef MCGP_TRACE_PASS
 #define MCGP_TRACE_PASS(sim, lap, pass, n_cand)
 #endif
+// ... and of the lap step's rare events, per (simulation, lap, slot): the car stops / retires on this lap (tools/step_rare_stats.py)
+#ifndef MCGP_TRACE_STEP
+#define MCGP_TRACE_STEP(sim, lap, slot, stop, retire)
+#endif
 // Race-interrupting events handled by the wave with lane = car (1) or by every lane for itself (0: the same
 // results; for the host debugging build, whose threads run one at a time).
 #ifndef MCGP_COOPERATIVE_EVENTS
@@ -247,6 +251,11 @@ __host__ __device__ constexpr bool reg_commit_by_selects(int n) { return n == 6 
 // VGPRs).  Everywhere else every instantiation keeps or lowers both (N = 20: 28 -> 0 B, batch 108 -> 88, reference width
 // 192 -> 176); occupancy changes nowhere.
 __host__ __device__ constexpr bool reg_step_by_selects(int n) { return n == 3 || n == 11 || n == 12 || n == 25 || n == 26 || n == 29; }
+// ... and, of the others, the ones whose statement keeps every write on the common path (StepSlotFit, race_isa.hip.h): the
+// ones where jumping over the pit and retirement writes costs some instantiation scratch or a register
+__host__ __device__ constexpr bool reg_step_plain(int n) { return n == 5 || n == 6 || n == 9 || n == 10 || n == 28; }
+// the lap step gathers the word a pit stop leaves for every slot (otherwise the statement fetches it on the laps with a stop)
+__host__ __device__ constexpr bool reg_step_gathers_fit(int n) { return reg_step_by_selects(n) || reg_step_plain(n); }
 // Field sizes whose position update of a field without equal times stays merged by selects instead of written under EXEC
 // (update_positions_distinct; upd_commit*, race_isa.hip.h): the ones where the EXEC form costs some instantiation scratch
 // or registers (select form -> EXEC form: N = 1 56 -> 57 VGPRs, batch 74 -> 75; N = 6 batch 188 -> 208 B of scratch per lane;
@@ -1108,6 +1117,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
         double last, var, base, eff, cdelta, drs;
         uint32_t la;            // byte offset of the driver's LAST row
         uint32_t fit;           // compound and used-set a pit stop on this lap would leave, positioned as in pk
+                                // (reg_step_gathers_fit() only)
     };
     // a car's oIc entry: one mask where the compound sits directly above the driver index
     auto ic_of = [&](uint32_t p) -> uint32_t {
@@ -1121,7 +1131,8 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
     };
     auto load_slot = [&](uint32_t p, uint32_t lut_base) -> SlotIn {
         SlotIn r;
-        r.fit = lds_ld<uint32_t>(((p & k3UsedMask) << 2) + lut_base);
+        if constexpr (reg_step_gathers_fit(N)) r.fit = lds_ld<uint32_t>(((p & k3UsedMask) << 2) + lut_base);
+        else r.fit = 0u;
         const uint32_t id16 = pk_driver16(p);                                     // 16 x driver
         r.la = id16 * (uint32_t)(B / 2) + tid8;                                   // = driver x (B x 8) + tid8
         r.last = lds_ld<double>(G::oLast + r.la);
@@ -1750,7 +1761,9 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                 if constexpr (!kStepBySelects) {
                     // (scalar_*: six v_readfirstlane a lap make its scalar operands scalar)
                     const uint32_t window32 = scalar_u32(pit_window ? ~0u : 0u);
-                    step_lap = StepLap{retire_word, ((uint64_t)window32 << 32) | window32, scalar_f64(pit_loss_lap), scalar_f64(dirty_pen_lap)};
+                    static_assert(k3UsedMask == kStepUsed, "step_commit* indexes the rule row by the used-set bits");
+                    step_lap = StepLap{retire_word, ((uint64_t)window32 << 32) | window32, scalar_f64(pit_loss_lap), scalar_f64(dirty_pen_lap),
+                                       reg_step_plain(N) ? 0u : scalar_u32(lut_base)};
                 }
                 constexpr uint32_t kKeepPit = ~(k3CompMask | k3UsedMask | k3AgeMask), kKeepRet = ~k3AgeMask;    // what of p a stop / a retirement keeps
                 double carry = 0.0;
@@ -1848,7 +1861,8 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                         static_assert(kStepBatch == 4, "step_commit1..4");
                         const int K = N - i0 < kStepBatch ? N - i0 : kStepBatch;      // (a constant once the loop is unrolled)
                         double lt[kStepBatch];
-                        StepSlot ss[kStepBatch];
+                        using Slot = std::conditional_t<reg_step_plain(N), StepSlotFit, StepSlot>;
+                        Slot ss[kStepBatch];
 #pragma unroll
                         for (int j = 0; j < kStepBatch; ++j) {
                             if (j >= K) continue;
@@ -1857,7 +1871,10 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                             const double tire = (double)agef * s.eff;                                   // :319-322 (eff x 2^-16)
                             const double noise = s.var * (double)z[j];                                  // :330 (see below)
                             lt[j] = s.base + tire - fuel_effect + s.cdelta - s.drs + noise;             // :332
-                            ss[j] = StepSlot{s.last, agef, s.pitw, s.fit};
+                            MCGP_TRACE_STEP(local, lap, i0 + j, !(pk[i0 + j] & k3Dnf) && __double2hiint(s.last) >= 0 && pit_window && agef >= s.pitw,
+                                            !(pk[i0 + j] & k3Dnf) && __double2hiint(s.last) < 0);
+                            if constexpr (reg_step_plain(N)) ss[j] = StepSlotFit{{s.last, agef, s.pitw}, s.fit};
+                            else ss[j] = StepSlot{s.last, agef, s.pitw};
                         }
                         if constexpr (N >= 4) if (K == 4) step_commit4<k3Dnf, k3Dirty, 1u << k3AgeShift, kKeepPit, kKeepRet>(&cum[i0], &pk[i0], lt, carry, ss, step_lap);
                         if constexpr (N % 4 == 3) if (K == 3) step_commit3<k3Dnf, k3Dirty, 1u << k3AgeShift, kKeepPit, kKeepRet>(&cum[i0], &pk[i0], lt, carry, ss, step_lap);
@@ -1904,6 +1921,7 @@ __device__ __forceinline__ void reg_simulate(const KParams *__restrict__ P, unsi
                         // pit stop (:450-492): (tyre age + 1) << 16 against the pit word; compound and used-set from
                         // the rule table (pit_rule_word)
                         const bool pit = run && pit_window && agef >= s.pitw;       // age + 1 > threshold (both fields << 16)
+                        MCGP_TRACE_STEP(local, lap, i, pit, active && dnf_hit);
                         const uint32_t p_pit = (p & ~(k3CompMask | k3UsedMask | k3AgeMask)) | s.fit;
                         uint32_t p_run = pit ? p_pit : p + (1u << k3AgeShift);
                         uint32_t p_ret = (p & ~k3AgeMask) | retire_word;

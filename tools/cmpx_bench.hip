@@ -19,9 +19,18 @@
 //   TE the same under EXEC (race_isa.hip.h ovt_threshold_x): threshold zeroed, word read, v_cmpx, then ceil, convert, min and the row
 //      advance in place on the candidates' lanes; EXEC saved and restored per pair.  TE4: four pairs to a statement (EXEC saved once
 //      per four).  TE4Z: TE4 with two thresholds zeroed by one v_mov_b64.  (per pair; 5 pairs in 32 are candidates, lane by lane)
+//   LF.. the lap step's commit of four slots with the rare writes behind a branch (race_isa.hip.h step_commit*): LF the sequence
+//      without a branch (rule-word fetch for every slot, pit and retirement writes always issued), LFS a branch per slot over
+//      the pit region (fetch, wait and both writes inside), LFB one branch per batch of four over all four pit regions, LFR a
+//      branch per slot over the retirement write, LFSR / LFBR both; at r0 / r13 / r100: 0 %, 13 % and 100 % of slot visits have a
+//      stopping lane, 4.7 % a retiring one (tools/cmpx_bench_gen.py says how).  The forms of one rate print equal check values.
+//      tools/cmpx_bench LF runs these alone (any argument: the cases whose name starts with it).  Their bodies are generated
+//      where the benchmark is built (python3 tools/cmpx_bench_gen.py step > tools/cmpx_step_bodies.inc); without that file
+//      the benchmark builds without them
 // each as layers of 8 independent comparators (the sorting network) and as a chain of 15 dependent ones (a bubble pass).
 // The loop bodies are written on fixed registers (v[10:41] = 16 times, v50..v65 = 16 payloads): inline assembly cannot
 // name the halves of a 64-bit operand, which form B needs.
+//   python3 tools/cmpx_bench_gen.py step > tools/cmpx_step_bodies.inc
 //   hipcc --offload-arch=gfx950 -O3 -o tools/cmpx_bench tools/cmpx_bench.hip && tools/cmpx_bench
 #include <hip/hip_runtime.h>
 
@@ -33,11 +42,16 @@
 
 // the kernels: tools/cmpx_bench_gen.py > tools/cmpx_bodies.inc
 #include "cmpx_bodies.inc"
+#if __has_include("cmpx_step_bodies.inc")
+#include "cmpx_step_bodies.inc"
+#define CMPX_STEP_FORMS 1
+#endif
 
 struct Case { const char *name; void (*fn)(uint32_t, double *); int comparators; };
 
-int main()
+int main(int argc, char **argv)
 {
+    const std::string only = argc > 1 ? argv[1] : "";
     const Case cases[] = {{"A layers (cmp, min, max, 2 cndmask + 3 moves)", k_A_layer, 16}, {"A0 layers (the 3 moves alone)", k_A0_layer, 16},
                           {"B layers (cmpx, 3 swaps, restore)", k_B_layer, 16}, {"C layers (cmp, s_and exec, 3 swaps, restore)", k_C_layer, 16},
                           {"D layers (cmpx, payload swap, restore, min, max + 2 moves)", k_D_layer, 16},
@@ -53,7 +67,17 @@ int main()
                           {"TS (overtake thresholds of 19 pairs by selects; per pair)", k_TS_chain, 19},
                           {"TE (overtake thresholds under EXEC, a pair to a statement; per pair)", k_TE_chain, 19},
                           {"TE4 (the same, four pairs to a statement; per pair)", k_TE4_chain, 19},
-                          {"TE4Z (TE4, thresholds zeroed two at a time; per pair)", k_TE4Z_chain, 19}};
+                          {"TE4Z (TE4, thresholds zeroed two at a time; per pair)", k_TE4Z_chain, 19},
+#ifdef CMPX_STEP_FORMS
+#define STEPF(form, what)                                                                                               \
+    {#form " r0 (" what "; no stop; per slot)", k_##form##_r0_chain, 4}, {#form " r13 (" what "; 13 % stops; per slot)", k_##form##_r13_chain, 4},   \
+    {#form " r100 (" what "; 100 % stops; per slot)", k_##form##_r100_chain, 4}
+                          STEPF(LF, "no branch"), STEPF(LFS, "pit branch per slot"), STEPF(LFB, "pit branch per batch"),
+                          STEPF(LFR, "retirement branch"), STEPF(LFSR, "pit per slot + retirement"),
+                          STEPF(LFBR, "pit per batch + retirement"),
+#undef STEPF
+#endif
+    };
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
@@ -65,6 +89,7 @@ int main()
     const uint32_t iters = 40000;
     for (int W = 2; W <= 4; ++W) {
         for (const Case &c : cases) {
+            if (std::string(c.name).compare(0, only.size(), only) != 0) continue;
             // W blocks of 256 threads per CU (LDS reservation keeps it at W)
             const size_t lds = 160 * 1024 / W - 1024;
             CHECK(hipFuncSetAttribute((const void *)c.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -80,7 +105,7 @@ int main()
             CHECK(hipMemcpy(h, out, sizeof(h), hipMemcpyDeviceToHost));
             for (double x : h) sum += x;
             const double cyc = 1024.0 * 2.4e9 * ms * 1e-3 / ((double)cus * 4 * W * iters * c.comparators);
-            printf("waves/SIMD %d  %-48s %.2f cycles per comparator per SIMD   (check %.3f %.3f, all lanes %.3f)\n", W, c.name, cyc, h[0], h[5], sum);
+            printf("waves/SIMD %d  %-56s %.2f cycles per comparator per SIMD   (check %.3f %.3f, all lanes %.3f)\n", W, c.name, cyc, h[0], h[5], sum);
         }
     }
     return 0;

@@ -98,6 +98,95 @@ def step_setup():
             'v_or_b32 v105, v105, v141']
     return ins
 
+# The lap step's rare writes behind a branch (race_isa.hip.h step_commit*): a chain of the four slots of LE in which stops and
+# retirements come as they do in a race -- on few iterations, clustered by iteration, in lanes that change.  The word a stop leaves
+# is fetched from an eight-entry rule row (LDS address 64, its base in s23, indexed by the used-set bits of the old pk word) as
+# the kernel's load_slot does.  All forms read the same inputs and leave the same check value:
+#   LF   today's sequence: the fetch for every slot ahead of the statement, both pit writes under the c mask, the retirement
+#        write under the d mask, whether or not a lane of the wave has either
+#   LFS  per slot: s_and_b64 c, c, win sets SCC, s_cbranch_scc0 jumps over the pit region (address, fetch, wait, both writes)
+#   LFB  per batch: the four c masks (in pairs of their own, s[50:57]) OR-ed, one branch over the four pit regions, which sit at
+#        the end of the statement (a stopping lane is in no other write of its slot after the lap time's addition)
+#   LFR  per slot: s_and_b64 exec, ex, d sets SCC, s_cbranch_scc0 jumps over the retirement write;  LFSR / LFBR: with S / B
+# Rates (the share of slot visits with a stopping lane): r0 the window is closed; r13 every lane stops each 23rd iteration, in three
+# groups of lanes an iteration apart (3 / 23); r100 every fourth iteration, in four groups (every iteration has a stop in a
+# quarter of the lanes).  Retirements: on every 16th iteration slots 1..3 retire in a sixteenth of the lanes (3 / 64 = 4.7 % of
+# slot visits); the DNF bit is cleared at the end of the iteration so that they can retire again.  The lanes that retire never
+# stop (their pit word is the largest age), so that a retirement does not shift the phase of a stop.
+# Registers beyond step_setup's: rule-row addresses v[142:145], the sign-free high words of LAST v146..v148 (slots 1..3), this
+# iteration's sign bit for the retiring lanes v149, their lanes' 0x80000000 in v141 (kept: the F forms do not use v141), s58 scratch.
+def stepf_addr(i, dst): return [f'v_lshlrev_b32 {dst}, 2, {p(i)}', f'v_and_or_b32 {dst}, {dst}, 28, s23']
+def stepf_pit(i, c, fetch):    # the pit region of slot i under its c mask
+    ins = [f's_and_b64 exec, s[20:21], {c}']
+    if fetch: ins += stepf_addr(i, 'v140') + [f'ds_read_b32 v{132 + i}, v140']
+    ins += [f'v_add_f64 {t(i)}, {t(i)}, s[24:25]']
+    if fetch: ins += ['s_waitcnt lgkmcnt(0)']
+    return ins + [f'v_and_or_b32 {p(i)}, {p(i)}, s32, v{132 + i}']
+def stepf_write(i, g, form):
+    a, d, c, y = (f's[{g + 2 * k}:{g + 2 * k + 1}]' for k in range(4))
+    S, B, R = 'S' in form, 'B' in form, 'R' in form
+    if B: c = f's[{50 + 2 * i}:{51 + 2 * i}]'
+    ins = [f's_and_b64 exec, s[20:21], {y}', f'v_add_f64 {lt(i)}, {lt(i)}, s[26:27]', f'v_max_f64 {lt(i)}, |v[138:139]|, {lt(i)}',
+           f's_and_b64 exec, s[20:21], {a}', f'v_mov_b64 v[138:139], {last(i)}',
+           f's_and_b64 {d}, {a}, {d}', f's_xor_b64 {a}, {a}, {d}']
+    if not (S or B):     # today's order (MCGP_STEP_WRITE of the parent)
+        ins += [f's_and_b64 {c}, {c}, {a}', f's_and_b64 {c}, {c}, s[30:31]', f's_and_b64 exec, s[20:21], {a}', f'v_add_f64 {t(i)}, {t(i)}, {lt(i)}',
+                f's_xor_b64 {a}, {a}, {c}'] + stepf_pit(i, c, False)
+    else:                # the mask's last AND directly ahead of the branch: every scalar instruction in between would set SCC anew
+        ins += [f's_and_b64 exec, s[20:21], {a}', f'v_add_f64 {t(i)}, {t(i)}, {lt(i)}', f's_and_b64 {c}, {c}, {a}', f's_and_b64 {c}, {c}, s[30:31]']
+        if S: ins += ['s_cbranch_scc0 2f', f's_xor_b64 {a}, {a}, {c}'] + stepf_pit(i, c, True) + ['2:']
+        else: ins += [f's_xor_b64 {a}, {a}, {c}']
+    ins += [f's_and_b64 exec, s[20:21], {a}', f'v_add_u32 {p(i)}, 0x10000, {p(i)}', f's_and_b64 exec, s[20:21], {d}']
+    if R: ins += ['s_cbranch_scc0 3f']
+    ins += [f'v_and_or_b32 {p(i)}, {p(i)}, s33, v136']
+    if R: ins += ['3:']
+    return ins
+def stepf_test(i, g, form):
+    ins = step_test(i, g)
+    if 'B' in form: ins[5] = f'v_cmp_ge_u32 s[{50 + 2 * i}:{51 + 2 * i}], v{124 + i}, v{128 + i}'
+    return ins
+def stepf_body(form):
+    # this iteration's retirements: the sign of LAST in slots 1..3, in the retiring lanes, on every 16th iteration
+    ins = ['s_and_b32 s58, s22, 15', 's_cmp_eq_u32 s58, 7', 's_cselect_b32 s58, -1, 0', 'v_and_b32 v149, s58, v141']
+    for i in range(1, 4): ins += [f'v_or_b32 v{101 + 2 * i}, v{145 + i}, v149']
+    ins += ['v_mov_b32 v138, 0', 'v_mov_b32 v139, 0']
+    if not ('S' in form or 'B' in form):
+        for i in range(4): ins += stepf_addr(i, f'v{142 + i}') + [f'ds_read_b32 v{132 + i}, v{142 + i}']
+    for i in range(4):
+        ins += [f'v_add_f64 {lt(i)}, v[{108 + 2 * i}:{109 + 2 * i}], 0.5', f'v_and_b32 v{124 + i}, 0x7ff0000, {p(i)}']
+    if not ('S' in form or 'B' in form): ins += ['s_waitcnt lgkmcnt(0)']
+    ins += stepf_test(0, 34, form) + stepf_test(1, 42, form) + stepf_write(0, 34, form) + stepf_test(2, 34, form) + stepf_write(1, 42, form)
+    ins += stepf_test(3, 42, form) + stepf_write(2, 34, form) + stepf_write(3, 42, form)
+    if 'B' in form:
+        ins += ['s_or_b64 s[34:35], s[50:51], s[52:53]', 's_or_b64 s[36:37], s[54:55], s[56:57]', 's_or_b64 s[34:35], s[34:35], s[36:37]',
+                's_cbranch_scc0 2f']
+        for i in range(4): ins += stepf_pit(i, f's[{50 + 2 * i}:{51 + 2 * i}]', True)
+        ins += ['2:']
+    ins += ['s_mov_b64 exec, s[20:21]']
+    for i in range(4): ins += [f'v_and_b32 {p(i)}, 0xfffffdff, {p(i)}']
+    return ins + [f'v_add_f64 {t(12)}, {t(12)}, v[138:139]', f'v_add_f64 {t(12)}, {t(12)}, {lt(3)}']
+def stepf_setup(rate):
+    period, groups = {'r0': (23, 3), 'r13': (23, 3), 'r100': (4, 4)}[rate]
+    ins = ['v_mov_b32 v136, 0x70200', 's_mov_b32 s24, 0', 's_mov_b32 s25, 0x40340000', 's_mov_b32 s26, 0', 's_mov_b32 s27, 0x3fe00000',
+           f's_mov_b64 s[30:31], {0 if rate == "r0" else -1}', 's_mov_b32 s32, 0xf800e3f8', 's_mov_b32 s33, 0xf800ffff', 's_mov_b32 s23, 64',
+           'v_mov_b32 v140, 0']
+    for j in range(8):   # the rule row: a compound by entry, the entry's own used set with one more bit
+        ins += [f'v_mov_b32 v142, 0x{(1 + j % 3) << 10 | j | 1 << j % 3:x}', f'ds_write_b32 v140, v142 offset:{64 + 4 * j}']
+    ins += ['s_waitcnt lgkmcnt(0)',
+            # the retiring lanes: lane & 15 == 5
+            'v_and_b32 v140, 15, v70', 'v_cmp_eq_u32 vcc, 5, v140', 'v_mov_b32 v141, 0x80000000', 'v_mov_b32 v143, 0x7ff0000', 's_nop 1',
+            'v_cndmask_b32 v141, 0, v141, vcc',
+            # the lane's group: its age at the start, so that the groups stop an iteration apart
+            f'v_mov_b32 v140, 0x{(1 << 32) // groups + 1:x}', 'v_mul_hi_u32 v142, v70, v140', f'v_mul_u32_u24 v142, {groups}, v142',
+            'v_sub_u32 v142, v70, v142', 'v_lshlrev_b32 v142, 16, v142']
+    for i in range(4):   # dirty flag by lane and slot, the start age, the pit word (the largest age in the retiring lanes)
+        ins += [f'v_lshrrev_b32 v140, {i}, v70', 'v_and_b32 v140, 1, v140', 'v_lshlrev_b32 v140, 13, v140', f'v_or_b32 {p(i)}, {i << 4}, v140',
+                f'v_or_b32 {p(i)}, {p(i)}, v142', f'v_mov_b32 v140, 0x{(period - 1) << 16:x}', f'v_cndmask_b32 v{128 + i}, v140, v143, vcc',
+                f'v_mov_b32 v140, {90 + i}', f'v_cvt_f64_u32 {last(i)}, v140',
+                f'v_mov_b32 v140, {88 + i}', f'v_cvt_f64_u32 v[{108 + 2 * i}:{109 + 2 * i}], v140']
+    for i in range(1, 4): ins += [f'v_mov_b32 v{145 + i}, v{101 + 2 * i}']
+    return ins
+
 # The position update of one slot (race_kernel_reg.hip.h update_positions_reg<N, true>; race_isa.hip.h upd_commit*): slot i has
 # its time in t(i) and its pk word in p(i); leader in v[100:101], prev in v[102:103], the two gaps in v[104:107]; the lanes that
 # have not met a running car in s[24:25], the dirty-air threshold in s[26:27] (v[114:115] for the select form's VOPC compare), the
@@ -201,11 +290,18 @@ def thr_kernel(form):
 
 clob = ','.join(f'"v{i}"' for i in list(range(10, 42)) + list(range(50, 66)) + list(range(70, 76))) + ',"vcc","s20","s21","s22","memory"'
 step_clob = ','.join(f'"v{i}"' for i in range(76, 160)) + ',' + ','.join(f'"s{i}"' for i in range(23, 50)) + ','
+stepf_clob = step_clob + ','.join(f'"s{i}"' for i in range(50, 60)) + ','
+# `tools/cmpx_bench_gen.py step` emits the LF.. forms alone, for tools/cmpx_step_bodies.inc (generated where the benchmark is
+# built, not kept in the repository: eighteen kernels of some 350 lines)
+import sys
+STEPF = tuple((f, r) for f in ('LF', 'LFS', 'LFB', 'LFR', 'LFSR', 'LFBR') for r in ('r0', 'r13', 'r100'))
+STEP_ONLY = sys.argv[1:] == ['step']
 commit_clob = ','.join(f'"v{i}"' for i in (76, 77) + tuple(range(80, 96))) + ',"s24","s25","s26","s27","s28","s29",'
-for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE', 'US', 'UE', 'UF'):
+for form in STEPF if STEP_ONLY else ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE', 'US', 'UE', 'UF'):
+    form, rate = form if isinstance(form, tuple) else (form, None)
     commit = form in 'SE'
     upd = form[0] == 'U'
-    step = form in ('LS', 'LE') or upd      # (a body of its own on the step forms' registers)
+    step = form in ('LS', 'LE') or upd or rate is not None      # (a body of its own on the step forms' registers)
     for shape in ('chain',) if commit or step else ('layer', 'chain'):
         ins = ['v_mbcnt_lo_u32_b32 v70, -1, 0', 'v_mbcnt_hi_u32_b32 v70, -1, v70', 'v_mov_b32 v72, 0', 'v_mov_b32 v73, 0', 'v_mov_b32 v74, 0']
         for i in range(16):
@@ -217,10 +313,12 @@ for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE', 'US', 'UE', 'UF'):
             ins += ['s_mov_b32 s24, 0x9999999a', 's_mov_b32 s25, 0xbfb99999', 's_mov_b32 s26, 0x33333333', 's_mov_b32 s27, 0x3fd33333',
                     's_mov_b64 s[28:29], 0']
         if upd: ins += upd_setup()
+        elif rate: ins += stepf_setup(rate)
         elif step: ins += step_setup()
         ins += ['s_mov_b64 s[20:21], exec', 's_mov_b32 s22, %0', '1:']
         pairs = [(i, i + 1) for i in range(15)] if shape == 'chain' else [(i, i + 8) for i in range(8)] + [(2 * i, 2 * i + 1) for i in range(8)]
         if upd: ins += upd_body(form)
+        elif rate: ins += stepf_body(form)
         elif step: ins += step_body(form)
         for a, b in [] if step else pairs:
             ins += comparator(form, a, b)
@@ -232,9 +330,9 @@ for form in ('A', 'A0', 'B', 'C', 'D', 'S', 'E', 'LS', 'LE', 'US', 'UE', 'UF'):
         ins += ['v_mov_b32 v75, v50'] + [f'v_mad_u32_u24 v75, v75, 31, {p(i)}' for i in range(1, 16)]
         ins += ['v_cvt_f64_u32 v[72:73], v75', f'v_add_f64 v[72:73], v[72:73], {t(3)}', f'v_add_f64 v[72:73], v[72:73], {t(12)}',
                 'v_lshlrev_b32 v70, 3, v70', 'global_store_dwordx2 v70, v[72:73], %1', 's_waitcnt vmcnt(0)']
-        print(f'__global__ void __launch_bounds__(256) k_{form}_{shape}(uint32_t iters, double *out)\n{{\n    asm volatile(')
+        print(f'__global__ void __launch_bounds__(256) k_{form}{"_" + rate if rate else ""}_{shape}(uint32_t iters, double *out)\n{{\n    asm volatile(')
         for x in ins:
             print(f'        "{x}\\n\\t"')
-        print(f'        : : "s"(iters), "s"(out) : {commit_clob if commit else step_clob if step else ""}{clob});\n}}')
-for form in ('TS', 'TE', 'TE4', 'TE4Z'):
+        print(f'        : : "s"(iters), "s"(out) : {commit_clob if commit else stepf_clob if rate else step_clob if step else ""}{clob});\n}}')
+for form in () if STEP_ONLY else ('TS', 'TE', 'TE4', 'TE4Z'):
     thr_kernel(form)

@@ -23,6 +23,19 @@ unsigned long long emu_trace_sims = 0, emu_trace_laps = 0;
         if (emu_trace_buf && (unsigned long long)(sim) < emu_trace_sims && (unsigned long long)(lap) < emu_trace_laps) \
             emu_trace_buf[((unsigned long long)(sim) * emu_trace_laps + (lap)) * 3 + (pass)] = (unsigned char)((n_cand) + 1); \
     } while (0)
+// per-(simulation, lap, slot) trace of the lap step's rare events (tools/step_rare_stats.py): emu_step_buf[sim][lap][slot] =
+// 1 (the car in that slot stops on this lap) | 2 (it retires on this lap); 32 slots per lap
+extern "C" unsigned char *emu_step_buf;
+extern "C" unsigned long long emu_step_sims, emu_step_laps;
+#if !defined(EMU_PART) || EMU_PART == 0
+unsigned char *emu_step_buf = nullptr;
+unsigned long long emu_step_sims = 0, emu_step_laps = 0;
+#endif
+#define MCGP_TRACE_STEP(sim, lap, slot, stop, retire)                                                        \
+    do {                                                                                                     \
+        if (emu_step_buf && (unsigned long long)(sim) < emu_step_sims && (unsigned long long)(lap) < emu_step_laps) \
+            emu_step_buf[((unsigned long long)(sim) * emu_step_laps + (lap)) * 32 + (slot)] = (unsigned char)(((stop) ? 1 : 0) | ((retire) ? 2 : 0)); \
+    } while (0)
 #define MCGP_COOPERATIVE_EVENTS 0        // threads run one at a time here: every lane handles its own event
 #include "race_isa_host.h"
 

@@ -152,15 +152,24 @@ inline bool ovt_lane_hit(uint64_t acc) { return acc != 0u; }
 // lap-step commits (reference :179-223, :450-492): the portable body of one slot, slots in order
 struct StepSlot {
     double last;
-    uint32_t agef, pitw, fit;
+    uint32_t agef, pitw;
 };
+struct StepSlotFit : StepSlot {
+    uint32_t fit;
+};
+inline uint32_t step_fit(const StepSlot &, uint32_t p, uint32_t lut);
+inline uint32_t step_fit(const StepSlotFit &s, uint32_t, uint32_t) { return s.fit; }
 struct StepLap {
     uint32_t retire_word;
     uint64_t window;
     double pit_loss, pen;
+    uint32_t lut;
 };
-template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
-inline void step_commit1(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+constexpr uint32_t kStepUsed = 7u;
+// fetched on a stop only, as on the device
+inline uint32_t step_fit(const StepSlot &, uint32_t p, uint32_t lut) { return lds_ld<uint32_t>(((p & kStepUsed) << 2) + lut); }
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET, class Slot>
+inline void step_commit1(double *cum, uint32_t *pk, double *lt, double &carry, const Slot *s, const StepLap &c)
 {
     const uint32_t p = pk[0];
     const bool active = !(p & DNF);
@@ -173,24 +182,24 @@ inline void step_commit1(double *cum, uint32_t *pk, double *lt, double &carry, c
     if (active) carry = s[0].last;
     if (run) cum[0] = cum[0] + lt[0];
     if (pit) cum[0] = cum[0] + c.pit_loss;
-    if (pit) pk[0] = (p & KEEP_PIT) | s[0].fit;
+    if (pit) pk[0] = (p & KEEP_PIT) | step_fit(s[0], p, c.lut);
     else if (run) pk[0] = p + AGE1;
     else if (active) pk[0] = (p & KEEP_RET) | c.retire_word;
 }
-template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
-inline void step_commit2(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET, class Slot>
+inline void step_commit2(double *cum, uint32_t *pk, double *lt, double &carry, const Slot *s, const StepLap &c)
 {
     step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum, pk, lt, carry, s, c);
     step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum + 1, pk + 1, lt + 1, carry, s + 1, c);
 }
-template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
-inline void step_commit3(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET, class Slot>
+inline void step_commit3(double *cum, uint32_t *pk, double *lt, double &carry, const Slot *s, const StepLap &c)
 {
     step_commit2<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum, pk, lt, carry, s, c);
     step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum + 2, pk + 2, lt + 2, carry, s + 2, c);
 }
-template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET>
-inline void step_commit4(double *cum, uint32_t *pk, double *lt, double &carry, const StepSlot *s, const StepLap &c)
+template <uint32_t DNF, uint32_t DIRTY, uint32_t AGE1, uint32_t KEEP_PIT, uint32_t KEEP_RET, class Slot>
+inline void step_commit4(double *cum, uint32_t *pk, double *lt, double &carry, const Slot *s, const StepLap &c)
 {
     step_commit3<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum, pk, lt, carry, s, c);
     step_commit1<DNF, DIRTY, AGE1, KEEP_PIT, KEEP_RET>(cum + 3, pk + 3, lt + 3, carry, s + 3, c);
