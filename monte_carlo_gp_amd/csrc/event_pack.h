@@ -1,5 +1,5 @@
 // event_pack.h -- host side of mcgp_run_events: a caller's mcgp_lap_event[] (include/mcgp.h) checked against the
-// documented limits and packed into what race_events_kernel reads (one byte per scenario and lap, events.hip.h).
+// documented limits and packed into what race_scenario_kernel reads (one byte per scenario and lap, events.hip.h).
 // Plain C++, no device code, beside plan_pack.h and penalty_pack.h and for the same reason: mcgp_hip.hip includes it for
 // the C ABI, and the host debugging build of the generic kernels (tools/emu/emu_generic.cpp) includes the same text.
 #pragma once

@@ -26,7 +26,7 @@
 #include "penalty_pack.h"
 #include "pace_pack.h"
 #include "event_pack.h"
-#include "combined.hip.h"
+#include "scenario.hip.h"
 #include "champ_pack.h"
 
 #define MCGP_FE_FN __host__ __device__ static inline
@@ -953,7 +953,49 @@ struct ScenarioChunk {
     const mcgp::StopLap *sl;
     unsigned long long *hist;
     uint8_t *stage;                         // [S][m][n] bytes: every driver's finishing position
+    // the tables of the kind's rule sets, and what they stage beside the bytes; NULL where the kind has none or the
+    // output is not wanted (ScenarioKind::regions lays them out)
+    const mcgp::PenaltyScenario *pn;
+    const mcgp::PenaltyLap *nl;
+    const uint8_t *el;
+    const mcgp::PaceScenario *ps;
+    const mcgp::PaceLap *pl;
+    const double *sec;
+    uint32_t *evs;                          // [S][m] packed event counts
+    uint16_t *car;                          // [S][m][n] laps carried
 };
+
+// Grid width of a counting kernel over m simulations in blocks of `block` threads: the tiles, but no more blocks than
+// the device holds at once shared out over the grid's `rows` rows (and layers), and at least one.
+uint32_t count_grid_x(uint64_t m, uint32_t block, uint64_t grid_cap, uint64_t rows)
+{
+    const uint64_t tiles = (m + block - 1) / block;
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / rows));
+}
+
+// The counting kernels of the rule sets over a chunk's staging, one grid row per scenario; mcgp_run_combined runs all
+// three, each on the staging in its own layout.  delta and the kind's own segment are NULL for what is not wanted.
+void count_penalties(const ScenarioChunk &l, uint32_t n, uint64_t grid_cap, unsigned long long *delta, unsigned long long *fate)
+{
+    hipLaunchKernelGGL(mcgp::penalties_count, dim3(count_grid_x(l.m, mcgp::kPenaltyCountBlock, grid_cap, l.S), l.S),
+                       dim3(mcgp::kPenaltyCountBlock), 0, nullptr, l.stage, l.m, n, delta, fate);
+}
+
+void count_events(const ScenarioChunk &l, uint32_t n, uint32_t L, uint64_t grid_cap, unsigned long long *delta,
+                  unsigned long long *events)
+{
+    hipLaunchKernelGGL(mcgp::events_count, dim3(count_grid_x(l.m, mcgp::kEventsCountBlock, grid_cap, l.S), l.S),
+                       dim3(mcgp::kEventsCountBlock), 0, nullptr, l.stage, l.evs, l.m, n, L, delta, events);
+}
+
+// grid layers: the deltas (a layer that returns at once when delta is NULL), then (carried wanted) one per driver
+void count_paces(const ScenarioChunk &l, uint32_t n, uint32_t L, uint64_t grid_cap, unsigned long long *delta,
+                 unsigned long long *carried)
+{
+    const uint32_t gz = carried ? 1u + n : 1u;
+    hipLaunchKernelGGL(mcgp::paces_count, dim3(count_grid_x(l.m, mcgp::kPacesCountBlock, grid_cap, (uint64_t)l.S * gz), l.S, gz),
+                       dim3(mcgp::kPacesCountBlock), 0, nullptr, l.stage, l.car, l.ps, l.m, n, L, delta, carried);
+}
 
 // One item table of a scenario call beside the plans, one count per scenario: the arguments, their names and the check of
 // the counts before anything is packed.
@@ -976,14 +1018,16 @@ struct ScenarioOutput {
 // own; run_scenarios has the rest.
 struct ScenarioKind {
     const char *what;                       // the call in check_deviates_32's message
-    const char *geo_name, *kernel_name;     // generic_geometry's and note_launch's name of the race kernel
-    KernelFn geo_fn;                        // the race kernel (for its register count)
+    // generic_geometry's and note_launch's name of the race kernel.  These are the documented names of the calls
+    // (include/mcgp.h: mcgp_last_kernel_name), not of symbols: every kind runs an instantiation of race_scenario_kernel
+    const char *geo_name, *kernel_name;
+    uint32_t rules;                         // the kind's rule sets (mcgp::kRule*): the instantiation that runs
     std::vector<ScenarioTable> tables;                                   // the kind's own input tables, checked in this order
     std::function<std::string(int first_lap, bool resumed)> pack;        // their items, behind pack_scenarios
     size_t sim_bytes = 0;                                                // staged per (scenario, simulation)
     uint8_t pos_mask = 0xFF;                                             // the position in a staged byte
-    std::function<void(Layout &, uint64_t chunk)> regions;               // its regions of the workspace
-    std::function<void(const ScenarioChunk &)> race;                     // launches the race kernel
+    // its regions of the workspace: the tables and staging of its rule sets, into the chunk's pointers
+    std::function<void(Layout &, ScenarioChunk &, uint64_t chunk)> regions;
     // launches the counting kernels (run when delta or one of the kind's outputs is wanted): delta and extra[i], the
     // device segment of outputs[i], are NULL for what is not wanted
     std::function<void(const ScenarioChunk &, uint64_t grid_cap, unsigned long long *delta, unsigned long long *const *extra)>
@@ -1061,7 +1105,7 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
         ws.add(&l.st, 1, &st);
         ws.add(&l.sc, S, scen.data());
         ws.add(&l.sl, stop_laps.size(), stop_laps.data());
-        if (k.regions) k.regions(ws, chunk);
+        if (k.regions) k.regions(ws, l, chunk);
         ws.counts(segs);
         const int r = ws.commit(c.work);
         if (r != MCGP_OK) return r;
@@ -1075,10 +1119,14 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
         }
         const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
         const bool count_delta = delta_out && S > 1;
-        return staged_run(c, k.geo_fn, k.geo_name, k.kernel_name, n, S, n_sims, chunk, ws, counts,
+        // the instantiation that runs is also the one whose register count shapes the launch
+        const mcgp::ScenarioKernel kernel = mcgp::scenario_kernel(k.rules, state != nullptr);
+        return staged_run(c, reinterpret_cast<KernelFn>(kernel), k.geo_name, k.kernel_name, n, S, n_sims, chunk, ws, counts,
                           [&](uint64_t done, uint64_t m, uint32_t gx, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
             l.gx = gx, l.block = block, l.lds = lds, l.n_batches = n_batches, l.m = m, l.first_sim = sim_offset + done;
-            k.race(l);
+            hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, l.pn, l.nl, l.el,
+                               l.ps, l.pl, l.sec, l.m, l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage,
+                               l.evs, l.car, l.n_batches);
             HIP_TRY(hipGetLastError());
             if (count_delta || want_extra) {
                 std::vector<unsigned long long *> extra;
@@ -2128,19 +2176,13 @@ int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, con
                             const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
                             int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint8_t *orders_out)
 {
-    const auto kernel = state ? &mcgp::race_strategy_kernel<true> : &mcgp::race_strategy_kernel<false>;
-    ScenarioKind k = {"strategies run", "strategy", "mcgp::race_strategy_kernel", reinterpret_cast<KernelFn>(kernel)};
+    ScenarioKind k = {"strategies run", "strategy", "mcgp::race_strategy_kernel", 0u};
     k.sim_bytes = n;                        // a position byte per driver
-    k.race = [&](const ScenarioChunk &l) {
-        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, l.m, l.first_sim,
-                           (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, l.n_batches);
-    };
     // every scenario but the first against the first: S - 1 grid rows (never run for one scenario)
     k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *) {
-        const uint64_t tiles = (l.m + mcgp::kStrategyCountBlock - 1) / mcgp::kStrategyCountBlock;
-        const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / (l.S - 1)));
-        hipLaunchKernelGGL(mcgp::strategy_count_deltas, dim3((uint32_t)gxc, l.S - 1), dim3(mcgp::kStrategyCountBlock), 0,
-                           nullptr, l.stage, l.m, n, d_delta);
+        hipLaunchKernelGGL(mcgp::strategy_count_deltas,
+                           dim3(count_grid_x(l.m, mcgp::kStrategyCountBlock, grid_cap, l.S - 1), l.S - 1),
+                           dim3(mcgp::kStrategyCountBlock), 0, nullptr, l.stage, l.m, n, d_delta);
     };
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
                          hist_out, delta_out, orders_out, k);
@@ -2152,12 +2194,9 @@ int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, cons
                            uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                            uint64_t *delta_out, uint64_t *fate_out, uint8_t *orders_out)
 {
-    const auto kernel = state ? &mcgp::race_penalties_kernel<true> : &mcgp::race_penalties_kernel<false>;
     std::vector<mcgp::PenaltyScenario> pens;
     std::vector<mcgp::PenaltyLap> pen_laps;
-    const mcgp::PenaltyScenario *d_pn = nullptr;
-    const mcgp::PenaltyLap *d_pl = nullptr;
-    ScenarioKind k = {"penalties run", "penalties", "mcgp::race_penalties_kernel", reinterpret_cast<KernelFn>(kernel)};
+    ScenarioKind k = {"penalties run", "penalties", "mcgp::race_penalties_kernel", mcgp::kRulePenalties};
     k.tables = {{"penalty_count", "penalties", penalty_count, penalties, [&](uint64_t *n_pens) {
         return mcgp::check_penalty_counts(n_scenarios, penalty_count, n_pens);
     }}};
@@ -2167,20 +2206,12 @@ int32_t mcgp_run_penalties(const mcgp_config *cfg, const mcgp_drivers *drv, cons
     };
     k.sim_bytes = n;                        // a byte per driver: its position, and the fate of its penalty above it
     k.pos_mask = mcgp::kStagePosMask;
-    k.regions = [&](Layout &ws, uint64_t) {
-        ws.add(&d_pn, n_scenarios, pens.data());
-        ws.add(&d_pl, pen_laps.size(), pen_laps.data());
-    };
-    k.race = [&](const ScenarioChunk &l) {
-        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_pn, d_pl, l.m,
-                           l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, l.n_batches);
+    k.regions = [&](Layout &ws, ScenarioChunk &l, uint64_t) {
+        ws.add(&l.pn, n_scenarios, pens.data());
+        ws.add(&l.nl, pen_laps.size(), pen_laps.data());
     };
     k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
-        unsigned long long *d_fate = extra[0];
-        const uint64_t tiles = (l.m + mcgp::kPenaltyCountBlock - 1) / mcgp::kPenaltyCountBlock;
-        const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
-        hipLaunchKernelGGL(mcgp::penalties_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kPenaltyCountBlock), 0, nullptr,
-                           l.stage, l.m, n, d_delta, d_fate);
+        count_penalties(l, n, grid_cap, d_delta, extra[0]);
     };
     // fate [S][n][4]; column 0 (no SERVE_AT_STOP penalty) is, like delta's centre bin, what the others leave of n_sims
     k.outputs = {fate_output(fate_out)};
@@ -2194,11 +2225,8 @@ int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const d
                         uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                         uint64_t *delta_out, uint64_t *events_out, uint8_t *orders_out)
 {
-    const auto kernel = state ? &mcgp::race_events_kernel<true> : &mcgp::race_events_kernel<false>;
     std::vector<uint8_t> event_laps;
-    const uint8_t *d_el = nullptr;
-    uint32_t *d_evs = nullptr;              // [S][m] packed event counts of a chunk's simulations
-    ScenarioKind k = {"events run", "events", "mcgp::race_events_kernel", reinterpret_cast<KernelFn>(kernel)};
+    ScenarioKind k = {"events run", "events", "mcgp::race_events_kernel", mcgp::kRuleEvents};
     k.tables = {{"event_count", "events", event_count, events, [&](uint64_t *n_events) {
         return mcgp::check_event_counts(n_scenarios, event_count, n_events);
     }}};
@@ -2207,20 +2235,12 @@ int32_t mcgp_run_events(const mcgp_config *cfg, const mcgp_drivers *drv, const d
     };
     // positions and event counts of a chunk share the strategy call's budget: n + 4 bytes per scenario and simulation
     k.sim_bytes = (size_t)n + 4;
-    k.regions = [&](Layout &ws, uint64_t chunk) {
-        ws.add(&d_evs, (size_t)n_scenarios * chunk);
-        ws.add(&d_el, event_laps.size(), event_laps.data());
-    };
-    k.race = [&](const ScenarioChunk &l) {
-        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_el, l.m,
-                           l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, d_evs, l.n_batches);
+    k.regions = [&](Layout &ws, ScenarioChunk &l, uint64_t chunk) {
+        ws.add(&l.evs, (size_t)n_scenarios * chunk);
+        ws.add(&l.el, event_laps.size(), event_laps.data());
     };
     k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
-        unsigned long long *d_ev = extra[0];
-        const uint64_t tiles = (l.m + mcgp::kEventsCountBlock - 1) / mcgp::kEventsCountBlock;
-        const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
-        hipLaunchKernelGGL(mcgp::events_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kEventsCountBlock), 0, nullptr, l.stage,
-                           d_evs, l.m, n, (uint32_t)cfg->total_laps, d_delta, d_ev);
+        count_events(l, n, (uint32_t)cfg->total_laps, grid_cap, d_delta, extra[0]);
     };
     k.outputs = {events_output(events_out)};
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
@@ -2233,15 +2253,10 @@ int32_t mcgp_run_paces(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                        uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
                        uint64_t *delta_out, uint64_t *carried_out, uint8_t *orders_out)
 {
-    const auto kernel = state ? &mcgp::race_paces_kernel<true> : &mcgp::race_paces_kernel<false>;
     std::vector<mcgp::PaceScenario> pscen;
     std::vector<mcgp::PaceLap> pace_laps;
     std::vector<double> lap_sec;
-    const mcgp::PaceScenario *d_ps = nullptr;
-    const mcgp::PaceLap *d_pl = nullptr;
-    const double *d_sec = nullptr;
-    uint16_t *d_car = nullptr;              // [S][m][n] laps carried of a chunk's simulations (carried_out wanted)
-    ScenarioKind k = {"paces run", "paces", "mcgp::race_paces_kernel", reinterpret_cast<KernelFn>(kernel)};
+    ScenarioKind k = {"paces run", "paces", "mcgp::race_paces_kernel", mcgp::kRulePaces};
     k.tables = {{"pace_count", "paces", pace_count, paces, [&](uint64_t *n_paces) {
         return mcgp::check_pace_counts(n_scenarios, pace_count, n_paces);
     }}};
@@ -2252,24 +2267,14 @@ int32_t mcgp_run_paces(const mcgp_config *cfg, const mcgp_drivers *drv, const do
     };
     // a position byte per driver, and its u16 of laps carried when they are counted
     k.sim_bytes = carried_out ? (size_t)n * 3 : (size_t)n;
-    k.regions = [&](Layout &ws, uint64_t chunk) {
-        if (carried_out) ws.add(&d_car, (size_t)n_scenarios * chunk * n);
-        ws.add(&d_ps, n_scenarios, pscen.data());
-        ws.add(&d_pl, pace_laps.size(), pace_laps.data());
-        ws.add(&d_sec, lap_sec.size(), lap_sec.data());
+    k.regions = [&](Layout &ws, ScenarioChunk &l, uint64_t chunk) {
+        if (carried_out) ws.add(&l.car, (size_t)n_scenarios * chunk * n);
+        ws.add(&l.ps, n_scenarios, pscen.data());
+        ws.add(&l.pl, pace_laps.size(), pace_laps.data());
+        ws.add(&l.sec, lap_sec.size(), lap_sec.data());
     };
-    k.race = [&](const ScenarioChunk &l) {
-        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_ps, d_pl, d_sec,
-                           l.m, l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, d_car, l.n_batches);
-    };
-    // grid rows: the scenarios; grid layers: the deltas, then (carried_out wanted) one per driver
     k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
-        unsigned long long *d_carried = extra[0];
-        const uint32_t gz = d_carried ? 1u + n : 1u;
-        const uint64_t tiles = (l.m + mcgp::kPacesCountBlock - 1) / mcgp::kPacesCountBlock;
-        const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / ((uint64_t)l.S * gz)));
-        hipLaunchKernelGGL(mcgp::paces_count, dim3((uint32_t)gxc, l.S, gz), dim3(mcgp::kPacesCountBlock), 0, nullptr, l.stage,
-                           d_car, d_ps, l.m, n, (uint32_t)cfg->total_laps, d_delta, d_carried);
+        count_paces(l, n, (uint32_t)cfg->total_laps, grid_cap, d_delta, extra[0]);
     };
     k.outputs = {carried_output(carried_out, cfg)};
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
@@ -2284,7 +2289,6 @@ int32_t mcgp_run_combined(const mcgp_config *cfg, const mcgp_drivers *drv, const
                           int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *fate_out, uint64_t *events_out,
                           uint64_t *carried_out, uint8_t *orders_out)
 {
-    const auto kernel = state ? &mcgp::race_combined_kernel<true> : &mcgp::race_combined_kernel<false>;
     // a NULL count array: none in any scenario (n_scenarios is checked, against the same limit, before a count is read)
     static const uint32_t none[mcgp::kMaxStrategyScenarios] = {};
     if (!penalty_count) penalty_count = none;
@@ -2296,15 +2300,7 @@ int32_t mcgp_run_combined(const mcgp_config *cfg, const mcgp_drivers *drv, const
     std::vector<mcgp::PaceScenario> pscen;
     std::vector<mcgp::PaceLap> pace_laps;
     std::vector<double> lap_sec;
-    const mcgp::PenaltyScenario *d_pn = nullptr;
-    const mcgp::PenaltyLap *d_nl = nullptr;
-    const uint8_t *d_el = nullptr;
-    const mcgp::PaceScenario *d_ps = nullptr;
-    const mcgp::PaceLap *d_pl = nullptr;
-    const double *d_sec = nullptr;
-    uint32_t *d_evs = nullptr;              // [S][m] packed event counts of a chunk's simulations (events_out wanted)
-    uint16_t *d_car = nullptr;              // [S][m][n] laps carried of a chunk's simulations (carried_out wanted)
-    ScenarioKind k = {"combined run", "combined", "mcgp::race_combined_kernel", reinterpret_cast<KernelFn>(kernel)};
+    ScenarioKind k = {"combined run", "combined", "mcgp::race_combined_kernel", mcgp::kRuleAll};
     k.tables = {
         {"penalty_count", "penalties", penalty_count, penalties,
          [&](uint64_t *total) { return mcgp::check_penalty_counts(n_scenarios, penalty_count, total); }},
@@ -2326,44 +2322,22 @@ int32_t mcgp_run_combined(const mcgp_config *cfg, const mcgp_drivers *drv, const
     // a byte per driver (position | fate << 5), the u32 of event counts and the drivers' u16 of laps carried when wanted
     k.sim_bytes = (size_t)n + (events_out ? 4 : 0) + (carried_out ? (size_t)n * 2 : 0);
     k.pos_mask = mcgp::kStagePosMask;
-    k.regions = [&](Layout &ws, uint64_t chunk) {
-        if (events_out) ws.add(&d_evs, (size_t)n_scenarios * chunk);
-        if (carried_out) ws.add(&d_car, (size_t)n_scenarios * chunk * n);
-        ws.add(&d_pn, n_scenarios, pens.data());
-        ws.add(&d_nl, pen_laps.size(), pen_laps.data());
-        ws.add(&d_el, event_laps.size(), event_laps.data());
-        ws.add(&d_ps, n_scenarios, pscen.data());
-        ws.add(&d_pl, pace_laps.size(), pace_laps.data());
-        ws.add(&d_sec, lap_sec.size(), lap_sec.data());
+    k.regions = [&](Layout &ws, ScenarioChunk &l, uint64_t chunk) {
+        if (events_out) ws.add(&l.evs, (size_t)n_scenarios * chunk);
+        if (carried_out) ws.add(&l.car, (size_t)n_scenarios * chunk * n);
+        ws.add(&l.pn, n_scenarios, pens.data());
+        ws.add(&l.nl, pen_laps.size(), pen_laps.data());
+        ws.add(&l.el, event_laps.size(), event_laps.data());
+        ws.add(&l.ps, n_scenarios, pscen.data());
+        ws.add(&l.pl, pace_laps.size(), pace_laps.data());
+        ws.add(&l.sec, lap_sec.size(), lap_sec.data());
     };
-    k.race = [&](const ScenarioChunk &l) {
-        hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, d_pn, d_nl, d_el, d_ps,
-                           d_pl, d_sec, l.m, l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage, d_evs,
-                           d_car, l.n_batches);
-    };
-    // the three siblings' counting kernels as they are, each on the staging in its own layout; the deltas come from
-    // penalties_count, the one that masks the fate off the position byte
+    // the deltas come from penalties_count, the one that masks the fate off the position byte
     k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
         const uint32_t L = (uint32_t)cfg->total_laps;
-        if (d_delta || extra[0]) {
-            const uint64_t tiles = (l.m + mcgp::kPenaltyCountBlock - 1) / mcgp::kPenaltyCountBlock;
-            const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
-            hipLaunchKernelGGL(mcgp::penalties_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kPenaltyCountBlock), 0, nullptr,
-                               l.stage, l.m, n, d_delta, extra[0]);
-        }
-        if (extra[1]) {
-            const uint64_t tiles = (l.m + mcgp::kEventsCountBlock - 1) / mcgp::kEventsCountBlock;
-            const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / l.S));
-            hipLaunchKernelGGL(mcgp::events_count, dim3((uint32_t)gxc, l.S), dim3(mcgp::kEventsCountBlock), 0, nullptr, l.stage,
-                               d_evs, l.m, n, L, (unsigned long long *)nullptr, extra[1]);
-        }
-        if (extra[2]) {
-            const uint32_t gz = 1u + n;     // layer 0, the deltas, returns at once
-            const uint64_t tiles = (l.m + mcgp::kPacesCountBlock - 1) / mcgp::kPacesCountBlock;
-            const uint64_t gxc = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / ((uint64_t)l.S * gz)));
-            hipLaunchKernelGGL(mcgp::paces_count, dim3((uint32_t)gxc, l.S, gz), dim3(mcgp::kPacesCountBlock), 0, nullptr,
-                               l.stage, d_car, d_ps, l.m, n, L, (unsigned long long *)nullptr, extra[2]);
-        }
+        if (d_delta || extra[0]) count_penalties(l, n, grid_cap, d_delta, extra[0]);
+        if (extra[1]) count_events(l, n, L, grid_cap, nullptr, extra[1]);
+        if (extra[2]) count_paces(l, n, L, grid_cap, nullptr, extra[2]);
     };
     k.outputs = {fate_output(fate_out), events_output(events_out), carried_output(carried_out, cfg)};
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,

@@ -1,5 +1,5 @@
 // pace_pack.h -- host side of mcgp_run_paces: a caller's mcgp_pace_offset[] (include/mcgp.h) checked against the
-// documented limits and packed into what race_paces_kernel reads (PaceScenario, PaceLap and the list of LAPS seconds,
+// documented limits and packed into what race_scenario_kernel reads (PaceScenario, PaceLap and the list of LAPS seconds,
 // paces.hip.h).  Plain C++, no device code, beside plan_pack.h, penalty_pack.h and event_pack.h and for the same reason:
 // mcgp_hip.hip includes it for the C ABI, and the host debugging build of the generic kernels
 // (tools/emu/emu_generic.cpp) includes the same text.

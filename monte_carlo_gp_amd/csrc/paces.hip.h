@@ -1,16 +1,16 @@
 // paces.hip.h -- race odds under lap-time offsets by lap or until a car's next stop (mcgp_run_paces, include/mcgp.h).
 //
-// race_paces_kernel is race_strategy_kernel (strategy.hip.h: S scenarios of one race with common random numbers, one
-// lane per (scenario, simulation), blockIdx.y the scenario, load_block's LDS rows unchanged, PlannedTyres and PlanPit)
-// with two policies:
+// The tables and policies of the paces rule set of race_scenario_kernel (scenario.hip.h: S scenarios of one race with
+// common random numbers, one lane per (scenario, simulation), blockIdx.y the scenario), and paces_count.  The rule set
+// is two policies:
 //
 //   pace     OffsetPace, the pace policy of start_from_grid (lap 1) and run_laps: wherever the model reads base_pace[d]
 //            -- lap 1's base_lap, the lap time of laps >= 2, the pace of the three overtake passes -- the car's base is
 //            b = base_pace[d]; b = b + seconds of the LAPS offset that covers the lap; b = b + seconds of the car's
 //            active UNTIL_STOP offset: at most two binary64 additions, in that order;
-//   pit      PacePit wraps PlanPit as PenaltyPit does: its after_pit clears the lane's UNTIL_STOP bit of a car that
-//            stopped (the rule's stop or a planned one) on a lap >= the offset's first_lap.  The lap time of that lap is
-//            computed before the pit step and carries the offset; the overtakes of that lap are after it and do not.
+//   pit      ScenarioPit's after_pit clears the lane's UNTIL_STOP bit of a car that stopped (the rule's stop or a planned
+//            one) on a lap >= the offset's first_lap.  The lap time of that lap is computed before the pit step and
+//            carries the offset; the overtakes of that lap are after it and do not.
 //
 // Offset data reach the kernel as read-only global memory at wave-uniform addresses, as a scenario's StopLap does: a
 // PaceLap per scenario and lap (16 bytes, one scalar load: the drivers with a LAPS offset on the lap, where their seconds
@@ -22,12 +22,12 @@
 // seconds.  The per-lane state is one u32 in a register, the UNTIL_STOP offsets not yet cleared; both policies (passed
 // by value) hold a pointer to it.  Nothing new is drawn and no draw moves.
 //
-// Staging: the strategy kernel's byte per scenario, simulation and driver (the classified position) and, when
+// Staging: the strategy call's byte per scenario, simulation and driver (the classified position) and, when
 // carried_out is wanted, one u16 per scenario, simulation and driver: the laps whose lap time carried the driver's
 // UNTIL_STOP offset.  It is written when the bit clears (lap - first_lap + 1) and, after run_laps, for the bits still set
 // (from the retirement lap in `pk`, or L); cells of drivers without such an offset are not written and not read.
 // paces_count reads the staging once, blockIdx.y the scenario: blockIdx.z = 0 counts pos_s(d) - pos_0(d) for scenarios
-// s >= 1 (the centre bin left out, as strategy_count_deltas does); blockIdx.z = 1 + d counts driver d's laps carried, if
+// s >= 1 (count_position_deltas, strategy.hip.h: the centre bin left out); blockIdx.z = 1 + d counts driver d's laps carried, if
 // the scenario gives d an UNTIL_STOP offset, into [L + 1] u32 LDS bins (4 KB at L = 1000; a whole [n][L + 1] block of bins
 // would be 128 KB), column 0 left out: the host derives it, for every driver, from n_sims.  One u64 global atomic per
 // non-zero bin.  It has no cross-lane operation and strides by its block's size.
@@ -92,82 +92,6 @@ struct OffsetPace {
     }
 };
 
-// run_laps' pit policy under offsets: PlanPit decides the stops; after_pit clears the UNTIL_STOP offset of a car that
-// stopped on a lap >= its first_lap and stages the laps it was carried.
-struct PacePit {
-    PlanPit plan;
-    const PaceLap *__restrict__ laps;           // this scenario's [L + 1]
-    const uint16_t *__restrict__ until_from;    // PaceScenario::until_from
-    uint32_t *active;                           // the lane's UNTIL_STOP offsets not yet cleared
-    uint16_t *carried;                          // the lane's staged [n], or NULL
-    uint32_t until;                             // the current lap's PaceLap::until
-
-    __device__ __forceinline__ void begin_lap(int l)
-    {
-        plan.begin_lap(l);
-        until = laps[l].until;
-    }
-    __device__ __forceinline__ int decide(uint32_t d, uint32_t &newc) const { return plan.decide(d, newc); }
-    __device__ __forceinline__ double after_pit(uint32_t d, bool stopped, double t) const
-    {
-        const uint32_t bit = 1u << d;
-        if (stopped && ((until & *active) & bit)) {
-            *active &= ~bit;
-            if (carried) carried[d] = (uint16_t)(plan.lap - (int)until_from[d] + 1);
-        }
-        return t;
-    }
-};
-
-// Simulations sim_offset + [0, m) of every scenario (gridDim.y = S), from the grid (kFromState false) or from `state`.
-// hist [S][n][n] is ACCUMULATED into; stage [S][m][n] (classified position of each driver) is written, and carried
-// [S][m][n] u16 (NULL: not wanted) at the drivers that have an UNTIL_STOP offset in the scenario.
-template <bool kFromState>
-__global__ void __launch_bounds__(512)
-race_paces_kernel(const KParams *__restrict__ P, const ResumeState *__restrict__ state,
-                  const StrategyScenario *__restrict__ scen, const StopLap *__restrict__ stop_laps,
-                  const PaceScenario *__restrict__ paces, const PaceLap *__restrict__ pace_laps,
-                  const double *__restrict__ lap_sec, uint64_t m, uint64_t sim_offset, uint32_t seed_lo, uint32_t seed_hi,
-                  unsigned long long *__restrict__ hist, uint8_t *__restrict__ stage, uint16_t *__restrict__ carried,
-                  uint32_t n_batches)
-{
-    const uint32_t sid = blockIdx.y;
-    const StrategyScenario *__restrict__ sc = scen + sid;
-    const PaceScenario *__restrict__ ps = paces + sid;
-    const size_t lap0 = (size_t)sid * (size_t)(P->total_laps + 1);
-    const PlanPit plan = {stop_laps + lap0, sc->planned, 0u, 0};
-    const PaceLap *__restrict__ pl = pace_laps + lap0;
-    const uint32_t until = ps->until;
-    run_block(P, m, n_batches, hist + (size_t)sid * (size_t)(P->n * P->n),
-              [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
-        const uint64_t sim = sim_offset + local;
-        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-        const uint64_t cell = ((uint64_t)sid * m + local) * (uint64_t)e.n;
-        uint16_t *crow = carried ? carried + cell : nullptr;
-        uint32_t active = until;
-        const OffsetPace pace = {pl, lap_sec, ps->until_sec, &active, 0u, 0u, 0u};
-        const PacePit pit = {plan, pl, ps->until_from, &active, crow, 0u};
-        const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
-                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr, PlannedTyres{sc}, pace);
-        NoLapObserver none;
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, none, pit, DrawnEvents(),
-                 pace);                                                                             // reference :166-228
-        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
-        // each driver's classified position
-        uint8_t *row = stage + cell;
-        for (int p = 0; p < e.n; ++p) row[s.Ord(p)] = (uint8_t)p;
-        // the offsets no stop cleared: carried up to the car's retirement, or to the flag
-        if (crow) {
-            for (uint32_t rest = active; rest; rest &= rest - 1u) {
-                const uint32_t d = (uint32_t)__ffs((int)rest) - 1u, pk = s.Pk(d);
-                const int from = (int)ps->until_from[d];
-                const int end = (pk & kDnf) ? (int)(pk & kAgeMask) : e.L + 1;       // the first lap without a lap time
-                crow[d] = (uint16_t)(end > from ? end - from : 0);
-            }
-        }
-    });
-}
-
 // From the staged data of m simulations, for scenario s = blockIdx.y: a block with blockIdx.z = 0 adds the paired
 // changes of position against scenario 0 to delta [S][n][2n - 1] (s >= 1, the centre left out; delta may be NULL); a
 // block with blockIdx.z = 1 + d adds driver d's laps carried to carried_out [S][n][L + 1] (column 0 left out; only if the
@@ -189,20 +113,14 @@ paces_count(const uint8_t *__restrict__ stage, const uint16_t *__restrict__ carr
     const uint64_t base = (uint64_t)s * m * n;
     for (uint64_t i = (uint64_t)blockIdx.x * nt + t; i < m; i += (uint64_t)gridDim.x * nt) {
         if (deltas) {
-            const uint8_t *r0 = stage + i * n, *r1 = stage + base + i * n;
-            for (uint32_t k = 0; k < n; ++k) {
-                const uint32_t p0 = r0[k], p1 = r1[k];
-                if (p0 != p1) atomicAdd(&bins[k * w + (p1 + n - 1u - p0)], 1u);
-            }
+            count_position_deltas(stage + i * n, stage + base + i * n, n, 0xFFu, bins);
         } else {
             const uint32_t c = carried[base + i * n + d];
             if (c) atomicAdd(&bins[c < L ? c : L], 1u);
         }
     }
     __syncthreads();
-    unsigned long long *out = deltas ? delta + (uint64_t)s * n_bins : carried_out + ((uint64_t)s * n + d) * n_bins;
-    for (uint32_t i = t; i < n_bins; i += nt)
-        if (bins[i]) atomicAdd(&out[i], (unsigned long long)bins[i]);
+    flush_bins(bins, n_bins, deltas ? delta + (uint64_t)s * n_bins : carried_out + ((uint64_t)s * n + d) * n_bins, t, nt);
 }
 
 }  // namespace mcgp

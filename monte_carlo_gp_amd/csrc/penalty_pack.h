@@ -1,5 +1,5 @@
 // penalty_pack.h -- host side of mcgp_run_penalties: a caller's mcgp_time_penalty[] (include/mcgp.h) checked against the
-// documented limits and packed into what race_penalties_kernel reads (PenaltyScenario and PenaltyLap, penalties.hip.h).
+// documented limits and packed into what race_scenario_kernel reads (PenaltyScenario and PenaltyLap, penalties.hip.h).
 // Plain C++, no device code, beside plan_pack.h and for the same reason: mcgp_hip.hip includes it for the C ABI, and the
 // host debugging build of the generic kernels (tools/emu/emu_generic.cpp) includes the same text.
 #pragma once

@@ -24,7 +24,7 @@
 // The block protocol (run_block, over load_block), the start of a race (start_from_grid), the laps after lap 1
 // (run_laps) and the classification (classify_and_count) are functions shared with the other race kernels of this
 // family: race_resume_kernel (resume.hip.h) runs a race on from a mid-race state, race_trace_kernel (trace.hip.h) and
-// race_gaps_kernel (gaps.hip.h) observe every lap, race_strategy_kernel (strategy.hip.h) plans the pit stops.  A kernel
+// race_gaps_kernel (gaps.hip.h) observe every lap, race_scenario_kernel (scenario.hip.h) plans the pit stops.  A kernel
 // is its arguments and the lane body it hands run_block: sim id, start, run_laps, classify_and_count, its own output.
 //
 // Floating point: IEEE binary64 in the reference's evaluation order; this file
@@ -205,7 +205,7 @@ struct ModelTyres {
     __device__ __forceinline__ void operator()(uint32_t /*driver*/, uint32_t & /*comp*/, uint32_t & /*age*/) const {}
 };
 
-// The pace policy of every kernel but race_paces_kernel: a car's base pace is the model's.  start_from_grid and run_laps
+// The pace policy of every kernel but race_scenario_kernel with paces: a car's base pace is the model's.  start_from_grid and run_laps
 // ask a policy once per lap, begin_lap(lap) (wave-uniform), and wherever the model reads base_pace[d] -- lap 1's base_lap,
 // the lap time of laps >= 2, the pace of the overtake passes (candidate scan and attempt probability) -- base(d, b) with
 // b = base_pace[d], and use what it returns.  ModelPace returns b itself, so that the call vanishes; OffsetPace
@@ -218,7 +218,7 @@ struct ModelPace {
 // The start of one lane's race: grid (`fixed_grid`, or NULL: sampled from grid_probs), cars, lap 1 and the once-per-race
 // retirement draws.  Leaves the rows after update_positions of lap 1 and every driver's retirement lap (laps >= 2) in
 // `out`.  hook(driver, comp, age) may replace a car's starting tyres after the model has picked them
-// (race_strategy_kernel, strategy.hip.h).  `pace` gives lap 1's base pace (ModelPace: the model's).
+// (race_scenario_kernel: PlannedTyres, strategy.hip.h).  `pace` gives lap 1's base pace (ModelPace: the model's).
 template <class StartHook = ModelTyres, class PacePolicy = ModelPace>
 __device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1,
                                                      uint32_t seed_lo, uint32_t seed_hi,
@@ -341,14 +341,14 @@ struct NoLapObserver {
 // car's lap time, decide(d, newc): -1 = the rule decides (_handle_pit_stops, reference :454-492); 0 = no stop and the
 // rule is off; 1 = a stop onto compound `newc`, rule off.  RulePit's constant -1 folds the branch away.  After the pit
 // step of every running car, after_pit(d, stopped, t) sees the car's new cumulative time and returns what is stored:
-// `t` itself here and in PlanPit, so that the call vanishes; race_penalties_kernel (penalties.hip.h) adds time there.
+// `t` itself here and in PlanPit, so that the call vanishes; ScenarioPit (scenario.hip.h) adds time penalties there.
 struct RulePit {
     __device__ __forceinline__ void begin_lap(int /*lap*/) {}
     __device__ __forceinline__ int decide(uint32_t /*d*/, uint32_t & /*newc*/) const { return -1; }
     __device__ __forceinline__ double after_pit(uint32_t /*d*/, bool /*stopped*/, double t) const { return t; }
 };
 
-// The event policy of every kernel but race_events_kernel: each lap's event is drawn.  run_laps asks a policy once per
+// The event policy of every kernel but race_scenario_kernel with events: each lap's event is drawn.  run_laps asks a policy once per
 // lap, at a wave-uniform point before the event step, at(lap): -1 = the short-circuit chain decides, as drawn; a kEvent*
 // = that outcome replaces the chain's, whatever the lap's event words say (ForcedEvents, events.hip.h).  DrawnEvents'
 // constant -1 folds the test away.
@@ -361,10 +361,10 @@ struct DrawnEvents {
 // and the reference's drs_disabled_until.  race_kernel runs it from lap 2, race_resume_kernel (resume.hip.h) from k + 1.
 // After update_positions of every lap, obs(s, lap, event) sees the rows and the lap's kEvent* (race_trace_kernel,
 // trace.hip.h, records them; the other kernels pass a NoLapObserver).  `pit` decides the stops (RulePit: the model's
-// rule; race_strategy_kernel, strategy.hip.h, passes planned stops; race_penalties_kernel, penalties.hip.h, planned stops
-// and time penalties).  `evp` may replace a lap's event (DrawnEvents: never; race_events_kernel, events.hip.h, passes the
-// caller's overrides).  `pace` gives a car's base pace on a lap (ModelPace: the model's; race_paces_kernel, paces.hip.h,
-// passes the caller's lap-time offsets).
+// rule; race_scenario_kernel, scenario.hip.h, passes a ScenarioPit: planned stops and, by rule set, time penalties).
+// `evp` may replace a lap's event (DrawnEvents: never; with events the scenario kernel passes ForcedEvents, the
+// caller's overrides).  `pace` gives a car's base pace on a lap (ModelPace: the model's; with paces it passes OffsetPace,
+// the caller's lap-time offsets).
 template <class LapObserver, class PitPolicy = RulePit, class EventPolicy = DrawnEvents, class PacePolicy = ModelPace>
 __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1, uint32_t seed_lo,
                                          uint32_t seed_hi, int first_lap, int drs_disabled_until, LapObserver &obs,

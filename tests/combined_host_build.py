@@ -1,6 +1,6 @@
-"""Host DEBUGGING build of csrc/combined.hip.h (tools/emu/emu_generic.cpp, kernel_host_build.generic_lib): run
-race_combined_kernel<false / true> and the three siblings' counting kernels on the CPU and decode the raw stagings by the
-layouts documented at the top of combined.hip.h.  Test infrastructure only -- the product (monte_carlo_gp_amd/) never
+"""Host DEBUGGING build of csrc/scenario.hip.h (tools/emu/emu_generic.cpp, kernel_host_build.generic_lib): run
+race_scenario_kernel<false / true, kRuleAll> and the three rule sets' counting kernels on the CPU and decode the raw stagings
+by the layouts documented at the top of scenario.hip.h.  Test infrastructure only -- the product (monte_carlo_gp_amd/) never
 imports this and has no CPU path."""
 import ctypes as C
 
@@ -28,7 +28,7 @@ def lib():
 
 
 def combined_raw(case, scen, n_sims, seed, sim_offset=0, state=None, prob=None, grid_x=3, count=True, null_counts=False):
-    """race_combined_kernel (and penalties_count, events_count, paces_count as blocks of one thread) on the host -> dict:
+    """race_scenario_kernel with all three rule sets (and penalties_count, events_count, paces_count as blocks of one thread) on the host -> dict:
     hist [S][n][n], stage [S][n_sims][n], evs [S][n_sims], car [S][n_sims][n], delta [S][n][2n-1] without its derived
     centre bin, fate [S][n][4] and carried [S][n][L+1] without their derived column 0, events [S][3][L+1]; after checking
     that nothing is written before or past any of the three chunks, nor at a driver without an UNTIL_STOP offset."""

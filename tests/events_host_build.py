@@ -1,5 +1,5 @@
 """Host DEBUGGING build of csrc/events.hip.h (tools/emu/emu_generic.cpp, kernel_host_build.generic_lib): run
-race_events_kernel<false / true> and events_count on the CPU and decode the raw staging by the layout documented at the
+race_scenario_kernel<false / true, kRuleEvents> and events_count on the CPU and decode the raw staging by the layout documented at the
 top of events.hip.h.  Test infrastructure only -- the product (monte_carlo_gp_amd/) never imports this and has no CPU
 path."""
 import ctypes as C
@@ -23,7 +23,7 @@ def lib():
 
 
 def events_raw(case, plans, overrides, n_sims, seed, sim_offset=0, state=None, prob=None, grid_x=3, count=True):
-    """race_events_kernel (and events_count, as grid_x x S blocks of one thread) on the host -> (hist [S][n][n], stage
+    """race_scenario_kernel with events (and events_count, as grid_x x S blocks of one thread) on the host -> (hist [S][n][n], stage
     [S][n_sims][n], ev_stage [S][n_sims], delta [S][n][2n-1] without its derived centre bin, events [S][3][L+1]), after
     checking that nothing is written before or past the chunk."""
     p, g = prob or KH.generic_problem(case)

@@ -1,6 +1,6 @@
 """Inputs shared by the tests of the generic kernel family (race_kernel, race_resume_kernel, race_trace_kernel,
-race_strategy_kernel, race_gaps_kernel, race_conditions_kernel, race_stints_kernel, race_moves_kernel,
-race_penalties_kernel, race_fastest_kernel) on the host build (test_generic_host_build.py, test_gaps_host_build.py,
+race_scenario_kernel, race_gaps_kernel, race_conditions_kernel, race_stints_kernel, race_moves_kernel,
+race_fastest_kernel) on the host build (test_generic_host_build.py, test_gaps_host_build.py,
 test_conditions_host_build.py, test_stints_host_build.py, test_moves_host_build.py, test_penalties_host_build.py,
 test_fastest_host_build.py) and on the device (test_gpu_generic_fuzz.py for trace, resume and strategies,
 test_gpu_gaps_conditions_fuzz.py for gaps and conditions, test_gpu_stints_moves_fuzz.py for stints and moves with their

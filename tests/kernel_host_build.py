@@ -89,7 +89,7 @@ TRACE_PIT, TRACE_POS_MASK = 0x80, 0x3F          # csrc/trace.hip.h: kTracePit, k
 
 
 def build_generic():
-    """tools/emu/libmcgp_emu_generic.so: race_kernel, race_resume_kernel, race_trace_kernel, race_strategy_kernel and
+    """tools/emu/libmcgp_emu_generic.so: race_kernel, race_resume_kernel, race_trace_kernel, race_scenario_kernel and
     race_gaps_kernel compiled for the host (build()'s flags; rebuilt when one of the product's headers, every csrc/*.h
     and include/mcgp.h, is newer)."""
     srcs = [os.path.join(EMU_DIR, f) for f in ('emu_generic.cpp', 'hip/hip_runtime.h')]
@@ -198,7 +198,7 @@ def generic_trace(case, n_sims, seed, sim_offset=0, prob=None):
 
 
 def generic_strategy(case, scenarios, n_sims, seed, sim_offset=0, state=None, prob=None):
-    """race_strategy_kernel<false> (state None) or <true> on the host: scenarios as strategy_ref.c_plans takes them ->
+    """race_scenario_kernel<false, 0> (state None) or <true, 0> on the host: scenarios as strategy_ref.c_plans takes them ->
     (hist [S][n][n], orders [S][n_sims][n])."""
     import resume_ref as RR
     import strategy_ref as SR

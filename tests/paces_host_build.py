@@ -1,5 +1,5 @@
 """Host DEBUGGING build of csrc/paces.hip.h (tools/emu/emu_generic.cpp, kernel_host_build.generic_lib): run
-race_paces_kernel<false / true> and paces_count on the CPU and decode the raw staging by the layout documented at the
+race_scenario_kernel<false / true, kRulePaces> and paces_count on the CPU and decode the raw staging by the layout documented at the
 top of paces.hip.h.  Test infrastructure only -- the product (monte_carlo_gp_amd/) never imports this and has no CPU
 path."""
 import ctypes as C
@@ -33,7 +33,7 @@ def until_mask(offsets, n):
 
 
 def paces_raw(case, plans, offsets, n_sims, seed, sim_offset=0, state=None, prob=None, grid_x=3, count=True):
-    """race_paces_kernel (and paces_count, as grid_x x S x (1 + n) blocks of one thread) on the host -> (hist [S][n][n],
+    """race_scenario_kernel with paces (and paces_count, as grid_x x S x (1 + n) blocks of one thread) on the host -> (hist [S][n][n],
     stage [S][n_sims][n], car_stage [S][n_sims][n], delta [S][n][2n-1] without its derived centre bin, carried
     [S][n][L+1] without its derived column 0), after checking that nothing is written before or past the chunk, nor at a
     driver without an UNTIL_STOP offset."""

@@ -1,5 +1,5 @@
 """Host DEBUGGING build of csrc/penalties.hip.h (tools/emu/emu_generic.cpp, kernel_host_build.generic_lib): run
-race_penalties_kernel<false / true> and penalties_count on the CPU and decode the raw staging by the layout documented at
+race_scenario_kernel<false / true, kRulePenalties> and penalties_count on the CPU and decode the raw staging by the layout documented at
 the top of penalties.hip.h.  Test infrastructure only -- the product (monte_carlo_gp_amd/) never imports this and has no
 CPU path."""
 import ctypes as C
@@ -22,7 +22,7 @@ def lib():
 
 
 def penalties_raw(case, plans, penalties, n_sims, seed, sim_offset=0, state=None, prob=None, grid_x=3, count=True):
-    """race_penalties_kernel (and penalties_count, as grid_x x S blocks of one thread) on the host -> (hist [S][n][n],
+    """race_scenario_kernel with penalties (and penalties_count, as grid_x x S blocks of one thread) on the host -> (hist [S][n][n],
     stage [S][n_sims][n], delta [S][n][2n-1], fate [S][n][4]; the last two without their derived centre bin and column
     0, as the device leaves them), after checking that nothing is written past the chunk."""
     p, g = prob or KH.generic_problem(case)

@@ -1,4 +1,4 @@
-"""race_combined_kernel<false / true> and the three counting kernels it shares with its siblings, executed on the host
+"""race_scenario_kernel<false / true, kRuleAll> and the three counting kernels it shares with its siblings, executed on the host
 (tools/emu/emu_generic.cpp, through combined_host_build), against
 
   1. the Python restatement (combined_ref) on the scenarios where the rule sets meet (combined_ref.meeting_scenarios),

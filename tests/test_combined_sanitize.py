@@ -1,4 +1,4 @@
-"""The host build of race_combined_kernel, the three counting kernels it shares with its siblings and the packers of
+"""The host build of race_scenario_kernel with all three rule sets (csrc/scenario.hip.h), the three counting kernels and the packers of
 csrc/penalty_pack.h, event_pack.h and pace_pack.h under the host's address and undefined-behaviour sanitizers:
 tools/emu/sanitize_combined_main.cpp, a stand-alone program with its own main, compiled with g++ together with
 tools/emu/emu_generic.cpp and run as a process of its own on the CPU.  Nothing loaded into python is sanitized, and

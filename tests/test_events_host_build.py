@@ -1,4 +1,4 @@
-"""race_events_kernel<false / true> and events_count executed on the host (tools/emu/emu_generic.cpp, through
+"""race_scenario_kernel<false / true, kRuleEvents> and events_count executed on the host (tools/emu/emu_generic.cpp, through
 events_host_build) against three independent references:
 
   1. the pinned C oracle under ANOTHER config: a single override 2..L (or k + 1..L from a state) of kind K, run under

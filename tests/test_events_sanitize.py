@@ -1,4 +1,4 @@
-"""The host build of race_events_kernel, events_count and the packer of csrc/event_pack.h under the host's address and
+"""The host build of race_scenario_kernel with events (csrc/scenario.hip.h), events_count and the packer of csrc/event_pack.h under the host's address and
 undefined-behaviour sanitizers: tools/emu/sanitize_events_main.cpp, a stand-alone program with its own main, compiled with
 g++ together with tools/emu/emu_generic.cpp and run as a process of its own on the CPU.  Nothing loaded into python is
 sanitized, and nothing here touches a GPU."""

@@ -1,4 +1,4 @@
-"""race_paces_kernel<false / true> and paces_count executed on the host (tools/emu/emu_generic.cpp, through
+"""race_scenario_kernel<false / true, kRulePaces> and paces_count executed on the host (tools/emu/emu_generic.cpp, through
 paces_host_build) against two independent references:
 
   1. the pinned C oracle under ANOTHER base_pace: a LAPS offset [1, L] (or [k + 1, L] from a state) of x_d on every

@@ -1,4 +1,4 @@
-"""race_penalties_kernel<false / true> and penalties_count executed on the host (tools/emu/emu_generic.cpp, through
+"""race_scenario_kernel<false / true, kRulePenalties> and penalties_count executed on the host (tools/emu/emu_generic.cpp, through
 penalties_host_build) against the Python restatement (penalties_ref): order for order and fate for fate, from the grid and
 from states after laps 1, L // 2 and L - 1, under the scenarios of penalties_ref.scenarios; the staged bytes stay inside
 the chunk; the counting kernel's bins are the counts of the staged orders and fates whatever its grid.

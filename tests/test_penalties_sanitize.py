@@ -1,4 +1,4 @@
-"""The host build of race_penalties_kernel, penalties_count and the packer of csrc/penalty_pack.h under the host's address
+"""The host build of race_scenario_kernel with penalties (csrc/scenario.hip.h), penalties_count and the packer of csrc/penalty_pack.h under the host's address
 and undefined-behaviour sanitizers: tools/emu/sanitize_penalties_main.cpp, a stand-alone program with its own main,
 compiled with g++ together with tools/emu/emu_generic.cpp and run as a process of its own on the CPU.  Nothing loaded
 into python is sanitized, and nothing here touches a GPU."""

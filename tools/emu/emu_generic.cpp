@@ -1,11 +1,10 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
 // fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
-// strategy.hip.h, gaps.hip.h, conditions.hip.h, stints.hip.h, moves.hip.h, fastest.hip.h and penalties.hip.h with g++ through
-// the stand-in <hip/hip_runtime.h> of this directory and calls the real __global__ functions: race_kernel, race_resume_kernel,
-// race_trace_kernel, race_strategy_kernel<false / true>, race_gaps_kernel<false / true>, race_conditions_kernel<false /
-// true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false / true>, race_fastest_kernel,
-// race_penalties_kernel<false / true>, penalties_count; and events.hip.h: race_events_kernel<false / true>, events_count;
-// and paces.hip.h: race_paces_kernel<false / true>, paces_count; and combined.hip.h: race_combined_kernel<false / true>.
+// gaps.hip.h, conditions.hip.h, stints.hip.h, moves.hip.h, fastest.hip.h and scenario.hip.h (with strategy.hip.h,
+// penalties.hip.h, events.hip.h and paces.hip.h) with g++ through the stand-in <hip/hip_runtime.h> of this directory and
+// calls the real __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_gaps_kernel<false / true>,
+// race_conditions_kernel<false / true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false /
+// true>, race_fastest_kernel, the ten instantiations of race_scenario_kernel, penalties_count, events_count, paces_count.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -30,7 +29,6 @@
 
 #include "../../monte_carlo_gp_amd/csrc/params_build.h"
 #include "../../monte_carlo_gp_amd/csrc/trace.hip.h"
-#include "../../monte_carlo_gp_amd/csrc/strategy.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/gaps.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/conditions.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/stints.hip.h"
@@ -40,7 +38,7 @@
 #include "../../monte_carlo_gp_amd/csrc/penalty_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/event_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/pace_pack.h"
-#include "../../monte_carlo_gp_amd/csrc/combined.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/scenario.hip.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
 namespace mcgp {
@@ -77,6 +75,95 @@ void one_thread_block(uint32_t grid_y)
     blockIdx = {0, 0, 0};
     blockDim = {1, 1, 1};
     gridDim = {1, grid_y, 1};
+}
+
+// The scenario calls: race_scenario_kernel<false, rules> (state NULL: from the grid) or <true, rules> over simulations
+// sim_offset + [0, n_sims) of every scenario, one thread block per scenario, and then the rule sets' counting kernels as
+// the C ABI runs them, as grid_x x S (x 1 + n, paces_count with carried) blocks of one thread.  The plans are packed by
+// plan_pack.h; of the three item tables those in `rules` (mcgp::kRule*) are checked and packed by penalty_pack.h,
+// event_pack.h and pace_pack.h, and the kernel gets NULL for the others.  hist [S][n][n] is accumulated into; stage
+// [S][n_sims][n] is written, and ev_stage [S][n_sims] and car_stage [S][n_sims][n] u16 where given (NULL: not staged).
+// delta [S][n][2n - 1], fate [S][n][4], events_cnt [S][3][L + 1] (needs ev_stage) and carried [S][n][L + 1] (needs
+// car_stage), each of which may be NULL, are accumulated into: delta by penalties_count where the call has penalties,
+// else by the counting kernel of its one rule set; the centre bin and the columns 0 stay what they were, as on the device.
+int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                 const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                 const mcgp_pit_plan *plans, const uint32_t *penalty_count, const mcgp_time_penalty *penalties,
+                 const uint32_t *event_count, const mcgp_lap_event *events, const uint32_t *pace_count,
+                 const mcgp_pace_offset *paces, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist,
+                 uint8_t *stage, uint32_t *ev_stage, uint16_t *car_stage, unsigned long long *delta, unsigned long long *fate,
+                 unsigned long long *events_cnt, unsigned long long *carried, uint32_t grid_x, const char **err)
+{
+    const bool pen = rules & mcgp::kRulePenalties, ev = rules & mcgp::kRuleEvents, pace = rules & mcgp::kRulePaces;
+    static mcgp::KParams kp;
+    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    if (rc != MCGP_OK) return rc;
+    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
+        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    // (the events call always stages the event word: its kernel does not test the pointer.  The check is new for
+    // emu_events_run, whose old body had none)
+    if ((events_cnt || rules == mcgp::kRuleEvents) && !ev_stage) return fail(MCGP_E_BAD_ARG, "events need ev_stage", err);
+    if (carried && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
+    const int L = cfg->total_laps;
+    mcgp::ResumeState st;
+    std::memset(&st, 0, sizeof(st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+        st.sim_offset = sim_offset;
+    }
+    const int first_lap = state ? st.lap + 1 : 2;
+    const bool resumed = state != nullptr;
+    std::vector<mcgp::StrategyScenario> scen;
+    std::vector<mcgp::StopLap> stop_laps;
+    std::vector<mcgp::PenaltyScenario> pens;
+    std::vector<mcgp::PenaltyLap> pen_laps;
+    std::vector<uint8_t> event_laps;
+    std::vector<mcgp::PaceScenario> pscen;
+    std::vector<mcgp::PaceLap> pace_laps;
+    std::vector<double> lap_sec;
+    uint64_t n_pens = 0, n_events = 0, n_paces = 0;
+    std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, resumed, &scen, &stop_laps);
+    if (e.empty() && pen) e = mcgp::check_penalty_counts(n_scenarios, penalty_count, &n_pens);
+    if (e.empty() && ev) e = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
+    if (e.empty() && pace) e = mcgp::check_pace_counts(n_scenarios, pace_count, &n_paces);
+    if (e.empty() && n_pens && !penalties) e = "penalties is NULL";
+    if (e.empty() && n_events && !events) e = "events is NULL";
+    if (e.empty() && n_paces && !paces) e = "paces is NULL";
+    if (e.empty() && pen)
+        e = mcgp::pack_penalties(n_scenarios, penalty_count, penalties, n, L, first_lap, resumed, &pens, &pen_laps);
+    if (e.empty() && ev) e = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, resumed, &event_laps);
+    if (e.empty() && pace)      // lap 1 reads the base pace too: from the grid an offset may name it
+        e = mcgp::pack_paces(n_scenarios, pace_count, paces, n, L, state ? first_lap : 1, resumed, &pscen, &pace_laps, &lap_sec);
+    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    const auto kernel = mcgp::scenario_kernel(rules, resumed);
+    one_thread_block(n_scenarios);
+    for (uint32_t si = 0; si < n_scenarios; ++si) {
+        blockIdx.y = si;
+        kernel(&kp, &st, scen.data(), stop_laps.data(), pen ? pens.data() : nullptr, pen ? pen_laps.data() : nullptr,
+               ev ? event_laps.data() : nullptr, pace ? pscen.data() : nullptr, pace ? pace_laps.data() : nullptr,
+               pace ? lap_sec.data() : nullptr, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
+               ev_stage, car_stage, (uint32_t)n_sims);
+    }
+    unsigned long long *ev_delta = pen ? nullptr : delta, *pace_delta = pen ? nullptr : delta;
+    const uint32_t gz = carried ? 1u + n : 1u;
+    for (uint32_t z = 0; rules != 0u && z < gz; ++z)        // (the strategies call has no counting kernel that runs here)
+        for (uint32_t y = 0; y < n_scenarios; ++y)
+            for (uint32_t x = 0; x < grid_x; ++x) {
+                blockIdx = {x, y, z};
+                if (z == 0) {
+                    gridDim = {grid_x, n_scenarios, 1};
+                    if (pen && (delta || fate)) mcgp::penalties_count(stage, n_sims, n, delta, fate);
+                    if (ev && (ev_delta || events_cnt))
+                        mcgp::events_count(stage, ev_stage, n_sims, n, (uint32_t)L, ev_delta, events_cnt);
+                }
+                gridDim = {grid_x, n_scenarios, gz};
+                if (pace && (pace_delta || carried))
+                    mcgp::paces_count(stage, car_stage, pscen.data(), n_sims, n, (uint32_t)L, pace_delta, carried);
+            }
+    one_thread_block(1);
+    return MCGP_OK;
 }
 
 }  // namespace
@@ -135,43 +222,6 @@ int emu_generic_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     one_thread_block(1);
     mcgp::race_trace_kernel(&kp, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage, stride, rec,
                             (uint32_t)n_sims);
-    return MCGP_OK;
-}
-
-// race_strategy_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every
-// scenario.  hist [S][n][n] is accumulated into; positions [S][n_sims][n] (each driver's classified position) is written.
-int emu_generic_strategy(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
-                         const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
-                         const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
-                         unsigned long long *hist, uint8_t *positions, const char **err)
-{
-    static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
-        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    const int L = cfg->total_laps;
-    mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-        st.sim_offset = sim_offset;
-    }
-    std::vector<mcgp::StrategyScenario> scen;
-    std::vector<mcgp::StopLap> stop_laps;
-    const std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, state ? st.lap + 1 : 2,
-                                               state != nullptr, &scen, &stop_laps);
-    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    one_thread_block(n_scenarios);
-    const auto kernel = state ? &mcgp::race_strategy_kernel<true> : &mcgp::race_strategy_kernel<false>;
-    for (uint32_t si = 0; si < n_scenarios; ++si) {
-        blockIdx.y = si;
-        kernel(&kp, &st, scen.data(), stop_laps.data(), n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist,
-               positions, (uint32_t)n_sims);
-    }
-    blockIdx.y = 0;
     return MCGP_OK;
 }
 
@@ -308,185 +358,52 @@ int emu_fastest_run(const mcgp_config *cfg, const mcgp_drivers *drv, const doubl
     return MCGP_OK;
 }
 
-// race_penalties_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every
-// scenario, plans and penalties packed by plan_pack.h and penalty_pack.h.  hist [S][n][n] is accumulated into; stage
-// [S][n_sims][n] (classified position | fate << 5 of each driver) is written.  delta [S][n][2n - 1] and fate [S][n][4]
-// (either may be NULL) are accumulated into by penalties_count, run as grid_x x S blocks of one thread (both NULL: not
-// run): the centre bin and fate column 0 stay what they were, as on the device.
+// The five scenario calls (scenario_run above).  stage [S][n_sims][n] holds each driver's classified position, with
+// penalties | fate << 5; ev_stage the packed event counts (red | sc << 10 | vsc << 20); car_stage the laps carried at the
+// drivers with an UNTIL_STOP offset.  emu_combined_run takes a NULL count array as none in any scenario.
+int emu_generic_strategy(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                         const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                         const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                         unsigned long long *hist, uint8_t *positions, const char **err)
+{
+    return scenario_run(0u, cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, n_sims, sim_offset, seed, hist, positions, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, 1, err);
+}
+
 int emu_penalties_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
                       uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
                       const uint32_t *penalty_count, const mcgp_time_penalty *penalties, uint64_t n_sims, uint64_t sim_offset,
                       uint64_t seed, unsigned long long *hist, uint8_t *stage, unsigned long long *delta,
                       unsigned long long *fate, uint32_t grid_x, const char **err)
 {
-    static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
-        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    const int L = cfg->total_laps;
-    mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-        st.sim_offset = sim_offset;
-    }
-    const int first_lap = state ? st.lap + 1 : 2;
-    std::vector<mcgp::StrategyScenario> scen;
-    std::vector<mcgp::StopLap> stop_laps;
-    std::vector<mcgp::PenaltyScenario> pens;
-    std::vector<mcgp::PenaltyLap> pen_laps;
-    uint64_t n_pens = 0;
-    std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen, &stop_laps);
-    if (e.empty()) e = mcgp::check_penalty_counts(n_scenarios, penalty_count, &n_pens);
-    if (e.empty() && n_pens && !penalties) e = "penalties is NULL";
-    if (e.empty())
-        e = mcgp::pack_penalties(n_scenarios, penalty_count, penalties, n, L, first_lap, state != nullptr, &pens, &pen_laps);
-    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    one_thread_block(n_scenarios);
-    const auto kernel = state ? &mcgp::race_penalties_kernel<true> : &mcgp::race_penalties_kernel<false>;
-    for (uint32_t si = 0; si < n_scenarios; ++si) {
-        blockIdx.y = si;
-        kernel(&kp, &st, scen.data(), stop_laps.data(), pens.data(), pen_laps.data(), n_sims, sim_offset, (uint32_t)seed,
-               (uint32_t)(seed >> 32), hist, stage, (uint32_t)n_sims);
-    }
-    if (delta || fate) {
-        gridDim = {grid_x, n_scenarios, 1};
-        for (uint32_t y = 0; y < n_scenarios; ++y)
-            for (uint32_t x = 0; x < grid_x; ++x) {
-                blockIdx = {x, y, 0};
-                mcgp::penalties_count(stage, n_sims, n, delta, fate);
-            }
-    }
-    one_thread_block(1);
-    return MCGP_OK;
+    return scenario_run(mcgp::kRulePenalties, cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, penalty_count,
+                        penalties, nullptr, nullptr, nullptr, nullptr, n_sims, sim_offset, seed, hist, stage, nullptr, nullptr,
+                        delta, fate, nullptr, nullptr, grid_x, err);
 }
 
-// race_events_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every scenario,
-// plans and event overrides packed by plan_pack.h and event_pack.h.  hist [S][n][n] is accumulated into; stage
-// [S][n_sims][n] (classified position of each driver) and ev_stage [S][n_sims] (red | sc << 10 | vsc << 20) are written.
-// delta [S][n][2n - 1] and events_cnt [S][3][L + 1] (either may be NULL) are accumulated into by events_count, run as
-// grid_x x S blocks of one thread (both NULL: not run): the centre bin stays what it was, as on the device.
 int emu_events_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
                    uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
                    const uint32_t *event_count, const mcgp_lap_event *events, uint64_t n_sims, uint64_t sim_offset,
                    uint64_t seed, unsigned long long *hist, uint8_t *stage, uint32_t *ev_stage, unsigned long long *delta,
                    unsigned long long *events_cnt, uint32_t grid_x, const char **err)
 {
-    static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
-        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    const int L = cfg->total_laps;
-    mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-        st.sim_offset = sim_offset;
-    }
-    const int first_lap = state ? st.lap + 1 : 2;
-    std::vector<mcgp::StrategyScenario> scen;
-    std::vector<mcgp::StopLap> stop_laps;
-    std::vector<uint8_t> event_laps;
-    uint64_t n_events = 0;
-    std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen, &stop_laps);
-    if (e.empty()) e = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
-    if (e.empty() && n_events && !events) e = "events is NULL";
-    if (e.empty()) e = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, state != nullptr, &event_laps);
-    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    one_thread_block(n_scenarios);
-    const auto kernel = state ? &mcgp::race_events_kernel<true> : &mcgp::race_events_kernel<false>;
-    for (uint32_t si = 0; si < n_scenarios; ++si) {
-        blockIdx.y = si;
-        kernel(&kp, &st, scen.data(), stop_laps.data(), event_laps.data(), n_sims, sim_offset, (uint32_t)seed,
-               (uint32_t)(seed >> 32), hist, stage, ev_stage, (uint32_t)n_sims);
-    }
-    if (delta || events_cnt) {
-        gridDim = {grid_x, n_scenarios, 1};
-        for (uint32_t y = 0; y < n_scenarios; ++y)
-            for (uint32_t x = 0; x < grid_x; ++x) {
-                blockIdx = {x, y, 0};
-                mcgp::events_count(stage, ev_stage, n_sims, n, (uint32_t)L, delta, events_cnt);
-            }
-    }
-    one_thread_block(1);
-    return MCGP_OK;
+    return scenario_run(mcgp::kRuleEvents, cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, nullptr, nullptr,
+                        event_count, events, nullptr, nullptr, n_sims, sim_offset, seed, hist, stage, ev_stage, nullptr, delta,
+                        nullptr, events_cnt, nullptr, grid_x, err);
 }
 
-// race_paces_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every scenario,
-// plans and offsets packed by plan_pack.h and pace_pack.h.  hist [S][n][n] is accumulated into; stage [S][n_sims][n]
-// (classified position of each driver) and car_stage [S][n_sims][n] u16 (the laps carried, at the drivers with an
-// UNTIL_STOP offset; NULL: not staged) are written.  delta [S][n][2n - 1] and carried [S][n][L + 1] (either may be NULL;
-// carried needs car_stage) are accumulated into by paces_count, run as grid_x x S x (1 + n) blocks of one thread (both
-// NULL: not run): the centre bin and column 0 stay what they were, as on the device.
 int emu_paces_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
                   uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
                   const uint32_t *pace_count, const mcgp_pace_offset *paces, uint64_t n_sims, uint64_t sim_offset,
                   uint64_t seed, unsigned long long *hist, uint8_t *stage, uint16_t *car_stage, unsigned long long *delta,
                   unsigned long long *carried, uint32_t grid_x, const char **err)
 {
-    static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
-        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    if (carried && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
-    const int L = cfg->total_laps;
-    mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-        st.sim_offset = sim_offset;
-    }
-    const int first_lap = state ? st.lap + 1 : 2;
-    std::vector<mcgp::StrategyScenario> scen;
-    std::vector<mcgp::StopLap> stop_laps;
-    std::vector<mcgp::PaceScenario> pscen;
-    std::vector<mcgp::PaceLap> pace_laps;
-    std::vector<double> lap_sec;
-    uint64_t n_paces = 0;
-    std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, state != nullptr, &scen, &stop_laps);
-    if (e.empty()) e = mcgp::check_pace_counts(n_scenarios, pace_count, &n_paces);
-    if (e.empty() && n_paces && !paces) e = "paces is NULL";
-    if (e.empty())      // lap 1 reads the base pace too: from the grid an offset may name it
-        e = mcgp::pack_paces(n_scenarios, pace_count, paces, n, L, state ? first_lap : 1, state != nullptr, &pscen, &pace_laps,
-                             &lap_sec);
-    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    one_thread_block(n_scenarios);
-    const auto kernel = state ? &mcgp::race_paces_kernel<true> : &mcgp::race_paces_kernel<false>;
-    for (uint32_t si = 0; si < n_scenarios; ++si) {
-        blockIdx.y = si;
-        kernel(&kp, &st, scen.data(), stop_laps.data(), pscen.data(), pace_laps.data(), lap_sec.data(), n_sims, sim_offset,
-               (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage, car_stage, (uint32_t)n_sims);
-    }
-    if (delta || carried) {
-        const uint32_t gz = carried ? 1u + n : 1u;
-        gridDim = {grid_x, n_scenarios, gz};
-        for (uint32_t z = 0; z < gz; ++z)
-            for (uint32_t y = 0; y < n_scenarios; ++y)
-                for (uint32_t x = 0; x < grid_x; ++x) {
-                    blockIdx = {x, y, z};
-                    mcgp::paces_count(stage, car_stage, pscen.data(), n_sims, n, (uint32_t)L, delta, carried);
-                }
-    }
-    one_thread_block(1);
-    return MCGP_OK;
+    return scenario_run(mcgp::kRulePaces, cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, nullptr, nullptr,
+                        nullptr, nullptr, pace_count, paces, n_sims, sim_offset, seed, hist, stage, nullptr, car_stage, delta,
+                        nullptr, nullptr, carried, grid_x, err);
 }
 
-// race_combined_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims) of every
-// scenario, plans, penalties, overrides and offsets packed by plan_pack.h, penalty_pack.h, event_pack.h and pace_pack.h
-// (a NULL count array: none in any scenario).  hist [S][n][n] is accumulated into; stage [S][n_sims][n] (position |
-// fate << 5) is written, and ev_stage [S][n_sims] and car_stage [S][n_sims][n] u16 where given (NULL: not staged).  delta
-// [S][n][2n - 1], fate [S][n][4], events_cnt [S][3][L + 1] (needs ev_stage) and carried [S][n][L + 1] (needs car_stage),
-// each of which may be NULL, are accumulated into as the C ABI does it: delta and fate by penalties_count, events_cnt by
-// events_count and carried by paces_count, both with delta NULL, as grid_x (x S (x 1 + n)) blocks of one thread.
 int emu_combined_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
                      uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
                      const uint32_t *penalty_count, const mcgp_time_penalty *penalties, const uint32_t *event_count,
@@ -495,72 +412,11 @@ int emu_combined_run(const mcgp_config *cfg, const mcgp_drivers *drv, const doub
                      uint16_t *car_stage, unsigned long long *delta, unsigned long long *fate, unsigned long long *events_cnt,
                      unsigned long long *carried, uint32_t grid_x, const char **err)
 {
-    static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if (n_scenarios < 1 || n_scenarios > mcgp::kMaxStrategyScenarios)
-        return fail(MCGP_E_BAD_ARG, "n_scenarios must be in [1, 64]", err);
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    if (events_cnt && !ev_stage) return fail(MCGP_E_BAD_ARG, "events_cnt needs ev_stage", err);
-    if (carried && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
     static const uint32_t none[mcgp::kMaxStrategyScenarios] = {};
-    if (!penalty_count) penalty_count = none;
-    if (!event_count) event_count = none;
-    if (!pace_count) pace_count = none;
-    const int L = cfg->total_laps;
-    mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, L, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-        st.sim_offset = sim_offset;
-    }
-    const int first_lap = state ? st.lap + 1 : 2;
-    const bool resumed = state != nullptr;
-    std::vector<mcgp::StrategyScenario> scen;
-    std::vector<mcgp::StopLap> stop_laps;
-    std::vector<mcgp::PenaltyScenario> pens;
-    std::vector<mcgp::PenaltyLap> pen_laps;
-    std::vector<uint8_t> event_laps;
-    std::vector<mcgp::PaceScenario> pscen;
-    std::vector<mcgp::PaceLap> pace_laps;
-    std::vector<double> lap_sec;
-    uint64_t n_pens = 0, n_events = 0, n_paces = 0;
-    std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, resumed, &scen, &stop_laps);
-    if (e.empty()) e = mcgp::check_penalty_counts(n_scenarios, penalty_count, &n_pens);
-    if (e.empty()) e = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
-    if (e.empty()) e = mcgp::check_pace_counts(n_scenarios, pace_count, &n_paces);
-    if (e.empty() && n_pens && !penalties) e = "penalties is NULL";
-    if (e.empty() && n_events && !events) e = "events is NULL";
-    if (e.empty() && n_paces && !paces) e = "paces is NULL";
-    if (e.empty()) e = mcgp::pack_penalties(n_scenarios, penalty_count, penalties, n, L, first_lap, resumed, &pens, &pen_laps);
-    if (e.empty()) e = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, resumed, &event_laps);
-    if (e.empty())      // lap 1 reads the base pace too: from the grid an offset may name it
-        e = mcgp::pack_paces(n_scenarios, pace_count, paces, n, L, state ? first_lap : 1, resumed, &pscen, &pace_laps, &lap_sec);
-    if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    one_thread_block(n_scenarios);
-    const auto kernel = state ? &mcgp::race_combined_kernel<true> : &mcgp::race_combined_kernel<false>;
-    for (uint32_t si = 0; si < n_scenarios; ++si) {
-        blockIdx.y = si;
-        kernel(&kp, &st, scen.data(), stop_laps.data(), pens.data(), pen_laps.data(), event_laps.data(), pscen.data(),
-               pace_laps.data(), lap_sec.data(), n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
-               ev_stage, car_stage, (uint32_t)n_sims);
-    }
-    const uint32_t gz = carried ? 1u + n : 1u;
-    for (uint32_t z = 0; z < gz; ++z)
-        for (uint32_t y = 0; y < n_scenarios; ++y)
-            for (uint32_t x = 0; x < grid_x; ++x) {
-                blockIdx = {x, y, z};
-                if (z == 0) {
-                    gridDim = {grid_x, n_scenarios, 1};
-                    if (delta || fate) mcgp::penalties_count(stage, n_sims, n, delta, fate);
-                    if (events_cnt) mcgp::events_count(stage, ev_stage, n_sims, n, (uint32_t)L, nullptr, events_cnt);
-                }
-                gridDim = {grid_x, n_scenarios, gz};
-                if (carried) mcgp::paces_count(stage, car_stage, pscen.data(), n_sims, n, (uint32_t)L, nullptr, carried);
-            }
-    one_thread_block(1);
-    return MCGP_OK;
+    return scenario_run(mcgp::kRuleAll, cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans,
+                        penalty_count ? penalty_count : none, penalties, event_count ? event_count : none, events,
+                        pace_count ? pace_count : none, paces, n_sims, sim_offset, seed, hist, stage, ev_stage, car_stage, delta,
+                        fate, events_cnt, carried, grid_x, err);
 }
 
 }  // extern "C"

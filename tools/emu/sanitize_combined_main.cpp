@@ -7,7 +7,7 @@
 //       tools/emu/sanitize_combined_main.cpp tools/emu/emu_generic.cpp -o san_combined
 //
 // (-fno-sanitize=alignment for the reason given in sanitize_bonus_main.cpp: a block of one thread.)  It runs
-// emu_combined_run (race_combined_kernel<false>, then penalties_count, events_count and paces_count as blocks of one
+// emu_combined_run (race_scenario_kernel<false, kRuleAll>, then penalties_count, events_count and paces_count as blocks of one
 // thread) at the limits: 64 scenarios on 3 cars over 70 laps, each with 64 single-lap offsets, 64 single-lap overrides
 // and additions on 64 laps; 1000 laps on 2 cars that cannot retire, with a penalty to serve and an offset from lap 2
 // under a plan whose only stop is on lap 1000; a race of one lap (penalties and events cannot name lap 1: only an offset

@@ -6,7 +6,7 @@
 //       tools/emu/sanitize_events_main.cpp tools/emu/emu_generic.cpp -o san_events
 //
 // (-fno-sanitize=alignment for the reason given in sanitize_bonus_main.cpp: a block of one thread.)  It runs
-// emu_events_run (race_events_kernel<false>, then events_count as blocks of one thread) on fields of 1, 2, 20 and 32
+// emu_events_run (race_scenario_kernel<false, kRuleEvents>, then events_count as blocks of one thread) on fields of 1, 2, 20 and 32
 // cars, a race of two laps and one of 1000, under scenarios that hold every kind on single laps (the first and the last
 // included), a whole-race range of each kind, the most overrides a scenario takes (64) and a planned stop on a forced
 // safety-car lap; every buffer on the heap at exactly its size.  It checks that every staged row is a permutation, that

@@ -6,7 +6,7 @@
 //       tools/emu/sanitize_paces_main.cpp tools/emu/emu_generic.cpp -o san_paces
 //
 // (-fno-sanitize=alignment for the reason given in sanitize_bonus_main.cpp: a block of one thread.)  It runs
-// emu_paces_run (race_paces_kernel<false>, then paces_count as blocks of one thread) at the limits: 64 scenarios of 64
+// emu_paces_run (race_scenario_kernel<false, kRulePaces>, then paces_count as blocks of one thread) at the limits: 64 scenarios of 64
 // single-lap offsets on 3 cars over 70 laps; 1000 laps on 2 cars with an UNTIL_STOP offset from lap 1 that no stop
 // clears and two LAPS ranges that meet; a race of one lap with an offset on lap 1; and 32 cars with offsets of both kinds
 // on drivers 0 and 31; every buffer on the heap at exactly its size.  It checks that every staged row is a permutation,

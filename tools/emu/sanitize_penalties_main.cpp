@@ -6,7 +6,7 @@
 //       tools/emu/sanitize_penalties_main.cpp tools/emu/emu_generic.cpp -o san_penalties
 //
 // (-fno-sanitize=alignment for the reason given in sanitize_bonus_main.cpp: a block of one thread.)  It runs
-// emu_penalties_run (race_penalties_kernel<false>, then penalties_count as blocks of one thread) on fields of 1, 2, 20
+// emu_penalties_run (race_scenario_kernel<false, kRulePenalties>, then penalties_count as blocks of one thread) on fields of 1, 2, 20
 // and 32 cars and a race of two laps, under scenarios that hold every kind of penalty, the most penalties a scenario
 // takes (256), a planned stop that serves a penalty, and driver n - 1 (mask bit 31 at 32 cars); every buffer on the heap
 // at exactly its size.  It checks that every staged row is a permutation with fate bits that agree with the scenario,
