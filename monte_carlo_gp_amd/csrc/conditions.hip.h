@@ -1,7 +1,7 @@
 // conditions.hip.h -- combination and conditional odds, counted on the device (mcgp_run_conditions, include/mcgp.h).
 //
 // race_conditions_kernel runs mcgp_run's simulations (from the grid, kFromState false) or mcgp_run_from_state's (from one
-// state) with the generic kernel's code -- start_from_grid or start_from_state, run_laps, classify_and_count -- and a
+// state) with the generic kernel's code -- run_observed (resume.hip.h), the analysis kernels' shared lane body -- and a
 // per-lap observer that only counts the lap's event (EventCounter: three registers, no store).  Simulation i draws
 // exactly what those calls' simulation i draws, so the position histogram is theirs.  At the flag the lane holds every
 // fact a condition may ask for, all integers:
@@ -116,27 +116,21 @@ race_conditions_kernel(const KParams *__restrict__ P, const ResumeState *__restr
                        unsigned long long *__restrict__ hist, uint8_t *__restrict__ stage, uint64_t stride,
                        uint32_t n_batches)
 {
-    run_block(P, m, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
-        const uint64_t sim = sim_offset + local;
-        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-        const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
-                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr);
-        EventCounter ev = {0u, 0u, 0u};
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, ev);          // reference :166-228
-        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
-
-        // the staged order, the inverse of `ord` and the finishers
-        uint8_t *lane = stage + local;
-        int32_t finishers = 0;
-        for (int p = 0; p < e.n; ++p) {
-            const uint32_t d = s.Ord(p);
-            lane[(uint64_t)p * stride] = (uint8_t)d;
-            s.Out(d) = (uint16_t)(p + 1);
-            finishers += (s.Pk(d) & kDnf) ? 0 : 1;
-        }
-        reinterpret_cast<uint64_t *>(stage + (uint64_t)e.n * stride)[local] =
-            evaluate_conditions(s, conds, n_conditions, finishers, ev);
-    });
+    run_observed<kFromState>(P, state, m, sim_offset, seed_lo, seed_hi, hist, n_batches,
+        [](const Rows &, const LapEnv &, const RaceStart &, uint64_t) { return EventCounter{0u, 0u, 0u}; },
+        [=](const Rows &s, const LapEnv &e, const EventCounter &ev, uint64_t local) {
+            // the staged order, the inverse of `ord` and the finishers
+            uint8_t *lane = stage + local;
+            int32_t finishers = 0;
+            for (int p = 0; p < e.n; ++p) {
+                const uint32_t d = s.Ord(p);
+                lane[(uint64_t)p * stride] = (uint8_t)d;
+                s.Out(d) = (uint16_t)(p + 1);
+                finishers += (s.Pk(d) & kDnf) ? 0 : 1;
+            }
+            reinterpret_cast<uint64_t *>(stage + (uint64_t)e.n * stride)[local] =
+                evaluate_conditions(s, conds, n_conditions, finishers, ev);
+        });
 }
 
 // The staged orders' and masks' counts of m simulations, added into count [C] and, unless NULL, cond_hist [C][n][n]

@@ -1,7 +1,7 @@
 // gaps.hip.h -- the time gaps of a race, counted on the device (mcgp_run_gaps, include/mcgp.h).
 //
 // race_gaps_kernel runs mcgp_run's simulations (from the grid, kFromState false) or mcgp_run_from_state's (from one
-// state) with the generic kernel's code -- start_from_grid or start_from_state, run_laps, classify_and_count -- and
+// state) with the generic kernel's code -- run_observed (resume.hip.h), the analysis kernels' shared lane body -- and
 // a per-lap observer (GapObserver) that sees the rows after update_positions of every recorded lap: laps 1..L from the
 // grid, laps k + 1 .. L from a state after lap k.  Simulation i draws exactly what those calls' simulation i draws, so
 // the position histogram is theirs.  Read at that point of a lap (the state the CPU oracle's per-lap trace records):
@@ -113,27 +113,14 @@ race_gaps_kernel(const KParams *__restrict__ P, const ResumeState *__restrict__ 
                  uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist, uint8_t *__restrict__ stage,
                  uint64_t stride, uint32_t n_batches)
 {
-    run_block(P, m, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
-        const uint64_t sim = sim_offset + local;
-        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-        const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
-                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr);
-
-        GapObserver obs;
-        obs.lane = stage + local;
-        obs.lap_bytes = (uint64_t)(e.n + 1 + (int)n_pairs) * stride;
-        obs.stride = stride;
-        obs.edges = edges;
-        obs.pairs = pairs;
-        obs.n_edges = n_edges;
-        obs.n_pairs = n_pairs;
-        obs.n = e.n;
-        obs.first_lap = kFromState ? at.first_lap : 1;
-        if (!kFromState) obs(s, 1, kEventNone);
-
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, obs);         // reference :166-228
-        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
-    });
+    run_observed<kFromState>(P, state, m, sim_offset, seed_lo, seed_hi, hist, n_batches,
+        [=](const Rows &s, const LapEnv &e, const RaceStart &at, uint64_t local) {
+            GapObserver obs = {stage + local, (uint64_t)(e.n + 1 + (int)n_pairs) * stride, stride, edges, pairs, n_edges, n_pairs,
+                               e.n, kFromState ? at.first_lap : 1};
+            if (!kFromState) obs(s, 1, kEventNone);
+            return obs;
+        },
+        [](const Rows &, const LapEnv &, const GapObserver &, uint64_t) {});
 }
 
 // The staged rows' counts of m simulations, added into their places: staged row q = lap_index R + j (lap_index = lap -

@@ -529,9 +529,10 @@ uint64_t max_sims_per_launch()
 // with orders_out): the staging holds kOrdersChunk x n bytes.
 constexpr uint64_t kOrdersChunk = 1ull << 22;
 
-// Staging budgets of mcgp_run_trace (one byte per lap, driver and simulation) and mcgp_run_strategies and
-// mcgp_run_penalties (one byte per scenario, simulation and driver; mcgp_run_events one u32 per scenario and simulation
-// more): device memory does not grow with n_sims.
+// Staging budgets, so that device memory does not grow with n_sims: of mcgp_run_trace (one byte per lap, driver and
+// simulation) and of the five scenario calls, mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces
+// and mcgp_run_combined (per scenario and simulation a byte per driver, and what the kind stages beside it:
+// ScenarioKind::sim_bytes)
 constexpr uint64_t kTraceStageBytes = 512ull << 20;
 constexpr uint64_t kStrategyStageBytes = 256ull << 20;
 // ... and of mcgp_run_gaps: one byte per recorded lap, row (n drivers + 1 lead + n_pairs pairs) and simulation.
@@ -553,7 +554,7 @@ uint64_t stage_chunk_sims(uint64_t budget, uint64_t bytes_per_sim)
 }
 
 // ... rounded down to whole rounds of the device under the generic-shaped `kernel` (every resident block one batch: a
-// chunk of 5.5 rounds costs 6), and at most n_sims (mcgp_run_trace, mcgp_run_gaps).
+// chunk of 5.5 rounds costs 6), and at most n_sims (run_analysis: the trace, gaps, conditions, stints and moves calls).
 uint64_t stage_chunk_rounds(const DeviceCtx &c, uint32_t n, KernelFn kernel, uint64_t budget, uint64_t bytes_per_sim,
                             uint64_t n_sims)
 {
@@ -1196,6 +1197,110 @@ ScenarioOutput carried_output(uint64_t *carried_out, const mcgp_config *cfg)
                     c[row * w] = n_sims - rest;
                 }
             }};
+}
+
+// One chunk of an analysis call as its kernels are launched: `grid` blocks of `block` threads over simulations first_sim
+// .. first_sim + m - 1, staged in rows of `stride` items, and the call's counts on the device.
+struct AnalysisChunk {
+    uint32_t grid, block, lds, n_batches;
+    uint64_t m, first_sim, stride;
+    uint32_t seed_lo, seed_hi;
+    uint64_t grid_cap;                      // blocks of a counting kernel the device holds at once (count_grid_x)
+    const mcgp::KParams *kp;
+    const mcgp::ResumeState *st;            // zero from the grid
+    const Layout *ws;
+    const std::vector<CountSeg> *segs;
+    unsigned long long *count(size_t i) const { return ws->count(i); }
+    // ... NULL for a segment that is not wanted
+    unsigned long long *wanted(size_t i) const { return (*segs)[i].dst ? ws->count(i) : nullptr; }
+};
+
+// What the checked arguments give: known once the parameter block and the state have been accepted.
+struct AnalysisPlan {
+    std::vector<CountSeg> segs;             // the call's counts, hist [n][n] first
+    uint64_t sim_bytes;                     // staged per simulation, out of the kind's budget
+    size_t count_lds = 0;                   // dynamic LDS of its counting kernel's block (0: none to check)
+    const void *count_fn = nullptr;         // that kernel, where it may need more than the default limit
+};
+
+// What mcgp_run_trace, mcgp_run_gaps, mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves each have of their own;
+// run_analysis has the rest.
+struct AnalysisKind {
+    const char *what;                       // the call in check_deviates_32's message
+    // generic_geometry's name of the race kernel (and the counting kernel's in the LDS message), note_launch's name
+    const char *geo_name, *kernel_name;
+    // the instantiation that runs, chosen where its type is known; its register count shapes the launch
+    KernelFn kernel;
+    uint64_t budget;                        // bytes of staging (kTraceStageBytes ...)
+    // the output beside hist_out that must be given, and its name; NULL name: a call from the grid only (mcgp_run_trace),
+    // which has checked its pointers with its own message
+    const char *required_name;
+    const uint64_t *required_out;
+    // the call's own checks: behind the source, before the parameter block / behind it (n is checked), before the state
+    std::function<int()> check_args, check_fields;
+    std::function<AnalysisPlan(uint32_t L, uint32_t lap)> plan;          // lap: the state's, 0 from the grid
+    std::function<void(Layout &, uint64_t stride)> regions;              // its staging and its tables
+    std::function<int(const AnalysisChunk &)> launch;                    // the race kernel and its counting kernels
+};
+
+int32_t run_analysis(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                     uint32_t n, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out,
+                     const AnalysisKind &k)
+{
+    // ---- every argument is checked before any device is looked up
+    int rc = MCGP_OK;
+    if (k.required_name) {
+        if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
+        if (!k.required_out) return fail(MCGP_E_BAD_ARG, std::string(k.required_name) + " is NULL");
+        rc = check_source(grid_probs, state);
+        if (rc != MCGP_OK) return rc;
+    }
+    if (k.check_args && (rc = k.check_args()) != MCGP_OK) return rc;
+    std::vector<mcgp::KParams> kps(1);
+    mcgp::KParams &kp = kps[0];
+    rc = build_params_32(cfg, drv, grid_probs, n, k.what, &kp);
+    if (rc != MCGP_OK) return rc;
+    if (k.check_fields && (rc = k.check_fields()) != MCGP_OK) return rc;
+    const uint32_t L = (uint32_t)cfg->total_laps;
+    mcgp::ResumeState st;
+    rc = pack_state(state, n, (int)L, 0, &st);
+    if (rc != MCGP_OK) return rc;
+    if (n_sims == 0) return MCGP_OK;
+    const AnalysisPlan p = k.plan(L, state ? (uint32_t)st.lap : 0u);
+    Counts counts;
+    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
+        const uint64_t chunk = stage_chunk_rounds(c, n, k.kernel, k.budget, p.sim_bytes, n_sims);
+        // workspace: the kind's staging of one chunk, in rows of `stride` items (a multiple of 256: whole, aligned words
+        // for the counting kernels), and its tables | parameter block | state | the counts
+        AnalysisChunk a = {};
+        a.stride = (chunk + 255) / 256 * 256;
+        Layout ws;
+        k.regions(ws, a.stride);
+        ws.add(&a.kp, 1, &kp);
+        if (k.required_name) ws.add(&a.st, 1, &st);
+        ws.counts(p.segs);
+        const int r = ws.commit(c.work);
+        if (r != MCGP_OK) return r;
+        if (p.count_lds > c.lds_per_block)
+            return fail(MCGP_E_HIP, std::string("the ") + k.geo_name + " counting kernel's block needs " +
+                                        std::to_string(p.count_lds) + " bytes of LDS, the device offers " +
+                                        std::to_string(c.lds_per_block) + " per block");
+        if (p.count_fn)
+            HIP_TRY(hipFuncSetAttribute(p.count_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k.kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)c.lds_per_block));
+        a.ws = &ws, a.segs = &p.segs;
+        a.seed_lo = (uint32_t)seed, a.seed_hi = (uint32_t)(seed >> 32);
+        a.grid_cap = (uint64_t)c.cu_count * 8;
+        return staged_run(c, k.kernel, k.geo_name, k.kernel_name, n, 1, n_sims, chunk, ws, counts,
+                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
+            a.grid = grid, a.block = block, a.lds = lds, a.n_batches = n_batches, a.m = m, a.first_sim = sim_offset + done;
+            return k.launch(a);
+        });
+    });
+    if (rc != MCGP_OK) return rc;
+    counts.add_to(p.segs);
+    return MCGP_OK;
 }
 
 }  // namespace
@@ -1979,8 +2084,9 @@ int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const
     rc = check_wide(kp);
     if (rc != MCGP_OK) return rc;
     if (n_sims == 0) return MCGP_OK;
-    const size_t pair_cells = (size_t)n * n, podium_cells = podium_out ? (size_t)n * n * n : 0;
-    const size_t cells = 2 * pair_cells + podium_cells;
+    // hist [n][n] | ahead [n][n] | podium [n][n][n]
+    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n}, {ahead_out, (size_t)n * n},
+                                           {podium_out, podium_out ? (size_t)n * n * n : 0}};
     Counts counts;
     rc = on_device(device, true, [&](DeviceCtx &c) -> int {
         // block shape: the widest block whose LDS fits the device's budget, with the podium table in LDS if any block
@@ -2004,16 +2110,14 @@ int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const
         const uint32_t lds = mcgp::match_lds(n, block, mode == mcgp::kPodiumLds).bytes;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::race_matchups),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        // workspace: orders staging of one chunk | hist | ahead | podium
+        // workspace: orders staging of one chunk | the counts
         const uint64_t cap = std::min<uint64_t>(n_sims, mcgp::kMatchMaxSims);
+        uint8_t *d_orders;
         Layout ws;
-        const size_t o_orders = ws.add(cap * n), o_cnt = ws.add(cells * 8);
-        int r = c.work.reserve(ws.bytes);
+        ws.add(&d_orders, cap * n);
+        ws.counts(segs);
+        int r = ws.commit(c.work);
         if (r != MCGP_OK) return r;
-        uint8_t *d_orders = c.work.at<uint8_t>(o_orders);
-        unsigned long long *h_hist = c.work.at<unsigned long long>(o_cnt), *h_ahead = h_hist + pair_cells;
-        unsigned long long *h_podium = h_ahead + pair_cells;
-        HIP_TRY(hipMemsetAsync(h_hist, 0, cells * 8, nullptr));
         uint64_t per_cu = budget / lds;
         if (per_cu > 8) per_cu = 8;
         if (per_cu < 1) per_cu = 1;
@@ -2022,17 +2126,17 @@ int32_t mcgp_run_matchups(const mcgp_config *cfg, const mcgp_drivers *drv, const
             const uint64_t m = (n_sims - done) < cap ? (n_sims - done) : cap;
             // the chunk's race through mcgp_run's own launch path (the position histogram is counted there), its
             // orders into the staging buffer, then counted before the next chunk overwrites them
-            r = launch(c, kp, m, sim_offset + done, seed, nullptr, h_hist, d_orders, nullptr);
+            r = launch(c, kp, m, sim_offset + done, seed, nullptr, ws.count(0), d_orders, nullptr);
             if (r != MCGP_OK) return r;
             const uint64_t tiles = (m + block - 1) / block;
             hipLaunchKernelGGL(mcgp::race_matchups, dim3((uint32_t)std::min(tiles, grid_cap)), dim3(block), lds, nullptr,
-                               d_orders, m, n, mode, h_ahead, podium_out ? h_podium : nullptr);
+                               d_orders, m, n, mode, ws.count(1), podium_out ? ws.count(2) : nullptr);
             HIP_TRY(hipGetLastError());
         }
-        return counts.download(h_hist, cells);
+        return counts.download(ws);
     });
     if (rc != MCGP_OK) return rc;
-    counts.add_to({{hist_out, pair_cells}, {ahead_out, pair_cells}, {podium_out, podium_cells}});
+    counts.add_to(segs);
     return MCGP_OK;
 }
 
@@ -2106,69 +2210,47 @@ int32_t mcgp_run_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                        uint64_t *lap_pos_out, uint64_t *laps_led_out, uint64_t *stops_out, uint64_t *fastest_out,
                        uint64_t *events_out)
 {
-    // ---- every argument is checked before any device is looked up
     if (!grid_probs || !hist_out || !lap_pos_out) return fail(MCGP_E_BAD_ARG, "grid_probs / hist_out / lap_pos_out is NULL");
-    std::vector<mcgp::KParams> kps(1);
-    mcgp::KParams &kp = kps[0];
-    int rc = build_params_32(cfg, drv, grid_probs, n, "a trace runs", &kp);
-    if (rc != MCGP_OK) return rc;
-    if (n_sims == 0) return MCGP_OK;
-    const uint32_t L = (uint32_t)kp.total_laps;
-    const uint32_t rows = L * n;
-    const size_t c_laps = (size_t)n * (L + 1);
-    // hist [n][n] | lap_pos [L][n][n + 1] | laps_led [n][L + 1] | stops [n][L + 1] | fastest [n] | events [3][L + 1]
-    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n}, {lap_pos_out, (size_t)rows * (n + 1)},
-                                           {laps_led_out, c_laps},    {stops_out, c_laps},
-                                           {fastest_out, n},          {events_out, 3 * (size_t)(L + 1)}};
-    Counts counts;
-    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        const KernelFn geo_fn = reinterpret_cast<KernelFn>(&mcgp::race_trace_kernel);   // (for its register count)
-        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kTraceStageBytes, (uint64_t)L * n, n_sims);
-        // workspace: staging of one chunk in rows of `stride` bytes (a multiple of 256: whole, aligned words for the
-        // counting kernels) | the chunk's records | parameter block | the counts
-        const uint64_t stride = (chunk + 255) / 256 * 256;
-        uint8_t *d_stage;
-        uint64_t *d_rec;
-        const mcgp::KParams *d_kp;
-        Layout ws;
+    uint32_t L = 0, rows = 0;
+    uint8_t *d_stage;
+    uint64_t *d_rec;
+    AnalysisKind k = {"a trace runs", "trace", "mcgp::race_trace_kernel", reinterpret_cast<KernelFn>(&mcgp::race_trace_kernel),
+                      kTraceStageBytes};
+    k.plan = [&](uint32_t laps, uint32_t) {
+        L = laps, rows = L * n;
+        const size_t c_laps = (size_t)n * (L + 1);
+        // hist [n][n] | lap_pos [L][n][n + 1] | laps_led [n][L + 1] | stops [n][L + 1] | fastest [n] | events [3][L + 1]
+        return AnalysisPlan{{{hist_out, (size_t)n * n}, {lap_pos_out, (size_t)rows * (n + 1)}, {laps_led_out, c_laps},
+                             {stops_out, c_laps}, {fastest_out, n}, {events_out, 3 * (size_t)(L + 1)}},
+                            rows};
+    };
+    // staging of one chunk, L n rows of `stride` bytes | the chunk's records
+    k.regions = [&](Layout &ws, uint64_t stride) {
         ws.add(&d_stage, (size_t)rows * stride);
         ws.add(&d_rec, (size_t)stride);
-        ws.add(&d_kp, 1, &kp);
-        ws.counts(segs);
-        const int r = ws.commit(c.work);
-        if (r != MCGP_OK) return r;
-        unsigned long long *d_hist = ws.count(0), *d_pos = ws.count(1), *d_led = ws.count(2), *d_stops = ws.count(3);
-        unsigned long long *d_fast = ws.count(4), *d_ev = ws.count(5);
-        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
-        const size_t laps_lds = 2 * (size_t)(L + 1) * 4, rec_lds = ((size_t)mcgp::kMaxCars + 3 * (size_t)(L + 1)) * 4;
-        return staged_run(c, geo_fn, "trace", "mcgp::race_trace_kernel", n, 1, n_sims, chunk, ws, counts,
-                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
-            hipLaunchKernelGGL(mcgp::race_trace_kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), d_hist, d_stage, stride, d_rec, n_batches);
+    };
+    k.launch = [&](const AnalysisChunk &a) -> int {
+        hipLaunchKernelGGL(mcgp::race_trace_kernel, dim3(a.grid), dim3(a.block), a.lds, nullptr, a.kp, a.m, a.first_sim, a.seed_lo,
+                           a.seed_hi, a.count(0), d_stage, a.stride, d_rec, a.n_batches);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(mcgp::trace_count_positions, dim3((uint32_t)std::min<uint64_t>(rows, a.grid_cap)),
+                           dim3(mcgp::kTraceCountBlock), 0, nullptr, d_stage, a.stride, a.m, rows, n, a.count(1));
+        HIP_TRY(hipGetLastError());
+        if (laps_led_out || stops_out) {
+            hipLaunchKernelGGL(mcgp::trace_count_laps, dim3(count_grid_x((a.m + 3) / 4, mcgp::kTraceCountBlock, a.grid_cap, n), n),
+                               dim3(mcgp::kTraceCountBlock), 2 * (size_t)(L + 1) * 4, nullptr, d_stage, a.stride, a.m, n, L,
+                               a.count(2), a.count(3));
             HIP_TRY(hipGetLastError());
-            const uint64_t words = (m + 3) / 4;
-            const uint64_t tiles = (words + mcgp::kTraceCountBlock - 1) / mcgp::kTraceCountBlock;
-            hipLaunchKernelGGL(mcgp::trace_count_positions, dim3((uint32_t)std::min<uint64_t>(rows, grid_cap)),
-                               dim3(mcgp::kTraceCountBlock), 0, nullptr, d_stage, stride, m, rows, n, d_pos);
+        }
+        if (fastest_out || events_out) {
+            hipLaunchKernelGGL(mcgp::trace_count_records, dim3(count_grid_x(a.m, mcgp::kTraceCountBlock, a.grid_cap, 1)),
+                               dim3(mcgp::kTraceCountBlock), ((size_t)mcgp::kMaxCars + 3 * (size_t)(L + 1)) * 4, nullptr, d_rec,
+                               a.m, n, L, a.count(4), a.count(5));
             HIP_TRY(hipGetLastError());
-            if (laps_led_out || stops_out) {
-                const uint64_t gx = std::max<uint64_t>(1, std::min<uint64_t>(tiles, grid_cap / n));
-                hipLaunchKernelGGL(mcgp::trace_count_laps, dim3((uint32_t)gx, n), dim3(mcgp::kTraceCountBlock), laps_lds,
-                                   nullptr, d_stage, stride, m, n, L, d_led, d_stops);
-                HIP_TRY(hipGetLastError());
-            }
-            if (fastest_out || events_out) {
-                const uint64_t rtiles = (m + mcgp::kTraceCountBlock - 1) / mcgp::kTraceCountBlock;
-                hipLaunchKernelGGL(mcgp::trace_count_records, dim3((uint32_t)std::min<uint64_t>(rtiles, grid_cap)),
-                                   dim3(mcgp::kTraceCountBlock), rec_lds, nullptr, d_rec, m, n, L, d_fast, d_ev);
-                HIP_TRY(hipGetLastError());
-            }
-            return MCGP_OK;
-        });
-    });
-    if (rc != MCGP_OK) return rc;
-    counts.add_to(segs);
-    return MCGP_OK;
+        }
+        return MCGP_OK;
+    };
+    return run_analysis(cfg, drv, grid_probs, nullptr, n, n_sims, sim_offset, seed, device, hist_out, k);
 }
 
 int32_t mcgp_run_strategies(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
@@ -2349,99 +2431,70 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
                       const uint8_t *pairs, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device,
                       uint64_t *hist_out, uint64_t *lap_gap_out, uint64_t *lead_out, uint64_t *pair_out)
 {
-    // ---- every argument is checked before any device is looked up
-    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
-    if (!lap_gap_out) return fail(MCGP_E_BAD_ARG, "lap_gap_out is NULL");
-    int rc = check_source(grid_probs, state);
-    if (rc != MCGP_OK) return rc;
-    if (n_edges < 1 || n_edges > mcgp::kMaxGapEdges) return fail(MCGP_E_BAD_ARG, "n_edges must be in [1, 63]");
-    if (!edges) return fail(MCGP_E_BAD_ARG, "edges is NULL");
-    for (uint32_t i = 0; i < n_edges; ++i) {
-        if (!std::isfinite(edges[i])) return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] is not finite");
-        if (i == 0 && !(edges[0] > 0.0)) return fail(MCGP_E_BAD_ARG, "edges[0] must be > 0");
-        if (i > 0 && !(edges[i] > edges[i - 1]))
-            return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] must be above edges[" + std::to_string(i - 1) + "]");
-    }
-    if (n_pairs > mcgp::kMaxGapPairs) return fail(MCGP_E_BAD_ARG, "n_pairs must be in [0, 64]");
-    if (n_pairs && !pairs) return fail(MCGP_E_BAD_ARG, "pairs is NULL");
-    if (n_pairs && !pair_out) return fail(MCGP_E_BAD_ARG, "pair_out is NULL");
-    if (!n_pairs && pair_out) return fail(MCGP_E_BAD_ARG, "pair_out must be NULL when n_pairs is 0");
-    std::vector<mcgp::KParams> kps(1);
-    mcgp::KParams &kp = kps[0];
-    rc = build_params_32(cfg, drv, grid_probs, n, "gaps run", &kp);
-    if (rc != MCGP_OK) return rc;
-    for (uint32_t p = 0; p < n_pairs; ++p) {
-        const uint32_t a = pairs[2 * p], b = pairs[2 * p + 1];
-        if (a >= n || b >= n)
-            return fail(MCGP_E_BAD_ARG, "pairs[" + std::to_string(p) + "]: driver index must be below n");
-        if (a == b) return fail(MCGP_E_BAD_ARG, "pairs[" + std::to_string(p) + "]: a pair needs two different drivers");
-    }
-    const uint32_t L = (uint32_t)cfg->total_laps;
-    mcgp::ResumeState st;
-    rc = pack_state(state, n, (int)L, 0, &st);
-    if (rc != MCGP_OK) return rc;
-    if (n_sims == 0) return MCGP_OK;
-    const uint32_t lap0 = state ? (uint32_t)st.lap : 0u;       // laps lap0 + 1 .. L are recorded
-    const uint32_t B = n_edges + 1, R = n + 1 + n_pairs;
-    const uint32_t rows = (L - lap0) * R;
-    // hist [n][n] | lap_gap [L][n][B + 1] | lead [L][B + 1] | pair [L][n_pairs][2B + 1]
-    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n},
-                                           {lap_gap_out, (size_t)L * n * (B + 1)},
-                                           {lead_out, (size_t)L * (B + 1)},
-                                           {pair_out, (size_t)L * n_pairs * (2 * B + 1)}};
-    Counts counts;
-    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        const auto kernel = state ? &mcgp::race_gaps_kernel<true> : &mcgp::race_gaps_kernel<false>;
-        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
-        // a race resumed after its last lap records nothing: one row's worth of staging keeps the sizes non-zero
-        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kGapsStageBytes, std::max<uint64_t>(rows, 1), n_sims);
-        // workspace: staging of one chunk in rows of `stride` bytes (a multiple of 256: whole, aligned words for the
-        // counting kernel) | parameter block | state | edges | pairs | the counts
-        const uint64_t stride = (chunk + 255) / 256 * 256;
-        double edge_table[mcgp::kGapEdgeSlots];                 // the call's edges, then +inf (gaps.hip.h: gap_bin)
+    const auto kernel = state ? &mcgp::race_gaps_kernel<true> : &mcgp::race_gaps_kernel<false>;
+    uint32_t L = 0, lap0 = 0, rows = 0;                         // laps lap0 + 1 .. L are recorded
+    const uint32_t B = n_edges + 1;
+    double edge_table[mcgp::kGapEdgeSlots];                     // the call's edges, then +inf (gaps.hip.h: gap_bin)
+    size_t count_lds = 0;
+    uint8_t *d_stage;
+    const double *d_edges;
+    const uint8_t *d_pairs;
+    AnalysisKind k = {"gaps run", "gaps", "mcgp::race_gaps_kernel", reinterpret_cast<KernelFn>(kernel), kGapsStageBytes,
+                      "lap_gap_out", lap_gap_out};
+    k.check_args = [&]() -> int {
+        if (n_edges < 1 || n_edges > mcgp::kMaxGapEdges) return fail(MCGP_E_BAD_ARG, "n_edges must be in [1, 63]");
+        if (!edges) return fail(MCGP_E_BAD_ARG, "edges is NULL");
+        for (uint32_t i = 0; i < n_edges; ++i) {
+            if (!std::isfinite(edges[i])) return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] is not finite");
+            if (i == 0 && !(edges[0] > 0.0)) return fail(MCGP_E_BAD_ARG, "edges[0] must be > 0");
+            if (i > 0 && !(edges[i] > edges[i - 1]))
+                return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] must be above edges[" + std::to_string(i - 1) + "]");
+        }
+        if (n_pairs > mcgp::kMaxGapPairs) return fail(MCGP_E_BAD_ARG, "n_pairs must be in [0, 64]");
+        if (n_pairs && !pairs) return fail(MCGP_E_BAD_ARG, "pairs is NULL");
+        if (n_pairs && !pair_out) return fail(MCGP_E_BAD_ARG, "pair_out is NULL");
+        if (!n_pairs && pair_out) return fail(MCGP_E_BAD_ARG, "pair_out must be NULL when n_pairs is 0");
+        return MCGP_OK;
+    };
+    k.check_fields = [&]() -> int {
+        for (uint32_t p = 0; p < n_pairs; ++p) {
+            const uint32_t a = pairs[2 * p], b = pairs[2 * p + 1];
+            if (a >= n || b >= n)
+                return fail(MCGP_E_BAD_ARG, "pairs[" + std::to_string(p) + "]: driver index must be below n");
+            if (a == b) return fail(MCGP_E_BAD_ARG, "pairs[" + std::to_string(p) + "]: a pair needs two different drivers");
+        }
+        return MCGP_OK;
+    };
+    k.plan = [&](uint32_t laps, uint32_t lap) {
+        L = laps, lap0 = lap, rows = (L - lap0) * (n + 1 + n_pairs);
         for (uint32_t i = 0; i < mcgp::kGapEdgeSlots; ++i) edge_table[i] = i < n_edges ? edges[i] : HUGE_VAL;
-        uint8_t *d_stage;
-        const mcgp::KParams *d_kp;
-        const mcgp::ResumeState *d_st;
-        const double *d_edges;
-        const uint8_t *d_pairs;
-        Layout ws;
+        // the counting kernel's columns: 4 x 256 bytes per value, up to 129 values (129 KiB of a CU's 160)
+        count_lds = (size_t)(n_pairs ? 2 * B + 1 : B + 1) * mcgp::kGapsCountBlock * 4;
+        // hist [n][n] | lap_gap [L][n][B + 1] | lead [L][B + 1] | pair [L][n_pairs][2B + 1].  A race resumed after its
+        // last lap records nothing: one row's worth of staging keeps the sizes non-zero
+        return AnalysisPlan{{{hist_out, (size_t)n * n}, {lap_gap_out, (size_t)L * n * (B + 1)}, {lead_out, (size_t)L * (B + 1)},
+                             {pair_out, (size_t)L * n_pairs * (2 * B + 1)}},
+                            std::max<uint64_t>(rows, 1), count_lds, reinterpret_cast<const void *>(&mcgp::gaps_count_rows)};
+    };
+    // staging of one chunk in rows of `stride` bytes | edges | pairs
+    k.regions = [&](Layout &ws, uint64_t stride) {
         ws.add(&d_stage, (size_t)std::max<uint32_t>(rows, 1) * stride);
-        ws.add(&d_kp, 1, &kp);
-        ws.add(&d_st, 1, &st);
         ws.add(&d_edges, mcgp::kGapEdgeSlots, edge_table);
         ws.add(&d_pairs, 2 * (size_t)std::max<uint32_t>(n_pairs, 1), n_pairs ? pairs : nullptr);
-        ws.counts(segs);
-        const int r = ws.commit(c.work);
-        if (r != MCGP_OK) return r;
-        // the counting kernel's columns: 4 x 256 bytes per value, up to 129 values (129 KiB of a CU's 160)
-        const size_t count_lds = (size_t)(n_pairs ? 2 * B + 1 : B + 1) * mcgp::kGapsCountBlock * 4;
-        if (count_lds > c.lds_per_block)
-            return fail(MCGP_E_HIP, "the gaps counting kernel's block needs " + std::to_string(count_lds) +
-                                        " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcgp::gaps_count_rows),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_per_block));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)c.lds_per_block));
-        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
-        return staged_run(c, geo_fn, "gaps", "mcgp::race_gaps_kernel", n, 1, n_sims, chunk, ws, counts,
-                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_edges, n_edges, d_pairs, n_pairs,
-                               m, sim_offset + done, (uint32_t)seed, (uint32_t)(seed >> 32), ws.count(0), d_stage, stride,
-                               n_batches);
+    };
+    k.launch = [&](const AnalysisChunk &a) -> int {
+        hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(a.block), a.lds, nullptr, a.kp, a.st, d_edges, n_edges, d_pairs, n_pairs,
+                           a.m, a.first_sim, a.seed_lo, a.seed_hi, a.count(0), d_stage, a.stride, a.n_batches);
+        HIP_TRY(hipGetLastError());
+        if (rows) {
+            hipLaunchKernelGGL(mcgp::gaps_count_rows, dim3((uint32_t)std::min<uint64_t>(rows, a.grid_cap)),
+                               dim3(mcgp::kGapsCountBlock), count_lds, nullptr, d_stage, a.stride, a.m, rows, n, n_pairs, B,
+                               lap0, a.count(1), a.count(2), a.count(3));
             HIP_TRY(hipGetLastError());
-            if (rows) {
-                hipLaunchKernelGGL(mcgp::gaps_count_rows, dim3((uint32_t)std::min<uint64_t>(rows, grid_cap)),
-                                   dim3(mcgp::kGapsCountBlock), count_lds, nullptr, d_stage, stride, m, rows, n, n_pairs, B,
-                                   lap0, ws.count(1), ws.count(2), ws.count(3));
-                HIP_TRY(hipGetLastError());
-            }
-            return MCGP_OK;
-        });
-    });
-    if (rc != MCGP_OK) return rc;
-    counts.add_to(segs);
-    return MCGP_OK;
+        }
+        return MCGP_OK;
+    };
+    return run_analysis(cfg, drv, grid_probs, state, n, n_sims, sim_offset, seed, device, hist_out, k);
 }
 
 static_assert(sizeof(mcgp::CondAtom) == sizeof(mcgp_condition_atom) && sizeof(mcgp::Cond) == sizeof(mcgp_condition) &&
@@ -2455,84 +2508,60 @@ int32_t mcgp_run_conditions(const mcgp_config *cfg, const mcgp_drivers *drv, con
                             const mcgp_condition *conditions, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
                             int32_t device, uint64_t *hist_out, uint64_t *count_out, uint64_t *cond_hist_out)
 {
-    // ---- every argument is checked before any device is looked up
-    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
-    if (!count_out) return fail(MCGP_E_BAD_ARG, "count_out is NULL");
-    int rc = check_source(grid_probs, state);
-    if (rc != MCGP_OK) return rc;
-    if (n_conditions < 1 || n_conditions > mcgp::kMaxConditions) return fail(MCGP_E_BAD_ARG, "n_conditions must be in [1, 64]");
-    if (!conditions) return fail(MCGP_E_BAD_ARG, "conditions is NULL");
-    std::vector<mcgp::KParams> kps(1);
-    mcgp::KParams &kp = kps[0];
-    rc = build_params_32(cfg, drv, grid_probs, n, "conditions run", &kp);
-    if (rc != MCGP_OK) return rc;
-    for (uint32_t ci = 0; ci < n_conditions; ++ci) {
-        const mcgp_condition &cond = conditions[ci];
-        const std::string where = "conditions[" + std::to_string(ci) + "]";
-        if (cond.n_atoms > mcgp::kMaxConditionAtoms) return fail(MCGP_E_BAD_ARG, where + ".n_atoms must be in [0, 8]");
-        for (uint32_t k = 0; k < cond.n_atoms; ++k) {
-            const mcgp_condition_atom &at = cond.atom[k];
-            const std::string atom = where + ".atom[" + std::to_string(k) + "]";
-            if (at.fact < 0 || at.fact >= mcgp::kFactCount)
-                return fail(MCGP_E_BAD_ARG, atom + ".fact: unknown fact " + std::to_string(at.fact));
-            const bool per_driver = at.fact <= MCGP_FACT_GAINED;
-            if (per_driver && (at.a < 0 || at.a >= (int32_t)n))
-                return fail(MCGP_E_BAD_ARG, atom + ".a: driver index must be in [0, n)");
-            if (at.fact == MCGP_FACT_AHEAD_BY) {
-                if (at.b < 0 || at.b >= (int32_t)n) return fail(MCGP_E_BAD_ARG, atom + ".b: driver index must be in [0, n)");
-                if (at.a == at.b) return fail(MCGP_E_BAD_ARG, atom + ".b: AHEAD_BY needs two different drivers");
-            }
-            if (at.lo > at.hi) return fail(MCGP_E_BAD_ARG, atom + ".lo must not be above .hi");
-        }
-    }
-    mcgp::ResumeState st;
-    rc = pack_state(state, n, cfg->total_laps, 0, &st);
-    if (rc != MCGP_OK) return rc;
-    if (n_sims == 0) return MCGP_OK;
+    const auto kernel = state ? &mcgp::race_conditions_kernel<true> : &mcgp::race_conditions_kernel<false>;
     const uint32_t C = n_conditions;
-    // hist [n][n] | count [C] | cond_hist [C][n][n]
-    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n}, {count_out, C},
-                                           {cond_hist_out, cond_hist_out ? (size_t)C * n * n : 0}};
-    Counts counts;
-    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        const auto kernel = state ? &mcgp::race_conditions_kernel<true> : &mcgp::race_conditions_kernel<false>;
-        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
-        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kConditionsStageBytes, (uint64_t)n + 8, n_sims);
-        // workspace: staging of one chunk, n rows of `stride` bytes (a multiple of 256) then `stride` u64 masks |
-        // parameter block | state | condition table | the counts
-        const uint64_t stride = (chunk + 255) / 256 * 256;
-        uint8_t *d_stage;
-        const mcgp::KParams *d_kp;
-        const mcgp::ResumeState *d_st;
-        const mcgp::Cond *d_cond;
-        Layout ws;
+    uint8_t *d_stage;
+    const mcgp::Cond *d_cond;
+    AnalysisKind k = {"conditions run", "conditions", "mcgp::race_conditions_kernel", reinterpret_cast<KernelFn>(kernel),
+                      kConditionsStageBytes, "count_out", count_out};
+    k.check_args = [&]() -> int {
+        if (C < 1 || C > mcgp::kMaxConditions) return fail(MCGP_E_BAD_ARG, "n_conditions must be in [1, 64]");
+        if (!conditions) return fail(MCGP_E_BAD_ARG, "conditions is NULL");
+        return MCGP_OK;
+    };
+    k.check_fields = [&]() -> int {
+        for (uint32_t ci = 0; ci < C; ++ci) {
+            const mcgp_condition &cond = conditions[ci];
+            const std::string where = "conditions[" + std::to_string(ci) + "]";
+            if (cond.n_atoms > mcgp::kMaxConditionAtoms) return fail(MCGP_E_BAD_ARG, where + ".n_atoms must be in [0, 8]");
+            for (uint32_t j = 0; j < cond.n_atoms; ++j) {
+                const mcgp_condition_atom &at = cond.atom[j];
+                const std::string atom = where + ".atom[" + std::to_string(j) + "]";
+                if (at.fact < 0 || at.fact >= mcgp::kFactCount)
+                    return fail(MCGP_E_BAD_ARG, atom + ".fact: unknown fact " + std::to_string(at.fact));
+                const bool per_driver = at.fact <= MCGP_FACT_GAINED;
+                if (per_driver && (at.a < 0 || at.a >= (int32_t)n))
+                    return fail(MCGP_E_BAD_ARG, atom + ".a: driver index must be in [0, n)");
+                if (at.fact == MCGP_FACT_AHEAD_BY) {
+                    if (at.b < 0 || at.b >= (int32_t)n) return fail(MCGP_E_BAD_ARG, atom + ".b: driver index must be in [0, n)");
+                    if (at.a == at.b) return fail(MCGP_E_BAD_ARG, atom + ".b: AHEAD_BY needs two different drivers");
+                }
+                if (at.lo > at.hi) return fail(MCGP_E_BAD_ARG, atom + ".lo must not be above .hi");
+            }
+        }
+        return MCGP_OK;
+    };
+    // hist [n][n] | count [C] | cond_hist [C][n][n]; per simulation the finishing order and one u64 mask
+    k.plan = [&](uint32_t, uint32_t) {
+        return AnalysisPlan{{{hist_out, (size_t)n * n}, {count_out, C}, {cond_hist_out, cond_hist_out ? (size_t)C * n * n : 0}},
+                            (uint64_t)n + 8};
+    };
+    // staging of one chunk, n rows of `stride` bytes then `stride` u64 masks | condition table
+    k.regions = [&](Layout &ws, uint64_t stride) {
         ws.add(&d_stage, (size_t)(n + 8) * stride);
-        ws.add(&d_kp, 1, &kp);
-        ws.add(&d_st, 1, &st);
         ws.add(&d_cond, C, reinterpret_cast<const mcgp::Cond *>(conditions));
-        ws.counts(segs);
-        const int r = ws.commit(c.work);
-        if (r != MCGP_OK) return r;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)c.lds_per_block));
+    };
+    k.launch = [&](const AnalysisChunk &a) -> int {
+        hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(a.block), a.lds, nullptr, a.kp, a.st, d_cond, C, a.m, a.first_sim,
+                           a.seed_lo, a.seed_hi, a.count(0), d_stage, a.stride, a.n_batches);
+        HIP_TRY(hipGetLastError());
         const uint32_t groups = (C + mcgp::kCondGroup - 1) / mcgp::kCondGroup;
-        const uint64_t grid_cap = std::max<uint64_t>(1, (uint64_t)c.cu_count * 8 / groups);
-        return staged_run(c, geo_fn, "conditions", "mcgp::race_conditions_kernel", n, 1, n_sims, chunk, ws, counts,
-                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, d_cond, C, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), ws.count(0), d_stage, stride, n_batches);
-            HIP_TRY(hipGetLastError());
-            const uint64_t tiles = (m + mcgp::kCondCountBlock - 1) / mcgp::kCondCountBlock;
-            hipLaunchKernelGGL(mcgp::conditions_count, dim3((uint32_t)std::min<uint64_t>(tiles, grid_cap), groups),
-                               dim3(mcgp::kCondCountBlock), 0, nullptr, d_stage, stride, m, n, C, ws.count(1),
-                               cond_hist_out ? ws.count(2) : nullptr);
-            HIP_TRY(hipGetLastError());
-            return MCGP_OK;
-        });
-    });
-    if (rc != MCGP_OK) return rc;
-    counts.add_to(segs);
-    return MCGP_OK;
+        hipLaunchKernelGGL(mcgp::conditions_count, dim3(count_grid_x(a.m, mcgp::kCondCountBlock, a.grid_cap, groups), groups),
+                           dim3(mcgp::kCondCountBlock), 0, nullptr, d_stage, a.stride, a.m, n, C, a.count(1), a.wanted(2));
+        HIP_TRY(hipGetLastError());
+        return MCGP_OK;
+    };
+    return run_analysis(cfg, drv, grid_probs, state, n, n_sims, sim_offset, seed, device, hist_out, k);
 }
 
 static_assert(mcgp::kStintStops == MCGP_STINT_STOPS && mcgp::kStintSeq == MCGP_STINT_SEQ &&
@@ -2543,70 +2572,41 @@ int32_t mcgp_run_stints(const mcgp_config *cfg, const mcgp_drivers *drv, const d
                         int32_t device, uint64_t *hist_out, uint64_t *stop_lap_out, uint64_t *stops_pos_out,
                         uint64_t *seq_out)
 {
-    // ---- every argument is checked before any device is looked up
-    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
-    if (!stop_lap_out) return fail(MCGP_E_BAD_ARG, "stop_lap_out is NULL");
-    int rc = check_source(grid_probs, state);
-    if (rc != MCGP_OK) return rc;
-    std::vector<mcgp::KParams> kps(1);
-    mcgp::KParams &kp = kps[0];
-    rc = build_params_32(cfg, drv, grid_probs, n, "stints run", &kp);
-    if (rc != MCGP_OK) return rc;
-    const uint32_t L = (uint32_t)cfg->total_laps;
-    mcgp::ResumeState st;
-    rc = pack_state(state, n, (int)L, 0, &st);
-    if (rc != MCGP_OK) return rc;
-    if (n_sims == 0) return MCGP_OK;
-    // hist [n][n] | stop_lap [n][4][L + 1] | stops_pos [n][5][n] | seq [n][1296]
-    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n},
-                                           {stop_lap_out, (size_t)n * mcgp::kStintStops * (L + 1)},
-                                           {stops_pos_out, stops_pos_out ? (size_t)n * (mcgp::kStintStops + 1) * n : 0},
-                                           {seq_out, seq_out ? (size_t)n * mcgp::kStintSeqCodes : 0}};
-    Counts counts;
-    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        const auto kernel = state ? &mcgp::race_stints_kernel<true> : &mcgp::race_stints_kernel<false>;
-        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
-        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kStintsStageBytes, 9ull * n, n_sims);
-        // workspace: staging of one chunk, n rows of `stride` u64 records then n rows of `stride` position bytes (stride
-        // a multiple of 256) | parameter block | state | the counts
-        const uint64_t stride = (chunk + 255) / 256 * 256;
-        uint64_t *d_rec;
-        uint8_t *d_pos;
-        const mcgp::KParams *d_kp;
-        const mcgp::ResumeState *d_st;
-        Layout ws;
+    const auto kernel = state ? &mcgp::race_stints_kernel<true> : &mcgp::race_stints_kernel<false>;
+    uint32_t L = 0;
+    size_t count_lds = 0;
+    uint64_t *d_rec;
+    uint8_t *d_pos;
+    AnalysisKind k = {"stints run", "stints", "mcgp::race_stints_kernel", reinterpret_cast<KernelFn>(kernel), kStintsStageBytes,
+                      "stop_lap_out", stop_lap_out};
+    k.plan = [&](uint32_t laps, uint32_t) {
+        L = laps;
+        // the counting kernel's histograms: 6.4 KiB at 60 laps and 20 cars, 21 KiB at 1000 laps
+        count_lds = ((size_t)mcgp::kStintStops * (L + 1) + (size_t)(mcgp::kStintStops + 1) * n + mcgp::kStintSeqCodes) * 4;
+        // hist [n][n] | stop_lap [n][4][L + 1] | stops_pos [n][5][n] | seq [n][1296]; per driver and simulation one u64
+        // record and one position byte
+        return AnalysisPlan{{{hist_out, (size_t)n * n},
+                             {stop_lap_out, (size_t)n * mcgp::kStintStops * (L + 1)},
+                             {stops_pos_out, stops_pos_out ? (size_t)n * (mcgp::kStintStops + 1) * n : 0},
+                             {seq_out, seq_out ? (size_t)n * mcgp::kStintSeqCodes : 0}},
+                            9ull * n, count_lds};
+    };
+    // staging of one chunk, n rows of `stride` u64 records then n rows of `stride` position bytes
+    k.regions = [&](Layout &ws, uint64_t stride) {
         ws.add(&d_rec, (size_t)n * stride);
         ws.add(&d_pos, (size_t)n * stride);
-        ws.add(&d_kp, 1, &kp);
-        ws.add(&d_st, 1, &st);
-        ws.counts(segs);
-        const int r = ws.commit(c.work);
-        if (r != MCGP_OK) return r;
-        // the counting kernel's histograms: 6.4 KiB at 60 laps and 20 cars, 21 KiB at 1000 laps
-        const size_t count_lds = ((size_t)mcgp::kStintStops * (L + 1) + (size_t)(mcgp::kStintStops + 1) * n +
-                                  mcgp::kStintSeqCodes) * 4;
-        if (count_lds > c.lds_per_block)
-            return fail(MCGP_E_HIP, "the stints counting kernel's block needs " + std::to_string(count_lds) +
-                                        " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)c.lds_per_block));
-        const uint64_t grid_cap = std::max<uint64_t>(1, (uint64_t)c.cu_count * 8 / n);
-        return staged_run(c, geo_fn, "stints", "mcgp::race_stints_kernel", n, 1, n_sims, chunk, ws, counts,
-                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), ws.count(0), d_rec, d_pos, stride, n_batches);
-            HIP_TRY(hipGetLastError());
-            const uint64_t tiles = (m + mcgp::kStintsCountBlock - 1) / mcgp::kStintsCountBlock;
-            hipLaunchKernelGGL(mcgp::stints_count, dim3((uint32_t)std::min<uint64_t>(tiles, grid_cap), n),
-                               dim3(mcgp::kStintsCountBlock), count_lds, nullptr, d_rec, d_pos, stride, m, n, L, ws.count(1),
-                               stops_pos_out ? ws.count(2) : nullptr, seq_out ? ws.count(3) : nullptr);
-            HIP_TRY(hipGetLastError());
-            return MCGP_OK;
-        });
-    });
-    if (rc != MCGP_OK) return rc;
-    counts.add_to(segs);
-    return MCGP_OK;
+    };
+    k.launch = [&](const AnalysisChunk &a) -> int {
+        hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(a.block), a.lds, nullptr, a.kp, a.st, a.m, a.first_sim, a.seed_lo,
+                           a.seed_hi, a.count(0), d_rec, d_pos, a.stride, a.n_batches);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(mcgp::stints_count, dim3(count_grid_x(a.m, mcgp::kStintsCountBlock, a.grid_cap, n), n),
+                           dim3(mcgp::kStintsCountBlock), count_lds, nullptr, d_rec, d_pos, a.stride, a.m, n, L, a.count(1),
+                           a.wanted(2), a.wanted(3));
+        HIP_TRY(hipGetLastError());
+        return MCGP_OK;
+    };
+    return run_analysis(cfg, drv, grid_probs, state, n, n_sims, sim_offset, seed, device, hist_out, k);
 }
 
 static_assert(mcgp::kMoveDriverCap == MCGP_MOVE_DRIVER_CAP && mcgp::kMoveRaceCap == MCGP_MOVE_RACE_CAP,
@@ -2618,91 +2618,62 @@ int32_t mcgp_run_moves(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                        uint64_t *passes_out, uint64_t *race_passes_out, uint64_t *lap_passes_out,
                        uint64_t *pair_passes_out)
 {
-    // ---- every argument is checked before any device is looked up
-    if (!hist_out) return fail(MCGP_E_BAD_ARG, "hist_out is NULL");
-    if (!grid_fin_out) return fail(MCGP_E_BAD_ARG, "grid_fin_out is NULL");
-    int rc = check_source(grid_probs, state);
-    if (rc != MCGP_OK) return rc;
-    if (state && start_gain_out)
-        return fail(MCGP_E_BAD_ARG, "start_gain_out must be NULL when a state is given (a start gain is from the grid)");
-    std::vector<mcgp::KParams> kps(1);
-    mcgp::KParams &kp = kps[0];
-    rc = build_params_32(cfg, drv, grid_probs, n, "moves run", &kp);
-    if (rc != MCGP_OK) return rc;
-    const uint32_t L = (uint32_t)cfg->total_laps;
-    mcgp::ResumeState st;
-    rc = pack_state(state, n, (int)L, 0, &st);
-    if (rc != MCGP_OK) return rc;
-    if (n_sims == 0) return MCGP_OK;
-    const uint32_t lap0 = state ? (uint32_t)st.lap : 1u;                    // the baseline row
-    // hist [n][n] | grid_fin [n][n][n] | start_gain [n][2n] | passes [n][4][128] | race_passes [1024] |
-    // lap_passes [L + 1][2] | pair_passes [n][n]: the optional ones take no cells when they are not wanted
-    const std::vector<Counts::Seg> segs = {{hist_out, (size_t)n * n},
-                                           {grid_fin_out, (size_t)n * n * n},
-                                           {start_gain_out, start_gain_out ? (size_t)n * 2 * n : 0},
-                                           {passes_out, passes_out ? (size_t)n * 4 * (mcgp::kMoveDriverCap + 1) : 0},
-                                           {race_passes_out, race_passes_out ? (size_t)mcgp::kMoveRaceCap + 1 : 0},
-                                           {lap_passes_out, lap_passes_out ? 2 * (size_t)(L + 1) : 0},
-                                           {pair_passes_out, pair_passes_out ? (size_t)n * n : 0}};
+    const auto kernel = state ? &mcgp::race_moves_kernel<true> : &mcgp::race_moves_kernel<false>;
     const bool walk = passes_out || race_passes_out || lap_passes_out || pair_passes_out;
-    Counts counts;
-    rc = on_device(device, true, [&](DeviceCtx &c) -> int {
-        const auto kernel = state ? &mcgp::race_moves_kernel<true> : &mcgp::race_moves_kernel<false>;
-        const KernelFn geo_fn = reinterpret_cast<KernelFn>(kernel);         // (for its register count)
-        const uint64_t rows = ((uint64_t)L + 2) * n;
-        const uint64_t chunk = stage_chunk_rounds(c, n, geo_fn, kMovesStageBytes, rows, n_sims);
-        // workspace: staging of one chunk, (L + 2) n rows of `stride` bytes (a multiple of 256) | every car's packed
-        // pass counts, n rows of `stride` u32 (only if passes_out) | parameter block | state | the counts
-        const uint64_t stride = (chunk + 255) / 256 * 256;
-        uint8_t *d_stage;
-        uint32_t *d_tot;
-        const mcgp::KParams *d_kp;
-        const mcgp::ResumeState *d_st;
-        Layout ws;
+    uint32_t L = 0, lap0 = 0;                                   // lap0: the baseline row
+    uint64_t rows = 0;
+    size_t laps_lds = 0;
+    uint8_t *d_stage;
+    uint32_t *d_tot;
+    AnalysisKind k = {"moves run", "moves", "mcgp::race_moves_kernel", reinterpret_cast<KernelFn>(kernel), kMovesStageBytes,
+                      "grid_fin_out", grid_fin_out};
+    k.check_args = [&]() -> int {
+        if (state && start_gain_out)
+            return fail(MCGP_E_BAD_ARG, "start_gain_out must be NULL when a state is given (a start gain is from the grid)");
+        return MCGP_OK;
+    };
+    k.plan = [&](uint32_t laps, uint32_t lap) {
+        L = laps, lap0 = state ? lap : 1u, rows = ((uint64_t)L + 2) * n;
+        // moves_count_laps' tables and sums: 29 KiB at 60 laps and 20 cars, 52 KiB at 1000 laps and 32 cars
+        laps_lds = 9 * (size_t)n * mcgp::kMovesLapsBlock + ((size_t)n * n + 2 * (size_t)(L + 1) + mcgp::kMoveRaceCap + 1) * 4;
+        // hist [n][n] | grid_fin [n][n][n] | start_gain [n][2n] | passes [n][4][128] | race_passes [1024] |
+        // lap_passes [L + 1][2] | pair_passes [n][n]: the optional ones take no cells when they are not wanted
+        return AnalysisPlan{{{hist_out, (size_t)n * n},
+                             {grid_fin_out, (size_t)n * n * n},
+                             {start_gain_out, start_gain_out ? (size_t)n * 2 * n : 0},
+                             {passes_out, passes_out ? (size_t)n * 4 * (mcgp::kMoveDriverCap + 1) : 0},
+                             {race_passes_out, race_passes_out ? (size_t)mcgp::kMoveRaceCap + 1 : 0},
+                             {lap_passes_out, lap_passes_out ? 2 * (size_t)(L + 1) : 0},
+                             {pair_passes_out, pair_passes_out ? (size_t)n * n : 0}},
+                            rows, laps_lds};
+    };
+    // staging of one chunk, (L + 2) n rows of `stride` bytes | every car's packed pass counts, n rows of `stride` u32
+    // (only if passes_out)
+    k.regions = [&](Layout &ws, uint64_t stride) {
         ws.add(&d_stage, (size_t)rows * stride);
         ws.add(&d_tot, passes_out ? (size_t)n * stride : 0);
-        ws.add(&d_kp, 1, &kp);
-        ws.add(&d_st, 1, &st);
-        ws.counts(segs);
-        const int r = ws.commit(c.work);
-        if (r != MCGP_OK) return r;
-        if (!passes_out) d_tot = nullptr;
-        // a segment that is not wanted is NULL for the counting kernels
-        auto wanted = [&](size_t i) { return segs[i].dst ? ws.count(i) : nullptr; };
-        // moves_count_laps' tables and sums: 29 KiB at 60 laps and 20 cars, 52 KiB at 1000 laps and 32 cars
-        const size_t laps_lds = 9 * (size_t)n * mcgp::kMovesLapsBlock +
-                                ((size_t)n * n + 2 * (size_t)(L + 1) + mcgp::kMoveRaceCap + 1) * 4;
-        if (laps_lds > c.lds_per_block)
-            return fail(MCGP_E_HIP, "the moves counting kernel's block needs " + std::to_string(laps_lds) +
-                                        " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(geo_fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)c.lds_per_block));
-        const uint64_t grid_cap = (uint64_t)c.cu_count * 8;
-        return staged_run(c, geo_fn, "moves", "mcgp::race_moves_kernel", n, 1, n_sims, chunk, ws, counts,
-                          [&](uint64_t done, uint64_t m, uint32_t grid, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, nullptr, d_kp, d_st, m, sim_offset + done,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), ws.count(0), d_stage, stride, n_batches);
+    };
+    k.launch = [&](const AnalysisChunk &a) -> int {
+        uint32_t *tot = passes_out ? d_tot : nullptr;
+        hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(a.block), a.lds, nullptr, a.kp, a.st, a.m, a.first_sim, a.seed_lo,
+                           a.seed_hi, a.count(0), d_stage, a.stride, a.n_batches);
+        HIP_TRY(hipGetLastError());
+        if (walk) {
+            // a block takes at most kMovesBlockShare simulations, so that its u32 sums cannot wrap (moves.hip.h)
+            const uint64_t tiles = (a.m + mcgp::kMovesLapsBlock - 1) / mcgp::kMovesLapsBlock;
+            const uint64_t per_block = mcgp::kMovesBlockShare / mcgp::kMovesLapsBlock;
+            const uint64_t gx = std::min<uint64_t>(tiles, std::max<uint64_t>(a.grid_cap, (tiles + per_block - 1) / per_block));
+            hipLaunchKernelGGL(mcgp::moves_count_laps, dim3((uint32_t)gx), dim3(mcgp::kMovesLapsBlock), laps_lds, nullptr,
+                               d_stage, a.stride, a.m, n, L, lap0, tot, a.wanted(4), a.wanted(5), a.wanted(6));
             HIP_TRY(hipGetLastError());
-            if (walk) {
-                // a block takes at most kMovesBlockShare simulations, so that its u32 sums cannot wrap (moves.hip.h)
-                const uint64_t tiles = (m + mcgp::kMovesLapsBlock - 1) / mcgp::kMovesLapsBlock;
-                const uint64_t per_block = mcgp::kMovesBlockShare / mcgp::kMovesLapsBlock;
-                const uint64_t gx = std::min<uint64_t>(tiles, std::max<uint64_t>(grid_cap, (tiles + per_block - 1) / per_block));
-                hipLaunchKernelGGL(mcgp::moves_count_laps, dim3((uint32_t)gx), dim3(mcgp::kMovesLapsBlock), laps_lds, nullptr,
-                                   d_stage, stride, m, n, L, lap0, d_tot, wanted(4), wanted(5), wanted(6));
-                HIP_TRY(hipGetLastError());
-            }
-            const uint64_t dtiles = (m + mcgp::kMovesDriversBlock - 1) / mcgp::kMovesDriversBlock;
-            const uint64_t gx = std::max<uint64_t>(1, std::min<uint64_t>(dtiles, grid_cap / n));
-            hipLaunchKernelGGL(mcgp::moves_count_drivers, dim3((uint32_t)gx, n), dim3(mcgp::kMovesDriversBlock), 0, nullptr,
-                               d_stage, d_tot, stride, m, n, L, ws.count(1), wanted(2), wanted(3));
-            HIP_TRY(hipGetLastError());
-            return MCGP_OK;
-        });
-    });
-    if (rc != MCGP_OK) return rc;
-    counts.add_to(segs);
-    return MCGP_OK;
+        }
+        hipLaunchKernelGGL(mcgp::moves_count_drivers, dim3(count_grid_x(a.m, mcgp::kMovesDriversBlock, a.grid_cap, n), n),
+                           dim3(mcgp::kMovesDriversBlock), 0, nullptr, d_stage, tot, a.stride, a.m, n, L, a.count(1),
+                           a.wanted(2), a.wanted(3));
+        HIP_TRY(hipGetLastError());
+        return MCGP_OK;
+    };
+    return run_analysis(cfg, drv, grid_probs, state, n, n_sims, sim_offset, seed, device, hist_out, k);
 }
 
 int32_t mcgp_last_kernel_ms(int32_t device, float *ms_out)

@@ -1,7 +1,7 @@
 // moves.hip.h -- how the field moves in a race, counted on the device (mcgp_run_moves, include/mcgp.h).
 //
 // race_moves_kernel runs mcgp_run's simulations (from the grid, kFromState false) or mcgp_run_from_state's (from one
-// state) with the generic kernel's code -- start_from_grid or start_from_state, run_laps, classify_and_count -- and the
+// state) with the generic kernel's code -- run_observed (resume.hip.h), the analysis kernels' shared lane body -- and the
 // trace's own per-lap observer (TraceObserver, trace.hip.h), which sees the rows after update_positions of every lap.
 // Simulation i draws exactly what those calls' simulation i draws, so the position histogram is theirs.  Definitions
 // (include/mcgp.h has them in full), all read at that point of lap k:
@@ -71,31 +71,21 @@ race_moves_kernel(const KParams *__restrict__ P, const ResumeState *__restrict__
                   uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist, uint8_t *__restrict__ stage,
                   uint64_t stride, uint32_t n_batches)
 {
-    run_block(P, m, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
-        const uint64_t sim = sim_offset + local;
-        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-        const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
-                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr);
-        TraceObserver obs;
-        obs.lane = stage + local;
-        obs.lap_bytes = (uint64_t)e.n * stride;
-        obs.stride = stride;
-        obs.n = e.n;
-        obs.best = __builtin_inf();
-        obs.best_d = kNoFastest;
-        obs.red = obs.sc = obs.vsc = 0u;
-        obs(s, at.first_lap - 1, kEventNone);                    // lap 1 from the grid, the baseline row from a state
-
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, obs);         // reference :166-228
-        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
-        uint8_t *slot = stage + (uint64_t)e.L * obs.lap_bytes + local;
-        uint8_t *pos = slot + obs.lap_bytes;
-        for (int p = 0; p < e.n; ++p) {
-            const uint32_t d = s.Ord(p);
-            slot[(uint64_t)d * stride] = (uint8_t)gpos_of(s.Pk(d));
-            pos[(uint64_t)d * stride] = (uint8_t)p;
-        }
-    });
+    run_observed<kFromState>(P, state, m, sim_offset, seed_lo, seed_hi, hist, n_batches,
+        [=](const Rows &s, const LapEnv &e, const RaceStart &at, uint64_t local) {
+            TraceObserver obs = TraceObserver::make(stage, stride, e.n, local);
+            obs(s, at.first_lap - 1, kEventNone);                // lap 1 from the grid, the baseline row from a state
+            return obs;
+        },
+        [=](const Rows &s, const LapEnv &e, const TraceObserver &obs, uint64_t local) {
+            uint8_t *slot = stage + (uint64_t)e.L * obs.lap_bytes + local;
+            uint8_t *pos = slot + obs.lap_bytes;
+            for (int p = 0; p < e.n; ++p) {
+                const uint32_t d = s.Ord(p);
+                slot[(uint64_t)d * stride] = (uint8_t)gpos_of(s.Pk(d));
+                pos[(uint64_t)d * stride] = (uint8_t)p;
+            }
+        });
 }
 
 // One saturating byte of a car's packed counts: ((w >> shift) & 255) + add, at most kMoveDriverCap.

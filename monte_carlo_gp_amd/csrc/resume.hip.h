@@ -74,6 +74,28 @@ __device__ __forceinline__ RaceStart start_from_state(const Rows &s, const LapEn
     return {k + 1, drs_disabled_until};
 }
 
+// One lane's body of the analysis kernels (trace, gaps, conditions, stints, moves): the unmodified race of simulation
+// sim_offset + local, from the grid (kFromState false; `state` is not read and may be NULL) or from `state`, watched by
+// a per-lap observer.  begin(s, e, at, local) builds the observer once the start has run (and records what the start
+// itself left, where the kernel stages that); run_laps hands it every lap; end(s, e, obs, local) runs over the
+// classified order.  m, hist and n_batches are run_block's.
+template <bool kFromState, class Begin, class End>
+__device__ __forceinline__ void run_observed(const KParams *__restrict__ P, const ResumeState *__restrict__ state, uint64_t m,
+                                             uint64_t sim_offset, uint32_t seed_lo, uint32_t seed_hi,
+                                             unsigned long long *__restrict__ hist, uint32_t n_batches, Begin begin, End end)
+{
+    run_block(P, m, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
+        const uint64_t sim = sim_offset + local;
+        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
+        const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
+                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr);
+        auto obs = begin(s, e, at, local);
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, obs);         // reference :166-228
+        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
+        end(s, e, obs, local);
+    });
+}
+
 // n_sims simulations per state, ids states[s].sim_offset + sim_base + [0, n_sims); gridDim.y = number of states.
 // hist [states][n][n] is ACCUMULATED into; orders (NULL: none) = [states][n_sims][n].
 __global__ void __launch_bounds__(512)

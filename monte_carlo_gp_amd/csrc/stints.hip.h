@@ -1,7 +1,7 @@
 // stints.hip.h -- tyre stints of a race, counted on the device (mcgp_run_stints, include/mcgp.h).
 //
 // race_stints_kernel runs mcgp_run's simulations (from the grid, kFromState false) or mcgp_run_from_state's (from one
-// state) with the generic kernel's code -- start_from_grid or start_from_state, run_laps, classify_and_count -- and a
+// state) with the generic kernel's code -- run_observed (resume.hip.h), the analysis kernels' shared lane body -- and a
 // per-lap observer (StintObserver) that sees the rows after update_positions of every lap run_laps runs: laps 2..L from
 // the grid (lap 1 has no pit step and no event), laps k + 1 .. L from a state after lap k.  Simulation i draws exactly
 // what those calls' simulation i draws, so the position histogram is theirs.  Read at that point of lap k (the state the
@@ -100,22 +100,16 @@ race_stints_kernel(const KParams *__restrict__ P, const ResumeState *__restrict_
                    uint32_t seed_lo, uint32_t seed_hi, unsigned long long *__restrict__ hist, uint64_t *__restrict__ rec,
                    uint8_t *__restrict__ pos, uint64_t stride, uint32_t n_batches)
 {
-    run_block(P, m, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
-        const uint64_t sim = sim_offset + local;
-        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-        const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
-                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr);
-        StintObserver obs;
-        obs.lane = rec + local;
-        obs.stride = stride;
-        obs.n = e.n;
-        obs.start(s);
-
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, obs);         // reference :166-228
-        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
-        uint8_t *out = pos + local;
-        for (int p = 0; p < e.n; ++p) out[(uint64_t)s.Ord(p) * stride] = (uint8_t)p;
-    });
+    run_observed<kFromState>(P, state, m, sim_offset, seed_lo, seed_hi, hist, n_batches,
+        [=](const Rows &s, const LapEnv &e, const RaceStart &, uint64_t local) {
+            const StintObserver obs = {rec + local, stride, e.n};
+            obs.start(s);
+            return obs;
+        },
+        [=](const Rows &s, const LapEnv &e, const StintObserver &, uint64_t local) {
+            uint8_t *out = pos + local;
+            for (int p = 0; p < e.n; ++p) out[(uint64_t)s.Ord(p) * stride] = (uint8_t)p;
+        });
 }
 
 // The sequence code of a record: sum over the stints j < m of (compound_j + 1) 6^j for m <= 4 stints, 0 for more.

@@ -1,8 +1,9 @@
 // trace.hip.h -- what happened lap by lap in a race, counted on the device (mcgp_run_trace, include/mcgp.h).
 //
 // race_trace_kernel runs mcgp_run's simulations with the generic kernel's code -- start_from_grid for the grid and
-// lap 1, run_laps for laps 2..L, classify_and_count -- and a per-lap observer (TraceObserver) that sees the rows after
-// update_positions of every lap, lap 1 included.  Simulation i draws exactly what race_kernel's simulation i draws, so
+// lap 1, run_laps for laps 2..L, classify_and_count: run_observed (resume.hip.h), the lane body the five analysis
+// kernels share -- and a per-lap observer (TraceObserver) that sees the rows after update_positions of every lap, lap 1
+// included.  Simulation i draws exactly what race_kernel's simulation i draws, so
 // its position histogram is mcgp_run's.  Read at that point of lap k (the state the CPU oracle's per-lap trace records):
 //
 //   running position  rank of a car among the cars not retired, in `ord` order (cumulative time, grid slot); a retired
@@ -33,7 +34,7 @@
 //
 // Overflow: a chunk is at most max_sims_per_launch() < 2^32 simulations, so no u32 counter can wrap.
 #pragma once
-#include "race_kernel.hip.h"
+#include "resume.hip.h"
 
 namespace mcgp {
 
@@ -51,6 +52,12 @@ struct TraceObserver {
     double best;            // fastest lap so far, and its driver (kNoFastest: none yet)
     uint32_t best_d;
     uint32_t red, sc, vsc;  // events so far
+
+    // the observer of lane `local` over a staging of n rows of `stride` bytes per lap: nothing seen yet
+    static __device__ __forceinline__ TraceObserver make(uint8_t *stage, uint64_t stride, int n, uint64_t local)
+    {
+        return {stage + local, (uint64_t)n * stride, stride, n, __builtin_inf(), kNoFastest, 0u, 0u, 0u};
+    }
 
     __device__ __forceinline__ void operator()(const Rows &s, int lap, int event)
     {
@@ -83,25 +90,15 @@ race_trace_kernel(const KParams *__restrict__ P, uint64_t n_sims, uint64_t sim_o
                   uint32_t seed_hi, unsigned long long *__restrict__ hist, uint8_t *__restrict__ stage, uint64_t stride,
                   uint64_t *__restrict__ rec, uint32_t n_batches)
 {
-    run_block(P, n_sims, n_batches, hist, [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
-        const uint64_t sim = sim_offset + local;
-        const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-        const RaceStart at = start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr);
-
-        TraceObserver obs;
-        obs.lane = stage + local;
-        obs.lap_bytes = (uint64_t)e.n * stride;
-        obs.stride = stride;
-        obs.n = e.n;
-        obs.best = __builtin_inf();
-        obs.best_d = kNoFastest;
-        obs.red = obs.sc = obs.vsc = 0u;
-        obs(s, 1, kEventNone);
-
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, obs);         // reference :166-228
-        classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
-        rec[local] = (uint64_t)obs.best_d | ((uint64_t)obs.red << 16) | ((uint64_t)obs.sc << 32) | ((uint64_t)obs.vsc << 48);
-    });
+    run_observed<false>(P, nullptr, n_sims, sim_offset, seed_lo, seed_hi, hist, n_batches,
+        [=](const Rows &s, const LapEnv &e, const RaceStart &, uint64_t local) {
+            TraceObserver obs = TraceObserver::make(stage, stride, e.n, local);
+            obs(s, 1, kEventNone);
+            return obs;
+        },
+        [=](const Rows &, const LapEnv &, const TraceObserver &obs, uint64_t local) {
+            rec[local] = (uint64_t)obs.best_d | ((uint64_t)obs.red << 16) | ((uint64_t)obs.sc << 32) | ((uint64_t)obs.vsc << 48);
+        });
 }
 
 // lap_pos [L n][n + 1] += the staged rows' counts: row r (= (lap - 1) n + driver) of m simulations, value v at

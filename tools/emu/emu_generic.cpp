@@ -19,9 +19,15 @@
 // records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
 // operation and strides by its block's size, so it does run here, as blocks of one thread; so do penalties_count, events_count
 // and paces_count.
-// tests/test_events_host_build.py, tests/test_generic_host_build.py, tests/test_gaps_host_build.py, tests/test_conditions_host_build.py,
-// tests/test_stints_host_build.py, tests/test_moves_host_build.py, tests/test_fastest_host_build.py,
-// tests/test_penalties_host_build.py, tests/test_paces_host_build.py, tests/test_combined_host_build.py.
+//
+// Shared text: the five analysis calls (emu_generic_trace, emu_gaps_run, emu_conditions_run, emu_stints_run,
+// emu_moves_run) start with analysis_setup, the five scenario calls are scenario_run with their rule sets.
+//
+// Used by tests/test_generic_host_build.py (race, resume, trace, strategies) and by tests/test_<call>_host_build.py for
+// gaps, conditions, stints, moves, fastest, penalties, events, paces and combined, each through its helper
+// tests/<call>_host_build.py (tests/kernel_host_build.py compiles this file); the stand-alone programs
+// tools/emu/sanitize_{penalties,events,paces,combined,bonus}_main.cpp are built with it for
+// tests/test_{penalties,events,paces,combined,fastest}_sanitize.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -75,6 +81,30 @@ void one_thread_block(uint32_t grid_y)
     blockIdx = {0, 0, 0};
     blockDim = {1, 1, 1};
     gridDim = {1, grid_y, 1};
+}
+
+// The start of the five analysis calls (trace, gaps, conditions, stints, moves): the parameter block, the source (a state
+// or grid_probs; the trace passes no state, so it needs grid_probs), the call's own complaint `own` (NULL: none), the
+// staging's stride (masks: conditions' u64 masks sit behind the rows, so a multiple of 8), the state as the kernels read
+// it (zero from the grid) and a block of one thread.
+int analysis_setup(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                   uint32_t n, uint64_t n_sims, uint64_t stride, bool masks, const char *own, mcgp::KParams *kp,
+                   mcgp::ResumeState *st, const char **err)
+{
+    const int rc = params(cfg, drv, grid_probs, n, kp, err);
+    if (rc != MCGP_OK) return rc;
+    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
+    if (own) return fail(MCGP_E_BAD_ARG, own, err);
+    if (masks && (stride < n_sims || stride % 8))
+        return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims and a multiple of 8", err);
+    if (stride < n_sims) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims", err);
+    std::memset(st, 0, sizeof(*st));
+    if (state) {
+        const std::string e = mcgp::pack_race_state(*state, 0, n, cfg->total_laps, st);
+        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
+    }
+    one_thread_block(1);
+    return MCGP_OK;
 }
 
 // The scenario calls: race_scenario_kernel<false, rules> (state NULL: from the grid) or <true, rules> over simulations
@@ -216,10 +246,9 @@ int emu_generic_trace(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
                       uint64_t *rec, const char **err)
 {
     static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
+    mcgp::ResumeState st;
+    const int rc = analysis_setup(cfg, drv, grid_probs, nullptr, n, n_sims, stride, false, nullptr, &kp, &st, err);
     if (rc != MCGP_OK) return rc;
-    if (stride < n_sims) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims", err);
-    one_thread_block(1);
     mcgp::race_trace_kernel(&kp, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage, stride, rec,
                             (uint32_t)n_sims);
     return MCGP_OK;
@@ -233,21 +262,13 @@ int emu_gaps_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *
                  const char **err)
 {
     static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    if (n_edges < 1 || n_edges > mcgp::kMaxGapEdges || n_pairs > mcgp::kMaxGapPairs)
-        return fail(MCGP_E_BAD_ARG, "n_edges in [1, 63], n_pairs in [0, 64]", err);
-    if (stride < n_sims) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims", err);
     mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, cfg->total_laps, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    }
+    const bool bad = n_edges < 1 || n_edges > mcgp::kMaxGapEdges || n_pairs > mcgp::kMaxGapPairs;
+    const int rc = analysis_setup(cfg, drv, grid_probs, state, n, n_sims, stride, false,
+                                  bad ? "n_edges in [1, 63], n_pairs in [0, 64]" : nullptr, &kp, &st, err);
+    if (rc != MCGP_OK) return rc;
     double table[mcgp::kGapEdgeSlots];                      // the call's edges, then +inf, as the C ABI uploads them
     for (uint32_t i = 0; i < mcgp::kGapEdgeSlots; ++i) table[i] = i < n_edges ? edges[i] : HUGE_VAL;
-    one_thread_block(1);
     const auto kernel = state ? &mcgp::race_gaps_kernel<true> : &mcgp::race_gaps_kernel<false>;
     kernel(&kp, &st, table, n_edges, pairs, n_pairs, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
            stride, (uint32_t)n_sims);
@@ -264,20 +285,13 @@ int emu_conditions_run(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                        uint64_t stride, unsigned long long *count, unsigned long long *cond_hist, uint32_t grid_x,
                        const char **err)
 {
-    static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    if (n_conditions < 1 || n_conditions > mcgp::kMaxConditions) return fail(MCGP_E_BAD_ARG, "n_conditions in [1, 64]", err);
-    if (stride < n_sims || stride % 8) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims and a multiple of 8", err);
     static_assert(sizeof(mcgp::Cond) == sizeof(mcgp_condition), "the table is the C ABI's array");
+    static mcgp::KParams kp;
     mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, cfg->total_laps, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    }
-    one_thread_block(1);
+    const bool bad = n_conditions < 1 || n_conditions > mcgp::kMaxConditions;
+    const int rc = analysis_setup(cfg, drv, grid_probs, state, n, n_sims, stride, true, bad ? "n_conditions in [1, 64]" : nullptr,
+                                  &kp, &st, err);
+    if (rc != MCGP_OK) return rc;
     const auto kernel = state ? &mcgp::race_conditions_kernel<true> : &mcgp::race_conditions_kernel<false>;
     kernel(&kp, &st, reinterpret_cast<const mcgp::Cond *>(conditions), n_conditions, n_sims, sim_offset, (uint32_t)seed,
            (uint32_t)(seed >> 32), hist, stage, stride, (uint32_t)n_sims);
@@ -302,17 +316,9 @@ int emu_stints_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double
                    uint8_t *pos, uint64_t stride, const char **err)
 {
     static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    if (stride < n_sims) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims", err);
     mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, cfg->total_laps, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    }
-    one_thread_block(1);
+    const int rc = analysis_setup(cfg, drv, grid_probs, state, n, n_sims, stride, false, nullptr, &kp, &st, err);
+    if (rc != MCGP_OK) return rc;
     const auto kernel = state ? &mcgp::race_stints_kernel<true> : &mcgp::race_stints_kernel<false>;
     kernel(&kp, &st, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, rec, pos, stride, (uint32_t)n_sims);
     return MCGP_OK;
@@ -326,17 +332,9 @@ int emu_moves_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double 
                   uint64_t stride, const char **err)
 {
     static mcgp::KParams kp;
-    const int rc = params(cfg, drv, grid_probs, n, &kp, err);
-    if (rc != MCGP_OK) return rc;
-    if ((state != nullptr) == (grid_probs != nullptr)) return fail(MCGP_E_BAD_ARG, "either a state or grid_probs", err);
-    if (stride < n_sims) return fail(MCGP_E_BAD_ARG, "stride must be at least n_sims", err);
     mcgp::ResumeState st;
-    std::memset(&st, 0, sizeof(st));
-    if (state) {
-        const std::string e = mcgp::pack_race_state(*state, 0, n, cfg->total_laps, &st);
-        if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
-    }
-    one_thread_block(1);
+    const int rc = analysis_setup(cfg, drv, grid_probs, state, n, n_sims, stride, false, nullptr, &kp, &st, err);
+    if (rc != MCGP_OK) return rc;
     const auto kernel = state ? &mcgp::race_moves_kernel<true> : &mcgp::race_moves_kernel<false>;
     kernel(&kp, &st, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage, stride, (uint32_t)n_sims);
     return MCGP_OK;
