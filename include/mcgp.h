@@ -711,6 +711,79 @@ int32_t mcgp_run_combined(const mcgp_config *cfg, const mcgp_drivers *drv, const
                           uint64_t *hist_out, uint64_t *delta_out, uint64_t *fate_out,
                           uint64_t *events_out, uint64_t *carried_out, uint8_t *orders_out);
 
+/* A track-condition change: in a scenario of mcgp_run_weather, laps first_lap..last_lap have `condition` instead of
+ * cfg->track_condition.  A wrong-tyre model: the seconds a car on `compound` loses per lap under `condition`. */
+#define MCGP_MAX_SCENARIO_TRACK_CHANGES 64
+typedef struct mcgp_track_change {
+    int32_t first_lap, last_lap;  /* both in [first, L], first_lap <= last_lap */
+    int32_t condition;            /* MCGP_DRY .. MCGP_WET_TRACK */
+} mcgp_track_change;
+typedef struct mcgp_weather_model {
+    double wrong_tyre_sec[3][5];  /* [condition][compound], seconds, finite, in [0, 60] */
+} mcgp_weather_model;
+
+/* Weather scenarios: one race under n_scenarios sets of planned pit stops AND track conditions by lap ("it starts to
+ * rain on lap 30: who gains if NOR boxes for intermediates at once and VER stays out two laps?"), with common random
+ * numbers.  Scenario s holds plan_count[s] plans (concatenated in `plans`; exactly mcgp_run_strategies' plans, with its
+ * checks; `plans` may be NULL when every count is 0) and change_count[s] changes (concatenated in `changes`, which may be
+ * NULL when every count is 0).  `model` is one table for the whole call.  L = cfg->total_laps; `first`, the first lap a
+ * change may name, is 2 from the grid and state->lap + 1 from a state.
+ *   - condition of a lap: c_k is the `condition` of the scenario's change that covers lap k, else cfg->track_condition.
+ *     Lap 1 from the grid always has cfg->track_condition.  The changes of one scenario share no lap, and a scenario has
+ *     at most MCGP_MAX_SCENARIO_TRACK_CHANGES of them; a change to cfg->track_condition is legal and changes nothing;
+ *   - classes: SOFT, MEDIUM and HARD are dry tyres, INTERMEDIATE and WET wet tyres; DRY is a dry condition, DAMP and
+ *     WET_TRACK wet ones.  A car is on the wrong tyres on lap k iff the class of its compound is not the class of c_k;
+ *   - c_k stands wherever lap k's code reads the track condition, and nowhere else: the red flag's free tyre change
+ *     (stint_compound(c_k, remaining)), the rule stop's stint_compound, and the rule stop's two-compound waiver (the
+ *     waiver tests c_k == MCGP_DRY; the compounds used are still the dry ones the car has run);
+ *   - crossover stop: a car under the model's rule (no plan in the scenario) stops when
+ *     (age > optimal stint || on the wrong tyres on lap k) && remaining_laps > 5; what follows the test is the rule's
+ *     own pit step, with c_k.  Every rule car therefore reacts on the same lap.  A planned driver has the rule off, as
+ *     everywhere: "stays out" is a plan without a stop on that lap;
+ *   - wrong-tyre pace: b = base_pace[d] + model->wrong_tyre_sec[c_k][compound] replaces base_pace[d] in exactly the places
+ *     where mcgp_run_paces puts its b: lap 1's base_lap (cfg->track_condition, the start compound); the lap time of laps
+ *     >= 2, with the compound the car is on when the lap time is computed, before the pit step; the pace of the overtake
+ *     model in the candidate scan and the attempt on all three passes, with the compound after the pit step.  The table
+ *     is read whether or not the class is wrong: intermediates on a fully wet track can cost something too.
+ * Identities: a scenario whose changes, if any, all name cfg->track_condition, in which no car is ever on the wrong tyres
+ * (true from the grid with plans of the right class) and whose table entries are 0 where it reads them, is cell for cell
+ * the same scenario of mcgp_run_strategies, and its wrong_laps is all in column 0.
+ * Random numbers: simulation i of every scenario has id sim_offset + i and draws what mcgp_run's (from the grid) or
+ * mcgp_run_from_state's (from a state) simulation i draws; nothing new is drawn and no draw moves.
+ *   hist_out       [S][n][n]      [scenario][driver][position - 1]
+ *   delta_out      [S][n][2n - 1] as mcgp_run_strategies': paired position changes against scenario 0; or NULL
+ *   wrong_laps_out [S][n][L + 1]  [scenario][driver][w], w = the number of recorded laps (1 .. L from the grid,
+ *                                 state->lap + 1 .. L from a state) whose lap time was computed with the car on the wrong
+ *                                 tyres; a car that retires on lap k has no lap time on k.  Every row sums to n_sims; or
+ *                                 NULL
+ *   orders_out     [S][n_sims][n] driver index classified p-th, or NULL
+ * hist_out, delta_out and wrong_laps_out are ACCUMULATED into, orders_out is written, and all only after every launch has
+ * succeeded: on an error they are left as they were.  Every argument is checked before any device lookup: what
+ * mcgp_run_strategies checks (n_scenarios, plans, the state, grid_probs, deviates other than MCGP_DEVIATES_32, NULLs),
+ * change_count NULL or above 64, `changes` NULL with a non-zero count, `model` NULL, a table entry that is not finite or
+ * outside [0, 60], a condition outside the enum, a lap outside [first, L] ("(lap 1 has the configuration's condition)"
+ * from the grid, "(after the state's lap)" from a state), first_lap > last_lap and two changes of one scenario that share
+ * a lap are MCGP_E_BAD_ARG with a message that names the scenario, the change and the field.  n_sims == 0 succeeds
+ * without a device.  The device work goes chunk by chunk through mcgp_run_strategies' staging budget (one byte per
+ * scenario, simulation and driver, and a u16 more when wrong_laps_out is wanted); device memory does not grow with
+ * n_sims.  Any split of [0, N) over calls, sim_offsets or devices sums to the same counts.  mcgp_last_kernel_name
+ * afterwards is "mcgp::race_weather_kernel".  Added entry point only: MCGP_ABI_VERSION stays 6 and a caller tests for
+ * the symbol.
+ * Not in this call: weather inside mcgp_run_combined; a condition that is drawn rather than given; rule cars that react
+ * on different laps; MCGP_DEVIATES_53; the register kernels.
+ * Price (one MI355X, S60, two scenarios x 10^6 simulations, device ms per 10^6, medians of five with max - min;
+ * profiles/weather_time.txt): mcgp_run_strategies built from the parent commit, two empty scenarios, 97.39 (0.11);
+ * mcgp_run_weather, two empty scenarios and a zero table, 101.64 (0.21), 4.4 % more; an empty scenario and one that is damp
+ * from lap L / 2 to the flag, a zero table, 101.44 (0.43), 4.2 % more; the same change under the default table, 107.27 (0.15),
+ * 10.1 % more: a lap whose condition has a non-zero row pays a bit test wherever a base pace is read, and the read of the
+ * table where the car's entry is non-zero; every other lap one wave-uniform test.  The five other scenario calls compile to the parent's code and keep its times. */
+int32_t mcgp_run_weather(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                         const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                         const mcgp_pit_plan *plans, const uint32_t *change_count, const mcgp_track_change *changes,
+                         const mcgp_weather_model *model, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                         int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *wrong_laps_out,
+                         uint8_t *orders_out);
+
 /* Race time gaps: the model's binary64 cumulative times, counted on the device as histograms over caller-given edges
  * (seconds): every car's gap to the leader by lap, the lead (winning margin on the last lap) and the gap between named
  * pairs of drivers, from the grid or from a mid-race state.  Everything is read from the race model's state after the

@@ -11,6 +11,7 @@ RaceSimulator.run_penalties adds time penalties to the scenarios (TimePenalty, P
 RaceSimulator.run_events sets the race's events on chosen laps (RaceEvent, EventResult: a safety car on lap 31, a green rest of the race);
 RaceSimulator.run_paces adds lap-time offsets to the scenarios (PaceOffset, PaceResult: damage until the next stop, an engine mode for ten laps);
 RaceSimulator.run_combined holds plans, penalties, events and offsets in one scenario (CombinedResult: a safety car on lap 31, a penalty served under it);
+RaceSimulator.run_weather changes the track condition by lap (TrackChange, WeatherModel, WeatherResult: rain from lap 30, who gains by boxing at once);
 RaceSimulator.run_stints counts the model's tyre stints (StintResult: stop laps, compound sequences, odds by stop count);
 RaceSimulator.run_moves counts how the field moves (MoveResult: grid-to-finish odds, start gains, passes by driver, lap and pair);
 RaceSimulator.run_conditions counts combinations and conditional odds (conditions.parse, Condition, ConditionResult).
@@ -19,13 +20,13 @@ CPU fallback.
 """
 from .simulation import (DEFAULT_GAP_EDGES, CarState, ChampionshipResult, CombinedResult, EventResult, GapResult, MatchupResult,  # noqa: F401
                          MoveResult, PaceOffset, PaceResult, PenaltyResult, PitPlan, RaceConfig, RaceEvent, RaceSimulator, RaceState, StintResult, StrategyResult,
-                         TimePenalty, TraceResult,
+                         TimePenalty, TraceResult, TrackChange, WeatherModel, WeatherResult,
                          decode_stints, encode_stints, histogram_to_probs, pit_window, run_championship,
                          run_monte_carlo_batch)
 from .conditions import Condition, ConditionResult  # noqa: F401
 from . import conditions, config  # noqa: F401
 
 __all__ = ['DEFAULT_GAP_EDGES', 'CarState', 'ChampionshipResult', 'CombinedResult', 'Condition', 'ConditionResult', 'EventResult', 'GapResult', 'MatchupResult', 'MoveResult', 'PaceOffset', 'PaceResult', 'PenaltyResult', 'PitPlan', 'RaceConfig', 'RaceEvent',
-           'RaceSimulator', 'RaceState', 'StintResult', 'StrategyResult', 'TimePenalty', 'TraceResult', 'decode_stints', 'encode_stints',
+           'RaceSimulator', 'RaceState', 'StintResult', 'StrategyResult', 'TimePenalty', 'TraceResult', 'TrackChange', 'WeatherModel', 'WeatherResult', 'decode_stints', 'encode_stints',
            'histogram_to_probs', 'pit_window',
            'run_championship', 'run_monte_carlo_batch', 'conditions', 'config']

@@ -115,6 +115,21 @@ class McgpPaceOffset(C.Structure):
                 ('seconds', C.c_double)]
 
 
+MAX_SCENARIO_TRACK_CHANGES = 64                    # include/mcgp.h: MCGP_MAX_SCENARIO_TRACK_CHANGES
+MAX_WRONG_TYRE_SECONDS = 60.0
+TRACKS = ('dry', 'damp', 'wet')                    # MCGP_DRY .. MCGP_WET_TRACK, by id
+
+
+class McgpTrackChange(C.Structure):
+    """mcgp_track_change: the track condition of laps first_lap..last_lap in a scenario of mcgp_run_weather."""
+    _fields_ = [('first_lap', C.c_int32), ('last_lap', C.c_int32), ('condition', C.c_int32)]
+
+
+class McgpWeatherModel(C.Structure):
+    """mcgp_weather_model: seconds a lap on [condition][compound], for one call of mcgp_run_weather."""
+    _fields_ = [('wrong_tyre_sec', (C.c_double * 5) * 3)]
+
+
 class McgpConditionAtom(C.Structure):
     """mcgp_condition_atom: holds iff (lo <= value <= hi) != (negate != 0)."""
     _fields_ = [('fact', C.c_int32), ('a', C.c_int32), ('b', C.c_int32), ('lo', C.c_int32), ('hi', C.c_int32),
@@ -298,7 +313,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
            'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
            'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live', 'mcgp_run_paces',
-           'mcgp_run_combined')
+           'mcgp_run_combined', 'mcgp_run_weather')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -452,6 +467,15 @@ def lib():
                                             C.POINTER(C.c_uint32), C.POINTER(McgpLapEvent),
                                             C.POINTER(C.c_uint32), C.POINTER(McgpPaceOffset), C.c_uint64, C.c_uint64,
                                             C.c_uint64, C.c_int32, u64p, u64p, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
+        if 'mcgp_run_weather' not in missing:
+            # the plans, (count, changes), the call's model; hist, delta, wrong_laps, orders
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_weather.restype = C.c_int32
+            L.mcgp_run_weather.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.POINTER(McgpRaceState),
+                                           C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
+                                           C.POINTER(C.c_uint32), C.POINTER(McgpTrackChange),
+                                           C.POINTER(McgpWeatherModel), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32,
+                                           u64p, u64p, u64p, C.POINTER(C.c_uint8)]
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES

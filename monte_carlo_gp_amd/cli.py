@@ -17,6 +17,8 @@
         --offset 'box now=NOR:0.6@12+' --plan 'box now=:13/HARD' --offset push=NOR:-0.15@40-49
     python -m monte_carlo_gp_amd.cli what-if --race Bahrain --season 2024 --offline --state lap30.json --driver NOR \
         --event 'sc=sc@31' --plan 'sc=:31/HARD' --give 'sc=NOR:5' --offset 'sc=VER:0.4@31+'
+    python -m monte_carlo_gp_amd.cli weather --race Bahrain --season 2024 --offline --driver NOR --change 'rain=damp@30-45' \
+        --plan 'rain=:30/INTERMEDIATE,46/MEDIUM' [--state lap29.json] [--wrong-tyre dry:INTERMEDIATE=3.0]
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -57,6 +59,12 @@ the car's next pit stop; negative seconds are faster; several per NAME make one 
 matches joins that scenario) and compares the scenarios with `as is` (no offset, no plan): for --driver the win, podium
 and expected-position change against the first scenario and, for an until-stop offset, the distribution of the laps it
 was carried.
+weather changes the track condition on chosen laps (--change NAME=CONDITION@LAP[-LAP], CONDITION dry | damp | wet; several
+per NAME make one scenario; a --plan of --driver whose NAME matches joins that scenario, and a plan without a stop on the
+change lap stays out) and compares the scenarios with `as forecast` (no change, no plan): for --driver the win, podium and
+expected-position change against the first scenario and the expected laps on the wrong class of tyres.  Cars without a
+plan cross over by the model's rule.  --wrong-tyre CONDITION:COMPOUND=SECONDS replaces a cell of the project's default
+table of seconds lost per lap.
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
 on the data path; results are gathered once).
 """
@@ -656,6 +664,138 @@ def cmd_events(args) -> int:
     if args.json:
         with open(args.json, 'w') as f:
             json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
+    return 0
+
+
+WEATHER_BASELINE = 'as forecast'
+
+
+def parse_change(text: str):
+    """--change NAME=CONDITION@LAP[-LAP] -> (NAME, TrackChange)."""
+    from .simulation import TrackChange
+    name, sep, rest = text.partition('=')
+    if not sep or not name.strip():
+        raise ValueError(f'--change {text!r}: expected NAME=CONDITION@LAP[-LAP]')
+    cond, at, laps = rest.partition('@')
+    cond = cond.strip().lower()
+    if cond not in ('dry', 'damp', 'wet'):
+        raise ValueError(f"--change {text!r}: CONDITION is 'dry', 'damp' or 'wet', got {cond!r}")
+    a, dash, b = laps.partition('-')
+    if not at or not a.strip().isdigit() or (dash and not b.strip().isdigit()):
+        raise ValueError(f'--change {text!r}: expected @LAP or @LAP-LAP after the condition')
+    lo, hi = int(a), int(b) if dash else int(a)
+    if hi < lo:
+        raise ValueError(f'--change {text!r}: the range runs backwards')
+    return name.strip(), TrackChange(lo, hi, cond)
+
+
+def parse_wrong_tyre(items):
+    """--wrong-tyre CONDITION:COMPOUND=SECONDS ... -> WeatherModel: the project's default table with those cells
+    replaced (none given: the default table)."""
+    from .simulation import DEFAULT_WRONG_TYRE_SECONDS, WeatherModel
+    table = {c: dict(row) for c, row in DEFAULT_WRONG_TYRE_SECONDS.items()}
+    for text in items or ():
+        usage = f'--wrong-tyre {text!r}: expected CONDITION:COMPOUND=SECONDS'
+        cell, sep, seconds = text.partition('=')
+        cond, colon, comp = cell.partition(':')
+        cond, comp = cond.strip().lower(), comp.strip().upper()
+        if not sep or not colon:
+            raise ValueError(usage)
+        if cond not in table:
+            raise ValueError(f"--wrong-tyre {text!r}: CONDITION is 'dry', 'damp' or 'wet', got {cond!r}")
+        if comp not in table[cond]:
+            raise ValueError(f'--wrong-tyre {text!r}: COMPOUND is one of {list(table[cond])}, got {comp!r}')
+        try:
+            table[cond][comp] = float(seconds)
+        except ValueError:
+            raise ValueError(f'--wrong-tyre {text!r}: SECONDS is a number, got {seconds.strip()!r}') from None
+    model = WeatherModel(table)
+    model.table()                                           # the range of every cell
+    return model
+
+
+def weather_scenarios(changes, driver=None, plans=()):
+    """The weather command's scenarios -> (changes, strategies): 'as forecast' (no change, no plan) first, unless the user
+    names a scenario 'as forecast' themselves; then one scenario per NAME, holding every --change of that NAME and the
+    --plan of that NAME."""
+    if not changes:
+        raise ValueError('give at least one --change NAME=CONDITION@LAP[-LAP]')
+    if plans and not driver:
+        raise ValueError('--plan needs --driver')
+    out, strategies = {WEATHER_BASELINE: []}, {}
+    for text in changes:
+        name, ch = parse_change(text)
+        out.setdefault(name, []).append(ch)
+    for text in plans or ():
+        name, plan = parse_plan(text, driver)
+        if name in strategies:
+            raise ValueError(f'--plan: scenario {name!r} given twice')
+        out.setdefault(name, [])
+        strategies[name] = [plan]
+    return out, strategies
+
+
+def cmd_weather(args) -> int:
+    from .simulation import RaceState
+    fixture = synthetic_fixture()
+    if args.fixture:
+        with open(args.fixture) as f:
+            fixture = json.load(f)
+    elif not args.offline:
+        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+        return 2
+    state = None
+    if args.state:
+        with open(args.state) as f:
+            state = RaceState.from_json(json.load(f))
+    try:
+        changes, strategies = weather_scenarios(args.change, args.driver, args.plan)
+        model = parse_wrong_tyre(args.wrong_tyre)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    print(f"\n{'=' * 60}\nF1 Weather Scenarios: {args.season} {args.race}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
+          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
+    print('=' * 60 + '\n')
+    try:
+        res = F1Predictor(device=args.device).predict_weather(args.season, args.race, fixture, changes, strategies, model,
+                                                              state=state, n_simulations=args.simulations, seed=args.seed,
+                                                              allow_single_compound=args.allow_single_compound)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    base = res.names[0]
+    shown = [args.driver] if args.driver else sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
+    rows = []
+    for name in res.names:
+        print(f"scenario: {name}")
+        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'change':>7} {'P(better)':>10}"
+              f"  gain +- SE   wrong-tyre laps")
+        epos, epos0 = res.expected_position(name), res.expected_position(base)
+        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
+                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
+                   expected_position=epos, drivers={})
+        for d in shown:
+            c = res.compare(name, d)
+            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
+            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
+            wrong = res.expected_wrong_tyre_laps(name, d)
+            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
+                                     expected_position_change=epos[d] - epos0[d], p_better=c['p_better'],
+                                     p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'],
+                                     expected_wrong_tyre_laps=wrong,
+                                     wrong_tyre_laps=[float(x) for x in res.wrong_tyre_laps_distribution(name, d)])
+            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {epos[d] - epos0[d]:+7.2f} "
+                  f"{c['p_better']:10.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}   {wrong:.2f}")
+        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
+        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
+        rows.append(row)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump({'baseline': base, 'n_simulations': res.n_simulations,
+                       'wrong_tyre_seconds': [[float(x) for x in r] for r in model.table()], 'scenarios': rows}, f)
     return 0
 
 
@@ -1451,6 +1591,29 @@ def main(argv=None) -> int:
     t.add_argument('--device', type=int, default=0)
     t.add_argument('--json', type=str, default=None)
     t.set_defaults(fn=cmd_pace)
+    t = sub.add_parser('weather', help='race odds when the track condition changes on chosen laps')
+    t.add_argument('--season', type=int, default=2025)
+    t.add_argument('--race', type=str, required=True)
+    t.add_argument('--change', type=str, action='append', default=[],
+                   help="NAME=CONDITION@LAP[-LAP]: in scenario NAME the laps have CONDITION (dry, damp, wet) instead of the "
+                        "race's; repeat for more; several of one NAME make one scenario")
+    t.add_argument('--driver', type=str, default=None, help='the driver of the --plan scenarios, and the one shown')
+    t.add_argument('--plan', type=str, action='append', default=[],
+                   help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's; joins the --change scenario of that NAME "
+                        "(a plan without stops stays out)")
+    t.add_argument('--wrong-tyre', type=str, action='append', default=[],
+                   help="CONDITION:COMPOUND=SECONDS: seconds a lap on COMPOUND under CONDITION, replacing that cell of the "
+                        "project's default table; repeat for more")
+    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
+    t.add_argument('--allow-single-compound', action='store_true',
+                   help='run plans that use one dry compound (the rule is otherwise enforced where the track stays dry)')
+    t.add_argument('--simulations', type=int, default=100000)
+    t.add_argument('--seed', type=int, default=None)
+    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
+    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
+    t.add_argument('--device', type=int, default=0)
+    t.add_argument('--json', type=str, default=None)
+    t.set_defaults(fn=cmd_weather)
     t = sub.add_parser('what-if', help='race odds under scenarios that mix pit plans, time penalties, race events and '
                                        'lap-time offsets')
     t.add_argument('--season', type=int, default=2025)

@@ -26,6 +26,7 @@
 #include "penalty_pack.h"
 #include "pace_pack.h"
 #include "event_pack.h"
+#include "weather_pack.h"
 #include "scenario.hip.h"
 #include "champ_pack.h"
 
@@ -530,8 +531,8 @@ uint64_t max_sims_per_launch()
 constexpr uint64_t kOrdersChunk = 1ull << 22;
 
 // Staging budgets, so that device memory does not grow with n_sims: of mcgp_run_trace (one byte per lap, driver and
-// simulation) and of the five scenario calls, mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces
-// and mcgp_run_combined (per scenario and simulation a byte per driver, and what the kind stages beside it:
+// simulation) and of the six scenario calls, mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces,
+// mcgp_run_combined and mcgp_run_weather (per scenario and simulation a byte per driver, and what the kind stages beside it:
 // ScenarioKind::sim_bytes)
 constexpr uint64_t kTraceStageBytes = 512ull << 20;
 constexpr uint64_t kStrategyStageBytes = 256ull << 20;
@@ -958,12 +959,12 @@ struct ScenarioChunk {
     // output is not wanted (ScenarioKind::regions lays them out)
     const mcgp::PenaltyScenario *pn;
     const mcgp::PenaltyLap *nl;
-    const uint8_t *el;
+    const uint8_t *el;                      // (with weather: the laps' condition bytes)
     const mcgp::PaceScenario *ps;
     const mcgp::PaceLap *pl;
-    const double *sec;
+    const double *sec;                      // (with weather: the table of wrong-tyre seconds)
     uint32_t *evs;                          // [S][m] packed event counts
-    uint16_t *car;                          // [S][m][n] laps carried
+    uint16_t *car;                          // [S][m][n] laps carried (with weather: laps on the wrong tyres)
 };
 
 // Grid width of a counting kernel over m simulations in blocks of `block` threads: the tiles, but no more blocks than
@@ -1015,8 +1016,8 @@ struct ScenarioOutput {
     std::function<void(unsigned long long *extra, size_t rows, uint64_t n_sims)> fix_up;
 };
 
-// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces and mcgp_run_combined each have of their
-// own; run_scenarios has the rest.
+// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces, mcgp_run_combined and mcgp_run_weather
+// each have of their own; run_scenarios has the rest.
 struct ScenarioKind {
     const char *what;                       // the call in check_deviates_32's message
     // generic_geometry's and note_launch's name of the race kernel.  These are the documented names of the calls
@@ -2422,6 +2423,49 @@ int32_t mcgp_run_combined(const mcgp_config *cfg, const mcgp_drivers *drv, const
         if (extra[2]) count_paces(l, n, L, grid_cap, nullptr, extra[2]);
     };
     k.outputs = {fate_output(fate_out), events_output(events_out), carried_output(carried_out, cfg)};
+    return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
+                         hist_out, delta_out, orders_out, k);
+}
+
+int32_t mcgp_run_weather(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                         const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                         const mcgp_pit_plan *plans, const uint32_t *change_count, const mcgp_track_change *changes,
+                         const mcgp_weather_model *model, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                         int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *wrong_laps_out,
+                         uint8_t *orders_out)
+{
+    std::vector<uint8_t> cond_laps;
+    std::vector<double> table;
+    ScenarioKind k = {"weather run", "weather", "mcgp::race_weather_kernel", mcgp::kRuleWeather};
+    k.tables = {{"change_count", "changes", change_count, changes, [&](uint64_t *n_changes) {
+        return mcgp::check_change_counts(n_scenarios, change_count, n_changes);
+    }}};
+    // the call-wide model is checked with the changes (cfg has been checked by then)
+    k.pack = [&](int first_lap, bool resumed) {
+        return mcgp::pack_weather(n_scenarios, change_count, changes, model, cfg->track_condition, cfg->total_laps, first_lap,
+                                  resumed, &cond_laps, &table);
+    };
+    // a position byte per driver, and its u16 of laps on the wrong tyres when they are counted
+    k.sim_bytes = wrong_laps_out ? (size_t)n * 3 : (size_t)n;
+    // the kernel reads the condition bytes and the table through the arguments of the rule sets it never meets
+    k.regions = [&](Layout &ws, ScenarioChunk &l, uint64_t chunk) {
+        if (wrong_laps_out) ws.add(&l.car, (size_t)n_scenarios * chunk * n);
+        ws.add(&l.el, cond_laps.size(), cond_laps.data());
+        ws.add(&l.sec, table.size(), table.data());
+    };
+    // the deltas as mcgp_run_strategies counts them (S - 1 grid rows), the laps on the wrong tyres one layer per driver
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
+        if (d_delta)
+            hipLaunchKernelGGL(mcgp::strategy_count_deltas,
+                               dim3(count_grid_x(l.m, mcgp::kStrategyCountBlock, grid_cap, l.S - 1), l.S - 1),
+                               dim3(mcgp::kStrategyCountBlock), 0, nullptr, l.stage, l.m, n, d_delta);
+        if (extra[0])
+            hipLaunchKernelGGL(mcgp::weather_count,
+                               dim3(count_grid_x(l.m, mcgp::kWeatherCountBlock, grid_cap, (uint64_t)l.S * n), l.S, n),
+                               dim3(mcgp::kWeatherCountBlock), 0, nullptr, l.car, l.m, n, (uint32_t)cfg->total_laps, extra[0]);
+    };
+    // wrong_laps [S][n][L + 1]; column 0 is, like carried's, what the others leave of n_sims
+    k.outputs = {carried_output(wrong_laps_out, cfg)};
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
                          hist_out, delta_out, orders_out, k);
 }

@@ -205,11 +205,12 @@ struct ModelTyres {
     __device__ __forceinline__ void operator()(uint32_t /*driver*/, uint32_t & /*comp*/, uint32_t & /*age*/) const {}
 };
 
-// The pace policy of every kernel but race_scenario_kernel with paces: a car's base pace is the model's.  start_from_grid and run_laps
+// The pace policy of every kernel but race_scenario_kernel with paces or weather: a car's base pace is the model's.  start_from_grid and run_laps
 // ask a policy once per lap, begin_lap(lap) (wave-uniform), and wherever the model reads base_pace[d] -- lap 1's base_lap,
 // the lap time of laps >= 2, the pace of the overtake passes (candidate scan and attempt probability) -- base(d, b) with
 // b = base_pace[d], and use what it returns.  ModelPace returns b itself, so that the call vanishes; OffsetPace
-// (paces.hip.h) adds the caller's lap-time offsets there.
+// (paces.hip.h) adds the caller's lap-time offsets there, WeatherPace (weather.hip.h) the seconds of the car's compound
+// under the lap's track condition.
 struct ModelPace {
     __device__ __forceinline__ void begin_lap(int /*lap*/) {}
     __device__ __forceinline__ double base(uint32_t /*d*/, double b) const { return b; }
@@ -356,6 +357,18 @@ struct DrawnEvents {
     __device__ __forceinline__ int at(int /*lap*/) const { return -1; }
 };
 
+// The track policy of every kernel but race_scenario_kernel with weather: the track condition is the race's own on every
+// lap.  run_laps asks a policy once per lap, begin_lap(lap, track) (wave-uniform) with the parameter block's condition,
+// and uses what it returns wherever that lap's code reads the condition: the red flag's and the rule stop's
+// stint_compound and the rule stop's two-compound waiver.  Once per running car and lap, where the lap time is computed,
+// lap_time_on(d, comp) sees the compound it is computed on and says whether a car under the model's rule has to stop
+// for the other class of tyres.  ModelTrack returns `track` itself and a constant false, so that both calls vanish;
+// WeatherTrack (weather.hip.h) reads the caller's condition of the lap.
+struct ModelTrack {
+    __device__ __forceinline__ int begin_lap(int /*lap*/, int track) { return track; }
+    __device__ __forceinline__ bool lap_time_on(uint32_t /*d*/, uint32_t /*comp*/) const { return false; }
+};
+
 // Laps first_lap .. L of one lane's race, reference :166-228, from the state the rows hold after lap first_lap - 1: `ord`
 // sorted by (cumulative time, grid slot), the DRS / dirty-air flags of update_positions, the retirement laps in `out`,
 // and the reference's drs_disabled_until.  race_kernel runs it from lap 2, race_resume_kernel (resume.hip.h) from k + 1.
@@ -364,15 +377,17 @@ struct DrawnEvents {
 // rule; race_scenario_kernel, scenario.hip.h, passes a ScenarioPit: planned stops and, by rule set, time penalties).
 // `evp` may replace a lap's event (DrawnEvents: never; with events the scenario kernel passes ForcedEvents, the
 // caller's overrides).  `pace` gives a car's base pace on a lap (ModelPace: the model's; with paces it passes OffsetPace,
-// the caller's lap-time offsets).
-template <class LapObserver, class PitPolicy = RulePit, class EventPolicy = DrawnEvents, class PacePolicy = ModelPace>
+// the caller's lap-time offsets; with weather WeatherPace).  `trk` gives a lap's track condition (ModelTrack: the
+// race's; with weather it passes WeatherTrack, the caller's condition by lap).
+template <class LapObserver, class PitPolicy = RulePit, class EventPolicy = DrawnEvents, class PacePolicy = ModelPace,
+          class TrackPolicy = ModelTrack>
 __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1, uint32_t seed_lo,
                                          uint32_t seed_hi, int first_lap, int drs_disabled_until, LapObserver &obs,
                                          PitPolicy pit = PitPolicy(), EventPolicy evp = EventPolicy(),
-                                         PacePolicy pace = PacePolicy())
+                                         PacePolicy pace = PacePolicy(), TrackPolicy trk = TrackPolicy())
 {
     const KParams *__restrict__ P = e.P;
-    const int n = e.n, L = e.L, track = e.track;
+    const int n = e.n, L = e.L, race_track = e.track;
     const float4 *t_norm = e.norm;
     const double *t_base = e.base, *t_factor = e.factor, *t_deg = e.deg, *t_var = e.var;
     const double *t_cdeg = e.cdeg, *t_cdelta = e.cdelta;
@@ -382,6 +397,7 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
     for (int lap = first_lap; lap <= L; ++lap) {
         const int remaining_laps = L - lap;
         int event = kEventNone;
+        const int track = trk.begin_lap(lap, race_track);
         pace.begin_lap(lap);
         // ---- race-interrupting events, :168-176 (short-circuit chain, Q8) ----
         {
@@ -470,11 +486,12 @@ __device__ __forceinline__ void run_laps(const Rows &s, const LapEnv &e, uint32_
                 }
                 double t = s.Cum(d) + lap_time;
                 age += 1u;
+                const bool wrong = trk.lap_time_on(d, comp);
                 // _handle_pit_stops :454-492 (no randomness, no cross-car dependence), or the policy's planned stop
                 uint32_t plan_c = 0u;
                 const int plan = pit.decide(d, plan_c);
                 bool stopped = false;
-                if (plan < 0 ? ((int)age > (int)t_opt[d * kCompStride + comp] && remaining_laps > 5) : plan > 0) {
+                if (plan < 0 ? (((int)age > (int)t_opt[d * kCompStride + comp] || wrong) && remaining_laps > 5) : plan > 0) {
                     stopped = true;
                     t = t + pit_loss;
                     uint32_t newc;

@@ -1,5 +1,5 @@
-// scenario.hip.h -- the race kernel of the five what-if calls: mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events,
-// mcgp_run_paces and mcgp_run_combined (include/mcgp.h, which states how the rule sets meet on one lap).
+// scenario.hip.h -- the race kernel of the six what-if calls: mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events,
+// mcgp_run_paces, mcgp_run_combined (include/mcgp.h, which states how the rule sets meet on one lap) and mcgp_run_weather.
 //
 // race_scenario_kernel<kFromState, kRules> is the generic kernel's code -- start_from_grid or start_from_state, run_laps,
 // classify_and_count -- over S scenarios of one race with common random numbers: one lane runs one (scenario, simulation)
@@ -13,10 +13,14 @@
 //                   event word;
 //   kRulePaces      (paces.hip.h) OffsetPace in the pace slot of start_from_grid (lap 1 reads the base pace) and of
 //                   run_laps; ScenarioPit's clear of an UNTIL_STOP offset; the laps carried of an offset no stop cleared.
+//   kRuleWeather    (weather.hip.h) WeatherTrack in run_laps' track slot and WeatherPace in the pace slot of
+//                   start_from_grid and of run_laps; the laps on the wrong tyres.  It is instantiated alone, and its
+//                   tables come in the arguments of the rule sets it never meets: the condition bytes in `event_laps`
+//                   (the same [S][L + 1] bytes), the table of seconds in `lap_sec`, the staged u16 in `carried`.
 //
-// A slot whose bit is clear holds the model's policy (ModelPace, DrawnEvents, NoLapObserver), which vanishes at compile
-// time.  The instantiations are the ten the C ABI has: no rule set, each one alone, all three, each from the grid and
-// from a state.  An instantiation never reads a table whose bit is clear: callers pass NULL there.
+// A slot whose bit is clear holds the model's policy (ModelPace, DrawnEvents, NoLapObserver, ModelTrack), which vanishes
+// at compile time.  The instantiations are the twelve the C ABI has: no rule set, each one alone, the first three
+// together, each from the grid and from a state.  An instantiation never reads a table whose bit is clear: callers pass NULL there.
 //
 // Every table is packed by its rule set's packer and read at wave-uniform addresses once per lap: ScenarioPit::begin_lap
 // reads the lap's StopLap, PenaltyLap and PaceLap::until, OffsetPace::begin_lap the lap's PaceLap, ForcedEvents the lap's
@@ -28,23 +32,26 @@
 // Staging per scenario and simulation, each in the layout its counting kernel reads: n bytes (the classified position;
 // with penalties | fate << 5, and penalties_count, which masks the position, also counts mcgp_run_combined's deltas), one
 // u32 with events (the packed event counts: events_count; with all three rule sets only when ev_stage is given), n u16
-// with paces when `carried` is given (paces_count; for mcgp_run_combined both with delta NULL).
+// with paces when `carried` is given (paces_count; for mcgp_run_combined both with delta NULL), n u16 with weather when
+// `carried` is given (the laps on the wrong tyres: weather_count).
 //
 // Price (one MI355X, S60, two scenarios x 10^6 simulations, device ms per 10^6, medians of five with max - min;
 // profiles/combined_time.txt): all three rule sets, two empty scenarios 102.84 (0.41) against 98.22 (0.39) with
 // none and 106.69 (0.39) for mcgp_run_paces with an UNTIL_STOP offset, the dearest single-kind call; with a penalty to
 // serve 103.08 (0.35), a forced safety car 102.50 (0.45), an UNTIL_STOP offset 108.13 (0.49), all three and a planned stop
-// 109.59 (0.42).  profiles/penalties_time.txt, events_time.txt and paces_time.txt have each rule set alone.
+// 109.59 (0.42).  profiles/penalties_time.txt, events_time.txt, paces_time.txt and weather_time.txt have each rule set
+// alone.
 #pragma once
 #include <type_traits>
 
 #include "penalties.hip.h"
 #include "events.hip.h"
 #include "paces.hip.h"
+#include "weather.hip.h"
 
 namespace mcgp {
 
-constexpr uint32_t kRulePenalties = 1u, kRuleEvents = 2u, kRulePaces = 4u;
+constexpr uint32_t kRulePenalties = 1u, kRuleEvents = 2u, kRulePaces = 4u, kRuleWeather = 8u;
 constexpr uint32_t kRuleAll = kRulePenalties | kRuleEvents | kRulePaces;
 
 // run_laps' pit policy of a scenario: PlanPit decides the stops; after_pit adds the served SERVE_AT_STOP penalty after
@@ -103,8 +110,9 @@ struct ScenarioPit {
 // Simulations sim_offset + [0, m) of every scenario (gridDim.y = S), from the grid (kFromState false) or from `state`.
 // hist [S][n][n] is ACCUMULATED into; stage [S][m][n] (classified position of each driver, | fate << 5 with penalties) is
 // written, and, where wanted (NULL: not), ev_stage [S][m] (the packed event counts) with events and carried [S][m][n] u16
-// at the drivers that have an UNTIL_STOP offset in the scenario with paces.  Pointers of a rule set outside kRules are
-// not read: pass NULL.
+// at the drivers that have an UNTIL_STOP offset in the scenario with paces.  With weather event_laps [S][L + 1] holds the
+// laps' condition bytes, lap_sec the [3][5] table and carried [S][m][n] u16 (NULL: not wanted) gets every driver's laps
+// on the wrong tyres.  Pointers of a rule set outside kRules are not read: pass NULL.
 template <bool kFromState, uint32_t kRules>
 __global__ void __launch_bounds__(512)
 race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restrict__ state,
@@ -117,10 +125,11 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
                      uint32_t n_batches)
 {
     static_assert(kRules == 0u || kRules == kRulePenalties || kRules == kRuleEvents || kRules == kRulePaces ||
-                      kRules == kRuleAll, "the rule sets of the C ABI");
+                      kRules == kRuleAll || kRules == kRuleWeather, "the rule sets of the C ABI");
     constexpr bool kPen = (kRules & kRulePenalties) != 0u, kEv = (kRules & kRuleEvents) != 0u;
-    constexpr bool kPace = (kRules & kRulePaces) != 0u;
-    using Pace = std::conditional_t<kPace, OffsetPace, ModelPace>;
+    constexpr bool kPace = (kRules & kRulePaces) != 0u, kWx = (kRules & kRuleWeather) != 0u;
+    using Pace = std::conditional_t<kPace, OffsetPace, std::conditional_t<kWx, WeatherPace, ModelPace>>;
+    using Track = std::conditional_t<kWx, WeatherTrack, ModelTrack>;
     using Events = std::conditional_t<kEv, ForcedEvents, DrawnEvents>;
     using Observer = std::conditional_t<kEv, PackedEventCounter, NoLapObserver>;
     const uint32_t sid = blockIdx.y;
@@ -138,24 +147,39 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
               [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
         const uint64_t sim = sim_offset + local;
         const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
-        // the lane's place in the stagings: worked out here where events or paces stage beside the position bytes, after
-        // the race otherwise
+        // the lane's place in the stagings: worked out here where events, paces or weather stage beside the position
+        // bytes, after the race otherwise
         uint64_t lane = 0, cell = 0;
-        if constexpr (kEv || kPace) {
+        if constexpr (kEv || kPace || kWx) {
             lane = (uint64_t)sid * m + local;
             cell = lane * (uint64_t)e.n;
         }
-        uint16_t *crow = kPace && carried ? carried + cell : nullptr;
+        uint16_t *crow = (kPace || kWx) && carried ? carried + cell : nullptr;
         uint32_t served = 0u, active = until;
         Pace pace;
         if constexpr (kPace) pace = {pl, lap_sec, ps->until_sec, &active, 0u, 0u, 0u};
+        Track trk;
+        if constexpr (kWx) {
+            pace = {event_laps + lap0, lap_sec, s, nullptr, 0u};
+            trk = {event_laps + lap0, crow, 0u};
+        }
         const ScenarioPit<kRules> pit = {plan, pen, nl, pl, kPace ? ps->until_from : nullptr, &served, &active, crow, serve,
                                          0u, 0u, 0u};
         const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
                                         : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr, PlannedTyres{sc}, pace);
+        if constexpr (kWx) {
+            // lap 1's lap time, from the grid: on the start compound under the configuration's condition
+            if (crow) {
+                for (int d = 0; d < e.n; ++d) {
+                    const uint32_t pk = s.Pk((uint32_t)d);
+                    crow[d] = (uint16_t)(!kFromState && !(pk & kDnf) &&
+                                         wrong_tyres((uint32_t)e.track, (pk >> kCompShift) & 7u));
+                }
+            }
+        }
         Observer seen = {};
-        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, seen, pit, forced,
-                 pace);                                                                             // reference :166-228
+        run_laps(s, e, c0, c1, seed_lo, seed_hi, at.first_lap, at.drs_disabled_until, seen, pit, forced, pace,
+                 trk);                                                                              // reference :166-228
         // at the flag: the unserved penalty, then the post-race one, of every running car.  A scenario without serve and
         // flag penalties skips the step: its field is sorted already
         uint32_t retired = 0u;
@@ -175,7 +199,7 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
         }
         classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
         // each driver's classified position and, with penalties, the fate of its serve penalty
-        if constexpr (!(kEv || kPace)) cell = ((uint64_t)sid * m + local) * (uint64_t)e.n;
+        if constexpr (!(kEv || kPace || kWx)) cell = ((uint64_t)sid * m + local) * (uint64_t)e.n;
         uint8_t *row = stage + cell;
         for (int p = 0; p < e.n; ++p) {
             const uint32_t d = s.Ord(p);
@@ -193,7 +217,7 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
             if (kRules == kRuleEvents || ev_stage) ev_stage[lane] = seen.packed;
         }
         // the offsets no stop cleared: carried up to the car's retirement, or to the flag
-        if (crow) {
+        if (kPace && crow) {
             for (uint32_t rest = active; rest; rest &= rest - 1u) {
                 const uint32_t d = (uint32_t)__ffs((int)rest) - 1u, pk = s.Pk(d);
                 const int from = (int)ps->until_from[d];
@@ -205,7 +229,7 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
 }
 
 // The instantiation behind a scenario call, for the launch and for its register count: `rules` is one of the five sets
-// above (anything else: NULL), from the grid or from a state.
+// above or kRuleWeather (anything else: NULL), from the grid or from a state.
 using ScenarioKernel = decltype(&race_scenario_kernel<false, 0u>);
 inline ScenarioKernel scenario_kernel(uint32_t rules, bool from_state)
 {
@@ -216,6 +240,8 @@ inline ScenarioKernel scenario_kernel(uint32_t rules, bool from_state)
     case kRuleEvents: return from_state ? &race_scenario_kernel<true, kRuleEvents> : &race_scenario_kernel<false, kRuleEvents>;
     case kRulePaces: return from_state ? &race_scenario_kernel<true, kRulePaces> : &race_scenario_kernel<false, kRulePaces>;
     case kRuleAll: return from_state ? &race_scenario_kernel<true, kRuleAll> : &race_scenario_kernel<false, kRuleAll>;
+    case kRuleWeather:
+        return from_state ? &race_scenario_kernel<true, kRuleWeather> : &race_scenario_kernel<false, kRuleWeather>;
     }
     return nullptr;
 }

@@ -370,6 +370,25 @@ class F1Predictor:
                              track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
                              allow_single_compound=allow_single_compound)
 
+    def predict_weather(self, season: int, race: str, fixture: dict | str, changes: dict, strategies: dict | None = None,
+                        model=None, state=None, n_simulations: int = 100000, seed: int | None = None,
+                        prediction_point: str = 'fp2', allow_single_compound: bool = False):
+        """Weather scenarios (not in the reference): predict_strategies' race run through RaceSimulator.run_weather under
+        each scenario of `changes` ({name: [TrackChange, ...]}) and `strategies` ({name: [PitPlan, ...]} or None), with
+        `model` (a WeatherModel, None: the project's default table).  Returns the WeatherResult."""
+        if isinstance(fixture, str):
+            with open(fixture) as f:
+                fixture = json.load(f)
+        if not fixture.get('drivers'):
+            raise ValueError(f"No practice data available for {season} {race}")
+        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
+        sim = RaceSimulator(inp['config'], device=self.device)
+        return sim.run_weather(n_simulations, changes, strategies, model, inp['base_pace'], inp['tire_deg'],
+                               inp['driver_variance'], inp['driver_dnf_rates'],
+                               grid_probs=inp['grid_probs'] if state is None else None, state=state, seed=seed,
+                               track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
+                               allow_single_compound=allow_single_compound)
+
     def predict_combined(self, season: int, race: str, fixture: dict | str, scenarios: dict, state=None,
                          n_simulations: int = 100000, seed: int | None = None, prediction_point: str = 'fp2',
                          allow_single_compound: bool = False):

@@ -417,7 +417,8 @@ class RaceSimulator:
         """The scenarios' pit plans as mcgp_pit_plan structs with their count per scenario, and likewise the items of
         each of the call's own `kinds`, (items_of {name: [item]}, pack_items), through pack_items(name, items, index)
         -> [struct]: scenario by scenario, plans first, then the kinds in their order.  check_compounds: the
-        two-compound rule holds for every plan.  -> counts, structs, [(counts, structs) of each kind]."""
+        two-compound rule holds for every plan (a bool, or scenario name -> bool).  -> counts, structs, [(counts,
+        structs) of each kind]."""
         index = {d: i for i, d in enumerate(src.drivers)}
         counts, c_plans, packed_kinds = [], [], [([], []) for _ in kinds]
         for name in names:
@@ -425,7 +426,7 @@ class RaceSimulator:
             for plan in plans:
                 if str(plan.driver) not in index:
                     raise ValueError(f'scenario {name!r}: {plan.driver!r} is not one of the drivers')
-                if check_compounds:
+                if check_compounds(name) if callable(check_compounds) else check_compounds:
                     used = None
                     if src.arrays is not None:
                         used = {c for j, c in enumerate(N.COMPOUNDS)
@@ -440,13 +441,16 @@ class RaceSimulator:
         return counts, c_plans, packed_kinds
 
     def _run_scenarios(self, entry, result, label, n_simulations, kinds, strategies, race, grid_probs, state, seed,
-                       sim_offset, drivers, return_orders, allow_single_compound):
-        """run_strategies, run_penalties, run_events, run_paces and run_combined: the race under named scenarios of pit
+                       sim_offset, drivers, return_orders, allow_single_compound, call_wide=(), all_dry=None):
+        """run_strategies, run_penalties, run_events, run_paces, run_combined and run_weather: the race under named scenarios of pit
         plans (`strategies`) and of the call's own `kinds` of items, a list (empty for run_strategies) of (items {name:
         [item]}, item_type: their struct, pack_items: see _pack_plans, extra = (name, shape(S, n, L)): the kind's own
         count array).  The scenario names are the union of the dicts in the order given, the kinds' first; the kinds'
         (count, items) pairs follow the plans among the arguments and their count arrays follow hist and delta among
-        the outputs, both in the kinds' order.  result: the result class; label: the dicts' names for the message."""
+        the outputs, both in the kinds' order.  result: the result class; label: the dicts' names for the message.
+        call_wide: the call's arguments that hold for every scenario, after the kinds' (run_weather: its model).
+        all_dry: scenario name -> is the track dry on every lap (None: track_condition says so for all of them); the
+        two-compound rule is checked for the plans of those scenarios."""
         src = self._source(grid_probs, state, drivers)
         strategies = strategies or {}
         names = []
@@ -460,11 +464,13 @@ class RaceSimulator:
         src.arrays                                   # (a bad state is reported before a bad plan)
         by_name = lambda given: {str(k): list(v) for k, v in given.items()}
         counts, c_plans, packed_kinds = self._pack_plans(
-            names, by_name(strategies), src, not allow_single_compound and race[-1] == 'dry',
+            names, by_name(strategies), src,
+            not allow_single_compound and (all_dry if all_dry is not None else race[-1] == 'dry'),
             [(by_name(items), pack) for items, _, pack, _ in kinds])
         head = src.c_args() + (n, S, (C.c_uint32 * S)(*counts), (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans))
         for (_, item_type, _, _), (item_counts, c_items) in zip(kinds, packed_kinds):
             head += ((C.c_uint32 * S)(*item_counts), (item_type * max(len(c_items), 1))(*c_items))
+        head += tuple(call_wide)
         n_simulations = max(int(n_simulations), 0)
         seed64 = self._resolve_seed(seed)
         if not hasattr(N.lib(), entry):
@@ -892,6 +898,79 @@ class RaceSimulator:
             drivers, return_orders, allow_single_compound)
         res.until_from = self._until_from(paces)
         return res
+
+    def _change_kind(self, changes, state):
+        first = 2 if state is None else int(state.lap) + 1
+
+        def pack(name, chs, index):
+            if len(chs) > N.MAX_SCENARIO_TRACK_CHANGES:
+                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_TRACK_CHANGES} changes, got {len(chs)}')
+            packed, covered = [], {}
+            for ch in chs:
+                try:
+                    c = ch.c_struct(first, int(self.config.total_laps))
+                except ValueError as e:
+                    raise ValueError(f'scenario {name!r}: {e}') from None
+                for lap in range(c.first_lap, c.last_lap + 1):
+                    if lap in covered:
+                        raise ValueError(f'scenario {name!r}: lap {lap} has two changes ({covered[lap]} and {ch})')
+                    covered[lap] = ch
+                packed.append(c)
+            return packed
+
+        return changes, N.McgpTrackChange, pack, ('wrong_laps', lambda S, n, L: (S, n, L + 1))
+
+    def run_weather(
+        self,
+        n_simulations: int,
+        changes: dict,
+        strategies: dict | None = None,
+        model: 'WeatherModel | None' = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        grid_probs: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        return_orders: bool = False,
+        allow_single_compound: bool = False,
+    ) -> 'WeatherResult':
+        """Weather scenarios (include/mcgp.h: mcgp_run_weather): the race under each scenario of `changes`, {name:
+        [TrackChange, ...]}, and `strategies`, {name: [PitPlan, ...]} or None; a scenario holds the changes and the plans
+        given under its name, and the scenario names are the union of the two dicts in the order given (changes first; at
+        most 64; the first is the one `compare` measures against).  On the laps a TrackChange covers the track has that
+        condition instead of `track_condition`: a red flag's tyre change and the model's pit rule pick their compound
+        for it, a car under the rule also stops as soon as it is on the wrong class of tyres (dry tyres on a damp or wet
+        track, INTERMEDIATE or WET on a dry one; not in the last five laps), and every car's base pace carries
+        `model`'s seconds for its compound under the lap's condition (WeatherModel(): the project's default table).
+        A planned driver stops only where its plan says: "stays out" is a plan without a stop on that lap.  From the
+        grid a change may name laps 2..L (lap 1 has `track_condition`); from a state, the laps after the state's.
+        Overlapping changes in one scenario, an unknown condition and a lap outside those raise ValueError.  The
+        two-compound check on plans applies only to a scenario whose track is dry on every lap.  Everything else -- the
+        remaining arguments, the plans' other checks, the simulation ids and draws, the seed rules and the device
+        sharding -- is run_strategies': a scenario without changes in which nobody is on the wrong tyres gives, under a
+        model that is zero there, exactly its counts.  last_histogram: [S, n, n]."""
+        model = model if model is not None else WeatherModel()
+        L = int(self.config.total_laps)
+        first_run = 1 if state is None else int(state.lap) + 1
+        changes = {str(k): list(v) for k, v in changes.items()}
+
+        def all_dry(name):
+            cond = [str(track_condition)] * (L + 1)
+            for ch in changes.get(name, []):
+                for lap in range(max(int(ch.first_lap), 0), min(int(ch.last_lap), L) + 1):
+                    cond[lap] = str(ch.condition)
+            return all(c == 'dry' for c in cond[first_run:])
+
+        return self._run_scenarios(
+            'mcgp_run_weather', WeatherResult, 'changes / strategies', n_simulations, [self._change_kind(changes, state)],
+            strategies, (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed,
+            sim_offset, drivers, return_orders, allow_single_compound, call_wide=(C.byref(model.c_struct()),),
+            all_dry=all_dry)
 
     def run_gaps(
         self,
@@ -2531,6 +2610,92 @@ class PaceResult(StrategyResult):
             raise KeyError(f'{driver!r} has no until-stop offset in scenario {key[0]!r}')
         c = int(lap) - self.until_from[key] + 1
         return float(self.carried_distribution(name, driver)[:max(c + 1, 0)].sum()) if c >= 1 else 0.0
+
+
+# ---------------------------------------------------------------------------------------------- weather scenarios
+# The project's own assumption, not the reference's (which has no lap-time cost for the wrong tyres): seconds a lap.
+# Slicks lose more the wetter the track and the harder the compound; wet-weather tyres overheat on a dry track; WET on a
+# merely damp track and INTERMEDIATE on a fully wet one lose a little to the right tyre.
+DEFAULT_WRONG_TYRE_SECONDS = {
+    'dry': {'SOFT': 0.0, 'MEDIUM': 0.0, 'HARD': 0.0, 'INTERMEDIATE': 3.0, 'WET': 6.0},
+    'damp': {'SOFT': 4.0, 'MEDIUM': 5.0, 'HARD': 6.0, 'INTERMEDIATE': 0.0, 'WET': 1.5},
+    'wet': {'SOFT': 12.0, 'MEDIUM': 14.0, 'HARD': 16.0, 'INTERMEDIATE': 2.0, 'WET': 0.0},
+}
+
+
+@dataclass
+class TrackChange:
+    """One change of the track condition in a scenario of RaceSimulator.run_weather: laps first_lap..last_lap have
+    `condition` ('dry', 'damp' or 'wet') instead of the race's track_condition."""
+    first_lap: int
+    last_lap: int
+    condition: str
+
+    def c_struct(self, first_lap=2, total_laps=None) -> N.McgpTrackChange:
+        """mcgp_track_change; ValueError on an unknown condition, first_lap > last_lap, or a lap outside [first_lap,
+        total_laps]."""
+        if self.condition not in N.TRACK_ID:
+            raise ValueError(f"condition must be 'dry', 'damp' or 'wet', got {self.condition!r}")
+        a, b = int(self.first_lap), int(self.last_lap)
+        if a > b:
+            raise ValueError(f'{self.condition}@{a}-{b}: first_lap must not be above last_lap')
+        hi = b if total_laps is None else int(total_laps)
+        if a < int(first_lap) or b > hi:
+            raise ValueError(f'{self.condition}@{a}' + (f'-{b}' if b != a else '') +
+                             f': laps must be in [{int(first_lap)}, {hi}]' +
+                             (" (lap 1 has the configuration's condition)" if int(first_lap) == 2
+                              else " (after the state's lap)"))
+        c = N.McgpTrackChange()
+        c.first_lap, c.last_lap, c.condition = a, b, N.TRACK_ID[self.condition]
+        return c
+
+
+@dataclass
+class WeatherModel:
+    """The seconds a lap a car loses on a compound under a track condition, for RaceSimulator.run_weather:
+    wrong_tyre_seconds = {condition: {compound: seconds}} (finite, in [0, 60]; a cell left out is 0.0).  None: the
+    project's default table, DEFAULT_WRONG_TYRE_SECONDS -- an assumption of this project, not a figure of the reference
+    model, which has no such cost.  The table is read whether or not the class is wrong."""
+    wrong_tyre_seconds: dict | None = None
+
+    def table(self) -> np.ndarray:
+        """[3][5] seconds by condition and compound id; ValueError on an unknown name or a value out of range."""
+        given = DEFAULT_WRONG_TYRE_SECONDS if self.wrong_tyre_seconds is None else self.wrong_tyre_seconds
+        out = np.zeros((3, 5), np.float64)
+        for cond, row in given.items():
+            if cond not in N.TRACK_ID:
+                raise ValueError(f"wrong_tyre_seconds: condition must be 'dry', 'damp' or 'wet', got {cond!r}")
+            for comp, sec in row.items():
+                if comp not in N.COMPOUND_ID:
+                    raise ValueError(f'wrong_tyre_seconds[{cond!r}]: compound must be one of {list(N.COMPOUNDS)}, got {comp!r}')
+                sec = float(sec)
+                if not math.isfinite(sec) or not 0.0 <= sec <= N.MAX_WRONG_TYRE_SECONDS:
+                    raise ValueError(f'wrong_tyre_seconds[{cond!r}][{comp!r}]: seconds must be finite and in [0, 60]')
+                out[N.TRACK_ID[cond], N.COMPOUND_ID[comp]] = sec
+        return out
+
+    def c_struct(self) -> N.McgpWeatherModel:
+        m = N.McgpWeatherModel()
+        for c, row in enumerate(self.table()):
+            for k, sec in enumerate(row):
+                m.wrong_tyre_sec[c][k] = float(sec)
+        return m
+
+
+@dataclass
+class WeatherResult(StrategyResult):
+    """What RaceSimulator.run_weather returns: StrategyResult's counts and helpers, and
+      wrong_laps  [S][n][L + 1]  [scenario][driver][laps whose lap time was computed with the car on the wrong tyres]:
+                                 the simulations with that many; every row sums to N"""
+    wrong_laps: np.ndarray | None = None
+
+    def wrong_tyre_laps_distribution(self, name, driver) -> np.ndarray:
+        """Probabilities by number of laps on the wrong tyres of `driver` in scenario `name`."""
+        return np.asarray(self.wrong_laps[self._s(name), self._d(driver)], np.float64) / max(self.n_simulations, 1)
+
+    def expected_wrong_tyre_laps(self, name, driver) -> float:
+        p = self.wrong_tyre_laps_distribution(name, driver)
+        return float(p @ np.arange(p.shape[0], dtype=np.float64))
 
 
 # ---------------------------------------------------------------------------------------------- combined scenarios

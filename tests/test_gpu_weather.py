@@ -1,0 +1,103 @@
+"""Weather scenarios on the device (mcgp_run_weather, through the C ABI) against the Python restatement (weather_ref)
+under the generated scenario sets of weather_cases -- the 100 inputs of generic_cases.run_inputs() from the grid at 8
+simulations with sim_offset 3 (n = 1, 2, 3, 19, 31, 32, L from 1 up, DMP, WET, EVT and the red-flag-heavy fuzz cases among
+them) and the 94 of resume_inputs() from a state, into pre-filled buffers: finishing orders, hist, delta and wrong_laps --
+and against the device's own mcgp_run / mcgp_run_from_state for scenario 0, and against itself: a split by sim_offset sums
+to the one call.
+
+The sweeps do not pass empty.  By weather_ref alone, on this project's CPU reference: from the grid a car under the rule
+crossed over (stopped only because it was on the wrong tyres) on 87 of the 100 inputs, a red flag fell on a changed lap on
+33 and a finishing order moved on 89; from a state 69, 26 and 79 of 94.  The floors (weather_cases.GRID_FLOORS,
+STATE_FLOORS) are a little below: 80, 28, 82 and 62, 21, 72."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle_py as O
+import resume_ref as RR
+import weather_cases as WC
+import weather_ref as WR
+from monte_carlo_gp_amd import _native as N
+
+pytestmark = pytest.mark.gpu
+
+KERNEL = 'mcgp::race_weather_kernel'
+FILL = 7
+
+
+def _run(case, table, scen, m, seed, off=0, fill=0, **kw):
+    """mcgp_run_weather under [(changes, plans)] -> dict(hist, delta, wrong_laps, orders), the pre-filled `fill` taken
+    off the accumulated counts."""
+    rc, h, dl, wl, o = WR.run_c(case, [pl for _, pl in scen], [ch for ch, _ in scen], table, m, seed, sim_offset=off,
+                                fill=fill, **kw)
+    assert rc == 0, N.lib().mcgp_last_error().decode()
+    assert N.lib().mcgp_last_kernel_name(0).decode() == KERNEL
+    return dict(hist=h - fill, delta=dl - fill, wrong_laps=wl - fill, orders=o)
+
+
+def _mcgp_run(case, prob, m, seed, off):
+    g = np.ascontiguousarray(O.Problem(case).grid_probs, np.float64)
+    h, o = np.zeros((prob.n, prob.n), np.uint64), np.zeros((m, prob.n), np.uint8)
+    N.check(N.lib().mcgp_run(C.byref(prob.cfg), C.byref(prob.drv), g.ctypes.data_as(C.POINTER(C.c_double)), prob.n, m,
+                             off, seed, 0, h.ctypes.data_as(C.POINTER(C.c_uint64)), o.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return h.astype(np.int64), o
+
+
+@pytest.mark.parametrize('part', range(WC.GRID_PARTS))
+def test_device_on_every_input_from_the_grid(require_gpu, part):
+    m, off = WC.FUZZ_SIMS, WC.FUZZ_OFFSET
+    for name, case, seed, calls in WC.grid_wanted(part)[0]:
+        prob = RR.problem(case)
+        for table, scen, want_o, want_w in calls:
+            got = _run(case, table, scen, m, seed, off, fill=FILL, prob=prob)
+            WC.check_against(got, case, want_o, want_w, m)
+            assert (got['wrong_laps'].sum(axis=2) == m).all(), name
+        # scenario 0 of the zero-table call is mcgp_run's race
+        hist, orders = _mcgp_run(case, prob, m, seed, off)
+        got = _run(case, None, calls[0][1][:1], m, seed, off, prob=prob)
+        assert np.array_equal(got['orders'][0], orders) and np.array_equal(got['hist'][0], hist), name
+        assert (got['wrong_laps'][0, :, 0] == m).all(), name
+
+
+@pytest.mark.parametrize('part', range(WC.STATE_PARTS))
+def test_device_on_every_input_from_a_state(require_gpu, part):
+    m = WC.FUZZ_SIMS
+    for name, case, seed, state, calls in WC.state_wanted(part)[0]:
+        prob = RR.problem(case)
+        for table, scen, want_o, want_w in calls:
+            got = _run(case, table, scen, m, seed, 0, fill=FILL, state=state, prob=prob)
+            WC.check_against(got, case, want_o, want_w, m)
+            assert (got['wrong_laps'].sum(axis=2) == m).all(), name
+        # scenario 0 of the zero-table call is mcgp_run_from_state's race
+        rc, hist, orders = RR.run_c(prob, [state], m, [0], seed)
+        assert rc == 0, N.lib().mcgp_last_error().decode()
+        got = _run(case, None, calls[0][1][:1], m, seed, 0, state=state, prob=prob)
+        assert np.array_equal(got['orders'][0], orders[0]) and np.array_equal(got['hist'][0], hist[0].astype(np.int64)), name
+
+
+def test_the_sweeps_do_not_pass_empty(require_gpu):
+    WC.check_floors(WC.grid_marks(), WC.GRID_FLOORS)
+    WC.check_floors(WC.state_marks(), WC.STATE_FLOORS)
+
+
+def test_a_split_by_sim_offset_sums_to_one_call(require_gpu):
+    case = O.load_case('S60')
+    L, n = case['config']['total_laps'], len(case['grid_probs'])
+    scen = [([], {}), ([(L // 2, L, WR.DAMP)], {0: (-1, 0, [(L // 2, WR.INTER)]), n - 1: (-1, 0, [])}),
+            ([(20, 30, WR.WET_TRACK)], {})]
+    m, cut = 1000, 333                                      # neither a multiple of a wave or of a counting block
+    whole = _run(case, WC.FULL_TABLE, scen, m, 11, 5)
+    a = _run(case, WC.FULL_TABLE, scen, cut, 11, 5)
+    b = _run(case, WC.FULL_TABLE, scen, m - cut, 11, 5 + cut)
+    for k in ('hist', 'delta', 'wrong_laps'):
+        assert np.array_equal(a[k] + b[k], whole[k]), k
+    assert np.array_equal(np.concatenate([a['orders'], b['orders']], axis=1), whole['orders'])
+    # the counts are those of the returned orders, and the rain bites
+    assert np.array_equal(whole['hist'], WR.hist_counts(whole['orders'], n))
+    assert (whole['wrong_laps'].sum(axis=2) == m).all() and whole['wrong_laps'][1, n - 1, 1:].sum() > m // 2
+    assert not np.array_equal(whole['orders'][1], whole['orders'][0])
+    # without the optional outputs the histogram is the same
+    rc, h, _, _, _ = WR.run_c(case, [pl for _, pl in scen], [ch for ch, _ in scen], WC.FULL_TABLE, m, 11, 5, orders=False,
+                              delta=False, wrong_laps=False)
+    assert rc == 0 and np.array_equal(h, whole['hist'])

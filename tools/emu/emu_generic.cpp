@@ -1,10 +1,11 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
 // fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
 // gaps.hip.h, conditions.hip.h, stints.hip.h, moves.hip.h, fastest.hip.h and scenario.hip.h (with strategy.hip.h,
-// penalties.hip.h, events.hip.h and paces.hip.h) with g++ through the stand-in <hip/hip_runtime.h> of this directory and
+// penalties.hip.h, events.hip.h, paces.hip.h and weather.hip.h) with g++ through the stand-in <hip/hip_runtime.h> of this directory and
 // calls the real __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_gaps_kernel<false / true>,
 // race_conditions_kernel<false / true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false /
-// true>, race_fastest_kernel, the ten instantiations of race_scenario_kernel, penalties_count, events_count, paces_count.
+// true>, race_fastest_kernel, the twelve instantiations of race_scenario_kernel, penalties_count, events_count, paces_count,
+// weather_count.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -18,16 +19,16 @@
 // threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
 // records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
 // operation and strides by its block's size, so it does run here, as blocks of one thread; so do penalties_count, events_count
-// and paces_count.
+// paces_count and weather_count.
 //
 // Shared text: the five analysis calls (emu_generic_trace, emu_gaps_run, emu_conditions_run, emu_stints_run,
-// emu_moves_run) start with analysis_setup, the five scenario calls are scenario_run with their rule sets.
+// emu_moves_run) start with analysis_setup, the six scenario calls are scenario_run with their rule sets.
 //
 // Used by tests/test_generic_host_build.py (race, resume, trace, strategies) and by tests/test_<call>_host_build.py for
-// gaps, conditions, stints, moves, fastest, penalties, events, paces and combined, each through its helper
+// gaps, conditions, stints, moves, fastest, penalties, events, paces, combined and weather, each through its helper
 // tests/<call>_host_build.py (tests/kernel_host_build.py compiles this file); the stand-alone programs
-// tools/emu/sanitize_{penalties,events,paces,combined,bonus}_main.cpp are built with it for
-// tests/test_{penalties,events,paces,combined,fastest}_sanitize.py.
+// tools/emu/sanitize_{penalties,events,paces,combined,bonus,weather}_main.cpp are built with it for
+// tests/test_{penalties,events,paces,combined,fastest,weather}_sanitize.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -44,6 +45,7 @@
 #include "../../monte_carlo_gp_amd/csrc/penalty_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/event_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/pace_pack.h"
+#include "../../monte_carlo_gp_amd/csrc/weather_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/scenario.hip.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -116,13 +118,24 @@ int analysis_setup(const mcgp_config *cfg, const mcgp_drivers *drv, const double
 // delta [S][n][2n - 1], fate [S][n][4], events_cnt [S][3][L + 1] (needs ev_stage) and carried [S][n][L + 1] (needs
 // car_stage), each of which may be NULL, are accumulated into: delta by penalties_count where the call has penalties,
 // else by the counting kernel of its one rule set; the centre bin and the columns 0 stay what they were, as on the device.
+// The weather call (rules = kRuleWeather) hands its own inputs in `wx`: they are checked and packed by weather_pack.h into
+// the condition bytes and the table, which the kernel reads through its event_laps and lap_sec arguments; car_stage
+// gets the laps on the wrong tyres, and weather_count (grid_x x S x n blocks) adds them to `wrong` [S][n][L + 1].
+struct WeatherArgs {
+    const uint32_t *change_count;
+    const mcgp_track_change *changes;
+    const mcgp_weather_model *model;
+    unsigned long long *wrong;
+};
+
 int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
                  const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
                  const mcgp_pit_plan *plans, const uint32_t *penalty_count, const mcgp_time_penalty *penalties,
                  const uint32_t *event_count, const mcgp_lap_event *events, const uint32_t *pace_count,
                  const mcgp_pace_offset *paces, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist,
                  uint8_t *stage, uint32_t *ev_stage, uint16_t *car_stage, unsigned long long *delta, unsigned long long *fate,
-                 unsigned long long *events_cnt, unsigned long long *carried, uint32_t grid_x, const char **err)
+                 unsigned long long *events_cnt, unsigned long long *carried, uint32_t grid_x, const char **err,
+                 const WeatherArgs *wx = nullptr)
 {
     const bool pen = rules & mcgp::kRulePenalties, ev = rules & mcgp::kRuleEvents, pace = rules & mcgp::kRulePaces;
     static mcgp::KParams kp;
@@ -134,7 +147,8 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     // (the events call always stages the event word: its kernel does not test the pointer.  The check is new for
     // emu_events_run, whose old body had none)
     if ((events_cnt || rules == mcgp::kRuleEvents) && !ev_stage) return fail(MCGP_E_BAD_ARG, "events need ev_stage", err);
-    if (carried && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
+    if ((carried || (wx && wx->wrong)) && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
+    if ((rules == mcgp::kRuleWeather) != (wx != nullptr)) return fail(MCGP_E_BAD_ARG, "weather needs its inputs", err);
     const int L = cfg->total_laps;
     mcgp::ResumeState st;
     std::memset(&st, 0, sizeof(st));
@@ -153,7 +167,7 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     std::vector<mcgp::PaceScenario> pscen;
     std::vector<mcgp::PaceLap> pace_laps;
     std::vector<double> lap_sec;
-    uint64_t n_pens = 0, n_events = 0, n_paces = 0;
+    uint64_t n_pens = 0, n_events = 0, n_paces = 0, n_changes = 0;
     std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, resumed, &scen, &stop_laps);
     if (e.empty() && pen) e = mcgp::check_penalty_counts(n_scenarios, penalty_count, &n_pens);
     if (e.empty() && ev) e = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
@@ -166,14 +180,20 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     if (e.empty() && ev) e = mcgp::pack_events(n_scenarios, event_count, events, L, first_lap, resumed, &event_laps);
     if (e.empty() && pace)      // lap 1 reads the base pace too: from the grid an offset may name it
         e = mcgp::pack_paces(n_scenarios, pace_count, paces, n, L, state ? first_lap : 1, resumed, &pscen, &pace_laps, &lap_sec);
+    if (e.empty() && wx && !wx->change_count) e = "change_count is NULL";
+    if (e.empty() && wx) e = mcgp::check_change_counts(n_scenarios, wx->change_count, &n_changes);
+    if (e.empty() && n_changes && !wx->changes) e = "changes is NULL";
+    if (e.empty() && wx)
+        e = mcgp::pack_weather(n_scenarios, wx->change_count, wx->changes, wx->model, cfg->track_condition, L, first_lap,
+                               resumed, &event_laps, &lap_sec);
     if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
     const auto kernel = mcgp::scenario_kernel(rules, resumed);
     one_thread_block(n_scenarios);
     for (uint32_t si = 0; si < n_scenarios; ++si) {
         blockIdx.y = si;
         kernel(&kp, &st, scen.data(), stop_laps.data(), pen ? pens.data() : nullptr, pen ? pen_laps.data() : nullptr,
-               ev ? event_laps.data() : nullptr, pace ? pscen.data() : nullptr, pace ? pace_laps.data() : nullptr,
-               pace ? lap_sec.data() : nullptr, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
+               ev || wx ? event_laps.data() : nullptr, pace ? pscen.data() : nullptr, pace ? pace_laps.data() : nullptr,
+               pace || wx ? lap_sec.data() : nullptr, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
                ev_stage, car_stage, (uint32_t)n_sims);
     }
     unsigned long long *ev_delta = pen ? nullptr : delta, *pace_delta = pen ? nullptr : delta;
@@ -192,6 +212,15 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
                 if (pace && (pace_delta || carried))
                     mcgp::paces_count(stage, car_stage, pscen.data(), n_sims, n, (uint32_t)L, pace_delta, carried);
             }
+    if (wx && wx->wrong) {
+        gridDim = {grid_x, n_scenarios, n};
+        for (uint32_t z = 0; z < n; ++z)
+            for (uint32_t y = 0; y < n_scenarios; ++y)
+                for (uint32_t x = 0; x < grid_x; ++x) {
+                    blockIdx = {x, y, z};
+                    mcgp::weather_count(car_stage, n_sims, n, (uint32_t)L, wx->wrong);
+                }
+    }
     one_thread_block(1);
     return MCGP_OK;
 }
@@ -356,9 +385,10 @@ int emu_fastest_run(const mcgp_config *cfg, const mcgp_drivers *drv, const doubl
     return MCGP_OK;
 }
 
-// The five scenario calls (scenario_run above).  stage [S][n_sims][n] holds each driver's classified position, with
+// The six scenario calls (scenario_run above).  stage [S][n_sims][n] holds each driver's classified position, with
 // penalties | fate << 5; ev_stage the packed event counts (red | sc << 10 | vsc << 20); car_stage the laps carried at the
-// drivers with an UNTIL_STOP offset.  emu_combined_run takes a NULL count array as none in any scenario.
+// drivers with an UNTIL_STOP offset (emu_weather_run: every driver's laps on the wrong tyres, or NULL: not staged).
+// emu_combined_run takes a NULL count array as none in any scenario.
 int emu_generic_strategy(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
                          const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
                          const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
@@ -415,6 +445,18 @@ int emu_combined_run(const mcgp_config *cfg, const mcgp_drivers *drv, const doub
                         penalty_count ? penalty_count : none, penalties, event_count ? event_count : none, events,
                         pace_count ? pace_count : none, paces, n_sims, sim_offset, seed, hist, stage, ev_stage, car_stage, delta,
                         fate, events_cnt, carried, grid_x, err);
+}
+
+int emu_weather_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                    uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                    const uint32_t *change_count, const mcgp_track_change *changes, const mcgp_weather_model *model,
+                    uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *stage,
+                    uint16_t *car_stage, unsigned long long *wrong, uint32_t grid_x, const char **err)
+{
+    const WeatherArgs wx = {change_count, changes, model, wrong};
+    return scenario_run(mcgp::kRuleWeather, cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, n_sims, sim_offset, seed, hist, stage, nullptr, car_stage, nullptr,
+                        nullptr, nullptr, nullptr, grid_x, err, &wx);
 }
 
 }  // extern "C"
