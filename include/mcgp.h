@@ -36,7 +36,7 @@ extern "C" {
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
  * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too; and
  * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties; mcgp_lap_event and mcgp_run_events;
- * mcgp_run_championship_live; mcgp_pace_offset and mcgp_run_paces */
+ * mcgp_run_championship_live; mcgp_pace_offset and mcgp_run_paces; mcgp_grid_edit and mcgp_run_grids */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -783,6 +783,73 @@ int32_t mcgp_run_weather(const mcgp_config *cfg, const mcgp_drivers *drv, const 
                          const mcgp_weather_model *model, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
                          int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *wrong_laps_out,
                          uint8_t *orders_out);
+
+/* A grid edit: in a scenario of mcgp_run_grids, `driver` (row index of grid_probs) is moved on the grid that the
+ * simulation draws. */
+enum { MCGP_GRID_DROP = 0, MCGP_GRID_PIN = 1, MCGP_GRID_PIT_LANE = 2 };
+typedef struct mcgp_grid_edit {
+    int32_t driver;   /* [0, n) */
+    int32_t kind;     /* MCGP_GRID_DROP .. MCGP_GRID_PIT_LANE */
+    int32_t value;    /* DROP: places, in [1, 255]; PIN: the slot, in [1, n]; PIT_LANE: 0 */
+    double seconds;   /* PIT_LANE: seconds added to lap 1, finite, in [0, 1e6]; DROP and PIN: 0 */
+} mcgp_grid_edit;
+
+/* Grid scenarios: one race under n_scenarios sets of planned pit stops AND grid edits ("what does a new power unit
+ * cost VER?  A pit-lane start?  NOR and VER have the front row, the rest is a forecast"), with common random numbers.
+ * Scenario s holds plan_count[s] plans (concatenated in `plans`; exactly mcgp_run_strategies' plans from the grid, with
+ * its checks; `plans` may be NULL when every count is 0) and edit_count[s] edits (concatenated in `edits`, which may be
+ * NULL when every count is 0), at most one per driver.  There is no state argument: a mid-race state has no grid.
+ * Per simulation, with s_d the slot (0-based) that mcgp_run's simulation of the same id draws for driver d, the slots
+ * are assigned in this order:
+ *   1. the PIT_LANE drivers take the last slots, ordered among themselves by s_d;
+ *   2. the PIN drivers take their slots.  Two pins of one scenario may not name one slot, and a pin must lie in front of
+ *      the pit-lane slots;
+ *   3. every other driver is sorted by (s_d + drop_d, s_d), drop_d = 0 without an edit, and they fill the free slots front
+ *      to back.  With drops alone this is the reference's apply_grid_penalties (src/predictor.py:69-97) per simulation:
+ *      a dropped driver whose key ties with a driver drawn on that slot stays in front of it, so a one-place drop moves
+ *      nobody; a drop of n - 1 places or more is the back of the grid (for the driver drawn on pole with exactly n - 1,
+ *      in front of the car drawn last).
+ * The cars are then set up by the new slot: the start compound and age follow it (SOFT at age 4 on slots 1-10 of a dry
+ * race, and so on), a plan's start tyres are applied after that, the new slot is the car's grid slot in every tie of
+ * times, and lap 1's position factor and top-three clip use it.  A pit-lane car that does not retire on lap 1 gets one
+ * more binary64 addition, cum = (0.0 + lap_time) + seconds, before lap 1's sort.
+ * Random numbers: nothing new is drawn and no draw moves.  The grid words are drawn exactly as mcgp_run draws them; lap
+ * 1's words are keyed by driver and follow the driver.
+ * Identities: a scenario without edits is mcgp_run_strategies' scenario cell for cell, an empty scenario mcgp_run's race;
+ * a scenario that pins all n drivers gives, for simulation i, what mcgp_simulate_race gives with that grid and
+ * sim_id = sim_offset + i.
+ *   hist_out   [S][n][n]      [scenario][driver][position - 1]
+ *   delta_out  [S][n][2n - 1] as mcgp_run_strategies': paired position changes against scenario 0; or NULL
+ *   start_out  [S][n][n]      [scenario][driver][start slot after the edits]; every row and every column sums to n_sims;
+ *                             or NULL
+ *   gain_out   [S][n][2n - 1] [scenario][driver][(start slot - classified position) + n - 1]: above the centre, places
+ *                             gained from the edited grid; every row sums to n_sims; or NULL
+ *   orders_out [S][n_sims][n] driver index classified p-th, or NULL
+ * hist_out, delta_out, start_out and gain_out are ACCUMULATED into, orders_out is written, and all only after every launch
+ * has succeeded: on an error they are left as they were.  Every argument is checked before any device lookup: what
+ * mcgp_run_strategies checks from the grid (n_scenarios, plans, grid_probs, deviates other than MCGP_DEVIATES_32, NULLs),
+ * edit_count NULL or above n, `edits` NULL with a non-zero count, a driver outside [0, n), a kind outside the enum, a
+ * value outside its range, seconds that are not finite or outside [0, 1e6], non-zero seconds on DROP or PIN, two edits of
+ * one driver, two pins on one slot and a pin inside the pit-lane slots are MCGP_E_BAD_ARG with a message that names the
+ * scenario, the edit and the field.  n_sims == 0 succeeds without a device.  The device work goes chunk by chunk through
+ * mcgp_run_strategies' staging budget (one byte per scenario, simulation and driver, and a u16 more when start_out or
+ * gain_out is wanted); device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or devices
+ * sums to the same counts.  mcgp_last_kernel_name afterwards is "mcgp::race_grids_kernel".  Added entry point only:
+ * MCGP_ABI_VERSION stays 6 and a caller tests for the symbol.
+ * Not in this call: grid edits from a mid-race state or inside mcgp_run_combined; MCGP_DEVIATES_53; the register
+ * kernels; a pit-lane start with a free first-lap tyre rule beyond what a plan gives.
+ * Price (one MI355X, S60, two scenarios x 10^6 simulations, device ms per 10^6, medians of five with max - min;
+ * profiles/grid_time.txt): mcgp_run_strategies built from the parent commit, two empty scenarios, 97.65 (0.20);
+ * mcgp_run_grids, two empty scenarios, 98.20 (0.15), 0.6 % more: the edit step is skipped by one wave-uniform test, but the
+ * instantiation is another kernel (its table, lap 1's pit-lane test, its own register allocation), and 0.55 ms is outside the
+ * parent's spread; an empty scenario and a ten-place drop of one driver, 98.27 (0.51); an empty scenario and a pit-lane
+ * start with start_out and gain_out wanted, 99.31 (0.49), 1.7 % more: the u16 staging and grid_count.  The six other
+ * scenario calls compile to the parent's code. */
+int32_t mcgp_run_grids(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
+                       uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                       const uint32_t *edit_count, const mcgp_grid_edit *edits, uint64_t n_sims, uint64_t sim_offset,
+                       uint64_t seed, int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *start_out,
+                       uint64_t *gain_out, uint8_t *orders_out);
 
 /* Race time gaps: the model's binary64 cumulative times, counted on the device as histograms over caller-given edges
  * (seconds): every car's gap to the leader by lap, the lead (winning margin on the last lap) and the gap between named

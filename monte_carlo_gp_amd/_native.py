@@ -120,6 +120,16 @@ MAX_WRONG_TYRE_SECONDS = 60.0
 TRACKS = ('dry', 'damp', 'wet')                    # MCGP_DRY .. MCGP_WET_TRACK, by id
 
 
+GRID_DROP, GRID_PIN, GRID_PIT_LANE = 0, 1, 2       # include/mcgp.h: MCGP_GRID_DROP .. MCGP_GRID_PIT_LANE
+MAX_GRID_DROP = 255
+MAX_PIT_LANE_SECONDS = 1e6
+
+
+class McgpGridEdit(C.Structure):
+    """mcgp_grid_edit: one driver's drop, pin or pit-lane start in a scenario of mcgp_run_grids."""
+    _fields_ = [('driver', C.c_int32), ('kind', C.c_int32), ('value', C.c_int32), ('seconds', C.c_double)]
+
+
 class McgpTrackChange(C.Structure):
     """mcgp_track_change: the track condition of laps first_lap..last_lap in a scenario of mcgp_run_weather."""
     _fields_ = [('first_lap', C.c_int32), ('last_lap', C.c_int32), ('condition', C.c_int32)]
@@ -313,7 +323,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
            'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
            'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live', 'mcgp_run_paces',
-           'mcgp_run_combined', 'mcgp_run_weather')
+           'mcgp_run_combined', 'mcgp_run_weather', 'mcgp_run_grids')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -476,6 +486,14 @@ def lib():
                                            C.POINTER(C.c_uint32), C.POINTER(McgpTrackChange),
                                            C.POINTER(McgpWeatherModel), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32,
                                            u64p, u64p, u64p, C.POINTER(C.c_uint8)]
+        if 'mcgp_run_grids' not in missing:
+            # no state; the plans, (count, edits); hist, delta, start, gain, orders
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_grids.restype = C.c_int32
+            L.mcgp_run_grids.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.c_uint32, C.c_uint32,
+                                         C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan), C.POINTER(C.c_uint32),
+                                         C.POINTER(McgpGridEdit), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32,
+                                         u64p, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES

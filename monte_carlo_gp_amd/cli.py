@@ -19,6 +19,8 @@
         --event 'sc=sc@31' --plan 'sc=:31/HARD' --give 'sc=NOR:5' --offset 'sc=VER:0.4@31+'
     python -m monte_carlo_gp_amd.cli weather --race Bahrain --season 2024 --offline --driver NOR --change 'rain=damp@30-45' \
         --plan 'rain=:30/INTERMEDIATE,46/MEDIUM' [--state lap29.json] [--wrong-tyre dry:INTERMEDIATE=3.0]
+    python -m monte_carlo_gp_amd.cli grid --race Bahrain --season 2024 --offline --driver VER --drop 'new engine=VER:engine' \
+        --pit-lane 'pit lane=VER:2.5' --plan 'pit lane=VER:HARD@0:30/MEDIUM' --pin 'front row=NOR:1' --pin 'front row=VER:2'
 
 Flags kept from the reference: --season, --race, --prediction-point, --simulations (main.py:8-16);
 --seasons, --seed (backtest.py:9-14).  Unlike the reference, --simulations and --seed reach the
@@ -65,6 +67,11 @@ change lap stays out) and compares the scenarios with `as forecast` (no change, 
 expected-position change against the first scenario and the expected laps on the wrong class of tyres.  Cars without a
 plan cross over by the model's rule.  --wrong-tyre CONDITION:COMPOUND=SECONDS replaces a cell of the project's default
 table of seconds lost per lap.
+grid edits the starting grid that every simulation draws (--drop NAME=DRIVER:PLACES, PLACES a number, a reference
+penalty name such as engine, or back; --pin NAME=DRIVER:SLOT; --pit-lane NAME=DRIVER[:SECONDS], the seconds lost on lap 1,
+by default the project's own assumption; several per NAME make one scenario; a --plan NAME=DRIVER:START[@AGE]:LAP/COMP,...
+joins the scenario of that NAME) and compares the scenarios with `forecast grid` (no edit, no plan): for --driver the win,
+podium and expected-position change against the first scenario, the expected start slot and the places gained from it.
 Under torch.distributed.run the backtest shards RACES over ranks (independent problems, no collective
 on the data path; results are gathered once).
 """
@@ -796,6 +803,158 @@ def cmd_weather(args) -> int:
         with open(args.json, 'w') as f:
             json.dump({'baseline': base, 'n_simulations': res.n_simulations,
                        'wrong_tyre_seconds': [[float(x) for x in r] for r in model.table()], 'scenarios': rows}, f)
+    return 0
+
+
+GRID_BASELINE = 'forecast grid'
+
+
+def _named_driver(flag, text, usage):
+    """NAME=DRIVER[:REST] -> (NAME, DRIVER, REST or None)."""
+    name, sep, rest = text.partition('=')
+    driver, colon, what = rest.partition(':')
+    if not sep or not name.strip() or not driver.strip():
+        raise ValueError(f'{flag} {text!r}: expected {usage}')
+    return name.strip(), driver.strip(), what.strip() if colon else None
+
+
+def parse_drop(text: str):
+    """--drop NAME=DRIVER:PLACES -> (NAME, GridEdit); PLACES a number of places, a PENALTY_TYPES name or 'back'."""
+    from .simulation import GridEdit
+    name, driver, places = _named_driver('--drop', text, 'NAME=DRIVER:PLACES')
+    if not places:
+        raise ValueError(f'--drop {text!r}: expected NAME=DRIVER:PLACES')
+    if places.lower() == 'back':
+        return name, GridEdit.back(driver)
+    if places.isdigit():
+        if not 1 <= int(places) <= 255:
+            raise ValueError(f'--drop {text!r}: PLACES is in [1, 255]')
+        return name, GridEdit.drop(driver, int(places))
+    try:
+        return name, GridEdit.drop(driver, places.lower())
+    except ValueError:
+        from .predictor import PENALTY_TYPES
+        raise ValueError(f"--drop {text!r}: PLACES is a number, 'back' or one of {sorted(PENALTY_TYPES)}, "
+                         f'got {places!r}') from None
+
+
+def parse_pin(text: str):
+    """--pin NAME=DRIVER:SLOT -> (NAME, GridEdit); SLOT is 1-based."""
+    from .simulation import GridEdit
+    name, driver, slot = _named_driver('--pin', text, 'NAME=DRIVER:SLOT')
+    if not slot or not slot.isdigit() or int(slot) < 1:
+        raise ValueError(f'--pin {text!r}: SLOT is a grid slot, 1 or more')
+    return name, GridEdit.pin(driver, int(slot))
+
+
+def parse_pit_lane(text: str):
+    """--pit-lane NAME=DRIVER[:SECONDS] -> (NAME, GridEdit); SECONDS left out: the project's default."""
+    from .simulation import GridEdit
+    name, driver, seconds = _named_driver('--pit-lane', text, 'NAME=DRIVER[:SECONDS]')
+    if seconds is None:
+        return name, GridEdit.pit_lane(driver)
+    try:
+        sec = float(seconds)
+    except ValueError:
+        raise ValueError(f'--pit-lane {text!r}: SECONDS is a number, got {seconds!r}') from None
+    if not (0.0 <= sec <= 1e6):
+        raise ValueError(f'--pit-lane {text!r}: SECONDS is in [0, 1e6]')
+    return name, GridEdit.pit_lane(driver, sec)
+
+
+def parse_grid_plan(text: str):
+    """--plan NAME=DRIVER:START[@AGE]:LAP/COMP,LAP/COMP -> (NAME, PitPlan): the strategy command's plan behind the
+    driver's name, with the age of the start tyres after '@' (a pit-lane starter's free choice)."""
+    usage = 'NAME=DRIVER:START[@AGE]:LAP/COMP,... (START may be empty)'
+    name, driver, rest = _named_driver('--plan', text, usage)
+    if rest is None or ':' not in rest:
+        raise ValueError(f'--plan {text!r}: expected {usage}')
+    start, _, stops = rest.partition(':')
+    start, at, age = start.partition('@')
+    if at and (not start.strip() or not age.strip().isdigit()):
+        raise ValueError(f'--plan {text!r}: START@AGE needs a compound and a number of laps')
+    _, plan = parse_plan(f'{name}={start}:{stops}', driver)
+    if at:
+        plan.start_age = int(age)
+    return name, plan
+
+
+def grid_scenarios(drops=(), pins=(), pit_lanes=(), plans=()):
+    """The grid command's scenarios -> (edits, strategies): 'forecast grid' (no edit, no plan) first, unless the user names
+    a scenario 'forecast grid' themselves; then one scenario per NAME in the order --drop, --pin, --pit-lane, --plan,
+    holding every edit of that NAME and the --plan items of that NAME (one per driver)."""
+    if not (drops or pins or pit_lanes):
+        raise ValueError('give at least one --drop NAME=DRIVER:PLACES, --pin NAME=DRIVER:SLOT or --pit-lane '
+                         'NAME=DRIVER[:SECONDS]')
+    out, strategies = {GRID_BASELINE: []}, {}
+    for flag, parse, items in (('--drop', parse_drop, drops), ('--pin', parse_pin, pins),
+                               ('--pit-lane', parse_pit_lane, pit_lanes)):
+        for text in items or ():
+            name, ed = parse(text)
+            if any(e.driver == ed.driver for e in out.get(name, [])):
+                raise ValueError(f'{flag} {text!r}: {ed.driver} has an edit in scenario {name!r} already')
+            out.setdefault(name, []).append(ed)
+    for text in plans or ():
+        name, plan = parse_grid_plan(text)
+        if any(p.driver == plan.driver for p in strategies.get(name, [])):
+            raise ValueError(f'--plan {text!r}: {plan.driver} has a plan in scenario {name!r} already')
+        out.setdefault(name, [])
+        strategies.setdefault(name, []).append(plan)
+    return out, strategies
+
+
+def cmd_grid(args) -> int:
+    fixture = synthetic_fixture()
+    if args.fixture:
+        with open(args.fixture) as f:
+            fixture = json.load(f)
+    elif not args.offline:
+        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+        return 2
+    try:
+        edits, strategies = grid_scenarios(args.drop, args.pin, args.pit_lane, args.plan)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    print(f"\n{'=' * 60}\nF1 Grid Scenarios: {args.season} {args.race}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}")
+    print('=' * 60 + '\n')
+    try:
+        res = F1Predictor(device=args.device).predict_grids(args.season, args.race, fixture, edits, strategies,
+                                                            n_simulations=args.simulations, seed=args.seed,
+                                                            allow_single_compound=args.allow_single_compound)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    base = res.names[0]
+    shown = [args.driver] if args.driver else sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
+    rows = []
+    for name in res.names:
+        print(f"scenario: {name}" + (''.join(f'  [{e}]' for e in edits.get(name, []))))
+        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'change':>7} {'P(better)':>10}"
+              f"  gain +- SE   E[start]  places gained")
+        epos, epos0, estart = res.expected_position(name), res.expected_position(base), res.expected_start(name)
+        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
+                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
+                   expected_position=epos, expected_start=estart, drivers={})
+        for d in shown:
+            c = res.compare(name, d)
+            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
+            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
+            gained = res.expected_places_gained(name, d)
+            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
+                                     expected_position_change=epos[d] - epos0[d], p_better=c['p_better'],
+                                     p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'],
+                                     expected_start=estart[d], expected_places_gained=gained)
+            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {epos[d] - epos0[d]:+7.2f} "
+                  f"{c['p_better']:10.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}   {estart[d]:8.2f}  {gained:+.2f}")
+        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
+        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
+        rows.append(row)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
     return 0
 
 
@@ -1614,6 +1773,29 @@ def main(argv=None) -> int:
     t.add_argument('--device', type=int, default=0)
     t.add_argument('--json', type=str, default=None)
     t.set_defaults(fn=cmd_weather)
+    t = sub.add_parser('grid', help='race odds under grid drops, pit-lane starts and pinned grid slots')
+    t.add_argument('--season', type=int, default=2025)
+    t.add_argument('--race', type=str, required=True)
+    t.add_argument('--drop', type=str, action='append', default=[],
+                   help="NAME=DRIVER:PLACES: in scenario NAME the driver drops PLACES on the grid each simulation draws; PLACES "
+                        "is a number, back, or a penalty name (engine, full_pu, gearbox, pitlane_start); repeat for more")
+    t.add_argument('--pin', type=str, action='append', default=[],
+                   help='NAME=DRIVER:SLOT: in scenario NAME the driver starts from SLOT in every simulation')
+    t.add_argument('--pit-lane', type=str, action='append', default=[],
+                   help="NAME=DRIVER[:SECONDS]: in scenario NAME the driver starts from the pit lane, behind the grid, and loses "
+                        "SECONDS on lap 1 (default: the project's assumption)")
+    t.add_argument('--driver', type=str, default=None, help='the driver shown (default: the five likeliest winners)')
+    t.add_argument('--plan', type=str, action='append', default=[],
+                   help="NAME=DRIVER:START[@AGE]:LAP/COMP,LAP/COMP: the strategy command's plan for DRIVER; joins the scenario "
+                        "of that NAME")
+    t.add_argument('--allow-single-compound', action='store_true', help='run plans that use one dry compound')
+    t.add_argument('--simulations', type=int, default=100000)
+    t.add_argument('--seed', type=int, default=None)
+    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
+    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
+    t.add_argument('--device', type=int, default=0)
+    t.add_argument('--json', type=str, default=None)
+    t.set_defaults(fn=cmd_grid)
     t = sub.add_parser('what-if', help='race odds under scenarios that mix pit plans, time penalties, race events and '
                                        'lap-time offsets')
     t.add_argument('--season', type=int, default=2025)

@@ -27,6 +27,7 @@
 #include "pace_pack.h"
 #include "event_pack.h"
 #include "weather_pack.h"
+#include "grid_pack.h"
 #include "scenario.hip.h"
 #include "champ_pack.h"
 
@@ -964,7 +965,9 @@ struct ScenarioChunk {
     const mcgp::PaceLap *pl;
     const double *sec;                      // (with weather: the table of wrong-tyre seconds)
     uint32_t *evs;                          // [S][m] packed event counts
-    uint16_t *car;                          // [S][m][n] laps carried (with weather: laps on the wrong tyres)
+    uint16_t *car;                          // [S][m][n] laps carried (with weather: laps on the wrong tyres; with grid
+                                            // edits: start slots)
+    const mcgp::GridScenario *gr;           // with grid edits: the edit table, which the kernel reads through `pens`
 };
 
 // Grid width of a counting kernel over m simulations in blocks of `block` threads: the tiles, but no more blocks than
@@ -1016,8 +1019,8 @@ struct ScenarioOutput {
     std::function<void(unsigned long long *extra, size_t rows, uint64_t n_sims)> fix_up;
 };
 
-// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces, mcgp_run_combined and mcgp_run_weather
-// each have of their own; run_scenarios has the rest.
+// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces, mcgp_run_combined, mcgp_run_weather and
+// mcgp_run_grids each have of their own; run_scenarios has the rest.
 struct ScenarioKind {
     const char *what;                       // the call in check_deviates_32's message
     // generic_geometry's and note_launch's name of the race kernel.  These are the documented names of the calls
@@ -1126,7 +1129,8 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
         return staged_run(c, reinterpret_cast<KernelFn>(kernel), k.geo_name, k.kernel_name, n, S, n_sims, chunk, ws, counts,
                           [&](uint64_t done, uint64_t m, uint32_t gx, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
             l.gx = gx, l.block = block, l.lds = lds, l.n_batches = n_batches, l.m = m, l.first_sim = sim_offset + done;
-            hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, l.pn, l.nl, l.el,
+            const mcgp::PenaltyScenario *pens = l.gr ? reinterpret_cast<const mcgp::PenaltyScenario *>(l.gr) : l.pn;
+            hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, pens, l.nl, l.el,
                                l.ps, l.pl, l.sec, l.m, l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage,
                                l.evs, l.car, l.n_batches);
             HIP_TRY(hipGetLastError());
@@ -2467,6 +2471,44 @@ int32_t mcgp_run_weather(const mcgp_config *cfg, const mcgp_drivers *drv, const 
     // wrong_laps [S][n][L + 1]; column 0 is, like carried's, what the others leave of n_sims
     k.outputs = {carried_output(wrong_laps_out, cfg)};
     return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
+                         hist_out, delta_out, orders_out, k);
+}
+
+int32_t mcgp_run_grids(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n,
+                       uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                       const uint32_t *edit_count, const mcgp_grid_edit *edits, uint64_t n_sims, uint64_t sim_offset,
+                       uint64_t seed, int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *start_out,
+                       uint64_t *gain_out, uint8_t *orders_out)
+{
+    std::vector<mcgp::GridScenario> grids;
+    ScenarioKind k = {"grids run", "grids", "mcgp::race_grids_kernel", mcgp::kRuleGrid};
+    k.tables = {{"edit_count", "edits", edit_count, edits, [&](uint64_t *n_edits) {
+        return mcgp::check_edit_counts(n_scenarios, edit_count, n, n_edits);
+    }}};
+    k.pack = [&](int, bool) { return mcgp::pack_grids(n_scenarios, edit_count, edits, n, &grids); };
+    // a position byte per driver, and its u16 start slot when the start slots or the gains are counted
+    const bool want_start = start_out || gain_out;
+    k.sim_bytes = want_start ? (size_t)n * 3 : (size_t)n;
+    // the kernel reads the edit table through the argument of a rule set it never meets
+    k.regions = [&](Layout &ws, ScenarioChunk &l, uint64_t chunk) {
+        if (want_start) ws.add(&l.car, (size_t)n_scenarios * chunk * n);
+        ws.add(&l.gr, grids.size(), grids.data());
+    };
+    // the deltas as mcgp_run_strategies counts them (S - 1 grid rows), the start slots and gains one layer per driver
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
+        if (d_delta)
+            hipLaunchKernelGGL(mcgp::strategy_count_deltas,
+                               dim3(count_grid_x(l.m, mcgp::kStrategyCountBlock, grid_cap, l.S - 1), l.S - 1),
+                               dim3(mcgp::kStrategyCountBlock), 0, nullptr, l.stage, l.m, n, d_delta);
+        if (extra[0] || extra[1])
+            hipLaunchKernelGGL(mcgp::grid_count,
+                               dim3(count_grid_x(l.m, mcgp::kGridCountBlock, grid_cap, (uint64_t)l.S * n), l.S, n),
+                               dim3(mcgp::kGridCountBlock), 0, nullptr, l.stage, l.car, l.m, n, extra[0], extra[1]);
+    };
+    // start [S][n][n] and gain [S][n][2n - 1]: every cell is counted, neither needs a fix-up
+    k.outputs = {{start_out, [](size_t S, size_t n, size_t) { return S * n * n; }, nullptr},
+                 {gain_out, [](size_t S, size_t n, size_t) { return S * n * (2 * n - 1); }, nullptr}};
+    return run_scenarios(cfg, drv, grid_probs, nullptr, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
                          hist_out, delta_out, orders_out, k);
 }
 

@@ -216,15 +216,37 @@ struct ModelPace {
     __device__ __forceinline__ double base(uint32_t /*d*/, double b) const { return b; }
 };
 
+// _initialize_cars' tyres of the car on grid slot `pos` (0-based) under track condition `track`, reference :244-273.
+__device__ __forceinline__ void start_tyres(int track, int pos, uint32_t &comp, uint32_t &age)
+{
+    if (track == 2) { comp = 4u; age = 0u; }
+    else if (track == 1) { comp = 3u; age = 0u; }
+    else { comp = pos < 10 ? 0u : 1u; age = pos < 10 ? 4u : 0u; }
+}
+
+// The grid policy of every kernel but race_scenario_kernel with grid edits: the cars start from the slots they drew.
+// Where kEdits is set start_from_grid calls, after the sampling loop (pk holds every driver's drawn slot and its cars, ord
+// the drawn order, cum 0), edit(s, n, track, hook), which may move the drivers to other slots and sets their cars up by
+// the new slot, and, for every car that sets a lap time on lap 1, lap1(d, t) with t = 0.0 + lap_time, and stores what it
+// returns.  ModelGrid has neither: both calls vanish at compile time.  GridEdits (grids.hip.h) is the caller's drops, pins
+// and pit-lane starts.
+struct ModelGrid {
+    static constexpr bool kEdits = false;
+    template <class StartHook>
+    __device__ __forceinline__ void edit(const Rows &, int /*n*/, int /*track*/, StartHook) const {}
+    __device__ __forceinline__ double lap1(uint32_t /*d*/, double t) const { return t; }
+};
+
 // The start of one lane's race: grid (`fixed_grid`, or NULL: sampled from grid_probs), cars, lap 1 and the once-per-race
 // retirement draws.  Leaves the rows after update_positions of lap 1 and every driver's retirement lap (laps >= 2) in
 // `out`.  hook(driver, comp, age) may replace a car's starting tyres after the model has picked them
-// (race_scenario_kernel: PlannedTyres, strategy.hip.h).  `pace` gives lap 1's base pace (ModelPace: the model's).
-template <class StartHook = ModelTyres, class PacePolicy = ModelPace>
+// (race_scenario_kernel: PlannedTyres, strategy.hip.h).  `pace` gives lap 1's base pace (ModelPace: the model's), `grid`
+// may move the drivers on the drawn grid (ModelGrid: never).
+template <class StartHook = ModelTyres, class PacePolicy = ModelPace, class GridPolicy = ModelGrid>
 __device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv &e, uint32_t c0, uint32_t c1,
                                                      uint32_t seed_lo, uint32_t seed_hi,
                                                      const uint8_t *__restrict__ fixed_grid, StartHook hook = StartHook(),
-                                                     PacePolicy pace = PacePolicy())
+                                                     PacePolicy pace = PacePolicy(), GridPolicy grid = GridPolicy())
 {
     const KParams *__restrict__ P = e.P;
     const int n = e.n, L = e.L, track = e.track;
@@ -276,9 +298,7 @@ __device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv
             if ((remaining >> sel) & 1u) { remaining &= ~(1u << sel); --n_remaining; }
             // _initialize_cars, reference :244-273
             uint32_t comp, age;
-            if (track == 2) { comp = 4u; age = 0u; }
-            else if (track == 1) { comp = 3u; age = 0u; }
-            else { comp = pos < 10 ? 0u : 1u; age = pos < 10 ? 4u : 0u; }
+            start_tyres(track, pos, comp, age);
             hook(sel, comp, age);
             s.Pk(sel) = age | (comp << kCompShift) | ((1u << comp) << kUsedShift) | ((uint32_t)pos << kGposShift);
             s.Cum(sel) = 0.0;
@@ -286,6 +306,7 @@ __device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv
         }
         for (int d = 0; d < n; ++d) s.Last(d) = 0.0;
     }
+    if constexpr (GridPolicy::kEdits) grid.edit(s, n, track, hook);
 
     // ================= _simulate_lap_1, reference :275-311 =================
     pace.begin_lap(1);
@@ -310,7 +331,7 @@ __device__ __forceinline__ RaceStart start_from_grid(const Rows &s, const LapEnv
         double sd = 0.0 + pf * (double)normal_from_u32(w2, e.norm);
         if (pos + 1 <= 3 && 1.0 < sd) sd = 1.0;
         const double lap_time = base_lap - sd * 0.5;
-        s.Cum(d) = 0.0 + lap_time;
+        s.Cum(d) = grid.lap1(d, 0.0 + lap_time);
         s.Pk(d) = (pk & ~kAgeMask) | (age + 1u);
     }
     sort_by_time(s, n);

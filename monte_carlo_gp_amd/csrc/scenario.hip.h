@@ -1,5 +1,6 @@
-// scenario.hip.h -- the race kernel of the six what-if calls: mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events,
-// mcgp_run_paces, mcgp_run_combined (include/mcgp.h, which states how the rule sets meet on one lap) and mcgp_run_weather.
+// scenario.hip.h -- the race kernel of the seven what-if calls: mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events,
+// mcgp_run_paces, mcgp_run_combined (include/mcgp.h, which states how the rule sets meet on one lap), mcgp_run_weather
+// and mcgp_run_grids.
 //
 // race_scenario_kernel<kFromState, kRules> is the generic kernel's code -- start_from_grid or start_from_state, run_laps,
 // classify_and_count -- over S scenarios of one race with common random numbers: one lane runs one (scenario, simulation)
@@ -17,10 +18,14 @@
 //                   start_from_grid and of run_laps; the laps on the wrong tyres.  It is instantiated alone, and its
 //                   tables come in the arguments of the rule sets it never meets: the condition bytes in `event_laps`
 //                   (the same [S][L + 1] bytes), the table of seconds in `lap_sec`, the staged u16 in `carried`.
+//   kRuleGrid       (grids.hip.h) GridEdits in the grid slot of start_from_grid: drops, pins and pit-lane starts on the
+//                   drawn grid; every driver's start slot.  It is instantiated alone and only from the grid (a mid-race
+//                   state has no grid), and its table comes the same way: the GridScenario [S] in `pens`, the staged u16
+//                   in `carried`.
 //
-// A slot whose bit is clear holds the model's policy (ModelPace, DrawnEvents, NoLapObserver, ModelTrack), which vanishes
-// at compile time.  The instantiations are the twelve the C ABI has: no rule set, each one alone, the first three
-// together, each from the grid and from a state.  An instantiation never reads a table whose bit is clear: callers pass NULL there.
+// A slot whose bit is clear holds the model's policy (ModelPace, DrawnEvents, NoLapObserver, ModelTrack, ModelGrid), which
+// vanishes at compile time.  The instantiations are the thirteen the C ABI has: no rule set, each one alone, the first
+// three together, each from the grid and, but for the grid edits, from a state.  An instantiation never reads a table whose bit is clear: callers pass NULL there.
 //
 // Every table is packed by its rule set's packer and read at wave-uniform addresses once per lap: ScenarioPit::begin_lap
 // reads the lap's StopLap, PenaltyLap and PaceLap::until, OffsetPace::begin_lap the lap's PaceLap, ForcedEvents the lap's
@@ -33,14 +38,15 @@
 // with penalties | fate << 5, and penalties_count, which masks the position, also counts mcgp_run_combined's deltas), one
 // u32 with events (the packed event counts: events_count; with all three rule sets only when ev_stage is given), n u16
 // with paces when `carried` is given (paces_count; for mcgp_run_combined both with delta NULL), n u16 with weather when
-// `carried` is given (the laps on the wrong tyres: weather_count).
+// `carried` is given (the laps on the wrong tyres: weather_count), n u16 with grid edits when `carried` is given (the
+// start slots: grid_count).
 //
 // Price (one MI355X, S60, two scenarios x 10^6 simulations, device ms per 10^6, medians of five with max - min;
 // profiles/combined_time.txt): all three rule sets, two empty scenarios 102.84 (0.41) against 98.22 (0.39) with
 // none and 106.69 (0.39) for mcgp_run_paces with an UNTIL_STOP offset, the dearest single-kind call; with a penalty to
 // serve 103.08 (0.35), a forced safety car 102.50 (0.45), an UNTIL_STOP offset 108.13 (0.49), all three and a planned stop
-// 109.59 (0.42).  profiles/penalties_time.txt, events_time.txt, paces_time.txt and weather_time.txt have each rule set
-// alone.
+// 109.59 (0.42).  profiles/penalties_time.txt, events_time.txt, paces_time.txt, weather_time.txt and grid_time.txt have
+// each rule set alone.
 #pragma once
 #include <type_traits>
 
@@ -48,10 +54,11 @@
 #include "events.hip.h"
 #include "paces.hip.h"
 #include "weather.hip.h"
+#include "grids.hip.h"
 
 namespace mcgp {
 
-constexpr uint32_t kRulePenalties = 1u, kRuleEvents = 2u, kRulePaces = 4u, kRuleWeather = 8u;
+constexpr uint32_t kRulePenalties = 1u, kRuleEvents = 2u, kRulePaces = 4u, kRuleWeather = 8u, kRuleGrid = 16u;
 constexpr uint32_t kRuleAll = kRulePenalties | kRuleEvents | kRulePaces;
 
 // run_laps' pit policy of a scenario: PlanPit decides the stops; after_pit adds the served SERVE_AT_STOP penalty after
@@ -112,7 +119,8 @@ struct ScenarioPit {
 // written, and, where wanted (NULL: not), ev_stage [S][m] (the packed event counts) with events and carried [S][m][n] u16
 // at the drivers that have an UNTIL_STOP offset in the scenario with paces.  With weather event_laps [S][L + 1] holds the
 // laps' condition bytes, lap_sec the [3][5] table and carried [S][m][n] u16 (NULL: not wanted) gets every driver's laps
-// on the wrong tyres.  Pointers of a rule set outside kRules are not read: pass NULL.
+// on the wrong tyres.  With grid edits pens holds the GridScenario [S] and carried [S][m][n] u16 (NULL: not wanted) gets
+// every driver's start slot.  Pointers of a rule set outside kRules are not read: pass NULL.
 template <bool kFromState, uint32_t kRules>
 __global__ void __launch_bounds__(512)
 race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restrict__ state,
@@ -125,13 +133,16 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
                      uint32_t n_batches)
 {
     static_assert(kRules == 0u || kRules == kRulePenalties || kRules == kRuleEvents || kRules == kRulePaces ||
-                      kRules == kRuleAll || kRules == kRuleWeather, "the rule sets of the C ABI");
+                      kRules == kRuleAll || kRules == kRuleWeather || (kRules == kRuleGrid && !kFromState),
+                  "the rule sets of the C ABI");
     constexpr bool kPen = (kRules & kRulePenalties) != 0u, kEv = (kRules & kRuleEvents) != 0u;
     constexpr bool kPace = (kRules & kRulePaces) != 0u, kWx = (kRules & kRuleWeather) != 0u;
+    constexpr bool kGrid = (kRules & kRuleGrid) != 0u;
     using Pace = std::conditional_t<kPace, OffsetPace, std::conditional_t<kWx, WeatherPace, ModelPace>>;
     using Track = std::conditional_t<kWx, WeatherTrack, ModelTrack>;
     using Events = std::conditional_t<kEv, ForcedEvents, DrawnEvents>;
     using Observer = std::conditional_t<kEv, PackedEventCounter, NoLapObserver>;
+    using Grid = std::conditional_t<kGrid, GridEdits, ModelGrid>;
     const uint32_t sid = blockIdx.y;
     const StrategyScenario *__restrict__ sc = scen + sid;
     const PenaltyScenario *__restrict__ pen = kPen ? pens + sid : nullptr;
@@ -142,13 +153,18 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
     const PaceLap *__restrict__ pl = kPace ? pace_laps + lap0 : nullptr;
     Events forced;
     if constexpr (kEv) forced = {event_laps + lap0};
+    Grid grid;
+    if constexpr (kGrid) {
+        const GridScenario *__restrict__ gs = reinterpret_cast<const GridScenario *>(pens) + sid;
+        grid = {gs, gs->pit};
+    }
     const uint32_t serve = kPen ? pen->serve : 0u, flag = kPen ? pen->flag : 0u, until = kPace ? ps->until : 0u;
     run_block(P, m, n_batches, hist + (size_t)sid * (size_t)(P->n * P->n),
               [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
         const uint64_t sim = sim_offset + local;
         const uint32_t c0 = (uint32_t)sim, c1 = (uint32_t)(sim >> 32);
         // the lane's place in the stagings: worked out here where events, paces or weather stage beside the position
-        // bytes, after the race otherwise
+        // bytes, after the race otherwise (the start slots are staged after the race too)
         uint64_t lane = 0, cell = 0;
         if constexpr (kEv || kPace || kWx) {
             lane = (uint64_t)sid * m + local;
@@ -166,7 +182,8 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
         const ScenarioPit<kRules> pit = {plan, pen, nl, pl, kPace ? ps->until_from : nullptr, &served, &active, crow, serve,
                                          0u, 0u, 0u};
         const RaceStart at = kFromState ? start_from_state(s, e, *state, c0, c1, seed_lo, seed_hi)
-                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr, PlannedTyres{sc}, pace);
+                                        : start_from_grid(s, e, c0, c1, seed_lo, seed_hi, nullptr, PlannedTyres{sc}, pace,
+                                                          grid);
         if constexpr (kWx) {
             // lap 1's lap time, from the grid: on the start compound under the configuration's condition
             if (crow) {
@@ -212,6 +229,13 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
             }
             row[d] = (uint8_t)b;
         }
+        // each driver's start slot after the edits: its pk word keeps it to the flag
+        if constexpr (kGrid) {
+            if (carried) {
+                uint16_t *srow = carried + cell;
+                for (int d = 0; d < e.n; ++d) srow[d] = (uint16_t)gpos_of(s.Pk((uint32_t)d));
+            }
+        }
         if constexpr (kEv) {
             // mcgp_run_events always stages the word (its chunk budget counts it); only mcgp_run_combined can do without
             if (kRules == kRuleEvents || ev_stage) ev_stage[lane] = seen.packed;
@@ -229,7 +253,7 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
 }
 
 // The instantiation behind a scenario call, for the launch and for its register count: `rules` is one of the five sets
-// above or kRuleWeather (anything else: NULL), from the grid or from a state.
+// above, kRuleWeather or, from the grid only, kRuleGrid (anything else: NULL), from the grid or from a state.
 using ScenarioKernel = decltype(&race_scenario_kernel<false, 0u>);
 inline ScenarioKernel scenario_kernel(uint32_t rules, bool from_state)
 {
@@ -242,6 +266,7 @@ inline ScenarioKernel scenario_kernel(uint32_t rules, bool from_state)
     case kRuleAll: return from_state ? &race_scenario_kernel<true, kRuleAll> : &race_scenario_kernel<false, kRuleAll>;
     case kRuleWeather:
         return from_state ? &race_scenario_kernel<true, kRuleWeather> : &race_scenario_kernel<false, kRuleWeather>;
+    case kRuleGrid: return from_state ? nullptr : &race_scenario_kernel<false, kRuleGrid>;
     }
     return nullptr;
 }

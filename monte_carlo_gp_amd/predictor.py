@@ -389,6 +389,25 @@ class F1Predictor:
                                track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
                                allow_single_compound=allow_single_compound)
 
+    def predict_grids(self, season: int, race: str, fixture: dict | str, edits: dict, strategies: dict | None = None,
+                      n_simulations: int = 100000, seed: int | None = None, prediction_point: str = 'fp2',
+                      allow_single_compound: bool = False):
+        """Grid scenarios (not in the reference, whose adjust_for_penalties smears a driver's grid distribution before
+        the run): predict_strategies' race run through RaceSimulator.run_grids under each scenario of `edits` ({name:
+        [GridEdit, ...]}) and `strategies` ({name: [PitPlan, ...]} or None), paired by simulation.  A scenario without
+        edits or plans reproduces predict_weekend's race for the same seed.  Returns the GridResult."""
+        if isinstance(fixture, str):
+            with open(fixture) as f:
+                fixture = json.load(f)
+        if not fixture.get('drivers'):
+            raise ValueError(f"No practice data available for {season} {race}")
+        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
+        sim = RaceSimulator(inp['config'], device=self.device)
+        return sim.run_grids(n_simulations, edits, strategies, inp['base_pace'], inp['tire_deg'],
+                             inp['driver_variance'], inp['driver_dnf_rates'], grid_probs=inp['grid_probs'], seed=seed,
+                             track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
+                             allow_single_compound=allow_single_compound)
+
     def predict_combined(self, season: int, race: str, fixture: dict | str, scenarios: dict, state=None,
                          n_simulations: int = 100000, seed: int | None = None, prediction_point: str = 'fp2',
                          allow_single_compound: bool = False):

@@ -441,16 +441,18 @@ class RaceSimulator:
         return counts, c_plans, packed_kinds
 
     def _run_scenarios(self, entry, result, label, n_simulations, kinds, strategies, race, grid_probs, state, seed,
-                       sim_offset, drivers, return_orders, allow_single_compound, call_wide=(), all_dry=None):
-        """run_strategies, run_penalties, run_events, run_paces, run_combined and run_weather: the race under named scenarios of pit
+                       sim_offset, drivers, return_orders, allow_single_compound, call_wide=(), all_dry=None,
+                       grid_only=False):
+        """run_strategies, run_penalties, run_events, run_paces, run_combined, run_weather and run_grids: the race under named scenarios of pit
         plans (`strategies`) and of the call's own `kinds` of items, a list (empty for run_strategies) of (items {name:
         [item]}, item_type: their struct, pack_items: see _pack_plans, extra = (name, shape(S, n, L)): the kind's own
-        count array).  The scenario names are the union of the dicts in the order given, the kinds' first; the kinds'
+        count array, or a list of such pairs).  The scenario names are the union of the dicts in the order given, the kinds' first; the kinds'
         (count, items) pairs follow the plans among the arguments and their count arrays follow hist and delta among
         the outputs, both in the kinds' order.  result: the result class; label: the dicts' names for the message.
         call_wide: the call's arguments that hold for every scenario, after the kinds' (run_weather: its model).
         all_dry: scenario name -> is the track dry on every lap (None: track_condition says so for all of them); the
-        two-compound rule is checked for the plans of those scenarios."""
+        two-compound rule is checked for the plans of those scenarios.  grid_only: the entry point has no state argument
+        (run_grids, which has refused a state by then)."""
         src = self._source(grid_probs, state, drivers)
         strategies = strategies or {}
         names = []
@@ -467,7 +469,7 @@ class RaceSimulator:
             names, by_name(strategies), src,
             not allow_single_compound and (all_dry if all_dry is not None else race[-1] == 'dry'),
             [(by_name(items), pack) for items, _, pack, _ in kinds])
-        head = src.c_args() + (n, S, (C.c_uint32 * S)(*counts), (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans))
+        head = (src.c_args()[:1] if grid_only else src.c_args()) + (n, S, (C.c_uint32 * S)(*counts), (N.McgpPitPlan * max(len(c_plans), 1))(*c_plans))
         for (_, item_type, _, _), (item_counts, c_items) in zip(kinds, packed_kinds):
             head += ((C.c_uint32 * S)(*item_counts), (item_type * max(len(c_items), 1))(*c_items))
         head += tuple(call_wide)
@@ -475,7 +477,8 @@ class RaceSimulator:
         seed64 = self._resolve_seed(seed)
         if not hasattr(N.lib(), entry):
             raise N.McgpError(-1, f'the loaded library does not export {entry}')
-        shapes = dict(hist=(S, n, n), delta=(S, n, 2 * n - 1), **{extra[0]: extra[1](S, n, L) for _, _, _, extra in kinds})
+        extras = [pair for _, _, _, extra in kinds for pair in (extra if isinstance(extra, list) else [extra])]
+        shapes = dict(hist=(S, n, n), delta=(S, n, 2 * n - 1), **{name: shape(S, n, L) for name, shape in extras})
 
         def alloc(count):
             return dict({k: np.zeros(shape, np.uint64) for k, shape in shapes.items()},
@@ -971,6 +974,75 @@ class RaceSimulator:
             strategies, (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed,
             sim_offset, drivers, return_orders, allow_single_compound, call_wide=(C.byref(model.c_struct()),),
             all_dry=all_dry)
+
+    def _grid_kind(self, edits):
+        def pack(name, eds, index):
+            n = len(index)
+            if len(eds) > n:
+                raise ValueError(f'scenario {name!r}: at most one edit per driver, got {len(eds)} for {n} drivers')
+            packed, seen, slots = [], {}, {}
+            for ed in eds:
+                if str(ed.driver) not in index:
+                    raise ValueError(f'scenario {name!r}: {ed.driver!r} is not one of the drivers')
+                try:
+                    c = ed.c_struct(index)
+                except ValueError as e:
+                    raise ValueError(f'scenario {name!r}: {e}') from None
+                if c.driver in seen:
+                    raise ValueError(f'scenario {name!r}: {ed.driver} has two edits ({seen[c.driver]} and {ed})')
+                seen[c.driver] = ed
+                if c.kind == N.GRID_PIN:
+                    if c.value in slots:
+                        raise ValueError(f'scenario {name!r}: slot {c.value} is pinned twice ({slots[c.value]} and {ed})')
+                    slots[c.value] = ed
+                packed.append(c)
+            n_pit = sum(1 for c in packed if c.kind == N.GRID_PIT_LANE)
+            for slot, ed in slots.items():
+                if slot > n - n_pit:
+                    raise ValueError(f"scenario {name!r}: {ed}: slot {slot} is one of the last {n_pit}, which the scenario's "
+                                     f'pit-lane starters take')
+            return packed
+
+        return edits, N.McgpGridEdit, pack, [('start', lambda S, n, L: (S, n, n)),
+                                             ('gain', lambda S, n, L: (S, n, 2 * n - 1))]
+
+    def run_grids(
+        self,
+        n_simulations: int,
+        edits: dict,
+        strategies: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        grid_probs: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        return_orders: bool = False,
+        allow_single_compound: bool = False,
+    ) -> 'GridResult':
+        """Grid scenarios (include/mcgp.h: mcgp_run_grids): the race under each scenario of `edits`, {name: [GridEdit,
+        ...]}, and `strategies`, {name: [PitPlan, ...]} or None; a scenario holds the edits and the plans given under its
+        name, and the scenario names are the union of the two dicts in the order given (edits first; at most 64; the
+        first is the one `compare` measures against).  Every simulation draws its grid as run_monte_carlo's does; then
+        the scenario's pit-lane starters take the last slots (in their drawn order), its pinned drivers their slots, and
+        the others line up by (drawn slot + places dropped, drawn slot) on the slots left, as the reference's
+        apply_grid_penalties does for one grid.  The cars start from the new slots: start tyres, lap 1 and every tie
+        of times follow them, and a pit-lane starter's lap 1 is longer by its seconds.  At most one edit per driver and
+        scenario; two pins on one slot, a pin on a slot the pit-lane starters take and an unknown driver raise
+        ValueError.  A mid-race state has no grid: `state` raises ValueError.  Everything else -- the remaining
+        arguments, the plans' checks, the simulation ids and draws, the seed rules and the device sharding -- is
+        run_strategies': a scenario without edits gives exactly its counts.  last_histogram: [S, n, n]."""
+        if state is not None:
+            raise ValueError('run_grids runs from the grid: a mid-race state has no grid to edit (state must be None)')
+        edits = {str(k): list(v) for k, v in edits.items()}
+        return self._run_scenarios(
+            'mcgp_run_grids', GridResult, 'edits / strategies', n_simulations, [self._grid_kind(edits)], strategies,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, None, seed, sim_offset,
+            drivers, return_orders, allow_single_compound, grid_only=True)
 
     def run_gaps(
         self,
@@ -2696,6 +2768,109 @@ class WeatherResult(StrategyResult):
     def expected_wrong_tyre_laps(self, name, driver) -> float:
         p = self.wrong_tyre_laps_distribution(name, driver)
         return float(p @ np.arange(p.shape[0], dtype=np.float64))
+
+
+# ---------------------------------------------------------------------------------------------- grid scenarios
+# The project's own assumption, not the reference's (which has no pit-lane start: it maps 'pitlane_start' to a 20-place
+# drop): the seconds a car that starts from the pit lane loses on lap 1 to one that starts from the last grid slot.
+DEFAULT_PIT_LANE_SECONDS = 2.5
+
+
+@dataclass
+class GridEdit:
+    """One driver's edit of the starting grid in a scenario of RaceSimulator.run_grids: kind 'drop' (value: places, 1 to
+    255), 'pin' (value: the slot, 1-based) or 'pit_lane' (seconds added to lap 1).  Use the constructors drop, back, pin
+    and pit_lane.  The pit-lane default, DEFAULT_PIT_LANE_SECONDS, is an assumption of this project, not a figure of
+    the reference model, which has no pit-lane start."""
+    driver: str
+    kind: str
+    value: int = 0
+    seconds: float = 0.0
+
+    KINDS = {'drop': N.GRID_DROP, 'pin': N.GRID_PIN, 'pit_lane': N.GRID_PIT_LANE}
+
+    @classmethod
+    def drop(cls, driver, places) -> 'GridEdit':
+        """`places` down the drawn grid: an int in [1, 255] or a PENALTY_TYPES name ('engine', 'full_pu', 'gearbox',
+        'pitlane_start': the reference's 20-place drop, not a pit-lane start)."""
+        if isinstance(places, str):
+            from .predictor import PENALTY_TYPES
+            if places not in PENALTY_TYPES:
+                raise ValueError(f'places must be an int or one of {sorted(PENALTY_TYPES)}, got {places!r}')
+            places = PENALTY_TYPES[places]
+        return cls(str(driver), 'drop', int(places))
+
+    @classmethod
+    def back(cls, driver) -> 'GridEdit':
+        """To the back of the grid (in front of any pit-lane starter): the largest drop."""
+        return cls(str(driver), 'drop', N.MAX_GRID_DROP)
+
+    @classmethod
+    def pin(cls, driver, slot) -> 'GridEdit':
+        """On grid slot `slot` (1-based) in every simulation."""
+        return cls(str(driver), 'pin', int(slot))
+
+    @classmethod
+    def pit_lane(cls, driver, seconds=DEFAULT_PIT_LANE_SECONDS) -> 'GridEdit':
+        """From the pit lane: behind the whole grid, and `seconds` more on lap 1."""
+        return cls(str(driver), 'pit_lane', 0, float(seconds))
+
+    def __str__(self):
+        return (f'{self.driver}:pit_lane+{self.seconds:g}s' if self.kind == 'pit_lane'
+                else f'{self.driver}:{self.kind} {self.value}')
+
+    def c_struct(self, index) -> N.McgpGridEdit:
+        """mcgp_grid_edit; ValueError on an unknown kind, a value outside its range or seconds where they do not belong."""
+        if self.kind not in self.KINDS:
+            raise ValueError(f"{self.driver}: kind must be 'drop', 'pin' or 'pit_lane', got {self.kind!r}")
+        value, seconds = int(self.value), float(self.seconds)
+        if self.kind == 'drop' and not 1 <= value <= N.MAX_GRID_DROP:
+            raise ValueError(f'{self}: places must be in [1, {N.MAX_GRID_DROP}]')
+        if self.kind == 'pin' and not 1 <= value <= len(index):
+            raise ValueError(f'{self}: the slot must be in [1, {len(index)}]')
+        if self.kind == 'pit_lane':
+            if value != 0:
+                raise ValueError(f'{self}: a pit-lane start has no value')
+            if not math.isfinite(seconds) or not 0.0 <= seconds <= N.MAX_PIT_LANE_SECONDS:
+                raise ValueError(f'{self.driver}: pit-lane seconds must be finite and in [0, 1e6], got {self.seconds!r}')
+        elif seconds != 0.0:
+            raise ValueError(f'{self}: only a pit-lane start has seconds')
+        c = N.McgpGridEdit()
+        c.driver, c.kind, c.value, c.seconds = index[str(self.driver)], self.KINDS[self.kind], value, seconds
+        return c
+
+
+@dataclass
+class GridResult(StrategyResult):
+    """What RaceSimulator.run_grids returns: StrategyResult's counts and helpers, and
+      start  [S][n][n]       [scenario][driver][start slot - 1 after the edits]; rows and columns sum to N
+      gain   [S][n][2n - 1]  [scenario][driver][(start slot - classified position) + n - 1]: above the centre, places
+                             gained from the edited grid; every row sums to N"""
+    start: np.ndarray | None = None
+    gain: np.ndarray | None = None
+
+    def start_probabilities(self, name=None) -> dict:
+        """{driver: {slot: probability}} of scenario `name` (None: {name: that dict} for every scenario)."""
+        if name is None:
+            return {s: self.start_probabilities(s) for s in self.names}
+        return histogram_to_probs(self.start[self._s(name)], self.drivers, max(self.n_simulations, 1))
+
+    def expected_start(self, name) -> dict:
+        """{driver: mean start slot (1-based)} of scenario `name`."""
+        p = np.asarray(self.start[self._s(name)], np.float64) / max(self.n_simulations, 1)
+        slot = np.arange(1, len(self.drivers) + 1, dtype=np.float64)
+        return {d: float(p[i] @ slot) for i, d in enumerate(self.drivers)}
+
+    def places_gained_distribution(self, name, driver) -> dict:
+        """{places gained from the start slot (negative: lost): probability} of `driver` in scenario `name`."""
+        n = len(self.drivers)
+        row = np.asarray(self.gain[self._s(name), self._d(driver)], np.float64) / max(self.n_simulations, 1)
+        return {int(k - (n - 1)): float(p) for k, p in enumerate(row)}
+
+    def expected_places_gained(self, name, driver) -> float:
+        n = len(self.drivers)
+        row = np.asarray(self.gain[self._s(name), self._d(driver)], np.float64) / max(self.n_simulations, 1)
+        return float(row @ np.arange(-(n - 1), n, dtype=np.float64))
 
 
 # ---------------------------------------------------------------------------------------------- combined scenarios

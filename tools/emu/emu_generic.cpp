@@ -1,11 +1,11 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
 // fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
 // gaps.hip.h, conditions.hip.h, stints.hip.h, moves.hip.h, fastest.hip.h and scenario.hip.h (with strategy.hip.h,
-// penalties.hip.h, events.hip.h, paces.hip.h and weather.hip.h) with g++ through the stand-in <hip/hip_runtime.h> of this directory and
+// penalties.hip.h, events.hip.h, paces.hip.h, weather.hip.h and grids.hip.h) with g++ through the stand-in <hip/hip_runtime.h> of this directory and
 // calls the real __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_gaps_kernel<false / true>,
 // race_conditions_kernel<false / true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false /
-// true>, race_fastest_kernel, the twelve instantiations of race_scenario_kernel, penalties_count, events_count, paces_count,
-// weather_count.
+// true>, race_fastest_kernel, the thirteen instantiations of race_scenario_kernel, penalties_count, events_count,
+// paces_count, weather_count, grid_count.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -19,16 +19,16 @@
 // threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
 // records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
 // operation and strides by its block's size, so it does run here, as blocks of one thread; so do penalties_count, events_count
-// paces_count and weather_count.
+// paces_count, weather_count and grid_count.
 //
 // Shared text: the five analysis calls (emu_generic_trace, emu_gaps_run, emu_conditions_run, emu_stints_run,
-// emu_moves_run) start with analysis_setup, the six scenario calls are scenario_run with their rule sets.
+// emu_moves_run) start with analysis_setup, the seven scenario calls are scenario_run with their rule sets.
 //
 // Used by tests/test_generic_host_build.py (race, resume, trace, strategies) and by tests/test_<call>_host_build.py for
-// gaps, conditions, stints, moves, fastest, penalties, events, paces, combined and weather, each through its helper
+// gaps, conditions, stints, moves, fastest, penalties, events, paces, combined, weather and grids, each through its helper
 // tests/<call>_host_build.py (tests/kernel_host_build.py compiles this file); the stand-alone programs
-// tools/emu/sanitize_{penalties,events,paces,combined,bonus,weather}_main.cpp are built with it for
-// tests/test_{penalties,events,paces,combined,fastest,weather}_sanitize.py.
+// tools/emu/sanitize_{penalties,events,paces,combined,bonus,weather,grids}_main.cpp are built with it for
+// tests/test_{penalties,events,paces,combined,fastest,weather,grids}_sanitize.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -46,6 +46,7 @@
 #include "../../monte_carlo_gp_amd/csrc/event_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/pace_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/weather_pack.h"
+#include "../../monte_carlo_gp_amd/csrc/grid_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/scenario.hip.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -121,6 +122,15 @@ int analysis_setup(const mcgp_config *cfg, const mcgp_drivers *drv, const double
 // The weather call (rules = kRuleWeather) hands its own inputs in `wx`: they are checked and packed by weather_pack.h into
 // the condition bytes and the table, which the kernel reads through its event_laps and lap_sec arguments; car_stage
 // gets the laps on the wrong tyres, and weather_count (grid_x x S x n blocks) adds them to `wrong` [S][n][L + 1].
+// The grid call (rules = kRuleGrid, from the grid only) hands its own inputs in `gr`: they are checked and packed by
+// grid_pack.h into the GridScenario table, which the kernel reads through its `pens` argument; car_stage gets the start
+// slots, and grid_count (grid_x x S x n blocks) adds them to `start` [S][n][n] and `gain` [S][n][2n - 1].
+struct GridArgs {
+    const uint32_t *edit_count;
+    const mcgp_grid_edit *edits;
+    unsigned long long *start, *gain;
+};
+
 struct WeatherArgs {
     const uint32_t *change_count;
     const mcgp_track_change *changes;
@@ -135,7 +145,7 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
                  const mcgp_pace_offset *paces, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist,
                  uint8_t *stage, uint32_t *ev_stage, uint16_t *car_stage, unsigned long long *delta, unsigned long long *fate,
                  unsigned long long *events_cnt, unsigned long long *carried, uint32_t grid_x, const char **err,
-                 const WeatherArgs *wx = nullptr)
+                 const WeatherArgs *wx = nullptr, const GridArgs *gr = nullptr)
 {
     const bool pen = rules & mcgp::kRulePenalties, ev = rules & mcgp::kRuleEvents, pace = rules & mcgp::kRulePaces;
     static mcgp::KParams kp;
@@ -149,6 +159,9 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     if ((events_cnt || rules == mcgp::kRuleEvents) && !ev_stage) return fail(MCGP_E_BAD_ARG, "events need ev_stage", err);
     if ((carried || (wx && wx->wrong)) && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
     if ((rules == mcgp::kRuleWeather) != (wx != nullptr)) return fail(MCGP_E_BAD_ARG, "weather needs its inputs", err);
+    if ((rules == mcgp::kRuleGrid) != (gr != nullptr)) return fail(MCGP_E_BAD_ARG, "grid edits need their inputs", err);
+    if (gr && state) return fail(MCGP_E_BAD_ARG, "grid edits run from the grid only", err);
+    if (gr && (gr->start || gr->gain) && !car_stage) return fail(MCGP_E_BAD_ARG, "start and gain need car_stage", err);
     const int L = cfg->total_laps;
     mcgp::ResumeState st;
     std::memset(&st, 0, sizeof(st));
@@ -167,7 +180,8 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     std::vector<mcgp::PaceScenario> pscen;
     std::vector<mcgp::PaceLap> pace_laps;
     std::vector<double> lap_sec;
-    uint64_t n_pens = 0, n_events = 0, n_paces = 0, n_changes = 0;
+    std::vector<mcgp::GridScenario> grids;
+    uint64_t n_pens = 0, n_events = 0, n_paces = 0, n_changes = 0, n_edits = 0;
     std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, resumed, &scen, &stop_laps);
     if (e.empty() && pen) e = mcgp::check_penalty_counts(n_scenarios, penalty_count, &n_pens);
     if (e.empty() && ev) e = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
@@ -186,12 +200,18 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     if (e.empty() && wx)
         e = mcgp::pack_weather(n_scenarios, wx->change_count, wx->changes, wx->model, cfg->track_condition, L, first_lap,
                                resumed, &event_laps, &lap_sec);
+    if (e.empty() && gr && !gr->edit_count) e = "edit_count is NULL";
+    if (e.empty() && gr) e = mcgp::check_edit_counts(n_scenarios, gr->edit_count, n, &n_edits);
+    if (e.empty() && n_edits && !gr->edits) e = "edits is NULL";
+    if (e.empty() && gr) e = mcgp::pack_grids(n_scenarios, gr->edit_count, gr->edits, n, &grids);
     if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
     const auto kernel = mcgp::scenario_kernel(rules, resumed);
+    const mcgp::PenaltyScenario *pens_arg = pen ? pens.data()
+                                            : gr ? reinterpret_cast<const mcgp::PenaltyScenario *>(grids.data()) : nullptr;
     one_thread_block(n_scenarios);
     for (uint32_t si = 0; si < n_scenarios; ++si) {
         blockIdx.y = si;
-        kernel(&kp, &st, scen.data(), stop_laps.data(), pen ? pens.data() : nullptr, pen ? pen_laps.data() : nullptr,
+        kernel(&kp, &st, scen.data(), stop_laps.data(), pens_arg, pen ? pen_laps.data() : nullptr,
                ev || wx ? event_laps.data() : nullptr, pace ? pscen.data() : nullptr, pace ? pace_laps.data() : nullptr,
                pace || wx ? lap_sec.data() : nullptr, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
                ev_stage, car_stage, (uint32_t)n_sims);
@@ -219,6 +239,15 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
                 for (uint32_t x = 0; x < grid_x; ++x) {
                     blockIdx = {x, y, z};
                     mcgp::weather_count(car_stage, n_sims, n, (uint32_t)L, wx->wrong);
+                }
+    }
+    if (gr && (gr->start || gr->gain)) {
+        gridDim = {grid_x, n_scenarios, n};
+        for (uint32_t z = 0; z < n; ++z)
+            for (uint32_t y = 0; y < n_scenarios; ++y)
+                for (uint32_t x = 0; x < grid_x; ++x) {
+                    blockIdx = {x, y, z};
+                    mcgp::grid_count(stage, car_stage, n_sims, n, gr->start, gr->gain);
                 }
     }
     one_thread_block(1);
@@ -385,10 +414,11 @@ int emu_fastest_run(const mcgp_config *cfg, const mcgp_drivers *drv, const doubl
     return MCGP_OK;
 }
 
-// The six scenario calls (scenario_run above).  stage [S][n_sims][n] holds each driver's classified position, with
+// The seven scenario calls (scenario_run above).  stage [S][n_sims][n] holds each driver's classified position, with
 // penalties | fate << 5; ev_stage the packed event counts (red | sc << 10 | vsc << 20); car_stage the laps carried at the
 // drivers with an UNTIL_STOP offset (emu_weather_run: every driver's laps on the wrong tyres, or NULL: not staged).
-// emu_combined_run takes a NULL count array as none in any scenario.
+// emu_combined_run takes a NULL count array as none in any scenario.  emu_grid_run: car_stage gets every driver's start
+// slot after the edits (NULL: not staged).
 int emu_generic_strategy(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
                          const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
                          const mcgp_pit_plan *plans, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
@@ -457,6 +487,18 @@ int emu_weather_run(const mcgp_config *cfg, const mcgp_drivers *drv, const doubl
     return scenario_run(mcgp::kRuleWeather, cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, nullptr, nullptr,
                         nullptr, nullptr, nullptr, nullptr, n_sims, sim_offset, seed, hist, stage, nullptr, car_stage, nullptr,
                         nullptr, nullptr, nullptr, grid_x, err, &wx);
+}
+
+int emu_grid_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, uint32_t n, uint32_t n_scenarios,
+                 const uint32_t *plan_count, const mcgp_pit_plan *plans, const uint32_t *edit_count,
+                 const mcgp_grid_edit *edits, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist,
+                 uint8_t *stage, uint16_t *car_stage, unsigned long long *start, unsigned long long *gain, uint32_t grid_x,
+                 const char **err)
+{
+    const GridArgs gr = {edit_count, edits, start, gain};
+    return scenario_run(mcgp::kRuleGrid, cfg, drv, grid_probs, nullptr, n, n_scenarios, plan_count, plans, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, n_sims, sim_offset, seed, hist, stage, nullptr, car_stage, nullptr,
+                        nullptr, nullptr, nullptr, grid_x, err, nullptr, &gr);
 }
 
 }  // extern "C"
