@@ -7,6 +7,7 @@ oracle's finishing orders (tests/test_strategy_host.py checks that), which is wh
 
 plans: {driver index: (start_compound or -1, start_age, [(lap, compound id), ...])}."""
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -62,6 +63,12 @@ def _stint(track, remaining):
     return 2 if remaining > 30 else 1 if remaining > 15 else 0
 
 
+@functools.lru_cache(maxsize=1 << 16)
+def _philox(c0, c1, lap, purpose, k0, k1):
+    """The four words of one counter, kept: the scenarios of a call draw the same words, simulation by simulation."""
+    return tuple(O.philox([c0, c1, lap, purpose], [k0, k1]))
+
+
 class _Race:
     """One simulation's cars: per driver cum, last, comp, age, used, gpos, dnf (lap or 0), drs, dirty; `ord`."""
 
@@ -74,7 +81,7 @@ class _Race:
         self.ord = list(range(n))
 
     def draw(self, lap, purpose):
-        return O.philox(self.ctr + [lap, purpose], self.key)
+        return _philox(self.ctr[0], self.ctr[1], lap, purpose, self.key[0], self.key[1])
 
     def sort(self):
         self.ord.sort(key=lambda d: (self.cum[d], self.gpos[d]))

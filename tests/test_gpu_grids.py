@@ -7,7 +7,10 @@ and device='all' gives device 0's counts.
 
 The sweep does not pass empty.  By grids_ref alone, on this project's CPU reference: an edit changed a start compound on
 49 of the 100 inputs (the dry ones with 11 cars or more), a finishing order moved on 94, and a pit-lane car was classified
-ahead of a car that started from the grid on 97.  The floors (grids_cases.FLOORS) are a little below: 44, 88, 90."""
+ahead of a car that started from the grid on 97.  The floors (grids_cases.FLOORS) are a little below: 44, 88, 90.
+
+Left to tests/test_gpu_weather_grids_fuzz.py: random mixtures of edits and the whole field edited at once, grid_count past
+one step of its loop against a reference, staging chunks, and a call past the staging budget."""
 import ctypes as C
 
 import numpy as np

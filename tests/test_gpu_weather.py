@@ -8,7 +8,11 @@ to the one call.
 The sweeps do not pass empty.  By weather_ref alone, on this project's CPU reference: from the grid a car under the rule
 crossed over (stopped only because it was on the wrong tyres) on 87 of the 100 inputs, a red flag fell on a changed lap on
 33 and a finishing order moved on 89; from a state 69, 26 and 79 of 94.  The floors (weather_cases.GRID_FLOORS,
-STATE_FLOORS) are a little below: 80, 28, 82 and 62, 21, 72."""
+STATE_FLOORS) are a little below: 80, 28, 82 and 62, 21, 72.
+
+Left to tests/test_gpu_weather_grids_fuzz.py: tables with zero cells, the limits of include/mcgp.h (64 changes, 1000
+laps, one lap, column L), states after the first and the last laps, weather_count past one step of its loop against a
+reference, staging chunks, a call past the staging budget, and device='all'."""
 import ctypes as C
 
 import numpy as np
