@@ -112,13 +112,28 @@ def _bars(title, probs, top=10):
         print(f"{i:2}. {d:4} {p:6.1%} {'#' * int(p * 30)}")
 
 
-def cmd_predict(args) -> int:
-    fixture = synthetic_fixture()
+def load_fixture(args):
+    """The race fixture of a command: the --fixture file, else the synthetic weekend under --offline, else None after the
+    error line (the command then ends with status 2)."""
     if args.fixture:
         with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+            return json.load(f)
+    if args.offline:
+        return synthetic_fixture()
+    print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+    return None
+
+
+def load_state(path):
+    """The RaceState of a --state file (RaceState.to_json)."""
+    from .simulation import RaceState
+    with open(path) as f:
+        return RaceState.from_json(json.load(f))
+
+
+def cmd_predict(args) -> int:
+    fixture = load_fixture(args)
+    if fixture is None:
         return 2
     print(f"\n{'=' * 60}\nF1 Race Prediction: {args.season} {args.race}\nPrediction point: {args.prediction_point}")
     print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
@@ -307,18 +322,10 @@ def _print_moves(mv, label='', top=10) -> None:
 
 
 def cmd_in_race(args) -> int:
-    from .simulation import RaceState
-    fixture = synthetic_fixture()
-    if args.fixture:
-        with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
+    fixture = load_fixture(args)
+    if fixture is None:
         return 2
-    states = []
-    for path in args.state:
-        with open(path) as f:
-            states.append(RaceState.from_json(json.load(f)))
+    states = [load_state(path) for path in args.state]
     print(f"\n{'=' * 60}\nF1 In-Race Prediction: {args.season} {args.race}")
     print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
           f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}")
@@ -419,52 +426,128 @@ def strategy_scenarios(driver: str, plans=(), window=None) -> dict:
     return out
 
 
-def cmd_strategy(args) -> int:
-    from .simulation import RaceState
-    fixture = synthetic_fixture()
-    if args.fixture:
-        with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
-        return 2
-    state = None
-    if args.state:
-        with open(args.state) as f:
-            state = RaceState.from_json(json.load(f))
-    try:
-        scenarios = strategy_scenarios(args.driver, args.plan, args.window)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
+def _strategy_call(args):
+    scenarios = strategy_scenarios(args.driver, args.plan, args.window)
     if len(scenarios) < 2:
-        print('error: give at least one --plan or --window to compare with the model', file=sys.stderr)
-        return 2
-    print(f"\n{'=' * 60}\nF1 Pit Strategy: {args.season} {args.race}, {args.driver}")
-    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
-          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
-          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
-    print('=' * 60 + '\n')
-    res = F1Predictor(device=args.device).predict_strategies(args.season, args.race, fixture, scenarios, state=state,
-                                                             n_simulations=args.simulations, seed=args.seed,
-                                                             allow_single_compound=args.allow_single_compound)
+        raise ValueError('give at least one --plan or --window to compare with the model')
+    return (scenarios,)
+
+
+def _strategy_table(args, kind, call, res) -> dict:
     d = args.driver
     rows = []
     print(f"{'scenario':16} {'win':>7} {'podium':>7} {'E[pts]':>7} {'E[pos]':>7} {'P(better)':>10}  gain +- SE")
     print('-' * 78)
     for name in res.names:
-        c = res.compare(name, d)
         row = dict(scenario=name, win=res.win_probability(name, d), podium=res.podium_probability(name, d),
                    expected_points=res.expected_points(name)[d], expected_position=res.expected_position(name)[d],
-                   p_better=c['p_better'], p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'],
-                   se=c['se'], win_probabilities={x: res.win_probability(name, x) for x in res.drivers})
+                   **_compared(res, name, d), win_probabilities={x: res.win_probability(name, x) for x in res.drivers})
         rows.append(row)
         print(f"{name[:16]:16} {row['win']:7.1%} {row['podium']:7.1%} {row['expected_points']:7.2f} "
               f"{row['expected_position']:7.2f} {row['p_better']:10.1%}  {row['mean_gain']:+.3f} +- {row['se']:.3f}")
     print(f"\nbest by expected points: {res.best(d)}")
+    return {'driver': d, 'n_simulations': res.n_simulations, 'scenarios': rows}
+
+
+def _compared(res, name, d) -> dict:
+    """A driver's paired comparison of scenario `name` with the first scenario, as every what-if row holds it."""
+    c = res.compare(name, d)
+    return {k: c[k] for k in ('p_better', 'p_same', 'p_worse', 'mean_gain', 'se')}
+
+
+ROW_KEYS = ('scenario', 'win_probabilities', 'podium_probabilities', 'expected_position', 'drivers')
+
+
+def _scenario_row(res, name) -> dict:
+    """What the JSON row of a scenario holds in every what-if command but `strategy`; 'drivers' is filled per command."""
+    return dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
+                podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
+                expected_position=res.expected_position(name), drivers={})
+
+
+def _print_winners(res, row) -> None:
+    lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
+    print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
+
+
+def _scenario_table(args, kind, call, res) -> dict:
+    """The table and JSON document of events, pace, weather, grid and what-if: per scenario the drivers shown with their
+    odds and the change against the first scenario.  The kind may add: 'shown' (args, call, res) -> the drivers to show
+    (none: the five likeliest winners); 'scenario' (res, name, call) -> (text behind the scenario's heading, its extra row
+    keys); 'driver' (res, name, d, call) -> (the driver's extra keys, the text of its extra columns, lines printed below
+    it), with the extra columns' heading in 'columns'; 'row_keys', the order of a row's keys where it is not ROW_KEYS;
+    'document' (call) -> extra top-level keys; 'position_change': False leaves the expected-position change out."""
+    base = res.names[0]
+    shown = kind.get('shown', lambda args, call, res: [args.driver] if args.driver else [])(args, call, res) \
+        or sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
+    change = kind.get('position_change', True)
+    epos0 = res.expected_position(base)
+    rows = []
+    for name in res.names:
+        head, extra = kind['scenario'](res, name, call) if 'scenario' in kind else ('', {})
+        print(f"scenario: {name}{head}")
+        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} "
+              + (f"{'change':>7} " if change else '') + f"{'P(better)':>10}  gain +- SE" + kind.get('columns', ''))
+        row = dict(_scenario_row(res, name), **extra)
+        for d in shown:
+            win, pod, epos = row['win_probabilities'][d], row['podium_probabilities'][d], row['expected_position'][d]
+            r = row['drivers'][d] = dict(win=win, win_change=win - res.win_probability(base, d), podium=pod,
+                                         podium_change=pod - res.podium_probability(base, d), expected_position=epos)
+            if change:
+                r['expected_position_change'] = epos - epos0[d]
+            r.update(_compared(res, name, d))
+            more, columns, lines = kind['driver'](res, name, d, call) if 'driver' in kind else ({}, '', [])
+            r.update(more)
+            print(f"  {d[:8]:8} {win:7.1%} {r['win_change']:+8.1%} {pod:7.1%} {r['podium_change']:+8.1%} {epos:7.2f} "
+                  + (f"{r['expected_position_change']:+7.2f} " if change else '')
+                  + f"{r['p_better']:10.1%}  {r['mean_gain']:+.3f} +- {r['se']:.3f}" + columns)
+            for line in lines:
+                print(line)
+            if (name, d) in (getattr(res, 'until_from', None) or {}):       # the laps its until-stop offset was carried
+                dist = res.carried_distribution(name, d)
+                r['laps_carried'] = [float(x) for x in dist]
+                r['expected_laps_carried'] = res.expected_laps_carried(name, d)
+                top = sorted(range(len(dist)), key=lambda k: -dist[k])[:5]
+                print(f"    offset carried {r['expected_laps_carried']:.2f} laps on average; most likely: "
+                      + ', '.join(f'{k} laps {dist[k]:.1%}' for k in sorted(top) if dist[k] > 0))
+        _print_winners(res, row)
+        rows.append({k: row[k] for k in kind.get('row_keys', ROW_KEYS) if k in row})
+    return dict({'baseline': base, 'n_simulations': res.n_simulations},
+                **(kind['document'](call) if 'document' in kind else {}), scenarios=rows)
+
+
+def run_what_if(args) -> int:
+    """The seven what-if commands, each a description in WHAT_IFS: 'title', the banner's first line over vars(args);
+    'call' (args) -> the predictor's arguments behind the fixture (a ValueError is the user's mistake); 'method', the
+    F1Predictor method; 'state': False where the command has no --state; 'table' (args, kind, call, result) -> the JSON
+    document, printing the table on its way (default: _scenario_table, whose own entries are listed there)."""
+    kind = WHAT_IFS[args.cmd]
+    takes_state = kind.get('state', True)
+    fixture = load_fixture(args)
+    if fixture is None:
+        return 2
+    state = load_state(args.state) if takes_state and args.state else None
+    try:
+        call = kind['call'](args)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    print(f"\n{'=' * 60}\n{kind['title'].format(**vars(args))}")
+    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
+          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
+          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
+    print('=' * 60 + '\n')
+    try:
+        res = getattr(F1Predictor(device=args.device), kind['method'])(
+            args.season, args.race, fixture, *call, **({'state': state} if takes_state else {}),
+            n_simulations=args.simulations, seed=args.seed, allow_single_compound=args.allow_single_compound)
+    except ValueError as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    doc = kind.get('table', _scenario_table)(args, kind, call, res)
     if args.json:
         with open(args.json, 'w') as f:
-            json.dump({'driver': d, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
+            json.dump(doc, f)
     return 0
 
 
@@ -513,98 +596,66 @@ def penalty_scenarios(gives, driver=None, plans=()):
     return penalties, strategies
 
 
-def cmd_penalty(args) -> int:
-    from .simulation import RaceState
-    fixture = synthetic_fixture()
-    if args.fixture:
-        with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
-        return 2
-    state = None
-    if args.state:
-        with open(args.state) as f:
-            state = RaceState.from_json(json.load(f))
-    try:
-        penalties, strategies = penalty_scenarios(args.give, args.driver, args.plan)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    print(f"\n{'=' * 60}\nF1 Time Penalties: {args.season} {args.race}")
-    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
-          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
-          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
-    print('=' * 60 + '\n')
-    try:
-        res = F1Predictor(device=args.device).predict_penalties(args.season, args.race, fixture, penalties, strategies,
-                                                                state=state, n_simulations=args.simulations,
-                                                                seed=args.seed,
-                                                                allow_single_compound=args.allow_single_compound)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    penalised = list(dict.fromkeys(p.driver for p in penalties['penalised']))
+def _penalty_table(args, kind, call, res) -> dict:
+    penalised = list(dict.fromkeys(p.driver for p in call[0]['penalised']))
     rows = []
     for name in res.names:
         print(f"scenario: {name}")
         print(f"  {'driver':8} {'win':>7} {'podium':>7} {'E[pos]':>7} {'P(better)':>10} {'P(worse)':>9}  gain +- SE"
               f"       served  at flag  retired")
-        epos = res.expected_position(name)
-        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
-                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
-                   expected_position=epos, drivers={})
+        row = _scenario_row(res, name)
         for d in penalised:
-            c, f = res.compare(name, d), res.fate_probabilities(name, d)
-            row['drivers'][d] = dict(win=row['win_probabilities'][d], podium=row['podium_probabilities'][d],
-                                     expected_position=epos[d], p_better=c['p_better'], p_same=c['p_same'],
-                                     p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'], fate=f)
-            print(f"  {d[:8]:8} {row['win_probabilities'][d]:7.1%} {row['podium_probabilities'][d]:7.1%} {epos[d]:7.2f} "
-                  f"{c['p_better']:10.1%} {c['p_worse']:9.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}  "
+            f = res.fate_probabilities(name, d)
+            r = row['drivers'][d] = dict(win=row['win_probabilities'][d], podium=row['podium_probabilities'][d],
+                                         expected_position=row['expected_position'][d], **_compared(res, name, d), fate=f)
+            print(f"  {d[:8]:8} {r['win']:7.1%} {r['podium']:7.1%} {r['expected_position']:7.2f} "
+                  f"{r['p_better']:10.1%} {r['p_worse']:9.1%}  {r['mean_gain']:+.3f} +- {r['se']:.3f}  "
                   f"{f['served']:7.1%} {f['at_flag']:8.1%} {f['retired']:8.1%}")
-        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
-        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
+        _print_winners(res, row)
         rows.append(row)
-    if args.json:
-        with open(args.json, 'w') as f:
-            json.dump({'penalised': penalised, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
-    return 0
+    return {'penalised': penalised, 'n_simulations': res.n_simulations, 'scenarios': rows}
 
 
 EVENT_BASELINE = 'as drawn'
 
 
+def _parse_word_at_laps(flag: str, word: str, words: tuple, text: str):
+    """NAME=WORD@LAP[-LAP], WORD one of `words` in either case -> (NAME, word, first lap, last lap or None); `word` is what
+    the flag's usage calls it."""
+    name, sep, rest = text.partition('=')
+    if not sep or not name.strip():
+        raise ValueError(f'{flag} {text!r}: expected NAME={word}@LAP[-LAP]')
+    what, at, laps = rest.partition('@')
+    what = what.strip().lower()
+    if what not in words:
+        raise ValueError(f"{flag} {text!r}: {word} is {', '.join(map(repr, words[:-1]))} or {words[-1]!r}, got {what!r}")
+    a, dash, b = laps.partition('-')
+    if not at or not a.strip().isdigit() or (dash and not b.strip().isdigit()):
+        raise ValueError(f'{flag} {text!r}: expected @LAP or @LAP-LAP after the {word.lower()}')
+    if dash and int(b) < int(a):
+        raise ValueError(f'{flag} {text!r}: the range runs backwards')
+    return name.strip(), what, int(a), int(b) if dash else None
+
+
 def parse_event(text: str):
     """--event NAME=KIND@LAP[-LAP] -> (NAME, RaceEvent)."""
     from .simulation import RaceEvent
-    name, sep, rest = text.partition('=')
-    if not sep or not name.strip():
-        raise ValueError(f'--event {text!r}: expected NAME=KIND@LAP[-LAP]')
-    kind, at, laps = rest.partition('@')
-    kind = kind.strip().lower()
-    if kind not in ('sc', 'vsc', 'red', 'none'):
-        raise ValueError(f"--event {text!r}: KIND is 'sc', 'vsc', 'red' or 'none', got {kind!r}")
-    a, dash, b = laps.partition('-')
-    if not at or not a.strip().isdigit() or (dash and not b.strip().isdigit()):
-        raise ValueError(f'--event {text!r}: expected @LAP or @LAP-LAP after the kind')
-    lo, hi = int(a), int(b) if dash else int(a)
-    if hi < lo:
-        raise ValueError(f'--event {text!r}: the range runs backwards')
-    return name.strip(), RaceEvent(kind, lo, hi if dash else None)
+    name, kind, lo, hi = _parse_word_at_laps('--event', 'KIND', ('sc', 'vsc', 'red', 'none'), text)
+    return name, RaceEvent(kind, lo, hi)
 
 
-def event_scenarios(events, driver=None, plans=()):
-    """The events command's scenarios -> (events, strategies): 'as drawn' (no override, no plan) first, unless the user
-    names a scenario 'as drawn' themselves (then theirs, wherever it stands, is moved to the front); then one scenario
-    per NAME, holding every --event of that NAME and the --plan of that NAME."""
-    if not events:
-        raise ValueError('give at least one --event NAME=KIND@LAP[-LAP]')
+def _named_scenarios(baseline: str, usage: str, parse, items, driver, plans):
+    """event_scenarios, weather_scenarios and pace_scenarios -> ({NAME: [item]}, strategies): `baseline` (no item, no plan)
+    first, unless the user names a scenario so themselves (then theirs, wherever it stands, is the first); then one
+    scenario per NAME, holding every item of that NAME and the --plan of that NAME."""
+    if not items:
+        raise ValueError(f'give at least one {usage}')
     if plans and not driver:
         raise ValueError('--plan needs --driver')
-    out, strategies = {EVENT_BASELINE: []}, {}
-    for text in events:
-        name, ev = parse_event(text)
-        out.setdefault(name, []).append(ev)
+    out, strategies = {baseline: []}, {}
+    for text in items:
+        name, item = parse(text)
+        out.setdefault(name, []).append(item)
     for text in plans or ():
         name, plan = parse_plan(text, driver)
         if name in strategies:
@@ -614,64 +665,16 @@ def event_scenarios(events, driver=None, plans=()):
     return out, strategies
 
 
-def cmd_events(args) -> int:
-    from .simulation import RaceState
-    fixture = synthetic_fixture()
-    if args.fixture:
-        with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
-        return 2
-    state = None
-    if args.state:
-        with open(args.state) as f:
-            state = RaceState.from_json(json.load(f))
-    try:
-        events, strategies = event_scenarios(args.event, args.driver, args.plan)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    print(f"\n{'=' * 60}\nF1 Event Scenarios: {args.season} {args.race}")
-    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
-          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
-          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
-    print('=' * 60 + '\n')
-    try:
-        res = F1Predictor(device=args.device).predict_events(args.season, args.race, fixture, events, strategies,
-                                                             state=state, n_simulations=args.simulations, seed=args.seed,
-                                                             allow_single_compound=args.allow_single_compound)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    base = res.names[0]
-    shown = [args.driver] if args.driver else sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
-    rows = []
-    for name in res.names:
-        ee = res.expected_events(name)
-        print(f"scenario: {name}   (laps with: safety car {ee['sc']:.2f}, VSC {ee['vsc']:.2f}, red flag {ee['red']:.2f})")
-        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'P(better)':>10}  gain +- SE")
-        epos = res.expected_position(name)
-        row = dict(scenario=name, expected_events=ee,
-                   win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
-                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
-                   expected_position=epos, drivers={})
-        for d in shown:
-            c = res.compare(name, d)
-            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
-            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
-            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
-                                     p_better=c['p_better'], p_same=c['p_same'], p_worse=c['p_worse'],
-                                     mean_gain=c['mean_gain'], se=c['se'])
-            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {c['p_better']:10.1%}  "
-                  f"{c['mean_gain']:+.3f} +- {c['se']:.3f}")
-        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
-        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
-        rows.append(row)
-    if args.json:
-        with open(args.json, 'w') as f:
-            json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
-    return 0
+def event_scenarios(events, driver=None, plans=()):
+    """The events command's scenarios -> (events, strategies): 'as drawn' (no override, no plan) first, unless the user
+    names a scenario 'as drawn' themselves (then theirs, wherever it stands, is moved to the front); then one scenario
+    per NAME, holding every --event of that NAME and the --plan of that NAME."""
+    return _named_scenarios(EVENT_BASELINE, '--event NAME=KIND@LAP[-LAP]', parse_event, events, driver, plans)
+
+
+def _event_laps(res, name, call=None):
+    ee = res.expected_events(name)
+    return f"   (laps with: safety car {ee['sc']:.2f}, VSC {ee['vsc']:.2f}, red flag {ee['red']:.2f})", {'expected_events': ee}
 
 
 WEATHER_BASELINE = 'as forecast'
@@ -680,20 +683,8 @@ WEATHER_BASELINE = 'as forecast'
 def parse_change(text: str):
     """--change NAME=CONDITION@LAP[-LAP] -> (NAME, TrackChange)."""
     from .simulation import TrackChange
-    name, sep, rest = text.partition('=')
-    if not sep or not name.strip():
-        raise ValueError(f'--change {text!r}: expected NAME=CONDITION@LAP[-LAP]')
-    cond, at, laps = rest.partition('@')
-    cond = cond.strip().lower()
-    if cond not in ('dry', 'damp', 'wet'):
-        raise ValueError(f"--change {text!r}: CONDITION is 'dry', 'damp' or 'wet', got {cond!r}")
-    a, dash, b = laps.partition('-')
-    if not at or not a.strip().isdigit() or (dash and not b.strip().isdigit()):
-        raise ValueError(f'--change {text!r}: expected @LAP or @LAP-LAP after the condition')
-    lo, hi = int(a), int(b) if dash else int(a)
-    if hi < lo:
-        raise ValueError(f'--change {text!r}: the range runs backwards')
-    return name.strip(), TrackChange(lo, hi, cond)
+    name, cond, lo, hi = _parse_word_at_laps('--change', 'CONDITION', ('dry', 'damp', 'wet'), text)
+    return name, TrackChange(lo, lo if hi is None else hi, cond)
 
 
 def parse_wrong_tyre(items):
@@ -725,85 +716,13 @@ def weather_scenarios(changes, driver=None, plans=()):
     """The weather command's scenarios -> (changes, strategies): 'as forecast' (no change, no plan) first, unless the user
     names a scenario 'as forecast' themselves; then one scenario per NAME, holding every --change of that NAME and the
     --plan of that NAME."""
-    if not changes:
-        raise ValueError('give at least one --change NAME=CONDITION@LAP[-LAP]')
-    if plans and not driver:
-        raise ValueError('--plan needs --driver')
-    out, strategies = {WEATHER_BASELINE: []}, {}
-    for text in changes:
-        name, ch = parse_change(text)
-        out.setdefault(name, []).append(ch)
-    for text in plans or ():
-        name, plan = parse_plan(text, driver)
-        if name in strategies:
-            raise ValueError(f'--plan: scenario {name!r} given twice')
-        out.setdefault(name, [])
-        strategies[name] = [plan]
-    return out, strategies
+    return _named_scenarios(WEATHER_BASELINE, '--change NAME=CONDITION@LAP[-LAP]', parse_change, changes, driver, plans)
 
 
-def cmd_weather(args) -> int:
-    from .simulation import RaceState
-    fixture = synthetic_fixture()
-    if args.fixture:
-        with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
-        return 2
-    state = None
-    if args.state:
-        with open(args.state) as f:
-            state = RaceState.from_json(json.load(f))
-    try:
-        changes, strategies = weather_scenarios(args.change, args.driver, args.plan)
-        model = parse_wrong_tyre(args.wrong_tyre)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    print(f"\n{'=' * 60}\nF1 Weather Scenarios: {args.season} {args.race}")
-    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
-          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
-          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
-    print('=' * 60 + '\n')
-    try:
-        res = F1Predictor(device=args.device).predict_weather(args.season, args.race, fixture, changes, strategies, model,
-                                                              state=state, n_simulations=args.simulations, seed=args.seed,
-                                                              allow_single_compound=args.allow_single_compound)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    base = res.names[0]
-    shown = [args.driver] if args.driver else sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
-    rows = []
-    for name in res.names:
-        print(f"scenario: {name}")
-        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'change':>7} {'P(better)':>10}"
-              f"  gain +- SE   wrong-tyre laps")
-        epos, epos0 = res.expected_position(name), res.expected_position(base)
-        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
-                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
-                   expected_position=epos, drivers={})
-        for d in shown:
-            c = res.compare(name, d)
-            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
-            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
-            wrong = res.expected_wrong_tyre_laps(name, d)
-            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
-                                     expected_position_change=epos[d] - epos0[d], p_better=c['p_better'],
-                                     p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'],
-                                     expected_wrong_tyre_laps=wrong,
-                                     wrong_tyre_laps=[float(x) for x in res.wrong_tyre_laps_distribution(name, d)])
-            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {epos[d] - epos0[d]:+7.2f} "
-                  f"{c['p_better']:10.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}   {wrong:.2f}")
-        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
-        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
-        rows.append(row)
-    if args.json:
-        with open(args.json, 'w') as f:
-            json.dump({'baseline': base, 'n_simulations': res.n_simulations,
-                       'wrong_tyre_seconds': [[float(x) for x in r] for r in model.table()], 'scenarios': rows}, f)
-    return 0
+def _wrong_tyre_laps(res, name, d, call):
+    wrong = res.expected_wrong_tyre_laps(name, d)
+    return dict(expected_wrong_tyre_laps=wrong,
+                wrong_tyre_laps=[float(x) for x in res.wrong_tyre_laps_distribution(name, d)]), f"   {wrong:.2f}", []
 
 
 GRID_BASELINE = 'forecast grid'
@@ -903,59 +822,13 @@ def grid_scenarios(drops=(), pins=(), pit_lanes=(), plans=()):
     return out, strategies
 
 
-def cmd_grid(args) -> int:
-    fixture = synthetic_fixture()
-    if args.fixture:
-        with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
-        return 2
-    try:
-        edits, strategies = grid_scenarios(args.drop, args.pin, args.pit_lane, args.plan)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    print(f"\n{'=' * 60}\nF1 Grid Scenarios: {args.season} {args.race}")
-    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
-          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}")
-    print('=' * 60 + '\n')
-    try:
-        res = F1Predictor(device=args.device).predict_grids(args.season, args.race, fixture, edits, strategies,
-                                                            n_simulations=args.simulations, seed=args.seed,
-                                                            allow_single_compound=args.allow_single_compound)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    base = res.names[0]
-    shown = [args.driver] if args.driver else sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
-    rows = []
-    for name in res.names:
-        print(f"scenario: {name}" + (''.join(f'  [{e}]' for e in edits.get(name, []))))
-        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'change':>7} {'P(better)':>10}"
-              f"  gain +- SE   E[start]  places gained")
-        epos, epos0, estart = res.expected_position(name), res.expected_position(base), res.expected_start(name)
-        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
-                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
-                   expected_position=epos, expected_start=estart, drivers={})
-        for d in shown:
-            c = res.compare(name, d)
-            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
-            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
-            gained = res.expected_places_gained(name, d)
-            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
-                                     expected_position_change=epos[d] - epos0[d], p_better=c['p_better'],
-                                     p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'],
-                                     expected_start=estart[d], expected_places_gained=gained)
-            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {epos[d] - epos0[d]:+7.2f} "
-                  f"{c['p_better']:10.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}   {estart[d]:8.2f}  {gained:+.2f}")
-        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
-        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
-        rows.append(row)
-    if args.json:
-        with open(args.json, 'w') as f:
-            json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
-    return 0
+def _grid_edits(res, name, call):
+    return ''.join(f'  [{e}]' for e in call[0].get(name, [])), {'expected_start': res.expected_start(name)}
+
+
+def _grid_start(res, name, d, call):
+    start, gained = res.expected_start(name)[d], res.expected_places_gained(name, d)
+    return dict(expected_start=start, expected_places_gained=gained), f"   {start:8.2f}  {gained:+.2f}", []
 
 
 PACE_BASELINE = 'as is'
@@ -994,87 +867,8 @@ def pace_scenarios(offsets, driver=None, plans=()):
     """The pace command's scenarios -> (paces, strategies): 'as is' (no offset, no plan) first, unless the user names a
     scenario 'as is' themselves; then one scenario per NAME, holding every --offset of that NAME and the --plan of that
     NAME."""
-    if not offsets:
-        raise ValueError('give at least one --offset NAME=DRIVER:SECONDS@LAP-LAP or NAME=DRIVER:SECONDS@LAP+')
-    if plans and not driver:
-        raise ValueError('--plan needs --driver')
-    out, strategies = {PACE_BASELINE: []}, {}
-    for text in offsets:
-        name, off = parse_offset(text)
-        out.setdefault(name, []).append(off)
-    for text in plans or ():
-        name, plan = parse_plan(text, driver)
-        if name in strategies:
-            raise ValueError(f'--plan: scenario {name!r} given twice')
-        out.setdefault(name, [])
-        strategies[name] = [plan]
-    return out, strategies
-
-
-def cmd_pace(args) -> int:
-    from .simulation import RaceState
-    fixture = synthetic_fixture()
-    if args.fixture:
-        with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
-        return 2
-    state = None
-    if args.state:
-        with open(args.state) as f:
-            state = RaceState.from_json(json.load(f))
-    try:
-        paces, strategies = pace_scenarios(args.offset, args.driver, args.plan)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    print(f"\n{'=' * 60}\nF1 Pace Scenarios: {args.season} {args.race}")
-    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
-          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
-          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
-    print('=' * 60 + '\n')
-    try:
-        res = F1Predictor(device=args.device).predict_paces(args.season, args.race, fixture, paces, strategies,
-                                                            state=state, n_simulations=args.simulations, seed=args.seed,
-                                                            allow_single_compound=args.allow_single_compound)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    base = res.names[0]
-    shown = [args.driver] if args.driver else sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
-    rows = []
-    for name in res.names:
-        print(f"scenario: {name}")
-        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'change':>7} {'P(better)':>10}"
-              f"  gain +- SE")
-        epos, epos0 = res.expected_position(name), res.expected_position(base)
-        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
-                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers},
-                   expected_position=epos, drivers={})
-        for d in shown:
-            c = res.compare(name, d)
-            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
-            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
-            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
-                                     expected_position_change=epos[d] - epos0[d], p_better=c['p_better'],
-                                     p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'])
-            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {epos[d] - epos0[d]:+7.2f} "
-                  f"{c['p_better']:10.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}")
-            if (name, d) in (res.until_from or {}):         # the laps its until-stop offset was carried
-                dist = res.carried_distribution(name, d)
-                row['drivers'][d]['laps_carried'] = [float(x) for x in dist]
-                row['drivers'][d]['expected_laps_carried'] = res.expected_laps_carried(name, d)
-                top = sorted(range(len(dist)), key=lambda k: -dist[k])[:5]
-                print(f"    offset carried {row['drivers'][d]['expected_laps_carried']:.2f} laps on average; most likely: "
-                      + ', '.join(f'{k} laps {dist[k]:.1%}' for k in sorted(top) if dist[k] > 0))
-        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
-        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
-        rows.append(row)
-    if args.json:
-        with open(args.json, 'w') as f:
-            json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
-    return 0
+    return _named_scenarios(PACE_BASELINE, '--offset NAME=DRIVER:SECONDS@LAP-LAP or NAME=DRIVER:SECONDS@LAP+', parse_offset,
+                            offsets, driver, plans)
 
 
 WHAT_IF_BASELINE = 'as drawn'
@@ -1125,84 +919,52 @@ def what_if_scenarios(driver=None, plans=(), window=None, gives=(), events=(), o
     return out
 
 
-def cmd_what_if(args) -> int:
-    from .simulation import RaceState
-    fixture = synthetic_fixture()
-    if args.fixture:
-        with open(args.fixture) as f:
-            fixture = json.load(f)
-    elif not args.offline:
-        print('error: live FastF1 data is not available in this build; use --offline or --fixture FILE', file=sys.stderr)
-        return 2
-    state = None
-    if args.state:
-        with open(args.state) as f:
-            state = RaceState.from_json(json.load(f))
-    try:
-        scenarios = what_if_scenarios(args.driver, args.plan, args.window, args.give, args.event, args.offset)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    print(f"\n{'=' * 60}\nF1 What-If Scenarios: {args.season} {args.race}")
-    print(f"Simulations: {args.simulations}  seed: {args.seed}  data: "
-          f"{'synthetic fixture' if fixture.get('synthetic') else args.fixture}"
-          + (f"  from: {args.state} (after lap {state.lap})" if state else ''))
-    print('=' * 60 + '\n')
-    try:
-        res = F1Predictor(device=args.device).predict_combined(args.season, args.race, fixture, scenarios, state=state,
-                                                               n_simulations=args.simulations, seed=args.seed,
-                                                               allow_single_compound=args.allow_single_compound)
-    except ValueError as e:
-        print(f'error: {e}', file=sys.stderr)
-        return 2
-    base = res.names[0]
-    # --driver, then every driver an item names, in the order given; without either the five likeliest winners
-    named = ([args.driver] if args.driver else []) + [x.driver for sc in scenarios.values()
+def _what_if_shown(args, call, res):
+    """--driver, then every driver an item names, in the order given."""
+    named = ([args.driver] if args.driver else []) + [x.driver for sc in call[0].values()
                                                       for k in ('penalties', 'paces') for x in sc[k]]
-    shown = list(dict.fromkeys(d for d in named if d in res.drivers)) \
-        or sorted(res.drivers, key=lambda x: -res.win_probability(base, x))[:5]
-    rows = []
-    for name in res.names:
-        sc = scenarios.get(name, {})
-        head = f"scenario: {name}"
-        row = dict(scenario=name, win_probabilities={x: res.win_probability(name, x) for x in res.drivers},
-                   podium_probabilities={x: res.podium_probability(name, x) for x in res.drivers}, drivers={})
-        if sc.get('events'):
-            ee = row['expected_events'] = res.expected_events(name)
-            head += f"   (laps with: safety car {ee['sc']:.2f}, VSC {ee['vsc']:.2f}, red flag {ee['red']:.2f})"
-        print(head)
-        print(f"  {'driver':8} {'win':>7} {'change':>8} {'podium':>7} {'change':>8} {'E[pos]':>7} {'change':>7} {'P(better)':>10}"
-              f"  gain +- SE")
-        epos, epos0 = res.expected_position(name), res.expected_position(base)
-        row['expected_position'] = epos
-        serving = {p.driver for p in sc.get('penalties', ()) if p.kind == 'serve'}
-        for d in shown:
-            c = res.compare(name, d)
-            win, pod = row['win_probabilities'][d], row['podium_probabilities'][d]
-            dwin, dpod = win - res.win_probability(base, d), pod - res.podium_probability(base, d)
-            row['drivers'][d] = dict(win=win, win_change=dwin, podium=pod, podium_change=dpod, expected_position=epos[d],
-                                     expected_position_change=epos[d] - epos0[d], p_better=c['p_better'],
-                                     p_same=c['p_same'], p_worse=c['p_worse'], mean_gain=c['mean_gain'], se=c['se'])
-            print(f"  {d[:8]:8} {win:7.1%} {dwin:+8.1%} {pod:7.1%} {dpod:+8.1%} {epos[d]:7.2f} {epos[d] - epos0[d]:+7.2f} "
-                  f"{c['p_better']:10.1%}  {c['mean_gain']:+.3f} +- {c['se']:.3f}")
-            if d in serving:                                # the fate of its penalty to serve
-                f = row['drivers'][d]['fate'] = res.fate_probabilities(name, d)
-                print(f"    penalty served at a stop {f['served']:.1%}, added at the flag {f['at_flag']:.1%}, "
-                      f"retired unserved {f['retired']:.1%}")
-            if (name, d) in (res.until_from or {}):         # the laps its until-stop offset was carried
-                dist = res.carried_distribution(name, d)
-                row['drivers'][d]['laps_carried'] = [float(x) for x in dist]
-                row['drivers'][d]['expected_laps_carried'] = res.expected_laps_carried(name, d)
-                top = sorted(range(len(dist)), key=lambda k: -dist[k])[:5]
-                print(f"    offset carried {row['drivers'][d]['expected_laps_carried']:.2f} laps on average; most likely: "
-                      + ', '.join(f'{k} laps {dist[k]:.1%}' for k in sorted(top) if dist[k] > 0))
-        lead = sorted(res.drivers, key=lambda x: -row['win_probabilities'][x])[:3]
-        print('  most likely winners: ' + ', '.join(f"{x} {row['win_probabilities'][x]:.1%}" for x in lead) + '\n')
-        rows.append(row)
-    if args.json:
-        with open(args.json, 'w') as f:
-            json.dump({'baseline': base, 'n_simulations': res.n_simulations, 'scenarios': rows}, f)
-    return 0
+    return list(dict.fromkeys(d for d in named if d in res.drivers))
+
+
+def _what_if_event_laps(res, name, call):
+    return _event_laps(res, name) if call[0].get(name, {}).get('events') else ('', {})
+
+
+def _what_if_fate(res, name, d, call):
+    """The fate of the driver's penalty to serve, if the scenario gives it one."""
+    if not any(p.driver == d and p.kind == 'serve' for p in call[0].get(name, {}).get('penalties', ())):
+        return {}, '', []
+    f = res.fate_probabilities(name, d)
+    return {'fate': f}, '', [f"    penalty served at a stop {f['served']:.1%}, added at the flag {f['at_flag']:.1%}, "
+                             f"retired unserved {f['retired']:.1%}"]
+
+
+WHAT_IFS = {
+    'strategy': dict(title='F1 Pit Strategy: {season} {race}, {driver}', method='predict_strategies', call=_strategy_call,
+                     table=_strategy_table),
+    'penalty': dict(title='F1 Time Penalties: {season} {race}', method='predict_penalties', table=_penalty_table,
+                    call=lambda args: penalty_scenarios(args.give, args.driver, args.plan)),
+    'events': dict(title='F1 Event Scenarios: {season} {race}', method='predict_events',
+                   call=lambda args: event_scenarios(args.event, args.driver, args.plan), scenario=_event_laps,
+                   position_change=False, row_keys=('scenario', 'expected_events') + ROW_KEYS[1:]),
+    'pace': dict(title='F1 Pace Scenarios: {season} {race}', method='predict_paces',
+                 call=lambda args: pace_scenarios(args.offset, args.driver, args.plan)),
+    'weather': dict(title='F1 Weather Scenarios: {season} {race}', method='predict_weather',
+                    call=lambda args: weather_scenarios(args.change, args.driver, args.plan)
+                    + (parse_wrong_tyre(args.wrong_tyre),),
+                    driver=_wrong_tyre_laps, columns='   wrong-tyre laps',
+                    document=lambda call: {'wrong_tyre_seconds': [[float(x) for x in r] for r in call[2].table()]}),
+    'grid': dict(title='F1 Grid Scenarios: {season} {race}', method='predict_grids', state=False,
+                 call=lambda args: grid_scenarios(args.drop, args.pin, args.pit_lane, args.plan), scenario=_grid_edits,
+                 driver=_grid_start, columns='   E[start]  places gained',
+                 row_keys=ROW_KEYS[:-1] + ('expected_start', 'drivers')),
+    'what-if': dict(title='F1 What-If Scenarios: {season} {race}', method='predict_combined',
+                    call=lambda args: (what_if_scenarios(args.driver, args.plan, args.window, args.give, args.event,
+                                                         args.offset),),
+                    shown=_what_if_shown, scenario=_what_if_event_laps, driver=_what_if_fate,
+                    row_keys=('scenario', 'win_probabilities', 'podium_probabilities', 'drivers', 'expected_events',
+                              'expected_position')),
+}
 
 
 def load_results(season: int) -> list:
@@ -1457,9 +1219,7 @@ def cmd_championship(args) -> int:
     state = None
     if args.state:
         # round --from-round is under way: it resumes from the state, in the field's own driver order
-        from .simulation import RaceState
-        with open(args.state) as f:
-            state = RaceState.from_json(json.load(f))
+        state = load_state(args.state)
         live['drivers'] = [str(d) for d in races[0]['grid_probs']]
         races[0] = {k: v for k, v in races[0].items() if k not in ('grid_probs', 'fastest_lap_points', 'fastest_lap_within')}
         races[0]['state'] = state
@@ -1573,24 +1333,39 @@ def _print_title_needs(driver, rows, round_no, race):
               + '  '.join(f'{e} {v * 100:.1f}%' for e, v in rivals))
 
 
-def main(argv=None) -> int:
-    ap = argparse.ArgumentParser(prog='monte_carlo_gp_amd', description='F1 race prediction on MI355X')
-    sub = ap.add_subparsers(dest='cmd', required=True)
-    p = sub.add_parser('predict', help='predict one race weekend (main.py of the reference)')
+def _add_race_arguments(p) -> None:
     p.add_argument('--season', type=int, default=2025)
     p.add_argument('--race', type=str, required=True)
-    p.add_argument('--prediction-point', type=str, default='fp2', choices=['fp1', 'fp2', 'fp3', 'quali', 'sprint'])
-    p.add_argument('--simulations', type=int, default=10000)
+
+
+def _add_run_arguments(p, simulations=100000) -> None:
+    p.add_argument('--simulations', type=int, default=simulations)
     p.add_argument('--seed', type=int, default=None)
     p.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
     p.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
     p.add_argument('--device', type=int, default=0)
     p.add_argument('--json', type=str, default=None)
-    p.add_argument('--matchups', action='store_true',
-                   help='also count teammate head-to-heads and the most likely podiums (and add them to --json)')
-    p.add_argument('--trace', action='store_true',
-                   help='also count the race lap by lap: leader, laps led, fastest lap, pit stops, safety cars '
-                        '(and add them to --json)')
+
+
+def _what_if_parser(sub, name, text):
+    """The subparser of a what-if command (WHAT_IFS[name]) with the arguments in front of its own."""
+    t = sub.add_parser(name, help=text)
+    _add_race_arguments(t)
+    t.set_defaults(fn=run_what_if)
+    return t
+
+
+def _add_what_if_arguments(t, state=True, single_compound='run plans that use one dry compound (the two-compound rule is '
+                                                          'otherwise enforced)') -> None:
+    """The arguments behind a what-if command's own."""
+    if state:
+        t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
+    t.add_argument('--allow-single-compound', action='store_true', help=single_compound)
+    _add_run_arguments(t)
+
+
+def _add_analysis_arguments(p) -> None:
+    """The analysis flags predict and in-race share."""
     p.add_argument('--gaps', action='store_true',
                    help='also count time gaps: winning margin, gap to the winner at the flag, named pairs (and add them '
                         'to --json)')
@@ -1607,6 +1382,21 @@ def main(argv=None) -> int:
     p.add_argument('--moves', action='store_true',
                    help='also count how the field moves: expected places gained, start gain, passes made and lost per '
                         'driver, on-track passes per race and the commonest pairs (and add them to --json)')
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog='monte_carlo_gp_amd', description='F1 race prediction on MI355X')
+    sub = ap.add_subparsers(dest='cmd', required=True)
+    p = sub.add_parser('predict', help='predict one race weekend (main.py of the reference)')
+    _add_race_arguments(p)
+    p.add_argument('--prediction-point', type=str, default='fp2', choices=['fp1', 'fp2', 'fp3', 'quali', 'sprint'])
+    _add_run_arguments(p, simulations=10000)
+    p.add_argument('--matchups', action='store_true',
+                   help='also count teammate head-to-heads and the most likely podiums (and add them to --json)')
+    p.add_argument('--trace', action='store_true',
+                   help='also count the race lap by lap: leader, laps led, fastest lap, pit stops, safety cars '
+                        '(and add them to --json)')
+    _add_analysis_arguments(p)
     p.set_defaults(fn=cmd_predict)
     b = sub.add_parser('backtest', help='sweep a season and score it (backtest.py of the reference)')
     b.add_argument('--seasons', type=int, nargs='+', default=[2024])
@@ -1648,91 +1438,35 @@ def main(argv=None) -> int:
                         '--from-round')
     c.set_defaults(fn=cmd_championship)
     r = sub.add_parser('in-race', help='win and podium odds from a mid-race state (one column per --state)')
-    r.add_argument('--season', type=int, default=2025)
-    r.add_argument('--race', type=str, required=True)
+    _add_race_arguments(r)
     r.add_argument('--state', type=str, action='append', required=True,
                    help='race state JSON (RaceState.to_json); repeat for scenarios run with common random numbers')
-    r.add_argument('--simulations', type=int, default=100000)
-    r.add_argument('--seed', type=int, default=None)
-    r.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
-    r.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
-    r.add_argument('--device', type=int, default=0)
-    r.add_argument('--json', type=str, default=None)
-    r.add_argument('--gaps', action='store_true',
-                   help='also count time gaps: winning margin, gap to the winner at the flag, named pairs (and add them '
-                        'to --json)')
-    r.add_argument('--gap-edges', type=str, default=None,
-                   help='with --gaps: the bin edges in seconds, comma-separated and increasing (default: 0.5 ... 120)')
-    r.add_argument('--gap-pair', type=str, action='append', default=None,
-                   help='with --gaps: a pair of drivers A:B whose gap is counted; repeat for more (at most 64)')
-    r.add_argument('--if', dest='conditions', metavar='TEXT', type=str, action='append', default=None,
-                   help="a condition evaluated inside every simulation, e.g. 'VER.wins & NOR.podium', 'sc>=1', 'LEC.pole': "
-                        'its probability and the odds given it (and in --json); repeat for more (at most 64)')
-    r.add_argument('--tyres', action='store_true',
-                   help="also count the model's tyre stints: stop-count odds, first-stop window, most likely compound "
-                        'sequence and win odds by stop count (and add them to --json)')
-    r.add_argument('--moves', action='store_true',
-                   help='also count how the field moves: expected places gained, start gain, passes made and lost per '
-                        'driver, on-track passes per race and the commonest pairs (and add them to --json)')
+    _add_run_arguments(r)
+    _add_analysis_arguments(r)
     r.set_defaults(fn=cmd_in_race)
-    t = sub.add_parser('strategy', help="compare pit strategies for one driver against the model's own stops")
-    t.add_argument('--season', type=int, default=2025)
-    t.add_argument('--race', type=str, required=True)
+    t = _what_if_parser(sub, 'strategy', "compare pit strategies for one driver against the model's own stops")
     t.add_argument('--driver', type=str, required=True)
     t.add_argument('--plan', type=str, action='append', default=[],
                    help='NAME=START:LAP/COMP,LAP/COMP (START empty: the model\'s start); repeat for more scenarios')
     t.add_argument('--window', type=str, default=None, help='A-B/COMP: one single-stop scenario per lap A..B')
-    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
-    t.add_argument('--allow-single-compound', action='store_true',
-                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
-    t.add_argument('--simulations', type=int, default=100000)
-    t.add_argument('--seed', type=int, default=None)
-    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
-    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
-    t.add_argument('--device', type=int, default=0)
-    t.add_argument('--json', type=str, default=None)
-    t.set_defaults(fn=cmd_strategy)
-    t = sub.add_parser('penalty', help='race odds under time penalties, served in the pits or added at the flag')
-    t.add_argument('--season', type=int, default=2025)
-    t.add_argument('--race', type=str, required=True)
+    _add_what_if_arguments(t)
+    t = _what_if_parser(sub, 'penalty', 'race odds under time penalties, served in the pits or added at the flag')
     t.add_argument('--give', type=str, action='append', default=[],
                    help="DRIVER:SECONDS[:serve|flag|lap][@LAP]: 'serve' (default) is served at the car's first stop from "
                         "LAP on, else added at the flag; 'flag' is added at the flag; 'lap' is lost on LAP; repeat for more")
     t.add_argument('--driver', type=str, default=None, help='the driver whose --plan scenarios are compared')
     t.add_argument('--plan', type=str, action='append', default=[],
                    help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's: one scenario 'penalised + NAME' each")
-    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
-    t.add_argument('--allow-single-compound', action='store_true',
-                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
-    t.add_argument('--simulations', type=int, default=100000)
-    t.add_argument('--seed', type=int, default=None)
-    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
-    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
-    t.add_argument('--device', type=int, default=0)
-    t.add_argument('--json', type=str, default=None)
-    t.set_defaults(fn=cmd_penalty)
-    t = sub.add_parser('events', help='race odds with a safety car, VSC, red flag or no event on chosen laps')
-    t.add_argument('--season', type=int, default=2025)
-    t.add_argument('--race', type=str, required=True)
+    _add_what_if_arguments(t)
+    t = _what_if_parser(sub, 'events', 'race odds with a safety car, VSC, red flag or no event on chosen laps')
     t.add_argument('--event', type=str, action='append', default=[],
                    help="NAME=KIND@LAP[-LAP]: in scenario NAME the laps have KIND (sc, vsc, red, none) instead of their "
                         "draw; repeat for more; several of one NAME make one scenario")
     t.add_argument('--driver', type=str, default=None, help='the driver of the --plan scenarios, and the one shown')
     t.add_argument('--plan', type=str, action='append', default=[],
                    help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's; joins the --event scenario of that NAME")
-    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
-    t.add_argument('--allow-single-compound', action='store_true',
-                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
-    t.add_argument('--simulations', type=int, default=100000)
-    t.add_argument('--seed', type=int, default=None)
-    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
-    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
-    t.add_argument('--device', type=int, default=0)
-    t.add_argument('--json', type=str, default=None)
-    t.set_defaults(fn=cmd_events)
-    t = sub.add_parser('pace', help="race odds under lap-time offsets on chosen laps or until a car's next stop")
-    t.add_argument('--season', type=int, default=2025)
-    t.add_argument('--race', type=str, required=True)
+    _add_what_if_arguments(t)
+    t = _what_if_parser(sub, 'pace', "race odds under lap-time offsets on chosen laps or until a car's next stop")
     t.add_argument('--offset', type=str, action='append', default=[],
                    help="NAME=DRIVER:SECONDS@LAP-LAP or NAME=DRIVER:SECONDS@LAP+: in scenario NAME, SECONDS (negative = "
                         "faster) are added to DRIVER's base pace on the laps, or ('+') from LAP until the car's next stop; "
@@ -1740,19 +1474,8 @@ def main(argv=None) -> int:
     t.add_argument('--driver', type=str, default=None, help='the driver of the --plan scenarios, and the one shown')
     t.add_argument('--plan', type=str, action='append', default=[],
                    help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's; joins the --offset scenario of that NAME")
-    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
-    t.add_argument('--allow-single-compound', action='store_true',
-                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
-    t.add_argument('--simulations', type=int, default=100000)
-    t.add_argument('--seed', type=int, default=None)
-    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
-    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
-    t.add_argument('--device', type=int, default=0)
-    t.add_argument('--json', type=str, default=None)
-    t.set_defaults(fn=cmd_pace)
-    t = sub.add_parser('weather', help='race odds when the track condition changes on chosen laps')
-    t.add_argument('--season', type=int, default=2025)
-    t.add_argument('--race', type=str, required=True)
+    _add_what_if_arguments(t)
+    t = _what_if_parser(sub, 'weather', 'race odds when the track condition changes on chosen laps')
     t.add_argument('--change', type=str, action='append', default=[],
                    help="NAME=CONDITION@LAP[-LAP]: in scenario NAME the laps have CONDITION (dry, damp, wet) instead of the "
                         "race's; repeat for more; several of one NAME make one scenario")
@@ -1763,19 +1486,9 @@ def main(argv=None) -> int:
     t.add_argument('--wrong-tyre', type=str, action='append', default=[],
                    help="CONDITION:COMPOUND=SECONDS: seconds a lap on COMPOUND under CONDITION, replacing that cell of the "
                         "project's default table; repeat for more")
-    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
-    t.add_argument('--allow-single-compound', action='store_true',
-                   help='run plans that use one dry compound (the rule is otherwise enforced where the track stays dry)')
-    t.add_argument('--simulations', type=int, default=100000)
-    t.add_argument('--seed', type=int, default=None)
-    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
-    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
-    t.add_argument('--device', type=int, default=0)
-    t.add_argument('--json', type=str, default=None)
-    t.set_defaults(fn=cmd_weather)
-    t = sub.add_parser('grid', help='race odds under grid drops, pit-lane starts and pinned grid slots')
-    t.add_argument('--season', type=int, default=2025)
-    t.add_argument('--race', type=str, required=True)
+    _add_what_if_arguments(t, single_compound='run plans that use one dry compound (the rule is otherwise enforced where '
+                                              'the track stays dry)')
+    t = _what_if_parser(sub, 'grid', 'race odds under grid drops, pit-lane starts and pinned grid slots')
     t.add_argument('--drop', type=str, action='append', default=[],
                    help="NAME=DRIVER:PLACES: in scenario NAME the driver drops PLACES on the grid each simulation draws; PLACES "
                         "is a number, back, or a penalty name (engine, full_pu, gearbox, pitlane_start); repeat for more")
@@ -1788,18 +1501,9 @@ def main(argv=None) -> int:
     t.add_argument('--plan', type=str, action='append', default=[],
                    help="NAME=DRIVER:START[@AGE]:LAP/COMP,LAP/COMP: the strategy command's plan for DRIVER; joins the scenario "
                         "of that NAME")
-    t.add_argument('--allow-single-compound', action='store_true', help='run plans that use one dry compound')
-    t.add_argument('--simulations', type=int, default=100000)
-    t.add_argument('--seed', type=int, default=None)
-    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
-    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
-    t.add_argument('--device', type=int, default=0)
-    t.add_argument('--json', type=str, default=None)
-    t.set_defaults(fn=cmd_grid)
-    t = sub.add_parser('what-if', help='race odds under scenarios that mix pit plans, time penalties, race events and '
-                                       'lap-time offsets')
-    t.add_argument('--season', type=int, default=2025)
-    t.add_argument('--race', type=str, required=True)
+    _add_what_if_arguments(t, state=False, single_compound='run plans that use one dry compound')
+    t = _what_if_parser(sub, 'what-if', 'race odds under scenarios that mix pit plans, time penalties, race events and '
+                                        'lap-time offsets')
     t.add_argument('--event', type=str, action='append', default=[],
                    help="NAME=KIND@LAP[-LAP], as the events command's; items of one NAME make one scenario")
     t.add_argument('--give', type=str, action='append', default=[],
@@ -1812,16 +1516,7 @@ def main(argv=None) -> int:
                    help="NAME=START:LAP/COMP,LAP/COMP, as the strategy command's; joins the scenario of that NAME")
     t.add_argument('--window', type=str, default=None,
                    help='[NAME=]A-B/COMP: one scenario per lap A..B with the items of NAME and a single stop on that lap')
-    t.add_argument('--state', type=str, default=None, help='race state JSON (RaceState.to_json) to start from')
-    t.add_argument('--allow-single-compound', action='store_true',
-                   help='run plans that use one dry compound (the two-compound rule is otherwise enforced)')
-    t.add_argument('--simulations', type=int, default=100000)
-    t.add_argument('--seed', type=int, default=None)
-    t.add_argument('--offline', action='store_true', help='use the synthetic weekend fixture')
-    t.add_argument('--fixture', type=str, default=None, help='race fixture JSON (see predictor.py)')
-    t.add_argument('--device', type=int, default=0)
-    t.add_argument('--json', type=str, default=None)
-    t.set_defaults(fn=cmd_what_if)
+    _add_what_if_arguments(t)
     args = ap.parse_args(argv)
     return args.fn(args)
 

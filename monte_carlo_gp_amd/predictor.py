@@ -122,6 +122,16 @@ def actual_grid_probs(drivers, actual_grid: dict) -> dict:
     return out
 
 
+def _open_fixture(fixture, season, race) -> dict:
+    """The race fixture, read from its JSON file if `fixture` is a path; a weekend without drivers raises (:183-184)."""
+    if isinstance(fixture, str):
+        with open(fixture) as f:
+            fixture = json.load(f)
+    if not fixture.get('drivers'):
+        raise ValueError(f"No practice data available for {season} {race}")
+    return fixture
+
+
 class F1Predictor:
     """predict_weekend over a race fixture; the Monte Carlo step runs on the GPU."""
 
@@ -201,11 +211,7 @@ class F1Predictor:
         and the result gains 'moves', the block move_keys builds: per driver the expected places gained, the expected
         start gain and the passes made and lost, and for the race the expected on-track passes with their 10-90 % range
         and the commonest (a, b) pairs."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")       # :183-184
+        fixture = _open_fixture(fixture, season, race)
         inp = self.simulator_inputs(fixture, race, grid_penalties, circuit_info, prediction_point, actual_grid)
         sim = RaceSimulator(inp['config'], device=self.device)
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
@@ -244,11 +250,7 @@ class F1Predictor:
         state's dict gains 'tyres' from RaceSimulator.run_stints on that state, same simulations; stops count from the
         state's lap on.  moves (as in predict_weekend): every state's dict gains 'moves' from RaceSimulator.run_moves on
         that state, same simulations; passes count from the state's lap on and there is no start gain."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")
+        fixture = _open_fixture(fixture, season, race)
         single = not isinstance(state, (list, tuple))
         states = [state] if single else list(state)
         inp = self.simulator_inputs(fixture, race)
@@ -290,6 +292,17 @@ class F1Predictor:
                 res['moves'] = move_keys(mv)
         return out[0] if single else out
 
+    def _scenario_run(self, season, race, fixture, state, seed, prediction_point, allow_single_compound):
+        """What the seven scenario methods below share -> (simulator, the keyword arguments every run_* takes after its
+        scenarios): the weekend's race inputs as predict_weekend builds them, drawn from the grid unless a mid-race
+        `state` is given, in predict_weekend's driver order."""
+        inp = self.simulator_inputs(_open_fixture(fixture, season, race), race, prediction_point=prediction_point)
+        sim = RaceSimulator(inp['config'], device=self.device)
+        return sim, dict(base_pace=inp['base_pace'], tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
+                         driver_dnf_rates=inp['driver_dnf_rates'], grid_probs=inp['grid_probs'] if state is None else None,
+                         state=state, seed=seed, track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
+                         allow_single_compound=allow_single_compound)
+
     def predict_strategies(self, season: int, race: str, fixture: dict | str, strategies: dict, state=None,
                            n_simulations: int = 100000, seed: int | None = None, prediction_point: str = 'fp2',
                            allow_single_compound: bool = False):
@@ -298,17 +311,8 @@ class F1Predictor:
         RaceSimulator.run_strategies -- from the grid, or from a mid-race RaceState -- with common random numbers.  The
         driver order is predict_weekend's, so an empty scenario reproduces predict_weekend's (or predict_from_state's)
         race for the same seed.  Returns the StrategyResult."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")
-        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
-        sim = RaceSimulator(inp['config'], device=self.device)
-        return sim.run_strategies(n_simulations, strategies, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
-                                  inp['driver_dnf_rates'], grid_probs=inp['grid_probs'] if state is None else None,
-                                  state=state, seed=seed, track_condition=inp['track_condition'],
-                                  drivers=list(inp['grid_probs']), allow_single_compound=allow_single_compound)
+        sim, common = self._scenario_run(season, race, fixture, state, seed, prediction_point, allow_single_compound)
+        return sim.run_strategies(n_simulations, strategies, **common)
 
     def predict_penalties(self, season: int, race: str, fixture: dict | str, penalties: dict, strategies: dict | None = None,
                           state=None, n_simulations: int = 100000, seed: int | None = None,
@@ -317,18 +321,8 @@ class F1Predictor:
         each scenario of `penalties` ({name: [TimePenalty, ...]}) and `strategies` ({name: [PitPlan, ...]} or None).  A
         scenario without penalties or plans reproduces predict_weekend's (or predict_from_state's) race for the same
         seed.  Returns the PenaltyResult."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")
-        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
-        sim = RaceSimulator(inp['config'], device=self.device)
-        return sim.run_penalties(n_simulations, penalties, strategies, inp['base_pace'], inp['tire_deg'],
-                                 inp['driver_variance'], inp['driver_dnf_rates'],
-                                 grid_probs=inp['grid_probs'] if state is None else None, state=state, seed=seed,
-                                 track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
-                                 allow_single_compound=allow_single_compound)
+        sim, common = self._scenario_run(season, race, fixture, state, seed, prediction_point, allow_single_compound)
+        return sim.run_penalties(n_simulations, penalties, strategies, **common)
 
     def predict_events(self, season: int, race: str, fixture: dict | str, events: dict, strategies: dict | None = None,
                        state=None, n_simulations: int = 100000, seed: int | None = None,
@@ -337,18 +331,8 @@ class F1Predictor:
         each scenario of `events` ({name: [RaceEvent, ...]}) and `strategies` ({name: [PitPlan, ...]} or None).  A
         scenario without overrides or plans reproduces predict_weekend's (or predict_from_state's) race for the same
         seed.  Returns the EventResult."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")
-        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
-        sim = RaceSimulator(inp['config'], device=self.device)
-        return sim.run_events(n_simulations, events, strategies, inp['base_pace'], inp['tire_deg'],
-                              inp['driver_variance'], inp['driver_dnf_rates'],
-                              grid_probs=inp['grid_probs'] if state is None else None, state=state, seed=seed,
-                              track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
-                              allow_single_compound=allow_single_compound)
+        sim, common = self._scenario_run(season, race, fixture, state, seed, prediction_point, allow_single_compound)
+        return sim.run_events(n_simulations, events, strategies, **common)
 
     def predict_paces(self, season: int, race: str, fixture: dict | str, paces: dict, strategies: dict | None = None,
                       state=None, n_simulations: int = 100000, seed: int | None = None,
@@ -357,18 +341,8 @@ class F1Predictor:
         scenario of `paces` ({name: [PaceOffset, ...]}) and `strategies` ({name: [PitPlan, ...]} or None).  A scenario
         without offsets or plans reproduces predict_weekend's (or predict_from_state's) race for the same seed.  Returns
         the PaceResult."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")
-        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
-        sim = RaceSimulator(inp['config'], device=self.device)
-        return sim.run_paces(n_simulations, paces, strategies, inp['base_pace'], inp['tire_deg'],
-                             inp['driver_variance'], inp['driver_dnf_rates'],
-                             grid_probs=inp['grid_probs'] if state is None else None, state=state, seed=seed,
-                             track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
-                             allow_single_compound=allow_single_compound)
+        sim, common = self._scenario_run(season, race, fixture, state, seed, prediction_point, allow_single_compound)
+        return sim.run_paces(n_simulations, paces, strategies, **common)
 
     def predict_weather(self, season: int, race: str, fixture: dict | str, changes: dict, strategies: dict | None = None,
                         model=None, state=None, n_simulations: int = 100000, seed: int | None = None,
@@ -376,18 +350,8 @@ class F1Predictor:
         """Weather scenarios (not in the reference): predict_strategies' race run through RaceSimulator.run_weather under
         each scenario of `changes` ({name: [TrackChange, ...]}) and `strategies` ({name: [PitPlan, ...]} or None), with
         `model` (a WeatherModel, None: the project's default table).  Returns the WeatherResult."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")
-        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
-        sim = RaceSimulator(inp['config'], device=self.device)
-        return sim.run_weather(n_simulations, changes, strategies, model, inp['base_pace'], inp['tire_deg'],
-                               inp['driver_variance'], inp['driver_dnf_rates'],
-                               grid_probs=inp['grid_probs'] if state is None else None, state=state, seed=seed,
-                               track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
-                               allow_single_compound=allow_single_compound)
+        sim, common = self._scenario_run(season, race, fixture, state, seed, prediction_point, allow_single_compound)
+        return sim.run_weather(n_simulations, changes, strategies, model, **common)
 
     def predict_grids(self, season: int, race: str, fixture: dict | str, edits: dict, strategies: dict | None = None,
                       n_simulations: int = 100000, seed: int | None = None, prediction_point: str = 'fp2',
@@ -396,17 +360,8 @@ class F1Predictor:
         the run): predict_strategies' race run through RaceSimulator.run_grids under each scenario of `edits` ({name:
         [GridEdit, ...]}) and `strategies` ({name: [PitPlan, ...]} or None), paired by simulation.  A scenario without
         edits or plans reproduces predict_weekend's race for the same seed.  Returns the GridResult."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")
-        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
-        sim = RaceSimulator(inp['config'], device=self.device)
-        return sim.run_grids(n_simulations, edits, strategies, inp['base_pace'], inp['tire_deg'],
-                             inp['driver_variance'], inp['driver_dnf_rates'], grid_probs=inp['grid_probs'], seed=seed,
-                             track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
-                             allow_single_compound=allow_single_compound)
+        sim, common = self._scenario_run(season, race, fixture, None, seed, prediction_point, allow_single_compound)
+        return sim.run_grids(n_simulations, edits, strategies, **common)
 
     def predict_combined(self, season: int, race: str, fixture: dict | str, scenarios: dict, state=None,
                          n_simulations: int = 100000, seed: int | None = None, prediction_point: str = 'fp2',
@@ -415,17 +370,8 @@ class F1Predictor:
         RaceSimulator.run_combined under each scenario of `scenarios` ({name: {'plans': [PitPlan, ...], 'penalties':
         [TimePenalty, ...], 'events': [RaceEvent, ...], 'paces': [PaceOffset, ...]}}).  An empty scenario reproduces
         predict_weekend's (or predict_from_state's) race for the same seed.  Returns the CombinedResult."""
-        if isinstance(fixture, str):
-            with open(fixture) as f:
-                fixture = json.load(f)
-        if not fixture.get('drivers'):
-            raise ValueError(f"No practice data available for {season} {race}")
-        inp = self.simulator_inputs(fixture, race, prediction_point=prediction_point)
-        sim = RaceSimulator(inp['config'], device=self.device)
-        return sim.run_combined(n_simulations, scenarios, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
-                                inp['driver_dnf_rates'], grid_probs=inp['grid_probs'] if state is None else None,
-                                state=state, seed=seed, track_condition=inp['track_condition'],
-                                drivers=list(inp['grid_probs']), allow_single_compound=allow_single_compound)
+        sim, common = self._scenario_run(season, race, fixture, state, seed, prediction_point, allow_single_compound)
+        return sim.run_combined(n_simulations, scenarios, **common)
 
     @staticmethod
     def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace,

@@ -1,10 +1,10 @@
 """The `grid` command: flag parsing, scenario assembly, error messages and output with a stand-in predictor."""
 import json
 
-import numpy as np
 import pytest
 
-from monte_carlo_gp_amd import GridEdit, GridResult, PitPlan, cli
+from cli_cases import grid_result as _result
+from monte_carlo_gp_amd import GridEdit, PitPlan, cli
 
 
 def test_edit_parsing():
@@ -69,26 +69,6 @@ def test_scenario_assembly():
         cli.grid_scenarios(['x=VER:5'], [], ['x=VER'])
     with pytest.raises(ValueError, match="VER has a plan in scenario 'x' already"):
         cli.grid_scenarios(['x=VER:5'], plans=['x=VER::20/HARD', 'x=VER::21/HARD'])
-
-
-def _result(names):
-    hist = np.zeros((2, 3, 3), np.int64)
-    hist[0] = [[5, 3, 2], [3, 4, 3], [2, 3, 5]]
-    hist[1] = [[2, 3, 5], [5, 3, 2], [3, 4, 3]]
-    delta = np.zeros((2, 3, 5), np.int64)
-    delta[0, :, 2] = 10
-    delta[1, 0] = [0, 0, 4, 4, 2]
-    delta[1, 1] = [0, 3, 7, 0, 0]
-    delta[1, 2] = [0, 2, 8, 0, 0]
-    start = np.zeros((2, 3, 3), np.int64)
-    start[0] = [[6, 3, 1], [3, 5, 2], [1, 2, 7]]
-    start[1] = [[0, 0, 10], [7, 3, 0], [3, 7, 0]]
-    gain = np.zeros((2, 3, 5), np.int64)
-    gain[0, :, 2] = 10
-    gain[1, 0] = [0, 0, 5, 3, 2]
-    gain[1, 1] = [0, 2, 8, 0, 0]
-    gain[1, 2] = [1, 3, 6, 0, 0]
-    return GridResult(names=names, drivers=['A', 'B', 'C'], n_simulations=10, hist=hist, delta=delta, start=start, gain=gain)
 
 
 def test_grid_cli_with_a_stand_in_predictor(tmp_path, capsys, monkeypatch):

@@ -4,7 +4,8 @@ import json
 import numpy as np
 import pytest
 
-from monte_carlo_gp_amd import PitPlan, TrackChange, WeatherModel, WeatherResult, cli
+from cli_cases import weather_result as _result
+from monte_carlo_gp_amd import PitPlan, TrackChange, WeatherModel, cli
 
 
 def test_change_parsing():
@@ -50,21 +51,6 @@ def test_scenario_assembly():
         cli.weather_scenarios(['x=damp@2-3'], None, ['x=:31/HARD'])
     with pytest.raises(ValueError, match='twice'):
         cli.weather_scenarios(['x=damp@2-3'], 'NOR', ['x=:31/HARD', 'x=:32/HARD'])
-
-
-def _result(names):
-    hist = np.zeros((2, 3, 3), np.int64)
-    hist[0] = [[5, 3, 2], [3, 4, 3], [2, 3, 5]]
-    hist[1] = [[7, 2, 1], [2, 5, 3], [1, 3, 6]]
-    delta = np.zeros((2, 3, 5), np.int64)
-    delta[0, :, 2] = 10
-    delta[1, 0] = [1, 3, 5, 1, 0]
-    delta[1, 1] = [0, 1, 6, 3, 0]
-    delta[1, 2] = [0, 2, 7, 1, 0]
-    wrong = np.zeros((2, 3, 5), np.int64)
-    wrong[:, :, 0] = 10
-    wrong[1, 0] = [1, 4, 3, 2, 0]
-    return WeatherResult(names=names, drivers=['A', 'B', 'C'], n_simulations=10, hist=hist, delta=delta, wrong_laps=wrong)
 
 
 def test_weather_cli_with_a_stand_in_predictor(tmp_path, capsys, monkeypatch):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_py as O
+from cli_cases import combined_result as _result
 from monte_carlo_gp_amd import (CombinedResult, EventResult, PaceOffset, PaceResult, PenaltyResult, PitPlan, RaceConfig,
                                 RaceEvent, StrategyResult, TimePenalty, cli)
 from monte_carlo_gp_amd import _native as N
@@ -96,29 +97,6 @@ def test_run_combined_packs_each_table_behind_the_plans(monkeypatch):
     assert list(ev_count) == [0, 2, 0] and [(e.first_lap, e.last_lap) for e in evs] == [(31, 31), (32, 40)]
     assert list(pace_count) == [0, 1, 1]
     assert [(o.driver, o.kind, o.first_lap, o.last_lap) for o in offs] == [(1, N.PACE_UNTIL_STOP, 31, 0), (2, N.PACE_LAPS, 1, 3)]
-
-
-def _result():
-    """3 drivers, 2 scenarios, 10 simulations, 4 laps, hand-made."""
-    hist = np.zeros((2, 3, 3), np.int64)
-    hist[0] = [[5, 3, 2], [3, 4, 3], [2, 3, 5]]
-    hist[1] = [[7, 2, 1], [2, 5, 3], [1, 3, 6]]
-    delta = np.zeros((2, 3, 5), np.int64)
-    delta[0, :, 2] = 10
-    delta[1, 0] = [1, 3, 5, 1, 0]
-    delta[1, 1] = [0, 1, 6, 3, 0]
-    delta[1, 2] = [0, 2, 7, 1, 0]
-    fate = np.zeros((2, 3, 4), np.int64)
-    fate[:, :, 0] = 10
-    fate[1, 0] = [0, 7, 2, 1]
-    events = np.zeros((2, 3, 5), np.int64)
-    events[0] = [[9, 1, 0, 0, 0], [6, 3, 1, 0, 0], [8, 2, 0, 0, 0]]
-    events[1] = [[9, 1, 0, 0, 0], [0, 7, 2, 1, 0], [8, 2, 0, 0, 0]]
-    carried = np.zeros((2, 3, 5), np.int64)
-    carried[:, :, 0] = 10
-    carried[1, 1] = [1, 4, 3, 2, 0]
-    return CombinedResult(names=['as drawn', 'sc'], drivers=['A', 'B', 'C'], n_simulations=10, hist=hist, delta=delta,
-                          fate=fate, events=events, carried=carried, until_from={('sc', 'B'): 2})
 
 
 def test_combined_result_offers_what_its_three_siblings_offer():

@@ -11,6 +11,7 @@ import events_ref as ER
 import oracle_py as O
 import resume_ref as RR
 import strategy_ref as SR
+from cli_cases import event_result as _result
 from monte_carlo_gp_amd import EventResult, PitPlan, RaceConfig, RaceEvent, StrategyResult, cli
 from monte_carlo_gp_amd import _native as N
 from monte_carlo_gp_amd.simulation import DEFAULT_SET_POP, RaceSimulator, _Problem
@@ -195,23 +196,6 @@ def test_run_events_value_errors_and_scenario_names():
                        {'sc': [PitPlan(d[0], [(31, 'HARD')])], 'plan only': [PitPlan(d[1], [(25, 'HARD')])]}, *args, **kw)
     assert r.names == ['as drawn', 'sc', 'plan only'] and r.n_simulations == 0 and isinstance(r, EventResult)
     assert r.hist.shape == (3, 20, 20) and r.delta.shape == (3, 20, 39) and r.events.shape == (3, 3, L + 1)
-
-
-def _result():
-    """3 drivers, 2 scenarios, 10 simulations, 4 laps, hand-made (test_strategy_host's counts, with event counts)."""
-    hist = np.zeros((2, 3, 3), np.int64)
-    hist[0] = [[5, 3, 2], [3, 4, 3], [2, 3, 5]]
-    hist[1] = [[7, 2, 1], [2, 5, 3], [1, 3, 6]]
-    delta = np.zeros((2, 3, 5), np.int64)
-    delta[0, :, 2] = 10
-    delta[1, 0] = [1, 3, 5, 1, 0]
-    delta[1, 1] = [0, 1, 6, 3, 0]
-    delta[1, 2] = [0, 2, 7, 1, 0]
-    events = np.zeros((2, 3, 5), np.int64)
-    events[0] = [[9, 1, 0, 0, 0], [6, 3, 1, 0, 0], [10, 0, 0, 0, 0]]
-    events[1] = [[10, 0, 0, 0, 0], [0, 8, 2, 0, 0], [5, 5, 0, 0, 0]]
-    return EventResult(names=['as drawn', 'sc'], drivers=['A', 'B', 'C'], n_simulations=10, hist=hist, delta=delta,
-                       events=events)
 
 
 def test_event_result_helpers():

@@ -11,6 +11,7 @@ import oracle_py as O
 import paces_ref as PR
 import resume_ref as RR
 import strategy_ref as SR
+from cli_cases import pace_result as _result
 from monte_carlo_gp_amd import PaceOffset, PaceResult, PitPlan, RaceConfig, StrategyResult, cli
 from monte_carlo_gp_amd import _native as N
 from monte_carlo_gp_amd.simulation import DEFAULT_SET_POP, RaceSimulator, _Problem
@@ -222,24 +223,6 @@ def test_run_paces_value_errors_and_scenario_names():
     assert r.names == ['as is', 'damage', 'plan only'] and r.n_simulations == 0 and isinstance(r, PaceResult)
     assert r.hist.shape == (3, 20, 20) and r.delta.shape == (3, 20, 39) and r.carried.shape == (3, 20, L + 1)
     assert r.until_from == {('damage', d[0]): 1}
-
-
-def _result():
-    """3 drivers, 2 scenarios, 10 simulations, 4 laps, hand-made (test_strategy_host's counts, with laps carried): A's
-    until-stop offset of scenario 'damage' begins on lap 2."""
-    hist = np.zeros((2, 3, 3), np.int64)
-    hist[0] = [[5, 3, 2], [3, 4, 3], [2, 3, 5]]
-    hist[1] = [[7, 2, 1], [2, 5, 3], [1, 3, 6]]
-    delta = np.zeros((2, 3, 5), np.int64)
-    delta[0, :, 2] = 10
-    delta[1, 0] = [1, 3, 5, 1, 0]
-    delta[1, 1] = [0, 1, 6, 3, 0]
-    delta[1, 2] = [0, 2, 7, 1, 0]
-    carried = np.zeros((2, 3, 5), np.int64)
-    carried[:, :, 0] = 10
-    carried[1, 0] = [1, 4, 3, 2, 0]
-    return PaceResult(names=['as is', 'damage'], drivers=['A', 'B', 'C'], n_simulations=10, hist=hist, delta=delta,
-                      carried=carried, until_from={('damage', 'A'): 2})
 
 
 def test_pace_result_helpers():

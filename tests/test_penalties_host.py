@@ -12,6 +12,7 @@ import oracle_py as O
 import penalties_ref as PR
 import resume_ref as RR
 import strategy_ref as SR
+from cli_cases import penalty_result as _result
 from monte_carlo_gp_amd import PenaltyResult, PitPlan, RaceConfig, StrategyResult, TimePenalty, cli
 from monte_carlo_gp_amd import _native as N
 from monte_carlo_gp_amd.simulation import DEFAULT_SET_POP, RaceSimulator, _Problem
@@ -235,23 +236,6 @@ def test_two_penalties_of_one_kind_say_to_sum_them():
                           {'pen': [PitPlan(d[0], [(20, 'HARD')])], 'plan only': [PitPlan(d[1], [(25, 'HARD')])]}, *args, **kw)
     assert r.names == ['none', 'pen', 'plan only'] and r.n_simulations == 0
     assert r.hist.shape == (3, 20, 20) and r.delta.shape == (3, 20, 39) and r.fate.shape == (3, 20, 4)
-
-
-def _result():
-    """3 drivers, 2 scenarios, 10 simulations, hand-made (test_strategy_host's counts, with fates)."""
-    hist = np.zeros((2, 3, 3), np.int64)
-    hist[0] = [[5, 3, 2], [3, 4, 3], [2, 3, 5]]
-    hist[1] = [[7, 2, 1], [2, 5, 3], [1, 3, 6]]
-    delta = np.zeros((2, 3, 5), np.int64)
-    delta[0, :, 2] = 10
-    delta[1, 0] = [1, 3, 5, 1, 0]
-    delta[1, 1] = [0, 1, 6, 3, 0]
-    delta[1, 2] = [0, 2, 7, 1, 0]
-    fate = np.zeros((2, 3, 4), np.int64)
-    fate[0, :, 0] = 10
-    fate[1] = [[0, 6, 3, 1], [10, 0, 0, 0], [10, 0, 0, 0]]
-    return PenaltyResult(names=['none', 'penalised'], drivers=['A', 'B', 'C'], n_simulations=10, hist=hist, delta=delta,
-                         fate=fate)
 
 
 def test_penalty_result_helpers():

@@ -11,6 +11,7 @@ import pytest
 import oracle_py as O
 import resume_ref as RR
 import strategy_ref as SR
+from cli_cases import strategy_result as _result
 from monte_carlo_gp_amd import PitPlan, RaceConfig, StrategyResult, cli, pit_window
 from monte_carlo_gp_amd import _native as N
 from monte_carlo_gp_amd.simulation import DEFAULT_SET_POP, _Problem, check_two_compounds
@@ -223,19 +224,6 @@ def test_pit_window():
     assert w['VER L19'] == [PitPlan('VER', [(19, 'HARD'), (45, 'SOFT')], start='MEDIUM')]
 
 
-def _result():
-    """3 drivers, 2 scenarios, 10 simulations, hand-made."""
-    hist = np.zeros((2, 3, 3), np.int64)
-    hist[0] = [[5, 3, 2], [3, 4, 3], [2, 3, 5]]
-    hist[1] = [[7, 2, 1], [2, 5, 3], [1, 3, 6]]
-    delta = np.zeros((2, 3, 5), np.int64)
-    delta[0, :, 2] = 10
-    delta[1, 0] = [1, 3, 5, 1, 0]          # driver A: gains 2 once, 1 three times, same 5, loses 1 once
-    delta[1, 1] = [0, 1, 6, 3, 0]
-    delta[1, 2] = [0, 2, 7, 1, 0]
-    return StrategyResult(names=['model', 'early'], drivers=['A', 'B', 'C'], n_simulations=10, hist=hist, delta=delta)
-
-
 def test_strategy_result_helpers():
     r = _result()
     assert r.position_probabilities('early')['A'] == {1: 0.7, 2: 0.2, 3: 0.1}
@@ -316,3 +304,20 @@ def test_strategy_cli_with_a_stand_in_predictor(tmp_path, capsys, monkeypatch):
     assert rows[1]['win'] == pytest.approx(0.7) and rows[1]['p_better'] == pytest.approx(0.4)
     assert cli.main(['strategy', '--race', 'Bahrain', '--offline', '--driver', 'A']) == 2       # nothing to compare
     assert cli.main(['strategy', '--race', 'Bahrain', '--offline', '--driver', 'A', '--plan', 'bad']) == 2
+
+
+def test_strategy_cli_reports_the_librarys_value_error(capsys, monkeypatch):
+    class Fake:
+        def __init__(self, device=0):
+            pass
+
+        def predict_strategies(self, season, race, fixture, strategies, state=None, n_simulations=0, seed=None,
+                               allow_single_compound=False):
+            raise ValueError("scenario 'early': A uses one dry compound")
+
+    monkeypatch.setattr(cli, 'F1Predictor', Fake)
+    rc = cli.main(['strategy', '--race', 'Bahrain', '--offline', '--driver', 'A', '--plan', 'early=:15/HARD'])
+    assert rc == 2                                          # as the other six what-if commands: no traceback
+    captured = capsys.readouterr()
+    assert captured.err == "error: scenario 'early': A uses one dry compound\n"
+    assert 'F1 Pit Strategy' in captured.out and 'best by expected points' not in captured.out
