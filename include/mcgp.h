@@ -36,7 +36,8 @@ extern "C" {
  * function changed, so the version stays; a caller tests for the symbol); later still, mcgp_run_gaps, in the same way;
  * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too; and
  * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties; mcgp_lap_event and mcgp_run_events;
- * mcgp_run_championship_live; mcgp_pace_offset and mcgp_run_paces; mcgp_grid_edit and mcgp_run_grids */
+ * mcgp_run_championship_live; mcgp_pace_offset and mcgp_run_paces; mcgp_grid_edit and mcgp_run_grids;
+ * mcgp_run_pit_windows */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -892,6 +893,49 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
                       const mcgp_race_state *state, uint32_t n, uint32_t n_edges, const double *edges, uint32_t n_pairs,
                       const uint8_t *pairs, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, int32_t device,
                       uint64_t *hist_out, uint64_t *lap_gap_out, uint64_t *lead_out, uint64_t *pair_out);
+
+/* Pit window: if driver a stopped at the end of this lap and lost `loss` seconds, where would it rejoin, behind whom, how
+ * far behind, and is the stop free?  Counted on the device by lap for up to 64 windows (driver, loss), from the grid or
+ * from a mid-race state.  NOTHING IS RE-SIMULATED: the simulations are mcgp_run's / mcgp_run_from_state's, unmodified --
+ * same ids, same draws, hist_out equal to theirs -- and a window only asks a question of the times they have after the
+ * end of each recorded lap (the race model's update_positions; where mcgp_run_gaps reads).  The race after such a stop
+ * (fresh tyres, the traffic's reaction) is mcgp_run_strategies' question.  L = cfg->total_laps, B = n_edges + 1 bins, W =
+ * n_windows; several windows may name the same driver with different losses.  For window w = (a, loss) =
+ * (window_drivers[w], window_losses[w]) after a lap on which a is running:
+ *   - hypothetical rejoin time t* = cum_a + loss: one binary64 addition, the model's own stop arithmetic;
+ *   - a running car d != a is ahead at rejoin if (cum_d, grid slot of d) < (t*, grid slot of a) -- the running order's own
+ *     key, as mcgp_run_trace defines it --, else behind at rejoin;
+ *   - rejoin position = the number of running cars ahead at rejoin, 0-based; places lost = rejoin position - a's own
+ *     0-based running position, in [0, n - 1]; a free stop is places lost = 0;
+ *   - car ahead = the last car in running order among those ahead at rejoin, car behind = the first among those behind;
+ *     gap ahead = t* - cum_ahead and gap behind = cum_behind - t*, one subtraction each, >= 0;
+ *   - bins as mcgp_run_gaps has them: edges finite, edges[0] > 0, strictly increasing; bin(x) = the number of edges <= x
+ *     (a gap of zero is in bin 0).
+ * Laps 1 .. L are recorded from the grid, laps state->lap + 1 .. L from a state; the rows of earlier laps are left as the
+ * caller passed them.
+ *   hist_out        [n][n]          [driver][position - 1]
+ *   rejoin_out      [L][W][n + 1]   [lap - 1][w][rejoin position], column n = a has retired
+ *   lost_out        [L][W][n + 1]   [lap - 1][w][places lost], column n = retired
+ *   ahead_out       [L][W][n + 2]   [lap - 1][w][driver index of the car ahead], column n = rejoins in the lead, n + 1 =
+ *                                   retired
+ *   gap_ahead_out   [L][W][B + 1]   [lap - 1][w][bin(gap ahead)], column B = no car ahead, or retired
+ *   gap_behind_out  [L][W][B + 1]   [lap - 1][w][bin(gap behind)], column B = no car behind, or retired
+ * Every recorded row sums to n_sims.  All are ACCUMULATED into (caller zeroes), and only after every launch has
+ * succeeded: on an error they are left as they were.  All six outputs are required.  Every argument is checked before
+ * any device lookup (MCGP_E_BAD_ARG, the message names the field): what mcgp_run / mcgp_run_from_state check, grid_probs
+ * and state both or neither given, the edge rules of mcgp_run_gaps, n_windows outside [1, 64], a NULL pointer, a driver
+ * index >= n, a loss that is not finite or is negative, deviates other than MCGP_DEVIATES_32.  n_sims == 0 succeeds
+ * without a device.  The device work goes chunk by chunk through a staging buffer of 1 GiB / (recorded laps x 5 W)
+ * simulations (five bytes per recorded lap, window and simulation; rounded as mcgp_run_gaps rounds its chunk) that a
+ * counting kernel reads; device memory does not grow with n_sims.  Any split of [0, N) over calls, sim_offsets or
+ * devices sums to the same counts.  mcgp_last_kernel_ms afterwards = the device time of everything the call ran;
+ * mcgp_last_kernel_name = "mcgp::race_window_kernel". */
+#define MCGP_MAX_PIT_WINDOWS 64
+int32_t mcgp_run_pit_windows(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                             const mcgp_race_state *state, uint32_t n, uint32_t n_edges, const double *edges,
+                             uint32_t n_windows, const uint8_t *window_drivers, const double *window_losses, uint64_t n_sims,
+                             uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out, uint64_t *rejoin_out,
+                             uint64_t *lost_out, uint64_t *ahead_out, uint64_t *gap_ahead_out, uint64_t *gap_behind_out);
 
 /* Combination and conditional odds: up to 64 conditions evaluated inside every simulation on its own finished race, from
  * the grid or from a mid-race state; per condition the number of simulations that met it and the position histogram

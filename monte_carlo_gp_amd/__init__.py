@@ -7,6 +7,8 @@ RaceSimulator.run_from_state simulates the rest of a race from a mid-race RaceSt
 happened lap by lap (TraceResult: lap chart, laps led, pit stops, fastest lap, race events);
 RaceSimulator.run_strategies compares pit strategies (PitPlan, pit_window, StrategyResult); RaceSimulator.run_gaps counts
 the race's time gaps (GapResult: gap to the leader by lap, winning margin, gaps between named drivers);
+RaceSimulator.run_pit_windows counts where a car would rejoin if it stopped at the end of a lap (PitWindowResult: rejoin position,
+places lost, car ahead and gaps by lap, nothing re-simulated; the command is python -m monte_carlo_gp_amd.pit_window);
 RaceSimulator.run_penalties adds time penalties to the scenarios (TimePenalty, PenaltyResult: served in the pits or at the flag);
 RaceSimulator.run_events sets the race's events on chosen laps (RaceEvent, EventResult: a safety car on lap 31, a green rest of the race);
 RaceSimulator.run_paces adds lap-time offsets to the scenarios (PaceOffset, PaceResult: damage until the next stop, an engine mode for ten laps);
@@ -20,14 +22,14 @@ The compute path is the HIP library libmcgp_hip.so (C ABI: include/mcgp.h); ther
 CPU fallback.
 """
 from .simulation import (DEFAULT_GAP_EDGES, CarState, ChampionshipResult, CombinedResult, EventResult, GapResult, GridEdit, GridResult, MatchupResult,  # noqa: F401
-                         MoveResult, PaceOffset, PaceResult, PenaltyResult, PitPlan, RaceConfig, RaceEvent, RaceSimulator, RaceState, StintResult, StrategyResult,
+                         MoveResult, PaceOffset, PaceResult, PenaltyResult, PitPlan, PitWindowResult, RaceConfig, RaceEvent, RaceSimulator, RaceState, StintResult, StrategyResult,
                          TimePenalty, TraceResult, TrackChange, WeatherModel, WeatherResult,
                          decode_stints, encode_stints, histogram_to_probs, pit_window, run_championship,
                          run_monte_carlo_batch)
 from .conditions import Condition, ConditionResult  # noqa: F401
 from . import conditions, config  # noqa: F401
 
-__all__ = ['DEFAULT_GAP_EDGES', 'CarState', 'ChampionshipResult', 'CombinedResult', 'Condition', 'ConditionResult', 'EventResult', 'GapResult', 'GridEdit', 'GridResult', 'MatchupResult', 'MoveResult', 'PaceOffset', 'PaceResult', 'PenaltyResult', 'PitPlan', 'RaceConfig', 'RaceEvent',
+__all__ = ['DEFAULT_GAP_EDGES', 'CarState', 'ChampionshipResult', 'CombinedResult', 'Condition', 'ConditionResult', 'EventResult', 'GapResult', 'GridEdit', 'GridResult', 'MatchupResult', 'MoveResult', 'PaceOffset', 'PaceResult', 'PenaltyResult', 'PitPlan', 'PitWindowResult', 'RaceConfig', 'RaceEvent',
            'RaceSimulator', 'RaceState', 'StintResult', 'StrategyResult', 'TimePenalty', 'TraceResult', 'TrackChange', 'WeatherModel', 'WeatherResult', 'decode_stints', 'encode_stints',
            'histogram_to_probs', 'pit_window',
            'run_championship', 'run_monte_carlo_batch', 'conditions', 'config']

@@ -60,6 +60,7 @@ MAX_PLAN_STOPS = 8
 MAX_SCENARIOS = 64
 MAX_GAP_EDGES = 63          # include/mcgp.h: MCGP_MAX_GAP_EDGES, MCGP_MAX_GAP_PAIRS
 MAX_GAP_PAIRS = 64
+MAX_PIT_WINDOWS = 64        # include/mcgp.h: MCGP_MAX_PIT_WINDOWS
 STINT_STOPS = 4             # include/mcgp.h: MCGP_STINT_STOPS, MCGP_STINT_SEQ, MCGP_STINT_SEQ_CODES
 STINT_SEQ = 4
 STINT_SEQ_CODES = 1296
@@ -323,7 +324,7 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
            'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
            'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live', 'mcgp_run_paces',
-           'mcgp_run_combined', 'mcgp_run_weather', 'mcgp_run_grids')
+           'mcgp_run_combined', 'mcgp_run_weather', 'mcgp_run_grids', 'mcgp_run_pit_windows')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -331,6 +332,12 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
 GAPS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
                  C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint64,
                  C.c_uint64, C.c_int32] + [C.POINTER(C.c_uint64)] * 4
+
+# mcgp_run_pit_windows(cfg, drv, grid_probs, state, n, n_edges, edges, n_windows, window_drivers, window_losses, n_sims,
+# sim_offset, seed, device, hist_out, rejoin_out, lost_out, ahead_out, gap_ahead_out, gap_behind_out)
+PIT_WINDOWS_ARGTYPES = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), C.POINTER(C.c_double), C.POINTER(McgpRaceState),
+                        C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint8),
+                        C.POINTER(C.c_double), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32] + [C.POINTER(C.c_uint64)] * 6
 
 # mcgp_run_conditions(cfg, drv, grid_probs, state, n, n_conditions, conditions, n_sims, sim_offset, seed, device, hist_out,
 # count_out, cond_hist_out)
@@ -497,6 +504,9 @@ def lib():
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES
+        if 'mcgp_run_pit_windows' not in missing:
+            L.mcgp_run_pit_windows.restype = C.c_int32
+            L.mcgp_run_pit_windows.argtypes = PIT_WINDOWS_ARGTYPES
         if 'mcgp_run_conditions' not in missing:
             L.mcgp_run_conditions.restype = C.c_int32
             L.mcgp_run_conditions.argtypes = CONDITIONS_ARGTYPES

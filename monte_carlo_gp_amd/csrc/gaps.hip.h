@@ -123,6 +123,36 @@ race_gaps_kernel(const KParams *__restrict__ P, const ResumeState *__restrict__ 
         [](const Rows &, const LapEnv &, const GapObserver &, uint64_t) {});
 }
 
+// One staged row's counts, added into out[width]: every thread of the block (blockDim.x = kGapsCountBlock) counts its
+// words of the row's m bytes into its own column of `bins` ([value][thread] u32, width x kGapsCountBlock of them), then a
+// reduction per value and one u64 atomic per non-zero one.  A value past the width counts in the last column.  Every
+// thread of the block calls it (two barriers); the counting kernels of the gaps and pit-window calls are loops over it.
+__device__ __forceinline__ void count_staged_row(uint32_t *bins, const uint8_t *__restrict__ bytes, uint64_t m, uint32_t width,
+                                                 unsigned long long *__restrict__ out)
+{
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint64_t words = (m + 3) / 4;
+    for (uint32_t v = 0; v < width; ++v) bins[v * kGapsCountBlock + t] = 0u;
+    const uint32_t *row = reinterpret_cast<const uint32_t *>(bytes);
+    for (uint64_t i = t; i < words; i += kGapsCountBlock) {
+        const uint32_t w = row[i];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            uint32_t v = (w >> (8 * k)) & 0xFFu;
+            v = v < width ? v : width - 1u;
+            if (4 * i + k < m) ++bins[v * kGapsCountBlock + t];
+        }
+    }
+    __syncthreads();
+    for (uint32_t v = wave; v < width; v += kGapsCountBlock / 64) {
+        const uint32_t *b = bins + v * kGapsCountBlock;
+        uint32_t c = b[lane] + b[lane + 64] + b[lane + 128] + b[lane + 192];
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+        if (lane == 0 && c) atomicAdd(&out[v], (unsigned long long)c);
+    }
+    __syncthreads();
+}
+
 // The staged rows' counts of m simulations, added into their places: staged row q = lap_index R + j (lap_index = lap -
 // first_lap, R = n + 1 + n_pairs, lap0 = first_lap - 1) goes to
 //   j < n       lap_gap[(lap0 + lap_index) n + j][B + 1]
@@ -137,8 +167,6 @@ gaps_count_rows(const uint8_t *__restrict__ stage, uint64_t stride, uint64_t m, 
 {
     extern __shared__ __align__(16) unsigned char smem[];
     uint32_t *bins = reinterpret_cast<uint32_t *>(smem);              // [value][thread]
-    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint64_t words = (m + 3) / 4;
     const uint32_t R = n + 1u + n_pairs;
     for (uint32_t q = blockIdx.x; q < rows; q += gridDim.x) {
         const uint32_t lap = lap0 + q / R, j = q % R;
@@ -146,25 +174,7 @@ gaps_count_rows(const uint8_t *__restrict__ stage, uint64_t stride, uint64_t m, 
         unsigned long long *out = j < n    ? lap_gap + ((uint64_t)lap * n + j) * width
                                   : j == n ? lead + (uint64_t)lap * width
                                            : pair + ((uint64_t)lap * n_pairs + (j - n - 1u)) * width;
-        for (uint32_t v = 0; v < width; ++v) bins[v * kGapsCountBlock + t] = 0u;
-        const uint32_t *row = reinterpret_cast<const uint32_t *>(stage + (uint64_t)q * stride);
-        for (uint64_t i = t; i < words; i += kGapsCountBlock) {
-            const uint32_t w = row[i];
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-                uint32_t v = (w >> (8 * k)) & 0xFFu;
-                v = v < width ? v : width - 1u;
-                if (4 * i + k < m) ++bins[v * kGapsCountBlock + t];
-            }
-        }
-        __syncthreads();
-        for (uint32_t v = wave; v < width; v += kGapsCountBlock / 64) {
-            const uint32_t *b = bins + v * kGapsCountBlock;
-            uint32_t c = b[lane] + b[lane + 64] + b[lane + 128] + b[lane + 192];
-            for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-            if (lane == 0 && c) atomicAdd(&out[v], (unsigned long long)c);
-        }
-        __syncthreads();
+        count_staged_row(bins, stage + (uint64_t)q * stride, m, width, out);
     }
 }
 

@@ -16,6 +16,7 @@
 #include "trace.hip.h"
 #include "strategy.hip.h"
 #include "gaps.hip.h"
+#include "pit_window.hip.h"
 #include "conditions.hip.h"
 #include "stints.hip.h"
 #include "moves.hip.h"
@@ -539,6 +540,9 @@ constexpr uint64_t kTraceStageBytes = 512ull << 20;
 constexpr uint64_t kStrategyStageBytes = 256ull << 20;
 // ... and of mcgp_run_gaps: one byte per recorded lap, row (n drivers + 1 lead + n_pairs pairs) and simulation.
 constexpr uint64_t kGapsStageBytes = 512ull << 20;
+// ... and of mcgp_run_pit_windows: five bytes per recorded lap, window and simulation (19 200 per simulation at 60 laps and
+// 64 windows, so twice the gaps call's budget keeps a chunk above 50 000 simulations there).
+constexpr uint64_t kWindowStageBytes = 1024ull << 20;
 // ... and of mcgp_run_conditions: per simulation the finishing order (n bytes) and one u64 mask of the conditions met.
 constexpr uint64_t kConditionsStageBytes = 256ull << 20;
 // ... and of mcgp_run_stints: per driver and simulation one u64 record and one position byte.
@@ -1228,7 +1232,8 @@ struct AnalysisPlan {
     const void *count_fn = nullptr;         // that kernel, where it may need more than the default limit
 };
 
-// What mcgp_run_trace, mcgp_run_gaps, mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves each have of their own;
+// What mcgp_run_trace, mcgp_run_gaps, mcgp_run_conditions, mcgp_run_stints, mcgp_run_moves and mcgp_run_pit_windows each
+// have of their own;
 // run_analysis has the rest.
 struct AnalysisKind {
     const char *what;                       // the call in check_deviates_32's message
@@ -1306,6 +1311,26 @@ int32_t run_analysis(const mcgp_config *cfg, const mcgp_drivers *drv, const doub
     if (rc != MCGP_OK) return rc;
     counts.add_to(p.segs);
     return MCGP_OK;
+}
+
+// The bin edges of mcgp_run_gaps and mcgp_run_pit_windows: 1 to 63, finite, the first above 0, strictly increasing ...
+int check_gap_edges(uint32_t n_edges, const double *edges)
+{
+    if (n_edges < 1 || n_edges > mcgp::kMaxGapEdges) return fail(MCGP_E_BAD_ARG, "n_edges must be in [1, 63]");
+    if (!edges) return fail(MCGP_E_BAD_ARG, "edges is NULL");
+    for (uint32_t i = 0; i < n_edges; ++i) {
+        if (!std::isfinite(edges[i])) return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] is not finite");
+        if (i == 0 && !(edges[0] > 0.0)) return fail(MCGP_E_BAD_ARG, "edges[0] must be > 0");
+        if (i > 0 && !(edges[i] > edges[i - 1]))
+            return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] must be above edges[" + std::to_string(i - 1) + "]");
+    }
+    return MCGP_OK;
+}
+
+// ... and the device's table of them: the call's edges, then +inf to kGapEdgeSlots (gaps.hip.h: gap_bin).
+void fill_edge_table(double *table, uint32_t n_edges, const double *edges)
+{
+    for (uint32_t i = 0; i < mcgp::kGapEdgeSlots; ++i) table[i] = i < n_edges ? edges[i] : HUGE_VAL;
 }
 
 }  // namespace
@@ -2528,14 +2553,8 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     AnalysisKind k = {"gaps run", "gaps", "mcgp::race_gaps_kernel", reinterpret_cast<KernelFn>(kernel), kGapsStageBytes,
                       "lap_gap_out", lap_gap_out};
     k.check_args = [&]() -> int {
-        if (n_edges < 1 || n_edges > mcgp::kMaxGapEdges) return fail(MCGP_E_BAD_ARG, "n_edges must be in [1, 63]");
-        if (!edges) return fail(MCGP_E_BAD_ARG, "edges is NULL");
-        for (uint32_t i = 0; i < n_edges; ++i) {
-            if (!std::isfinite(edges[i])) return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] is not finite");
-            if (i == 0 && !(edges[0] > 0.0)) return fail(MCGP_E_BAD_ARG, "edges[0] must be > 0");
-            if (i > 0 && !(edges[i] > edges[i - 1]))
-                return fail(MCGP_E_BAD_ARG, "edges[" + std::to_string(i) + "] must be above edges[" + std::to_string(i - 1) + "]");
-        }
+        const int rc = check_gap_edges(n_edges, edges);
+        if (rc != MCGP_OK) return rc;
         if (n_pairs > mcgp::kMaxGapPairs) return fail(MCGP_E_BAD_ARG, "n_pairs must be in [0, 64]");
         if (n_pairs && !pairs) return fail(MCGP_E_BAD_ARG, "pairs is NULL");
         if (n_pairs && !pair_out) return fail(MCGP_E_BAD_ARG, "pair_out is NULL");
@@ -2553,7 +2572,7 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     };
     k.plan = [&](uint32_t laps, uint32_t lap) {
         L = laps, lap0 = lap, rows = (L - lap0) * (n + 1 + n_pairs);
-        for (uint32_t i = 0; i < mcgp::kGapEdgeSlots; ++i) edge_table[i] = i < n_edges ? edges[i] : HUGE_VAL;
+        fill_edge_table(edge_table, n_edges, edges);
         // the counting kernel's columns: 4 x 256 bytes per value, up to 129 values (129 KiB of a CU's 160)
         count_lds = (size_t)(n_pairs ? 2 * B + 1 : B + 1) * mcgp::kGapsCountBlock * 4;
         // hist [n][n] | lap_gap [L][n][B + 1] | lead [L][B + 1] | pair [L][n_pairs][2B + 1].  A race resumed after its
@@ -2576,6 +2595,82 @@ int32_t mcgp_run_gaps(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
             hipLaunchKernelGGL(mcgp::gaps_count_rows, dim3((uint32_t)std::min<uint64_t>(rows, a.grid_cap)),
                                dim3(mcgp::kGapsCountBlock), count_lds, nullptr, d_stage, a.stride, a.m, rows, n, n_pairs, B,
                                lap0, a.count(1), a.count(2), a.count(3));
+            HIP_TRY(hipGetLastError());
+        }
+        return MCGP_OK;
+    };
+    return run_analysis(cfg, drv, grid_probs, state, n, n_sims, sim_offset, seed, device, hist_out, k);
+}
+
+static_assert(mcgp::kMaxPitWindows == MCGP_MAX_PIT_WINDOWS, "the device's window table holds the C ABI's limit");
+
+int32_t mcgp_run_pit_windows(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                             const mcgp_race_state *state, uint32_t n, uint32_t n_edges, const double *edges,
+                             uint32_t n_windows, const uint8_t *window_drivers, const double *window_losses, uint64_t n_sims,
+                             uint64_t sim_offset, uint64_t seed, int32_t device, uint64_t *hist_out, uint64_t *rejoin_out,
+                             uint64_t *lost_out, uint64_t *ahead_out, uint64_t *gap_ahead_out, uint64_t *gap_behind_out)
+{
+    const auto kernel = state ? &mcgp::race_window_kernel<true> : &mcgp::race_window_kernel<false>;
+    uint32_t L = 0, lap0 = 0, rows = 0;                         // laps lap0 + 1 .. L are recorded
+    const uint32_t B = n_edges + 1, W = n_windows;
+    double edge_table[mcgp::kGapEdgeSlots];                     // the call's edges, then +inf (gaps.hip.h: gap_bin)
+    uint8_t driver_table[mcgp::kWindowSlots] = {};              // the call's windows, then (driver 0, loss 0): whole groups
+    double loss_table[mcgp::kWindowSlots] = {};
+    size_t count_lds = 0;
+    uint8_t *d_stage;
+    const double *d_edges, *d_losses;
+    const uint8_t *d_drivers;
+    AnalysisKind k = {"pit windows run", "pit windows", "mcgp::race_window_kernel", reinterpret_cast<KernelFn>(kernel),
+                      kWindowStageBytes, "rejoin_out", rejoin_out};
+    k.check_args = [&]() -> int {
+        const int rc = check_gap_edges(n_edges, edges);
+        if (rc != MCGP_OK) return rc;
+        if (W < 1 || W > mcgp::kMaxPitWindows) return fail(MCGP_E_BAD_ARG, "n_windows must be in [1, 64]");
+        if (!window_drivers) return fail(MCGP_E_BAD_ARG, "window_drivers is NULL");
+        if (!window_losses) return fail(MCGP_E_BAD_ARG, "window_losses is NULL");
+        if (!lost_out) return fail(MCGP_E_BAD_ARG, "lost_out is NULL");
+        if (!ahead_out) return fail(MCGP_E_BAD_ARG, "ahead_out is NULL");
+        if (!gap_ahead_out) return fail(MCGP_E_BAD_ARG, "gap_ahead_out is NULL");
+        if (!gap_behind_out) return fail(MCGP_E_BAD_ARG, "gap_behind_out is NULL");
+        for (uint32_t w = 0; w < W; ++w)
+            if (!std::isfinite(window_losses[w]) || !(window_losses[w] >= 0.0))
+                return fail(MCGP_E_BAD_ARG, "window_losses[" + std::to_string(w) + "] must be finite and >= 0");
+        return MCGP_OK;
+    };
+    k.check_fields = [&]() -> int {
+        for (uint32_t w = 0; w < W; ++w)
+            if (window_drivers[w] >= n)
+                return fail(MCGP_E_BAD_ARG, "window_drivers[" + std::to_string(w) + "]: driver index must be below n");
+        return MCGP_OK;
+    };
+    k.plan = [&](uint32_t laps, uint32_t lap) {
+        L = laps, lap0 = lap, rows = (L - lap0) * W * mcgp::kWindowRows;
+        fill_edge_table(edge_table, n_edges, edges);
+        for (uint32_t w = 0; w < W; ++w) driver_table[w] = window_drivers[w], loss_table[w] = window_losses[w];
+        // the counting kernel's columns: 4 x 256 bytes per value, up to 65 values (the gap rows at 63 edges)
+        count_lds = (size_t)std::max(n + 2, B + 1) * mcgp::kGapsCountBlock * 4;
+        // hist [n][n] | rejoin, lost [L][W][n + 1] | ahead [L][W][n + 2] | gap_ahead, gap_behind [L][W][B + 1].  A race
+        // resumed after its last lap records nothing: one row's worth of staging keeps the sizes non-zero
+        const size_t cells = (size_t)L * W;
+        return AnalysisPlan{{{hist_out, (size_t)n * n}, {rejoin_out, cells * (n + 1)}, {lost_out, cells * (n + 1)},
+                             {ahead_out, cells * (n + 2)}, {gap_ahead_out, cells * (B + 1)}, {gap_behind_out, cells * (B + 1)}},
+                            std::max<uint64_t>(rows, 1), count_lds, reinterpret_cast<const void *>(&mcgp::window_count_rows)};
+    };
+    // staging of one chunk in rows of `stride` bytes | edges | window drivers | window losses
+    k.regions = [&](Layout &ws, uint64_t stride) {
+        ws.add(&d_stage, (size_t)std::max<uint32_t>(rows, 1) * stride);
+        ws.add(&d_edges, mcgp::kGapEdgeSlots, edge_table);
+        ws.add(&d_losses, mcgp::kWindowSlots, loss_table);
+        ws.add(&d_drivers, mcgp::kWindowSlots, driver_table);
+    };
+    k.launch = [&](const AnalysisChunk &a) -> int {
+        hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(a.block), a.lds, nullptr, a.kp, a.st, d_edges, n_edges, d_drivers, d_losses,
+                           W, a.m, a.first_sim, a.seed_lo, a.seed_hi, a.count(0), d_stage, a.stride, a.n_batches);
+        HIP_TRY(hipGetLastError());
+        if (rows) {
+            hipLaunchKernelGGL(mcgp::window_count_rows, dim3((uint32_t)std::min<uint64_t>(rows, a.grid_cap)),
+                               dim3(mcgp::kGapsCountBlock), count_lds, nullptr, d_stage, a.stride, a.m, rows, n, W, B, lap0,
+                               a.count(1), a.count(2), a.count(3), a.count(4), a.count(5));
             HIP_TRY(hipGetLastError());
         }
         return MCGP_OK;

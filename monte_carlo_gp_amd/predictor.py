@@ -182,7 +182,7 @@ class F1Predictor:
     def predict_weekend(self, season: int, race: str, fixture: dict | str, grid_penalties=None, circuit_info=None,
                         prediction_point: str = 'fp2', actual_grid=None, n_simulations: int = 10000,
                         seed: int | None = None, matchups: bool = False, trace: bool = False, gaps=None,
-                        conditions=None, tyres: bool = False, moves: bool = False) -> dict:
+                        conditions=None, tyres: bool = False, moves: bool = False, pit_window=None) -> dict:
         """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU.
 
         matchups=True (not in the reference): the race runs through RaceSimulator.run_matchups -- the same simulations,
@@ -210,27 +210,32 @@ class F1Predictor:
         moves=True (not in the reference): the race also runs through RaceSimulator.run_moves -- the same simulations --
         and the result gains 'moves', the block move_keys builds: per driver the expected places gained, the expected
         start gain and the passes made and lost, and for the race the expected on-track passes with their 10-90 % range
-        and the commonest (a, b) pairs."""
+        and the commonest (a, b) pairs.
+
+        pit_window=[(driver, loss in seconds or None: the config's pit_loss), ...], or {'windows': [...], 'edges': [...]}
+        (not in the reference): the race also runs through RaceSimulator.run_pit_windows -- the same simulations,
+        nothing re-simulated -- and the result gains 'pit_window', the block pit_window_keys builds: per window and lap
+        the odds of a free stop, the rejoin position, the likeliest car ahead and the odds of clear air at rejoin."""
         fixture = _open_fixture(fixture, season, race)
         inp = self.simulator_inputs(fixture, race, grid_penalties, circuit_info, prediction_point, actual_grid)
         sim = RaceSimulator(inp['config'], device=self.device)
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
             # same inputs, the matrix built on the device from the ratings (no host matrix crosses PCIe)
             ratings = {d: self.elo_system.ratings.get(d, {}).get('quali', self.elo_system.initial) for d in inp['drivers']}
-            if matchups or trace or gaps or conditions or tyres or moves:
+            if matchups or trace or gaps or conditions or tyres or moves or pit_window:
                 # the same matrix, read back from the device front end and handed to the matchups / trace / gaps run
                 grid = sim.grid_probs_on_device(inp['drivers'], ratings, fixture.get('quali_features', {}),
                                                 grid_penalties or {})
                 return self._with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups,
-                                         trace, gaps, conditions, tyres, moves)
+                                         trace, gaps, conditions, tyres, moves, pit_window)
             race_probs, grid = sim.run_from_ratings(
                 n_simulations, inp['drivers'], ratings, fixture.get('quali_features', {}), grid_penalties or {},
                 inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'], seed=seed,
                 track_condition=inp['track_condition'])
             return pack_result(inp['drivers'], grid, race_probs, inp['weather'], prediction_point, actual_grid)
-        if matchups or trace or gaps or conditions or tyres or moves:
+        if matchups or trace or gaps or conditions or tyres or moves or pit_window:
             return self._with_counts(sim, inp, inp['grid_probs'], n_simulations, seed, prediction_point, actual_grid,
-                                     matchups, trace, gaps, conditions, tyres, moves)
+                                     matchups, trace, gaps, conditions, tyres, moves, pit_window)
         race_probs = sim.run_monte_carlo(
             n_simulations=n_simulations, grid_probs=inp['grid_probs'], base_pace=inp['base_pace'],
             tire_deg=inp['tire_deg'], driver_variance=inp['driver_variance'],
@@ -239,7 +244,7 @@ class F1Predictor:
 
     def predict_from_state(self, season: int, race: str, fixture: dict | str, state, n_simulations: int = 100000,
                            seed: int | None = None, gaps=None, conditions=None, tyres: bool = False,
-                           moves: bool = False):
+                           moves: bool = False, pit_window=None):
         """In-race odds (not in the reference): the weekend's race inputs (simulator_inputs, as predict_weekend builds
         them) run from a mid-race RaceState of the fixture's drivers -- or from each of a list of them, with common
         random numbers -- through RaceSimulator.run_from_state.  Returns, per state, {'lap', 'win_probabilities', 'podium_probabilities',
@@ -249,13 +254,15 @@ class F1Predictor:
         that state, same simulations; race events count from the state's lap on.  tyres (as in predict_weekend): every
         state's dict gains 'tyres' from RaceSimulator.run_stints on that state, same simulations; stops count from the
         state's lap on.  moves (as in predict_weekend): every state's dict gains 'moves' from RaceSimulator.run_moves on
-        that state, same simulations; passes count from the state's lap on and there is no start gain."""
+        that state, same simulations; passes count from the state's lap on and there is no start gain.  pit_window (as
+        in predict_weekend): every state's dict gains 'pit_window' from RaceSimulator.run_pit_windows on that state, same
+        simulations; the laps after the state's are recorded."""
         fixture = _open_fixture(fixture, season, race)
         single = not isinstance(state, (list, tuple))
         states = [state] if single else list(state)
         inp = self.simulator_inputs(fixture, race)
         sim = RaceSimulator(inp['config'], device=self.device)
-        seed = sim._resolve_seed(seed) if gaps or conditions or tyres or moves else seed
+        seed = sim._resolve_seed(seed) if gaps or conditions or tyres or moves or pit_window else seed
         # the driver order of predict_weekend's run: a state that run's simulation i reached continues as simulation i
         probs = sim.run_from_state(n_simulations, states, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
                                    inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'],
@@ -290,6 +297,13 @@ class F1Predictor:
                                    inp['driver_dnf_rates'], state=st, seed=seed, track_condition=inp['track_condition'],
                                    drivers=list(inp['grid_probs']))
                 res['moves'] = move_keys(mv)
+        if pit_window:
+            for st, res in zip(states, out):
+                pw = sim.run_pit_windows(n_simulations, None, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
+                                         inp['driver_dnf_rates'], state=st, seed=seed,
+                                         track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
+                                         **pit_window_options(pit_window, inp['config'].pit_loss))
+                res['pit_window'] = pit_window_keys(pw, inp['config'].dirty_air_threshold)
         return out[0] if single else out
 
     def _scenario_run(self, season, race, fixture, state, seed, prediction_point, allow_single_compound):
@@ -375,9 +389,9 @@ class F1Predictor:
 
     @staticmethod
     def _with_counts(sim, inp, grid, n_simulations, seed, prediction_point, actual_grid, matchups, trace,
-                     gaps=None, conditions=None, tyres=False, moves=False) -> dict:
-        """predict_weekend's result from run_matchups, run_trace, run_gaps, run_conditions, run_stints and / or run_moves calls on
-        `grid` (the same simulations: one seed for all), with their keys added."""
+                     gaps=None, conditions=None, tyres=False, moves=False, pit_window=None) -> dict:
+        """predict_weekend's result from run_matchups, run_trace, run_gaps, run_conditions, run_stints, run_moves and / or
+        run_pit_windows calls on `grid` (the same simulations: one seed for all), with their keys added."""
         args = (n_simulations, grid, inp['base_pace'], inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'])
         seed = sim._resolve_seed(seed)
         res = None
@@ -417,6 +431,13 @@ class F1Predictor:
                 res = pack_result(inp['drivers'], grid, mv.position_probabilities(), inp['weather'], prediction_point,
                                   actual_grid)
             res['moves'] = move_keys(mv)
+        if pit_window:
+            pw = sim.run_pit_windows(*args, seed=seed, track_condition=inp['track_condition'],
+                                     **pit_window_options(pit_window, inp['config'].pit_loss))
+            if res is None:
+                res = pack_result(inp['drivers'], grid, pw.position_probabilities(), inp['weather'], prediction_point,
+                                  actual_grid)
+            res['pit_window'] = pit_window_keys(pw, inp['config'].dirty_air_threshold)
         return res
 
 
@@ -503,6 +524,53 @@ def gap_options(gaps) -> dict:
     if gaps.get('pairs'):
         out['pairs'] = [(str(a), str(b)) for a, b in gaps['pairs']]
     return out
+
+
+def pit_window_options(pit_window, pit_loss) -> dict:
+    """run_pit_windows's windows / edges from predict_weekend's pit_window argument: [(driver, loss or None), ...], or
+    {'windows': [...], 'edges': [...]}.  None stands for `pit_loss`; a window given twice is kept once."""
+    if not isinstance(pit_window, dict):
+        pit_window = {'windows': pit_window}
+    unknown = set(pit_window) - {'windows', 'edges'}
+    if unknown:
+        raise ValueError(f'pit_window: unknown keys {sorted(unknown)} (windows, edges)')
+    windows = []
+    for d, loss in pit_window.get('windows') or ():
+        w = (str(d), float(pit_loss if loss is None else loss))
+        if w not in windows:
+            windows.append(w)
+    out = {'windows': windows}
+    if pit_window.get('edges') is not None:
+        out['edges'] = [float(x) for x in pit_window['edges']]
+    return out
+
+
+def pit_window_keys(pw, clear_air_seconds=2.0) -> dict:
+    """The 'pit_window' block predict_weekend(pit_window=...) / predict_from_state(pit_window=...) add, JSON-safe, from a
+    PitWindowResult: the edges, the first recorded lap, the edge nearest to `clear_air_seconds` (the model's
+    dirty_air_threshold; the counts answer at edges only) and per window, by lap (index lap - 1; None where the lap is
+    not recorded or the driver never runs), all given that the driver is running: 'free_stop' P(no place lost),
+    'expected_rejoin_position' and 'median_rejoin_position' (1-based), 'clear_air' P(car ahead at least that edge up
+    the road, or none), 'safe_from_behind' likewise for the car behind, 'likeliest_ahead' [driver or 'in the lead',
+    probability]; and 'running' P(running), 'open_laps' the laps with P(free stop) >= 0.5."""
+    edge = min(pw.edges, key=lambda x: (abs(x - clear_air_seconds), x))           # (as cli._nearest_edges picks)
+    laps = range(1, pw.total_laps + 1)
+    recorded = lambda lap: lap >= pw.first_lap
+    safe = lambda xs: [None if x is None or x != x else float(x) for x in xs]
+    rows = []
+    for w, (d, loss) in enumerate(pw.windows):
+        ahead = [(pw.rejoins_behind(w, lap, 1) or [None])[0] if recorded(lap) else None for lap in laps]
+        rows.append({
+            'driver': d, 'loss': loss, 'running': safe(pw.running_probability(w)),
+            'free_stop': safe(pw.free_stop_probability(w)),
+            'expected_rejoin_position': safe(pw.expected_rejoin_position(w)),
+            'median_rejoin_position': [pw.median_rejoin_position(w, lap) if recorded(lap) else None for lap in laps],
+            'clear_air': safe(pw.clear_air_probability(w, edge)),
+            'safe_from_behind': safe(pw.safe_from_behind_probability(w, edge)),
+            'likeliest_ahead': [None if a is None else [a[0], a[1]] for a in ahead],
+            'open_laps': pw.open_laps(w)})
+    return {'edges': list(pw.edges), 'first_lap': pw.first_lap, 'total_laps': pw.total_laps, 'clear_air_seconds': edge,
+            'windows': rows}
 
 
 def gap_keys(g) -> dict:

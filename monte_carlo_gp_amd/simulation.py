@@ -188,6 +188,16 @@ def _optr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8 if a.dtype == np.uint8 else C.c_uint64))
 
 
+def _gap_edge_array(edges):
+    """The bin edges of run_gaps / run_pit_windows as the C ABI takes them (None: DEFAULT_GAP_EDGES), checked."""
+    edge_arr = np.ascontiguousarray(DEFAULT_GAP_EDGES if edges is None else list(edges), np.float64)
+    if edge_arr.ndim != 1 or not 1 <= len(edge_arr) <= N.MAX_GAP_EDGES:
+        raise ValueError(f'edges: 1 to {N.MAX_GAP_EDGES} values, got {edge_arr.shape}')
+    if not (np.isfinite(edge_arr).all() and edge_arr[0] > 0 and (np.diff(edge_arr) > 0).all()):
+        raise ValueError('edges must be finite, positive and strictly increasing')
+    return edge_arr
+
+
 def _count_arrays(result):
     """The count arrays of a result object, by field name."""
     return {k: v for k, v in vars(result).items() if isinstance(v, np.ndarray)}
@@ -1068,11 +1078,7 @@ class RaceSimulator:
         deviates only; same seed rules and device sharding as run_monte_carlo.  Sets last_histogram / last_drivers."""
         src = self._source(grid_probs, state, drivers)
         drivers = src.drivers
-        edge_arr = np.ascontiguousarray(DEFAULT_GAP_EDGES if edges is None else list(edges), np.float64)
-        if edge_arr.ndim != 1 or not 1 <= len(edge_arr) <= N.MAX_GAP_EDGES:
-            raise ValueError(f'edges: 1 to {N.MAX_GAP_EDGES} values, got {edge_arr.shape}')
-        if not (np.isfinite(edge_arr).all() and edge_arr[0] > 0 and (np.diff(edge_arr) > 0).all()):
-            raise ValueError('edges must be finite, positive and strictly increasing')
+        edge_arr = _gap_edge_array(edges)
         index = {d: i for i, d in enumerate(drivers)}
         names = [(str(a), str(b)) for a, b in pairs]
         for a, b in names:
@@ -1094,6 +1100,57 @@ class RaceSimulator:
             ['hist', 'lap_gap', 'lead', 'pair' if P else None])
         return GapResult(drivers=drivers, n_simulations=n_simulations if drivers and n_simulations > 0 else 0,
                          total_laps=L, edges=tuple(float(x) for x in edge_arr), pairs=names, first_lap=first_lap, **total)
+
+    def run_pit_windows(
+        self,
+        n_simulations: int,
+        grid_probs: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        state: 'RaceState | None' = None,
+        windows=(),
+        edges=None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+    ) -> 'PitWindowResult':
+        """Pit windows (include/mcgp.h: mcgp_run_pit_windows): for each of `windows` = [(driver, loss in seconds or None:
+        config.pit_loss), ...] (1 to 64; a driver may appear with several losses) and every lap, where the driver would
+        rejoin if it stopped at the end of that lap and lost that much -- position, places lost, the car ahead and the
+        gaps ahead and behind over `edges` (seconds, default DEFAULT_GAP_EDGES) --, counted on the device.  Nothing is
+        re-simulated: the races are run_monte_carlo's (grid_probs, laps 1..L) or run_from_state's (state, the laps after
+        the state's), unmodified, and the PitWindowResult's position histogram equals that call's; the race AFTER a stop
+        is run_strategies' question.  32-bit deviates only; same seed rules and device sharding as run_gaps.  Sets
+        last_histogram / last_drivers."""
+        src = self._source(grid_probs, state, drivers)
+        drivers = src.drivers
+        edge_arr = _gap_edge_array(edges)
+        index = {d: i for i, d in enumerate(drivers)}
+        wins = [(str(d), float(self.config.pit_loss if loss is None else loss)) for d, loss in windows]
+        if not 1 <= len(wins) <= N.MAX_PIT_WINDOWS:
+            raise ValueError(f'windows: 1 to {N.MAX_PIT_WINDOWS}, got {len(wins)}')
+        for d, loss in wins:
+            if d not in index:
+                raise ValueError(f'window ({d!r}, {loss:g}): not among the drivers')
+            if not (math.isfinite(loss) and loss >= 0):
+                raise ValueError(f'window ({d!r}, {loss!r}): the loss must be finite and >= 0')
+        L, E, W = int(self.config.total_laps), len(edge_arr), len(wins)
+        n_simulations = int(n_simulations)
+        first_lap = src.first_lap(1)
+        driver_arr = np.ascontiguousarray([index[d] for d, _ in wins], np.uint8)
+        loss_arr = np.ascontiguousarray([loss for _, loss in wins], np.float64)
+        total = self._run_entry(
+            'mcgp_run_pit_windows', n_simulations, drivers,
+            (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), seed, sim_offset,
+            lambda n: src.c_args() + (n, E, _dptr(edge_arr), W, _optr(driver_arr), _dptr(loss_arr)),
+            lambda count: _count_arrays(PitWindowResult.empty(drivers, L, edge_arr, wins, count, first_lap, np.uint64)),
+            ['hist', 'rejoin', 'lost', 'ahead', 'gap_ahead', 'gap_behind'])
+        return PitWindowResult(drivers=drivers, n_simulations=n_simulations if drivers and n_simulations > 0 else 0,
+                               total_laps=L, edges=tuple(float(x) for x in edge_arr), windows=wins, first_lap=first_lap,
+                               **total)
 
     def run_stints(
         self,
@@ -1631,7 +1688,146 @@ class GapResult:
         return self._p(self.pair[:, p, :j].sum(axis=1) + self.pair[:, p, B:B + j].sum(axis=1))
 
 
-STINT_LETTERS = 'SMHIW'                 # one letter per compound of _native.COMPOUNDS, as strategy strings spell them
+IN_THE_LEAD = 'in the lead'            # PitWindowResult.rejoins_behind's entry for a rejoin with no car ahead
+
+
+@dataclass
+class PitWindowResult:
+    """What RaceSimulator.run_pit_windows returns: integer counts over n_simulations of where a driver would rejoin if it
+    stopped at the end of a lap and lost `loss` seconds (include/mcgp.h: mcgp_run_pit_windows has the definitions).
+    Nothing is re-simulated: the races are the unmodified ones, and a window asks a question of their times after each
+    lap.  L = total_laps, n = len(drivers), W = len(windows) = [(driver, loss), ...], B = len(edges) + 1 bins as
+    GapResult has them.
+      hist        [n][n]          [driver][position - 1], run_monte_carlo's / run_from_state's histogram
+      rejoin      [L][W][n + 1]   [lap - 1][window][rejoin position, 0-based], column n = the driver has retired
+      lost        [L][W][n + 1]   [lap - 1][window][places lost], column n = retired; 0 is a free stop
+      ahead       [L][W][n + 2]   [lap - 1][window][index of the car ahead at rejoin], n = rejoins in the lead, n + 1 = retired
+      gap_ahead   [L][W][B + 1]   [lap - 1][window][bin of the gap to the car ahead], column B = no car ahead, or retired
+      gap_behind  [L][W][B + 1]   [lap - 1][window][bin of the gap to the car behind], column B = no car behind, or retired
+    Laps before first_lap (a run from a state) are not recorded: their rows are zero.  Every reader that speaks of the
+    rejoin is CONDITIONAL ON THE DRIVER RUNNING after that lap (a retired car has no stop to make); running_probability
+    gives the condition's own probability.  A window `w` is named by its index, by (driver, loss), or by the driver alone
+    where only one window names it.  The counts carry no value between two edges: `seconds` must be an edge."""
+    drivers: list
+    n_simulations: int
+    total_laps: int
+    edges: tuple
+    windows: list
+    first_lap: int
+    hist: np.ndarray
+    rejoin: np.ndarray
+    lost: np.ndarray
+    ahead: np.ndarray
+    gap_ahead: np.ndarray
+    gap_behind: np.ndarray
+
+    @classmethod
+    def empty(cls, drivers, total_laps, edges, windows, n_simulations=0, first_lap=1, dtype=np.int64) -> 'PitWindowResult':
+        n, L, B, W = len(drivers), int(total_laps), len(edges) + 1, len(windows)
+        z = lambda *shape: np.zeros(shape, dtype)
+        return cls(drivers=list(drivers), n_simulations=int(n_simulations), total_laps=L,
+                   edges=tuple(float(x) for x in edges), windows=[(str(d), float(loss)) for d, loss in windows],
+                   first_lap=int(first_lap), hist=z(n, n), rejoin=z(L, W, n + 1), lost=z(L, W, n + 1), ahead=z(L, W, n + 2),
+                   gap_ahead=z(L, W, B + 1), gap_behind=z(L, W, B + 1))
+
+    _lap = GapResult._lap
+    _edge = GapResult._edge
+
+    def _w(self, w) -> int:
+        if isinstance(w, (int, np.integer)):
+            if not 0 <= int(w) < len(self.windows):
+                raise ValueError(f'window index must be in [0, {len(self.windows) - 1}], got {w}')
+            return int(w)
+        if isinstance(w, str):
+            hits = [i for i, (d, _) in enumerate(self.windows) if d == w]
+            if len(hits) != 1:
+                raise ValueError(f'{w!r} names {len(hits)} of the windows {self.windows}: give (driver, loss) or an index')
+            return hits[0]
+        key = (str(w[0]), float(w[1]))
+        if key not in self.windows:
+            raise ValueError(f'{key!r} is not one of the windows {self.windows}')
+        return self.windows.index(key)
+
+    @staticmethod
+    def _given_running(counts) -> np.ndarray:
+        """counts [..., k + 1] (last column: retired) -> [..., k] probabilities among the simulations in which the driver
+        runs; nan where there is none (a lap that is not recorded, or a car that is always out by then)."""
+        c = np.asarray(counts[..., :-1], np.float64)
+        tot = c.sum(axis=-1, keepdims=True)
+        return np.divide(c, tot, out=np.full(c.shape, np.nan), where=tot > 0)
+
+    def position_probabilities(self) -> dict:
+        """{driver: {position: probability}}, what run_monte_carlo / run_from_state returns for the same arguments."""
+        return histogram_to_probs(self.hist, self.drivers, self.n_simulations)
+
+    def running_probability(self, w) -> np.ndarray:
+        """[L]: P(the window's driver is running after each lap) -- what the other readers are conditional on; 0 for a lap
+        that is not recorded."""
+        n = len(self.drivers)
+        return self.rejoin[:, self._w(w), :n].sum(axis=1) / max(self.n_simulations, 1)
+
+    def rejoin_distribution(self, w, lap) -> np.ndarray:
+        """[n]: P(rejoins in position p + 1 | running) for a stop at the end of `lap`."""
+        return self._given_running(self.rejoin[self._lap(lap), self._w(w)])
+
+    def expected_rejoin_position(self, w) -> np.ndarray:
+        """[L]: the expected rejoin position (1-based) for a stop at the end of each lap, given running; nan where that
+        never happens."""
+        p = self._given_running(self.rejoin[:, self._w(w)])
+        return p @ np.arange(1, len(self.drivers) + 1, dtype=np.float64)
+
+    def places_lost_distribution(self, w, lap) -> np.ndarray:
+        """[n]: P(the stop costs j places | running) for a stop at the end of `lap`; entry 0 is the free stop."""
+        return self._given_running(self.lost[self._lap(lap), self._w(w)])
+
+    def free_stop_probability(self, w) -> np.ndarray:
+        """[L]: P(the stop costs no place | running) by lap; nan where the driver never runs or the lap is not recorded."""
+        return self._given_running(self.lost[:, self._w(w)])[:, 0]
+
+    def _gap_at_least(self, counts, w, seconds, lap):
+        """P(gap >= seconds, or no such car | running) from gap_ahead / gap_behind: by lap [L], or for one lap."""
+        j, B, n = self._edge(seconds), len(self.edges) + 1, len(self.drivers)
+        c = counts[:, self._w(w)]
+        running = self.rejoin[:, self._w(w), :n].sum(axis=1)
+        retired = self.rejoin[:, self._w(w), n]
+        hits = c[:, j:B].sum(axis=1) + (c[:, B] - retired)         # (column B: no such car, or retired)
+        out = np.divide(hits, running, out=np.full(len(hits), np.nan), where=running > 0)
+        return out if lap is None else float(out[self._lap(lap)])
+
+    def clear_air_probability(self, w, seconds, lap=None):
+        """P(the car ahead at rejoin is at least `seconds` up the road, or there is none | running): [L] by lap, or one
+        number for `lap`.  `seconds` must be one of the edges (ValueError otherwise, as GapResult.within)."""
+        return self._gap_at_least(self.gap_ahead, w, seconds, lap)
+
+    def safe_from_behind_probability(self, w, seconds, lap=None):
+        """P(the car behind at rejoin is at least `seconds` back, or there is none | running): [L] by lap, or one number
+        for `lap`.  `seconds` must be one of the edges."""
+        return self._gap_at_least(self.gap_behind, w, seconds, lap)
+
+    def rejoins_behind(self, w, lap, k=5) -> list:
+        """[(driver or IN_THE_LEAD, P(that is the car ahead at rejoin | running))]: the k most likely, for a stop at the
+        end of `lap`; empty where the driver never runs."""
+        p = self._given_running(self.ahead[self._lap(lap), self._w(w)])
+        if np.isnan(p).any():
+            return []
+        names = list(self.drivers) + [IN_THE_LEAD]
+        first = sorted(range(len(names)), key=lambda i: (-p[i], i))[:int(k)]
+        return [(names[i], float(p[i])) for i in first if p[i] > 0]
+
+    def median_rejoin_position(self, w, lap):
+        """The lower median of the rejoin position (1-based) given running, for a stop at the end of `lap`; None where
+        the driver never runs."""
+        c = self.rejoin[self._lap(lap), self._w(w), :len(self.drivers)]
+        tot = int(c.sum())
+        return int(np.searchsorted(2 * np.cumsum(c), tot, side='left')) + 1 if tot else None
+
+    def open_laps(self, w, p=0.5) -> list:
+        """The laps after which P(free stop | running) >= p."""
+        free = self.free_stop_probability(w)
+        return [k + 1 for k in range(self.total_laps) if free[k] >= p]         # (nan >= p is False)
+
+
+STINT_LETTERS = 'SMHIW'               # one letter per compound of _native.COMPOUNDS, as strategy strings spell them
 MANY_STINTS = '5+ stints'              # column 0 of StintResult.seq: more stints than a sequence code holds
 
 

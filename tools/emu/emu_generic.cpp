@@ -1,8 +1,9 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
 // fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
-// gaps.hip.h, conditions.hip.h, stints.hip.h, moves.hip.h, fastest.hip.h and scenario.hip.h (with strategy.hip.h,
+// gaps.hip.h, pit_window.hip.h, conditions.hip.h, stints.hip.h, moves.hip.h, fastest.hip.h and scenario.hip.h (with strategy.hip.h,
 // penalties.hip.h, events.hip.h, paces.hip.h, weather.hip.h and grids.hip.h) with g++ through the stand-in <hip/hip_runtime.h> of this directory and
 // calls the real __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_gaps_kernel<false / true>,
+// race_window_kernel<false / true>,
 // race_conditions_kernel<false / true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false /
 // true>, race_fastest_kernel, the thirteen instantiations of race_scenario_kernel, penalties_count, events_count,
 // paces_count, weather_count, grid_count.
@@ -13,7 +14,7 @@
 // stand-in header is correct for a block of one thread); blockIdx.y (states, scenarios) is looped over here.  The
 // state and plan arguments go through csrc/plan_pack.h, the text the C ABI itself uses.
 //
-// Not run here: trace_count_positions, gaps_count_rows and moves_count_laps (__shfl_down), the matchups kernel and
+// Not run here: trace_count_positions, gaps_count_rows, window_count_rows and moves_count_laps (__shfl_down), the matchups kernel and
 // stints_count (__ballot), moves_count_drivers (a fixed block of 256 threads), and
 // trace_count_laps, trace_count_records and strategy_count_deltas, whose loops are written for their fixed block of 256
 // threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
@@ -21,11 +22,11 @@
 // operation and strides by its block's size, so it does run here, as blocks of one thread; so do penalties_count, events_count
 // paces_count, weather_count and grid_count.
 //
-// Shared text: the five analysis calls (emu_generic_trace, emu_gaps_run, emu_conditions_run, emu_stints_run,
-// emu_moves_run) start with analysis_setup, the seven scenario calls are scenario_run with their rule sets.
+// Shared text: the six analysis calls (emu_generic_trace, emu_gaps_run, emu_window_run, emu_conditions_run,
+// emu_stints_run, emu_moves_run) start with analysis_setup, the seven scenario calls are scenario_run with their rule sets.
 //
 // Used by tests/test_generic_host_build.py (race, resume, trace, strategies) and by tests/test_<call>_host_build.py for
-// gaps, conditions, stints, moves, fastest, penalties, events, paces, combined, weather and grids, each through its helper
+// gaps, pit_window, conditions, stints, moves, fastest, penalties, events, paces, combined, weather and grids, each through its helper
 // tests/<call>_host_build.py (tests/kernel_host_build.py compiles this file); the stand-alone programs
 // tools/emu/sanitize_{penalties,events,paces,combined,bonus,weather,grids}_main.cpp are built with it for
 // tests/test_{penalties,events,paces,combined,fastest,weather,grids}_sanitize.py.
@@ -37,6 +38,7 @@
 #include "../../monte_carlo_gp_amd/csrc/params_build.h"
 #include "../../monte_carlo_gp_amd/csrc/trace.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/gaps.hip.h"
+#include "../../monte_carlo_gp_amd/csrc/pit_window.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/conditions.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/stints.hip.h"
 #include "../../monte_carlo_gp_amd/csrc/moves.hip.h"
@@ -86,7 +88,7 @@ void one_thread_block(uint32_t grid_y)
     gridDim = {1, grid_y, 1};
 }
 
-// The start of the five analysis calls (trace, gaps, conditions, stints, moves): the parameter block, the source (a state
+// The start of the six analysis calls (trace, gaps, pit windows, conditions, stints, moves): the parameter block, the source (a state
 // or grid_probs; the trace passes no state, so it needs grid_probs), the call's own complaint `own` (NULL: none), the
 // staging's stride (masks: conditions' u64 masks sit behind the rows, so a multiple of 8), the state as the kernels read
 // it (zero from the grid) and a block of one thread.
@@ -330,6 +332,33 @@ int emu_gaps_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *
     const auto kernel = state ? &mcgp::race_gaps_kernel<true> : &mcgp::race_gaps_kernel<false>;
     kernel(&kp, &st, table, n_edges, pairs, n_pairs, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32), hist, stage,
            stride, (uint32_t)n_sims);
+    return MCGP_OK;
+}
+
+// race_window_kernel<false> (state NULL: from the grid) or <true>: simulations sim_offset + [0, n_sims).  hist [n][n] is
+// accumulated into; stage [(L - first_lap + 1) 5 n_windows][stride] (stride >= n_sims) is written.
+int emu_window_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                   uint32_t n, uint32_t n_edges, const double *edges, uint32_t n_windows, const uint8_t *window_drivers,
+                   const double *window_losses, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist,
+                   uint8_t *stage, uint64_t stride, const char **err)
+{
+    static mcgp::KParams kp;
+    mcgp::ResumeState st;
+    bool bad = n_edges < 1 || n_edges > mcgp::kMaxGapEdges || n_windows < 1 || n_windows > mcgp::kMaxPitWindows;
+    for (uint32_t w = 0; !bad && w < n_windows; ++w)
+        bad = window_drivers[w] >= n || !std::isfinite(window_losses[w]) || !(window_losses[w] >= 0.0);
+    const int rc = analysis_setup(cfg, drv, grid_probs, state, n, n_sims, stride, false,
+                                  bad ? "n_edges in [1, 63], n_windows in [1, 64], drivers below n, losses finite and >= 0"
+                                      : nullptr, &kp, &st, err);
+    if (rc != MCGP_OK) return rc;
+    double table[mcgp::kGapEdgeSlots];                      // the tables padded as the C ABI uploads them
+    for (uint32_t i = 0; i < mcgp::kGapEdgeSlots; ++i) table[i] = i < n_edges ? edges[i] : HUGE_VAL;
+    uint8_t drivers[mcgp::kWindowSlots] = {};
+    double losses[mcgp::kWindowSlots] = {};
+    for (uint32_t w = 0; w < n_windows; ++w) drivers[w] = window_drivers[w], losses[w] = window_losses[w];
+    const auto kernel = state ? &mcgp::race_window_kernel<true> : &mcgp::race_window_kernel<false>;
+    kernel(&kp, &st, table, n_edges, drivers, losses, n_windows, n_sims, sim_offset, (uint32_t)seed, (uint32_t)(seed >> 32),
+           hist, stage, stride, (uint32_t)n_sims);
     return MCGP_OK;
 }
 
