@@ -37,7 +37,7 @@ extern "C" {
  * mcgp_run_championship_rounds likewise; mcgp_run_conditions, mcgp_run_stints and mcgp_run_moves too; and
  * mcgp_run_championship_bonus; mcgp_time_penalty and mcgp_run_penalties; mcgp_lap_event and mcgp_run_events;
  * mcgp_run_championship_live; mcgp_pace_offset and mcgp_run_paces; mcgp_grid_edit and mcgp_run_grids;
- * mcgp_run_pit_windows */
+ * mcgp_run_pit_windows; mcgp_pace_prior and mcgp_run_priors */
 #define MCGP_ABI_VERSION 6
 #define MCGP_MAX_CARS 32
 #define MCGP_MAX_LAPS 1000
@@ -851,6 +851,73 @@ int32_t mcgp_run_grids(const mcgp_config *cfg, const mcgp_drivers *drv, const do
                        const uint32_t *edit_count, const mcgp_grid_edit *edits, uint64_t n_sims, uint64_t sim_offset,
                        uint64_t seed, int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *start_out,
                        uint64_t *gain_out, uint8_t *orders_out);
+
+/* A pace prior: in a scenario of mcgp_run_priors, every simulation draws an error of `driver`'s base pace
+ * (MCGP_PRIOR_DRIVER) or one error shared by the drivers in `members` (MCGP_PRIOR_GROUP: a team), normal with standard
+ * deviation `sigma` seconds a lap. */
+#define MCGP_MAX_SCENARIO_PRIORS 64
+#define MCGP_MAX_PRIOR_EDGES 15
+enum { MCGP_PRIOR_DRIVER = 0, MCGP_PRIOR_GROUP = 1 };
+typedef struct mcgp_pace_prior {
+    int32_t kind;       /* MCGP_PRIOR_* */
+    int32_t driver;     /* DRIVER: 0 .. n - 1; GROUP: 0 */
+    uint32_t members;   /* GROUP: bit d = driver d; at least one bit, none at or above n; DRIVER: 0 */
+    uint32_t pad;
+    double sigma;       /* seconds a lap, finite, 0 <= sigma <= 10 */
+} mcgp_pace_prior;
+
+/* Pace uncertainty: one race under n_scenarios sets of planned pit stops AND pace priors ("the pace figures are FP1
+ * estimates, good to 0.15 s a driver and 0.2 s a team: how sure are these odds, and what is a tenth worth to VER?"),
+ * with common random numbers.  Scenario s holds plan_count[s] plans (concatenated in `plans`; exactly
+ * mcgp_run_strategies' plans, with its checks; `plans` may be NULL when every count is 0) and prior_count[s] items
+ * (concatenated in `priors`, which may be NULL when every count is 0).  Per scenario a driver has at most one DRIVER item
+ * and belongs to at most one GROUP item; a scenario has at most MCGP_MAX_SCENARIO_PRIORS items.
+ *   - draws: simulation i has id sim_offset + i = c1 << 32 | c0, and block j is philox4x32_10(c0, c1, 0, 5 << 16 | j)
+ *     under the seed, a purpose no other draw has.  Driver d's own deviate is word d & 3 of block d >> 2; the deviate of a
+ *     group whose lowest member is g is word g & 3 of block 8 + (g >> 2); z is the word through the model's binary32
+ *     inverse-normal table.  A deviate depends on (seed, id, driver index) alone: it is the same in every scenario, from
+ *     the grid and from a state, so two scenarios that differ only in their sigmas are compared under common random
+ *     numbers.  Only blocks that hold a wanted deviate are drawn.  Every other random word stays where it is;
+ *   - offset x_d, binary32 seconds a lap, in this arithmetic: t = sigma_own * (double)z_d for a driver with a DRIVER item,
+ *     else t = +0.0; for a member of a group t = t + sigma_group * (double)z_g; x_d = (float)t.  A driver with neither
+ *     kind of item has x_d = +0.0f;
+ *   - b = base_pace[d] + (double)x_d, one binary64 addition, replaces base_pace[d] where mcgp_run_paces puts its b and
+ *     nowhere else: lap 1's base_lap; the lap time of laps >= 2; the pace of the overtake model, in the candidate scan and
+ *     in the attempt probability, on all three passes.  From a state it applies to laps state->lap + 1 .. L;
+ *   - bins: `edges` holds n_edges (0 .. MCGP_MAX_PRIOR_EDGES) finite, strictly increasing seconds, the same for every
+ *     scenario; the bin of x_d is the number of edges e with e <= (double)x_d (an IEEE compare: -0.0 counts as 0.0), which
+ *     is searchsorted(edges, x, side='right'); B = n_edges + 1 bins.
+ * Identities: a scenario without items, or whose sigmas are all 0, is cell for cell the same scenario of
+ * mcgp_run_strategies; simulation i of a scenario is the race under base_pace[d] + (double)x_d(i), which mcgp_run_paces
+ * gives with a LAPS offset [first, L] of x_d(i) seconds on every driver.
+ *   hist_out    [S][n][n]       [scenario][driver][position - 1]
+ *   delta_out   [S][n][2n - 1]  as mcgp_run_strategies': paired position changes against scenario 0; or NULL
+ *   draws_out   [S][n][B][n]    [scenario][driver][bin of x_d][position - 1]: the driver's finishing distribution by its
+ *                               own drawn error, a pace-sensitivity curve; every [s][d] block sums to n_sims; or NULL
+ *   offsets_out [S][n_sims][n]  x_d of each simulation; or NULL
+ *   orders_out  [S][n_sims][n]  driver index classified p-th, or NULL
+ * hist_out, delta_out and draws_out are ACCUMULATED into, offsets_out and orders_out are written, and all only after every
+ * launch has succeeded: on an error they are left as they were.  Every argument is checked before any device lookup: what
+ * mcgp_run_strategies checks (n_scenarios, plans, the state, grid_probs, deviates other than MCGP_DEVIATES_32, NULLs),
+ * prior_count NULL or above 64, `priors` NULL with a non-zero count, n_edges above 15, `edges` NULL with n_edges > 0, an
+ * edge that is not finite or not above the one before, a kind outside the enum, a driver outside [0, n), non-zero
+ * members on a DRIVER item or a non-zero driver on a GROUP item, empty members or a bit at or above n, a sigma that is
+ * not finite, negative or above 10, a second DRIVER item of one driver and a driver in two groups are MCGP_E_BAD_ARG with
+ * a message that names the scenario, the item and the field.  n_sims == 0 succeeds without a device.  The device work goes
+ * chunk by chunk through mcgp_run_strategies' staging budget (two bytes per scenario, simulation and driver, and four
+ * more when offsets_out is wanted) that one counting kernel reads; device memory does not grow with n_sims.  Any split of
+ * [0, N) over calls, sim_offsets or devices sums to the same counts.  mcgp_last_kernel_name afterwards is
+ * "mcgp::race_priors_kernel".  Added entry point only: MCGP_ABI_VERSION stays 6 and a caller tests for the symbol.
+ * Not in this call: uncertainty in tyre degradation, variance or retirement rates; MCGP_DEVIATES_53; the register kernels;
+ * the other what-if rule sets.
+ * Launch shape: a lane keeps its n binary32 offsets in LDS behind its rows (4n bytes: 27n against 23n a lane), so a block
+ * may hold one wave fewer than mcgp_run_strategies' (DESIGN 3.24 has the shape and the price). */
+int32_t mcgp_run_priors(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                        const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                        const mcgp_pit_plan *plans, const uint32_t *prior_count, const mcgp_pace_prior *priors,
+                        uint32_t n_edges, const double *edges, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                        int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *draws_out, float *offsets_out,
+                        uint8_t *orders_out);
 
 /* Race time gaps: the model's binary64 cumulative times, counted on the device as histograms over caller-given edges
  * (seconds): every car's gap to the leader by lap, the lead (winning margin on the last lap) and the gap between named

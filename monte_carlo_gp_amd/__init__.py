@@ -15,6 +15,7 @@ RaceSimulator.run_paces adds lap-time offsets to the scenarios (PaceOffset, Pace
 RaceSimulator.run_combined holds plans, penalties, events and offsets in one scenario (CombinedResult: a safety car on lap 31, a penalty served under it);
 RaceSimulator.run_weather changes the track condition by lap (TrackChange, WeatherModel, WeatherResult: rain from lap 30, who gains by boxing at once);
 RaceSimulator.run_grids edits the starting grid (GridEdit, GridResult: a ten-place drop, a pit-lane start, a front row fixed by qualifying);
+RaceSimulator.run_priors draws a pace error per driver and simulation (PacePrior, PriorResult: how sure are these odds when the pace figures are FP1 estimates; what a tenth is worth);
 RaceSimulator.run_stints counts the model's tyre stints (StintResult: stop laps, compound sequences, odds by stop count);
 RaceSimulator.run_moves counts how the field moves (MoveResult: grid-to-finish odds, start gains, passes by driver, lap and pair);
 RaceSimulator.run_conditions counts combinations and conditional odds (conditions.parse, Condition, ConditionResult).
@@ -22,14 +23,14 @@ The compute path is the HIP library libmcgp_hip.so (C ABI: include/mcgp.h); ther
 CPU fallback.
 """
 from .simulation import (DEFAULT_GAP_EDGES, CarState, ChampionshipResult, CombinedResult, EventResult, GapResult, GridEdit, GridResult, MatchupResult,  # noqa: F401
-                         MoveResult, PaceOffset, PaceResult, PenaltyResult, PitPlan, PitWindowResult, RaceConfig, RaceEvent, RaceSimulator, RaceState, StintResult, StrategyResult,
+                         MoveResult, PaceOffset, PacePrior, PaceResult, PenaltyResult, PitPlan, PitWindowResult, PriorResult, RaceConfig, RaceEvent, RaceSimulator, RaceState, StintResult, StrategyResult,
                          TimePenalty, TraceResult, TrackChange, WeatherModel, WeatherResult,
                          decode_stints, encode_stints, histogram_to_probs, pit_window, run_championship,
                          run_monte_carlo_batch)
 from .conditions import Condition, ConditionResult  # noqa: F401
 from . import conditions, config  # noqa: F401
 
-__all__ = ['DEFAULT_GAP_EDGES', 'CarState', 'ChampionshipResult', 'CombinedResult', 'Condition', 'ConditionResult', 'EventResult', 'GapResult', 'GridEdit', 'GridResult', 'MatchupResult', 'MoveResult', 'PaceOffset', 'PaceResult', 'PenaltyResult', 'PitPlan', 'PitWindowResult', 'RaceConfig', 'RaceEvent',
+__all__ = ['DEFAULT_GAP_EDGES', 'CarState', 'ChampionshipResult', 'CombinedResult', 'Condition', 'ConditionResult', 'EventResult', 'GapResult', 'GridEdit', 'GridResult', 'MatchupResult', 'MoveResult', 'PaceOffset', 'PacePrior', 'PaceResult', 'PenaltyResult', 'PitPlan', 'PitWindowResult', 'PriorResult', 'RaceConfig', 'RaceEvent',
            'RaceSimulator', 'RaceState', 'StintResult', 'StrategyResult', 'TimePenalty', 'TraceResult', 'TrackChange', 'WeatherModel', 'WeatherResult', 'decode_stints', 'encode_stints',
            'histogram_to_probs', 'pit_window',
            'run_championship', 'run_monte_carlo_batch', 'conditions', 'config']

@@ -131,6 +131,19 @@ class McgpGridEdit(C.Structure):
     _fields_ = [('driver', C.c_int32), ('kind', C.c_int32), ('value', C.c_int32), ('seconds', C.c_double)]
 
 
+MAX_SCENARIO_PRIORS = 64                           # include/mcgp.h: MCGP_MAX_SCENARIO_PRIORS, MCGP_PRIOR_*
+MAX_PRIOR_EDGES = 15
+PRIOR_DRIVER, PRIOR_GROUP = range(2)
+MAX_PRIOR_SIGMA = 10.0
+
+
+class McgpPacePrior(C.Structure):
+    """mcgp_pace_prior: the standard deviation of one driver's, or one group's shared, pace error in a scenario of
+    mcgp_run_priors."""
+    _fields_ = [('kind', C.c_int32), ('driver', C.c_int32), ('members', C.c_uint32), ('pad', C.c_uint32),
+                ('sigma', C.c_double)]
+
+
 class McgpTrackChange(C.Structure):
     """mcgp_track_change: the track condition of laps first_lap..last_lap in a scenario of mcgp_run_weather."""
     _fields_ = [('first_lap', C.c_int32), ('last_lap', C.c_int32), ('condition', C.c_int32)]
@@ -324,7 +337,8 @@ EXPORTS = ('mcgp_abi_version', 'mcgp_build_hash', 'mcgp_run_batch', 'mcgp_device
            'mcgp_run_from_state', 'mcgp_run_trace', 'mcgp_run_strategies', 'mcgp_run_gaps', 'mcgp_run_conditions',
            'mcgp_run_championship_rounds', 'mcgp_run_stints', 'mcgp_run_moves', 'mcgp_run_championship_bonus',
            'mcgp_run_penalties', 'mcgp_run_events', 'mcgp_run_championship_live', 'mcgp_run_paces',
-           'mcgp_run_combined', 'mcgp_run_weather', 'mcgp_run_grids', 'mcgp_run_pit_windows')
+           'mcgp_run_combined', 'mcgp_run_weather', 'mcgp_run_grids', 'mcgp_run_pit_windows',
+           'mcgp_run_priors')
 
 
 # mcgp_run_gaps(cfg, drv, grid_probs, state, n, n_edges, edges, n_pairs, pairs, n_sims, sim_offset, seed, device, hist_out,
@@ -501,6 +515,15 @@ def lib():
                                          C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan), C.POINTER(C.c_uint32),
                                          C.POINTER(McgpGridEdit), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32,
                                          u64p, u64p, u64p, u64p, C.POINTER(C.c_uint8)]
+        if 'mcgp_run_priors' not in missing:
+            # the plans, (count, items), (n_edges, edges); hist, delta, draws, offsets, orders
+            u64p = C.POINTER(C.c_uint64)
+            L.mcgp_run_priors.restype = C.c_int32
+            L.mcgp_run_priors.argtypes = [C.POINTER(McgpConfig), C.POINTER(McgpDrivers), dp, C.POINTER(McgpRaceState),
+                                          C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(McgpPitPlan),
+                                          C.POINTER(C.c_uint32), C.POINTER(McgpPacePrior), C.c_uint32, dp, C.c_uint64,
+                                          C.c_uint64, C.c_uint64, C.c_int32, u64p, u64p, u64p, C.POINTER(C.c_float),
+                                          C.POINTER(C.c_uint8)]
         if 'mcgp_run_gaps' not in missing:
             L.mcgp_run_gaps.restype = C.c_int32
             L.mcgp_run_gaps.argtypes = GAPS_ARGTYPES

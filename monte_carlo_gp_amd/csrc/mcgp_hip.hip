@@ -28,6 +28,7 @@
 #include "pace_pack.h"
 #include "event_pack.h"
 #include "weather_pack.h"
+#include "prior_pack.h"
 #include "grid_pack.h"
 #include "scenario.hip.h"
 #include "champ_pack.h"
@@ -457,7 +458,8 @@ int pack_state(const mcgp_race_state *state, uint32_t n, int total_laps, uint64_
 // kernel); the number of blocks per CU follows from LDS and the kernel's register allocation.
 void launch_geometry(const DeviceCtx &c, uint32_t n, bool is_reg, KernelFn kernel, uint64_t n_sims, uint32_t *grid,
                      uint32_t *block, uint32_t *lds, int reg_waves = 0 /* 0: the register kernel's default block shape */,
-                     bool wide = false /* the reference-width build: its block also holds table rows (WideGeo) */, int total_laps = 0)
+                     bool wide = false /* the reference-width build: its block also holds table rows (WideGeo) */, int total_laps = 0,
+                     size_t lane_lds = 0 /* a generic-shaped kernel's own LDS bytes per lane behind the rows (mcgp_run_priors) */)
 {
     // waves per CU the kernel's register allocation admits: 4 SIMDs x floor(512 / VGPRs, granule 8), at most 8 each
     int reg_cap = 8;
@@ -478,7 +480,8 @@ void launch_geometry(const DeviceCtx &c, uint32_t n, bool is_reg, KernelFn kerne
         bytes = wide ? mcgp::wide_launch_lds_bytes((int)n, waves, total_laps)
                      : mcgp::shared_lds_bytes_reg((int)n) + (size_t)waves * 64 * mcgp::per_thread_lds_bytes_reg((int)n);
     } else {
-        const size_t per_wave = 64 * mcgp::per_thread_lds_bytes((int)n);
+        const size_t per_lane = mcgp::per_thread_lds_bytes((int)n) + lane_lds;
+        const size_t per_wave = 64 * per_lane;
         waves = (int)((c.lds_per_block - mcgp::kSharedTableBytes) / per_wave);
         if (waves > 8) waves = 8;
         if (waves < 1) waves = 1;
@@ -486,7 +489,7 @@ void launch_geometry(const DeviceCtx &c, uint32_t n, bool is_reg, KernelFn kerne
         if (n_sims < threads) threads = (uint32_t)(((n_sims + 63) / 64) * 64);
         if (threads == 0) threads = 64;
         waves = (int)(threads / 64);
-        bytes = mcgp::kSharedTableBytes + (size_t)threads * mcgp::per_thread_lds_bytes((int)n);
+        bytes = mcgp::kSharedTableBytes + (size_t)threads * per_lane;
     }
     blocks_per_cu = (int)(c.lds_per_block / bytes);
     if (blocks_per_cu * waves > reg_cap) blocks_per_cu = reg_cap / waves;
@@ -505,9 +508,9 @@ void launch_geometry(const DeviceCtx &c, uint32_t n, bool is_reg, KernelFn kerne
 // `n_sims` simulations; MCGP_E_HIP when its block needs more LDS than the device offers.  `name` is the kernel's, for
 // the message.
 int generic_geometry(const DeviceCtx &c, KernelFn kernel, const char *name, uint32_t n, uint64_t n_sims, uint32_t *grid,
-                     uint32_t *block, uint32_t *lds)
+                     uint32_t *block, uint32_t *lds, size_t lane_lds = 0)
 {
-    launch_geometry(c, n, false, kernel, n_sims, grid, block, lds);
+    launch_geometry(c, n, false, kernel, n_sims, grid, block, lds, 0, false, 0, lane_lds);
     if (*lds > c.lds_per_block)
         return fail(MCGP_E_HIP, std::string("the ") + name + " kernel's block needs " + std::to_string(*lds) +
                                     " bytes of LDS, the device offers " + std::to_string(c.lds_per_block) + " per block");
@@ -928,16 +931,17 @@ int on_device(int32_t device, bool timed, Body &&body)
 // handed to body(done, m, gx, block, lds, n_batches): simulations done .. done + m - 1 of the call in a launch of (gx,
 // rows) blocks, each striding over the chunk's n_batches batches of `block` simulations.  The body launches the race
 // and its counting kernels, before the next chunk overwrites the staging.  Afterwards the first (fullest) chunk's shape
-// is what mcgp_last_launch_info reports, under `kernel_name`, and the counts laid out in `ws` are downloaded.
+// is what mcgp_last_launch_info reports, under `kernel_name`, and the counts laid out in `ws` are downloaded.  lane_lds:
+// the kernel's own LDS bytes per lane behind the generic rows (launch_geometry).
 template <class Body>
 int staged_run(DeviceCtx &c, KernelFn geo_fn, const char *geo_name, const char *kernel_name, uint32_t n, uint32_t rows,
-               uint64_t n_sims, uint64_t chunk, const Layout &ws, Counts &counts, Body &&body)
+               uint64_t n_sims, uint64_t chunk, const Layout &ws, Counts &counts, Body &&body, size_t lane_lds = 0)
 {
     uint32_t grid0 = 0, block0 = 0, lds0 = 0;
     for (uint64_t done = 0; done < n_sims; done += chunk) {
         const uint64_t m = (n_sims - done) < chunk ? (n_sims - done) : chunk;
         uint32_t grid = 0, block = 0, lds = 0;
-        int r = generic_geometry(c, geo_fn, geo_name, n, m * rows, &grid, &block, &lds);
+        int r = generic_geometry(c, geo_fn, geo_name, n, m * rows, &grid, &block, &lds, lane_lds);
         if (r != MCGP_OK) return r;
         const uint64_t n_batches = (m + block - 1) / block;
         const uint32_t gx = (uint32_t)std::min<uint64_t>(n_batches, (grid + rows - 1) / rows);
@@ -972,6 +976,11 @@ struct ScenarioChunk {
     uint16_t *car;                          // [S][m][n] laps carried (with weather: laps on the wrong tyres; with grid
                                             // edits: start slots)
     const mcgp::GridScenario *gr;           // with grid edits: the edit table, which the kernel reads through `pens`
+    // with priors: the item table, which the kernel reads through `pens`; [S][m][n] bins of the drawn offsets, which it
+    // writes through `carried`; [S][m][n] offsets (NULL: not wanted), which it writes through `ev_stage`
+    const mcgp::PriorScenario *pr;
+    uint8_t *bins;
+    float *offs;
 };
 
 // Grid width of a counting kernel over m simulations in blocks of `block` threads: the tiles, but no more blocks than
@@ -1019,12 +1028,12 @@ struct ScenarioTable {
 // fix-up on the host (empty: none).
 struct ScenarioOutput {
     uint64_t *out;
-    size_t (*cells)(size_t S, size_t n, size_t L);
+    std::function<size_t(size_t S, size_t n, size_t L)> cells;
     std::function<void(unsigned long long *extra, size_t rows, uint64_t n_sims)> fix_up;
 };
 
-// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces, mcgp_run_combined, mcgp_run_weather and
-// mcgp_run_grids each have of their own; run_scenarios has the rest.
+// What mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events, mcgp_run_paces, mcgp_run_combined, mcgp_run_weather,
+// mcgp_run_grids and mcgp_run_priors each have of their own; run_scenarios has the rest.
 struct ScenarioKind {
     const char *what;                       // the call in check_deviates_32's message
     // generic_geometry's and note_launch's name of the race kernel.  These are the documented names of the calls
@@ -1042,6 +1051,11 @@ struct ScenarioKind {
     std::function<void(const ScenarioChunk &, uint64_t grid_cap, unsigned long long *delta, unsigned long long *const *extra)>
         count;
     std::vector<ScenarioOutput> outputs;                                 // the kind's own count segments
+    size_t lane_lds = 0;                                                 // its lanes' own LDS bytes behind the generic rows
+    // what it reads back per chunk beside the counts (simulations done .. done + m - 1 of the call are staged), into
+    // memory of its own, and hands to the caller once everything has run; empty: nothing
+    std::function<int(const ScenarioChunk &, uint64_t done)> read_back;
+    std::function<void()> hand_over;
 };
 
 int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
@@ -1133,10 +1147,13 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
         return staged_run(c, reinterpret_cast<KernelFn>(kernel), k.geo_name, k.kernel_name, n, S, n_sims, chunk, ws, counts,
                           [&](uint64_t done, uint64_t m, uint32_t gx, uint32_t block, uint32_t lds, uint32_t n_batches) -> int {
             l.gx = gx, l.block = block, l.lds = lds, l.n_batches = n_batches, l.m = m, l.first_sim = sim_offset + done;
-            const mcgp::PenaltyScenario *pens = l.gr ? reinterpret_cast<const mcgp::PenaltyScenario *>(l.gr) : l.pn;
+            const mcgp::PenaltyScenario *pens = l.gr   ? reinterpret_cast<const mcgp::PenaltyScenario *>(l.gr)
+                                                : l.pr ? reinterpret_cast<const mcgp::PenaltyScenario *>(l.pr) : l.pn;
+            uint32_t *evs = l.pr ? reinterpret_cast<uint32_t *>(l.offs) : l.evs;
+            uint16_t *car = l.pr ? reinterpret_cast<uint16_t *>(l.bins) : l.car;
             hipLaunchKernelGGL(kernel, dim3(l.gx, l.S), dim3(l.block), l.lds, nullptr, l.kp, l.st, l.sc, l.sl, pens, l.nl, l.el,
                                l.ps, l.pl, l.sec, l.m, l.first_sim, (uint32_t)l.seed, (uint32_t)(l.seed >> 32), l.hist, l.stage,
-                               l.evs, l.car, l.n_batches);
+                               evs, car, l.n_batches);
             HIP_TRY(hipGetLastError());
             if (count_delta || want_extra) {
                 std::vector<unsigned long long *> extra;
@@ -1153,8 +1170,8 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
                         for (uint32_t d = 0; d < n; ++d) ord[pos[d] & k.pos_mask] = (uint8_t)d;
                     }
             }
-            return MCGP_OK;
-        });
+            return k.read_back ? k.read_back(l, done) : MCGP_OK;
+        }, k.lane_lds);
     });
     if (rc != MCGP_OK) return rc;
     unsigned long long *b = counts.v.data() + c_hist;
@@ -1175,6 +1192,7 @@ int32_t run_scenarios(const mcgp_config *cfg, const mcgp_drivers *drv, const dou
     }
     counts.add_to(segs);
     if (orders_out) std::memcpy(orders_out, orders.data(), orders.size());
+    if (k.hand_over) k.hand_over();
     return MCGP_OK;
 }
 
@@ -2534,6 +2552,56 @@ int32_t mcgp_run_grids(const mcgp_config *cfg, const mcgp_drivers *drv, const do
     k.outputs = {{start_out, [](size_t S, size_t n, size_t) { return S * n * n; }, nullptr},
                  {gain_out, [](size_t S, size_t n, size_t) { return S * n * (2 * n - 1); }, nullptr}};
     return run_scenarios(cfg, drv, grid_probs, nullptr, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
+                         hist_out, delta_out, orders_out, k);
+}
+
+int32_t mcgp_run_priors(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs,
+                        const mcgp_race_state *state, uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count,
+                        const mcgp_pit_plan *plans, const uint32_t *prior_count, const mcgp_pace_prior *priors,
+                        uint32_t n_edges, const double *edges, uint64_t n_sims, uint64_t sim_offset, uint64_t seed,
+                        int32_t device, uint64_t *hist_out, uint64_t *delta_out, uint64_t *draws_out, float *offsets_out,
+                        uint8_t *orders_out)
+{
+    std::vector<mcgp::PriorScenario> pscen;
+    std::vector<float> offsets, back;       // collected on the host, handed over only once everything has run
+    ScenarioKind k = {"priors run", "priors", "mcgp::race_priors_kernel", mcgp::kRulePriors};
+    // the call-wide edges are checked with the counts, in front of the items
+    k.tables = {{"prior_count", "priors", prior_count, priors, [&](uint64_t *n_priors) {
+        const std::string e = mcgp::check_prior_counts(n_scenarios, prior_count, n_priors);
+        return e.empty() ? mcgp::check_prior_edges(n_edges, edges) : e;
+    }}};
+    k.pack = [&](int, bool) { return mcgp::pack_priors(n_scenarios, prior_count, priors, n, n_edges, edges, &pscen); };
+    // a position byte and a bin byte per driver, and its binary32 offset when the offsets are wanted
+    k.sim_bytes = offsets_out ? (size_t)n * 6 : (size_t)n * 2;
+    k.lane_lds = mcgp::prior_lane_lds_bytes((int)n);
+    // the kernel reads the item table and writes the bins and the offsets through the arguments of rule sets it never meets
+    k.regions = [&](Layout &ws, ScenarioChunk &l, uint64_t chunk) {
+        if (offsets_out) ws.add(&l.offs, (size_t)n_scenarios * chunk * n);
+        ws.add(&l.bins, (size_t)n_scenarios * chunk * n);
+        ws.add(&l.pr, pscen.size(), pscen.data());
+    };
+    // one pass: the deltas' layer (which returns at once when they are not wanted), then (draws wanted) one per driver
+    k.count = [&](const ScenarioChunk &l, uint64_t grid_cap, unsigned long long *d_delta, unsigned long long *const *extra) {
+        const uint32_t gz = extra[0] ? 1u + n : 1u;
+        hipLaunchKernelGGL(mcgp::priors_count,
+                           dim3(count_grid_x(l.m, mcgp::kPriorsCountBlock, grid_cap, (uint64_t)l.S * gz), l.S, gz),
+                           dim3(mcgp::kPriorsCountBlock), 0, nullptr, l.stage, l.bins, l.m, n, n_edges + 1u, d_delta, extra[0]);
+    };
+    // draws [S][n][n_edges + 1][n]: every cell is counted, no fix-up
+    k.outputs = {{draws_out, [n_edges](size_t S, size_t n, size_t) { return S * n * (n_edges + 1) * n; }, nullptr}};
+    if (offsets_out) {
+        k.read_back = [&](const ScenarioChunk &l, uint64_t done) -> int {
+            if (offsets.empty()) offsets.resize((size_t)n_scenarios * n_sims * n);
+            back.resize((size_t)n_scenarios * l.m * n);
+            HIP_TRY(hipMemcpy(back.data(), l.offs, back.size() * sizeof(float), hipMemcpyDeviceToHost));
+            for (uint32_t si = 0; si < n_scenarios; ++si)
+                std::memcpy(offsets.data() + ((size_t)si * n_sims + done) * n, back.data() + (size_t)si * l.m * n,
+                            (size_t)l.m * n * sizeof(float));
+            return MCGP_OK;
+        };
+        k.hand_over = [&] { std::memcpy(offsets_out, offsets.data(), offsets.size() * sizeof(float)); };
+    }
+    return run_scenarios(cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, n_sims, sim_offset, seed, device,
                          hist_out, delta_out, orders_out, k);
 }
 

@@ -18,6 +18,7 @@ constexpr uint32_t kPurposeEvent = 1u << 16;
 constexpr uint32_t kPurposeCar = 2u << 16;
 constexpr uint32_t kPurposeOvt = 3u << 16;
 constexpr uint32_t kPurposeRetire = 4u << 16;
+constexpr uint32_t kPurposePrior = 5u << 16;       // the pace draws of mcgp_run_priors (priors.hip.h)
 
 // ---- retirements of laps >= 2 (reference :190-197), drawn once per race ----
 // The reference retires a running car on a lap if a fresh uniform is below the driver's per-lap probability p; the lap of

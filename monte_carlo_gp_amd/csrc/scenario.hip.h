@@ -1,6 +1,6 @@
-// scenario.hip.h -- the race kernel of the seven what-if calls: mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events,
-// mcgp_run_paces, mcgp_run_combined (include/mcgp.h, which states how the rule sets meet on one lap), mcgp_run_weather
-// and mcgp_run_grids.
+// scenario.hip.h -- the race kernel of the eight what-if calls: mcgp_run_strategies, mcgp_run_penalties, mcgp_run_events,
+// mcgp_run_paces, mcgp_run_combined (include/mcgp.h, which states how the rule sets meet on one lap), mcgp_run_weather,
+// mcgp_run_grids and mcgp_run_priors.
 //
 // race_scenario_kernel<kFromState, kRules> is the generic kernel's code -- start_from_grid or start_from_state, run_laps,
 // classify_and_count -- over S scenarios of one race with common random numbers: one lane runs one (scenario, simulation)
@@ -22,9 +22,13 @@
 //                   drawn grid; every driver's start slot.  It is instantiated alone and only from the grid (a mid-race
 //                   state has no grid), and its table comes the same way: the GridScenario [S] in `pens`, the staged u16
 //                   in `carried`.
+//   kRulePriors     (priors.hip.h) draw_priors before the start; PriorPace in the pace slot of start_from_grid and of
+//                   run_laps.  It is instantiated alone, and its table comes the same way: the PriorScenario [S] in `pens`,
+//                   the staged bin bytes in `carried` (as bytes), the staged binary32 offsets in `ev_stage` (as floats).
+//                   Its lanes have n binary32 offsets in LDS behind their rows, which the launch counts.
 //
 // A slot whose bit is clear holds the model's policy (ModelPace, DrawnEvents, NoLapObserver, ModelTrack, ModelGrid), which
-// vanishes at compile time.  The instantiations are the thirteen the C ABI has: no rule set, each one alone, the first
+// vanishes at compile time.  The instantiations are the fifteen the C ABI has: no rule set, each one alone, the first
 // three together, each from the grid and, but for the grid edits, from a state.  An instantiation never reads a table whose bit is clear: callers pass NULL there.
 //
 // Every table is packed by its rule set's packer and read at wave-uniform addresses once per lap: ScenarioPit::begin_lap
@@ -39,7 +43,7 @@
 // u32 with events (the packed event counts: events_count; with all three rule sets only when ev_stage is given), n u16
 // with paces when `carried` is given (paces_count; for mcgp_run_combined both with delta NULL), n u16 with weather when
 // `carried` is given (the laps on the wrong tyres: weather_count), n u16 with grid edits when `carried` is given (the
-// start slots: grid_count).
+// start slots: grid_count), n bin bytes with priors and n floats when the offsets are wanted (priors_count).
 //
 // Price (one MI355X, S60, two scenarios x 10^6 simulations, device ms per 10^6, medians of five with max - min;
 // profiles/combined_time.txt): all three rule sets, two empty scenarios 102.84 (0.41) against 98.22 (0.39) with
@@ -55,10 +59,12 @@
 #include "paces.hip.h"
 #include "weather.hip.h"
 #include "grids.hip.h"
+#include "priors.hip.h"
 
 namespace mcgp {
 
-constexpr uint32_t kRulePenalties = 1u, kRuleEvents = 2u, kRulePaces = 4u, kRuleWeather = 8u, kRuleGrid = 16u;
+constexpr uint32_t kRulePenalties = 1u, kRuleEvents = 2u, kRulePaces = 4u, kRuleWeather = 8u, kRuleGrid = 16u,
+                   kRulePriors = 32u;
 constexpr uint32_t kRuleAll = kRulePenalties | kRuleEvents | kRulePaces;
 
 // run_laps' pit policy of a scenario: PlanPit decides the stops; after_pit adds the served SERVE_AT_STOP penalty after
@@ -120,7 +126,8 @@ struct ScenarioPit {
 // at the drivers that have an UNTIL_STOP offset in the scenario with paces.  With weather event_laps [S][L + 1] holds the
 // laps' condition bytes, lap_sec the [3][5] table and carried [S][m][n] u16 (NULL: not wanted) gets every driver's laps
 // on the wrong tyres.  With grid edits pens holds the GridScenario [S] and carried [S][m][n] u16 (NULL: not wanted) gets
-// every driver's start slot.  Pointers of a rule set outside kRules are not read: pass NULL.
+// every driver's start slot.  With priors pens holds the PriorScenario [S], carried [S][m][n] BYTES gets every driver's bin
+// and ev_stage [S][m][n] FLOATS (NULL: not wanted) its offset.  Pointers of a rule set outside kRules are not read: pass NULL.
 template <bool kFromState, uint32_t kRules>
 __global__ void __launch_bounds__(512)
 race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restrict__ state,
@@ -133,12 +140,14 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
                      uint32_t n_batches)
 {
     static_assert(kRules == 0u || kRules == kRulePenalties || kRules == kRuleEvents || kRules == kRulePaces ||
-                      kRules == kRuleAll || kRules == kRuleWeather || (kRules == kRuleGrid && !kFromState),
+                      kRules == kRuleAll || kRules == kRuleWeather || (kRules == kRuleGrid && !kFromState) ||
+                      kRules == kRulePriors,
                   "the rule sets of the C ABI");
     constexpr bool kPen = (kRules & kRulePenalties) != 0u, kEv = (kRules & kRuleEvents) != 0u;
     constexpr bool kPace = (kRules & kRulePaces) != 0u, kWx = (kRules & kRuleWeather) != 0u;
-    constexpr bool kGrid = (kRules & kRuleGrid) != 0u;
-    using Pace = std::conditional_t<kPace, OffsetPace, std::conditional_t<kWx, WeatherPace, ModelPace>>;
+    constexpr bool kGrid = (kRules & kRuleGrid) != 0u, kPri = (kRules & kRulePriors) != 0u;
+    using Pace = std::conditional_t<kPace, OffsetPace,
+                                    std::conditional_t<kWx, WeatherPace, std::conditional_t<kPri, PriorPace, ModelPace>>>;
     using Track = std::conditional_t<kWx, WeatherTrack, ModelTrack>;
     using Events = std::conditional_t<kEv, ForcedEvents, DrawnEvents>;
     using Observer = std::conditional_t<kEv, PackedEventCounter, NoLapObserver>;
@@ -158,6 +167,7 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
         const GridScenario *__restrict__ gs = reinterpret_cast<const GridScenario *>(pens) + sid;
         grid = {gs, gs->pit};
     }
+    const PriorScenario *__restrict__ pri = kPri ? reinterpret_cast<const PriorScenario *>(pens) + sid : nullptr;
     const uint32_t serve = kPen ? pen->serve : 0u, flag = kPen ? pen->flag : 0u, until = kPace ? ps->until : 0u;
     run_block(P, m, n_batches, hist + (size_t)sid * (size_t)(P->n * P->n),
               [=](const Rows &s, const LapEnv &e, uint32_t *s_hist, uint64_t local) {
@@ -166,7 +176,7 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
         // the lane's place in the stagings: worked out here where events, paces or weather stage beside the position
         // bytes, after the race otherwise (the start slots are staged after the race too)
         uint64_t lane = 0, cell = 0;
-        if constexpr (kEv || kPace || kWx) {
+        if constexpr (kEv || kPace || kWx || kPri) {
             lane = (uint64_t)sid * m + local;
             cell = lane * (uint64_t)e.n;
         }
@@ -178,6 +188,14 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
         if constexpr (kWx) {
             pace = {event_laps + lap0, lap_sec, s, nullptr, 0u};
             trk = {event_laps + lap0, crow, 0u};
+        }
+        if constexpr (kPri) {
+            // the lane's offsets, behind its rows; their bins and, where wanted, the floats are staged before the race
+            float *x = reinterpret_cast<float *>(s.out + (size_t)e.n * s.B) + s.tid;
+            float *offs = reinterpret_cast<float *>(ev_stage);
+            draw_priors(pri, e.n, e.norm, c0, c1, seed_lo, seed_hi, x, s.B, reinterpret_cast<uint8_t *>(carried) + cell,
+                        offs ? offs + cell : nullptr);
+            pace = {x, s.B, pri->items};
         }
         const ScenarioPit<kRules> pit = {plan, pen, nl, pl, kPace ? ps->until_from : nullptr, &served, &active, crow, serve,
                                          0u, 0u, 0u};
@@ -216,7 +234,7 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
         }
         classify_and_count(s, e.n, s_hist, nullptr);                                                // reference :230-242
         // each driver's classified position and, with penalties, the fate of its serve penalty
-        if constexpr (!(kEv || kPace || kWx)) cell = ((uint64_t)sid * m + local) * (uint64_t)e.n;
+        if constexpr (!(kEv || kPace || kWx || kPri)) cell = ((uint64_t)sid * m + local) * (uint64_t)e.n;
         uint8_t *row = stage + cell;
         for (int p = 0; p < e.n; ++p) {
             const uint32_t d = s.Ord(p);
@@ -253,7 +271,7 @@ race_scenario_kernel(const KParams *__restrict__ P, const ResumeState *__restric
 }
 
 // The instantiation behind a scenario call, for the launch and for its register count: `rules` is one of the five sets
-// above, kRuleWeather or, from the grid only, kRuleGrid (anything else: NULL), from the grid or from a state.
+// above, kRuleWeather, kRulePriors or, from the grid only, kRuleGrid (anything else: NULL), from the grid or from a state.
 using ScenarioKernel = decltype(&race_scenario_kernel<false, 0u>);
 inline ScenarioKernel scenario_kernel(uint32_t rules, bool from_state)
 {
@@ -267,6 +285,8 @@ inline ScenarioKernel scenario_kernel(uint32_t rules, bool from_state)
     case kRuleWeather:
         return from_state ? &race_scenario_kernel<true, kRuleWeather> : &race_scenario_kernel<false, kRuleWeather>;
     case kRuleGrid: return from_state ? nullptr : &race_scenario_kernel<false, kRuleGrid>;
+    case kRulePriors:
+        return from_state ? &race_scenario_kernel<true, kRulePriors> : &race_scenario_kernel<false, kRulePriors>;
     }
     return nullptr;
 }

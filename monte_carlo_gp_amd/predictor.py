@@ -182,7 +182,8 @@ class F1Predictor:
     def predict_weekend(self, season: int, race: str, fixture: dict | str, grid_penalties=None, circuit_info=None,
                         prediction_point: str = 'fp2', actual_grid=None, n_simulations: int = 10000,
                         seed: int | None = None, matchups: bool = False, trace: bool = False, gaps=None,
-                        conditions=None, tyres: bool = False, moves: bool = False, pit_window=None) -> dict:
+                        conditions=None, tyres: bool = False, moves: bool = False, pit_window=None,
+                        pace_uncertainty=None) -> dict:
         """Pole / win / podium probabilities for one weekend (:99-319), Monte Carlo on the GPU.
 
         matchups=True (not in the reference): the race runs through RaceSimulator.run_matchups -- the same simulations,
@@ -215,10 +216,27 @@ class F1Predictor:
         pit_window=[(driver, loss in seconds or None: the config's pit_loss), ...], or {'windows': [...], 'edges': [...]}
         (not in the reference): the race also runs through RaceSimulator.run_pit_windows -- the same simulations,
         nothing re-simulated -- and the result gains 'pit_window', the block pit_window_keys builds: per window and lap
-        the odds of a free stop, the rejoin position, the likeliest car ahead and the odds of clear air at rejoin."""
+        the odds of a free stop, the rejoin position, the likeliest car ahead and the odds of clear air at rejoin.
+
+        pace_uncertainty={'own': sigma or {driver: sigma}, 'team': sigma or {team: sigma}, 'edges': [...]} (not in the
+        reference; seconds a lap, either of 'own' and 'team' may be left out): the race also runs through
+        RaceSimulator.run_priors -- the same simulations as the forecast, and beside them the same simulations under a
+        pace error drawn per driver (own) and per team of the race config's driver_teams (shared) -- and the result gains
+        'pace_uncertainty', the block pace_uncertainty_keys builds: the odds under the draws beside the forecast's, and
+        per driver the win odds and expected points by bin of its own drawn error.  There are no default sigmas, and
+        prediction_point sets none: nobody has measured what an FP1 pace error is."""
         fixture = _open_fixture(fixture, season, race)
         inp = self.simulator_inputs(fixture, race, grid_penalties, circuit_info, prediction_point, actual_grid)
         sim = RaceSimulator(inp['config'], device=self.device)
+        if pace_uncertainty:
+            seed = sim._resolve_seed(seed)
+            if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
+                raise ValueError('pace_uncertainty runs from the host grid matrix: device_front_end must be off')
+            res = self.predict_weekend(season, race, fixture, grid_penalties, circuit_info, prediction_point, actual_grid,
+                                       n_simulations, seed, matchups, trace, gaps, conditions, tyres, moves, pit_window)
+            res['pace_uncertainty'] = self._pace_uncertainty(sim, inp, pace_uncertainty, n_simulations, seed,
+                                                             grid_probs=inp['grid_probs'])
+            return res
         if self.device_front_end and not (actual_grid and prediction_point in ('quali', 'sprint')):
             # same inputs, the matrix built on the device from the ratings (no host matrix crosses PCIe)
             ratings = {d: self.elo_system.ratings.get(d, {}).get('quali', self.elo_system.initial) for d in inp['drivers']}
@@ -244,7 +262,7 @@ class F1Predictor:
 
     def predict_from_state(self, season: int, race: str, fixture: dict | str, state, n_simulations: int = 100000,
                            seed: int | None = None, gaps=None, conditions=None, tyres: bool = False,
-                           moves: bool = False, pit_window=None):
+                           moves: bool = False, pit_window=None, pace_uncertainty=None):
         """In-race odds (not in the reference): the weekend's race inputs (simulator_inputs, as predict_weekend builds
         them) run from a mid-race RaceState of the fixture's drivers -- or from each of a list of them, with common
         random numbers -- through RaceSimulator.run_from_state.  Returns, per state, {'lap', 'win_probabilities', 'podium_probabilities',
@@ -256,13 +274,15 @@ class F1Predictor:
         state's lap on.  moves (as in predict_weekend): every state's dict gains 'moves' from RaceSimulator.run_moves on
         that state, same simulations; passes count from the state's lap on and there is no start gain.  pit_window (as
         in predict_weekend): every state's dict gains 'pit_window' from RaceSimulator.run_pit_windows on that state, same
-        simulations; the laps after the state's are recorded."""
+        simulations; the laps after the state's are recorded.  pace_uncertainty (as in predict_weekend): every state's
+        dict gains 'pace_uncertainty' from RaceSimulator.run_priors on that state; the drawn errors apply to the laps after
+        the state's."""
         fixture = _open_fixture(fixture, season, race)
         single = not isinstance(state, (list, tuple))
         states = [state] if single else list(state)
         inp = self.simulator_inputs(fixture, race)
         sim = RaceSimulator(inp['config'], device=self.device)
-        seed = sim._resolve_seed(seed) if gaps or conditions or tyres or moves or pit_window else seed
+        seed = sim._resolve_seed(seed) if gaps or conditions or tyres or moves or pit_window or pace_uncertainty else seed
         # the driver order of predict_weekend's run: a state that run's simulation i reached continues as simulation i
         probs = sim.run_from_state(n_simulations, states, inp['base_pace'], inp['tire_deg'], inp['driver_variance'],
                                    inp['driver_dnf_rates'], seed=seed, track_condition=inp['track_condition'],
@@ -304,7 +324,21 @@ class F1Predictor:
                                          track_condition=inp['track_condition'], drivers=list(inp['grid_probs']),
                                          **pit_window_options(pit_window, inp['config'].pit_loss))
                 res['pit_window'] = pit_window_keys(pw, inp['config'].dirty_air_threshold)
+        if pace_uncertainty:
+            for st, res in zip(states, out):
+                res['pace_uncertainty'] = self._pace_uncertainty(sim, inp, pace_uncertainty, n_simulations, seed, state=st)
         return out[0] if single else out
+
+    @staticmethod
+    def _pace_uncertainty(sim, inp, argument, n_simulations, seed, grid_probs=None, state=None) -> dict:
+        """The 'pace_uncertainty' block: RaceSimulator.run_priors on the weekend's race inputs with the scenarios
+        'forecast' (no prior) and 'uncertain' (the argument's priors), from the grid or from `state`."""
+        drivers = list(inp['grid_probs'])
+        priors, edges = pace_uncertainty_options(argument, drivers, inp['config'].driver_teams)
+        r = sim.run_priors(n_simulations, {'forecast': [], 'uncertain': priors}, edges, None, inp['base_pace'],
+                           inp['tire_deg'], inp['driver_variance'], inp['driver_dnf_rates'], grid_probs=grid_probs,
+                           state=state, seed=seed, track_condition=inp['track_condition'], drivers=drivers)
+        return pace_uncertainty_keys(r)
 
     def _scenario_run(self, season, race, fixture, state, seed, prediction_point, allow_single_compound):
         """What the seven scenario methods below share -> (simulator, the keyword arguments every run_* takes after its
@@ -571,6 +605,65 @@ def pit_window_keys(pw, clear_air_seconds=2.0) -> dict:
             'open_laps': pw.open_laps(w)})
     return {'edges': list(pw.edges), 'first_lap': pw.first_lap, 'total_laps': pw.total_laps, 'clear_air_seconds': edge,
             'windows': rows}
+
+
+DEFAULT_PACE_EDGES = (-0.3, -0.1, 0.0, 0.1, 0.3)      # seconds a lap: the by-draw table's bins when none are given
+
+
+def pace_uncertainty_options(argument, drivers, driver_teams):
+    """run_priors' priors and edges from predict_weekend's pace_uncertainty argument {'own': sigma or {driver: sigma},
+    'team': sigma or {team: sigma}, 'edges': [...]}: one own prior per driver that has a sigma, one group per team of
+    `driver_teams` that has a sigma and a driver in the race."""
+    from .simulation import PacePrior
+    if not isinstance(argument, dict) or set(argument) - {'own', 'team', 'edges'}:
+        raise ValueError("pace_uncertainty: a dict with any of the keys 'own', 'team', 'edges'")
+    own, team = argument.get('own'), argument.get('team')
+    if own is None and team is None:
+        raise ValueError("pace_uncertainty: give 'own', 'team' or both (there are no default sigmas)")
+    priors = []
+    if own is not None:
+        if isinstance(own, dict):
+            unknown = [d for d in own if d not in drivers]
+            if unknown:
+                raise ValueError(f'pace_uncertainty: own: {unknown} not among the drivers')
+        priors += [PacePrior.driver(d, own[d] if isinstance(own, dict) else own) for d in drivers
+                   if not isinstance(own, dict) or d in own]
+    if team is not None:
+        members = {}
+        for d in drivers:
+            members.setdefault(driver_teams.get(d, 'Unknown'), []).append(d)
+        if isinstance(team, dict):
+            unknown = [t for t in team if t not in members]
+            if unknown:
+                raise ValueError(f'pace_uncertainty: team: {unknown} not among the teams {sorted(members)}')
+        priors += [PacePrior.group(ds, team[t] if isinstance(team, dict) else team) for t, ds in members.items()
+                   if not isinstance(team, dict) or t in team]
+    edges = argument.get('edges')
+    return priors, list(DEFAULT_PACE_EDGES if edges is None else edges)
+
+
+def pace_uncertainty_keys(r) -> dict:
+    """The 'pace_uncertainty' block, JSON-safe, from a PriorResult with the scenarios 'forecast' and 'uncertain': the
+    edges and each bin's bounds (None: open), per driver the win, podium and points odds and the expected points under
+    both, the paired comparison, and by bin of the driver's own drawn error the share of simulations, the win odds and
+    the expected points (None for an empty bin)."""
+    num = lambda x: None if x is None or x != x or x in (float('inf'), float('-inf')) else float(x)
+    B = len(r.edges) + 1
+    out = {'n_simulations': int(r.n_simulations), 'edges': [float(e) for e in r.edges],
+           'bins': [[num(v) for v in r.bin_bounds(b)] for b in range(B)], 'drivers': {}}
+    points = {s: r.expected_points(s) for s in r.names}
+    for d in r.drivers:
+        i = r.drivers.index(d)
+        odds = lambda s: {'win': float(r._p(s)[i, 0]), 'podium': float(r._p(s)[i, :3].sum()),
+                          'points': float(r._p(s)[i, :10].sum()), 'expected_points': points[s][d]}
+        c = r.compare('uncertain', d)
+        out['drivers'][d] = {
+            'forecast': odds('forecast'), 'uncertain': odds('uncertain'),
+            'paired': {k: c[k] for k in ('p_better', 'p_same', 'p_worse', 'mean_gain', 'se')},
+            'by_draw': {'share': [float(v) for v in r.draw_probabilities('uncertain', d)],
+                        'win': [num(v) for v in r.win_probability_by_draw('uncertain', d)],
+                        'expected_points': [num(v) for v in r.expected_points_by_draw('uncertain', d)]}}
+    return out
 
 
 def gap_keys(g) -> dict:

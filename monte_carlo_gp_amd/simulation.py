@@ -184,8 +184,11 @@ def _dptr(a):
 
 
 def _optr(a):
-    """An output buffer as the C ABI takes it: uint64 counts or uint8 finishing orders; None (not wanted) is NULL."""
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8 if a.dtype == np.uint8 else C.c_uint64))
+    """An output buffer as the C ABI takes it: uint64 counts, uint8 finishing orders or binary32 values; None (not wanted)
+    is NULL."""
+    if a is None:
+        return None
+    return a.ctypes.data_as(C.POINTER(C.c_uint8 if a.dtype == np.uint8 else C.c_float if a.dtype == np.float32 else C.c_uint64))
 
 
 def _gap_edge_array(edges):
@@ -397,7 +400,7 @@ class RaceSimulator:
         for k, first in parts[0].items():
             if first is None:
                 total[k] = None
-            elif k == 'orders':
+            elif k in ('orders', 'offsets'):                 # written per simulation, not counted
                 total[k] = np.concatenate([p[k] for p in parts], axis=orders_axis)
             else:
                 total[k] = np.sum([p[k] for p in parts], axis=0, dtype=np.uint64).astype(np.int64)
@@ -452,7 +455,7 @@ class RaceSimulator:
 
     def _run_scenarios(self, entry, result, label, n_simulations, kinds, strategies, race, grid_probs, state, seed,
                        sim_offset, drivers, return_orders, allow_single_compound, call_wide=(), all_dry=None,
-                       grid_only=False):
+                       grid_only=False, written=None, result_args=None):
         """run_strategies, run_penalties, run_events, run_paces, run_combined, run_weather and run_grids: the race under named scenarios of pit
         plans (`strategies`) and of the call's own `kinds` of items, a list (empty for run_strategies) of (items {name:
         [item]}, item_type: their struct, pack_items: see _pack_plans, extra = (name, shape(S, n, L)): the kind's own
@@ -462,7 +465,9 @@ class RaceSimulator:
         call_wide: the call's arguments that hold for every scenario, after the kinds' (run_weather: its model).
         all_dry: scenario name -> is the track dry on every lap (None: track_condition says so for all of them); the
         two-compound rule is checked for the plans of those scenarios.  grid_only: the entry point has no state argument
-        (run_grids, which has refused a state by then)."""
+        (run_grids, which has refused a state by then).  written: {name: dtype} of the call's own outputs that are
+        written per simulation, [S][count][n], between the count arrays and the orders (run_priors: its offsets; None as a
+        dtype: NULL).  result_args: further keyword arguments of the result."""
         src = self._source(grid_probs, state, drivers)
         strategies = strategies or {}
         names = []
@@ -492,11 +497,13 @@ class RaceSimulator:
 
         def alloc(count):
             return dict({k: np.zeros(shape, np.uint64) for k, shape in shapes.items()},
+                        **{k: np.zeros((S, count, n), dt) if dt is not None else None for k, dt in (written or {}).items()},
                         orders=np.zeros((S, count, n), np.uint8) if return_orders else None)
 
+        outs = list(shapes) + list(written or {}) + ['orders']
         total = self._run_counted(n_simulations, drivers, alloc,
-                                  self._entry_call(entry, prob, head, sim_offset, seed64, list(shapes) + ['orders']), 1)
-        return result(names=names, drivers=drivers, n_simulations=n_simulations, **total)
+                                  self._entry_call(entry, prob, head, sim_offset, seed64, outs), 1)
+        return result(names=names, drivers=drivers, n_simulations=n_simulations, **total, **(result_args or {}))
 
     # ---- the scenario calls' own kinds of items: (items, struct, pack_items, (count array, its shape)) for _run_scenarios
     def _penalty_kind(self, penalties, state):
@@ -1053,6 +1060,81 @@ class RaceSimulator:
             'mcgp_run_grids', GridResult, 'edits / strategies', n_simulations, [self._grid_kind(edits)], strategies,
             (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, None, seed, sim_offset,
             drivers, return_orders, allow_single_compound, grid_only=True)
+
+    def run_priors(
+        self,
+        n_simulations: int,
+        priors: dict,
+        edges=(),
+        strategies: dict | None = None,
+        base_pace: dict | None = None,
+        tire_deg: dict | None = None,
+        driver_variance: dict | None = None,
+        driver_dnf_rates: dict | None = None,
+        grid_probs: dict | None = None,
+        state: 'RaceState | None' = None,
+        seed: int | None = None,
+        track_condition: str = 'dry',
+        sim_offset: int = 0,
+        drivers=None,
+        return_orders: bool = False,
+        return_offsets: bool = False,
+        allow_single_compound: bool = False,
+    ) -> 'PriorResult':
+        """Pace uncertainty (include/mcgp.h: mcgp_run_priors): the race under each scenario of `priors`, {name:
+        [PacePrior, ...]}, and `strategies`, {name: [PitPlan, ...]} or None; a scenario holds the priors and the plans
+        given under its name, and the scenario names are the union of the two dicts in the order given (priors first; at
+        most 64; the first is the one `compare` measures against, so give it no priors to compare against the race as
+        forecast).  Every simulation first draws an error of each driver's base pace -- PacePrior.driver's own
+        component, PacePrior.group's component shared by its members, both normal with the given sigma in seconds a lap
+        -- and races under it, wherever the model reads the base pace.  The deviates depend on the seed, the simulation
+        and the driver alone, so scenarios that differ in their sigmas are compared under common random numbers.
+        `edges` (at most 15 increasing seconds) bin each driver's own drawn error: the result's `draws` holds its
+        finishing distribution by that bin, a pace-sensitivity curve from the same simulations.  A second own prior of
+        one driver, a driver in two groups and an unknown driver raise ValueError.  return_offsets: also the drawn errors
+        [S, N, n] (binary32).  Everything else -- the remaining arguments, the plans' checks, the simulation ids and the
+        race's own draws, the seed rules and the device sharding -- is run_strategies': a scenario without priors gives
+        exactly its counts.  last_histogram: [S, n, n]."""
+        edge_arr = np.ascontiguousarray(list(edges), np.float64)
+        if edge_arr.ndim != 1 or len(edge_arr) > N.MAX_PRIOR_EDGES:
+            raise ValueError(f'edges: at most {N.MAX_PRIOR_EDGES} values, got {edge_arr.shape}')
+        if not (np.isfinite(edge_arr).all() and (np.diff(edge_arr) > 0).all()):
+            raise ValueError('edges must be finite and strictly increasing')
+        n_edges = len(edge_arr)
+        edge_buf = np.ascontiguousarray(np.concatenate([edge_arr, [0.0]]))      # (never empty: a NULL-free pointer)
+        return self._run_scenarios(
+            'mcgp_run_priors', PriorResult, 'priors / strategies', n_simulations, [self._prior_kind(priors, n_edges)],
+            strategies, (base_pace, tire_deg, driver_variance, driver_dnf_rates, track_condition), grid_probs, state, seed,
+            sim_offset, drivers, return_orders, allow_single_compound, call_wide=(n_edges, _dptr(edge_buf)),
+            written={'offsets': np.float32 if return_offsets else None}, result_args={'edges': edge_arr})
+
+    @staticmethod
+    def _prior_kind(priors, n_edges):
+        def pack(name, items, index):
+            if len(items) > N.MAX_SCENARIO_PRIORS:
+                raise ValueError(f'scenario {name!r}: at most {N.MAX_SCENARIO_PRIORS} priors, got {len(items)}')
+            packed, own, grouped = [], {}, {}
+            for it in items:
+                for code in it.codes:
+                    if str(code) not in index:
+                        raise ValueError(f'scenario {name!r}: {code!r} is not one of the drivers')
+                try:
+                    c = it.c_struct(index)
+                except ValueError as e:
+                    raise ValueError(f'scenario {name!r}: {e}') from None
+                if c.kind == N.PRIOR_DRIVER:
+                    if c.driver in own:
+                        raise ValueError(f'scenario {name!r}: {it.codes[0]} has two own priors ({own[c.driver]} and {it})')
+                    own[c.driver] = it
+                else:
+                    for code in it.codes:
+                        if index[str(code)] in grouped:
+                            raise ValueError(f'scenario {name!r}: {code} is in two groups ({grouped[index[str(code)]]} and {it})')
+                        grouped[index[str(code)]] = it
+                packed.append(c)
+            return packed
+
+        return priors, N.McgpPacePrior, pack, ('draws', lambda S, n, L: (S, n, n_edges + 1, n))
 
     def run_gaps(
         self,
@@ -3067,6 +3149,87 @@ class GridResult(StrategyResult):
         n = len(self.drivers)
         row = np.asarray(self.gain[self._s(name), self._d(driver)], np.float64) / max(self.n_simulations, 1)
         return float(row @ np.arange(-(n - 1), n, dtype=np.float64))
+
+
+# ---------------------------------------------------------------------------------------------- pace uncertainty
+@dataclass
+class PacePrior:
+    """One item in a scenario of RaceSimulator.run_priors: the standard deviation `sigma` (seconds a lap, in [0, 10]) of
+    the error that every simulation draws for the base pace of one driver (PacePrior.driver) or, as one shared draw, of
+    the drivers of a group such as a team (PacePrior.group).  A driver's drawn error is the sum of its own and its
+    group's."""
+    codes: tuple
+    sigma: float
+    shared: bool = False
+
+    @classmethod
+    def driver(cls, code, sigma) -> 'PacePrior':
+        return cls((str(code),), float(sigma), False)
+
+    @classmethod
+    def group(cls, codes, sigma) -> 'PacePrior':
+        return cls(tuple(str(c) for c in codes), float(sigma), True)
+
+    def c_struct(self, index) -> N.McgpPacePrior:
+        """mcgp_pace_prior with the driver indices from `index`; ValueError on an empty or repeating group or a sigma
+        outside [0, 10]."""
+        if not (math.isfinite(self.sigma) and 0.0 <= self.sigma <= N.MAX_PRIOR_SIGMA):
+            raise ValueError(f'{"+".join(self.codes)}: sigma must be finite and in [0, {N.MAX_PRIOR_SIGMA:g}], got {self.sigma!r}')
+        if not self.codes or len(set(self.codes)) != len(self.codes):
+            raise ValueError(f'{"+".join(self.codes)}: a group needs at least one driver, each once')
+        p = N.McgpPacePrior()
+        p.sigma = float(self.sigma)
+        if self.shared:
+            p.kind, p.driver = N.PRIOR_GROUP, 0
+            p.members = sum(1 << int(index[c]) for c in self.codes)
+        else:
+            p.kind, p.driver, p.members = N.PRIOR_DRIVER, int(index[self.codes[0]]), 0
+        return p
+
+
+@dataclass
+class PriorResult(StrategyResult):
+    """What RaceSimulator.run_priors returns: StrategyResult's counts and helpers, and
+      draws    [S][n][B][n]  [scenario][driver][bin of the driver's own drawn error][position - 1], B = len(edges) + 1;
+                             every [scenario][driver] block sums to N
+      edges    [B - 1]       the bins' edges, seconds a lap: bin b holds edges[b - 1] <= x < edges[b]
+      offsets  [S][N][n]     the drawn errors (return_offsets=True), else None"""
+    draws: np.ndarray | None = None
+    offsets: np.ndarray | None = None
+    edges: np.ndarray | None = None
+
+    def bin_bounds(self, b) -> tuple:
+        """(low, high) of bin `b` in seconds a lap: low <= x < high, -inf and inf at the ends."""
+        B = len(self.edges) + 1
+        if not 0 <= int(b) < B:
+            raise IndexError(f'bin {b} of {B}')
+        b = int(b)
+        return (float(self.edges[b - 1]) if b > 0 else -math.inf, float(self.edges[b]) if b < B - 1 else math.inf)
+
+    def _block(self, name, driver):
+        return np.asarray(self.draws[self._s(name), self._d(driver)], np.float64)
+
+    def draw_probabilities(self, name, driver) -> np.ndarray:
+        """[B]: the probability that `driver`'s own drawn error fell into each bin, in scenario `name`."""
+        return self._block(name, driver).sum(axis=1) / max(self.n_simulations, 1)
+
+    def position_probabilities_by_draw(self, name, driver) -> np.ndarray:
+        """[B][n]: `driver`'s finishing distribution given the bin of its own drawn error; NaN rows for empty bins."""
+        block = self._block(name, driver)
+        tot = block.sum(axis=1, keepdims=True)
+        return np.where(tot > 0, block / np.where(tot > 0, tot, 1.0), np.nan)
+
+    def win_probability_by_draw(self, name, driver) -> np.ndarray:
+        """[B]: P(win | bin of the own drawn error); NaN for empty bins."""
+        return self.position_probabilities_by_draw(name, driver)[:, 0]
+
+    def expected_points_by_draw(self, name, driver, points=DEFAULT_POINTS) -> np.ndarray:
+        """[B]: expected points given the bin of the own drawn error; NaN for empty bins."""
+        n = len(self.drivers)
+        table = np.zeros(n, np.float64)
+        m = min(n, len(points))
+        table[:m] = np.asarray(points[:m], np.float64)
+        return self.position_probabilities_by_draw(name, driver) @ table
 
 
 # ---------------------------------------------------------------------------------------------- combined scenarios

@@ -1,12 +1,12 @@
 // emu_generic.cpp -- DEBUGGING build of the generic kernel family's source for the host (not product code, not a
 // fallback: nothing in monte_carlo_gp_amd/ can reach it).  Compiles csrc/race_kernel.hip.h, resume.hip.h, trace.hip.h,
 // gaps.hip.h, pit_window.hip.h, conditions.hip.h, stints.hip.h, moves.hip.h, fastest.hip.h and scenario.hip.h (with strategy.hip.h,
-// penalties.hip.h, events.hip.h, paces.hip.h, weather.hip.h and grids.hip.h) with g++ through the stand-in <hip/hip_runtime.h> of this directory and
+// penalties.hip.h, events.hip.h, paces.hip.h, weather.hip.h, grids.hip.h and priors.hip.h) with g++ through the stand-in <hip/hip_runtime.h> of this directory and
 // calls the real __global__ functions: race_kernel, race_resume_kernel, race_trace_kernel, race_gaps_kernel<false / true>,
 // race_window_kernel<false / true>,
 // race_conditions_kernel<false / true>, conditions_count, race_stints_kernel<false / true>, race_moves_kernel<false /
-// true>, race_fastest_kernel, the thirteen instantiations of race_scenario_kernel, penalties_count, events_count,
-// paces_count, weather_count, grid_count.
+// true>, race_fastest_kernel, the fifteen instantiations of race_scenario_kernel, penalties_count, events_count,
+// paces_count, weather_count, grid_count, priors_count.
 //
 // Execution model: these kernels give one simulation to a lane and have no cross-lane operation, only
 // __syncthreads() between "load tables", "simulate" and "flush".  With blockDim = gridDim.x = 1 and n_batches = n_sims
@@ -20,16 +20,16 @@
 // threads (a one-thread block would visit a 256th of the data).  The tests derive the counts from the staging bytes and
 // records in numpy instead; the counting kernels are compared on the device.  conditions_count has no cross-lane
 // operation and strides by its block's size, so it does run here, as blocks of one thread; so do penalties_count, events_count
-// paces_count, weather_count and grid_count.
+// paces_count, weather_count, grid_count and priors_count.
 //
 // Shared text: the six analysis calls (emu_generic_trace, emu_gaps_run, emu_window_run, emu_conditions_run,
-// emu_stints_run, emu_moves_run) start with analysis_setup, the seven scenario calls are scenario_run with their rule sets.
+// emu_stints_run, emu_moves_run) start with analysis_setup, the eight scenario calls are scenario_run with their rule sets.
 //
 // Used by tests/test_generic_host_build.py (race, resume, trace, strategies) and by tests/test_<call>_host_build.py for
-// gaps, pit_window, conditions, stints, moves, fastest, penalties, events, paces, combined, weather and grids, each through its helper
+// gaps, pit_window, conditions, stints, moves, fastest, penalties, events, paces, combined, weather, grids and priors, each through its helper
 // tests/<call>_host_build.py (tests/kernel_host_build.py compiles this file); the stand-alone programs
-// tools/emu/sanitize_{penalties,events,paces,combined,bonus,weather,grids}_main.cpp are built with it for
-// tests/test_{penalties,events,paces,combined,fastest,weather,grids}_sanitize.py.
+// tools/emu/sanitize_{penalties,events,paces,combined,bonus,weather,grids,priors}_main.cpp are built with it for
+// tests/test_{penalties,events,paces,combined,fastest,weather,grids,priors}_sanitize.py.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -49,6 +49,7 @@
 #include "../../monte_carlo_gp_amd/csrc/pace_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/weather_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/grid_pack.h"
+#include "../../monte_carlo_gp_amd/csrc/prior_pack.h"
 #include "../../monte_carlo_gp_amd/csrc/scenario.hip.h"
 
 emu_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1}, gridDim{1, 1, 1};
@@ -127,6 +128,20 @@ int analysis_setup(const mcgp_config *cfg, const mcgp_drivers *drv, const double
 // The grid call (rules = kRuleGrid, from the grid only) hands its own inputs in `gr`: they are checked and packed by
 // grid_pack.h into the GridScenario table, which the kernel reads through its `pens` argument; car_stage gets the start
 // slots, and grid_count (grid_x x S x n blocks) adds them to `start` [S][n][n] and `gain` [S][n][2n - 1].
+// The priors call (rules = kRulePriors) hands its own inputs in `pr`: they are checked and packed by prior_pack.h into the
+// PriorScenario table, which the kernel reads through its `pens` argument; bin_stage [S][n_sims][n] bytes gets the bins
+// of the drawn offsets through `carried`, off_stage [S][n_sims][n] floats (NULL: not staged) the offsets through
+// `ev_stage`, and priors_count (grid_x x S x (1 + n) blocks) adds to `delta` and to `draws` [S][n][n_edges + 1][n].
+struct PriorArgs {
+    const uint32_t *prior_count;
+    const mcgp_pace_prior *priors;
+    uint32_t n_edges;
+    const double *edges;
+    uint8_t *bin_stage;
+    float *off_stage;
+    unsigned long long *draws;
+};
+
 struct GridArgs {
     const uint32_t *edit_count;
     const mcgp_grid_edit *edits;
@@ -147,7 +162,7 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
                  const mcgp_pace_offset *paces, uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist,
                  uint8_t *stage, uint32_t *ev_stage, uint16_t *car_stage, unsigned long long *delta, unsigned long long *fate,
                  unsigned long long *events_cnt, unsigned long long *carried, uint32_t grid_x, const char **err,
-                 const WeatherArgs *wx = nullptr, const GridArgs *gr = nullptr)
+                 const WeatherArgs *wx = nullptr, const GridArgs *gr = nullptr, const PriorArgs *pr = nullptr)
 {
     const bool pen = rules & mcgp::kRulePenalties, ev = rules & mcgp::kRuleEvents, pace = rules & mcgp::kRulePaces;
     static mcgp::KParams kp;
@@ -162,6 +177,8 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     if ((carried || (wx && wx->wrong)) && !car_stage) return fail(MCGP_E_BAD_ARG, "carried needs car_stage", err);
     if ((rules == mcgp::kRuleWeather) != (wx != nullptr)) return fail(MCGP_E_BAD_ARG, "weather needs its inputs", err);
     if ((rules == mcgp::kRuleGrid) != (gr != nullptr)) return fail(MCGP_E_BAD_ARG, "grid edits need their inputs", err);
+    if ((rules == mcgp::kRulePriors) != (pr != nullptr)) return fail(MCGP_E_BAD_ARG, "priors need their inputs", err);
+    if (pr && !pr->bin_stage) return fail(MCGP_E_BAD_ARG, "priors need bin_stage", err);
     if (gr && state) return fail(MCGP_E_BAD_ARG, "grid edits run from the grid only", err);
     if (gr && (gr->start || gr->gain) && !car_stage) return fail(MCGP_E_BAD_ARG, "start and gain need car_stage", err);
     const int L = cfg->total_laps;
@@ -183,7 +200,8 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     std::vector<mcgp::PaceLap> pace_laps;
     std::vector<double> lap_sec;
     std::vector<mcgp::GridScenario> grids;
-    uint64_t n_pens = 0, n_events = 0, n_paces = 0, n_changes = 0, n_edits = 0;
+    std::vector<mcgp::PriorScenario> priors;
+    uint64_t n_pens = 0, n_events = 0, n_paces = 0, n_changes = 0, n_edits = 0, n_priors = 0;
     std::string e = mcgp::pack_scenarios(n_scenarios, plan_count, plans, n, L, first_lap, resumed, &scen, &stop_laps);
     if (e.empty() && pen) e = mcgp::check_penalty_counts(n_scenarios, penalty_count, &n_pens);
     if (e.empty() && ev) e = mcgp::check_event_counts(n_scenarios, event_count, &n_events);
@@ -206,10 +224,20 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     if (e.empty() && gr) e = mcgp::check_edit_counts(n_scenarios, gr->edit_count, n, &n_edits);
     if (e.empty() && n_edits && !gr->edits) e = "edits is NULL";
     if (e.empty() && gr) e = mcgp::pack_grids(n_scenarios, gr->edit_count, gr->edits, n, &grids);
+    if (e.empty() && pr && !pr->prior_count) e = "prior_count is NULL";
+    if (e.empty() && pr) e = mcgp::check_prior_counts(n_scenarios, pr->prior_count, &n_priors);
+    if (e.empty() && pr) e = mcgp::check_prior_edges(pr->n_edges, pr->edges);
+    if (e.empty() && n_priors && !pr->priors) e = "priors is NULL";
+    if (e.empty() && pr) e = mcgp::pack_priors(n_scenarios, pr->prior_count, pr->priors, n, pr->n_edges, pr->edges, &priors);
     if (!e.empty()) return fail(MCGP_E_BAD_ARG, e, err);
     const auto kernel = mcgp::scenario_kernel(rules, resumed);
-    const mcgp::PenaltyScenario *pens_arg = pen ? pens.data()
-                                            : gr ? reinterpret_cast<const mcgp::PenaltyScenario *>(grids.data()) : nullptr;
+    const mcgp::PenaltyScenario *pens_arg = pen  ? pens.data()
+                                            : gr ? reinterpret_cast<const mcgp::PenaltyScenario *>(grids.data())
+                                            : pr ? reinterpret_cast<const mcgp::PenaltyScenario *>(priors.data()) : nullptr;
+    if (pr) {
+        ev_stage = reinterpret_cast<uint32_t *>(pr->off_stage);
+        car_stage = reinterpret_cast<uint16_t *>(pr->bin_stage);
+    }
     one_thread_block(n_scenarios);
     for (uint32_t si = 0; si < n_scenarios; ++si) {
         blockIdx.y = si;
@@ -220,7 +248,7 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
     }
     unsigned long long *ev_delta = pen ? nullptr : delta, *pace_delta = pen ? nullptr : delta;
     const uint32_t gz = carried ? 1u + n : 1u;
-    for (uint32_t z = 0; rules != 0u && z < gz; ++z)        // (the strategies call has no counting kernel that runs here)
+    for (uint32_t z = 0; rules != 0u && !pr && z < gz; ++z)  // (the strategies call has no counting kernel that runs here)
         for (uint32_t y = 0; y < n_scenarios; ++y)
             for (uint32_t x = 0; x < grid_x; ++x) {
                 blockIdx = {x, y, z};
@@ -250,6 +278,16 @@ int scenario_run(uint32_t rules, const mcgp_config *cfg, const mcgp_drivers *drv
                 for (uint32_t x = 0; x < grid_x; ++x) {
                     blockIdx = {x, y, z};
                     mcgp::grid_count(stage, car_stage, n_sims, n, gr->start, gr->gain);
+                }
+    }
+    if (pr && (delta || pr->draws)) {
+        const uint32_t layers = pr->draws ? 1u + n : 1u;
+        gridDim = {grid_x, n_scenarios, layers};
+        for (uint32_t z = 0; z < layers; ++z)
+            for (uint32_t y = 0; y < n_scenarios; ++y)
+                for (uint32_t x = 0; x < grid_x; ++x) {
+                    blockIdx = {x, y, z};
+                    mcgp::priors_count(stage, pr->bin_stage, n_sims, n, pr->n_edges + 1u, delta, pr->draws);
                 }
     }
     one_thread_block(1);
@@ -528,6 +566,22 @@ int emu_grid_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *
     return scenario_run(mcgp::kRuleGrid, cfg, drv, grid_probs, nullptr, n, n_scenarios, plan_count, plans, nullptr, nullptr,
                         nullptr, nullptr, nullptr, nullptr, n_sims, sim_offset, seed, hist, stage, nullptr, car_stage, nullptr,
                         nullptr, nullptr, nullptr, grid_x, err, nullptr, &gr);
+}
+
+// stage [S][n_sims][n] positions, bin_stage [S][n_sims][n] the bins of the drawn offsets, off_stage [S][n_sims][n] the
+// offsets (NULL: not staged); delta [S][n][2n - 1] and draws [S][n][n_edges + 1][n] (either may be NULL) are accumulated
+// into by priors_count.
+int emu_priors_run(const mcgp_config *cfg, const mcgp_drivers *drv, const double *grid_probs, const mcgp_race_state *state,
+                   uint32_t n, uint32_t n_scenarios, const uint32_t *plan_count, const mcgp_pit_plan *plans,
+                   const uint32_t *prior_count, const mcgp_pace_prior *priors, uint32_t n_edges, const double *edges,
+                   uint64_t n_sims, uint64_t sim_offset, uint64_t seed, unsigned long long *hist, uint8_t *stage,
+                   uint8_t *bin_stage, float *off_stage, unsigned long long *delta, unsigned long long *draws, uint32_t grid_x,
+                   const char **err)
+{
+    const PriorArgs pr = {prior_count, priors, n_edges, edges, bin_stage, off_stage, draws};
+    return scenario_run(mcgp::kRulePriors, cfg, drv, grid_probs, state, n, n_scenarios, plan_count, plans, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, n_sims, sim_offset, seed, hist, stage, nullptr, nullptr, delta,
+                        nullptr, nullptr, nullptr, grid_x, err, nullptr, nullptr, &pr);
 }
 
 }  // extern "C"
